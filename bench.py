@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark of the mgf hot path on MI355X (contract: see the task statement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" is one physics tick (mgf_demo/world.rs::World::step): complete_motion, integrate, broadphase, narrowphase,
 ContactConstraint::new for every contact, Solver::solve(10 iterations).
@@ -72,6 +72,8 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend of the rendezvous / barrier (and of --transport torch): nccl = RCCL; gloo = host-staged, "
                          "for validating the multi-rank flow on one GPU")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last tick to DIR/<name>.npy (f32 / f64, <= 64 MB in all): see dump_outputs")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -213,6 +215,49 @@ def _roofline(units, launches, kms, mode, what, window, workload="config2"):
             "avg_launch_us": round(kms * 1e3 / launches, 3), "avg_units_per_launch": round(units / launches, 1), "launches_timed": int(launches)}
 
 
+DUMP_BODY_ROWS = 262144        # --dump-outputs: body rows in all (shared among the job's worlds); beyond that a seeded sample
+DUMP_CONSTRAINT_ROWS = 131072  # constraint rows in all, likewise: at most ~35 MB per dump with the row indices
+DUMP_SEED = 0x6D6766
+DUMP_STAT_KEYS = ("n_bodies", "n_constraints", "n_terrain_constraints", "n_pair_candidates", "n_terrain_candidates", "n_ghost_constraints")
+
+
+def _dump_rows(n, cap, salt):
+    """The rows of an n-row output that go into a dump: all of them, or a fixed seeded sample of `cap` (ascending)."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng([DUMP_SEED, salt]).choice(n, cap, replace=False))
+
+
+def dump_outputs(path, worlds, last_stats, n_worlds_total=None):
+    """--dump-outputs: what the timed path computed in its last tick, as a caller of mgf_world_step_many / mgf_tiles_step receives it -
+    each world's state (x, q, v, omega, delta) and constraint list after that tick, and the tick's counts from StepStats (its timings
+    are not outputs) - written as `path`/<prefix><name>.npy in f32 (f64 for integers).  `worlds`: (prefix, world, tile id or None);
+    a tile's dump adds its bodies' tags.  Larger outputs are cut to a fixed seeded sample of rows; <prefix>body_rows /
+    <prefix>constraint_rows say which rows.  The scene, the warm-up and the timed ticks are seeded, so the same command line
+    dumps the same inputs' outputs on every run."""
+    os.makedirs(path, exist_ok=True)
+    share = max(1, n_worlds_total or len(worlds))
+    out = {}
+    for (prefix, w, tile), stats in zip(worlds, last_stats):
+        salt = 0 if tile is None else tile + 1
+        st = w.state()
+        rows = _dump_rows(len(st["x"]), DUMP_BODY_ROWS // share, salt)
+        out[prefix + "body_rows"] = rows.astype(np.float64)
+        for k in ("x", "q", "v", "omega", "delta"):
+            out[prefix + k] = st[k][rows]
+        if tile is not None:
+            out[prefix + "tags"] = np.asarray(w.tags())[rows].astype(np.float64)
+        cons = w.constraints()
+        rows = _dump_rows(len(cons), DUMP_CONSTRAINT_ROWS // share, salt)
+        out[prefix + "constraint_rows"] = rows.astype(np.float64)
+        for f in cons.dtype.names:
+            a = cons[f][rows]
+            out[prefix + "constraint_" + f] = a.astype(np.float64) if a.dtype.kind == "i" else a
+        out[prefix + "step_stats"] = np.array([float(stats[k]) if k in _keys(stats) else np.nan for k in DUMP_STAT_KEYS], np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def _standin_lib(args):
     """The library named to stand in for librccl (several ranks on ONE GPU over tests/fake_rccl: the multi-rank flow, never a
     measurement of xGMI), or None: --rccl-lib, or MGF_RCCL_LIB together with MGF_BENCH_ALLOW_RCCL_OVERRIDE=1."""
@@ -270,7 +315,11 @@ def bench_single_world(args, ctx, mgf_amd, scenes, configure, mode):
         el = time.perf_counter() - t0
         windows.append((el, _window_stats(per_tick, args.iters), _roofline_tick(per_tick, args.iters, el)))
         total += el
+        final = (w, per_tick) if args.dump_outputs else None  # (every window steps the same ticks from the same snapshot)
         del w
+    if final:
+        dump_outputs(args.dump_outputs, [("", final[0], None)], [final[1][args.steps - 1]])
+        del final
     windows.sort(key=lambda x: x[0])
     elapsed, (units, cons, _l, _k, _p), tick_roof = windows[len(windows) // 2]
     ru, rc, launches, kms, phase = _instrumented_replays(snap, configure, dt, args.iters, args.steps)
@@ -381,7 +430,11 @@ def bench_other_config(args, ctx, mgf_amd, scenes, configure, mode, kind, standa
         el = time.perf_counter() - t0
         windows.append((el, _window_stats(per_tick, args.iters), per_tick[len(per_tick) - 1], _roofline_tick(per_tick, args.iters, el)))
         total += el
+        final = (w, per_tick) if standalone and args.dump_outputs else None
         del w
+    if final:
+        dump_outputs(args.dump_outputs, [("", final[0], None)], [final[1][steps - 1]])
+        del final
     windows.sort(key=lambda x: x[0])
     elapsed, (units, cons, _l, _k, _p), last, tick_roof = windows[len(windows) // 2]
     _u, _c, launches, kms, phase = _instrumented_replays(snap, configure, dt, args.iters, steps)
@@ -520,6 +573,11 @@ def bench_tiles(args, ctx, mgf_amd, scenes, configure, mode, scene_kind, rank, w
     ticks = [step() for _ in range(args.steps)]
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        if transport == "native":
+            dump_outputs(args.dump_outputs, [(f"tile{first + k}_", w, first + k) for k, w in enumerate(worlds)], list(ticks[-1]), total_tiles)
+        else:
+            dump_outputs(args.dump_outputs, [(f"tile{first}_", tw.world, first)], [ticks[-1][0]], total_tiles)
     # what the neighbour exchanges cost in the timed window, per rank (mgf_tiles_counter; stream time between the events around every
     # exchange, the wait for the neighbouring rank included), and - outside the timed region - how deep bodies rest in each other
     # across tile faces against inside the tiles (the price of block-Jacobi across faces: DESIGN.md, tests/test_gpu_tiles_native.py)

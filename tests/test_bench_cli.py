@@ -48,3 +48,72 @@ def test_the_stand_in_transport_puts_the_ranks_on_one_device(monkeypatch, tmp_pa
 def test_a_mismatched_launcher_is_refused(monkeypatch):
     calls, code = _run_main(monkeypatch, ["--gpus", "4"], env={"WORLD_SIZE": "2", "RANK": "0"})
     assert not calls and "WORLD_SIZE=2" in str(code)
+
+
+class _FakeWorld:
+    """What dump_outputs reads of a world (mgf_amd.World's state / constraints / tags), filled with seeded numbers."""
+
+    def __init__(self, n_bodies, n_constraints, seed):
+        from mgf_amd._capi import CONSTRAINT_DTYPE
+        import numpy as np
+        rng = np.random.default_rng(seed)
+        self.st = {k: rng.standard_normal((n_bodies, d)).astype(np.float32) for k, d in (("x", 3), ("q", 4), ("v", 3), ("omega", 3), ("delta", 3))}
+        self.cons = np.zeros(n_constraints, CONSTRAINT_DTYPE)
+        self.cons["a"] = np.arange(n_constraints)
+        self.cons["normal"] = rng.standard_normal((n_constraints, 3))
+        self.cons["normal_impulse"] = rng.standard_normal(n_constraints)
+
+    def state(self):
+        return self.st
+
+    def constraints(self):
+        return self.cons
+
+    def tags(self):
+        import numpy as np
+        return np.arange(len(self.st["x"]), dtype=np.uint32)[::-1].copy()
+
+
+def _stats(n):
+    import bench
+    return {k: n + i for i, k in enumerate(bench.DUMP_STAT_KEYS)}
+
+
+def test_dump_outputs_writes_the_whole_of_a_small_world(tmp_path):
+    import numpy as np
+    import bench
+    w = _FakeWorld(100, 40, 1)
+    bench.dump_outputs(str(tmp_path), [("", w, None)], [_stats(100)])
+    got = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    for k in ("x", "q", "v", "omega", "delta"):
+        assert np.array_equal(got[k], w.st[k])
+    assert np.array_equal(got["body_rows"], np.arange(100)) and np.array_equal(got["constraint_rows"], np.arange(40))
+    assert np.array_equal(got["constraint_a"], np.arange(40)) and got["constraint_a"].dtype == np.float64
+    assert np.array_equal(got["constraint_normal"], w.cons["normal"]) and np.array_equal(got["constraint_normal_impulse"], w.cons["normal_impulse"])
+    assert list(got["step_stats"]) == [100 + i for i in range(len(bench.DUMP_STAT_KEYS))]
+    assert "tags" not in got
+
+
+def test_dump_outputs_samples_large_outputs_the_same_way_every_time_within_64_mb(tmp_path):
+    import numpy as np
+    import bench
+    worlds = [(f"tile{t}_", _FakeWorld(40000, 30000, t), t) for t in range(8)]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), worlds, [_stats(40000)] * 8)
+    a = {p.name: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    b = {p.name: np.load(p) for p in (tmp_path / "b").glob("*.npy")}
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    assert sum(p.stat().st_size for p in (tmp_path / "a").glob("*.npy")) <= 64 << 20
+    rows = a["tile3_body_rows.npy"].astype(np.int64)
+    assert len(rows) == bench.DUMP_BODY_ROWS // 8 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["tile3_x.npy"], worlds[3][1].st["x"][rows]) and np.array_equal(a["tile3_tags.npy"], worlds[3][1].tags()[rows])
+    assert len(a["tile3_constraint_rows.npy"]) == bench.DUMP_CONSTRAINT_ROWS // 8
+    assert not np.array_equal(rows, a["tile4_body_rows.npy"])   # (each tile its own sample)
+
+
+def test_dump_outputs_of_the_largest_single_world_stays_within_64_mb(tmp_path):
+    import bench
+    w = _FakeWorld(2 * bench.DUMP_BODY_ROWS, 3 * bench.DUMP_CONSTRAINT_ROWS, 2)
+    bench.dump_outputs(str(tmp_path), [("", w, None)], [_stats(1)])
+    assert sum(p.stat().st_size for p in tmp_path.glob("*.npy")) <= 64 << 20
