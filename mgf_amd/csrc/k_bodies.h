@@ -125,8 +125,9 @@ struct CellSort { const SceneBounds* grid; int shift; float min_frac; uint32_t* 
 // With `limit` set (the host: 1.5 x the largest half extent of the bodies that were NOT wide in the last tick) k_integrate keeps the
 // bodies above it out of the scene bounds and rmax and lists them (fat box, slot, order id; at most `cap`: more is a failed tick, run
 // again without the list); the grid's pair search never accepts a listed body as a partner (its leaf record carries no order id:
-// scatter_leaf) and k_pair_wide finds its partners-to-be from ITS side, by one launch over the few of them.  The accepted set is the
-// reference's (the same predicate on the same boxes, bvh.rs:283-310), whatever the limit.
+// scatter_leaf) and k_pair_wide finds its partners-to-be from ITS side, by one launch over the few of them: the ordinary bodies in the
+// cells its fat box reaches, the other listed bodies one by one (a wide partner's centre may lie far outside that reach).  The accepted
+// set is the reference's (the same predicate on the same boxes, bvh.rs:283-310), whatever the limit.
 constexpr uint32_t kWideCap = 64;
 struct WideSpec { float limit[3]; float4* list; uint32_t* count; const uint32_t* ext; };
 __device__ __forceinline__ bool is_wide(const float* limit, float4 fr) { return fr.x > limit[0] || fr.y > limit[1] || fr.z > limit[2]; }

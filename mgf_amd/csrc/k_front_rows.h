@@ -523,11 +523,16 @@ __global__ __launch_bounds__(kCoopBlock) void k_pair_grid_n(Bodies B, uint32_t n
 // ---- the partners-to-be of the WIDE bodies (WideSpec, k_bodies.h) ------------------------------------------------------------------
 // The grid's pair search finds pair (i, j) - j the body of the smaller order id - from i's side: i's tight box against the fat boxes of
 // the bodies in the cells around it, as far as the largest fat half extent of the scene reaches.  A wide j is kept out of that reach and
-// out of the partners (its leaf record carries no order id); here it looks for its i's itself: a workgroup per listed body, the cells its
-// FAT box can reach (a body whose tight box meets fat_j has its own fat box's centre within fat_j grown by rmax), the reference's
-// acceptance test (bvh.rs:297, world.rs:266) on every record there with a larger order id.  An accepted pair goes where the pair search
-// would have put it - behind the entries of i's row (the order inside a row never mattered) - through the pair test first where the rows
-// hold contacts.  One launch of kWideCap workgroups behind the pair search, whose rows and counts it appends to.
+// out of the partners (its leaf record carries no order id); here it looks for its i's itself: a workgroup per listed body, the
+// reference's acceptance test (bvh.rs:297, world.rs:266) on every candidate with a larger order id.  The candidates are of two kinds:
+// - the bodies that are NOT listed: in the cells its FAT box can reach (such a body's half extent is at most rmax, so if its tight box
+//   meets fat_j its centre lies within fat_j grown by rmax);
+// - the other LISTED bodies, each tested directly (at most kWideCap of them): their half extents are above rmax by definition, so a
+//   wide i whose tight box meets fat_j may sit with its centre far outside that region - two runaways flying at each other.
+//   The cell walk skips them (their leaf records carry the wide mark), so no pair is accepted twice.
+// An accepted pair goes where the pair search would have put it - behind the entries of i's row (the order inside a row never mattered) -
+// through the pair test first where the rows hold contacts.  One launch of kWideCap workgroups behind the pair search, whose rows and
+// counts it appends to.
 struct PairWide {
   const float4* list; const uint32_t* count;
   Lbvh T; const SceneBounds* sb; const SceneBounds* box; float pad_abs, min_frac;
@@ -557,26 +562,37 @@ __global__ __launch_bounds__(kBlock) void k_pair_wide(Bodies B, PairWide A) {
   Comp Bc; Bc.kind = KIND_SPHERE; Bc.p = mk3(0, 0, 0); Bc.d = mk3(0, 0, 0); Bc.r = 0.0f;
   if (A.contacts) Bc = load_comp_moving(B, j, &vB);
   uint32_t accepted = 0;
+  auto accept = [&](uint32_t i) {  // i's tight box met fat_j: counted, through the pair test where the rows hold contacts, appended to i's row
+    ++accepted;
+    if (A.contacts) {
+      V3 vA;
+      const Comp Ac = load_comp_moving(B, i, &vA);
+      LocalContact lc;
+      if (!comp_pair_local(Ac, vA, Bc, vB, &lc)) return;
+    }
+    const uint32_t pos = atomicAdd(&A.p_cnt[i], 1u);
+    if (pos < (uint32_t)kRowCap) A.rows_p[(size_t)i * kRowCap + pos] = j;
+    else atomicOr(A.overflow, 1u);
+  };
+  if (threadIdx.x < nw) {  // the other listed bodies: a lane each
+    const uint32_t i = f2u(A.list[2 * threadIdx.x].w);
+    if (i != j && f2u(A.list[2 * threadIdx.x + 1].w) > oj) {  // world.rs:266
+      Box q; q.c = xyz(B.tb_c[i]); q.r = xyz(B.tb_r[i]);
+      if (box_overlaps(q, fat)) accept(i);  // bvh.rs:297
+    }
+  }
   for (uint32_t idx = threadIdx.x; idx < (uint32_t)ncell; idx += (uint32_t)kBlock) {
     const uint32_t cz = idx % d[2], t = idx / d[2], cy = t % d[1], cx = t / d[1];
     const uint32_t code = (expand10((ca[0] + cx) << (10u - nb[0])) << 2) | (expand10((ca[1] + cy) << (10u - nb[1])) << 1) | expand10((ca[2] + cz) << (10u - nb[2]));
     const uint32_t cell = code >> shift;
     for (uint32_t p = A.T.cell_lo[cell], p1 = A.T.cell_lo[cell + 1]; p < p1; ++p) {
+      if (f2u(A.T.leaves[p].r.w) == 0xFFFFFFFFu) continue;  // a listed body (scatter_leaf's mark): tested directly above
       const uint32_t i = A.T.sidx[p];
       if (i == j || order_id(A.T.ext, i) <= oj) continue;  // world.rs:266: partners have the smaller order id (j is owned: listed by k_integrate)
       const float4 tc = A.T.ltb[2 * (size_t)p], tr = A.T.ltb[2 * (size_t)p + 1];
       Box q; q.c = xyz(tc); q.r = xyz(tr);
       if (!box_overlaps(q, fat)) continue;  // the reference's own acceptance test (bvh.rs:297): i's tight box, j's fat box
-      ++accepted;
-      if (A.contacts) {
-        V3 vA;
-        const Comp Ac = load_comp_moving(B, i, &vA);
-        LocalContact lc;
-        if (!comp_pair_local(Ac, vA, Bc, vB, &lc)) continue;
-      }
-      const uint32_t pos = atomicAdd(&A.p_cnt[i], 1u);
-      if (pos < (uint32_t)kRowCap) A.rows_p[(size_t)i * kRowCap + pos] = j;
-      else atomicOr(A.overflow, 1u);
+      accept(i);
     }
   }
   if (accepted) atomicAdd(&s_acc, accepted);
