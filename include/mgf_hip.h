@@ -271,6 +271,34 @@ MGF_API mgf_status mgf_world_read_state(mgf_world* w, mgf_vec3* x, mgf_quat* q, 
 MGF_API mgf_status mgf_world_write_state(mgf_world* w, const mgf_vec3* x, const mgf_quat* q, const mgf_vec3* v,
                                          const mgf_vec3* omega, const mgf_vec3* delta, int64_t n);
 MGF_API mgf_status mgf_world_read_colliders(mgf_world* w, mgf_moving_component* out, int64_t cap); /* colliders() :256 */
+/* ---- queries against the world between ticks (NOT in the reference: its World is the demo's, so the definition is this
+ * build's; DESIGN.md "world queries").  A query sees each owned body's collider at its current pose as mgf_world_read_colliders
+ * returns it (the Moving displacement is not swept) - for a body of several components each of its parts in world coordinates -
+ * the terrain's faces and each obstacle as Intersects<Compound> (compound.rs:309-332) at its pose.  Ghost bodies are never
+ * reported; the tick's state is not touched (a step after a query is bit-identical to one without it). ----
+ * Ray cast: per particle (a Ray has dt = INFINITY, a Segment dt = 1) the closest hit of Intersects<shape> (collision.rs:169-373;
+ * compound.rs:150 for a component): the smallest t, ties to the target first in the order bodies (ascending caller index, a body's
+ * parts in order), terrain faces (ascending index), obstacles (in the order added).  inter is bit-identical to that single test.
+ * kind: MGF_HIT_NONE (-1, the other fields zero), MGF_HIT_BODY (index = the caller's body index), MGF_HIT_TERRAIN (index = face),
+ * MGF_HIT_OBSTACLE (index = obstacle); part = the component within a body of several components or within an obstacle (else 0).
+ * A particle with d = 0 hits nothing (the single tests divide by |d|^2 there: every sphere would answer at t = 0). */
+#define MGF_HIT_NONE (-1)
+#define MGF_HIT_BODY 0
+#define MGF_HIT_TERRAIN 1
+#define MGF_HIT_OBSTACLE 2
+#define MGF_QUERY_BODIES 1
+#define MGF_QUERY_TERRAIN 2
+#define MGF_QUERY_OBSTACLES 4
+#define MGF_QUERY_ALL 7
+typedef struct mgf_ray_hit { int32_t kind; int32_t index; int32_t part; mgf_intersection inter; } mgf_ray_hit;
+/* ignore_body: NULL, or n caller body indices (-1: none) that particle i skips; kinds_mask: MGF_QUERY_* bits (0 is refused). */
+MGF_API mgf_status mgf_world_raycast_many(mgf_world* w, const mgf_particle* parts, int64_t n, const int32_t* ignore_body,
+                                          int32_t kinds_mask, mgf_ray_hit* out);
+/* Box overlap: per mgf_aabb every owned body whose tight bound BoundedBy<AABB> (bounds.rs:170-190; for a body of several components
+ * the union of its parts' bounds) passes Overlaps<AABB> (collision.rs:22), in ascending caller index: out_bodies[out_offsets[q] ..
+ * out_offsets[q+1]).  As mgf_bvh_query_many: out_offsets and *total are always filled; MGF_ERR_CAPACITY if *total > cap. */
+MGF_API mgf_status mgf_world_overlap_aabb_many(mgf_world* w, const mgf_aabb* boxes, int64_t n, uint64_t* out_offsets /* n+1 */,
+                                               uint32_t* out_bodies, int64_t cap, int64_t* total);
 /* The Solver's constraint list of the last tick, in insertion order. */
 MGF_API mgf_status mgf_world_read_constraints(mgf_world* w, mgf_constraint* out, int64_t cap, int64_t* count);
 /* Solver::add_constraint in bulk + solve on the resident RigidBodyVec (solver.rs:66-78):
@@ -472,7 +500,8 @@ MGF_API mgf_status mgf_world_set_option(mgf_world* w, const char* key, int64_t v
  * "wide_bodies" (listed in the last tick), "wide_ticks", "wide_overflows" (ticks run again because more bodies were wide than the list holds),
  * "flow6_skipped" (plans that declined the block-local solver because the last launch that did not fit says it still would not), "solver_abort_fallbacks" (Solver::solve calls whose persistent launch gave up and that were solved again from
  * the pre-launch state: Solver::solve has no failure mode, solver.rs:72-78), "device_ptrs_out" (1 while mgf_world_device_ptr's pointers pin
- * the store to the caller's order)}. */
+ * the store to the caller's order), "query_large_bodies" / "query_cells" (the last world query's large-body list and grid),
+ * "query_build_ns" / "query_run_ns" (HIP-event times of its grid build and of its query pass)}. */
 MGF_API mgf_status mgf_world_counter(const mgf_world* w, const char* name, int64_t* out);
 /* Raw device pointers of resident state for zero-copy exchange (multi-GPU halo): name in
  * {"x","q","solver_rec","delta"} (the pub fields `x`, `q` of RigidBodyVec physics.rs:142-154 and what ConstrainedSet::get returns,

@@ -104,6 +104,11 @@ CONSTRAINT_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("n_contacts", "<i4"),
 assert COMPONENT_DTYPE.itemsize == C.sizeof(Component) == 32
 assert MOVING_DTYPE.itemsize == C.sizeof(MovingComponent) == 44
 assert CONSTRAINT_DTYPE.itemsize == 96
+# mgf_ray_hit: kind (HIT_*), index, part, inter = (p, t)
+RAY_HIT_DTYPE = np.dtype([("kind", "<i4"), ("index", "<i4"), ("part", "<i4"), ("p", "<f4", 3), ("t", "<f4")])
+assert RAY_HIT_DTYPE.itemsize == 28
+HIT_NONE, HIT_BODY, HIT_TERRAIN, HIT_OBSTACLE = -1, 0, 1, 2
+QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -120,7 +125,7 @@ SYMBOLS = [
     "mgf_world_new", "mgf_world_free", "mgf_world_set_terrain", "mgf_world_add_bodies", "mgf_world_add_compound_bodies", "mgf_world_len",
     "mgf_world_step", "mgf_world_step_many", "mgf_world_build_constraints", "mgf_world_solve", "mgf_world_complete_motion",
     "mgf_world_integrate", "mgf_world_get", "mgf_world_set", "mgf_world_read_state", "mgf_world_write_state",
-    "mgf_world_read_colliders", "mgf_world_read_constraints", "mgf_world_set_constraints", "mgf_world_set_option",
+    "mgf_world_read_colliders", "mgf_world_raycast_many", "mgf_world_overlap_aabb_many", "mgf_world_read_constraints", "mgf_world_set_constraints", "mgf_world_set_option",
     "mgf_world_device_ptr",
     "mgf_world_release_device_ptrs",
     "mgf_world_begin_tick", "mgf_world_collide", "mgf_world_select_boundary", "mgf_world_export_bodies",
@@ -217,6 +222,8 @@ def load_library():
         "mgf_world_read_state": (i32, [vp, vp, vp, vp, vp, vp, i64]),
         "mgf_world_write_state": (i32, [vp, vp, vp, vp, vp, vp, i64]),
         "mgf_world_read_colliders": (i32, [vp, vp, i64]),
+        "mgf_world_raycast_many": (i32, [vp, vp, i64, vp, C.c_int32, vp]),
+        "mgf_world_overlap_aabb_many": (i32, [vp, vp, i64, vp, vp, i64, P(i64)]),
         "mgf_world_read_constraints": (i32, [vp, vp, i64, P(i64)]),
         "mgf_world_set_constraints": (i32, [vp, vp, i64]),
         "mgf_world_set_option": (i32, [vp, C.c_char_p, i64]),
@@ -944,6 +951,51 @@ class World:
         out = np.zeros(len(self), MOVING_DTYPE)
         _check(load_library().mgf_world_read_colliders(self._h, out.ctypes.data, len(out)))
         return out
+
+    def raycast(self, p, d, dt=float("inf"), ignore=None, kinds=QUERY_ALL):
+        """Closest hit of each particle (rows of p, d; dt = inf: a Ray, 1: a Segment from p to p + d) against the bodies, the terrain
+        and the obstacles (mgf_world_raycast_many): a RAY_HIT_DTYPE array, kind HIT_NONE where nothing is hit.  ignore: None or a
+        caller body index per particle (-1: none); kinds: QUERY_* bits."""
+        p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(np.broadcast_to(np.asarray(d, np.float32), p.shape))
+        n = len(p)
+        parts = np.empty((n, 7), np.float32)
+        parts[:, 0:3] = p
+        parts[:, 3:6] = d
+        parts[:, 6] = np.broadcast_to(np.asarray(dt, np.float32), (n,))
+        ign = None
+        if ignore is not None:
+            ign = np.ascontiguousarray(np.broadcast_to(np.asarray(ignore, np.int32), (n,)))
+        out = np.zeros(n, RAY_HIT_DTYPE)
+        _check(load_library().mgf_world_raycast_many(self._h, parts.ctypes.data, n, ign.ctypes.data if ign is not None else None,
+                                                     int(kinds), out.ctypes.data))
+        return out
+
+    def overlap_aabb(self, lo, hi):
+        """The bodies whose tight box overlaps each box [lo, hi] (rows; mgf_world_overlap_aabb_many): (offsets[n + 1], bodies) in CSR
+        form, each list in ascending caller index.  The box handed over is the mgf_aabb c = (hi + lo) / 2, r = (hi - lo) / 2 in f32."""
+        lo = np.asarray(lo, np.float32).reshape(-1, 3)
+        hi = np.asarray(hi, np.float32).reshape(-1, 3)
+        boxes = np.empty((len(lo), 6), np.float32)
+        boxes[:, 0:3] = (hi + lo) / np.float32(2)
+        boxes[:, 3:6] = (hi - lo) / np.float32(2)
+        return self.overlap_boxes(boxes)
+
+    def overlap_boxes(self, boxes, cap=None):
+        """overlap_aabb for mgf_aabb rows (c.xyz, r.xyz) as given; cap None sizes the output from a first call's count."""
+        boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+        n = len(boxes)
+        off = np.zeros(n + 1, np.uint64)
+        total = C.c_int64()
+        lib = load_library()
+        if cap is None:
+            st = lib.mgf_world_overlap_aabb_many(self._h, boxes.ctypes.data, n, off.ctypes.data, None, 0, C.byref(total))
+            if st not in (0, ERR_CAPACITY):
+                _check(st)
+            cap = total.value
+        vals = np.zeros(max(int(cap), 1), np.uint32)
+        _check(lib.mgf_world_overlap_aabb_many(self._h, boxes.ctypes.data, n, off.ctypes.data, vals.ctypes.data, int(cap), C.byref(total)))
+        return off.astype(np.int64), vals[:total.value].copy()
 
     def constraints(self):
         n = C.c_int64()

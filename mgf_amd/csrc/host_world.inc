@@ -72,6 +72,12 @@ struct mgf_world {
   uint32_t wide_hold = 0, wide_last = 0;
   uint64_t n_wide_ticks = 0, n_wide_overflows = 0;
   DBuf<float4> wide_list;
+  // mgf_world_raycast_many / mgf_world_overlap_aabb_many (host_query.inc): the query's own grid and lists - nothing of the tick's is read or written
+  DBuf<float4> q_bc, q_br;
+  DBuf<uint32_t> q_cnt, q_start, q_items, q_large, q_misc, q_off, q_vals;
+  DBuf<ParticleIn> q_parts; DBuf<int32_t> q_ign, q_hits; DBuf<float> q_boxes;
+  uint32_t q_last_large = 0, q_last_cells = 0;
+  float q_last_build_ms = 0.0f, q_last_run_ms = 0.0f;
   int64_t opt_side_stream = 1;       // (r06) the terrain kernels of the list-free front end on the context's second stream, beside the pair search (0: one stream)
   int64_t opt_front_rows_check = 0;  // tests: the faces k_terrain_near's cheap reject (comp_tri_far) drops go through the reference's tests as well; a contact among them is an internal error
   bool front_rows_off = false;       // ... switched off for good: a body accepted more faces than k_terrain_near lists
@@ -562,6 +568,10 @@ extern "C" mgf_status mgf_world_counter(const mgf_world* w, const char* name, in
   if (!strcmp(name, "flow5_fallbacks")) { *out = (int64_t)w->n_flow5_fallbacks; return MGF_OK; }
   if (!strcmp(name, "flow6_fallbacks")) { *out = (int64_t)w->n_flow6_fallbacks; return MGF_OK; }
   if (!strcmp(name, "wide_bodies")) { *out = (int64_t)w->wide_last; return MGF_OK; }
+  if (!strcmp(name, "query_large_bodies")) { *out = (int64_t)w->q_last_large; return MGF_OK; }
+  if (!strcmp(name, "query_cells")) { *out = (int64_t)w->q_last_cells; return MGF_OK; }
+  if (!strcmp(name, "query_build_ns")) { *out = (int64_t)std::llround((double)w->q_last_build_ms * 1e6); return MGF_OK; }
+  if (!strcmp(name, "query_run_ns")) { *out = (int64_t)std::llround((double)w->q_last_run_ms * 1e6); return MGF_OK; }
   if (!strcmp(name, "wide_ticks")) { *out = (int64_t)w->n_wide_ticks; return MGF_OK; }
   if (!strcmp(name, "wide_overflows")) { *out = (int64_t)w->n_wide_overflows; return MGF_OK; }
   if (!strcmp(name, "flow6_skipped")) { *out = (int64_t)w->n_flow6_skipped; return MGF_OK; }

@@ -73,6 +73,8 @@
 //                      tile's tick changes, kept for the retry of a tick in which a persistent launch gave up
 //   k_compound_* / k_bvh_raytrace / k_intersections_batch
 //                      Compound (compound.rs:230-352), BVH::raytrace and Intersects (bvh.rs:345-369, collision.rs:169-373)
+//   k_query_* (k_query.h) ray casts and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid of
+//                      the bodies' current tight boxes built per call (never the tick's lists)
 //
 // All f32 arithmetic follows the reference's operation order; the TU is built with
 // -ffp-contract=off.
@@ -80,3 +82,4 @@
 // The kernels live in the k_*.h parts, each including the one before it:
 //   k_bodies.h -> k_broadphase.h -> k_contacts.h -> k_front_rows.h -> k_links.h -> k_solver_flow.h -> k_tiles.h -> k_api.h
 #include "k_api.h"
+#include "k_query.h"  // the world queries between ticks (k_query_*), beside the tick
