@@ -501,7 +501,9 @@ MGF_API mgf_status mgf_world_set_option(mgf_world* w, const char* key, int64_t v
  * "flow6_skipped" (plans that declined the block-local solver because the last launch that did not fit says it still would not), "solver_abort_fallbacks" (Solver::solve calls whose persistent launch gave up and that were solved again from
  * the pre-launch state: Solver::solve has no failure mode, solver.rs:72-78), "device_ptrs_out" (1 while mgf_world_device_ptr's pointers pin
  * the store to the caller's order), "query_large_bodies" / "query_cells" (the last world query's large-body list and grid),
- * "query_build_ns" / "query_run_ns" (HIP-event times of its grid build and of its query pass)}. */
+ * "query_build_ns" / "query_run_ns" (HIP-event times of its grid build and of its query pass), "pair_brick_ticks", "front_rows_ticks",
+ * "fused_contacts_ticks", "early_cells_ticks" (ticks whose collide phase settled on k_pair_brick, on the list-free front end, on
+ * k_contacts_spheres without candidate lists, on cells worked out inside k_integrate)}. */
 MGF_API mgf_status mgf_world_counter(const mgf_world* w, const char* name, int64_t* out);
 /* Raw device pointers of resident state for zero-copy exchange (multi-GPU halo): name in
  * {"x","q","solver_rec","delta"} (the pub fields `x`, `q` of RigidBodyVec physics.rs:142-154 and what ConstrainedSet::get returns,

@@ -430,6 +430,8 @@ static mgf_status collide_enqueue(mgf_world* w, float dt, bool solver_follows = 
                           (!terrain_any || (terrain_grid && !w->has_compound) || (!terrain_grid && rows_done && w->opt_fused_contacts));
   w->ts->fused = fused || front_rows;  // (the accepted partners are counted by the pair search: the read-back takes the statistic along)
   w->ts->front_rows = front_rows;
+  w->ts->contacts_fused = contacts_fused;
+  w->ts->cells_early = cells_done;
   if (front_rows) w->ts->brick = false;  // (k_pair_grid_n is the pair search of such a world)
   const bool tc_job = (contacts_fused || (front_rows && !terrain_grid)) && terrain_any;
   bool forked = false;
@@ -867,6 +869,7 @@ static mgf_status collide_process(mgf_world* w, bool* retry) {
     *retry = true;
   }
   if (*retry) { w->n_cap_retries++; return MGF_OK; }
+  w->n_path_ticks[0] += w->ts->brick; w->n_path_ticks[1] += w->ts->front_rows; w->n_path_ticks[2] += w->ts->contacts_fused; w->n_path_ticks[3] += w->ts->cells_early;
   if (w->opt_wide_list) {  // the wide bodies' limit for the ticks to come (WideSpec, k_bodies.h)
     if (w->wide_tick_on) {  // (the read-back's rmax is the largest half extent of the bodies that were NOT wide)
       w->n_wide_ticks++;

@@ -71,6 +71,10 @@ struct mgf_world {
   float shape_rmax[3] = {0, 0, 0};   // the largest fat half extent the bodies had AT REST when they were added (the reference a world starts from)
   uint32_t wide_hold = 0, wide_last = 0;
   uint64_t n_wide_ticks = 0, n_wide_overflows = 0;
+  // ticks whose collide phase settled on each fast path (counted by collide_process; read-only, for tests that must prove a path ran):
+  // [0] k_pair_brick, [1] the list-free front end (k_front_rows.h), [2] k_contacts_spheres' rows -> records without candidate lists,
+  // [3] cells and ranks worked out by k_integrate over the last tick's box
+  uint64_t n_path_ticks[4] = {0, 0, 0, 0};
   DBuf<float4> wide_list;
   // mgf_world_raycast_many / mgf_world_overlap_aabb_many (host_query.inc): the query's own grid and lists - nothing of the tick's is read or written
   DBuf<float4> q_bc, q_br;
@@ -264,6 +268,8 @@ struct mgf_world {
     bool brick = false;               // the tick ran k_pair_brick
     bool fused = false;               // the tick ran the fused sphere filter (the read-back includes the candidate statistic)
     bool front_rows = false;          // the tick ran the list-free front end of a world that is not spheres only (k_front_rows.h)
+    bool contacts_fused = false;      // ... k_contacts_spheres: rows to constraint records without candidate lists
+    bool cells_early = false;         // ... took its cells and ranks from k_integrate (over the last tick's box)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // the side stream's start and end inside the tick (no timing: created on first use)
     uint32_t* pin = nullptr;
     uint32_t* pin_dev = nullptr;      // the same memory as the device sees it (k_publish)
@@ -572,6 +578,10 @@ extern "C" mgf_status mgf_world_counter(const mgf_world* w, const char* name, in
   if (!strcmp(name, "query_cells")) { *out = (int64_t)w->q_last_cells; return MGF_OK; }
   if (!strcmp(name, "query_build_ns")) { *out = (int64_t)std::llround((double)w->q_last_build_ms * 1e6); return MGF_OK; }
   if (!strcmp(name, "query_run_ns")) { *out = (int64_t)std::llround((double)w->q_last_run_ms * 1e6); return MGF_OK; }
+  if (!strcmp(name, "pair_brick_ticks")) { *out = (int64_t)w->n_path_ticks[0]; return MGF_OK; }
+  if (!strcmp(name, "front_rows_ticks")) { *out = (int64_t)w->n_path_ticks[1]; return MGF_OK; }
+  if (!strcmp(name, "fused_contacts_ticks")) { *out = (int64_t)w->n_path_ticks[2]; return MGF_OK; }
+  if (!strcmp(name, "early_cells_ticks")) { *out = (int64_t)w->n_path_ticks[3]; return MGF_OK; }
   if (!strcmp(name, "wide_ticks")) { *out = (int64_t)w->n_wide_ticks; return MGF_OK; }
   if (!strcmp(name, "wide_overflows")) { *out = (int64_t)w->n_wide_overflows; return MGF_OK; }
   if (!strcmp(name, "flow6_skipped")) { *out = (int64_t)w->n_flow6_skipped; return MGF_OK; }
