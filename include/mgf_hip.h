@@ -294,6 +294,29 @@ typedef struct mgf_ray_hit { int32_t kind; int32_t index; int32_t part; mgf_inte
 /* ignore_body: NULL, or n caller body indices (-1: none) that particle i skips; kinds_mask: MGF_QUERY_* bits (0 is refused). */
 MGF_API mgf_status mgf_world_raycast_many(mgf_world* w, const mgf_particle* parts, int64_t n, const int32_t* ignore_body,
                                           int32_t kinds_mask, mgf_ray_hit* out);
+/* Sweep: per cast (a sphere, tag 0, or a capsule, tag 1, in world coordinates, swept by delta) the earliest contact of the target's
+ * continuous test, the target the receiver and the cast Moving::sweep(shape, delta):
+ *   body       every component of an owned body's collider at its current pose (as mgf_world_read_colliders and, for a body of several
+ *              components, its world parts give it; the collider's own delta is not applied): Contacts<Moving<Sphere | Capsule>> of that
+ *              sphere or capsule (collision.rs:1089-1356; Sphere vs Moving<Capsule> through commute_contacts!, :1143);
+ *   terrain    each face, the mesh's position added: Contacts<Moving<_>> for Poly (collision.rs:610-1000), up to two contacts for a
+ *              capsule, in the order it emits them;
+ *   obstacle   Compound::contacts(&Moving::sweep(shape, delta)) at the obstacle's pose (compound.rs:334-351); part = the component.
+ * Among all contacts of the selected kinds the one with the least (t, kind, index, part, order emitted within that one target) is
+ * reported; every part of ignore_body[i] is skipped; ghosts are never reported.  contact is bit-identical to the single test's: a on
+ * the target, b on the cast, both at time t, n as the target's test emits it.  No contact: kind MGF_HIT_NONE, every other field zero.
+ *   delta = 0 is a valid cast: the single tests report a cast that starts overlapping a target at t = 0 (except sphere on sphere with
+ *   equal centres, which reports nothing, collision.rs:1097-1100).
+ *   The face test of a capsule is not local, and its answers stand as the definition's: its axis test (collision.rs:698-719) measures
+ *   along the unit axis and steps along the whole one, so it answers at t = 0 for a capsule up to max(1, |d|) from a face; with
+ *   delta = 0 its fallback (:901-1060) casts rays of direction 0, which can answer at t = 0 at any face.
+ *   A contact whose t is not finite is not a candidate: a capsule whose length overflows f32 (d finite, |d| = inf) makes the face test
+ *   emit t = NaN beside finite contacts (collision.rs:693-1086).
+ * ignore_body: NULL, or n caller body indices (-1: none); kinds_mask: MGF_QUERY_* bits (0 is refused); a tag other than 0 or 1 is
+ * refused (MGF_ERR_INVALID). */
+typedef struct mgf_sweep_hit { int32_t kind; int32_t index; int32_t part; mgf_contact contact; } mgf_sweep_hit;   /* 52 bytes */
+MGF_API mgf_status mgf_world_sweep_many(mgf_world* w, const mgf_moving_component* casts, int64_t n, const int32_t* ignore_body,
+                                        int32_t kinds_mask, mgf_sweep_hit* out);
 /* Box overlap: per mgf_aabb every owned body whose tight bound BoundedBy<AABB> (bounds.rs:170-190; for a body of several components
  * the union of its parts' bounds) passes Overlaps<AABB> (collision.rs:22), in ascending caller index: out_bodies[out_offsets[q] ..
  * out_offsets[q+1]).  As mgf_bvh_query_many: out_offsets and *total are always filled; MGF_ERR_CAPACITY if *total > cap. */

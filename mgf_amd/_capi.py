@@ -107,6 +107,9 @@ assert CONSTRAINT_DTYPE.itemsize == 96
 # mgf_ray_hit: kind (HIT_*), index, part, inter = (p, t)
 RAY_HIT_DTYPE = np.dtype([("kind", "<i4"), ("index", "<i4"), ("part", "<i4"), ("p", "<f4", 3), ("t", "<f4")])
 assert RAY_HIT_DTYPE.itemsize == 28
+# mgf_sweep_hit: kind (HIT_*), index, part, contact = (a, b, n, t)
+SWEEP_HIT_DTYPE = np.dtype([("kind", "<i4"), ("index", "<i4"), ("part", "<i4"), ("a", "<f4", 3), ("b", "<f4", 3), ("n", "<f4", 3), ("t", "<f4")])
+assert SWEEP_HIT_DTYPE.itemsize == 52
 HIT_NONE, HIT_BODY, HIT_TERRAIN, HIT_OBSTACLE = -1, 0, 1, 2
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
@@ -125,7 +128,7 @@ SYMBOLS = [
     "mgf_world_new", "mgf_world_free", "mgf_world_set_terrain", "mgf_world_add_bodies", "mgf_world_add_compound_bodies", "mgf_world_len",
     "mgf_world_step", "mgf_world_step_many", "mgf_world_build_constraints", "mgf_world_solve", "mgf_world_complete_motion",
     "mgf_world_integrate", "mgf_world_get", "mgf_world_set", "mgf_world_read_state", "mgf_world_write_state",
-    "mgf_world_read_colliders", "mgf_world_raycast_many", "mgf_world_overlap_aabb_many", "mgf_world_read_constraints", "mgf_world_set_constraints", "mgf_world_set_option",
+    "mgf_world_read_colliders", "mgf_world_raycast_many", "mgf_world_sweep_many", "mgf_world_overlap_aabb_many", "mgf_world_read_constraints", "mgf_world_set_constraints", "mgf_world_set_option",
     "mgf_world_device_ptr",
     "mgf_world_release_device_ptrs",
     "mgf_world_begin_tick", "mgf_world_collide", "mgf_world_select_boundary", "mgf_world_export_bodies",
@@ -223,6 +226,7 @@ def load_library():
         "mgf_world_write_state": (i32, [vp, vp, vp, vp, vp, vp, i64]),
         "mgf_world_read_colliders": (i32, [vp, vp, i64]),
         "mgf_world_raycast_many": (i32, [vp, vp, i64, vp, C.c_int32, vp]),
+        "mgf_world_sweep_many": (i32, [vp, vp, i64, vp, C.c_int32, vp]),
         "mgf_world_overlap_aabb_many": (i32, [vp, vp, i64, vp, vp, i64, P(i64)]),
         "mgf_world_read_constraints": (i32, [vp, vp, i64, P(i64)]),
         "mgf_world_set_constraints": (i32, [vp, vp, i64]),
@@ -969,6 +973,31 @@ class World:
         out = np.zeros(n, RAY_HIT_DTYPE)
         _check(load_library().mgf_world_raycast_many(self._h, parts.ctypes.data, n, ign.ctypes.data if ign is not None else None,
                                                      int(kinds), out.ctypes.data))
+        return out
+
+    def sweep(self, comps, delta=None, ignore=None, kinds=QUERY_ALL):
+        """Earliest contact of each swept sphere or capsule against the bodies, the terrain and the obstacles (mgf_world_sweep_many): a
+        SWEEP_HIT_DTYPE array, kind HIT_NONE where nothing is met.  comps: COMPONENT_DTYPE rows swept by delta (rows, or one vector for
+        all), or a MOVING_DTYPE array that carries its own delta (then delta is None); ignore: None or a caller body index per cast
+        (-1: none); kinds: QUERY_* bits."""
+        comps = np.asarray(comps)
+        if comps.dtype == MOVING_DTYPE:
+            if delta is not None:
+                raise ValueError("a MOVING_DTYPE array carries its own delta")
+            casts = np.ascontiguousarray(comps.reshape(-1))
+        else:
+            comps = np.asarray(comps, COMPONENT_DTYPE).reshape(-1)
+            casts = np.zeros(len(comps), MOVING_DTYPE)
+            for k in ("tag", "p", "d", "r"):
+                casts[k] = comps[k]
+            casts["delta"] = np.broadcast_to(np.asarray(0.0 if delta is None else delta, np.float32), (len(comps), 3))
+        n = len(casts)
+        ign = None
+        if ignore is not None:
+            ign = np.ascontiguousarray(np.broadcast_to(np.asarray(ignore, np.int32), (n,)))
+        out = np.zeros(n, SWEEP_HIT_DTYPE)
+        _check(load_library().mgf_world_sweep_many(self._h, casts.ctypes.data, n, ign.ctypes.data if ign is not None else None,
+                                                   int(kinds), out.ctypes.data))
         return out
 
     def overlap_aabb(self, lo, hi):

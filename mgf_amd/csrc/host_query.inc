@@ -1,4 +1,4 @@
-// Queries against the world between ticks: mgf_world_raycast_many, mgf_world_overlap_aabb_many (k_query.h).
+// Queries against the world between ticks: mgf_world_raycast_many, mgf_world_sweep_many, mgf_world_overlap_aabb_many (k_query.h).
 // Part of the single translation unit mgf_hip.hip (included there, in order); not compiled on its own.
 //
 // Each call builds its own uniform grid over the bodies' CURRENT tight boxes (two synchronisations: the bounds, the cell total).
@@ -119,6 +119,56 @@ extern "C" mgf_status mgf_world_raycast_many(mgf_world* w, const mgf_particle* p
   LAUNCH_CHECK();
   MGF_TRY(tm.mark(2, s));
   MGF_TRY(d2h(ctx, reinterpret_cast<int32_t*>(out), w->q_hits.p, 7 * (size_t)n));
+  MGF_TRY(tm.read(w));
+  uint32_t err = 0;
+  MGF_TRY(d2h(ctx, &err, w->q_misc.p + 7, 1));
+  if (err) return fail(MGF_ERR_CAPACITY, "BVH traversal stack overflow in a world query");
+  return MGF_OK;
+}
+
+extern "C" mgf_status mgf_world_sweep_many(mgf_world* w, const mgf_moving_component* casts, int64_t n, const int32_t* ignore_body,
+                                           int32_t kinds_mask, mgf_sweep_hit* out) {
+  if (!w || n < 0 || (n && (!casts || !out))) return fail(MGF_ERR_INVALID, "NULL argument or negative count");
+  if (kinds_mask <= 0 || (kinds_mask & ~MGF_QUERY_ALL)) return fail(MGF_ERR_INVALID, "kinds_mask must be a non-empty set of MGF_QUERY_* bits");
+  static_assert(sizeof(mgf_sweep_hit) == 52 && sizeof(mgf_moving_component) == sizeof(MovingIn), "k_query_sweep writes mgf_sweep_hit as 13 words");
+  for (int64_t i = 0; i < n; ++i)
+    if (casts[i].shape.tag != 0 && casts[i].shape.tag != 1) return fail(MGF_ERR_INVALID, "a cast's shape tag must be 0 (sphere) or 1 (capsule)");
+  MGF_TRY(ctx_bind(w->ctx));
+  if (n == 0) return MGF_OK;
+  if (n > (int64_t)INT32_MAX) return fail(MGF_ERR_INVALID, "too many casts in one call");
+  mgf_ctx* ctx = w->ctx;
+  hipStream_t s = ctx->stream;
+  QueryTimer tm;
+  MGF_TRY(tm.init());
+  MGF_TRY(w->q_casts.ensure((size_t)n, s));
+  MGF_TRY(h2d(ctx, w->q_casts.p, reinterpret_cast<const MovingIn*>(casts), (size_t)n));
+  if (ignore_body) { MGF_TRY(w->q_ign.ensure((size_t)n, s)); MGF_TRY(h2d(ctx, w->q_ign.p, ignore_body, (size_t)n)); }
+  MGF_TRY(w->q_hits.ensure(13 * (size_t)n, s));
+  MGF_TRY(tm.mark(0, s));
+  QueryGrid G;
+  if (kinds_mask & MGF_QUERY_BODIES) {
+    MGF_TRY(query_grid(w, &G));
+  } else {
+    MGF_TRY(w->q_misc.ensure(16, s));
+    MGF_HIP_TRY(hipMemsetAsync(w->q_misc.p, 0, 64, s));
+    G.dims[0] = G.dims[1] = G.dims[2] = 0; G.n_large = w->q_misc.p + 6; G.large = nullptr; G.start = G.items = nullptr;
+    G.h = G.inv_h = 1.0f; G.margin = 0.0f; G.lo[0] = G.lo[1] = G.lo[2] = 0.0f;
+  }
+  MGF_TRY(tm.mark(1, s));
+  QueryTargets T;
+  T.B = w->bodies(); T.ext = w->ext_ptr(); T.qb_c = w->q_bc.p; T.qb_r = w->q_br.p;
+  T.err = w->q_misc.p + 7;
+  T.M.n_nodes = 0;
+  if ((kinds_mask & MGF_QUERY_TERRAIN) && w->terrain) { MGF_TRY(w->terrain->sync()); T.M = w->terrain->dev(T.err); }
+  T.obs = w->d_obs.p; T.n_obs = (kinds_mask & MGF_QUERY_OBSTACLES) ? (uint32_t)w->obstacles.size() : 0u;
+  k_query_sweep<<<nblk(n), kBlock, 0, s>>>(G, T, w->q_casts.p, n, ignore_body ? w->q_ign.p : nullptr, kinds_mask, w->q_hits.p);
+  LAUNCH_CHECK();
+  if ((kinds_mask & MGF_QUERY_BODIES) && G.dims[0] > 0) {
+    k_query_sweep_cells<<<nblk(n), kBlock, 0, s>>>(G, T, w->q_casts.p, n, ignore_body ? w->q_ign.p : nullptr, w->q_hits.p);
+    LAUNCH_CHECK();
+  }
+  MGF_TRY(tm.mark(2, s));
+  MGF_TRY(d2h(ctx, reinterpret_cast<int32_t*>(out), w->q_hits.p, 13 * (size_t)n));
   MGF_TRY(tm.read(w));
   uint32_t err = 0;
   MGF_TRY(d2h(ctx, &err, w->q_misc.p + 7, 1));

@@ -80,6 +80,7 @@ struct mgf_world {
   DBuf<float4> q_bc, q_br;
   DBuf<uint32_t> q_cnt, q_start, q_items, q_large, q_misc, q_off, q_vals;
   DBuf<ParticleIn> q_parts; DBuf<int32_t> q_ign, q_hits; DBuf<float> q_boxes;
+  DBuf<MovingIn> q_casts;
   uint32_t q_last_large = 0, q_last_cells = 0;
   float q_last_build_ms = 0.0f, q_last_run_ms = 0.0f;
   int64_t opt_side_stream = 1;       // (r06) the terrain kernels of the list-free front end on the context's second stream, beside the pair search (0: one stream)

@@ -221,6 +221,36 @@ __device__ inline ShapeIn comp_shape(const Comp& k) {
   else { st3(s.v, k.p); st3(s.v + 3, k.d); s.v[6] = k.r; }
   return s;
 }
+// Contacts<Moving<Sphere | Capsule>> of a sphere or capsule receiver (collision.rs:1089-1356; Sphere vs Moving<Capsule> through
+// commute_contacts!): what contacts_dispatch(self, false, 0, m, true, v) answers for these four pairs, without its other cases
+__device__ __forceinline__ bool comp_mcomp(const Comp& self, const Comp& m, V3 v, Contact* out) {
+  if (self.kind == KIND_SPHERE) {
+    const Sphere s = mks(self.p, self.r);
+    return m.kind == KIND_SPHERE ? sphere_msphere(s, mks(m.p, m.r), v, out) : sphere_mcapsule(s, mkcap(m.p, m.d, m.r), v, out);
+  }
+  const Capsule c = mkcap(self.p, self.d, self.r);
+  return m.kind == KIND_SPHERE ? capsule_msphere(c, mks(m.p, m.r), v, out) : capsule_mcapsule(c, mkcap(m.p, m.d, m.r), v, out);
+}
+// Compound::contacts(&Moving::sweep(R, vel)) compound.rs:334-352: its BVH queried with R's swept bounds turned into the compound's
+// frame, then per component met Moving<R>.contacts(&component) (:1368-1382: the component sweeps at -vel against R, the result shifted
+// by vel * t), negated - a on the compound.  emit(component, contact) in the reference's order (k_compound_contacts, k_query_sweep).
+template <class F>
+__device__ __forceinline__ void compound_contacts_walk(const CompoundDev& D, const Comp& R, V3 vel, F&& emit) {
+  const V3 disp = ld3(D.disp);
+  const Quat rot = mkq(D.rot[0], mk3(D.rot[1], D.rot[2], D.rot[3]));
+  const Quat conj = mkq(rot.s, -rot.v);
+  Box rb = box_rotate(swept_bounds(R, vel), conj);
+  rb.c = rotate(conj, rb.c + -disp) + disp;
+  terrain_traverse(D.tree, rb, [&](uint32_t ci) {
+    Comp shape = comp_rotate_about(to_comp(D.comps[ci]), rot, mk3(0.0f, 0.0f, 0.0f));
+    shape.p = shape.p + disp;
+    Contact c;
+    if (comp_mcomp(R, shape, -vel, &c)) {
+      const V3 d = vel * c.t;
+      emit(ci, neg(mkc(c.a + d, c.b + d, c.n, c.t)));
+    }
+  });
+}
 // Contacts<RHS> for Compound compound.rs:334-352, RHS = Moving<Sphere | Capsule>: one thread per rhs, contacts in BVH
 // query order (count pass / fill pass).
 template <bool FILL>
@@ -229,22 +259,11 @@ __global__ __launch_bounds__(kBlock) void k_compound_contacts(CompoundDev D, con
   int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   Comp R; R.kind = rhs[i].tag; R.p = ld3(rhs[i].p); R.d = ld3(rhs[i].d); R.r = rhs[i].r;
-  V3 vel = ld3(rhs[i].delta), disp = ld3(D.disp);
-  Quat rot = mkq(D.rot[0], mk3(D.rot[1], D.rot[2], D.rot[3]));
-  Quat conj = mkq(rot.s, -rot.v);
-  Box rb = box_rotate(swept_bounds(R, vel), conj);
-  rb.c = rotate(conj, rb.c + -disp) + disp;
-  ShapeIn rs = comp_shape(R);
+  const V3 vel = ld3(rhs[i].delta);
   uint32_t m = 0, base = FILL ? off[i] : 0;
-  terrain_traverse(D.tree, rb, [&](uint32_t ci) {
-    Comp shape = comp_rotate_about(to_comp(D.comps[ci]), rot, mk3(0.0f, 0.0f, 0.0f));
-    shape.p = shape.p + disp;
-    Contact c[2];
-    int k = contacts_dispatch(rs, true, vel, comp_shape(shape), false, mk3(0, 0, 0), c);  // Moving<Recv>.contacts(&Arg) :1368-1382
-    for (int e = 0; e < k; ++e) {
-      if (FILL) out[base + m] = to_out(neg(c[e]));
-      ++m;
-    }
+  compound_contacts_walk(D, R, vel, [&](uint32_t, const Contact& c) {
+    if (FILL) out[base + m] = to_out(c);
+    ++m;
   });
   if (!FILL) cnt[i] = m;
 }

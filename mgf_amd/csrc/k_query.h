@@ -9,6 +9,9 @@
 //   k_query_cells<F>   the counting sort: every body in each cell its (margin-padded) box touches, at most 2x2x2; count, scan, fill
 //   k_query_ray        a lane per particle: the large bodies, the obstacles (Intersects<Compound>, compound.rs:309-332), the
 //                      terrain's BVH, then the grid's cells in DDA order until the next cell starts beyond the best t so far
+//   k_query_sweep      a lane per swept sphere or capsule: the large bodies, the obstacles (Compound::contacts' own walk), the terrain's
+//                      BVH with the padded swept box; then k_query_sweep_cells walks the grid: a DDA along the path of the cast's
+//                      centre, visiting the block of cells its half extent can reach, until the next cell starts beyond the best t
 //   k_query_overlap<F> a lane per box: the cells it touches (a body is tested in the first cell it shares with the box), the
 //                      large bodies; count, scan, fill, then k_query_sort puts each list into the caller's order
 // Which of the targets a hit belongs to never depends on the visiting order: hits are ranked by (t, kind, index, part).
@@ -319,6 +322,245 @@ __global__ __launch_bounds__(kBlock) void k_query_ray(QueryGrid G, QueryTargets 
   } else {
     o[0] = MGF_HIT_NONE; o[1] = 0; o[2] = 0; o[3] = 0; o[4] = 0; o[5] = 0; o[6] = 0;
   }
+}
+
+// ---- swept spheres and capsules (mgf_world_sweep_many) ----------------------------------------------------------------------
+// The earliest contact of a cast: (t, kind, index, part, order emitted within the target) ascending, whatever order the targets are
+// visited in; a contact whose t is not finite is not a candidate (include/mgf_hip.h)
+struct SweepBest {
+  // the key as two words: t (ordered-int, -0 taken as +0), then kind (2 bits) | index (32) | part (19) | order (1); sub = ~0: no contact
+  int tk = 0x7FFFFFFF;
+  uint64_t sub = ~0ull;
+  Contact c;
+  __device__ __forceinline__ bool have() const { return sub != ~0ull; }
+  __device__ __forceinline__ void offer(const Contact& k, int kd, uint32_t idx, uint32_t pt, uint32_t ord) {
+    if (!(fabsf(k.t) < kInf)) return;
+    const int t = f_ord(k.t + 0.0f);
+    const uint64_t u = ((uint64_t)kd << 52) | ((uint64_t)idx << 20) | ((uint64_t)(pt & 0x7FFFFu) << 1) | (uint64_t)(ord & 1u);
+    if (t < tk || (t == tk && u < sub)) { tk = t; sub = u; c = k; }
+  }
+  __device__ __forceinline__ int kind() const { return (int)(sub >> 52); }
+  __device__ __forceinline__ uint32_t index() const { return (uint32_t)(sub >> 20); }
+  __device__ __forceinline__ uint32_t part() const { return (uint32_t)(sub >> 1) & 0x7FFFFu; }
+};
+
+// The cast: its shape at t = 0, its sweep, and the bounding sphere (centre cc, radius cr) that the cheap reject moves along the sweep
+struct SweepCast {
+  Comp s;
+  V3 v;
+  V3 cc;
+  float cr;
+  float pad;  // the reject's absolute pad: the grid's margin, a millimetre and the rounding of the path's arithmetic
+};
+
+// May a target component, through its bounding sphere, touch the cast's bounding sphere somewhere along the sweep?  Every contact the
+// single tests report is a touching of the two shapes at some t in [0, 1]; the radii carry 1 % for the tests' own rounding.
+__device__ __forceinline__ bool q_sweep_far(const Comp& A, const SweepCast& K) {
+  const bool sa = A.kind == KIND_SPHERE;
+  const V3 ma = sa ? A.p : A.p + A.d * 0.5f;
+  const float ra = sa ? A.r : A.r + 0.5f * mag(A.d);
+  const V3 w = ma - K.cc;
+  const float vv = dot(K.v, K.v);
+  const float s = vv > 0.0f ? fminf(fmaxf(dot(w, K.v) / vv, 0.0f), 1.0f) : 0.0f;
+  const V3 e = w - K.v * s;
+  const float lim = (ra + K.cr) * 1.01f + K.pad;
+  return dot(e, e) > lim * lim;  // (NaN: not far - the test decides)
+}
+
+// every component of slot s: the body's Contacts<Moving<cast>> (collision.rs:1089-1356)
+__device__ __forceinline__ void q_sweep_body(const QueryTargets& T, uint32_t s, const SweepCast& K, int32_t ign, SweepBest& best) {
+  const uint32_t e = T.ext ? T.ext[s] : s;
+  if ((int32_t)e == ign) return;
+  const Bodies& B = T.B;
+  const uint32_t pc = B.pcount ? B.pcount[s] : 0u;
+  const uint32_t np = pc ? pc : 1u;
+  for (uint32_t k = 0; k < np; ++k) {
+    float4 a, b;
+    if (pc) world_part(B, s, k, pc, a, b);
+    else { a = B.col0[s]; b = B.col1[s]; }
+    Comp t; t.kind = (int)f2u(b.w); t.p = xyz(a); t.d = xyz(b); t.r = a.w;
+    if (q_sweep_far(t, K)) continue;
+    Contact c;
+    if (comp_mcomp(t, K.s, K.v, &c)) best.offer(c, MGF_HIT_BODY, e, k, 0u);
+  }
+}
+
+// Contacts<Moving<_>> for Poly (collision.rs:610-1000) of every face the walk of the mesh BVH with the cast's padded swept box reaches.
+// A capsule's face test reaches further than the capsule: its axis test (:698-719) measures the start's distance to the plane along the
+// unit axis but steps along the whole one, so it answers at t = 0 for a capsule up to max(1, |d|) from the face - the box grows by that.
+// A capsule that does not move tests every face: the fallback (:901-1060) then casts rays of direction 0, whose tests divide by
+// |delta|^2 and can answer at t = 0 at a face nowhere near the capsule.
+__device__ __forceinline__ void q_sweep_terrain(const TerrainDev& M, const SweepCast& K, uint32_t* err, SweepBest& best) {
+  const bool every = K.s.kind != KIND_SPHERE && mag2(K.v) == 0.0f;
+  const float reach = K.s.kind == KIND_SPHERE ? 0.0f : fmaxf(1.0f, mag(K.s.d));
+  const V3 mx = mk3(M.x[0], M.x[1], M.x[2]);
+  Box q = swept_bounds(K.s, K.v);
+  q.c = q.c + -mx;  // the tree's boxes are in the mesh's frame
+  uint32_t stack[kStack];
+  int sp = 0;
+  stack[sp++] = M.root;
+  while (sp > 0) {
+    const uint32_t top = stack[--sp];
+    const float4* raw = reinterpret_cast<const float4*>(&M.nodes[top]);
+    const float4 n0 = raw[0], n1 = raw[1];
+    const V3 c = xyz(n0), r = xyz(n1);
+    const float pad = 1e-5f * (q_maxabs(c) + q_maxabs(r) + q_maxabs(mx) + q_maxabs(q.c) + q_maxabs(q.r)) + 1e-6f + reach;
+    if (!every && !(fabsf(c.x - q.c.x) <= r.x + q.r.x + pad && fabsf(c.y - q.c.y) <= r.y + q.r.y + pad && fabsf(c.z - q.c.z) <= r.z + q.r.z + pad)) continue;
+    const uint32_t w0 = f2u(n0.w), w1 = f2u(n1.w);
+    if (w0 & 0x80000000u) {
+      const uint32_t f = w0 & 0x7FFFFFFFu;
+      const uint4 fi = M.faces[f];
+      const Triangle tri = mkt(xyz(M.verts[fi.x]) + mx, xyz(M.verts[fi.y]) + mx, xyz(M.verts[fi.z]) + mx);
+      Contact c0, c1;
+      if (K.s.kind == KIND_SPHERE) {
+        if (tri_msphere(tri, mks(K.s.p, K.s.r), K.v, &c0)) best.offer(c0, MGF_HIT_TERRAIN, f, 0u, 0u);
+      } else {
+        const int m = tri_mcapsule(tri, mkcap(K.s.p, K.s.d, K.s.r), K.v, c0, c1);
+        if (m > 0) best.offer(c0, MGF_HIT_TERRAIN, f, 0u, 0u);
+        if (m > 1) best.offer(c1, MGF_HIT_TERRAIN, f, 0u, 1u);
+      }
+    } else if (sp + 2 <= kStack) { stack[sp++] = w0; stack[sp++] = w1; }
+    else *err = 1u;
+  }
+}
+
+// the grid cells [lo, hi] (clamped to the grid)
+__device__ __forceinline__ void q_sweep_cells(const QueryGrid& G, const QueryTargets& T, const int lo[3], const int hi[3], const SweepCast& K, int32_t ign,
+                                              SweepBest& best) {
+  for (int z = max(lo[2], 0); z <= min(hi[2], G.dims[2] - 1); ++z)
+    for (int y = max(lo[1], 0); y <= min(hi[1], G.dims[1] - 1); ++y)
+      for (int x = max(lo[0], 0); x <= min(hi[0], G.dims[0] - 1); ++x) {
+        const uint32_t cell = (uint32_t)x + (uint32_t)G.dims[0] * ((uint32_t)y + (uint32_t)G.dims[1] * (uint32_t)z);
+        for (uint32_t k = G.start[cell], ke = G.start[cell + 1]; k < ke; ++k) q_sweep_body(T, G.items[k], K, ign, best);
+      }
+}
+
+__device__ __forceinline__ SweepCast q_sweep_cast(const MovingIn& m, const QueryGrid& G) {
+  SweepCast K;
+  K.s.kind = m.tag; K.s.p = ld3(m.p); K.s.d = m.tag == KIND_SPHERE ? mk3(0.0f, 0.0f, 0.0f) : ld3(m.d); K.s.r = m.r;
+  K.v = ld3(m.delta);
+  const Box sb = comp_bounds(K.s);
+  K.cc = sb.c; K.cr = sb.r.x;
+  K.pad = G.margin + 1e-3f + 1e-5f * (q_maxabs(K.cc) + q_maxabs(K.v));
+  return K;
+}
+__device__ __forceinline__ void q_sweep_store(int32_t* o, const SweepBest& best) {
+  if (best.have()) {
+    o[0] = best.kind(); o[1] = (int32_t)best.index(); o[2] = (int32_t)best.part();
+    const Contact& c = best.c;
+    o[3] = (int32_t)f2u(c.a.x); o[4] = (int32_t)f2u(c.a.y); o[5] = (int32_t)f2u(c.a.z);
+    o[6] = (int32_t)f2u(c.b.x); o[7] = (int32_t)f2u(c.b.y); o[8] = (int32_t)f2u(c.b.z);
+    o[9] = (int32_t)f2u(c.n.x); o[10] = (int32_t)f2u(c.n.y); o[11] = (int32_t)f2u(c.n.z);
+    o[12] = (int32_t)f2u(c.t);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 13; ++k) o[k] = k == 0 ? MGF_HIT_NONE : 0;
+  }
+}
+
+// A lane per cast, in two kernels (one held the walks of all four kinds of target live at once and spilled scalar registers inside its
+// nested cell loops): k_query_sweep tests the large bodies, the obstacles and the terrain and writes its best contact; k_query_sweep_cells
+// takes that contact up again and walks the grid.  The ranking does not depend on the visiting order, so the split changes no answer.
+__global__ __launch_bounds__(kBlock) void k_query_sweep(QueryGrid G, QueryTargets T, const MovingIn* casts, int64_t n, const int32_t* ignore, int32_t mask,
+                                                        int32_t* out /* 13 words per cast: mgf_sweep_hit */) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const SweepCast K = q_sweep_cast(casts[i], G);
+  const int32_t ign = ignore ? ignore[i] : -1;
+  SweepBest best;
+  if (mask & MGF_QUERY_BODIES) {
+    const uint32_t nl = *G.n_large;
+    for (uint32_t k = 0; k < nl; ++k) q_sweep_body(T, G.large[k], K, ign, best);
+  }
+  if (mask & MGF_QUERY_OBSTACLES)
+    for (uint32_t o = 0; o < T.n_obs; ++o)
+      compound_contacts_walk(T.obs[o], K.s, K.v, [&](uint32_t ci, const Contact& c) { best.offer(c, MGF_HIT_OBSTACLE, o, ci, 0u); });
+  if ((mask & MGF_QUERY_TERRAIN) && T.M.n_nodes) q_sweep_terrain(T.M, K, T.err, best);
+  q_sweep_store(out + 13 * i, best);
+}
+
+// The grid walk is a DDA along the path of the centre of the cast's box: at each cell c it covers the block c +- R, R = the cells the
+// box's half extent (plus the margin) can reach from c, so a body the cast touches at t is in the block of the cell the centre is in at t.
+// The first cell visits its whole block, each step after it only the slab of cells the step brings into the block (the walk moves one
+// cell along one axis at a time: no cell twice).  The walk stops once the next cell starts beyond the best t by a cell's worth of time,
+// as the ray walk does.  (Launched only when bodies are asked for and the grid has cells.)
+__global__ __launch_bounds__(kBlock) void k_query_sweep_cells(QueryGrid G, QueryTargets T, const MovingIn* casts, int64_t n, const int32_t* ignore,
+                                                              int32_t* out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const SweepCast K = q_sweep_cast(casts[i], G);
+  const int32_t ign = ignore ? ignore[i] : -1;
+  int32_t* o = out + 13 * i;
+  SweepBest best;
+  if (o[0] != MGF_HIT_NONE)  // k_query_sweep's answer (its order within a target does not matter here: the grid offers bodies only)
+    best.offer(mkc(mk3(u2f(o[3]), u2f(o[4]), u2f(o[5])), mk3(u2f(o[6]), u2f(o[7]), u2f(o[8])), mk3(u2f(o[9]), u2f(o[10]), u2f(o[11])), u2f(o[12])), o[0],
+               (uint32_t)o[1], (uint32_t)o[2], 0u);
+  const Box sb = comp_bounds(K.s);
+  const float dmax = q_maxabs(K.v);
+  // the block's half extent in cells; a cast whose own rounding (far from the grid, a long sweep) may exceed the margin takes one more.
+  // (a block as wide as the grid along an axis covers that axis wherever the centre is: the walk ignores the axis)
+  const bool fat = 4e-7f * (q_maxabs(K.cc) + dmax) > 0.25f * G.margin;
+  int R[3];
+  bool whole[3];
+  float elo[3], ehi[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    R[k] = (int)fminf(ceilf((at(sb.r, k) + G.margin) * G.inv_h) + (fat ? 1.0f : 0.0f), (float)G.dims[k]);  // (NaN: the whole grid)
+    whole[k] = R[k] >= G.dims[k];
+    elo[k] = G.lo[k] - (float)(R[k] + 1) * G.h;
+    ehi[k] = G.lo[k] + (float)(G.dims[k] + R[k] + 1) * G.h;
+  }
+  // clip the centre's path to the grid's box grown by the block (beyond it a block holds no cell of the grid)
+  float t0 = 0.0f, t1 = 1.0f;
+  bool miss = false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float pk = at(K.cc, k), dk = at(K.v, k);
+    if (whole[k]) continue;
+    if (dk == 0.0f) {
+      if (!(pk >= elo[k] && pk <= ehi[k])) miss = true;
+    } else {
+      float ta = (elo[k] - pk) / dk, tb = (ehi[k] - pk) / dk;
+      if (ta > tb) { const float s = ta; ta = tb; tb = s; }
+      t0 = fmaxf(t0, ta); t1 = fminf(t1, tb);
+    }
+  }
+  if (!miss && t0 <= t1) {
+    const V3 e = K.cc + K.v * t0;
+    int c[3], step[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float f = floorf((at(e, k) - G.lo[k]) * G.inv_h);
+      c[k] = whole[k] ? 0 : (int)fminf(fmaxf(f, (float)(-R[k] - 1)), (float)(G.dims[k] + R[k]));  // (NaN: the low end)
+      step[k] = whole[k] ? 0 : (at(K.v, k) > 0.0f ? 1 : (at(K.v, k) < 0.0f ? -1 : 0));
+    }
+    const float tpad = dmax > 0.0f ? G.h / dmax : kInf;
+    int lo[3], hi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { lo[k] = c[k] - R[k]; hi[k] = c[k] + R[k]; }
+    q_sweep_cells(G, T, lo, hi, K, ign, best);
+    const int max_steps = G.dims[0] + G.dims[1] + G.dims[2] + 2 * (R[0] + R[1] + R[2]) + 6;
+    for (int s = 0; s < max_steps; ++s) {
+      float tn = kInf;
+      int ax = -1;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        if (step[k] == 0) continue;
+        const float face = G.lo[k] + (float)(c[k] + (step[k] > 0 ? 1 : 0)) * G.h;
+        const float tk = (face - at(K.cc, k)) / at(K.v, k);
+        if (ax < 0 || tk < tn) { tn = tk; ax = k; }
+      }
+      if (ax < 0 || !(tn <= t1 + tpad)) break;
+      if (best.have() && tn > best.c.t + tpad) break;
+      c[ax] += step[ax];
+      if (c[ax] < -R[ax] - 1 || c[ax] > G.dims[ax] + R[ax]) break;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { lo[k] = c[k] - R[k]; hi[k] = c[k] + R[k]; }
+      lo[ax] = hi[ax] = c[ax] + step[ax] * R[ax];  // the slab the step brings in
+      q_sweep_cells(G, T, lo, hi, K, ign, best);
+    }
+  }
+  q_sweep_store(o, best);
 }
 
 // Overlaps<AABB> (collision.rs:22) of each query box with every body's tight box; a body filed in several cells is tested in the
