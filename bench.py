@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark of the mgf hot path on MI355X (contract: see the task statement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one physics tick (mgf_demo/world.rs::World::step): complete_motion, integrate, broadphase, narrowphase,
 ContactConstraint::new for every contact, Solver::solve(10 iterations).
@@ -20,6 +20,12 @@ Workloads (BASELINE.json `configs`):
           `--gpus 1 --scene config4` runs the 8 tiles on one GPU.
           `--scene config5 --gpus N` (N > 1), or `--scene config5_tiles` at any N: BASELINE config 5 as BASELINE.json states it - 65 536
           bodies of a sphere and a capsule each, cut into 8 x-slab tiles of 8 lattice columns, rank r owning 8 / N of them.
+
+A plain run of one world (config 2, or --scene config3 / config5) sets up, warms up, times its window, writes --dump-outputs and prints
+the line: the headline figures and what the timed windows themselves yield.  `--full` adds everything that takes runs of its own: the
+instrumented replays behind `roofline`, `phase_ms_per_step_rank0` and `gpu_event_ms`; config 2's settled window, nested configs 3 and 5
+and constraint-order checks; the CPU baseline (every N = 1 line).  The --no-* options trim a --full run.  The tile lines (N > 1,
+--scene config4 / config5_tiles / weak) carry their replay, settled window and one-GPU reference either way.
 """
 import argparse
 import json
@@ -53,10 +59,12 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--min-seconds", type=float, default=5.0, help="N = 1: repeat the timed window from a snapshot until this much has been measured "
                                                                      "(the settled window likewise; the nested configs 3 and 5 for a third of it each)")
-    ap.add_argument("--no-settled", action="store_true", help="N = 1: skip the second window after tick 400")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="N = 1: skip the nested one-window runs of BASELINE configs 3 and 5")
-    ap.add_argument("--no-order-check", action="store_true", help="N = 1: skip the canonical-vs-world.rs-order deviation (a few seconds of host BVH replay)")
+    ap.add_argument("--full", action="store_true", help="beyond the headline: instrumented replays (roofline, phase_ms), config 2's settled window, nested "
+                                                        "configs 3 and 5 and order checks, the CPU baseline (see the module docstring)")
+    ap.add_argument("--no-settled", action="store_true", help="--full, N = 1: skip the second window after tick 400")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full, N = 1: skip the nested one-window runs of BASELINE configs 3 and 5")
+    ap.add_argument("--no-order-check", action="store_true", help="--full, N = 1: skip the canonical-vs-world.rs-order deviation (a few seconds of host BVH replay)")
     ap.add_argument("--solver-mode", type=int, default=None, help="override the library's default solver mode (development)")
     ap.add_argument("--refresh-every", type=int, default=None, help="solver iterations between ghost velocity refreshes (tiles)")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE", help="library option for an experiment (mgf_world_set_option), repeatable")
@@ -141,7 +149,7 @@ def main():
     else:
         out = bench_tiles(args, ctx, mgf_amd, scenes, configure, mode, scene_kind, rank, world_size, dist, torch, red_dev, barrier, refresh_every)
     if rank == 0:
-        if world_size == 1 and not args.no_cpu_baseline:
+        if world_size == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.iters)
             except Exception as e:  # (the line with the GPU measurement is printed whatever happens to the CPU sample)
@@ -322,8 +330,6 @@ def bench_single_world(args, ctx, mgf_amd, scenes, configure, mode):
         del final
     windows.sort(key=lambda x: x[0])
     elapsed, (units, cons, _l, _k, _p), tick_roof = windows[len(windows) // 2]
-    ru, rc, launches, kms, phase = _instrumented_replays(snap, configure, dt, args.iters, args.steps)
-    assert (ru, rc) == (units, cons), "a replay of the window did other work than the window"
     window_name = f"ticks {args.warmup}..{args.warmup + args.steps} of the falling pile"
     out = {
         "metric": "contact_constraint_iters_per_sec", "value": units / elapsed, "unit": "constraint-iters/s", "n_gpus": 1,
@@ -341,14 +347,20 @@ def bench_single_world(args, ctx, mgf_amd, scenes, configure, mode):
                          "ms_per_step_min": windows[0][0] * 1e3 / args.steps, "ms_per_step_max": windows[-1][0] * 1e3 / args.steps},
         "lib_sha256": _lib_sha256(),
         "physics_steps_per_sec": args.steps / elapsed, "constraints_per_step": cons / args.steps,
+        "roofline_tick": tick_roof,
+    }
+    if not args.full:
+        return out
+    ru, rc, launches, kms, phase = _instrumented_replays(snap, configure, dt, args.iters, args.steps)
+    assert (ru, rc) == (units, cons), "a replay of the window did other work than the window"
+    out.update({
         "solver_launches_per_step": launches / args.steps, "phase_ms_per_step_rank0": phase,
         "solve_phase_constraint_iters_per_sec_rank0": units / (phase["ms_solve"] * args.steps * 1e-3) if phase["ms_solve"] > 0 else None,
         "roofline": _roofline(units, launches, kms, mode, "all iterations of a tick", ("transient", args.warmup, args.steps)),
-        "roofline_tick": tick_roof,
         # GPU activity as the stream itself saw it (HIP events around every tick of the instrumented replay; no sampler needed)
         "gpu_event_ms": {"replayed_window": round(phase["ms_total"] * args.steps, 3), "solver_kernel_ms_replayed_window": round(kms, 3)},
         "instrumentation": INSTRUMENTATION_NOTE,
-    }
+    })
     if not args.no_order_check:
         try:
             out["constraint_order_deviation"] = order_deviation(ctx, mgf_amd, scene, dt, args.iters)
@@ -437,16 +449,17 @@ def bench_other_config(args, ctx, mgf_amd, scenes, configure, mode, kind, standa
         del final
     windows.sort(key=lambda x: x[0])
     elapsed, (units, cons, _l, _k, _p), last, tick_roof = windows[len(windows) // 2]
-    _u, _c, launches, kms, phase = _instrumented_replays(snap, configure, dt, args.iters, steps)
     res = {
         "value": units / elapsed, "unit": "constraint-iters/s", "ms_per_step": elapsed * 1e3 / steps, "steps": steps, "warmup": warmup,
         "windows": len(windows), "bodies": len(world), "constraints_per_step": cons / steps, "terrain_constraints_last_tick": int(last["n_terrain_constraints"]),
-        "accepted_pairs_last_tick": int(last["n_pair_candidates"]), "phase_ms_per_step": phase,
-        "gpu_event_ms_replayed_window": round(phase["ms_total"] * steps, 3),
-        "roofline": _roofline(units, launches, kms, mode, "all iterations of a tick", (kind, warmup, steps), workload=kind),
+        "accepted_pairs_last_tick": int(last["n_pair_candidates"]),
         "roofline_tick": tick_roof,
         "store_resorts": world.counter("store_resorts"),
     }
+    if args.full or not standalone:  # (nested in config 2's line, which is itself a --full run)
+        _u, _c, launches, kms, phase = _instrumented_replays(snap, configure, dt, args.iters, steps)
+        res.update({"phase_ms_per_step": phase, "gpu_event_ms_replayed_window": round(phase["ms_total"] * steps, 3),
+                    "roofline": _roofline(units, launches, kms, mode, "all iterations of a tick", (kind, warmup, steps), workload=kind)})
     if not standalone:
         res["workload"] = what
         return res

@@ -117,3 +117,96 @@ def test_dump_outputs_of_the_largest_single_world_stays_within_64_mb(tmp_path):
     w = _FakeWorld(2 * bench.DUMP_BODY_ROWS, 3 * bench.DUMP_CONSTRAINT_ROWS, 2)
     bench.dump_outputs(str(tmp_path), [("", w, None)], [_stats(1)])
     assert sum(p.stat().st_size for p in tmp_path.glob("*.npy")) <= 64 << 20
+
+
+class _TickWorld:
+    """What bench.py's one-world lines drive of an mgf_amd.World (options, ticks, clones, counters), with fixed StepStats per tick."""
+
+    def __init__(self, n_bodies=64):
+        self.n = n_bodies
+
+    def __len__(self):
+        return self.n
+
+    def set_option(self, key, value):
+        pass
+
+    def _tick(self):
+        from mgf_amd._capi import StepStats
+        return StepStats(n_bodies=self.n, n_constraints=100, n_pair_candidates=150, solver_kernel_launches=2, ms_solver_kernels=0.25,
+                         ms_integrate=0.1, ms_broadphase=0.1, ms_narrowphase=0.1, ms_setup=0.1, ms_solve=0.5, ms_total=1.0)
+
+    def step(self, dt, iters):
+        return self._tick()
+
+    def step_many(self, dt, iters, n):
+        return [self._tick() for _ in range(n)]
+
+    def clone(self):
+        return _TickWorld(self.n)
+
+    def counter(self, name):
+        return 0
+
+
+def _run_one_world(monkeypatch, capsys, argv):
+    """bench.main() on a stand-in world: the JSON line it prints and which of the legs beyond the timed window it entered."""
+    import json
+    import torch
+    import mgf_amd
+    import bench
+    entered = []
+
+    def spy(name, fn=None, ret=None):
+        def leg(*a, **k):
+            entered.append(name)
+            return fn(*a, **k) if fn else ret
+        monkeypatch.setattr(bench, name, leg)
+    spy("_instrumented_replays", bench._instrumented_replays)
+    spy("bench_other_config", bench.bench_other_config)
+    for name in ("order_deviation", "demo_order_cost", "cpu_baseline"):
+        spy(name, ret={})
+    small = lambda sc: sc.sphere_pile(4, 4, 4)  # noqa: E731  (configs 3 and 5's own scenes are large: their legs are what is counted here)
+    for kind in ("config3", "config5"):
+        monkeypatch.setitem(bench.OTHER_CONFIGS, kind, (bench.OTHER_CONFIGS[kind][0], small, bench.OTHER_CONFIGS[kind][2]))
+    monkeypatch.setattr(mgf_amd, "Context", lambda dev: object())
+    monkeypatch.setattr(mgf_amd.World, "from_scene", staticmethod(lambda ctx, scene: _TickWorld(len(scene["mass"]))))
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--tile", "4", "4", "4", "--min-seconds", "0"] + argv)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MGF_RCCL_LIB", "MGF_BENCH_ALLOW_RCCL_OVERRIDE", "MGF_BENCH_DEVICE"):
+        monkeypatch.delenv(k, raising=False)
+    capsys.readouterr()
+    bench.main()
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0]), entered
+
+
+HEADLINE = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+
+
+def test_a_plain_run_times_its_window_and_nothing_else(monkeypatch, capsys):
+    d, entered = _run_one_world(monkeypatch, capsys, ["--gpus", "1", "--steps", "6", "--warmup", "2"])
+    assert entered == []
+    assert all(k in d for k in HEADLINE) and d["metric"] == "contact_constraint_iters_per_sec" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 6 and d["warmup"] == 2 and d["constraints_per_step"] == 100
+    for extra in ("roofline", "phase_ms_per_step_rank0", "gpu_event_ms", "settled", "config3", "config5", "constraint_order_deviation", "cpu_baseline"):
+        assert extra not in d, extra
+
+
+def test_full_runs_every_leg_of_the_one_world_line(monkeypatch, capsys):
+    d, entered = _run_one_world(monkeypatch, capsys, ["--gpus", "1", "--steps", "6", "--warmup", "2", "--full"])
+    # the window's replays, the settled window's, then configs 3 and 5 each with their own replays; the order checks; the CPU baseline
+    assert entered == ["_instrumented_replays", "order_deviation", "demo_order_cost", "_instrumented_replays",
+                       "bench_other_config", "_instrumented_replays", "bench_other_config", "_instrumented_replays", "cpu_baseline"]
+    assert all(k in d for k in HEADLINE) and d["steps"] == 6 and d["warmup"] == 2
+    assert d["roofline"]["launches_timed"] == 12 and d["solver_launches_per_step"] == 2 and d["gpu_event_ms"]["replayed_window"] == 6.0
+    assert d["settled"]["ms_per_step"] > 0 and d["settled"]["roofline"] and d["config3"]["roofline"] and d["config5"]["roofline"]
+    assert d["cpu_baseline"] == {} and "constraint_order_deviation" in d
+
+
+def test_the_other_configs_own_lines_replay_only_with_full(monkeypatch, capsys):
+    d, entered = _run_one_world(monkeypatch, capsys, ["--scene", "config3", "--steps", "4"])
+    assert entered == ["bench_other_config"] and "roofline" not in d and d["value"] > 0 and d["ms_per_step"] > 0
+    d, entered = _run_one_world(monkeypatch, capsys, ["--scene", "config5", "--steps", "4", "--full", "--no-cpu-baseline"])
+    assert entered == ["bench_other_config", "_instrumented_replays"] and d["roofline"]["launches_timed"] == 8

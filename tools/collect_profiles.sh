@@ -9,7 +9,7 @@ set -u
 TAG=${1:-r05}
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
-B="python $R/bench.py --no-cpu-baseline --no-settled --no-order-check --no-other-configs --min-seconds 0"
+B="python $R/bench.py --full --no-cpu-baseline --no-settled --no-order-check --no-other-configs --min-seconds 0"
 cd /tmp && export TMPDIR=/tmp
 run() {  # name, timed ticks, dominant kernel, window label for bench.py, its warm-up, bench args...
   local N=$1 K=$2 KER=$3 WIN=$4 W=$5; shift 5
@@ -55,9 +55,9 @@ run_tiles config5_tiles config5_tiles 80
 fi
 cd $R
 if [ -z "${ONLY_TILES:-}" ]; then
-python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
-python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_driver_command.json 2> /dev/null
-python bench.py --scene config5 --no-cpu-baseline > $O/${TAG}_config5_undivided_1gpu.json 2> /dev/null
+python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_driver_command.json 2> /dev/null
+python bench.py --full --scene config5 --no-cpu-baseline > $O/${TAG}_config5_undivided_1gpu.json 2> /dev/null
 python tools/config4_undivided.py > /dev/null 2>&1; cp $O/config4_undivided_1gpu.json $O/${TAG}_config4_undivided_1gpu.json
 fi
 python bench.py --gpus 1 --scene config4 --no-cpu-baseline > $O/${TAG}_config4_8tiles_1gpu_bench.json 2> /dev/null

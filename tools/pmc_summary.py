@@ -69,7 +69,7 @@ def main():
                  hbm_bytes_per_launch=2 * f + w, lib_sha256=lib_sha256())
         if window:
             d["window"] = window
-            d["note"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `python bench.py --no-cpu-baseline --no-settled "
+            d["note"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `python bench.py --full --no-cpu-baseline --no-settled "
                          f"--no-order-check --min-seconds 0 --warmup {window[1]}` (262144 spheres, {window[2]} timed ticks, tools/collect_profiles.sh); "
                          f"average over the LAST {count} launches of {pattern} = the timed window; counter unit KiB; hbm_bytes_per_launch = 2*FETCH + WRITE "
                          "(gfx950 FETCH_SIZE reads 1/2 of 16-B/lane loads, MI355X_MICROARCH.md HBM section)")

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for G in "$@"; do
   i=$((i+1))
-  rocprofv3 --pmc $G -d $O/pmck_$i -o bench -- python $R/bench.py --no-cpu-baseline --no-settled --no-order-check --no-other-configs --min-seconds 0 ${BENCH_ARGS:---steps 20 --warmup 5} > $O/pmck_$i.log 2>&1
+  rocprofv3 --pmc $G -d $O/pmck_$i -o bench -- python $R/bench.py --full --no-cpu-baseline --no-settled --no-order-check --no-other-configs --min-seconds 0 ${BENCH_ARGS:---steps 20 --warmup 5} > $O/pmck_$i.log 2>&1
   KPAT="${KPAT:-.}" python - <<PY
 import sqlite3, glob, collections, os, re
 db = sqlite3.connect(glob.glob("$O/pmck_$i/*results.db")[0])
