@@ -95,6 +95,10 @@ typedef struct mgf_step_stats {
   uint64_t n_constraints;          /* ContactConstraints handed to the Solver this tick            */
   uint64_t n_terrain_constraints;  /* of which body-vs-Mesh (one per terrain contact, world.rs:243) */
   uint64_t n_pair_candidates;      /* broadphase hits (j < i, tight_i overlaps fat_j)               */
+  /* (LIMIT: counted from the bodies' own boxes.  The reference reaches a leaf of its tree only through the leaf's ancestors (bvh.rs:283-310),
+   * whose boxes are (upper + lower) / 2 rounded to f32: about 1e5 from the origin, where an ulp is 1/128, such a box can miss its child by that
+   * ulp and the reference then skips a pair whose boxes touch exactly.  The count - and the pair, which is tested for contacts here - can exceed the
+   * reference's by such pairs; up to coordinates of 1e4 no test has seen one.  tests/contact_corpus.py: LeafRecount.) */
   uint64_t n_terrain_candidates;   /* mesh-BVH face hits                                            */
   uint64_t n_refits;               /* bodies whose swept AABB left their fat AABB (world.rs:235)    */
   uint32_t n_levels;               /* depth of the order-preserving dependency DAG                  */
@@ -526,7 +530,9 @@ MGF_API mgf_status mgf_world_set_option(mgf_world* w, const char* key, int64_t v
  * the store to the caller's order), "query_large_bodies" / "query_cells" (the last world query's large-body list and grid),
  * "query_build_ns" / "query_run_ns" (HIP-event times of its grid build and of its query pass), "pair_brick_ticks", "front_rows_ticks",
  * "fused_contacts_ticks", "early_cells_ticks" (ticks whose collide phase settled on k_pair_brick, on the list-free front end, on
- * k_contacts_spheres without candidate lists, on cells worked out inside k_integrate)}. */
+ * k_contacts_spheres without candidate lists, on cells worked out inside k_integrate), "two_pass_ticks", "tree_ticks", "big_parts_ticks"
+ * (ticks whose candidate lists were counted and filled in two passes, whose pair search walked the tree instead of the cell grid, whose
+ * narrowphase ran the kernels for bodies of more than four components), "max_parts" (the most components any body has)}. */
 MGF_API mgf_status mgf_world_counter(const mgf_world* w, const char* name, int64_t* out);
 /* Raw device pointers of resident state for zero-copy exchange (multi-GPU halo): name in
  * {"x","q","solver_rec","delta"} (the pub fields `x`, `q` of RigidBodyVec physics.rs:142-154 and what ConstrainedSet::get returns,

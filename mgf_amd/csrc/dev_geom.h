@@ -604,11 +604,17 @@ __device__ inline bool capsule_mcapsule(const Capsule& self, const Capsule& c, V
 // in [0, 1] of B's relative motion (t is clamped at 0 or rejected below it: collision.rs:249-359, 1089-1356), so the shapes'
 // bounding spheres come within reach of each other during the tick - with a margin of 1 % and a millimetre for rounding.  Nine
 // candidates in ten of a pile of capsules or two-part bodies end here.
+// The margin also grows with the coordinates themselves: the mid points below, and the closest points and end positions the reference's tests
+// form (geom.rs:408-444, 590-603; collision.rs:1165, 1262), are ABSOLUTE positions rounded to f32 - half an ulp per coordinate each, 0.004 at
+// 1e5 - so a pair of 5 cm bodies 100 km out touches, for the reference, from a few ulps further than its shapes do (tests/contact_corpus.py,
+// the rung of offset 1e5 and size 0.05, lost two contacts in five thousand to the fixed margin).  Half a dozen such roundings are below
+// 1e-6 of the largest coordinate; 1e-5 of the coordinates' sum is the slack the part-pair reject of k_narrow_pairs_parts already allows.
 __device__ __forceinline__ bool comp_pair_far(const Comp& A, V3 vA, const Comp& B, V3 vB) {
   const bool sa = A.kind == KIND_SPHERE, sb = B.kind == KIND_SPHERE;
   const V3 ma = sa ? A.p : A.p + A.d * 0.5f, mb = sb ? B.p : B.p + B.d * 0.5f;
   const float ra = sa ? A.r : A.r + 0.5f * mag(A.d), rb = sb ? B.r : B.r + 0.5f * mag(B.d);
-  const float lim = (ra + rb + mag(vB - vA)) * 1.01f + 1e-3f;
+  const float slack = 1e-3f + 1e-5f * (fabs_rs(ma.x) + fabs_rs(ma.y) + fabs_rs(ma.z) + fabs_rs(mb.x) + fabs_rs(mb.y) + fabs_rs(mb.z));
+  const float lim = (ra + rb + mag(vB - vA)) * 1.01f + slack;
   const V3 dd = mb - ma;
   return dot(dd, dd) > lim * lim;
 }
@@ -673,12 +679,21 @@ __device__ __forceinline__ bool comp_tri_far(const Comp& A, V3 vA, const Triangl
   // (tests/test_gpu_tri_reject.py found it; a sphere is guarded: tri_msphere returns at |v| = 0, collision.rs:640).
   if (A.kind != KIND_SPHERE && mag2(vA) == 0.0f) return false;
   const V3 p0 = A.p, p1 = A.kind == KIND_SPHERE ? A.p : A.p + A.d;
+  // Nor is a capsule whose axis the coordinates hardly resolve (shorter than 1e-5 of them: a hundred ulps): the reference extrudes every edge of
+  // the face by the axis (collision.rs:973-1060, `edge_a + -c.d`), and where a component of the axis is below the ulp of the vertex those quads
+  // are collinear or tilted by rounding - a 4 cm capsule 1e5 from the origin, 2.7 degrees off an edge, "touches" a face 5 m away at t = 0
+  // (found in a world of 32-part bodies at that rung; tests/contact_corpus.py, family reject_tri_unresolved_axis).  Its tests decide.
+  const float res = 1e-5f * (fabs_rs(p0.x) + fabs_rs(p0.y) + fabs_rs(p0.z));
+  if (A.kind != KIND_SPHERE && !(mag2(A.d) > res * res)) return false;
   // (... of the reference's ARITHMETIC, which is f32 relative to the far end of an edge: ray_capsule forms |m|^2 |D|^2 - (m.D)^2 with m from
   // the edge's start - 200 m away on the floor of config 5's box - and whether a capsule 0.31 from the floor's diagonal touches it comes out
   // of the last bits (it did: tools/r06/dbg_c5.py).  The reach below grows with the square of the distance to the face's farthest vertex:
   // nothing beside a 2 m triangle, 0.7 instead of 0.3 beside a 200 m one.)
   const float far2 = fmax_rs(fmax_rs(mag2(p0 - tri.a), mag2(p0 - tri.b)), mag2(p0 - tri.c)) + mag2(p1 - p0);
-  const float lim0 = (A.r + mag(vA)) * 1.01f + 1e-3f;
+  // (... and with the coordinates themselves: the reference measures the body against the face's plane as n . c - n . a, two dot products of
+  // ABSOLUTE positions - 1e-6 of the largest coordinate in error, more than a 3 cm sphere's radius at 1e5 - while the tests below work on
+  // differences; tests/contact_corpus.py lost 13 contacts in 96 000 at offset 1e5, size 0.05.  The same 1e-5 of the coordinates as comp_pair_far.)
+  const float lim0 = (A.r + mag(vA)) * 1.01f + 1e-3f + res;
   const float lim = __builtin_sqrtf(lim0 * lim0 + 1e-5f * far2);
   const V3 e0 = tri.b - tri.a, e1 = tri.c - tri.b, e2 = tri.a - tri.c;
   const V3 n = cross(e0, tri.c - tri.a);

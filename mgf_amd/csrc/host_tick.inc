@@ -432,6 +432,9 @@ static mgf_status collide_enqueue(mgf_world* w, float dt, bool solver_follows = 
   w->ts->front_rows = front_rows;
   w->ts->contacts_fused = contacts_fused;
   w->ts->cells_early = cells_done;
+  w->ts->two_pass = two_pass;
+  w->ts->tree = !two_pass && !use_grid && !demo;
+  w->ts->big_parts = w->max_parts > (uint32_t)kMaxParts;
   if (front_rows) w->ts->brick = false;  // (k_pair_grid_n is the pair search of such a world)
   const bool tc_job = (contacts_fused || (front_rows && !terrain_grid)) && terrain_any;
   bool forked = false;
@@ -870,6 +873,7 @@ static mgf_status collide_process(mgf_world* w, bool* retry) {
   }
   if (*retry) { w->n_cap_retries++; return MGF_OK; }
   w->n_path_ticks[0] += w->ts->brick; w->n_path_ticks[1] += w->ts->front_rows; w->n_path_ticks[2] += w->ts->contacts_fused; w->n_path_ticks[3] += w->ts->cells_early;
+  w->n_path_ticks[4] += w->ts->two_pass; w->n_path_ticks[5] += w->ts->tree; w->n_path_ticks[6] += w->ts->big_parts;
   if (w->opt_wide_list) {  // the wide bodies' limit for the ticks to come (WideSpec, k_bodies.h)
     if (w->wide_tick_on) {  // (the read-back's rmax is the largest half extent of the bodies that were NOT wide)
       w->n_wide_ticks++;

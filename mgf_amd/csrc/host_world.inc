@@ -74,7 +74,7 @@ struct mgf_world {
   // ticks whose collide phase settled on each fast path (counted by collide_process; read-only, for tests that must prove a path ran):
   // [0] k_pair_brick, [1] the list-free front end (k_front_rows.h), [2] k_contacts_spheres' rows -> records without candidate lists,
   // [3] cells and ranks worked out by k_integrate over the last tick's box
-  uint64_t n_path_ticks[4] = {0, 0, 0, 0};
+  uint64_t n_path_ticks[7] = {0, 0, 0, 0, 0, 0, 0};
   DBuf<float4> wide_list;
   // mgf_world_raycast_many / mgf_world_overlap_aabb_many (host_query.inc): the query's own grid and lists - nothing of the tick's is read or written
   DBuf<float4> q_bc, q_br;
@@ -271,6 +271,9 @@ struct mgf_world {
     bool front_rows = false;          // the tick ran the list-free front end of a world that is not spheres only (k_front_rows.h)
     bool contacts_fused = false;      // ... k_contacts_spheres: rows to constraint records without candidate lists
     bool cells_early = false;         // ... took its cells and ranks from k_integrate (over the last tick's box)
+    bool two_pass = false;            // ... counted and filled its candidate lists in two passes (k_candidates)
+    bool tree = false;                // ... searched its pairs in the tree (k_pair_rows), not in the cell grid
+    bool big_parts = false;           // ... ran k_narrow_pairs_big / k_narrow_terrain_big (a body of more than kMaxParts components)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // the side stream's start and end inside the tick (no timing: created on first use)
     uint32_t* pin = nullptr;
     uint32_t* pin_dev = nullptr;      // the same memory as the device sees it (k_publish)
@@ -583,6 +586,10 @@ extern "C" mgf_status mgf_world_counter(const mgf_world* w, const char* name, in
   if (!strcmp(name, "front_rows_ticks")) { *out = (int64_t)w->n_path_ticks[1]; return MGF_OK; }
   if (!strcmp(name, "fused_contacts_ticks")) { *out = (int64_t)w->n_path_ticks[2]; return MGF_OK; }
   if (!strcmp(name, "early_cells_ticks")) { *out = (int64_t)w->n_path_ticks[3]; return MGF_OK; }
+  if (!strcmp(name, "two_pass_ticks")) { *out = (int64_t)w->n_path_ticks[4]; return MGF_OK; }
+  if (!strcmp(name, "tree_ticks")) { *out = (int64_t)w->n_path_ticks[5]; return MGF_OK; }
+  if (!strcmp(name, "big_parts_ticks")) { *out = (int64_t)w->n_path_ticks[6]; return MGF_OK; }
+  if (!strcmp(name, "max_parts")) { *out = (int64_t)w->max_parts; return MGF_OK; }
   if (!strcmp(name, "wide_ticks")) { *out = (int64_t)w->n_wide_ticks; return MGF_OK; }
   if (!strcmp(name, "wide_overflows")) { *out = (int64_t)w->n_wide_overflows; return MGF_OK; }
   if (!strcmp(name, "flow6_skipped")) { *out = (int64_t)w->n_flow6_skipped; return MGF_OK; }

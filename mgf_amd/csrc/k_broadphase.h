@@ -1011,7 +1011,10 @@ __device__ __forceinline__ void pair_query_cells(const Src& S, const Box& q, con
       for (int u = 0; u < 2; ++u) {
         const uint32_t a = a0 + (uint32_t)u * kCoopLanes + (uint32_t)sub;
         if (a < na) {
-          // cheap and conservative first: the centres never come closer than |d| - |v| during the tick
+          // cheap and conservative first: the centres never come closer than |d| - |v| during the tick.  (No term for the size of the
+          // coordinates here, unlike comp_pair_far: the reference's sphere-sphere test works on the same difference of centres, s.c - self.c,
+          // and forms no absolute position before its verdict, so 0.1 % covers its rounding at any offset: tests/test_gpu_contact_corpus.py,
+          // the sphere worlds at 1e5.)
           const V3 dd = xyz(c0[u]) - A.p, v = xyz(d0[u]) - vA;
           const float lim = A.r + c0[u].w + __builtin_sqrtf(dot(v, v));
           if (dot(dd, dd) <= lim * lim * 1.001f) {
@@ -1131,6 +1134,7 @@ __device__ __forceinline__ void brick_query(const Src& S, const Box& q, const Co
   if (!SPHERES) return;
   // the accepted partners through the sphere-sphere test: first the cheap conservative reject (the centres never come closer
   // than |d| - |v| during the tick), survivors compacted in place, then the narrowphase's own function on those
+  // (as in k_pair_grid<true>: nothing grows with the coordinates, the reference's test works on the same difference of centres)
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   const uint32_t na = min(*(volatile uint32_t*)&cnt[0], (uint32_t)kRowCap);
   for (uint32_t a = s; a < na; a += LQ) {

@@ -8,6 +8,7 @@ HIP extension is missing instead of falling back to this.
 import ctypes as C
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -88,13 +89,21 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        build()
-        L = C.CDLL(_LIB_PATH)
+        # MGF_ORACLE_LIB: another build of the same sources (tests/oracle_coverage.py loads its instrumented copy in a child process)
+        path = os.environ.get("MGF_ORACLE_LIB")
+        if path:
+            print(f"oracle: loading {path} (MGF_ORACLE_LIB) instead of {_LIB_PATH}", file=sys.stderr)
+        else:
+            build()
+            path = _LIB_PATH
+        L = C.CDLL(path)
         P = C.POINTER
         L.mgfo_contacts.argtypes = [P(Shape), P(Vec3), P(Shape), P(Vec3), P(Contact), C.c_int]
         L.mgfo_contacts.restype = C.c_int
         L.mgfo_local_contacts_pair.argtypes = [P(Component), P(Vec3), P(Component), P(Vec3), P(LocalContact), C.c_int]
         L.mgfo_local_contacts_pair.restype = C.c_int
+        L.mgfo_contacts_batch.argtypes = [C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
+        L.mgfo_local_contacts_pair_batch.argtypes = [C.c_int64] + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p]
         for f in (L.mgfo_ray_capsule, L.mgfo_ray_sphere):
             f.argtypes = [P(Vec3), P(Vec3), P(Shape), P(Vec3), P(C.c_float)]
             f.restype = C.c_int
@@ -189,6 +198,8 @@ def lib():
         L.mgfo_world_get_state.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.mgfo_world_set_state.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.mgfo_world_get_colliders.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mgfo_world_get_parts.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, P(Vec3), C.c_int64]
+        L.mgfo_world_get_parts.restype = C.c_int64
         L.mgfo_world_get_inv_moment.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.mgfo_world_set_velocity.argtypes = [C.c_void_p, C.c_int64, P(Vec3), P(Vec3)]
         L.mgfo_world_terrain_contacts.argtypes = [C.c_void_p, C.c_int64, P(LocalContact), C.c_int64]
@@ -265,6 +276,37 @@ def intersection_aabb(p, d, dt, c, r):
     box = Aabb(vec3(c), vec3(r))
     hit = lib().mgfo_intersection_aabb(C.byref(vec3(p)), C.byref(vec3(d)), C.c_float(dt), C.byref(box), C.byref(ip), C.byref(t))
     return (ip.tup(), t.value) if hit else None
+
+
+SHAPE_DTYPE = np.dtype([("kind", "<i4"), ("v", "<f4", 12)])
+CONTACT_DTYPE = np.dtype([("a", "<f4", 3), ("b", "<f4", 3), ("n", "<f4", 3), ("t", "<f4")])
+assert SHAPE_DTYPE.itemsize == C.sizeof(Shape) and CONTACT_DTYPE.itemsize == C.sizeof(Contact)
+
+
+def contacts_batch(a, vel_a, b, vel_b, has_vel, slots=2):
+    """contacts() for n problems held in arrays: a, b SHAPE_DTYPE (n,), vel_a, vel_b (n, 3), has_vel (n,) uint8 (bit0: a moves, bit1: b moves).
+    Returns (contacts CONTACT_DTYPE (n, slots), counts (n,) int32) in callback order."""
+    a, b = np.ascontiguousarray(a, SHAPE_DTYPE), np.ascontiguousarray(b, SHAPE_DTYPE)
+    n = len(a)
+    va, vb = (np.ascontiguousarray(v, np.float32).reshape(n, 3) for v in (vel_a, vel_b))
+    hv = np.ascontiguousarray(has_vel, np.uint8)
+    out = np.zeros((n, slots), CONTACT_DTYPE)
+    counts = np.zeros(n, np.int32)
+    lib().mgfo_contacts_batch(n, a.ctypes.data, va.ctypes.data, b.ctypes.data, vb.ctypes.data, hv.ctypes.data, out.ctypes.data, slots,
+                              counts.ctypes.data)
+    return out, counts
+
+
+def local_contacts_pair_batch(a, delta_a, b, delta_b, slots=1):
+    """local_contacts_pair() for n pairs: a, b COMPONENT_DTYPE (n,), delta_a, delta_b (n, 3) -> (LOCAL_CONTACT_DTYPE (n, slots), counts)."""
+    a, b = np.ascontiguousarray(a, COMPONENT_DTYPE), np.ascontiguousarray(b, COMPONENT_DTYPE)
+    n = len(a)
+    da, db = (np.ascontiguousarray(v, np.float32).reshape(n, 3) for v in (delta_a, delta_b))
+    out = np.zeros((n, slots), LOCAL_CONTACT_DTYPE)
+    counts = np.zeros(n, np.int32)
+    lib().mgfo_local_contacts_pair_batch(n, a.ctypes.data, da.ctypes.data, b.ctypes.data, db.ctypes.data, out.ctypes.data, slots,
+                                         counts.ctypes.data)
+    return out, counts
 
 
 LOCAL_CONTACT_DTYPE = np.dtype([("local_a", "<f4", 3), ("local_b", "<f4", 3), ("a", "<f4", 3), ("b", "<f4", 3), ("n", "<f4", 3), ("t", "<f4")])
@@ -575,6 +617,13 @@ class World:
         d = np.zeros((n, 3), np.float32)
         lib().mgfo_world_get_colliders(self.h, comps.ctypes.data, d.ctypes.data)
         return comps, d
+
+    def parts(self, i, cap=32):
+        """the world-space parts of body i as the collide phase tests them, and their common motion"""
+        out = np.zeros(cap, COMPONENT_DTYPE)
+        vel = Vec3()
+        n = lib().mgfo_world_get_parts(self.h, int(i), out.ctypes.data, C.byref(vel), cap)
+        return out[:n], np.array(vel.tup(), np.float32)
 
     def inv_moment(self):
         n = len(self)

@@ -122,6 +122,18 @@ int mgfo_local_contacts_pair(const o_component* a, const o_vec3* delta_a, const 
   return n;
 }
 
+// Batched forms of the two entries above for corpora of many thousand problems (tests/contact_corpus.py): has_vel bit0 = a moving,
+// bit1 = b moving; `slots` contacts are kept per problem, counts[i] is the number emitted (it may exceed slots; -1 unsupported).
+void mgfo_contacts_batch(int64_t n, const o_shape* a, const o_vec3* vel_a, const o_shape* b, const o_vec3* vel_b, const uint8_t* has_vel,
+                         o_contact* out, int32_t slots, int32_t* counts) {
+  for (int64_t i = 0; i < n; ++i)
+    counts[i] = mgfo_contacts(a + i, (has_vel[i] & 1) ? vel_a + i : nullptr, b + i, (has_vel[i] & 2) ? vel_b + i : nullptr, out + slots * i, slots);
+}
+void mgfo_local_contacts_pair_batch(int64_t n, const o_component* a, const o_vec3* delta_a, const o_component* b, const o_vec3* delta_b,
+                                    o_local_contact* out, int32_t slots, int32_t* counts) {
+  for (int64_t i = 0; i < n; ++i) counts[i] = mgfo_local_contacts_pair(a + i, delta_a + i, b + i, delta_b + i, out + slots * i, slots);
+}
+
 int mgfo_ray_capsule(const o_vec3* p, const o_vec3* d, const o_shape* cap, o_vec3* ip, float* t) {
   Intersection i;
   if (!ray_capsule(Ray{V(*p), V(*d)}, as_capsule(*cap), &i)) return 0;
@@ -493,6 +505,17 @@ void mgfo_world_get_colliders(void* wp, o_component* comps, o_vec3* delta) {
     comps[i] = from_component(w->bodies.collider[i].shape);
     if (delta) delta[i] = O(w->bodies.collider[i].vel);
   }
+}
+// the world-space parts of body i as the collide phase tests them (a plain body: its collider), and their common motion
+int64_t mgfo_world_get_parts(void* wp, int64_t i, o_component* out, o_vec3* vel, int64_t cap) {
+  World* w = (World*)wp;
+  const size_t np = w->bodies.n_parts((size_t)i);
+  for (size_t pa = 0; pa < np && (int64_t)pa < cap; ++pa) {
+    const Moving<Component> m = w->bodies.part((size_t)i, pa);
+    out[pa] = from_component(m.shape);
+    *vel = O(m.vel);
+  }
+  return (int64_t)np;
 }
 void mgfo_world_get_inv_moment(void* wp, float* out9_body, float* out9_world) {
   World* w = (World*)wp;

@@ -36,7 +36,7 @@ def _same_contacts(got, want, what):
 @pytest.mark.parametrize("ka,kb", [("sphere", "sphere"), ("capsule", "sphere"), ("sphere", "capsule"), ("capsule", "capsule")])
 def test_random_moving_pairs_bit_exact(ctx, ka, kb):
     import mgf_amd
-    rng = np.random.default_rng(hash((ka, kb)) % 2 ** 32)
+    rng = np.random.default_rng(1000 + 2 * (kb == "capsule") + (ka == "capsule"))  # (hash() of strings is salted per process)
     probs = []
     for _ in range(3000):
         a, b = _rand_shape(rng, ka), _rand_shape(rng, kb)
