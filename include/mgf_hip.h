@@ -130,6 +130,7 @@ typedef struct mgf_world mgf_world;
 typedef struct mgf_compound mgf_compound;
 typedef struct mgf_solver mgf_solver;
 typedef struct mgf_tiles mgf_tiles;
+typedef struct mgf_batch mgf_batch;
 
 /* ---- context ---------------------------------------------------------------------- */
 MGF_API mgf_status mgf_ctx_create(int device, mgf_ctx** out);
@@ -541,6 +542,49 @@ MGF_API mgf_status mgf_world_counter(const mgf_world* w, const char* name, int64
  * mgf_world_release_device_ptrs gives them back - after it the pointers must not be used. */
 MGF_API mgf_status mgf_world_device_ptr(mgf_world* w, const char* name, void** ptr, int64_t* bytes);
 MGF_API mgf_status mgf_world_release_device_ptrs(mgf_world* w);
+
+/* ---- many small worlds (NOT in the reference: world.rs has one World; DESIGN.md "many small worlds") ----------------------------
+ * A batch of n_worlds independent worlds, resident in HBM, stepped together: ONE kernel launch per tick whatever n_worlds is, one
+ * workgroup per world, no host wait between the ticks of a call.  Per world the definition is exactly World::step
+ * (mgf_demo/world.rs:227-294) in the canonical constraint order, as mgf_world_step computes it: complete_motion + integrate
+ * (physics.rs:222-269), the fat-box refit rule (world.rs:235-238), Mesh::contacts in mesh-BVH DFS order with every contact a constraint of
+ * its own (world.rs:243-251), the partners j < i ascending through ContactPruner / Manifold / ContactConstraint::new
+ * (manifold.rs:72-148, solver.rs:101-191), Solver::solve (solver.rs:72-78).  Worlds never interact; what world k computes does not
+ * depend on what else is in the batch or on where in it the world sits.  No workgroup waits for another: a batch may hold more
+ * worlds than the device holds workgroups, and it is safe on a device shared with another process.
+ * LIMITS: bodies of one component (spheres and capsules); at most MGF_BATCH_MAX_BODIES bodies per world (a call that would exceed it
+ * is refused with MGF_ERR_INVALID and adds nothing); one terrain mesh shared by every world (copied, its position included; NULL =
+ * none); canonical constraint order only.  There are no bodies of several components, no obstacles, no ghosts or tiles, no
+ * constraint_order = demo, no queries: a batch has no entry point for them.  A tick never fails for list sizes: a world whose
+ * constraints outgrow its share of the storage gets its tick undone on the device and run again with more (Solver::solve and
+ * World::step have no capacity failure, solver.rs:72-78); mgf_batch_counter "capacity_retries" counts those re-runs.
+ * Calls are synchronous on the context's stream; the handle keeps a reference on the context; there is no CPU fallback. */
+#define MGF_BATCH_MAX_BODIES 1024
+MGF_API mgf_status mgf_batch_new(mgf_ctx* ctx, const mgf_params* params, int64_t n_worlds, mgf_batch** out);  /* n_worlds x World::new world.rs:160 */
+MGF_API void mgf_batch_free(mgf_batch* b);
+MGF_API mgf_status mgf_batch_set_terrain(mgf_batch* b, const mgf_mesh* mesh);                     /* World.terrain, shared */
+/* World::add_body / RigidBodyVec::add_body (physics.rs:200-218, world.rs:178-184) in bulk, for world `world`; *first_id = the index of the
+ * first new body within that world.  A tag other than 0 or 1, a negative n, a world index out of range: MGF_ERR_INVALID. */
+MGF_API mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mgf_component* comps, int64_t n, const float* mass,
+                                        const float* restitution, const float* friction, const mgf_vec3* world_force, uint64_t* first_id);
+MGF_API int64_t mgf_batch_len(const mgf_batch* b, int64_t world);   /* RigidBodyVec::len; world = -1: all bodies of the batch; -1 for a bad argument */
+/* n_ticks x World::step (world.rs:227-294) of every world.  stats: NULL or n_ticks * n_worlds records, tick-major (record t * n_worlds + k =
+ * world k's tick t): n_bodies, n_constraints, n_terrain_constraints, n_pair_candidates, n_refits and iters are filled; the fields the batch
+ * path has no meaning for - n_terrain_candidates, n_levels, the ms_* times, solver_kernel_launches, n_ghost_constraints - are zero. */
+MGF_API mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats);
+/* As mgf_world_read_state / mgf_world_write_state (physics.rs:142-154) for world `world`, or for world = -1 the whole batch, worlds
+ * concatenated in order; any array pointer may be NULL.  Writing one world's state between ticks resets that environment: no other
+ * world is touched. */
+MGF_API mgf_status mgf_batch_read_state(mgf_batch* b, int64_t world, mgf_vec3* x, mgf_quat* q, mgf_vec3* v, mgf_vec3* omega, mgf_vec3* delta, int64_t cap);
+MGF_API mgf_status mgf_batch_write_state(mgf_batch* b, int64_t world, const mgf_vec3* x, const mgf_quat* q, const mgf_vec3* v, const mgf_vec3* omega,
+                                         const mgf_vec3* delta, int64_t n);
+/* The Solver's constraint list (solver.rs:53-79) of world `world`'s last tick, in insertion order; bodies by their index within the world. */
+MGF_API mgf_status mgf_batch_read_constraints(mgf_batch* b, int64_t world, mgf_constraint* out, int64_t cap, int64_t* count);
+/* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: it does not grow with n_worlds), "capacity_retries"}. */
+MGF_API mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out);
+/* Options (test knobs): "cons_per_body" [4] = the constraint records per body a world's share of the storage starts with (1 .. 4096); a
+ * low value makes the first busy tick outgrow it, which the re-run path then handles. */
+MGF_API mgf_status mgf_batch_set_option(mgf_batch* b, const char* key, int64_t value);
 
 #ifdef __cplusplus
 }

@@ -111,6 +111,7 @@ assert RAY_HIT_DTYPE.itemsize == 28
 SWEEP_HIT_DTYPE = np.dtype([("kind", "<i4"), ("index", "<i4"), ("part", "<i4"), ("a", "<f4", 3), ("b", "<f4", 3), ("n", "<f4", 3), ("t", "<f4")])
 assert SWEEP_HIT_DTYPE.itemsize == 52
 HIT_NONE, HIT_BODY, HIT_TERRAIN, HIT_OBSTACLE = -1, 0, 1, 2
+BATCH_MAX_BODIES = 1024  # MGF_BATCH_MAX_BODIES
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -141,6 +142,8 @@ SYMBOLS = [
     "mgf_geom_to_json", "mgf_geom_from_json",
     "mgf_tiles_create", "mgf_tiles_free", "mgf_rccl_unique_id", "mgf_rccl_allow_override", "mgf_tiles_connect", "mgf_tiles_preflight", "mgf_tiles_step",
     "mgf_tiles_migrated", "mgf_tiles_set_option", "mgf_world_add_obstacle", "mgf_tiles_counter",
+    "mgf_batch_new", "mgf_batch_free", "mgf_batch_set_terrain", "mgf_batch_add_bodies", "mgf_batch_len", "mgf_batch_step",
+    "mgf_batch_read_state", "mgf_batch_write_state", "mgf_batch_read_constraints", "mgf_batch_counter", "mgf_batch_set_option",
 ]
 
 _lib = None
@@ -273,6 +276,17 @@ def load_library():
         "mgf_tiles_counter": (i64, [vp, C.c_char_p]),
         "mgf_tiles_set_option": (i32, [vp, C.c_char_p, i64]),
         "mgf_world_add_obstacle": (i32, [vp, vp]),
+        "mgf_batch_new": (i32, [vp, P(Params), i64, P(vp)]),
+        "mgf_batch_free": (None, [vp]),
+        "mgf_batch_set_terrain": (i32, [vp, vp]),
+        "mgf_batch_add_bodies": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, P(u64)]),
+        "mgf_batch_len": (i64, [vp, i64]),
+        "mgf_batch_step": (i32, [vp, f32, i32, i64, vp]),
+        "mgf_batch_read_state": (i32, [vp, i64, vp, vp, vp, vp, vp, i64]),
+        "mgf_batch_write_state": (i32, [vp, i64, vp, vp, vp, vp, vp, i64]),
+        "mgf_batch_read_constraints": (i32, [vp, i64, vp, i64, P(i64)]),
+        "mgf_batch_counter": (i32, [vp, C.c_char_p, P(i64)]),
+        "mgf_batch_set_option": (i32, [vp, C.c_char_p, i64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1140,6 +1154,110 @@ class World:
 
     def release_device_ptrs(self):
         _check(load_library().mgf_world_release_device_ptrs(self._h))
+
+
+class WorldBatch:
+    """Many small independent worlds resident on one GPU, stepped together (mgf_batch_*): per world `step` is
+    mgf_demo/world.rs::World::step, one workgroup a world.  At most BATCH_MAX_BODIES single-component bodies per world, one
+    terrain mesh shared by all."""
+
+    def __init__(self, ctx, n_worlds, params=None):
+        self._ctx = ctx
+        self._h = C.c_void_p()
+        self.n_worlds = int(n_worlds)
+        p = C.byref(params) if params is not None else None
+        _check(load_library().mgf_batch_new(ctx._h, p, self.n_worlds, C.byref(self._h)))
+        ctx._adopt(self)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load_library().mgf_batch_free(self._h)
+            self._h = None
+
+    @classmethod
+    def from_scenes(cls, ctx, scenes, params=None):
+        """scenes as mgf_amd.scenes makes them, one per world; the first scene's terrain serves all"""
+        b = cls(ctx, len(scenes), params)
+        t = scenes[0]["terrain"] if len(scenes) else None
+        if t is not None:
+            m = Mesh(ctx)
+            m.build(t["verts"], t["faces"])
+            m.set_pos(t["pos"])
+            b.set_terrain(m)
+        for k, sc in enumerate(scenes):
+            if sc.get("compound") is not None:
+                raise MgfError(ERR_INVALID, "a batch world holds bodies of one component")
+            if len(sc["comps"]):
+                b.add_bodies(k, sc["comps"], sc["mass"], sc["restitution"], sc["friction"], sc["force"])
+            if sc.get("v0") is not None and len(sc["comps"]):
+                b.write_state(k, v=sc["v0"])
+        return b
+
+    def set_terrain(self, mesh):
+        _check(load_library().mgf_batch_set_terrain(self._h, mesh._h if mesh is not None else None))
+
+    def add_bodies(self, world, comps, mass, restitution, friction, world_force):
+        comps = np.ascontiguousarray(comps, dtype=COMPONENT_DTYPE)
+        n = len(comps)
+        mass = np.ascontiguousarray(np.broadcast_to(np.asarray(mass, np.float32), (n,)))
+        rest = np.ascontiguousarray(np.broadcast_to(np.asarray(restitution, np.float32), (n,)))
+        fric = np.ascontiguousarray(np.broadcast_to(np.asarray(friction, np.float32), (n,)))
+        force = np.ascontiguousarray(np.broadcast_to(np.asarray(world_force, np.float32), (n, 3)))
+        first = C.c_uint64()
+        _check(load_library().mgf_batch_add_bodies(self._h, int(world), comps.ctypes.data, n, mass.ctypes.data, rest.ctypes.data,
+                                                   fric.ctypes.data, force.ctypes.data, C.byref(first)))
+        return first.value
+
+    def __len__(self):
+        return load_library().mgf_batch_len(self._h, -1)
+
+    def world_len(self, world):
+        return load_library().mgf_batch_len(self._h, int(world))
+
+    def step(self, dt, iters, n=1):
+        """n ticks of every world in one call; returns the statistics, arr[t * n_worlds + k] = world k's tick t"""
+        arr = (StepStats * (int(n) * self.n_worlds))()
+        _check(load_library().mgf_batch_step(self._h, float(dt), int(iters), int(n), arr))
+        return arr
+
+    def state(self, world=None):
+        """x, q, v, omega, delta of one world, or (world=None) of the whole batch, worlds concatenated in order"""
+        w = -1 if world is None else int(world)
+        n = max(load_library().mgf_batch_len(self._h, w), 0)
+        a = {k: np.empty((n, 4 if k == "q" else 3), np.float32) for k in ("x", "q", "v", "omega", "delta")}
+        _check(load_library().mgf_batch_read_state(self._h, w, a["x"].ctypes.data, a["q"].ctypes.data, a["v"].ctypes.data,
+                                                   a["omega"].ctypes.data, a["delta"].ctypes.data, n))
+        return a
+
+    def write_state(self, world, x=None, q=None, v=None, omega=None, delta=None):
+        """the given arrays of one world (None: of the whole batch); no other world is touched"""
+        w = -1 if world is None else int(world)
+        n = max(load_library().mgf_batch_len(self._h, w), 0)
+        keep = []
+
+        def p(a, k):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.float32).reshape(-1, k)
+            assert len(a) == n
+            keep.append(a)
+            return a.ctypes.data
+        _check(load_library().mgf_batch_write_state(self._h, w, p(x, 3), p(q, 4), p(v, 3), p(omega, 3), p(delta, 3), n))
+
+    def constraints(self, world):
+        cnt = C.c_int64()
+        _check(load_library().mgf_batch_read_constraints(self._h, int(world), None, 0, C.byref(cnt)))
+        out = np.zeros(cnt.value, CONSTRAINT_DTYPE)
+        _check(load_library().mgf_batch_read_constraints(self._h, int(world), out.ctypes.data, len(out), C.byref(cnt)))
+        return out
+
+    def counter(self, name):
+        v = C.c_int64()
+        _check(load_library().mgf_batch_counter(self._h, name.encode(), C.byref(v)))
+        return v.value
+
+    def set_option(self, key, value):
+        _check(load_library().mgf_batch_set_option(self._h, key.encode(), int(value)))
 
 
 def rccl_allow_override(allow=True):

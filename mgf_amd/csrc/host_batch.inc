@@ -1,0 +1,444 @@
+// mgf_batch_*: many small independent worlds, resident in HBM, stepped together - one launch per tick, a workgroup per world (k_batch.h).
+// Part of the single translation unit mgf_hip.hip (included there, in order); not compiled on its own.
+//
+// The bodies of all worlds sit in one set of arrays, world after world.  Bodies are added on the host side of a mirror of those arrays
+// (a world in the middle of the batch grows by insertion); the mirror goes up before the first call that needs the device and comes
+// back down if bodies are added after that.  Every world has a share of the candidate and of the constraint storage; a tick that needs
+// more than its share undoes itself on the device and is run again with more (counter "capacity_retries").
+
+struct mgf_batch {
+  mgf_ctx* ctx = nullptr;
+  mgf_params params;
+  uint32_t K = 0;
+  enum { AX, AQ, ASREC, ASP0, ASP1, ACTOR, AIMB, ADELTA, AFBC, AFBR, kArr };  // the persistent rows of Bodies (k_bodies.h), words of 16 bytes a body:
+  static constexpr int kWords[kArr] = {1, 1, 4, 1, 1, 1, 3, 1, 1, 1};
+  std::vector<float4> hm[kArr];
+  DBuf<float4> dm[kArr];
+  DBuf<float4> bpk, undo;          // the tick's packed copy (4 a body); what a tick that did not fit puts back (7 a body)
+  std::vector<uint32_t> h_n, h_off;  // bodies per world; their prefix sums (K + 1)
+  bool dev_valid = false;            // the device arrays hold the state (else the mirror does)
+  // the shared terrain
+  DBuf<float4> t_nodes, t_verts;
+  DBuf<uint4> t_faces;
+  uint32_t t_n_nodes = 0;
+  V3 t_x = mk3(0, 0, 0);
+  // constraint storage
+  std::vector<uint32_t> h_coff, h_cap, h_floor, h_qfloor, h_ccount;  // offsets / shares of the lists / the least a world has asked for (records, candidates) / length of the last tick's list
+  bool lists_valid = false;
+  DBuf<CRec> cons;
+  DBuf<float4> cont, slot;
+  DBuf<uint2> cand;
+  DBuf<uint32_t> rows, d_off, d_coff, d_cap, d_qoff, d_qcap, d_qcount, ncq, d_done, d_stage, d_need, d_ccount, d_err, d_stats, d_na, d_degb;
+  DBuf<float> pack;
+  int64_t cons_per_body = 4;  // option "cons_per_body": a world's first share of the constraint storage; of the candidate storage it gets four times that
+  int64_t capacity_retries = 0;
+  uint32_t lds_set = 0;
+
+  size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
+  Bodies bodies(size_t first) const {
+    Bodies B;
+    memset(&B, 0, sizeof(B));
+    B.x = dm[AX].p + first; B.q = dm[AQ].p + first; B.srec = dm[ASREC].p + 4 * first; B.sp0 = dm[ASP0].p + first; B.sp1 = dm[ASP1].p + first;
+    B.ctor = dm[ACTOR].p + first; B.imb = dm[AIMB].p + 3 * first; B.delta = dm[ADELTA].p + first; B.fb_c = dm[AFBC].p + first;
+    B.fb_r = dm[AFBR].p + first; B.bpk = bpk.p + 4 * first;
+    return B;
+  }
+};
+constexpr int mgf_batch::kWords[mgf_batch::kArr];
+
+static void batch_offsets(mgf_batch* b) {
+  b->h_off.assign(b->K + 1, 0u);
+  for (uint32_t k = 0; k < b->K; ++k) b->h_off[k + 1] = b->h_off[k] + b->h_n[k];
+}
+// the device arrays back into the mirror (bodies are being added behind a tick)
+static mgf_status batch_pull(mgf_batch* b) {
+  if (!b->dev_valid) return MGF_OK;
+  const size_t n = b->total();
+  for (int a = 0; a < mgf_batch::kArr; ++a) {
+    b->hm[a].resize(n * mgf_batch::kWords[a]);
+    MGF_TRY(d2h(b->ctx, b->hm[a].data(), b->dm[a].p, b->hm[a].size()));
+  }
+  b->dev_valid = false;
+  return MGF_OK;
+}
+// every world's share of the constraint storage; the lists of the last tick move along when `keep`
+static mgf_status batch_allot(mgf_batch* b, bool keep) {
+  mgf_ctx* ctx = b->ctx;
+  hipStream_t s = ctx->stream;
+  std::vector<uint32_t> coff(b->K + 1, 0u), cap(b->K), qoff(b->K + 1, 0u), qcap(b->K);
+  for (uint32_t k = 0; k < b->K; ++k) {
+    const uint64_t qwant = std::max<uint64_t>({64ull, 4ull * (uint64_t)b->cons_per_body * b->h_n[k], (uint64_t)b->h_qfloor[k]});
+    qcap[k] = (uint32_t)std::min<uint64_t>(qwant, 0x0FFFFFFFull);
+    if ((uint64_t)qoff[k] + qcap[k] > 0x7FFFFFF0ull) return fail(MGF_ERR_OOM, "the batch's candidate lists exceed 2^31 entries");
+    qoff[k + 1] = qoff[k] + qcap[k];
+    const uint64_t want = std::max<uint64_t>({16ull, (uint64_t)b->cons_per_body * b->h_n[k], (uint64_t)b->h_floor[k]});
+    cap[k] = (uint32_t)std::min<uint64_t>(want, 0x0FFFFFFFull);
+    if ((uint64_t)coff[k] + cap[k] > 0x7FFFFFF0ull) return fail(MGF_ERR_OOM, "the batch's constraint lists exceed 2^31 records");
+    coff[k + 1] = coff[k] + cap[k];
+  }
+  DBuf<CRec> ncons;
+  DBuf<uint32_t> ncoff;
+  MGF_TRY(ncons.ensure(std::max<size_t>(coff[b->K], 1), s));
+  MGF_TRY(ncoff.ensure(b->K + 1, s));
+  MGF_TRY(h2d(ctx, ncoff.p, coff.data(), coff.size()));
+  if (keep && b->lists_valid && b->K) {
+    k_batch_move_lists<<<b->K, kBatchBlock, 0, s>>>(b->cons.p, b->d_coff.p, ncons.p, ncoff.p, b->d_ccount.p);
+    LAUNCH_CHECK();
+    MGF_HIP_TRY(hipStreamSynchronize(s));
+  } else {
+    std::fill(b->h_ccount.begin(), b->h_ccount.end(), 0u);
+    MGF_TRY(b->d_ccount.ensure(std::max<size_t>(b->K, 1), s));
+    MGF_HIP_TRY(hipMemsetAsync(b->d_ccount.p, 0, 4 * (size_t)b->K, s));
+  }
+  std::swap(b->cons.p, ncons.p); std::swap(b->cons.cap, ncons.cap);
+  std::swap(b->d_coff.p, ncoff.p); std::swap(b->d_coff.cap, ncoff.cap);
+  MGF_TRY(b->rows.ensure(std::max<size_t>(coff[b->K], 1), s));
+  MGF_TRY(b->cont.ensure(4 * std::max<size_t>(coff[b->K], 1), s));
+  MGF_TRY(b->cand.ensure(std::max<size_t>(qoff[b->K], 1), s));
+  MGF_TRY(b->ncq.ensure(std::max<size_t>(qoff[b->K], 1), s)); MGF_TRY(b->slot.ensure(6 * std::max<size_t>(qoff[b->K], 1), s));
+  MGF_TRY(b->d_qoff.ensure(b->K + 1, s)); MGF_TRY(b->d_qcap.ensure(std::max<size_t>(b->K, 1), s)); MGF_TRY(b->d_qcount.ensure(std::max<size_t>(b->K, 1), s));
+  MGF_TRY(h2d(ctx, b->d_qoff.p, qoff.data(), qoff.size()));
+  MGF_TRY(h2d(ctx, b->d_qcap.p, qcap.data(), qcap.size()));
+  MGF_TRY(b->d_cap.ensure(std::max<size_t>(b->K, 1), s));
+  MGF_TRY(h2d(ctx, b->d_cap.p, cap.data(), cap.size()));
+  b->h_coff = coff; b->h_cap = cap;
+  b->lists_valid = true;
+  return MGF_OK;
+}
+// the mirror onto the device
+static mgf_status batch_push(mgf_batch* b) {
+  if (b->dev_valid) return MGF_OK;
+  mgf_ctx* ctx = b->ctx;
+  hipStream_t s = ctx->stream;
+  batch_offsets(b);
+  const size_t n = b->total();
+  for (int a = 0; a < mgf_batch::kArr; ++a) {
+    MGF_TRY(b->dm[a].ensure(std::max<size_t>(n * mgf_batch::kWords[a], 1), s));
+    MGF_TRY(h2d(ctx, b->dm[a].p, b->hm[a].data(), n * mgf_batch::kWords[a]));
+  }
+  MGF_TRY(b->bpk.ensure(std::max<size_t>(4 * n, 1), s));
+  MGF_TRY(b->undo.ensure(std::max<size_t>(7 * n, 1), s));
+  MGF_TRY(b->d_off.ensure(b->K + 1, s));
+  MGF_TRY(h2d(ctx, b->d_off.p, b->h_off.data(), b->h_off.size()));
+  MGF_TRY(b->d_na.ensure(std::max<size_t>(n, 1), s)); MGF_TRY(b->d_degb.ensure(std::max<size_t>(n, 1), s));
+  MGF_TRY(b->d_done.ensure(b->K, s)); MGF_TRY(b->d_stage.ensure(b->K, s)); MGF_TRY(b->d_need.ensure(2 * (size_t)b->K, s)); MGF_TRY(b->d_err.ensure(4, s));
+  MGF_HIP_TRY(hipMemsetAsync(b->d_err.p, 0, 16, s));
+  b->lists_valid = false;  // (the lists named the bodies of another layout)
+  MGF_TRY(batch_allot(b, false));
+  b->dev_valid = true;
+  return MGF_OK;
+}
+
+static mgf_status batch_bind(mgf_batch* b) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  return ctx_bind(b->ctx);
+}
+
+extern "C" mgf_status mgf_batch_new(mgf_ctx* ctx, const mgf_params* params, int64_t n_worlds, mgf_batch** out) {
+  if (!out) return fail(MGF_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (n_worlds <= 0 || n_worlds > (1 << 20)) return fail(MGF_ERR_INVALID, "n_worlds must be in 1 .. 2^20");
+  MGF_TRY(ctx_bind(ctx));
+  std::unique_ptr<mgf_batch> b(new mgf_batch());
+  b->ctx = ctx;
+  b->params = params ? *params : mgf_default_params();
+  b->K = (uint32_t)n_worlds;
+  b->h_n.assign(b->K, 0u); b->h_floor.assign(b->K, 0u); b->h_qfloor.assign(b->K, 0u); b->h_ccount.assign(b->K, 0u);
+  batch_offsets(b.get());
+  ctx_retain(ctx);
+  *out = b.release();
+  return MGF_OK;
+}
+extern "C" void mgf_batch_free(mgf_batch* b) {
+  if (!b) return;
+  mgf_ctx* ctx = b->ctx;
+  (void)hipSetDevice(ctx->device);
+  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  delete b;
+  ctx_release(ctx);
+}
+extern "C" int64_t mgf_batch_len(const mgf_batch* b, int64_t world) {
+  if (!b || world < -1 || world >= (int64_t)b->K) return -1;
+  if (world < 0) { int64_t t = 0; for (uint32_t n : b->h_n) t += n; return t; }
+  return b->h_n[(size_t)world];
+}
+extern "C" mgf_status mgf_batch_set_option(mgf_batch* b, const char* key, int64_t value) {
+  if (!b || !key) return fail(MGF_ERR_INVALID, "NULL argument");
+  if (!strcmp(key, "cons_per_body")) {
+    if (value < 1 || value > 4096) return fail(MGF_ERR_INVALID, "cons_per_body must be in 1 .. 4096");
+    MGF_TRY(ctx_bind(b->ctx));
+    b->cons_per_body = value;
+    std::fill(b->h_floor.begin(), b->h_floor.end(), 0u);
+    std::fill(b->h_qfloor.begin(), b->h_qfloor.end(), 0u);
+    if (b->dev_valid) { b->lists_valid = false; MGF_TRY(batch_allot(b, false)); }
+    return MGF_OK;
+  }
+  return fail(MGF_ERR_INVALID, "unknown batch option");
+}
+extern "C" mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out) {
+  if (!b || !name || !out) return fail(MGF_ERR_INVALID, "NULL argument");
+  if (!strcmp(name, "launches_per_tick")) { *out = 6; return MGF_OK; }
+  if (!strcmp(name, "capacity_retries")) { *out = b->capacity_retries; return MGF_OK; }
+  return fail(MGF_ERR_INVALID, "unknown batch counter");
+}
+
+// The mesh BVH in the order a query visits it, every node with the index of the first node behind its subtree (BatchTerrain, k_batch.h).
+static void batch_thread_tree(const HostBvh& t, uint64_t id, std::vector<float4>* out) {
+  const HostBvh::Node& n = t.node(id);
+  const size_t at = out->size() / 2;
+  out->push_back(make_float4(n.box.c.x, n.box.c.y, n.box.c.z, 0.0f));
+  out->push_back(make_float4(n.box.r.x, n.box.r.y, n.box.r.z, 0.0f));
+  uint32_t w0 = 0u;
+  if (n.leaf) w0 = 0x80000000u | (uint32_t)(n.value & 0x7fffffffu);
+  else { batch_thread_tree(t, n.kid[1], out); batch_thread_tree(t, n.kid[0], out); }  // (bvh.rs:283-310: the right child is popped first)
+  const uint32_t skip = (uint32_t)(out->size() / 2);
+  memcpy(&(*out)[2 * at].w, &w0, 4);
+  memcpy(&(*out)[2 * at + 1].w, &skip, 4);
+}
+extern "C" mgf_status mgf_batch_set_terrain(mgf_batch* b, const mgf_mesh* mesh) {
+  MGF_TRY(batch_bind(b));
+  if (!mesh || mesh->m.tree.empty()) { b->t_n_nodes = 0; return MGF_OK; }
+  hipStream_t s = b->ctx->stream;
+  std::vector<float4> nodes;
+  batch_thread_tree(mesh->m.tree, mesh->m.tree.root(), &nodes);
+  std::vector<float4> hv(mesh->verts.size());
+  for (size_t i = 0; i < hv.size(); ++i) hv[i] = make_float4(mesh->verts[i].x, mesh->verts[i].y, mesh->verts[i].z, 0.0f);
+  std::vector<uint4> hf(mesh->faces.size() / 3);
+  for (size_t i = 0; i < hf.size(); ++i) hf[i] = make_uint4(mesh->faces[3 * i], mesh->faces[3 * i + 1], mesh->faces[3 * i + 2], 0);
+  MGF_HIP_TRY(hipStreamSynchronize(s));
+  MGF_TRY(b->t_nodes.ensure(nodes.size(), s)); MGF_TRY(b->t_verts.ensure(std::max<size_t>(hv.size(), 1), s)); MGF_TRY(b->t_faces.ensure(std::max<size_t>(hf.size(), 1), s));
+  MGF_TRY(h2d(b->ctx, b->t_nodes.p, nodes.data(), nodes.size()));
+  MGF_TRY(h2d(b->ctx, b->t_verts.p, hv.data(), hv.size()));
+  MGF_TRY(h2d(b->ctx, b->t_faces.p, hf.data(), hf.size()));
+  b->t_n_nodes = (uint32_t)(nodes.size() / 2);
+  b->t_x = mesh->x;
+  return MGF_OK;
+}
+
+// RigidBodyVec::add_body physics.rs:200-218 + World::add_body world.rs:178-184 (initial fat AABB), as mgf_world_add_bodies, for one world of the batch.
+extern "C" mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mgf_component* comps, int64_t n, const float* mass, const float* restitution,
+                                           const float* friction, const mgf_vec3* world_force, uint64_t* first_id) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (n < 0) return fail(MGF_ERR_INVALID, "n is negative");
+  if (n && (!comps || !mass || !restitution || !friction || !world_force)) return fail(MGF_ERR_INVALID, "NULL argument");
+  if (world < 0) return fail(MGF_ERR_INVALID, "world index out of range");
+  if (n > MGF_BATCH_MAX_BODIES) return fail(MGF_ERR_INVALID, "a world of a batch holds at most MGF_BATCH_MAX_BODIES (1024) bodies");
+  for (int64_t i = 0; i < n; ++i) {
+    if (comps[i].tag != MGF_SPHERE && comps[i].tag != MGF_CAPSULE) return fail(MGF_ERR_INVALID, "component tag must be sphere (0) or capsule (1)");
+    if (!(comps[i].r > 0.0f)) return fail(MGF_ERR_INVALID, "radius must be > 0 (geom.rs:300,328)");
+  }
+  MGF_TRY(ctx_bind(b->ctx));
+  if (world >= (int64_t)b->K) return fail(MGF_ERR_INVALID, "world index out of range");
+  const uint32_t k = (uint32_t)world;
+  if ((int64_t)b->h_n[k] + n > MGF_BATCH_MAX_BODIES) return fail(MGF_ERR_INVALID, "a world of a batch holds at most MGF_BATCH_MAX_BODIES (1024) bodies: nothing was added");
+  if (first_id) *first_id = b->h_n[k];
+  if (n == 0) return MGF_OK;
+  const size_t N = (size_t)n;
+  std::vector<float4> add[mgf_batch::kArr];
+  for (int a = 0; a < mgf_batch::kArr; ++a) add[a].resize(N * mgf_batch::kWords[a]);
+  for (size_t i = 0; i < N; ++i) {
+    Comp c = comp_of(comps[i]);
+    if (c.kind == KIND_SPHERE) c.d = mk3(0, 0, 0);
+    // Component::deconstruct compound.rs:42-52
+    V3 px; Quat pq; float half_h = 0.0f;
+    if (c.kind == KIND_SPHERE) { px = c.p; pq = mkq(1.0f, mk3(0, 0, 0)); }
+    else {
+      const float h = mag(c.d);
+      pq = quat_from_arc(mk3(0.0f, 1.0f, 0.0f) * h, c.d);
+      px = c.p + c.d * 0.5f;
+      half_h = h * 0.5f;
+    }
+    Comp local = c; local.p = c.p + -px;  // collider - x.to_vec()
+    M3 inv;
+    if (!invert(tensor_of(local, mass[i]), &inv)) return fail(MGF_ERR_SINGULAR, "inertia tensor is not invertible (physics.rs:212)");
+    const float inv_mass = 1.0f / mass[i];
+    const V3 force = mk3(world_force[i].x, world_force[i].y, world_force[i].z) * mass[i];
+    add[mgf_batch::AX][i] = make_float4(px.x, px.y, px.z, 0.0f);
+    add[mgf_batch::AQ][i] = make_float4(pq.s, pq.v.x, pq.v.y, pq.v.z);
+    float4* sr = &add[mgf_batch::ASREC][4 * i];
+    sr[0] = make_float4(0, 0, 0, 0);
+    sr[1] = make_float4(0, 0, inv_mass, inv.c[0].x);
+    sr[2] = make_float4(inv.c[0].y, inv.c[0].z, inv.c[1].x, inv.c[1].y);
+    sr[3] = make_float4(inv.c[1].z, inv.c[2].x, inv.c[2].y, inv.c[2].z);
+    add[mgf_batch::ASP0][i] = make_float4(force.x, force.y, force.z, restitution[i]);
+    add[mgf_batch::ASP1][i] = make_float4(0, 0, 0, friction[i]);
+    const uint32_t kind_bits = (uint32_t)c.kind;
+    float kf; memcpy(&kf, &kind_bits, 4);
+    add[mgf_batch::ACTOR][i] = make_float4(kf, c.r, half_h, 0.0f);
+    for (int col = 0; col < 3; ++col) add[mgf_batch::AIMB][3 * i + col] = make_float4(inv.c[col].x, inv.c[col].y, inv.c[col].z, 0.0f);
+    add[mgf_batch::ADELTA][i] = make_float4(0, 0, 0, friction[i]);
+    const Box tb = swept_bounds(c, mk3(0, 0, 0));
+    const V3 fr = tb.r + mk3(b->params.fat_margin, b->params.fat_margin, b->params.fat_margin);
+    add[mgf_batch::AFBC][i] = make_float4(tb.c.x, tb.c.y, tb.c.z, 0.0f);
+    add[mgf_batch::AFBR][i] = make_float4(fr.x, fr.y, fr.z, 0.0f);
+  }
+  MGF_TRY(batch_pull(b));
+  const size_t at = b->h_off[k + 1];  // behind the world's last body
+  for (int a = 0; a < mgf_batch::kArr; ++a) b->hm[a].insert(b->hm[a].begin() + at * mgf_batch::kWords[a], add[a].begin(), add[a].end());
+  b->h_n[k] += (uint32_t)n;
+  batch_offsets(b);
+  std::fill(b->h_ccount.begin(), b->h_ccount.end(), 0u);
+  return MGF_OK;
+}
+
+static mgf_status batch_range(mgf_batch* b, int64_t world, size_t* first, size_t* n) {
+  if (world < -1 || world >= (int64_t)b->K) return fail(MGF_ERR_INVALID, "world index out of range");
+  *first = world < 0 ? 0 : b->h_off[(size_t)world];
+  *n = world < 0 ? b->total() : b->h_n[(size_t)world];
+  return MGF_OK;
+}
+// As mgf_world_read_state / mgf_world_write_state for one world, or (world = -1) for all bodies of the batch, worlds concatenated in order.
+extern "C" mgf_status mgf_batch_read_state(mgf_batch* b, int64_t world, mgf_vec3* x, mgf_quat* q, mgf_vec3* v, mgf_vec3* omega, mgf_vec3* delta, int64_t cap) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (world < -1) return fail(MGF_ERR_INVALID, "world index out of range");
+  MGF_TRY(ctx_bind(b->ctx));
+  size_t first, n;
+  MGF_TRY(batch_range(b, world, &first, &n));
+  if ((int64_t)n > cap) return fail(MGF_ERR_CAPACITY, "state buffers too small");
+  if (n == 0) return MGF_OK;
+  MGF_TRY(batch_push(b));
+  hipStream_t s = b->ctx->stream;
+  const size_t fl[5] = {x ? 3 * n : 0, q ? 4 * n : 0, v ? 3 * n : 0, omega ? 3 * n : 0, delta ? 3 * n : 0};
+  size_t off[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = 0; k < 5; ++k) off[k + 1] = off[k] + ((fl[k] + 3) & ~(size_t)3);  // (every section 16-byte aligned: q goes out as float4)
+  if (off[5] == 0) return MGF_OK;
+  MGF_TRY(b->pack.ensure(off[5], s));
+  float* P = b->pack.p;
+  k_pack_state<<<nblk(n), kBlock, 0, s>>>(b->bodies(first), (uint32_t)n, nullptr, x ? P + off[0] : nullptr, q ? P + off[1] : nullptr, v ? P + off[2] : nullptr,
+                                          omega ? P + off[3] : nullptr, delta ? P + off[4] : nullptr);
+  LAUNCH_CHECK();
+  void* dst[5] = {x, q, v, omega, delta};
+  for (int k = 0; k < 5; ++k)
+    if (fl[k]) MGF_HIP_TRY(hipMemcpyAsync(dst[k], P + off[k], 4 * fl[k], hipMemcpyDeviceToHost, s));
+  MGF_HIP_TRY(hipStreamSynchronize(s));
+  return MGF_OK;
+}
+extern "C" mgf_status mgf_batch_write_state(mgf_batch* b, int64_t world, const mgf_vec3* x, const mgf_quat* q, const mgf_vec3* v, const mgf_vec3* omega,
+                                            const mgf_vec3* delta, int64_t n_in) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (world < -1) return fail(MGF_ERR_INVALID, "world index out of range");
+  if (n_in < 0) return fail(MGF_ERR_INVALID, "n is negative");
+  MGF_TRY(ctx_bind(b->ctx));
+  size_t first, n;
+  MGF_TRY(batch_range(b, world, &first, &n));
+  if ((size_t)n_in != n) return fail(MGF_ERR_INVALID, "n must equal the number of bodies");
+  if (n == 0) return MGF_OK;
+  MGF_TRY(batch_push(b));
+  hipStream_t s = b->ctx->stream;
+  const size_t fl[5] = {x ? 3 * n : 0, q ? 4 * n : 0, v ? 3 * n : 0, omega ? 3 * n : 0, delta ? 3 * n : 0};
+  size_t off[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = 0; k < 5; ++k) off[k + 1] = off[k] + ((fl[k] + 3) & ~(size_t)3);
+  if (off[5] == 0) return MGF_OK;
+  MGF_TRY(b->pack.ensure(off[5], s));
+  float* P = b->pack.p;
+  const void* src[5] = {x, q, v, omega, delta};
+  for (int k = 0; k < 5; ++k)
+    if (fl[k]) MGF_HIP_TRY(hipMemcpyAsync(P + off[k], src[k], 4 * fl[k], hipMemcpyHostToDevice, s));
+  k_unpack_state<<<nblk(n), kBlock, 0, s>>>(b->bodies(first), (uint32_t)n, nullptr, x ? P + off[0] : nullptr, q ? P + off[1] : nullptr, v ? P + off[2] : nullptr,
+                                            omega ? P + off[3] : nullptr, delta ? P + off[4] : nullptr);
+  LAUNCH_CHECK();
+  MGF_HIP_TRY(hipStreamSynchronize(s));
+  return MGF_OK;
+}
+
+// n_ticks x World::step (world.rs:227-294) of every world: one launch per tick, no host wait between the ticks.
+extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (n_ticks < 0) return fail(MGF_ERR_INVALID, "n_ticks is negative");
+  if (iters < 0) return fail(MGF_ERR_INVALID, "iters is negative");
+  if (n_ticks > (1 << 20)) return fail(MGF_ERR_INVALID, "n_ticks must be at most 2^20");
+  MGF_TRY(ctx_bind(b->ctx));
+  MGF_TRY(batch_push(b));
+  if (n_ticks == 0) return MGF_OK;
+  mgf_ctx* ctx = b->ctx;
+  hipStream_t s = ctx->stream;
+  const uint32_t K = b->K, NT = (uint32_t)n_ticks;
+  uint32_t nmax = 0;
+  for (uint32_t n : b->h_n) nmax = std::max(nmax, n);
+  const uint32_t lds = 80u * nmax;  // k_batch_solve: 64 bytes a body of solver records, four words of counts (k_batch_front: 64 + 4, k_batch_setup: 12)
+  if (lds > b->lds_set) {
+    MGF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch_front), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(68u * MGF_BATCH_MAX_BODIES)));
+    MGF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(80u * MGF_BATCH_MAX_BODIES)));
+    b->lds_set = 80u * MGF_BATCH_MAX_BODIES;
+  }
+  MGF_TRY(b->d_stats.ensure((size_t)NT * K * 8, s));
+  MGF_HIP_TRY(hipMemsetAsync(b->d_done.p, 0, 4 * (size_t)K, s));
+  MGF_HIP_TRY(hipMemsetAsync(b->d_need.p, 0, 8 * (size_t)K, s));
+  MGF_HIP_TRY(hipMemsetAsync(b->d_stage.p, 0, 4 * (size_t)K, s));
+  std::vector<uint32_t> done(K), need(2 * (size_t)K);
+  for (uint32_t first = 0; first < NT;) {
+    BatchArgs A;
+    memset(&A, 0, sizeof(A));
+    A.B = b->bodies(0);
+    float4* u = b->undo.p;
+    const size_t n = b->total();
+    A.U.p = u; A.U.n = (uint32_t)n;
+    A.M.nodes = b->t_nodes.p; A.M.verts = b->t_verts.p; A.M.faces = b->t_faces.p; A.M.n_nodes = b->t_n_nodes;
+    A.M.x[0] = b->t_x.x; A.M.x[1] = b->t_x.y; A.M.x[2] = b->t_x.z;
+    A.w_off = b->d_off.p; A.cons = b->cons.p; A.rows = b->rows.p; A.c_off = b->d_coff.p; A.c_cap = b->d_cap.p;
+    A.cand = b->cand.p; A.q_off = b->d_qoff.p; A.q_cap = b->d_qcap.p; A.q_count = b->d_qcount.p; A.cont = b->cont.p; A.ncq = b->ncq.p; A.slot = b->slot.p;
+    A.na = b->d_na.p; A.degb = b->d_degb.p; A.stage = b->d_stage.p;
+    A.done = b->d_done.p; A.need = b->d_need.p; A.c_count = b->d_ccount.p; A.err = b->d_err.p; A.stats = b->d_stats.p;
+    A.n_worlds = K; A.iters = (uint32_t)iters;
+    A.dt = dt; A.fat_margin = b->params.fat_margin; A.baumgarte = b->params.baumgarte; A.slop = b->params.penetration_slop;
+    for (uint32_t t = first; t < NT; ++t) {
+      A.tick = t;
+      k_batch_front<<<K, kBatchBlock, 68u * nmax, s>>>(A);
+      LAUNCH_CHECK();
+      k_batch_faces<<<K, kBatchBlock, 0, s>>>(A);
+      LAUNCH_CHECK();
+      k_batch_pairs<<<K, kBatchBlock, 0, s>>>(A);
+      LAUNCH_CHECK();
+      k_batch_pack<<<K, kBatchBlock, 0, s>>>(A);
+      LAUNCH_CHECK();
+      k_batch_setup<<<K, kBatchBlock, 12u * nmax, s>>>(A);
+      LAUNCH_CHECK();
+      k_batch_solve<<<K, kBatchBlock, lds, s>>>(A);
+      LAUNCH_CHECK();
+    }
+    MGF_TRY(d2h(ctx, done.data(), b->d_done.p, K));
+    uint32_t err = 0;
+    MGF_TRY(d2h(ctx, &err, b->d_err.p, 1));
+    if (err) return fail(MGF_ERR_HIP, "internal error: a lane of the batch solver gave up waiting for its turn");
+    first = *std::min_element(done.begin(), done.end());
+    if (first >= NT) break;
+    // Solver::solve and World::step have no capacity failure (solver.rs:72-78): the worlds whose tick did not fit get what it asked for, and half again
+    MGF_TRY(d2h(ctx, need.data(), b->d_need.p, 2 * (size_t)K));
+    for (uint32_t k = 0; k < K; ++k) {
+      b->h_qfloor[k] = std::max(b->h_qfloor[k], need[2 * k] + need[2 * k] / 2);
+      b->h_floor[k] = std::max(b->h_floor[k], need[2 * k + 1] + need[2 * k + 1] / 2);
+    }
+    MGF_HIP_TRY(hipMemsetAsync(b->d_need.p, 0, 8 * (size_t)K, s));
+    ++b->capacity_retries;
+    MGF_TRY(batch_allot(b, true));
+  }
+  MGF_TRY(d2h(ctx, b->h_ccount.data(), b->d_ccount.p, K));
+  if (stats) {
+    std::vector<uint32_t> h((size_t)NT * K * 8);
+    MGF_TRY(d2h(ctx, h.data(), b->d_stats.p, h.size()));
+    for (size_t r = 0; r < (size_t)NT * K; ++r) {
+      mgf_step_stats& o = stats[r];
+      memset(&o, 0, sizeof(o));
+      o.n_bodies = h[8 * r]; o.n_constraints = h[8 * r + 1]; o.n_terrain_constraints = h[8 * r + 2]; o.n_pair_candidates = h[8 * r + 3];
+      o.n_refits = h[8 * r + 4]; o.iters = (uint32_t)iters;
+    }
+  }
+  return MGF_OK;
+}
+
+// The Solver's constraint list of world `world`'s last tick, in insertion order (bodies named by their index in the world).
+extern "C" mgf_status mgf_batch_read_constraints(mgf_batch* b, int64_t world, mgf_constraint* out, int64_t cap, int64_t* count) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (world < 0) return fail(MGF_ERR_INVALID, "world index out of range");
+  MGF_TRY(ctx_bind(b->ctx));
+  if (world >= (int64_t)b->K) return fail(MGF_ERR_INVALID, "world index out of range");
+  const uint32_t C = b->dev_valid ? b->h_ccount[(size_t)world] : 0u;
+  if (count) *count = C;
+  if (!out) return MGF_OK;
+  if ((int64_t)C > cap) return fail(MGF_ERR_CAPACITY, "constraint buffer too small");
+  if (C == 0) return MGF_OK;
+  std::vector<CRec> h(C);
+  MGF_TRY(d2h(b->ctx, h.data(), b->cons.p + b->h_coff[(size_t)world], C));
+  for (uint32_t i = 0; i < C; ++i) crec_to_public(h[i], &out[i]);
+  return MGF_OK;
+}

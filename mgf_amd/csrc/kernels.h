@@ -73,6 +73,10 @@
 //                      tile's tick changes, kept for the retry of a tick in which a persistent launch gave up
 //   k_compound_* / k_bvh_raytrace / k_intersections_batch
 //                      Compound (compound.rs:230-352), BVH::raytrace and Intersects (bvh.rs:345-369, collision.rs:169-373)
+//   k_batch_front / _faces / _pairs / _pack / _setup / _solve (k_batch.h)
+//                      a batch of small independent worlds (mgf_batch_*): the whole tick of one world by one workgroup per launch - integrate,
+//                      the boxes and the pair search in LDS, the tests, the constraint records, Solver::solve with the bodies' records and
+//                      progress counters in LDS
 //   k_query_* (k_query.h) ray casts and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid of
 //                      the bodies' current tight boxes built per call (never the tick's lists)
 //
@@ -83,3 +87,4 @@
 //   k_bodies.h -> k_broadphase.h -> k_contacts.h -> k_front_rows.h -> k_links.h -> k_solver_flow.h -> k_tiles.h -> k_api.h
 #include "k_api.h"
 #include "k_query.h"  // the world queries between ticks (k_query_*), beside the tick
+#include "k_batch.h"  // many small worlds, a workgroup each (k_batch_*), beside the one-world tick

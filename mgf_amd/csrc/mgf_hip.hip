@@ -154,3 +154,4 @@ extern "C" mgf_status mgf_exclusive_scan_u32(mgf_ctx* ctx, const uint32_t* in, i
 #include "host_boundary.inc"
 #include "host_tiles_native.inc"
 #include "host_query.inc"
+#include "host_batch.inc"
