@@ -555,7 +555,7 @@ MGF_API mgf_status mgf_world_release_device_ptrs(mgf_world* w);
  * LIMITS: bodies of one component (spheres and capsules); at most MGF_BATCH_MAX_BODIES bodies per world (a call that would exceed it
  * is refused with MGF_ERR_INVALID and adds nothing); one terrain mesh shared by every world (copied, its position included; NULL =
  * none); canonical constraint order only.  There are no bodies of several components, no obstacles, no ghosts or tiles, no
- * constraint_order = demo, no queries: a batch has no entry point for them.  A tick never fails for list sizes: a world whose
+ * constraint_order = demo and no box-overlap query: a batch has no entry point for them.  A tick never fails for list sizes: a world whose
  * constraints outgrow its share of the storage gets its tick undone on the device and run again with more (Solver::solve and
  * World::step have no capacity failure, solver.rs:72-78); mgf_batch_counter "capacity_retries" counts those re-runs.
  * Calls are synchronous on the context's stream; the handle keeps a reference on the context; there is no CPU fallback. */
@@ -580,7 +580,37 @@ MGF_API mgf_status mgf_batch_write_state(mgf_batch* b, int64_t world, const mgf_
                                          const mgf_vec3* delta, int64_t n);
 /* The Solver's constraint list (solver.rs:53-79) of world `world`'s last tick, in insertion order; bodies by their index within the world. */
 MGF_API mgf_status mgf_batch_read_constraints(mgf_batch* b, int64_t world, mgf_constraint* out, int64_t cap, int64_t* count);
-/* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: it does not grow with n_worlds), "capacity_retries"}. */
+/* ---- queries against the worlds of a batch, between ticks.  The definition is the lone world's ("queries against the world between
+ * ticks", above): out[i] is, bit for bit, what mgf_world_raycast_many / mgf_world_sweep_many reports for query i on a lone mgf_world
+ * that holds world world[i]'s bodies and the batch's terrain and has been through the same calls.
+ *   Ray cast: the closest hit of Intersects<shape> (collision.rs:169-373; compound.rs:150 for a component), the smallest t, ties to the
+ *   target first in the order bodies (ascending index), terrain faces (ascending index); a particle with d = 0 hits nothing.
+ *   Sweep: the earliest contact of Contacts<Moving<Sphere | Capsule>> of a body's sphere or capsule (collision.rs:1089-1356; :1143
+ *   through commute_contacts!) and of Contacts<Moving<_>> for Poly of each face (collision.rs:610-1000, up to two contacts for a
+ *   capsule), the least (t, kind, index, part, order emitted within the target); a contact whose t is not finite is not a candidate
+ *   (collision.rs:693-1086); a capsule cast with delta = 0 tests every face (:901-1060), a capsule reaches max(1, |d|) (:698-719);
+ *   delta = 0 is a valid cast (sphere on sphere with equal centres reports nothing, :1097-1100).
+ * index is the body's index within its world, or the face index; part is 0.  ignore_body: NULL, or n indices within world world[i]
+ * (-1: none).  kinds_mask: MGF_QUERY_* bits; 0 or a bit beyond MGF_QUERY_ALL is refused; MGF_QUERY_OBSTACLES is accepted and matches
+ * nothing (a batch has no obstacles), so MGF_QUERY_ALL means what it means for a lone world without obstacles.
+ * The collider a query sees is the one the world's query would see: the one the last tick built (physics.rs:243-251); for a body no
+ * tick has touched, the component it was added as; mgf_batch_write_state does not move it, as mgf_world_write_state does not.
+ * mgf_batch_read_colliders returns exactly that collider with the body's current delta (colliders() physics.rs:256).
+ * Refused with MGF_ERR_INVALID, nothing computed: a NULL batch, NULL arrays with n > 0, a negative n, a cast tag other than 0 or 1, a
+ * world index < 0 or >= n_worlds, n > INT32_MAX.
+ * out[i] depends on nothing but query i and world world[i] - not on the other queries, their order, or what else the batch holds.  A
+ * query touches nothing of the tick's state: a step after a query is bit-identical to one without it.  The number of kernel launches
+ * of a call depends on neither n_worlds nor n (mgf_batch_counter "query_launches"). */
+/* As mgf_world_read_colliders for world `world`, or for world = -1 the whole batch, worlds concatenated in order. */
+MGF_API mgf_status mgf_batch_read_colliders(mgf_batch* b, int64_t world, mgf_moving_component* out, int64_t cap);
+/* n queries, query i against world world[i] (any order, any mix; a world may get none). */
+MGF_API mgf_status mgf_batch_raycast_many(mgf_batch* b, const int32_t* world, const mgf_particle* parts, int64_t n,
+                                          const int32_t* ignore_body, int32_t kinds_mask, mgf_ray_hit* out);
+MGF_API mgf_status mgf_batch_sweep_many(mgf_batch* b, const int32_t* world, const mgf_moving_component* casts, int64_t n,
+                                        const int32_t* ignore_body, int32_t kinds_mask, mgf_sweep_hit* out);
+/* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: it does not grow with n_worlds), "capacity_retries",
+ * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
+ * the last query call's kernels, as mgf_world_counter's)}. */
 MGF_API mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out);
 /* Options (test knobs): "cons_per_body" [4] = the constraint records per body a world's share of the storage starts with (1 .. 4096); a
  * low value makes the first busy tick outgrow it, which the re-run path then handles. */

@@ -144,6 +144,7 @@ SYMBOLS = [
     "mgf_tiles_migrated", "mgf_tiles_set_option", "mgf_world_add_obstacle", "mgf_tiles_counter",
     "mgf_batch_new", "mgf_batch_free", "mgf_batch_set_terrain", "mgf_batch_add_bodies", "mgf_batch_len", "mgf_batch_step",
     "mgf_batch_read_state", "mgf_batch_write_state", "mgf_batch_read_constraints", "mgf_batch_counter", "mgf_batch_set_option",
+    "mgf_batch_read_colliders", "mgf_batch_raycast_many", "mgf_batch_sweep_many",
 ]
 
 _lib = None
@@ -287,6 +288,9 @@ def load_library():
         "mgf_batch_read_constraints": (i32, [vp, i64, vp, i64, P(i64)]),
         "mgf_batch_counter": (i32, [vp, C.c_char_p, P(i64)]),
         "mgf_batch_set_option": (i32, [vp, C.c_char_p, i64]),
+        "mgf_batch_read_colliders": (i32, [vp, i64, vp, i64]),
+        "mgf_batch_raycast_many": (i32, [vp, vp, vp, i64, vp, i32, vp]),
+        "mgf_batch_sweep_many": (i32, [vp, vp, vp, i64, vp, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1249,6 +1253,56 @@ class WorldBatch:
         _check(load_library().mgf_batch_read_constraints(self._h, int(world), None, 0, C.byref(cnt)))
         out = np.zeros(cnt.value, CONSTRAINT_DTYPE)
         _check(load_library().mgf_batch_read_constraints(self._h, int(world), out.ctypes.data, len(out), C.byref(cnt)))
+        return out
+
+    def colliders(self, world=None):
+        """the collider a query sees and the body's delta (MOVING_DTYPE) of one world, or (world=None) of the whole batch"""
+        w = -1 if world is None else int(world)
+        out = np.zeros(max(load_library().mgf_batch_len(self._h, w), 0), MOVING_DTYPE)
+        _check(load_library().mgf_batch_read_colliders(self._h, w, out.ctypes.data, len(out)))
+        return out
+
+    def raycast(self, world, p, d, dt=float("inf"), ignore=None, kinds=QUERY_ALL):
+        """As World.raycast, particle i against world[i] (a scalar: all against that world) of the batch (mgf_batch_raycast_many): a
+        RAY_HIT_DTYPE array; index and ignore are body indices within the particle's world."""
+        p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(np.broadcast_to(np.asarray(d, np.float32), p.shape))
+        n = len(p)
+        parts = np.empty((n, 7), np.float32)
+        parts[:, 0:3] = p
+        parts[:, 3:6] = d
+        parts[:, 6] = np.broadcast_to(np.asarray(dt, np.float32), (n,))
+        wd = np.ascontiguousarray(np.broadcast_to(np.asarray(world, np.int32), (n,)))
+        ign = None
+        if ignore is not None:
+            ign = np.ascontiguousarray(np.broadcast_to(np.asarray(ignore, np.int32), (n,)))
+        out = np.zeros(n, RAY_HIT_DTYPE)
+        _check(load_library().mgf_batch_raycast_many(self._h, wd.ctypes.data, parts.ctypes.data, n, ign.ctypes.data if ign is not None else None,
+                                                     int(kinds), out.ctypes.data))
+        return out
+
+    def sweep(self, world, comps, delta=None, ignore=None, kinds=QUERY_ALL):
+        """As World.sweep, cast i against world[i] (a scalar: all against that world) of the batch (mgf_batch_sweep_many): a
+        SWEEP_HIT_DTYPE array; index and ignore are body indices within the cast's world."""
+        comps = np.asarray(comps)
+        if comps.dtype == MOVING_DTYPE:
+            if delta is not None:
+                raise ValueError("a MOVING_DTYPE array carries its own delta")
+            casts = np.ascontiguousarray(comps.reshape(-1))
+        else:
+            comps = np.asarray(comps, COMPONENT_DTYPE).reshape(-1)
+            casts = np.zeros(len(comps), MOVING_DTYPE)
+            for k in ("tag", "p", "d", "r"):
+                casts[k] = comps[k]
+            casts["delta"] = np.broadcast_to(np.asarray(0.0 if delta is None else delta, np.float32), (len(comps), 3))
+        n = len(casts)
+        wd = np.ascontiguousarray(np.broadcast_to(np.asarray(world, np.int32), (n,)))
+        ign = None
+        if ignore is not None:
+            ign = np.ascontiguousarray(np.broadcast_to(np.asarray(ignore, np.int32), (n,)))
+        out = np.zeros(n, SWEEP_HIT_DTYPE)
+        _check(load_library().mgf_batch_sweep_many(self._h, wd.ctypes.data, casts.ctypes.data, n, ign.ctypes.data if ign is not None else None,
+                                                   int(kinds), out.ctypes.data))
         return out
 
     def counter(self, name):

@@ -10,8 +10,8 @@ struct mgf_batch {
   mgf_ctx* ctx = nullptr;
   mgf_params params;
   uint32_t K = 0;
-  enum { AX, AQ, ASREC, ASP0, ASP1, ACTOR, AIMB, ADELTA, AFBC, AFBR, kArr };  // the persistent rows of Bodies (k_bodies.h), words of 16 bytes a body:
-  static constexpr int kWords[kArr] = {1, 1, 4, 1, 1, 1, 3, 1, 1, 1};
+  enum { AX, AQ, ASREC, ASP0, ASP1, ACTOR, AIMB, ADELTA, AFBC, AFBR, ACOL0, ACOL1, kArr };  // the persistent rows of Bodies (k_bodies.h), words of 16 bytes a body:
+  static constexpr int kWords[kArr] = {1, 1, 4, 1, 1, 1, 3, 1, 1, 1, 1, 1};
   std::vector<float4> hm[kArr];
   DBuf<float4> dm[kArr];
   DBuf<float4> bpk, undo;          // the tick's packed copy (4 a body); what a tick that did not fit puts back (7 a body)
@@ -33,6 +33,15 @@ struct mgf_batch {
   int64_t cons_per_body = 4;  // option "cons_per_body": a world's first share of the constraint storage; of the candidate storage it gets four times that
   int64_t capacity_retries = 0;
   uint32_t lds_set = 0;
+  // the queries (host_batch_query.inc).  col0 / col1 are the collider a query sees: the component a body was added as until a tick has run
+  // on it, then what that tick built - gathered from bpk by one launch before the first reader behind a mgf_batch_step (cols_stale)
+  bool cols_stale = false;
+  DBuf<float4> q_in;
+  DBuf<int32_t> q_out;
+  hipEvent_t q_ev[2] = {nullptr, nullptr};
+  int64_t q_launches = 0;
+  float q_run_ms = 0.0f;
+  ~mgf_batch() { for (hipEvent_t e : q_ev) if (e) (void)hipEventDestroy(e); }
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {
@@ -40,7 +49,7 @@ struct mgf_batch {
     memset(&B, 0, sizeof(B));
     B.x = dm[AX].p + first; B.q = dm[AQ].p + first; B.srec = dm[ASREC].p + 4 * first; B.sp0 = dm[ASP0].p + first; B.sp1 = dm[ASP1].p + first;
     B.ctor = dm[ACTOR].p + first; B.imb = dm[AIMB].p + 3 * first; B.delta = dm[ADELTA].p + first; B.fb_c = dm[AFBC].p + first;
-    B.fb_r = dm[AFBR].p + first; B.bpk = bpk.p + 4 * first;
+    B.fb_r = dm[AFBR].p + first; B.col0 = dm[ACOL0].p + first; B.col1 = dm[ACOL1].p + first; B.bpk = bpk.p + 4 * first;
     return B;
   }
 };
@@ -50,9 +59,24 @@ static void batch_offsets(mgf_batch* b) {
   b->h_off.assign(b->K + 1, 0u);
   for (uint32_t k = 0; k < b->K; ++k) b->h_off[k + 1] = b->h_off[k] + b->h_n[k];
 }
+// col0 / col1 of the bodies the last mgf_batch_step ran on: every world has completed every tick of the call (a tick that was undone was
+// run again before the call returned), so bpk words 0 and 3 are their colliders.  The launches that follow on the stream see the rows.
+static mgf_status batch_cols_refresh(mgf_batch* b, int64_t* launches) {
+  if (!b->cols_stale || !b->dev_valid) return MGF_OK;
+  const size_t n = b->total();
+  if (n) {
+    k_batch_query_gather<<<(unsigned)((n + kBatchBlock - 1) / kBatchBlock), kBatchBlock, 0, b->ctx->stream>>>(b->bpk.p, b->dm[mgf_batch::ACOL0].p,
+                                                                                                       b->dm[mgf_batch::ACOL1].p, (uint32_t)n);
+    LAUNCH_CHECK();
+    if (launches) ++*launches;
+  }
+  b->cols_stale = false;
+  return MGF_OK;
+}
 // the device arrays back into the mirror (bodies are being added behind a tick)
 static mgf_status batch_pull(mgf_batch* b) {
   if (!b->dev_valid) return MGF_OK;
+  MGF_TRY(batch_cols_refresh(b, nullptr));
   const size_t n = b->total();
   for (int a = 0; a < mgf_batch::kArr; ++a) {
     b->hm[a].resize(n * mgf_batch::kWords[a]);
@@ -179,6 +203,8 @@ extern "C" mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, in
   if (!b || !name || !out) return fail(MGF_ERR_INVALID, "NULL argument");
   if (!strcmp(name, "launches_per_tick")) { *out = 6; return MGF_OK; }
   if (!strcmp(name, "capacity_retries")) { *out = b->capacity_retries; return MGF_OK; }
+  if (!strcmp(name, "query_launches")) { *out = b->q_launches; return MGF_OK; }
+  if (!strcmp(name, "query_run_ns")) { *out = (int64_t)((double)b->q_run_ms * 1e6); return MGF_OK; }
   return fail(MGF_ERR_INVALID, "unknown batch counter");
 }
 
@@ -271,6 +297,8 @@ extern "C" mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mg
     const V3 fr = tb.r + mk3(b->params.fat_margin, b->params.fat_margin, b->params.fat_margin);
     add[mgf_batch::AFBC][i] = make_float4(tb.c.x, tb.c.y, tb.c.z, 0.0f);
     add[mgf_batch::AFBR][i] = make_float4(fr.x, fr.y, fr.z, 0.0f);
+    add[mgf_batch::ACOL0][i] = make_float4(c.p.x, c.p.y, c.p.z, c.r);  // (what a query sees until a tick has run on the body)
+    add[mgf_batch::ACOL1][i] = make_float4(c.d.x, c.d.y, c.d.z, kf);
   }
   MGF_TRY(batch_pull(b));
   const size_t at = b->h_off[k + 1];  // behind the world's last body
@@ -362,6 +390,7 @@ extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int6
     b->lds_set = 80u * MGF_BATCH_MAX_BODIES;
   }
   MGF_TRY(b->d_stats.ensure((size_t)NT * K * 8, s));
+  b->cols_stale = true;  // (the tick's six launches stay as they are: the colliders are gathered before the first reader)
   MGF_HIP_TRY(hipMemsetAsync(b->d_done.p, 0, 4 * (size_t)K, s));
   MGF_HIP_TRY(hipMemsetAsync(b->d_need.p, 0, 8 * (size_t)K, s));
   MGF_HIP_TRY(hipMemsetAsync(b->d_stage.p, 0, 4 * (size_t)K, s));

@@ -1,0 +1,135 @@
+// mgf_batch_read_colliders, mgf_batch_raycast_many, mgf_batch_sweep_many: the queries of host_query.inc for the worlds of a batch
+// (k_batch_query.h).  Part of the single translation unit mgf_hip.hip (included there, in order); not compiled on its own.
+//
+// A call sorts its query indices by world (one stable counting sort), cuts every world's run into work items of up to 256 queries,
+// uploads items, queries, order and ignore list in ONE copy, launches a workgroup per work item - the number of launches depends on
+// neither the number of worlds nor the number of queries - and downloads the hits: one host wait per call.  Nothing of the tick's state
+// is written; of it only bpk is read, once, by the collider gather behind a mgf_batch_step (batch_cols_refresh).
+
+extern "C" mgf_status mgf_batch_read_colliders(mgf_batch* b, int64_t world, mgf_moving_component* out, int64_t cap) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (!out) return fail(MGF_ERR_INVALID, "NULL argument");
+  if (world < -1) return fail(MGF_ERR_INVALID, "world index out of range");
+  MGF_TRY(ctx_bind(b->ctx));
+  size_t first, n;
+  MGF_TRY(batch_range(b, world, &first, &n));
+  if ((int64_t)n > cap) return fail(MGF_ERR_CAPACITY, "buffer too small");
+  if (n == 0) return MGF_OK;
+  MGF_TRY(batch_push(b));
+  MGF_TRY(batch_cols_refresh(b, nullptr));
+  hipStream_t s = b->ctx->stream;
+  MGF_TRY(b->pack.ensure(11 * n, s));
+  k_pack_colliders<<<nblk(n), kBlock, 0, s>>>(b->bodies(first), (uint32_t)n, nullptr, reinterpret_cast<uint32_t*>(b->pack.p));
+  LAUNCH_CHECK();
+  MGF_HIP_TRY(hipMemcpyAsync(out, b->pack.p, 44 * n, hipMemcpyDeviceToHost, s));
+  MGF_HIP_TRY(hipStreamSynchronize(s));
+  return MGF_OK;
+}
+
+// the checks of a query call that need neither the handle's contents nor a device
+static mgf_status batch_query_args(const mgf_batch* b, const int32_t* world, const void* q, int64_t n, int32_t kinds_mask, const void* out) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (n < 0) return fail(MGF_ERR_INVALID, "n is negative");
+  if (n && (!world || !q || !out)) return fail(MGF_ERR_INVALID, "NULL argument");
+  if (kinds_mask <= 0 || (kinds_mask & ~MGF_QUERY_ALL)) return fail(MGF_ERR_INVALID, "kinds_mask must be a non-empty set of MGF_QUERY_* bits");
+  if (n > (int64_t)INT32_MAX) return fail(MGF_ERR_INVALID, "too many queries in one call");
+  for (int64_t i = 0; i < n; ++i)
+    if (world[i] < 0) return fail(MGF_ERR_INVALID, "world index out of range");
+  return MGF_OK;
+}
+
+// Q = ParticleIn (7 words out) or MovingIn (13 words out)
+template <class Q>
+static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* queries, int64_t n_in, const int32_t* ignore_body, int32_t kinds_mask,
+                                  int32_t* out) {
+  constexpr bool kRays = std::is_same<Q, ParticleIn>::value;
+  constexpr size_t kOut = kRays ? 7 : 13;
+  MGF_TRY(ctx_bind(b->ctx));
+  const uint32_t K = b->K;
+  const size_t n = (size_t)n_in;
+  for (size_t i = 0; i < n; ++i)
+    if ((uint32_t)world[i] >= K) return fail(MGF_ERR_INVALID, "world index out of range");
+  b->q_launches = 0; b->q_run_ms = 0.0f;
+  if (n == 0) return MGF_OK;
+  MGF_TRY(batch_push(b));
+  mgf_ctx* ctx = b->ctx;
+  hipStream_t s = ctx->stream;
+  for (hipEvent_t& e : b->q_ev)
+    if (!e) MGF_HIP_TRY(hipEventCreate(&e));
+  // the query indices by world, in the caller's order within a world; work items of up to 256 queries
+  std::vector<uint32_t> start((size_t)K + 1, 0u);
+  for (size_t i = 0; i < n; ++i) ++start[(size_t)world[i] + 1];
+  for (uint32_t k = 0; k < K; ++k) start[k + 1] += start[k];
+  size_t n_items = 0;
+  for (uint32_t k = 0; k < K; ++k) n_items += (start[k + 1] - start[k] + 255u) / 256u;
+  // one upload: items | queries | order | ignore, every section from a 16-byte boundary
+  const size_t w_items = n_items, w_q = (n * sizeof(Q) + 15) / 16, w_idx = (4 * n + 15) / 16;
+  const size_t o_q = w_items, o_order = o_q + w_q, o_ign = o_order + w_idx, total = o_ign + (ignore_body ? w_idx : 0);
+  std::vector<float4> h(total);
+  uint4* items = reinterpret_cast<uint4*>(h.data());
+  size_t at = 0;
+  for (uint32_t k = 0; k < K; ++k)
+    for (uint32_t f = start[k]; f < start[k + 1]; f += 256u) items[at++] = make_uint4(k, f, std::min(256u, start[k + 1] - f), 0u);
+  memcpy(h.data() + o_q, queries, n * sizeof(Q));
+  uint32_t* order = reinterpret_cast<uint32_t*>(h.data() + o_order);
+  {
+    std::vector<uint32_t> cur(start.begin(), start.end() - 1);
+    for (size_t i = 0; i < n; ++i) order[cur[(size_t)world[i]]++] = (uint32_t)i;
+  }
+  if (ignore_body) memcpy(h.data() + o_ign, ignore_body, 4 * n);
+  MGF_TRY(b->q_in.ensure(total, s));
+  MGF_TRY(b->q_out.ensure(kOut * n, s));
+  MGF_HIP_TRY(hipMemcpyAsync(b->q_in.p, h.data(), 16 * total, hipMemcpyHostToDevice, s));
+  MGF_TRY(batch_cols_refresh(b, &b->q_launches));
+  uint32_t nmax = 0;
+  for (uint32_t c : b->h_n) nmax = std::max(nmax, c);
+  const uint32_t lds = 32u * nmax + 16u * kBatchQueryRed;  // (at most 32 KB + 256 bytes: two workgroups a CU at the largest world)
+  BatchQueryArgs A;
+  memset(&A, 0, sizeof(A));
+  A.col0 = b->dm[mgf_batch::ACOL0].p; A.col1 = b->dm[mgf_batch::ACOL1].p; A.w_off = b->d_off.p;
+  A.M.nodes = b->t_nodes.p; A.M.verts = b->t_verts.p; A.M.faces = b->t_faces.p;
+  A.M.n_nodes = (kinds_mask & MGF_QUERY_TERRAIN) ? b->t_n_nodes : 0u;
+  A.M.x[0] = b->t_x.x; A.M.x[1] = b->t_x.y; A.M.x[2] = b->t_x.z;
+  A.items = reinterpret_cast<const uint4*>(b->q_in.p);
+  A.order = reinterpret_cast<const uint32_t*>(b->q_in.p + o_order);
+  A.ignore = ignore_body ? reinterpret_cast<const int32_t*>(b->q_in.p + o_ign) : nullptr;
+  A.mask = kinds_mask;
+  A.out = b->q_out.p;
+  const Q* dq = reinterpret_cast<const Q*>(b->q_in.p + o_q);
+  MGF_HIP_TRY(hipEventRecord(b->q_ev[0], s));
+  if constexpr (kRays) {
+    k_batch_query_ray<<<(unsigned)n_items, kBatchBlock, lds, s>>>(A, dq);
+    LAUNCH_CHECK();
+    ++b->q_launches;
+  } else {
+    k_batch_query_sweep_bodies<<<(unsigned)n_items, kBatchBlock, lds, s>>>(A, dq);
+    LAUNCH_CHECK();
+    ++b->q_launches;
+    if (A.M.n_nodes) {
+      k_batch_query_sweep_faces<<<(unsigned)((n + kBatchBlock - 1) / kBatchBlock), kBatchBlock, 0, s>>>(A.M, dq, (uint32_t)n, A.out);
+      LAUNCH_CHECK();
+      ++b->q_launches;
+    }
+  }
+  MGF_HIP_TRY(hipEventRecord(b->q_ev[1], s));
+  MGF_HIP_TRY(hipMemcpyAsync(out, b->q_out.p, 4 * kOut * n, hipMemcpyDeviceToHost, s));
+  MGF_HIP_TRY(hipStreamSynchronize(s));
+  MGF_HIP_TRY(hipEventElapsedTime(&b->q_run_ms, b->q_ev[0], b->q_ev[1]));
+  return MGF_OK;
+}
+
+extern "C" mgf_status mgf_batch_raycast_many(mgf_batch* b, const int32_t* world, const mgf_particle* parts, int64_t n, const int32_t* ignore_body,
+                                             int32_t kinds_mask, mgf_ray_hit* out) {
+  MGF_TRY(batch_query_args(b, world, parts, n, kinds_mask, out));
+  static_assert(sizeof(mgf_ray_hit) == 28 && sizeof(mgf_particle) == sizeof(ParticleIn), "k_batch_query_ray writes mgf_ray_hit as seven words");
+  return batch_query_run(b, world, reinterpret_cast<const ParticleIn*>(parts), n, ignore_body, kinds_mask, reinterpret_cast<int32_t*>(out));
+}
+
+extern "C" mgf_status mgf_batch_sweep_many(mgf_batch* b, const int32_t* world, const mgf_moving_component* casts, int64_t n, const int32_t* ignore_body,
+                                           int32_t kinds_mask, mgf_sweep_hit* out) {
+  MGF_TRY(batch_query_args(b, world, casts, n, kinds_mask, out));
+  static_assert(sizeof(mgf_sweep_hit) == 52 && sizeof(mgf_moving_component) == sizeof(MovingIn), "k_batch_query_sweep_bodies writes mgf_sweep_hit as 13 words");
+  for (int64_t i = 0; i < n; ++i)
+    if (casts[i].shape.tag != 0 && casts[i].shape.tag != 1) return fail(MGF_ERR_INVALID, "a cast's shape tag must be 0 (sphere) or 1 (capsule)");
+  return batch_query_run(b, world, reinterpret_cast<const MovingIn*>(casts), n, ignore_body, kinds_mask, reinterpret_cast<int32_t*>(out));
+}

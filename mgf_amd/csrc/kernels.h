@@ -77,6 +77,9 @@
 //                      a batch of small independent worlds (mgf_batch_*): the whole tick of one world by one workgroup per launch - integrate,
 //                      the boxes and the pair search in LDS, the tests, the constraint records, Solver::solve with the bodies' records and
 //                      progress counters in LDS
+//   k_batch_query_gather / _ray / _sweep_bodies / _sweep_faces (k_batch_query.h)
+//                      ray casts and sweeps against the worlds of a batch (mgf_batch_raycast_many / _sweep_many): a workgroup per (world,
+//                      up to 256 queries), the world's colliders in LDS, 256 / count lanes a query, the mesh tree walked without a stack
 //   k_query_* (k_query.h) ray casts and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid of
 //                      the bodies' current tight boxes built per call (never the tick's lists)
 //
@@ -88,3 +91,4 @@
 #include "k_api.h"
 #include "k_query.h"  // the world queries between ticks (k_query_*), beside the tick
 #include "k_batch.h"  // many small worlds, a workgroup each (k_batch_*), beside the one-world tick
+#include "k_batch_query.h"  // the queries of k_query.h for the worlds of a batch (k_batch_query_*)

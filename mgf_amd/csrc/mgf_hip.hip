@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <memory>
+#include <type_traits>
 #include <utility>
 
 #include "common.h"
@@ -155,3 +156,4 @@ extern "C" mgf_status mgf_exclusive_scan_u32(mgf_ctx* ctx, const uint32_t* in, i
 #include "host_tiles_native.inc"
 #include "host_query.inc"
 #include "host_batch.inc"
+#include "host_batch_query.inc"
