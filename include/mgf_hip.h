@@ -494,11 +494,10 @@ MGF_API int64_t mgf_tiles_counter(const mgf_tiles* t, const char* key);
  * so with "flow_max_blocks");
  * "constraint_order" [0] 1 = the reference's own insertion order, replayed on the host (world.rs:233-291);
  * "pair_brick" [1] (grid broadphase with an 8x8x8-cell box staged in LDS; 0 = every look-up from global memory);
- * "body_pack" [1] (the constraint setup reads collider, motion and info from the packed per-tick copy);
  * "grid_min_frac_pct" [50] (axes of the scene shorter than this percentage of the longest one are widened to it before
  * the Morton cells are laid over it: cells stay near-cubic in an x-slab tile);
  * "flow6_fcap", "flow6_const_lds", "flow6_poll_waves", "flow6_test_cap" (mode 6: foreign-body slots, constants in LDS,
- * polling waves, a test limit that forces the stand-by kernel); "two_pass_candidates" [0]; "broadphase_tree" [0]; "terrain_tree" [0]; "no_fused_narrowphase" [0] (a world of spheres only runs the sphere-sphere test inside the grid broadphase and lists contacts only; 1 = list every accepted partner); "stream_ordered" [0]; "phase_timing" [0] (HIP events at the tick's phase boundaries: mgf_step_stats::ms_*), "time_solver_kernels" [0] (events around the solver launches: ms_solver_kernels); "spin_wait" [1] (the tick's one wait polls an event instead of blocking); "pipeline" [1] (mgf_world_step_many enqueues the next tick before it waits for this one); "cell_fill" [16] (bodies per Morton cell, in eighths, beyond which the broadphase grid gets another level); "no_fused_terrain_rows" [0], "no_fused_scene_bounds" [0] (mgf_world_step and mgf_world_begin_tick list the terrain faces of a body and gather the scene bounds inside the integration kernel; 1 = always the separate kernels); "list_capacity";
+ * polling waves, a test limit that forces the stand-by kernel); "two_pass_candidates" [0]; "broadphase_tree" [0]; "terrain_tree" [0]; "no_fused_narrowphase" [0] (a world of spheres only runs the sphere-sphere test inside the grid broadphase and lists contacts only; 1 = list every accepted partner); "stream_ordered" [0]; "phase_timing" [0] (HIP events at the tick's phase boundaries: mgf_step_stats::ms_*), "time_solver_kernels" [0] (events around the solver launches: ms_solver_kernels); "pipeline" [1] (mgf_world_step_many enqueues the next tick before it waits for this one); "cell_fill" [16] (bodies per Morton cell, in eighths, beyond which the broadphase grid gets another level); "no_fused_terrain_rows" [0], "no_fused_scene_bounds" [0] (mgf_world_step and mgf_world_begin_tick list the terrain faces of a body and gather the scene bounds inside the integration kernel; 1 = always the separate kernels); "list_capacity";
  * "fused_contacts" [1] (a world of spheres over a small mesh: rows -> constraint records without candidate lists; 0 = the candidate-list kernels);
  * "front_rows" [1] (r06: a world of single-component bodies that are not all spheres - capsules, mixed - or of bodies of up to two components:
  * the pair search runs the pair test on the partners it accepts, the bodies near the mesh get their faces and the body-triangle test in
@@ -516,7 +515,14 @@ MGF_API int64_t mgf_tiles_counter(const mgf_tiles* t, const char* key);
  * share a device each take a part, so that their launches are resident together); "flow_spin_limit" [0] (tests: 1 = every other workgroup of a
  * persistent launch returns at once and the launch gives up - the world then restores its pre-launch velocities and solves the list with the
  * launch-per-frontier executor, counter "solver_abort_fallbacks");
- * "flow_blocks_per_cu"; "flow_sleep"; "flow_trace"; "debug_bvh"; "flow5_block", "flow5_slow_x2", "flow5_poller", "flow5_test_cap" (block-local solver: block size, wave split, polling wave, a test limit that forces the stand-by kernel); "body_kinds" (OR-in, bit0 sphere, bit1 capsule): the
+ * "flow6_foreign_lds" [1], "flow6_nimp_lds" [1], "flow6_rec_lds" [1] (mode 6: the foreign bodies' constants, the accumulated normal impulses and
+ * the solver half of the constraint records in LDS where there is room; 0 = never), "flow6_slot_margin" [0] (what the LDS split lets a block's
+ * slots grow over the last tick's largest block), "flow6_quad" [1] and "flow6_quad_max" [-1] (four lanes per node while the ready queue is short;
+ * -1 = chosen by the launch), "flow6_spec" [0] and "flow6_spec_wl" [-1] (positions the polling waves read on spec; chosen by the launch);
+ * "resort_every" [-1] (ticks between two re-sorts of the body store into compact spatial blocks in the fused tick; 0 = the caller's order, -1 =
+ * automatic); "readback_kernel" [1] (the tick's read-back is written to pinned memory by a kernel and polled; 0 = a copy command and an event);
+ * "flow_trace" [0] (development: per-node timestamps of a dataflow launch); "flow5_block" [0] (tests: the minimum bodies per block of the
+ * block-local solvers), "flow5_test_cap" [0] (tests: a limit on a block's constraints that forces mode 5's stand-by kernel); "body_kinds" (OR-in, bit0 sphere, bit1 capsule): the
  * kinds this world's ghosts may have - a tile whose own bodies are all of one kind must be told when a neighbour's are
  * not, because the narrowphase dispatch is chosen on the host (the tiles driver exchanges the masks with the counts). */
 MGF_API mgf_status mgf_world_set_option(mgf_world* w, const char* key, int64_t value);

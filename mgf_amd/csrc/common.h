@@ -81,6 +81,32 @@ struct DBuf {
   size_t bytes() const { return cap * sizeof(T); }
 };
 
+// The words of the tick's `scalars` block (mgf_world::scalars, 32 words inside the read-back block) that the code uses: written by kernels,
+// cleared by the tick's clearing launches, read back by the host.  Host and device share the names, so a new flag takes a free index HERE.
+enum FlagWord : uint32_t {
+  kWFrontier0 = 0, kWFrontier1 = 1, kWFrontier2 = 2,  // the three rotating frontier counters of the launch-per-frontier solver (Frontier::cnt)
+  kWStackOverflow = 3,      // a BVH traversal's stack overflowed; the `err` pointer that kernels take points HERE (err_at)
+  kWRowOverflow = 4,        // a body has more partners / faces than a candidate row holds
+  kWSolverAbort = 5,        // a persistent solver launch gave up waiting
+  kWGridWide = 6,           // the largest body spans too many Morton cells for the grid broadphase
+  kWFlow5Fail = 7,          // mode 5's preparation: a block does not fit
+  kWTerrainWide = 8,        // the mesh's faces span too many cells for the face grid
+  kWFlow5MaxBlock = 9,      // mode 5: the tick's largest block
+  kWRevRowOverflow = 10,    // a body takes part as `b` in more constraints than a rev row holds
+  kWNarrowMismatch = 11,    // the pair search's contact test and the constraint setup disagree about a contact
+  kWStandbyBar = 12,        // k_solve_flow's barrier word when it runs as a block-local launch's stand-by
+  kWSkipGuard = 14,         // this tick is being skipped (a speculative tick behind a failed one)
+  kWF6MaxSlots = 16, kWF6MaxForeign = 17, kWF6Fail = 18, kWF6Edges = 19, kWF6EdgesBlock = 20,  // mode 6's preparation: largest block, most foreign
+                            // bodies, fail bits, edges across block faces per iteration (all / the most any block receives); cleared as one run
+  kWGhostCons = 21,         // constraints that involve a ghost body
+  kWBrickSlow = 22,         // queries k_pair_brick answered from global memory
+  kWLinksTicket = 23,       // k_flow6_links' last-block ticket (0 between launches)
+  kWBigPartsOverflow = 24,  // k_narrow_pairs_big: a pair of bodies of many parts with more contacts than its lists hold
+  kWLast = kWBigPartsOverflow
+};
+// index of a flag word from the `err` pointer of the kernels that take one (the address of kWStackOverflow)
+constexpr int err_at(FlagWord k) { return (int)k - (int)kWStackOverflow; }
+
 // Library primitive (rocPRIM) — prims.hip.  The device-wide scan is a stock primitive; every
 // physics kernel is hand-written (kernels.h).
 // out[0..n] = exclusive prefix sum of in[0..n-1], out[n] = total (in must have n+1 readable slots; slot n is ignored)

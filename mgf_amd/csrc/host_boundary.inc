@@ -136,7 +136,7 @@ extern "C" mgf_status mgf_world_clone(mgf_world* src, mgf_world** out) {
     MGF_TRY(clone_buf(ctx, w->ext_of, src->ext_of, n)); MGF_TRY(clone_buf(ctx, w->slot_of, src->slot_of, n));
     w->permuted = true;
   }
-  w->opt_resort_every = src->opt_resort_every; w->ticks_since_resort = src->ticks_since_resort;
+  w->ticks_since_resort = src->ticks_since_resort;
   MGF_HIP_TRY(hipStreamSynchronize(ctx->stream));
   w->n = w->n_owned = src->n_owned;
   w->has_sphere = src->has_sphere; w->has_capsule = src->has_capsule; w->has_compound = src->has_compound; w->max_parts = src->max_parts;
@@ -144,26 +144,18 @@ extern "C" mgf_status mgf_world_clone(mgf_world* src, mgf_world** out) {
   if (src->terrain) MGF_TRY(mgf_world_set_terrain(w, src->terrain.get()));
   for (const auto& ob : src->obstacles) MGF_TRY(mgf_world_add_obstacle(w, ob.get()));
   // options and the sticky plans a world settles into (so that the clone takes the same kernels from its first tick)
-  w->opt_constraint_order = src->opt_constraint_order; w->demo_tree = src->demo_tree; w->demo_leaf = src->demo_leaf;
-  w->opt_flow6_poll_prio = src->opt_flow6_poll_prio; w->opt_flow6_slot_blocks = src->opt_flow6_slot_blocks; w->opt_resort_partition = src->opt_resort_partition; w->opt_part_cell_x8 = src->opt_part_cell_x8;
-  w->opt_flow6_poll_k = src->opt_flow6_poll_k; w->opt_flow6_spec = src->opt_flow6_spec; w->opt_flow6_spec_wl = src->opt_flow6_spec_wl; w->opt_flow6_test_cap = src->opt_flow6_test_cap; w->opt_flow_trace = src->opt_flow_trace; w->opt_debug_bvh = src->opt_debug_bvh;
-  w->opt_flow6_fcap = src->opt_flow6_fcap; w->opt_flow6_const_lds = src->opt_flow6_const_lds; w->opt_flow6_nimp_lds = src->opt_flow6_nimp_lds; w->opt_flow6_rec_lds = src->opt_flow6_rec_lds; w->opt_flow6_slot_margin = src->opt_flow6_slot_margin; w->opt_flow6_quad = src->opt_flow6_quad; w->opt_flow6_quad_max = src->opt_flow6_quad_max; w->opt_flow6_foreign_lds = src->opt_flow6_foreign_lds; w->opt_flow6_poll_waves = src->opt_flow6_poll_waves;
-  w->opt_solver_mode = src->opt_solver_mode; w->opt_two_pass = src->opt_two_pass; w->opt_broadphase_tree = src->opt_broadphase_tree;
-  w->opt_terrain_tree = src->opt_terrain_tree; w->opt_no_fused_narrowphase = src->opt_no_fused_narrowphase;
-  w->opt_no_fused_scene_bounds = src->opt_no_fused_scene_bounds; w->opt_no_fused_terrain_rows = src->opt_no_fused_terrain_rows;
-  w->opt_pair_brick = src->opt_pair_brick; w->opt_body_pack = src->opt_body_pack; w->opt_grid_min_frac_pct = src->opt_grid_min_frac_pct;
+  w->opt = src->opt;
+  w->opt.flow_spin_limit = 0;  // (a test's short fuse for one world's persistent launches: a clone never took it along)
+  w->demo_tree = src->demo_tree; w->demo_leaf = src->demo_leaf;
   w->grid_occupancy = src->grid_occupancy;
-  w->opt_cell_fill = src->opt_cell_fill; w->opt_cell_fill_set = src->opt_cell_fill_set; w->opt_pipeline = src->opt_pipeline; w->opt_spin_wait = src->opt_spin_wait; w->opt_readback_kernel = src->opt_readback_kernel;
-  w->opt_stream_ordered = src->opt_stream_ordered; w->opt_flow_blocks_per_cu = src->opt_flow_blocks_per_cu; w->opt_flow_sleep = src->opt_flow_sleep;
-  w->opt_flow5_slow_x2 = src->opt_flow5_slow_x2; w->opt_flow5_poller = src->opt_flow5_poller; w->opt_flow5_block = src->opt_flow5_block;
-  w->opt_flow5_test_cap = src->opt_flow5_test_cap; w->opt_time_solver_kernels = src->opt_time_solver_kernels; w->opt_phase_timing = src->opt_phase_timing;
-  w->row_cap_t = src->row_cap_t; w->rev_cap = src->rev_cap; w->pair_brick_off = src->pair_brick_off; w->pair_brick_backoff = src->pair_brick_backoff; w->terrain_grid_off = src->terrain_grid_off; w->grid_too_wide = src->grid_too_wide;
+  w->row_cap_t = src->row_cap_t; w->rev_cap = src->rev_cap; w->pair_brick_off = src->pair_brick_off; w->pair_brick_backoff = src->pair_brick_backoff;
+  w->terrain_grid_off = src->terrain_grid_off; w->grid_too_wide = src->grid_too_wide; w->front_rows_off = src->front_rows_off;
   w->cap_t = src->cap_t; w->cap_p = src->cap_p; w->cap_c = src->cap_c; w->flow5_last_max = src->flow5_last_max;
   w->f6_fail_slots = src->f6_fail_slots; w->f6_fail_foreign = src->f6_fail_foreign; w->f6_fail_C = src->f6_fail_C; w->prev_C = src->prev_C;
   w->f6_last_slots = src->f6_last_slots; w->f6_last_foreign = src->f6_last_foreign; w->f6_last_msgs = src->f6_last_msgs;
   w->f6_last_block_msgs = src->f6_last_block_msgs; w->f6_prep_iters = src->f6_prep_iters;
-  w->opt_merged_lists = src->opt_merged_lists; w->opt_fused_contacts = src->opt_fused_contacts; w->opt_front_rows = src->opt_front_rows; w->opt_front_rows_check = src->opt_front_rows_check; w->opt_side_stream = src->opt_side_stream; w->opt_wide_list = src->opt_wide_list; w->wide_engaged = src->wide_engaged; w->wide_hold = src->wide_hold;
-  for (int k = 0; k < 3; ++k) { w->wide_ref[k] = src->wide_ref[k]; w->wide_limit[k] = src->wide_limit[k]; w->shape_rmax[k] = src->shape_rmax[k]; } w->front_rows_off = src->front_rows_off; w->opt_flow_max_blocks = src->opt_flow_max_blocks; w->opt_cells_in_integrate = src->opt_cells_in_integrate; w->opt_resort_every = src->opt_resort_every;
+  w->wide_engaged = src->wide_engaged; w->wide_hold = src->wide_hold;
+  for (int k = 0; k < 3; ++k) { w->wide_ref[k] = src->wide_ref[k]; w->wide_limit[k] = src->wide_limit[k]; w->shape_rmax[k] = src->shape_rmax[k]; }
   for (int k = 0; k < 3; ++k) { w->h_scene_ext[k] = src->h_scene_ext[k]; w->h_scene_rmax[k] = src->h_scene_rmax[k]; }
   *out = guard.release();
   return MGF_OK;

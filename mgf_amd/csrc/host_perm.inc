@@ -63,7 +63,7 @@ static mgf_status perm_apply(mgf_world* w, const uint32_t* order, bool to_identi
 static uint32_t flow_block_size(const mgf_world* w) {  // (as flow6_plan cuts them)
   const uint32_t need = (w->n_owned + (uint32_t)w->ctx->num_cus - 1u) / (uint32_t)w->ctx->num_cus;
   uint32_t nb = std::max(need, std::min(w->n_owned, 256u));
-  if (w->opt_flow5_block > 0) nb = std::max(need, (uint32_t)w->opt_flow5_block);
+  if (w->opt.flow5_block > 0) nb = std::max(need, (uint32_t)w->opt.flow5_block);
   return std::max(nb, 1u);
 }
 static mgf_status partition_order(mgf_world* w, const uint32_t** order) {
@@ -80,8 +80,8 @@ static mgf_status partition_order(mgf_world* w, const uint32_t** order) {
   if ((uint64_t)fx * fy >= (1u << (32 - kPartCoordBits))) return fail(MGF_ERR_CAPACITY, "internal: too many partition units");
   PartPlan P;
   P.nb = nb; P.B = B; P.fx = fx; P.fy = fy;
-  for (int k = 0; k < 3; ++k) {  // coarse cells of about the largest body along the axis (4..10 bits)
-    const double cell = std::max(2.0 * (double)w->h_scene_rmax[k] * (double)w->opt_part_cell_x8 / 8.0, 1e-3 * e[k]);
+  for (int k = 0; k < 3; ++k) {  // coarse cells of half the largest fat box's width along the axis (4..10 bits)
+    const double cell = std::max((double)w->h_scene_rmax[k], 1e-3 * e[k]);
     uint32_t cb = 4;
     while (cb < 10u && e[k] / (double)(1u << (cb + 1u)) >= cell) ++cb;
     P.cb[k] = cb;
@@ -111,11 +111,11 @@ static mgf_status partition_order(mgf_world* w, const uint32_t** order) {
   *order = w->part_vals[1].p;
   return MGF_OK;
 }
-// The store into a spatial order: compact blocks (partition_order), or that of the last cell sort.  Enqueue only.
+// The store into a spatial order: compact blocks (partition_order).  Enqueue only.
 static mgf_status world_resort(mgf_world* w) {
   if (!w->sidx_valid || w->n != w->n_owned || w->n_owned == 0) return MGF_OK;
-  const uint32_t* order = w->sidx.p;
-  if (w->opt_resort_partition) MGF_TRY(partition_order(w, &order));
+  const uint32_t* order = nullptr;
+  MGF_TRY(partition_order(w, &order));
   return perm_apply(w, order, false);
 }
 // The store back into the caller's order (no-op when it is).  The tick's lists name slots: they die with the order.
@@ -132,15 +132,15 @@ static mgf_status world_identity(mgf_world* w) {
 static uint32_t flow_block_size(const mgf_world* w);
 // Does the tick that begins now re-sort?  Only the fused tick asks (allow); the world.rs replay keeps the caller's order.
 static mgf_status maybe_resort(mgf_world* w, bool allow) {
-  if (w->opt_constraint_order == 1) return world_identity(w);
-  if (w->opt_solver_mode == 4) return world_identity(w);  // (the experimental slot executor walks constraint ids as the insertion order)
+  if (w->opt.constraint_order == 1) return world_identity(w);
+  if (w->opt.solver_mode == 4) return world_identity(w);  // (the experimental slot executor walks constraint ids as the insertion order)
   if (!allow) return MGF_OK;
   if (w->ptrs_out) return MGF_OK;  // (a caller holds raw pointers into the arrays, indexed by its own body indices: mgf_world_device_ptr)
-  int64_t every = w->opt_resort_every;
+  int64_t every = w->opt.resort_every;
   if (every < 0) every = w->n_owned >= 16384u ? 64 : 0;  // auto: worlds small enough to live in L2 gain nothing; a good order lasts (tools/store_probe.py)
   // (the automatic choice: only where the block-local solver can take the world - a world too large for its LDS tables is solved by
   // the global dataflow launch, which is no faster on a re-sorted store: config 4 as one world, 6.5 against 5.7 ms per tick)
-  if (w->opt_resort_every < 0 && flow_block_size(w) + 64u >= kF6NoBody) every = 0;
+  if (w->opt.resort_every < 0 && flow_block_size(w) + 64u >= kF6NoBody) every = 0;
   if (every == 0) return MGF_OK;  // (a world that was permuted stays as it is: correct in any order)
   ++w->ticks_since_resort;
   // A store that a boundary call put back into the caller's order (write_state, set_tags, export_*: world_identity) is re-sorted

@@ -4,17 +4,17 @@
 static mgf_status dump_flow_trace(mgf_world* w, uint32_t C, int32_t iters) {
   std::vector<uint64_t> h(2 * (size_t)iters * C);
   MGF_TRY(d2h(w->ctx, h.data(), w->flow_trace.p, h.size()));
-  if (w->opt_solver_mode == 6 && w->flow6_prepped) {
+  if (w->opt.solver_mode == 6 && w->flow6_prepped) {
     std::vector<uint64_t> st(kF6TraceWords * (size_t)w->f5_nblocks);
     MGF_TRY(d2h(w->ctx, st.data(), w->flow_trace.p + h.size(), st.size()));
     if (FILE* f = fopen("/tmp/mgf_flow6_poll.bin", "wb")) { fwrite(st.data(), 8, st.size(), f); fclose(f); }
   }
   // block-local solver: the body -> cell-order rank table and the block size tell which block ran a constraint
-  const bool f5 = ((w->opt_solver_mode == 5 && w->flow5_prepped) || (w->opt_solver_mode == 6 && w->flow6_prepped)) && w->f5_nb > 0;
+  const bool f5 = ((w->opt.solver_mode == 5 && w->flow5_prepped) || (w->opt.solver_mode == 6 && w->flow6_prepped)) && w->f5_nb > 0;
   std::vector<uint32_t> rank(f5 ? (size_t)w->n + (w->n & 1u) : 0);
   if (f5) {
     // (blocks cut from the slots of a re-sorted store: the caller's body index -> its slot; else the tick's cell order)
-    const bool slots = w->opt_solver_mode == 6 && w->permuted && w->opt_flow6_slot_blocks && w->iota_n >= w->n;
+    const bool slots = w->opt.solver_mode == 6 && w->permuted && w->iota_n >= w->n;
     if (slots) { MGF_TRY(perm_host(w)); for (size_t e = 0; e < w->h_slot_of.size(); ++e) rank[e] = w->h_slot_of[e]; }
     else MGF_TRY(d2h(w->ctx, rank.data(), w->brank.p, (size_t)w->n));
   }
@@ -38,7 +38,7 @@ static mgf_status dump_flow_trace(mgf_world* w, uint32_t C, int32_t iters) {
 // the CUs a persistent launch may count on: all of them, or this world's share of a device it has been told it shares (option flow_max_blocks)
 static uint32_t flow_cus(const mgf_world* w) {
   const uint32_t cus = (uint32_t)std::max(w->ctx->num_cus, 1);
-  return w->opt_flow_max_blocks > 0 ? std::max(1u, std::min(cus, (uint32_t)w->opt_flow_max_blocks)) : cus;
+  return w->opt.flow_max_blocks > 0 ? std::max(1u, std::min(cus, (uint32_t)w->opt.flow_max_blocks)) : cus;
 }
 // Block-local solver: block size (bodies per workgroup) and buffers for a constraint list of up to cap_c.  *ok = false when
 // the blocks would not fit the LDS layouts (the global dataflow launch runs instead).
@@ -50,7 +50,7 @@ static mgf_status flow5_plan(mgf_world* w, uint32_t cap_c, bool* ok) {
   // one block per CU when there are enough bodies (262 144 -> 1024 per block); smaller worlds keep every CU busy with
   // blocks down to 256 bodies (config 5, 65 536 bodies: 0.52 -> 0.45 ms solve)
   uint32_t nb = std::max(need, std::min(w->n, 256u));
-  if (w->opt_flow5_block > 0) nb = std::max(need, (uint32_t)w->opt_flow5_block);  // tests: small blocks on small scenes
+  if (w->opt.flow5_block > 0) nb = std::max(need, (uint32_t)w->opt.flow5_block);  // tests: small blocks on small scenes
   if (nb > kF5MaxBodies) { *ok = false; return MGF_OK; }
   w->f5_nb = nb; w->f5_nblocks = (w->n + nb - 1u) / nb;
   *ok = true;
@@ -65,10 +65,10 @@ static mgf_status flow5_plan(mgf_world* w, uint32_t cap_c, bool* ok) {
 static void flow5_zero_entries(mgf_world* w, uint32_t cap_c, ZeroList& z, int first) {
   z.p[first + 0] = w->f5_shared.p; z.words[first + 0] = w->n / 4 + 1;
   z.p[first + 1] = w->f5_gcnt.p; z.words[first + 1] = cap_c + 1;
-  z.p[first + 2] = w->d_err() + 4; z.words[first + 2] = 1;
+  z.p[first + 2] = w->word(kWFlow5Fail); z.words[first + 2] = 1;
   z.p[first + 3] = w->f5_wg_cnt.p; z.words[first + 3] = 4 * w->f5_nblocks * kF5CntStride;
-  z.p[first + 4] = w->d_err() + 6; z.words[first + 4] = 1;  // largest block of the tick
-  z.p[first + 5] = w->d_err() + 2; z.words[first + 5] = 1;  // the solvers' abort flag (k_flow_init resets it for the other modes)
+  z.p[first + 4] = w->word(kWFlow5MaxBlock); z.words[first + 4] = 1;  // largest block of the tick
+  z.p[first + 5] = w->word(kWSolverAbort); z.words[first + 5] = 1;  // the solvers' abort flag (k_flow_init resets it for the other modes)
 }
 
 // Persistent dataflow launch (modes 1 and 4), enqueue only.  Every lane must be resident, so the grid is sized
@@ -80,7 +80,7 @@ static void flow5_zero_entries(mgf_world* w, uint32_t cap_c, ZeroList& z, int fi
 // the tile path: no gain.)
 static mgf_status flow5_prepare(mgf_world* w, uint32_t cap_c, bool* use5) {
   hipStream_t s = w->ctx->stream;
-  *use5 = w->opt_solver_mode == 5 && w->flow5_ok && w->n > 0;
+  *use5 = w->opt.solver_mode == 5 && w->flow5_ok && w->n > 0;
   if (*use5) MGF_TRY(flow5_plan(w, cap_c, use5));
   if (!*use5 || w->flow5_prepped) return MGF_OK;
   if (!w->flow5_attr_set) {
@@ -136,16 +136,16 @@ static mgf_status flow6_plan(mgf_world* w, uint32_t cap_c, uint32_t iters, bool*
   const uint32_t cus = flow_cus(w);
   const uint32_t need = (w->n + cus - 1u) / cus;
   uint32_t nb = std::max(need, std::min(w->n, 256u));
-  if (w->opt_flow5_block > 0) nb = std::max(need, (uint32_t)w->opt_flow5_block);  // tests: small blocks on small scenes
+  if (w->opt.flow5_block > 0) nb = std::max(need, (uint32_t)w->opt.flow5_block);  // tests: small blocks on small scenes
   *ok = false;
   if (iters > kF6MaxIters) return MGF_OK;
   // foreign body slots: what the last tick needed plus a quarter; the rest of the LDS goes to constraint slots
-  uint32_t fcap = w->opt_flow6_fcap > 0 ? (uint32_t)w->opt_flow6_fcap
+  uint32_t fcap = w->opt.flow6_fcap > 0 ? (uint32_t)w->opt.flow6_fcap
                                         : (w->f6_last_foreign ? std::min(1536u, (w->f6_last_foreign + w->f6_last_foreign / 4u + 95u) & ~63u) : 512u);
   if (nb + fcap >= kF6NoBody) { if (nb + 64u >= kF6NoBody) return MGF_OK; fcap = (kF6NoBody - 1u - nb) & ~31u; }
   // What else lives in LDS for the launch, if the last tick's largest block (plus an eighth) still fits beside it: the own bodies'
   // constants (40 bytes per body) and the constraints' accumulated normal impulses (4 bytes per slot) - both, one, or neither
-  const uint32_t want_slots = w->opt_flow6_slot_margin > 0 ? w->f6_last_slots + w->f6_last_slots / (uint32_t)w->opt_flow6_slot_margin + 32u
+  const uint32_t want_slots = w->opt.flow6_slot_margin > 0 ? w->f6_last_slots + w->f6_last_slots / (uint32_t)w->opt.flow6_slot_margin + 32u
                                                             : w->f6_last_slots + w->f6_last_slots / 8u + 64u;
   auto room = [&](int cl, bool nl, bool rl = false) -> uint32_t {
     const uint32_t fx = f6_lds_bytes(nb, fcap, 0, cl, nl, rl);
@@ -155,20 +155,20 @@ static mgf_status flow6_plan(mgf_world* w, uint32_t cap_c, uint32_t iters, bool*
   bool nimp_lds = false, rec_lds = false;
   // (the impulses are read into LDS when a launch starts and written back when it ends: that pays from about four iterations per
   // launch on - a tile's launches of R = 2 iterations are 0.5 % faster without)
-  const bool cl_ok = w->opt_flow6_const_lds != 0, nl_ok = w->opt_flow6_nimp_lds != 0 && (iters >= 4u || w->opt_flow6_nimp_lds >= 2);
-  const bool fl_ok = cl_ok && w->opt_flow6_foreign_lds != 0;  // the foreign bodies' constants too (r04)
+  const bool cl_ok = w->opt.flow6_const_lds != 0, nl_ok = w->opt.flow6_nimp_lds != 0 && (iters >= 4u || w->opt.flow6_nimp_lds >= 2);
+  const bool fl_ok = cl_ok && w->opt.flow6_foreign_lds != 0;  // the foreign bodies' constants too (r04)
   // the whole solver half of every record (r04): where it fits, a node touches no global memory
-  const bool rl_ok = w->opt_flow6_rec_lds != 0 && w->opt_flow6_nimp_lds != 0;
+  const bool rl_ok = w->opt.flow6_rec_lds != 0 && w->opt.flow6_nimp_lds != 0;
   const uint32_t want_fit = std::max(want_slots, 256u);
   if (rl_ok && fl_ok && room(2, true, true) >= want_fit) { const_lds = 2; nimp_lds = true; rec_lds = true; }
   else if (rl_ok && cl_ok && room(1, true, true) >= want_fit) { const_lds = 1; nimp_lds = true; rec_lds = true; }
-  else if (rl_ok && w->opt_flow6_rec_lds >= 2 && room(0, true, true) >= want_fit) { nimp_lds = true; rec_lds = true; }
+  else if (rl_ok && w->opt.flow6_rec_lds >= 2 && room(0, true, true) >= want_fit) { nimp_lds = true; rec_lds = true; }
   else if (fl_ok && nl_ok && room(2, true) >= want_fit) { const_lds = 2; nimp_lds = true; }
   else if (cl_ok && nl_ok && room(1, true) >= want_fit) { const_lds = 1; nimp_lds = true; }
-  else if (nl_ok && w->opt_flow6_const_lds < 2 && room(0, true) >= want_fit) nimp_lds = true;  // (measured: worth more than the constants)
+  else if (nl_ok && w->opt.flow6_const_lds < 2 && room(0, true) >= want_fit) nimp_lds = true;  // (measured: worth more than the constants)
   else if (fl_ok && !nl_ok && room(2, false) >= want_fit) const_lds = 2;
-  else if (cl_ok && (w->opt_flow6_const_lds >= 2 ? room(1, false) >= 256u : room(1, false) >= want_fit)) const_lds = 1;
-  else if (nl_ok && w->opt_flow6_const_lds < 2 && w->opt_flow6_fcap <= 0 && w->f6_last_foreign && w->f6_last_slots) {
+  else if (cl_ok && (w->opt.flow6_const_lds >= 2 ? room(1, false) >= 256u : room(1, false) >= want_fit)) const_lds = 1;
+  else if (nl_ok && w->opt.flow6_const_lds < 2 && w->opt.flow6_fcap <= 0 && w->f6_last_foreign && w->f6_last_slots) {
     // the settled pile: the impulses fit only with narrow margins (a sixteenth more foreign bodies, a thirty-second more slots than
     // the last tick; the counts drift slowly there, and a tick that outgrows them is re-run with the global solver)
     const uint32_t fcap_std = fcap;
@@ -178,8 +178,8 @@ static mgf_status flow6_plan(mgf_world* w, uint32_t cap_c, uint32_t iters, bool*
   }
   if (room(const_lds, nimp_lds, rec_lds) < 256u) return MGF_OK;
   uint32_t slot_cap = std::min(kF6MaxSlots, room(const_lds, nimp_lds, rec_lds) & ~1u);
-  if (w->opt_flow6_test_cap > 0) slot_cap = std::min(slot_cap, (uint32_t)w->opt_flow6_test_cap);
-  if (w->f6_fail_C && w->opt_flow6_test_cap <= 0 && !w->flow6_prepped) {
+  if (w->opt.flow6_test_cap > 0) slot_cap = std::min(slot_cap, (uint32_t)w->opt.flow6_test_cap);
+  if (w->f6_fail_C && w->opt.flow6_test_cap <= 0 && !w->flow6_prepped) {
     // a launch of this world did not fit before: the need then, scaled by the constraints since (slots per block follow them; the foreign
     // bodies of a block grow with its surface, not faster than them) - if that still does not fit the split above, not this tick
     const double scale = (double)std::max(w->prev_C, 1u) / (double)w->f6_fail_C;
@@ -188,7 +188,7 @@ static mgf_status flow6_plan(mgf_world* w, uint32_t cap_c, uint32_t iters, bool*
   }
   *ok = true;
   if (w->flow6_prepped) return MGF_OK;  // (the split of a prepared list stays)
-  if (w->permuted && w->opt_flow6_slot_blocks && w->iota_n < w->n) {
+  if (w->permuted && w->iota_n < w->n) {
     MGF_TRY(w->iota.ensure(w->n, s));
     w->iota_n = w->iota.cap;
     k_iota<<<nblk(w->iota_n), kBlock, 0, s>>>(w->iota.p, (uint32_t)w->iota_n);
@@ -229,22 +229,23 @@ static Flow6 flow6_args(mgf_world* w) {
   // instead of runs of the tick's cell order, whose runs of 1024 bodies straddle the cell grid's own boundaries differently every
   // tick (tools/store_probe.py: 9-12 % of the pile's body pairs cross a block face against 12-18 %)
   F.ident = 0u;
-  if (w->permuted && w->opt_flow6_slot_blocks && w->iota_n >= w->n) { F.sidx = w->iota.p; F.brank = w->iota.p; F.ident = 1u; }
+  if (w->permuted && w->iota_n >= w->n) { F.sidx = w->iota.p; F.brank = w->iota.p; F.ident = 1u; }
   F.binfo = w->f6_binfo.p; F.bref = w->f6_bref.p; F.skipwb = w->f6_skipwb.p;
   F.fcnt = w->f6_fcnt.p; F.fbody = w->f6_fbody.p; F.nslots = w->f6_nslots.p; F.table = w->f6_table.p;
   F.in_key = w->f6_in_key.p; F.in_cnt = w->f6_in_cnt.p; F.out_key = w->f6_out_key.p; F.out_val = w->f6_out_val.p;
   F.chan_prefix = w->f6_chan_prefix.p; F.mbox = w->f6_mbox.p; F.mbox_cap = w->f6_mbox_cap; F.tails = w->f6_tails.p;
-  F.fail = w->scalars.p + 18; F.tick_fail = &w->sc.p->fail; F.max_slots = w->scalars.p + 16; F.max_foreign = w->scalars.p + 17;
+  F.fail = w->word(kWF6Fail); F.tick_fail = &w->sc.p->fail; F.max_slots = w->word(kWF6MaxSlots); F.max_foreign = w->word(kWF6MaxForeign);
   F.nb = w->f5_nb; F.nblocks = w->f5_nblocks; F.n = w->n; F.rows = w->f6_rows; F.fcap = w->f6_fcap; F.slot_cap = w->f6_slot_cap;
   // (measured, profiles/r04_pollers_sweep.txt: two polling waves that also read four positions behind the producers' hint on spec cut the falling
   // pile's launch by 4 %, configs 3 by 3 %; a launch whose constants come from global memory - the settled pile - loses 2 % with a serving wave less)
   const bool busy_cu = w->f6_const_lds == 0;
-  F.poll_waves = w->opt_flow6_poll_waves > 0 ? (uint32_t)w->opt_flow6_poll_waves : (busy_cu ? 1u : 2u);
-  F.poll_spec_wl = w->opt_flow6_spec_wl >= 0 ? (uint32_t)w->opt_flow6_spec_wl : (busy_cu ? 0u : 4u);
-  F.poll_k = (uint32_t)w->opt_flow6_poll_k; F.poll_prio = (uint32_t)w->opt_flow6_poll_prio; F.poll_spec = w->opt_flow6_spec > 0 ? (uint32_t)w->opt_flow6_spec : (busy_cu ? 4u : 8u);
+  F.poll_waves = w->opt.flow6_poll_waves > 0 ? (uint32_t)w->opt.flow6_poll_waves : (busy_cu ? 1u : 2u);
+  F.poll_spec_wl = w->opt.flow6_spec_wl >= 0 ? (uint32_t)w->opt.flow6_spec_wl : (busy_cu ? 0u : 4u);
+  constexpr uint32_t kPollK = 2u, kPollPrio = 3u;  // quiet sweeps read the channels' heads straight; s_setprio of the polling waves
+  F.poll_k = kPollK; F.poll_prio = kPollPrio; F.poll_spec = w->opt.flow6_spec > 0 ? (uint32_t)w->opt.flow6_spec : (busy_cu ? 4u : 8u);
   // (measured, profiles/r04_quad_max_sweep.txt: 48 is best for the falling pile and BASELINE configs 3 and 5; a launch whose bodies' constants come
   // from global memory - the settled pile - is fastest with quad trips only: its one-lane trips wait for six more loads per node)
-  F.quad_max = w->opt_flow6_quad_max >= 0 ? (uint32_t)w->opt_flow6_quad_max : (w->f6_const_lds ? 48u : (1u << 20));
+  F.quad_max = w->opt.flow6_quad_max >= 0 ? (uint32_t)w->opt.flow6_quad_max : (w->f6_const_lds ? 48u : (1u << 20));
   return F;
 }
 // what the preparation kernels need cleared (8 entries of a ZeroList, from `first`)
@@ -256,13 +257,13 @@ static void flow6_zero_entries(mgf_world* w, uint32_t cap_c, ZeroList& z, int fi
   z.p[first + 3] = w->f6_out_key.p; z.words[first + 3] = chw;
   z.p[first + 4] = reinterpret_cast<uint32_t*>(w->f6_skipwb.p); z.words[first + 4] = w->n / 4 + 1;
   z.p[first + 5] = nullptr; z.words[first + 5] = 0;
-  z.p[first + 6] = w->scalars.p + 16; z.words[first + 6] = 5;  // largest block, most foreign bodies, fail, edges per iteration (all / most per block)
-  z.p[first + 7] = w->d_err() + 2; z.words[first + 7] = 1;     // the solvers' abort flag
+  z.p[first + 6] = w->word(kWF6MaxSlots); z.words[first + 6] = kWF6EdgesBlock - kWF6MaxSlots + 1;  // largest block, most foreign bodies, fail, edges per iteration (all / most per block)
+  z.p[first + 7] = w->word(kWSolverAbort); z.words[first + 7] = 1;     // the solvers' abort flag
 }
 // k_chain_rows on the tick's own list.  only_if: a device word; the kernel does nothing while it is 0 (the stand-by's links).
 static mgf_status chain_rows_launch(mgf_world* w, const uint32_t* only_if) {
-  k_chain_rows<<<nblk(w->n), kBlock, 0, w->ctx->stream>>>(w->n, w->links(), w->base.p, w->degb.p, w->rev.p, w->rev_cap, w->d_err() + 7, w->sc.p, w->tcn.p,
-                                                          w->n_owned, only_if ? nullptr : w->scalars.p + 21, only_if, w->ext_ptr());
+  k_chain_rows<<<nblk(w->n), kBlock, 0, w->ctx->stream>>>(w->n, w->links(), w->base.p, w->degb.p, w->rev.p, w->rev_cap, w->word(kWRevRowOverflow), w->sc.p, w->tcn.p,
+                                                          w->n_owned, only_if ? nullptr : w->word(kWGhostCons), only_if, w->ext_ptr());
   LAUNCH_CHECK();
   return MGF_OK;
 }
@@ -272,12 +273,12 @@ static mgf_status chain_rows_launch(mgf_world* w, const uint32_t* only_if) {
 // a caller's list can be cut into spatial blocks when the bodies' spatial order is known: the slots of a re-sorted store, or the
 // cell order of a collide phase that ran on these bodies
 static bool flow6_generic_ok(const mgf_world* w) {
-  return w->list_generic && ((w->permuted && w->opt_flow6_slot_blocks) || w->sidx_valid);
+  return w->list_generic && (w->permuted || w->sidx_valid);
 }
 static mgf_status flow6_build_tables(mgf_world* w, uint32_t cap_c, bool* built) {
   hipStream_t s = w->ctx->stream;
   *built = false;
-  if (!(w->opt_solver_mode == 6 && !w->tick_mode1 && (w->flow5_ok || flow6_generic_ok(w)) && w->n > 0)) return MGF_OK;
+  if (!(w->opt.solver_mode == 6 && !w->tick_mode1 && (w->flow5_ok || flow6_generic_ok(w)) && w->n > 0)) return MGF_OK;
   bool ok = false;
   MGF_TRY(flow6_plan(w, cap_c, w->f6_prep_iters ? w->f6_prep_iters : 10u, &ok));
   if (!ok) return MGF_OK;
@@ -309,11 +310,11 @@ static mgf_status flow6_build_tables(mgf_world* w, uint32_t cap_c, bool* built) 
   }
   k_flow6_blocks<<<F.nblocks, kF6PrepThreads, 0, s>>>(F, w->links());
   LAUNCH_CHECK();
-  // (the channel layout - k_flow6_chan's work - is done by the links launch's last block: scalars[23] is its ticket, 0 between launches)
+  // (the channel layout - k_flow6_chan's work - is done by the links launch's last block: kWLinksTicket is its ticket, 0 between launches)
   const uint32_t iters = w->f6_prep_iters ? w->f6_prep_iters : 10u;
   MGF_TRY(w->vsnap.ensure(2 * (size_t)std::max(w->n, 1u), s));
-  k_flow6_links<<<nblk(w->n), kBlock, 0, s>>>(F, w->links(), w->n, w->degb.p, w->rev.p, w->rev_cap, w->d_err() + 7, w->sc.p, w->n_owned, w->scalars.p + 21, w->ext_ptr(),
-                                              w->scalars.p + 23, iters, w->srec.p, w->vsnap.p);
+  k_flow6_links<<<nblk(w->n), kBlock, 0, s>>>(F, w->links(), w->n, w->degb.p, w->rev.p, w->rev_cap, w->word(kWRevRowOverflow), w->sc.p, w->n_owned, w->word(kWGhostCons), w->ext_ptr(),
+                                              w->word(kWLinksTicket), iters, w->srec.p, w->vsnap.p);
   LAUNCH_CHECK();
   w->snap_in_links = true;  // (the velocities at this point; good for a launch that follows with nothing in between: the fused tick's)
   w->flow6_prepped = true;
@@ -323,7 +324,7 @@ static mgf_status flow6_build_tables(mgf_world* w, uint32_t cap_c, bool* built) 
 }
 static mgf_status flow6_prepare(mgf_world* w, uint32_t cap_c, uint32_t iters, bool* use6) {
   hipStream_t s = w->ctx->stream;
-  *use6 = w->opt_solver_mode == 6 && !w->tick_mode1 && (w->flow5_ok || flow6_generic_ok(w)) && w->n > 0;
+  *use6 = w->opt.solver_mode == 6 && !w->tick_mode1 && (w->flow5_ok || flow6_generic_ok(w)) && w->n > 0;
   if (*use6) MGF_TRY(flow6_plan(w, cap_c, iters, use6));
   if (!*use6) return MGF_OK;
   if (!w->flow6_prepped) {  // (the mode was switched to 6 after the collide phase)
@@ -365,7 +366,7 @@ static mgf_status solve_flow_enqueue(mgf_world* w, int32_t iters, uint32_t cap_c
   w->snap_in_links = false;
   // (the slot executor walks constraint ids as the insertion order: on a re-sorted store - the mode was switched after the collide
   // phase - the global dataflow launch takes the list, through its `canon` indirection)
-  const bool kslots = w->opt_solver_mode == 4 && !(w->permuted && w->flow5_ok);
+  const bool kslots = w->opt.solver_mode == 4 && !(w->permuted && w->flow5_ok);
   bool use5 = false, use6 = false;
   MGF_TRY(flow6_prepare(w, cap_c, (uint32_t)iters, &use6));
   if (!use6 && !w->links_ready) { MGF_TRY(chain_rows_launch(w, nullptr)); w->links_ready = true; }  // (k_flow6_links stood in for k_chain_rows)
@@ -375,54 +376,52 @@ static mgf_status solve_flow_enqueue(mgf_world* w, int32_t iters, uint32_t cap_c
     int per_cu = 0;
     if (kslots) MGF_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_solve_flowk<4, false>, kBlock, 0));
     else MGF_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_solve_flow<false>, kBlock, 0));
-    int want = w->opt_flow_blocks_per_cu > 0 ? (int)w->opt_flow_blocks_per_cu : 4;
-    if (w->opt_flow_blocks_per_cu < 0) per_cu = (int)-w->opt_flow_blocks_per_cu;  // experiment: exact value, no occupancy margin
-    else per_cu = std::max(1, std::min(per_cu - 1, want));
+    per_cu = std::max(1, std::min(per_cu - 1, 4));
     if (getenv("MGF_FLOW_DEBUG")) fprintf(stderr, "[mgf] dataflow grid: %d blocks/CU x %d CUs\n", per_cu, ctx->num_cus);
     grid = per_cu * (int)flow_cus(w);
   }
   // what solver_abort_fallback restores if the launch gives up (not for stream-ordered launches - several per wait, ghost refreshes in
   // between: a tile set reports the tick as lost instead)
   if (links_snap && use6 && w->f6_tables_in_collide) { w->snap_valid = true; w->snap_nimp = false; }
-  else if (!w->opt_stream_ordered && !w->solve_pending) {
+  else if (!w->opt.stream_ordered && !w->solve_pending) {
     const uint32_t C = w->constraints_ready ? w->C : 0u;  // (a tick in flight: the list is fresh from ContactConstraint::new - zero impulses)
     MGF_TRY(w->vsnap.ensure(2 * (size_t)std::max(w->n, 1u), s));
     if (C) MGF_TRY(w->nsnap.ensure(C, s));
-    k_solver_snapshot<<<std::max(1u, nblk(std::max(w->n, C))), kBlock, 0, s>>>(w->srec.p, w->n, w->vsnap.p, w->cons_nat.p, C, C ? w->nsnap.p : nullptr, w->scalars.p + 14);
+    k_solver_snapshot<<<std::max(1u, nblk(std::max(w->n, C))), kBlock, 0, s>>>(w->srec.p, w->n, w->vsnap.p, w->cons_nat.p, C, C ? w->nsnap.p : nullptr, w->word(kWSkipGuard));
     LAUNCH_CHECK();
     w->snap_valid = true; w->snap_nimp = C != 0u;
   } else {
     w->snap_valid = false;
   }
   const uint32_t* C_ptr = &w->sc.p->C;
-  uint32_t* abort_flag = w->d_err() + 2;
+  uint32_t* abort_flag = w->word(kWSolverAbort);
   unsigned g = std::min<unsigned>((unsigned)grid, std::max(1u, nblk(cap_c)));
   MGF_TRY(w->flow_arr.ensure(std::max(cap_c, 1u), s));
   if (!use5 && !use6) {  // (the block-local solvers' stand-by initialises its counters itself, when it runs at all)
     k_flow_init<<<std::max(1u, nblk(cap_c)), kBlock, 0, s>>>(C_ptr, w->links(), w->flow_arr.p, abort_flag);
     LAUNCH_CHECK();
   }
-  const bool timed = w->opt_time_solver_kernels != 0;
+  const bool timed = w->opt.time_solver_kernels != 0;
   if (!w->solve_pending) w->ts->kev_used = 0;  // a tiled tick enqueues several launches before it reads the events
   if (timed) {
     while (w->ts->kev.size() < w->ts->kev_used + 2) { hipEvent_t e; MGF_HIP_TRY(hipEventCreate(&e)); w->ts->kev.push_back(e); }
     MGF_HIP_TRY(hipEventRecord(w->ts->kev[w->ts->kev_used], s));
   }
   uint64_t* trace = nullptr;
-  if (w->opt_flow_trace) {  // development aid (needs the host-side C: only after a synchronous collide)
+  if (w->opt.flow_trace) {  // development aid (needs the host-side C: only after a synchronous collide)
     const size_t tail = (size_t)kF6TraceWords * 4096;  // per-block polling statistics and phase clocks (mode 6)
     const size_t words = 2 * (size_t)iters * std::max(w->C, 1u) + tail;
     MGF_TRY(w->flow_trace.ensure(words, s));
     MGF_HIP_TRY(hipMemsetAsync(w->flow_trace.p + words - tail, 0, tail * 8, s));
     trace = w->flow_trace.p;
   }
-  const uint32_t spin_limit = w->opt_flow_spin_limit > 0 ? (uint32_t)w->opt_flow_spin_limit : 4u << 20;
-  const int sleep = (int)w->opt_flow_sleep;
+  const uint32_t spin_limit = w->opt.flow_spin_limit > 0 ? (uint32_t)w->opt.flow_spin_limit : 4u << 20;
+  constexpr int sleep = 2;  // how a waiting lane of k_solve_flow / k_solve_flowk idles (their sleep_mode)
   if (use6) {
     Flow6 F = flow6_args(w);
     if (++w->f6_epoch == 0u) ++w->f6_epoch;
     const size_t lds = f6_lds_bytes(F.nb, F.fcap, F.slot_cap, w->f6_const_lds, w->f6_nimp_lds, w->f6_rec_lds);
-    const int kidx = f6_kern_index(trace != nullptr, w->opt_flow6_quad != 0, w->f6_rec_lds, w->f6_const_lds, w->f6_nimp_lds);
+    const int kidx = f6_kern_index(trace != nullptr, w->opt.flow6_quad != 0, w->f6_rec_lds, w->f6_const_lds, w->f6_nimp_lds);
     const F6Kern kern = f6_kern(kidx);
     if (!(w->f6_attr_mask >> kidx & 1ull)) {  // (the one variant this launch takes, the first time it does: not all 64 of the table up front - ADVICE r4)
       MGF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kF6LdsBytes));
@@ -445,7 +444,7 @@ static mgf_status solve_flow_enqueue(mgf_world* w, int32_t iters, uint32_t cap_c
       if (!w->links_ready) MGF_TRY(chain_rows_launch(w, F.fail));
       const uint32_t* canon = nullptr;
       MGF_TRY(canon_ptr(w, cap_c, &canon));
-      k_solve_flow<false><<<g, kBlock, 0, s>>>(w->srec.p, w->cons_nat.p, w->links(), w->flow_arr.p, C_ptr, (uint32_t)iters, abort_flag, spin_limit, sleep, nullptr, F.fail, w->scalars.p + 12, canon);
+      k_solve_flow<false><<<g, kBlock, 0, s>>>(w->srec.p, w->cons_nat.p, w->links(), w->flow_arr.p, C_ptr, (uint32_t)iters, abort_flag, spin_limit, sleep, nullptr, F.fail, w->word(kWStandbyBar), canon);
     }
   } else if (use5) {
     Flow5 F = w->flow5();
@@ -457,7 +456,7 @@ static mgf_status solve_flow_enqueue(mgf_world* w, int32_t iters, uint32_t cap_c
     // stand-by: the global dataflow kernel runs only if a block did not fit its workgroup (flag raised by k_flow5_prep)
     const uint32_t* canon = nullptr;
     MGF_TRY(canon_ptr(w, cap_c, &canon));
-    k_solve_flow<false><<<g, kBlock, 0, s>>>(w->srec.p, w->cons_nat.p, w->links(), w->flow_arr.p, C_ptr, (uint32_t)iters, abort_flag, spin_limit, sleep, nullptr, F.fail, w->scalars.p + 12, canon);
+    k_solve_flow<false><<<g, kBlock, 0, s>>>(w->srec.p, w->cons_nat.p, w->links(), w->flow_arr.p, C_ptr, (uint32_t)iters, abort_flag, spin_limit, sleep, nullptr, F.fail, w->word(kWStandbyBar), canon);
   } else if (kslots) {
     if (trace) k_solve_flowk<4, true><<<g, kBlock, 0, s>>>(w->srec.p, w->cons_nat.p, w->links(), w->flow_arr.p, C_ptr, (uint32_t)iters, abort_flag, spin_limit, sleep, trace);
     else k_solve_flowk<4, false><<<g, kBlock, 0, s>>>(w->srec.p, w->cons_nat.p, w->links(), w->flow_arr.p, C_ptr, (uint32_t)iters, abort_flag, spin_limit, sleep, nullptr);
@@ -478,7 +477,7 @@ static mgf_status solve_frontier(mgf_world* w, int32_t iters) {
   mgf_ctx* ctx = w->ctx;
   hipStream_t s = ctx->stream;
   const uint32_t C = w->C;
-  const bool timed = w->opt_time_solver_kernels != 0;
+  const bool timed = w->opt.time_solver_kernels != 0;
   size_t kev_used = 0;
   auto tick = [&](void) -> mgf_status {  // event before/after a solver kernel (option)
     if (!timed) return MGF_OK;
@@ -490,7 +489,7 @@ static mgf_status solve_frontier(mgf_world* w, int32_t iters) {
   MGF_TRY(w->order.ensure((size_t)iters * C, s));
   if (w->lvl_cap == 0) { w->lvl_cap = 1u << 16; MGF_TRY(w->lvl_off.ensure(w->lvl_cap + 4, s)); }
   Frontier F = w->frontier();
-  MGF_HIP_TRY(hipMemsetAsync(w->scalars.p, 0, 12, s));
+  MGF_HIP_TRY(hipMemsetAsync(w->word(kWFrontier0), 0, 3 * 4, s));
   k_frontier0<<<std::min<unsigned>(nblk(C), 1024u), kBlock, 0, s>>>(C, w->cons_nat.p, w->links(), F);
   LAUNCH_CHECK();
   uint32_t r = 0;
@@ -509,7 +508,7 @@ static mgf_status solve_frontier(mgf_world* w, int32_t iters) {
     }
     r += batch;
     // launch r's list was filled by the last launch under counter r % 3; empty means everything ran
-    MGF_HIP_TRY(hipMemcpyAsync(pin, w->d_cnt() + (r % 3), 4, hipMemcpyDeviceToHost, s));
+    MGF_HIP_TRY(hipMemcpyAsync(pin, w->word(kWFrontier0) + (r % 3), 4, hipMemcpyDeviceToHost, s));
     MGF_HIP_TRY(hipMemcpyAsync(pin + 1, w->lvl_off.p + r, 4, hipMemcpyDeviceToHost, s));
     MGF_HIP_TRY(hipStreamSynchronize(s));
     if (pin[0] == 0) {
@@ -533,37 +532,41 @@ static mgf_status solve_frontier(mgf_world* w, int32_t iters) {
   return MGF_OK;
 }
 
+// The solvers' flag words (mgf_world::kSolverFlagsFirst ..) into the tick slot's pinned copy of the block.  Enqueue only.
+static mgf_status solver_flags_fetch(mgf_world* w) {
+  MGF_HIP_TRY(hipMemcpyAsync(w->ts->pin + mgf_world::kRbScalars + mgf_world::kSolverFlagsFirst, w->word(kWSolverAbort), 4 * mgf_world::kSolverFlagsWords,
+                             hipMemcpyDeviceToHost, w->ctx->stream));
+  return MGF_OK;
+}
 // After a dataflow launch has been synchronised: abort flag, timings.
 static mgf_status solve_flow_finish(mgf_world* w) {
-  uint32_t* pin = w->ts->pin;
-  // d_err()[2..6]: abort, grid-wide, flow5 fail, terrain-wide, flow5 max block.  In the one-synchronisation tick the solver
-  // was enqueued before collide_finish fetched the read-back block, so that copy already holds them.
-  const uint32_t* f = pin + mgf_world::kRbScalars + 3 + 2;
+  const mgf_world::TickSlot& h = *w->ts;
+  // In the one-synchronisation tick the solver was enqueued before collide_finish fetched the read-back block, so that copy already
+  // holds the solvers' flags.
   if (!w->rb_fresh) {
-    MGF_HIP_TRY(hipMemcpyAsync(pin + mgf_world::kRbScalars + 3 + 2, w->d_err() + 2, 4 * 16, hipMemcpyDeviceToHost, w->ctx->stream));  // scalars[5..20]
+    MGF_TRY(solver_flags_fetch(w));
     MGF_HIP_TRY(hipStreamSynchronize(w->ctx->stream));
   }
   w->rb_fresh = false;
-  if (f[0]) { w->solver_aborted = true; return fail(MGF_ERR_HIP, "dataflow solver gave up waiting (grid not fully resident?)"); }
-  if (w->opt_solver_mode == 5 && w->flow5_prepped) {
-    if (f[2]) w->n_flow5_fallbacks++;
-    w->flow5_last_max = f[4];
+  if (h.word(kWSolverAbort)) { w->solver_aborted = true; return fail(MGF_ERR_HIP, "dataflow solver gave up waiting (grid not fully resident?)"); }
+  if (w->opt.solver_mode == 5 && w->flow5_prepped) {
+    if (h.word(kWFlow5Fail)) w->n_flow5_fallbacks++;
+    w->flow5_last_max = h.word(kWFlow5MaxBlock);
   }
-  if (w->opt_solver_mode == 6 && w->flow6_prepped) {
-    const uint32_t* f6 = pin + mgf_world::kRbScalars + 16;  // largest block, most foreign bodies, fail, edges per iteration
-    if (f6[2]) {
-      w->n_flow6_fallbacks++; w->f6_fail_reason = f6[2];
+  if (w->opt.solver_mode == 6 && w->flow6_prepped) {
+    if (h.word(kWF6Fail)) {
+      w->n_flow6_fallbacks++; w->f6_fail_reason = h.word(kWF6Fail);
       // (a tick in flight re-runs from its collide phase on kFailFlow6; a finished list must have had its stand-by)
       if (w->constraints_ready && !w->f6_standby) return fail(MGF_ERR_HIP, "internal error: the block-local solver declined and no stand-by launch was enqueued");
     }
     else { w->n_flow6_runs++; w->f6_fail_C = 0; }
-    w->f6_last_slots = f6[0]; w->f6_last_foreign = f6[1];
-    w->f6_last_msgs = (uint64_t)f6[3] * std::max(w->f6_prep_iters, 1u);
-    w->f6_last_block_msgs = (uint64_t)f6[4] * std::max(w->f6_prep_iters, 1u);
+    w->f6_last_slots = h.word(kWF6MaxSlots); w->f6_last_foreign = h.word(kWF6MaxForeign);
+    w->f6_last_msgs = (uint64_t)h.word(kWF6Edges) * std::max(w->f6_prep_iters, 1u);
+    w->f6_last_block_msgs = (uint64_t)h.word(kWF6EdgesBlock) * std::max(w->f6_prep_iters, 1u);
   }
   w->stats.solver_kernel_launches = 1;
   w->depth = 1;
-  if (w->opt_time_solver_kernels) {
+  if (w->opt.time_solver_kernels) {
     float ms, total = 0.0f;
     // (a tick that ended on the polled read-back word instead of a stream synchronisation: the event's own completion may lag it)
     if (w->ts->kev_used >= 2) MGF_HIP_TRY(hipEventSynchronize(w->ts->kev[w->ts->kev_used - 1]));
@@ -577,7 +580,7 @@ static mgf_status solve_flow_finish(mgf_world* w) {
 // them in the pinned block (rb_fresh) and does not wait again.  The caller synchronises the stream before it calls mgf_world_finish.
 static mgf_status solve_flow_fetch_enqueue(mgf_world* w) {
   if (!w->solve_pending || !w->stats.solver_kernel_launches || w->rb_fresh) return MGF_OK;
-  MGF_HIP_TRY(hipMemcpyAsync(w->ts->pin + mgf_world::kRbScalars + 3 + 2, w->d_err() + 2, 4 * 16, hipMemcpyDeviceToHost, w->ctx->stream));  // scalars[5..20]
+  MGF_TRY(solver_flags_fetch(w));
   w->rb_fresh = true;
   return MGF_OK;
 }
@@ -594,7 +597,7 @@ static mgf_status solver_abort_fallback(mgf_world* w, int32_t iters, bool recoll
   MGF_HIP_TRY(hipStreamSynchronize(s));
   if (!w->snap_valid)
     return fail(MGF_ERR_HIP, "dataflow solver gave up waiting (grid not fully resident?) and the launches were stream-ordered: no snapshot to solve the list again from");
-  k_solver_restore<<<std::max(1u, nblk(std::max(w->n, w->C))), kBlock, 0, s>>>(w->srec.p, w->n, w->vsnap.p, w->cons_nat.p, w->C, w->snap_nimp ? w->nsnap.p : nullptr, w->d_err() + 2);
+  k_solver_restore<<<std::max(1u, nblk(std::max(w->n, w->C))), kBlock, 0, s>>>(w->srec.p, w->n, w->vsnap.p, w->cons_nat.p, w->C, w->snap_nimp ? w->nsnap.p : nullptr, w->word(kWSolverAbort));
   LAUNCH_CHECK();
   w->snap_valid = false;
   ++w->n_solver_abort_fallbacks;
@@ -621,7 +624,7 @@ static mgf_status solver_abort_fallback(mgf_world* w, int32_t iters, bool recoll
   return MGF_OK;
 }
 // (a solve that may use a persistent launch: not while the world is backing off after one that gave up)
-static bool frontier_only(mgf_world* w) { return w->opt_solver_mode == 0 || w->abort_backoff > 0; }
+static bool frontier_only(mgf_world* w) { return w->opt.solver_mode == 0 || w->abort_backoff > 0; }
 
 // Solver::solve solver.rs:72-78 (exact sequential order, see kernels.h).
 extern "C" mgf_status mgf_world_solve(mgf_world* w, int32_t iters, mgf_step_stats* stats) {
@@ -643,7 +646,7 @@ extern "C" mgf_status mgf_world_solve(mgf_world* w, int32_t iters, mgf_step_stat
       MGF_TRY(solve_frontier(w, iters));
     } else {
       MGF_TRY(solve_flow_enqueue(w, iters, w->C));
-      if (w->opt_flow_trace) MGF_TRY(dump_flow_trace(w, w->C, iters));
+      if (w->opt.flow_trace) MGF_TRY(dump_flow_trace(w, w->C, iters));
       MGF_TRY(phase_mark(w, 6, s));
       const mgf_status st = solve_flow_finish(w);
       if (st != MGF_OK && w->solver_aborted) MGF_TRY(solver_abort_fallback(w, iters));
@@ -666,7 +669,7 @@ extern "C" mgf_status mgf_world_solve(mgf_world* w, int32_t iters, mgf_step_stat
 extern "C" mgf_status mgf_world_solve_enqueue(mgf_world* w, int32_t iters) {
   if (!w) return fail(MGF_ERR_INVALID, "world is NULL");
   if (iters < 0) return fail(MGF_ERR_INVALID, "iters must be >= 0");
-  if (frontier_only(w) || w->opt_flow_trace) return mgf_world_solve(w, iters, nullptr);
+  if (frontier_only(w) || w->opt.flow_trace) return mgf_world_solve(w, iters, nullptr);
   MGF_TRY(ctx_bind(w->ctx));
   if (!w->constraints_ready) return fail(MGF_ERR_INVALID, "no constraint list: call mgf_world_build_constraints or mgf_world_set_constraints first");
   if (!w->solve_pending) {
@@ -712,28 +715,35 @@ extern "C" mgf_status mgf_world_finish(mgf_world* w, mgf_step_stats* stats) {
   return MGF_OK;
 }
 
+// the collide phase and the solve of a tick whose begin has run, into the stream; nothing is waited for
+static mgf_status collide_solve_enqueue(mgf_world* w, float dt, int32_t iters) {
+  hipStream_t s = w->ctx->stream;
+  MGF_TRY(collide_enqueue(w, dt, w->n > 0 && iters > 0));
+  MGF_TRY(phase_mark(w, 5, s));
+  if (w->n > 0 && iters > 0) MGF_TRY(solve_flow_enqueue(w, iters, w->cap_c, true));
+  return phase_mark(w, 6, s);
+}
+// ... enqueued and read back until the collide phase has settled its buffer capacities (a miss re-runs the phase: the solver was a no-op)
+static mgf_status collide_solve_settle(mgf_world* w, float dt, int32_t iters) {
+  for (int attempt = 0; attempt < 8; ++attempt) {
+    bool retry = false;
+    MGF_TRY(collide_solve_enqueue(w, dt, iters));
+    MGF_TRY(collide_finish(w, &retry));
+    if (!retry) return MGF_OK;
+  }
+  return fail(MGF_ERR_HIP, "internal error: collide phase did not settle its buffer capacities");
+}
 // World::step world.rs:227-294.  With a dataflow solver the whole tick is enqueued without a read-back
 // and synchronised once at the end; a capacity miss re-runs the collide phase (the solver was a no-op).
 extern "C" mgf_status mgf_world_step(mgf_world* w, float dt, int32_t iters, mgf_step_stats* stats) {
   if (!w) return fail(MGF_ERR_INVALID, "world is NULL");
   if (iters < 0) return fail(MGF_ERR_INVALID, "iters must be >= 0");
-  if (frontier_only(w) || w->opt_flow_trace || w->opt_debug_bvh || w->opt_constraint_order == 1) {
+  if (frontier_only(w) || w->opt.flow_trace || w->opt.constraint_order == 1) {
     MGF_TRY(mgf_world_build_constraints(w, dt, nullptr));
     MGF_TRY(mgf_world_solve(w, iters, nullptr));
   } else {
     MGF_TRY(world_begin(w, dt, false, true, true, w->n_owned > 0 && iters > 0));
-    hipStream_t s = w->ctx->stream;
-    bool done = false;
-    for (int attempt = 0; attempt < 8 && !done; ++attempt) {
-      bool retry = false;
-      MGF_TRY(collide_enqueue(w, dt, w->n > 0 && iters > 0));
-      MGF_TRY(phase_mark(w, 5, s));
-      if (w->n > 0 && iters > 0) MGF_TRY(solve_flow_enqueue(w, iters, w->cap_c, true));
-      MGF_TRY(phase_mark(w, 6, s));
-      MGF_TRY(collide_finish(w, &retry));
-      done = !retry;
-    }
-    if (!done) return fail(MGF_ERR_HIP, "internal error: collide phase did not settle its buffer capacities");
+    MGF_TRY(collide_solve_settle(w, dt, iters));
     w->stats.iters = (uint32_t)iters;
     w->stats.solver_kernel_launches = 0;
     w->stats.ms_solver_kernels = 0.0f;
@@ -778,12 +788,8 @@ static mgf_status step_complete(mgf_world* w, int32_t iters, mgf_step_stats* sta
 }
 // one whole tick into the stream, read-back copy and its event included; nothing is waited for
 static mgf_status tick_enqueue(mgf_world* w, float dt, int32_t iters, bool speculative) {
-  hipStream_t s = w->ctx->stream;
   MGF_TRY(world_begin(w, dt, speculative, true, true, w->n_owned > 0 && iters > 0));
-  MGF_TRY(collide_enqueue(w, dt, w->n > 0 && iters > 0));
-  MGF_TRY(phase_mark(w, 5, s));
-  if (w->n > 0 && iters > 0) MGF_TRY(solve_flow_enqueue(w, iters, w->cap_c, true));
-  MGF_TRY(phase_mark(w, 6, s));
+  MGF_TRY(collide_solve_enqueue(w, dt, iters));
   return readback_enqueue(w);
 }
 
@@ -794,7 +800,7 @@ static mgf_status tick_enqueue(mgf_world* w, float dt, int32_t iters, bool specu
 extern "C" mgf_status mgf_world_step_many(mgf_world* w, float dt, int32_t iters, int64_t n, mgf_step_stats* stats) {
   if (!w || n < 0) return fail(MGF_ERR_INVALID, "bad argument");
   if (iters < 0) return fail(MGF_ERR_INVALID, "iters must be >= 0");
-  if (frontier_only(w) || w->opt_flow_trace || w->opt_debug_bvh || !w->opt_pipeline || w->opt_constraint_order == 1) {
+  if (frontier_only(w) || w->opt.flow_trace || !w->opt.pipeline || w->opt.constraint_order == 1) {
     for (int64_t k = 0; k < n; ++k) MGF_TRY(mgf_world_step(w, dt, iters, stats ? stats + k : nullptr));
     return MGF_OK;
   }
@@ -823,22 +829,12 @@ extern "C" mgf_status mgf_world_step_many(mgf_world* w, float dt, int32_t iters,
         w->ts = &w->slots[cur ^ 1];
         MGF_TRY(readback_wait(w));
         w->ts = &w->slots[cur];
-        MGF_HIP_TRY(hipMemsetAsync(w->scalars.p + 14, 0, 4, s));
+        MGF_HIP_TRY(hipMemsetAsync(w->word(kWSkipGuard), 0, 4, s));
         // (its clearing launch went over the counters all the same - the terrain rows' counts that this tick's k_integrate wrote among
         // them: the re-run lists the rows again - r05: they used to be taken as still there, and the tick lost its terrain contacts)
         w->invalidate_tick_caches();
       }
-      bool done = false;
-      for (int attempt = 0; attempt < 8 && !done; ++attempt) {  // tick k again (its begin has run), as mgf_world_step does
-        bool again = false;
-        MGF_TRY(collide_enqueue(w, dt, w->n > 0 && iters > 0));
-        MGF_TRY(phase_mark(w, 5, s));
-        if (w->n > 0 && iters > 0) MGF_TRY(solve_flow_enqueue(w, iters, w->cap_c, true));
-        MGF_TRY(phase_mark(w, 6, s));
-        MGF_TRY(collide_finish(w, &again));
-        done = !again;
-      }
-      if (!done) return fail(MGF_ERR_HIP, "internal error: collide phase did not settle its buffer capacities");
+      MGF_TRY(collide_solve_settle(w, dt, iters));  // tick k again (its begin has run), as mgf_world_step does
       have = false;
     } else {
       have = spec;
@@ -852,7 +848,7 @@ extern "C" mgf_status mgf_world_step_many(mgf_world* w, float dt, int32_t iters,
         w->ts = &w->slots[cur ^ 1];
         MGF_TRY(readback_wait(w));
         w->ts = &w->slots[cur];
-        MGF_HIP_TRY(hipMemsetAsync(w->scalars.p + 14, 0, 4, s));
+        MGF_HIP_TRY(hipMemsetAsync(w->word(kWSkipGuard), 0, 4, s));
         have = false;
       }
       MGF_TRY(solver_abort_fallback(w, iters, behind, dt));

@@ -100,7 +100,7 @@ static mgf_status raise_parts_for_records(mgf_world* w, const float* rec, int64_
 static mgf_status world_import_ghosts2(mgf_world* w, const float* src, int64_t n_ghost, const float* src2, int64_t n_first);
 extern "C" mgf_status mgf_world_import_ghosts(mgf_world* w, const float* src, int64_t n_ghost) {
   // (a stream-ordered world belongs to a tile driver, which announces its neighbours' kinds - option body_kinds - and must not be made to wait here)
-  if (w && src && n_ghost > 0 && !w->opt_stream_ordered) { MGF_TRY(ctx_bind(w->ctx)); MGF_TRY(raise_parts_for_records(w, src, n_ghost, (uint32_t)kGhostFloats, 36u)); }
+  if (w && src && n_ghost > 0 && !w->opt.stream_ordered) { MGF_TRY(ctx_bind(w->ctx)); MGF_TRY(raise_parts_for_records(w, src, n_ghost, (uint32_t)kGhostFloats, 36u)); }
   return world_import_ghosts2(w, src, n_ghost, nullptr, n_ghost);
 }
 // (the host half: room for the ghosts, what the tick's caches cover afterwards; `I` = what k_import_ghosts needs, I->m == 0: nothing to launch)

@@ -127,10 +127,10 @@ extern "C" mgf_status mgf_tiles_create(mgf_ctx* ctx, int32_t n_local, mgf_world*
     if (!worlds[i] || worlds[i]->ctx != ctx) return fail(MGF_ERR_INVALID, "every tile's world must live on the tiles' context");
     if (worlds[i]->max_parts > (uint32_t)kTileParts) return fail(MGF_ERR_INVALID, "bodies of more than four parts cannot cross tiles (the tile records carry four part slots)");
     T->t[(size_t)i].w = worlds[i]; T->t[(size_t)i].x_lo = x_lo[i]; T->t[(size_t)i].x_hi = x_hi[i];
-    worlds[i]->opt_stream_ordered = 1;  // the tiling calls only enqueue: the driver synchronises where it needs a number
+    worlds[i]->opt.stream_ordered = 1;  // the tiling calls only enqueue: the driver synchronises where it needs a number
     // (a slab's cell grid is widened along its thin axis - grid_box - and its occupancy rule then adds a level: one level coarser serves the falling
     // pile of config 4 better, 5.52 -> 5.44 ms for 8 tiles, and changes nothing at rest or for config 5's tiles; a caller's own cell_fill stands)
-    if (!worlds[i]->opt_cell_fill_set && worlds[i]->opt_cell_fill < 32) worlds[i]->opt_cell_fill = 32;
+    if (!worlds[i]->opt.cell_fill_set && worlds[i]->opt.cell_fill < 32) worlds[i]->opt.cell_fill = 32;
     if (!worlds[i]->f6_prep_iters) worlds[i]->f6_prep_iters = (uint32_t)refresh_every;  // (the most iterations one solver launch of this set runs: the channel buffer is sized for it, not for ten)
   }
   MGF_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&T->pin), (8 * (size_t)n_local + 16 + 4 + 4 * (size_t)n_local) * 4, hipHostMallocDefault));
@@ -530,7 +530,7 @@ static mgf_status tiles_step_once(mgf_tiles* T, float dt, int32_t iters, mgf_ste
       if (!w->solve_pending || !w->stats.solver_kernel_launches || w->rb_fresh) continue;
       if (!w->ts->pin_dev) { TILE_TRY(solve_flow_fetch_enqueue(w)); continue; }
       FlagTile F;
-      F.src = w->d_err() + 2; F.dst = w->ts->pin_dev + mgf_world::kRbScalars + 3 + 2; F.words = 16; F.pad = 0;
+      F.src = w->word(kWSolverAbort); F.dst = w->ts->pin_dev + mgf_world::kRbScalars + mgf_world::kSolverFlagsFirst; F.words = mgf_world::kSolverFlagsWords; F.pad = 0;
       fl.push_back(F);
       w->rb_fresh = true;
     }
@@ -663,7 +663,7 @@ extern "C" mgf_status mgf_tiles_step(mgf_tiles* T, float dt, int32_t iters, mgf_
       S.B = w->bodies(); S.n = w->n_owned; S.pad = 0; S.snap = w->tick_snap.p;
       MGF_TRY(snapshot_batches(s, std::vector<SnapTile>{S}, std::vector<uint32_t>{nblk(w->n_owned)}, 1));
     }
-    MGF_HIP_TRY(hipMemsetAsync(w->d_err() + 2, 0, 4, s));  // the solvers' abort flag
+    MGF_HIP_TRY(hipMemsetAsync(w->word(kWSolverAbort), 0, 4, s));  // the solvers' abort flag
     if (w->abort_backoff == 0) { w->abort_backoff = w->abort_backoff_next; w->abort_backoff_next = std::min(2u * w->abort_backoff_next, 4096u); }
     ++w->n_solver_abort_fallbacks;
   }

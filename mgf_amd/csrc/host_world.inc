@@ -3,9 +3,72 @@
 // ---------------------------------------------------------------------------------------------
 // World
 // ---------------------------------------------------------------------------------------------
+// What mgf_world_set_option stores (the table behind it names every key; the keys that do more than store a value are code there).
+// mgf_world_clone copies the struct whole: an option added here is cloned.
+struct WorldOptions {
+  // the store's order and the cell grid
+  int64_t resort_every = -1;           // ticks between two re-sorts of the store in the fused tick; 0 = never; -1 = automatic
+  int64_t grid_min_frac_pct = 50;      // body grid: axes shorter than this percentage of the longest one are widened to it (grid_box)
+  int64_t cell_fill = 16;              // bodies per Morton cell (in eighths) beyond which the cell grid gets another level
+  bool cell_fill_set = false;          // the caller chose it (else a world with capsules uses 8: collide_prepare)
+  int64_t cells_in_integrate = 1;      // the fused tick: k_integrate works out the bodies' Morton cells and ranks (over last tick's bounds) - no k_morton_count launch
+  int64_t no_fused_scene_bounds = 0;   // 1: always the separate scene-bounds kernel
+  int64_t no_fused_terrain_rows = 0;   // 1: always a separate terrain candidate kernel
+  // the collide phase's paths
+  int64_t two_pass = 0;                // 1 = always use the exact two-pass candidate path (tests the overflow fallback)
+  int64_t terrain_tree = 0;            // 1 = always walk the mesh BVH (k_terrain_rows) instead of the face grid
+  int64_t broadphase_tree = 0;         // 1 = always walk the tree (k_pair_rows) instead of enumerating grid cells
+  int64_t pair_brick = 1;              // grid broadphase with the cells staged in LDS (k_pair_brick); 0 = every look-up from global memory (k_pair_grid)
+  int64_t no_fused_narrowphase = 0;
+  int64_t fused_contacts = 1;          // (r05) a world of spheres: rows -> constraint records in one launch, no candidate lists (k_contacts_spheres; 0: k_lists_spheres + k_setup_pairs)
+  int64_t front_rows = 1;              // (r06) worlds of single-component bodies that are not all spheres: the list-free front end (k_front_rows.h; 0: candidate lists, one narrowphase launch per shape-pair type)
+  int64_t front_rows_check = 0;        // tests: the faces k_terrain_near's cheap reject (comp_tri_far) drops go through the reference's tests as well; a contact among them is an internal error
+  int64_t side_stream = 1;             // (r06) the terrain kernels of the list-free front end on the context's second stream, beside the pair search (0: one stream)
+  // (r06) the wide bodies' list (WideSpec, k_bodies.h): engaged by the host when the scene's largest fat half extent jumps above 1.5 x what the
+  // bodies had so far, from the tick after; the limit then follows the bodies that are not wide
+  int64_t wide_list = 1;
+  // constraint order "demo" (= 1): the reference's own insertion order, world.rs:233-291 - the partners
+  // of body i in the DFS order of a world BVH that is refit (remove + insert) inside the loop.  Inherently sequential: the host
+  // replays it on the reference-faithful HostBvh and hands the partner rows to the device (small scenes: BASELINE config 1).
+  int64_t constraint_order = 0;
+  // the solver:
+  // 6 (default) = block-local dataflow launch with message channels (k_solve_flow6: every body a block touches, every arrival
+  //     counter and the ready queue in LDS; hand-offs across block faces are tagged messages), k_solve_flow as its stand-by;
+  // 5 = block-local dataflow launch k_solve_flow5 (bodies shared by two blocks and arrivals from other blocks go through
+  //     global memory), same stand-by;
+  // 1 = one persistent dataflow launch per Solver::solve, everything through L2 (k_solve_flow);
+  // 0 = one launch per frontier of the dependency graph (k_solve, the independent cross-check);
+  // 4 = dataflow launch with out-of-order slots per lane (k_solve_flowk)
+  int64_t solver_mode = 6;
+  int64_t flow_spin_limit = 0;         // tests: polls (x 256) a persistent launch waits before it gives up (0: the default, ~0.5 s)
+  int64_t flow_max_blocks = 0;         // the persistent launches use at most this many workgroups (0: one per CU): processes that share a device each take a part
+  int64_t flow_trace = 0;
+  int64_t flow5_block = 0;             // minimum bodies per block of the block-local solver (tests)
+  int64_t flow5_test_cap = 0;          // > 0: pretend a block of mode 5 holds at most this many constraints (tests: forces the k_solve_flow stand-by)
+  int64_t flow6_fcap = 0;              // > 0: foreign body slots per block (tests / experiments); 0 = chosen from the last tick
+  int64_t flow6_spec_wl = -1;          // worklist sweeps: positions behind the producers' hint read on spec (-1: by the launch's LDS plan)
+  int64_t flow6_spec = 0;              // positions behind a channel's head the polling wave's quiet sweep reads on spec (1..8; 0 = by the launch: 8 where the bodies'
+                                       // constants sit in LDS - configs 3 / 5, tiles: -1 % - and 4 where they do not: the settled pile loses 3 % at 8)
+  int64_t flow6_poll_waves = 0;        // polling waves per block (0: by the launch's LDS plan)
+  int64_t flow6_const_lds = 1;         // 1: the own bodies' inverse mass / inertia in LDS when the block's constraints leave room; 2: always; 0: never
+  int64_t flow6_foreign_lds = 1;       // mode 6: the FOREIGN bodies' inverse mass / inertia in LDS as well when there is room (k_solve_flow6<., 2, ...>)
+  int64_t flow6_quad = 1;              // mode 6: four lanes per node, the solve component-parallel with DPP quad permutes (k_solve_flow6<.., QD>)
+  int64_t flow6_quad_max = -1;         // ... while the ready queue holds at most this many nodes (more: a one-lane-per-node trip of up to 64); -1 = automatic (host_solver.inc: flow6_args)
+  int64_t flow6_slot_margin = 0;       // mode 6: what the LDS split allows a block's slots to grow over the last tick's largest block: 0 = an eighth + 64, v > 0 = 1 / v + 32 (experiments: tools/scratch/rl_calib.sh)
+  int64_t flow6_rec_lds = 1;           // mode 6: the solver half of every constraint record in LDS for the launch when the blocks' slots leave room (k_solve_flow6<.., RL>)
+  int64_t flow6_nimp_lds = 1;          // mode 6: the constraints' accumulated normal impulses in LDS for the launch when there is room
+  int64_t flow6_test_cap = 0;          // > 0: pretend a block holds at most this many constraints (tests: forces the stand-by kernel)
+  // the host's side of the tick
+  int64_t pipeline = 1;                // mgf_world_step_many enqueues tick k + 1 before it waits for tick k
+  int64_t readback_kernel = 1;         // the tick's read-back: k_publish writes pinned memory + a sequence word the host polls; 0 = hipMemcpyAsync + an event
+  int64_t stream_ordered = 0;          // 1: the tiling calls (begin_tick, export_*, import_*) do not synchronise the ctx stream
+  int64_t time_solver_kernels = 0;
+  int64_t phase_timing = 0;            // HIP events at the tick's phase boundaries (mgf_step_stats::ms_*): each is a barrier packet, ~8-15 us of an idle GPU - off unless asked for
+};
 struct mgf_world {
   mgf_ctx* ctx = nullptr;
   mgf_params params;
+  WorldOptions opt;
   uint32_t n = 0;        // local bodies = owned + ghosts of the current tick
   uint32_t n_owned = 0;  // bodies of this world's RigidBodyVec (added through add_bodies)
   bool has_sphere = false, has_capsule = false;
@@ -29,21 +92,17 @@ struct mgf_world {
   DBuf<float4> perm_tmp;
   bool permuted = false;
   bool sidx_valid = false;          // sidx (the last collide phase's cell order) names the current slots of the current bodies
-  int64_t opt_resort_every = -1;    // ticks between two re-sorts of the store in the fused tick; 0 = never; -1 = automatic
   uint64_t ticks_since_resort = 0, n_resorts = 0;
   std::vector<uint32_t> h_ext_of, h_slot_of;
   bool h_perm_valid = false;
   const uint32_t* ext_ptr() const { return permuted ? ext_of.p : nullptr; }
   DBuf<uint32_t> part_keys[2], part_vals[2];  // partition_order's sort buffers
-  int64_t opt_part_cell_x8 = 4;         // partition_order: the coarse cells along a level's axis, in eighths of the largest fat box's width there
-  int64_t opt_resort_partition = 1;     // 1: a re-sort orders the store by compact blocks (three-level split by counts); 0: by the last tick's cell order
   float h_scene_ext[3] = {0, 0, 0};     // extents of the scene at the last read-back (fat-box centres)
   float h_scene_rmax[3] = {0, 0, 0};    // ... and the largest fat half extents
   bool list_generic = false;            // the constraint list is a caller's (no per-body structure): the block-local solver's tables come from the generic builder (k_flow6g_*)
   DBuf<uint32_t> f6_cslot, f6_clist;
-  DBuf<uint32_t> iota;                  // 0, 1, 2, ...: "cell order = slots" for the block-local solver's tables (opt_flow6_slot_blocks)
+  DBuf<uint32_t> iota;                  // 0, 1, 2, ...: "cell order = slots" for the block-local solver's tables (a re-sorted store: its blocks are runs of slots)
   size_t iota_n = 0;
-  int64_t opt_flow6_slot_blocks = 1;    // a re-sorted store: the block-local solver cuts its blocks from the slots (the order of the last re-sort) instead of the tick's cell order
   DBuf<uint32_t> cnt_e, base_e, canon;  // the tick's list in insertion order (k_canon_*): for the executors that walk ids in order
   bool canon_ready = false;
   // terrain (copy of the caller's Mesh)
@@ -58,14 +117,7 @@ struct mgf_world {
   DBuf<LeafRec> leaves;
   DBuf<float4> ltb;              // cell-ordered tight boxes and cell regions (the queries of k_pair_brick)
   DBuf<float4> lcol;             // cell-ordered (collider, motion) copies for the fused sphere test of k_pair_grid
-  int64_t opt_no_fused_narrowphase = 0;
-  int64_t opt_grid_min_frac_pct = 50;  // body grid: axes shorter than this percentage of the longest one are widened to it (grid_box)
-  int64_t opt_merged_lists = 1;      // a world of spheres over a small mesh: candidate lists, terrain narrowphase and contact numbering in one launch (k_lists_spheres)
-  int64_t opt_cells_in_integrate = 1; // the fused tick: k_integrate works out the bodies' Morton cells and ranks (over last tick's bounds) - no k_morton_count launch
-  int64_t opt_front_rows = 1;        // (r06) worlds of single-component bodies that are not all spheres: the list-free front end (k_front_rows.h; 0: candidate lists, one narrowphase launch per shape-pair type)
-  // (r06) the wide bodies' list (WideSpec, k_bodies.h): engaged by the host when the scene's largest fat half extent jumps above 1.5 x what the
-  // bodies had so far, from the tick after; the limit then follows the bodies that are not wide
-  int64_t opt_wide_list = 1;
+  // the wide bodies' list (option wide_list): the host's state
   bool wide_engaged = false, wide_tick_on = false;
   float wide_ref[3] = {0, 0, 0}, wide_limit[3] = {0, 0, 0};
   float shape_rmax[3] = {0, 0, 0};   // the largest fat half extent the bodies had AT REST when they were added (the reference a world starts from)
@@ -83,12 +135,7 @@ struct mgf_world {
   DBuf<MovingIn> q_casts;
   uint32_t q_last_large = 0, q_last_cells = 0;
   float q_last_build_ms = 0.0f, q_last_run_ms = 0.0f;
-  int64_t opt_side_stream = 1;       // (r06) the terrain kernels of the list-free front end on the context's second stream, beside the pair search (0: one stream)
-  int64_t opt_front_rows_check = 0;  // tests: the faces k_terrain_near's cheap reject (comp_tri_far) drops go through the reference's tests as well; a contact among them is an internal error
-  bool front_rows_off = false;       // ... switched off for good: a body accepted more faces than k_terrain_near lists
-  int64_t opt_fused_contacts = 1;    // ... and (r05) rows -> constraint records in one launch, no candidate lists (k_contacts_spheres; 0: k_lists_spheres + k_setup_pairs)
-  int64_t opt_body_pack = 1;         // the constraint setup reads (collider, motion, info) from the packed per-tick copy (Bodies::bpk)
-  int64_t opt_pair_brick = 1;        // grid broadphase with the cells staged in LDS (k_pair_brick); 0 = every look-up from global memory (k_pair_grid)
+  bool front_rows_off = false;       // the list-free front end switched off for good: a body accepted more faces than k_terrain_near lists
   uint64_t pair_brick_slow = 0;      // last tick: queries k_pair_brick answered from global memory (one lane each: slow)
   uint32_t pair_brick_off = 0;       // ticks left during which k_pair_grid runs instead (too many such queries: cells much denser or bodies much larger than the box copy allows)
   uint32_t pair_brick_backoff = 256;
@@ -96,14 +143,6 @@ struct mgf_world {
   DBuf<float4> sub_lo, sub_hi, sub2_lo, sub2_hi;
   DBuf<uint32_t> cell_lo, cell_cnt;
   DBuf<uint32_t> t_cnt, p_cnt, t_off, p_off, t_cand, t_owner, p_cand, p_owner, rows, rows_t;
-  // 6 (default) = block-local dataflow launch with message channels (k_solve_flow6: every body a block touches, every arrival
-  //     counter and the ready queue in LDS; hand-offs across block faces are tagged messages), k_solve_flow as its stand-by;
-  // 5 = block-local dataflow launch k_solve_flow5 (bodies shared by two blocks and arrivals from other blocks go through
-  //     global memory), same stand-by;
-  // 1 = one persistent dataflow launch per Solver::solve, everything through L2 (k_solve_flow);
-  // 0 = one launch per frontier of the dependency graph (k_solve, the independent cross-check);
-  // 4 = dataflow launch with out-of-order slots per lane (k_solve_flowk)
-  int64_t opt_solver_mode = 6;
   DBuf<uint32_t> flow_arr, flow_arr5;
   DBuf<uint64_t> flow_trace;
   // block-local solver (mode 5)
@@ -147,8 +186,6 @@ struct mgf_world {
   DBuf<float4> tick_snap;          // mgf_tiles_step: what a tick changes of a tile's owned bodies before anything can go wrong (x, q, v / w, delta, fat box)
   uint64_t n_solver_abort_fallbacks = 0;
   uint32_t abort_backoff = 0, abort_backoff_next = 16;
-  int64_t opt_flow_spin_limit = 0;   // tests: polls (x 256) a persistent launch waits before it gives up (0: the default, ~0.5 s)
-  int64_t opt_flow_max_blocks = 0;   // the persistent launches use at most this many workgroups (0: one per CU): processes that share a device each take a part
   int flow_grid = 0;
   // device-resident list sizes + speculative capacities (see StepCounts)
   // Everything the host reads back at the tick's one synchronisation lives in ONE device block, fetched with one copy:
@@ -156,6 +193,9 @@ struct mgf_world {
   // of the partners accepted by the fused broadphase)]
   DBuf<uint32_t> rb;
   static constexpr uint32_t kRbSc = 0, kRbSb = 16, kRbScalars = 32, kRbPairStat = 64, kRbWords = 64 + kPairStatWords;
+  static_assert(kWLast < kRbPairStat - kRbScalars, "the flag words (FlagWord, common.h) lie inside the scalars block");
+  // the solvers' flags, abort .. mode 6's edge counts: the run of words a solve fetches by itself (solver_flags_fetch, the tile set's batched copy)
+  static constexpr uint32_t kSolverFlagsFirst = kWSolverAbort, kSolverFlagsWords = kWF6EdgesBlock - kWSolverAbort + 1;
   template <class T> struct View { T* p = nullptr; };
   View<StepCounts> sc;
   bool rb_fresh = false;         // the pinned copy of the block was fetched after the last solver launch was enqueued
@@ -170,39 +210,14 @@ struct mgf_world {
   uint32_t row_cap_t = kRowCapT;    // terrain faces per body in the row path (grows on overflow, sticky)
   bool terrain_grid_off = false;    // sticky: the mesh's faces span too many cells for the face grid (k_terrain_grid)
   bool grid_too_wide = false;       // sticky: the largest body spans too many Morton cells for the grid broadphase
-  int64_t opt_terrain_tree = 0;     // 1 = always walk the mesh BVH (k_terrain_rows) instead of the face grid
-  int64_t opt_broadphase_tree = 0;  // 1 = always walk the tree (k_pair_rows) instead of enumerating grid cells
-  int64_t opt_flow_blocks_per_cu = 0, opt_flow_sleep = 2;
   int flowk_grid = 0;
-  int64_t opt_debug_bvh = 0, opt_flow_trace = 0;
-  int64_t opt_flow5_slow_x2 = 3;
-  int64_t opt_flow5_poller = -1;   // 1: one slow wave only polls the outside-arrival counters; -1: with the narrow layout only (measured)
-  int64_t opt_flow5_test_cap = 0;   // > 0: pretend a block holds at most this many constraints (tests: forces the k_solve_flow stand-by)
-  int64_t opt_flow5_block = 0;     // minimum bodies per block of the block-local solver (tests)
-  int64_t opt_flow6_fcap = 0;      // > 0: foreign body slots per block (tests / experiments); 0 = chosen from the last tick
-  int64_t opt_flow6_poll_prio = 3;   // s_setprio of the polling waves
-  int64_t opt_flow6_spec_wl = -1;    // worklist sweeps: positions behind the producers' hint read on spec (-1: by the launch's LDS plan)
-  int64_t opt_flow6_spec = 0;        // positions behind a channel's head the polling wave's quiet sweep reads on spec (1..8; 0 = by the launch: 8 where the bodies'
-                                     // constants sit in LDS - configs 3 / 5, tiles: -1 % - and 4 where they do not: the settled pile loses 3 % at 8)
-  int64_t opt_flow6_poll_waves = 0, opt_flow6_poll_k = 2;  // polling waves per block (0: by the launch's LDS plan); 1: every sweep through the worklist, >= 2: quiet sweeps read the heads straight
-  int64_t opt_flow6_const_lds = 1;  // 1: the own bodies' inverse mass / inertia in LDS when the block's constraints leave room; 2: always; 0: never
   int f6_const_lds = 0;              // 0: the bodies' constants from global memory; 1: the own bodies' in LDS; 2: the foreign bodies' too
   bool f6_nimp_lds = false, f6_rec_lds = false;
-  int64_t opt_flow6_foreign_lds = 1; // mode 6: the FOREIGN bodies' inverse mass / inertia in LDS as well when there is room (k_solve_flow6<., 2, ...>)
   bool ptrs_out = false;             // mgf_world_device_ptr handed raw pointers out: the store keeps the caller's order until they are released
-  int64_t opt_flow6_quad_max = -1;   // -1 = automatic (host_solver.inc: flow6_args)  // ... while the ready queue holds at most this many nodes (more: a one-lane-per-node trip of up to 64)
-  int64_t opt_flow6_quad = 1;        // mode 6: four lanes per node, the solve component-parallel with DPP quad permutes (k_solve_flow6<.., QD>)
-  int64_t opt_flow6_slot_margin = 0; // mode 6: what the LDS split allows a block's slots to grow over the last tick's largest block: 0 = an eighth + 64, v > 0 = 1 / v + 32 (experiments: tools/scratch/rl_calib.sh)
-  int64_t opt_flow6_rec_lds = 1;     // mode 6: the solver half of every constraint record in LDS for the launch when the blocks' slots leave room (k_solve_flow6<.., RL>)
-  int64_t opt_flow6_nimp_lds = 1;    // mode 6: the constraints' accumulated normal impulses in LDS for the launch when there is room
   uint32_t f6_fail_reason = 0;     // bits of the last fall-back (Flow6::fail)
-  int64_t opt_flow6_test_cap = 0;  // > 0: pretend a block holds at most this many constraints (tests: forces the stand-by kernel)
   bool flow5_attr_set = false;
   bool flow5_wide = false;          // LDS layout of k_solve_flow5 for this tick (chosen from the largest block of the last one)
   uint32_t flow5_last_max = 0;
-  int64_t opt_cell_fill = 16;             // bodies per Morton cell (in eighths) beyond which the cell grid gets another level
-  bool opt_cell_fill_set = false;         // the caller chose it (else a world with capsules uses 8: collide_prepare)
-  int64_t opt_no_fused_scene_bounds = 0;  // 1: always the separate scene-bounds kernel
   uint32_t bounds_cover = 0;              // bodies [0, bounds_cover) are in the partial scene bounds gathered since this tick's k_integrate
                                           // (owned bodies, then imported ghosts); the next collide_enqueue uses them if that is every body
   uint32_t pack_cover = 0;                // bodies [0, pack_cover) have their bpk record written since this tick's k_integrate
@@ -213,20 +228,10 @@ struct mgf_world {
   bool sbg_valid = false;
   uint32_t cells_cover = 0, cells_levels = 0;  // bodies [0, cells_cover) have their cell and rank from this tick's k_integrate, for a grid of cells_levels
   DBuf<int> sb_part;                      // kBoundSlots partial scene-bounds records
-  int64_t opt_no_fused_terrain_rows = 0;  // 1: always a separate terrain candidate kernel
   bool terrain_rows_done = false;         // this tick's k_integrate wrote rows_t / t_cnt (consumed by the next collide_enqueue)
-  int64_t opt_pipeline = 1;        // mgf_world_step_many enqueues tick k + 1 before it waits for tick k
-  int64_t opt_readback_kernel = 1; // the tick's read-back: k_publish writes pinned memory + a sequence word the host polls; 0 = hipMemcpyAsync + an event
   uint32_t rb_seq = 0;
-  int64_t opt_spin_wait = 1;       // the tick's wait polls an event instead of blocking in hipStreamSynchronize
-  int64_t opt_stream_ordered = 0;  // 1: the tiling calls (begin_tick, export_*, import_*) do not synchronise the ctx stream
   bool solve_pending = false;      // a dataflow launch was enqueued by mgf_world_solve_enqueue and not yet checked
-  DBuf<unsigned long long> dbg;
-  int64_t opt_two_pass = 0;  // 1 = always use the exact two-pass candidate path (tests the overflow fallback)
-  // constraint order "demo" (option constraint_order = 1): the reference's own insertion order, world.rs:233-291 - the partners
-  // of body i in the DFS order of a world BVH that is refit (remove + insert) inside the loop.  Inherently sequential: the host
-  // replays it on the reference-faithful HostBvh and hands the partner rows to the device (small scenes: BASELINE config 1).
-  int64_t opt_constraint_order = 0;
+  // constraint order "demo" (option constraint_order = 1): the host's replay of world.rs
   HostBvh demo_tree;
   std::vector<uint64_t> demo_leaf;   // body -> its leaf in demo_tree
   bool demo_rows_ready = false;      // this tick's partner rows (rows / p_cnt) came from the host replay
@@ -249,7 +254,7 @@ struct mgf_world {
   DBuf<uint32_t> degb;           // per body: count ...
   DBuf<RevEnt> rev;              // ... and row (rev_cap entries) of the constraints it takes part in as `b`
   uint32_t rev_cap = 16;          // grows on overflow (kFailRevRow), sticky
-  View<uint32_t> scalars;  // [0..2] rotating level counters, [3] err
+  View<uint32_t> scalars;  // the flag words (FlagWord, common.h)
   View<SceneBounds> sb;
   uint32_t Mt = 0, Mp = 0, C = 0, Ct = 0, depth = 0, last_launches = 0, lvl_cap = 0;
   size_t order_cap_iters = 0;
@@ -257,8 +262,6 @@ struct mgf_world {
   float last_dt = 0.0f;
   float last_rmax_x = 0.0f;   // largest fat half extent along x among the tick's bodies, ghosts included (tiles: bounds the halo)
   float grid_occupancy = 1.0f;  // the part of the cell grid the scene actually covers (the last tick's bounds against the widened box: grid_box)
-  int64_t opt_time_solver_kernels = 0;
-  int64_t opt_phase_timing = 0;     // HIP events at the tick's phase boundaries (mgf_step_stats::ms_*): each is a barrier packet, ~8-15 us of an idle GPU - off unless asked for
   // Per-tick host state that must survive while the NEXT tick is already being enqueued (mgf_world_step_many): phase
   // events, solver-kernel events, the pinned landing area of the read-back block.  Two slots, `ts` is the current one.
   struct TickSlot {
@@ -277,6 +280,7 @@ struct mgf_world {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // the side stream's start and end inside the tick (no timing: created on first use)
     uint32_t* pin = nullptr;
     uint32_t* pin_dev = nullptr;      // the same memory as the device sees it (k_publish)
+    uint32_t word(FlagWord k) const { return pin[kRbScalars + k]; }  // the host copy of a flag word, once the read-back (or solver_flags_fetch) has landed
     uint32_t seq = 0;                 // the read-back in flight carries this sequence number in pin[kPinSeqWord] (0: an event, ev[7], instead)
   };
   static constexpr uint32_t kPinWords = 4096, kPinSeqWord = 4095;
@@ -293,38 +297,37 @@ struct mgf_world {
     B.xl0 = xl0.p; B.xl1 = xl1.p; B.xw0 = xw0.p; B.xw1 = xw1.p;
     return B;
   }
-  uint32_t* d_cnt() { return scalars.p; }
-  uint32_t* d_err() { return scalars.p + 3; }
+  uint32_t* word(FlagWord k) { return scalars.p + k; }  // a flag word's device address; its host copy: TickSlot::word
   uint32_t flow5_narrow_cap() const { return f5_narrow_cap(f5_nb); }  // slots of the narrow LDS layout at this block size
   Flow5 flow5() {
     Flow5 F;
     F.sidx = sidx.p; F.brank = brank.p; F.shared = reinterpret_cast<uint8_t*>(f5_shared.p);
     F.gcnt = f5_gcnt.p; F.arr5 = flow_arr5.p; F.lslot = f5_lslot.p; F.wg_cnt = f5_wg_cnt.p;
     F.table = f5_table.p;
-    F.fail = d_err() + 4; F.max_block = d_err() + 6;
+    F.fail = word(kWFlow5Fail); F.max_block = word(kWFlow5MaxBlock);
     F.cap_fast = flow5_wide ? kF5MaxFast : flow5_narrow_cap(); F.cap_slow = flow5_wide ? kF5MaxSlow : flow5_narrow_cap();
     F.cap_all = flow5_wide ? kF5MaxCons : flow5_narrow_cap();
-    if (opt_flow5_test_cap > 0) F.cap_all = std::min<uint32_t>(F.cap_all, (uint32_t)opt_flow5_test_cap);  // tests: force the stand-by path
-    F.slow_x2 = (uint32_t)opt_flow5_slow_x2;
-    F.poller = opt_flow5_poller < 0 ? (flow5_wide ? 0u : 1u) : (uint32_t)opt_flow5_poller;
+    if (opt.flow5_test_cap > 0) F.cap_all = std::min<uint32_t>(F.cap_all, (uint32_t)opt.flow5_test_cap);  // tests: force the stand-by path
+    F.slow_x2 = 3u;
+    F.poller = flow5_wide ? 0u : 1u;  // one slow wave only polls the outside-arrival counters: with the narrow layout only (measured)
     F.nb = f5_nb; F.nblocks = f5_nblocks; F.n = n;
     return F;
   }
   ConsLinks links() { ConsLinks K; K.ab = c_ab.p; K.succ = c_succ.p; K.pred = c_pred.p; return K; }
-  Frontier frontier() { Frontier F; F.order = order.p; F.lvl_off = lvl_off.p; F.cnt = d_cnt(); return F; }
+  Frontier frontier() { Frontier F; F.order = order.p; F.lvl_off = lvl_off.p; F.cnt = word(kWFrontier0); return F; }
 };
 // The tick's phase-boundary events (mgf_step_stats::ms_integrate .. ms_total).  A HIP event on this stack is a barrier packet with a
 // completion signal - 8 to 15 us of an idle GPU each, eight of them a tick (tools/trace_gaps.py: 45 us of a 0.81 ms tick) - so they
 // are recorded only on request (option "phase_timing"); the fields read 0 otherwise.  [7], the read-back's event, is not one of them.
 static mgf_status phase_mark(mgf_world* w, int k, hipStream_t s) {
-  if (!w->opt_phase_timing) return MGF_OK;
+  if (!w->opt.phase_timing) return MGF_OK;
   MGF_HIP_TRY(hipEventRecord(w->ts->ev[k], s));
   w->ts->ev_set |= 1u << k;
   return MGF_OK;
 }
 static mgf_status phase_ms(mgf_world* w, int a, int b, float* ms) {
   *ms = 0.0f;
-  if (!w->opt_phase_timing || (w->ts->ev_set & (1u << a)) == 0u || (w->ts->ev_set & (1u << b)) == 0u) return MGF_OK;
+  if (!w->opt.phase_timing || (w->ts->ev_set & (1u << a)) == 0u || (w->ts->ev_set & (1u << b)) == 0u) return MGF_OK;
   if (hipEventElapsedTime(ms, w->ts->ev[a], w->ts->ev[b]) != hipSuccess) { (void)hipGetLastError(); *ms = 0.0f; }  // (an event of another tick's slot: no figure)
   return MGF_OK;
 }
@@ -378,83 +381,87 @@ extern "C" void mgf_world_free(mgf_world* w) {
 }
 extern "C" int64_t mgf_world_len(const mgf_world* w) { return w ? (int64_t)w->n_owned : 0; }
 
+// The options that are a stored value.  lo > hi: any value is taken; else values outside [lo, hi] are refused with `range`.
+// plan: the option changes which kernels the collide phase takes.  Whatever this tick's k_integrate gathered (terrain rows, scene bounds,
+// packed records) was gathered under the old plan: such an option, set between mgf_world_begin_tick and mgf_world_collide, must not leave
+// rows of the other kind behind.  (Only those: the tile drivers set "body_kinds" at exactly that point of every tick - invalidating there
+// cost every tile-tick a second pass over the terrain rows and the scene bounds and the packed records, ~30 us.)
+// prep: the block-local solvers' preparation of the current list is stale.
+struct OptionEntry { const char* key; int64_t WorldOptions::*field; int64_t lo, hi; const char* range; bool plan, prep; };
+static const OptionEntry kOptionTable[] = {
+    {"time_solver_kernels", &WorldOptions::time_solver_kernels, 1, 0, nullptr, false, false},
+    {"two_pass_candidates", &WorldOptions::two_pass, 1, 0, nullptr, true, false},
+    {"broadphase_tree", &WorldOptions::broadphase_tree, 1, 0, nullptr, true, false},
+    {"terrain_tree", &WorldOptions::terrain_tree, 1, 0, nullptr, true, false},
+    {"no_fused_scene_bounds", &WorldOptions::no_fused_scene_bounds, 1, 0, nullptr, true, false},
+    {"no_fused_terrain_rows", &WorldOptions::no_fused_terrain_rows, 1, 0, nullptr, true, false},
+    {"grid_min_frac_pct", &WorldOptions::grid_min_frac_pct, 0, 100, "grid_min_frac_pct: 0..100", true, false},
+    {"no_fused_narrowphase", &WorldOptions::no_fused_narrowphase, 1, 0, nullptr, false, false},
+    {"pair_brick", &WorldOptions::pair_brick, 1, 0, nullptr, false, false},
+    {"fused_contacts", &WorldOptions::fused_contacts, 1, 0, nullptr, false, false},
+    {"front_rows", &WorldOptions::front_rows, 1, 0, nullptr, false, false},
+    {"front_rows_check", &WorldOptions::front_rows_check, 1, 0, nullptr, false, false},
+    {"side_stream", &WorldOptions::side_stream, 1, 0, nullptr, false, false},
+    {"cells_in_integrate", &WorldOptions::cells_in_integrate, 1, 0, nullptr, false, false},
+    {"solver_mode", &WorldOptions::solver_mode, 1, 0, nullptr, false, true},
+    {"flow_trace", &WorldOptions::flow_trace, 1, 0, nullptr, false, false},
+    {"flow_spin_limit", &WorldOptions::flow_spin_limit, 0, 4 << 20, "flow_spin_limit: 0 .. 4194304", false, false},
+    {"flow5_test_cap", &WorldOptions::flow5_test_cap, 1, 0, nullptr, false, false},
+    {"flow6_fcap", &WorldOptions::flow6_fcap, 0, 1536, "flow6_fcap out of range", false, false},
+    {"flow6_const_lds", &WorldOptions::flow6_const_lds, 1, 0, nullptr, false, false},
+    {"flow6_foreign_lds", &WorldOptions::flow6_foreign_lds, 1, 0, nullptr, false, false},
+    {"flow6_nimp_lds", &WorldOptions::flow6_nimp_lds, 1, 0, nullptr, false, false},
+    {"flow6_rec_lds", &WorldOptions::flow6_rec_lds, 1, 0, nullptr, false, false},
+    {"flow6_slot_margin", &WorldOptions::flow6_slot_margin, 0, 1024, "flow6_slot_margin: 0..1024", false, false},
+    {"flow6_quad", &WorldOptions::flow6_quad, 1, 0, nullptr, false, false},
+    {"flow6_quad_max", &WorldOptions::flow6_quad_max, -1, 1000000, "flow6_quad_max out of range", false, false},
+    {"flow6_test_cap", &WorldOptions::flow6_test_cap, 1, 0, nullptr, false, false},
+    {"flow6_spec_wl", &WorldOptions::flow6_spec_wl, -1, 8, "flow6_spec_wl: -1..8", false, false},
+    {"flow6_spec", &WorldOptions::flow6_spec, 0, 8, "flow6_spec: 0 (by the launch), 1..8", false, false},
+    {"flow6_poll_waves", &WorldOptions::flow6_poll_waves, 0, 4, "flow6_poll_waves out of range", false, false},
+    {"pipeline", &WorldOptions::pipeline, 1, 0, nullptr, false, false},
+    {"stream_ordered", &WorldOptions::stream_ordered, 1, 0, nullptr, false, false},
+};
 extern "C" mgf_status mgf_world_set_option(mgf_world* w, const char* key, int64_t value) {
   if (!w || !key) return fail(MGF_ERR_INVALID, "NULL argument");
-  // whatever this tick's k_integrate gathered (terrain rows, scene bounds, packed records) was gathered under the old plan: an
-  // option that changes the plan, set between mgf_world_begin_tick and mgf_world_collide, must not leave rows of the other kind
-  // behind.  (Only those: the tile drivers set "body_kinds" at exactly that point of every tick - invalidating there cost
-  // every tile-tick a second pass over the terrain rows and the scene bounds and the packed records, ~30 us.)
-  for (const char* plan_key : {"terrain_tree", "two_pass_candidates", "no_fused_terrain_rows", "no_fused_scene_bounds", "broadphase_tree", "constraint_order",
-                               "cell_fill", "grid_min_frac_pct"})
-    if (!strcmp(key, plan_key)) w->invalidate_tick_caches();
-  if (!strcmp(key, "time_solver_kernels")) { w->opt_time_solver_kernels = value; return MGF_OK; }
-  if (!strcmp(key, "phase_timing")) { w->opt_phase_timing = value != 0; for (auto& sl : w->slots) sl.ev_set = 0; return MGF_OK; }
-  if (!strcmp(key, "two_pass_candidates")) { w->opt_two_pass = value; return MGF_OK; }
+  for (const OptionEntry& e : kOptionTable) {
+    if (strcmp(key, e.key)) continue;
+    if (e.plan) w->invalidate_tick_caches();
+    if (e.lo <= e.hi && (value < e.lo || value > e.hi)) return fail(MGF_ERR_INVALID, e.range);
+    w->opt.*e.field = value;
+    if (e.prep) { w->flow5_prepped = false; w->flow6_prepped = false; }
+    return MGF_OK;
+  }
+  // the keys that do more than store a value
+  if (!strcmp(key, "phase_timing")) { w->opt.phase_timing = value != 0; for (auto& sl : w->slots) sl.ev_set = 0; return MGF_OK; }
+  if (!strcmp(key, "readback_kernel")) { w->opt.readback_kernel = value != 0; return MGF_OK; }
   if (!strcmp(key, "constraint_order")) {
+    w->invalidate_tick_caches();  // (it changes the plan)
     if (value != 0 && value != 1) return fail(MGF_ERR_INVALID, "constraint_order: 0 = canonical, 1 = demo (world.rs order)");
-    if (value != w->opt_constraint_order) { w->demo_tree.clear(); w->demo_leaf.clear(); }
-    w->opt_constraint_order = value;
+    if (value != w->opt.constraint_order) { w->demo_tree.clear(); w->demo_leaf.clear(); }
+    w->opt.constraint_order = value;
     if (value == 1) MGF_TRY(world_identity(w));  // (the replay walks the bodies in the caller's order)
     return MGF_OK;
   }
-  if (!strcmp(key, "broadphase_tree")) { w->opt_broadphase_tree = value; return MGF_OK; }
-  if (!strcmp(key, "terrain_tree")) { w->opt_terrain_tree = value; return MGF_OK; }
-  if (!strcmp(key, "flow_trace")) { w->opt_flow_trace = value; return MGF_OK; }
-  if (!strcmp(key, "debug_bvh")) { w->opt_debug_bvh = value; return MGF_OK; }
-  if (!strcmp(key, "solver_mode")) { w->opt_solver_mode = value; w->flow5_prepped = false; w->flow6_prepped = false; return MGF_OK; }
-  if (!strcmp(key, "flow6_fcap")) { if (value < 0 || value > 1536) return fail(MGF_ERR_INVALID, "flow6_fcap out of range"); w->opt_flow6_fcap = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_const_lds")) { w->opt_flow6_const_lds = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_nimp_lds")) { w->opt_flow6_nimp_lds = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_rec_lds")) { w->opt_flow6_rec_lds = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_slot_margin")) { if (value < 0 || value > 1024) return fail(MGF_ERR_INVALID, "flow6_slot_margin: 0..1024"); w->opt_flow6_slot_margin = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_quad")) { w->opt_flow6_quad = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_quad_max")) { if (value < -1 || value > 1000000) return fail(MGF_ERR_INVALID, "flow6_quad_max out of range"); w->opt_flow6_quad_max = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_foreign_lds")) { w->opt_flow6_foreign_lds = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_test_cap")) { w->opt_flow6_test_cap = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_poll_prio")) { if (value < 0 || value > 3) return fail(MGF_ERR_INVALID, "flow6_poll_prio: 0..3"); w->opt_flow6_poll_prio = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_spec_wl")) { if (value < -1 || value > 8) return fail(MGF_ERR_INVALID, "flow6_spec_wl: -1..8"); w->opt_flow6_spec_wl = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_spec")) { if (value < 0 || value > 8) return fail(MGF_ERR_INVALID, "flow6_spec: 0 (by the launch), 1..8"); w->opt_flow6_spec = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_poll_waves")) { if (value < 0 || value > 4) return fail(MGF_ERR_INVALID, "flow6_poll_waves out of range"); w->opt_flow6_poll_waves = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_poll_k")) { if (value < 1 || value > 4) return fail(MGF_ERR_INVALID, "flow6_poll_k out of range"); w->opt_flow6_poll_k = value; return MGF_OK; }
-  if (!strcmp(key, "flow_blocks_per_cu")) { w->opt_flow_blocks_per_cu = value; w->flow_grid = 0; w->flowk_grid = 0; return MGF_OK; }
-  if (!strcmp(key, "flow_sleep")) { w->opt_flow_sleep = value; return MGF_OK; }
-  if (!strcmp(key, "flow5_poller")) { w->opt_flow5_poller = value < 0 ? -1 : (value ? 1 : 0); return MGF_OK; }
-  if (!strcmp(key, "flow5_slow_x2")) { if (value < 1 || value > 16) return fail(MGF_ERR_INVALID, "flow5_slow_x2 out of range"); w->opt_flow5_slow_x2 = value; return MGF_OK; }
-  if (!strcmp(key, "flow5_test_cap")) { w->opt_flow5_test_cap = value; return MGF_OK; }
-  if (!strcmp(key, "flow5_block")) { w->opt_flow5_block = value; w->flow5_prepped = false; return MGF_OK; }
-  if (!strcmp(key, "no_fused_narrowphase")) { w->opt_no_fused_narrowphase = value; return MGF_OK; }
-  if (!strcmp(key, "pair_brick")) { w->opt_pair_brick = value; return MGF_OK; }
-  if (!strcmp(key, "merged_lists")) { w->opt_merged_lists = value; return MGF_OK; }
-  if (!strcmp(key, "fused_contacts")) { w->opt_fused_contacts = value; return MGF_OK; }
-  if (!strcmp(key, "front_rows")) { w->opt_front_rows = value; return MGF_OK; }
-  if (!strcmp(key, "side_stream")) { w->opt_side_stream = value; return MGF_OK; }
-  if (!strcmp(key, "wide_list")) { w->opt_wide_list = value; if (!value) w->wide_engaged = false; return MGF_OK; }
-  if (!strcmp(key, "front_rows_check")) { w->opt_front_rows_check = value; return MGF_OK; }
-  if (!strcmp(key, "cells_in_integrate")) { w->opt_cells_in_integrate = value; return MGF_OK; }
-  if (!strcmp(key, "flow_spin_limit")) { if (value < 0 || value > (4 << 20)) return fail(MGF_ERR_INVALID, "flow_spin_limit: 0 .. 4194304"); w->opt_flow_spin_limit = value; return MGF_OK; }
-  if (!strcmp(key, "flow_max_blocks")) {
-    if (value < 0 || value > 4096) return fail(MGF_ERR_INVALID, "flow_max_blocks: 0 (one workgroup per CU) .. 4096");
-    w->opt_flow_max_blocks = value; w->flow_grid = 0; w->flowk_grid = 0; w->flow5_prepped = false; w->flow6_prepped = false;
+  if (!strcmp(key, "cell_fill")) {
+    w->invalidate_tick_caches();  // (it changes the plan)
+    if (value < 1 || value > 1024) return fail(MGF_ERR_INVALID, "cell_fill out of range");
+    w->opt.cell_fill = value; w->opt.cell_fill_set = true;
     return MGF_OK;
   }
-  if (!strcmp(key, "body_pack")) { w->opt_body_pack = value; return MGF_OK; }
-  if (!strcmp(key, "grid_min_frac_pct")) { if (value < 0 || value > 100) return fail(MGF_ERR_INVALID, "grid_min_frac_pct: 0..100"); w->opt_grid_min_frac_pct = value; return MGF_OK; }
-  if (!strcmp(key, "cell_fill")) { if (value < 1 || value > 1024) return fail(MGF_ERR_INVALID, "cell_fill out of range"); w->opt_cell_fill = value; w->opt_cell_fill_set = true; return MGF_OK; }
-  if (!strcmp(key, "no_fused_scene_bounds")) { w->opt_no_fused_scene_bounds = value; return MGF_OK; }
-  if (!strcmp(key, "no_fused_terrain_rows")) { w->opt_no_fused_terrain_rows = value; return MGF_OK; }
-  if (!strcmp(key, "part_cell_x8")) { if (value < 0 || value > 64) return fail(MGF_ERR_INVALID, "part_cell_x8: 0..64"); w->opt_part_cell_x8 = value; return MGF_OK; }
-  if (!strcmp(key, "resort_partition")) { w->opt_resort_partition = value; return MGF_OK; }
-  if (!strcmp(key, "flow6_slot_blocks")) { w->opt_flow6_slot_blocks = value; return MGF_OK; }
+  if (!strcmp(key, "wide_list")) { w->opt.wide_list = value; if (!value) w->wide_engaged = false; return MGF_OK; }
+  if (!strcmp(key, "flow5_block")) { w->opt.flow5_block = value; w->flow5_prepped = false; return MGF_OK; }  // (mode 5's preparation alone, as ever)
+  if (!strcmp(key, "flow_max_blocks")) {
+    if (value < 0 || value > 4096) return fail(MGF_ERR_INVALID, "flow_max_blocks: 0 (one workgroup per CU) .. 4096");
+    w->opt.flow_max_blocks = value; w->flow_grid = 0; w->flowk_grid = 0; w->flow5_prepped = false; w->flow6_prepped = false;
+    return MGF_OK;
+  }
   if (!strcmp(key, "resort_every")) {  // the fused tick keeps the store in cell order, re-sorted every `value` ticks (host_perm.inc); 0 = the caller's order
     if (value < -1 || value > 1000000) return fail(MGF_ERR_INVALID, "resort_every out of range");
-    w->opt_resort_every = value;
+    w->opt.resort_every = value;
     if (value == 0) MGF_TRY(world_identity(w));
     return MGF_OK;
   }
-  if (!strcmp(key, "pipeline")) { w->opt_pipeline = value; return MGF_OK; }
-  if (!strcmp(key, "spin_wait")) { w->opt_spin_wait = value; return MGF_OK; }
-  if (!strcmp(key, "readback_kernel")) { w->opt_readback_kernel = value != 0; return MGF_OK; }
-  if (!strcmp(key, "stream_ordered")) { w->opt_stream_ordered = value; return MGF_OK; }
   if (!strcmp(key, "body_kinds")) {  // OR-in: kinds (bit0 sphere, bit1 capsule, bit2 several parts, bit3 more than two parts) that ghosts / arrivals of this world may have
     if (value & 1) w->has_sphere = true;
     if (value & 2) w->has_capsule = true;
@@ -605,9 +612,9 @@ extern "C" mgf_status mgf_world_counter(const mgf_world* w, const char* name, in
   if (!strcmp(name, "flow6_slot_cap")) { *out = (int64_t)w->f6_slot_cap; return MGF_OK; }
   if (!strcmp(name, "flow6_fcap")) { *out = (int64_t)w->f6_fcap; return MGF_OK; }
   if (!strcmp(name, "grid_too_wide")) { *out = w->grid_too_wide ? 1 : 0; return MGF_OK; }
-  if (!strcmp(name, "terrain_grid")) { *out = (w->terrain && w->terrain->grid.ready && !w->terrain_grid_off && !w->opt_terrain_tree) ? 1 : 0; return MGF_OK; }
+  if (!strcmp(name, "terrain_grid")) { *out = (w->terrain && w->terrain->grid.ready && !w->terrain_grid_off && !w->opt.terrain_tree) ? 1 : 0; return MGF_OK; }
   if (!strcmp(name, "terrain_row_capacity")) { *out = (int64_t)w->row_cap_t; return MGF_OK; }
-  if (!strcmp(name, "front_rows")) { *out = (w->opt_front_rows && !w->front_rows_off) ? 1 : 0; return MGF_OK; }
+  if (!strcmp(name, "front_rows")) { *out = (w->opt.front_rows && !w->front_rows_off) ? 1 : 0; return MGF_OK; }
   if (!strcmp(name, "front_near") || !strcmp(name, "front_slots") || !strcmp(name, "front_faces")) {  // the last tick's: bodies near the mesh, faces that passed the cheap reject, faces accepted
     mgf_world* mw = const_cast<mgf_world*>(w);
     uint32_t v = 0;
@@ -766,7 +773,7 @@ extern "C" mgf_status mgf_world_add_obstacle(mgf_world* w, const mgf_compound* c
   w->obstacles.push_back(std::move(o));
   std::vector<CompoundDev> h;
   std::vector<float4> hc;
-  for (auto& ob : w->obstacles) { h.push_back(ob->dev(w->d_err())); hc.push_back(make_float4(ob->disp.x, ob->disp.y, ob->disp.z, 0.0f)); }
+  for (auto& ob : w->obstacles) { h.push_back(ob->dev(w->word(kWStackOverflow))); hc.push_back(make_float4(ob->disp.x, ob->disp.y, ob->disp.z, 0.0f)); }
   MGF_TRY(w->d_obs.ensure(h.size(), w->ctx->stream)); MGF_TRY(w->d_obs_center.ensure(h.size(), w->ctx->stream));
   MGF_TRY(h2d(w->ctx, w->d_obs.p, h.data(), h.size())); MGF_TRY(h2d(w->ctx, w->d_obs_center.p, hc.data(), hc.size()));
   w->constraints_ready = false;
@@ -1124,6 +1131,6 @@ extern "C" mgf_status mgf_world_release_device_ptrs(mgf_world* w) {
 // returns); with option stream_ordered = 1 they only enqueue on the ctx stream - for a caller that issues its
 // own work (copies, RCCL) on that same stream (mgf_ctx_set_stream).
 static mgf_status sync_unless_ordered(mgf_world* w) {
-  if (!w->opt_stream_ordered) MGF_HIP_TRY(hipStreamSynchronize(w->ctx->stream));
+  if (!w->opt.stream_ordered) MGF_HIP_TRY(hipStreamSynchronize(w->ctx->stream));
   return MGF_OK;
 }

@@ -157,9 +157,9 @@ __global__ __launch_bounds__(kBlock) void k_tick_clear(ZeroList z, SceneBounds* 
                                                        int* sb_part) {
   // (see k_reset_step: a speculative tick behind a failed one raises the guard and resets nothing - but the counters are cleared all
   // the same: the kernels of the cell sort run unguarded, on the unchanged bodies, and must start from zero)
-  // (err[2]: the solvers' abort flag - a tick whose persistent launch gave up is solved again by the host, solver_abort_fallback; this
+  // (kWSolverAbort: the solvers' abort flag - a tick whose persistent launch gave up is solved again by the host, solver_abort_fallback; this
   // launch clears the flag below, its first wave has read it here)
-  const bool skip = spec && (*prev_fail || err[2]);
+  const bool skip = spec && (*prev_fail || err[err_at(kWSolverAbort)]);
   if (skip && blockIdx.x == 0 && threadIdx.x == 0) *guard = 1u;
   if (blockIdx.x == 0 && !skip) {
     if (sb_part && threadIdx.x < kBoundSlots) {
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void k_tick_clear(ZeroList z, SceneBounds* 
       for (int k = 0; k < 3; ++k) { sb->lo[k] = 0x7FFFFFFF; sb->hi[k] = (int)0x80000000; }
       sb->n_refits = 0; sb->pad = 0; sb->pad2 = 0;
       for (int k = 0; k < 3; ++k) sb->rmax[k] = 0;
-      err[0] = 0; err[1] = 0; err[8] = 0;
+      err[err_at(kWStackOverflow)] = 0; err[err_at(kWRowOverflow)] = 0; err[err_at(kWNarrowMismatch)] = 0;
     }
   }
   for (int a = 0; a < kZeroSlots; ++a) zero_words(z.p[a], z.words[a]);

@@ -62,6 +62,7 @@ constexpr uint32_t kTnHitCap = 128;  // faces a body's query may accept (more: t
 // The slots of the tick are handed out from kTnRegions counters, a block uses the one of its XCD (blockIdx & 7): one counter for all
 // cost the launch 13 ns per workgroup (returning atomics on one word serialise) - 2 500 of them - however short the blocks' own work.
 constexpr uint32_t kTnRegions = 8, kTnCntStride = 32;  // (words between counters: a cache line)
+constexpr int kTnLanes = 16;  // lanes that share a body's query in k_terrain_near (its LANES)
 constexpr uint32_t kTnFarBit = 0x40000000u;  // a hit that comp_tri_far rejects (DFS ranks are below 2^30)
 struct TerrainNear {
   TerrainDev M; FaceGrid G;

@@ -285,3 +285,57 @@ def test_handles_outlive_a_destroyed_context():
     w2 = mgf_amd.World.from_scene(c2, sc)
     assert w2.step(float(sc["dt"]), sc["iters"]).n_constraints >= 0
     c2.close()
+
+
+# (not among them: "flow5_test_cap" - tests/test_gpu_parity.py sets it, as f"flow{mode}_test_cap", to force mode 5's stand-by kernel: it stays)
+RETIRED_OPTIONS = ("body_pack", "debug_bvh", "flow5_poller", "flow5_slow_x2", "flow6_poll_k", "flow6_poll_prio",
+                   "flow6_slot_blocks", "flow_blocks_per_cu", "flow_sleep", "merged_lists", "part_cell_x8", "resort_partition", "spin_wait")
+
+
+def test_retired_option_keys_are_unknown(ctx):
+    """The option keys that nothing set are gone from mgf_world_set_option's table: each is refused like any unknown key
+    (MGF_ERR_INVALID), a key that stayed is taken."""
+    w = mgf_amd.World.from_scene(ctx, scenes.sphere_pile(1, 1, 1))
+    for key in RETIRED_OPTIONS:
+        with pytest.raises(mgf_amd.MgfError) as e:
+            w.set_option(key, 1)
+        assert e.value.status == mgf_amd._capi.ERR_INVALID and "unknown option" in str(e.value), (key, str(e.value))
+    for key in ("pair_brick", "flow5_test_cap"):
+        w.set_option(key, 0)
+
+
+def _same_state(a, b):
+    sa, sb = a.state(), b.state()
+    return all(bits_equal(sa[k], sb[k]) for k in ("x", "q", "v", "omega", "delta"))
+
+
+def test_a_clone_takes_its_sources_options(ctx):
+    """mgf_world_clone copies the options whole: a clone of a world with non-default options steps bit-identically to its source and
+    never takes the paths the options switched off (its path counters start at 0 and stay there)."""
+    sc = scenes.sphere_pile(8, 8, 8)
+    dt, iters = float(sc["dt"]), sc["iters"]
+    w = mgf_amd.World.from_scene(ctx, sc)
+    for key, v in (("pair_brick", 0), ("cells_in_integrate", 0), ("solver_mode", 1)):
+        w.set_option(key, v)
+    for _ in range(2):
+        w.step(dt, iters)
+    c = w.clone()
+    for _ in range(3):
+        w.step(dt, iters)
+        c.step(dt, iters)
+    assert _same_state(w, c)
+    assert c.counter("pair_brick_ticks") == 0 and c.counter("early_cells_ticks") == 0
+    assert w.counter("pair_brick_ticks") == 0 and w.counter("early_cells_ticks") == 0
+
+    sc = scenes.capsule_field(8, 4, 8)
+    dt, iters = float(sc["dt"]), sc["iters"]
+    w = mgf_amd.World.from_scene(ctx, sc)
+    w.set_option("front_rows", 0)
+    for _ in range(2):
+        w.step(dt, iters)
+    c = w.clone()
+    for _ in range(3):
+        w.step(dt, iters)
+        c.step(dt, iters)
+    assert _same_state(w, c)
+    assert c.counter("front_rows_ticks") == 0 and w.counter("front_rows_ticks") == 0
