@@ -324,7 +324,8 @@ MGF_API mgf_status mgf_world_sweep_many(mgf_world* w, const mgf_moving_component
                                         int32_t kinds_mask, mgf_sweep_hit* out);
 /* Box overlap: per mgf_aabb every owned body whose tight bound BoundedBy<AABB> (bounds.rs:170-190; for a body of several components
  * the union of its parts' bounds) passes Overlaps<AABB> (collision.rs:22), in ascending caller index: out_bodies[out_offsets[q] ..
- * out_offsets[q+1]).  As mgf_bvh_query_many: out_offsets and *total are always filled; MGF_ERR_CAPACITY if *total > cap. */
+ * out_offsets[q+1]); a box with a NaN or a negative half extent answers as that test does.  As mgf_bvh_query_many: out_offsets and
+ * *total are always filled; MGF_ERR_CAPACITY if *total > cap. */
 MGF_API mgf_status mgf_world_overlap_aabb_many(mgf_world* w, const mgf_aabb* boxes, int64_t n, uint64_t* out_offsets /* n+1 */,
                                                uint32_t* out_bodies, int64_t cap, int64_t* total);
 /* The Solver's constraint list of the last tick, in insertion order. */
@@ -560,8 +561,8 @@ MGF_API mgf_status mgf_world_release_device_ptrs(mgf_world* w);
  * worlds than the device holds workgroups, and it is safe on a device shared with another process.
  * LIMITS: bodies of one component (spheres and capsules); at most MGF_BATCH_MAX_BODIES bodies per world (a call that would exceed it
  * is refused with MGF_ERR_INVALID and adds nothing); one terrain mesh shared by every world (copied, its position included; NULL =
- * none); canonical constraint order only.  There are no bodies of several components, no obstacles, no ghosts or tiles, no
- * constraint_order = demo and no box-overlap query: a batch has no entry point for them.  A tick never fails for list sizes: a world whose
+ * none); canonical constraint order only.  There are no bodies of several components, no obstacles, no ghosts or tiles and no
+ * constraint_order = demo: a batch has no entry point for them.  A tick never fails for list sizes: a world whose
  * constraints outgrow its share of the storage gets its tick undone on the device and run again with more (Solver::solve and
  * World::step have no capacity failure, solver.rs:72-78); mgf_batch_counter "capacity_retries" counts those re-runs.
  * Calls are synchronous on the context's stream; the handle keeps a reference on the context; there is no CPU fallback. */
@@ -614,6 +615,38 @@ MGF_API mgf_status mgf_batch_raycast_many(mgf_batch* b, const int32_t* world, co
                                           const int32_t* ignore_body, int32_t kinds_mask, mgf_ray_hit* out);
 MGF_API mgf_status mgf_batch_sweep_many(mgf_batch* b, const int32_t* world, const mgf_moving_component* casts, int64_t n,
                                         const int32_t* ignore_body, int32_t kinds_mask, mgf_sweep_hit* out);
+/* ---- what a caller reads of a batch every tick besides rays and sweeps: who touches what and how hard, who is in this box ----
+ * mgf_batch_read_body_contacts: the constraint list of the last tick folded per body, on the device, beside the list.  The struct and
+ * its definition are this build's: the reference has no such report (its Solver keeps the list, solver.rs:53-79, and World::step fills
+ * it, world.rs:243-291; nothing there sums it per body).  The list described is exactly the one mgf_batch_read_constraints would return
+ * for that world at that moment: the last tick's, in insertion order; empty before the first tick and, for every world, once bodies have
+ * been added behind a tick; unchanged by mgf_batch_write_state.  Per body x, over the records that name x in the order of its chain -
+ * its own range of the list first (x is `a`), then the records where x is `b`, ascending: the order ContactConstraint::solve
+ * (solver.rs:203-252) meets them in - with impulse and normal_impulse starting at +0 and t = (normal.x * ni, normal.y * ni,
+ * normal.z * ni), ni = the record's normal_impulse, in f32:  x is `a`: impulse = impulse - t (va -= impulse * inv_mass_a,
+ * solver.rs:243-247); x is `b`: impulse = impulse + t; in both roles normal_impulse = normal_impulse + ni.  Sequential f32
+ * operations in that order, no fused multiply-add: the answer is defined to the bit, and a body in no record gets an all-zero record.
+ * Tangent impulses are not part of it: mgf_constraint does not carry them. */
+typedef struct mgf_body_contacts {
+  int32_t n_contacts;     /* records of the list that name the body, as a or as b */
+  int32_t n_terrain;      /* of those, records against RigidBodyRef::Static (b = -1; the body is a) */
+  mgf_vec3 impulse;       /* net accumulated normal impulse on the body, see above */
+  float normal_impulse;   /* sum of the records' normal_impulse */
+} mgf_body_contacts;      /* 24 bytes */
+/* world: one world, or -1 for the whole batch, worlds concatenated in order (as mgf_batch_read_state); cap: records `out` holds.
+ * MGF_ERR_INVALID: a NULL batch, NULL out, a world index < -1 or >= n_worlds; MGF_ERR_CAPACITY: cap below the number of bodies.
+ * One kernel launch whatever the number of worlds and bodies, one copy, one host wait (counters "query_launches", "query_run_ns"). */
+MGF_API mgf_status mgf_batch_read_body_contacts(mgf_batch* b, int64_t world, mgf_body_contacts* out, int64_t cap);
+/* Box overlap, as mgf_world_overlap_aabb_many: box i against world world[i] (any order, any mix) reports every body of that world whose
+ * tight bound BoundedBy<AABB> (bounds.rs:170-190) of the collider a query sees (above) passes Overlaps<AABB> (collision.rs:22-29),
+ * in ascending body index within the world, at out_bodies[out_offsets[i] .. out_offsets[i+1]) - bit for bit what
+ * mgf_world_overlap_aabb_many reports on a lone world with that world's bodies after the same calls.  A box with a NaN or a negative
+ * half extent answers as the single test does.  out_offsets and *total are always filled; MGF_ERR_CAPACITY if *total > cap.
+ * Refused with MGF_ERR_INVALID: a NULL batch, NULL arrays with n > 0, NULL out_offsets, a negative n or cap, a world index < 0 or
+ * >= n_worlds, n > INT32_MAX.  The kernel launches of a call depend on neither n_worlds nor n ("query_launches": the collider gather
+ * behind a step, count, fill; the prefix sum between them is the library's). */
+MGF_API mgf_status mgf_batch_overlap_aabb_many(mgf_batch* b, const int32_t* world, const mgf_aabb* boxes, int64_t n,
+                                               uint64_t* out_offsets /* n+1 */, uint32_t* out_bodies, int64_t cap, int64_t* total);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's)}. */

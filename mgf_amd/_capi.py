@@ -110,6 +110,9 @@ assert RAY_HIT_DTYPE.itemsize == 28
 # mgf_sweep_hit: kind (HIT_*), index, part, contact = (a, b, n, t)
 SWEEP_HIT_DTYPE = np.dtype([("kind", "<i4"), ("index", "<i4"), ("part", "<i4"), ("a", "<f4", 3), ("b", "<f4", 3), ("n", "<f4", 3), ("t", "<f4")])
 assert SWEEP_HIT_DTYPE.itemsize == 52
+# mgf_body_contacts
+BODY_CONTACTS_DTYPE = np.dtype([("n_contacts", "<i4"), ("n_terrain", "<i4"), ("impulse", "<f4", 3), ("normal_impulse", "<f4")])
+assert BODY_CONTACTS_DTYPE.itemsize == 24
 HIT_NONE, HIT_BODY, HIT_TERRAIN, HIT_OBSTACLE = -1, 0, 1, 2
 BATCH_MAX_BODIES = 1024  # MGF_BATCH_MAX_BODIES
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
@@ -145,6 +148,7 @@ SYMBOLS = [
     "mgf_batch_new", "mgf_batch_free", "mgf_batch_set_terrain", "mgf_batch_add_bodies", "mgf_batch_len", "mgf_batch_step",
     "mgf_batch_read_state", "mgf_batch_write_state", "mgf_batch_read_constraints", "mgf_batch_counter", "mgf_batch_set_option",
     "mgf_batch_read_colliders", "mgf_batch_raycast_many", "mgf_batch_sweep_many",
+    "mgf_batch_read_body_contacts", "mgf_batch_overlap_aabb_many",
 ]
 
 _lib = None
@@ -291,6 +295,8 @@ def load_library():
         "mgf_batch_read_colliders": (i32, [vp, i64, vp, i64]),
         "mgf_batch_raycast_many": (i32, [vp, vp, vp, i64, vp, i32, vp]),
         "mgf_batch_sweep_many": (i32, [vp, vp, vp, i64, vp, i32, vp]),
+        "mgf_batch_read_body_contacts": (i32, [vp, i64, vp, i64]),
+        "mgf_batch_overlap_aabb_many": (i32, [vp, vp, vp, i64, vp, vp, i64, P(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1304,6 +1310,41 @@ class WorldBatch:
         _check(load_library().mgf_batch_sweep_many(self._h, wd.ctypes.data, casts.ctypes.data, n, ign.ctypes.data if ign is not None else None,
                                                    int(kinds), out.ctypes.data))
         return out
+
+    def body_contacts(self, world=None):
+        """the last tick's constraint list folded per body (mgf_batch_read_body_contacts): a BODY_CONTACTS_DTYPE array for one world, or
+        (world=None) for the whole batch, worlds concatenated in order"""
+        w = -1 if world is None else int(world)
+        out = np.zeros(max(load_library().mgf_batch_len(self._h, w), 0), BODY_CONTACTS_DTYPE)
+        _check(load_library().mgf_batch_read_body_contacts(self._h, w, out.ctypes.data, len(out)))
+        return out
+
+    def overlap_aabb(self, world, lo, hi):
+        """As World.overlap_aabb, box i against world[i] (a scalar: all against that world) of the batch (mgf_batch_overlap_aabb_many):
+        (offsets[n + 1], bodies) in CSR form, each list in ascending body index within the box's world."""
+        lo = np.asarray(lo, np.float32).reshape(-1, 3)
+        hi = np.asarray(hi, np.float32).reshape(-1, 3)
+        boxes = np.empty((len(lo), 6), np.float32)
+        boxes[:, 0:3] = (hi + lo) / np.float32(2)
+        boxes[:, 3:6] = (hi - lo) / np.float32(2)
+        return self.overlap_boxes(world, boxes)
+
+    def overlap_boxes(self, world, boxes, cap=None):
+        """overlap_aabb for mgf_aabb rows (c.xyz, r.xyz) as given; cap None sizes the output from a first call's count."""
+        boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+        n = len(boxes)
+        wd = np.ascontiguousarray(np.broadcast_to(np.asarray(world, np.int32), (n,)))
+        off = np.zeros(n + 1, np.uint64)
+        total = C.c_int64()
+        lib = load_library()
+        if cap is None:
+            st = lib.mgf_batch_overlap_aabb_many(self._h, wd.ctypes.data, boxes.ctypes.data, n, off.ctypes.data, None, 0, C.byref(total))
+            if st not in (0, ERR_CAPACITY):
+                _check(st)
+            cap = total.value
+        vals = np.zeros(max(int(cap), 1), np.uint32)
+        _check(lib.mgf_batch_overlap_aabb_many(self._h, wd.ctypes.data, boxes.ctypes.data, n, off.ctypes.data, vals.ctypes.data, int(cap), C.byref(total)))
+        return off.astype(np.int64), vals[:total.value].copy()
 
     def counter(self, name):
         v = C.c_int64()

@@ -38,6 +38,7 @@ struct mgf_batch {
   bool cols_stale = false;
   DBuf<float4> q_in;
   DBuf<int32_t> q_out;
+  DBuf<uint32_t> q_cnt, q_off, q_vals;  // mgf_batch_overlap_aabb_many: hits per box, their prefix sums, the lists
   hipEvent_t q_ev[2] = {nullptr, nullptr};
   int64_t q_launches = 0;
   float q_run_ms = 0.0f;

@@ -38,6 +38,26 @@ static mgf_status batch_query_args(const mgf_batch* b, const int32_t* world, con
   return MGF_OK;
 }
 
+// the query indices of a call by world, in the caller's order within a world (one stable counting sort); work items of up to 256 queries
+struct BatchQueryPlan {
+  std::vector<uint32_t> start;  // world k's queries at the sorted positions [start[k], start[k + 1])
+  size_t n_items = 0;
+  BatchQueryPlan(uint32_t K, const int32_t* world, size_t n) : start((size_t)K + 1, 0u) {
+    for (size_t i = 0; i < n; ++i) ++start[(size_t)world[i] + 1];
+    for (uint32_t k = 0; k < K; ++k) start[k + 1] += start[k];
+    for (uint32_t k = 0; k < K; ++k) n_items += (start[k + 1] - start[k] + 255u) / 256u;
+  }
+  // items[n_items] = (world, first, count <= 256, -); order[n]: sorted position -> the caller's query index
+  void fill(const int32_t* world, size_t n, uint4* items, uint32_t* order) const {
+    const uint32_t K = (uint32_t)start.size() - 1u;
+    size_t at = 0;
+    for (uint32_t k = 0; k < K; ++k)
+      for (uint32_t f = start[k]; f < start[k + 1]; f += 256u) items[at++] = make_uint4(k, f, std::min(256u, start[k + 1] - f), 0u);
+    std::vector<uint32_t> cur(start.begin(), start.end() - 1);
+    for (size_t i = 0; i < n; ++i) order[cur[(size_t)world[i]]++] = (uint32_t)i;
+  }
+};
+
 // Q = ParticleIn (7 words out) or MovingIn (13 words out)
 template <class Q>
 static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* queries, int64_t n_in, const int32_t* ignore_body, int32_t kinds_mask,
@@ -56,26 +76,14 @@ static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* q
   hipStream_t s = ctx->stream;
   for (hipEvent_t& e : b->q_ev)
     if (!e) MGF_HIP_TRY(hipEventCreate(&e));
-  // the query indices by world, in the caller's order within a world; work items of up to 256 queries
-  std::vector<uint32_t> start((size_t)K + 1, 0u);
-  for (size_t i = 0; i < n; ++i) ++start[(size_t)world[i] + 1];
-  for (uint32_t k = 0; k < K; ++k) start[k + 1] += start[k];
-  size_t n_items = 0;
-  for (uint32_t k = 0; k < K; ++k) n_items += (start[k + 1] - start[k] + 255u) / 256u;
+  const BatchQueryPlan plan(K, world, n);
+  const size_t n_items = plan.n_items;
   // one upload: items | queries | order | ignore, every section from a 16-byte boundary
   const size_t w_items = n_items, w_q = (n * sizeof(Q) + 15) / 16, w_idx = (4 * n + 15) / 16;
   const size_t o_q = w_items, o_order = o_q + w_q, o_ign = o_order + w_idx, total = o_ign + (ignore_body ? w_idx : 0);
   std::vector<float4> h(total);
-  uint4* items = reinterpret_cast<uint4*>(h.data());
-  size_t at = 0;
-  for (uint32_t k = 0; k < K; ++k)
-    for (uint32_t f = start[k]; f < start[k + 1]; f += 256u) items[at++] = make_uint4(k, f, std::min(256u, start[k + 1] - f), 0u);
   memcpy(h.data() + o_q, queries, n * sizeof(Q));
-  uint32_t* order = reinterpret_cast<uint32_t*>(h.data() + o_order);
-  {
-    std::vector<uint32_t> cur(start.begin(), start.end() - 1);
-    for (size_t i = 0; i < n; ++i) order[cur[(size_t)world[i]]++] = (uint32_t)i;
-  }
+  plan.fill(world, n, reinterpret_cast<uint4*>(h.data()), reinterpret_cast<uint32_t*>(h.data() + o_order));
   if (ignore_body) memcpy(h.data() + o_ign, ignore_body, 4 * n);
   MGF_TRY(b->q_in.ensure(total, s));
   MGF_TRY(b->q_out.ensure(kOut * n, s));

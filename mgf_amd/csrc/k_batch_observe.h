@@ -1,0 +1,142 @@
+// What a caller reads of a batch between ticks besides rays and sweeps (mgf_batch_read_body_contacts, mgf_batch_overlap_aabb_many;
+// host_batch_observe.inc).  (Part of the kernel set described in kernels.h.)
+//   k_batch_observe_contacts  a workgroup per world of the requested range folds the world's constraint list per body (mgf_body_contacts):
+//                             the counts, the net normal impulse -normal * normal_impulse where the body is `a` (solver.rs:243-247) and
+//                             +normal * normal_impulse where it is `b`, and the sum of the normal impulses, in the body's chain order -
+//                             its own range of the list, then its `b` occurrences ascending, the order k_batch_solve builds.  The
+//                             ranges are rebuilt from the records on every call (na, degb and rows are the tick's scratch, and the
+//                             lists may have moved since: batch_allot carries the records only): per body the length of its own range
+//                             and how often it is `b` by integer atomics in LDS, the range's start by a prefix sum, the `b` occurrences
+//                             into `rows` in whatever order the lanes come and then sorted per body.  A lane per body walks its chain
+//                             with sequential f32 adds: nothing of the answer depends on lane scheduling, and there is no float atomic.
+//                             Of the tick's state only `rows` is written - every tick rebuilds it.
+//   k_batch_observe_overlap<FILL>
+//                             a workgroup per work item = (world, up to 256 boxes) of the queries' sort by world (batch_query_plan).
+//                             The tight bounds BoundedBy<AABB> (bounds.rs:170-190) of the world's colliders col0 / col1 staged in LDS
+//                             once; a box gets min(64, 256 / (count rounded up to a power of two)) lanes of one wave, which take the
+//                             bodies in chunks of that many, ascending; Overlaps<AABB> (collision.rs:22-29) per lane, and a hit's place
+//                             within its chunk is its rank in the wave's ballot: the list of a box is in ascending body index whatever
+//                             the lane split.  Count (FILL = false), the scan of prims.hip, fill.
+// No workgroup waits for another.
+#pragma once
+#include "k_batch_query.h"
+
+namespace mgf {
+
+struct BatchContactsArgs {
+  const CRec* cons;         // world k's list at c_off[k], c_count[k] records
+  uint32_t* rows;           // same offsets: the `b` occurrences of every body of the world (CSR), rebuilt here
+  const uint32_t* c_off;
+  const uint32_t* c_count;
+  const uint32_t* w_off;
+  uint32_t world0;          // workgroup g answers for world world0 + g ...
+  uint32_t* out;            // ... six words a body (mgf_body_contacts), the body w_off[world0] first
+};
+
+// LDS (dynamic): four words a body.
+__global__ __launch_bounds__(kBatchBlock) void k_batch_observe_contacts(BatchContactsArgs A) {
+  extern __shared__ float4 s_dyn[];
+  __shared__ uint32_t s_tot;
+  const uint32_t k = A.world0 + blockIdx.x, T = kBatchBlock, tid = threadIdx.x;
+  const uint32_t g0 = A.w_off[k], n = A.w_off[k + 1] - g0, C = A.c_count[k];
+  uint32_t* s_first = reinterpret_cast<uint32_t*>(s_dyn);
+  uint32_t *s_na = s_first + n, *s_boff = s_first + 2 * (size_t)n, *s_cur = s_first + 3 * (size_t)n;
+  const CRec* cons = A.cons + A.c_off[k];
+  uint32_t* rows = A.rows + A.c_off[k];
+  for (uint32_t i = tid; i < n; i += T) { s_na[i] = 0u; s_boff[i] = 0u; s_cur[i] = 0u; }
+  __syncthreads();
+  for (uint32_t c = tid; c < C; c += T) {
+    const uint32_t a = cons[c].a, b = cons[c].b;
+    atomicAdd(&s_na[a], 1u);
+    if (b != kNone) atomicAdd(&s_boff[b], 1u);
+  }
+  __syncthreads();
+  for (uint32_t i = tid; i < n; i += T) s_first[i] = s_na[i];
+  batch_scan(s_first, n, &s_tot);  // body i's own range: contiguous (the list is in the order of its `a`), from the prefix sum of the lengths
+  batch_scan(s_boff, n, &s_tot);
+  for (uint32_t c = tid; c < C; c += T) {
+    const uint32_t b = cons[c].b;
+    if (b != kNone) rows[s_boff[b] + atomicAdd(&s_cur[b], 1u)] = c;
+  }
+  __syncthreads();
+  uint32_t* out = A.out + 6 * (size_t)(g0 - A.w_off[A.world0]);
+  for (uint32_t x = tid; x < n; x += T) {
+    uint32_t* row = rows + s_boff[x];
+    const uint32_t nb = s_cur[x], na = s_na[x], first = s_first[x];
+    for (uint32_t a = 1; a < nb; ++a) {  // ascending list index, whatever order the lanes came in
+      const uint32_t v = row[a];
+      uint32_t b = a;
+      while (b > 0 && row[b - 1] > v) { row[b] = row[b - 1]; --b; }
+      row[b] = v;
+    }
+    V3 imp = mk3(0.0f, 0.0f, 0.0f);
+    float sum = 0.0f;
+    uint32_t n_terrain = 0;
+    for (uint32_t c = first; c < first + na; ++c) {
+      const CRec* r = &cons[c];
+      const float ni = r->nimp;
+      imp = imp - ld3(r->n) * ni;  // va -= impulse * inv_mass_a, solver.rs:243-247
+      sum = sum + ni;
+      if (r->b == kNone) ++n_terrain;
+    }
+    for (uint32_t e = 0; e < nb; ++e) {
+      const CRec* r = &cons[row[e]];
+      const float ni = r->nimp;
+      imp = imp + ld3(r->n) * ni;
+      sum = sum + ni;
+    }
+    uint32_t* o = out + 6 * (size_t)x;
+    o[0] = na + nb; o[1] = n_terrain; o[2] = f2u(imp.x); o[3] = f2u(imp.y); o[4] = f2u(imp.z); o[5] = f2u(sum);
+  }
+}
+
+struct BatchOverlapArgs {
+  const float4* col0;     // as BatchQueryArgs
+  const float4* col1;
+  const uint32_t* w_off;
+  const uint4* items;
+  const uint32_t* order;
+  const float* boxes;     // by the caller's index: c.xyz, r.xyz
+  uint32_t* cnt;          // by the caller's index: the hits of box i (written when !FILL) ...
+  const uint32_t* off;    // ... their exclusive prefix sums (read when FILL)
+  uint32_t* out;          // the bodies of box i at off[i], ascending
+};
+
+// LDS (dynamic): 32 bytes a body.
+template <bool FILL>
+__global__ __launch_bounds__(kBatchBlock) void k_batch_observe_overlap(BatchOverlapArgs A) {
+  extern __shared__ float4 s_dyn[];
+  const uint4 it = A.items[blockIdx.x];
+  const uint32_t tid = threadIdx.x, g0 = A.w_off[it.x], n = A.w_off[it.x + 1] - g0;
+  float4 *s_c = s_dyn, *s_r = s_dyn + n;
+  for (uint32_t i = tid; i < n; i += kBatchBlock) {
+    const float4 a = A.col0[(size_t)g0 + i], b = A.col1[(size_t)g0 + i];
+    Comp c; c.kind = (int)f2u(b.w); c.p = xyz(a); c.d = xyz(b); c.r = a.w;
+    const Box tb = comp_bounds(c);
+    s_c[i] = mk4(tb.c, 0.0f); s_r[i] = mk4(tb.r, 0.0f);
+  }
+  __syncthreads();
+  const uint32_t sh = min(bq_lane_shift(it.z), 6u), L = 1u << sh, j = tid >> sh, sub = tid & (L - 1u);
+  const bool live = j < it.z;
+  const uint32_t qi = live ? A.order[it.y + j] : 0u;
+  Box Q; Q.c = mk3(0.0f, 0.0f, 0.0f); Q.r = Q.c;
+  if (live) { Q.c = ld3(A.boxes + 6 * (size_t)qi); Q.r = ld3(A.boxes + 6 * (size_t)qi + 3); }
+  const uint32_t base = (FILL && live) ? A.off[qi] : 0u;
+  const uint32_t shift = (tid & 63u) - sub;                        // the first lane of the box's group within the wave
+  const uint64_t group = L == 64u ? ~0ull : ((1ull << L) - 1ull);  // the group's lanes, from that lane
+  uint32_t m = 0;
+  for (uint32_t i0 = 0; i0 < n; i0 += L) {  // (n and L are the work item's: every lane of the wave makes every trip)
+    const uint32_t i = i0 + sub;
+    bool hit = false;
+    if (live && i < n) {
+      Box b; b.c = xyz(s_c[i]); b.r = xyz(s_r[i]);
+      hit = box_overlaps(b, Q);
+    }
+    const uint64_t g = ((uint64_t)__ballot(hit) >> shift) & group;
+    if (FILL && hit) A.out[base + m + (uint32_t)__popcll(g & ((1ull << sub) - 1ull))] = i;
+    m += (uint32_t)__popcll(g);
+  }
+  if (!FILL && live && sub == 0u) A.cnt[qi] = m;
+}
+
+}  // namespace mgf

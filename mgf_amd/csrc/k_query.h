@@ -592,7 +592,9 @@ __global__ __launch_bounds__(kBlock) void k_query_overlap(QueryGrid G, const uin
     }
     if (!outside) {
       int lo[3], hi[3];
-      q_cell_range(Q, G, lo, hi);
+      Box Qc = Q;  // (a negative half extent: Overlaps can still hold, and only for a body whose box holds Q.c - the cells of Q.c, not an empty range)
+      Qc.r = mk3(fmaxf(Q.r.x, 0.0f), fmaxf(Q.r.y, 0.0f), fmaxf(Q.r.z, 0.0f));
+      q_cell_range(Qc, G, lo, hi);
       for (int z = lo[2]; z <= hi[2]; ++z)
         for (int y = lo[1]; y <= hi[1]; ++y)
           for (int x = lo[0]; x <= hi[0]; ++x) {

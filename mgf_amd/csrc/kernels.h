@@ -80,6 +80,10 @@
 //   k_batch_query_gather / _ray / _sweep_bodies / _sweep_faces (k_batch_query.h)
 //                      ray casts and sweeps against the worlds of a batch (mgf_batch_raycast_many / _sweep_many): a workgroup per (world,
 //                      up to 256 queries), the world's colliders in LDS, 256 / count lanes a query, the mesh tree walked without a stack
+//   k_batch_observe_contacts / _overlap<FILL> (k_batch_observe.h)
+//                      what else a caller reads of a batch every tick: the constraint list of every world folded per body
+//                      (mgf_batch_read_body_contacts: a workgroup per world, the per-body ranges rebuilt in LDS, a lane per body walks its
+//                      chain) and the bodies in a box (mgf_batch_overlap_aabb_many: the world's tight boxes in LDS, ballot-rank compaction)
 //   k_query_* (k_query.h) ray casts and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid of
 //                      the bodies' current tight boxes built per call (never the tick's lists)
 //
@@ -92,3 +96,4 @@
 #include "k_query.h"  // the world queries between ticks (k_query_*), beside the tick
 #include "k_batch.h"  // many small worlds, a workgroup each (k_batch_*), beside the one-world tick
 #include "k_batch_query.h"  // the queries of k_query.h for the worlds of a batch (k_batch_query_*)
+#include "k_batch_observe.h"  // per-body contact summaries and box overlaps of a batch (k_batch_observe_*)
