@@ -843,6 +843,66 @@ class Solver:
         return world.stats
 
 
+# ---- marshalling shared by the queries of World and WorldBatch ------------------------------------------------------------------
+def _per_query(v, n, optional=False, dtype=np.int32):
+    """a value per query (world, ignore): a scalar or one row for all, or n rows; optional: None stays None (no ignore list)"""
+    return None if optional and v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype), (n,)))
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _particle_rows(p, d, dt):
+    """mgf_particle rows (p.xyz, d.xyz, dt) from rows of p; d and dt are rows, or one for all"""
+    p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+    parts = np.empty((len(p), 7), np.float32)
+    parts[:, 0:3] = p
+    parts[:, 3:6] = np.broadcast_to(np.asarray(d, np.float32), p.shape)
+    parts[:, 6] = np.broadcast_to(np.asarray(dt, np.float32), (len(p),))
+    return parts
+
+
+def _cast_rows(comps, delta):
+    """MOVING_DTYPE rows from COMPONENT_DTYPE rows swept by delta (rows, or one vector for all), or from a MOVING_DTYPE array as it is"""
+    comps = np.asarray(comps)
+    if comps.dtype == MOVING_DTYPE:
+        if delta is not None:
+            raise ValueError("a MOVING_DTYPE array carries its own delta")
+        return np.ascontiguousarray(comps.reshape(-1))
+    comps = np.asarray(comps, COMPONENT_DTYPE).reshape(-1)
+    casts = np.zeros(len(comps), MOVING_DTYPE)
+    for k in ("tag", "p", "d", "r"):
+        casts[k] = comps[k]
+    casts["delta"] = np.broadcast_to(np.asarray(0.0 if delta is None else delta, np.float32), (len(comps), 3))
+    return casts
+
+
+def _boxes_from_corners(lo, hi):
+    """mgf_aabb rows c = (hi + lo) / 2, r = (hi - lo) / 2 in f32"""
+    lo = np.asarray(lo, np.float32).reshape(-1, 3)
+    hi = np.asarray(hi, np.float32).reshape(-1, 3)
+    boxes = np.empty((len(lo), 6), np.float32)
+    boxes[:, 0:3] = (hi + lo) / np.float32(2)
+    boxes[:, 3:6] = (hi - lo) / np.float32(2)
+    return boxes
+
+
+def _overlap_lists(call, n, cap):
+    """(offsets[n + 1], bodies) of call(off, vals, cap, total) - an overlap entry point with everything but its output bound; cap None
+    sizes the output from a first call's count"""
+    off = np.zeros(n + 1, np.uint64)
+    total = C.c_int64()
+    if cap is None:
+        st = call(off.ctypes.data, None, 0, C.byref(total))
+        if st not in (0, ERR_CAPACITY):
+            _check(st)
+        cap = total.value
+    vals = np.zeros(max(int(cap), 1), np.uint32)
+    _check(call(off.ctypes.data, vals.ctypes.data, int(cap), C.byref(total)))
+    return off.astype(np.int64), vals[:total.value].copy()
+
+
 class World:
     """RigidBodyVec + Solver + terrain + broadphase resident on one GPU; `step` is
     mgf_demo/world.rs::World::step."""
@@ -984,19 +1044,10 @@ class World:
         """Closest hit of each particle (rows of p, d; dt = inf: a Ray, 1: a Segment from p to p + d) against the bodies, the terrain
         and the obstacles (mgf_world_raycast_many): a RAY_HIT_DTYPE array, kind HIT_NONE where nothing is hit.  ignore: None or a
         caller body index per particle (-1: none); kinds: QUERY_* bits."""
-        p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(np.broadcast_to(np.asarray(d, np.float32), p.shape))
-        n = len(p)
-        parts = np.empty((n, 7), np.float32)
-        parts[:, 0:3] = p
-        parts[:, 3:6] = d
-        parts[:, 6] = np.broadcast_to(np.asarray(dt, np.float32), (n,))
-        ign = None
-        if ignore is not None:
-            ign = np.ascontiguousarray(np.broadcast_to(np.asarray(ignore, np.int32), (n,)))
-        out = np.zeros(n, RAY_HIT_DTYPE)
-        _check(load_library().mgf_world_raycast_many(self._h, parts.ctypes.data, n, ign.ctypes.data if ign is not None else None,
-                                                     int(kinds), out.ctypes.data))
+        parts = _particle_rows(p, d, dt)
+        ign = _per_query(ignore, len(parts), optional=True)
+        out = np.zeros(len(parts), RAY_HIT_DTYPE)
+        _check(load_library().mgf_world_raycast_many(self._h, parts.ctypes.data, len(parts), _ptr(ign), int(kinds), out.ctypes.data))
         return out
 
     def sweep(self, comps, delta=None, ignore=None, kinds=QUERY_ALL):
@@ -1004,51 +1055,22 @@ class World:
         SWEEP_HIT_DTYPE array, kind HIT_NONE where nothing is met.  comps: COMPONENT_DTYPE rows swept by delta (rows, or one vector for
         all), or a MOVING_DTYPE array that carries its own delta (then delta is None); ignore: None or a caller body index per cast
         (-1: none); kinds: QUERY_* bits."""
-        comps = np.asarray(comps)
-        if comps.dtype == MOVING_DTYPE:
-            if delta is not None:
-                raise ValueError("a MOVING_DTYPE array carries its own delta")
-            casts = np.ascontiguousarray(comps.reshape(-1))
-        else:
-            comps = np.asarray(comps, COMPONENT_DTYPE).reshape(-1)
-            casts = np.zeros(len(comps), MOVING_DTYPE)
-            for k in ("tag", "p", "d", "r"):
-                casts[k] = comps[k]
-            casts["delta"] = np.broadcast_to(np.asarray(0.0 if delta is None else delta, np.float32), (len(comps), 3))
-        n = len(casts)
-        ign = None
-        if ignore is not None:
-            ign = np.ascontiguousarray(np.broadcast_to(np.asarray(ignore, np.int32), (n,)))
-        out = np.zeros(n, SWEEP_HIT_DTYPE)
-        _check(load_library().mgf_world_sweep_many(self._h, casts.ctypes.data, n, ign.ctypes.data if ign is not None else None,
-                                                   int(kinds), out.ctypes.data))
+        casts = _cast_rows(comps, delta)
+        ign = _per_query(ignore, len(casts), optional=True)
+        out = np.zeros(len(casts), SWEEP_HIT_DTYPE)
+        _check(load_library().mgf_world_sweep_many(self._h, casts.ctypes.data, len(casts), _ptr(ign), int(kinds), out.ctypes.data))
         return out
 
     def overlap_aabb(self, lo, hi):
         """The bodies whose tight box overlaps each box [lo, hi] (rows; mgf_world_overlap_aabb_many): (offsets[n + 1], bodies) in CSR
         form, each list in ascending caller index.  The box handed over is the mgf_aabb c = (hi + lo) / 2, r = (hi - lo) / 2 in f32."""
-        lo = np.asarray(lo, np.float32).reshape(-1, 3)
-        hi = np.asarray(hi, np.float32).reshape(-1, 3)
-        boxes = np.empty((len(lo), 6), np.float32)
-        boxes[:, 0:3] = (hi + lo) / np.float32(2)
-        boxes[:, 3:6] = (hi - lo) / np.float32(2)
-        return self.overlap_boxes(boxes)
+        return self.overlap_boxes(_boxes_from_corners(lo, hi))
 
     def overlap_boxes(self, boxes, cap=None):
         """overlap_aabb for mgf_aabb rows (c.xyz, r.xyz) as given; cap None sizes the output from a first call's count."""
         boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
-        n = len(boxes)
-        off = np.zeros(n + 1, np.uint64)
-        total = C.c_int64()
-        lib = load_library()
-        if cap is None:
-            st = lib.mgf_world_overlap_aabb_many(self._h, boxes.ctypes.data, n, off.ctypes.data, None, 0, C.byref(total))
-            if st not in (0, ERR_CAPACITY):
-                _check(st)
-            cap = total.value
-        vals = np.zeros(max(int(cap), 1), np.uint32)
-        _check(lib.mgf_world_overlap_aabb_many(self._h, boxes.ctypes.data, n, off.ctypes.data, vals.ctypes.data, int(cap), C.byref(total)))
-        return off.astype(np.int64), vals[:total.value].copy()
+        fn = load_library().mgf_world_overlap_aabb_many
+        return _overlap_lists(lambda *o: fn(self._h, boxes.ctypes.data, len(boxes), *o), len(boxes), cap)
 
     def constraints(self):
         n = C.c_int64()
@@ -1271,44 +1293,19 @@ class WorldBatch:
     def raycast(self, world, p, d, dt=float("inf"), ignore=None, kinds=QUERY_ALL):
         """As World.raycast, particle i against world[i] (a scalar: all against that world) of the batch (mgf_batch_raycast_many): a
         RAY_HIT_DTYPE array; index and ignore are body indices within the particle's world."""
-        p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(np.broadcast_to(np.asarray(d, np.float32), p.shape))
-        n = len(p)
-        parts = np.empty((n, 7), np.float32)
-        parts[:, 0:3] = p
-        parts[:, 3:6] = d
-        parts[:, 6] = np.broadcast_to(np.asarray(dt, np.float32), (n,))
-        wd = np.ascontiguousarray(np.broadcast_to(np.asarray(world, np.int32), (n,)))
-        ign = None
-        if ignore is not None:
-            ign = np.ascontiguousarray(np.broadcast_to(np.asarray(ignore, np.int32), (n,)))
-        out = np.zeros(n, RAY_HIT_DTYPE)
-        _check(load_library().mgf_batch_raycast_many(self._h, wd.ctypes.data, parts.ctypes.data, n, ign.ctypes.data if ign is not None else None,
-                                                     int(kinds), out.ctypes.data))
+        parts = _particle_rows(p, d, dt)
+        wd, ign = _per_query(world, len(parts)), _per_query(ignore, len(parts), optional=True)
+        out = np.zeros(len(parts), RAY_HIT_DTYPE)
+        _check(load_library().mgf_batch_raycast_many(self._h, wd.ctypes.data, parts.ctypes.data, len(parts), _ptr(ign), int(kinds), out.ctypes.data))
         return out
 
     def sweep(self, world, comps, delta=None, ignore=None, kinds=QUERY_ALL):
         """As World.sweep, cast i against world[i] (a scalar: all against that world) of the batch (mgf_batch_sweep_many): a
         SWEEP_HIT_DTYPE array; index and ignore are body indices within the cast's world."""
-        comps = np.asarray(comps)
-        if comps.dtype == MOVING_DTYPE:
-            if delta is not None:
-                raise ValueError("a MOVING_DTYPE array carries its own delta")
-            casts = np.ascontiguousarray(comps.reshape(-1))
-        else:
-            comps = np.asarray(comps, COMPONENT_DTYPE).reshape(-1)
-            casts = np.zeros(len(comps), MOVING_DTYPE)
-            for k in ("tag", "p", "d", "r"):
-                casts[k] = comps[k]
-            casts["delta"] = np.broadcast_to(np.asarray(0.0 if delta is None else delta, np.float32), (len(comps), 3))
-        n = len(casts)
-        wd = np.ascontiguousarray(np.broadcast_to(np.asarray(world, np.int32), (n,)))
-        ign = None
-        if ignore is not None:
-            ign = np.ascontiguousarray(np.broadcast_to(np.asarray(ignore, np.int32), (n,)))
-        out = np.zeros(n, SWEEP_HIT_DTYPE)
-        _check(load_library().mgf_batch_sweep_many(self._h, wd.ctypes.data, casts.ctypes.data, n, ign.ctypes.data if ign is not None else None,
-                                                   int(kinds), out.ctypes.data))
+        casts = _cast_rows(comps, delta)
+        wd, ign = _per_query(world, len(casts)), _per_query(ignore, len(casts), optional=True)
+        out = np.zeros(len(casts), SWEEP_HIT_DTYPE)
+        _check(load_library().mgf_batch_sweep_many(self._h, wd.ctypes.data, casts.ctypes.data, len(casts), _ptr(ign), int(kinds), out.ctypes.data))
         return out
 
     def body_contacts(self, world=None):
@@ -1322,29 +1319,14 @@ class WorldBatch:
     def overlap_aabb(self, world, lo, hi):
         """As World.overlap_aabb, box i against world[i] (a scalar: all against that world) of the batch (mgf_batch_overlap_aabb_many):
         (offsets[n + 1], bodies) in CSR form, each list in ascending body index within the box's world."""
-        lo = np.asarray(lo, np.float32).reshape(-1, 3)
-        hi = np.asarray(hi, np.float32).reshape(-1, 3)
-        boxes = np.empty((len(lo), 6), np.float32)
-        boxes[:, 0:3] = (hi + lo) / np.float32(2)
-        boxes[:, 3:6] = (hi - lo) / np.float32(2)
-        return self.overlap_boxes(world, boxes)
+        return self.overlap_boxes(world, _boxes_from_corners(lo, hi))
 
     def overlap_boxes(self, world, boxes, cap=None):
         """overlap_aabb for mgf_aabb rows (c.xyz, r.xyz) as given; cap None sizes the output from a first call's count."""
         boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
-        n = len(boxes)
-        wd = np.ascontiguousarray(np.broadcast_to(np.asarray(world, np.int32), (n,)))
-        off = np.zeros(n + 1, np.uint64)
-        total = C.c_int64()
-        lib = load_library()
-        if cap is None:
-            st = lib.mgf_batch_overlap_aabb_many(self._h, wd.ctypes.data, boxes.ctypes.data, n, off.ctypes.data, None, 0, C.byref(total))
-            if st not in (0, ERR_CAPACITY):
-                _check(st)
-            cap = total.value
-        vals = np.zeros(max(int(cap), 1), np.uint32)
-        _check(lib.mgf_batch_overlap_aabb_many(self._h, wd.ctypes.data, boxes.ctypes.data, n, off.ctypes.data, vals.ctypes.data, int(cap), C.byref(total)))
-        return off.astype(np.int64), vals[:total.value].copy()
+        wd = _per_query(world, len(boxes))
+        fn = load_library().mgf_batch_overlap_aabb_many
+        return _overlap_lists(lambda *o: fn(self._h, wd.ctypes.data, boxes.ctypes.data, len(boxes), *o), len(boxes), cap)
 
     def counter(self, name):
         v = C.c_int64()

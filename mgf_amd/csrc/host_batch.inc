@@ -39,10 +39,9 @@ struct mgf_batch {
   DBuf<float4> q_in;
   DBuf<int32_t> q_out;
   DBuf<uint32_t> q_cnt, q_off, q_vals;  // mgf_batch_overlap_aabb_many: hits per box, their prefix sums, the lists
-  hipEvent_t q_ev[2] = {nullptr, nullptr};
+  QueryEvents q_tm;  // 0 | a query pass | 1
   int64_t q_launches = 0;
   float q_run_ms = 0.0f;
-  ~mgf_batch() { for (hipEvent_t e : q_ev) if (e) (void)hipEventDestroy(e); }
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {

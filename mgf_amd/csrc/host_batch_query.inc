@@ -5,6 +5,8 @@
 // uploads items, queries, order and ignore list in ONE copy, launches a workgroup per work item - the number of launches depends on
 // neither the number of worlds nor the number of queries - and downloads the hits: one host wait per call.  Nothing of the tick's state
 // is written; of it only bpk is read, once, by the collider gather behind a mgf_batch_step (batch_cols_refresh).
+// batch_query_args / _worlds / _open / _upload are every front end's steps ahead of its launches, the box query's
+// (host_batch_observe.inc) too; the kinds_mask and tag checks are host_query.inc's.
 
 extern "C" mgf_status mgf_batch_read_colliders(mgf_batch* b, int64_t world, mgf_moving_component* out, int64_t cap) {
   if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
@@ -26,13 +28,15 @@ extern "C" mgf_status mgf_batch_read_colliders(mgf_batch* b, int64_t world, mgf_
   return MGF_OK;
 }
 
-// the checks of a query call that need neither the handle's contents nor a device
-static mgf_status batch_query_args(const mgf_batch* b, const int32_t* world, const void* q, int64_t n, int32_t kinds_mask, const void* out) {
+// the checks of a query call that need neither the handle's contents nor a device (q: the queries; out: where the call's answers go)
+static mgf_status batch_query_args(const mgf_batch* b, const int32_t* world, const void* q, int64_t n, const void* out) {
   if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
   if (n < 0) return fail(MGF_ERR_INVALID, "n is negative");
   if (n && (!world || !q || !out)) return fail(MGF_ERR_INVALID, "NULL argument");
-  if (kinds_mask <= 0 || (kinds_mask & ~MGF_QUERY_ALL)) return fail(MGF_ERR_INVALID, "kinds_mask must be a non-empty set of MGF_QUERY_* bits");
-  if (n > (int64_t)INT32_MAX) return fail(MGF_ERR_INVALID, "too many queries in one call");
+  return MGF_OK;
+}
+static mgf_status batch_query_worlds(const int32_t* world, int64_t n, const char* too_many) {
+  if (n > (int64_t)INT32_MAX) return fail(MGF_ERR_INVALID, too_many);
   for (int64_t i = 0; i < n; ++i)
     if (world[i] < 0) return fail(MGF_ERR_INVALID, "world index out of range");
   return MGF_OK;
@@ -58,59 +62,80 @@ struct BatchQueryPlan {
   }
 };
 
+// the checks that need the handle; the call's counters start from zero
+static mgf_status batch_query_open(mgf_batch* b, const int32_t* world, size_t n) {
+  MGF_TRY(ctx_bind(b->ctx));
+  for (size_t i = 0; i < n; ++i)
+    if ((uint32_t)world[i] >= b->K) return fail(MGF_ERR_INVALID, "world index out of range");
+  b->q_launches = 0; b->q_run_ms = 0.0f;
+  return MGF_OK;
+}
+
+// What the ray, sweep and box queries do ahead of their launches (n > 0): the bodies added since pushed, the plan, ONE upload -
+// items | queries | order | ignore, every section from a 16-byte boundary - and the colliders refreshed behind a tick.
+struct BatchQueryUpload {
+  size_t n_items = 0;
+  const float4* queries = nullptr;  // the caller's q_bytes a query, in the caller's order
+  const int32_t* ignore = nullptr;  // null: none given
+  uint32_t lds = 0;                 // 32 bytes a body of the largest world (at most 32 KB)
+  std::vector<float4> host;         // what the copy reads: alive until the call has waited for the stream
+};
+static mgf_status batch_query_upload(mgf_batch* b, const int32_t* world, const void* queries, size_t q_bytes, size_t n, const int32_t* ignore_body,
+                                     BatchWorkArgs* A, BatchQueryUpload* U) {
+  MGF_TRY(batch_push(b));
+  hipStream_t s = b->ctx->stream;
+  const BatchQueryPlan plan(b->K, world, n);
+  const size_t w_q = (n * q_bytes + 15) / 16, w_idx = (4 * n + 15) / 16;
+  const size_t o_q = plan.n_items, o_order = o_q + w_q, o_ign = o_order + w_idx, total = o_ign + (ignore_body ? w_idx : 0);
+  std::vector<float4>& h = U->host;
+  h.resize(total);
+  memcpy(h.data() + o_q, queries, n * q_bytes);
+  plan.fill(world, n, reinterpret_cast<uint4*>(h.data()), reinterpret_cast<uint32_t*>(h.data() + o_order));
+  if (ignore_body) memcpy(h.data() + o_ign, ignore_body, 4 * n);
+  MGF_TRY(b->q_in.ensure(total, s));
+  MGF_HIP_TRY(hipMemcpyAsync(b->q_in.p, h.data(), 16 * total, hipMemcpyHostToDevice, s));
+  MGF_TRY(batch_cols_refresh(b, &b->q_launches));
+  uint32_t nmax = 0;
+  for (uint32_t c : b->h_n) nmax = std::max(nmax, c);
+  A->col0 = b->dm[mgf_batch::ACOL0].p; A->col1 = b->dm[mgf_batch::ACOL1].p; A->w_off = b->d_off.p;
+  A->items = reinterpret_cast<const uint4*>(b->q_in.p);
+  A->order = reinterpret_cast<const uint32_t*>(b->q_in.p + o_order);
+  U->n_items = plan.n_items; U->queries = b->q_in.p + o_q;
+  U->ignore = ignore_body ? reinterpret_cast<const int32_t*>(b->q_in.p + o_ign) : nullptr;
+  U->lds = 32u * nmax;
+  return MGF_OK;
+}
+
 // Q = ParticleIn (7 words out) or MovingIn (13 words out)
 template <class Q>
 static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* queries, int64_t n_in, const int32_t* ignore_body, int32_t kinds_mask,
                                   int32_t* out) {
   constexpr bool kRays = std::is_same<Q, ParticleIn>::value;
   constexpr size_t kOut = kRays ? 7 : 13;
-  MGF_TRY(ctx_bind(b->ctx));
-  const uint32_t K = b->K;
   const size_t n = (size_t)n_in;
-  for (size_t i = 0; i < n; ++i)
-    if ((uint32_t)world[i] >= K) return fail(MGF_ERR_INVALID, "world index out of range");
-  b->q_launches = 0; b->q_run_ms = 0.0f;
+  MGF_TRY(batch_query_open(b, world, n));
   if (n == 0) return MGF_OK;
-  MGF_TRY(batch_push(b));
-  mgf_ctx* ctx = b->ctx;
-  hipStream_t s = ctx->stream;
-  for (hipEvent_t& e : b->q_ev)
-    if (!e) MGF_HIP_TRY(hipEventCreate(&e));
-  const BatchQueryPlan plan(K, world, n);
-  const size_t n_items = plan.n_items;
-  // one upload: items | queries | order | ignore, every section from a 16-byte boundary
-  const size_t w_items = n_items, w_q = (n * sizeof(Q) + 15) / 16, w_idx = (4 * n + 15) / 16;
-  const size_t o_q = w_items, o_order = o_q + w_q, o_ign = o_order + w_idx, total = o_ign + (ignore_body ? w_idx : 0);
-  std::vector<float4> h(total);
-  memcpy(h.data() + o_q, queries, n * sizeof(Q));
-  plan.fill(world, n, reinterpret_cast<uint4*>(h.data()), reinterpret_cast<uint32_t*>(h.data() + o_order));
-  if (ignore_body) memcpy(h.data() + o_ign, ignore_body, 4 * n);
-  MGF_TRY(b->q_in.ensure(total, s));
-  MGF_TRY(b->q_out.ensure(kOut * n, s));
-  MGF_HIP_TRY(hipMemcpyAsync(b->q_in.p, h.data(), 16 * total, hipMemcpyHostToDevice, s));
-  MGF_TRY(batch_cols_refresh(b, &b->q_launches));
-  uint32_t nmax = 0;
-  for (uint32_t c : b->h_n) nmax = std::max(nmax, c);
-  const uint32_t lds = 32u * nmax + 16u * kBatchQueryRed;  // (at most 32 KB + 256 bytes: two workgroups a CU at the largest world)
+  hipStream_t s = b->ctx->stream;
   BatchQueryArgs A;
   memset(&A, 0, sizeof(A));
-  A.col0 = b->dm[mgf_batch::ACOL0].p; A.col1 = b->dm[mgf_batch::ACOL1].p; A.w_off = b->d_off.p;
+  BatchQueryUpload U;
+  MGF_TRY(batch_query_upload(b, world, queries, sizeof(Q), n, ignore_body, &A, &U));
+  MGF_TRY(b->q_out.ensure(kOut * n, s));
+  const uint32_t lds = U.lds + 16u * kBatchQueryRed;  // (at most 32 KB + 256 bytes: two workgroups a CU at the largest world)
   A.M.nodes = b->t_nodes.p; A.M.verts = b->t_verts.p; A.M.faces = b->t_faces.p;
   A.M.n_nodes = (kinds_mask & MGF_QUERY_TERRAIN) ? b->t_n_nodes : 0u;
   A.M.x[0] = b->t_x.x; A.M.x[1] = b->t_x.y; A.M.x[2] = b->t_x.z;
-  A.items = reinterpret_cast<const uint4*>(b->q_in.p);
-  A.order = reinterpret_cast<const uint32_t*>(b->q_in.p + o_order);
-  A.ignore = ignore_body ? reinterpret_cast<const int32_t*>(b->q_in.p + o_ign) : nullptr;
+  A.ignore = U.ignore;
   A.mask = kinds_mask;
   A.out = b->q_out.p;
-  const Q* dq = reinterpret_cast<const Q*>(b->q_in.p + o_q);
-  MGF_HIP_TRY(hipEventRecord(b->q_ev[0], s));
+  const Q* dq = reinterpret_cast<const Q*>(U.queries);
+  MGF_TRY(b->q_tm.mark(0, s));
   if constexpr (kRays) {
-    k_batch_query_ray<<<(unsigned)n_items, kBatchBlock, lds, s>>>(A, dq);
+    k_batch_query_ray<<<(unsigned)U.n_items, kBatchBlock, lds, s>>>(A, dq);
     LAUNCH_CHECK();
     ++b->q_launches;
   } else {
-    k_batch_query_sweep_bodies<<<(unsigned)n_items, kBatchBlock, lds, s>>>(A, dq);
+    k_batch_query_sweep_bodies<<<(unsigned)U.n_items, kBatchBlock, lds, s>>>(A, dq);
     LAUNCH_CHECK();
     ++b->q_launches;
     if (A.M.n_nodes) {
@@ -119,25 +144,27 @@ static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* q
       ++b->q_launches;
     }
   }
-  MGF_HIP_TRY(hipEventRecord(b->q_ev[1], s));
+  MGF_TRY(b->q_tm.mark(1, s));
   MGF_HIP_TRY(hipMemcpyAsync(out, b->q_out.p, 4 * kOut * n, hipMemcpyDeviceToHost, s));
   MGF_HIP_TRY(hipStreamSynchronize(s));
-  MGF_HIP_TRY(hipEventElapsedTime(&b->q_run_ms, b->q_ev[0], b->q_ev[1]));
-  return MGF_OK;
+  return b->q_tm.ms(0, 1, &b->q_run_ms);
 }
 
 extern "C" mgf_status mgf_batch_raycast_many(mgf_batch* b, const int32_t* world, const mgf_particle* parts, int64_t n, const int32_t* ignore_body,
                                              int32_t kinds_mask, mgf_ray_hit* out) {
-  MGF_TRY(batch_query_args(b, world, parts, n, kinds_mask, out));
+  MGF_TRY(batch_query_args(b, world, parts, n, out));
+  MGF_TRY(query_mask_check(kinds_mask));
+  MGF_TRY(batch_query_worlds(world, n, "too many queries in one call"));
   static_assert(sizeof(mgf_ray_hit) == 28 && sizeof(mgf_particle) == sizeof(ParticleIn), "k_batch_query_ray writes mgf_ray_hit as seven words");
   return batch_query_run(b, world, reinterpret_cast<const ParticleIn*>(parts), n, ignore_body, kinds_mask, reinterpret_cast<int32_t*>(out));
 }
 
 extern "C" mgf_status mgf_batch_sweep_many(mgf_batch* b, const int32_t* world, const mgf_moving_component* casts, int64_t n, const int32_t* ignore_body,
                                            int32_t kinds_mask, mgf_sweep_hit* out) {
-  MGF_TRY(batch_query_args(b, world, casts, n, kinds_mask, out));
+  MGF_TRY(batch_query_args(b, world, casts, n, out));
+  MGF_TRY(query_mask_check(kinds_mask));
+  MGF_TRY(batch_query_worlds(world, n, "too many queries in one call"));
   static_assert(sizeof(mgf_sweep_hit) == 52 && sizeof(mgf_moving_component) == sizeof(MovingIn), "k_batch_query_sweep_bodies writes mgf_sweep_hit as 13 words");
-  for (int64_t i = 0; i < n; ++i)
-    if (casts[i].shape.tag != 0 && casts[i].shape.tag != 1) return fail(MGF_ERR_INVALID, "a cast's shape tag must be 0 (sphere) or 1 (capsule)");
+  MGF_TRY(query_tags_check(casts, n));
   return batch_query_run(b, world, reinterpret_cast<const MovingIn*>(casts), n, ignore_body, kinds_mask, reinterpret_cast<int32_t*>(out));
 }

@@ -65,6 +65,24 @@ struct WorldOptions {
   int64_t time_solver_kernels = 0;
   int64_t phase_timing = 0;            // HIP events at the tick's phase boundaries (mgf_step_stats::ms_*): each is a barrier packet, ~8-15 us of an idle GPU - off unless asked for
 };
+// HIP events around the phases of a query call (host_query.inc, host_batch_query.inc, host_batch_observe.inc).  They live with the
+// handle, created at the first call that marks them: a query call creates and destroys none.
+struct QueryEvents {
+  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+  QueryEvents() = default;
+  QueryEvents(const QueryEvents&) = delete;
+  QueryEvents& operator=(const QueryEvents&) = delete;
+  ~QueryEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  mgf_status mark(int k, hipStream_t s) {
+    if (!e[k]) MGF_HIP_TRY(hipEventCreate(&e[k]));
+    MGF_HIP_TRY(hipEventRecord(e[k], s));
+    return MGF_OK;
+  }
+  // milliseconds from mark a to mark b; the caller has waited for the stream, or for b (wait)
+  mgf_status wait(int k) { MGF_HIP_TRY(hipEventSynchronize(e[k])); return MGF_OK; }
+  mgf_status ms(int a, int b, float* out) { MGF_HIP_TRY(hipEventElapsedTime(out, e[a], e[b])); return MGF_OK; }
+};
+
 struct mgf_world {
   mgf_ctx* ctx = nullptr;
   mgf_params params;
@@ -135,6 +153,7 @@ struct mgf_world {
   DBuf<MovingIn> q_casts;
   uint32_t q_last_large = 0, q_last_cells = 0;
   float q_last_build_ms = 0.0f, q_last_run_ms = 0.0f;
+  QueryEvents q_tm;  // 0 | the grid | 1 | the query pass | 2
   bool front_rows_off = false;       // the list-free front end switched off for good: a body accepted more faces than k_terrain_near lists
   uint64_t pair_brick_slow = 0;      // last tick: queries k_pair_brick answered from global memory (one lane each: slow)
   uint32_t pair_brick_off = 0;       // ticks left during which k_pair_grid runs instead (too many such queries: cells much denser or bodies much larger than the box copy allows)

@@ -11,7 +11,8 @@
 //                             with sequential f32 adds: nothing of the answer depends on lane scheduling, and there is no float atomic.
 //                             Of the tick's state only `rows` is written - every tick rebuilds it.
 //   k_batch_observe_overlap<FILL>
-//                             a workgroup per work item = (world, up to 256 boxes) of the queries' sort by world (batch_query_plan).
+//                             a workgroup per work item = (world, up to 256 boxes) of the queries' sort by world (BatchQueryPlan; the
+//                             kernel's share of it: BatchWork, k_batch_query.h).
 //                             The tight bounds BoundedBy<AABB> (bounds.rs:170-190) of the world's colliders col0 / col1 staged in LDS
 //                             once; a box gets min(64, 256 / (count rounded up to a power of two)) lanes of one wave, which take the
 //                             bodies in chunks of that many, ascending; Overlaps<AABB> (collision.rs:22-29) per lane, and a hit's place
@@ -90,12 +91,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_observe_contacts(BatchCon
   }
 }
 
-struct BatchOverlapArgs {
-  const float4* col0;     // as BatchQueryArgs
-  const float4* col1;
-  const uint32_t* w_off;
-  const uint4* items;
-  const uint32_t* order;
+struct BatchOverlapArgs : BatchWorkArgs {
   const float* boxes;     // by the caller's index: c.xyz, r.xyz
   uint32_t* cnt;          // by the caller's index: the hits of box i (written when !FILL) ...
   const uint32_t* off;    // ... their exclusive prefix sums (read when FILL)
@@ -106,19 +102,17 @@ struct BatchOverlapArgs {
 template <bool FILL>
 __global__ __launch_bounds__(kBatchBlock) void k_batch_observe_overlap(BatchOverlapArgs A) {
   extern __shared__ float4 s_dyn[];
-  const uint4 it = A.items[blockIdx.x];
-  const uint32_t tid = threadIdx.x, g0 = A.w_off[it.x], n = A.w_off[it.x + 1] - g0;
+  BatchWork W(A, true);
+  const uint32_t tid = threadIdx.x, g0 = W.g0, n = W.n;
   float4 *s_c = s_dyn, *s_r = s_dyn + n;
   for (uint32_t i = tid; i < n; i += kBatchBlock) {
-    const float4 a = A.col0[(size_t)g0 + i], b = A.col1[(size_t)g0 + i];
-    Comp c; c.kind = (int)f2u(b.w); c.p = xyz(a); c.d = xyz(b); c.r = a.w;
-    const Box tb = comp_bounds(c);
+    const Box tb = comp_bounds(to_comp(A.col0[(size_t)g0 + i], A.col1[(size_t)g0 + i]));
     s_c[i] = mk4(tb.c, 0.0f); s_r[i] = mk4(tb.r, 0.0f);
   }
   __syncthreads();
-  const uint32_t sh = min(bq_lane_shift(it.z), 6u), L = 1u << sh, j = tid >> sh, sub = tid & (L - 1u);
-  const bool live = j < it.z;
-  const uint32_t qi = live ? A.order[it.y + j] : 0u;
+  W.split(A, min(W.shift(), 6u));  // (a box's lanes in one wave: the ballot)
+  const uint32_t L = W.L, sub = W.sub, qi = W.qi;
+  const bool live = W.live;
   Box Q; Q.c = mk3(0.0f, 0.0f, 0.0f); Q.r = Q.c;
   if (live) { Q.c = ld3(A.boxes + 6 * (size_t)qi); Q.r = ld3(A.boxes + 6 * (size_t)qi + 3); }
   const uint32_t base = (FILL && live) ? A.off[qi] : 0u;

@@ -1,4 +1,4 @@
-// Queries against a world's resident bodies, terrain and obstacles between ticks (mgf_world_raycast_many,
+// Queries against a world's resident bodies, terrain and obstacles between ticks (mgf_world_raycast_many, mgf_world_sweep_many,
 // mgf_world_overlap_aabb_many; host_query.inc).  (Part of the kernel set described in kernels.h.)
 //
 // The bodies are reached through a uniform grid built per call from their CURRENT tight boxes (the tick's own cell grid is
@@ -17,6 +17,12 @@
 // Which of the targets a hit belongs to never depends on the visiting order: hits are ranked by (t, kind, index, part).
 // Every acceleration step is conservative (cells and boxes padded by QueryGrid::margin); each answer comes from the
 // reference's single-shape test.
+// What a query tests and records is written here once, for these kernels and the batch's (k_batch_query.h, k_batch_observe.h):
+//   to_comp(float4, float4)                          a collider's two rows as a Comp
+//   q_ray_terrain / q_sweep_terrain<Mesh>            the terrain's node-box and face tests, over either walk of a mesh tree (q_mesh_walk)
+//   QueryBest / SweepBest                            the candidate and its ranking; shfl / pack / unpack / merge for the batch's bq_reduce
+//   q_ray_store / q_sweep_store / q_sweep_load       the 7- and 13-word records, and a record taken up again by a later launch
+//   q_clip / q_next_crossing                         the grid walks: a path clipped to a box, the DDA's next cell face
 #pragma once
 #include "k_api.h"
 
@@ -47,6 +53,9 @@ __device__ __forceinline__ void q_cell_range(const Box& b, const QueryGrid& G, i
   }
 }
 
+// a collider or a world-space part as its two rows: (p.xyz, r), (d.xyz, kind)
+__device__ __forceinline__ Comp to_comp(float4 a, float4 b) { Comp c; c.kind = (int)f2u(b.w); c.p = xyz(a); c.d = xyz(b); c.r = a.w; return c; }
+
 // BoundedBy<AABB> of slot i: its collider, or the union of its parts in order (what k_integrate's tight box is, unswept)
 __device__ __forceinline__ Box q_body_box(const Bodies& B, uint32_t i) {
   const uint32_t pc = B.pcount ? B.pcount[i] : 0u;
@@ -55,14 +64,11 @@ __device__ __forceinline__ Box q_body_box(const Bodies& B, uint32_t i) {
     for (uint32_t k = 0; k < pc; ++k) {
       float4 a, b;
       world_part(B, i, k, pc, a, b);
-      Comp part; part.kind = (int)f2u(b.w); part.p = xyz(a); part.d = xyz(b); part.r = a.w;
-      const Box pb = comp_bounds(part);
+      const Box pb = comp_bounds(to_comp(a, b));
       tb = k == 0 ? pb : box_combine(tb, pb);
     }
   } else {
-    const float4 a = B.col0[i], b = B.col1[i];
-    Comp c; c.kind = (int)f2u(b.w); c.p = xyz(a); c.d = xyz(b); c.r = a.w;
-    tb = comp_bounds(c);
+    tb = comp_bounds(to_comp(B.col0[i], B.col1[i]));
   }
   return tb;
 }
@@ -118,6 +124,8 @@ __device__ __forceinline__ bool q_ray_comp(V3 p, V3 d, float dt, float4 a, float
   return ray_capsule(p, d, mkcap(xyz(a), xyz(b), a.w), ip, t, dt);
 }
 
+__device__ __forceinline__ V3 q_shfl3(V3 v, int off) { return mk3(__shfl_xor(v.x, off), __shfl_xor(v.y, off), __shfl_xor(v.z, off)); }
+
 struct QueryBest {
   bool have = false;
   int kind = -1;
@@ -129,13 +137,60 @@ struct QueryBest {
     const bool better = !have || it < t || (it == t && (k < kind || (k == kind && (idx < index || (idx == index && pt < part)))));
     if (better) { have = true; kind = k; index = idx; part = pt; p = ip; t = it; }
   }
+  // for bq_reduce (k_batch_query.h; a batch's bodies have one part: `part` does not travel)
+  static constexpr uint32_t kRed = 2;  // float4 words of a packed candidate
+  __device__ __forceinline__ QueryBest shfl(int off) const {
+    QueryBest o;
+    o.kind = __shfl_xor(have ? kind : -1, off); o.index = (uint32_t)__shfl_xor((int)index, off); o.p = q_shfl3(p, off); o.t = __shfl_xor(t, off);
+    o.have = o.kind >= 0;
+    return o;
+  }
+  __device__ __forceinline__ void pack(float4* w) const {
+    w[0] = make_float4(u2f((uint32_t)(have ? kind : -1)), u2f(index), t, 0.0f);
+    w[1] = mk4(p, 0.0f);
+  }
+  static __device__ __forceinline__ QueryBest unpack(const float4* w) {
+    const float4 r0 = w[0], r1 = w[1];
+    QueryBest o;
+    o.kind = (int)f2u(r0.x); o.index = f2u(r0.y); o.p = xyz(r1); o.t = r0.z;
+    o.have = o.kind >= 0;
+    return o;
+  }
+  __device__ __forceinline__ void merge(const QueryBest& o) { if (o.have) offer(o.p, o.t, o.kind, o.index, 0u); }
 };
+// mgf_ray_hit as seven words
+__device__ __forceinline__ void q_ray_store(int32_t* o, const QueryBest& best) {
+  if (best.have) {
+    o[0] = best.kind; o[1] = (int32_t)best.index; o[2] = (int32_t)best.part;
+    o[3] = (int32_t)f2u(best.p.x); o[4] = (int32_t)f2u(best.p.y); o[5] = (int32_t)f2u(best.p.z); o[6] = (int32_t)f2u(best.t);
+  } else {
+    o[0] = MGF_HIT_NONE; o[1] = 0; o[2] = 0; o[3] = 0; o[4] = 0; o[5] = 0; o[6] = 0;
+  }
+}
 
+// clip the path p + d t, t in [t0, t1], to the box [lo, hi] (an axis with skip[k] set is not looked at; skip null: none): false - the
+// path misses the box
+__device__ __forceinline__ bool q_clip(V3 p, V3 d, const float lo[3], const float hi[3], const bool* skip, float& t0, float& t1) {
+  bool miss = false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float pk = at(p, k), dk = at(d, k);
+    if (skip && skip[k]) continue;
+    if (dk == 0.0f) {
+      if (!(pk >= lo[k] && pk <= hi[k])) miss = true;
+    } else {
+      float ta = (lo[k] - pk) / dk, tb = (hi[k] - pk) / dk;
+      if (ta > tb) { const float s = ta; ta = tb; tb = s; }
+      t0 = fmaxf(t0, ta); t1 = fminf(t1, tb);
+    }
+  }
+  return !miss && t0 <= t1;
+}
 // conservative slab test of a particle against a padded box: may the particle meet the box at a parameter in [0, tmax]?
 __device__ __forceinline__ bool q_slab(V3 p, V3 d, V3 c, V3 r, float pad, float tmax) {
   float t0 = 0.0f, t1 = tmax;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < 3; ++k) {  // (q_clip with an early way out: this runs per node of a mesh walk)
     const float pk = at(p, k), dk = at(d, k), lo = at(c, k) - at(r, k) - pad, hi = at(c, k) + at(r, k) + pad;
     if (dk == 0.0f) {
       if (!(pk >= lo && pk <= hi)) return false;
@@ -148,6 +203,21 @@ __device__ __forceinline__ bool q_slab(V3 p, V3 d, V3 c, V3 r, float pad, float 
   return t0 <= t1;
 }
 __device__ __forceinline__ float q_maxabs(V3 v) { return fmaxf(fabsf(v.x), fmaxf(fabsf(v.y), fabsf(v.z))); }
+
+// The DDA's next step from cell c along p + d t (Amanatides-Woo): the axis whose cell face the path crosses first and the parameter tn
+// there, computed afresh from the face - nothing accumulates.  -1: no axis steps.
+__device__ __forceinline__ int q_next_crossing(const QueryGrid& G, const int c[3], const int step[3], V3 p, V3 d, float& tn) {
+  tn = kInf;
+  int ax = -1;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (step[k] == 0) continue;
+    const float face = G.lo[k] + (float)(c[k] + (step[k] > 0 ? 1 : 0)) * G.h;
+    const float tk = (face - at(p, k)) / at(d, k);
+    if (ax < 0 || tk < tn) { tn = tk; ax = k; }
+  }
+  return ax;
+}
 
 struct QueryTargets {
   Bodies B;
@@ -213,10 +283,11 @@ __device__ __forceinline__ void q_ray_obstacle(const CompoundDev& D, uint32_t o,
   if (have) best.offer(best_p, best_t, MGF_HIT_OBSTACLE, o, best_c);
 }
 
-// Intersects<Triangle> of every face the padded walk of the mesh BVH reaches
-__device__ __forceinline__ void q_ray_terrain(const TerrainDev& M, V3 p, V3 d, float dt, uint32_t* err, QueryBest& best) {
-  const V3 mx = mk3(M.x[0], M.x[1], M.x[2]);
-  const V3 lp = p + -mx;  // the tree's boxes are in the mesh's frame
+// The terrain's tests are written once, over either walk of a mesh tree: q_mesh_walk(M, err, pass, emit) calls emit(f) for every face f
+// whose node boxes (centre, half extent) all pass - here the explicit stack over TerrainDev, in k_batch_query.h the threaded tree over
+// BatchTerrain.  Mesh: either struct (x, verts, faces).
+template <class P, class F>
+__device__ __forceinline__ void q_mesh_walk(const TerrainDev& M, uint32_t* err, P&& pass, F&& emit) {
   uint32_t stack[kStack];
   int sp = 0;
   stack[sp++] = M.root;
@@ -224,20 +295,35 @@ __device__ __forceinline__ void q_ray_terrain(const TerrainDev& M, V3 p, V3 d, f
     const uint32_t top = stack[--sp];
     const float4* raw = reinterpret_cast<const float4*>(&M.nodes[top]);
     const float4 n0 = raw[0], n1 = raw[1];
-    const V3 c = xyz(n0), r = xyz(n1);
-    const float pad = 1e-5f * (q_maxabs(c) + q_maxabs(r) + q_maxabs(mx) + q_maxabs(p)) + 1e-6f;
-    const float lim = best.have ? fminf(dt, best.t * 1.0001f + 1e-6f) : dt;
-    if (!q_slab(lp, d, c, r, pad, lim)) continue;
+    if (!pass(xyz(n0), xyz(n1))) continue;
     const uint32_t w0 = f2u(n0.w), w1 = f2u(n1.w);
-    if (w0 & 0x80000000u) {
-      const uint32_t f = w0 & 0x7FFFFFFFu;
-      const uint4 fi = M.faces[f];
-      const Triangle tri = mkt(xyz(M.verts[fi.x]) + mx, xyz(M.verts[fi.y]) + mx, xyz(M.verts[fi.z]) + mx);
-      V3 ip; float t;
-      if (ray_triangle(p, d, tri, &ip, &t, dt)) best.offer(ip, t, MGF_HIT_TERRAIN, f, 0u);
-    } else if (sp + 2 <= kStack) { stack[sp++] = w0; stack[sp++] = w1; }
+    if (w0 & 0x80000000u) emit(w0 & 0x7FFFFFFFu);
+    else if (sp + 2 <= kStack) { stack[sp++] = w0; stack[sp++] = w1; }
     else *err = 1u;
   }
+}
+template <class Mesh>
+__device__ __forceinline__ Triangle q_face(const Mesh& M, V3 mx, uint32_t f) {
+  const uint4 fi = M.faces[f];
+  return mkt(xyz(M.verts[fi.x]) + mx, xyz(M.verts[fi.y]) + mx, xyz(M.verts[fi.z]) + mx);
+}
+
+// Intersects<Triangle> of every face the padded walk of the mesh BVH reaches: the slab test of a node is bounded by the best t so far
+template <class Mesh>
+__device__ __forceinline__ void q_ray_terrain(const Mesh& M, V3 p, V3 d, float dt, uint32_t* err, QueryBest& best) {
+  const V3 mx = mk3(M.x[0], M.x[1], M.x[2]);
+  const V3 lp = p + -mx;  // the tree's boxes are in the mesh's frame
+  q_mesh_walk(
+      M, err,
+      [&](V3 c, V3 r) {
+        const float pad = 1e-5f * (q_maxabs(c) + q_maxabs(r) + q_maxabs(mx) + q_maxabs(p)) + 1e-6f;
+        const float lim = best.have ? fminf(dt, best.t * 1.0001f + 1e-6f) : dt;
+        return q_slab(lp, d, c, r, pad, lim);
+      },
+      [&](uint32_t f) {
+        V3 ip; float t;
+        if (ray_triangle(p, d, q_face(M, mx, f), &ip, &t, dt)) best.offer(ip, t, MGF_HIT_TERRAIN, f, 0u);
+      });
 }
 
 // the grid cell (x, y, z) - with `fat`, its 3x3x3 neighbourhood - for one particle
@@ -270,24 +356,12 @@ __global__ __launch_bounds__(kBlock) void k_query_ray(QueryGrid G, QueryTargets 
     for (uint32_t o = 0; o < T.n_obs; ++o) q_ray_obstacle(T.obs[o], o, q, T.err, best);
   if ((mask & MGF_QUERY_TERRAIN) && T.M.n_nodes) q_ray_terrain(T.M, p, d, dt, T.err, best);
   if ((mask & MGF_QUERY_BODIES) && G.dims[0] > 0) {
-    // clip to the grid's box, then walk its cells in the order the particle enters them (Amanatides-Woo, every crossing parameter
-    // computed afresh from the cell's face - nothing accumulates)
+    // clip to the grid's box, then walk its cells in the order the particle enters them
     float t0 = 0.0f, t1 = dt;
-    bool miss = false;
     float ghi[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      ghi[k] = G.lo[k] + (float)G.dims[k] * G.h;
-      const float pk = at(p, k), dk = at(d, k);
-      if (dk == 0.0f) {
-        if (!(pk >= G.lo[k] && pk <= ghi[k])) miss = true;
-      } else {
-        float ta = (G.lo[k] - pk) / dk, tb = (ghi[k] - pk) / dk;
-        if (ta > tb) { const float s = ta; ta = tb; tb = s; }
-        t0 = fmaxf(t0, ta); t1 = fminf(t1, tb);
-      }
-    }
-    if (!miss && t0 <= t1) {
+    for (int k = 0; k < 3; ++k) ghi[k] = G.lo[k] + (float)G.dims[k] * G.h;
+    if (q_clip(p, d, G.lo, ghi, nullptr, t0, t1)) {
       const V3 e = p + d * t0;
       int c[3], step[3];
 #pragma unroll
@@ -299,15 +373,8 @@ __global__ __launch_bounds__(kBlock) void k_query_ray(QueryGrid G, QueryTargets 
       const int max_steps = G.dims[0] + G.dims[1] + G.dims[2] + 3;
       for (int s = 0; s < max_steps; ++s) {
         q_ray_cells(G, T, c, fat, p, d, dt, ign, best);
-        float tn = kInf;
-        int ax = -1;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          if (step[k] == 0) continue;
-          const float face = G.lo[k] + (float)(c[k] + (step[k] > 0 ? 1 : 0)) * G.h;
-          const float tk = (face - at(p, k)) / at(d, k);
-          if (ax < 0 || tk < tn) { tn = tk; ax = k; }
-        }
+        float tn;
+        const int ax = q_next_crossing(G, c, step, p, d, tn);
         if (ax < 0 || !(tn <= t1 + tpad)) break;
         if (best.have && tn > best.t + tpad) break;
         c[ax] += step[ax];
@@ -315,13 +382,7 @@ __global__ __launch_bounds__(kBlock) void k_query_ray(QueryGrid G, QueryTargets 
       }
     }
   }
-  int32_t* o = out + 7 * i;
-  if (best.have) {
-    o[0] = best.kind; o[1] = (int32_t)best.index; o[2] = (int32_t)best.part;
-    o[3] = (int32_t)f2u(best.p.x); o[4] = (int32_t)f2u(best.p.y); o[5] = (int32_t)f2u(best.p.z); o[6] = (int32_t)f2u(best.t);
-  } else {
-    o[0] = MGF_HIT_NONE; o[1] = 0; o[2] = 0; o[3] = 0; o[4] = 0; o[5] = 0; o[6] = 0;
-  }
+  q_ray_store(out + 7 * i, best);
 }
 
 // ---- swept spheres and capsules (mgf_world_sweep_many) ----------------------------------------------------------------------
@@ -342,6 +403,30 @@ struct SweepBest {
   __device__ __forceinline__ int kind() const { return (int)(sub >> 52); }
   __device__ __forceinline__ uint32_t index() const { return (uint32_t)(sub >> 20); }
   __device__ __forceinline__ uint32_t part() const { return (uint32_t)(sub >> 1) & 0x7FFFFu; }
+  // for bq_reduce (k_batch_query.h)
+  static constexpr uint32_t kRed = 4;  // float4 words of a packed candidate
+  __device__ __forceinline__ SweepBest shfl(int off) const {
+    SweepBest o;
+    o.tk = __shfl_xor(tk, off);
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)sub, off), hi = (uint32_t)__shfl_xor((int)(uint32_t)(sub >> 32), off);
+    o.sub = ((uint64_t)hi << 32) | lo;
+    o.c.a = q_shfl3(c.a, off); o.c.b = q_shfl3(c.b, off); o.c.n = q_shfl3(c.n, off); o.c.t = __shfl_xor(c.t, off);
+    return o;
+  }
+  __device__ __forceinline__ void pack(float4* w) const {
+    w[0] = make_float4(u2f((uint32_t)tk), u2f((uint32_t)sub), u2f((uint32_t)(sub >> 32)), c.t);
+    w[1] = mk4(c.a, 0.0f); w[2] = mk4(c.b, 0.0f); w[3] = mk4(c.n, 0.0f);
+  }
+  static __device__ __forceinline__ SweepBest unpack(const float4* w) {
+    const float4 r0 = w[0];
+    SweepBest o;
+    o.tk = (int)f2u(r0.x); o.sub = ((uint64_t)f2u(r0.z) << 32) | f2u(r0.y);
+    o.c = mkc(xyz(w[1]), xyz(w[2]), xyz(w[3]), r0.w);
+    return o;
+  }
+  __device__ __forceinline__ void merge(const SweepBest& o) {
+    if (o.tk < tk || (o.tk == tk && o.sub < sub)) { tk = o.tk; sub = o.sub; c = o.c; }
+  }
 };
 
 // The cast: its shape at t = 0, its sweep, and the bounding sphere (centre cc, radius cr) that the cheap reject moves along the sweep
@@ -378,7 +463,7 @@ __device__ __forceinline__ void q_sweep_body(const QueryTargets& T, uint32_t s, 
     float4 a, b;
     if (pc) world_part(B, s, k, pc, a, b);
     else { a = B.col0[s]; b = B.col1[s]; }
-    Comp t; t.kind = (int)f2u(b.w); t.p = xyz(a); t.d = xyz(b); t.r = a.w;
+    const Comp t = to_comp(a, b);
     if (q_sweep_far(t, K)) continue;
     Contact c;
     if (comp_mcomp(t, K.s, K.v, &c)) best.offer(c, MGF_HIT_BODY, e, k, 0u);
@@ -390,38 +475,30 @@ __device__ __forceinline__ void q_sweep_body(const QueryTargets& T, uint32_t s, 
 // unit axis but steps along the whole one, so it answers at t = 0 for a capsule up to max(1, |d|) from the face - the box grows by that.
 // A capsule that does not move tests every face: the fallback (:901-1060) then casts rays of direction 0, whose tests divide by
 // |delta|^2 and can answer at t = 0 at a face nowhere near the capsule.
-__device__ __forceinline__ void q_sweep_terrain(const TerrainDev& M, const SweepCast& K, uint32_t* err, SweepBest& best) {
+template <class Mesh>
+__device__ __forceinline__ void q_sweep_terrain(const Mesh& M, const SweepCast& K, uint32_t* err, SweepBest& best) {
   const bool every = K.s.kind != KIND_SPHERE && mag2(K.v) == 0.0f;
   const float reach = K.s.kind == KIND_SPHERE ? 0.0f : fmaxf(1.0f, mag(K.s.d));
   const V3 mx = mk3(M.x[0], M.x[1], M.x[2]);
   Box q = swept_bounds(K.s, K.v);
   q.c = q.c + -mx;  // the tree's boxes are in the mesh's frame
-  uint32_t stack[kStack];
-  int sp = 0;
-  stack[sp++] = M.root;
-  while (sp > 0) {
-    const uint32_t top = stack[--sp];
-    const float4* raw = reinterpret_cast<const float4*>(&M.nodes[top]);
-    const float4 n0 = raw[0], n1 = raw[1];
-    const V3 c = xyz(n0), r = xyz(n1);
-    const float pad = 1e-5f * (q_maxabs(c) + q_maxabs(r) + q_maxabs(mx) + q_maxabs(q.c) + q_maxabs(q.r)) + 1e-6f + reach;
-    if (!every && !(fabsf(c.x - q.c.x) <= r.x + q.r.x + pad && fabsf(c.y - q.c.y) <= r.y + q.r.y + pad && fabsf(c.z - q.c.z) <= r.z + q.r.z + pad)) continue;
-    const uint32_t w0 = f2u(n0.w), w1 = f2u(n1.w);
-    if (w0 & 0x80000000u) {
-      const uint32_t f = w0 & 0x7FFFFFFFu;
-      const uint4 fi = M.faces[f];
-      const Triangle tri = mkt(xyz(M.verts[fi.x]) + mx, xyz(M.verts[fi.y]) + mx, xyz(M.verts[fi.z]) + mx);
-      Contact c0, c1;
-      if (K.s.kind == KIND_SPHERE) {
-        if (tri_msphere(tri, mks(K.s.p, K.s.r), K.v, &c0)) best.offer(c0, MGF_HIT_TERRAIN, f, 0u, 0u);
-      } else {
-        const int m = tri_mcapsule(tri, mkcap(K.s.p, K.s.d, K.s.r), K.v, c0, c1);
-        if (m > 0) best.offer(c0, MGF_HIT_TERRAIN, f, 0u, 0u);
-        if (m > 1) best.offer(c1, MGF_HIT_TERRAIN, f, 0u, 1u);
-      }
-    } else if (sp + 2 <= kStack) { stack[sp++] = w0; stack[sp++] = w1; }
-    else *err = 1u;
-  }
+  q_mesh_walk(
+      M, err,
+      [&](V3 c, V3 r) {
+        const float pad = 1e-5f * (q_maxabs(c) + q_maxabs(r) + q_maxabs(mx) + q_maxabs(q.c) + q_maxabs(q.r)) + 1e-6f + reach;
+        return every || (fabsf(c.x - q.c.x) <= r.x + q.r.x + pad && fabsf(c.y - q.c.y) <= r.y + q.r.y + pad && fabsf(c.z - q.c.z) <= r.z + q.r.z + pad);
+      },
+      [&](uint32_t f) {
+        const Triangle tri = q_face(M, mx, f);
+        Contact c0, c1;
+        if (K.s.kind == KIND_SPHERE) {
+          if (tri_msphere(tri, mks(K.s.p, K.s.r), K.v, &c0)) best.offer(c0, MGF_HIT_TERRAIN, f, 0u, 0u);
+        } else {
+          const int m = tri_mcapsule(tri, mkcap(K.s.p, K.s.d, K.s.r), K.v, c0, c1);
+          if (m > 0) best.offer(c0, MGF_HIT_TERRAIN, f, 0u, 0u);
+          if (m > 1) best.offer(c1, MGF_HIT_TERRAIN, f, 0u, 1u);
+        }
+      });
 }
 
 // the grid cells [lo, hi] (clamped to the grid)
@@ -458,6 +535,16 @@ __device__ __forceinline__ void q_sweep_store(int32_t* o, const SweepBest& best)
   }
 }
 
+// a stored record taken up again by a later launch (the order within its target does not matter there: the launches offer different
+// kinds of target, or only bodies of one part)
+__device__ __forceinline__ SweepBest q_sweep_load(const int32_t* o) {
+  SweepBest best;
+  if (o[0] != MGF_HIT_NONE)
+    best.offer(mkc(mk3(u2f(o[3]), u2f(o[4]), u2f(o[5])), mk3(u2f(o[6]), u2f(o[7]), u2f(o[8])), mk3(u2f(o[9]), u2f(o[10]), u2f(o[11])), u2f(o[12])), o[0],
+               (uint32_t)o[1], (uint32_t)o[2], 0u);
+  return best;
+}
+
 // A lane per cast, in two kernels (one held the walks of all four kinds of target live at once and spilled scalar registers inside its
 // nested cell loops): k_query_sweep tests the large bodies, the obstacles and the terrain and writes its best contact; k_query_sweep_cells
 // takes that contact up again and walks the grid.  The ranking does not depend on the visiting order, so the split changes no answer.
@@ -491,10 +578,7 @@ __global__ __launch_bounds__(kBlock) void k_query_sweep_cells(QueryGrid G, Query
   const SweepCast K = q_sweep_cast(casts[i], G);
   const int32_t ign = ignore ? ignore[i] : -1;
   int32_t* o = out + 13 * i;
-  SweepBest best;
-  if (o[0] != MGF_HIT_NONE)  // k_query_sweep's answer (its order within a target does not matter here: the grid offers bodies only)
-    best.offer(mkc(mk3(u2f(o[3]), u2f(o[4]), u2f(o[5])), mk3(u2f(o[6]), u2f(o[7]), u2f(o[8])), mk3(u2f(o[9]), u2f(o[10]), u2f(o[11])), u2f(o[12])), o[0],
-               (uint32_t)o[1], (uint32_t)o[2], 0u);
+  SweepBest best = q_sweep_load(o);  // k_query_sweep's answer
   const Box sb = comp_bounds(K.s);
   const float dmax = q_maxabs(K.v);
   // the block's half extent in cells; a cast whose own rounding (far from the grid, a long sweep) may exceed the margin takes one more.
@@ -512,20 +596,7 @@ __global__ __launch_bounds__(kBlock) void k_query_sweep_cells(QueryGrid G, Query
   }
   // clip the centre's path to the grid's box grown by the block (beyond it a block holds no cell of the grid)
   float t0 = 0.0f, t1 = 1.0f;
-  bool miss = false;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float pk = at(K.cc, k), dk = at(K.v, k);
-    if (whole[k]) continue;
-    if (dk == 0.0f) {
-      if (!(pk >= elo[k] && pk <= ehi[k])) miss = true;
-    } else {
-      float ta = (elo[k] - pk) / dk, tb = (ehi[k] - pk) / dk;
-      if (ta > tb) { const float s = ta; ta = tb; tb = s; }
-      t0 = fmaxf(t0, ta); t1 = fminf(t1, tb);
-    }
-  }
-  if (!miss && t0 <= t1) {
+  if (q_clip(K.cc, K.v, elo, ehi, whole, t0, t1)) {
     const V3 e = K.cc + K.v * t0;
     int c[3], step[3];
 #pragma unroll
@@ -541,15 +612,8 @@ __global__ __launch_bounds__(kBlock) void k_query_sweep_cells(QueryGrid G, Query
     q_sweep_cells(G, T, lo, hi, K, ign, best);
     const int max_steps = G.dims[0] + G.dims[1] + G.dims[2] + 2 * (R[0] + R[1] + R[2]) + 6;
     for (int s = 0; s < max_steps; ++s) {
-      float tn = kInf;
-      int ax = -1;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        if (step[k] == 0) continue;
-        const float face = G.lo[k] + (float)(c[k] + (step[k] > 0 ? 1 : 0)) * G.h;
-        const float tk = (face - at(K.cc, k)) / at(K.v, k);
-        if (ax < 0 || tk < tn) { tn = tk; ax = k; }
-      }
+      float tn;
+      const int ax = q_next_crossing(G, c, step, K.cc, K.v, tn);
       if (ax < 0 || !(tn <= t1 + tpad)) break;
       if (best.have() && tn > best.c.t + tpad) break;
       c[ax] += step[ax];

@@ -79,13 +79,18 @@
 //                      progress counters in LDS
 //   k_batch_query_gather / _ray / _sweep_bodies / _sweep_faces (k_batch_query.h)
 //                      ray casts and sweeps against the worlds of a batch (mgf_batch_raycast_many / _sweep_many): a workgroup per (world,
-//                      up to 256 queries), the world's colliders in LDS, 256 / count lanes a query, the mesh tree walked without a stack
+//                      up to 256 queries; BatchWork), the world's colliders in LDS, 256 / count lanes a query and the best of them by
+//                      bq_reduce, the mesh tree walked without a stack; the tests are k_query.h's
 //   k_batch_observe_contacts / _overlap<FILL> (k_batch_observe.h)
 //                      what else a caller reads of a batch every tick: the constraint list of every world folded per body
 //                      (mgf_batch_read_body_contacts: a workgroup per world, the per-body ranges rebuilt in LDS, a lane per body walks its
 //                      chain) and the bodies in a box (mgf_batch_overlap_aabb_many: the world's tight boxes in LDS, ballot-rank compaction)
-//   k_query_* (k_query.h) ray casts and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid of
-//                      the bodies' current tight boxes built per call (never the tick's lists)
+//   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
+//                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
+//                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
+//                      terrain's node and face tests (q_ray_terrain / q_sweep_terrain<Mesh> over q_mesh_walk), q_ray_store / q_sweep_store /
+//                      q_sweep_load, the candidates QueryBest / SweepBest with what bq_reduce needs of them, and the grid walk's
+//                      q_clip / q_next_crossing
 //
 // All f32 arithmetic follows the reference's operation order; the TU is built with
 // -ffp-contract=off.

@@ -181,6 +181,86 @@ def test_inertia_tensor_matches_oracle(comp):
     assert np.array_equal(np.asarray(got, np.float32).view(np.uint32), np.asarray(list(out), np.float32).view(np.uint32))
 
 
+def test_query_marshalling_helpers():
+    """What World and WorldBatch hand to the query entry points (the module-level helpers of _capi.py): d, dt, ignore and world broadcast
+    from a scalar or a single row; a COMPONENT_DTYPE array plus delta is the MOVING_DTYPE array, byte for byte; lo / hi become
+    c = (hi + lo) / 2, r = (hi - lo) / 2 in f32."""
+    rng = np.random.default_rng(11)
+    n = 5
+    p = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
+    d = rng.uniform(-1, 1, (n, 3)).astype(np.float32)
+    dt = rng.uniform(0.5, 2, n).astype(np.float32)
+    rows = _capi._particle_rows(p, d, dt)
+    assert rows.dtype == np.float32 and rows.shape == (n, 7) and rows.flags.c_contiguous
+    assert np.array_equal(rows[:, 0:3], p) and np.array_equal(rows[:, 3:6], d) and np.array_equal(rows[:, 6], dt)
+    for one_d in (d[0], d[0:1], [0.0, -1.0, 0.5]):   # a single row, a (1, 3) array, a list: the same direction for all
+        for one_dt in (2.5, [2.5], float("inf")):
+            rows = _capi._particle_rows(p, one_d, one_dt)
+            assert np.array_equal(rows[:, 0:3], p)
+            assert np.array_equal(rows[:, 3:6], np.tile(np.asarray(one_d, np.float32).reshape(1, 3), (n, 1)))
+            assert np.array_equal(rows[:, 6], np.full(n, np.float32(np.asarray(one_dt).reshape(-1)[0])))
+    assert _capi._particle_rows([1, 2, 3], [0, 0, 1], 1.0).shape == (1, 7)   # one particle given as a vector
+    # ignore and world: None stays None; a scalar, a single row or n rows become n contiguous int32
+    assert _capi._per_query(None, n, optional=True) is None and _capi._ptr(None) is None
+    with pytest.raises(TypeError):
+        _capi._per_query(None, n)   # a world is not optional
+    for v, want in ((3, [3] * n), ([4], [4] * n), (np.arange(n, dtype=np.int64), list(range(n))), (-1, [-1] * n)):
+        got = _capi._per_query(v, n)
+        assert got.dtype == np.int32 and got.shape == (n,) and got.flags.c_contiguous and got.tolist() == want
+        assert _capi._ptr(got) == got.ctypes.data
+    with pytest.raises(ValueError):
+        _capi._per_query([1, 2], n)   # neither one nor n
+    # casts
+    comps = np.zeros(n, _capi.COMPONENT_DTYPE)
+    comps["tag"] = [0, 1, 1, 0, 1]
+    comps["p"], comps["d"], comps["r"] = p, d, dt
+    delta = rng.uniform(-2, 2, (n, 3)).astype(np.float32)
+    moving = np.zeros(n, _capi.MOVING_DTYPE)
+    for k in ("tag", "p", "d", "r"):
+        moving[k] = comps[k]
+    moving["delta"] = delta
+    casts = _capi._cast_rows(comps, delta)
+    assert casts.dtype == _capi.MOVING_DTYPE and casts.itemsize == 44 and casts.flags.c_contiguous
+    assert casts.tobytes() == moving.tobytes() == _capi._cast_rows(moving, None).tobytes()
+    moving["delta"] = delta[0]
+    assert _capi._cast_rows(comps, delta[0]).tobytes() == moving.tobytes()          # one vector for all
+    moving["delta"] = 0.0
+    assert _capi._cast_rows(comps, None).tobytes() == moving.tobytes()              # no delta: a cast that does not move
+    assert _capi._cast_rows(moving.reshape(n, 1), None).shape == (n,)
+    with pytest.raises(ValueError, match="carries its own delta"):
+        _capi._cast_rows(moving, delta)
+    # boxes: the f32 operations as written, a rounding case included (hi + lo is not representable: the sum rounds, then halves)
+    lo = np.array([[0.1, -2.0, 3.0], [1e8, 1.0, -0.3], [5.0, 5.0, 5.0]], np.float32)
+    hi = np.array([[0.7, 2.5, 3.0], [1e8 + 16, 3.0, 0.1], [4.0, 6.0, 5.0]], np.float32)   # (the last: a negative half extent)
+    boxes = _capi._boxes_from_corners(lo, hi)
+    assert boxes.dtype == np.float32 and boxes.shape == (3, 6) and boxes.flags.c_contiguous
+    two = np.float32(2)
+    assert np.array_equal(boxes[:, 0:3].view(np.uint32), ((hi + lo) / two).view(np.uint32))
+    assert np.array_equal(boxes[:, 3:6].view(np.uint32), ((hi - lo) / two).view(np.uint32))
+    assert boxes[0].tolist() == [np.float32(0.1) / two + np.float32(0.7) / two, 0.25, 3.0, (np.float32(0.7) - np.float32(0.1)) / two, 2.25, 0.0]
+    assert boxes[1, 0] == np.float32(1e8 + 8) and boxes[1, 3] == 8.0 and boxes[2, 3] == -0.5
+    assert _capi._boxes_from_corners([0, 0, 0], [2, 4, 6]).tolist() == [[1, 2, 3, 1, 2, 3]]   # one box given as two vectors
+    # the two-call sizing: a first call that reports the total (as a capacity refusal), a second with room
+    calls = []
+
+    def fake(off, vals, cap, total):
+        calls.append((vals, cap))
+        C.cast(off, C.POINTER(C.c_uint64))[2] = 3
+        C.cast(total, C.POINTER(C.c_int64))[0] = 3
+        if cap < 3:
+            return _capi.ERR_CAPACITY
+        for k, v in enumerate((7, 8, 9)):
+            C.cast(vals, C.POINTER(C.c_uint32))[k] = v
+        return 0
+    off, vals = _capi._overlap_lists(fake, 2, None)
+    assert [c[1] for c in calls] == [0, 3] and calls[0][0] is None
+    assert off.dtype == np.int64 and off.tolist() == [0, 0, 3] and vals.dtype == np.uint32 and vals.tolist() == [7, 8, 9]
+    off, vals = _capi._overlap_lists(fake, 2, 8)   # a given capacity: one call
+    assert len(calls) == 3 and calls[2][1] == 8 and vals.tolist() == [7, 8, 9]
+    with pytest.raises(mgf_amd.MgfError):
+        _capi._overlap_lists(fake, 2, 1)
+
+
 def test_scenes_are_deterministic():
     z = scenes.splitmix64(0x6D6766, 3)
     assert z.dtype == np.uint64 and len(set(z.tolist())) == 3
