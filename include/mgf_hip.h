@@ -560,8 +560,9 @@ MGF_API mgf_status mgf_world_release_device_ptrs(mgf_world* w);
  * depend on what else is in the batch or on where in it the world sits.  No workgroup waits for another: a batch may hold more
  * worlds than the device holds workgroups, and it is safe on a device shared with another process.
  * LIMITS: bodies of one component (spheres and capsules); at most MGF_BATCH_MAX_BODIES bodies per world (a call that would exceed it
- * is refused with MGF_ERR_INVALID and adds nothing); one terrain mesh shared by every world (copied, its position included; NULL =
- * none); canonical constraint order only.  There are no bodies of several components, no obstacles, no ghosts or tiles and no
+ * is refused with MGF_ERR_INVALID and adds nothing); the static geometry of a world is one terrain mesh, or none: an entry of the
+ * batch's terrain table (meshes are copied in; any number of worlds may share an entry) at a position of the world's own; canonical
+ * constraint order only.  There are no bodies of several components, no obstacles, no ghosts or tiles and no
  * constraint_order = demo: a batch has no entry point for them.  A tick never fails for list sizes: a world whose
  * constraints outgrow its share of the storage gets its tick undone on the device and run again with more (Solver::solve and
  * World::step have no capacity failure, solver.rs:72-78); mgf_batch_counter "capacity_retries" counts those re-runs.
@@ -569,7 +570,26 @@ MGF_API mgf_status mgf_world_release_device_ptrs(mgf_world* w);
 #define MGF_BATCH_MAX_BODIES 1024
 MGF_API mgf_status mgf_batch_new(mgf_ctx* ctx, const mgf_params* params, int64_t n_worlds, mgf_batch** out);  /* n_worlds x World::new world.rs:160 */
 MGF_API void mgf_batch_free(mgf_batch* b);
-MGF_API mgf_status mgf_batch_set_terrain(mgf_batch* b, const mgf_mesh* mesh);                     /* World.terrain, shared */
+/* ---- the terrain table: a mesh per world.  World k behaves, bit for bit, as a lone mgf_world that holds world k's bodies and has had
+ * mgf_world_set_terrain called with mesh terrain[k] after mgf_mesh_set_pos(pos[k]) - the tick's state, the constraint list with impulses
+ * (Static{ center } of a terrain constraint is the world's mesh position, world.rs:247), the statistics, the queries below (a face index
+ * is the mesh's own) - or as one without terrain.  What a world computes depends neither on the order of the table nor on which other
+ * worlds share its mesh; the number of launches of a tick or a query does not depend on the table.
+ * mgf_batch_add_terrain copies the mesh (its tree, vertices, faces and current position) behind the table's last entry and returns its
+ * id: 0, 1, ...; no world changes.  A mesh with an empty tree is a valid entry that behaves as no terrain.
+ * mgf_batch_set_world_terrain applies n assignments in order (a world named twice keeps the last): world[i] gets entry terrain[i], or
+ * none for -1, at pos[i], or with pos = NULL at the position the mesh had when it was added - one heightfield at a thousand offsets is
+ * stored once.  It may be called between any two mgf_batch_step calls and holds from the next tick; it moves no body, no fat box and no
+ * collider a query sees.
+ * mgf_batch_terrain_count: the table's length, -1 for NULL.
+ * mgf_batch_set_terrain(b, mesh) empties the table, makes `mesh` its entry 0 and gives it to every world at the mesh's position; with
+ * NULL the table is empty and no world has terrain.
+ * Refused with MGF_ERR_INVALID, nothing changed at all: a NULL batch, a NULL mesh or id, NULL world or terrain with n > 0, a negative n,
+ * a world index outside [0, n_worlds), a terrain id below -1 or >= the table's length. */
+MGF_API mgf_status mgf_batch_set_terrain(mgf_batch* b, const mgf_mesh* mesh);                     /* World.terrain, of every world */
+MGF_API mgf_status mgf_batch_add_terrain(mgf_batch* b, const mgf_mesh* mesh, int32_t* id);
+MGF_API mgf_status mgf_batch_set_world_terrain(mgf_batch* b, const int32_t* world, const int32_t* terrain, const mgf_vec3* pos, int64_t n);
+MGF_API int64_t mgf_batch_terrain_count(const mgf_batch* b);
 /* World::add_body / RigidBodyVec::add_body (physics.rs:200-218, world.rs:178-184) in bulk, for world `world`; *first_id = the index of the
  * first new body within that world.  A tag other than 0 or 1, a negative n, a world index out of range: MGF_ERR_INVALID. */
 MGF_API mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mgf_component* comps, int64_t n, const float* mass,
@@ -589,7 +609,8 @@ MGF_API mgf_status mgf_batch_write_state(mgf_batch* b, int64_t world, const mgf_
 MGF_API mgf_status mgf_batch_read_constraints(mgf_batch* b, int64_t world, mgf_constraint* out, int64_t cap, int64_t* count);
 /* ---- queries against the worlds of a batch, between ticks.  The definition is the lone world's ("queries against the world between
  * ticks", above): out[i] is, bit for bit, what mgf_world_raycast_many / mgf_world_sweep_many reports for query i on a lone mgf_world
- * that holds world world[i]'s bodies and the batch's terrain and has been through the same calls.
+ * that holds world world[i]'s bodies and that world's terrain at that world's mesh position (the terrain table, above) and has been
+ * through the same calls.
  *   Ray cast: the closest hit of Intersects<shape> (collision.rs:169-373; compound.rs:150 for a component), the smallest t, ties to the
  *   target first in the order bodies (ascending index), terrain faces (ascending index); a particle with d = 0 hits nothing.
  *   Sweep: the earliest contact of Contacts<Moving<Sphere | Capsule>> of a body's sphere or capsule (collision.rs:1089-1356; :1143

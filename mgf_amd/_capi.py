@@ -145,7 +145,8 @@ SYMBOLS = [
     "mgf_geom_to_json", "mgf_geom_from_json",
     "mgf_tiles_create", "mgf_tiles_free", "mgf_rccl_unique_id", "mgf_rccl_allow_override", "mgf_tiles_connect", "mgf_tiles_preflight", "mgf_tiles_step",
     "mgf_tiles_migrated", "mgf_tiles_set_option", "mgf_world_add_obstacle", "mgf_tiles_counter",
-    "mgf_batch_new", "mgf_batch_free", "mgf_batch_set_terrain", "mgf_batch_add_bodies", "mgf_batch_len", "mgf_batch_step",
+    "mgf_batch_new", "mgf_batch_free", "mgf_batch_set_terrain", "mgf_batch_add_terrain", "mgf_batch_set_world_terrain",
+    "mgf_batch_terrain_count", "mgf_batch_add_bodies", "mgf_batch_len", "mgf_batch_step",
     "mgf_batch_read_state", "mgf_batch_write_state", "mgf_batch_read_constraints", "mgf_batch_counter", "mgf_batch_set_option",
     "mgf_batch_read_colliders", "mgf_batch_raycast_many", "mgf_batch_sweep_many",
     "mgf_batch_read_body_contacts", "mgf_batch_overlap_aabb_many",
@@ -284,6 +285,9 @@ def load_library():
         "mgf_batch_new": (i32, [vp, P(Params), i64, P(vp)]),
         "mgf_batch_free": (None, [vp]),
         "mgf_batch_set_terrain": (i32, [vp, vp]),
+        "mgf_batch_add_terrain": (i32, [vp, vp, P(i32)]),
+        "mgf_batch_set_world_terrain": (i32, [vp, vp, vp, vp, i64]),
+        "mgf_batch_terrain_count": (i64, [vp]),
         "mgf_batch_add_bodies": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, P(u64)]),
         "mgf_batch_len": (i64, [vp, i64]),
         "mgf_batch_step": (i32, [vp, f32, i32, i64, vp]),
@@ -1188,10 +1192,29 @@ class World:
         _check(load_library().mgf_world_release_device_ptrs(self._h))
 
 
+def terrain_table(terrains):
+    """The terrain table of WorldBatch.from_scenes(own_terrain=True) for one scene terrain (dict of verts, faces, pos, or None) per
+    world: (entries, assignment) - the distinct geometries in the order they first occur, each at its first position, and per world
+    (entry id or -1, pos).  Terrains with the same vertices and faces, bit for bit, share an entry whatever their pos."""
+    entries, ids, assign = [], {}, []
+    for t in terrains:
+        if t is None:
+            assign.append((-1, (0.0, 0.0, 0.0)))
+            continue
+        v = np.ascontiguousarray(t["verts"], np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(t["faces"], np.uint32).reshape(-1, 3)
+        key = (v.shape[0], f.shape[0], v.tobytes(), f.tobytes())
+        if key not in ids:
+            ids[key] = len(entries)
+            entries.append(t)
+        assign.append((ids[key], tuple(float(c) for c in t["pos"])))
+    return entries, assign
+
+
 class WorldBatch:
     """Many small independent worlds resident on one GPU, stepped together (mgf_batch_*): per world `step` is
-    mgf_demo/world.rs::World::step, one workgroup a world.  At most BATCH_MAX_BODIES single-component bodies per world, one
-    terrain mesh shared by all."""
+    mgf_demo/world.rs::World::step, one workgroup a world.  At most BATCH_MAX_BODIES single-component bodies per world; a world's
+    terrain is an entry of the batch's terrain table (shared by any number of worlds) at a position of its own, or none."""
 
     def __init__(self, ctx, n_worlds, params=None):
         self._ctx = ctx
@@ -1207,15 +1230,26 @@ class WorldBatch:
             self._h = None
 
     @classmethod
-    def from_scenes(cls, ctx, scenes, params=None):
-        """scenes as mgf_amd.scenes makes them, one per world; the first scene's terrain serves all"""
+    def from_scenes(cls, ctx, scenes, params=None, own_terrain=False):
+        """scenes as mgf_amd.scenes makes them, one per world; the first scene's terrain serves all, or (own_terrain) every world gets
+        its scene's: scenes whose terrains have the same vertices and faces share a table entry, each at its own `pos`"""
         b = cls(ctx, len(scenes), params)
-        t = scenes[0]["terrain"] if len(scenes) else None
-        if t is not None:
-            m = Mesh(ctx)
-            m.build(t["verts"], t["faces"])
-            m.set_pos(t["pos"])
-            b.set_terrain(m)
+        if own_terrain:
+            entry, pos = terrain_table([sc["terrain"] for sc in scenes])
+            for t in entry:
+                m = Mesh(ctx)
+                m.build(t["verts"], t["faces"])
+                m.set_pos(t["pos"])
+                b.add_terrain(m)
+            if len(scenes):
+                b.set_world_terrain(np.arange(len(scenes)), [e for e, _ in pos], [p for _, p in pos])
+        else:
+            t = scenes[0]["terrain"] if len(scenes) else None
+            if t is not None:
+                m = Mesh(ctx)
+                m.build(t["verts"], t["faces"])
+                m.set_pos(t["pos"])
+                b.set_terrain(m)
         for k, sc in enumerate(scenes):
             if sc.get("compound") is not None:
                 raise MgfError(ERR_INVALID, "a batch world holds bodies of one component")
@@ -1226,7 +1260,26 @@ class WorldBatch:
         return b
 
     def set_terrain(self, mesh):
+        """the table emptied, `mesh` its entry 0 and every world's terrain; None: no world has terrain"""
         _check(load_library().mgf_batch_set_terrain(self._h, mesh._h if mesh is not None else None))
+
+    def add_terrain(self, mesh):
+        """a copy of the mesh (at its current position) as a new entry of the terrain table; returns its id.  No world changes."""
+        i = C.c_int32(-1)
+        _check(load_library().mgf_batch_add_terrain(self._h, mesh._h if mesh is not None else None, C.byref(i)))
+        return i.value
+
+    def set_world_terrain(self, world, terrain, pos=None):
+        """world[i] gets table entry terrain[i] (-1: none) at pos[i] (None: where the mesh was when it was added), from the next tick;
+        scalars or arrays (a scalar terrain, one pos: for every world named)"""
+        wd = np.ascontiguousarray(np.atleast_1d(world), np.int32)
+        n = len(wd)
+        tr = np.ascontiguousarray(np.broadcast_to(np.asarray(terrain, np.int32), (n,)))
+        ps = None if pos is None else np.ascontiguousarray(np.broadcast_to(np.asarray(pos, np.float32), (n, 3)))
+        _check(load_library().mgf_batch_set_world_terrain(self._h, wd.ctypes.data, tr.ctypes.data, _ptr(ps), n))
+
+    def terrain_count(self):
+        return load_library().mgf_batch_terrain_count(self._h)
 
     def add_bodies(self, world, comps, mass, restitution, friction, world_force):
         comps = np.ascontiguousarray(comps, dtype=COMPONENT_DTYPE)

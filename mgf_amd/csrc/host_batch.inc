@@ -5,6 +5,9 @@
 // (a world in the middle of the batch grows by insertion); the mirror goes up before the first call that needs the device and comes
 // back down if bodies are added after that.  Every world has a share of the candidate and of the constraint storage; a tick that needs
 // more than its share undoes itself on the device and is run again with more (counter "capacity_retries").
+// The terrain is a table of meshes, copied one behind the other into one store each of nodes, vertices and faces as they are added, and
+// per world an entry of the table (or none) and a mesh position; the kernels read a descriptor per world (BatchTerrains, k_batch.h), which
+// goes up before the first tick or query behind a change.
 
 struct mgf_batch {
   mgf_ctx* ctx = nullptr;
@@ -17,11 +20,16 @@ struct mgf_batch {
   DBuf<float4> bpk, undo;          // the tick's packed copy (4 a body); what a tick that did not fit puts back (7 a body)
   std::vector<uint32_t> h_n, h_off;  // bodies per world; their prefix sums (K + 1)
   bool dev_valid = false;            // the device arrays hold the state (else the mirror does)
-  // the shared terrain
+  // the terrain table (its meshes concatenated on the device) and every world's entry of it (-1: none) and mesh position
+  struct TerrainEntry { uint32_t node0, n_nodes, vert0, face0; V3 x; };
+  std::vector<TerrainEntry> t_table;
   DBuf<float4> t_nodes, t_verts;
-  DBuf<uint4> t_faces;
-  uint32_t t_n_nodes = 0;
-  V3 t_x = mk3(0, 0, 0);
+  DBuf<uint4> t_faces, t_desc;
+  size_t t_n_nodes = 0, t_n_verts = 0, t_n_faces = 0;  // the stores' lengths (nodes: two words each)
+  std::vector<int32_t> h_wt;
+  std::vector<V3> h_wx;
+  bool t_desc_stale = true;   // the descriptors on the device are behind the table or the assignments
+  uint32_t t_worlds = 0;      // worlds whose terrain has a node, as of the descriptors on the device
   // constraint storage
   std::vector<uint32_t> h_coff, h_cap, h_floor, h_qfloor, h_ccount;  // offsets / shares of the lists / the least a world has asked for (records, candidates) / length of the last tick's list
   bool lists_valid = false;
@@ -167,6 +175,7 @@ extern "C" mgf_status mgf_batch_new(mgf_ctx* ctx, const mgf_params* params, int6
   b->ctx = ctx;
   b->params = params ? *params : mgf_default_params();
   b->K = (uint32_t)n_worlds;
+  b->h_wt.assign(b->K, -1); b->h_wx.assign(b->K, mk3(0, 0, 0));
   b->h_n.assign(b->K, 0u); b->h_floor.assign(b->K, 0u); b->h_qfloor.assign(b->K, 0u); b->h_ccount.assign(b->K, 0u);
   batch_offsets(b.get());
   ctx_retain(ctx);
@@ -221,25 +230,99 @@ static void batch_thread_tree(const HostBvh& t, uint64_t id, std::vector<float4>
   memcpy(&(*out)[2 * at].w, &w0, 4);
   memcpy(&(*out)[2 * at + 1].w, &skip, 4);
 }
-extern "C" mgf_status mgf_batch_set_terrain(mgf_batch* b, const mgf_mesh* mesh) {
-  MGF_TRY(batch_bind(b));
-  if (!mesh || mesh->m.tree.empty()) { b->t_n_nodes = 0; return MGF_OK; }
-  hipStream_t s = b->ctx->stream;
+// a copy of the mesh behind the table's last entry
+static mgf_status batch_table_add(mgf_batch* b, const mgf_mesh* mesh) {
   std::vector<float4> nodes;
-  batch_thread_tree(mesh->m.tree, mesh->m.tree.root(), &nodes);
+  if (!mesh->m.tree.empty()) batch_thread_tree(mesh->m.tree, mesh->m.tree.root(), &nodes);
   std::vector<float4> hv(mesh->verts.size());
   for (size_t i = 0; i < hv.size(); ++i) hv[i] = make_float4(mesh->verts[i].x, mesh->verts[i].y, mesh->verts[i].z, 0.0f);
   std::vector<uint4> hf(mesh->faces.size() / 3);
   for (size_t i = 0; i < hf.size(); ++i) hf[i] = make_uint4(mesh->faces[3 * i], mesh->faces[3 * i + 1], mesh->faces[3 * i + 2], 0);
-  MGF_HIP_TRY(hipStreamSynchronize(s));
-  MGF_TRY(b->t_nodes.ensure(nodes.size(), s)); MGF_TRY(b->t_verts.ensure(std::max<size_t>(hv.size(), 1), s)); MGF_TRY(b->t_faces.ensure(std::max<size_t>(hf.size(), 1), s));
-  MGF_TRY(h2d(b->ctx, b->t_nodes.p, nodes.data(), nodes.size()));
-  MGF_TRY(h2d(b->ctx, b->t_verts.p, hv.data(), hv.size()));
-  MGF_TRY(h2d(b->ctx, b->t_faces.p, hf.data(), hf.size()));
-  b->t_n_nodes = (uint32_t)(nodes.size() / 2);
-  b->t_x = mesh->x;
+  if (b->t_n_nodes + nodes.size() / 2 > 0x7FFFFFF0ull || b->t_n_verts + hv.size() > 0x7FFFFFF0ull || b->t_n_faces + hf.size() > 0x7FFFFFF0ull)
+    return fail(MGF_ERR_OOM, "the batch's terrain table exceeds 2^31 nodes, vertices or faces");
+  MGF_TRY(append(b->ctx, b->t_nodes, 2 * b->t_n_nodes, nodes));
+  MGF_TRY(append(b->ctx, b->t_verts, b->t_n_verts, hv));
+  MGF_TRY(append(b->ctx, b->t_faces, b->t_n_faces, hf));
+  mgf_batch::TerrainEntry e;
+  e.node0 = (uint32_t)b->t_n_nodes; e.n_nodes = (uint32_t)(nodes.size() / 2); e.vert0 = (uint32_t)b->t_n_verts; e.face0 = (uint32_t)b->t_n_faces;
+  e.x = mesh->x;
+  b->t_table.push_back(e);
+  b->t_n_nodes += nodes.size() / 2; b->t_n_verts += hv.size(); b->t_n_faces += hf.size();
   return MGF_OK;
 }
+// every world's descriptor onto the device, before the first launch behind a change of the table or of an assignment
+static mgf_status batch_terrain_sync(mgf_batch* b) {
+  if (!b->t_desc_stale) return MGF_OK;
+  hipStream_t s = b->ctx->stream;
+  std::vector<uint4> d(2 * (size_t)b->K, make_uint4(0u, 0u, 0u, 0u));
+  uint32_t with = 0;
+  for (uint32_t k = 0; k < b->K; ++k) {
+    if (b->h_wt[k] < 0) continue;
+    const mgf_batch::TerrainEntry& e = b->t_table[(size_t)b->h_wt[k]];
+    const V3 x = b->h_wx[k];
+    uint32_t xb[3];
+    memcpy(&xb[0], &x.x, 4); memcpy(&xb[1], &x.y, 4); memcpy(&xb[2], &x.z, 4);
+    d[2 * (size_t)k] = make_uint4(e.node0, e.vert0, e.face0, e.n_nodes);
+    d[2 * (size_t)k + 1] = make_uint4(xb[0], xb[1], xb[2], 0u);
+    if (e.n_nodes) ++with;
+  }
+  MGF_TRY(b->t_desc.ensure(d.size(), s));
+  MGF_TRY(b->t_nodes.ensure(1, s)); MGF_TRY(b->t_verts.ensure(1, s)); MGF_TRY(b->t_faces.ensure(1, s));
+  MGF_TRY(h2d(b->ctx, b->t_desc.p, d.data(), d.size()));
+  b->t_worlds = with;
+  b->t_desc_stale = false;
+  return MGF_OK;
+}
+static BatchTerrains batch_terrains(const mgf_batch* b) {
+  BatchTerrains T;
+  T.nodes = b->t_nodes.p; T.verts = b->t_verts.p; T.faces = b->t_faces.p; T.desc = b->t_desc.p;
+  return T;
+}
+// The table emptied, `mesh` its entry 0 and every world's terrain, at the mesh's position; NULL: an empty table, no world has terrain.
+extern "C" mgf_status mgf_batch_set_terrain(mgf_batch* b, const mgf_mesh* mesh) {
+  MGF_TRY(batch_bind(b));
+  b->t_table.clear();
+  b->t_n_nodes = b->t_n_verts = b->t_n_faces = 0;
+  std::fill(b->h_wt.begin(), b->h_wt.end(), -1);
+  b->t_desc_stale = true;
+  if (!mesh) return MGF_OK;
+  MGF_TRY(batch_table_add(b, mesh));
+  std::fill(b->h_wt.begin(), b->h_wt.end(), 0);
+  std::fill(b->h_wx.begin(), b->h_wx.end(), mesh->x);
+  return MGF_OK;
+}
+extern "C" mgf_status mgf_batch_add_terrain(mgf_batch* b, const mgf_mesh* mesh, int32_t* id) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (!mesh || !id) return fail(MGF_ERR_INVALID, "NULL argument");
+  MGF_TRY(ctx_bind(b->ctx));
+  if (b->t_table.size() >= 0x7FFFFFFFull) return fail(MGF_ERR_OOM, "the batch's terrain table is full");
+  MGF_TRY(batch_table_add(b, mesh));
+  *id = (int32_t)(b->t_table.size() - 1);
+  return MGF_OK;
+}
+extern "C" mgf_status mgf_batch_set_world_terrain(mgf_batch* b, const int32_t* world, const int32_t* terrain, const mgf_vec3* pos, int64_t n) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (n < 0) return fail(MGF_ERR_INVALID, "n is negative");
+  if (n && (!world || !terrain)) return fail(MGF_ERR_INVALID, "NULL argument");
+  for (int64_t i = 0; i < n; ++i) {
+    if (world[i] < 0) return fail(MGF_ERR_INVALID, "world index out of range");
+    if (terrain[i] < -1) return fail(MGF_ERR_INVALID, "terrain id out of range");
+  }
+  MGF_TRY(ctx_bind(b->ctx));
+  for (int64_t i = 0; i < n; ++i) {
+    if ((uint32_t)world[i] >= b->K) return fail(MGF_ERR_INVALID, "world index out of range");
+    if (terrain[i] >= 0 && (size_t)terrain[i] >= b->t_table.size()) return fail(MGF_ERR_INVALID, "terrain id out of range");
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const size_t k = (size_t)world[i];
+    b->h_wt[k] = terrain[i];
+    if (terrain[i] < 0) b->h_wx[k] = mk3(0, 0, 0);
+    else b->h_wx[k] = pos ? mk3(pos[i].x, pos[i].y, pos[i].z) : b->t_table[(size_t)terrain[i]].x;
+  }
+  if (n) b->t_desc_stale = true;
+  return MGF_OK;
+}
+extern "C" int64_t mgf_batch_terrain_count(const mgf_batch* b) { return b ? (int64_t)b->t_table.size() : -1; }
 
 // RigidBodyVec::add_body physics.rs:200-218 + World::add_body world.rs:178-184 (initial fat AABB), as mgf_world_add_bodies, for one world of the batch.
 extern "C" mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mgf_component* comps, int64_t n, const float* mass, const float* restitution,
@@ -377,6 +460,7 @@ extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int6
   if (n_ticks > (1 << 20)) return fail(MGF_ERR_INVALID, "n_ticks must be at most 2^20");
   MGF_TRY(ctx_bind(b->ctx));
   MGF_TRY(batch_push(b));
+  MGF_TRY(batch_terrain_sync(b));
   if (n_ticks == 0) return MGF_OK;
   mgf_ctx* ctx = b->ctx;
   hipStream_t s = ctx->stream;
@@ -402,8 +486,7 @@ extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int6
     float4* u = b->undo.p;
     const size_t n = b->total();
     A.U.p = u; A.U.n = (uint32_t)n;
-    A.M.nodes = b->t_nodes.p; A.M.verts = b->t_verts.p; A.M.faces = b->t_faces.p; A.M.n_nodes = b->t_n_nodes;
-    A.M.x[0] = b->t_x.x; A.M.x[1] = b->t_x.y; A.M.x[2] = b->t_x.z;
+    A.T = batch_terrains(b);
     A.w_off = b->d_off.p; A.cons = b->cons.p; A.rows = b->rows.p; A.c_off = b->d_coff.p; A.c_cap = b->d_cap.p;
     A.cand = b->cand.p; A.q_off = b->d_qoff.p; A.q_cap = b->d_qcap.p; A.q_count = b->d_qcount.p; A.cont = b->cont.p; A.ncq = b->ncq.p; A.slot = b->slot.p;
     A.na = b->d_na.p; A.degb = b->d_degb.p; A.stage = b->d_stage.p;

@@ -2,7 +2,7 @@
 // (k_batch_query.h).  Part of the single translation unit mgf_hip.hip (included there, in order); not compiled on its own.
 //
 // A call sorts its query indices by world (one stable counting sort), cuts every world's run into work items of up to 256 queries,
-// uploads items, queries, order and ignore list in ONE copy, launches a workgroup per work item - the number of launches depends on
+// uploads items, queries, order, ignore list and (for the sweeps' face pass, a lane per cast) the worlds in ONE copy, launches a workgroup per work item - the number of launches depends on
 // neither the number of worlds nor the number of queries - and downloads the hits: one host wait per call.  Nothing of the tick's state
 // is written; of it only bpk is read, once, by the collider gather behind a mgf_batch_step (batch_cols_refresh).
 // batch_query_args / _worlds / _open / _upload are every front end's steps ahead of its launches, the box query's
@@ -72,26 +72,29 @@ static mgf_status batch_query_open(mgf_batch* b, const int32_t* world, size_t n)
 }
 
 // What the ray, sweep and box queries do ahead of their launches (n > 0): the bodies added since pushed, the plan, ONE upload -
-// items | queries | order | ignore, every section from a 16-byte boundary - and the colliders refreshed behind a tick.
+// items | queries | order | ignore | world, every section from a 16-byte boundary - and the colliders refreshed behind a tick.
 struct BatchQueryUpload {
   size_t n_items = 0;
   const float4* queries = nullptr;  // the caller's q_bytes a query, in the caller's order
   const int32_t* ignore = nullptr;  // null: none given
+  const int32_t* world = nullptr;   // by the caller's index; null: not asked for
   uint32_t lds = 0;                 // 32 bytes a body of the largest world (at most 32 KB)
   std::vector<float4> host;         // what the copy reads: alive until the call has waited for the stream
 };
 static mgf_status batch_query_upload(mgf_batch* b, const int32_t* world, const void* queries, size_t q_bytes, size_t n, const int32_t* ignore_body,
-                                     BatchWorkArgs* A, BatchQueryUpload* U) {
+                                     BatchWorkArgs* A, BatchQueryUpload* U, bool with_world = false) {
   MGF_TRY(batch_push(b));
   hipStream_t s = b->ctx->stream;
   const BatchQueryPlan plan(b->K, world, n);
   const size_t w_q = (n * q_bytes + 15) / 16, w_idx = (4 * n + 15) / 16;
-  const size_t o_q = plan.n_items, o_order = o_q + w_q, o_ign = o_order + w_idx, total = o_ign + (ignore_body ? w_idx : 0);
+  const size_t o_q = plan.n_items, o_order = o_q + w_q, o_ign = o_order + w_idx, o_world = o_ign + (ignore_body ? w_idx : 0),
+               total = o_world + (with_world ? w_idx : 0);
   std::vector<float4>& h = U->host;
   h.resize(total);
   memcpy(h.data() + o_q, queries, n * q_bytes);
   plan.fill(world, n, reinterpret_cast<uint4*>(h.data()), reinterpret_cast<uint32_t*>(h.data() + o_order));
   if (ignore_body) memcpy(h.data() + o_ign, ignore_body, 4 * n);
+  if (with_world) memcpy(h.data() + o_world, world, 4 * n);
   MGF_TRY(b->q_in.ensure(total, s));
   MGF_HIP_TRY(hipMemcpyAsync(b->q_in.p, h.data(), 16 * total, hipMemcpyHostToDevice, s));
   MGF_TRY(batch_cols_refresh(b, &b->q_launches));
@@ -102,6 +105,7 @@ static mgf_status batch_query_upload(mgf_batch* b, const int32_t* world, const v
   A->order = reinterpret_cast<const uint32_t*>(b->q_in.p + o_order);
   U->n_items = plan.n_items; U->queries = b->q_in.p + o_q;
   U->ignore = ignore_body ? reinterpret_cast<const int32_t*>(b->q_in.p + o_ign) : nullptr;
+  U->world = with_world ? reinterpret_cast<const int32_t*>(b->q_in.p + o_world) : nullptr;
   U->lds = 32u * nmax;
   return MGF_OK;
 }
@@ -119,12 +123,12 @@ static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* q
   BatchQueryArgs A;
   memset(&A, 0, sizeof(A));
   BatchQueryUpload U;
-  MGF_TRY(batch_query_upload(b, world, queries, sizeof(Q), n, ignore_body, &A, &U));
+  MGF_TRY(batch_terrain_sync(b));
+  const bool faces = !kRays && (kinds_mask & MGF_QUERY_TERRAIN) && b->t_worlds;  // a world of the batch has a terrain to sweep against
+  MGF_TRY(batch_query_upload(b, world, queries, sizeof(Q), n, ignore_body, &A, &U, faces));
   MGF_TRY(b->q_out.ensure(kOut * n, s));
   const uint32_t lds = U.lds + 16u * kBatchQueryRed;  // (at most 32 KB + 256 bytes: two workgroups a CU at the largest world)
-  A.M.nodes = b->t_nodes.p; A.M.verts = b->t_verts.p; A.M.faces = b->t_faces.p;
-  A.M.n_nodes = (kinds_mask & MGF_QUERY_TERRAIN) ? b->t_n_nodes : 0u;
-  A.M.x[0] = b->t_x.x; A.M.x[1] = b->t_x.y; A.M.x[2] = b->t_x.z;
+  A.T = batch_terrains(b);
   A.ignore = U.ignore;
   A.mask = kinds_mask;
   A.out = b->q_out.p;
@@ -138,8 +142,8 @@ static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* q
     k_batch_query_sweep_bodies<<<(unsigned)U.n_items, kBatchBlock, lds, s>>>(A, dq);
     LAUNCH_CHECK();
     ++b->q_launches;
-    if (A.M.n_nodes) {
-      k_batch_query_sweep_faces<<<(unsigned)((n + kBatchBlock - 1) / kBatchBlock), kBatchBlock, 0, s>>>(A.M, dq, (uint32_t)n, A.out);
+    if (faces) {
+      k_batch_query_sweep_faces<<<(unsigned)((n + kBatchBlock - 1) / kBatchBlock), kBatchBlock, 0, s>>>(A.T, U.world, dq, (uint32_t)n, A.out);
       LAUNCH_CHECK();
       ++b->q_launches;
     }

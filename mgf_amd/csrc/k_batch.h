@@ -32,6 +32,17 @@ constexpr uint32_t kBatchSpinLimit = 1u << 22;  // trips of the solve loop witho
 // of the first node behind its subtree: a walk without a stack - and so without scratch memory - that reports the same leaves in the same order.
 //   node = (c.xyz, w0), (r.xyz, skip); leaf: w0 = 0x80000000 | face.
 struct BatchTerrain { const float4* nodes; const float4* verts; const uint4* faces; uint32_t n_nodes; float x[3]; };
+// The meshes of the batch's terrain table, one behind the other in one store each of nodes, vertices and faces (a node's skip index, a
+// face's vertex indices and the face index of a leaf are the mesh's own), and what world k has of it: desc[2k] = (first node, first
+// vertex, first face, nodes - 0: no terrain), desc[2k + 1] = (the world's mesh position, -).
+struct BatchTerrains { const float4* nodes; const float4* verts; const uint4* faces; const uint4* desc; };
+__device__ __forceinline__ BatchTerrain batch_terrain_of(const BatchTerrains& T, uint32_t k) {
+  const uint4 d0 = T.desc[2 * (size_t)k], d1 = T.desc[2 * (size_t)k + 1];
+  BatchTerrain M;
+  M.nodes = T.nodes + 2 * (size_t)d0.x; M.verts = T.verts + d0.y; M.faces = T.faces + d0.z; M.n_nodes = d0.w;
+  M.x[0] = u2f(d1.x); M.x[1] = u2f(d1.y); M.x[2] = u2f(d1.z);
+  return M;
+}
 
 template <class F>
 __device__ __forceinline__ void batch_terrain_walk(const BatchTerrain& M, const Box& q, F&& emit) {
@@ -52,7 +63,7 @@ __device__ __forceinline__ float4& undo_at(const TickUndo& U, int r, size_t g) {
 struct BatchArgs {
   Bodies B;                  // every world's bodies, world k at [w_off[k], w_off[k + 1]); bpk is the tick's packed copy
   TickUndo U;
-  BatchTerrain M;
+  BatchTerrains T;           // world k's terrain: batch_terrain_of(T, k), k the workgroup's index (wave-uniform loads)
   const uint32_t* w_off;
   uint2* cand;               // world k's candidates at q_off[k], q_cap[k] entries: (i, j) or (i, 0x80000000 | face)
   const uint32_t* q_off;
@@ -169,7 +180,8 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_front(BatchArgs A) {
   __syncthreads();
   // the candidates of body i, in the list's order: counted, scanned, listed
   uint2* cand = A.cand + A.q_off[k];
-  const V3 mx = mk3(A.M.x[0], A.M.x[1], A.M.x[2]);
+  const BatchTerrain M = batch_terrain_of(A.T, k);
+  const V3 mx = mk3(M.x[0], M.x[1], M.x[2]);
 #pragma unroll 1
   for (int pass = 0; pass < 2; ++pass) {
     uint32_t npair = 0;
@@ -177,7 +189,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_front(BatchArgs A) {
       Box q; q.c = xyz(s_tc[i]); q.r = xyz(s_tr[i]);
       Box qm = q; qm.c = q.c + -mx;  // Mesh::contacts queries bounds - mesh.x (mesh.rs:121)
       uint32_t at = pass ? s_off[i] : 0u;
-      batch_terrain_walk(A.M, qm, [&](uint32_t f) {
+      batch_terrain_walk(M, qm, [&](uint32_t f) {
         if (pass) cand[at] = make_uint2(i, 0x80000000u | f);
         ++at;
       });
@@ -214,7 +226,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_faces(BatchArgs A) {
   __shared__ uint32_t s_ct;
   const uint32_t k = blockIdx.x, T = kBatchBlock, tid = threadIdx.x;
   if (A.done[k] != A.tick || A.stage[k] != 8u * A.tick + 1u || batch_failed(A, k)) return;
-  const uint32_t g0 = A.w_off[k], M = A.q_count[k];
+  const uint32_t g0 = A.w_off[k], Q = A.q_count[k];
   const Bodies& B = A.B;
   const uint2* cand = A.cand + A.q_off[k];
   uint32_t* ncq = A.ncq + A.q_off[k];
@@ -222,14 +234,15 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_faces(BatchArgs A) {
   if (tid == 0) s_ct = 0u;
   __syncthreads();
   {
-    const V3 mx = mk3(A.M.x[0], A.M.x[1], A.M.x[2]);
+    const BatchTerrain M = batch_terrain_of(A.T, k);
+    const V3 mx = mk3(M.x[0], M.x[1], M.x[2]);
     uint32_t ct = 0;
-    for (uint32_t p = tid; p < M; p += T) {
+    for (uint32_t p = tid; p < Q; p += T) {
       const uint2 e = cand[p];
       if (!(e.y & 0x80000000u)) continue;
       const BatchBody Pa = batch_load(B, (size_t)g0 + e.x);
-      const uint4 fi = A.M.faces[e.y & 0x7FFFFFFFu];
-      const Triangle tri = mkt(xyz(A.M.verts[fi.x]) + mx, xyz(A.M.verts[fi.y]) + mx, xyz(A.M.verts[fi.z]) + mx);  // mesh.rs:122-126
+      const uint4 fi = M.faces[e.y & 0x7FFFFFFFu];
+      const Triangle tri = mkt(xyz(M.verts[fi.x]) + mx, xyz(M.verts[fi.y]) + mx, xyz(M.verts[fi.z]) + mx);  // mesh.rs:122-126
       LocalContact lc[2];
       const int nc = comp_tri_local(Pa.col, Pa.d, tri, mx, lc);
       ncq[p] = (uint32_t)nc;
@@ -335,7 +348,8 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_setup(BatchArgs A) {
   uint32_t *s_na = s_first + n, *s_degb = s_first + 2 * (size_t)n;
   const float4* cont = A.cont + 4 * (size_t)A.c_off[k];
   CRec* cons = A.cons + A.c_off[k];
-  const V3 mx = mk3(A.M.x[0], A.M.x[1], A.M.x[2]);
+  const uint4 tx = A.T.desc[2 * (size_t)k + 1];  // the world's mesh position
+  const V3 mx = mk3(u2f(tx.x), u2f(tx.y), u2f(tx.z));
   for (uint32_t i = tid; i < n; i += T) { s_first[i] = kNone; s_na[i] = 0u; s_degb[i] = 0u; }
   __syncthreads();
   for (uint32_t c = tid; c < C; c += T) {

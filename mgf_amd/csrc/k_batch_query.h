@@ -2,7 +2,7 @@
 // (Part of the kernel set described in kernels.h.)
 //
 // The definition is the lone world's (k_query.h): out[i] is what mgf_world_raycast_many / mgf_world_sweep_many reports for query i on a
-// world that holds world[i]'s bodies and the batch's terrain - the same single-shape tests, the same ranking (t, kind, index, part, order
+// world that holds world[i]'s bodies and that world's terrain (BatchTerrains, k_batch.h) - the same single-shape tests, the same ranking (t, kind, index, part, order
 // emitted).  What differs is the work split.  A small world needs no grid: its colliders fit in LDS.
 //   k_batch_query_gather        the colliders the last tick built (bpk words 0 and 3, physics.rs:243-251) into the batch's persistent rows
 //                               col0 / col1; launched once behind a mgf_batch_step, before the first reader
@@ -34,7 +34,7 @@ struct BatchWorkArgs {
   const uint32_t* order;  // sorted position -> the caller's query index
 };
 struct BatchQueryArgs : BatchWorkArgs {
-  BatchTerrain M;         // n_nodes 0: no terrain
+  BatchTerrains T;        // a world's terrain: batch_terrain_of(T, world)
   const int32_t* ignore;  // by the caller's index: a body of the query's world, -1: none; null: none for all
   int32_t mask;
   int32_t* out;           // by the caller's index: 7 words a particle (mgf_ray_hit), 13 a cast (mgf_sweep_hit)
@@ -155,7 +155,10 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_query_ray(BatchQueryArgs 
   }
   bq_reduce(best, W, s_red);
   if (W.sub != 0u || !W.live) return;
-  if ((mask & MGF_QUERY_TERRAIN) && A.M.n_nodes) q_ray_terrain(A.M, p, d, dt, nullptr, best);
+  if (mask & MGF_QUERY_TERRAIN) {
+    const BatchTerrain M = batch_terrain_of(A.T, W.it.x);  // (the work item's world: wave-uniform loads)
+    if (M.n_nodes) q_ray_terrain(M, p, d, dt, nullptr, best);
+  }
   q_ray_store(A.out + 7 * (size_t)qi, best);
 }
 
@@ -192,10 +195,13 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_bodies(BatchQ
   q_sweep_store(A.out + 13 * (size_t)qi, best);
 }
 
-// q_sweep_terrain's tests over the threaded tree, a lane per cast (in the caller's order: the faces are the same for every world)
-__global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_faces(BatchTerrain M, const MovingIn* casts, uint32_t n, int32_t* out) {
+// q_sweep_terrain's tests over the threaded tree, a lane per cast in the caller's order, each over the terrain of its own cast's world
+// (world[i]; the walk is per lane as it is)
+__global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_faces(BatchTerrains T, const int32_t* world, const MovingIn* casts, uint32_t n, int32_t* out) {
   const uint32_t i = blockIdx.x * kBatchBlock + threadIdx.x;
   if (i >= n) return;
+  const BatchTerrain M = batch_terrain_of(T, (uint32_t)world[i]);
+  if (M.n_nodes == 0u) return;
   const SweepCast K = bq_sweep_cast(casts[i]);
   int32_t* o = out + 13 * (size_t)i;
   SweepBest best = q_sweep_load(o);  // k_batch_query_sweep_bodies' answer
