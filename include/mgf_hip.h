@@ -668,9 +668,60 @@ MGF_API mgf_status mgf_batch_read_body_contacts(mgf_batch* b, int64_t world, mgf
  * behind a step, count, fill; the prefix sum between them is the library's). */
 MGF_API mgf_status mgf_batch_overlap_aabb_many(mgf_batch* b, const int32_t* world, const mgf_aabb* boxes, int64_t n,
                                                uint64_t* out_offsets /* n+1 */, uint32_t* out_bodies, int64_t cap, int64_t* total);
+/* ---- driving a batch between ticks: get / set, forces and torques, impulses, world-to-world copies - on the device ----
+ * A (world[i], body[i]) pair names body body[i] of world world[i]; any order, any mix of worlds, a world may get no record (the
+ * addressing of mgf_batch_raycast_many).  The calls address a body no tick has touched yet like any other: a batch still in its host
+ * mirror, bodies added behind a tick; for such a body inv_moment is inv_moment_body, as add_body leaves it (physics.rs:212-214).
+ * They write the rows the tick reads - velocities, force, torque - and nothing else of the tick's state: fat boxes, colliders and the
+ * constraint list stay as they are, mgf_batch_read_body_contacts / _read_constraints still describe the last tick and the collider a
+ * query sees does not move, as mgf_world_set leaves the lone world.  A world that no record names is bit-for-bit untouched.
+ * Forces and torques are rows of the body: they survive mgf_batch_add_bodies behind a tick, mgf_batch_write_state does not touch them,
+ * mgf_batch_copy_worlds copies them.
+ * Records that name the same body are resolved deterministically: the record indices are sorted by body on the host (a stable sort:
+ * a body's records keep the caller's order) and one lane takes each body - no float atomic, no race between lanes.
+ * The number of kernel launches of a call depends on neither n nor n_worlds (mgf_batch_counter "drive_launches").
+ * Refused with MGF_ERR_INVALID, nothing changed: a NULL batch, NULL world / body with n > 0, NULL vel for mgf_batch_set_many, a negative
+ * n or n > INT32_MAX, a world index outside [0, n_worlds), a body index outside [0, mgf_batch_len(b, world[i])).
+ * OUT OF SCOPE here: the lone mgf_world gets no force setter (its migrant records, 148 floats and part of the ABI, carry the force but
+ * no torque); impulses at a point; a whole-batch clone; copies between contexts. */
+/* ConstrainedSet::get (physics.rs:272-304) for n bodies; any output may be NULL.  force / torque: RigidBodyVec.force / .torque
+ * (physics.rs:146-147) as stored: force = world_force * mass at add_body (physics.rs:207). */
+MGF_API mgf_status mgf_batch_get_many(mgf_batch* b, const int32_t* world, const int32_t* body, int64_t n,
+                                      mgf_velocity* vel, mgf_rigid_body_info* info, mgf_vec3* force, mgf_vec3* torque);
+/* ConstrainedSet::set (physics.rs:306-314), as n calls in array order: a body named twice keeps the last. */
+MGF_API mgf_status mgf_batch_set_many(mgf_batch* b, const int32_t* world, const int32_t* body, int64_t n, const mgf_velocity* vel);
+/* RigidBodyVec.force[i] = force[k], .torque[i] = torque[k]; either array NULL = left as it is; a body named twice keeps the last.
+ * Holds for every later tick until set again (physics.rs:236, 240 read them every integrate). */
+MGF_API mgf_status mgf_batch_set_forces(mgf_batch* b, const int32_t* world, const int32_t* body, int64_t n,
+                                        const mgf_vec3* force, const mgf_vec3* torque);
+/* This build's definition (the reference changes velocities only inside ContactConstraint::solve, solver.rs:243-247, in this form):
+ * record k, in array order:  v = v + linear[k] * inv_mass;  omega = omega + I * angular[k]
+ * inv_mass and I = the world-frame inv_moment as mgf_batch_get_many returns them at that moment.
+ * M * v = (c0 * v.x + c1 * v.y) + c2 * v.z (cgmath, column-major).  f32, no fused multiply-add.
+ * A body named several times receives its records one after the other in array order: the answer is defined to the bit.
+ * Either array NULL = zero for all records of that array. */
+MGF_API mgf_status mgf_batch_apply_impulses(mgf_batch* b, const int32_t* world, const int32_t* body, int64_t n,
+                                            const mgf_vec3* linear, const mgf_vec3* angular);
+/* RigidBodyVec: Clone (physics.rs:140) per world: world dst_world[i] of dst becomes world src_world[i] of src.  dst and src are one batch
+ * or two batches of one context.  src is const in what it holds, not in where: a source batch that is still in its host mirror is
+ * moved to the device first (its bodies, shares and lists allotted as its own next call would), nothing of its state changes.
+ * Copied is everything that makes the world step on, and answer, exactly like its source: every
+ * persistent row of its bodies (state, velocities, inverse mass and inertias, force, torque, restitution, friction, constructor, delta,
+ * fat box, the collider a query sees), the tick's packed copy, and the last tick's constraint list with its impulses and its length -
+ * mgf_batch_read_constraints, _read_body_contacts, _read_colliders, the ray casts, sweeps and box overlaps answer for the destination
+ * what they answer for the source, and with the same terrain the destination steps bit-identically to the source.
+ * Not copied: the terrain assignment (the environment is the destination's: mgf_batch_set_world_terrain copies it), the shares of the
+ * storage (a destination whose share is smaller than the source's list gets a larger one first, and keeps it - as a world keeps
+ * what a tick that did not fit asked for - until "cons_per_body" is set again), counters and options.
+ * A source may be named any number of times (fan-out).  Refused with MGF_ERR_INVALID, nothing copied, before any launch: a NULL batch,
+ * NULL arrays with n > 0, a negative n or n > INT32_MAX, a world index out of range, batches of different contexts, a destination and
+ * its source of different lengths, a destination named twice, and - where dst == src - a world that is both a source and a
+ * destination.  One workgroup per pair, one launch (and one more when shares grow): "drive_launches" of dst. */
+MGF_API mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_world, const mgf_batch* src, const int32_t* src_world, int64_t n);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
- * the last query call's kernels, as mgf_world_counter's)}. */
+ * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /
+ * _set_forces / _apply_impulses / _copy_worlds call on this batch - for a copy, on its destination: it depends on neither n_worlds nor n)}. */
 MGF_API mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out);
 /* Options (test knobs): "cons_per_body" [4] = the constraint records per body a world's share of the storage starts with (1 .. 4096); a
  * low value makes the first busy tick outgrow it, which the re-run path then handles. */

@@ -113,6 +113,9 @@ assert SWEEP_HIT_DTYPE.itemsize == 52
 # mgf_body_contacts
 BODY_CONTACTS_DTYPE = np.dtype([("n_contacts", "<i4"), ("n_terrain", "<i4"), ("impulse", "<f4", 3), ("normal_impulse", "<f4")])
 assert BODY_CONTACTS_DTYPE.itemsize == 24
+# what WorldBatch.get returns per record: mgf_velocity, mgf_rigid_body_info, and the force and torque rows
+BODY_GET_DTYPE = np.dtype([("linear", "<f4", 3), ("angular", "<f4", 3), ("x", "<f4", 3), ("restitution", "<f4"), ("friction", "<f4"),
+                           ("inv_mass", "<f4"), ("inv_moment", "<f4", 9), ("force", "<f4", 3), ("torque", "<f4", 3)])
 HIT_NONE, HIT_BODY, HIT_TERRAIN, HIT_OBSTACLE = -1, 0, 1, 2
 BATCH_MAX_BODIES = 1024  # MGF_BATCH_MAX_BODIES
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
@@ -150,6 +153,7 @@ SYMBOLS = [
     "mgf_batch_read_state", "mgf_batch_write_state", "mgf_batch_read_constraints", "mgf_batch_counter", "mgf_batch_set_option",
     "mgf_batch_read_colliders", "mgf_batch_raycast_many", "mgf_batch_sweep_many",
     "mgf_batch_read_body_contacts", "mgf_batch_overlap_aabb_many",
+    "mgf_batch_get_many", "mgf_batch_set_many", "mgf_batch_set_forces", "mgf_batch_apply_impulses", "mgf_batch_copy_worlds",
 ]
 
 _lib = None
@@ -301,6 +305,11 @@ def load_library():
         "mgf_batch_sweep_many": (i32, [vp, vp, vp, i64, vp, i32, vp]),
         "mgf_batch_read_body_contacts": (i32, [vp, i64, vp, i64]),
         "mgf_batch_overlap_aabb_many": (i32, [vp, vp, vp, i64, vp, vp, i64, P(i64)]),
+        "mgf_batch_get_many": (i32, [vp, vp, vp, i64, vp, vp, vp, vp]),
+        "mgf_batch_set_many": (i32, [vp, vp, vp, i64, vp]),
+        "mgf_batch_set_forces": (i32, [vp, vp, vp, i64, vp, vp]),
+        "mgf_batch_apply_impulses": (i32, [vp, vp, vp, i64, vp, vp]),
+        "mgf_batch_copy_worlds": (i32, [vp, vp, vp, vp, i64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1380,6 +1389,61 @@ class WorldBatch:
         wd = _per_query(world, len(boxes))
         fn = load_library().mgf_batch_overlap_aabb_many
         return _overlap_lists(lambda *o: fn(self._h, wd.ctypes.data, boxes.ctypes.data, len(boxes), *o), len(boxes), cap)
+
+    def _records(self, world, body):
+        """(world, body) pairs as two contiguous int32 arrays of one length (a scalar world: every body of that world)"""
+        bd = np.ascontiguousarray(np.atleast_1d(body), np.int32).reshape(-1)
+        return _per_query(world, len(bd)), bd
+
+    def get(self, world, body):
+        """ConstrainedSet::get of body[i] of world[i] (mgf_batch_get_many): a BODY_GET_DTYPE array - linear, angular, x (= x + delta),
+        restitution, friction, inv_mass, inv_moment (column-major), and the body's force and torque rows"""
+        wd, bd = self._records(world, body)
+        n = len(bd)
+        vel, info = np.zeros((n, 6), np.float32), np.zeros((n, 15), np.float32)
+        force, torque = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+        _check(load_library().mgf_batch_get_many(self._h, wd.ctypes.data, bd.ctypes.data, n, vel.ctypes.data, info.ctypes.data,
+                                                 force.ctypes.data, torque.ctypes.data))
+        out = np.zeros(n, BODY_GET_DTYPE)
+        out["linear"], out["angular"] = vel[:, 0:3], vel[:, 3:6]
+        out["x"], out["restitution"], out["friction"], out["inv_mass"], out["inv_moment"] = info[:, 0:3], info[:, 3], info[:, 4], info[:, 5], info[:, 6:15]
+        out["force"], out["torque"] = force, torque
+        return out
+
+    def set_velocities(self, world, body, linear, angular):
+        """ConstrainedSet::set of body[i] of world[i] (mgf_batch_set_many), in array order: a body named twice keeps the last"""
+        wd, bd = self._records(world, body)
+        n = len(bd)
+        vel = np.empty((n, 6), np.float32)
+        vel[:, 0:3] = np.broadcast_to(np.asarray(linear, np.float32), (n, 3))
+        vel[:, 3:6] = np.broadcast_to(np.asarray(angular, np.float32), (n, 3))
+        _check(load_library().mgf_batch_set_many(self._h, wd.ctypes.data, bd.ctypes.data, n, vel.ctypes.data))
+
+    def _rows3(self, a, n):
+        return None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), (n, 3)))
+
+    def set_forces(self, world, body, force=None, torque=None):
+        """RigidBodyVec.force / .torque of body[i] of world[i] (mgf_batch_set_forces), for every later tick until set again; None
+        leaves that row as it is.  force is the stored one: world_force * mass."""
+        wd, bd = self._records(world, body)
+        f, t = self._rows3(force, len(bd)), self._rows3(torque, len(bd))
+        _check(load_library().mgf_batch_set_forces(self._h, wd.ctypes.data, bd.ctypes.data, len(bd), _ptr(f), _ptr(t)))
+
+    def apply_impulses(self, world, body, linear=None, angular=None):
+        """v += linear * inv_mass, omega += inv_moment * angular on body[i] of world[i] (mgf_batch_apply_impulses); a body's records
+        are applied in array order; None: zero"""
+        wd, bd = self._records(world, body)
+        a, b = self._rows3(linear, len(bd)), self._rows3(angular, len(bd))
+        _check(load_library().mgf_batch_apply_impulses(self._h, wd.ctypes.data, bd.ctypes.data, len(bd), _ptr(a), _ptr(b)))
+
+    def copy_worlds(self, dst_world, src, src_world):
+        """world dst_world[i] of this batch becomes world src_world[i] of `src` (another batch of the context, or None / self: this
+        one) on the device (mgf_batch_copy_worlds): bodies, colliders, the last tick's constraint list; a scalar src_world fans one
+        world out.  The terrain assignment is not copied."""
+        dw = np.ascontiguousarray(np.atleast_1d(dst_world), np.int32).reshape(-1)
+        sw = _per_query(src_world, len(dw))
+        s = self if src is None else src
+        _check(load_library().mgf_batch_copy_worlds(self._h, dw.ctypes.data, s._h, sw.ctypes.data, len(dw)))
 
     def counter(self, name):
         v = C.c_int64()

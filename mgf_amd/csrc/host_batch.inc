@@ -50,6 +50,7 @@ struct mgf_batch {
   QueryEvents q_tm;  // 0 | a query pass | 1
   int64_t q_launches = 0;
   float q_run_ms = 0.0f;
+  int64_t d_launches = 0;  // kernel launches of the last get / set / forces / impulses / copy call (host_batch_drive.inc)
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {
@@ -214,6 +215,7 @@ extern "C" mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, in
   if (!strcmp(name, "capacity_retries")) { *out = b->capacity_retries; return MGF_OK; }
   if (!strcmp(name, "query_launches")) { *out = b->q_launches; return MGF_OK; }
   if (!strcmp(name, "query_run_ns")) { *out = (int64_t)((double)b->q_run_ms * 1e6); return MGF_OK; }
+  if (!strcmp(name, "drive_launches")) { *out = b->d_launches; return MGF_OK; }
   return fail(MGF_ERR_INVALID, "unknown batch counter");
 }
 

@@ -85,6 +85,11 @@
 //                      what else a caller reads of a batch every tick: the constraint list of every world folded per body
 //                      (mgf_batch_read_body_contacts: a workgroup per world, the per-body ranges rebuilt in LDS, a lane per body walks its
 //                      chain) and the bodies in a box (mgf_batch_overlap_aabb_many: the world's tight boxes in LDS, ballot-rank compaction)
+//   k_batch_drive_get / _set<MODE> / _copy (k_batch_drive.h)
+//                      acting on a batch between ticks: ConstrainedSet::get / set, the force and torque rows and impulses for any mix
+//                      of (world, body) records (mgf_batch_get_many / _set_many / _set_forces / _apply_impulses: a lane per body the call
+//                      names, its records in the caller's order from the host's stable sort) and world-to-world copies
+//                      (mgf_batch_copy_worlds: a workgroup per pair, rows, packed copy, colliders and the constraint list in 16-byte words)
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -102,3 +107,4 @@
 #include "k_batch.h"  // many small worlds, a workgroup each (k_batch_*), beside the one-world tick
 #include "k_batch_query.h"  // the queries of k_query.h for the worlds of a batch (k_batch_query_*)
 #include "k_batch_observe.h"  // per-body contact summaries and box overlaps of a batch (k_batch_observe_*)
+#include "k_batch_drive.h"  // get / set, forces, impulses and world copies of a batch (k_batch_drive_*)
