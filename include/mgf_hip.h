@@ -561,9 +561,10 @@ MGF_API mgf_status mgf_world_release_device_ptrs(mgf_world* w);
  * worlds than the device holds workgroups, and it is safe on a device shared with another process.
  * LIMITS: bodies of one component (spheres and capsules); at most MGF_BATCH_MAX_BODIES bodies per world (a call that would exceed it
  * is refused with MGF_ERR_INVALID and adds nothing); the static geometry of a world is one terrain mesh, or none: an entry of the
- * batch's terrain table (meshes are copied in; any number of worlds may share an entry) at a position of the world's own; canonical
- * constraint order only.  There are no bodies of several components, no obstacles, no ghosts or tiles and no
- * constraint_order = demo: a batch has no entry point for them.  A tick never fails for list sizes: a world whose
+ * batch's terrain table (meshes are copied in; any number of worlds may share an entry) at a position of the world's own, and beside it
+ * up to MGF_BATCH_MAX_WORLD_OBSTACLES static Compound obstacles: entries of the batch's obstacle table, each at a pose of the world's
+ * own ("the obstacle table" below); canonical constraint order only.  There are no bodies of several components, no moving obstacles,
+ * no ghosts or tiles and no constraint_order = demo: a batch has no entry point for them.  A tick never fails for list sizes: a world whose
  * constraints outgrow its share of the storage gets its tick undone on the device and run again with more (Solver::solve and
  * World::step have no capacity failure, solver.rs:72-78); mgf_batch_counter "capacity_retries" counts those re-runs.
  * Calls are synchronous on the context's stream; the handle keeps a reference on the context; there is no CPU fallback. */
@@ -590,6 +591,34 @@ MGF_API mgf_status mgf_batch_set_terrain(mgf_batch* b, const mgf_mesh* mesh);   
 MGF_API mgf_status mgf_batch_add_terrain(mgf_batch* b, const mgf_mesh* mesh, int32_t* id);
 MGF_API mgf_status mgf_batch_set_world_terrain(mgf_batch* b, const int32_t* world, const int32_t* terrain, const mgf_vec3* pos, int64_t n);
 MGF_API int64_t mgf_batch_terrain_count(const mgf_batch* b);
+/* ---- the obstacle table: static Compound obstacles per world.  World k behaves, bit for bit, as a lone mgf_world that holds world k's
+ * bodies, has world k's terrain at world k's mesh position, and has had mgf_world_add_obstacle called once per entry of world k's
+ * obstacle list, in list order, each after mgf_compound_set_pose(disp, rot) with that entry's pose - the tick's state, the constraint
+ * list with its impulses, the statistics (n_terrain_constraints counts obstacle contacts too) and the queries below.  The definition
+ * is the lone world's (the oracle's World::obstacles): behind body i's terrain contacts every obstacle in list order goes through
+ * Compound::contacts(&Moving::sweep(collider_i, delta_i)) (compound.rs:334-352), every contact a constraint of its own against
+ * Static{ center: the entry's disp, friction: 0 }; the partners j < i follow.  What a world computes depends neither on the order of
+ * the table, nor on which other worlds use the same entry, nor on where in the batch the world sits.
+ * mgf_batch_add_obstacle copies the compound (components, tree and current pose) behind the table's last entry and returns its id: 0,
+ * 1, ...; no world changes.  An empty compound is a valid entry that meets nothing but keeps its place in a world's list (a hit's
+ * `index` still counts it; mgf_world_add_obstacle accepts one too).  A compound of 2^18 components or more: MGF_ERR_CAPACITY, as
+ * mgf_world_add_obstacle.
+ * mgf_batch_set_world_obstacles: every world some record names gets its list replaced by its records, in array order; a world no
+ * record names is untouched.  A record with obstacle[i] = -1 contributes nothing: a world named only by such records ends with an
+ * empty list.  disp and rot are per record; NULL (each on its own) means the pose the compound had when it was added; rot is taken
+ * as normalised, as by mgf_compound_set_pose.  It may be called between any two mgf_batch_step calls and holds from the next tick; it
+ * moves no body, no fat box, no collider and no constraint list.
+ * mgf_batch_obstacle_count: the table's length, -1 for NULL.  mgf_batch_world_obstacle_count: the length of a world's list, -1 for a
+ * NULL batch or a world index outside [0, n_worlds).
+ * Refused with MGF_ERR_INVALID, nothing changed at all: a NULL batch, a NULL compound or id, NULL world or obstacle with n > 0, a
+ * negative n, a world index outside [0, n_worlds), an id below -1 or >= the table's length, a world that would get more than
+ * MGF_BATCH_MAX_WORLD_OBSTACLES entries.  The number of launches of a tick does not depend on the table or the lists. */
+#define MGF_BATCH_MAX_WORLD_OBSTACLES 64
+MGF_API mgf_status mgf_batch_add_obstacle(mgf_batch* b, const mgf_compound* c, int32_t* id);
+MGF_API mgf_status mgf_batch_set_world_obstacles(mgf_batch* b, const int32_t* world, const int32_t* obstacle, const mgf_vec3* disp,
+                                                 const mgf_quat* rot, int64_t n);
+MGF_API int64_t mgf_batch_obstacle_count(const mgf_batch* b);                       /* the table's length; -1 for NULL */
+MGF_API int64_t mgf_batch_world_obstacle_count(const mgf_batch* b, int64_t world);  /* a world's list; -1 for a bad argument */
 /* World::add_body / RigidBodyVec::add_body (physics.rs:200-218, world.rs:178-184) in bulk, for world `world`; *first_id = the index of the
  * first new body within that world.  A tag other than 0 or 1, a negative n, a world index out of range: MGF_ERR_INVALID. */
 MGF_API mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mgf_component* comps, int64_t n, const float* mass,
@@ -609,18 +638,21 @@ MGF_API mgf_status mgf_batch_write_state(mgf_batch* b, int64_t world, const mgf_
 MGF_API mgf_status mgf_batch_read_constraints(mgf_batch* b, int64_t world, mgf_constraint* out, int64_t cap, int64_t* count);
 /* ---- queries against the worlds of a batch, between ticks.  The definition is the lone world's ("queries against the world between
  * ticks", above): out[i] is, bit for bit, what mgf_world_raycast_many / mgf_world_sweep_many reports for query i on a lone mgf_world
- * that holds world world[i]'s bodies and that world's terrain at that world's mesh position (the terrain table, above) and has been
- * through the same calls.
+ * that holds world world[i]'s bodies, that world's terrain at that world's mesh position (the terrain table, above) and that world's
+ * obstacles at their poses (the obstacle table, above), and has been through the same calls.
  *   Ray cast: the closest hit of Intersects<shape> (collision.rs:169-373; compound.rs:150 for a component), the smallest t, ties to the
- *   target first in the order bodies (ascending index), terrain faces (ascending index); a particle with d = 0 hits nothing.
+ *   target first in the order bodies (ascending index), terrain faces (ascending index), obstacles (Intersects<Compound>,
+ *   compound.rs:309-332; ascending place in the world's list); a particle with d = 0 hits nothing.
  *   Sweep: the earliest contact of Contacts<Moving<Sphere | Capsule>> of a body's sphere or capsule (collision.rs:1089-1356; :1143
  *   through commute_contacts!) and of Contacts<Moving<_>> for Poly of each face (collision.rs:610-1000, up to two contacts for a
- *   capsule), the least (t, kind, index, part, order emitted within the target); a contact whose t is not finite is not a candidate
+ *   capsule) and of Compound::contacts of the cast for each obstacle (compound.rs:334-352), the least (t, kind, index, part, order
+ *   emitted within the target); a contact whose t is not finite is not a candidate
  *   (collision.rs:693-1086); a capsule cast with delta = 0 tests every face (:901-1060), a capsule reaches max(1, |d|) (:698-719);
  *   delta = 0 is a valid cast (sphere on sphere with equal centres reports nothing, :1097-1100).
- * index is the body's index within its world, or the face index; part is 0.  ignore_body: NULL, or n indices within world world[i]
- * (-1: none).  kinds_mask: MGF_QUERY_* bits; 0 or a bit beyond MGF_QUERY_ALL is refused; MGF_QUERY_OBSTACLES is accepted and matches
- * nothing (a batch has no obstacles), so MGF_QUERY_ALL means what it means for a lone world without obstacles.
+ * index is the body's index within its world, the face index, or (kind = MGF_HIT_OBSTACLE) the obstacle's place in the world's list;
+ * part is 0, or the component of the obstacle.  ignore_body: NULL, or n indices within world world[i] (-1: none).  kinds_mask:
+ * MGF_QUERY_* bits; 0 or a bit beyond MGF_QUERY_ALL is refused; MGF_QUERY_OBSTACLES matches the world's obstacles exactly as on the
+ * lone world (one more launch, and only where the mask has the bit and some world of the batch has an obstacle).
  * The collider a query sees is the one the world's query would see: the one the last tick built (physics.rs:243-251); for a body no
  * tick has touched, the component it was added as; mgf_batch_write_state does not move it, as mgf_world_write_state does not.
  * mgf_batch_read_colliders returns exactly that collider with the body's current delta (colliders() physics.rs:256).
@@ -647,10 +679,11 @@ MGF_API mgf_status mgf_batch_sweep_many(mgf_batch* b, const int32_t* world, cons
  * normal.z * ni), ni = the record's normal_impulse, in f32:  x is `a`: impulse = impulse - t (va -= impulse * inv_mass_a,
  * solver.rs:243-247); x is `b`: impulse = impulse + t; in both roles normal_impulse = normal_impulse + ni.  Sequential f32
  * operations in that order, no fused multiply-add: the answer is defined to the bit, and a body in no record gets an all-zero record.
- * Tangent impulses are not part of it: mgf_constraint does not carry them. */
+ * Tangent impulses are not part of it: mgf_constraint does not carry them.  A record against an obstacle of the world counts in
+ * n_terrain like every other record with b = -1. */
 typedef struct mgf_body_contacts {
   int32_t n_contacts;     /* records of the list that name the body, as a or as b */
-  int32_t n_terrain;      /* of those, records against RigidBodyRef::Static (b = -1; the body is a) */
+  int32_t n_terrain;      /* of those, records against RigidBodyRef::Static (b = -1; the body is a): terrain and obstacle contacts alike */
   mgf_vec3 impulse;       /* net accumulated normal impulse on the body, see above */
   float normal_impulse;   /* sum of the records' normal_impulse */
 } mgf_body_contacts;      /* 24 bytes */
@@ -710,7 +743,8 @@ MGF_API mgf_status mgf_batch_apply_impulses(mgf_batch* b, const int32_t* world, 
  * fat box, the collider a query sees), the tick's packed copy, and the last tick's constraint list with its impulses and its length -
  * mgf_batch_read_constraints, _read_body_contacts, _read_colliders, the ray casts, sweeps and box overlaps answer for the destination
  * what they answer for the source, and with the same terrain the destination steps bit-identically to the source.
- * Not copied: the terrain assignment (the environment is the destination's: mgf_batch_set_world_terrain copies it), the shares of the
+ * Not copied: the terrain assignment and the obstacle list (the environment is the destination's: mgf_batch_set_world_terrain and
+ * mgf_batch_set_world_obstacles copy them; with the same terrain and the same list the destination steps like the source), the shares of the
  * storage (a destination whose share is smaller than the source's list gets a larger one first, and keeps it - as a world keeps
  * what a tick that did not fit asked for - until "cons_per_body" is set again), counters and options.
  * A source may be named any number of times (fan-out).  Refused with MGF_ERR_INVALID, nothing copied, before any launch: a NULL batch,
@@ -718,7 +752,7 @@ MGF_API mgf_status mgf_batch_apply_impulses(mgf_batch* b, const int32_t* world, 
  * its source of different lengths, a destination named twice, and - where dst == src - a world that is both a source and a
  * destination.  One workgroup per pair, one launch (and one more when shares grow): "drive_launches" of dst. */
 MGF_API mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_world, const mgf_batch* src, const int32_t* src_world, int64_t n);
-/* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: it does not grow with n_worlds), "capacity_retries",
+/* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /
  * _set_forces / _apply_impulses / _copy_worlds call on this batch - for a copy, on its destination: it depends on neither n_worlds nor n)}. */

@@ -118,6 +118,7 @@ BODY_GET_DTYPE = np.dtype([("linear", "<f4", 3), ("angular", "<f4", 3), ("x", "<
                            ("inv_mass", "<f4"), ("inv_moment", "<f4", 9), ("force", "<f4", 3), ("torque", "<f4", 3)])
 HIT_NONE, HIT_BODY, HIT_TERRAIN, HIT_OBSTACLE = -1, 0, 1, 2
 BATCH_MAX_BODIES = 1024  # MGF_BATCH_MAX_BODIES
+BATCH_MAX_WORLD_OBSTACLES = 64  # MGF_BATCH_MAX_WORLD_OBSTACLES
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -154,6 +155,7 @@ SYMBOLS = [
     "mgf_batch_read_colliders", "mgf_batch_raycast_many", "mgf_batch_sweep_many",
     "mgf_batch_read_body_contacts", "mgf_batch_overlap_aabb_many",
     "mgf_batch_get_many", "mgf_batch_set_many", "mgf_batch_set_forces", "mgf_batch_apply_impulses", "mgf_batch_copy_worlds",
+    "mgf_batch_add_obstacle", "mgf_batch_set_world_obstacles", "mgf_batch_obstacle_count", "mgf_batch_world_obstacle_count",
 ]
 
 _lib = None
@@ -310,6 +312,10 @@ def load_library():
         "mgf_batch_set_forces": (i32, [vp, vp, vp, i64, vp, vp]),
         "mgf_batch_apply_impulses": (i32, [vp, vp, vp, i64, vp, vp]),
         "mgf_batch_copy_worlds": (i32, [vp, vp, vp, vp, i64]),
+        "mgf_batch_add_obstacle": (i32, [vp, vp, P(i32)]),
+        "mgf_batch_set_world_obstacles": (i32, [vp, vp, vp, vp, vp, i64]),
+        "mgf_batch_obstacle_count": (i64, [vp]),
+        "mgf_batch_world_obstacle_count": (i64, [vp, i64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1223,7 +1229,8 @@ def terrain_table(terrains):
 class WorldBatch:
     """Many small independent worlds resident on one GPU, stepped together (mgf_batch_*): per world `step` is
     mgf_demo/world.rs::World::step, one workgroup a world.  At most BATCH_MAX_BODIES single-component bodies per world; a world's
-    terrain is an entry of the batch's terrain table (shared by any number of worlds) at a position of its own, or none."""
+    terrain is an entry of the batch's terrain table (shared by any number of worlds) at a position of its own, or none; its static
+    Compound obstacles are a list of entries of the batch's obstacle table, each at a pose of the world's own."""
 
     def __init__(self, ctx, n_worlds, params=None):
         self._ctx = ctx
@@ -1241,7 +1248,9 @@ class WorldBatch:
     @classmethod
     def from_scenes(cls, ctx, scenes, params=None, own_terrain=False):
         """scenes as mgf_amd.scenes makes them, one per world; the first scene's terrain serves all, or (own_terrain) every world gets
-        its scene's: scenes whose terrains have the same vertices and faces share a table entry, each at its own `pos`"""
+        its scene's: scenes whose terrains have the same vertices and faces share a table entry, each at its own `pos`.  A scene may
+        carry "obstacles": a list of (comps, disp, rot) - static Compounds of COMPONENT_DTYPE rows at a pose (rot = (s, x, y, z)), in
+        the order the tick meets them; compounds with the same components, bit for bit, share an entry of the obstacle table"""
         b = cls(ctx, len(scenes), params)
         if own_terrain:
             entry, pos = terrain_table([sc["terrain"] for sc in scenes])
@@ -1259,6 +1268,16 @@ class WorldBatch:
                 m.build(t["verts"], t["faces"])
                 m.set_pos(t["pos"])
                 b.set_terrain(m)
+        ids, rec = {}, []
+        for k, sc in enumerate(scenes):
+            for comps, disp, rot in (sc.get("obstacles") or ()):
+                comps = np.ascontiguousarray(comps, COMPONENT_DTYPE)
+                key = (len(comps), comps.tobytes())
+                if key not in ids:
+                    ids[key] = b.add_obstacle(Compound(ctx, comps))
+                rec.append((k, ids[key], tuple(float(c) for c in disp), tuple(float(c) for c in rot)))
+        if rec:
+            b.set_world_obstacles([r[0] for r in rec], [r[1] for r in rec], [r[2] for r in rec], [r[3] for r in rec])
         for k, sc in enumerate(scenes):
             if sc.get("compound") is not None:
                 raise MgfError(ERR_INVALID, "a batch world holds bodies of one component")
@@ -1289,6 +1308,31 @@ class WorldBatch:
 
     def terrain_count(self):
         return load_library().mgf_batch_terrain_count(self._h)
+
+    def add_obstacle(self, compound):
+        """a copy of the Compound (components, tree and current pose) as a new entry of the obstacle table; returns its id.  No world
+        changes."""
+        i = C.c_int32(-1)
+        _check(load_library().mgf_batch_add_obstacle(self._h, compound._h if compound is not None else None, C.byref(i)))
+        return i.value
+
+    def set_world_obstacles(self, world, obstacle, disp=None, rot=None):
+        """every world some record names gets its list of obstacles replaced by its records, in array order, from the next tick:
+        record i puts table entry obstacle[i] (-1: nothing - a world named only so ends with an empty list) at disp[i], rot[i] =
+        (s, x, y, z) taken as normalised (None, each on its own: the pose the compound had when it was added) into world[i]'s list.
+        Scalars or arrays (a scalar world or obstacle, one disp, one rot: for every record)"""
+        n = max(np.size(world), np.size(obstacle))
+        wd = np.ascontiguousarray(np.broadcast_to(np.asarray(world, np.int32), (n,)))
+        ob = np.ascontiguousarray(np.broadcast_to(np.asarray(obstacle, np.int32), (n,)))
+        dp = None if disp is None else np.ascontiguousarray(np.broadcast_to(np.asarray(disp, np.float32), (n, 3)))
+        rt = None if rot is None else np.ascontiguousarray(np.broadcast_to(np.asarray(rot, np.float32), (n, 4)))
+        _check(load_library().mgf_batch_set_world_obstacles(self._h, wd.ctypes.data, ob.ctypes.data, _ptr(dp), _ptr(rt), n))
+
+    def obstacle_count(self):
+        return load_library().mgf_batch_obstacle_count(self._h)
+
+    def world_obstacle_count(self, world):
+        return load_library().mgf_batch_world_obstacle_count(self._h, int(world))
 
     def add_bodies(self, world, comps, mass, restitution, friction, world_force):
         comps = np.ascontiguousarray(comps, dtype=COMPONENT_DTYPE)

@@ -8,6 +8,9 @@
 // The terrain is a table of meshes, copied one behind the other into one store each of nodes, vertices and faces as they are added, and
 // per world an entry of the table (or none) and a mesh position; the kernels read a descriptor per world (BatchTerrains, k_batch.h), which
 // goes up before the first tick or query behind a change.
+// The obstacles are a table of static Compounds in the same way - every entry's threaded tree and components behind the last entry's in
+// one store each - and per world a list of (entry, disp, rot); the kernels read a descriptor per list entry (BatchObstacles, k_batch.h).
+// Both tables and all lists live beside the mirror: adding bodies behind a tick, or none yet, leaves them as they are.
 
 struct mgf_batch {
   mgf_ctx* ctx = nullptr;
@@ -30,6 +33,18 @@ struct mgf_batch {
   std::vector<V3> h_wx;
   bool t_desc_stale = true;   // the descriptors on the device are behind the table or the assignments
   uint32_t t_worlds = 0;      // worlds whose terrain has a node, as of the descriptors on the device
+  // the obstacle table and every world's list of it: (entry, pose) in the order the tick meets them
+  struct ObstacleEntry { uint32_t node0, n_nodes, comp0; V3 disp; Quat rot; };
+  struct ObstacleRef { uint32_t entry; V3 disp; Quat rot; };
+  std::vector<ObstacleEntry> o_table;
+  DBuf<float4> o_nodes;
+  DBuf<CompIn> o_comps;
+  DBuf<uint4> o_desc;
+  std::vector<uint32_t> h_orange;       // per world first << 7 | count of its descriptors, as of the descriptors on the device
+  size_t o_n_nodes = 0, o_n_comps = 0;  // the stores' lengths (nodes: two words each)
+  std::vector<std::vector<ObstacleRef>> h_wo;
+  bool o_desc_stale = true;   // the descriptors on the device are behind the lists (or the stores have moved)
+  uint32_t o_worlds = 0;      // worlds whose list has an entry, as of the descriptors on the device
   // constraint storage
   std::vector<uint32_t> h_coff, h_cap, h_floor, h_qfloor, h_ccount;  // offsets / shares of the lists / the least a world has asked for (records, candidates) / length of the last tick's list
   bool lists_valid = false;
@@ -177,6 +192,7 @@ extern "C" mgf_status mgf_batch_new(mgf_ctx* ctx, const mgf_params* params, int6
   b->params = params ? *params : mgf_default_params();
   b->K = (uint32_t)n_worlds;
   b->h_wt.assign(b->K, -1); b->h_wx.assign(b->K, mk3(0, 0, 0));
+  b->h_wo.assign(b->K, {}); b->h_orange.assign(b->K, 0u);
   b->h_n.assign(b->K, 0u); b->h_floor.assign(b->K, 0u); b->h_qfloor.assign(b->K, 0u); b->h_ccount.assign(b->K, 0u);
   batch_offsets(b.get());
   ctx_retain(ctx);
@@ -256,17 +272,23 @@ static mgf_status batch_table_add(mgf_batch* b, const mgf_mesh* mesh) {
 static mgf_status batch_terrain_sync(mgf_batch* b) {
   if (!b->t_desc_stale) return MGF_OK;
   hipStream_t s = b->ctx->stream;
-  std::vector<uint4> d(2 * (size_t)b->K, make_uint4(0u, 0u, 0u, 0u));
+  std::vector<uint4> d(2 * (size_t)b->K + 2, make_uint4(0u, 0u, 0u, 0u));
   uint32_t with = 0;
   for (uint32_t k = 0; k < b->K; ++k) {
+    d[2 * (size_t)k + 1].w = b->h_orange[k];  // the world's obstacles (batch_obstacle_sync)
     if (b->h_wt[k] < 0) continue;
     const mgf_batch::TerrainEntry& e = b->t_table[(size_t)b->h_wt[k]];
     const V3 x = b->h_wx[k];
     uint32_t xb[3];
     memcpy(&xb[0], &x.x, 4); memcpy(&xb[1], &x.y, 4); memcpy(&xb[2], &x.z, 4);
     d[2 * (size_t)k] = make_uint4(e.node0, e.vert0, e.face0, e.n_nodes);
-    d[2 * (size_t)k + 1] = make_uint4(xb[0], xb[1], xb[2], 0u);
+    d[2 * (size_t)k + 1] = make_uint4(xb[0], xb[1], xb[2], b->h_orange[k]);
     if (e.n_nodes) ++with;
+  }
+  {  // behind the worlds' descriptors: where the obstacle stores are (batch_obstacles_of, k_batch.h)
+    const uint64_t pn = reinterpret_cast<uint64_t>(b->o_nodes.p), pc = reinterpret_cast<uint64_t>(b->o_comps.p), pd = reinterpret_cast<uint64_t>(b->o_desc.p);
+    d[2 * (size_t)b->K] = make_uint4((uint32_t)pn, (uint32_t)(pn >> 32), (uint32_t)pc, (uint32_t)(pc >> 32));
+    d[2 * (size_t)b->K + 1] = make_uint4((uint32_t)pd, (uint32_t)(pd >> 32), 0u, 0u);
   }
   MGF_TRY(b->t_desc.ensure(d.size(), s));
   MGF_TRY(b->t_nodes.ensure(1, s)); MGF_TRY(b->t_verts.ensure(1, s)); MGF_TRY(b->t_faces.ensure(1, s));
@@ -325,6 +347,113 @@ extern "C" mgf_status mgf_batch_set_world_terrain(mgf_batch* b, const int32_t* w
   return MGF_OK;
 }
 extern "C" int64_t mgf_batch_terrain_count(const mgf_batch* b) { return b ? (int64_t)b->t_table.size() : -1; }
+
+static BatchObstacles batch_obstacles(const mgf_batch* b) {
+  BatchObstacles O;
+  O.nodes = b->o_nodes.p; O.comps = b->o_comps.p; O.desc = b->o_desc.p;
+  return O;
+}
+// every list entry's descriptor onto the device, before the first launch behind a change of a list (batch_terrain_sync's counterpart).
+// Every index a kernel takes from a descriptor is in range here: an entry's nodes and components lie within the stores, a skip index
+// and a leaf's component within the entry (batch_thread_tree over the compound's own tree).
+static mgf_status batch_obstacle_sync(mgf_batch* b) {
+  if (!b->o_desc_stale) return MGF_OK;
+  hipStream_t s = b->ctx->stream;
+  std::vector<uint4> d;
+  uint32_t with = 0;
+  size_t total = 0;
+  for (uint32_t k = 0; k < b->K; ++k) total += b->h_wo[k].size();
+  if (total >= (1ull << (32 - kBatchObstCountBits))) return fail(MGF_ERR_OOM, "the batch's obstacle lists exceed 2^25 entries");
+  for (uint32_t k = 0; k < b->K; ++k) {
+    for (const mgf_batch::ObstacleRef& r : b->h_wo[k]) {
+      const mgf_batch::ObstacleEntry& e = b->o_table[r.entry];
+      uint32_t w[7];
+      const float f[7] = {r.disp.x, r.disp.y, r.disp.z, r.rot.s, r.rot.v.x, r.rot.v.y, r.rot.v.z};
+      memcpy(w, f, sizeof(w));
+      d.push_back(make_uint4(e.node0, e.n_nodes, e.comp0, 0u));
+      d.push_back(make_uint4(w[0], w[1], w[2], w[3]));
+      d.push_back(make_uint4(w[4], w[5], w[6], 0u));
+    }
+    const uint32_t cnt = (uint32_t)b->h_wo[k].size();
+    b->h_orange[k] = cnt ? ((uint32_t)(d.size() / 3 - cnt) << kBatchObstCountBits) | cnt : 0u;
+    if (cnt) ++with;
+  }
+  MGF_TRY(b->o_desc.ensure(std::max<size_t>(d.size(), 1), s));
+  MGF_TRY(b->o_nodes.ensure(1, s)); MGF_TRY(b->o_comps.ensure(1, s));
+  MGF_TRY(h2d(b->ctx, b->o_desc.p, d.data(), d.size()));
+  b->o_worlds = with;
+  b->o_desc_stale = false;
+  b->t_desc_stale = true;  // (the worlds' ranges and the stores' addresses travel with the terrain descriptors)
+  return MGF_OK;
+}
+// a world's environment - its obstacle list, then its terrain descriptor, which names the list - before the first launch behind a change
+static mgf_status batch_env_sync(mgf_batch* b) {
+  MGF_TRY(batch_obstacle_sync(b));
+  return batch_terrain_sync(b);
+}
+// A copy of the compound - components, tree and current pose - behind the obstacle table's last entry; no world changes.  An empty
+// compound is an entry that meets nothing and keeps its place in a world's list.
+extern "C" mgf_status mgf_batch_add_obstacle(mgf_batch* b, const mgf_compound* c, int32_t* id) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (!c || !id) return fail(MGF_ERR_INVALID, "NULL argument");
+  if (c->comps.size() >= kObstacleCompMax) return fail(MGF_ERR_CAPACITY, "an obstacle holds at most 2^18 components");
+  MGF_TRY(ctx_bind(b->ctx));
+  if (b->o_table.size() >= 0x7FFFFFFFull) return fail(MGF_ERR_OOM, "the batch's obstacle table is full");
+  std::vector<float4> nodes;
+  if (!c->m.tree.empty()) batch_thread_tree(c->m.tree, c->m.tree.root(), &nodes);
+  std::vector<CompIn> hc(c->comps.size());
+  static_assert(sizeof(CompIn) == sizeof(mgf_component), "a compound's components go up as they are");
+  if (!hc.empty()) memcpy(hc.data(), c->comps.data(), hc.size() * sizeof(CompIn));
+  if (b->o_n_nodes + nodes.size() / 2 > 0x7FFFFFF0ull || b->o_n_comps + hc.size() > 0x7FFFFFF0ull)
+    return fail(MGF_ERR_OOM, "the batch's obstacle table exceeds 2^31 nodes or components");
+  MGF_TRY(append(b->ctx, b->o_nodes, 2 * b->o_n_nodes, nodes));
+  MGF_TRY(append(b->ctx, b->o_comps, b->o_n_comps, hc));
+  mgf_batch::ObstacleEntry e;
+  e.node0 = (uint32_t)b->o_n_nodes; e.n_nodes = (uint32_t)(nodes.size() / 2); e.comp0 = (uint32_t)b->o_n_comps;
+  e.disp = c->disp; e.rot = c->rot;
+  b->o_table.push_back(e);
+  b->o_n_nodes += nodes.size() / 2; b->o_n_comps += hc.size();
+  b->o_desc_stale = true;  // (a store that grew may have moved)
+  *id = (int32_t)(b->o_table.size() - 1);
+  return MGF_OK;
+}
+// Every world some record names gets its list replaced by its records, in array order (-1: a record that contributes nothing).
+extern "C" mgf_status mgf_batch_set_world_obstacles(mgf_batch* b, const int32_t* world, const int32_t* obstacle, const mgf_vec3* disp, const mgf_quat* rot,
+                                                    int64_t n) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (n < 0) return fail(MGF_ERR_INVALID, "n is negative");
+  if (n && (!world || !obstacle)) return fail(MGF_ERR_INVALID, "NULL argument");
+  for (int64_t i = 0; i < n; ++i) {
+    if (world[i] < 0) return fail(MGF_ERR_INVALID, "world index out of range");
+    if (obstacle[i] < -1) return fail(MGF_ERR_INVALID, "obstacle id out of range");
+  }
+  MGF_TRY(ctx_bind(b->ctx));
+  std::vector<uint32_t> cnt(b->K, 0u);
+  for (int64_t i = 0; i < n; ++i) {
+    if ((uint32_t)world[i] >= b->K) return fail(MGF_ERR_INVALID, "world index out of range");
+    if (obstacle[i] < 0) continue;
+    if ((size_t)obstacle[i] >= b->o_table.size()) return fail(MGF_ERR_INVALID, "obstacle id out of range");
+    if (++cnt[(size_t)world[i]] > MGF_BATCH_MAX_WORLD_OBSTACLES)
+      return fail(MGF_ERR_INVALID, "a world of a batch has at most MGF_BATCH_MAX_WORLD_OBSTACLES (64) obstacles: nothing was changed");
+  }
+  for (int64_t i = 0; i < n; ++i) b->h_wo[(size_t)world[i]].clear();
+  for (int64_t i = 0; i < n; ++i) {
+    if (obstacle[i] < 0) continue;
+    const mgf_batch::ObstacleEntry& e = b->o_table[(size_t)obstacle[i]];
+    mgf_batch::ObstacleRef r;
+    r.entry = (uint32_t)obstacle[i];
+    r.disp = disp ? mk3(disp[i].x, disp[i].y, disp[i].z) : e.disp;
+    r.rot = rot ? mkq(rot[i].s, mk3(rot[i].x, rot[i].y, rot[i].z)) : e.rot;
+    b->h_wo[(size_t)world[i]].push_back(r);
+  }
+  if (n) b->o_desc_stale = true;
+  return MGF_OK;
+}
+extern "C" int64_t mgf_batch_obstacle_count(const mgf_batch* b) { return b ? (int64_t)b->o_table.size() : -1; }
+extern "C" int64_t mgf_batch_world_obstacle_count(const mgf_batch* b, int64_t world) {
+  if (!b || world < 0 || world >= (int64_t)b->K) return -1;
+  return (int64_t)b->h_wo[(size_t)world].size();
+}
 
 // RigidBodyVec::add_body physics.rs:200-218 + World::add_body world.rs:178-184 (initial fat AABB), as mgf_world_add_bodies, for one world of the batch.
 extern "C" mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mgf_component* comps, int64_t n, const float* mass, const float* restitution,
@@ -462,7 +591,7 @@ extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int6
   if (n_ticks > (1 << 20)) return fail(MGF_ERR_INVALID, "n_ticks must be at most 2^20");
   MGF_TRY(ctx_bind(b->ctx));
   MGF_TRY(batch_push(b));
-  MGF_TRY(batch_terrain_sync(b));
+  MGF_TRY(batch_env_sync(b));
   if (n_ticks == 0) return MGF_OK;
   mgf_ctx* ctx = b->ctx;
   hipStream_t s = ctx->stream;

@@ -2,7 +2,7 @@
 // (k_batch_query.h).  Part of the single translation unit mgf_hip.hip (included there, in order); not compiled on its own.
 //
 // A call sorts its query indices by world (one stable counting sort), cuts every world's run into work items of up to 256 queries,
-// uploads items, queries, order, ignore list and (for the sweeps' face pass, a lane per cast) the worlds in ONE copy, launches a workgroup per work item - the number of launches depends on
+// uploads items, queries, order, ignore list and (for the sweeps' face pass and the obstacle pass, a lane per query) the worlds in ONE copy, launches a workgroup per work item - the number of launches depends on
 // neither the number of worlds nor the number of queries - and downloads the hits: one host wait per call.  Nothing of the tick's state
 // is written; of it only bpk is read, once, by the collider gather behind a mgf_batch_step (batch_cols_refresh).
 // batch_query_args / _worlds / _open / _upload are every front end's steps ahead of its launches, the box query's
@@ -123,9 +123,10 @@ static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* q
   BatchQueryArgs A;
   memset(&A, 0, sizeof(A));
   BatchQueryUpload U;
-  MGF_TRY(batch_terrain_sync(b));
+  MGF_TRY(batch_env_sync(b));
   const bool faces = !kRays && (kinds_mask & MGF_QUERY_TERRAIN) && b->t_worlds;  // a world of the batch has a terrain to sweep against
-  MGF_TRY(batch_query_upload(b, world, queries, sizeof(Q), n, ignore_body, &A, &U, faces));
+  const bool obstacles = (kinds_mask & MGF_QUERY_OBSTACLES) && b->o_worlds;      // ... an obstacle to meet: a pass of its own, a lane per query
+  MGF_TRY(batch_query_upload(b, world, queries, sizeof(Q), n, ignore_body, &A, &U, faces || obstacles));
   MGF_TRY(b->q_out.ensure(kOut * n, s));
   const uint32_t lds = U.lds + 16u * kBatchQueryRed;  // (at most 32 KB + 256 bytes: two workgroups a CU at the largest world)
   A.T = batch_terrains(b);
@@ -147,6 +148,13 @@ static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* q
       LAUNCH_CHECK();
       ++b->q_launches;
     }
+  }
+  if (obstacles) {
+    const unsigned nb = (unsigned)((n + kBatchBlock - 1) / kBatchBlock);
+    if constexpr (kRays) k_batch_query_ray_obstacles<<<nb, kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, U.world, dq, (uint32_t)n, A.out);
+    else k_batch_query_sweep_obstacles<<<nb, kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, U.world, dq, (uint32_t)n, A.out);
+    LAUNCH_CHECK();
+    ++b->q_launches;
   }
   MGF_TRY(b->q_tm.mark(1, s));
   MGF_HIP_TRY(hipMemcpyAsync(out, b->q_out.p, 4 * kOut * n, hipMemcpyDeviceToHost, s));

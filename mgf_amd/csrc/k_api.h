@@ -234,14 +234,25 @@ __device__ __forceinline__ bool comp_mcomp(const Comp& self, const Comp& m, V3 v
 // Compound::contacts(&Moving::sweep(R, vel)) compound.rs:334-352: its BVH queried with R's swept bounds turned into the compound's
 // frame, then per component met Moving<R>.contacts(&component) (:1368-1382: the component sweeps at -vel against R, the result shifted
 // by vel * t), negated - a on the compound.  emit(component, contact) in the reference's order (k_compound_contacts, k_query_sweep).
+// Written once over either form of a compound, C: CompoundDev - compound_box_walk is the explicit stack over its TerrainDev - or an
+// entry of a batch's obstacle table (BatchObstacle, k_batch.h: the threaded tree); both bring disp, rot and comps.
 template <class F>
-__device__ __forceinline__ void compound_contacts_walk(const CompoundDev& D, const Comp& R, V3 vel, F&& emit) {
+__device__ __forceinline__ void compound_box_walk(const CompoundDev& D, const Box& q, F&& emit) { terrain_traverse(D.tree, q, emit); }
+// the swept bounds of R turned into the compound's frame (compound.rs:340-344)
+template <class C>
+__device__ __forceinline__ Box compound_query_box(const C& D, const Comp& R, V3 vel) {
   const V3 disp = ld3(D.disp);
-  const Quat rot = mkq(D.rot[0], mk3(D.rot[1], D.rot[2], D.rot[3]));
-  const Quat conj = mkq(rot.s, -rot.v);
+  const Quat conj = mkq(D.rot[0], -mk3(D.rot[1], D.rot[2], D.rot[3]));
   Box rb = box_rotate(swept_bounds(R, vel), conj);
   rb.c = rotate(conj, rb.c + -disp) + disp;
-  terrain_traverse(D.tree, rb, [&](uint32_t ci) {
+  return rb;
+}
+template <class C, class F>
+__device__ __forceinline__ void compound_contacts_walk(const C& D, const Comp& R, V3 vel, F&& emit) {
+  const V3 disp = ld3(D.disp);
+  const Quat rot = mkq(D.rot[0], mk3(D.rot[1], D.rot[2], D.rot[3]));
+  const Box rb = compound_query_box(D, R, vel);
+  compound_box_walk(D, rb, [&](uint32_t ci) {
     Comp shape = comp_rotate_about(to_comp(D.comps[ci]), rot, mk3(0.0f, 0.0f, 0.0f));
     shape.p = shape.p + disp;
     Contact c;

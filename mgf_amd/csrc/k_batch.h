@@ -5,12 +5,14 @@
 // A tick is six launches, each a workgroup per world, whatever the number of worlds:
 //   k_batch_front   complete_motion + integrate (physics.rs:222-269), the swept tight box and the persistent fat box with the refit rule
 //                   (world.rs:235-238), both kept in LDS; per body i its candidates in the list's order - the mesh faces in mesh-BVH DFS
-//                   order (mesh.rs:115-139), then the partners j < i whose fat box overlaps i's tight box, ascending - counted, scanned
+//                   order (mesh.rs:115-139), then the components of the world's obstacles its swept box meets (the oracle's
+//                   World::obstacles: the obstacles in list order, the components in the order Compound::contacts visits them,
+//                   compound.rs:334-352), then the partners j < i whose fat box overlaps i's tight box, ascending - counted, scanned
 //                   and listed
 //   k_batch_faces / k_batch_pairs / k_batch_pack
-//                   the face tests and the pair tests, a lane per candidate; then the contacts packed in the list's order: contact c is
-//                   constraint c (every terrain contact a constraint of its own, world.rs:243-251; a pair's one contact is its
-//                   manifold, manifold.rs:131-148)
+//                   the face tests and the pair tests, a lane per candidate (a component of an obstacle is tested beside the pairs);
+//                   then the contacts packed in the list's order: contact c is constraint c (every terrain or obstacle contact a
+//                   constraint of its own, world.rs:243-251; a pair's one contact is its manifold, manifold.rs:131-148)
 //   k_batch_setup   ContactConstraint::new (solver.rs:101-191) a lane per contact; per body the length of its own range of the list
 //                   (it is `a` there) and how often it is `b`
 //   k_batch_solve   per body the constraints it takes part in as `b`, sorted: behind its own range that is the body's chain in list
@@ -31,16 +33,18 @@ constexpr uint32_t kBatchSpinLimit = 1u << 22;  // trips of the solve loop witho
 // The mesh BVH in the order BVH::query visits it (bvh.rs:283-310: push lchild, push rchild, pop rchild first), each node with the index
 // of the first node behind its subtree: a walk without a stack - and so without scratch memory - that reports the same leaves in the same order.
 //   node = (c.xyz, w0), (r.xyz, skip); leaf: w0 = 0x80000000 | face.
-struct BatchTerrain { const float4* nodes; const float4* verts; const uint4* faces; uint32_t n_nodes; float x[3]; };
+struct BatchTerrain { const float4* nodes; const float4* verts; const uint4* faces; uint32_t n_nodes; float x[3]; uint32_t obst; };
 // The meshes of the batch's terrain table, one behind the other in one store each of nodes, vertices and faces (a node's skip index, a
 // face's vertex indices and the face index of a leaf are the mesh's own), and what world k has of it: desc[2k] = (first node, first
-// vertex, first face, nodes - 0: no terrain), desc[2k + 1] = (the world's mesh position, -).
+// vertex, first face, nodes - 0: no terrain), desc[2k + 1] = (the world's mesh position, the world's range of the obstacle descriptors:
+// first << 7 | count - BatchObstacles below; a world's environment is one load).
 struct BatchTerrains { const float4* nodes; const float4* verts; const uint4* faces; const uint4* desc; };
 __device__ __forceinline__ BatchTerrain batch_terrain_of(const BatchTerrains& T, uint32_t k) {
   const uint4 d0 = T.desc[2 * (size_t)k], d1 = T.desc[2 * (size_t)k + 1];
   BatchTerrain M;
   M.nodes = T.nodes + 2 * (size_t)d0.x; M.verts = T.verts + d0.y; M.faces = T.faces + d0.z; M.n_nodes = d0.w;
   M.x[0] = u2f(d1.x); M.x[1] = u2f(d1.y); M.x[2] = u2f(d1.z);
+  M.obst = d1.w;
   return M;
 }
 
@@ -56,6 +60,52 @@ __device__ __forceinline__ void batch_terrain_walk(const BatchTerrain& M, const 
   }
 }
 
+// The static Compound obstacles of the worlds (the oracle's World::obstacles, as mgf_world_add_obstacle's).  The entries of the batch's
+// obstacle table sit one behind the other in one store of threaded trees (as a mesh's: a leaf's w0 = 0x80000000 | component, a skip
+// index is the entry's own) and one of components; world k's list is a range of the descriptors (the fourth word of the world's
+// second terrain descriptor: first << 7 | count), three words each: (first node, nodes, first component, -), (disp, rot.s),
+// (rot.xyz, -) - the pose is the list entry's, the geometry the table's.  The tick's kernels find the three stores behind the last
+// world's terrain descriptors (desc[2 n_worlds], desc[2 n_worlds + 1]: the pointers' words), read only by a world that has obstacles:
+// their argument block is what it was, and k_batch_front has no scalar register to spare.
+struct BatchObstacle { const float4* nodes; const CompIn* comps; uint32_t n_nodes; float disp[3]; float rot[4]; };
+struct BatchObstacles { const float4* nodes; const CompIn* comps; const uint4* desc; };
+constexpr uint32_t kBatchObstCountBits = 7;
+__device__ __forceinline__ uint32_t batch_obst_first(uint32_t range) { return range >> kBatchObstCountBits; }
+__device__ __forceinline__ uint32_t batch_obst_count(uint32_t range) { return range & ((1u << kBatchObstCountBits) - 1u); }
+__device__ __forceinline__ BatchObstacles batch_obstacles_of(const BatchTerrains& T, uint32_t n_worlds) {
+  const uint4 h0 = T.desc[2 * (size_t)n_worlds], h1 = T.desc[2 * (size_t)n_worlds + 1];
+  BatchObstacles O;
+  O.nodes = reinterpret_cast<const float4*>(((uint64_t)h0.y << 32) | h0.x);
+  O.comps = reinterpret_cast<const CompIn*>(((uint64_t)h0.w << 32) | h0.z);
+  O.desc = reinterpret_cast<const uint4*>(((uint64_t)h1.y << 32) | h1.x);
+  return O;
+}
+__device__ __forceinline__ BatchObstacle batch_obstacle_of(const BatchObstacles& O, uint32_t e) {
+  const uint4 d0 = O.desc[3 * (size_t)e], d1 = O.desc[3 * (size_t)e + 1], d2 = O.desc[3 * (size_t)e + 2];
+  BatchObstacle D;
+  D.nodes = O.nodes + 2 * (size_t)d0.x; D.n_nodes = d0.y; D.comps = O.comps + d0.z;
+  D.disp[0] = u2f(d1.x); D.disp[1] = u2f(d1.y); D.disp[2] = u2f(d1.z);
+  D.rot[0] = u2f(d1.w); D.rot[1] = u2f(d2.x); D.rot[2] = u2f(d2.y); D.rot[3] = u2f(d2.z);
+  return D;
+}
+// the walk of batch_terrain_walk over an obstacle's tree (compound_contacts_walk, k_api.h): bounded by the node count, no stack
+template <class F>
+__device__ __forceinline__ void compound_box_walk(const BatchObstacle& D, const Box& q, F&& emit) {
+  for (uint32_t at = 0; at < D.n_nodes;) {
+    const float4 n0 = D.nodes[2 * (size_t)at], n1 = D.nodes[2 * (size_t)at + 1];
+    Box nb; nb.c = xyz(n0); nb.r = xyz(n1);
+    const bool hit = box_overlaps(q, nb);
+    const uint32_t w0 = f2u(n0.w);
+    if (hit && (w0 & 0x80000000u)) emit(w0 & 0x7FFFFFFFu);
+    at = hit ? at + 1u : max(f2u(n1.w), at + 1u);
+  }
+}
+// A candidate against an obstacle: (i | (list slot + 1) << kBatchSlotShift, 0x80000000 | component) - a body's index takes ten bits,
+// so a face's and a partner's words are what they were, and a candidate with slot bits is no face.
+constexpr uint32_t kBatchSlotShift = 10, kBatchBodyMask = (1u << kBatchSlotShift) - 1u;
+static_assert(MGF_BATCH_MAX_BODIES <= (1 << kBatchSlotShift) && MGF_BATCH_MAX_WORLD_OBSTACLES < (1 << (32 - kBatchSlotShift)), "a candidate's first word");
+static_assert(MGF_BATCH_MAX_WORLD_OBSTACLES < (1 << kBatchObstCountBits), "a world's range of the obstacle descriptors");
+
 // What a failed tick puts back: 7 words a body.
 struct TickUndo { float4* p; uint32_t n; };  // (row r of body g at p[r * n + g]: x, q, srec[0], srec[1], delta, fb_c, fb_r)
 __device__ __forceinline__ float4& undo_at(const TickUndo& U, int r, size_t g) { return U.p[(size_t)r * U.n + g]; }
@@ -63,9 +113,9 @@ __device__ __forceinline__ float4& undo_at(const TickUndo& U, int r, size_t g) {
 struct BatchArgs {
   Bodies B;                  // every world's bodies, world k at [w_off[k], w_off[k + 1]); bpk is the tick's packed copy
   TickUndo U;
-  BatchTerrains T;           // world k's terrain: batch_terrain_of(T, k), k the workgroup's index (wave-uniform loads)
+  BatchTerrains T;           // world k's terrain: batch_terrain_of(T, k), k the workgroup's index (wave-uniform loads); its obstacles: batch_obstacles_of(T, n_worlds)
   const uint32_t* w_off;
-  uint2* cand;               // world k's candidates at q_off[k], q_cap[k] entries: (i, j) or (i, 0x80000000 | face)
+  uint2* cand;               // world k's candidates at q_off[k], q_cap[k] entries: (i, j), (i, 0x80000000 | face) or (i | slot + 1 << 10, 0x80000000 | component)
   const uint32_t* q_off;
   const uint32_t* q_cap;
   uint32_t* q_count;
@@ -126,6 +176,16 @@ __device__ __forceinline__ void batch_undo(const BatchArgs& A, uint32_t g0, uint
   }
 }
 
+// batch_undo for k_batch_front, whose argument block is `A` alone: the rows' addresses read afresh from the block.  (Kept from the top of
+// the kernel for this one rare path they hold fourteen scalar registers through the candidate loops, which have none to spare.)
+__device__ __forceinline__ void batch_undo_front(uint32_t g0, uint32_t n) {
+  const volatile BatchArgs* K = (const volatile BatchArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  BatchArgs R;
+  R.B.x = K->B.x; R.B.q = K->B.q; R.B.srec = K->B.srec; R.B.delta = K->B.delta; R.B.fb_c = K->B.fb_c; R.B.fb_r = K->B.fb_r;
+  R.U.p = K->U.p; R.U.n = K->U.n;
+  batch_undo(R, g0, n);
+}
+
 // LDS: 64 bytes a body of boxes, one word a body of counts.
 __global__ __launch_bounds__(kBatchBlock) void k_batch_front(BatchArgs A) {
   extern __shared__ float4 s_dyn[];
@@ -182,17 +242,40 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_front(BatchArgs A) {
   uint2* cand = A.cand + A.q_off[k];
   const BatchTerrain M = batch_terrain_of(A.T, k);
   const V3 mx = mk3(M.x[0], M.x[1], M.x[2]);
+  // The world's obstacles: its range of the descriptors and the stores.  Body i's candidates against their components are what
+  // Compound::contacts' walk meets per obstacle, in list order (compound.rs:340-346).  The mesh's tree and the obstacles' are walked by
+  // one loop - tree 0 the mesh's, tree s the obstacle's at list slot s - 1: one walk's worth of scalar registers, which is all this
+  // kernel has.
+  const uint32_t ob0 = batch_obst_first(M.obst), nob = batch_obst_count(M.obst);
+  BatchObstacles O;
+  O.nodes = nullptr; O.comps = nullptr; O.desc = nullptr;
+  if (nob) O = batch_obstacles_of(A.T, A.n_worlds);
 #pragma unroll 1
   for (int pass = 0; pass < 2; ++pass) {
     uint32_t npair = 0;
     for (uint32_t i = tid; i < n; i += T) {
       Box q; q.c = xyz(s_tc[i]); q.r = xyz(s_tr[i]);
-      Box qm = q; qm.c = q.c + -mx;  // Mesh::contacts queries bounds - mesh.x (mesh.rs:121)
       uint32_t at = pass ? s_off[i] : 0u;
-      batch_terrain_walk(M, qm, [&](uint32_t f) {
-        if (pass) cand[at] = make_uint2(i, 0x80000000u | f);
-        ++at;
-      });
+#pragma unroll 1
+      for (uint32_t t = 0; t <= nob; ++t) {
+        BatchObstacle D;  // (of a tree: nodes, n_nodes)
+        Box qb = q;
+        if (t == 0u) {
+          D.nodes = M.nodes; D.n_nodes = M.n_nodes;
+          qb.c = q.c + -mx;  // Mesh::contacts queries bounds - mesh.x (mesh.rs:121)
+        } else {
+          D = batch_obstacle_of(O, ob0 + t - 1u);
+          if (D.n_nodes) {
+            const BatchBody P = batch_load(B, (size_t)g0 + i);
+            qb = compound_query_box(D, P.col, P.d);
+          }
+        }
+        const uint32_t w = i | (t << kBatchSlotShift);
+        compound_box_walk(D, qb, [&](uint32_t leaf) {  // (batch_terrain_walk's loop)
+          if (pass) cand[at] = make_uint2(w, 0x80000000u | leaf);
+          ++at;
+        });
+      }
       const uint32_t at0 = at;
       for (uint32_t j = 0; j < i; ++j) {  // world.rs:256-290, partners ascending
         Box fb; fb.c = xyz(s_fc[j]); fb.r = xyz(s_fr[j]);
@@ -207,7 +290,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_front(BatchArgs A) {
     if (npair) atomicAdd(&s_stat[1], npair);
     batch_scan(s_off, n, &s_tot);
     if (s_tot > A.q_cap[k]) {
-      batch_undo(A, g0, n);
+      batch_undo_front(g0, n);
       if (tid == 0) A.need[2 * k] = s_tot;
       return;
     }
@@ -239,7 +322,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_faces(BatchArgs A) {
     uint32_t ct = 0;
     for (uint32_t p = tid; p < Q; p += T) {
       const uint2 e = cand[p];
-      if (!(e.y & 0x80000000u)) continue;
+      if (!(e.y & 0x80000000u) || e.x > kBatchBodyMask) continue;
       const BatchBody Pa = batch_load(B, (size_t)g0 + e.x);
       const uint4 fi = M.faces[e.y & 0x7FFFFFFFu];
       const Triangle tri = mkt(xyz(M.verts[fi.x]) + mx, xyz(M.verts[fi.y]) + mx, xyz(M.verts[fi.z]) + mx);  // mesh.rs:122-126
@@ -264,18 +347,51 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_faces(BatchArgs A) {
   }
 }
 
-// The pair tests, a lane per candidate that is a partner, into the candidate's first slot.
+// The pair tests, a lane per candidate that is a partner, into the candidate's first slot; in a world with obstacles the candidates
+// against a component of one too: Moving<collider>.contacts(&component) through the wrapper of collision.rs:1368-1382 - the component,
+// turned about the origin by the entry's rot and moved by its disp, sweeps at -delta against the collider, the result shifted by
+// delta * t (k_narrow_obstacles' contacts_dispatch for a sphere or capsule on both sides is comp_mcomp and that shift: one contact at
+// most) - and the local points of LocalContacts (collision.rs:1490-1506) with the obstacle in the Mesh's place: the body's side relative
+// to its centre at the contact time, the obstacle's relative to its disp.
 __global__ __launch_bounds__(kBatchBlock) void k_batch_pairs(BatchArgs A) {
+  __shared__ uint32_t s_ct;
   const uint32_t k = blockIdx.x, T = kBatchBlock, tid = threadIdx.x;
   if (A.done[k] != A.tick || A.stage[k] != 8u * A.tick + 2u || batch_failed(A, k)) return;
   const uint32_t g0 = A.w_off[k], M = A.q_count[k];
+  const uint32_t obst = A.T.desc[2 * (size_t)k + 1].w, ob0 = batch_obst_first(obst);
+  const bool obstacles = batch_obst_count(obst) != 0u;  // (the workgroup's world: uniform)
+  BatchObstacles O;
+  O.nodes = nullptr; O.comps = nullptr; O.desc = nullptr;
+  if (obstacles) O = batch_obstacles_of(A.T, A.n_worlds);
   const Bodies& B = A.B;
   const uint2* cand = A.cand + A.q_off[k];
   uint32_t* ncq = A.ncq + A.q_off[k];
   float4* slot = A.slot + 6 * (size_t)A.q_off[k];
+  if (obstacles) {
+    if (tid == 0) s_ct = 0u;
+    __syncthreads();
+  }
+  uint32_t ct = 0;
   for (uint32_t p = tid; p < M; p += T) {
     const uint2 e = cand[p];
-    if (e.y & 0x80000000u) continue;
+    if (e.y & 0x80000000u) {
+      if (e.x <= kBatchBodyMask) continue;  // a face: k_batch_faces
+      const BatchBody Pa = batch_load(B, (size_t)g0 + (e.x & kBatchBodyMask));
+      const BatchObstacle D = batch_obstacle_of(O, ob0 + (e.x >> kBatchSlotShift) - 1u);
+      const V3 disp = ld3(D.disp);
+      Comp shape = comp_rotate_about(to_comp(D.comps[e.y & 0x7FFFFFFFu]), mkq(D.rot[0], mk3(D.rot[1], D.rot[2], D.rot[3])), mk3(0.0f, 0.0f, 0.0f));
+      shape.p = shape.p + disp;
+      Contact c;
+      const bool hit = comp_mcomp(Pa.col, shape, -Pa.d, &c);
+      ncq[p] = hit ? 1u : 0u;
+      if (hit) {
+        const V3 sh = Pa.d * c.t;
+        float4* o = slot + 6 * (size_t)p;
+        o[0] = mk4((c.a + sh) + -(comp_center(Pa.col) + Pa.d * c.t), c.t); o[1] = mk4((c.b + sh) + -disp, 0.0f); o[2] = mk4(c.n, 0.0f);
+        ++ct;
+      }
+      continue;
+    }
     const BatchBody Pa = batch_load(B, (size_t)g0 + e.x), Pb = batch_load(B, (size_t)g0 + e.y);
     LocalContact lc;
     const bool hit = comp_pair_local(Pa.col, Pa.d, Pb.col, Pb.d, &lc);
@@ -286,10 +402,16 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_pairs(BatchArgs A) {
       o[0] = mk4(lc.la, lc.g.t); o[1] = mk4(lc.lb, 0.0f); o[2] = mk4(nrm, 0.0f);
     }
   }
+  if (obstacles) {  // n_terrain_constraints counts the obstacles' contacts too (behind k_batch_faces' count of the faces')
+    if (ct) atomicAdd(&s_ct, ct);
+    __syncthreads();
+    if (tid == 0) A.stats[((size_t)A.tick * A.n_worlds + k) * 8u + 2u] += s_ct;
+  }
   if (tid == 0) A.stage[k] = 8u * A.tick + 3u;
 }
 
-// The contacts packed, 256 candidates at a time in list order: contact c of the world = constraint c: (la, t), (lb, i), (n, j).
+// The contacts packed, 256 candidates at a time in list order: contact c of the world = constraint c: (la, t), (lb, i), (n, j); an
+// obstacle's contact has its list slot + 1 above the ten bits of i (the candidate's first word).
 __global__ __launch_bounds__(kBatchBlock) void k_batch_pack(BatchArgs A) {
   __shared__ uint32_t s_wave[kBatchBlock / 64];
   const uint32_t k = blockIdx.x, T = kBatchBlock, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
@@ -319,7 +441,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_pack(BatchArgs A) {
         const float4* in = slot + 6 * (size_t)p + 3 * q;
         float4* o = cont + 4 * (size_t)(at + q);
         const float4 w1 = in[1], w2 = in[2];
-        o[0] = in[0]; o[1] = make_float4(w1.x, w1.y, w1.z, u2f(e.x)); o[2] = make_float4(w2.x, w2.y, w2.z, u2f(jb));
+        o[0] = in[0]; o[1] = make_float4(w1.x, w1.y, w1.z, u2f(e.x)); o[2] = make_float4(w2.x, w2.y, w2.z, u2f(jb));  // (e.x: the body, and above it the obstacle's slot + 1)
       }
     }
   }
@@ -353,7 +475,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_setup(BatchArgs A) {
   for (uint32_t i = tid; i < n; i += T) { s_first[i] = kNone; s_na[i] = 0u; s_degb[i] = 0u; }
   __syncthreads();
   for (uint32_t c = tid; c < C; c += T) {
-    const uint32_t i = f2u(cont[4 * (size_t)c + 1].w), j = f2u(cont[4 * (size_t)c + 2].w);
+    const uint32_t i = f2u(cont[4 * (size_t)c + 1].w) & kBatchBodyMask, j = f2u(cont[4 * (size_t)c + 2].w);
     atomicMin(&s_first[i], c);
     atomicAdd(&s_na[i], 1u);
     if (j != kNone) atomicAdd(&s_degb[j], 1u);
@@ -361,11 +483,16 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_setup(BatchArgs A) {
   __syncthreads();
   for (uint32_t c = tid; c < C; c += T) {
     const float4 w0 = cont[4 * (size_t)c], w1 = cont[4 * (size_t)c + 1], w2 = cont[4 * (size_t)c + 2];
-    const uint32_t i = f2u(w1.w), j = f2u(w2.w);
+    const uint32_t i = f2u(w1.w) & kBatchBodyMask, os = f2u(w1.w) >> kBatchSlotShift, j = f2u(w2.w);
     const float4 dli = B.bpk[4 * ((size_t)g0 + i) + 1], eii = B.bpk[4 * ((size_t)g0 + i) + 2];
     CRec r;
     if (j == kNone) {  // Static{ center: terrain.center(), friction: 0.0 } world.rs:247; Manifold::from(lc) manifold.rs:120-128
-      r = make_constraint(i, kNone, load_dyn(B.srec, g0 + i), xyz(eii), eii.w, dli.w, static_dyn(), mx, 0.0f, 0.0f, xyz(w2), xyz(w0), xyz(w1), A.dt, A.baumgarte,
+      V3 sc = mx;
+      if (os) {  // an obstacle's contact: Shape::center for Compound is its disp (compound.rs:289-291)
+        const uint4 od = batch_obstacles_of(A.T, A.n_worlds).desc[3 * (size_t)(batch_obst_first(tx.w) + os - 1u) + 1];
+        sc = mk3(u2f(od.x), u2f(od.y), u2f(od.z));
+      }
+      r = make_constraint(i, kNone, load_dyn(B.srec, g0 + i), xyz(eii), eii.w, dli.w, static_dyn(), sc, 0.0f, 0.0f, xyz(w2), xyz(w0), xyz(w1), A.dt, A.baumgarte,
                           A.slop);
     } else {
       const float4 dlj = B.bpk[4 * ((size_t)g0 + j) + 1], eij = B.bpk[4 * ((size_t)g0 + j) + 2];

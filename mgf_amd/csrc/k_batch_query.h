@@ -15,6 +15,11 @@
 //   k_batch_query_sweep_faces   a lane per cast takes its record up again and walks the mesh tree with the padded swept box (a capsule's
 //                               `reach`; `every` face for a capsule that does not move): tri_msphere / tri_mcapsule.  A launch of its own:
 //                               tri_mcapsule beside comp_mcomp needs more scalar registers than there are (as k_batch_faces / k_batch_pairs)
+//   k_batch_query_ray_obstacles / k_batch_query_sweep_obstacles
+//                               a lane per query takes its record up again and puts the query through the obstacles of its world in list
+//                               order: q_ray_obstacle (Intersects<Compound>) and compound_contacts_walk (Compound::contacts), the lone
+//                               world's own, over the threaded trees of the batch's obstacle table (BatchObstacles, k_batch.h).  Launched
+//                               only when the mask asks for obstacles and a world of the batch has one
 // Every test, the ranking and the records are k_query.h's own (q_ray_terrain / q_sweep_terrain, QueryBest / SweepBest, q_*_store, q_sweep_load);
 // here are the work split (BatchWork), the staging, the cheap rejects and the reduction over a query's lanes (bq_reduce).
 // The order is total and every reject is conservative, so neither the number of lanes a query gets, nor the other queries of its work
@@ -58,6 +63,19 @@ __device__ __forceinline__ void q_mesh_walk(const BatchTerrain& M, uint32_t*, P&
     const uint32_t w0 = f2u(n0.w);
     if (hit && (w0 & 0x80000000u)) emit(w0 & 0x7FFFFFFFu);
     at = hit ? at + 1u : f2u(n1.w);
+  }
+}
+
+// q_compound_walk over the threaded tree of an entry of the obstacle table (no stack: no error)
+template <class P, class F>
+__device__ __forceinline__ void q_compound_walk(const BatchObstacle& D, uint32_t*, P&& pass, F&& emit) {
+  for (uint32_t at = 0; at < D.n_nodes;) {
+    const float4 n0 = D.nodes[2 * (size_t)at], n1 = D.nodes[2 * (size_t)at + 1];
+    Box nb; nb.c = xyz(n0); nb.r = xyz(n1);
+    const bool hit = pass(nb);
+    const uint32_t w0 = f2u(n0.w);
+    if (hit && (w0 & 0x80000000u)) emit(w0 & 0x7FFFFFFFu);
+    at = hit ? at + 1u : max(f2u(n1.w), at + 1u);
   }
 }
 
@@ -206,6 +224,44 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_faces(BatchTe
   int32_t* o = out + 13 * (size_t)i;
   SweepBest best = q_sweep_load(o);  // k_batch_query_sweep_bodies' answer
   q_sweep_terrain(M, K, nullptr, best);
+  q_sweep_store(o, best);
+}
+
+// a stored ray record taken up again by a later launch (q_sweep_load's counterpart)
+__device__ __forceinline__ QueryBest q_ray_load(const int32_t* o) {
+  QueryBest best;
+  if (o[0] != MGF_HIT_NONE) { best.have = true; best.kind = o[0]; best.index = (uint32_t)o[1]; best.part = (uint32_t)o[2]; best.p = mk3(u2f(o[3]), u2f(o[4]), u2f(o[5])); best.t = u2f(o[6]); }
+  return best;
+}
+
+// The obstacles of every query's own world (world[i]), a lane per query in the caller's order: `index` of a hit is the obstacle's place
+// in the world's list, `part` the component.
+__global__ __launch_bounds__(kBatchBlock) void k_batch_query_ray_obstacles(BatchObstacles O, const uint4* tdesc, const int32_t* world, const ParticleIn* parts, uint32_t n,
+                                                                            int32_t* out) {
+  const uint32_t i = blockIdx.x * kBatchBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t obst = tdesc[2 * (size_t)world[i] + 1].w, ob0 = batch_obst_first(obst), ob1 = ob0 + batch_obst_count(obst);
+  if (ob0 == ob1) return;
+  const ParticleIn q = parts[i];
+  if (q.d[0] == 0.0f && q.d[1] == 0.0f && q.d[2] == 0.0f) return;  // (no direction: no hit, by definition - k_query_ray)
+  int32_t* o = out + 7 * (size_t)i;
+  QueryBest best = q_ray_load(o);  // k_batch_query_ray's answer
+#pragma unroll 1
+  for (uint32_t e = ob0; e < ob1; ++e) q_ray_obstacle(batch_obstacle_of(O, e), e - ob0, q, nullptr, best);
+  q_ray_store(o, best);
+}
+__global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_obstacles(BatchObstacles O, const uint4* tdesc, const int32_t* world, const MovingIn* casts, uint32_t n,
+                                                                              int32_t* out) {
+  const uint32_t i = blockIdx.x * kBatchBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t obst = tdesc[2 * (size_t)world[i] + 1].w, ob0 = batch_obst_first(obst), ob1 = ob0 + batch_obst_count(obst);
+  if (ob0 == ob1) return;
+  const SweepCast K = bq_sweep_cast(casts[i]);
+  int32_t* o = out + 13 * (size_t)i;
+  SweepBest best = q_sweep_load(o);  // k_batch_query_sweep_bodies' (and _faces') answer
+#pragma unroll 1
+  for (uint32_t e = ob0; e < ob1; ++e)
+    compound_contacts_walk(batch_obstacle_of(O, e), K.s, K.v, [&](uint32_t ci, const Contact& c) { best.offer(c, MGF_HIT_OBSTACLE, e - ob0, ci, 0u); });
   q_sweep_store(o, best);
 }
 

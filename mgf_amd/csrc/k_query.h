@@ -247,16 +247,11 @@ __device__ __forceinline__ void q_ray_body(const QueryTargets& T, uint32_t s, V3
   }
 }
 
-// Intersects<Compound> compound.rs:309-332 (k_compound_intersections' walk), with the component that answered
-__device__ __forceinline__ void q_ray_obstacle(const CompoundDev& D, uint32_t o, const ParticleIn& q, uint32_t* err, QueryBest& best) {
-  V3 pp = ld3(q.p), pd = ld3(q.d), disp = ld3(D.disp);
-  const float dt = q.dt;
-  Quat rot = mkq(D.rot[0], mk3(D.rot[1], D.rot[2], D.rot[3]));
-  Quat conj = mkq(rot.s, -rot.v);
-  V3 rp = rotate(conj, pp + -disp) + disp, rd = rotate(conj, pd);
-  bool have = false;
-  V3 best_p = mk3(0, 0, 0); float best_t = 0.0f;
-  uint32_t best_c = 0;
+// The walk of a compound's tree with any test of a node's box, in the order bvh.rs:283-310 visits it: emit(ci) for every leaf whose
+// boxes all pass, straight behind the leaf's own pass.  Here the explicit stack over a CompoundDev's TerrainDev; in k_batch_query.h
+// the threaded tree of an entry of a batch's obstacle table.
+template <class P, class F>
+__device__ __forceinline__ void q_compound_walk(const CompoundDev& D, uint32_t* err, P&& pass, F&& emit) {
   uint32_t stack[kStack];
   int sp = 0;
   if (D.tree.n_nodes) stack[sp++] = D.tree.root;
@@ -265,21 +260,40 @@ __device__ __forceinline__ void q_ray_obstacle(const CompoundDev& D, uint32_t o,
     const float4* raw = reinterpret_cast<const float4*>(&D.tree.nodes[top]);
     float4 n0 = raw[0], n1 = raw[1];
     Box nb; nb.c = xyz(n0); nb.r = xyz(n1);
-    V3 ip; float t;
-    if (ray_box(rp, rd, nb, &ip, &t, kInf)) {
+    if (pass(nb)) {
       uint32_t w0 = f2u(n0.w), w1 = f2u(n1.w);
-      if (w0 & 0x80000000u) {
-        if (!(t > dt)) {
-          const uint32_t ci = w0 & 0x7FFFFFFFu;
-          Comp shape = comp_rotate(to_comp(D.comps[ci]), rot);
-          shape.p = shape.p + disp;
-          V3 sip; float st;
-          if (intersection_dispatch(q, comp_shape(shape), &sip, &st) == 1 && !(have && st > best_t)) { best_p = sip; best_t = st; best_c = ci; have = true; }
-        }
-      } else if (sp + 2 <= kStack) { stack[sp++] = w0; stack[sp++] = w1; }
+      if (w0 & 0x80000000u) emit(w0 & 0x7FFFFFFFu);
+      else if (sp + 2 <= kStack) { stack[sp++] = w0; stack[sp++] = w1; }
       else *err = 1u;
     }
   }
+}
+// Intersects<Compound> compound.rs:309-332 (k_compound_intersections' walk), with the component that answered.  C: either form of a
+// compound (compound_contacts_walk, k_api.h).  A later hit with an equal t replaces the earlier: the walk's order is the reference's.
+template <class C>
+__device__ __forceinline__ void q_ray_obstacle(const C& D, uint32_t o, const ParticleIn& q, uint32_t* err, QueryBest& best) {
+  V3 pp = ld3(q.p), pd = ld3(q.d), disp = ld3(D.disp);
+  const float dt = q.dt;
+  Quat rot = mkq(D.rot[0], mk3(D.rot[1], D.rot[2], D.rot[3]));
+  Quat conj = mkq(rot.s, -rot.v);
+  V3 rp = rotate(conj, pp + -disp) + disp, rd = rotate(conj, pd);
+  bool have = false;
+  V3 best_p = mk3(0, 0, 0); float best_t = 0.0f;
+  uint32_t best_c = 0;
+  float t = 0.0f;  // where the particle enters the box of the node last passed
+  q_compound_walk(
+      D, err,
+      [&](const Box& nb) {
+        V3 ip;
+        return ray_box(rp, rd, nb, &ip, &t, kInf);
+      },
+      [&](uint32_t ci) {
+        if (t > dt) return;
+        Comp shape = comp_rotate(to_comp(D.comps[ci]), rot);
+        shape.p = shape.p + disp;
+        V3 sip; float st;
+        if (intersection_dispatch(q, comp_shape(shape), &sip, &st) == 1 && !(have && st > best_t)) { best_p = sip; best_t = st; best_c = ci; have = true; }
+      });
   if (have) best.offer(best_p, best_t, MGF_HIT_OBSTACLE, o, best_c);
 }
 
