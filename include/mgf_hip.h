@@ -141,6 +141,9 @@ MGF_API void mgf_ctx_destroy(mgf_ctx* ctx);
 /* Enqueue all work of this context on a caller-owned hipStream_t (e.g. the stream the caller's RCCL
  * transfers are ordered on) instead of the context's own stream.  The caller keeps ownership. */
 MGF_API mgf_status mgf_ctx_set_stream(mgf_ctx* ctx, void* hip_stream);
+/* Waits for the context's stream (its own, or the caller's after mgf_ctx_set_stream) and for nothing else on the device: how a caller
+ * who shares no stream with the library waits for the calls that return without waiting (the mgf_batch_*_dev calls). */
+MGF_API mgf_status mgf_ctx_synchronize(mgf_ctx* ctx);
 MGF_API const char* mgf_last_error(void);        /* thread-local message for the last non-OK status */
 MGF_API mgf_params mgf_default_params(void);     /* DefaultContactConstraintParams / DefaultPruningParams */
 MGF_API const char* mgf_version(void);
@@ -752,10 +755,65 @@ MGF_API mgf_status mgf_batch_apply_impulses(mgf_batch* b, const int32_t* world, 
  * its source of different lengths, a destination named twice, and - where dst == src - a world that is both a source and a
  * destination.  One workgroup per pair, one launch (and one more when shares grow): "drive_launches" of dst. */
 MGF_API mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_world, const mgf_batch* src, const int32_t* src_world, int64_t n);
+/* ---- device-pointer calls: state, forces, impulses, contact summaries and resets for a caller whose arrays are device memory ----
+ * The calls above move their records through host memory (an upload or a download and a host wait per call).  These take pointers
+ * marked *_dev* / documented as device memory: memory of the context's device (hipMalloc or managed - e.g. a torch tensor's data_ptr()).
+ * Each call is enqueued on the context's stream and RETURNS WITHOUT WAITING for it: order the caller's own work against it with
+ * mgf_ctx_set_stream (one shared stream) or wait with mgf_ctx_synchronize.  In the steady state - the batch on the device, the handle's
+ * scratch buffers large enough, and for the masked copy an unchanged pair table - a call makes no host wait and no copy between host
+ * and device.
+ * A body is named by its flat index g = (bodies in the worlds before its world) + index within its world: the order of
+ * mgf_batch_read_state(world = -1).  body_dev == NULL: record i names body i, and n <= mgf_batch_len(b, -1).
+ * Every index is checked on the device: a record whose index lies outside [0, mgf_batch_len(b, -1)) is skipped whole - it reads nothing
+ * and writes nothing - and counted in mgf_batch_counter "device_skipped" (cumulative over the batch's life; reading it waits for the
+ * stream).
+ * Pointer safety: before anything is enqueued every non-NULL device pointer is looked up on the host - hipPointerGetAttributes must
+ * report device or managed memory of the context's device, hipMemGetAddressRange that the bytes the call will touch lie inside the
+ * allocation - and the pointer must be 4-byte aligned; else MGF_ERR_INVALID, nothing enqueued.  Also refused before any device work: a
+ * NULL batch, a negative n, n > INT32_MAX, and what each call names below.
+ * Launches ("drive_launches" of the batch, as for the host-memory calls; none depends on n or on n_worlds):
+ *   mgf_batch_gather_state_dev                     1
+ *   the three setters, body_dev == NULL            1
+ *   the three setters, body_dev given              MGF_BATCH_DEV_SET_LAUNCHES = 3 (count, fill, apply; the prefix sum between count and
+ *                                                  fill is the library's and is not counted, as for mgf_batch_overlap_aabb_many)
+ *   mgf_batch_copy_worlds_where                    1, and 1 more when shares grow (as mgf_batch_copy_worlds)
+ *   mgf_batch_read_body_contacts_dev               1 ("query_launches", as mgf_batch_read_body_contacts)
+ * OUT OF SCOPE here: device-pointer rays, sweeps and box queries (their sort by world is on the host); a step without its one host wait
+ * per call (the capacity re-runs need it); hipGraph capture of these calls; anything for the lone mgf_world (it has
+ * mgf_world_export_bodies / _import_ghosts / _device_ptr). */
+#define MGF_BATCH_DEV_SET_LAUNCHES 3
+/* Tightly packed rows for record i: 3 floats, 4 for q (s, x, y, z: mgf_quat).  Any output may be NULL.  x, v, omega, force, torque
+ * equal mgf_batch_get_many's for the same bodies bit for bit (x is x + delta, physics.rs:282), q equals mgf_batch_read_state's. */
+MGF_API mgf_status mgf_batch_gather_state_dev(mgf_batch* b, const int32_t* body_dev, int64_t n,
+                                              float* x, float* q, float* v, float* omega, float* force, float* torque);
+/* mgf_batch_set_many / _set_forces / _apply_impulses with rows of 3 floats in device memory: the same rows written, the same left alone.
+ * linear and angular of mgf_batch_set_many_dev are both required (NULL: MGF_ERR_INVALID); either array of the other two may be NULL
+ * (force / torque: that row is left as it is; linear / angular: zero for every record).
+ * Records that name the same body are resolved on the device, to the definition of the host path's stable sort: a set takes the record
+ * with the highest array index; an impulse run is applied in ascending array index, v = v + linear * inv_mass, omega = omega + I *
+ * angular, sequential f32 operations, no fused multiply-add.  One lane owns a body, there is no float atomic, nothing of the answer
+ * depends on lane scheduling.  (The lane orders a body's records by insertion: a call that names ONE body many thousands of times is
+ * slow, not wrong.)  The caller's arrays must not change until the call has run. */
+MGF_API mgf_status mgf_batch_set_many_dev(mgf_batch* b, const int32_t* body_dev, int64_t n, const float* linear, const float* angular);
+MGF_API mgf_status mgf_batch_set_forces_dev(mgf_batch* b, const int32_t* body_dev, int64_t n, const float* force, const float* torque);
+MGF_API mgf_status mgf_batch_apply_impulses_dev(mgf_batch* b, const int32_t* body_dev, int64_t n, const float* linear, const float* angular);
+/* mgf_batch_read_body_contacts written straight into the caller's device buffer of cap records: no copy, no wait; "query_run_ns" is 0. */
+MGF_API mgf_status mgf_batch_read_body_contacts_dev(mgf_batch* b, int64_t world, mgf_body_contacts* out_dev, int64_t cap);
+/* mgf_batch_copy_worlds for the pairs a mask in device memory selects: pair i is copied iff mask_dev[i] != 0 (read by the pair's
+ * workgroup); a copied pair is bit-identical to mgf_batch_copy_worlds of that pair, a masked-out destination is untouched to the bit.
+ * dst_world and src_world are HOST arrays, checked and refused exactly as mgf_batch_copy_worlds does; also refused: NULL mask_dev with
+ * n > 0.  The host cannot know the mask: the share of EVERY named destination grows to its source's list before the launch (a larger
+ * share than needed may stay; no record is lost).  The pair table stays on the device in dst and is uploaded again only when the arrays
+ * differ from the last call's (mgf_batch_counter "pair_table_uploads", cumulative).  mgf_batch_read_constraints and a later copy out of
+ * dst first fetch the lengths of dst's lists from the device (one wait); mgf_batch_step does that anyway. */
+MGF_API mgf_status mgf_batch_copy_worlds_where(mgf_batch* dst, const int32_t* dst_world, const mgf_batch* src, const int32_t* src_world,
+                                               int64_t n, const int32_t* mask_dev);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /
- * _set_forces / _apply_impulses / _copy_worlds call on this batch - for a copy, on its destination: it depends on neither n_worlds nor n)}. */
+ * _set_forces / _apply_impulses / _copy_worlds call or device-pointer call on this batch - for a copy, on its destination: it depends on
+ * neither n_worlds nor n), "device_skipped" (records of the device-pointer calls whose index was out of range, cumulative; waits for the
+ * stream), "pair_table_uploads" (uploads of mgf_batch_copy_worlds_where's pair table, cumulative)}. */
 MGF_API mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out);
 /* Options (test knobs): "cons_per_body" [4] = the constraint records per body a world's share of the storage starts with (1 .. 4096); a
  * low value makes the first busy tick outgrow it, which the re-run path then handles. */

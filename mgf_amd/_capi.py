@@ -119,6 +119,7 @@ BODY_GET_DTYPE = np.dtype([("linear", "<f4", 3), ("angular", "<f4", 3), ("x", "<
 HIT_NONE, HIT_BODY, HIT_TERRAIN, HIT_OBSTACLE = -1, 0, 1, 2
 BATCH_MAX_BODIES = 1024  # MGF_BATCH_MAX_BODIES
 BATCH_MAX_WORLD_OBSTACLES = 64  # MGF_BATCH_MAX_WORLD_OBSTACLES
+BATCH_DEV_SET_LAUNCHES = 3  # MGF_BATCH_DEV_SET_LAUNCHES
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -156,6 +157,8 @@ SYMBOLS = [
     "mgf_batch_read_body_contacts", "mgf_batch_overlap_aabb_many",
     "mgf_batch_get_many", "mgf_batch_set_many", "mgf_batch_set_forces", "mgf_batch_apply_impulses", "mgf_batch_copy_worlds",
     "mgf_batch_add_obstacle", "mgf_batch_set_world_obstacles", "mgf_batch_obstacle_count", "mgf_batch_world_obstacle_count",
+    "mgf_ctx_synchronize", "mgf_batch_gather_state_dev", "mgf_batch_set_many_dev", "mgf_batch_set_forces_dev", "mgf_batch_apply_impulses_dev",
+    "mgf_batch_read_body_contacts_dev", "mgf_batch_copy_worlds_where",
 ]
 
 _lib = None
@@ -316,6 +319,13 @@ def load_library():
         "mgf_batch_set_world_obstacles": (i32, [vp, vp, vp, vp, vp, i64]),
         "mgf_batch_obstacle_count": (i64, [vp]),
         "mgf_batch_world_obstacle_count": (i64, [vp, i64]),
+        "mgf_ctx_synchronize": (i32, [vp]),
+        "mgf_batch_gather_state_dev": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp]),
+        "mgf_batch_set_many_dev": (i32, [vp, vp, i64, vp, vp]),
+        "mgf_batch_set_forces_dev": (i32, [vp, vp, i64, vp, vp]),
+        "mgf_batch_apply_impulses_dev": (i32, [vp, vp, i64, vp, vp]),
+        "mgf_batch_read_body_contacts_dev": (i32, [vp, i64, vp, i64]),
+        "mgf_batch_copy_worlds_where": (i32, [vp, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -366,6 +376,10 @@ class Context:
     def set_stream(self, hip_stream):
         """Enqueue this context's work on a caller-owned hipStream_t (an int handle, e.g. torch's cuda_stream)."""
         _check(load_library().mgf_ctx_set_stream(self._h, C.c_void_p(int(hip_stream))))
+
+    def synchronize(self):
+        """Wait for this context's stream (mgf_ctx_synchronize) - and for nothing else on the device"""
+        _check(load_library().mgf_ctx_synchronize(self._h))
 
     def close(self):
         """Destroy the context; handles created from it are released first.  (A handle that outlives it all the same - an interpreter's
@@ -870,6 +884,26 @@ def _per_query(v, n, optional=False, dtype=np.int32):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data
+
+
+def _dev_arg(a, dtype, cols, n, name):
+    """the address of a device-pointer call's argument: None, a raw integer address (taken as it is: the library checks that it is
+    device memory and large enough), or a torch tensor - float32 / int32 as the call needs, contiguous, on a GPU, n rows of `cols`"""
+    if a is None:
+        return None
+    if isinstance(a, (int, np.integer)):
+        return int(a)
+    if not hasattr(a, "data_ptr"):
+        raise ValueError(f"{name}: a torch tensor on the GPU or an integer address, not {type(a).__name__}")
+    if str(a.dtype) != "torch." + dtype:
+        raise ValueError(f"{name}: dtype must be {dtype}, not {a.dtype}")
+    if not a.is_contiguous():
+        raise ValueError(f"{name}: the tensor is not contiguous")
+    if a.numel() != n * cols or (a.dim() > 0 and a.shape[0] != n):
+        raise ValueError(f"{name}: {tuple(a.shape)} is not {n} rows of {cols}")
+    if a.device.type != "cuda":
+        raise ValueError(f"{name}: the tensor is on {a.device}, not on the GPU")
+    return int(a.data_ptr())
 
 
 def _particle_rows(p, d, dt):
@@ -1488,6 +1522,73 @@ class WorldBatch:
         sw = _per_query(src_world, len(dw))
         s = self if src is None else src
         _check(load_library().mgf_batch_copy_worlds(self._h, dw.ctypes.data, s._h, sw.ctypes.data, len(dw)))
+
+    # ---- the device-pointer calls: arguments are torch tensors on the context's device, or raw integer addresses -------------------------
+    def body_index(self, world, body):
+        """flat int32 indices of body[i] of world[i] (a scalar world: every body of that world), from the host's lengths: what the
+        device-pointer calls name a body by - the order of state(None)"""
+        lib = load_library()
+        off = np.concatenate([[0], np.cumsum([lib.mgf_batch_len(self._h, k) for k in range(self.n_worlds)])]).astype(np.int64)
+        wd, bd = self._records(world, body)
+        if len(wd) and (wd.min() < 0 or wd.max() >= self.n_worlds):
+            raise ValueError("world index out of range")
+        if np.any(bd < 0) or np.any(bd >= (off[1:] - off[:-1])[wd]):
+            raise ValueError("body index out of range")
+        return (off[wd] + bd).astype(np.int32)
+
+    def _dev_records(self, body, n):
+        """(address of the flat indices or None, n) of a device-pointer call"""
+        if body is None:
+            return None, (len(self) if n is None else int(n))
+        if n is None:
+            if not hasattr(body, "data_ptr"):
+                raise ValueError("n must be given with a raw address")
+            n = int(body.numel())
+        return _dev_arg(body, "int32", 1, int(n), "body"), int(n)
+
+    def gather_state(self, body=None, x=None, q=None, v=None, omega=None, force=None, torque=None, n=None):
+        """mgf_batch_gather_state_dev: x (= x + delta), q, v, omega, force, torque of the bodies `body` names (flat indices, a CUDA int32
+        tensor; None: every body in order) into the CUDA float32 tensors given - n rows of 3, q of 4; None: not asked for.  Enqueued on
+        the context's stream, not waited for."""
+        bp, n = self._dev_records(body, n)
+        p = [_dev_arg(a, "float32", 4 if k == 1 else 3, n, name)
+             for k, (a, name) in enumerate(((x, "x"), (q, "q"), (v, "v"), (omega, "omega"), (force, "force"), (torque, "torque")))]
+        _check(load_library().mgf_batch_gather_state_dev(self._h, bp, n, *p))
+
+    def set_velocities_dev(self, body, linear, angular, n=None):
+        """set_velocities with flat body indices and rows in device memory (mgf_batch_set_many_dev); both arrays are required"""
+        if linear is None or angular is None:
+            raise ValueError("linear and angular are both required")
+        bp, n = self._dev_records(body, n)
+        _check(load_library().mgf_batch_set_many_dev(self._h, bp, n, _dev_arg(linear, "float32", 3, n, "linear"), _dev_arg(angular, "float32", 3, n, "angular")))
+
+    def set_forces_dev(self, body, force=None, torque=None, n=None):
+        """set_forces with flat body indices and rows in device memory (mgf_batch_set_forces_dev); None leaves that row as it is"""
+        bp, n = self._dev_records(body, n)
+        _check(load_library().mgf_batch_set_forces_dev(self._h, bp, n, _dev_arg(force, "float32", 3, n, "force"), _dev_arg(torque, "float32", 3, n, "torque")))
+
+    def apply_impulses_dev(self, body, linear=None, angular=None, n=None):
+        """apply_impulses with flat body indices and rows in device memory (mgf_batch_apply_impulses_dev); None: zero"""
+        bp, n = self._dev_records(body, n)
+        _check(load_library().mgf_batch_apply_impulses_dev(self._h, bp, n, _dev_arg(linear, "float32", 3, n, "linear"), _dev_arg(angular, "float32", 3, n, "angular")))
+
+    def body_contacts_dev(self, out, world=None):
+        """body_contacts written straight into `out`: a CUDA float32 or int32 tensor of 6 words a body (BODY_CONTACTS_DTYPE's layout) for
+        one world, or (world=None) the whole batch (mgf_batch_read_body_contacts_dev); not waited for"""
+        w = -1 if world is None else int(world)
+        n = max(load_library().mgf_batch_len(self._h, w), 0)
+        words = "int32" if str(getattr(out, "dtype", "")) == "torch.int32" else "float32"
+        _check(load_library().mgf_batch_read_body_contacts_dev(self._h, w, _dev_arg(out, words, 6, n, "out"), n))
+
+    def copy_worlds_where(self, dst_world, src, src_world, mask):
+        """copy_worlds for the pairs whose word of `mask` (a CUDA int32 tensor, one a pair) is not zero, read on the device
+        (mgf_batch_copy_worlds_where); dst_world / src_world are host arrays as for copy_worlds.  Not waited for."""
+        dw = np.ascontiguousarray(np.atleast_1d(dst_world), np.int32).reshape(-1)
+        sw = _per_query(src_world, len(dw))
+        s = self if src is None else src
+        if mask is None:
+            raise ValueError("mask is required")
+        _check(load_library().mgf_batch_copy_worlds_where(self._h, dw.ctypes.data, s._h, sw.ctypes.data, len(dw), _dev_arg(mask, "int32", 1, len(dw), "mask")))
 
     def counter(self, name):
         v = C.c_int64()

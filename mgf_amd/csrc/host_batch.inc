@@ -65,7 +65,15 @@ struct mgf_batch {
   QueryEvents q_tm;  // 0 | a query pass | 1
   int64_t q_launches = 0;
   float q_run_ms = 0.0f;
-  int64_t d_launches = 0;  // kernel launches of the last get / set / forces / impulses / copy call (host_batch_drive.inc)
+  int64_t d_launches = 0;  // kernel launches of the last get / set / forces / impulses / copy call (host_batch_drive.inc, host_batch_dev.inc)
+  // the device-pointer calls (host_batch_dev.inc)
+  bool ccount_stale = false;            // a masked copy has changed d_ccount behind h_ccount: batch_ccount_fresh before the next reader
+  DBuf<unsigned long long> v_skipped;   // records whose index was out of range, cumulative (counter "device_skipped")
+  DBuf<uint32_t> v_cnt, v_off, v_seg;   // the setters' records per body, their prefix sums, the segments
+  std::vector<uint2> w_pairs;           // mgf_batch_copy_worlds_where: the last call's pair table, as it is on the device in ...
+  DBuf<uint2> w_pairs_d;                // ... this; uploaded (from w_pairs, which stays) only when the arrays differ
+  bool w_pairs_up = false;
+  int64_t w_uploads = 0;                // counter "pair_table_uploads"
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {
@@ -109,6 +117,13 @@ static mgf_status batch_pull(mgf_batch* b) {
   b->dev_valid = false;
   return MGF_OK;
 }
+// h_ccount as the device has it, before a reader on the host: a masked copy (mgf_batch_copy_worlds_where) leaves it unknown
+static mgf_status batch_ccount_fresh(mgf_batch* b) {
+  if (!b->ccount_stale) return MGF_OK;
+  if (b->dev_valid) MGF_TRY(d2h(b->ctx, b->h_ccount.data(), b->d_ccount.p, b->K));
+  b->ccount_stale = false;
+  return MGF_OK;
+}
 // every world's share of the constraint storage; the lists of the last tick move along when `keep`
 static mgf_status batch_allot(mgf_batch* b, bool keep) {
   mgf_ctx* ctx = b->ctx;
@@ -135,6 +150,7 @@ static mgf_status batch_allot(mgf_batch* b, bool keep) {
     MGF_HIP_TRY(hipStreamSynchronize(s));
   } else {
     std::fill(b->h_ccount.begin(), b->h_ccount.end(), 0u);
+    b->ccount_stale = false;
     MGF_TRY(b->d_ccount.ensure(std::max<size_t>(b->K, 1), s));
     MGF_HIP_TRY(hipMemsetAsync(b->d_ccount.p, 0, 4 * (size_t)b->K, s));
   }
@@ -232,6 +248,13 @@ extern "C" mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, in
   if (!strcmp(name, "query_launches")) { *out = b->q_launches; return MGF_OK; }
   if (!strcmp(name, "query_run_ns")) { *out = (int64_t)((double)b->q_run_ms * 1e6); return MGF_OK; }
   if (!strcmp(name, "drive_launches")) { *out = b->d_launches; return MGF_OK; }
+  if (!strcmp(name, "pair_table_uploads")) { *out = b->w_uploads; return MGF_OK; }
+  if (!strcmp(name, "device_skipped")) {  // (on the device: the stream is waited for)
+    unsigned long long v = 0;
+    if (b->v_skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, b->v_skipped.p, 1)); }
+    *out = (int64_t)v;
+    return MGF_OK;
+  }
   return fail(MGF_ERR_INVALID, "unknown batch counter");
 }
 
@@ -520,6 +543,7 @@ extern "C" mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mg
   b->h_n[k] += (uint32_t)n;
   batch_offsets(b);
   std::fill(b->h_ccount.begin(), b->h_ccount.end(), 0u);
+  b->ccount_stale = false;
   return MGF_OK;
 }
 
@@ -656,6 +680,7 @@ extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int6
     MGF_TRY(batch_allot(b, true));
   }
   MGF_TRY(d2h(ctx, b->h_ccount.data(), b->d_ccount.p, K));
+  b->ccount_stale = false;
   if (stats) {
     std::vector<uint32_t> h((size_t)NT * K * 8);
     MGF_TRY(d2h(ctx, h.data(), b->d_stats.p, h.size()));
@@ -675,6 +700,7 @@ extern "C" mgf_status mgf_batch_read_constraints(mgf_batch* b, int64_t world, mg
   if (world < 0) return fail(MGF_ERR_INVALID, "world index out of range");
   MGF_TRY(ctx_bind(b->ctx));
   if (world >= (int64_t)b->K) return fail(MGF_ERR_INVALID, "world index out of range");
+  MGF_TRY(batch_ccount_fresh(b));
   const uint32_t C = b->dev_valid ? b->h_ccount[(size_t)world] : 0u;
   if (count) *count = C;
   if (!out) return MGF_OK;

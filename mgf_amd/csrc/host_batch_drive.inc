@@ -139,14 +139,14 @@ extern "C" mgf_status mgf_batch_apply_impulses(mgf_batch* b, const int32_t* worl
   return batch_drive_run<DRIVE_IMPULSE>(b, g, reinterpret_cast<const float*>(linear), reinterpret_cast<const float*>(angular), 3u);
 }
 
-extern "C" mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_world, const mgf_batch* src_in, const int32_t* src_world, int64_t n_in) {
-  if (!dst || !src_in) return fail(MGF_ERR_INVALID, "batch is NULL");
+// the refusals of a copy, none of which changes anything (mgf_batch_copy_worlds, mgf_batch_copy_worlds_where)
+static mgf_status batch_copy_check(mgf_batch* dst, const int32_t* dst_world, const mgf_batch* src, const int32_t* src_world, int64_t n_in) {
+  if (!dst || !src) return fail(MGF_ERR_INVALID, "batch is NULL");
   if (n_in < 0) return fail(MGF_ERR_INVALID, "n is negative");
   if (n_in > (int64_t)INT32_MAX) return fail(MGF_ERR_INVALID, "too many pairs in one call");
   if (n_in && (!dst_world || !src_world)) return fail(MGF_ERR_INVALID, "NULL argument");
   for (int64_t i = 0; i < n_in; ++i)
     if (dst_world[i] < 0 || src_world[i] < 0) return fail(MGF_ERR_INVALID, "world index out of range");
-  mgf_batch* src = const_cast<mgf_batch*>(src_in);  // (its mirror may have to go up, its colliders are read where they are: nothing of its state changes)
   if (dst->ctx != src->ctx) return fail(MGF_ERR_INVALID, "the two batches belong to different contexts");
   MGF_TRY(ctx_bind(dst->ctx));
   const size_t n = (size_t)n_in;
@@ -161,14 +161,15 @@ extern "C" mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_w
   if (dst == src)
     for (size_t i = 0; i < n; ++i)
       if (is_dst[(size_t)src_world[i]]) return fail(MGF_ERR_INVALID, "a world is both a source and a destination: nothing was copied");
-  dst->d_launches = 0;
-  if (n == 0) return MGF_OK;
+  return MGF_OK;
+}
+// Both batches on the device, and the lists must fit: a destination with a smaller share asks for what the source's list needs, as a tick
+// that did not fit does (the larger share stays, as after a re-run tick, until "cons_per_body" is set again; a failed allotment leaves
+// the floors as they were)
+static mgf_status batch_copy_open(mgf_batch* dst, const int32_t* dst_world, mgf_batch* src, const int32_t* src_world, size_t n) {
   MGF_TRY(batch_push(src));
   MGF_TRY(batch_push(dst));
-  mgf_ctx* ctx = dst->ctx;
-  hipStream_t s = ctx->stream;
-  // the lists must fit: a destination with a smaller share asks for what the source's list needs, as a tick that did not fit does
-  // (the larger share stays, as after a re-run tick, until "cons_per_body" is set again; a failed allotment leaves the floors as they were)
+  MGF_TRY(batch_ccount_fresh(src));  // (behind a masked copy into `src`, host_batch_dev.inc)
   bool grow = false;
   const std::vector<uint32_t> floor_was = dst->h_floor;
   for (size_t i = 0; i < n; ++i) {
@@ -180,19 +181,34 @@ extern "C" mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_w
     const mgf_status st = batch_allot(dst, true);
     if (st != MGF_OK) { dst->h_floor = floor_was; return st; }
   }
-  std::vector<uint2> pairs(n);
-  for (size_t i = 0; i < n; ++i) pairs[i] = make_uint2((uint32_t)dst_world[i], (uint32_t)src_world[i]);
-  MGF_TRY(dst->q_in.ensure((n + 1) / 2, s));
-  MGF_HIP_TRY(hipMemcpyAsync(dst->q_in.p, pairs.data(), 8 * n, hipMemcpyHostToDevice, s));
+  return MGF_OK;
+}
+static BatchCopyArgs batch_copy_args(const mgf_batch* dst, const mgf_batch* src, const uint2* pairs) {
   BatchCopyArgs A;
   memset(&A, 0, sizeof(A));
   A.D = dst->bodies(0); A.S = src->bodies(0);
-  A.pairs = reinterpret_cast<const uint2*>(dst->q_in.p);
+  A.pairs = pairs;
   A.d_off = dst->d_off.p; A.s_off = src->d_off.p;
   A.d_cons = dst->cons.p; A.s_cons = src->cons.p;
   A.d_coff = dst->d_coff.p; A.d_cap = dst->d_cap.p; A.s_coff = src->d_coff.p;
   A.d_count = dst->d_ccount.p; A.s_count = src->d_ccount.p;
   A.s_stale = src->cols_stale ? 1u : 0u;
+  return A;
+}
+
+extern "C" mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_world, const mgf_batch* src_in, const int32_t* src_world, int64_t n_in) {
+  MGF_TRY(batch_copy_check(dst, dst_world, src_in, src_world, n_in));
+  mgf_batch* src = const_cast<mgf_batch*>(src_in);  // (its mirror may have to go up, its colliders are read where they are: nothing of its state changes)
+  const size_t n = (size_t)n_in;
+  dst->d_launches = 0;
+  if (n == 0) return MGF_OK;
+  MGF_TRY(batch_copy_open(dst, dst_world, src, src_world, n));
+  hipStream_t s = dst->ctx->stream;
+  std::vector<uint2> pairs(n);
+  for (size_t i = 0; i < n; ++i) pairs[i] = make_uint2((uint32_t)dst_world[i], (uint32_t)src_world[i]);
+  MGF_TRY(dst->q_in.ensure((n + 1) / 2, s));
+  MGF_HIP_TRY(hipMemcpyAsync(dst->q_in.p, pairs.data(), 8 * n, hipMemcpyHostToDevice, s));
+  const BatchCopyArgs A = batch_copy_args(dst, src, reinterpret_cast<const uint2*>(dst->q_in.p));
   k_batch_drive_copy<<<(unsigned)n, kBatchBlock, 0, s>>>(A);
   LAUNCH_CHECK();
   ++dst->d_launches;

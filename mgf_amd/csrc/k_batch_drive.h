@@ -49,39 +49,44 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_drive_get(BatchDriveArgs 
   o[6] = make_float4(p1.x, p1.y, p1.z, 0.0f);
 }
 
-template <int MODE>
-__global__ __launch_bounds__(kBatchBlock) void k_batch_drive_set(BatchDriveArgs A) {
-  const uint32_t r = blockIdx.x * kBatchBlock + threadIdx.x;
-  if (r >= A.n) return;
-  const Bodies& B = A.B;
-  const size_t g = A.gidx[r];
-  const uint32_t lo = A.run[r], hi = A.run[r + 1];
+// What one lane does for body g once it knows its records: the positions [lo, hi) of `order` hold their indices in the caller's order
+// (IDENT: position p is record p itself, no table).  Shared by k_batch_drive_set and the device-pointer calls (k_batch_dev.h).
+template <int MODE, bool IDENT>
+__device__ __forceinline__ void batch_drive_apply(const Bodies& B, size_t g, const uint32_t* order, uint32_t lo, uint32_t hi, const float* a0, const float* a1,
+                                                  uint32_t stride) {
   if (MODE == DRIVE_IMPULSE) {
     const float4 s0 = B.srec[4 * g], s1 = B.srec[4 * g + 1], s2 = B.srec[4 * g + 2], s3 = B.srec[4 * g + 3];
     V3 v = mk3(s0.x, s0.y, s0.z), w = mk3(s0.w, s1.x, s1.y);
     const float inv_mass = s1.z;
     const M3 I = m3_cols(mk3(s1.w, s2.x, s2.y), mk3(s2.z, s2.w, s3.x), mk3(s3.y, s3.z, s3.w));
     for (uint32_t p = lo; p < hi; ++p) {
-      const size_t k = A.order[p];
-      const V3 lin = A.a0 ? ld3(A.a0 + A.stride * k) : mk3(0.0f, 0.0f, 0.0f);
-      const V3 ang = A.a1 ? ld3(A.a1 + A.stride * k) : mk3(0.0f, 0.0f, 0.0f);
+      const size_t k = IDENT ? p : order[p];
+      const V3 lin = a0 ? ld3(a0 + stride * k) : mk3(0.0f, 0.0f, 0.0f);
+      const V3 ang = a1 ? ld3(a1 + stride * k) : mk3(0.0f, 0.0f, 0.0f);
       v = v + lin * inv_mass;
       w = w + I * ang;
     }
     B.srec[4 * g] = make_float4(v.x, v.y, v.z, w.x);
     B.srec[4 * g + 1] = make_float4(w.y, w.z, s1.z, s1.w);
   } else {
-    const size_t k = A.order[hi - 1u];  // (a run is never empty)
+    const size_t k = IDENT ? hi - 1u : order[hi - 1u];  // (a run is never empty)
     if (MODE == DRIVE_VEL) {
-      const V3 lin = ld3(A.a0 + A.stride * k), ang = ld3(A.a1 + A.stride * k);
+      const V3 lin = ld3(a0 + stride * k), ang = ld3(a1 + stride * k);
       const float4 s1 = B.srec[4 * g + 1];
       B.srec[4 * g] = make_float4(lin.x, lin.y, lin.z, ang.x);
       B.srec[4 * g + 1] = make_float4(ang.y, ang.z, s1.z, s1.w);
     } else {
-      if (A.a0) { const V3 f = ld3(A.a0 + A.stride * k); B.sp0[g] = mk4(f, B.sp0[g].w); }
-      if (A.a1) { const V3 t = ld3(A.a1 + A.stride * k); B.sp1[g] = mk4(t, B.sp1[g].w); }
+      if (a0) { const V3 f = ld3(a0 + stride * k); B.sp0[g] = mk4(f, B.sp0[g].w); }
+      if (a1) { const V3 t = ld3(a1 + stride * k); B.sp1[g] = mk4(t, B.sp1[g].w); }
     }
   }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kBatchBlock) void k_batch_drive_set(BatchDriveArgs A) {
+  const uint32_t r = blockIdx.x * kBatchBlock + threadIdx.x;
+  if (r >= A.n) return;
+  batch_drive_apply<MODE, false>(A.B, A.gidx[r], A.order, A.run[r], A.run[r + 1], A.a0, A.a1, A.stride);
 }
 
 struct BatchCopyArgs {
@@ -103,8 +108,8 @@ __device__ __forceinline__ void batch_copy_words(float4* d, const float4* s, uin
   for (uint32_t e = threadIdx.x; e < words; e += kBatchBlock) d[e] = s[e];
 }
 
-__global__ __launch_bounds__(kBatchBlock) void k_batch_drive_copy(BatchCopyArgs A) {
-  const uint2 pr = A.pairs[blockIdx.x];
+// one pair by its workgroup (k_batch_drive_copy; k_batch_dev_copy_where, k_batch_dev.h, for the pairs its mask selects)
+__device__ __forceinline__ void batch_copy_pair(const BatchCopyArgs& A, const uint2 pr) {
   const size_t gd = A.d_off[pr.x], gs = A.s_off[pr.y];
   const uint32_t n = min(A.d_off[pr.x + 1] - A.d_off[pr.x], A.s_off[pr.y + 1] - A.s_off[pr.y]);
   const Bodies &D = A.D, &S = A.S;
@@ -133,5 +138,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_drive_copy(BatchCopyArgs 
   batch_copy_words(reinterpret_cast<float4*>(A.d_cons + A.d_coff[pr.x]), reinterpret_cast<const float4*>(A.s_cons + A.s_coff[pr.y]), 8u * C);
   if (threadIdx.x == 0) A.d_count[pr.x] = C;
 }
+
+__global__ __launch_bounds__(kBatchBlock) void k_batch_drive_copy(BatchCopyArgs A) { batch_copy_pair(A, A.pairs[blockIdx.x]); }
 
 }  // namespace mgf

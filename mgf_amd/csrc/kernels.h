@@ -90,6 +90,12 @@
 //                      of (world, body) records (mgf_batch_get_many / _set_many / _set_forces / _apply_impulses: a lane per body the call
 //                      names, its records in the caller's order from the host's stable sort) and world-to-world copies
 //                      (mgf_batch_copy_worlds: a workgroup per pair, rows, packed copy, colliders and the constraint list in 16-byte words)
+//   k_batch_dev_gather / _count / _fill / _apply<MODE, SEG> / _copy_where (k_batch_dev.h)
+//                      the same for a caller whose arrays are device memory (mgf_batch_gather_state_dev / _set_many_dev / _set_forces_dev /
+//                      _apply_impulses_dev / _copy_worlds_where): bodies by their flat index, every index checked on the device, records
+//                      that name a body twice put in order per body on the device (counts by integer atomics, the library's prefix sum,
+//                      a lane per body sorts its segment) and applied by k_batch_drive_set's own apply step; the copy of the pairs a
+//                      device mask selects
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -108,3 +114,4 @@
 #include "k_batch_query.h"  // the queries of k_query.h for the worlds of a batch (k_batch_query_*)
 #include "k_batch_observe.h"  // per-body contact summaries and box overlaps of a batch (k_batch_observe_*)
 #include "k_batch_drive.h"  // get / set, forces, impulses and world copies of a batch (k_batch_drive_*)
+#include "k_batch_dev.h"  // the same from and into the caller's device memory (k_batch_dev_*)

@@ -81,6 +81,13 @@ extern "C" mgf_status mgf_ctx_set_stream(mgf_ctx* ctx, void* stream) {
   ctx->own_stream = false;
   return MGF_OK;
 }
+extern "C" mgf_status mgf_ctx_synchronize(mgf_ctx* ctx) {
+  if (!ctx) return fail(MGF_ERR_INVALID, "ctx is NULL");
+  if (ctx->closed) return fail(MGF_ERR_INVALID, "the context was destroyed (mgf_ctx_destroy): its handles can only be freed");
+  MGF_HIP_TRY(hipSetDevice(ctx->device));
+  MGF_HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return MGF_OK;
+}
 static void ctx_retain(mgf_ctx* ctx) { if (ctx) ++ctx->refs; }
 static void ctx_release(mgf_ctx* ctx) {
   if (!ctx || --ctx->refs > 0) return;
@@ -159,3 +166,4 @@ extern "C" mgf_status mgf_exclusive_scan_u32(mgf_ctx* ctx, const uint32_t* in, i
 #include "host_batch_query.inc"
 #include "host_batch_observe.inc"
 #include "host_batch_drive.inc"
+#include "host_batch_dev.inc"
