@@ -778,10 +778,17 @@ MGF_API mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_worl
  *                                                  fill is the library's and is not counted, as for mgf_batch_overlap_aabb_many)
  *   mgf_batch_copy_worlds_where                    1, and 1 more when shares grow (as mgf_batch_copy_worlds)
  *   mgf_batch_read_body_contacts_dev               1 ("query_launches", as mgf_batch_read_body_contacts)
- * OUT OF SCOPE here: device-pointer rays, sweeps and box queries (their sort by world is on the host); a step without its one host wait
- * per call (the capacity re-runs need it); hipGraph capture of these calls; anything for the lone mgf_world (it has
+ *   mgf_batch_raycast_many_dev / _sweep_many_dev   "query_launches": the collider gather behind a step (1, once), then with world_dev
+ *                                                  given MGF_BATCH_DEV_QUERY_PLAN_LAUNCHES = 3 (count, cut, fill; the two prefix sums
+ *                                                  between cut and fill are the library's and are not counted), with world_dev == NULL
+ *                                                  0; then the passes of the host-memory call: bodies 1, a sweep's faces 1 where the
+ *                                                  mask asks for terrain and a world has one, obstacles 1 where the mask asks for them
+ *                                                  and a world has one
+ * OUT OF SCOPE here: device-pointer box queries (their CSR total needs a host wait); rays given in a body's frame; a step without its
+ * one host wait per call (the capacity re-runs need it); hipGraph capture of these calls; anything for the lone mgf_world (it has
  * mgf_world_export_bodies / _import_ghosts / _device_ptr). */
 #define MGF_BATCH_DEV_SET_LAUNCHES 3
+#define MGF_BATCH_DEV_QUERY_PLAN_LAUNCHES 3
 /* Tightly packed rows for record i: 3 floats, 4 for q (s, x, y, z: mgf_quat).  Any output may be NULL.  x, v, omega, force, torque
  * equal mgf_batch_get_many's for the same bodies bit for bit (x is x + delta, physics.rs:282), q equals mgf_batch_read_state's. */
 MGF_API mgf_status mgf_batch_gather_state_dev(mgf_batch* b, const int32_t* body_dev, int64_t n,
@@ -808,6 +815,29 @@ MGF_API mgf_status mgf_batch_read_body_contacts_dev(mgf_batch* b, int64_t world,
  * dst first fetch the lengths of dst's lists from the device (one wait); mgf_batch_step does that anyway. */
 MGF_API mgf_status mgf_batch_copy_worlds_where(mgf_batch* dst, const int32_t* dst_world, const mgf_batch* src, const int32_t* src_world,
                                                int64_t n, const int32_t* mask_dev);
+/* Of a batch's rays, sweeps and box queries the first two have a device-pointer form, the observations a policy reads every tick.
+ * mgf_batch_raycast_many / mgf_batch_sweep_many with every array in device memory: out_dev[i] is, bit for bit, what the host-memory
+ * call writes to out[i] for the same query, world, ignore entry and mask on the same batch at the same moment - every kind bit, terrain
+ * table, obstacle list and "the collider a query sees" (above).  Nothing of the tick's state is written.  Enqueued on the context's
+ * stream, not waited for; in the steady state - the batch on the device, the terrain and obstacle tables unchanged, the handle's scratch
+ * large enough - no host wait and no copy between host and device.  No HIP events: "query_run_ns" is 0.
+ * The sort by world is built on the device (ranks within a world by integer atomics, the library's prefix sums, work items of up to 256
+ * queries).  The order of a world's queries inside a work item then depends on lane scheduling; no answer depends on that order, and
+ * every answer is stored by the caller's index.  No float atomic.
+ * world_dev == NULL is the fixed sensor layout: n must be a multiple of n_worlds (else MGF_ERR_INVALID), query i belongs to world
+ * i / (n / n_worlds); no sort, no plan, nothing uploaded.
+ * Checked on the device, before the index reads anything: a record whose world_dev[i] lies outside [0, n_worlds) - for a cast also one
+ * whose tag is neither 0 nor 1 - is skipped whole: matched against nothing, out_dev[i] = the no-hit record (kind MGF_HIT_NONE, every
+ * other word zero), counted in "device_skipped".  ignore_body_dev[i] (NULL: none) is only ever compared with a body index: a value that
+ * is no body of that world ignores nothing.
+ * Refused with MGF_ERR_INVALID, nothing enqueued: a NULL batch, a negative n or n > INT32_MAX, NULL parts_dev / casts_dev / out_dev with
+ * n > 0, a mask of 0 or with bits beyond MGF_QUERY_ALL, a pointer that fails the look-up above (world_dev and ignore_body_dev 4 n bytes,
+ * parts_dev 28 n, casts_dev 44 n, out_dev 28 n / 52 n), and out_dev's bytes overlapping those of an input array (a later pass reads the
+ * queries again after an earlier one wrote hits).  The caller's arrays must not change until the call has run. */
+MGF_API mgf_status mgf_batch_raycast_many_dev(mgf_batch* b, const int32_t* world_dev, const mgf_particle* parts_dev, int64_t n,
+                                              const int32_t* ignore_body_dev, int32_t kinds_mask, mgf_ray_hit* out_dev);
+MGF_API mgf_status mgf_batch_sweep_many_dev(mgf_batch* b, const int32_t* world_dev, const mgf_moving_component* casts_dev, int64_t n,
+                                            const int32_t* ignore_body_dev, int32_t kinds_mask, mgf_sweep_hit* out_dev);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /

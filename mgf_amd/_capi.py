@@ -120,6 +120,7 @@ HIT_NONE, HIT_BODY, HIT_TERRAIN, HIT_OBSTACLE = -1, 0, 1, 2
 BATCH_MAX_BODIES = 1024  # MGF_BATCH_MAX_BODIES
 BATCH_MAX_WORLD_OBSTACLES = 64  # MGF_BATCH_MAX_WORLD_OBSTACLES
 BATCH_DEV_SET_LAUNCHES = 3  # MGF_BATCH_DEV_SET_LAUNCHES
+BATCH_DEV_QUERY_PLAN_LAUNCHES = 3  # MGF_BATCH_DEV_QUERY_PLAN_LAUNCHES
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -158,7 +159,7 @@ SYMBOLS = [
     "mgf_batch_get_many", "mgf_batch_set_many", "mgf_batch_set_forces", "mgf_batch_apply_impulses", "mgf_batch_copy_worlds",
     "mgf_batch_add_obstacle", "mgf_batch_set_world_obstacles", "mgf_batch_obstacle_count", "mgf_batch_world_obstacle_count",
     "mgf_ctx_synchronize", "mgf_batch_gather_state_dev", "mgf_batch_set_many_dev", "mgf_batch_set_forces_dev", "mgf_batch_apply_impulses_dev",
-    "mgf_batch_read_body_contacts_dev", "mgf_batch_copy_worlds_where",
+    "mgf_batch_read_body_contacts_dev", "mgf_batch_copy_worlds_where", "mgf_batch_raycast_many_dev", "mgf_batch_sweep_many_dev",
 ]
 
 _lib = None
@@ -325,6 +326,8 @@ def load_library():
         "mgf_batch_set_forces_dev": (i32, [vp, vp, i64, vp, vp]),
         "mgf_batch_apply_impulses_dev": (i32, [vp, vp, i64, vp, vp]),
         "mgf_batch_read_body_contacts_dev": (i32, [vp, i64, vp, i64]),
+        "mgf_batch_raycast_many_dev": (i32, [vp, vp, vp, i64, vp, i32, vp]),
+        "mgf_batch_sweep_many_dev": (i32, [vp, vp, vp, i64, vp, i32, vp]),
         "mgf_batch_copy_worlds_where": (i32, [vp, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
@@ -1589,6 +1592,39 @@ class WorldBatch:
         if mask is None:
             raise ValueError("mask is required")
         _check(load_library().mgf_batch_copy_worlds_where(self._h, dw.ctypes.data, s._h, sw.ctypes.data, len(dw), _dev_arg(mask, "int32", 1, len(dw), "mask")))
+
+    def _dev_queries(self, world, q, q_cols, q_words, out, out_cols, ignore, n):
+        """(world, queries, n, ignore, out) of a device-pointer query: addresses, None where the call takes NULL"""
+        if q is None or out is None:
+            raise ValueError("the queries and out are both required")
+        if n is None:
+            if not hasattr(q, "data_ptr") or q.dim() != 2:
+                raise ValueError("n must be given with a raw address")
+            n = int(q.shape[0])
+        n = int(n)
+        if world is None and n % self.n_worlds:
+            raise ValueError("without world indices n is a multiple of the number of worlds")
+        return (_dev_arg(world, "int32", 1, n, "world"), _dev_arg(q, q_words, q_cols, n, "queries"), n,
+                _dev_arg(ignore, "int32", 1, n, "ignore"), _dev_arg(out, "int32", out_cols, n, "out"))
+
+    def raycast_dev(self, world, parts, out, ignore=None, kinds=QUERY_ALL, n=None):
+        """raycast with every array in device memory (mgf_batch_raycast_many_dev), enqueued on the context's stream and not waited for.
+        world: CUDA int32 [n], the world of each particle - None: the fixed layout, n a multiple of n_worlds and particle i belongs
+        to world i // (n // n_worlds).  parts: CUDA float32 [n, 7], a row (p.xyz, d.xyz, dt).  ignore: CUDA int32 [n] or None.
+        out: CUDA int32 [n, 7], RAY_HIT_DTYPE's words - columns 0:3 are kind, index, part; view columns 3:7 (p.xyz, t) as float32
+        (out[:, 3:].view(torch.float32)).  A particle whose world is out of range gets kind -1, the rest zero ("device_skipped")."""
+        wp, qp, n, ip, op = self._dev_queries(world, parts, 7, "float32", out, 7, ignore, n)
+        _check(load_library().mgf_batch_raycast_many_dev(self._h, wp, qp, n, ip, int(kinds), op))
+
+    def sweep_dev(self, world, casts, out, ignore=None, kinds=QUERY_ALL, n=None):
+        """sweep with every array in device memory (mgf_batch_sweep_many_dev), not waited for; world, ignore as for raycast_dev.
+        casts: CUDA [n, 11], float32 or int32, MOVING_DTYPE's words (tag, p.xyz, d.xyz, r, delta.xyz): word 0 holds the tag's BITS - the
+        integer 0 (sphere) or 1 (capsule), which in a float32 tensor is written through casts[:, 0].view(torch.int32).
+        out: CUDA int32 [n, 13], SWEEP_HIT_DTYPE's words - columns 0:3 are kind, index, part; view columns 3:13 (a.xyz, b.xyz, n.xyz, t)
+        as float32.  A cast whose world is out of range or whose tag is neither 0 nor 1 gets kind -1, the rest zero."""
+        words = "int32" if str(getattr(casts, "dtype", "")) == "torch.int32" else "float32"
+        wp, qp, n, ip, op = self._dev_queries(world, casts, 11, words, out, 13, ignore, n)
+        _check(load_library().mgf_batch_sweep_many_dev(self._h, wp, qp, n, ip, int(kinds), op))
 
     def counter(self, name):
         v = C.c_int64()

@@ -74,6 +74,11 @@ struct mgf_batch {
   DBuf<uint2> w_pairs_d;                // ... this; uploaded (from w_pairs, which stays) only when the arrays differ
   bool w_pairs_up = false;
   int64_t w_uploads = 0;                // counter "pair_table_uploads"
+  // the device-pointer queries (host_batch_query_dev.inc): the plan BatchQueryPlan builds on the host, built on the device
+  DBuf<uint32_t> p_cnt, p_off;          // [2 (K + 1)] queries | work items per world; their prefix sums
+  DBuf<int32_t> p_world;                // [n] the call's own copy of the worlds, -1: a skipped record
+  DBuf<uint32_t> p_rank, p_order;       // [n] a query's rank within its world; sorted position -> the caller's index
+  DBuf<uint4> p_items;                  // the work items
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {

@@ -144,15 +144,15 @@ static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* q
     LAUNCH_CHECK();
     ++b->q_launches;
     if (faces) {
-      k_batch_query_sweep_faces<<<(unsigned)((n + kBatchBlock - 1) / kBatchBlock), kBatchBlock, 0, s>>>(A.T, U.world, dq, (uint32_t)n, A.out);
+      k_batch_query_sweep_faces<<<(unsigned)((n + kBatchBlock - 1) / kBatchBlock), kBatchBlock, 0, s>>>(A.T, U.world, 0u, dq, (uint32_t)n, A.out);
       LAUNCH_CHECK();
       ++b->q_launches;
     }
   }
   if (obstacles) {
     const unsigned nb = (unsigned)((n + kBatchBlock - 1) / kBatchBlock);
-    if constexpr (kRays) k_batch_query_ray_obstacles<<<nb, kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, U.world, dq, (uint32_t)n, A.out);
-    else k_batch_query_sweep_obstacles<<<nb, kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, U.world, dq, (uint32_t)n, A.out);
+    if constexpr (kRays) k_batch_query_ray_obstacles<<<nb, kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, U.world, 0u, dq, (uint32_t)n, A.out);
+    else k_batch_query_sweep_obstacles<<<nb, kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, U.world, 0u, dq, (uint32_t)n, A.out);
     LAUNCH_CHECK();
     ++b->q_launches;
   }

@@ -24,6 +24,11 @@
 // here are the work split (BatchWork), the staging, the cheap rejects and the reduction over a query's lanes (bq_reduce).
 // The order is total and every reject is conservative, so neither the number of lanes a query gets, nor the other queries of its work
 // item, nor the split into launches changes a bit of an answer.  No workgroup waits for another.
+// The two kernels with a workgroup per work item are bq_ray_item<SRC> / bq_sweep_item<SRC> behind a kernel's signature: SRC says where
+// the work item comes from - the host's table here (kItemTable), the device-built table or arithmetic on blockIdx.x for the
+// device-pointer calls (kItemPlan, kItemFixed: k_batch_query_dev.h).  The three lane-per-query passes take the world of query i from
+// world[i], or (world == null: every world has `per` queries) as i / per, and leave at once for a negative world - a record the
+// device-pointer calls skip - and for a cast whose tag is no component's; the host-memory calls refuse both before anything runs.
 #pragma once
 #include "k_batch.h"
 #include "k_query.h"
@@ -44,6 +49,22 @@ struct BatchQueryArgs : BatchWorkArgs {
   int32_t mask;
   int32_t* out;           // by the caller's index: 7 words a particle (mgf_ray_hit), 13 a cast (mgf_sweep_hit)
 };
+
+// Where a workgroup's work item comes from: items[blockIdx.x] as the host wrote it; items[blockIdx.x] of a table built on the device,
+// whose length only the device knows (*n_items; the grid is an upper bound); or no table: every world has `per` queries, world k's at
+// [k * per, (k + 1) * per) in the caller's order, cut into ceil(per / 256) work items.
+enum : int { kItemTable = 0, kItemPlan = 1, kItemFixed = 2 };
+struct BatchItemSrc {
+  const uint32_t* n_items;      // kItemPlan: the work items of the call
+  uint32_t per;                 // kItemFixed: queries a world (> 0)
+  unsigned long long* skipped;  // kItemFixed: casts skipped for their tag, cumulative (the plan counts them itself)
+};
+template <int SRC>
+__device__ __forceinline__ uint4 bq_item(const BatchWorkArgs& A, const BatchItemSrc& S) {
+  if (SRC != kItemFixed) return A.items[blockIdx.x];
+  const uint32_t cuts = (S.per + 255u) >> 8, k = blockIdx.x / cuts, f = (blockIdx.x - k * cuts) << 8;
+  return make_uint4(k, k * S.per + f, min(256u, S.per - f), 0u);
+}
 
 constexpr uint32_t kBatchQueryRed = 16;  // float4 words behind the staged bodies: four a wave for the reduction across waves
 
@@ -93,16 +114,19 @@ struct BatchWork {
   uint32_t g0, n;
   uint32_t L, sub, qi;
   bool live;
-  __device__ __forceinline__ BatchWork(const BatchWorkArgs& A, bool bodies) : it(A.items[blockIdx.x]), g0(A.w_off[it.x]) {
+  __device__ __forceinline__ BatchWork(const BatchWorkArgs& A, bool bodies, uint4 item) : it(item), g0(A.w_off[it.x]) {
     n = bodies ? A.w_off[it.x + 1] - g0 : 0u;
   }
+  __device__ __forceinline__ BatchWork(const BatchWorkArgs& A, bool bodies) : BatchWork(A, bodies, A.items[blockIdx.x]) {}
   // sh: the lanes a query gets, as a shift - shift(), or less
   __device__ __forceinline__ uint32_t shift() const { return bq_lane_shift(it.z); }
+  // IDENTITY: sorted position = the caller's index (kItemFixed: there is no order array)
+  template <bool IDENTITY = false>
   __device__ __forceinline__ void split(const BatchWorkArgs& A, uint32_t sh) {
     const uint32_t j = threadIdx.x >> sh;
     L = 1u << sh; sub = threadIdx.x & (L - 1u);
     live = j < it.z;
-    qi = live ? A.order[it.y + j] : 0u;
+    qi = !live ? 0u : IDENTITY ? it.y + j : A.order[it.y + j];
   }
 };
 
@@ -141,14 +165,16 @@ __device__ __forceinline__ bool bq_ray_far(float4 a, float4 b, V3 p, V3 d, float
   return dot(e, e) > lim * lim + 1e-4f * dot(w, w);
 }
 
-// LDS (dynamic): 32 bytes a body, kBatchQueryRed words.
-__global__ __launch_bounds__(kBatchBlock) void k_batch_query_ray(BatchQueryArgs A, const ParticleIn* parts) {
-  extern __shared__ float4 s_dyn[];
-  BatchWork W(A, A.mask & MGF_QUERY_BODIES);
+// A workgroup's work item of rays.  kItemPlan: a workgroup at or beyond the device's item total has none - it leaves, the whole of it,
+// before anything is staged and ahead of the first __syncthreads.
+template <int SRC>
+__device__ __forceinline__ void bq_ray_item(const BatchQueryArgs& A, const ParticleIn* parts, const BatchItemSrc& S, float4* s_dyn) {
+  if (SRC == kItemPlan && blockIdx.x >= *S.n_items) return;
+  BatchWork W(A, A.mask & MGF_QUERY_BODIES, bq_item<SRC>(A, S));
   const uint32_t n = W.n;
   float4 *s_c0 = s_dyn, *s_c1 = s_dyn + n, *s_red = s_dyn + 2 * (size_t)n;
   bq_stage(A, W.g0, n, s_c0, s_c1);
-  W.split(A, W.shift());
+  W.template split<SRC == kItemFixed>(A, W.shift());
   const uint32_t qi = W.qi;
   V3 p = mk3(0.0f, 0.0f, 0.0f), d = p;
   float dt = 0.0f;
@@ -179,6 +205,11 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_query_ray(BatchQueryArgs 
   }
   q_ray_store(A.out + 7 * (size_t)qi, best);
 }
+// LDS (dynamic): 32 bytes a body, kBatchQueryRed words.
+__global__ __launch_bounds__(kBatchBlock) void k_batch_query_ray(BatchQueryArgs A, const ParticleIn* parts) {
+  extern __shared__ float4 s_dyn[];
+  bq_ray_item<kItemTable>(A, parts, BatchItemSrc(), s_dyn);
+}
 
 // q_sweep_cast without a grid: the reject's pad keeps its millimetre and the rounding of the path
 __device__ __forceinline__ SweepCast bq_sweep_cast(const MovingIn& m) {
@@ -187,17 +218,24 @@ __device__ __forceinline__ SweepCast bq_sweep_cast(const MovingIn& m) {
   return q_sweep_cast(m, G);
 }
 
-// LDS (dynamic): 32 bytes a body, kBatchQueryRed words.
-__global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_bodies(BatchQueryArgs A, const MovingIn* casts) {
-  extern __shared__ float4 s_dyn[];
-  BatchWork W(A, A.mask & MGF_QUERY_BODIES);
+// A workgroup's work item of casts (bq_ray_item's remarks).  kItemFixed: no plan has looked at the casts - one whose tag is no
+// component's is matched against nothing, keeps the no-hit record and is counted by the first of its lanes.
+template <int SRC>
+__device__ __forceinline__ void bq_sweep_item(const BatchQueryArgs& A, const MovingIn* casts, const BatchItemSrc& S, float4* s_dyn) {
+  if (SRC == kItemPlan && blockIdx.x >= *S.n_items) return;
+  BatchWork W(A, A.mask & MGF_QUERY_BODIES, bq_item<SRC>(A, S));
   const uint32_t n = W.n;
   float4 *s_c0 = s_dyn, *s_c1 = s_dyn + n, *s_red = s_dyn + 2 * (size_t)n;
   bq_stage(A, W.g0, n, s_c0, s_c1);
-  W.split(A, W.shift());
+  W.template split<SRC == kItemFixed>(A, W.shift());
   const uint32_t qi = W.qi;
   SweepBest best;
-  if (W.live && n) {
+  bool ok = W.live;
+  if (SRC == kItemFixed && ok && (uint32_t)casts[qi].tag > (uint32_t)KIND_CAPSULE) {
+    ok = false;
+    if (W.sub == 0u) atomicAdd(S.skipped, 1ull);
+  }
+  if (ok && n) {
     const SweepCast K = bq_sweep_cast(casts[qi]);
     const int32_t ign = A.ignore ? A.ignore[qi] : -1;
     for (uint32_t i = W.sub; i < n; i += W.L) {
@@ -212,14 +250,26 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_bodies(BatchQ
   if (W.sub != 0u || !W.live) return;
   q_sweep_store(A.out + 13 * (size_t)qi, best);
 }
+// LDS (dynamic): 32 bytes a body, kBatchQueryRed words.
+__global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_bodies(BatchQueryArgs A, const MovingIn* casts) {
+  extern __shared__ float4 s_dyn[];
+  bq_sweep_item<kItemTable>(A, casts, BatchItemSrc(), s_dyn);
+}
+
+// the world of query i for a lane-per-query pass; negative: the record is skipped
+__device__ __forceinline__ int32_t bq_lane_world(const int32_t* world, uint32_t per, uint32_t i) { return world ? world[i] : (int32_t)(i / per); }
 
 // q_sweep_terrain's tests over the threaded tree, a lane per cast in the caller's order, each over the terrain of its own cast's world
-// (world[i]; the walk is per lane as it is)
-__global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_faces(BatchTerrains T, const int32_t* world, const MovingIn* casts, uint32_t n, int32_t* out) {
+// (bq_lane_world; the walk is per lane as it is)
+__global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_faces(BatchTerrains T, const int32_t* world, uint32_t per, const MovingIn* casts, uint32_t n,
+                                                                          int32_t* out) {
   const uint32_t i = blockIdx.x * kBatchBlock + threadIdx.x;
   if (i >= n) return;
-  const BatchTerrain M = batch_terrain_of(T, (uint32_t)world[i]);
+  const int32_t w = bq_lane_world(world, per, i);
+  if (w < 0) return;
+  const BatchTerrain M = batch_terrain_of(T, (uint32_t)w);
   if (M.n_nodes == 0u) return;
+  if ((uint32_t)casts[i].tag > (uint32_t)KIND_CAPSULE) return;
   const SweepCast K = bq_sweep_cast(casts[i]);
   int32_t* o = out + 13 * (size_t)i;
   SweepBest best = q_sweep_load(o);  // k_batch_query_sweep_bodies' answer
@@ -234,13 +284,15 @@ __device__ __forceinline__ QueryBest q_ray_load(const int32_t* o) {
   return best;
 }
 
-// The obstacles of every query's own world (world[i]), a lane per query in the caller's order: `index` of a hit is the obstacle's place
+// The obstacles of every query's own world (bq_lane_world), a lane per query in the caller's order: `index` of a hit is the obstacle's place
 // in the world's list, `part` the component.
-__global__ __launch_bounds__(kBatchBlock) void k_batch_query_ray_obstacles(BatchObstacles O, const uint4* tdesc, const int32_t* world, const ParticleIn* parts, uint32_t n,
-                                                                            int32_t* out) {
+__global__ __launch_bounds__(kBatchBlock) void k_batch_query_ray_obstacles(BatchObstacles O, const uint4* tdesc, const int32_t* world, uint32_t per,
+                                                                            const ParticleIn* parts, uint32_t n, int32_t* out) {
   const uint32_t i = blockIdx.x * kBatchBlock + threadIdx.x;
   if (i >= n) return;
-  const uint32_t obst = tdesc[2 * (size_t)world[i] + 1].w, ob0 = batch_obst_first(obst), ob1 = ob0 + batch_obst_count(obst);
+  const int32_t w = bq_lane_world(world, per, i);
+  if (w < 0) return;
+  const uint32_t obst = tdesc[2 * (size_t)w + 1].w, ob0 = batch_obst_first(obst), ob1 = ob0 + batch_obst_count(obst);
   if (ob0 == ob1) return;
   const ParticleIn q = parts[i];
   if (q.d[0] == 0.0f && q.d[1] == 0.0f && q.d[2] == 0.0f) return;  // (no direction: no hit, by definition - k_query_ray)
@@ -250,12 +302,15 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_query_ray_obstacles(Batch
   for (uint32_t e = ob0; e < ob1; ++e) q_ray_obstacle(batch_obstacle_of(O, e), e - ob0, q, nullptr, best);
   q_ray_store(o, best);
 }
-__global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_obstacles(BatchObstacles O, const uint4* tdesc, const int32_t* world, const MovingIn* casts, uint32_t n,
-                                                                              int32_t* out) {
+__global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_obstacles(BatchObstacles O, const uint4* tdesc, const int32_t* world, uint32_t per,
+                                                                              const MovingIn* casts, uint32_t n, int32_t* out) {
   const uint32_t i = blockIdx.x * kBatchBlock + threadIdx.x;
   if (i >= n) return;
-  const uint32_t obst = tdesc[2 * (size_t)world[i] + 1].w, ob0 = batch_obst_first(obst), ob1 = ob0 + batch_obst_count(obst);
+  const int32_t w = bq_lane_world(world, per, i);
+  if (w < 0) return;
+  const uint32_t obst = tdesc[2 * (size_t)w + 1].w, ob0 = batch_obst_first(obst), ob1 = ob0 + batch_obst_count(obst);
   if (ob0 == ob1) return;
+  if ((uint32_t)casts[i].tag > (uint32_t)KIND_CAPSULE) return;
   const SweepCast K = bq_sweep_cast(casts[i]);
   int32_t* o = out + 13 * (size_t)i;
   SweepBest best = q_sweep_load(o);  // k_batch_query_sweep_bodies' (and _faces') answer

@@ -96,6 +96,11 @@
 //                      that name a body twice put in order per body on the device (counts by integer atomics, the library's prefix sum,
 //                      a lane per body sorts its segment) and applied by k_batch_drive_set's own apply step; the copy of the pairs a
 //                      device mask selects
+//   k_batch_query_plan_count<WORDS> / _plan_cut / _plan_fill, k_batch_query_ray_dev<SRC> / _sweep_bodies_dev<SRC> (k_batch_query_dev.h)
+//                      ray casts and sweeps for a caller whose queries and hits are device memory (mgf_batch_raycast_many_dev /
+//                      _sweep_many_dev): the sort by world built on the device (ranks by integer atomics, the library's prefix sums,
+//                      work items of up to 256 queries), every world index and tag checked there; then k_batch_query.h's own code
+//                      with the work item from that table, or - a fixed number of queries a world - from blockIdx.x by arithmetic
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -115,3 +120,4 @@
 #include "k_batch_observe.h"  // per-body contact summaries and box overlaps of a batch (k_batch_observe_*)
 #include "k_batch_drive.h"  // get / set, forces, impulses and world copies of a batch (k_batch_drive_*)
 #include "k_batch_dev.h"  // the same from and into the caller's device memory (k_batch_dev_*)
+#include "k_batch_query_dev.h"  // ray casts and sweeps from and into the caller's device memory (k_batch_query_plan_*, k_batch_query_*_dev)
