@@ -784,7 +784,11 @@ MGF_API mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_worl
  *                                                  0; then the passes of the host-memory call: bodies 1, a sweep's faces 1 where the
  *                                                  mask asks for terrain and a world has one, obstacles 1 where the mask asks for them
  *                                                  and a world has one
- * OUT OF SCOPE here: device-pointer box queries (their CSR total needs a host wait); rays given in a body's frame; a step without its
+ *   mgf_batch_cast_sensors / _cast_sensors_dev     "query_launches": the collider gather behind a step (1, once), then
+ *                                                  MGF_BATCH_SENSOR_LAUNCHES = 1, and obstacles 1 where the mask asks for them and a
+ *                                                  world has one
+ * OUT OF SCOPE here: device-pointer box queries (their CSR total needs a host wait); rays given in a body's frame per call (a rig that is
+ * set once has mgf_batch_set_sensors / _cast_sensors_dev, below); a step without its
  * one host wait per call (the capacity re-runs need it); hipGraph capture of these calls; anything for the lone mgf_world (it has
  * mgf_world_export_bodies / _import_ghosts / _device_ptr). */
 #define MGF_BATCH_DEV_SET_LAUNCHES 3
@@ -838,6 +842,46 @@ MGF_API mgf_status mgf_batch_raycast_many_dev(mgf_batch* b, const int32_t* world
                                               const int32_t* ignore_body_dev, int32_t kinds_mask, mgf_ray_hit* out_dev);
 MGF_API mgf_status mgf_batch_sweep_many_dev(mgf_batch* b, const int32_t* world_dev, const mgf_moving_component* casts_dev, int64_t n,
                                             const int32_t* ignore_body_dev, int32_t kinds_mask, mgf_sweep_hit* out_dev);
+/* ---- body-mounted ray sensors: rays fixed in the frame of a body, cast from the poses resident on the device in one call ----
+ * A range finder, a whisker, a ground probe, a line-of-sight check: a ray that is fixed in the frame of a body and moves with it.  A
+ * sensor is a record (world, body, p, d, dt, flags): body an index within world, p and d in the body's frame.  With x and q the body's
+ * rows as mgf_batch_read_state returns them - x WITHOUT delta: the pose from which the last tick built the collider a query sees - the
+ * sensor's particle in world coordinates is
+ *     P = x + rotate(q, p)      D = rotate(q, d)      dt unchanged
+ * rotate = Rotation::rotate_vector (Quaternion * Vector3: tmp = v x r + r * s; (v x tmp) * 2 + r, v and s the quaternion's vector and
+ * scalar part), the sum a plain vector add, every operation a separate f32 one, no fused multiply-add: P and D are defined to the bit.
+ * The sensor's answer is, bit for bit, what mgf_batch_raycast_many writes for the particle (P, D, dt) against world `world` with the
+ * same mask and the ignore value `body` if flags & MGF_SENSOR_IGNORE_SELF, else -1.  Every rule of that call holds unchanged: D = 0
+ * hits nothing, ties are resolved as there, the colliders are those the last tick built ("the collider a query sees", above), nothing
+ * of the tick's state is touched - a step after a cast is bit-identical to one without it.
+ * After a mgf_batch_write_state a sensor follows the new x and q AT ONCE; the colliders move at the next tick (mgf_batch_write_state
+ * does not move the collider a query sees).  (mgf_batch_gather_state_dev's x is x + delta: a ray a caller builds from it does not start
+ * where the collider stands; a sensor with p = 0 starts at the centre of its body's collider frame.)
+ * A rig is static, so what depends on it alone is done once, by mgf_batch_set_sensors: the checks, the sort by world, the work items of
+ * up to 256 sensors.  A cast is then MGF_BATCH_SENSOR_LAUNCHES = 1 launch (and the obstacle pass, and the collider gather behind a
+ * step: "query_launches") whatever the number of sensors and worlds - no plan, no index arrays. */
+#define MGF_SENSOR_IGNORE_SELF 1
+#define MGF_BATCH_SENSOR_LAUNCHES 1
+typedef struct mgf_batch_sensor { int32_t world, body; mgf_vec3 p, d; float dt; int32_t flags; } mgf_batch_sensor;  /* 40 bytes */
+/* Replaces the rig by a copy of s[0 .. n); n = 0 clears it.  Checked on the host and refused with MGF_ERR_INVALID, the rig as it was: a
+ * NULL batch, a NULL array with n > 0, a negative n or n > INT32_MAX, a world outside [0, n_worlds), a body outside
+ * [0, mgf_batch_len(b, world)), a flag bit beyond MGF_SENSOR_IGNORE_SELF.  No device work: the rig goes up with the next cast.
+ * The rig names (world, body), not flat indices: mgf_batch_add_bodies afterwards - also into a world in the middle of the batch -
+ * leaves every sensor on the body it named. */
+MGF_API mgf_status mgf_batch_set_sensors(mgf_batch* b, const mgf_batch_sensor* s, int64_t n);
+/* the sensors of the rig; -1 for NULL */
+MGF_API int64_t mgf_batch_sensor_count(const mgf_batch* b);
+/* The hit of sensor i at out[i], in the order of the array mgf_batch_set_sensors was given; parts_out non-NULL: also its particle
+ * (P, D, dt) at parts_out[i] - what turns t into a point, or draws the ray.  cap: records each array holds.
+ * MGF_ERR_INVALID: a NULL batch, a negative cap, a mask of 0 or with bits beyond MGF_QUERY_ALL, NULL out with a rig that is not empty;
+ * MGF_ERR_CAPACITY: cap below mgf_batch_sensor_count.  An empty rig: MGF_OK, nothing enqueued.  Synchronous, as mgf_batch_raycast_many: one download, one host
+ * wait.  No HIP events: "query_run_ns" is 0. */
+MGF_API mgf_status mgf_batch_cast_sensors(mgf_batch* b, int32_t kinds_mask, mgf_ray_hit* out, mgf_particle* parts_out, int64_t cap);
+/* The same with both arrays in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for.  In
+ * the steady state - the rig, the batch and the terrain and obstacle tables on the device, the handle's scratch large enough - no host
+ * wait and no copy between host and device.  Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of
+ * the device-pointer calls (28 * count bytes each), and out_dev's bytes overlapping parts_out_dev's. */
+MGF_API mgf_status mgf_batch_cast_sensors_dev(mgf_batch* b, int32_t kinds_mask, mgf_ray_hit* out_dev, mgf_particle* parts_out_dev, int64_t cap);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /

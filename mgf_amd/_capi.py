@@ -42,6 +42,10 @@ class Aabb(C.Structure):
     _fields_ = [("c", Vec3), ("r", Vec3)]
 
 
+class BatchSensor(C.Structure):
+    _fields_ = [("world", C.c_int32), ("body", C.c_int32), ("p", Vec3), ("d", Vec3), ("dt", C.c_float), ("flags", C.c_int32)]
+
+
 class Component(C.Structure):
     _fields_ = [("tag", C.c_int32), ("p", Vec3), ("d", Vec3), ("r", C.c_float)]
 
@@ -117,10 +121,14 @@ assert BODY_CONTACTS_DTYPE.itemsize == 24
 BODY_GET_DTYPE = np.dtype([("linear", "<f4", 3), ("angular", "<f4", 3), ("x", "<f4", 3), ("restitution", "<f4"), ("friction", "<f4"),
                            ("inv_mass", "<f4"), ("inv_moment", "<f4", 9), ("force", "<f4", 3), ("torque", "<f4", 3)])
 HIT_NONE, HIT_BODY, HIT_TERRAIN, HIT_OBSTACLE = -1, 0, 1, 2
+# mgf_batch_sensor: a ray fixed in the frame of body `body` of world `world`
+SENSOR_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("p", "<f4", 3), ("d", "<f4", 3), ("dt", "<f4"), ("flags", "<i4")])
 BATCH_MAX_BODIES = 1024  # MGF_BATCH_MAX_BODIES
 BATCH_MAX_WORLD_OBSTACLES = 64  # MGF_BATCH_MAX_WORLD_OBSTACLES
 BATCH_DEV_SET_LAUNCHES = 3  # MGF_BATCH_DEV_SET_LAUNCHES
 BATCH_DEV_QUERY_PLAN_LAUNCHES = 3  # MGF_BATCH_DEV_QUERY_PLAN_LAUNCHES
+SENSOR_IGNORE_SELF = 1  # MGF_SENSOR_IGNORE_SELF
+BATCH_SENSOR_LAUNCHES = 1  # MGF_BATCH_SENSOR_LAUNCHES
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -160,6 +168,7 @@ SYMBOLS = [
     "mgf_batch_add_obstacle", "mgf_batch_set_world_obstacles", "mgf_batch_obstacle_count", "mgf_batch_world_obstacle_count",
     "mgf_ctx_synchronize", "mgf_batch_gather_state_dev", "mgf_batch_set_many_dev", "mgf_batch_set_forces_dev", "mgf_batch_apply_impulses_dev",
     "mgf_batch_read_body_contacts_dev", "mgf_batch_copy_worlds_where", "mgf_batch_raycast_many_dev", "mgf_batch_sweep_many_dev",
+    "mgf_batch_set_sensors", "mgf_batch_sensor_count", "mgf_batch_cast_sensors", "mgf_batch_cast_sensors_dev",
 ]
 
 _lib = None
@@ -329,6 +338,10 @@ def load_library():
         "mgf_batch_raycast_many_dev": (i32, [vp, vp, vp, i64, vp, i32, vp]),
         "mgf_batch_sweep_many_dev": (i32, [vp, vp, vp, i64, vp, i32, vp]),
         "mgf_batch_copy_worlds_where": (i32, [vp, vp, vp, vp, i64, vp]),
+        "mgf_batch_set_sensors": (i32, [vp, vp, i64]),
+        "mgf_batch_sensor_count": (i64, [vp]),
+        "mgf_batch_cast_sensors": (i32, [vp, i32, vp, vp, i64]),
+        "mgf_batch_cast_sensors_dev": (i32, [vp, i32, vp, vp, i64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1625,6 +1638,50 @@ class WorldBatch:
         words = "int32" if str(getattr(casts, "dtype", "")) == "torch.int32" else "float32"
         wp, qp, n, ip, op = self._dev_queries(world, casts, 11, words, out, 13, ignore, n)
         _check(load_library().mgf_batch_sweep_many_dev(self._h, wp, qp, n, ip, int(kinds), op))
+
+    # ---- body-mounted ray sensors: a rig set once, cast from the resident poses -----------------------------------------------------------
+    def set_sensors(self, world, body=None, p=None, d=None, dt=float("inf"), ignore_self=True):
+        """the batch's rig replaced (mgf_batch_set_sensors): sensor i is the ray from p[i] along d[i] for dt[i], all in the frame of
+        body[i] of world[i]; ignore_self[i]: its own body is not a target.  Arrays, or scalars / single rows for all: the number of
+        sensors is that of the longest argument.  No sensors (empty arrays) clears the rig.  Also takes a SENSOR_DTYPE array as
+        `world` with every other argument None."""
+        if isinstance(world, np.ndarray) and world.dtype == SENSOR_DTYPE:
+            rig = np.ascontiguousarray(world.reshape(-1))
+        else:
+            p, d = np.asarray(p, np.float32), np.asarray(d, np.float32)
+            n = max(np.size(world), np.size(body), p.size // 3, d.size // 3, np.size(dt), np.size(ignore_self))
+            if min(np.size(world), np.size(body), p.size, d.size, np.size(dt), np.size(ignore_self)) == 0:
+                n = 0
+            rig = np.zeros(n, SENSOR_DTYPE)
+            rig["world"] = np.broadcast_to(np.asarray(world, np.int32).reshape(-1), (n,))
+            rig["body"] = np.broadcast_to(np.asarray(body, np.int32).reshape(-1), (n,))
+            rig["p"] = np.broadcast_to(p.reshape(-1, 3), (n, 3))
+            rig["d"] = np.broadcast_to(d.reshape(-1, 3), (n, 3))
+            rig["dt"] = np.broadcast_to(np.asarray(dt, np.float32).reshape(-1), (n,))
+            rig["flags"] = np.where(np.broadcast_to(np.asarray(ignore_self, bool).reshape(-1), (n,)), SENSOR_IGNORE_SELF, 0)
+        _check(load_library().mgf_batch_set_sensors(self._h, rig.ctypes.data if len(rig) else None, len(rig)))
+
+    def sensor_count(self):
+        return load_library().mgf_batch_sensor_count(self._h)
+
+    def cast_sensors(self, kinds=QUERY_ALL, parts=False):
+        """every sensor of the rig cast from its body's current pose (mgf_batch_cast_sensors): a RAY_HIT_DTYPE array in the rig's order,
+        as raycast returns it; parts=True: (hits, particles) - the PARTICLE_DTYPE array of the rays in world coordinates"""
+        n = max(self.sensor_count(), 0)
+        out = np.zeros(n, RAY_HIT_DTYPE)
+        pt = np.zeros(n, PARTICLE_DTYPE) if parts else None
+        _check(load_library().mgf_batch_cast_sensors(self._h, int(kinds), out.ctypes.data, _ptr(pt), n))
+        return (out, pt) if parts else out
+
+    def cast_sensors_dev(self, out, kinds=QUERY_ALL, parts=None):
+        """cast_sensors into device memory (mgf_batch_cast_sensors_dev), enqueued on the context's stream and not waited for.
+        out: CUDA int32 [n, 7], RAY_HIT_DTYPE's words as raycast_dev writes them, n = sensor_count(); parts: CUDA float32 [n, 7] or
+        None - a row (P.xyz, D.xyz, dt), the sensor's ray in world coordinates."""
+        if out is None:
+            raise ValueError("out is required")
+        n = max(self.sensor_count(), 0)
+        op, pp = _dev_arg(out, "int32", 7, n, "out"), _dev_arg(parts, "float32", 7, n, "parts")
+        _check(load_library().mgf_batch_cast_sensors_dev(self._h, int(kinds), op, pp, n))
 
     def counter(self, name):
         v = C.c_int64()

@@ -79,6 +79,14 @@ struct mgf_batch {
   DBuf<int32_t> p_world;                // [n] the call's own copy of the worlds, -1: a skipped record
   DBuf<uint32_t> p_rank, p_order;       // [n] a query's rank within its world; sorted position -> the caller's index
   DBuf<uint4> p_items;                  // the work items
+  // the body-mounted sensors (host_batch_sensor.inc): the rig in the caller's order and its plan, built when it is set
+  std::vector<mgf_batch_sensor> s_rig;
+  std::vector<uint4> s_items;           // BatchQueryPlan's work items: (world, first, count <= 256, -)
+  std::vector<uint32_t> s_order;        // ... and its order: sorted position -> the caller's index
+  bool s_stale = false;                 // the device copy is behind the rig or the batch's layout (mgf_batch_add_bodies)
+  DBuf<float4> s_dev;                   // items | records | order | worlds, the sections at s_o_*
+  size_t s_o_rig = 0, s_o_order = 0, s_o_world = 0;
+  DBuf<float> s_parts;                  // the particles of a cast that has nowhere else to put them: 7 words a sensor
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {
@@ -549,6 +557,7 @@ extern "C" mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mg
   batch_offsets(b);
   std::fill(b->h_ccount.begin(), b->h_ccount.end(), 0u);
   b->ccount_stale = false;
+  b->s_stale = true;  // (the sensors name (world, body): they are checked against the new lengths when the rig goes up again)
   return MGF_OK;
 }
 

@@ -101,6 +101,10 @@
 //                      _sweep_many_dev): the sort by world built on the device (ranks by integer atomics, the library's prefix sums,
 //                      work items of up to 256 queries), every world index and tag checked there; then k_batch_query.h's own code
 //                      with the work item from that table, or - a fixed number of queries a world - from blockIdx.x by arithmetic
+//   k_batch_sensor_ray (k_batch_sensor.h)
+//                      ray sensors fixed in the frame of a body (mgf_batch_set_sensors / _cast_sensors / _cast_sensors_dev): the rig sorted
+//                      by world and cut into work items on the host, once; a cast reads the bodies' x and q, forms every sensor's particle
+//                      P = x + rotate(q, p), D = rotate(q, d) and casts it by k_batch_query_ray's own work split, loop and reduction
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -121,3 +125,4 @@
 #include "k_batch_drive.h"  // get / set, forces, impulses and world copies of a batch (k_batch_drive_*)
 #include "k_batch_dev.h"  // the same from and into the caller's device memory (k_batch_dev_*)
 #include "k_batch_query_dev.h"  // ray casts and sweeps from and into the caller's device memory (k_batch_query_plan_*, k_batch_query_*_dev)
+#include "k_batch_sensor.h"  // ray sensors fixed in the frame of a body, cast from the resident poses (k_batch_sensor_ray)

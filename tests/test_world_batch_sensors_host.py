@@ -1,0 +1,312 @@
+"""The body-mounted ray sensors of a batch (mgf_batch_set_sensors, mgf_batch_sensor_count, mgf_batch_cast_sensors,
+mgf_batch_cast_sensors_dev) without a GPU: the numpy restatement of the definition the GPU tests hold the kernel to equals the oracle's
+mgfo_rotate_vector bit for bit; the header, the library, the binding and INTEGRATION.md carry the calls; what can be refused before a
+device is looked at is refused there; mgf_batch_cast_sensors_dev looks both pointers up before it enqueues anything; the binding turns
+a wrong tensor down before it calls C; the new kernel uses no scratch and spills nothing and the query kernels keep the figures
+DESIGN.md records; and the plan of a rig - BatchQueryPlan's, modelled in numpy - is a partition into items of at most 256 sensors."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import mgf_amd
+from mgf_amd import _capi
+from tests import batch_query_device_cases as QD
+from tests import batch_sensor_cases as SC
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CALLS = ("mgf_batch_set_sensors", "mgf_batch_sensor_count", "mgf_batch_cast_sensors", "mgf_batch_cast_sensors_dev")
+
+
+def _read(*path):
+    return open(os.path.join(ROOT, *path)).read()
+
+
+# ---- 1 ------------------------------------------------------------------------------------------------------------------------------------
+def test_the_restatement_is_the_oracles_rotate_vector_bit_for_bit():
+    """a few hundred seeded quaternions and vectors - unit and not, with denormal-sized and 1e4-sized components among them - through
+    SC.rotate and through mgfo_rotate_vector: equal bits, so that the GPU tests' reference is anchored to the oracle, not to itself"""
+    from oracle import oracle as O
+    rng = np.random.default_rng(17)
+    n = 400
+    q = rng.normal(0, 1, (n, 4))
+    q[: n // 2] /= np.linalg.norm(q[: n // 2], axis=1, keepdims=True)
+    v = rng.normal(0, 1, (n, 3)) * rng.choice([1.0, 1e-3, 30.0], (n, 1))
+    v[::7] *= 1e4                                    # 1e4-sized
+    v[3::11, rng.integers(0, 3)] = 1e-41             # a denormal component
+    q[5::13, 1 + rng.integers(0, 3)] = 3e-42
+    v[10], q[11] = 0.0, (1.0, 0.0, 0.0, 0.0)
+    q, v = q.astype(np.float32), v.astype(np.float32)
+    assert np.any((np.abs(v) > 0) & (np.abs(v) < 1.1754944e-38)) and np.any(np.abs(v) > 1e4)
+    got = SC.rotate(q, v)
+    want = np.empty_like(got)
+    lib = O.lib()
+    for i in range(n):
+        out = O.Vec3()
+        lib.mgfo_rotate_vector(C.byref(O.Quat(*q[i].tolist())), C.byref(O.Vec3(*v[i].tolist())), C.byref(out))
+        want[i] = (out.x, out.y, out.z)
+    assert got.tobytes() == want.tobytes(), np.flatnonzero(np.any(got.view(np.uint32) != want.view(np.uint32), axis=1))
+    # and the sum is a plain f32 add
+    x = rng.normal(0, 5, (n, 3)).astype(np.float32)
+    P, D = SC.particles(x, q, v, v)
+    assert P.tobytes() == (x + want).tobytes() and D.tobytes() == want.tobytes() and P.dtype == np.float32
+
+
+# ---- 2 ------------------------------------------------------------------------------------------------------------------------------------
+def test_header_library_binding_and_documents_carry_the_calls():
+    h = _read("include", "mgf_hip.h")
+    for sig in (r"mgf_status mgf_batch_set_sensors\(mgf_batch\* b, const mgf_batch_sensor\* s, int64_t n\);",
+                r"int64_t mgf_batch_sensor_count\(const mgf_batch\* b\);",
+                r"mgf_status mgf_batch_cast_sensors\(mgf_batch\* b, int32_t kinds_mask, mgf_ray_hit\* out, mgf_particle\* parts_out, int64_t cap\);",
+                r"mgf_status mgf_batch_cast_sensors_dev\(mgf_batch\* b, int32_t kinds_mask, mgf_ray_hit\* out_dev, mgf_particle\* parts_out_dev, int64_t cap\);"):
+        assert re.search(r"MGF_API " + sig, h), sig
+    assert h.index("mgf_batch_sweep_many_dev(") < h.index("typedef struct mgf_batch_sensor")      # behind the device-pointer queries
+    assert re.search(r"typedef struct mgf_batch_sensor \{ int32_t world, body; mgf_vec3 p, d; float dt; int32_t flags; \} mgf_batch_sensor;", h)
+    m = re.search(r"#define MGF_SENSOR_IGNORE_SELF (\d+)", h)
+    assert m and int(m.group(1)) == _capi.SENSOR_IGNORE_SELF == 1 == SC.IGNORE_SELF
+    m = re.search(r"#define MGF_BATCH_SENSOR_LAUNCHES (\d+)", h)
+    assert m and int(m.group(1)) == _capi.BATCH_SENSOR_LAUNCHES == 1
+    section = h[h.index("body-mounted ray sensors"):]
+    for word in ("P = x + rotate(q, p)", "D = rotate(q, d)", "WITHOUT delta", "AT ONCE", "the colliders move at the next tick", "bit for bit",
+                 "MGF_ERR_CAPACITY", "nothing enqueued", "mgf_batch_add_bodies"):
+        assert word in section, word
+    assert C.sizeof(_capi.BatchSensor) == 40 == _capi.SENSOR_DTYPE.itemsize
+    assert [f[0] for f in _capi.BatchSensor._fields_] == list(_capi.SENSOR_DTYPE.names) == ["world", "body", "p", "d", "dt", "flags"]
+    assert [_capi.SENSOR_DTYPE.fields[k][1] for k in _capi.SENSOR_DTYPE.names] == [0, 4, 8, 20, 32, 36]
+    lib = mgf_amd.load_library()
+    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
+    want = {"mgf_batch_set_sensors": (i32, [vp, vp, i64]), "mgf_batch_sensor_count": (i64, [vp]),
+            "mgf_batch_cast_sensors": (i32, [vp, i32, vp, vp, i64]), "mgf_batch_cast_sensors_dev": (i32, [vp, i32, vp, vp, i64])}
+    for name in CALLS:
+        assert name in _capi.SYMBOLS, name
+        fn = getattr(lib, name)
+        assert (fn.restype, list(fn.argtypes)) == want[name], name
+    for method in ("set_sensors", "sensor_count", "cast_sensors", "cast_sensors_dev"):
+        assert callable(getattr(mgf_amd.WorldBatch, method)), method
+    flat = re.sub(r"\s+", " ", _read("INTEGRATION.md"))
+    for sig in ("pub fn mgf_batch_set_sensors(b: *mut mgf_batch, s: *const mgf_batch_sensor, n: i64) -> mgf_status;",
+                "pub fn mgf_batch_sensor_count(b: *const mgf_batch) -> i64;",
+                "pub fn mgf_batch_cast_sensors(b: *mut mgf_batch, kinds_mask: i32, out: *mut mgf_ray_hit, parts_out: *mut mgf_particle, cap: i64) -> mgf_status;",
+                "pub fn mgf_batch_cast_sensors_dev(b: *mut mgf_batch, kinds_mask: i32, out_dev: *mut mgf_ray_hit, parts_out_dev: *mut mgf_particle, cap: i64) -> mgf_status;",
+                "pub struct mgf_batch_sensor"):
+        assert sig in flat, sig
+    kernels = _read("mgf_amd", "csrc", "kernels.h")
+    assert kernels.index('#include "k_batch_query_dev.h"') < kernels.index('#include "k_batch_sensor.h"') and "k_batch_sensor_ray" in kernels
+    hip = _read("mgf_amd", "csrc", "mgf_hip.hip")
+    assert hip.index('#include "host_batch_query_dev.inc"') < hip.index('#include "host_batch_sensor.inc"')
+    design = _read("DESIGN.md")
+    sub = design[design.index("Body-mounted sensors"):]
+    for word in ("k_batch_sensor_ray", "P = x + rotate(q, p)", "Out of scope", "batch_sensor_bench.py", "Compiler output"):
+        assert word in sub, word
+    readme = _read("README.md")
+    assert "set_sensors" in readme and "cast_sensors_dev" in readme
+    assert os.path.exists(os.path.join(ROOT, "tools", "batch_sensor_bench.py"))
+
+
+# ---- 3 ------------------------------------------------------------------------------------------------------------------------------------
+def test_what_needs_no_device_is_refused_before_the_handle_is_dereferenced():
+    lib = mgf_amd.load_library()
+    INV = _capi.ERR_INVALID
+
+    def err():
+        return lib.mgf_last_error().decode()
+    fake = C.c_void_p(16)   # a handle that is never dereferenced; addresses that are never looked up
+    rig = np.zeros(4, _capi.SENSOR_DTYPE)
+    out, parts = C.c_void_p(1 << 20), C.c_void_p(1 << 21)
+    assert lib.mgf_batch_sensor_count(None) == -1
+    assert lib.mgf_batch_set_sensors(None, rig.ctypes.data, 4) == INV and "NULL" in err()
+    assert lib.mgf_batch_set_sensors(None, None, 0) == INV and "NULL" in err()
+    assert lib.mgf_batch_set_sensors(fake, None, 4) == INV and "NULL" in err()
+    assert lib.mgf_batch_set_sensors(fake, rig.ctypes.data, -1) == INV and "negative" in err()
+    assert lib.mgf_batch_set_sensors(fake, rig.ctypes.data, -(1 << 40)) == INV and "negative" in err()
+    assert lib.mgf_batch_set_sensors(fake, rig.ctypes.data, 1 << 31) == INV and "too many" in err()
+    for fn in (lib.mgf_batch_cast_sensors, lib.mgf_batch_cast_sensors_dev):
+        assert fn(None, 7, out, parts, 4) == INV and "NULL" in err()
+        assert fn(fake, 7, out, None, -1) == INV and "negative" in err()
+        for mask in (0, 8, -1, 16):
+            assert fn(fake, mask, out, parts, 4) == INV and "kinds_mask" in err(), mask
+            assert fn(fake, mask, out, None, 0) == INV and "kinds_mask" in err(), mask
+    assert lib.mgf_batch_sensor_count(None) == -1
+    # what needs the handle - a world or a body out of range, a flag bit beyond the one defined, cap below the count - is refused on the
+    # host too, ahead of any device work (read here; run in tests/test_gpu_world_batch_sensors.py, where a handle exists)
+    src = _read("mgf_amd", "csrc", "host_batch_sensor.inc")
+    body = src[src.index('extern "C" mgf_status mgf_batch_set_sensors('):src.index('extern "C" int64_t mgf_batch_sensor_count(')]
+    first_change = body.index("b->s_rig.assign(")
+    for refusal in ("world index out of range", "body index out of range", "a bit beyond MGF_SENSOR_IGNORE_SELF"):
+        assert body.index(refusal) < first_change, refusal
+    assert not re.search(r"<<<|Async|hipMalloc|\.ensure\(|h2d\(", body)            # no device work at all
+    args = src[src.index("static mgf_status batch_sensor_args("):src.index('extern "C" mgf_status mgf_batch_cast_sensors(')]
+    assert args.index("MGF_ERR_CAPACITY") < args.index('"NULL argument"') < args.index("return MGF_OK;") and "ctx_bind" not in args and "<<<" not in args
+
+
+# ---- 4 ------------------------------------------------------------------------------------------------------------------------------------
+def test_both_pointers_are_looked_up_before_the_first_enqueue():
+    """the order "check, then enqueue" of mgf_batch_cast_sensors_dev, read in the source as tests/test_world_batch_query_device_host.py
+    reads batch_query_dev_run: the last dev_span and the overlap check come before the first thing that enqueues - here all of that
+    is batch_sensor_run - and the refusals that need no device before the context is bound"""
+    src = _read("mgf_amd", "csrc", "host_batch_sensor.inc")
+    run = src[src.index('extern "C" mgf_status mgf_batch_cast_sensors_dev('):]
+    enqueue = (r"batch_sensor_run\(|batch_sensors_up\(|batch_push\(|batch_dev_begin\(|batch_env_sync\(|batch_cols_refresh\(|hipMemsetAsync|hipMemcpyAsync|<<<|"
+               r"prim_exclusive_scan_u32|\.ensure\(|h2d\(")
+    first_enqueue = min(m.start() for m in re.finditer(enqueue, run))
+    checks = [m.start() for m in re.finditer(r"dev_span\(", run)]
+    assert len(checks) == 2 and max(checks) < first_enqueue
+    for name in ("out_dev, 28 \\* n", "parts_out_dev, 28 \\* n"):
+        assert re.search(r"dev_span\(b->ctx, " + name, run), name
+    overlap = run.index("dev_bytes_overlap(out_dev, 28 * n, parts_out_dev, 28 * n)")
+    assert max(checks) < overlap < first_enqueue
+    assert run.index("batch_sensor_args(") < run.index("ctx_bind(") < min(checks)
+    assert run.index("if (n == 0) return MGF_OK;") < first_enqueue                   # an empty rig enqueues nothing
+    # everything that enqueues is in batch_sensor_run and batch_sensors_up, and those are reached from the two cast calls only
+    helper = src[src.index("static mgf_status batch_sensor_run("):src.index("static mgf_status batch_sensor_args(")]
+    assert "<<<" in helper and "k_batch_sensor_ray<<<" in helper and "k_batch_query_ray_obstacles<<<" in helper
+    assert helper.count("<<<") == 2 and "hipStreamSynchronize" not in helper and "hipMemcpy" not in helper   # no wait, no copy
+    up = src[src.index("static mgf_status batch_sensors_up("):src.index("// The launches of a cast")]
+    assert up.index("if (!b->s_stale) return MGF_OK;") < up.index("h2d(")             # the steady state uploads nothing
+    k = _read("mgf_amd", "csrc", "k_batch_sensor.h")
+    body = k[k.index("void k_batch_sensor_ray("):]
+    assert body.index("bq_stage(") < body.index("bq_reduce(") < body.index("return;") and body.count("return;") == 1   # no exit ahead of a barrier
+    assert "atomic" not in body
+
+
+# ---- 5 ------------------------------------------------------------------------------------------------------------------------------------
+def test_the_binding_turns_a_wrong_tensor_down_before_it_calls_c():
+    import torch
+
+    class Handle(mgf_amd.WorldBatch):   # no context, no C handle: a call that got as far as C would fail differently
+        def __init__(self):
+            self._h, self.n_worlds = None, 2
+
+        def sensor_count(self):
+            return 4
+
+    b, n = Handle(), 4
+    wrong_out = [torch.zeros((n, 7), dtype=torch.float32), torch.zeros((n, 7), dtype=torch.int64), torch.zeros((7, n), dtype=torch.int32).t(),
+                 torch.zeros((n - 1, 7), dtype=torch.int32), torch.zeros((n, 6), dtype=torch.int32)]
+    wrong_parts = [torch.zeros((n, 7), dtype=torch.float64), torch.zeros((n, 7), dtype=torch.int32), torch.zeros((7, n), dtype=torch.float32).t(),
+                   torch.zeros((n - 1, 7), dtype=torch.float32), torch.zeros((n, 6), dtype=torch.float32)]
+    for t in wrong_out:
+        with pytest.raises(ValueError) as e:
+            b.cast_sensors_dev(t, parts=1 << 21)
+        assert "on cpu" not in str(e.value), str(e.value)              # turned down for what it is, not for where it is
+    for t in wrong_parts:
+        with pytest.raises(ValueError) as e:
+            b.cast_sensors_dev(1 << 20, parts=t)
+        assert "on cpu" not in str(e.value), str(e.value)
+    with pytest.raises(ValueError, match="on cpu"):                     # everything right but the device
+        b.cast_sensors_dev(torch.zeros((n, 7), dtype=torch.int32))
+    with pytest.raises(ValueError, match="on cpu"):
+        b.cast_sensors_dev(1 << 20, parts=torch.zeros((n, 7), dtype=torch.float32))
+    with pytest.raises(ValueError, match="required"):
+        b.cast_sensors_dev(None)
+    with pytest.raises(ValueError, match="not ndarray"):
+        b.cast_sensors_dev(np.zeros((n, 7), np.int32))
+    with pytest.raises(mgf_amd.MgfError):                               # and a call whose arguments are all in order does reach C
+        b.cast_sensors_dev(1 << 20, parts=1 << 21)
+    # set_sensors broadcasts scalars and single rows; what reaches C is SENSOR_DTYPE rows (no handle: C refuses, after the marshalling)
+    with pytest.raises(mgf_amd.MgfError):
+        b.set_sensors([0, 1, 1], 0, (0, 0, 0), [(0, 0, 1), (0, 1, 0), (1, 0, 0)])
+    with pytest.raises(ValueError):
+        b.set_sensors([0, 1, 1], [0, 1], (0, 0, 0), (0, 0, 1))         # neither one nor n
+
+
+# ---- 6 ------------------------------------------------------------------------------------------------------------------------------------
+Z = ("0", "0", "0", "0")
+RESOURCES = {  # DESIGN.md, "Device-pointer queries", compiler output: VGPR, SGPR | scratch, static LDS, spills
+    "k_batch_query_gather": ("10", "14") + Z, "k_batch_query_plan_count<7u>": ("9", "20") + Z, "k_batch_query_plan_count<13u>": ("14", "26") + Z,
+    "k_batch_query_plan_cut": ("4", "14") + Z, "k_batch_query_plan_fill": ("10", "20") + Z,
+    "k_batch_query_ray": ("45", "65") + Z, "k_batch_query_ray_dev<1>": ("45", "65") + Z, "k_batch_query_ray_dev<2>": ("45", "65") + Z,
+    "k_batch_query_sweep_bodies": ("108", "90") + Z, "k_batch_query_sweep_bodies_dev<1>": ("108", "90") + Z,
+    "k_batch_query_sweep_bodies_dev<2>": ("108", "90") + Z, "k_batch_query_sweep_faces": ("133", "69", "0", "9216", "0", "0"),
+    "k_batch_query_ray_obstacles": ("68", "63") + Z, "k_batch_query_sweep_obstacles": ("115", "87") + Z,
+}
+
+
+def _resources(prefix):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), prefix], capture_output=True, text=True, check=True).stdout
+    rows = {}
+    for line in out.splitlines()[1:]:
+        m = re.match(r"(.{80}) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+)$", line)
+        if m:
+            rows[m.group(1).strip()] = tuple(m.group(k) for k in range(2, 8))  # vgpr, sgpr, scratch, lds, sgpr spills, vgpr spills
+    return rows
+
+
+def test_the_new_kernel_uses_no_scratch_and_the_query_kernels_keep_their_figures():
+    if not os.path.exists(os.path.join(ROOT, "mgf_amd", "libmgf_hip.so")) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
+        pytest.skip("needs the built library and the ROCm LLVM tools")
+    rows = _resources("k_batch_sensor_")
+    assert set(rows) == {"k_batch_sensor_ray"}, sorted(rows)
+    v = rows["k_batch_sensor_ray"]
+    assert (v[2], v[3], v[4], v[5]) == ("0", "0", "0", "0"), v               # no scratch, no static LDS, no spills
+    old = _resources("k_batch_query_")
+    assert int(v[0]) <= int(old["k_batch_query_ray"][0]) + 8, (v, old["k_batch_query_ray"])   # one piece of work, about the same registers
+    assert set(old) == set(RESOURCES), sorted(old)
+    for name, want in RESOURCES.items():
+        assert old[name] == want, (name, old[name], want)
+    design = re.sub(r"\s+", " ", _read("DESIGN.md"))
+    for text in ("`k_batch_query_ray` 45 / 65 / 0 / 0 / 0", "`k_batch_query_sweep_faces` 133 / 69 / 9216 / 0 / 0", "`_ray_obstacles` 68 / 63 / 0 / 0 / 0",
+                 "`k_batch_query_sweep_bodies` 108 / 90 / 0 / 0 / 0", "`k_batch_query_plan_fill` 10 / 20", "`_sweep_obstacles` 115 / 87 / 0 / 0 / 0"):
+        assert text in design, text
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_lane_masks.py")], capture_output=True, text=True)
+    assert r.returncode == 0 and " 0 lane masks" in r.stdout, r.stdout[-400:]
+    k = _read("mgf_amd", "csrc", "k_batch_sensor.h")
+    assert len(re.findall(r"__global__ __launch_bounds__\(kBatchBlock\)", k)) == len(re.findall(r"__global__", k)) == 1
+
+
+# ---- 7 ------------------------------------------------------------------------------------------------------------------------------------
+def _plan_cases():
+    twin, pile = SC.twin_scenes(), QD.pile_scenes()
+    return [("worlds of 0, 1, 256, 257 and 600", SC.plan_worlds(), len(SC.PLAN_COUNTS), list(SC.PLAN_COUNTS)),
+            ("the same reversed", SC.plan_worlds()[::-1], len(SC.PLAN_COUNTS), list(SC.PLAN_COUNTS)),
+            ("twin", SC.twin_layout(twin)["world"], len(twin), [0, 1, 257]), ("pile", SC.pile_layout(pile)["world"], len(pile), [2, 42, 60, 0, 320])]
+
+
+@pytest.mark.parametrize("case", range(4))
+def test_the_plan_of_a_rig_is_a_partition_into_items_of_at_most_256(case):
+    """mgf_batch_set_sensors sorts the rig with the host's BatchQueryPlan: one stable counting sort.  QD.plan_model is that plan with the
+    ranks taken in array order - the host's order - so here the caller's relative order within a world is part of the claim"""
+    name, world, K, counts = _plan_cases()[case]
+    n = len(world)
+    assert np.any(np.diff(world) < 0), name                                        # shuffled world order
+    items, order, skipped = QD.plan_model(world, K)
+    assert skipped == 0 and sorted(order.tolist()) == list(range(n)), name
+    assert np.bincount(world, minlength=K).tolist() == counts, name
+    seen = np.zeros(n, np.int64)
+    for w, first, count in items:
+        assert 1 <= count <= 256, (name, count)
+        q = order[first:first + count]
+        assert np.all(world[q] == w) and np.all(np.diff(q) > 0), name              # one world; the caller's relative order
+        seen[q] += 1
+    assert np.all(seen == 1), name
+    assert np.all(np.diff(items[:, 0]) >= 0) and np.all(np.diff(items[:, 1]) > 0), name
+    assert len(items) == sum((c + 255) // 256 for c in counts), name
+    for w in range(K):                                                             # across a world's items too: ascending
+        q = order[np.flatnonzero(world[order] == w)]
+        assert np.all(np.diff(q) > 0), (name, w)
+    if case == 0:
+        assert items[:, 2].tolist() == [1, 256, 256, 1, 256, 256, 88]
+
+
+def test_the_layouts_hold_what_the_gpu_tests_ask_of_them():
+    """from the scenes alone: 257 sensors on the world of 300, none on one world, one on the world of one body, four on one body, the
+    d = 0 and the too-short sensor, the pair at one sphere's centre, and sensors for the floor, the ring and the sky"""
+    twin = SC.twin_scenes()
+    assert [len(sc["comps"]) for sc in twin] == [5, 1, 300] and all({0, 1} <= set(sc["comps"]["tag"].tolist()) for sc in twin[::2])
+    for scs, lay in ((twin, SC.twin_layout(twin)), (QD.pile_scenes(), SC.pile_layout(QD.pile_scenes()))):
+        n = [len(sc["comps"]) for sc in scs]
+        assert np.all(lay["body"] >= 0) and np.all(lay["body"] < np.int64(n)[lay["world"]])
+        role = lay["role"]
+        for r, least in ((SC.DOWN, 10), (SC.UP, 10), (SC.RING, 12), (SC.ZERO, 1), (SC.SHORT, 1), (SC.SELF_IGNORED, 1), (SC.SELF_SEEN, 1), (SC.RANDOM, 100)):
+            assert np.sum(role == r) >= least, r
+        pair = np.flatnonzero((role == SC.SELF_IGNORED) | (role == SC.SELF_SEEN))
+        assert len(pair) == 2 and lay["body"][pair[0]] == lay["body"][pair[1]] and lay["world"][pair[0]] == lay["world"][pair[1]]
+        assert scs[lay["world"][pair[0]]]["comps"]["tag"][lay["body"][pair[0]]] == 0
+        key = lay["world"].astype(np.int64) * 4096 + lay["body"]
+        assert np.bincount(np.unique(key, return_inverse=True)[1]).max() >= 4          # four on one body
+        for i in np.flatnonzero(role == SC.RING):
+            assert scs[lay["world"][i]].get("obstacles"), i
