@@ -882,6 +882,65 @@ MGF_API mgf_status mgf_batch_cast_sensors(mgf_batch* b, int32_t kinds_mask, mgf_
  * wait and no copy between host and device.  Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of
  * the device-pointer calls (28 * count bytes each), and out_dev's bytes overlapping parts_out_dev's. */
 MGF_API mgf_status mgf_batch_cast_sensors_dev(mgf_batch* b, int32_t kinds_mask, mgf_ray_hit* out_dev, mgf_particle* parts_out_dev, int64_t cap);
+/* ---- body-mounted depth cameras: an image of rays fixed in the frame of a body, cast from the resident poses a tile at a time ----
+ * An egocentric depth map, a height scan of the terrain under a walker, a lidar sweep: a pinhole camera fixed in the frame of a body.
+ * Described pixel by pixel as sensors it would be a record of 40 bytes a pixel; a camera is one record of 64 bytes, and its kernel's
+ * unit of work is an image tile, whose pixels settle together which bodies any of them can meet.
+ * The camera looks along +z of its own frame, with +x to the right and +y up.  Pixel (ix, iy) sits at row iy from the top and column ix
+ * from the left.  Its direction in the camera's frame is, in f32 with every operation rounded on its own and no fused multiply-add,
+ *     u = ((float)(2*ix + 1) / (float)width  - 1.0f) * tan_x
+ *     v = (1.0f - (float)(2*iy + 1) / (float)height) * tan_y
+ *     d_cam = (u, v, 1.0f)
+ * With x and q the body's rows as mgf_batch_read_state returns them (x WITHOUT delta, as for a sensor), the pixel's particle is
+ *     P = x + rotate(q, p)      D = rotate(q, rotate(r, d_cam))      dt = far
+ * rotate as in the sensors' definition above (Rotation::rotate_vector), r taken as given and not normalised.
+ * The pixel's hit record is, bit for bit, what mgf_batch_raycast_many writes for the particle (P, D, far) against world `world` with the
+ * call's mask and the ignore value `body` if flags & MGF_SENSOR_IGNORE_SELF, else -1.  The pixel's depth is the hit's inter.t, or far
+ * where the kind is MGF_HIT_NONE.  d_cam.z is 1, so t IS the depth along the optical axis wherever r and q are unit quaternions (for
+ * another r it is the hit's parameter along D, as for any ray).
+ * Everything else is the sensors' text: the colliders are those the last tick built; after a mgf_batch_write_state a camera follows the
+ * new x and q AT ONCE and its targets move at the next tick; a cast touches nothing of the tick's state - a step after a cast is bit-identical to
+ * one without it.  Pixels come out camera by camera in the order of the array given, row-major within a camera: pixel (ix, iy) of
+ * camera c at first(c) + iy * width + ix, first(c) the pixels of the cameras before c.
+ * "query_launches" of a cast: the collider gather behind a step (1, once), then MGF_BATCH_CAMERA_LAUNCHES = 1; where the mask asks for
+ * obstacles and a world has one, the unchanged obstacle pass over the stored particles and hit records (1; both live in the handle's
+ * scratch when the caller gave no array) and a lane-per-pixel pass that writes depth from the final hits (1; not where depth is NULL).
+ * None of it depends on the number of cameras, pixels or worlds.
+ * OUT OF SCOPE here: a near plane; colour, or anything but depth and the hit; several small cameras sharing one workgroup (a camera of
+ * a few pixels wastes lanes: a few rays are what sensors are for); a tile cull of the terrain walk; cameras on the lone mgf_world. */
+#define MGF_BATCH_CAMERA_LAUNCHES 1
+#define MGF_CAMERA_MAX_SIDE 4096
+typedef struct mgf_batch_camera {
+  int32_t world, body;     /* body: an index within world */
+  mgf_vec3 p;              /* the eye, in the body's frame */
+  mgf_quat r;              /* the camera's orientation in the body's frame (s, x, y, z); taken as given, not normalised */
+  float tan_x, tan_y;      /* tangents of the half angles of view, horizontal and vertical */
+  float far;               /* the rays' dt: > 0, or +inf */
+  int32_t width, height;   /* pixels */
+  int32_t flags;           /* MGF_SENSOR_IGNORE_SELF or 0 */
+  int32_t reserved;        /* 0 */
+} mgf_batch_camera;        /* 64 bytes */
+/* Replaces the camera rig by a copy of cams[0 .. n); n = 0 clears it.  Checked on the host and refused with MGF_ERR_INVALID, the rig as
+ * it was: what mgf_batch_set_sensors refuses (a NULL batch, a NULL array with n > 0, a negative n or n > INT32_MAX, a world or a body
+ * out of range, a flag bit beyond MGF_SENSOR_IGNORE_SELF); a width or height outside [1, MGF_CAMERA_MAX_SIDE]; more than INT32_MAX pixels
+ * in all; a non-finite p, r, tan_x or tan_y; a far that is NaN or <= 0; reserved != 0.  No device work: the rig - the records and a
+ * table of its tiles - goes up with the next cast.  The rig is independent of the sensor rig: each can be set, cleared and cast without
+ * the other changing.  It names (world, body): mgf_batch_add_bodies afterwards leaves every camera on the body it named. */
+MGF_API mgf_status mgf_batch_set_cameras(mgf_batch* b, const mgf_batch_camera* cams, int64_t n);
+/* the cameras of the rig, and the pixels of all of them; -1 for NULL */
+MGF_API int64_t mgf_batch_camera_count(const mgf_batch* b);
+MGF_API int64_t mgf_batch_camera_pixels(const mgf_batch* b);
+/* depth: float[pixels], hits: mgf_ray_hit[pixels], parts_out: mgf_particle[pixels]; each may be NULL.  cap: records each array holds.
+ * MGF_ERR_INVALID: a NULL batch, a negative cap, a mask of 0 or with bits beyond MGF_QUERY_ALL, depth and hits both NULL with a rig that
+ * is not empty; MGF_ERR_CAPACITY: cap below mgf_batch_camera_pixels.  An empty rig: MGF_OK, nothing enqueued.  Synchronous, as
+ * mgf_batch_cast_sensors: one download an array, one host wait.  No HIP events: "query_run_ns" is 0. */
+MGF_API mgf_status mgf_batch_cast_cameras(mgf_batch* b, int32_t kinds_mask, float* depth, mgf_ray_hit* hits, mgf_particle* parts_out, int64_t cap);
+/* The same with the arrays in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for.  In
+ * the steady state - the rig, the batch and the terrain and obstacle tables on the device, the handle's scratch large enough - no host
+ * wait and no copy between host and device.  Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of
+ * the device-pointer calls (4, 28 and 28 bytes a pixel), and any two of the three arrays overlapping. */
+MGF_API mgf_status mgf_batch_cast_cameras_dev(mgf_batch* b, int32_t kinds_mask, float* depth_dev, mgf_ray_hit* hits_dev, mgf_particle* parts_out_dev,
+                                              int64_t cap);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /

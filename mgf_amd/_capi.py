@@ -46,6 +46,11 @@ class BatchSensor(C.Structure):
     _fields_ = [("world", C.c_int32), ("body", C.c_int32), ("p", Vec3), ("d", Vec3), ("dt", C.c_float), ("flags", C.c_int32)]
 
 
+class BatchCamera(C.Structure):
+    _fields_ = [("world", C.c_int32), ("body", C.c_int32), ("p", Vec3), ("r", C.c_float * 4), ("tan_x", C.c_float), ("tan_y", C.c_float),
+                ("far", C.c_float), ("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Component(C.Structure):
     _fields_ = [("tag", C.c_int32), ("p", Vec3), ("d", Vec3), ("r", C.c_float)]
 
@@ -123,12 +128,18 @@ BODY_GET_DTYPE = np.dtype([("linear", "<f4", 3), ("angular", "<f4", 3), ("x", "<
 HIT_NONE, HIT_BODY, HIT_TERRAIN, HIT_OBSTACLE = -1, 0, 1, 2
 # mgf_batch_sensor: a ray fixed in the frame of body `body` of world `world`
 SENSOR_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("p", "<f4", 3), ("d", "<f4", 3), ("dt", "<f4"), ("flags", "<i4")])
+# mgf_batch_camera: a pinhole camera fixed in the frame of body `body` of world `world`; r = (s, x, y, z)
+CAMERA_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("p", "<f4", 3), ("r", "<f4", 4), ("tan_x", "<f4"), ("tan_y", "<f4"), ("far", "<f4"),
+                         ("width", "<i4"), ("height", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
+assert CAMERA_DTYPE.itemsize == 64
 BATCH_MAX_BODIES = 1024  # MGF_BATCH_MAX_BODIES
 BATCH_MAX_WORLD_OBSTACLES = 64  # MGF_BATCH_MAX_WORLD_OBSTACLES
 BATCH_DEV_SET_LAUNCHES = 3  # MGF_BATCH_DEV_SET_LAUNCHES
 BATCH_DEV_QUERY_PLAN_LAUNCHES = 3  # MGF_BATCH_DEV_QUERY_PLAN_LAUNCHES
 SENSOR_IGNORE_SELF = 1  # MGF_SENSOR_IGNORE_SELF
 BATCH_SENSOR_LAUNCHES = 1  # MGF_BATCH_SENSOR_LAUNCHES
+BATCH_CAMERA_LAUNCHES = 1  # MGF_BATCH_CAMERA_LAUNCHES
+CAMERA_MAX_SIDE = 4096  # MGF_CAMERA_MAX_SIDE
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -169,6 +180,7 @@ SYMBOLS = [
     "mgf_ctx_synchronize", "mgf_batch_gather_state_dev", "mgf_batch_set_many_dev", "mgf_batch_set_forces_dev", "mgf_batch_apply_impulses_dev",
     "mgf_batch_read_body_contacts_dev", "mgf_batch_copy_worlds_where", "mgf_batch_raycast_many_dev", "mgf_batch_sweep_many_dev",
     "mgf_batch_set_sensors", "mgf_batch_sensor_count", "mgf_batch_cast_sensors", "mgf_batch_cast_sensors_dev",
+    "mgf_batch_set_cameras", "mgf_batch_camera_count", "mgf_batch_camera_pixels", "mgf_batch_cast_cameras", "mgf_batch_cast_cameras_dev",
 ]
 
 _lib = None
@@ -342,6 +354,11 @@ def load_library():
         "mgf_batch_sensor_count": (i64, [vp]),
         "mgf_batch_cast_sensors": (i32, [vp, i32, vp, vp, i64]),
         "mgf_batch_cast_sensors_dev": (i32, [vp, i32, vp, vp, i64]),
+        "mgf_batch_set_cameras": (i32, [vp, vp, i64]),
+        "mgf_batch_camera_count": (i64, [vp]),
+        "mgf_batch_camera_pixels": (i64, [vp]),
+        "mgf_batch_cast_cameras": (i32, [vp, i32, vp, vp, vp, i64]),
+        "mgf_batch_cast_cameras_dev": (i32, [vp, i32, vp, vp, vp, i64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1682,6 +1699,61 @@ class WorldBatch:
         n = max(self.sensor_count(), 0)
         op, pp = _dev_arg(out, "int32", 7, n, "out"), _dev_arg(parts, "float32", 7, n, "parts")
         _check(load_library().mgf_batch_cast_sensors_dev(self._h, int(kinds), op, pp, n))
+
+    # ---- body-mounted depth cameras: a rig set once, an image per camera from the resident poses ------------------------------------------
+    def set_cameras(self, cams):
+        """the batch's camera rig replaced (mgf_batch_set_cameras).  cams: a CAMERA_DTYPE array - camera i is fixed to body[i] of world[i]
+        with its eye at p and the orientation r = (s, x, y, z) in the body's frame, looks along its own +z (+x right, +y up) with the half
+        angles atan(tan_x), atan(tan_y), sees as far as `far` and has width x height pixels; flags: SENSOR_IGNORE_SELF or 0 - or a
+        sequence of dicts with those keys (r defaults to the identity, far to inf, flags to SENSOR_IGNORE_SELF).  Empty: clears the rig."""
+        if isinstance(cams, np.ndarray):
+            if cams.dtype != CAMERA_DTYPE:
+                raise ValueError(f"cams: a CAMERA_DTYPE array, not {cams.dtype}")
+            rig = np.ascontiguousarray(cams.reshape(-1))
+        else:
+            cams = list(cams)
+            rig = np.zeros(len(cams), CAMERA_DTYPE)
+            rig["r"][:, 0], rig["far"], rig["flags"] = 1.0, np.inf, SENSOR_IGNORE_SELF
+            for i, c in enumerate(cams):
+                unknown = set(c) - set(CAMERA_DTYPE.names)
+                if unknown:
+                    raise ValueError(f"cams[{i}]: no such field: {sorted(unknown)}")
+                for k, v in c.items():
+                    rig[k][i] = v
+        _check(load_library().mgf_batch_set_cameras(self._h, rig.ctypes.data if len(rig) else None, len(rig)))
+        self._camera_shapes = [(int(h), int(w)) for h, w in zip(rig["height"], rig["width"])]
+
+    def camera_count(self):
+        return load_library().mgf_batch_camera_count(self._h)
+
+    def camera_pixels(self):
+        return load_library().mgf_batch_camera_pixels(self._h)
+
+    def cast_cameras(self, kinds=QUERY_ALL, hits=False, parts=False):
+        """every camera of the rig cast from its body's current pose (mgf_batch_cast_cameras): a list of [height, width] float32 depth
+        images in the rig's order - the hit's t, or far where nothing is hit.  hits=True / parts=True: (images, hits[, parts]) - the
+        flat RAY_HIT_DTYPE and PARTICLE_DTYPE arrays, camera by camera and row-major within a camera"""
+        n = max(self.camera_pixels(), 0)
+        depth = np.zeros(n, np.float32)
+        out = np.zeros(n, RAY_HIT_DTYPE) if hits else None
+        pt = np.zeros(n, PARTICLE_DTYPE) if parts else None
+        _check(load_library().mgf_batch_cast_cameras(self._h, int(kinds), depth.ctypes.data, _ptr(out), _ptr(pt), n))
+        images, at = [], 0
+        for h, w in getattr(self, "_camera_shapes", []):
+            images.append(depth[at:at + h * w].reshape(h, w))
+            at += h * w
+        res = (images,) + ((out,) if hits else ()) + ((pt,) if parts else ())
+        return res if len(res) > 1 else images
+
+    def cast_cameras_dev(self, depth=None, hits=None, parts=None, kinds=QUERY_ALL):
+        """cast_cameras into device memory (mgf_batch_cast_cameras_dev), enqueued on the context's stream and not waited for.  With
+        n = camera_pixels(): depth CUDA float32 [n], hits CUDA int32 [n, 7] (RAY_HIT_DTYPE's words as raycast_dev writes them), parts
+        CUDA float32 [n, 7] (P.xyz, D.xyz, dt) - torch tensors or addresses; each may be None, but not depth and hits both."""
+        if depth is None and hits is None:
+            raise ValueError("depth or hits is required")
+        n = max(self.camera_pixels(), 0)
+        dp, op, pp = _dev_arg(depth, "float32", 1, n, "depth"), _dev_arg(hits, "int32", 7, n, "hits"), _dev_arg(parts, "float32", 7, n, "parts")
+        _check(load_library().mgf_batch_cast_cameras_dev(self._h, int(kinds), dp, op, pp, n))
 
     def counter(self, name):
         v = C.c_int64()

@@ -87,6 +87,15 @@ struct mgf_batch {
   DBuf<float4> s_dev;                   // items | records | order | worlds, the sections at s_o_*
   size_t s_o_rig = 0, s_o_order = 0, s_o_world = 0;
   DBuf<float> s_parts;                  // the particles of a cast that has nowhere else to put them: 7 words a sensor
+  // the body-mounted depth cameras (host_batch_camera.inc): the rig in the caller's order and its tile table, built when it is set
+  std::vector<mgf_batch_camera> c_rig;
+  std::vector<uint4> c_tiles;           // (camera, the camera's first pixel, x0 | y0 << 16, -): a tile of kCamTileW x kCamTileH pixels
+  size_t c_pixels = 0;                  // the pixels of the rig, camera by camera
+  bool c_stale = false;                 // the device copy is behind the rig or the batch's layout (mgf_batch_add_bodies)
+  DBuf<float4> c_dev;                   // tiles | records, the records at c_o_rig
+  size_t c_o_rig = 0;
+  DBuf<float> c_parts, c_depth;         // what a cast has nowhere else to put: 7 words a pixel, one word a pixel
+  DBuf<int32_t> c_world;                // [pixels] a pixel's world, written by the tile pass for the obstacle pass
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {
@@ -558,6 +567,7 @@ extern "C" mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mg
   std::fill(b->h_ccount.begin(), b->h_ccount.end(), 0u);
   b->ccount_stale = false;
   b->s_stale = true;  // (the sensors name (world, body): they are checked against the new lengths when the rig goes up again)
+  b->c_stale = true;  // (and so do the cameras)
   return MGF_OK;
 }
 

@@ -105,6 +105,11 @@
 //                      ray sensors fixed in the frame of a body (mgf_batch_set_sensors / _cast_sensors / _cast_sensors_dev): the rig sorted
 //                      by world and cut into work items on the host, once; a cast reads the bodies' x and q, forms every sensor's particle
 //                      P = x + rotate(q, p), D = rotate(q, d) and casts it by k_batch_query_ray's own work split, loop and reduction
+//   k_batch_camera_tile / _depth (k_batch_camera.h)
+//                      depth cameras fixed in the frame of a body (mgf_batch_set_cameras / _cast_cameras / _cast_cameras_dev): a workgroup per
+//                      tile of 16 x 16 pixels, a lane per pixel; the tile bounds its rays by a cone and a length, drops every body whose
+//                      padded sphere lies outside both, compacts the survivors into LDS, and every pixel runs k_batch_query_ray's loop over
+//                      them alone; _depth writes the depth image behind the obstacle pass
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -126,3 +131,4 @@
 #include "k_batch_dev.h"  // the same from and into the caller's device memory (k_batch_dev_*)
 #include "k_batch_query_dev.h"  // ray casts and sweeps from and into the caller's device memory (k_batch_query_plan_*, k_batch_query_*_dev)
 #include "k_batch_sensor.h"  // ray sensors fixed in the frame of a body, cast from the resident poses (k_batch_sensor_ray)
+#include "k_batch_camera.h"  // depth cameras fixed in the frame of a body, a workgroup per image tile (k_batch_camera_*)
