@@ -503,6 +503,10 @@ MGF_API int64_t mgf_tiles_counter(const mgf_tiles* t, const char* key);
  * "flow6_fcap", "flow6_const_lds", "flow6_poll_waves", "flow6_test_cap" (mode 6: foreign-body slots, constants in LDS,
  * polling waves, a test limit that forces the stand-by kernel); "two_pass_candidates" [0]; "broadphase_tree" [0]; "terrain_tree" [0]; "no_fused_narrowphase" [0] (a world of spheres only runs the sphere-sphere test inside the grid broadphase and lists contacts only; 1 = list every accepted partner); "stream_ordered" [0]; "phase_timing" [0] (HIP events at the tick's phase boundaries: mgf_step_stats::ms_*), "time_solver_kernels" [0] (events around the solver launches: ms_solver_kernels); "pipeline" [1] (mgf_world_step_many enqueues the next tick before it waits for this one); "cell_fill" [16] (bodies per Morton cell, in eighths, beyond which the broadphase grid gets another level); "no_fused_terrain_rows" [0], "no_fused_scene_bounds" [0] (mgf_world_step and mgf_world_begin_tick list the terrain faces of a body and gather the scene bounds inside the integration kernel; 1 = always the separate kernels); "list_capacity";
  * "fused_contacts" [1] (a world of spheres over a small mesh: rows -> constraint records without candidate lists; 0 = the candidate-list kernels);
+ * "contacts_split" [1] (the launch that writes the constraint records from the rows in two: the numbering - ids, (a, b), the bodies' rows of
+ * `b` occurrences - ahead of the block-local solver's table kernels, the partner contacts' 128-byte records beside them, as foreign blocks of the
+ * links launch; where no tables are built inside the collide phase, a launch of their own behind the numbering.  2 = the record blocks first in that
+ * launch, 3 = a launch on the context's second stream, 4 = always a launch of their own: experiments; 0 = one launch, k_contacts_rows);
  * "front_rows" [1] (r06: a world of single-component bodies that are not all spheres - capsules, mixed - or of bodies of up to two components:
  * the pair search runs the pair test on the partners it accepts, the bodies near the mesh get their faces and the body-triangle test in
  * launches of their own, the constraint records are written from the rows; 0 = candidate lists and one narrowphase launch per shape-pair
@@ -543,7 +547,9 @@ MGF_API mgf_status mgf_world_set_option(mgf_world* w, const char* key, int64_t v
  * "fused_contacts_ticks", "early_cells_ticks" (ticks whose collide phase settled on k_pair_brick, on the list-free front end, on
  * k_contacts_spheres without candidate lists, on cells worked out inside k_integrate), "two_pass_ticks", "tree_ticks", "big_parts_ticks"
  * (ticks whose candidate lists were counted and filled in two passes, whose pair search walked the tree instead of the cell grid, whose
- * narrowphase ran the kernels for bodies of more than four components), "max_parts" (the most components any body has)}. */
+ * narrowphase ran the kernels for bodies of more than four components), "contacts_split_fused" / "contacts_split_standalone" (ticks whose partner
+ * records were written beside the links launch / by a launch of their own; both 0: option contacts_split = 0 or another front end),
+ * "contacts_records_pending" (tests: 1 only inside a collide phase being enqueued), "max_parts" (the most components any body has)}. */
 MGF_API mgf_status mgf_world_counter(const mgf_world* w, const char* name, int64_t* out);
 /* Raw device pointers of resident state for zero-copy exchange (multi-GPU halo): name in
  * {"x","q","solver_rec","delta"} (the pub fields `x`, `q` of RigidBodyVec physics.rs:142-154 and what ConstrainedSet::get returns,

@@ -308,14 +308,33 @@ static mgf_status flow6_build_tables(mgf_world* w, uint32_t cap_c, bool* built) 
     *built = true;
     return MGF_OK;
   }
+  const int64_t split = w->records_pending ? w->opt.contacts_split : 0;  // (pending: only inside the collide phase that ran k_contacts_rows_index)
+  if (split == 3) {  // the partner contacts' records in a launch of their own on the side stream, beside both table kernels
+    MGF_TRY(side_fork(w));
+    MGF_TRY(records_launch_alone(w, w->ctx->aux));
+    MGF_TRY(side_done(w));
+  }
   k_flow6_blocks<<<F.nblocks, kF6PrepThreads, 0, s>>>(F, w->links());
   LAUNCH_CHECK();
   // (the channel layout - k_flow6_chan's work - is done by the links launch's last block: kWLinksTicket is its ticket, 0 between launches)
   const uint32_t iters = w->f6_prep_iters ? w->f6_prep_iters : 10u;
   MGF_TRY(w->vsnap.ensure(2 * (size_t)std::max(w->n, 1u), s));
-  k_flow6_links<<<nblk(w->n), kBlock, 0, s>>>(F, w->links(), w->n, w->degb.p, w->rev.p, w->rev_cap, w->word(kWRevRowOverflow), w->sc.p, w->n_owned, w->word(kWGhostCons), w->ext_ptr(),
-                                              w->word(kWLinksTicket), iters, w->srec.p, w->vsnap.p);
-  LAUNCH_CHECK();
+  if (split == 1 || split == 2) {  // ... or as foreign blocks of the links launch
+    LinksArgs L;
+    L.n = w->n; L.degb = w->degb.p; L.rev = w->rev.p; L.rev_cap = w->rev_cap; L.rev_flag = w->word(kWRevRowOverflow); L.sc = w->sc.p; L.n_owned = w->n_owned;
+    L.n_ghost_cons = w->word(kWGhostCons); L.ext = w->ext_ptr(); L.ticket = w->word(kWLinksTicket); L.iters = iters; L.srec = w->srec.p; L.vsnap = w->vsnap.p;
+    const unsigned rb = std::max(1u, nblk(w->rec_A.cap_c));
+    const uint32_t links_first = split == 1 ? 1u : 0u;
+    if (w->rec_sph) k_flow6_links_records<true><<<nblk(w->n) + rb, kBlock, 0, s>>>(F, w->links(), L, w->rec_B, w->rec_A, rb, links_first);
+    else k_flow6_links_records<false><<<nblk(w->n) + rb, kBlock, 0, s>>>(F, w->links(), L, w->rec_B, w->rec_A, rb, links_first);
+    LAUNCH_CHECK();
+    w->records_pending = false; w->ts->split_fused = true;
+  } else {
+    k_flow6_links<<<nblk(w->n), kBlock, 0, s>>>(F, w->links(), w->n, w->degb.p, w->rev.p, w->rev_cap, w->word(kWRevRowOverflow), w->sc.p, w->n_owned, w->word(kWGhostCons), w->ext_ptr(),
+                                                w->word(kWLinksTicket), iters, w->srec.p, w->vsnap.p);
+    LAUNCH_CHECK();
+    if (split == 3) { MGF_TRY(side_join(w)); w->records_pending = false; w->ts->split_fused = true; }
+  }
   w->snap_in_links = true;  // (the velocities at this point; good for a launch that follows with nothing in between: the fused tick's)
   w->flow6_prepped = true;
   w->f6_prep_iters = iters;

@@ -635,8 +635,22 @@ static mgf_status contacts_from_rows(mgf_world* w, const CollidePlan& P, float d
     Q.cons = w->cons_nat.p; Q.ab = w->c_ab.p; Q.degb = w->degb.p; Q.rev = w->rev.p; Q.rev_cap = w->rev_cap; Q.rev_flag = w->word(kWRevRowOverflow); Q.flag = w->word(kWNarrowMismatch); Q.ext = w->ext_ptr();
     k_contacts_rows_parts<<<2 * nblk(P.n), kBlock, 0, P.s>>>(P.B, P.M, Q);  // (entries' blocks, then the same bodies' terrain blocks)
   }
+  else if (w->opt.contacts_split) {  // the numbering now, the partner contacts' records beside the solver's table kernels or behind them (stage_links)
+    if (P.front_rows) k_contacts_rows_index<false><<<A.t_blocks + nblk(P.n), kBlock, 0, P.s>>>(P.B, P.M, A);
+    else k_contacts_rows_index<true><<<nblk(P.n), kBlock, 0, P.s>>>(P.B, P.M, A);
+    w->rec_B = P.B; w->rec_A = A; w->rec_sph = !P.front_rows; w->records_pending = true;
+  }
   else if (P.front_rows) k_contacts_rows<false><<<A.t_blocks + nblk(P.n), kBlock, 0, P.s>>>(P.B, P.M, A);
   else k_contacts_rows<true><<<nblk(P.n), kBlock, 0, P.s>>>(P.B, P.M, A);
+  return MGF_OK;
+}
+// the record half of a split k_contacts_rows in a launch of its own (no tables are built inside this collide phase: another solver mode, a plan
+// that does not fit, a caller's list - or option contacts_split = 4)
+static mgf_status records_launch_alone(mgf_world* w, hipStream_t s) {
+  const unsigned g = std::max(1u, nblk(w->rec_A.cap_c));
+  if (w->rec_sph) k_contacts_rows_records<true><<<g, kBlock, 0, s>>>(w->rec_B, w->rec_A);
+  else k_contacts_rows_records<false><<<g, kBlock, 0, s>>>(w->rec_B, w->rec_A);
+  LAUNCH_CHECK();
   return MGF_OK;
 }
 // 7. the candidate lists from the rows (or the two-pass path's filling pass) - or, in their place, the list-free front ends' records
@@ -748,6 +762,11 @@ static mgf_status stage_links(mgf_world* w, const CollidePlan& P) {
   w->depth = 0;
   bool tables = false;
   if (w->opt.solver_mode == 6 && !w->tick_mode1) MGF_TRY(flow6_build_tables(w, P.cap_c, &tables));
+  if (w->records_pending) {  // (the tables' launch did not take them along)
+    w->records_pending = false;
+    MGF_TRY(records_launch_alone(w, P.s));
+    w->ts->split_alone = true;
+  }
   w->f6_tables_in_collide = tables; w->f6_collide_iters = w->f6_prep_iters;
   if (!tables) MGF_TRY(chain_rows_launch(w, nullptr));
   w->links_ready = !tables;
@@ -771,6 +790,7 @@ static mgf_status collide_enqueue(mgf_world* w, float dt, bool solver_follows = 
   w->ts->two_pass = P.two_pass;
   w->ts->tree = !P.two_pass && !P.use_grid && !P.demo;
   w->ts->big_parts = P.big;
+  w->records_pending = false; w->ts->split_fused = false; w->ts->split_alone = false;
   MGF_TRY(stage_cells(w, P));
   MGF_TRY(stage_side_terrain(w, P));
   MGF_TRY(stage_scatter(w, P));
@@ -929,6 +949,7 @@ static mgf_status collide_process(mgf_world* w, bool* retry) {
   }
   if (*retry) { w->n_cap_retries++; return MGF_OK; }
   w->n_path_ticks[0] += w->ts->brick; w->n_path_ticks[1] += w->ts->front_rows; w->n_path_ticks[2] += w->ts->contacts_fused; w->n_path_ticks[3] += w->ts->cells_early;
+  w->n_split_ticks[0] += w->ts->split_fused; w->n_split_ticks[1] += w->ts->split_alone;
   w->n_path_ticks[4] += w->ts->two_pass; w->n_path_ticks[5] += w->ts->tree; w->n_path_ticks[6] += w->ts->big_parts;
   if (w->opt.wide_list) {  // the wide bodies' limit for the ticks to come (WideSpec, k_bodies.h)
     if (w->wide_tick_on) {  // (the read-back's rmax is the largest half extent of the bodies that were NOT wide)

@@ -21,6 +21,11 @@ struct WorldOptions {
   int64_t pair_brick = 1;              // grid broadphase with the cells staged in LDS (k_pair_brick); 0 = every look-up from global memory (k_pair_grid)
   int64_t no_fused_narrowphase = 0;
   int64_t fused_contacts = 1;          // (r05) a world of spheres: rows -> constraint records in one launch, no candidate lists (k_contacts_spheres; 0: k_lists_spheres + k_setup_pairs)
+  // (r07) k_contacts_rows in two: the numbering (k_contacts_rows_index) ahead of the solver's table kernels, the partner contacts' records beside them.
+  // 1: as the last blocks of k_flow6_links' launch (k_flow6_links_records: the link blocks are all resident, the record blocks fill in around them);
+  // experiments (EXPERIMENTS.md r07): 2: as its first blocks; 3: a launch of their own on the side stream, joined behind the links; 4: a launch of their
+  // own on the main stream, always (what every path without tables in the collide phase does); 0: k_contacts_rows
+  int64_t contacts_split = 1;
   int64_t front_rows = 1;              // (r06) worlds of single-component bodies that are not all spheres: the list-free front end (k_front_rows.h; 0: candidate lists, one narrowphase launch per shape-pair type)
   int64_t front_rows_check = 0;        // tests: the faces k_terrain_near's cheap reject (comp_tri_far) drops go through the reference's tests as well; a contact among them is an internal error
   int64_t side_stream = 1;             // (r06) the terrain kernels of the list-free front end on the context's second stream, beside the pair search (0: one stream)
@@ -145,6 +150,12 @@ struct mgf_world {
   // [0] k_pair_brick, [1] the list-free front end (k_front_rows.h), [2] k_contacts_spheres' rows -> records without candidate lists,
   // [3] cells and ranks worked out by k_integrate over the last tick's box
   uint64_t n_path_ticks[7] = {0, 0, 0, 0, 0, 0, 0};
+  // option contacts_split: the record half of this collide phase's k_contacts_rows is still to be launched (set by contacts_from_rows, consumed by
+  // stage_links - fused into k_flow6_links' launch or launched alone; never true outside collide_enqueue), its arguments, and the ticks by path
+  bool records_pending = false, rec_sph = false;
+  Bodies rec_B;
+  ContactsSpheres rec_A;
+  uint64_t n_split_ticks[2] = {0, 0};  // [0] fused into the links launch (or beside it on the side stream), [1] a launch of their own
   DBuf<float4> wide_list;
   // mgf_world_raycast_many / mgf_world_overlap_aabb_many (host_query.inc): the query's own grid and lists - nothing of the tick's is read or written
   DBuf<float4> q_bc, q_br;
@@ -295,6 +306,7 @@ struct mgf_world {
     bool cells_early = false;         // ... took its cells and ranks from k_integrate (over the last tick's box)
     bool two_pass = false;            // ... counted and filled its candidate lists in two passes (k_candidates)
     bool tree = false;                // ... searched its pairs in the tree (k_pair_rows), not in the cell grid
+    bool split_fused = false, split_alone = false;  // ... wrote its partner records beside k_flow6_links / in a launch of their own (option contacts_split)
     bool big_parts = false;           // ... ran k_narrow_pairs_big / k_narrow_terrain_big (a body of more than kMaxParts components)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // the side stream's start and end inside the tick (no timing: created on first use)
     uint32_t* pin = nullptr;
@@ -418,6 +430,7 @@ static const OptionEntry kOptionTable[] = {
     {"no_fused_narrowphase", &WorldOptions::no_fused_narrowphase, 1, 0, nullptr, false, false},
     {"pair_brick", &WorldOptions::pair_brick, 1, 0, nullptr, false, false},
     {"fused_contacts", &WorldOptions::fused_contacts, 1, 0, nullptr, false, false},
+    {"contacts_split", &WorldOptions::contacts_split, 0, 4, "contacts_split: 0..4", false, false},
     {"front_rows", &WorldOptions::front_rows, 1, 0, nullptr, false, false},
     {"front_rows_check", &WorldOptions::front_rows_check, 1, 0, nullptr, false, false},
     {"side_stream", &WorldOptions::side_stream, 1, 0, nullptr, false, false},
@@ -615,6 +628,9 @@ extern "C" mgf_status mgf_world_counter(const mgf_world* w, const char* name, in
   if (!strcmp(name, "two_pass_ticks")) { *out = (int64_t)w->n_path_ticks[4]; return MGF_OK; }
   if (!strcmp(name, "tree_ticks")) { *out = (int64_t)w->n_path_ticks[5]; return MGF_OK; }
   if (!strcmp(name, "big_parts_ticks")) { *out = (int64_t)w->n_path_ticks[6]; return MGF_OK; }
+  if (!strcmp(name, "contacts_split_fused")) { *out = (int64_t)w->n_split_ticks[0]; return MGF_OK; }
+  if (!strcmp(name, "contacts_split_standalone")) { *out = (int64_t)w->n_split_ticks[1]; return MGF_OK; }
+  if (!strcmp(name, "contacts_records_pending")) { *out = w->records_pending ? 1 : 0; return MGF_OK; }
   if (!strcmp(name, "max_parts")) { *out = (int64_t)w->max_parts; return MGF_OK; }
   if (!strcmp(name, "wide_ticks")) { *out = (int64_t)w->n_wide_ticks; return MGF_OK; }
   if (!strcmp(name, "wide_overflows")) { *out = (int64_t)w->n_wide_overflows; return MGF_OK; }

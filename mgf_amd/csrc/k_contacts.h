@@ -1243,6 +1243,140 @@ __global__ __launch_bounds__(kBlock) void k_contacts_rows(Bodies B, TerrainDev M
   }
 }
 
+// k_contacts_rows in two (option contacts_split): the numbering and the records apart.  What the solver's table kernels read - ab, degb, rev, base -
+// is the index half's; the partner contacts' 128-byte records are first read by the solver, so their half (two packed copies, two srec loads, the
+// pair test, ContactConstraint::new, the transposed store: bandwidth) runs BESIDE the table kernels' chains of dependent look-ups, as foreign
+// blocks of k_flow6_links' launch, or as a launch of its own where no tables are built.
+// The index half: k_contacts_rows without the partner contacts' records.  The terrain contacts' records stay here (few; their slot cannot be
+// recovered from ab).  (A contact the pair test would refuse is numbered all the same: the record half raises the flag, the tick is an error.)
+template <bool SPH>
+__global__ __launch_bounds__(kBlock) void k_contacts_rows_index(Bodies B, TerrainDev M, ContactsSpheres A) {
+  __shared__ uint32_t s_j[kCsEntCap];           // the pass's partner contacts in canonical order: partner ...
+  __shared__ uint16_t s_b[kCsEntCap];           // ... and owner (the block's body)
+  __shared__ uint32_t s_cbase[kBlock];          // body -> id of its first partner constraint minus its first entry's position
+  __shared__ uint32_t s_wave[kBlock / 64];
+  if (A.sc->fail) return;  // (the scan's closing thread found a flag up or a capacity exceeded: the host re-runs the phase)
+  if (blockIdx.x < A.t_blocks) {  // ---- ContactConstraint::new for the terrain contacts (world.rs:243-251), a lane per slot
+    const uint32_t p = blockIdx.x * (uint32_t)kBlock + threadIdx.x, region = p / A.region_cap;
+    if (region >= A.regions || p - region * A.region_cap >= min(A.slot_cnt[region * A.cnt_stride], A.region_cap)) return;
+    const NContact in0 = A.t_out[2 * (size_t)p];
+    const uint32_t nc = f2u(in0.lb.w);
+    if (nc == 0) return;
+    const uint32_t i = A.slot_body[p], tp = A.tpos[i];
+    uint32_t c = A.base[i];
+    for (uint32_t q = tp; q < p; ++q) c += f2u(A.t_out[2 * (size_t)q].lb.w);  // the contacts of the body's earlier faces (its slots are a run, in Mesh::contacts' order)
+    const V3 mx = mk3(M.x[0], M.x[1], M.x[2]);
+    const BodyDyn Ad = load_dyn(B.srec, i), S = static_dyn();
+    const BodyPack Pa = load_pack(B, i, false);
+    for (uint32_t k = 0; k < nc; ++k, ++c) {
+      const NContact in = k == 0 ? in0 : A.t_out[2 * (size_t)p + k];
+      // Static{ center: terrain.center(), friction: 0.0 } world.rs:247
+      const CRec r = make_constraint(i, kNone, Ad, xyz(Pa.ei), Pa.ei.w, Pa.dl.w, S, mx, 0.0f, 0.0f, xyz(in.n), xyz(in.la), xyz(in.lb), A.dt, A.baumgarte, A.slop);
+      store_crec(&A.cons[c], r);
+      A.ab[c] = make_uint2(i, kNone);
+    }
+    return;
+  }
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint32_t i0 = (blockIdx.x - A.t_blocks) * (uint32_t)kBlock, i = i0 + (uint32_t)t;
+  uint32_t np = 0, run = 0, base_i = 0;
+  if (i < A.n) { np = A.p_cnt[i]; run = A.tcn[i]; base_i = A.base[i]; }
+  // ---- where the body's partner contacts start in the block's list
+  uint32_t inc_p = np;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(inc_p, o); if (lane >= o) inc_p += v; }
+  if (lane == 63) s_wave[wv] = inc_p;
+  __syncthreads();
+  uint32_t before_p = 0, totalp = 0;
+  for (int k = 0; k < kBlock / 64; ++k) { const uint32_t v = s_wave[k]; if (k < wv) before_p += v; totalp += v; }
+  const uint32_t excl_p = before_p + inc_p - np;
+  const uint32_t* rp = A.rows_p + (size_t)i * kRowCap;
+  if (np) cs_list_row(rp, np, A.ext, excl_p, 0u, (uint32_t)t, s_j, s_b);
+  s_cbase[t] = base_i + run - excl_p;
+  // ---- ContactConstraint::new for the terrain contacts (world.rs:243-251): the body's own thread (setup_terrain_one's work)
+  if (run && A.t_blocks == 0u) {
+    const uint32_t nt = A.t_cnt[i], tp = A.tpos[i];
+    const V3 mx = mk3(M.x[0], M.x[1], M.x[2]);
+    const BodyDyn Ad = load_dyn(B.srec, i), S = static_dyn();
+    const BodyPack Pa = load_pack(B, i, false);
+    uint32_t c = base_i;
+    for (uint32_t a = 0; a < nt; ++a) {
+      const NContact in0 = A.t_out[2 * (size_t)(tp + a)];
+      const uint32_t nc = f2u(in0.lb.w);
+      for (uint32_t k = 0; k < nc; ++k, ++c) {
+        const NContact in = k == 0 ? in0 : A.t_out[2 * (size_t)(tp + a) + k];
+        // Static{ center: terrain.center(), friction: 0.0 } world.rs:247
+        const CRec r = make_constraint(i, kNone, Ad, xyz(Pa.ei), Pa.ei.w, Pa.dl.w, S, mx, 0.0f, 0.0f, xyz(in.n), xyz(in.la), xyz(in.lb), A.dt, A.baumgarte, A.slop);
+        store_crec(&A.cons[c], r);
+        A.ab[c] = make_uint2(i, kNone);
+      }
+    }
+  }
+  // ---- the partner contacts' ids, and their rows: the block's list, kCsEntCap entries per pass, an entry per thread
+  __syncthreads();  // (the list's first pass, s_cbase)
+  for (uint32_t w0 = 0; w0 < totalp; w0 += kCsEntCap) {
+    if (w0) {  // (rare: a block with more contacts than a pass holds lists the next window)
+      __syncthreads();
+      if (np) cs_list_row_again(rp, np, A.ext, excl_p, w0, (uint32_t)t, s_j, s_b);
+      __syncthreads();
+    }
+    const uint32_t m = min(totalp - w0, kCsEntCap);
+    for (uint32_t e = (uint32_t)t; e < m; e += (uint32_t)kBlock) {
+      const uint32_t b = s_b[e], j = s_j[e], ia = i0 + b;
+      const uint32_t c = s_cbase[b] + w0 + e;
+      A.ab[c] = make_uint2(ia, j);
+      // body j's row of the constraints it takes part in as `b` (k_chain_rows); as `a` a body owns a contiguous id range
+      const uint32_t pos = atomicAdd(&A.degb[j], 1u);
+      if (pos < A.rev_cap) A.rev[(size_t)j * A.rev_cap + pos] = RevEnt{c, ia, order_id(A.ext, ia), 0u};
+      else *A.rev_flag = 1u;
+    }
+  }
+}
+// The record half: a thread per constraint id (the grid is sized from the list's capacity: its length is on the device).  ids are dense, so a
+// wave's 64 records are consecutive and leave as whole lines through the same LDS transpose.  Terrain constraints (b = kNone) have their records.
+template <bool SPH>
+__device__ __forceinline__ void contacts_records_job(const Bodies& B, const ContactsSpheres& A, uint32_t job_block) {
+  __shared__ float4 s_w[kBlock / 64][7 * 65];  // a wave's records on their way out (see k_setup_pairs)
+  __shared__ uint32_t s_c[kBlock / 64][64];
+  if (A.sc->fail) return;  // (the index half did nothing either: the host re-runs the phase)
+  const uint32_t C = min(A.sc->C, A.cap_c);
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint32_t c = job_block * (uint32_t)kBlock + (uint32_t)t;
+  if (c - (uint32_t)lane >= C) return;  // (the whole wave: no barrier below)
+  uint32_t cr = kNone;
+  if (c < C) {
+    const uint2 e = A.ab[c];
+    const uint32_t ia = e.x, j = e.y;
+    if (j != kNone && ia < A.n && j < A.n) {
+      const BodyPack Pa = load_pack(B, ia, true), Pb = load_pack(B, j, true);
+      const Comp Xa = pack_comp<SPH>(B, ia, Pa), Xb = pack_comp<SPH>(B, j, Pb);  // as k_narrow_pairs<KA, KB>
+      LocalContact lc;
+      if (!comp_pair_local(Xa, xyz(Pa.dl), Xb, xyz(Pb.dl), &lc)) {
+        *A.flag = 1u;  // the broadphase's pair test and this one disagree about a contact
+      } else {
+        const V3 nrm = (mk3(0.0f, 0.0f, 0.0f) + lc.g.n) / 1.0f;  // Manifold::from(pruner) of one contact (manifold.rs:135-140)
+        const BodyDyn Ad = load_dyn(B.srec, ia), Bd = load_dyn(B.srec, j);
+        const CRec r = make_constraint(ia, j, Ad, xyz(Pa.ei), Pa.ei.w, Pa.dl.w, Bd, xyz(Pb.ei), Pb.ei.w, Pb.dl.w, nrm, lc.la, lc.lb, A.dt, A.baumgarte, A.slop);
+        const float4* rw = reinterpret_cast<const float4*>(&r);
+#pragma unroll
+        for (int k = 0; k < 7; ++k) s_w[wv][k * 65 + lane] = rw[k];
+        cr = c;
+      }
+    }
+  }
+  float4* out = reinterpret_cast<float4*>(A.cons);
+  s_c[wv][lane] = cr;
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (a wave's LDS accesses are served in order; the wave reads only what it wrote)
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    const int rec = it * 8 + (lane >> 3), k = lane & 7;
+    const uint32_t cw = s_c[wv][rec];
+    if (cw != kNone && k < 7) out[(size_t)cw * 8 + k] = s_w[wv][k * 65 + rec];
+  }
+}
+template <bool SPH>
+__global__ __launch_bounds__(kBlock) void k_contacts_rows_records(Bodies B, ContactsSpheres A) { contacts_records_job<SPH>(B, A, blockIdx.x); }
+
 // ContactConstraint::new (solver.rs:101-191) for caller-built manifolds on the resident RigidBodyVec (mgf_constraints_new):
 // one thread per (manifold, contact) row.  obj_a is Dynamic; obj_b Dynamic or Static{center, friction} (b == kNone).
 struct ManifoldRow { uint32_t a, b; float cb[3], fric_b; float n[3], t0[3], t1[3], la[3], lb[3]; };

@@ -242,8 +242,9 @@ __device__ __forceinline__ uint32_t f6_chan_slot(uint32_t* keys, uint32_t key1, 
 // this kernel with a guard - for the stand-by when a block did not fit).
 struct F6Ent { uint32_t home, slot, role, c, bref; };
 __device__ __forceinline__ void f6_links_body(const Flow6& F, const ConsLinks& K, uint32_t n, const uint32_t* degb, RevEnt* rev, uint32_t rev_cap,
-                                              const uint32_t* rev_flag, StepCounts* sc, uint32_t n_owned, uint32_t* n_ghost_cons, const uint32_t* ext) {
-  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+                                              const uint32_t* rev_flag, StepCounts* sc, uint32_t n_owned, uint32_t* n_ghost_cons, const uint32_t* ext,
+                                              uint32_t job_block) {
+  const uint32_t t = job_block * kBlock + threadIdx.x;
   // constraints whose obj_a is a ghost (ids are ascending in obj_a): the copies of seam constraints (tiles count them once)
   if (t == 0) *n_ghost_cons = (sc->fail || *rev_flag) ? 0u : F.base[n] - F.base[n_owned];
   if (*rev_flag) {
@@ -388,20 +389,22 @@ __device__ __forceinline__ uint32_t f6_chan_one(const Flow6& F, uint32_t hs) {
 // The tick's launch: the links, and - by the block that finishes last (a ticket; the edge counts are complete when every block's
 // atomics have been acknowledged) - the channel layout, which used to be a launch of its own (k_flow6_chan: still there for a
 // caller's list and for a changed iteration count).
-__global__ __launch_bounds__(kBlock) void k_flow6_links(Flow6 F, ConsLinks K, uint32_t n, const uint32_t* degb, RevEnt* rev, uint32_t rev_cap,
-                                                        const uint32_t* rev_flag, StepCounts* sc, uint32_t n_owned, uint32_t* n_ghost_cons,
-                                                        const uint32_t* ext, uint32_t* ticket, uint32_t iters, const float4* srec, float4* vsnap) {
+// (job_block of job_blocks: the launch may carry foreign blocks - k_flow6_links_records - which the ticket does not count)
+__device__ __forceinline__ void f6_links_job(const Flow6& F, const ConsLinks& K, uint32_t n, const uint32_t* degb, RevEnt* rev, uint32_t rev_cap,
+                                             const uint32_t* rev_flag, StepCounts* sc, uint32_t n_owned, uint32_t* n_ghost_cons,
+                                             const uint32_t* ext, uint32_t* ticket, uint32_t iters, const float4* srec, float4* vsnap,
+                                             uint32_t job_block, uint32_t job_blocks) {
   {  // the velocities as Solver::solve is about to find them (k_solver_snapshot's work on the way: the solve follows this launch in the fused tick)
-    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t t = job_block * kBlock + threadIdx.x;
     // (not in a tick that is being skipped - a speculative one behind a tick that failed or gave up: the copy in place is that tick's)
     if (vsnap && t < n && !sc->fail) { vsnap[2 * (size_t)t] = srec[4 * (size_t)t]; vsnap[2 * (size_t)t + 1] = srec[4 * (size_t)t + 1]; }
   }
-  f6_links_body(F, K, n, degb, rev, rev_cap, rev_flag, sc, n_owned, n_ghost_cons, ext);
+  f6_links_body(F, K, n, degb, rev, rev_cap, rev_flag, sc, n_owned, n_ghost_cons, ext, job_block);
   if (!ticket) return;
   __shared__ uint32_t s_last;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's atomics on the edge counts are done ...
   __syncthreads();                                   // ... and the block's
-  if (threadIdx.x == 0) s_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u ? 1u : 0u;
+  if (threadIdx.x == 0) s_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == job_blocks - 1u ? 1u : 0u;
   __syncthreads();
   if (!s_last) return;
   // (the totals through the block, not through 256 atomics on one word: those alone took 6 us)
@@ -421,6 +424,27 @@ __global__ __launch_bounds__(kBlock) void k_flow6_links(Flow6 F, ConsLinks K, ui
     *ticket = 0u;  // (re-armed for the next tick)
     if (__hip_atomic_load(F.fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) atomicOr(F.tick_fail, kFailFlow6);
   }
+}
+__global__ __launch_bounds__(kBlock) void k_flow6_links(Flow6 F, ConsLinks K, uint32_t n, const uint32_t* degb, RevEnt* rev, uint32_t rev_cap,
+                                                        const uint32_t* rev_flag, StepCounts* sc, uint32_t n_owned, uint32_t* n_ghost_cons,
+                                                        const uint32_t* ext, uint32_t* ticket, uint32_t iters, const float4* srec, float4* vsnap) {
+  f6_links_job(F, K, n, degb, rev, rev_cap, rev_flag, sc, n_owned, n_ghost_cons, ext, ticket, iters, srec, vsnap, blockIdx.x, gridDim.x);
+}
+// ... with the record half of the split k_contacts_rows (k_contacts.h) as foreign blocks of the launch: the links are chains of dependent look-ups
+// that leave the memory system mostly idle, the records are bandwidth - and nothing here reads them.  links_first: the link blocks lead - they are
+// all resident at four waves per SIMD, and the record blocks fill in around them (r07: 57.7 us per launch on the falling pile against 67.4 with the
+// record blocks first, which keep the longest chains waiting; 46.8 + 25.8 one behind the other).  The ticket counts link blocks only.
+struct LinksArgs {
+  uint32_t n; const uint32_t* degb; RevEnt* rev; uint32_t rev_cap; const uint32_t* rev_flag; StepCounts* sc; uint32_t n_owned; uint32_t* n_ghost_cons;
+  const uint32_t* ext; uint32_t* ticket; uint32_t iters; const float4* srec; float4* vsnap;
+};
+template <bool SPH>
+__global__ __launch_bounds__(kBlock) void k_flow6_links_records(Flow6 F, ConsLinks K, LinksArgs L, Bodies B, ContactsSpheres A, uint32_t rec_blocks, uint32_t links_first) {
+  const uint32_t link_blocks = gridDim.x - rec_blocks;
+  const bool is_rec = links_first ? blockIdx.x >= link_blocks : blockIdx.x < rec_blocks;
+  if (is_rec) { contacts_records_job<SPH>(B, A, links_first ? blockIdx.x - link_blocks : blockIdx.x); return; }
+  f6_links_job(F, K, L.n, L.degb, L.rev, L.rev_cap, L.rev_flag, L.sc, L.n_owned, L.n_ghost_cons, L.ext, L.ticket, L.iters, L.srec, L.vsnap,
+               links_first ? blockIdx.x : blockIdx.x - rec_blocks, link_blocks);
 }
 // One wave per block (its kF6Chan hash slots = the wave's lanes): where each incoming channel's messages start inside the
 // block's region of the channel buffer (exclusive prefix of the per-iteration edge counts), and whether the region suffices.

@@ -42,6 +42,9 @@
 //                      beside the pair search); the pair search pools the accepted partners of a block's queries that may touch
 //                      and runs the pair test - or the two-part manifold, raw contacts staged in LDS - a lane each, the rows
 //                      hold contacts only; records from the rows.  k_contacts_rows<true> is r05's k_contacts_spheres.
+//   k_contacts_rows_index<SPH> / k_contacts_rows_records<SPH> / k_flow6_links_records<SPH> (r07, option contacts_split)
+//                      k_contacts_rows in two: ids, (a, b), degb / rev rows and the terrain contacts' records first; the partner contacts'
+//                      records - what the solver's table kernels never read - as the last blocks of the links launch, or a launch of their own
 //   k_pair_wide (r06)  the few bodies whose fat box is far larger than the rest's (WideSpec, k_bodies.h: kept out of the scene
 //                      bounds and rmax by k_integrate, never partners of the grid's pair search) find their partners-to-be
 //                      from their own side: a workgroup per listed body
