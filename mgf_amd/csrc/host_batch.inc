@@ -113,6 +113,13 @@ static void batch_offsets(mgf_batch* b) {
   b->h_off.assign(b->K + 1, 0u);
   for (uint32_t k = 0; k < b->K; ++k) b->h_off[k + 1] = b->h_off[k] + b->h_n[k];
 }
+// the bodies of the largest of the worlds [k0, k0 + nw), of the whole batch: what a kernel with a workgroup per world sizes its dynamic LDS by
+static uint32_t batch_nmax(const mgf_batch* b, uint32_t k0, uint32_t nw) {
+  uint32_t nmax = 0;
+  for (uint32_t k = k0; k < k0 + nw; ++k) nmax = std::max(nmax, b->h_n[k]);
+  return nmax;
+}
+static uint32_t batch_nmax(const mgf_batch* b) { return batch_nmax(b, 0u, b->K); }
 // col0 / col1 of the bodies the last mgf_batch_step ran on: every world has completed every tick of the call (a tick that was undone was
 // run again before the call returned), so bpk words 0 and 3 are their colliders.  The launches that follow on the stream see the rows.
 static mgf_status batch_cols_refresh(mgf_batch* b, int64_t* launches) {
@@ -644,8 +651,7 @@ extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int6
   mgf_ctx* ctx = b->ctx;
   hipStream_t s = ctx->stream;
   const uint32_t K = b->K, NT = (uint32_t)n_ticks;
-  uint32_t nmax = 0;
-  for (uint32_t n : b->h_n) nmax = std::max(nmax, n);
+  const uint32_t nmax = batch_nmax(b);
   const uint32_t lds = 80u * nmax;  // k_batch_solve: 64 bytes a body of solver records, four words of counts (k_batch_front: 64 + 4, k_batch_setup: 12)
   if (lds > b->lds_set) {
     MGF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch_front), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(68u * MGF_BATCH_MAX_BODIES)));

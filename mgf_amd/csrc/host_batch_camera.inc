@@ -22,9 +22,7 @@ extern "C" mgf_status mgf_batch_set_cameras(mgf_batch* b, const mgf_batch_camera
   uint64_t pixels = 0, n_tiles = 0;
   for (size_t i = 0; i < n; ++i) {
     const mgf_batch_camera& c = cams[i];
-    if (c.world < 0 || (uint32_t)c.world >= b->K) return fail(MGF_ERR_INVALID, "world index out of range: the rig was not changed");
-    if (c.body < 0 || (uint32_t)c.body >= b->h_n[(size_t)c.world]) return fail(MGF_ERR_INVALID, "body index out of range: the rig was not changed");
-    if (c.flags & ~MGF_SENSOR_IGNORE_SELF) return fail(MGF_ERR_INVALID, "a camera's flags hold a bit beyond MGF_SENSOR_IGNORE_SELF: the rig was not changed");
+    MGF_TRY(batch_rig_ref_check(b, c.world, c.body, c.flags, "camera"));
     if (c.reserved != 0) return fail(MGF_ERR_INVALID, "a camera's reserved word is not 0: the rig was not changed");
     if (c.width < 1 || c.width > MGF_CAMERA_MAX_SIDE || c.height < 1 || c.height > MGF_CAMERA_MAX_SIDE)
       return fail(MGF_ERR_INVALID, "a camera's width or height is outside [1, 4096]: the rig was not changed");
@@ -58,16 +56,12 @@ extern "C" int64_t mgf_batch_camera_pixels(const mgf_batch* b) { return b ? (int
 // the rig onto the device (n > 0): tiles | records
 static mgf_status batch_cameras_up(mgf_batch* b) {
   if (!b->c_stale) return MGF_OK;
-  const size_t n = b->c_rig.size(), n_tiles = b->c_tiles.size();
   for (const mgf_batch_camera& r : b->c_rig)
     if ((uint32_t)r.body >= b->h_n[(size_t)r.world]) return fail(MGF_ERR_INVALID, "internal error: a camera names a body its world does not hold");
-  const size_t total = n_tiles + 4 * n;
-  std::vector<float4> h(total);
-  memcpy(h.data(), b->c_tiles.data(), 16 * n_tiles);
-  memcpy(h.data() + n_tiles, b->c_rig.data(), 64 * n);
-  MGF_TRY(b->c_dev.ensure(total, b->ctx->stream));
-  MGF_TRY(h2d(b->ctx, b->c_dev.p, h.data(), total));
-  b->c_o_rig = n_tiles;
+  const RigSection sec[2] = {{b->c_tiles.data(), 16 * b->c_tiles.size()}, {b->c_rig.data(), 64 * b->c_rig.size()}};
+  size_t off[2];
+  MGF_TRY(batch_rig_upload(b, b->c_dev, sec, 2, off));
+  b->c_o_rig = off[1];
   b->c_stale = false;
   return MGF_OK;
 }
@@ -81,15 +75,13 @@ static mgf_status batch_camera_run(mgf_batch* b, int32_t kinds_mask, float* dept
   MGF_TRY(batch_cameras_up(b));
   MGF_TRY(batch_cols_refresh(b, &b->q_launches));
   hipStream_t s = b->ctx->stream;
-  const bool obstacles = (kinds_mask & MGF_QUERY_OBSTACLES) && b->o_worlds;  // as batch_query_run
+  const bool obstacles = batch_has_obstacles(b, kinds_mask);
   if (obstacles) {  // the obstacle pass takes the particles, the records and the worlds up again
     if (!parts_dev) { MGF_TRY(b->c_parts.ensure(7 * n, s)); parts_dev = b->c_parts.p; }
     if (!out_dev) { MGF_TRY(b->q_out.ensure(7 * n, s)); out_dev = b->q_out.p; }
     MGF_TRY(b->c_world.ensure(n, s));
   }
-  uint32_t nmax = 0;
-  for (uint32_t c : b->h_n) nmax = std::max(nmax, c);
-  const uint32_t lds = 36u * nmax + 16u;
+  const uint32_t lds = 36u * batch_nmax(b) + 16u;
   BatchCameraArgs A;
   memset(&A, 0, sizeof(A));
   A.col0 = b->dm[mgf_batch::ACOL0].p; A.col1 = b->dm[mgf_batch::ACOL1].p; A.w_off = b->d_off.p;
@@ -106,10 +98,7 @@ static mgf_status batch_camera_run(mgf_batch* b, int32_t kinds_mask, float* dept
   LAUNCH_CHECK();
   b->q_launches += MGF_BATCH_CAMERA_LAUNCHES;
   if (obstacles) {
-    k_batch_query_ray_obstacles<<<batch_dev_blocks(n), kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, b->c_world.p, 0u, reinterpret_cast<const ParticleIn*>(parts_dev),
-                                                                           (uint32_t)n, out_dev);
-    LAUNCH_CHECK();
-    ++b->q_launches;
+    MGF_TRY(batch_ray_obstacles(b, b->c_world.p, 0u, reinterpret_cast<const ParticleIn*>(parts_dev), n, out_dev));
     if (depth_dev) {  // (hits alone: the records are final as they stand)
       k_batch_camera_depth<<<batch_dev_blocks(n), kBatchBlock, 0, s>>>(out_dev, parts_dev, (uint32_t)n, depth_dev);
       LAUNCH_CHECK();
@@ -134,7 +123,7 @@ extern "C" mgf_status mgf_batch_cast_cameras(mgf_batch* b, int32_t kinds_mask, f
   size_t n = 0;
   MGF_TRY(batch_camera_args(b, kinds_mask, depth, hits, cap, &n));
   MGF_TRY(ctx_bind(b->ctx));
-  b->q_launches = 0; b->q_run_ms = 0.0f;
+  batch_call_begin(b);
   if (n == 0) return MGF_OK;
   hipStream_t s = b->ctx->stream;
   if (depth) MGF_TRY(b->c_depth.ensure(n, s));
@@ -157,10 +146,9 @@ extern "C" mgf_status mgf_batch_cast_cameras_dev(mgf_batch* b, int32_t kinds_mas
   MGF_TRY(dev_span(b->ctx, hits_dev, 28 * n, "hits_dev"));
   MGF_TRY(dev_span(b->ctx, parts_out_dev, 28 * n, "parts_out_dev"));
   // (the obstacle pass reads the particles again after the tile pass wrote hits, and the depth pass reads both)
-  if (dev_bytes_overlap(depth_dev, 4 * n, hits_dev, 28 * n)) return fail(MGF_ERR_INVALID, "depth_dev overlaps hits_dev");
-  if (dev_bytes_overlap(depth_dev, 4 * n, parts_out_dev, 28 * n)) return fail(MGF_ERR_INVALID, "depth_dev overlaps parts_out_dev");
-  if (dev_bytes_overlap(hits_dev, 28 * n, parts_out_dev, 28 * n)) return fail(MGF_ERR_INVALID, "hits_dev overlaps parts_out_dev");
-  b->q_launches = 0; b->q_run_ms = 0.0f;
+  const DevBytes arrays[3] = {{depth_dev, 4 * n, "depth_dev"}, {hits_dev, 28 * n, "hits_dev"}, {parts_out_dev, 28 * n, "parts_out_dev"}};
+  MGF_TRY(dev_outputs_overlap(arrays, 3, 3));
+  batch_call_begin(b);
   if (n == 0) return MGF_OK;
   return batch_camera_run(b, kinds_mask, depth_dev, reinterpret_cast<int32_t*>(hits_dev), reinterpret_cast<float*>(parts_out_dev));
 }

@@ -140,12 +140,11 @@ extern "C" mgf_status mgf_batch_read_body_contacts_dev(mgf_batch* b, int64_t wor
   MGF_TRY(batch_range(b, world, &first, &n));
   if ((int64_t)n > cap) return fail(MGF_ERR_CAPACITY, "buffer too small");
   MGF_TRY(dev_span(b->ctx, out_dev, 24 * n, "out_dev"));
-  b->q_launches = 0; b->q_run_ms = 0.0f;
+  batch_call_begin(b);
   if (n == 0) return MGF_OK;
   MGF_TRY(batch_push(b));
   const uint32_t k0 = world < 0 ? 0u : (uint32_t)world, nw = world < 0 ? b->K : 1u;
-  uint32_t nmax = 0;
-  for (uint32_t k = k0; k < k0 + nw; ++k) nmax = std::max(nmax, b->h_n[k]);
+  const uint32_t nmax = batch_nmax(b, k0, nw);
   BatchContactsArgs A;
   A.cons = b->cons.p; A.rows = b->rows.p; A.c_off = b->d_coff.p; A.c_count = b->d_ccount.p; A.w_off = b->d_off.p;
   A.world0 = k0;

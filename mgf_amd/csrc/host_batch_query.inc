@@ -6,7 +6,9 @@
 // neither the number of worlds nor the number of queries - and downloads the hits: one host wait per call.  Nothing of the tick's state
 // is written; of it only bpk is read, once, by the collider gather behind a mgf_batch_step (batch_cols_refresh).
 // batch_query_args / _worlds / _open / _upload are every front end's steps ahead of its launches, the box query's
-// (host_batch_observe.inc) too; the kinds_mask and tag checks are host_query.inc's.
+// (host_batch_observe.inc) too; the kinds_mask and tag checks are host_query.inc's.  What every cast of a batch shares beyond that is
+// here once, for the device-pointer calls, the sensors and the cameras (the files behind this one) as well: batch_call_begin,
+// batch_work_args, batch_ray_lds, and the passes with a lane per query - batch_ray_obstacles, batch_sweep_tail.
 
 extern "C" mgf_status mgf_batch_read_colliders(mgf_batch* b, int64_t world, mgf_moving_component* out, int64_t cap) {
   if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
@@ -62,12 +64,50 @@ struct BatchQueryPlan {
   }
 };
 
+// every call that counts its launches and times its passes opens with this ("query_launches", "query_run_ns")
+static void batch_call_begin(mgf_batch* b) { b->q_launches = 0; b->q_run_ms = 0.0f; }
+
 // the checks that need the handle; the call's counters start from zero
 static mgf_status batch_query_open(mgf_batch* b, const int32_t* world, size_t n) {
   MGF_TRY(ctx_bind(b->ctx));
   for (size_t i = 0; i < n; ++i)
     if ((uint32_t)world[i] >= b->K) return fail(MGF_ERR_INVALID, "world index out of range");
-  b->q_launches = 0; b->q_run_ms = 0.0f;
+  batch_call_begin(b);
+  return MGF_OK;
+}
+
+// What every kernel with a workgroup per work item reads of the handle, and the dynamic LDS of those that cast rays or sweep: 32 bytes
+// a body of the largest world, kBatchQueryRed words (at most 32 KB + 256 bytes: two workgroups a CU at the largest world)
+static void batch_work_args(const mgf_batch* b, BatchWorkArgs* A) {
+  A->col0 = b->dm[mgf_batch::ACOL0].p; A->col1 = b->dm[mgf_batch::ACOL1].p; A->w_off = b->d_off.p;
+}
+static uint32_t batch_ray_lds(const mgf_batch* b) { return 32u * batch_nmax(b) + 16u * kBatchQueryRed; }
+
+// The passes with a lane per query behind a body pass, for every front end of the casts.  Which of them a call has: the sweeps' face
+// pass when a world of the batch has a terrain to sweep against, the obstacle pass when one has an obstacle to meet.
+static bool batch_has_faces(const mgf_batch* b, int32_t kinds_mask) { return (kinds_mask & MGF_QUERY_TERRAIN) && b->t_worlds; }
+static bool batch_has_obstacles(const mgf_batch* b, int32_t kinds_mask) { return (kinds_mask & MGF_QUERY_OBSTACLES) && b->o_worlds; }
+// worlds: a query's world by the caller's index, or (null) every world has `per` queries; parts / casts, out: n records of device memory
+static mgf_status batch_ray_obstacles(mgf_batch* b, const int32_t* worlds, uint32_t per, const ParticleIn* parts, size_t n, int32_t* out) {
+  k_batch_query_ray_obstacles<<<(unsigned)((n + kBatchBlock - 1) / kBatchBlock), kBatchBlock, 0, b->ctx->stream>>>(batch_obstacles(b), b->t_desc.p, worlds, per, parts,
+                                                                                                             (uint32_t)n, out);
+  LAUNCH_CHECK();
+  ++b->q_launches;
+  return MGF_OK;
+}
+static mgf_status batch_sweep_tail(mgf_batch* b, bool faces, bool obstacles, const int32_t* worlds, uint32_t per, const MovingIn* casts, size_t n, int32_t* out) {
+  const unsigned nb = (unsigned)((n + kBatchBlock - 1) / kBatchBlock);
+  hipStream_t s = b->ctx->stream;
+  if (faces) {
+    k_batch_query_sweep_faces<<<nb, kBatchBlock, 0, s>>>(batch_terrains(b), worlds, per, casts, (uint32_t)n, out);
+    LAUNCH_CHECK();
+    ++b->q_launches;
+  }
+  if (obstacles) {
+    k_batch_query_sweep_obstacles<<<nb, kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, worlds, per, casts, (uint32_t)n, out);
+    LAUNCH_CHECK();
+    ++b->q_launches;
+  }
   return MGF_OK;
 }
 
@@ -98,15 +138,13 @@ static mgf_status batch_query_upload(mgf_batch* b, const int32_t* world, const v
   MGF_TRY(b->q_in.ensure(total, s));
   MGF_HIP_TRY(hipMemcpyAsync(b->q_in.p, h.data(), 16 * total, hipMemcpyHostToDevice, s));
   MGF_TRY(batch_cols_refresh(b, &b->q_launches));
-  uint32_t nmax = 0;
-  for (uint32_t c : b->h_n) nmax = std::max(nmax, c);
-  A->col0 = b->dm[mgf_batch::ACOL0].p; A->col1 = b->dm[mgf_batch::ACOL1].p; A->w_off = b->d_off.p;
+  batch_work_args(b, A);
   A->items = reinterpret_cast<const uint4*>(b->q_in.p);
   A->order = reinterpret_cast<const uint32_t*>(b->q_in.p + o_order);
   U->n_items = plan.n_items; U->queries = b->q_in.p + o_q;
   U->ignore = ignore_body ? reinterpret_cast<const int32_t*>(b->q_in.p + o_ign) : nullptr;
   U->world = with_world ? reinterpret_cast<const int32_t*>(b->q_in.p + o_world) : nullptr;
-  U->lds = 32u * nmax;
+  U->lds = 32u * batch_nmax(b);
   return MGF_OK;
 }
 
@@ -124,11 +162,10 @@ static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* q
   memset(&A, 0, sizeof(A));
   BatchQueryUpload U;
   MGF_TRY(batch_env_sync(b));
-  const bool faces = !kRays && (kinds_mask & MGF_QUERY_TERRAIN) && b->t_worlds;  // a world of the batch has a terrain to sweep against
-  const bool obstacles = (kinds_mask & MGF_QUERY_OBSTACLES) && b->o_worlds;      // ... an obstacle to meet: a pass of its own, a lane per query
+  const bool faces = !kRays && batch_has_faces(b, kinds_mask), obstacles = batch_has_obstacles(b, kinds_mask);
   MGF_TRY(batch_query_upload(b, world, queries, sizeof(Q), n, ignore_body, &A, &U, faces || obstacles));
   MGF_TRY(b->q_out.ensure(kOut * n, s));
-  const uint32_t lds = U.lds + 16u * kBatchQueryRed;  // (at most 32 KB + 256 bytes: two workgroups a CU at the largest world)
+  const uint32_t lds = batch_ray_lds(b);
   A.T = batch_terrains(b);
   A.ignore = U.ignore;
   A.mask = kinds_mask;
@@ -139,22 +176,12 @@ static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* q
     k_batch_query_ray<<<(unsigned)U.n_items, kBatchBlock, lds, s>>>(A, dq);
     LAUNCH_CHECK();
     ++b->q_launches;
+    if (obstacles) MGF_TRY(batch_ray_obstacles(b, U.world, 0u, dq, n, A.out));
   } else {
     k_batch_query_sweep_bodies<<<(unsigned)U.n_items, kBatchBlock, lds, s>>>(A, dq);
     LAUNCH_CHECK();
     ++b->q_launches;
-    if (faces) {
-      k_batch_query_sweep_faces<<<(unsigned)((n + kBatchBlock - 1) / kBatchBlock), kBatchBlock, 0, s>>>(A.T, U.world, 0u, dq, (uint32_t)n, A.out);
-      LAUNCH_CHECK();
-      ++b->q_launches;
-    }
-  }
-  if (obstacles) {
-    const unsigned nb = (unsigned)((n + kBatchBlock - 1) / kBatchBlock);
-    if constexpr (kRays) k_batch_query_ray_obstacles<<<nb, kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, U.world, 0u, dq, (uint32_t)n, A.out);
-    else k_batch_query_sweep_obstacles<<<nb, kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, U.world, 0u, dq, (uint32_t)n, A.out);
-    LAUNCH_CHECK();
-    ++b->q_launches;
+    MGF_TRY(batch_sweep_tail(b, faces, obstacles, U.world, 0u, dq, n, A.out));
   }
   MGF_TRY(b->q_tm.mark(1, s));
   MGF_HIP_TRY(hipMemcpyAsync(out, b->q_out.p, 4 * kOut * n, hipMemcpyDeviceToHost, s));

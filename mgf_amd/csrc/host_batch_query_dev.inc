@@ -18,6 +18,20 @@ static bool dev_bytes_overlap(const void* a, size_t na, const void* b, size_t nb
   return pa < pb + nb && pb < pa + na;
 }
 
+// The arrays of a device-pointer call that must not share a byte: the first n_out of the list are written, and each of them is held
+// against every entry behind it, in list order.  The first pair that overlaps is refused by name ("a overlaps b"; `inputs`, if given,
+// stands for the name of whatever is not written).
+struct DevBytes { const void* p; size_t bytes; const char* name; };
+static mgf_status dev_outputs_overlap(const DevBytes* a, size_t n, size_t n_out, const char* inputs = nullptr) {
+  for (size_t i = 0; i < n_out; ++i)
+    for (size_t j = i + 1; j < n; ++j)
+      if (dev_bytes_overlap(a[i].p, a[i].bytes, a[j].p, a[j].bytes)) {
+        set_error("%s overlaps %s", a[i].name, j < n_out || !inputs ? a[j].name : inputs);
+        return MGF_ERR_INVALID;
+      }
+  return MGF_OK;
+}
+
 // Q = ParticleIn (7 words out) or MovingIn (13 words out)
 template <class Q>
 static mgf_status batch_query_dev_run(mgf_batch* b, const int32_t* world_dev, const Q* q_dev, int64_t n_in, const int32_t* ignore_dev, int32_t kinds_mask,
@@ -35,10 +49,9 @@ static mgf_status batch_query_dev_run(mgf_batch* b, const int32_t* world_dev, co
   MGF_TRY(dev_span(b->ctx, ignore_dev, 4 * n, "ignore_body_dev"));
   MGF_TRY(dev_span(b->ctx, out_dev, 4 * kOut * n, "out_dev"));
   // (a kernel of a later pass reads the queries again after an earlier one wrote hits)
-  if (dev_bytes_overlap(out_dev, 4 * kOut * n, world_dev, 4 * n) || dev_bytes_overlap(out_dev, 4 * kOut * n, q_dev, sizeof(Q) * n) ||
-      dev_bytes_overlap(out_dev, 4 * kOut * n, ignore_dev, 4 * n))
-    return fail(MGF_ERR_INVALID, "out_dev overlaps an input array");
-  b->q_launches = 0; b->q_run_ms = 0.0f;
+  const DevBytes arrays[4] = {{out_dev, 4 * kOut * n, "out_dev"}, {world_dev, 4 * n, "world_dev"}, {q_dev, sizeof(Q) * n, "q_dev"}, {ignore_dev, 4 * n, "ignore_dev"}};
+  MGF_TRY(dev_outputs_overlap(arrays, 4, 1, "an input array"));  // "out_dev overlaps an input array"
+  batch_call_begin(b);
   if (n == 0) return MGF_OK;
   BatchDevArgs D;
   MGF_TRY(batch_dev_begin(b, &D));  // the mirror up, the counter of skipped records there
@@ -46,14 +59,11 @@ static mgf_status batch_query_dev_run(mgf_batch* b, const int32_t* world_dev, co
   MGF_TRY(batch_cols_refresh(b, &b->q_launches));
   hipStream_t s = b->ctx->stream;
   const uint32_t K = b->K;
-  const bool faces = !kRays && (kinds_mask & MGF_QUERY_TERRAIN) && b->t_worlds;  // as batch_query_run
-  const bool obstacles = (kinds_mask & MGF_QUERY_OBSTACLES) && b->o_worlds;
-  uint32_t nmax = 0;
-  for (uint32_t c : b->h_n) nmax = std::max(nmax, c);
-  const uint32_t lds = 32u * nmax + 16u * kBatchQueryRed;
+  const bool faces = !kRays && batch_has_faces(b, kinds_mask), obstacles = batch_has_obstacles(b, kinds_mask);
+  const uint32_t lds = batch_ray_lds(b);
   BatchQueryArgs A;
   memset(&A, 0, sizeof(A));
-  A.col0 = b->dm[mgf_batch::ACOL0].p; A.col1 = b->dm[mgf_batch::ACOL1].p; A.w_off = b->d_off.p;
+  batch_work_args(b, &A);
   A.T = batch_terrains(b);
   A.ignore = ignore_dev;
   A.mask = kinds_mask;
@@ -96,18 +106,8 @@ static mgf_status batch_query_dev_run(mgf_batch* b, const int32_t* world_dev, co
   }
   LAUNCH_CHECK();
   ++b->q_launches;
-  if (faces) {
-    if constexpr (!kRays) k_batch_query_sweep_faces<<<batch_dev_blocks(n), kBatchBlock, 0, s>>>(A.T, lane_world, S.per, q_dev, (uint32_t)n, A.out);
-    LAUNCH_CHECK();
-    ++b->q_launches;
-  }
-  if (obstacles) {
-    if constexpr (kRays) k_batch_query_ray_obstacles<<<batch_dev_blocks(n), kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, lane_world, S.per, q_dev, (uint32_t)n, A.out);
-    else k_batch_query_sweep_obstacles<<<batch_dev_blocks(n), kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, lane_world, S.per, q_dev, (uint32_t)n, A.out);
-    LAUNCH_CHECK();
-    ++b->q_launches;
-  }
-  return MGF_OK;
+  if constexpr (!kRays) return batch_sweep_tail(b, faces, obstacles, lane_world, S.per, q_dev, n, A.out);
+  else return obstacles ? batch_ray_obstacles(b, lane_world, S.per, q_dev, n, A.out) : MGF_OK;
 }
 
 extern "C" mgf_status mgf_batch_raycast_many_dev(mgf_batch* b, const int32_t* world_dev, const mgf_particle* parts_dev, int64_t n, const int32_t* ignore_body_dev,

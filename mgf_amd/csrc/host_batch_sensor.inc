@@ -11,16 +11,23 @@
 // The order of mgf_batch_cast_sensors_dev is host_batch_query_dev.inc's: the refusals that need no device, the handle's own, EVERY
 // device pointer looked up (dev_span), the overlap of the two outputs - and only then the first thing is enqueued.
 
+// what a record of a rig - a sensor's, a camera's - names: a world of the batch, a body of that world, no flag but the one defined
+static mgf_status batch_rig_ref_check(const mgf_batch* b, int32_t world, int32_t body, int32_t flags, const char* what) {
+  if (world < 0 || (uint32_t)world >= b->K) return fail(MGF_ERR_INVALID, "world index out of range: the rig was not changed");
+  if (body < 0 || (uint32_t)body >= b->h_n[(size_t)world]) return fail(MGF_ERR_INVALID, "body index out of range: the rig was not changed");
+  if (flags & ~MGF_SENSOR_IGNORE_SELF) {
+    set_error("a %s's flags hold a bit beyond MGF_SENSOR_IGNORE_SELF: the rig was not changed", what);
+    return MGF_ERR_INVALID;
+  }
+  return MGF_OK;
+}
+
 extern "C" mgf_status mgf_batch_set_sensors(mgf_batch* b, const mgf_batch_sensor* s, int64_t n_in) {
   MGF_TRY(batch_dev_args(b, n_in));
   if (n_in && !s) return fail(MGF_ERR_INVALID, "NULL argument");
   static_assert(sizeof(mgf_batch_sensor) == sizeof(SensorIn) && sizeof(mgf_batch_sensor) == 40, "the rig goes up as the caller's records");
   const size_t n = (size_t)n_in;
-  for (size_t i = 0; i < n; ++i) {
-    if (s[i].world < 0 || (uint32_t)s[i].world >= b->K) return fail(MGF_ERR_INVALID, "world index out of range: the rig was not changed");
-    if (s[i].body < 0 || (uint32_t)s[i].body >= b->h_n[(size_t)s[i].world]) return fail(MGF_ERR_INVALID, "body index out of range: the rig was not changed");
-    if (s[i].flags & ~MGF_SENSOR_IGNORE_SELF) return fail(MGF_ERR_INVALID, "a sensor's flags hold a bit beyond MGF_SENSOR_IGNORE_SELF: the rig was not changed");
-  }
+  for (size_t i = 0; i < n; ++i) MGF_TRY(batch_rig_ref_check(b, s[i].world, s[i].body, s[i].flags, "sensor"));
   // (no device is needed: a cast that was enqueued reads the device copy, which is replaced in stream order when the next cast puts the rig up)
   std::vector<int32_t> world(n);
   for (size_t i = 0; i < n; ++i) world[i] = s[i].world;
@@ -35,23 +42,33 @@ extern "C" mgf_status mgf_batch_set_sensors(mgf_batch* b, const mgf_batch_sensor
 
 extern "C" int64_t mgf_batch_sensor_count(const mgf_batch* b) { return b ? (int64_t)b->s_rig.size() : -1; }
 
-// the rig onto the device (n > 0): items | records | order | worlds, every section from a 16-byte boundary
+// A rig onto the device: the sections one behind the other, every one from a 16-byte boundary, in ONE copy.  off[k]: where section k
+// begins in `dev`, in words of 16 bytes.
+struct RigSection { const void* p; size_t bytes; };
+static mgf_status batch_rig_upload(mgf_batch* b, DBuf<float4>& dev, const RigSection* sec, size_t n_sec, size_t* off) {
+  size_t total = 0;
+  for (size_t k = 0; k < n_sec; ++k) { off[k] = total; total += (sec[k].bytes + 15) / 16; }
+  std::vector<float4> h(total);
+  for (size_t k = 0; k < n_sec; ++k)
+    if (sec[k].bytes) memcpy(h.data() + off[k], sec[k].p, sec[k].bytes);
+  MGF_TRY(dev.ensure(total, b->ctx->stream));
+  return h2d(b->ctx, dev.p, h.data(), total);
+}
+
+// the rig onto the device (n > 0): items | records | order | worlds
 static mgf_status batch_sensors_up(mgf_batch* b) {
   if (!b->s_stale) return MGF_OK;
-  const size_t n = b->s_rig.size(), n_items = b->s_items.size();
-  for (const mgf_batch_sensor& r : b->s_rig)
+  const size_t n = b->s_rig.size();
+  std::vector<int32_t> world(n);
+  for (size_t i = 0; i < n; ++i) {
+    const mgf_batch_sensor& r = b->s_rig[i];
     if ((uint32_t)r.body >= b->h_n[(size_t)r.world]) return fail(MGF_ERR_INVALID, "internal error: a sensor names a body its world does not hold");
-  const size_t w_rig = (40 * n + 15) / 16, w_idx = (4 * n + 15) / 16;
-  const size_t o_rig = n_items, o_order = o_rig + w_rig, o_world = o_order + w_idx, total = o_world + w_idx;
-  std::vector<float4> h(total);
-  memcpy(h.data(), b->s_items.data(), 16 * n_items);
-  memcpy(h.data() + o_rig, b->s_rig.data(), 40 * n);
-  memcpy(h.data() + o_order, b->s_order.data(), 4 * n);
-  int32_t* hw = reinterpret_cast<int32_t*>(h.data() + o_world);
-  for (size_t i = 0; i < n; ++i) hw[i] = b->s_rig[i].world;
-  MGF_TRY(b->s_dev.ensure(total, b->ctx->stream));
-  MGF_TRY(h2d(b->ctx, b->s_dev.p, h.data(), total));
-  b->s_o_rig = o_rig; b->s_o_order = o_order; b->s_o_world = o_world;
+    world[i] = r.world;
+  }
+  const RigSection sec[4] = {{b->s_items.data(), 16 * b->s_items.size()}, {b->s_rig.data(), 40 * n}, {b->s_order.data(), 4 * n}, {world.data(), 4 * n}};
+  size_t off[4];
+  MGF_TRY(batch_rig_upload(b, b->s_dev, sec, 4, off));
+  b->s_o_rig = off[1]; b->s_o_order = off[2]; b->s_o_world = off[3];
   b->s_stale = false;
   return MGF_OK;
 }
@@ -65,17 +82,14 @@ static mgf_status batch_sensor_run(mgf_batch* b, int32_t kinds_mask, int32_t* ou
   MGF_TRY(batch_sensors_up(b));
   MGF_TRY(batch_cols_refresh(b, &b->q_launches));
   hipStream_t s = b->ctx->stream;
-  const bool obstacles = (kinds_mask & MGF_QUERY_OBSTACLES) && b->o_worlds;  // as batch_query_run
+  const bool obstacles = batch_has_obstacles(b, kinds_mask);
   if (obstacles && !parts_dev) {  // the obstacle pass takes the particles up again
     MGF_TRY(b->s_parts.ensure(7 * n, s));
     parts_dev = b->s_parts.p;
   }
-  uint32_t nmax = 0;
-  for (uint32_t c : b->h_n) nmax = std::max(nmax, c);
-  const uint32_t lds = 32u * nmax + 16u * kBatchQueryRed;
   BatchSensorArgs A;
   memset(&A, 0, sizeof(A));
-  A.col0 = b->dm[mgf_batch::ACOL0].p; A.col1 = b->dm[mgf_batch::ACOL1].p; A.w_off = b->d_off.p;
+  batch_work_args(b, &A);
   A.items = reinterpret_cast<const uint4*>(b->s_dev.p);
   A.order = reinterpret_cast<const uint32_t*>(b->s_dev.p + b->s_o_order);
   A.T = batch_terrains(b);
@@ -84,16 +98,11 @@ static mgf_status batch_sensor_run(mgf_batch* b, int32_t kinds_mask, int32_t* ou
   A.x = b->dm[mgf_batch::AX].p; A.q = b->dm[mgf_batch::AQ].p;
   A.rig = reinterpret_cast<const SensorIn*>(b->s_dev.p + b->s_o_rig);
   A.parts = parts_dev;
-  k_batch_sensor_ray<<<(unsigned)b->s_items.size(), kBatchBlock, lds, s>>>(A);
+  k_batch_sensor_ray<<<(unsigned)b->s_items.size(), kBatchBlock, batch_ray_lds(b), s>>>(A);
   LAUNCH_CHECK();
   b->q_launches += MGF_BATCH_SENSOR_LAUNCHES;
-  if (obstacles) {
-    k_batch_query_ray_obstacles<<<batch_dev_blocks(n), kBatchBlock, 0, s>>>(batch_obstacles(b), b->t_desc.p, reinterpret_cast<const int32_t*>(b->s_dev.p + b->s_o_world),
-                                                                           0u, reinterpret_cast<const ParticleIn*>(parts_dev), (uint32_t)n, out_dev);
-    LAUNCH_CHECK();
-    ++b->q_launches;
-  }
-  return MGF_OK;
+  if (!obstacles) return MGF_OK;
+  return batch_ray_obstacles(b, reinterpret_cast<const int32_t*>(b->s_dev.p + b->s_o_world), 0u, reinterpret_cast<const ParticleIn*>(parts_dev), n, out_dev);
 }
 
 // the refusals of both cast calls that need no device; *n: the sensors of the rig
@@ -111,7 +120,7 @@ extern "C" mgf_status mgf_batch_cast_sensors(mgf_batch* b, int32_t kinds_mask, m
   size_t n = 0;
   MGF_TRY(batch_sensor_args(b, kinds_mask, out, cap, &n));
   MGF_TRY(ctx_bind(b->ctx));
-  b->q_launches = 0; b->q_run_ms = 0.0f;
+  batch_call_begin(b);
   if (n == 0) return MGF_OK;
   hipStream_t s = b->ctx->stream;
   MGF_TRY(b->q_out.ensure(7 * n, s));
@@ -130,8 +139,9 @@ extern "C" mgf_status mgf_batch_cast_sensors_dev(mgf_batch* b, int32_t kinds_mas
   MGF_TRY(dev_span(b->ctx, out_dev, 28 * n, "out_dev"));
   MGF_TRY(dev_span(b->ctx, parts_out_dev, 28 * n, "parts_out_dev"));
   // (the obstacle pass reads the particles again after the body pass wrote hits)
-  if (dev_bytes_overlap(out_dev, 28 * n, parts_out_dev, 28 * n)) return fail(MGF_ERR_INVALID, "out_dev overlaps parts_out_dev");
-  b->q_launches = 0; b->q_run_ms = 0.0f;
+  const DevBytes arrays[2] = {{out_dev, 28 * n, "out_dev"}, {parts_out_dev, 28 * n, "parts_out_dev"}};
+  MGF_TRY(dev_outputs_overlap(arrays, 2, 2));
+  batch_call_begin(b);
   if (n == 0) return MGF_OK;
   return batch_sensor_run(b, kinds_mask, reinterpret_cast<int32_t*>(out_dev), reinterpret_cast<float*>(parts_out_dev));
 }

@@ -26,7 +26,8 @@
 // item, nor the split into launches changes a bit of an answer.  No workgroup waits for another.
 // The two kernels with a workgroup per work item are bq_ray_item<SRC> / bq_sweep_item<SRC> behind a kernel's signature: SRC says where
 // the work item comes from - the host's table here (kItemTable), the device-built table or arithmetic on blockIdx.x for the
-// device-pointer calls (kItemPlan, kItemFixed: k_batch_query_dev.h).  The three lane-per-query passes take the world of query i from
+// device-pointer calls (kItemPlan, kItemFixed: k_batch_query_dev.h).  bq_ray_item is bq_ray_front - the front of a ray cast, written
+// once - over the caller's particles; k_batch_sensor_ray (k_batch_sensor.h) is the same front over particles formed from a rig.  The three lane-per-query passes take the world of query i from
 // world[i], or (world == null: every world has `per` queries) as i / per, and leave at once for a negative world - a record the
 // device-pointer calls skip - and for a cast whose tag is no component's; the host-memory calls refuse both before anything runs.
 #pragma once
@@ -165,10 +166,17 @@ __device__ __forceinline__ bool bq_ray_far(float4 a, float4 b, V3 p, V3 d, float
   return dot(e, e) > lim * lim + 1e-4f * dot(w, w);
 }
 
-// A workgroup's work item of rays.  kItemPlan: a workgroup at or beyond the device's item total has none - it leaves, the whole of it,
-// before anything is staged and ahead of the first __syncthreads.
-template <int SRC>
-__device__ __forceinline__ void bq_ray_item(const BatchQueryArgs& A, const ParticleIn* parts, const BatchItemSrc& S, float4* s_dyn) {
+// A live query's particle in world coordinates and the body of its world it does not see (-1: none): what a loader hands bq_ray_front
+struct BatchRay { V3 p, d; float dt; int32_t ign; };
+
+// A workgroup's work item of rays, written once for every kernel that casts rays with a workgroup per work item: k_batch_query_ray,
+// k_batch_query_ray_dev<SRC> (bq_ray_item) and k_batch_sensor_ray (k_batch_sensor.h).  What a kernel brings is where a particle comes
+// from - load(qi, g0) -> BatchRay, run by the live lanes behind the staging - and what else its first lane does behind the stored hit -
+// done(qi, p, d, dt).  Neither holds a barrier nor leaves the kernel.
+// kItemPlan: a workgroup at or beyond the device's item total has no work item - it leaves, the whole of it, before anything is staged
+// and ahead of the first __syncthreads.  The only other exit is behind bq_reduce.
+template <int SRC, class Load, class Done>
+__device__ __forceinline__ void bq_ray_front(const BatchQueryArgs& A, const BatchItemSrc& S, float4* s_dyn, Load&& load, Done&& done) {
   if (SRC == kItemPlan && blockIdx.x >= *S.n_items) return;
   BatchWork W(A, A.mask & MGF_QUERY_BODIES, bq_item<SRC>(A, S));
   const uint32_t n = W.n;
@@ -180,9 +188,8 @@ __device__ __forceinline__ void bq_ray_item(const BatchQueryArgs& A, const Parti
   float dt = 0.0f;
   int32_t ign = -1, mask = 0;
   if (W.live) {
-    const ParticleIn q = parts[qi];
-    p = ld3(q.p); d = ld3(q.d); dt = q.dt;
-    ign = A.ignore ? A.ignore[qi] : -1;
+    const BatchRay r = load(qi, W.g0);
+    p = r.p; d = r.d; dt = r.dt; ign = r.ign;
     mask = A.mask;
     if (d.x == 0.0f && d.y == 0.0f && d.z == 0.0f) mask = 0;  // (no direction: no hit, by definition - k_query_ray)
   }
@@ -204,6 +211,18 @@ __device__ __forceinline__ void bq_ray_item(const BatchQueryArgs& A, const Parti
     if (M.n_nodes) q_ray_terrain(M, p, d, dt, nullptr, best);
   }
   q_ray_store(A.out + 7 * (size_t)qi, best);
+  done(qi, p, d, dt);
+}
+// the front over the caller's particles: parts[qi] as it stands, A.ignore, nothing behind the hit
+template <int SRC>
+__device__ __forceinline__ void bq_ray_item(const BatchQueryArgs& A, const ParticleIn* parts, const BatchItemSrc& S, float4* s_dyn) {
+  bq_ray_front<SRC>(
+      A, S, s_dyn,
+      [&](uint32_t qi, uint32_t) {
+        const ParticleIn q = parts[qi];
+        return BatchRay{ld3(q.p), ld3(q.d), q.dt, A.ignore ? A.ignore[qi] : -1};
+      },
+      [](uint32_t, V3, V3, float) {});
 }
 // LDS (dynamic): 32 bytes a body, kBatchQueryRed words.
 __global__ __launch_bounds__(kBatchBlock) void k_batch_query_ray(BatchQueryArgs A, const ParticleIn* parts) {
@@ -218,7 +237,7 @@ __device__ __forceinline__ SweepCast bq_sweep_cast(const MovingIn& m) {
   return q_sweep_cast(m, G);
 }
 
-// A workgroup's work item of casts (bq_ray_item's remarks).  kItemFixed: no plan has looked at the casts - one whose tag is no
+// A workgroup's work item of casts (bq_ray_front's remarks).  kItemFixed: no plan has looked at the casts - one whose tag is no
 // component's is matched against nothing, keeps the no-hit record and is counted by the first of its lanes.
 template <int SRC>
 __device__ __forceinline__ void bq_sweep_item(const BatchQueryArgs& A, const MovingIn* casts, const BatchItemSrc& S, float4* s_dyn) {

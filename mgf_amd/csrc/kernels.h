@@ -107,7 +107,7 @@
 //   k_batch_sensor_ray (k_batch_sensor.h)
 //                      ray sensors fixed in the frame of a body (mgf_batch_set_sensors / _cast_sensors / _cast_sensors_dev): the rig sorted
 //                      by world and cut into work items on the host, once; a cast reads the bodies' x and q, forms every sensor's particle
-//                      P = x + rotate(q, p), D = rotate(q, d) and casts it by k_batch_query_ray's own work split, loop and reduction
+//                      P = x + rotate(q, p), D = rotate(q, d) and casts it through bq_ray_front (k_batch_query.h), k_batch_query_ray's front
 //   k_batch_camera_tile / _depth (k_batch_camera.h)
 //                      depth cameras fixed in the frame of a body (mgf_batch_set_cameras / _cast_cameras / _cast_cameras_dev): a workgroup per
 //                      tile of 16 x 16 pixels, a lane per pixel; the tile bounds its rays by a cone and a length, drops every body whose

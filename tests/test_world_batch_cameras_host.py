@@ -19,13 +19,9 @@ import mgf_amd
 from mgf_amd import _capi
 from tests import batch_camera_cases as CC
 from tests import batch_sensor_cases as SC
+from tests.util import RESOURCES, ROOT, kernel_resources, read
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("mgf_batch_set_cameras", "mgf_batch_camera_count", "mgf_batch_camera_pixels", "mgf_batch_cast_cameras", "mgf_batch_cast_cameras_dev")
-
-
-def _read(*path):
-    return open(os.path.join(ROOT, *path)).read()
 
 
 # ---- 1 ------------------------------------------------------------------------------------------------------------------------------------
@@ -84,7 +80,7 @@ def test_hand_checked_corners_of_the_restatement():
 
 # ---- 2 ------------------------------------------------------------------------------------------------------------------------------------
 def test_header_library_binding_and_documents_carry_the_calls():
-    h = _read("include", "mgf_hip.h")
+    h = read("include", "mgf_hip.h")
     for sig in (r"mgf_status mgf_batch_set_cameras\(mgf_batch\* b, const mgf_batch_camera\* cams, int64_t n\);",
                 r"int64_t mgf_batch_camera_count\(const mgf_batch\* b\);", r"int64_t mgf_batch_camera_pixels\(const mgf_batch\* b\);",
                 r"mgf_status mgf_batch_cast_cameras\(mgf_batch\* b, int32_t kinds_mask, float\* depth, mgf_ray_hit\* hits, mgf_particle\* parts_out, int64_t cap\);",
@@ -116,23 +112,23 @@ def test_header_library_binding_and_documents_carry_the_calls():
         assert (fn.restype, list(fn.argtypes)) == want[name], name
     for method in ("set_cameras", "camera_count", "camera_pixels", "cast_cameras", "cast_cameras_dev"):
         assert callable(getattr(mgf_amd.WorldBatch, method)), method
-    flat = re.sub(r"\s+", " ", _read("INTEGRATION.md"))
+    flat = re.sub(r"\s+", " ", read("INTEGRATION.md"))
     for sig in ("pub fn mgf_batch_set_cameras(b: *mut mgf_batch, cams: *const mgf_batch_camera, n: i64) -> mgf_status;",
                 "pub fn mgf_batch_camera_count(b: *const mgf_batch) -> i64;", "pub fn mgf_batch_camera_pixels(b: *const mgf_batch) -> i64;",
                 "pub fn mgf_batch_cast_cameras(b: *mut mgf_batch, kinds_mask: i32, depth: *mut f32, hits: *mut mgf_ray_hit, parts_out: *mut mgf_particle, cap: i64) -> mgf_status;",
                 "pub fn mgf_batch_cast_cameras_dev(b: *mut mgf_batch, kinds_mask: i32, depth_dev: *mut f32, hits_dev: *mut mgf_ray_hit, parts_out_dev: *mut mgf_particle, cap: i64) -> mgf_status;",
                 "pub struct mgf_batch_camera"):
         assert sig in flat, sig
-    kernels = _read("mgf_amd", "csrc", "kernels.h")
+    kernels = read("mgf_amd", "csrc", "kernels.h")
     assert kernels.index('#include "k_batch_sensor.h"') < kernels.index('#include "k_batch_camera.h"') and "k_batch_camera_tile" in kernels
-    hip = _read("mgf_amd", "csrc", "mgf_hip.hip")
+    hip = read("mgf_amd", "csrc", "mgf_hip.hip")
     assert hip.index('#include "host_batch_sensor.inc"') < hip.index('#include "host_batch_camera.inc"')
-    design = _read("DESIGN.md")
+    design = read("DESIGN.md")
     sub = design[design.index("Body-mounted depth cameras"):]
     for word in ("k_batch_camera_tile", "k_batch_camera_depth", "D = rotate(q, rotate(r, d_cam))", "conservative", "Out of scope", "batch_camera_bench.py",
                  "Compiler output"):
         assert word in sub, word
-    readme = _read("README.md")
+    readme = read("README.md")
     assert "set_cameras" in readme and "cast_cameras_dev" in readme
     assert os.path.exists(os.path.join(ROOT, "tools", "batch_camera_bench.py"))
 
@@ -161,44 +157,64 @@ def test_what_needs_no_device_is_refused_before_the_handle_is_dereferenced():
             assert fn(fake, mask, None, None, None, 0) == INV and "kinds_mask" in err(), mask
     # what needs the handle is refused on the host too, ahead of any change of the rig and of any device work (read here; run in
     # tests/test_gpu_world_batch_cameras.py, where a handle exists)
-    src = _read("mgf_amd", "csrc", "host_batch_camera.inc")
+    src = read("mgf_amd", "csrc", "host_batch_camera.inc")
     body = src[src.index('extern "C" mgf_status mgf_batch_set_cameras('):src.index('extern "C" int64_t mgf_batch_camera_count(')]
     first_change = body.index("b->c_rig.assign(")
-    for refusal in ("world index out of range", "body index out of range", "a bit beyond MGF_SENSOR_IGNORE_SELF", "reserved word is not 0",
+    for refusal in ("batch_rig_ref_check(b, c.world, c.body, c.flags, \"camera\")", "reserved word is not 0",
                     "outside [1, 4096]", "is not finite", "far is NaN or not above 0", "more than INT32_MAX pixels"):
         assert body.index(refusal) < first_change, refusal
+    # the world, the body and the flags: the sensors' check (host_batch_sensor.inc), which names the rig it is asked about
+    sens = read("mgf_amd", "csrc", "host_batch_sensor.inc")
+    check = sens[sens.index("static mgf_status batch_rig_ref_check("):sens.index('extern "C" mgf_status mgf_batch_set_sensors(')]
+    for refusal in ("world index out of range: the rig was not changed", "body index out of range: the rig was not changed",
+                    "a %s's flags hold a bit beyond MGF_SENSOR_IGNORE_SELF: the rig was not changed"):
+        assert refusal in check, refusal
+    assert not re.search(r"<<<|Async|hipMalloc|\.ensure\(|h2d\(|b->\w+ =[^=]", check)    # it refuses; it changes nothing
     assert not re.search(r"<<<|Async|hipMalloc|\.ensure\(|h2d\(", body)            # no device work at all
     assert not re.search(r"b->s_\w+", src)                                        # the sensor rig is not touched from here
-    assert "c_rig" not in _read("mgf_amd", "csrc", "host_batch_sensor.inc")
+    assert "c_rig" not in read("mgf_amd", "csrc", "host_batch_sensor.inc")
     args = src[src.index("static mgf_status batch_camera_args("):src.index('extern "C" mgf_status mgf_batch_cast_cameras(')]
     assert args.index("MGF_ERR_CAPACITY") < args.index("depth and hits are both NULL") < args.index("return MGF_OK;") and "ctx_bind" not in args and "<<<" not in args
-    host = _read("mgf_amd", "csrc", "host_batch.inc")
+    host = read("mgf_amd", "csrc", "host_batch.inc")
     add = host[host.index('extern "C" mgf_status mgf_batch_add_bodies('):]
     assert "b->c_stale = true;" in add[:add.index("\n}\n")]
 
 
 # ---- 4 ------------------------------------------------------------------------------------------------------------------------------------
 def test_all_pointers_are_looked_up_and_compared_before_the_first_enqueue():
-    src = _read("mgf_amd", "csrc", "host_batch_camera.inc")
+    src = read("mgf_amd", "csrc", "host_batch_camera.inc")
+    sens = read("mgf_amd", "csrc", "host_batch_sensor.inc")
     run = src[src.index('extern "C" mgf_status mgf_batch_cast_cameras_dev('):]
-    enqueue = (r"batch_camera_run\(|batch_cameras_up\(|batch_push\(|batch_dev_begin\(|batch_env_sync\(|batch_cols_refresh\(|hipMemsetAsync|hipMemcpyAsync|<<<|"
-               r"prim_exclusive_scan_u32|\.ensure\(|h2d\(")
+    enqueue = (r"batch_camera_run\(|batch_cameras_up\(|batch_rig_upload\(|batch_ray_obstacles\(|batch_sweep_tail\(|batch_push\(|batch_dev_begin\(|batch_env_sync\(|"
+               r"batch_cols_refresh\(|hipMemsetAsync|hipMemcpyAsync|<<<|prim_exclusive_scan_u32|\.ensure\(|h2d\(")
     first_enqueue = min(m.start() for m in re.finditer(enqueue, run))
     checks = [m.start() for m in re.finditer(r"dev_span\(", run)]
     assert len(checks) == 3 and max(checks) < first_enqueue
     for name in ("depth_dev, 4 \\* n", "hits_dev, 28 \\* n", "parts_out_dev, 28 \\* n"):
         assert re.search(r"dev_span\(b->ctx, " + name, run), name
-    overlaps = [run.index(t) for t in ("dev_bytes_overlap(depth_dev, 4 * n, hits_dev, 28 * n)", "dev_bytes_overlap(depth_dev, 4 * n, parts_out_dev, 28 * n)",
-                                       "dev_bytes_overlap(hits_dev, 28 * n, parts_out_dev, 28 * n)")]
-    assert max(checks) < overlaps[0] < overlaps[1] < overlaps[2] < first_enqueue
+    # all three are written, so the one helper holds every pair against each other, in list order: depth with hits, depth with
+    # particles, hits with particles
+    listed = run.index('arrays[3] = {{depth_dev, 4 * n, "depth_dev"}, {hits_dev, 28 * n, "hits_dev"}, {parts_out_dev, 28 * n, "parts_out_dev"}};')
+    assert max(checks) < listed < run.index("dev_outputs_overlap(arrays, 3, 3)") < first_enqueue
+    from tests.test_world_batch_sensors_host import _the_overlap_helper_compares_and_enqueues_nothing, _the_shared_obstacle_pass
+    _the_overlap_helper_compares_and_enqueues_nothing(enqueue)
+    dev = read("mgf_amd", "csrc", "host_batch_query_dev.inc")
+    loops = dev[dev.index("static mgf_status dev_outputs_overlap("):dev.index("// Q = ParticleIn")]
+    assert "for (size_t i = 0; i < n_out; ++i)" in loops and "for (size_t j = i + 1; j < n; ++j)" in loops
     assert run.index("batch_camera_args(") < run.index("ctx_bind(") < min(checks)
     assert run.index("if (n == 0) return MGF_OK;") < first_enqueue                   # an empty rig enqueues nothing
     helper = src[src.index("static mgf_status batch_camera_run("):src.index("static mgf_status batch_camera_args(")]
-    assert "k_batch_camera_tile<<<" in helper and "k_batch_query_ray_obstacles<<<" in helper and "k_batch_camera_depth<<<" in helper
-    assert helper.count("<<<") == 3 and "hipStreamSynchronize" not in helper and "hipMemcpy" not in helper   # no wait, no copy
+    # its own two kernels' launches with the shared obstacle pass between them; neither it nor that pass waits or copies
+    assert helper.index("k_batch_camera_tile<<<") < helper.index("batch_ray_obstacles(") < helper.index("k_batch_camera_depth<<<") and helper.count("<<<") == 2
+    assert "hipStreamSynchronize" not in helper and "hipMemcpy" not in helper
+    obstacles = _the_shared_obstacle_pass()
+    assert "hipStreamSynchronize" not in obstacles and "hipMemcpy" not in obstacles
     up = src[src.index("static mgf_status batch_cameras_up("):src.index("// The launches of a cast")]
-    assert up.index("if (!b->c_stale) return MGF_OK;") < up.index("h2d(") and up.count("h2d(") == 1     # the steady state uploads nothing; one copy
-    k = _read("mgf_amd", "csrc", "k_batch_camera.h")
+    assert up.index("if (!b->c_stale) return MGF_OK;") < up.index("internal error") < up.index("batch_rig_upload(") and up.count("batch_rig_upload(") == 1
+    assert "h2d(" not in up
+    upload = sens[sens.index("static mgf_status batch_rig_upload("):sens.index("// the rig onto the device")]
+    assert upload.count("h2d(") == 1 and upload.count(".ensure(") == 1 and "<<<" not in upload          # the steady state uploads nothing; one copy
+    k = read("mgf_amd", "csrc", "k_batch_camera.h")
     body = k[k.index("void k_batch_camera_tile("):k.index("void k_batch_camera_depth(")]
     assert "return" not in body[:body.rindex("}\n\n")] and body.count("__syncthreads()") == 3         # no exit ahead of a barrier: no exit at all
     assert "atomicAdd(&s_ctl[0]" in body and not re.search(r"atomic\w*\([^)]*float", body) and "__shared__ float4 s_dyn[]" in body
@@ -259,12 +275,12 @@ def test_the_binding_turns_a_wrong_tensor_down_before_it_calls_c():
 
 # ---- 6 ------------------------------------------------------------------------------------------------------------------------------------
 def test_the_tile_shape_of_the_model_is_the_kernels():
-    k = _read("mgf_amd", "csrc", "k_batch_camera.h")
+    k = read("mgf_amd", "csrc", "k_batch_camera.h")
     m = re.search(r"constexpr uint32_t kCamTileW = (\d+), kCamTileH = (\d+);", k)
     assert m and (int(m.group(1)), int(m.group(2))) == (CC.TILE_W, CC.TILE_H) and CC.TILE_W * CC.TILE_H == 256
     assert "x0 + (threadIdx.x % kCamTileW)" in k and "y0 + (threadIdx.x / kCamTileW)" in k
     assert "(size_t)it.y + (size_t)iy * (uint32_t)c.width + ix" in k
-    src = _read("mgf_amd", "csrc", "host_batch_camera.inc")
+    src = read("mgf_amd", "csrc", "host_batch_camera.inc")
     assert re.search(r"for \(uint32_t y0 = 0; y0 < \(uint32_t\)cams\[i\]\.height; y0 \+= kCamTileH\)\s+for \(uint32_t x0 = 0; x0 < \(uint32_t\)cams\[i\]\.width; x0 \+= kCamTileW\) "
                      r"tiles\.push_back\(make_uint4\(\(uint32_t\)i, first, x0 \| \(y0 << 16\), 0u\)\);", src)
 
@@ -292,38 +308,27 @@ def test_the_tile_table_partitions_every_cameras_pixels_exactly_once(shapes):
 
 
 # ---- 7 ------------------------------------------------------------------------------------------------------------------------------------
-def _resources(prefix):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), prefix], capture_output=True, text=True, check=True).stdout
-    rows = {}
-    for line in out.splitlines()[1:]:
-        m = re.match(r"(.{80}) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+)$", line)
-        if m:
-            rows[m.group(1).strip()] = tuple(m.group(k) for k in range(2, 8))  # vgpr, sgpr, scratch, lds, sgpr spills, vgpr spills
-    return rows
-
-
 def test_the_new_kernels_use_no_scratch_and_the_sensor_and_query_kernels_keep_their_figures():
-    from tests.test_world_batch_sensors_host import RESOURCES
     if not os.path.exists(os.path.join(ROOT, "mgf_amd", "libmgf_hip.so")) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("needs the built library and the ROCm LLVM tools")
-    rows = _resources("k_batch_camera_")
+    rows = kernel_resources("k_batch_camera_")
     assert set(rows) == {"k_batch_camera_tile", "k_batch_camera_depth"}, sorted(rows)
     for name, v in rows.items():
         assert (v[2], v[3], v[4], v[5]) == ("0", "0", "0", "0"), (name, v)         # no scratch, no static LDS, no spills
     assert int(rows["k_batch_camera_tile"][0]) <= 64, rows                         # eight waves a SIMD stay possible
-    sensor = _resources("k_batch_sensor_")
+    sensor = kernel_resources("k_batch_sensor_")
     assert sensor == {"k_batch_sensor_ray": ("45", "67", "0", "0", "0", "0")}, sensor
-    old = _resources("k_batch_query_")
+    old = kernel_resources("k_batch_query_")
     assert set(old) == set(RESOURCES), sorted(old)
     for name, want in RESOURCES.items():
         assert old[name] == want, (name, old[name], want)
-    design = re.sub(r"\s+", " ", _read("DESIGN.md"))
+    design = re.sub(r"\s+", " ", read("DESIGN.md"))
     t, d = rows["k_batch_camera_tile"], rows["k_batch_camera_depth"]
     for text in (f"`k_batch_camera_tile` {t[0]} / {t[1]} / 0 / 0 / 0", f"`k_batch_camera_depth` {d[0]} / {d[1]} / 0 / 0 / 0"):
         assert text in design, text
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_lane_masks.py")], capture_output=True, text=True)
     assert r.returncode == 0 and " 0 lane masks" in r.stdout, r.stdout[-400:]
-    k = _read("mgf_amd", "csrc", "k_batch_camera.h")
+    k = read("mgf_amd", "csrc", "k_batch_camera.h")
     assert len(re.findall(r"__global__ __launch_bounds__\(kBatchBlock\)", k)) == len(re.findall(r"__global__", k)) == 2
 
 

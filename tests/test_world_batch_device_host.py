@@ -15,9 +15,8 @@ import pytest
 import mgf_amd
 from mgf_amd import _capi
 from tests import batch_device_cases as DV
-from tests.util import oracle_world
+from tests.util import ROOT, kernel_resources, oracle_world, read
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SET = r"mgf_batch\* b, const int32_t\* body_dev, int64_t n, "
 ENTRY_POINTS = {
     "mgf_ctx_synchronize": r"mgf_status mgf_ctx_synchronize\(mgf_ctx\* ctx\);",
@@ -34,12 +33,8 @@ NEW_KERNELS = {"k_batch_dev_gather", "k_batch_dev_count", "k_batch_dev_fill", "k
     f"k_batch_dev_apply<{mode}, {seg}>" for mode in (0, 1, 2) for seg in ("false", "true")}
 
 
-def _read(*path):
-    return open(os.path.join(ROOT, *path)).read()
-
-
 def test_header_declares_the_calls_the_launch_constant_and_what_is_left_out():
-    h = _read("include", "mgf_hip.h")
+    h = read("include", "mgf_hip.h")
     for name, sig in ENTRY_POINTS.items():
         assert re.search(r"MGF_API " + sig, h), name
     section = h[h.index("device-pointer calls"):]
@@ -49,14 +44,14 @@ def test_header_declares_the_calls_the_launch_constant_and_what_is_left_out():
                  "skipped whole", "highest array index", "ascending array index", "no float atomic", "OUT OF SCOPE", "rays, sweeps and box queries",
                  "hipGraph", "lone mgf_world", "RETURNS WITHOUT WAITING"):
         assert word in section, word
-    design = _read("DESIGN.md")
+    design = read("DESIGN.md")
     sub = design[design.index("Device-pointer calls"):]
     for word in ("k_batch_dev_apply", "insertion", "device_skipped", "hipGraph", "batch_device_bench.py"):
         assert word in sub, word
-    assert "gather_state" in _read("README.md") and "copy_worlds_where" in _read("README.md")
-    kernels = _read("mgf_amd", "csrc", "kernels.h")
+    assert "gather_state" in read("README.md") and "copy_worlds_where" in read("README.md")
+    kernels = read("mgf_amd", "csrc", "kernels.h")
     assert "k_batch_dev.h" in kernels and "k_batch_dev_gather" in kernels
-    assert '#include "host_batch_dev.inc"' in _read("mgf_amd", "csrc", "mgf_hip.hip")
+    assert '#include "host_batch_dev.inc"' in read("mgf_amd", "csrc", "mgf_hip.hip")
 
 
 def test_library_and_binding_export_them_with_their_signatures():
@@ -82,7 +77,7 @@ def test_library_and_binding_export_them_with_their_signatures():
 
 
 def test_integration_md_has_the_rust_twins():
-    flat = re.sub(r"\s+", " ", _read("INTEGRATION.md"))
+    flat = re.sub(r"\s+", " ", read("INTEGRATION.md"))
     for sig in ("pub fn mgf_ctx_synchronize(ctx: *mut mgf_ctx) -> mgf_status;",
                 "pub fn mgf_batch_gather_state_dev(b: *mut mgf_batch, body_dev: *const i32, n: i64, x: *mut f32, q: *mut f32, v: *mut f32, "
                 "omega: *mut f32, force: *mut f32, torque: *mut f32) -> mgf_status;",
@@ -143,7 +138,7 @@ def test_what_needs_no_device_is_refused_before_the_handle_is_dereferenced():
 def test_every_device_pointer_is_looked_up_before_the_first_enqueue():
     """the order "check, then enqueue", read in the source: in every entry point of host_batch_dev.inc the last dev_span comes before
     the first thing that enqueues (a push of the mirror, a memset, a copy, a launch)"""
-    src = _read("mgf_amd", "csrc", "host_batch_dev.inc")
+    src = read("mgf_amd", "csrc", "host_batch_dev.inc")
     bodies = re.split(r"\n(?=extern \"C\"|template <int MODE>\nstatic mgf_status batch_dev_set)", src)[1:]
     assert len(bodies) == 7, len(bodies)
     checked = 0
@@ -208,12 +203,7 @@ def test_the_binding_turns_a_wrong_tensor_down_before_it_calls_c():
 def test_the_new_kernels_use_no_scratch_spill_nothing_and_keep_their_lane_masks():
     if not os.path.exists(os.path.join(ROOT, "mgf_amd", "libmgf_hip.so")) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("needs the built library and the ROCm LLVM tools")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "k_batch_dev_"], capture_output=True, text=True, check=True).stdout
-    rows = {}
-    for line in out.splitlines()[1:]:
-        m = re.match(r"(.{80}) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+)$", line)
-        if m:
-            rows[m.group(1).strip()] = tuple(m.group(k) for k in range(2, 8))  # vgpr, sgpr, scratch, lds, sgpr spills, vgpr spills
+    rows = kernel_resources("k_batch_dev_")
     assert set(rows) == NEW_KERNELS, rows
     bad = {k: v for k, v in rows.items() if (v[2], v[4], v[5]) != ("0", "0", "0")}
     assert not bad, bad

@@ -14,9 +14,8 @@ import pytest
 import mgf_amd
 from mgf_amd import _capi
 from tests import batch_drive_cases as DC
-from tests.util import oracle_world
+from tests.util import ROOT, kernel_resources, oracle_world, read
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REC = r"mgf_batch\* b, const int32_t\* world, const int32_t\* body, int64_t n,\s*"
 ENTRY_POINTS = {
     "mgf_batch_get_many": r"mgf_status mgf_batch_get_many\(" + REC + r"mgf_velocity\* vel, mgf_rigid_body_info\* info, mgf_vec3\* force, mgf_vec3\* torque\);",
@@ -27,12 +26,8 @@ ENTRY_POINTS = {
 }
 
 
-def _read(*path):
-    return open(os.path.join(ROOT, *path)).read()
-
-
 def test_header_declares_the_calls_and_says_what_they_leave_out():
-    h = _read("include", "mgf_hip.h")
+    h = read("include", "mgf_hip.h")
     section = h[h.index("many small worlds"):]
     for name, sig in ENTRY_POINTS.items():
         assert re.search(r"MGF_API " + sig, section), name
@@ -42,12 +37,12 @@ def test_header_declares_the_calls_and_says_what_they_leave_out():
     for word in ("drive_launches", "OUT OF SCOPE", "no force setter", "impulses at a point", "a whole-batch clone", "copies between contexts",
                  "no fused multiply-add", "a body named twice keeps the last", "the terrain assignment"):
         assert word in section, word
-    design = _read("DESIGN.md")
+    design = read("DESIGN.md")
     assert "Driving a batch" in design and "stable sort" in design[design.index("Driving a batch"):]
-    readme = _read("README.md")
+    readme = read("README.md")
     for name in ("get_many", "set_forces", "apply_impulses", "copy_worlds"):
         assert name in readme[readme.index("mgf_batch_new"):], name
-    kernels = _read("mgf_amd", "csrc", "kernels.h")
+    kernels = read("mgf_amd", "csrc", "kernels.h")
     assert "k_batch_drive.h" in kernels and "k_batch_drive_get" in kernels
 
 
@@ -64,7 +59,7 @@ def test_library_and_binding_export_them():
 
 
 def test_integration_md_has_the_rust_twins():
-    text = _read("INTEGRATION.md")
+    text = read("INTEGRATION.md")
     flat = re.sub(r"\s+", " ", text)
     for sig in ("pub fn mgf_batch_get_many(b: *mut mgf_batch, world: *const i32, body: *const i32, n: i64, vel: *mut mgf_velocity, "
                 "info: *mut mgf_rigid_body_info, force: *mut mgf_vec3, torque: *mut mgf_vec3) -> mgf_status;",
@@ -122,12 +117,7 @@ def test_null_and_negative_arguments_are_refused_before_the_handle_is_dereferenc
 def test_the_kernels_use_no_scratch_spill_nothing_and_keep_their_lane_masks():
     if not os.path.exists(os.path.join(ROOT, "mgf_amd", "libmgf_hip.so")) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("needs the built library and the ROCm LLVM tools")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "k_batch_drive_"], capture_output=True, text=True, check=True).stdout
-    rows = {}
-    for line in out.splitlines()[1:]:
-        m = re.match(r"(.{80}) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+)$", line)
-        if m:
-            rows[m.group(1).strip()] = tuple(m.group(k) for k in range(2, 8))  # vgpr, sgpr, scratch, lds, sgpr spills, vgpr spills
+    rows = kernel_resources("k_batch_drive_")
     assert set(rows) == {"k_batch_drive_get", "k_batch_drive_set<0>", "k_batch_drive_set<1>", "k_batch_drive_set<2>", "k_batch_drive_copy"}, rows
     bad = {k: v for k, v in rows.items() if (v[2], v[4], v[5]) != ("0", "0", "0")}
     assert not bad, bad

@@ -4,16 +4,14 @@ and the batch tick's kernels use no scratch memory and spill no register."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import mgf_amd
 from mgf_amd import _capi
+from tests.util import ROOT, kernel_resources, read
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = {
     "mgf_batch_new": r"mgf_status mgf_batch_new\(mgf_ctx\* ctx, const mgf_params\* params, int64_t n_worlds, mgf_batch\*\* out\);",
     "mgf_batch_free": r"void mgf_batch_free\(mgf_batch\* b\);",
@@ -32,12 +30,8 @@ ENTRY_POINTS = {
 }
 
 
-def _read(*path):
-    return open(os.path.join(ROOT, *path)).read()
-
-
 def test_header_declares_the_section_and_its_entry_points():
-    h = _read("include", "mgf_hip.h")
+    h = read("include", "mgf_hip.h")
     assert "typedef struct mgf_batch mgf_batch;" in h
     assert re.search(r"#define MGF_BATCH_MAX_BODIES 1024\b", h)
     assert "many small worlds" in h
@@ -60,7 +54,7 @@ def test_library_and_binding_export_them():
 
 
 def test_integration_md_has_the_rust_twins():
-    text = _read("INTEGRATION.md")
+    text = read("INTEGRATION.md")
     assert re.search(r"pub enum mgf_batch \{\}", text)
     assert "pub const MGF_BATCH_MAX_BODIES: usize = 1024;" in text
     for name in ENTRY_POINTS:
@@ -149,12 +143,7 @@ def test_no_batch_without_a_device():
 def test_the_batch_kernels_use_no_scratch_and_spill_nothing():
     if not os.path.exists(os.path.join(ROOT, "mgf_amd", "libmgf_hip.so")) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("needs the built library and the ROCm LLVM tools")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py")], capture_output=True, text=True, check=True).stdout
-    rows = {}
-    for line in out.splitlines()[1:]:
-        m = re.match(r"(.{80}) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+)$", line)
-        if m and m.group(1).startswith("k_batch_"):
-            rows[m.group(1).strip()] = tuple(m.group(k) for k in range(2, 8))  # vgpr, sgpr, scratch, lds, sgpr spills, vgpr spills
+    rows = kernel_resources("k_batch_")
     tick = {"k_batch_front", "k_batch_faces", "k_batch_pairs", "k_batch_pack", "k_batch_setup", "k_batch_solve"}
     assert tick <= set(rows), rows
     bad = {k: v for k, v in rows.items() if (v[2], v[4], v[5]) != ("0", "0", "0")}

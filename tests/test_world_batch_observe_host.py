@@ -4,8 +4,6 @@ the kernels use no scratch memory and spill no register - and the inputs of the 
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,9 +12,8 @@ import mgf_amd
 from mgf_amd import _capi
 from tests import batch_observe_cases as OC
 from tests import batch_query_cases as BQ
-from tests.util import oracle_world
+from tests.util import ROOT, kernel_resources, oracle_world, read
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = {
     "mgf_batch_read_body_contacts": r"mgf_status mgf_batch_read_body_contacts\(mgf_batch\* b, int64_t world, mgf_body_contacts\* out, int64_t cap\);",
     "mgf_batch_overlap_aabb_many": r"mgf_status mgf_batch_overlap_aabb_many\(mgf_batch\* b, const int32_t\* world, const mgf_aabb\* boxes, int64_t n,\s*"
@@ -24,12 +21,8 @@ ENTRY_POINTS = {
 }
 
 
-def _read(*path):
-    return open(os.path.join(ROOT, *path)).read()
-
-
 def test_header_declares_and_defines_them():
-    h = _read("include", "mgf_hip.h")
+    h = read("include", "mgf_hip.h")
     section = h[h.index("many small worlds"):]
     for name, sig in ENTRY_POINTS.items():
         assert re.search(r"MGF_API " + sig, section), name
@@ -43,9 +36,9 @@ def test_header_declares_and_defines_them():
     for word in ("the reference has no such report", "Tangent impulses are not part of it", "mgf_constraint does not carry them",
                  "unchanged by mgf_batch_write_state", "out_offsets and *total are always filled"):
         assert word in section, word
-    for text in (h, _read("DESIGN.md")):
+    for text in (h, read("DESIGN.md")):
         assert "no box-overlap query" not in text
-    readme = _read("README.md")
+    readme = read("README.md")
     for name in ("read_body_contacts", "overlap_aabb_many"):
         assert name in readme[readme.index("mgf_batch_new"):], name
 
@@ -63,7 +56,7 @@ def test_library_and_binding_export_them():
 
 
 def test_integration_md_has_the_rust_twins():
-    text = _read("INTEGRATION.md")
+    text = read("INTEGRATION.md")
     assert "pub fn mgf_batch_read_body_contacts(b: *mut mgf_batch, world: i64, out: *mut mgf_body_contacts, cap: i64) -> mgf_status;" in text
     assert re.search(r"pub fn mgf_batch_overlap_aabb_many\(b: \*mut mgf_batch, world: \*const i32, boxes: \*const mgf_aabb, n: i64, out_offsets: \*mut u64,\s*"
                      r"out_bodies: \*mut u32, cap: i64, total: \*mut i64\) -> mgf_status;", text)
@@ -113,12 +106,7 @@ def test_bad_arguments_are_refused_before_the_handle_or_a_device_is_touched():
 def test_the_kernels_use_no_scratch_and_spill_nothing():
     if not os.path.exists(os.path.join(ROOT, "mgf_amd", "libmgf_hip.so")) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("needs the built library and the ROCm LLVM tools")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "k_batch_observe_"], capture_output=True, text=True, check=True).stdout
-    rows = {}
-    for line in out.splitlines()[1:]:
-        m = re.match(r"(.{80}) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+)$", line)
-        if m:
-            rows[m.group(1).strip()] = tuple(m.group(k) for k in range(2, 8))  # vgpr, sgpr, scratch, lds, sgpr spills, vgpr spills
+    rows = kernel_resources("k_batch_observe_")
     assert set(rows) == {"k_batch_observe_contacts", "k_batch_observe_overlap<false>", "k_batch_observe_overlap<true>"}, rows
     bad = {k: v for k, v in rows.items() if (v[2], v[4], v[5]) != ("0", "0", "0")}
     assert not bad, bad

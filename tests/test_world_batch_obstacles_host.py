@@ -18,8 +18,8 @@ import pytest
 import mgf_amd
 from mgf_amd import _capi
 from tests import batch_obstacle_cases as BC
+from tests.util import ROOT, kernel_resources, read
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = {
     "mgf_batch_add_obstacle": r"mgf_status mgf_batch_add_obstacle\(mgf_batch\* b, const mgf_compound\* c, int32_t\* id\);",
     "mgf_batch_set_world_obstacles": r"mgf_status mgf_batch_set_world_obstacles\(mgf_batch\* b, const int32_t\* world, const int32_t\* obstacle, "
@@ -29,13 +29,9 @@ ENTRY_POINTS = {
 }
 
 
-def _read(*path):
-    return open(os.path.join(ROOT, *path)).read()
-
-
 # ---- a ------------------------------------------------------------------------------------------------------------------------------------
 def test_header_library_binding_and_documents_carry_the_entry_points():
-    h = _read("include", "mgf_hip.h")
+    h = read("include", "mgf_hip.h")
     section = h[h.index("many small worlds"):]
     lib = mgf_amd.load_library()
     for name, sig in ENTRY_POINTS.items():
@@ -46,7 +42,7 @@ def test_header_library_binding_and_documents_carry_the_entry_points():
     # the two sentences that said a batch has none are gone, in the header and in the design document
     flat = " ".join(h.split())
     assert "no obstacles" not in flat and "matches nothing" not in flat and "a batch has no obstacles" not in flat
-    design = " ".join(_read("DESIGN.md").split())
+    design = " ".join(read("DESIGN.md").split())
     assert "no obstacles, no ghosts" not in design and "is accepted and matches nothing" not in design
     for word in ("the obstacle table", "mgf_compound_set_pose", "MGF_HIT_OBSTACLE", "keeps its place in a world's list", "n_terrain like every other record"):
         assert word in " ".join(section.split()), word
@@ -56,9 +52,9 @@ def test_header_library_binding_and_documents_carry_the_entry_points():
     assert len(lib.mgf_batch_add_obstacle.argtypes) == 3 and len(lib.mgf_batch_set_world_obstacles.argtypes) == 6
     for method in ("add_obstacle", "set_world_obstacles", "obstacle_count", "world_obstacle_count"):
         assert callable(getattr(mgf_amd.WorldBatch, method)), method
-    for text in (_read("README.md"), _read("DESIGN.md")):
+    for text in (read("README.md"), read("DESIGN.md")):
         assert "Obstacles per world" in text and "mgf_batch_set_world_obstacles" in text
-    rust = _read("INTEGRATION.md")
+    rust = read("INTEGRATION.md")
     assert "pub fn mgf_batch_add_obstacle(b: *mut mgf_batch, c: *const mgf_compound, id: *mut i32) -> mgf_status;" in rust
     assert "pub fn mgf_batch_obstacle_count(b: *const mgf_batch) -> i64;" in rust
     assert "pub fn mgf_batch_world_obstacle_count(b: *const mgf_batch, world: i64) -> i64;" in rust
@@ -111,12 +107,7 @@ def test_bad_arguments_are_refused_before_the_handle_or_a_device_is_touched():
 def test_the_batch_kernels_use_no_scratch_spill_nothing_and_keep_their_lane_masks():
     if not os.path.exists(os.path.join(ROOT, "mgf_amd", "libmgf_hip.so")) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("needs the built library and the ROCm LLVM tools")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "k_batch_"], capture_output=True, text=True, check=True).stdout
-    rows = {}
-    for line in out.splitlines()[1:]:
-        m = re.match(r"(.{80}) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+)$", line)
-        if m:
-            rows[m.group(1).strip()] = tuple(m.group(k) for k in range(2, 8))  # vgpr, sgpr, scratch, lds, sgpr spills, vgpr spills
+    rows = kernel_resources("k_batch_")
     for name in ("k_batch_front", "k_batch_faces", "k_batch_pairs", "k_batch_pack", "k_batch_setup", "k_batch_solve", "k_batch_query_ray",
                  "k_batch_query_sweep_bodies", "k_batch_query_sweep_faces", "k_batch_query_ray_obstacles", "k_batch_query_sweep_obstacles"):
         assert name in rows, (name, sorted(rows))

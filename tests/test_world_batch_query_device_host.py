@@ -6,8 +6,6 @@ scratch and spill nothing - and the plan the device builds, modelled in numpy ov
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,8 +13,8 @@ import pytest
 import mgf_amd
 from mgf_amd import _capi
 from tests import batch_query_device_cases as QD
+from tests.util import ROOT, kernel_resources, read
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = {
     "mgf_batch_raycast_many_dev": r"mgf_status mgf_batch_raycast_many_dev\(mgf_batch\* b, const int32_t\* world_dev, const mgf_particle\* parts_dev, int64_t n,\s*"
                                   r"const int32_t\* ignore_body_dev, int32_t kinds_mask, mgf_ray_hit\* out_dev\);",
@@ -28,13 +26,9 @@ NEW_KERNELS = {"k_batch_query_plan_count<7u>", "k_batch_query_plan_count<13u>", 
 GUARDED = {"k_batch_query_sweep_faces", "k_batch_query_ray_obstacles", "k_batch_query_sweep_obstacles"}
 
 
-def _read(*path):
-    return open(os.path.join(ROOT, *path)).read()
-
-
 # ---- 1 ------------------------------------------------------------------------------------------------------------------------------------
 def test_header_library_binding_and_integration_md_carry_the_calls():
-    h = _read("include", "mgf_hip.h")
+    h = read("include", "mgf_hip.h")
     for name, sig in ENTRY_POINTS.items():
         assert re.search(r"MGF_API " + sig, h), name
     section = h[h.index("device-pointer calls"):]
@@ -56,21 +50,21 @@ def test_header_library_binding_and_integration_md_carry_the_calls():
         assert fn.restype is C.c_int32 and list(fn.argtypes) == [vp, vp, vp, i64, vp, i32, vp], name
     for method in ("raycast_dev", "sweep_dev"):
         assert callable(getattr(mgf_amd.WorldBatch, method)), method
-    flat = re.sub(r"\s+", " ", _read("INTEGRATION.md"))
+    flat = re.sub(r"\s+", " ", read("INTEGRATION.md"))
     for sig in ("pub fn mgf_batch_raycast_many_dev(b: *mut mgf_batch, world_dev: *const i32, parts_dev: *const mgf_particle, n: i64, "
                 "ignore_body_dev: *const i32, kinds_mask: i32, out_dev: *mut mgf_ray_hit) -> mgf_status;",
                 "pub fn mgf_batch_sweep_many_dev(b: *mut mgf_batch, world_dev: *const i32, casts_dev: *const mgf_moving_component, n: i64, "
                 "ignore_body_dev: *const i32, kinds_mask: i32, out_dev: *mut mgf_sweep_hit) -> mgf_status;"):
         assert sig in flat, sig
-    kernels = _read("mgf_amd", "csrc", "kernels.h")
+    kernels = read("mgf_amd", "csrc", "kernels.h")
     assert '#include "k_batch_query_dev.h"' in kernels and "k_batch_query_plan_count" in kernels
-    hip = _read("mgf_amd", "csrc", "mgf_hip.hip")
+    hip = read("mgf_amd", "csrc", "mgf_hip.hip")
     assert hip.index('#include "host_batch_query.inc"') < hip.index('#include "host_batch_dev.inc"') < hip.index('#include "host_batch_query_dev.inc"')
-    design = _read("DESIGN.md")
+    design = read("DESIGN.md")
     sub = design[design.index("Device-pointer queries"):]
     for word in ("k_batch_query_plan_count", "k_batch_query_plan_fill", "lane scheduling", "batch_device_query_bench.py"):
         assert word in sub, word
-    assert "raycast_dev" in _read("README.md") and "sweep_dev" in _read("README.md")
+    assert "raycast_dev" in read("README.md") and "sweep_dev" in read("README.md")
     assert os.path.exists(os.path.join(ROOT, "tools", "batch_device_query_bench.py"))
 
 
@@ -102,40 +96,51 @@ def test_every_device_pointer_is_looked_up_before_the_first_enqueue():
     """the order "check, then enqueue", read in the source: in host_batch_query_dev.inc - both entry points are one line each into
     batch_query_dev_run - the last dev_span and the overlap check come before the first thing that enqueues (a push of the mirror, an
     upload of a table, a memset, a copy, a launch, a prefix sum), and the refusals that need no device before the handle is read"""
-    src = _read("mgf_amd", "csrc", "host_batch_query_dev.inc")
+    src = read("mgf_amd", "csrc", "host_batch_query_dev.inc")
     parts = re.split(r"\n(?=extern \"C\"|template <class Q>\nstatic mgf_status batch_query_dev_run)", src)
     assert len(parts) == 4, len(parts)
     run, entries = parts[1], parts[2:]
     for e in entries:
         assert "return batch_query_dev_run(" in e and not re.search(r"dev_span|<<<|Async|batch_push|batch_dev_begin", e), e[:100]
-    enqueue = r"batch_push\(|batch_dev_begin\(|batch_env_sync\(|batch_cols_refresh\(|hipMemsetAsync|hipMemcpyAsync|<<<|prim_exclusive_scan_u32|\.ensure\("
+    enqueue = (r"batch_ray_obstacles\(|batch_sweep_tail\(|batch_push\(|batch_dev_begin\(|batch_env_sync\(|batch_cols_refresh\(|hipMemsetAsync|hipMemcpyAsync|<<<|"
+               r"prim_exclusive_scan_u32|\.ensure\(")
     first_enqueue = min(m.start() for m in re.finditer(enqueue, run))
     checks = [m.start() for m in re.finditer(r"dev_span\(", run)]
     assert len(checks) == 4 and max(checks) < first_enqueue
     for name in ("world_dev, 4 \\* n", "q_dev, sizeof\\(Q\\) \\* n", "ignore_dev, 4 \\* n", "out_dev, 4 \\* kOut \\* n"):
         assert re.search(r"dev_span\(b->ctx, " + name, run), name
-    overlaps = [m.start() for m in re.finditer(r"dev_bytes_overlap\(out_dev", run)]
-    assert len(overlaps) == 3 and max(checks) < min(overlaps) and max(overlaps) < first_enqueue
+    # out_dev, the one array written, against each of the three inputs (which may share bytes among themselves): the one helper over
+    # the list, ahead of the first enqueue, with the message as it was
+    listed = run.index('arrays[4] = {{out_dev, 4 * kOut * n, "out_dev"}, {world_dev, 4 * n, "world_dev"}, {q_dev, sizeof(Q) * n, "q_dev"}, '
+                       '{ignore_dev, 4 * n, "ignore_dev"}};')
+    overlap = run.index('dev_outputs_overlap(arrays, 4, 1, "an input array")')
+    assert max(checks) < listed < overlap < first_enqueue and run.count("dev_outputs_overlap(") == 1
     assert run.index("out_dev overlaps an input array") < first_enqueue
+    helper = parts[0][parts[0].index("static mgf_status dev_outputs_overlap("):]
+    assert "dev_bytes_overlap(a[i].p, a[i].bytes, a[j].p, a[j].bytes)" in helper and "for (size_t j = i + 1; j < n; ++j)" in helper
+    assert '"%s overlaps %s", a[i].name, j < n_out || !inputs ? a[j].name : inputs' in helper
+    assert not re.search(enqueue, helper) and "b->" not in helper
     # before the handle is read: NULL batch / n (batch_dev_args), NULL arrays, the mask
     first_deref = run.index("b->")
     for early in ("batch_dev_args(b, n_in)", "\"NULL argument\"", "query_mask_check(kinds_mask)"):
         assert run.index(early) < first_deref, early
     # n = 0 launches nothing: it returns before the first enqueue
     assert run.index("if (n == 0) return MGF_OK;") < first_enqueue
-    k = _read("mgf_amd", "csrc", "k_batch_query_dev.h")
+    k = read("mgf_amd", "csrc", "k_batch_query_dev.h")
     count = k[k.index("void k_batch_query_plan_count"):k.index("void k_batch_query_plan_cut")]
     assert count.index("(uint32_t)w < A.K") < count.index("A.cnt[w]") and "atomicAdd(A.skipped, 1ull)" in count
     assert not re.search(r"atomic\w*\((?![^;]*(skipped|cnt))", k), "an atomic on anything but the integer counters"
-    q = _read("mgf_amd", "csrc", "k_batch_query.h")
+    q = read("mgf_amd", "csrc", "k_batch_query.h")
     for kernel in GUARDED:
         body = q[q.index("void " + kernel + "("):]
         body = body[:body.index("\n}\n")]
         assert body.index("if (w < 0) return;") < min(body.index("tdesc[") if "tdesc[" in body else 1 << 30, body.index("batch_terrain_of(") if "batch_terrain_of(" in body else 1 << 30), kernel
         assert "world[i]" not in body, kernel
-    for item in ("bq_ray_item", "bq_sweep_item"):
+    for item in ("bq_ray_front", "bq_sweep_item"):   # (bq_ray_item<SRC> is bq_ray_front<SRC> over the caller's particles)
         body = q[q.index("void " + item + "("):]
         assert body.index("blockIdx.x >= *S.n_items) return;") < body.index("bq_stage(") < body.index("\n}\n"), item
+    wrapper = q[q.index("void bq_ray_item("):q.index("void k_batch_query_ray(")]
+    assert "bq_ray_front<SRC>(" in wrapper and not re.search(r"return;|__syncthreads|atomic", wrapper)
 
 
 # ---- 4 ------------------------------------------------------------------------------------------------------------------------------------
@@ -194,12 +199,7 @@ def test_the_binding_turns_a_wrong_tensor_down_before_it_calls_c():
 def test_the_new_and_the_guarded_kernels_use_no_scratch_and_spill_nothing():
     if not os.path.exists(os.path.join(ROOT, "mgf_amd", "libmgf_hip.so")) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("needs the built library and the ROCm LLVM tools")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "k_batch_query_"], capture_output=True, text=True, check=True).stdout
-    rows = {}
-    for line in out.splitlines()[1:]:
-        m = re.match(r"(.{80}) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+)$", line)
-        if m:
-            rows[m.group(1).strip()] = tuple(m.group(k) for k in range(2, 8))  # vgpr, sgpr, scratch, lds, sgpr spills, vgpr spills
+    rows = kernel_resources("k_batch_query_")
     assert NEW_KERNELS | GUARDED <= set(rows), sorted(rows)
     bad = {k: v for k, v in rows.items() if k in NEW_KERNELS | GUARDED and (v[2], v[4], v[5]) != ("0", "0", "0")}
     assert not bad, bad
@@ -208,7 +208,7 @@ def test_the_new_and_the_guarded_kernels_use_no_scratch_and_spill_nothing():
         for src in (1, 2):
             twin = rows[f"{dev}<{src}>"]
             assert twin[3] == rows[host][3] and int(twin[0]) <= int(rows[host][0]) + 8, (dev, src, twin, rows[host])
-    k = _read("mgf_amd", "csrc", "k_batch_query_dev.h")
+    k = read("mgf_amd", "csrc", "k_batch_query_dev.h")
     assert len(re.findall(r"__global__ __launch_bounds__\(kBatchBlock\)", k)) == len(re.findall(r"__global__", k)) == 5
 
 

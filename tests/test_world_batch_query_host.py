@@ -4,16 +4,14 @@ touched - and the query kernels use no scratch memory and spill no register."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import mgf_amd
 from mgf_amd import _capi
+from tests.util import ROOT, kernel_resources, read
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = {
     "mgf_batch_read_colliders": r"mgf_status mgf_batch_read_colliders\(mgf_batch\* b, int64_t world, mgf_moving_component\* out, int64_t cap\);",
     "mgf_batch_raycast_many": r"mgf_status mgf_batch_raycast_many\(mgf_batch\* b, const int32_t\* world, const mgf_particle\* parts, int64_t n,\s*"
@@ -23,12 +21,8 @@ ENTRY_POINTS = {
 }
 
 
-def _read(*path):
-    return open(os.path.join(ROOT, *path)).read()
-
-
 def test_header_declares_and_defines_the_queries():
-    h = _read("include", "mgf_hip.h")
+    h = read("include", "mgf_hip.h")
     section = h[h.index("many small worlds"):]
     for name, sig in ENTRY_POINTS.items():
         assert re.search(r"MGF_API " + sig, section), name
@@ -38,9 +32,9 @@ def test_header_declares_and_defines_the_queries():
         assert cite in section, cite
     for word in ("MGF_QUERY_OBSTACLES", "ignore_body", "query_launches", "query_run_ns", "mgf_batch_write_state does not move it"):
         assert word in section, word
-    for text in (h, _read("README.md"), _read("DESIGN.md")):
+    for text in (h, read("README.md"), read("DESIGN.md")):
         assert "no queries" not in text
-    readme = _read("README.md")
+    readme = read("README.md")
     for name in ("read_colliders", "raycast_many", "sweep_many"):
         assert name in readme[readme.index("mgf_batch_new"):], name
 
@@ -55,7 +49,7 @@ def test_library_and_binding_export_them():
 
 
 def test_integration_md_has_the_rust_twins():
-    text = _read("INTEGRATION.md")
+    text = read("INTEGRATION.md")
     assert "pub fn mgf_batch_read_colliders(b: *mut mgf_batch, world: i64, out: *mut mgf_moving_component, cap: i64) -> mgf_status;" in text
     assert re.search(r"pub fn mgf_batch_raycast_many\(b: \*mut mgf_batch, world: \*const i32, parts: \*const mgf_particle, n: i64, ignore_body: \*const i32,\s*"
                      r"kinds_mask: i32, out: \*mut mgf_ray_hit\) -> mgf_status;", text)
@@ -120,12 +114,7 @@ def test_bad_arguments_are_refused_before_the_handle_or_a_device_is_touched():
 def test_the_query_kernels_use_no_scratch_and_spill_nothing():
     if not os.path.exists(os.path.join(ROOT, "mgf_amd", "libmgf_hip.so")) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("needs the built library and the ROCm LLVM tools")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "k_batch_query_"], capture_output=True, text=True, check=True).stdout
-    rows = {}
-    for line in out.splitlines()[1:]:
-        m = re.match(r"(.{80}) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+)$", line)
-        if m:
-            rows[m.group(1).strip()] = tuple(m.group(k) for k in range(2, 8))  # vgpr, sgpr, scratch, lds, sgpr spills, vgpr spills
+    rows = kernel_resources("k_batch_query_")
     assert any("ray" in k for k in rows) and any("sweep" in k for k in rows) and "k_batch_query_gather" in rows, rows
     bad = {k: v for k, v in rows.items() if (v[2], v[4], v[5]) != ("0", "0", "0")}
     assert not bad, bad

@@ -17,13 +17,9 @@ import mgf_amd
 from mgf_amd import _capi
 from tests import batch_query_device_cases as QD
 from tests import batch_sensor_cases as SC
+from tests.util import RESOURCES, ROOT, kernel_resources, read
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("mgf_batch_set_sensors", "mgf_batch_sensor_count", "mgf_batch_cast_sensors", "mgf_batch_cast_sensors_dev")
-
-
-def _read(*path):
-    return open(os.path.join(ROOT, *path)).read()
 
 
 # ---- 1 ------------------------------------------------------------------------------------------------------------------------------------
@@ -58,7 +54,7 @@ def test_the_restatement_is_the_oracles_rotate_vector_bit_for_bit():
 
 # ---- 2 ------------------------------------------------------------------------------------------------------------------------------------
 def test_header_library_binding_and_documents_carry_the_calls():
-    h = _read("include", "mgf_hip.h")
+    h = read("include", "mgf_hip.h")
     for sig in (r"mgf_status mgf_batch_set_sensors\(mgf_batch\* b, const mgf_batch_sensor\* s, int64_t n\);",
                 r"int64_t mgf_batch_sensor_count\(const mgf_batch\* b\);",
                 r"mgf_status mgf_batch_cast_sensors\(mgf_batch\* b, int32_t kinds_mask, mgf_ray_hit\* out, mgf_particle\* parts_out, int64_t cap\);",
@@ -87,22 +83,22 @@ def test_header_library_binding_and_documents_carry_the_calls():
         assert (fn.restype, list(fn.argtypes)) == want[name], name
     for method in ("set_sensors", "sensor_count", "cast_sensors", "cast_sensors_dev"):
         assert callable(getattr(mgf_amd.WorldBatch, method)), method
-    flat = re.sub(r"\s+", " ", _read("INTEGRATION.md"))
+    flat = re.sub(r"\s+", " ", read("INTEGRATION.md"))
     for sig in ("pub fn mgf_batch_set_sensors(b: *mut mgf_batch, s: *const mgf_batch_sensor, n: i64) -> mgf_status;",
                 "pub fn mgf_batch_sensor_count(b: *const mgf_batch) -> i64;",
                 "pub fn mgf_batch_cast_sensors(b: *mut mgf_batch, kinds_mask: i32, out: *mut mgf_ray_hit, parts_out: *mut mgf_particle, cap: i64) -> mgf_status;",
                 "pub fn mgf_batch_cast_sensors_dev(b: *mut mgf_batch, kinds_mask: i32, out_dev: *mut mgf_ray_hit, parts_out_dev: *mut mgf_particle, cap: i64) -> mgf_status;",
                 "pub struct mgf_batch_sensor"):
         assert sig in flat, sig
-    kernels = _read("mgf_amd", "csrc", "kernels.h")
+    kernels = read("mgf_amd", "csrc", "kernels.h")
     assert kernels.index('#include "k_batch_query_dev.h"') < kernels.index('#include "k_batch_sensor.h"') and "k_batch_sensor_ray" in kernels
-    hip = _read("mgf_amd", "csrc", "mgf_hip.hip")
+    hip = read("mgf_amd", "csrc", "mgf_hip.hip")
     assert hip.index('#include "host_batch_query_dev.inc"') < hip.index('#include "host_batch_sensor.inc"')
-    design = _read("DESIGN.md")
+    design = read("DESIGN.md")
     sub = design[design.index("Body-mounted sensors"):]
     for word in ("k_batch_sensor_ray", "P = x + rotate(q, p)", "Out of scope", "batch_sensor_bench.py", "Compiler output"):
         assert word in sub, word
-    readme = _read("README.md")
+    readme = read("README.md")
     assert "set_sensors" in readme and "cast_sensors_dev" in readme
     assert os.path.exists(os.path.join(ROOT, "tools", "batch_sensor_bench.py"))
 
@@ -133,44 +129,82 @@ def test_what_needs_no_device_is_refused_before_the_handle_is_dereferenced():
     assert lib.mgf_batch_sensor_count(None) == -1
     # what needs the handle - a world or a body out of range, a flag bit beyond the one defined, cap below the count - is refused on the
     # host too, ahead of any device work (read here; run in tests/test_gpu_world_batch_sensors.py, where a handle exists)
-    src = _read("mgf_amd", "csrc", "host_batch_sensor.inc")
+    src = read("mgf_amd", "csrc", "host_batch_sensor.inc")
     body = src[src.index('extern "C" mgf_status mgf_batch_set_sensors('):src.index('extern "C" int64_t mgf_batch_sensor_count(')]
     first_change = body.index("b->s_rig.assign(")
-    for refusal in ("world index out of range", "body index out of range", "a bit beyond MGF_SENSOR_IGNORE_SELF"):
-        assert body.index(refusal) < first_change, refusal
+    assert body.index("batch_rig_ref_check(b, s[i].world, s[i].body, s[i].flags, \"sensor\")") < first_change   # every record, ahead of any change
+    check = src[src.index("static mgf_status batch_rig_ref_check("):src.index('extern "C" mgf_status mgf_batch_set_sensors(')]
+    assert (check.index("world index out of range: the rig was not changed") < check.index("body index out of range: the rig was not changed")
+            < check.index("a %s's flags hold a bit beyond MGF_SENSOR_IGNORE_SELF: the rig was not changed") < check.index("return MGF_OK;"))
+    assert not re.search(r"<<<|Async|hipMalloc|\.ensure\(|h2d\(|b->\w+ =[^=]", check)    # it refuses; it changes nothing
     assert not re.search(r"<<<|Async|hipMalloc|\.ensure\(|h2d\(", body)            # no device work at all
     args = src[src.index("static mgf_status batch_sensor_args("):src.index('extern "C" mgf_status mgf_batch_cast_sensors(')]
     assert args.index("MGF_ERR_CAPACITY") < args.index('"NULL argument"') < args.index("return MGF_OK;") and "ctx_bind" not in args and "<<<" not in args
 
 
 # ---- 4 ------------------------------------------------------------------------------------------------------------------------------------
+def _the_overlap_helper_compares_and_enqueues_nothing(enqueue):
+    """dev_outputs_overlap (host_batch_query_dev.inc), which every device-pointer cast calls between its last dev_span and its first
+    enqueue: dev_bytes_overlap over the pairs of its list, an error message, nothing else"""
+    src = read("mgf_amd", "csrc", "host_batch_query_dev.inc")
+    helper = src[src.index("static mgf_status dev_outputs_overlap("):src.index("// Q = ParticleIn")]
+    assert "dev_bytes_overlap(a[i].p, a[i].bytes, a[j].p, a[j].bytes)" in helper and '"%s overlaps %s"' in helper
+    assert not re.search(enqueue, helper) and "b->" not in helper
+
+
+def _the_shared_obstacle_pass():
+    """batch_ray_obstacles (host_batch_query.inc): the one launch of k_batch_query_ray_obstacles, counted"""
+    src = read("mgf_amd", "csrc", "host_batch_query.inc")
+    helper = src[src.index("static mgf_status batch_ray_obstacles("):src.index("static mgf_status batch_sweep_tail(")]
+    assert helper.count("<<<") == 1 and "k_batch_query_ray_obstacles<<<" in helper and helper.index("LAUNCH_CHECK();") < helper.index("++b->q_launches;")
+    for f in ("host_batch_query.inc", "host_batch_query_dev.inc", "host_batch_sensor.inc", "host_batch_camera.inc"):
+        text = read("mgf_amd", "csrc", f)
+        assert text.count("k_batch_query_ray_obstacles<<<") == (f == "host_batch_query.inc") and "batch_ray_obstacles(" in text, f
+    return helper
+
+
 def test_both_pointers_are_looked_up_before_the_first_enqueue():
     """the order "check, then enqueue" of mgf_batch_cast_sensors_dev, read in the source as tests/test_world_batch_query_device_host.py
     reads batch_query_dev_run: the last dev_span and the overlap check come before the first thing that enqueues - here all of that
     is batch_sensor_run - and the refusals that need no device before the context is bound"""
-    src = _read("mgf_amd", "csrc", "host_batch_sensor.inc")
+    src = read("mgf_amd", "csrc", "host_batch_sensor.inc")
     run = src[src.index('extern "C" mgf_status mgf_batch_cast_sensors_dev('):]
-    enqueue = (r"batch_sensor_run\(|batch_sensors_up\(|batch_push\(|batch_dev_begin\(|batch_env_sync\(|batch_cols_refresh\(|hipMemsetAsync|hipMemcpyAsync|<<<|"
-               r"prim_exclusive_scan_u32|\.ensure\(|h2d\(")
+    enqueue = (r"batch_sensor_run\(|batch_sensors_up\(|batch_rig_upload\(|batch_ray_obstacles\(|batch_sweep_tail\(|batch_push\(|batch_dev_begin\(|batch_env_sync\(|"
+               r"batch_cols_refresh\(|hipMemsetAsync|hipMemcpyAsync|<<<|prim_exclusive_scan_u32|\.ensure\(|h2d\(")
     first_enqueue = min(m.start() for m in re.finditer(enqueue, run))
     checks = [m.start() for m in re.finditer(r"dev_span\(", run)]
     assert len(checks) == 2 and max(checks) < first_enqueue
     for name in ("out_dev, 28 \\* n", "parts_out_dev, 28 \\* n"):
         assert re.search(r"dev_span\(b->ctx, " + name, run), name
-    overlap = run.index("dev_bytes_overlap(out_dev, 28 * n, parts_out_dev, 28 * n)")
+    # the two outputs, both written, held against each other by the one helper of host_batch_query_dev.inc
+    assert run.index('arrays[2] = {{out_dev, 28 * n, "out_dev"}, {parts_out_dev, 28 * n, "parts_out_dev"}};') < run.index("dev_outputs_overlap(arrays, 2, 2)")
+    overlap = run.index("dev_outputs_overlap(")
     assert max(checks) < overlap < first_enqueue
+    _the_overlap_helper_compares_and_enqueues_nothing(enqueue)
     assert run.index("batch_sensor_args(") < run.index("ctx_bind(") < min(checks)
     assert run.index("if (n == 0) return MGF_OK;") < first_enqueue                   # an empty rig enqueues nothing
     # everything that enqueues is in batch_sensor_run and batch_sensors_up, and those are reached from the two cast calls only
     helper = src[src.index("static mgf_status batch_sensor_run("):src.index("static mgf_status batch_sensor_args(")]
-    assert "<<<" in helper and "k_batch_sensor_ray<<<" in helper and "k_batch_query_ray_obstacles<<<" in helper
-    assert helper.count("<<<") == 2 and "hipStreamSynchronize" not in helper and "hipMemcpy" not in helper   # no wait, no copy
+    # its own kernel's launch and the shared obstacle pass; neither it nor that pass waits or copies
+    assert helper.count("<<<") == 1 and "k_batch_sensor_ray<<<" in helper and helper.index("k_batch_sensor_ray<<<") < helper.index("batch_ray_obstacles(")
+    assert "hipStreamSynchronize" not in helper and "hipMemcpy" not in helper
+    obstacles = _the_shared_obstacle_pass()
+    assert "hipStreamSynchronize" not in obstacles and "hipMemcpy" not in obstacles
     up = src[src.index("static mgf_status batch_sensors_up("):src.index("// The launches of a cast")]
-    assert up.index("if (!b->s_stale) return MGF_OK;") < up.index("h2d(")             # the steady state uploads nothing
-    k = _read("mgf_amd", "csrc", "k_batch_sensor.h")
+    assert up.index("if (!b->s_stale) return MGF_OK;") < up.index("internal error") < up.index("batch_rig_upload(") and "h2d(" not in up
+    upload = src[src.index("static mgf_status batch_rig_upload("):src.index("// the rig onto the device")]
+    assert upload.count("h2d(") == 1 and upload.count(".ensure(") == 1 and "<<<" not in upload          # the steady state uploads nothing; ONE copy
+    # no exit ahead of a barrier, no atomic: the front the kernel shares with k_batch_query_ray (k_batch_query.h) holds every exit and
+    # every barrier, and what the kernel itself brings - the loader and the store behind the hit - holds neither
+    q = read("mgf_amd", "csrc", "k_batch_query.h")
+    front = q[q.index("void bq_ray_front("):]
+    front = front[:front.index("\n}\n")]
+    assert front.count("return;") == 2 and "atomic" not in front
+    assert (front.index("blockIdx.x >= *S.n_items) return;") < front.index("bq_stage(") < front.index("load(") < front.index("bq_reduce(")
+            < front.index("if (W.sub != 0u || !W.live) return;") < front.index("q_ray_store(") < front.index("done("))
+    k = read("mgf_amd", "csrc", "k_batch_sensor.h")
     body = k[k.index("void k_batch_sensor_ray("):]
-    assert body.index("bq_stage(") < body.index("bq_reduce(") < body.index("return;") and body.count("return;") == 1   # no exit ahead of a barrier
-    assert "atomic" not in body
+    assert "bq_ray_front<kItemTable>(" in body and not re.search(r"return;|__syncthreads|atomic|bq_stage|bq_reduce", body)
 
 
 # ---- 5 ------------------------------------------------------------------------------------------------------------------------------------
@@ -215,46 +249,25 @@ def test_the_binding_turns_a_wrong_tensor_down_before_it_calls_c():
 
 
 # ---- 6 ------------------------------------------------------------------------------------------------------------------------------------
-Z = ("0", "0", "0", "0")
-RESOURCES = {  # DESIGN.md, "Device-pointer queries", compiler output: VGPR, SGPR | scratch, static LDS, spills
-    "k_batch_query_gather": ("10", "14") + Z, "k_batch_query_plan_count<7u>": ("9", "20") + Z, "k_batch_query_plan_count<13u>": ("14", "26") + Z,
-    "k_batch_query_plan_cut": ("4", "14") + Z, "k_batch_query_plan_fill": ("10", "20") + Z,
-    "k_batch_query_ray": ("45", "65") + Z, "k_batch_query_ray_dev<1>": ("45", "65") + Z, "k_batch_query_ray_dev<2>": ("45", "65") + Z,
-    "k_batch_query_sweep_bodies": ("108", "90") + Z, "k_batch_query_sweep_bodies_dev<1>": ("108", "90") + Z,
-    "k_batch_query_sweep_bodies_dev<2>": ("108", "90") + Z, "k_batch_query_sweep_faces": ("133", "69", "0", "9216", "0", "0"),
-    "k_batch_query_ray_obstacles": ("68", "63") + Z, "k_batch_query_sweep_obstacles": ("115", "87") + Z,
-}
-
-
-def _resources(prefix):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), prefix], capture_output=True, text=True, check=True).stdout
-    rows = {}
-    for line in out.splitlines()[1:]:
-        m = re.match(r"(.{80}) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+)$", line)
-        if m:
-            rows[m.group(1).strip()] = tuple(m.group(k) for k in range(2, 8))  # vgpr, sgpr, scratch, lds, sgpr spills, vgpr spills
-    return rows
-
-
 def test_the_new_kernel_uses_no_scratch_and_the_query_kernels_keep_their_figures():
     if not os.path.exists(os.path.join(ROOT, "mgf_amd", "libmgf_hip.so")) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("needs the built library and the ROCm LLVM tools")
-    rows = _resources("k_batch_sensor_")
+    rows = kernel_resources("k_batch_sensor_")
     assert set(rows) == {"k_batch_sensor_ray"}, sorted(rows)
     v = rows["k_batch_sensor_ray"]
     assert (v[2], v[3], v[4], v[5]) == ("0", "0", "0", "0"), v               # no scratch, no static LDS, no spills
-    old = _resources("k_batch_query_")
+    old = kernel_resources("k_batch_query_")
     assert int(v[0]) <= int(old["k_batch_query_ray"][0]) + 8, (v, old["k_batch_query_ray"])   # one piece of work, about the same registers
     assert set(old) == set(RESOURCES), sorted(old)
     for name, want in RESOURCES.items():
         assert old[name] == want, (name, old[name], want)
-    design = re.sub(r"\s+", " ", _read("DESIGN.md"))
+    design = re.sub(r"\s+", " ", read("DESIGN.md"))
     for text in ("`k_batch_query_ray` 45 / 65 / 0 / 0 / 0", "`k_batch_query_sweep_faces` 133 / 69 / 9216 / 0 / 0", "`_ray_obstacles` 68 / 63 / 0 / 0 / 0",
                  "`k_batch_query_sweep_bodies` 108 / 90 / 0 / 0 / 0", "`k_batch_query_plan_fill` 10 / 20", "`_sweep_obstacles` 115 / 87 / 0 / 0 / 0"):
         assert text in design, text
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_lane_masks.py")], capture_output=True, text=True)
     assert r.returncode == 0 and " 0 lane masks" in r.stdout, r.stdout[-400:]
-    k = _read("mgf_amd", "csrc", "k_batch_sensor.h")
+    k = read("mgf_amd", "csrc", "k_batch_sensor.h")
     assert len(re.findall(r"__global__ __launch_bounds__\(kBatchBlock\)", k)) == len(re.findall(r"__global__", k)) == 1
 
 

@@ -3,7 +3,6 @@ without a GPU: the header, the library and the binding carry them, bad arguments
 the table WorldBatch.from_scenes(own_terrain=True) builds - and, from the oracle alone, the conditions on the inputs of
 tests/test_gpu_world_batch_terrains.py, so that the GPU tests cannot pass on nothing."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -12,8 +11,8 @@ import pytest
 import mgf_amd
 from mgf_amd import _capi
 from tests import batch_terrain_cases as TC
+from tests.util import read
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = {
     "mgf_batch_add_terrain": r"mgf_status mgf_batch_add_terrain\(mgf_batch\* b, const mgf_mesh\* mesh, int32_t\* id\);",
     "mgf_batch_set_world_terrain": r"mgf_status mgf_batch_set_world_terrain\(mgf_batch\* b, const int32_t\* world, const int32_t\* terrain, "
@@ -22,13 +21,9 @@ ENTRY_POINTS = {
 }
 
 
-def _read(*path):
-    return open(os.path.join(ROOT, *path)).read()
-
-
 # ---- a ------------------------------------------------------------------------------------------------------------------------------------
 def test_header_library_and_binding_carry_the_entry_points():
-    h = _read("include", "mgf_hip.h")
+    h = read("include", "mgf_hip.h")
     section = h[h.index("many small worlds"):]
     lib = mgf_amd.load_library()
     for name, sig in ENTRY_POINTS.items():
@@ -44,9 +39,9 @@ def test_header_library_and_binding_carry_the_entry_points():
     assert len(lib.mgf_batch_add_terrain.argtypes) == 3 and len(lib.mgf_batch_set_world_terrain.argtypes) == 5
     for method in ("add_terrain", "set_world_terrain", "terrain_count", "set_terrain"):
         assert callable(getattr(mgf_amd.WorldBatch, method)), method
-    for text in (_read("README.md"), _read("DESIGN.md")):
+    for text in (read("README.md"), read("DESIGN.md")):
         assert "mgf_batch_set_world_terrain" in text
-    rust = _read("INTEGRATION.md")
+    rust = read("INTEGRATION.md")
     assert "pub fn mgf_batch_add_terrain(b: *mut mgf_batch, mesh: *const mgf_mesh, id: *mut i32) -> mgf_status;" in rust
     assert "pub fn mgf_batch_terrain_count(b: *const mgf_batch) -> i64;" in rust
     assert re.search(r"pub fn mgf_batch_set_world_terrain\(b: \*mut mgf_batch, world: \*const i32, terrain: \*const i32, pos: \*const mgf_vec3,\s*n: i64\) -> mgf_status;", rust)

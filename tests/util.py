@@ -1,7 +1,43 @@
-"""Test helpers: build the same scene in the CPU oracle and in the HIP world."""
+"""Test helpers: build the same scene in the CPU oracle and in the HIP world; read a file of the repository; the table of
+tools/kernel_resources.py and the figures DESIGN.md records of the batch's query kernels."""
+import os
+import re
+import subprocess
+import sys
+
 import numpy as np
 
 from oracle import oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def read(*path):
+    return open(os.path.join(ROOT, *path)).read()
+
+
+def kernel_resources(prefix=None):
+    """tools/kernel_resources.py's table of the built library, the kernels whose names hold `prefix` (None: all):
+    name -> (vgpr, sgpr, scratch, static lds, sgpr spills, vgpr spills), as the strings of the table"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py")] + ([prefix] if prefix else []), capture_output=True, text=True,
+                         check=True).stdout
+    rows = {}
+    for line in out.splitlines()[1:]:
+        m = re.match(r"(.{80}) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+) +(\S+)$", line)
+        if m:
+            rows[m.group(1).strip()] = tuple(m.group(k) for k in range(2, 8))
+    return rows
+
+
+Z = ("0", "0", "0", "0")
+RESOURCES = {  # DESIGN.md, "Device-pointer queries", compiler output: VGPR, SGPR | scratch, static LDS, spills
+    "k_batch_query_gather": ("10", "14") + Z, "k_batch_query_plan_count<7u>": ("9", "20") + Z, "k_batch_query_plan_count<13u>": ("14", "26") + Z,
+    "k_batch_query_plan_cut": ("4", "14") + Z, "k_batch_query_plan_fill": ("10", "20") + Z,
+    "k_batch_query_ray": ("45", "65") + Z, "k_batch_query_ray_dev<1>": ("45", "65") + Z, "k_batch_query_ray_dev<2>": ("45", "65") + Z,
+    "k_batch_query_sweep_bodies": ("108", "90") + Z, "k_batch_query_sweep_bodies_dev<1>": ("108", "90") + Z,
+    "k_batch_query_sweep_bodies_dev<2>": ("108", "90") + Z, "k_batch_query_sweep_faces": ("133", "69", "0", "9216", "0", "0"),
+    "k_batch_query_ray_obstacles": ("68", "63") + Z, "k_batch_query_sweep_obstacles": ("115", "87") + Z,
+}
 
 
 def oracle_world(scene, order=O.ORDER_CANONICAL):
