@@ -793,7 +793,8 @@ MGF_API mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_worl
  *   mgf_batch_cast_sensors / _cast_sensors_dev     "query_launches": the collider gather behind a step (1, once), then
  *                                                  MGF_BATCH_SENSOR_LAUNCHES = 1, and obstacles 1 where the mask asks for them and a
  *                                                  world has one
- * OUT OF SCOPE here: device-pointer box queries (their CSR total needs a host wait); rays given in a body's frame per call (a rig that is
+ * OUT OF SCOPE here: device-pointer box queries (their CSR total needs a host wait - a record of fixed width per box needs none:
+ * mgf_batch_read_zones_dev / mgf_batch_overlap_first_dev, below); rays given in a body's frame per call (a rig that is
  * set once has mgf_batch_set_sensors / _cast_sensors_dev, below); a step without its
  * one host wait per call (the capacity re-runs need it); hipGraph capture of these calls; anything for the lone mgf_world (it has
  * mgf_world_export_bodies / _import_ghosts / _device_ptr). */
@@ -947,6 +948,57 @@ MGF_API mgf_status mgf_batch_cast_cameras(mgf_batch* b, int32_t kinds_mask, floa
  * the device-pointer calls (4, 28 and 28 bytes a pixel), and any two of the three arrays overlapping. */
 MGF_API mgf_status mgf_batch_cast_cameras_dev(mgf_batch* b, int32_t kinds_mask, float* depth_dev, mgf_ray_hit* hits_dev, mgf_particle* parts_out_dev,
                                               int64_t cap);
+/* ---- box zones: who is in this box - the count and the first k bodies, a record of fixed width, answered on the device ----
+ * A goal region, a pressure plate, a proximity volume round an agent, "the k bodies near me": an axis-aligned box whose centre is fixed
+ * in the frame of a body, or in the world.  mgf_batch_overlap_aabb_many answers such a box in CSR form, whose total the caller must know
+ * before it can size the lists: a host wait.  A policy reads an observation of fixed width; with a record of 1 + k words per box no
+ * total is needed, count and fill are one pass, and nothing waits.
+ * A zone is a record (world, body, p, r, flags, reserved): body an index within world, or -1 for a zone fixed in the world.  With x and q
+ * the body's rows as mgf_batch_read_state returns them - x WITHOUT delta, as for a sensor - the zone's box is the mgf_aabb
+ *     c = x + rotate(q, p)      r = r            (body = -1: c = p)
+ * rotate and the add exactly the sensors' f32 operations (above): every operation rounded on its own, no fused multiply-add - c is
+ * defined to the bit.  The box stays axis-aligned: only its centre rides on the body.  p and r are taken as given: a NaN or a negative
+ * half extent answers as the single Overlaps<AABB> test does, as in mgf_batch_overlap_aabb_many (a NaN box holds nothing).
+ * The record of a zone, for a call's k: let `list` be what mgf_batch_overlap_aabb_many reports for that box against `world` at that
+ * moment - the bodies whose tight bounds of "the collider a query sees" (above) overlap it, in ascending body index - with `body` removed
+ * if flags & MGF_SENSOR_IGNORE_SELF.  The record is 1 + k int32 words: word 0 is len(list), the full count, NOT truncated; words 1 .. k
+ * are list[0 .. min(len, k)); the rest are -1.  Every word is defined to the bit.
+ * After a mgf_batch_write_state a zone follows the new x and q AT ONCE; the colliders move at the next tick.  Nothing of the tick's state
+ * is touched - a step after a read is bit-identical to one without it.
+ * "query_launches" of a read: the collider gather behind a step (1, once), then MGF_BATCH_ZONE_LAUNCHES = 1, whatever the number of
+ * worlds, zones and k.  No HIP events: "query_run_ns" is 0.
+ * OUT OF SCOPE here: a world tensor for mgf_batch_overlap_first_dev; oriented boxes (the reference's Overlaps is AABB against AABB);
+ * nearest-first ordering; zones on the lone mgf_world; a rig chosen per call by a device mask; hipGraph capture; terrain faces or
+ * obstacles in a zone. */
+#define MGF_BATCH_ZONE_LAUNCHES 1
+typedef struct mgf_batch_zone { int32_t world, body; mgf_vec3 p, r; int32_t flags, reserved; } mgf_batch_zone;  /* 40 bytes */
+/* Replaces the zone rig by a copy of z[0 .. n); n = 0 clears it.  Checked on the host and refused with MGF_ERR_INVALID, the rig as it
+ * was: what mgf_batch_set_sensors refuses (a NULL batch, a NULL array with n > 0, a negative n or n > INT32_MAX, a world out of range, a
+ * body >= mgf_batch_len(b, world), a flag bit beyond MGF_SENSOR_IGNORE_SELF); body < -1; body = -1 together with MGF_SENSOR_IGNORE_SELF;
+ * reserved != 0.  No device work: the rig goes up with the next read.  It is independent of the sensor and camera rigs.  It names
+ * (world, body): mgf_batch_add_bodies afterwards leaves every zone on the body it named. */
+MGF_API mgf_status mgf_batch_set_zones(mgf_batch* b, const mgf_batch_zone* z, int64_t n);
+/* the zones of the rig; -1 for NULL */
+MGF_API int64_t mgf_batch_zone_count(const mgf_batch* b);
+/* The record of zone i at out[(1 + k) * i], in the order of the array mgf_batch_set_zones was given; boxes_out non-NULL: also its box
+ * (c, r) as formed at boxes_out[i].  cap: records each array holds.  MGF_ERR_INVALID: a NULL batch, k < 0 or k > MGF_BATCH_MAX_BODIES,
+ * a negative cap, NULL out with a rig that is not empty; MGF_ERR_CAPACITY: cap below mgf_batch_zone_count.  An empty rig: MGF_OK, nothing
+ * enqueued.  Synchronous: one download, one host wait. */
+MGF_API mgf_status mgf_batch_read_zones(mgf_batch* b, int32_t k, int32_t* out, mgf_aabb* boxes_out, int64_t cap);
+/* The same with both arrays in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for.  In
+ * the steady state - the rig and the batch on the device - no host wait and no copy between host and device.  Also refused with
+ * MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls (4 (1 + k) count and 24 count bytes),
+ * and out_dev's bytes overlapping boxes_out_dev's. */
+MGF_API mgf_status mgf_batch_read_zones_dev(mgf_batch* b, int32_t k, int32_t* out_dev, mgf_aabb* boxes_out_dev, int64_t cap);
+/* The same kernel for boxes the caller computed on the device.  The fixed layout only: n must be a multiple of n_worlds (else
+ * MGF_ERR_INVALID), box i is held against world i / (n / n_worlds); out_dev[(1 + k) * i ...] is the record of box i as defined above,
+ * with ignore_body_dev[i] (NULL: none) removed from its list - only ever compared with a body index: a value that is no body of that
+ * world removes nothing.  Refused with MGF_ERR_INVALID, nothing enqueued, in the order of mgf_batch_raycast_many_dev with
+ * world_dev == NULL: a NULL batch, a negative n or n > INT32_MAX, NULL boxes_dev / out_dev with n > 0, k < 0 or k >
+ * MGF_BATCH_MAX_BODIES, n no multiple of n_worlds, a pointer that fails the look-up (boxes_dev 24 n bytes, ignore_body_dev 4 n, out_dev
+ * 4 (1 + k) n), out_dev's bytes overlapping those of an input array.  Not waited for; MGF_BATCH_ZONE_LAUNCHES = 1 launch. */
+MGF_API mgf_status mgf_batch_overlap_first_dev(mgf_batch* b, const mgf_aabb* boxes_dev, int64_t n, const int32_t* ignore_body_dev, int32_t k,
+                                               int32_t* out_dev);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /

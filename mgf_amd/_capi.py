@@ -51,6 +51,10 @@ class BatchCamera(C.Structure):
                 ("far", C.c_float), ("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BatchZone(C.Structure):
+    _fields_ = [("world", C.c_int32), ("body", C.c_int32), ("p", Vec3), ("r", Vec3), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Component(C.Structure):
     _fields_ = [("tag", C.c_int32), ("p", Vec3), ("d", Vec3), ("r", C.c_float)]
 
@@ -132,6 +136,9 @@ SENSOR_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("p", "<f4", 3), ("d
 CAMERA_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("p", "<f4", 3), ("r", "<f4", 4), ("tan_x", "<f4"), ("tan_y", "<f4"), ("far", "<f4"),
                          ("width", "<i4"), ("height", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 assert CAMERA_DTYPE.itemsize == 64
+# mgf_batch_zone: a box whose centre is fixed in the frame of body `body` of world `world` (body -1: in the world), half extents r
+ZONE_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("p", "<f4", 3), ("r", "<f4", 3), ("flags", "<i4"), ("reserved", "<i4")])
+assert ZONE_DTYPE.itemsize == C.sizeof(BatchZone) == 40
 BATCH_MAX_BODIES = 1024  # MGF_BATCH_MAX_BODIES
 BATCH_MAX_WORLD_OBSTACLES = 64  # MGF_BATCH_MAX_WORLD_OBSTACLES
 BATCH_DEV_SET_LAUNCHES = 3  # MGF_BATCH_DEV_SET_LAUNCHES
@@ -140,6 +147,7 @@ SENSOR_IGNORE_SELF = 1  # MGF_SENSOR_IGNORE_SELF
 BATCH_SENSOR_LAUNCHES = 1  # MGF_BATCH_SENSOR_LAUNCHES
 BATCH_CAMERA_LAUNCHES = 1  # MGF_BATCH_CAMERA_LAUNCHES
 CAMERA_MAX_SIDE = 4096  # MGF_CAMERA_MAX_SIDE
+BATCH_ZONE_LAUNCHES = 1  # MGF_BATCH_ZONE_LAUNCHES
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -181,6 +189,7 @@ SYMBOLS = [
     "mgf_batch_read_body_contacts_dev", "mgf_batch_copy_worlds_where", "mgf_batch_raycast_many_dev", "mgf_batch_sweep_many_dev",
     "mgf_batch_set_sensors", "mgf_batch_sensor_count", "mgf_batch_cast_sensors", "mgf_batch_cast_sensors_dev",
     "mgf_batch_set_cameras", "mgf_batch_camera_count", "mgf_batch_camera_pixels", "mgf_batch_cast_cameras", "mgf_batch_cast_cameras_dev",
+    "mgf_batch_set_zones", "mgf_batch_zone_count", "mgf_batch_read_zones", "mgf_batch_read_zones_dev", "mgf_batch_overlap_first_dev",
 ]
 
 _lib = None
@@ -354,6 +363,11 @@ def load_library():
         "mgf_batch_sensor_count": (i64, [vp]),
         "mgf_batch_cast_sensors": (i32, [vp, i32, vp, vp, i64]),
         "mgf_batch_cast_sensors_dev": (i32, [vp, i32, vp, vp, i64]),
+        "mgf_batch_set_zones": (i32, [vp, vp, i64]),
+        "mgf_batch_zone_count": (i64, [vp]),
+        "mgf_batch_read_zones": (i32, [vp, i32, vp, vp, i64]),
+        "mgf_batch_read_zones_dev": (i32, [vp, i32, vp, vp, i64]),
+        "mgf_batch_overlap_first_dev": (i32, [vp, vp, i64, vp, i32, vp]),
         "mgf_batch_set_cameras": (i32, [vp, vp, i64]),
         "mgf_batch_camera_count": (i64, [vp]),
         "mgf_batch_camera_pixels": (i64, [vp]),
@@ -1754,6 +1768,76 @@ class WorldBatch:
         n = max(self.camera_pixels(), 0)
         dp, op, pp = _dev_arg(depth, "float32", 1, n, "depth"), _dev_arg(hits, "int32", 7, n, "hits"), _dev_arg(parts, "float32", 7, n, "parts")
         _check(load_library().mgf_batch_cast_cameras_dev(self._h, int(kinds), dp, op, pp, n))
+
+    # ---- box zones: a rig set once, the count and the first k bodies of every box from the resident poses --------------------------------
+    def set_zones(self, world, body=None, p=(0.0, 0.0, 0.0), r=(0.0, 0.0, 0.0), ignore_self=None):
+        """the batch's zone rig replaced (mgf_batch_set_zones): zone i is the axis-aligned box of half extents r[i] whose centre is
+        p[i] in the frame of body[i] of world[i] - body None or -1: p[i] in the world; ignore_self[i]: its own body is not listed
+        (None: wherever there is a body).  Arrays, or scalars / single rows for all: the number of zones is that of the longest
+        argument.  No zones (empty arrays) clears the rig.  Also takes a ZONE_DTYPE array as `world` with every other argument left."""
+        if isinstance(world, np.ndarray) and world.dtype == ZONE_DTYPE:
+            rig = np.ascontiguousarray(world.reshape(-1))
+        else:
+            body = -1 if body is None else body
+            p, r = np.asarray(p, np.float32), np.asarray(r, np.float32)
+            sizes = [np.size(world), np.size(body), p.size // 3, r.size // 3] + ([] if ignore_self is None else [np.size(ignore_self)])
+            n = 0 if min(sizes) == 0 else max(sizes)
+            rig = np.zeros(n, ZONE_DTYPE)
+            rig["world"] = np.broadcast_to(np.asarray(world, np.int32).reshape(-1), (n,))
+            rig["body"] = np.broadcast_to(np.asarray(body, np.int32).reshape(-1), (n,))
+            rig["p"] = np.broadcast_to(p.reshape(-1, 3), (n, 3))
+            rig["r"] = np.broadcast_to(r.reshape(-1, 3), (n, 3))
+            ign = rig["body"] >= 0 if ignore_self is None else np.broadcast_to(np.asarray(ignore_self, bool).reshape(-1), (n,))
+            rig["flags"] = np.where(ign, SENSOR_IGNORE_SELF, 0)
+        _check(load_library().mgf_batch_set_zones(self._h, rig.ctypes.data if len(rig) else None, len(rig)))
+
+    def zone_count(self):
+        return load_library().mgf_batch_zone_count(self._h)
+
+    def read_zones(self, k, boxes=False):
+        """every zone of the rig from its body's current pose (mgf_batch_read_zones): (count[n], bodies[n, k]) int32 in the rig's
+        order - count the bodies of the zone's world whose tight box overlaps the zone's, bodies the first k of them in ascending
+        index, then -1; boxes=True: (count, bodies, boxes[n, 6]) - the boxes (c.xyz, r.xyz) as formed"""
+        n, k = max(self.zone_count(), 0), int(k)
+        out = np.zeros((n, 1 + max(k, 0)), np.int32)
+        bx = np.zeros((n, 6), np.float32) if boxes else None
+        _check(load_library().mgf_batch_read_zones(self._h, k, out.ctypes.data, _ptr(bx), n))
+        return (out[:, 0], out[:, 1:]) + ((bx,) if boxes else ())
+
+    def read_zones_dev(self, out, boxes=None, k=None):
+        """read_zones into device memory (mgf_batch_read_zones_dev), enqueued on the context's stream and not waited for.
+        out: CUDA int32 [n, 1 + k], n = zone_count() - column 0 the count, columns 1: the first k bodies, -1 behind them; k is
+        out.shape[1] - 1 (a raw address: give k).  boxes: CUDA float32 [n, 6] or None - a row (c.xyz, r.xyz), the zone's box."""
+        if out is None:
+            raise ValueError("out is required")
+        if k is None:
+            if not hasattr(out, "data_ptr") or out.dim() != 2 or out.shape[1] < 1:
+                raise ValueError("out: a tensor of n rows of 1 + k, or k given with a raw address")
+            k = int(out.shape[1]) - 1
+        n, k = max(self.zone_count(), 0), int(k)
+        op, bp = _dev_arg(out, "int32", 1 + k, n, "out"), _dev_arg(boxes, "float32", 6, n, "boxes")
+        _check(load_library().mgf_batch_read_zones_dev(self._h, k, op, bp, n))
+
+    def overlap_first_dev(self, boxes, out, ignore=None, n=None, k=None):
+        """the records of read_zones for boxes the caller computed on the device (mgf_batch_overlap_first_dev), not waited for.
+        boxes: CUDA float32 [n, 6], a row (c.xyz, r.xyz); the fixed layout: n a multiple of n_worlds, box i against world
+        i // (n // n_worlds).  out: CUDA int32 [n, 1 + k].  ignore: CUDA int32 [n] or None - a body of the box's world left out of its
+        list.  Raw addresses: give n and k."""
+        if boxes is None or out is None:
+            raise ValueError("boxes and out are both required")
+        if n is None:
+            if not hasattr(boxes, "data_ptr") or boxes.dim() != 2:
+                raise ValueError("n must be given with a raw address")
+            n = int(boxes.shape[0])
+        if k is None:
+            if not hasattr(out, "data_ptr") or out.dim() != 2 or out.shape[1] < 1:
+                raise ValueError("out: a tensor of n rows of 1 + k, or k given with a raw address")
+            k = int(out.shape[1]) - 1
+        n, k = int(n), int(k)
+        if n % self.n_worlds:
+            raise ValueError("n is a multiple of the number of worlds")
+        bp, ip, op = _dev_arg(boxes, "float32", 6, n, "boxes"), _dev_arg(ignore, "int32", 1, n, "ignore"), _dev_arg(out, "int32", 1 + k, n, "out")
+        _check(load_library().mgf_batch_overlap_first_dev(self._h, bp, n, ip, k, op))
 
     def counter(self, name):
         v = C.c_int64()

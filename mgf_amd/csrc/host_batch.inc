@@ -96,6 +96,14 @@ struct mgf_batch {
   size_t c_o_rig = 0;
   DBuf<float> c_parts, c_depth;         // what a cast has nowhere else to put: 7 words a pixel, one word a pixel
   DBuf<int32_t> c_world;                // [pixels] a pixel's world, written by the tile pass for the obstacle pass
+  // the box zones (host_batch_zone.inc): the rig in the caller's order and its plan, built when it is set
+  std::vector<mgf_batch_zone> z_rig;
+  std::vector<uint4> z_items;           // BatchQueryPlan's work items: (world, first, count <= 256, -)
+  std::vector<uint32_t> z_order;        // ... and its order: sorted position -> the caller's index
+  bool z_stale = false;                 // the device copy is behind the rig or the batch's layout (mgf_batch_add_bodies)
+  DBuf<float4> z_dev;                   // items | records | order, the sections at z_o_*
+  size_t z_o_rig = 0, z_o_order = 0;
+  DBuf<int32_t> z_out;                  // what the host-memory read downloads: 1 + k words a zone, then - where asked for - six a zone
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {
@@ -575,6 +583,7 @@ extern "C" mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mg
   b->ccount_stale = false;
   b->s_stale = true;  // (the sensors name (world, body): they are checked against the new lengths when the rig goes up again)
   b->c_stale = true;  // (and so do the cameras)
+  b->z_stale = true;  // (and the zones)
   return MGF_OK;
 }
 

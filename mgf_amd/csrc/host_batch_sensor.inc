@@ -11,10 +11,12 @@
 // The order of mgf_batch_cast_sensors_dev is host_batch_query_dev.inc's: the refusals that need no device, the handle's own, EVERY
 // device pointer looked up (dev_span), the overlap of the two outputs - and only then the first thing is enqueued.
 
-// what a record of a rig - a sensor's, a camera's - names: a world of the batch, a body of that world, no flag but the one defined
-static mgf_status batch_rig_ref_check(const mgf_batch* b, int32_t world, int32_t body, int32_t flags, const char* what) {
+// what a record of a rig - a sensor's, a camera's, a zone's - names: a world of the batch, a body of that world (or_world: or -1, the
+// world itself - a zone's), no flag but the one defined
+static mgf_status batch_rig_ref_check(const mgf_batch* b, int32_t world, int32_t body, int32_t flags, const char* what, bool or_world = false) {
   if (world < 0 || (uint32_t)world >= b->K) return fail(MGF_ERR_INVALID, "world index out of range: the rig was not changed");
-  if (body < 0 || (uint32_t)body >= b->h_n[(size_t)world]) return fail(MGF_ERR_INVALID, "body index out of range: the rig was not changed");
+  if (!(or_world && body == -1) && (body < 0 || (uint32_t)body >= b->h_n[(size_t)world]))
+    return fail(MGF_ERR_INVALID, "body index out of range: the rig was not changed");
   if (flags & ~MGF_SENSOR_IGNORE_SELF) {
     set_error("a %s's flags hold a bit beyond MGF_SENSOR_IGNORE_SELF: the rig was not changed", what);
     return MGF_ERR_INVALID;

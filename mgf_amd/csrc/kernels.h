@@ -113,6 +113,11 @@
 //                      tile of 16 x 16 pixels, a lane per pixel; the tile bounds its rays by a cone and a length, drops every body whose
 //                      padded sphere lies outside both, compacts the survivors into LDS, and every pixel runs k_batch_query_ray's loop over
 //                      them alone; _depth writes the depth image behind the obstacle pass
+//   k_batch_zone_first<SRC> (k_batch_zone.h)
+//                      box zones fixed in the frame of a body or of the world (mgf_batch_set_zones / _read_zones / _read_zones_dev), and
+//                      the caller's own boxes from device memory (mgf_batch_overlap_first_dev): per box the count and the first k bodies,
+//                      a record of fixed width - k_batch_observe_overlap's tight boxes in LDS and ballot ranks, count and fill in one pass,
+//                      no total, no host wait
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -135,3 +140,4 @@
 #include "k_batch_query_dev.h"  // ray casts and sweeps from and into the caller's device memory (k_batch_query_plan_*, k_batch_query_*_dev)
 #include "k_batch_sensor.h"  // ray sensors fixed in the frame of a body, cast from the resident poses (k_batch_sensor_ray)
 #include "k_batch_camera.h"  // depth cameras fixed in the frame of a body, a workgroup per image tile (k_batch_camera_*)
+#include "k_batch_zone.h"  // box zones: the count and the first k bodies of every box, a fixed-width record (k_batch_zone_first)
