@@ -953,6 +953,27 @@ def _dev_arg(a, dtype, cols, n, name):
     return int(a.data_ptr())
 
 
+def _rig_rows(dtype, **fields):
+    """a rig of `dtype` from its fields - arrays, or scalars / single rows for all: as many records as the longest argument has, none
+    where an argument is empty; a field that is not given stays zero; ValueError where an argument is neither one nor n"""
+    cols = {k: int(np.prod(dtype[k].shape, dtype=np.int64)) for k in fields}
+    vals = {k: np.asarray(v, dtype[k].base) for k, v in fields.items()}
+    n = 0 if min(v.size for v in vals.values()) == 0 else max(v.size // cols[k] for k, v in vals.items())
+    rig = np.zeros(n, dtype)
+    for k, v in vals.items():
+        rig[k] = np.broadcast_to(v.reshape((-1,) + dtype[k].shape), (n,) + dtype[k].shape)
+    return rig
+
+
+def _record_k(out, k):
+    """the k of records of 1 + k words: out.shape[1] - 1 of a tensor, or as given with a raw address"""
+    if k is None:
+        if not hasattr(out, "data_ptr") or out.dim() != 2 or out.shape[1] < 1:
+            raise ValueError("out: a tensor of n rows of 1 + k, or k given with a raw address")
+        k = int(out.shape[1]) - 1
+    return int(k)
+
+
 def _particle_rows(p, d, dt):
     """mgf_particle rows (p.xyz, d.xyz, dt) from rows of p; d and dt are rows, or one for all"""
     p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
@@ -1679,17 +1700,7 @@ class WorldBatch:
         if isinstance(world, np.ndarray) and world.dtype == SENSOR_DTYPE:
             rig = np.ascontiguousarray(world.reshape(-1))
         else:
-            p, d = np.asarray(p, np.float32), np.asarray(d, np.float32)
-            n = max(np.size(world), np.size(body), p.size // 3, d.size // 3, np.size(dt), np.size(ignore_self))
-            if min(np.size(world), np.size(body), p.size, d.size, np.size(dt), np.size(ignore_self)) == 0:
-                n = 0
-            rig = np.zeros(n, SENSOR_DTYPE)
-            rig["world"] = np.broadcast_to(np.asarray(world, np.int32).reshape(-1), (n,))
-            rig["body"] = np.broadcast_to(np.asarray(body, np.int32).reshape(-1), (n,))
-            rig["p"] = np.broadcast_to(p.reshape(-1, 3), (n, 3))
-            rig["d"] = np.broadcast_to(d.reshape(-1, 3), (n, 3))
-            rig["dt"] = np.broadcast_to(np.asarray(dt, np.float32).reshape(-1), (n,))
-            rig["flags"] = np.where(np.broadcast_to(np.asarray(ignore_self, bool).reshape(-1), (n,)), SENSOR_IGNORE_SELF, 0)
+            rig = _rig_rows(SENSOR_DTYPE, world=world, body=body, p=p, d=d, dt=dt, flags=np.where(np.asarray(ignore_self, bool), SENSOR_IGNORE_SELF, 0))
         _check(load_library().mgf_batch_set_sensors(self._h, rig.ctypes.data if len(rig) else None, len(rig)))
 
     def sensor_count(self):
@@ -1779,16 +1790,10 @@ class WorldBatch:
             rig = np.ascontiguousarray(world.reshape(-1))
         else:
             body = -1 if body is None else body
-            p, r = np.asarray(p, np.float32), np.asarray(r, np.float32)
-            sizes = [np.size(world), np.size(body), p.size // 3, r.size // 3] + ([] if ignore_self is None else [np.size(ignore_self)])
-            n = 0 if min(sizes) == 0 else max(sizes)
-            rig = np.zeros(n, ZONE_DTYPE)
-            rig["world"] = np.broadcast_to(np.asarray(world, np.int32).reshape(-1), (n,))
-            rig["body"] = np.broadcast_to(np.asarray(body, np.int32).reshape(-1), (n,))
-            rig["p"] = np.broadcast_to(p.reshape(-1, 3), (n, 3))
-            rig["r"] = np.broadcast_to(r.reshape(-1, 3), (n, 3))
-            ign = rig["body"] >= 0 if ignore_self is None else np.broadcast_to(np.asarray(ignore_self, bool).reshape(-1), (n,))
-            rig["flags"] = np.where(ign, SENSOR_IGNORE_SELF, 0)
+            flags = {} if ignore_self is None else dict(flags=np.where(np.asarray(ignore_self, bool), SENSOR_IGNORE_SELF, 0))
+            rig = _rig_rows(ZONE_DTYPE, world=world, body=body, p=p, r=r, **flags)
+            if ignore_self is None:
+                rig["flags"] = np.where(rig["body"] >= 0, SENSOR_IGNORE_SELF, 0)
         _check(load_library().mgf_batch_set_zones(self._h, rig.ctypes.data if len(rig) else None, len(rig)))
 
     def zone_count(self):
@@ -1810,11 +1815,8 @@ class WorldBatch:
         out.shape[1] - 1 (a raw address: give k).  boxes: CUDA float32 [n, 6] or None - a row (c.xyz, r.xyz), the zone's box."""
         if out is None:
             raise ValueError("out is required")
-        if k is None:
-            if not hasattr(out, "data_ptr") or out.dim() != 2 or out.shape[1] < 1:
-                raise ValueError("out: a tensor of n rows of 1 + k, or k given with a raw address")
-            k = int(out.shape[1]) - 1
-        n, k = max(self.zone_count(), 0), int(k)
+        k = _record_k(out, k)
+        n = max(self.zone_count(), 0)
         op, bp = _dev_arg(out, "int32", 1 + k, n, "out"), _dev_arg(boxes, "float32", 6, n, "boxes")
         _check(load_library().mgf_batch_read_zones_dev(self._h, k, op, bp, n))
 
@@ -1829,11 +1831,8 @@ class WorldBatch:
             if not hasattr(boxes, "data_ptr") or boxes.dim() != 2:
                 raise ValueError("n must be given with a raw address")
             n = int(boxes.shape[0])
-        if k is None:
-            if not hasattr(out, "data_ptr") or out.dim() != 2 or out.shape[1] < 1:
-                raise ValueError("out: a tensor of n rows of 1 + k, or k given with a raw address")
-            k = int(out.shape[1]) - 1
-        n, k = int(n), int(k)
+        k = _record_k(out, k)
+        n = int(n)
         if n % self.n_worlds:
             raise ValueError("n is a multiple of the number of worlds")
         bp, ip, op = _dev_arg(boxes, "float32", 6, n, "boxes"), _dev_arg(ignore, "int32", 1, n, "ignore"), _dev_arg(out, "int32", 1 + k, n, "out")

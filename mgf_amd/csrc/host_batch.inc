@@ -12,6 +12,18 @@
 // one store each - and per world a list of (entry, disp, rot); the kernels read a descriptor per list entry (BatchObstacles, k_batch.h).
 // Both tables and all lists live beside the mirror: adding bodies behind a tick, or none yet, leaves them as they are.
 
+// A rig of a batch - sensors, cameras, zones: the records in the caller's order, what is built from them when the rig is set, and the
+// device copy of both (host_batch_rig.inc)
+template <class Rec>
+struct BatchRig {
+  std::vector<Rec> recs;
+  std::vector<uint4> items;     // BatchQueryPlan's work items: (world, first, count <= 256, -); the cameras': their tiles
+  std::vector<uint32_t> order;  // ... and its order: sorted position -> the caller's index (the cameras have none)
+  bool stale = false;           // the device copy is behind the rig or the batch's layout (mgf_batch_add_bodies)
+  DBuf<float4> dev;             // the sections batch_rig_up lists, one behind the other ...
+  size_t off[4] = {0, 0, 0, 0}; // ... section k at off[k]: items, records, order, worlds
+};
+
 struct mgf_batch {
   mgf_ctx* ctx = nullptr;
   mgf_params params;
@@ -79,31 +91,16 @@ struct mgf_batch {
   DBuf<int32_t> p_world;                // [n] the call's own copy of the worlds, -1: a skipped record
   DBuf<uint32_t> p_rank, p_order;       // [n] a query's rank within its world; sorted position -> the caller's index
   DBuf<uint4> p_items;                  // the work items
-  // the body-mounted sensors (host_batch_sensor.inc): the rig in the caller's order and its plan, built when it is set
-  std::vector<mgf_batch_sensor> s_rig;
-  std::vector<uint4> s_items;           // BatchQueryPlan's work items: (world, first, count <= 256, -)
-  std::vector<uint32_t> s_order;        // ... and its order: sorted position -> the caller's index
-  bool s_stale = false;                 // the device copy is behind the rig or the batch's layout (mgf_batch_add_bodies)
-  DBuf<float4> s_dev;                   // items | records | order | worlds, the sections at s_o_*
-  size_t s_o_rig = 0, s_o_order = 0, s_o_world = 0;
-  DBuf<float> s_parts;                  // the particles of a cast that has nowhere else to put them: 7 words a sensor
-  // the body-mounted depth cameras (host_batch_camera.inc): the rig in the caller's order and its tile table, built when it is set
-  std::vector<mgf_batch_camera> c_rig;
-  std::vector<uint4> c_tiles;           // (camera, the camera's first pixel, x0 | y0 << 16, -): a tile of kCamTileW x kCamTileH pixels
-  size_t c_pixels = 0;                  // the pixels of the rig, camera by camera
-  bool c_stale = false;                 // the device copy is behind the rig or the batch's layout (mgf_batch_add_bodies)
-  DBuf<float4> c_dev;                   // tiles | records, the records at c_o_rig
-  size_t c_o_rig = 0;
-  DBuf<float> c_parts, c_depth;         // what a cast has nowhere else to put: 7 words a pixel, one word a pixel
+  // the rigs (host_batch_rig.inc): body-mounted ray sensors, depth cameras and box zones (host_batch_sensor.inc, _camera.inc, _zone.inc)
+  BatchRig<mgf_batch_sensor> sensors;   // on the device: items | records | order | worlds
+  BatchRig<mgf_batch_camera> cameras;   // on the device: tiles | records - (camera, the camera's first pixel, x0 | y0 << 16, -): a tile of kCamTileW x kCamTileH pixels
+  BatchRig<mgf_batch_zone> zones;       // on the device: items | records | order
+  // ... and what a call on one of them has nowhere else to put
+  DBuf<float> s_parts;                  // the particles of a sensor cast: 7 words a sensor
+  size_t c_pixels = 0;                  // the pixels of the camera rig, camera by camera
+  DBuf<float> c_parts, c_depth;         // of a camera cast: 7 words a pixel, one word a pixel
   DBuf<int32_t> c_world;                // [pixels] a pixel's world, written by the tile pass for the obstacle pass
-  // the box zones (host_batch_zone.inc): the rig in the caller's order and its plan, built when it is set
-  std::vector<mgf_batch_zone> z_rig;
-  std::vector<uint4> z_items;           // BatchQueryPlan's work items: (world, first, count <= 256, -)
-  std::vector<uint32_t> z_order;        // ... and its order: sorted position -> the caller's index
-  bool z_stale = false;                 // the device copy is behind the rig or the batch's layout (mgf_batch_add_bodies)
-  DBuf<float4> z_dev;                   // items | records | order, the sections at z_o_*
-  size_t z_o_rig = 0, z_o_order = 0;
-  DBuf<int32_t> z_out;                  // what the host-memory read downloads: 1 + k words a zone, then - where asked for - six a zone
+  DBuf<int32_t> z_out;                  // what the host-memory read of the zones downloads: 1 + k words a zone, then - where asked for - six a zone
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {
@@ -516,6 +513,13 @@ extern "C" int64_t mgf_batch_world_obstacle_count(const mgf_batch* b, int64_t wo
 }
 
 // RigidBodyVec::add_body physics.rs:200-218 + World::add_body world.rs:178-184 (initial fat AABB), as mgf_world_add_bodies, for one world of the batch.
+// The rigs name (world, body): behind a change of the batch's layout they are checked against the new lengths when they go up again
+static void batch_rigs_stale(mgf_batch* b) {
+  b->sensors.stale = true;
+  b->cameras.stale = true;
+  b->zones.stale = true;
+}
+
 extern "C" mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mgf_component* comps, int64_t n, const float* mass, const float* restitution,
                                            const float* friction, const mgf_vec3* world_force, uint64_t* first_id) {
   if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
@@ -581,9 +585,7 @@ extern "C" mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mg
   batch_offsets(b);
   std::fill(b->h_ccount.begin(), b->h_ccount.end(), 0u);
   b->ccount_stale = false;
-  b->s_stale = true;  // (the sensors name (world, body): they are checked against the new lengths when the rig goes up again)
-  b->c_stale = true;  // (and so do the cameras)
-  b->z_stale = true;  // (and the zones)
+  batch_rigs_stale(b);
   return MGF_OK;
 }
 

@@ -7,7 +7,9 @@
 // rig or of the batch's layout (mgf_batch_add_bodies: the rig names (world, body), as the sensors' does).  No record per pixel exists on
 // the host, and none on the device but what a cast is asked to write.  A cast is then one launch - and the obstacle pass with the depth
 // pass behind it, and the collider gather behind a step - with no plan and, for the device form, no host wait and no copy between host
-// and device.  The camera rig and the sensor rig share nothing but the handle: s_* is the sensors', c_* the cameras'.
+// and device.  What the rig shares with the sensors' and the zones' is host_batch_rig.inc's: the prologue and the world / body / flags
+// check of the set call, the upload (batch_rig_up) and the pieces of what a cast refuses before it looks at a device; its work items are
+// its tiles, built here, and it has no order.
 // The order of mgf_batch_cast_cameras_dev is host_batch_sensor.inc's: the refusals that need no device, the handle's own, EVERY device
 // pointer looked up (dev_span), the overlap of the outputs pair by pair - depth with hits, depth with particles, hits with particles -
 // and only then the first thing is enqueued.
@@ -15,8 +17,7 @@
 static bool camera_finite3(const mgf_vec3& v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); }
 
 extern "C" mgf_status mgf_batch_set_cameras(mgf_batch* b, const mgf_batch_camera* cams, int64_t n_in) {
-  MGF_TRY(batch_dev_args(b, n_in));
-  if (n_in && !cams) return fail(MGF_ERR_INVALID, "NULL argument");
+  MGF_TRY(batch_rig_set_args(b, cams, n_in));
   static_assert(sizeof(mgf_batch_camera) == sizeof(CameraIn) && sizeof(mgf_batch_camera) == 64, "the rig goes up as the caller's records");
   const size_t n = (size_t)n_in;
   uint64_t pixels = 0, n_tiles = 0;
@@ -43,36 +44,26 @@ extern "C" mgf_status mgf_batch_set_cameras(mgf_batch* b, const mgf_batch_camera
       for (uint32_t x0 = 0; x0 < (uint32_t)cams[i].width; x0 += kCamTileW) tiles.push_back(make_uint4((uint32_t)i, first, x0 | (y0 << 16), 0u));
     first += (uint32_t)cams[i].width * (uint32_t)cams[i].height;
   }
-  b->c_rig.assign(cams, cams + n);
-  b->c_tiles.swap(tiles);
+  b->cameras.recs.assign(cams, cams + n);
+  b->cameras.items.swap(tiles);
   b->c_pixels = (size_t)pixels;
-  b->c_stale = true;
+  b->cameras.stale = true;
   return MGF_OK;
 }
 
-extern "C" int64_t mgf_batch_camera_count(const mgf_batch* b) { return b ? (int64_t)b->c_rig.size() : -1; }
+extern "C" int64_t mgf_batch_camera_count(const mgf_batch* b) { return b ? (int64_t)b->cameras.recs.size() : -1; }
 extern "C" int64_t mgf_batch_camera_pixels(const mgf_batch* b) { return b ? (int64_t)b->c_pixels : -1; }
 
-// the rig onto the device (n > 0): tiles | records
-static mgf_status batch_cameras_up(mgf_batch* b) {
-  if (!b->c_stale) return MGF_OK;
-  for (const mgf_batch_camera& r : b->c_rig)
-    if ((uint32_t)r.body >= b->h_n[(size_t)r.world]) return fail(MGF_ERR_INVALID, "internal error: a camera names a body its world does not hold");
-  const RigSection sec[2] = {{b->c_tiles.data(), 16 * b->c_tiles.size()}, {b->c_rig.data(), 64 * b->c_rig.size()}};
-  size_t off[2];
-  MGF_TRY(batch_rig_upload(b, b->c_dev, sec, 2, off));
-  b->c_o_rig = off[1];
-  b->c_stale = false;
-  return MGF_OK;
-}
+static uint32_t batch_camera_lds(const mgf_batch* b) { return 36u * batch_nmax(b) + 16u; }
 
 // The launches of a cast, behind every check (pixels > 0): device memory of one record a pixel each, the caller's or the handle's; each
 // may be null, but not depth_dev and out_dev both.
 static mgf_status batch_camera_run(mgf_batch* b, int32_t kinds_mask, float* depth_dev, int32_t* out_dev, float* parts_dev) {
+  BatchRig<mgf_batch_camera>& R = b->cameras;
   const size_t n = b->c_pixels;
   MGF_TRY(batch_push(b));
   MGF_TRY(batch_env_sync(b));
-  MGF_TRY(batch_cameras_up(b));
+  MGF_TRY(batch_rig_up(b, R, "camera", 2));  // tiles | records
   MGF_TRY(batch_cols_refresh(b, &b->q_launches));
   hipStream_t s = b->ctx->stream;
   const bool obstacles = batch_has_obstacles(b, kinds_mask);
@@ -81,20 +72,19 @@ static mgf_status batch_camera_run(mgf_batch* b, int32_t kinds_mask, float* dept
     if (!out_dev) { MGF_TRY(b->q_out.ensure(7 * n, s)); out_dev = b->q_out.p; }
     MGF_TRY(b->c_world.ensure(n, s));
   }
-  const uint32_t lds = 36u * batch_nmax(b) + 16u;
   BatchCameraArgs A;
   memset(&A, 0, sizeof(A));
   A.col0 = b->dm[mgf_batch::ACOL0].p; A.col1 = b->dm[mgf_batch::ACOL1].p; A.w_off = b->d_off.p;
   A.T = batch_terrains(b);
   A.x = b->dm[mgf_batch::AX].p; A.q = b->dm[mgf_batch::AQ].p;
-  A.tiles = reinterpret_cast<const uint4*>(b->c_dev.p);
-  A.cams = reinterpret_cast<const CameraIn*>(b->c_dev.p + b->c_o_rig);
+  A.tiles = reinterpret_cast<const uint4*>(R.dev.p);
+  A.cams = reinterpret_cast<const CameraIn*>(R.dev.p + R.off[1]);
   A.mask = kinds_mask;
   A.depth = obstacles ? nullptr : depth_dev;
   A.out = out_dev;
   A.parts = parts_dev;
   A.world = obstacles ? b->c_world.p : nullptr;
-  k_batch_camera_tile<<<(unsigned)b->c_tiles.size(), kBatchBlock, lds, s>>>(A);
+  k_batch_camera_tile<<<(unsigned)R.items.size(), kBatchBlock, batch_camera_lds(b), s>>>(A);
   LAUNCH_CHECK();
   b->q_launches += MGF_BATCH_CAMERA_LAUNCHES;
   if (obstacles) {
@@ -110,13 +100,11 @@ static mgf_status batch_camera_run(mgf_batch* b, int32_t kinds_mask, float* dept
 
 // the refusals of both cast calls that need no device; *n: the pixels of the rig
 static mgf_status batch_camera_args(const mgf_batch* b, int32_t kinds_mask, const void* depth, const void* hits, int64_t cap, size_t* n) {
-  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
-  if (cap < 0) return fail(MGF_ERR_INVALID, "cap is negative");
+  MGF_TRY(batch_rig_handle(b));
+  MGF_TRY(batch_rig_cap(cap));
   MGF_TRY(query_mask_check(kinds_mask));
   *n = b->c_pixels;
-  if ((int64_t)*n > cap) return fail(MGF_ERR_CAPACITY, "buffer too small");
-  if (*n && !depth && !hits) return fail(MGF_ERR_INVALID, "NULL argument: depth and hits are both NULL");
-  return MGF_OK;
+  return batch_rig_fits(*n, cap, depth || hits, "NULL argument: depth and hits are both NULL");
 }
 
 extern "C" mgf_status mgf_batch_cast_cameras(mgf_batch* b, int32_t kinds_mask, float* depth, mgf_ray_hit* hits, mgf_particle* parts_out, int64_t cap) {

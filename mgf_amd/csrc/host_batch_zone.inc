@@ -5,17 +5,15 @@
 //
 // mgf_batch_overlap_aabb_many answers in CSR form: its caller must know the total before it can size the lists, and that costs a host
 // wait.  A record of 1 + k words per box needs no total, so count and fill are one pass and nothing waits.
-// A rig is static, as the sensors' (host_batch_sensor.inc): the checks, the sort by world and the work items (BatchQueryPlan) are made
-// once, when it is set; it goes up - items | records | order, ONE copy (batch_rig_upload) - before the first read behind a change of the
-// rig or of the batch's layout (mgf_batch_add_bodies).  A read is then MGF_BATCH_ZONE_LAUNCHES = 1 launch - and the collider gather behind
-// a step - with no plan, no index array and, for the device form, no host wait and no copy between host and device.  The zone rig shares
-// nothing but the handle with the sensor and camera rigs: z_* is its own.
+// What the rig shares with the sensors' and the cameras' is host_batch_rig.inc's: the prologue and the world / body / flags check of the
+// set call, the sort by world and the work items (batch_rig_plan), the upload - items | records | order, ONE copy (batch_rig_up) - and
+// the pieces of what a read refuses before it looks at a device.  A read is then MGF_BATCH_ZONE_LAUNCHES = 1 launch - and the collider
+// gather behind a step - with no plan, no index array and, for the device form, no host wait and no copy between host and device.
 // The order of both device-pointer calls is host_batch_query_dev.inc's: the refusals that need no device, the handle's own, EVERY device
 // pointer looked up (dev_span), the overlap of what is written with everything else - and only then the first thing is enqueued.
 
 extern "C" mgf_status mgf_batch_set_zones(mgf_batch* b, const mgf_batch_zone* z, int64_t n_in) {
-  MGF_TRY(batch_dev_args(b, n_in));
-  if (n_in && !z) return fail(MGF_ERR_INVALID, "NULL argument");
+  MGF_TRY(batch_rig_set_args(b, z, n_in));
   static_assert(sizeof(mgf_batch_zone) == sizeof(ZoneIn) && sizeof(mgf_batch_zone) == 40, "the rig goes up as the caller's records");
   const size_t n = (size_t)n_in;
   for (size_t i = 0; i < n; ++i) {
@@ -24,33 +22,11 @@ extern "C" mgf_status mgf_batch_set_zones(mgf_batch* b, const mgf_batch_zone* z,
       return fail(MGF_ERR_INVALID, "a zone fixed in the world (body = -1) has no body of its own to ignore: the rig was not changed");
     if (z[i].reserved != 0) return fail(MGF_ERR_INVALID, "a zone's reserved word is not 0: the rig was not changed");
   }
-  // (no device is needed: a read that was enqueued reads the device copy, which is replaced in stream order when the next read puts the rig up)
-  std::vector<int32_t> world(n);
-  for (size_t i = 0; i < n; ++i) world[i] = z[i].world;
-  const BatchQueryPlan plan(b->K, world.data(), n);
-  b->z_rig.assign(z, z + n);
-  b->z_items.resize(plan.n_items);
-  b->z_order.resize(n);
-  plan.fill(world.data(), n, b->z_items.data(), b->z_order.data());
-  b->z_stale = true;
+  batch_rig_plan(b, b->zones, z, n);
   return MGF_OK;
 }
 
-extern "C" int64_t mgf_batch_zone_count(const mgf_batch* b) { return b ? (int64_t)b->z_rig.size() : -1; }
-
-// the zone rig onto the device (n > 0): items | records | order
-static mgf_status batch_zones_up(mgf_batch* b) {
-  if (!b->z_stale) return MGF_OK;
-  for (const mgf_batch_zone& r : b->z_rig)
-    if (r.body >= 0 && (uint32_t)r.body >= b->h_n[(size_t)r.world]) return fail(MGF_ERR_INVALID, "internal error: a zone names a body its world does not hold");
-  const size_t n = b->z_rig.size();
-  const RigSection sec[3] = {{b->z_items.data(), 16 * b->z_items.size()}, {b->z_rig.data(), 40 * n}, {b->z_order.data(), 4 * n}};
-  size_t off[3];
-  MGF_TRY(batch_rig_upload(b, b->z_dev, sec, 3, off));
-  b->z_o_rig = off[1]; b->z_o_order = off[2];
-  b->z_stale = false;
-  return MGF_OK;
-}
+extern "C" int64_t mgf_batch_zone_count(const mgf_batch* b) { return b ? (int64_t)b->zones.recs.size() : -1; }
 
 // what both launches share: the colliders, the offsets, k and where the records go
 static void batch_zone_args(const mgf_batch* b, int32_t k, int32_t* out_dev, BatchZoneArgs* A) {
@@ -64,19 +40,20 @@ static uint32_t batch_zone_lds(const mgf_batch* b) { return 32u * batch_nmax(b);
 // The launch of a read, behind every check (n > 0): out_dev and boxes_dev are device memory of n records each, the caller's or the
 // handle's; boxes_dev may be null.
 static mgf_status batch_zone_run(mgf_batch* b, int32_t k, int32_t* out_dev, float* boxes_dev) {
+  BatchRig<mgf_batch_zone>& R = b->zones;
   MGF_TRY(batch_push(b));
-  MGF_TRY(batch_zones_up(b));
+  MGF_TRY(batch_rig_up(b, R, "zone", 3, true));
   MGF_TRY(batch_cols_refresh(b, &b->q_launches));
   BatchZoneArgs A;
   batch_zone_args(b, k, out_dev, &A);
-  A.items = reinterpret_cast<const uint4*>(b->z_dev.p);
-  A.order = reinterpret_cast<const uint32_t*>(b->z_dev.p + b->z_o_order);
+  A.items = reinterpret_cast<const uint4*>(R.dev.p);
+  A.order = reinterpret_cast<const uint32_t*>(R.dev.p + R.off[2]);
   A.x = b->dm[mgf_batch::AX].p; A.q = b->dm[mgf_batch::AQ].p;
-  A.rig = reinterpret_cast<const ZoneIn*>(b->z_dev.p + b->z_o_rig);
+  A.rig = reinterpret_cast<const ZoneIn*>(R.dev.p + R.off[1]);
   A.boxes_out = boxes_dev;
   BatchItemSrc S;
   memset(&S, 0, sizeof(S));
-  k_batch_zone_first<kItemTable><<<(unsigned)b->z_items.size(), kBatchBlock, batch_zone_lds(b), b->ctx->stream>>>(A, S);
+  k_batch_zone_first<kItemTable><<<(unsigned)R.items.size(), kBatchBlock, batch_zone_lds(b), b->ctx->stream>>>(A, S);
   LAUNCH_CHECK();
   b->q_launches += MGF_BATCH_ZONE_LAUNCHES;
   return MGF_OK;
@@ -89,13 +66,11 @@ static mgf_status zone_k_check(int32_t k) {
 
 // the refusals of both read calls that need no device; *n: the zones of the rig
 static mgf_status batch_zone_read_args(const mgf_batch* b, int32_t k, const void* out, int64_t cap, size_t* n) {
-  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  MGF_TRY(batch_rig_handle(b));
   MGF_TRY(zone_k_check(k));
-  if (cap < 0) return fail(MGF_ERR_INVALID, "cap is negative");
-  *n = b->z_rig.size();
-  if ((int64_t)*n > cap) return fail(MGF_ERR_CAPACITY, "buffer too small");
-  if (*n && !out) return fail(MGF_ERR_INVALID, "NULL argument");
-  return MGF_OK;
+  MGF_TRY(batch_rig_cap(cap));
+  *n = b->zones.recs.size();
+  return batch_rig_fits(*n, cap, out != nullptr);
 }
 
 extern "C" mgf_status mgf_batch_read_zones(mgf_batch* b, int32_t k, int32_t* out, mgf_aabb* boxes_out, int64_t cap) {

@@ -10,14 +10,20 @@
 //                             into `rows` in whatever order the lanes come and then sorted per body.  A lane per body walks its chain
 //                             with sequential f32 adds: nothing of the answer depends on lane scheduling, and there is no float atomic.
 //                             Of the tick's state only `rows` is written - every tick rebuilds it.
-//   k_batch_observe_overlap<FILL>
-//                             a workgroup per work item = (world, up to 256 boxes) of the queries' sort by world (BatchQueryPlan; the
-//                             kernel's share of it: BatchWork, k_batch_query.h).
+//   bo_front                  a workgroup's work item of boxes against the bodies of its world, written once for every kernel that does it
+//                             with a workgroup per work item: k_batch_observe_overlap<FILL> and k_batch_zone_first<SRC> (k_batch_zone.h).
 //                             The tight bounds BoundedBy<AABB> (bounds.rs:170-190) of the world's colliders col0 / col1 staged in LDS
 //                             once; a box gets min(64, 256 / (count rounded up to a power of two)) lanes of one wave, which take the
-//                             bodies in chunks of that many, ascending; Overlaps<AABB> (collision.rs:22-29) per lane, and a hit's place
-//                             within its chunk is its rank in the wave's ballot: the list of a box is in ascending body index whatever
-//                             the lane split.  Count (FILL = false), the scan of prims.hip, fill.
+//                             bodies in chunks of that many, ascending; Overlaps<AABB> (collision.rs:22-29) per lane, and a hit's rank
+//                             is the hits of the chunks before plus the hits below its lane in the wave's ballot: the hits of a box
+//                             come in ascending body index whatever the lane split.  What a kernel brings is where a box comes from -
+//                             load(qi, g0) -> BatchBox, run by the live lanes behind the staging - and what a hit stores -
+//                             put(hit, i, rank), run by every lane on every trip, so that a kernel's own condition joins `hit` in
+//                             one branch.  Neither holds a barrier nor leaves the kernel; the front returns the box's count.
+//   k_batch_observe_overlap<FILL>
+//                             a workgroup per work item = (world, up to 256 boxes) of the queries' sort by world (BatchQueryPlan; the
+//                             kernel's share of it: BatchWork, k_batch_query.h), through bo_front: the list of a box is in ascending
+//                             body index.  Count (FILL = false), the scan of prims.hip, fill.
 // No workgroup waits for another.
 #pragma once
 #include "k_batch_query.h"
@@ -98,11 +104,14 @@ struct BatchOverlapArgs : BatchWorkArgs {
   uint32_t* out;          // the bodies of box i at off[i], ascending
 };
 
-// LDS (dynamic): 32 bytes a body.
-template <bool FILL>
-__global__ __launch_bounds__(kBatchBlock) void k_batch_observe_overlap(BatchOverlapArgs A) {
-  extern __shared__ float4 s_dyn[];
-  BatchWork W(A, true);
+// a live box in world coordinates and the body of its world it does not hold (-1: none): what a loader hands bo_front
+struct BatchBox { Box Q; int32_t ign; };
+
+// IGNORE = false: no box of the kernel names a body - `ign` is not looked at.  W comes back split, z as loaded (not live: zeros, -1).
+// Every lane of a wave makes every trip of the loop (n and L are the work item's); there is no exit; a NaN box hits nothing because
+// box_overlaps is false for it.
+template <bool IDENTITY, bool IGNORE, class Load, class Put>
+__device__ __forceinline__ uint32_t bo_front(const BatchWorkArgs& A, BatchWork& W, float4* s_dyn, BatchBox& z, Load&& load, Put&& put) {
   const uint32_t tid = threadIdx.x, g0 = W.g0, n = W.n;
   float4 *s_c = s_dyn, *s_r = s_dyn + n;
   for (uint32_t i = tid; i < n; i += kBatchBlock) {
@@ -110,27 +119,47 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_observe_overlap(BatchOver
     s_c[i] = mk4(tb.c, 0.0f); s_r[i] = mk4(tb.r, 0.0f);
   }
   __syncthreads();
-  W.split(A, min(W.shift(), 6u));  // (a box's lanes in one wave: the ballot)
-  const uint32_t L = W.L, sub = W.sub, qi = W.qi;
+  W.template split<IDENTITY>(A, min(W.shift(), 6u));  // (a box's lanes in one wave: the ballot)
+  const uint32_t L = W.L, sub = W.sub;
   const bool live = W.live;
-  Box Q; Q.c = mk3(0.0f, 0.0f, 0.0f); Q.r = Q.c;
-  if (live) { Q.c = ld3(A.boxes + 6 * (size_t)qi); Q.r = ld3(A.boxes + 6 * (size_t)qi + 3); }
-  const uint32_t base = (FILL && live) ? A.off[qi] : 0u;
+  z.Q.c = mk3(0.0f, 0.0f, 0.0f); z.Q.r = z.Q.c; z.ign = -1;
+  if (live) z = load(W.qi, g0);
+  const Box Q = z.Q;
+  const int32_t ign = z.ign;
   const uint32_t shift = (tid & 63u) - sub;                        // the first lane of the box's group within the wave
   const uint64_t group = L == 64u ? ~0ull : ((1ull << L) - 1ull);  // the group's lanes, from that lane
   uint32_t m = 0;
   for (uint32_t i0 = 0; i0 < n; i0 += L) {  // (n and L are the work item's: every lane of the wave makes every trip)
     const uint32_t i = i0 + sub;
     bool hit = false;
-    if (live && i < n) {
+    if (live && i < n && (!IGNORE || (int32_t)i != ign)) {
       Box b; b.c = xyz(s_c[i]); b.r = xyz(s_r[i]);
       hit = box_overlaps(b, Q);
     }
     const uint64_t g = ((uint64_t)__ballot(hit) >> shift) & group;
-    if (FILL && hit) A.out[base + m + (uint32_t)__popcll(g & ((1ull << sub) - 1ull))] = i;
+    put(hit, i, m + (uint32_t)__popcll(g & ((1ull << sub) - 1ull)));
     m += (uint32_t)__popcll(g);
   }
-  if (!FILL && live && sub == 0u) A.cnt[qi] = m;
+  return m;
+}
+
+// LDS (dynamic): 32 bytes a body.
+template <bool FILL>
+__global__ __launch_bounds__(kBatchBlock) void k_batch_observe_overlap(BatchOverlapArgs A) {
+  extern __shared__ float4 s_dyn[];
+  BatchWork W(A, true);
+  BatchBox z;
+  uint32_t base = 0u;  // FILL: where the box's list begins
+  const uint32_t m = bo_front<false, false>(
+      A, W, s_dyn, z,
+      [&](uint32_t qi, uint32_t) {
+        if (FILL) base = A.off[qi];
+        return BatchBox{{ld3(A.boxes + 6 * (size_t)qi), ld3(A.boxes + 6 * (size_t)qi + 3)}, -1};
+      },
+      [&](bool hit, uint32_t i, uint32_t rank) {
+        if (FILL && hit) A.out[base + rank] = i;
+      });
+  if (!FILL && W.live && W.sub == 0u) A.cnt[W.qi] = m;
 }
 
 }  // namespace mgf

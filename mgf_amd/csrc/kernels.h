@@ -87,7 +87,9 @@
 //   k_batch_observe_contacts / _overlap<FILL> (k_batch_observe.h)
 //                      what else a caller reads of a batch every tick: the constraint list of every world folded per body
 //                      (mgf_batch_read_body_contacts: a workgroup per world, the per-body ranges rebuilt in LDS, a lane per body walks its
-//                      chain) and the bodies in a box (mgf_batch_overlap_aabb_many: the world's tight boxes in LDS, ballot-rank compaction)
+//                      chain) and the bodies in a box (mgf_batch_overlap_aabb_many: the world's tight boxes in LDS, ballot-rank compaction).
+//                      bo_front is that walk written once - the staging, the one barrier, the lane split, the ballot loop and a hit's
+//                      rank - with a loader for the box and a hook for what a hit stores: the overlap kernels' and k_batch_zone_first's
 //   k_batch_drive_get / _set<MODE> / _copy (k_batch_drive.h)
 //                      acting on a batch between ticks: ConstrainedSet::get / set, the force and torque rows and impulses for any mix
 //                      of (world, body) records (mgf_batch_get_many / _set_many / _set_forces / _apply_impulses: a lane per body the call
@@ -116,8 +118,8 @@
 //   k_batch_zone_first<SRC> (k_batch_zone.h)
 //                      box zones fixed in the frame of a body or of the world (mgf_batch_set_zones / _read_zones / _read_zones_dev), and
 //                      the caller's own boxes from device memory (mgf_batch_overlap_first_dev): per box the count and the first k bodies,
-//                      a record of fixed width - k_batch_observe_overlap's tight boxes in LDS and ballot ranks, count and fill in one pass,
-//                      no total, no host wait
+//                      a record of fixed width - through bo_front (k_batch_observe.h), k_batch_observe_overlap's front, with the ignored
+//                      body on: count and fill in one pass, no total, no host wait
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the

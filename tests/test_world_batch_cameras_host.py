@@ -4,13 +4,11 @@ to equals values worked out in float64 wherever every single operation is exact;
 carry the calls; what can be refused before a device is looked at is refused there; mgf_batch_cast_cameras_dev looks all three pointers
 up and checks their overlap before it enqueues anything; the binding turns a wrong tensor down before it calls C; the tile table of a
 rig partitions every camera's pixels exactly once; the new kernels use no scratch, spill nothing and hold no static LDS, and the sensor
-and query kernels keep the figures DESIGN.md records; and the scenes of the GPU tests hold what those tests claim of them, by the
+kernel keeps the figures DESIGN.md records (the query kernels': tests/test_world_batch_rigs_host.py); and the scenes of the GPU tests hold what those tests claim of them, by the
 oracle's ray tests."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,8 +16,9 @@ import pytest
 import mgf_amd
 from mgf_amd import _capi
 from tests import batch_camera_cases as CC
+from tests import batch_rig_cases as RC
 from tests import batch_sensor_cases as SC
-from tests.util import RESOURCES, ROOT, kernel_resources, read
+from tests.util import ROOT, kernel_resources, read
 
 CALLS = ("mgf_batch_set_cameras", "mgf_batch_camera_count", "mgf_batch_camera_pixels", "mgf_batch_cast_cameras", "mgf_batch_cast_cameras_dev")
 
@@ -159,33 +158,33 @@ def test_what_needs_no_device_is_refused_before_the_handle_is_dereferenced():
     # tests/test_gpu_world_batch_cameras.py, where a handle exists)
     src = read("mgf_amd", "csrc", "host_batch_camera.inc")
     body = src[src.index('extern "C" mgf_status mgf_batch_set_cameras('):src.index('extern "C" int64_t mgf_batch_camera_count(')]
-    first_change = body.index("b->c_rig.assign(")
-    for refusal in ("batch_rig_ref_check(b, c.world, c.body, c.flags, \"camera\")", "reserved word is not 0",
+    first_change = body.index("b->cameras.recs.assign(")
+    assert not re.search(r"b->cameras\.|b->c_pixels", body[:first_change])       # (the tiles are its own work items: no shared plan step)
+    for refusal in ("batch_rig_set_args(b, cams, n_in)", "batch_rig_ref_check(b, c.world, c.body, c.flags, \"camera\")", "reserved word is not 0",
                     "outside [1, 4096]", "is not finite", "far is NaN or not above 0", "more than INT32_MAX pixels"):
         assert body.index(refusal) < first_change, refusal
-    # the world, the body and the flags: the sensors' check (host_batch_sensor.inc), which names the rig it is asked about
-    sens = read("mgf_amd", "csrc", "host_batch_sensor.inc")
-    check = sens[sens.index("static mgf_status batch_rig_ref_check("):sens.index('extern "C" mgf_status mgf_batch_set_sensors(')]
+    # the world, the body and the flags: the rigs' one check (host_batch_rig.inc), which names the rig it is asked about
+    check = RC.ref_check_step()
     for refusal in ("world index out of range: the rig was not changed", "body index out of range: the rig was not changed",
                     "a %s's flags hold a bit beyond MGF_SENSOR_IGNORE_SELF: the rig was not changed"):
         assert refusal in check, refusal
     assert not re.search(r"<<<|Async|hipMalloc|\.ensure\(|h2d\(|b->\w+ =[^=]", check)    # it refuses; it changes nothing
     assert not re.search(r"<<<|Async|hipMalloc|\.ensure\(|h2d\(", body)            # no device work at all
-    assert not re.search(r"b->s_\w+", src)                                        # the sensor rig is not touched from here
-    assert "c_rig" not in read("mgf_amd", "csrc", "host_batch_sensor.inc")
+    # the sensor rig and the zone rig are not touched from here, nor this one from the sensors' file
+    assert not re.search(r"b->s_\w+", src) and "b->cameras" in src and "b->sensors" not in src and "b->zones" not in src
+    assert "b->cameras" not in read("mgf_amd", "csrc", "host_batch_sensor.inc")
     args = src[src.index("static mgf_status batch_camera_args("):src.index('extern "C" mgf_status mgf_batch_cast_cameras(')]
-    assert args.index("MGF_ERR_CAPACITY") < args.index("depth and hits are both NULL") < args.index("return MGF_OK;") and "ctx_bind" not in args and "<<<" not in args
+    RC.assert_the_read_and_cast_refusals(args, ["batch_rig_cap(cap)", "query_mask_check(kinds_mask)"], "depth and hits are both NULL")
     host = read("mgf_amd", "csrc", "host_batch.inc")
     add = host[host.index('extern "C" mgf_status mgf_batch_add_bodies('):]
-    assert "b->c_stale = true;" in add[:add.index("\n}\n")]
+    assert "batch_rigs_stale(b);" in add[:add.index("\n}\n")] and "b->cameras.stale = true;" in RC.stale_step()
 
 
 # ---- 4 ------------------------------------------------------------------------------------------------------------------------------------
 def test_all_pointers_are_looked_up_and_compared_before_the_first_enqueue():
     src = read("mgf_amd", "csrc", "host_batch_camera.inc")
-    sens = read("mgf_amd", "csrc", "host_batch_sensor.inc")
     run = src[src.index('extern "C" mgf_status mgf_batch_cast_cameras_dev('):]
-    enqueue = (r"batch_camera_run\(|batch_cameras_up\(|batch_rig_upload\(|batch_ray_obstacles\(|batch_sweep_tail\(|batch_push\(|batch_dev_begin\(|batch_env_sync\(|"
+    enqueue = (r"batch_camera_run\(|batch_rig_up\(|batch_rig_upload\(|batch_ray_obstacles\(|batch_sweep_tail\(|batch_push\(|batch_dev_begin\(|batch_env_sync\(|"
                r"batch_cols_refresh\(|hipMemsetAsync|hipMemcpyAsync|<<<|prim_exclusive_scan_u32|\.ensure\(|h2d\(")
     first_enqueue = min(m.start() for m in re.finditer(enqueue, run))
     checks = [m.start() for m in re.finditer(r"dev_span\(", run)]
@@ -209,10 +208,12 @@ def test_all_pointers_are_looked_up_and_compared_before_the_first_enqueue():
     assert "hipStreamSynchronize" not in helper and "hipMemcpy" not in helper
     obstacles = _the_shared_obstacle_pass()
     assert "hipStreamSynchronize" not in obstacles and "hipMemcpy" not in obstacles
-    up = src[src.index("static mgf_status batch_cameras_up("):src.index("// The launches of a cast")]
-    assert up.index("if (!b->c_stale) return MGF_OK;") < up.index("internal error") < up.index("batch_rig_upload(") and up.count("batch_rig_upload(") == 1
+    assert helper.index("batch_push(") < helper.index('batch_rig_up(b, R, "camera", 2)') < helper.index("k_batch_camera_tile<<<")
+    assert "k_batch_camera_tile<<<(unsigned)R.items.size(), kBatchBlock, batch_camera_lds(b), s>>>(A);" in helper
+    up = RC.up_step()
+    assert up.index("if (!R.stale) return MGF_OK;") < up.index("internal error") < up.index("batch_rig_upload(") and up.count("batch_rig_upload(") == 1
     assert "h2d(" not in up
-    upload = sens[sens.index("static mgf_status batch_rig_upload("):sens.index("// the rig onto the device")]
+    upload = RC.upload_step()
     assert upload.count("h2d(") == 1 and upload.count(".ensure(") == 1 and "<<<" not in upload          # the steady state uploads nothing; one copy
     k = read("mgf_amd", "csrc", "k_batch_camera.h")
     body = k[k.index("void k_batch_camera_tile("):k.index("void k_batch_camera_depth(")]
@@ -318,16 +319,10 @@ def test_the_new_kernels_use_no_scratch_and_the_sensor_and_query_kernels_keep_th
     assert int(rows["k_batch_camera_tile"][0]) <= 64, rows                         # eight waves a SIMD stay possible
     sensor = kernel_resources("k_batch_sensor_")
     assert sensor == {"k_batch_sensor_ray": ("45", "67", "0", "0", "0", "0")}, sensor
-    old = kernel_resources("k_batch_query_")
-    assert set(old) == set(RESOURCES), sorted(old)
-    for name, want in RESOURCES.items():
-        assert old[name] == want, (name, old[name], want)
     design = re.sub(r"\s+", " ", read("DESIGN.md"))
     t, d = rows["k_batch_camera_tile"], rows["k_batch_camera_depth"]
     for text in (f"`k_batch_camera_tile` {t[0]} / {t[1]} / 0 / 0 / 0", f"`k_batch_camera_depth` {d[0]} / {d[1]} / 0 / 0 / 0"):
         assert text in design, text
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_lane_masks.py")], capture_output=True, text=True)
-    assert r.returncode == 0 and " 0 lane masks" in r.stdout, r.stdout[-400:]
     k = read("mgf_amd", "csrc", "k_batch_camera.h")
     assert len(re.findall(r"__global__ __launch_bounds__\(kBatchBlock\)", k)) == len(re.findall(r"__global__", k)) == 2
 

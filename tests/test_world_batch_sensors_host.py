@@ -2,13 +2,11 @@
 mgf_batch_cast_sensors_dev) without a GPU: the numpy restatement of the definition the GPU tests hold the kernel to equals the oracle's
 mgfo_rotate_vector bit for bit; the header, the library, the binding and INTEGRATION.md carry the calls; what can be refused before a
 device is looked at is refused there; mgf_batch_cast_sensors_dev looks both pointers up before it enqueues anything; the binding turns
-a wrong tensor down before it calls C; the new kernel uses no scratch and spills nothing and the query kernels keep the figures
-DESIGN.md records; and the plan of a rig - BatchQueryPlan's, modelled in numpy - is a partition into items of at most 256 sensors."""
+a wrong tensor down before it calls C; the new kernel uses no scratch and spills nothing and DESIGN.md records the query kernels'
+figures (held to the build, as the plan of a rig is, in tests/test_world_batch_rigs_host.py)."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,6 +14,7 @@ import pytest
 import mgf_amd
 from mgf_amd import _capi
 from tests import batch_query_device_cases as QD
+from tests import batch_rig_cases as RC
 from tests import batch_sensor_cases as SC
 from tests.util import RESOURCES, ROOT, kernel_resources, read
 
@@ -131,15 +130,18 @@ def test_what_needs_no_device_is_refused_before_the_handle_is_dereferenced():
     # host too, ahead of any device work (read here; run in tests/test_gpu_world_batch_sensors.py, where a handle exists)
     src = read("mgf_amd", "csrc", "host_batch_sensor.inc")
     body = src[src.index('extern "C" mgf_status mgf_batch_set_sensors('):src.index('extern "C" int64_t mgf_batch_sensor_count(')]
-    first_change = body.index("b->s_rig.assign(")
+    assert not re.search(r"b->sensors\.|\bR\.", body.replace("batch_rig_plan(b, b->sensors, s, n);", ""))   # the rig changes in the plan step alone
+    body = RC.set_call_with_plan(body, "batch_rig_plan(b, b->sensors, s, n);")  # the set call together with the shared plan step
+    first_change = body.index("R.recs.assign(")
+    assert body.index("batch_rig_set_args(b, s, n_in)") < first_change
     assert body.index("batch_rig_ref_check(b, s[i].world, s[i].body, s[i].flags, \"sensor\")") < first_change   # every record, ahead of any change
-    check = src[src.index("static mgf_status batch_rig_ref_check("):src.index('extern "C" mgf_status mgf_batch_set_sensors(')]
+    check = RC.ref_check_step()
     assert (check.index("world index out of range: the rig was not changed") < check.index("body index out of range: the rig was not changed")
             < check.index("a %s's flags hold a bit beyond MGF_SENSOR_IGNORE_SELF: the rig was not changed") < check.index("return MGF_OK;"))
     assert not re.search(r"<<<|Async|hipMalloc|\.ensure\(|h2d\(|b->\w+ =[^=]", check)    # it refuses; it changes nothing
     assert not re.search(r"<<<|Async|hipMalloc|\.ensure\(|h2d\(", body)            # no device work at all
     args = src[src.index("static mgf_status batch_sensor_args("):src.index('extern "C" mgf_status mgf_batch_cast_sensors(')]
-    assert args.index("MGF_ERR_CAPACITY") < args.index('"NULL argument"') < args.index("return MGF_OK;") and "ctx_bind" not in args and "<<<" not in args
+    RC.assert_the_read_and_cast_refusals(args, ["batch_rig_cap(cap)", "query_mask_check(kinds_mask)"])
 
 
 # ---- 4 ------------------------------------------------------------------------------------------------------------------------------------
@@ -169,7 +171,7 @@ def test_both_pointers_are_looked_up_before_the_first_enqueue():
     is batch_sensor_run - and the refusals that need no device before the context is bound"""
     src = read("mgf_amd", "csrc", "host_batch_sensor.inc")
     run = src[src.index('extern "C" mgf_status mgf_batch_cast_sensors_dev('):]
-    enqueue = (r"batch_sensor_run\(|batch_sensors_up\(|batch_rig_upload\(|batch_ray_obstacles\(|batch_sweep_tail\(|batch_push\(|batch_dev_begin\(|batch_env_sync\(|"
+    enqueue = (r"batch_sensor_run\(|batch_rig_up\(|batch_rig_upload\(|batch_ray_obstacles\(|batch_sweep_tail\(|batch_push\(|batch_dev_begin\(|batch_env_sync\(|"
                r"batch_cols_refresh\(|hipMemsetAsync|hipMemcpyAsync|<<<|prim_exclusive_scan_u32|\.ensure\(|h2d\(")
     first_enqueue = min(m.start() for m in re.finditer(enqueue, run))
     checks = [m.start() for m in re.finditer(r"dev_span\(", run)]
@@ -183,16 +185,17 @@ def test_both_pointers_are_looked_up_before_the_first_enqueue():
     _the_overlap_helper_compares_and_enqueues_nothing(enqueue)
     assert run.index("batch_sensor_args(") < run.index("ctx_bind(") < min(checks)
     assert run.index("if (n == 0) return MGF_OK;") < first_enqueue                   # an empty rig enqueues nothing
-    # everything that enqueues is in batch_sensor_run and batch_sensors_up, and those are reached from the two cast calls only
+    # everything that enqueues is in batch_sensor_run and batch_rig_up, and those are reached from the two cast calls only
     helper = src[src.index("static mgf_status batch_sensor_run("):src.index("static mgf_status batch_sensor_args(")]
     # its own kernel's launch and the shared obstacle pass; neither it nor that pass waits or copies
     assert helper.count("<<<") == 1 and "k_batch_sensor_ray<<<" in helper and helper.index("k_batch_sensor_ray<<<") < helper.index("batch_ray_obstacles(")
     assert "hipStreamSynchronize" not in helper and "hipMemcpy" not in helper
     obstacles = _the_shared_obstacle_pass()
     assert "hipStreamSynchronize" not in obstacles and "hipMemcpy" not in obstacles
-    up = src[src.index("static mgf_status batch_sensors_up("):src.index("// The launches of a cast")]
-    assert up.index("if (!b->s_stale) return MGF_OK;") < up.index("internal error") < up.index("batch_rig_upload(") and "h2d(" not in up
-    upload = src[src.index("static mgf_status batch_rig_upload("):src.index("// the rig onto the device")]
+    assert helper.index("batch_push(") < helper.index('batch_rig_up(b, R, "sensor", 4)') < helper.index("k_batch_sensor_ray<<<")
+    up = RC.up_step()
+    assert up.index("if (!R.stale) return MGF_OK;") < up.index("internal error") < up.index("batch_rig_upload(") and "h2d(" not in up
+    upload = RC.upload_step()
     assert upload.count("h2d(") == 1 and upload.count(".ensure(") == 1 and "<<<" not in upload          # the steady state uploads nothing; ONE copy
     # no exit ahead of a barrier, no atomic: the front the kernel shares with k_batch_query_ray (k_batch_query.h) holds every exit and
     # every barrier, and what the kernel itself brings - the loader and the store behind the hit - holds neither
@@ -256,55 +259,17 @@ def test_the_new_kernel_uses_no_scratch_and_the_query_kernels_keep_their_figures
     assert set(rows) == {"k_batch_sensor_ray"}, sorted(rows)
     v = rows["k_batch_sensor_ray"]
     assert (v[2], v[3], v[4], v[5]) == ("0", "0", "0", "0"), v               # no scratch, no static LDS, no spills
-    old = kernel_resources("k_batch_query_")
-    assert int(v[0]) <= int(old["k_batch_query_ray"][0]) + 8, (v, old["k_batch_query_ray"])   # one piece of work, about the same registers
-    assert set(old) == set(RESOURCES), sorted(old)
-    for name, want in RESOURCES.items():
-        assert old[name] == want, (name, old[name], want)
+    # (RESOURCES is held to the build in tests/test_world_batch_rigs_host.py)
+    assert int(v[0]) <= int(RESOURCES["k_batch_query_ray"][0]) + 8, (v, RESOURCES["k_batch_query_ray"])   # one piece of work, about the same registers
     design = re.sub(r"\s+", " ", read("DESIGN.md"))
     for text in ("`k_batch_query_ray` 45 / 65 / 0 / 0 / 0", "`k_batch_query_sweep_faces` 133 / 69 / 9216 / 0 / 0", "`_ray_obstacles` 68 / 63 / 0 / 0 / 0",
                  "`k_batch_query_sweep_bodies` 108 / 90 / 0 / 0 / 0", "`k_batch_query_plan_fill` 10 / 20", "`_sweep_obstacles` 115 / 87 / 0 / 0 / 0"):
         assert text in design, text
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_lane_masks.py")], capture_output=True, text=True)
-    assert r.returncode == 0 and " 0 lane masks" in r.stdout, r.stdout[-400:]
     k = read("mgf_amd", "csrc", "k_batch_sensor.h")
     assert len(re.findall(r"__global__ __launch_bounds__\(kBatchBlock\)", k)) == len(re.findall(r"__global__", k)) == 1
 
 
 # ---- 7 ------------------------------------------------------------------------------------------------------------------------------------
-def _plan_cases():
-    twin, pile = SC.twin_scenes(), QD.pile_scenes()
-    return [("worlds of 0, 1, 256, 257 and 600", SC.plan_worlds(), len(SC.PLAN_COUNTS), list(SC.PLAN_COUNTS)),
-            ("the same reversed", SC.plan_worlds()[::-1], len(SC.PLAN_COUNTS), list(SC.PLAN_COUNTS)),
-            ("twin", SC.twin_layout(twin)["world"], len(twin), [0, 1, 257]), ("pile", SC.pile_layout(pile)["world"], len(pile), [2, 42, 60, 0, 320])]
-
-
-@pytest.mark.parametrize("case", range(4))
-def test_the_plan_of_a_rig_is_a_partition_into_items_of_at_most_256(case):
-    """mgf_batch_set_sensors sorts the rig with the host's BatchQueryPlan: one stable counting sort.  QD.plan_model is that plan with the
-    ranks taken in array order - the host's order - so here the caller's relative order within a world is part of the claim"""
-    name, world, K, counts = _plan_cases()[case]
-    n = len(world)
-    assert np.any(np.diff(world) < 0), name                                        # shuffled world order
-    items, order, skipped = QD.plan_model(world, K)
-    assert skipped == 0 and sorted(order.tolist()) == list(range(n)), name
-    assert np.bincount(world, minlength=K).tolist() == counts, name
-    seen = np.zeros(n, np.int64)
-    for w, first, count in items:
-        assert 1 <= count <= 256, (name, count)
-        q = order[first:first + count]
-        assert np.all(world[q] == w) and np.all(np.diff(q) > 0), name              # one world; the caller's relative order
-        seen[q] += 1
-    assert np.all(seen == 1), name
-    assert np.all(np.diff(items[:, 0]) >= 0) and np.all(np.diff(items[:, 1]) > 0), name
-    assert len(items) == sum((c + 255) // 256 for c in counts), name
-    for w in range(K):                                                             # across a world's items too: ascending
-        q = order[np.flatnonzero(world[order] == w)]
-        assert np.all(np.diff(q) > 0), (name, w)
-    if case == 0:
-        assert items[:, 2].tolist() == [1, 256, 256, 1, 256, 256, 88]
-
-
 def test_the_layouts_hold_what_the_gpu_tests_ask_of_them():
     """from the scenes alone: 257 sensors on the world of 300, none on one world, one on the world of one body, four on one body, the
     d = 0 and the too-short sensor, the pair at one sphere's centre, and sensors for the floor, the ring and the sky"""

@@ -2,14 +2,12 @@
 mgf_batch_overlap_first_dev) without a GPU: the numpy restatement the GPU tests hold the kernel to equals float64 where every operation
 is exact, and hand-checked corners; the header, the library, the binding and the documents carry the calls and the struct; what can be
 refused before a device is looked at is refused there; both device forms look every pointer up before they enqueue anything; the binding
-turns a wrong tensor down before it calls C; the plan of a rig is a partition into items of at most 256 zones; the new kernel uses no
-scratch and no static LDS and the query kernels keep the figures DESIGN.md records; and, by the oracle's box test, the scenes of the GPU
+turns a wrong tensor down before it calls C; the new kernel uses no scratch and no static LDS and keeps the figures DESIGN.md records
+(the plan of a rig and the query kernels' figures: tests/test_world_batch_rigs_host.py); and, by the oracle's box test, the scenes of the GPU
 tests hold the cases those tests are for."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,8 +15,9 @@ import pytest
 import mgf_amd
 from mgf_amd import _capi
 from tests import batch_query_device_cases as QD
+from tests import batch_rig_cases as RC
 from tests import batch_zone_cases as ZC
-from tests.util import RESOURCES, ROOT, kernel_resources, read
+from tests.util import ROOT, kernel_resources, read
 
 CALLS = ("mgf_batch_set_zones", "mgf_batch_zone_count", "mgf_batch_read_zones", "mgf_batch_read_zones_dev", "mgf_batch_overlap_first_dev")
 f32 = np.float32
@@ -167,28 +166,32 @@ def test_what_needs_no_device_is_refused_before_the_handle_is_dereferenced():
     # tests/test_gpu_world_batch_zones.py, where a handle exists)
     src = read("mgf_amd", "csrc", "host_batch_zone.inc")
     body = src[src.index('extern "C" mgf_status mgf_batch_set_zones('):src.index('extern "C" int64_t mgf_batch_zone_count(')]
-    first_change = body.index("b->z_rig.assign(")
-    for refusal in ('batch_rig_ref_check(b, z[i].world, z[i].body, z[i].flags, "zone", true)', "has no body of its own to ignore", "reserved word is not 0"):
+    assert not re.search(r"b->zones\.|\bR\.", body.replace("batch_rig_plan(b, b->zones, z, n);", ""))   # the rig changes in the plan step alone
+    body = RC.set_call_with_plan(body, "batch_rig_plan(b, b->zones, z, n);")    # the set call together with the shared plan step
+    first_change = body.index("R.recs.assign(")
+    for refusal in ("batch_rig_set_args(b, z, n_in)", 'batch_rig_ref_check(b, z[i].world, z[i].body, z[i].flags, "zone", true)', "has no body of its own to ignore", "reserved word is not 0"):
         assert body.index(refusal) < first_change, refusal
     assert not re.search(r"<<<|Async|hipMalloc|\.ensure\(|h2d\(", body)            # no device work at all
-    assert not re.search(r"b->[sc]_\w+", src)                                      # the sensor and camera rigs are not touched from here
-    # the helper is the sensors', extended: one copy of it, and it lets -1 through only where it is asked to
+    # the sensor and camera rigs are not touched from here: it names b->zones and neither b->sensors nor b->cameras
+    assert not re.search(r"b->[sc]_\w+", src) and "b->zones" in src and "b->sensors" not in src and "b->cameras" not in src
+    # the helper is the rigs' one: one copy of it, and it lets -1 through only where it is asked to
     sens = read("mgf_amd", "csrc", "host_batch_sensor.inc")
-    assert "batch_rig_ref_check(" not in src.replace("MGF_TRY(batch_rig_ref_check(", "") and sens.count("static mgf_status batch_rig_ref_check(") == 1
-    check = sens[sens.index("static mgf_status batch_rig_ref_check("):sens.index('extern "C" mgf_status mgf_batch_set_sensors(')]
+    assert "batch_rig_ref_check(" not in src.replace("MGF_TRY(batch_rig_ref_check(", "") and RC.rig_source().count("static mgf_status batch_rig_ref_check(") == 1
+    assert "static mgf_status batch_rig_ref_check(" not in sens
+    check = RC.ref_check_step()
     assert "bool or_world = false" in check and "!(or_world && body == -1) && (body < 0 ||" in check
     args = src[src.index("static mgf_status batch_zone_read_args("):src.index('extern "C" mgf_status mgf_batch_read_zones(')]
-    assert (args.index("zone_k_check(") < args.index("cap is negative") < args.index("MGF_ERR_CAPACITY") < args.index('"NULL argument"') < args.index("return MGF_OK;")
-            and "ctx_bind" not in args and "<<<" not in args)
+    RC.assert_the_read_and_cast_refusals(args, ["zone_k_check(k)", "batch_rig_cap(cap)"])          # k ahead of a negative cap
     host = read("mgf_amd", "csrc", "host_batch.inc")
     add = host[host.index('extern "C" mgf_status mgf_batch_add_bodies('):]
     add = add[:add.index("\n}\n")]
-    assert "b->z_stale = true;" in add and "b->s_stale = true;" in add and "b->c_stale = true;" in add
-    assert "z_rig" not in sens and "z_rig" not in read("mgf_amd", "csrc", "host_batch_camera.inc")
+    stale = RC.stale_step()
+    assert "batch_rigs_stale(b);" in add and "b->zones.stale = true;" in stale and "b->sensors.stale = true;" in stale and "b->cameras.stale = true;" in stale
+    assert "b->zones" not in sens and "b->zones" not in read("mgf_amd", "csrc", "host_batch_camera.inc")
 
 
 # ---- 4 ------------------------------------------------------------------------------------------------------------------------------------
-ENQUEUE = (r"batch_zone_run\(|batch_zones_up\(|batch_rig_upload\(|batch_push\(|batch_dev_begin\(|batch_env_sync\(|batch_cols_refresh\(|hipMemsetAsync|"
+ENQUEUE = (r"batch_zone_run\(|batch_rig_up\(|batch_rig_upload\(|batch_push\(|batch_dev_begin\(|batch_env_sync\(|batch_cols_refresh\(|hipMemsetAsync|"
            r"hipMemcpyAsync|<<<|prim_exclusive_scan_u32|\.ensure\(|h2d\(")
 
 
@@ -220,24 +223,34 @@ def test_both_device_forms_look_every_pointer_up_before_the_first_enqueue():
     q = read("mgf_amd", "csrc", "host_batch_query_dev.inc")
     helper = q[q.index("static mgf_status dev_outputs_overlap("):q.index("// Q = ParticleIn")]
     assert "dev_bytes_overlap(a[i].p, a[i].bytes, a[j].p, a[j].bytes)" in helper and not re.search(ENQUEUE, helper) and "b->" not in helper
-    # everything a rig read enqueues is in batch_zone_run and batch_zones_up: one launch, counted; no wait, no copy but the rig's
+    # everything a rig read enqueues is in batch_zone_run and batch_rig_up: one launch, counted; no wait, no copy but the rig's
     helper = src[src.index("static mgf_status batch_zone_run("):src.index("static mgf_status zone_k_check(")]
     assert helper.count("<<<") == 1 and "k_batch_zone_first<kItemTable><<<" in helper and "hipStreamSynchronize" not in helper and "hipMemcpy" not in helper
     assert helper.index("LAUNCH_CHECK();") < helper.index("b->q_launches += MGF_BATCH_ZONE_LAUNCHES;")
-    up = src[src.index("static mgf_status batch_zones_up("):src.index("// what both launches share")]
-    assert up.index("if (!b->z_stale) return MGF_OK;") < up.index("internal error") < up.index("batch_rig_upload(") and up.count("batch_rig_upload(") == 1 and "h2d(" not in up
+    assert helper.index("batch_push(") < helper.index('batch_rig_up(b, R, "zone", 3, true)') < helper.index("k_batch_zone_first<kItemTable><<<")
+    up = RC.up_step()
+    assert up.index("if (!R.stale) return MGF_OK;") < up.index("internal error") < up.index("batch_rig_upload(") and up.count("batch_rig_upload(") == 1 and "h2d(" not in up
     # the host form: one download, one wait
     host = src[src.index('extern "C" mgf_status mgf_batch_read_zones('):src.index('extern "C" mgf_status mgf_batch_read_zones_dev(')]
     assert host.count("hipMemcpyAsync(") == 2 and host.count("hipStreamSynchronize(") == 2 and host.index("if (!boxes_out) {") < host.index("hipMemcpyAsync(")
     # the kernel: no exit at all, no atomic, one barrier ahead of the split; every lane makes every trip
-    k = read("mgf_amd", "csrc", "k_batch_zone.h")
-    front = k[k.index("void bz_front("):k.index("// LDS (dynamic)")]
-    assert "return;" not in front and "atomic" not in front and front.count("__syncthreads()") == 1
-    assert (front.index("__syncthreads()") < front.index("W.template split<SRC == kItemFixed>(A, min(W.shift(), 6u))") < front.index("load(qi, g0)")
-            < front.index("for (uint32_t i0 = 0; i0 < n; i0 += L)") < front.index("(int32_t)i != ign") < front.index("__ballot(hit)")
-            < front.index("if (hit && rank < k)") < front.index("o[0] = (int32_t)m") < front.index("o[1u + s] = -1"))
-    assert "comp_bounds(to_comp(A.col0[(size_t)g0 + i], A.col1[(size_t)g0 + i]))" in front and "isnan" not in k
+    # (read in the front the kernel shares with k_batch_observe_overlap - bo_front, k_batch_observe.h - followed by the kernel itself,
+    # which brings the loaders, the store behind a hit and the epilogue)
+    k, o = read("mgf_amd", "csrc", "k_batch_zone.h"), read("mgf_amd", "csrc", "k_batch_observe.h")
+    shared = o[o.index("uint32_t bo_front("):o.index("// LDS (dynamic): 32 bytes a body.")]
     body = k[k.index("void k_batch_zone_first("):]
+    front = shared + body
+    # (the only returns: the front's count at its end and the values of the kernel's hooks - a loader's box, the record's address)
+    assert "return;" not in front and not re.search(r"return (?!m;|b;|BatchBox\{|A\.out \+)", front) and shared.rstrip().endswith("return m;\n}")
+    assert "atomic" not in front and front.count("__syncthreads()") == 1
+    assert (front.index("__syncthreads()") < front.index("W.template split<IDENTITY>(A, min(W.shift(), 6u))") < front.index("load(W.qi, g0)")
+            < front.index("for (uint32_t i0 = 0; i0 < n; i0 += L)") < front.index("(int32_t)i != ign") < front.index("__ballot(hit)")
+            < front.index("put(hit, i, m + (uint32_t)__popcll(g & ((1ull << sub) - 1ull)));") < len(shared)
+            < front.index("if (hit && rank < k) record()[1u + rank] = (int32_t)i") < front.index("o[0] = (int32_t)m") < front.index("o[1u + s] = -1"))
+    # the fixed layout splits with the identity for an order, and both layouts drop the ignored body
+    assert "SRC == kItemFixed ? bo_front<true, true>(A, W, s_dyn, z, fixed, store) : bo_front<false, true>(A, W, s_dyn, z, mounted, store)" in body
+    assert "template <bool IDENTITY, bool IGNORE, class Load, class Put>" in o and "(!IGNORE || (int32_t)i != ign)" in shared
+    assert "comp_bounds(to_comp(A.col0[(size_t)g0 + i], A.col1[(size_t)g0 + i]))" in shared and "isnan" not in k and "isnan" not in o
     assert not re.search(r"return;|__syncthreads|atomic|__shared__ (?!float4 s_dyn)", body.replace("extern __shared__ float4 s_dyn[];", ""))
 
 
@@ -307,36 +320,6 @@ def test_the_binding_turns_a_wrong_tensor_down_before_it_calls_c():
         b.set_zones([0, 1, 1], [0, 1], (0, 0, 0), (1, 1, 1))           # neither one nor n
 
 
-# ---- 6 ------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", range(len(ZC.PLAN_CASES)))
-def test_the_plan_of_a_rig_is_a_partition_into_items_of_at_most_256(case):
-    """mgf_batch_set_zones sorts the rig with the host's BatchQueryPlan: one stable counting sort.  QD.plan_model is that plan with the
-    ranks taken in array order - the host's order - so here the caller's relative order within a world is part of the claim"""
-    name, counts = ZC.PLAN_CASES[case]
-    world, K = ZC.plan_worlds(counts), len(counts)
-    n = len(world)
-    assert n == sum(counts)
-    items, order, skipped = QD.plan_model(world, K)
-    assert skipped == 0 and sorted(order.tolist()) == list(range(n)), name
-    seen = np.zeros(n, np.int64)
-    for w, first, count in items:
-        assert 1 <= count <= 256, (name, count)
-        q = order[first:first + count]
-        assert np.all(world[q] == w) and np.all(np.diff(q) > 0), name              # one world; the caller's relative order
-        seen[q] += 1
-    assert np.all(seen == 1), name
-    assert np.all(np.diff(items[:, 0]) >= 0) and np.all(np.diff(items[:, 1]) > 0), name
-    assert len(items) == sum((c + 255) // 256 for c in counts), name
-    assert set(items[:, 0].tolist()) == {k for k, c in enumerate(counts) if c}, name    # a world without zones has no item
-    if name == "257":
-        assert items[:, 2].tolist() == [256, 1]
-    if K > 1:
-        assert np.any(np.diff(world) < 0) and items[:, 2].tolist() == [3, 256, 1, 65]
-    src = read("mgf_amd", "csrc", "host_batch_zone.inc")
-    body = src[src.index('extern "C" mgf_status mgf_batch_set_zones('):src.index('extern "C" int64_t mgf_batch_zone_count(')]
-    assert "const BatchQueryPlan plan(b->K, world.data(), n);" in body and "plan.fill(world.data(), n, b->z_items.data(), b->z_order.data());" in body
-
-
 # ---- 7 ------------------------------------------------------------------------------------------------------------------------------------
 def test_the_new_kernel_uses_no_scratch_and_the_query_kernels_keep_their_figures():
     if not os.path.exists(os.path.join(ROOT, "mgf_amd", "libmgf_hip.so")) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
@@ -348,12 +331,6 @@ def test_the_new_kernel_uses_no_scratch_and_the_query_kernels_keep_their_figures
         assert (v[2], v[3], v[4], v[5]) == ("0", "0", "0", "0"), (name, v)       # no scratch, no static LDS, no spills
         assert int(v[0]) <= 64, (name, v)                                         # eight waves a SIMD at 64 VGPRs
         assert f"`{name}` {v[0]} / {v[1]} / 0 / 0 / 0" in design, (name, v)       # the line DESIGN.md records
-    old = kernel_resources("k_batch_query_")
-    assert set(old) == set(RESOURCES), sorted(old)
-    for name, want in RESOURCES.items():
-        assert old[name] == want, (name, old[name], want)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_lane_masks.py")], capture_output=True, text=True)
-    assert r.returncode == 0 and " 0 lane masks" in r.stdout, r.stdout[-400:]
     k = read("mgf_amd", "csrc", "k_batch_zone.h")
     assert len(re.findall(r"__global__ __launch_bounds__\(kBatchBlock\)", k)) == len(re.findall(r"__global__", k)) == 1
     assert "__shared__" not in k.replace("extern __shared__ float4 s_dyn[];", "")
