@@ -568,11 +568,15 @@ MGF_API mgf_status mgf_world_release_device_ptrs(mgf_world* w);
  * (manifold.rs:72-148, solver.rs:101-191), Solver::solve (solver.rs:72-78).  Worlds never interact; what world k computes does not
  * depend on what else is in the batch or on where in it the world sits.  No workgroup waits for another: a batch may hold more
  * worlds than the device holds workgroups, and it is safe on a device shared with another process.
- * LIMITS: bodies of one component (spheres and capsules); at most MGF_BATCH_MAX_BODIES bodies per world (a call that would exceed it
+ * LIMITS: bodies of one to four components (spheres and capsules; mgf_batch_add_compound_bodies below - the lone world takes 32, a body
+ * of 5..32 is refused here); on a batch that holds a body of more than one component the calls that read the shapes of bodies -
+ * mgf_batch_raycast_many(_dev), _sweep_many(_dev), _overlap_aabb_many, _overlap_first_dev, _cast_sensors(_dev), _cast_cameras(_dev),
+ * _read_zones(_dev) - return MGF_ERR_INVALID ("... several components ..."), enqueue nothing and change nothing: they do not see
+ * parts yet (the set_* calls of the rigs stay as they are); at most MGF_BATCH_MAX_BODIES bodies per world, counted in bodies, not parts (a call that would exceed it
  * is refused with MGF_ERR_INVALID and adds nothing); the static geometry of a world is one terrain mesh, or none: an entry of the
  * batch's terrain table (meshes are copied in; any number of worlds may share an entry) at a position of the world's own, and beside it
  * up to MGF_BATCH_MAX_WORLD_OBSTACLES static Compound obstacles: entries of the batch's obstacle table, each at a pose of the world's
- * own ("the obstacle table" below); canonical constraint order only.  There are no bodies of several components, no moving obstacles,
+ * own ("the obstacle table" below); canonical constraint order only.  There are no bodies of more than four components, no moving obstacles,
  * no ghosts or tiles and no constraint_order = demo: a batch has no entry point for them.  A tick never fails for list sizes: a world whose
  * constraints outgrow its share of the storage gets its tick undone on the device and run again with more (Solver::solve and
  * World::step have no capacity failure, solver.rs:72-78); mgf_batch_counter "capacity_retries" counts those re-runs.
@@ -632,6 +636,25 @@ MGF_API int64_t mgf_batch_world_obstacle_count(const mgf_batch* b, int64_t world
  * first new body within that world.  A tag other than 0 or 1, a negative n, a world index out of range: MGF_ERR_INVALID. */
 MGF_API mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mgf_component* comps, int64_t n, const float* mass,
                                         const float* restitution, const float* friction, const mgf_vec3* world_force, uint64_t* first_id);
+/* Bodies of 1..4 components for world `world`, as mgf_world_add_compound_bodies: body r is comps[offsets[r] .. offsets[r + 1]) in world
+ * coordinates at creation, comp_mass per component, restitution / friction / world_force per body; mass = the sum, x = the centre of
+ * mass, q = identity, parts fixed in the body frame and rebuilt from (x, q) every tick.  World k then behaves, bit for bit, as a lone
+ * mgf_world that has been through the same mgf_world_add_bodies / mgf_world_add_compound_bodies calls in the same order (the oracle's
+ * World::collide: a body's tight box is the union of its parts' swept bounds; per face met by that box the parts in order; per obstacle
+ * the parts in order, each with its own query box; all part pairs of a pair of bodies - the first body's parts outer - through
+ * ContactPruner and Manifold::from, every contact of the manifold a consecutive record with the manifold's normal, at most 16).
+ * *first_id = the index of the first new body within that world; indices follow call order across mgf_batch_add_bodies and this call.
+ * A body of ONE component is the ordinary body mgf_batch_add_bodies adds, with that component's mass; a batch without a body of more
+ * than one component keeps no part storage and runs the tick it always ran.  Allowed behind ticks and into a world in the middle of
+ * the batch; rigs keep naming the (world, body) they named.  mgf_batch_read_colliders gives such a body the lone world's row (a
+ * radius-0 sphere at the centre of mass); mgf_batch_copy_worlds(_where) carry a world's part rows - the destination is a clone.
+ * MGF_ERR_INVALID, nothing added, before the batch or a device is looked at: a NULL batch, comps, offsets or first_id; a negative n or
+ * world; offsets[0] != 0; a body of 0 or of more than 4 components (the batch takes four, the lone world 32); a tag other than 0 or 1;
+ * n > MGF_BATCH_MAX_BODIES.  A world index >= n_worlds or a world that would pass MGF_BATCH_MAX_BODIES: MGF_ERR_INVALID, nothing added.
+ * A singular mass: MGF_ERR_SINGULAR. */
+MGF_API mgf_status mgf_batch_add_compound_bodies(mgf_batch* b, int64_t world, const mgf_component* comps, const float* comp_mass,
+                                                 const int64_t* offsets /* n + 1 */, int64_t n, const float* restitution,
+                                                 const float* friction, const mgf_vec3* world_force, uint64_t* first_id);
 MGF_API int64_t mgf_batch_len(const mgf_batch* b, int64_t world);   /* RigidBodyVec::len; world = -1: all bodies of the batch; -1 for a bad argument */
 /* n_ticks x World::step (world.rs:227-294) of every world.  stats: NULL or n_ticks * n_worlds records, tick-major (record t * n_worlds + k =
  * world k's tick t): n_bodies, n_constraints, n_terrain_constraints, n_pair_candidates, n_refits and iters are filled; the fields the batch
@@ -759,7 +782,11 @@ MGF_API mgf_status mgf_batch_apply_impulses(mgf_batch* b, const int32_t* world, 
  * A source may be named any number of times (fan-out).  Refused with MGF_ERR_INVALID, nothing copied, before any launch: a NULL batch,
  * NULL arrays with n > 0, a negative n or n > INT32_MAX, a world index out of range, batches of different contexts, a destination and
  * its source of different lengths, a destination named twice, and - where dst == src - a world that is both a source and a
- * destination.  One workgroup per pair, one launch (and one more when shares grow): "drive_launches" of dst. */
+ * destination.  One workgroup per pair, one launch (and one more when shares grow): "drive_launches" of dst.
+ * Bodies of several components: a world's part rows travel in one more launch - the destination is a clone.  When src holds part
+ * storage (it has held a body of more than one component) and dst does not, dst gets it before anything is enqueued and KEEPS it,
+ * whatever the copied worlds hold: from then on dst ticks in seven launches and its calls that read the shapes of bodies (ray casts,
+ * sweeps, box overlaps, sensors, cameras, zones) return MGF_ERR_INVALID ("several components"), as on src. */
 MGF_API mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_world, const mgf_batch* src, const int32_t* src_world, int64_t n);
 /* ---- device-pointer calls: state, forces, impulses, contact summaries and resets for a caller whose arrays are device memory ----
  * The calls above move their records through host memory (an upload or a download and a host wait per call).  These take pointers
@@ -823,7 +850,9 @@ MGF_API mgf_status mgf_batch_read_body_contacts_dev(mgf_batch* b, int64_t world,
  * n > 0.  The host cannot know the mask: the share of EVERY named destination grows to its source's list before the launch (a larger
  * share than needed may stay; no record is lost).  The pair table stays on the device in dst and is uploaded again only when the arrays
  * differ from the last call's (mgf_batch_counter "pair_table_uploads", cumulative).  mgf_batch_read_constraints and a later copy out of
- * dst first fetch the lengths of dst's lists from the device (one wait); mgf_batch_step does that anyway. */
+ * dst first fetch the lengths of dst's lists from the device (one wait); mgf_batch_step does that anyway.
+ * As mgf_batch_copy_worlds, a src with part storage makes dst a batch with part storage for good - also when the mask selects nothing:
+ * the host cannot know the mask.  A ray cast on dst that then returns MGF_ERR_INVALID ("several components") has this cause. */
 MGF_API mgf_status mgf_batch_copy_worlds_where(mgf_batch* dst, const int32_t* dst_world, const mgf_batch* src, const int32_t* src_world,
                                                int64_t n, const int32_t* mask_dev);
 /* Of a batch's rays, sweeps and box queries the first two have a device-pointer form, the observations a policy reads every tick.

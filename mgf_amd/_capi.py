@@ -179,7 +179,7 @@ SYMBOLS = [
     "mgf_tiles_create", "mgf_tiles_free", "mgf_rccl_unique_id", "mgf_rccl_allow_override", "mgf_tiles_connect", "mgf_tiles_preflight", "mgf_tiles_step",
     "mgf_tiles_migrated", "mgf_tiles_set_option", "mgf_world_add_obstacle", "mgf_tiles_counter",
     "mgf_batch_new", "mgf_batch_free", "mgf_batch_set_terrain", "mgf_batch_add_terrain", "mgf_batch_set_world_terrain",
-    "mgf_batch_terrain_count", "mgf_batch_add_bodies", "mgf_batch_len", "mgf_batch_step",
+    "mgf_batch_terrain_count", "mgf_batch_add_bodies", "mgf_batch_add_compound_bodies", "mgf_batch_len", "mgf_batch_step",
     "mgf_batch_read_state", "mgf_batch_write_state", "mgf_batch_read_constraints", "mgf_batch_counter", "mgf_batch_set_option",
     "mgf_batch_read_colliders", "mgf_batch_raycast_many", "mgf_batch_sweep_many",
     "mgf_batch_read_body_contacts", "mgf_batch_overlap_aabb_many",
@@ -329,6 +329,7 @@ def load_library():
         "mgf_batch_set_world_terrain": (i32, [vp, vp, vp, vp, i64]),
         "mgf_batch_terrain_count": (i64, [vp]),
         "mgf_batch_add_bodies": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, P(u64)]),
+        "mgf_batch_add_compound_bodies": (i32, [vp, i64, vp, vp, vp, i64, vp, vp, vp, P(u64)]),
         "mgf_batch_len": (i64, [vp, i64]),
         "mgf_batch_step": (i32, [vp, f32, i32, i64, vp]),
         "mgf_batch_read_state": (i32, [vp, i64, vp, vp, vp, vp, vp, i64]),
@@ -1330,7 +1331,9 @@ def terrain_table(terrains):
 
 class WorldBatch:
     """Many small independent worlds resident on one GPU, stepped together (mgf_batch_*): per world `step` is
-    mgf_demo/world.rs::World::step, one workgroup a world.  At most BATCH_MAX_BODIES single-component bodies per world; a world's
+    mgf_demo/world.rs::World::step, one workgroup a world.  At most BATCH_MAX_BODIES bodies of one to four components per world
+    (add_compound_bodies; on a batch that holds a body of more than one component the calls that read the shapes of bodies - ray
+    casts, sweeps, box overlaps, sensors, cameras, zones - raise ERR_INVALID: they do not see parts yet); a world's
     terrain is an entry of the batch's terrain table (shared by any number of worlds) at a position of its own, or none; its static
     Compound obstacles are a list of entries of the batch's obstacle table, each at a pose of the world's own."""
 
@@ -1381,11 +1384,12 @@ class WorldBatch:
         if rec:
             b.set_world_obstacles([r[0] for r in rec], [r[1] for r in rec], [r[2] for r in rec], [r[3] for r in rec])
         for k, sc in enumerate(scenes):
-            if sc.get("compound") is not None:
-                raise MgfError(ERR_INVALID, "a batch world holds bodies of one component")
             if len(sc["comps"]):
                 b.add_bodies(k, sc["comps"], sc["mass"], sc["restitution"], sc["friction"], sc["force"])
-            if sc.get("v0") is not None and len(sc["comps"]):
+            cb = sc.get("compound")  # bodies of up to four components, behind the ordinary ones (World.from_scene)
+            if cb is not None:
+                b.add_compound_bodies(k, cb["comps"], cb["comp_mass"], cb["offsets"], cb["restitution"], cb["friction"], cb["force"])
+            if sc.get("v0") is not None and b.world_len(k):
                 b.write_state(k, v=sc["v0"])
         return b
 
@@ -1446,6 +1450,21 @@ class WorldBatch:
         first = C.c_uint64()
         _check(load_library().mgf_batch_add_bodies(self._h, int(world), comps.ctypes.data, n, mass.ctypes.data, rest.ctypes.data,
                                                    fric.ctypes.data, force.ctypes.data, C.byref(first)))
+        return first.value
+
+    def add_compound_bodies(self, world, comps, comp_mass, offsets, restitution, friction, world_force):
+        """Bodies of 1..4 components for one world (mgf_batch_add_compound_bodies): body r = comps[offsets[r]:offsets[r + 1]], as
+        World.add_compound_bodies; a body of one component is the ordinary body.  Returns the first new body's index in the world."""
+        comps = np.ascontiguousarray(comps, dtype=COMPONENT_DTYPE)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        n = len(offsets) - 1
+        cm = np.ascontiguousarray(np.broadcast_to(np.asarray(comp_mass, np.float32), (len(comps),)))
+        rest = np.ascontiguousarray(np.broadcast_to(np.asarray(restitution, np.float32), (n,)))
+        fric = np.ascontiguousarray(np.broadcast_to(np.asarray(friction, np.float32), (n,)))
+        force = np.ascontiguousarray(np.broadcast_to(np.asarray(world_force, np.float32), (n, 3)))
+        first = C.c_uint64()
+        _check(load_library().mgf_batch_add_compound_bodies(self._h, int(world), comps.ctypes.data, cm.ctypes.data, offsets.ctypes.data, n,
+                                                            rest.ctypes.data, fric.ctypes.data, force.ctypes.data, C.byref(first)))
         return first.value
 
     def __len__(self):

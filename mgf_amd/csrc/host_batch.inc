@@ -28,8 +28,13 @@ struct mgf_batch {
   mgf_ctx* ctx = nullptr;
   mgf_params params;
   uint32_t K = 0;
-  enum { AX, AQ, ASREC, ASP0, ASP1, ACTOR, AIMB, ADELTA, AFBC, AFBR, ACOL0, ACOL1, kArr };  // the persistent rows of Bodies (k_bodies.h), words of 16 bytes a body:
-  static constexpr int kWords[kArr] = {1, 1, 4, 1, 1, 1, 3, 1, 1, 1, 1, 1};
+  // the persistent rows of Bodies (k_bodies.h), words of 16 bytes a body; the last four - the local and the world parts, kMaxParts slots
+  // a body - exist only in a batch that holds a body of several components (`parts`, mgf_batch_add_compound_bodies)
+  enum { AX, AQ, ASREC, ASP0, ASP1, ACTOR, AIMB, ADELTA, AFBC, AFBR, ACOL0, ACOL1, ALP0, ALP1, AWP0, AWP1, kArr, kArrPlain = ALP0 };
+  static constexpr int kWords[kArr] = {1, 1, 4, 1, 1, 1, 3, 1, 1, 1, 1, 1, kMaxParts, kMaxParts, kMaxParts, kMaxParts};
+  bool parts = false;                // the batch has part rows: its tick is k_batch_parts.h's, the calls that read shapes are refused
+  int n_arr() const { return parts ? (int)kArr : (int)kArrPlain; }
+  DBuf<float4> pool;                 // ... and the kept contacts of its pairs of bodies, three words an entry, as many as constraint records
   std::vector<float4> hm[kArr];
   DBuf<float4> dm[kArr];
   DBuf<float4> bpk, undo;          // the tick's packed copy (4 a body); what a tick that did not fit puts back (7 a body)
@@ -109,6 +114,10 @@ struct mgf_batch {
     B.x = dm[AX].p + first; B.q = dm[AQ].p + first; B.srec = dm[ASREC].p + 4 * first; B.sp0 = dm[ASP0].p + first; B.sp1 = dm[ASP1].p + first;
     B.ctor = dm[ACTOR].p + first; B.imb = dm[AIMB].p + 3 * first; B.delta = dm[ADELTA].p + first; B.fb_c = dm[AFBC].p + first;
     B.fb_r = dm[AFBR].p + first; B.col0 = dm[ACOL0].p + first; B.col1 = dm[ACOL1].p + first; B.bpk = bpk.p + 4 * first;
+    if (parts) {
+      B.lp0 = dm[ALP0].p + kMaxParts * first; B.lp1 = dm[ALP1].p + kMaxParts * first;
+      B.wp0 = dm[AWP0].p + kMaxParts * first; B.wp1 = dm[AWP1].p + kMaxParts * first;
+    }
     return B;
   }
 };
@@ -144,7 +153,7 @@ static mgf_status batch_pull(mgf_batch* b) {
   if (!b->dev_valid) return MGF_OK;
   MGF_TRY(batch_cols_refresh(b, nullptr));
   const size_t n = b->total();
-  for (int a = 0; a < mgf_batch::kArr; ++a) {
+  for (int a = 0; a < b->n_arr(); ++a) {
     b->hm[a].resize(n * mgf_batch::kWords[a]);
     MGF_TRY(d2h(b->ctx, b->hm[a].data(), b->dm[a].p, b->hm[a].size()));
   }
@@ -192,6 +201,7 @@ static mgf_status batch_allot(mgf_batch* b, bool keep) {
   std::swap(b->d_coff.p, ncoff.p); std::swap(b->d_coff.cap, ncoff.cap);
   MGF_TRY(b->rows.ensure(std::max<size_t>(coff[b->K], 1), s));
   MGF_TRY(b->cont.ensure(4 * std::max<size_t>(coff[b->K], 1), s));
+  if (b->parts) MGF_TRY(b->pool.ensure(3 * std::max<size_t>(coff[b->K], 1), s));
   MGF_TRY(b->cand.ensure(std::max<size_t>(qoff[b->K], 1), s));
   MGF_TRY(b->ncq.ensure(std::max<size_t>(qoff[b->K], 1), s)); MGF_TRY(b->slot.ensure(6 * std::max<size_t>(qoff[b->K], 1), s));
   MGF_TRY(b->d_qoff.ensure(b->K + 1, s)); MGF_TRY(b->d_qcap.ensure(std::max<size_t>(b->K, 1), s)); MGF_TRY(b->d_qcount.ensure(std::max<size_t>(b->K, 1), s));
@@ -210,7 +220,7 @@ static mgf_status batch_push(mgf_batch* b) {
   hipStream_t s = ctx->stream;
   batch_offsets(b);
   const size_t n = b->total();
-  for (int a = 0; a < mgf_batch::kArr; ++a) {
+  for (int a = 0; a < b->n_arr(); ++a) {
     MGF_TRY(b->dm[a].ensure(std::max<size_t>(n * mgf_batch::kWords[a], 1), s));
     MGF_TRY(h2d(ctx, b->dm[a].p, b->hm[a].data(), n * mgf_batch::kWords[a]));
   }
@@ -277,7 +287,7 @@ extern "C" mgf_status mgf_batch_set_option(mgf_batch* b, const char* key, int64_
 }
 extern "C" mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out) {
   if (!b || !name || !out) return fail(MGF_ERR_INVALID, "NULL argument");
-  if (!strcmp(name, "launches_per_tick")) { *out = 6; return MGF_OK; }
+  if (!strcmp(name, "launches_per_tick")) { *out = b->parts ? 7 : 6; return MGF_OK; }
   if (!strcmp(name, "capacity_retries")) { *out = b->capacity_retries; return MGF_OK; }
   if (!strcmp(name, "query_launches")) { *out = b->q_launches; return MGF_OK; }
   if (!strcmp(name, "query_run_ns")) { *out = (int64_t)((double)b->q_run_ms * 1e6); return MGF_OK; }
@@ -520,6 +530,58 @@ static void batch_rigs_stale(mgf_batch* b) {
   b->zones.stale = true;
 }
 
+// the rows of `n` new bodies (empty part slots where the caller has filled none) behind world k's last body
+static mgf_status batch_insert(mgf_batch* b, uint32_t k, const std::vector<float4>* add, size_t n) {
+  const size_t at = b->h_off[k + 1];
+  for (int a = 0; a < b->n_arr(); ++a) b->hm[a].insert(b->hm[a].begin() + at * mgf_batch::kWords[a], add[a].begin(), add[a].end());
+  b->h_n[k] += (uint32_t)n;
+  batch_offsets(b);
+  std::fill(b->h_ccount.begin(), b->h_ccount.end(), 0u);
+  b->ccount_stale = false;
+  return MGF_OK;
+}
+// The rows of one ordinary body (RigidBodyVec::add_body physics.rs:200-218, World::add_body world.rs:178-184) into slot i of `add`.
+static mgf_status batch_body_rows(const mgf_batch* b, const mgf_component& mc, float mass, float restitution, float friction, const mgf_vec3& world_force,
+                                  std::vector<float4>* add, size_t i) {
+  Comp c = comp_of(mc);
+  if (c.kind == KIND_SPHERE) c.d = mk3(0, 0, 0);
+  // Component::deconstruct compound.rs:42-52
+  V3 px; Quat pq; float half_h = 0.0f;
+  if (c.kind == KIND_SPHERE) { px = c.p; pq = mkq(1.0f, mk3(0, 0, 0)); }
+  else {
+    const float h = mag(c.d);
+    pq = quat_from_arc(mk3(0.0f, 1.0f, 0.0f) * h, c.d);
+    px = c.p + c.d * 0.5f;
+    half_h = h * 0.5f;
+  }
+  Comp local = c; local.p = c.p + -px;  // collider - x.to_vec()
+  M3 inv;
+  if (!invert(tensor_of(local, mass), &inv)) return fail(MGF_ERR_SINGULAR, "inertia tensor is not invertible (physics.rs:212)");
+  const float inv_mass = 1.0f / mass;
+  const V3 force = mk3(world_force.x, world_force.y, world_force.z) * mass;
+  add[mgf_batch::AX][i] = make_float4(px.x, px.y, px.z, 0.0f);
+  add[mgf_batch::AQ][i] = make_float4(pq.s, pq.v.x, pq.v.y, pq.v.z);
+  float4* sr = &add[mgf_batch::ASREC][4 * i];
+  sr[0] = make_float4(0, 0, 0, 0);
+  sr[1] = make_float4(0, 0, inv_mass, inv.c[0].x);
+  sr[2] = make_float4(inv.c[0].y, inv.c[0].z, inv.c[1].x, inv.c[1].y);
+  sr[3] = make_float4(inv.c[1].z, inv.c[2].x, inv.c[2].y, inv.c[2].z);
+  add[mgf_batch::ASP0][i] = make_float4(force.x, force.y, force.z, restitution);
+  add[mgf_batch::ASP1][i] = make_float4(0, 0, 0, friction);
+  const uint32_t kind_bits = (uint32_t)c.kind;
+  float kf; memcpy(&kf, &kind_bits, 4);
+  add[mgf_batch::ACTOR][i] = make_float4(kf, c.r, half_h, 0.0f);
+  for (int col = 0; col < 3; ++col) add[mgf_batch::AIMB][3 * i + col] = make_float4(inv.c[col].x, inv.c[col].y, inv.c[col].z, 0.0f);
+  add[mgf_batch::ADELTA][i] = make_float4(0, 0, 0, friction);
+  const Box tb = swept_bounds(c, mk3(0, 0, 0));
+  const V3 fr = tb.r + mk3(b->params.fat_margin, b->params.fat_margin, b->params.fat_margin);
+  add[mgf_batch::AFBC][i] = make_float4(tb.c.x, tb.c.y, tb.c.z, 0.0f);
+  add[mgf_batch::AFBR][i] = make_float4(fr.x, fr.y, fr.z, 0.0f);
+  add[mgf_batch::ACOL0][i] = make_float4(c.p.x, c.p.y, c.p.z, c.r);  // (what a query sees until a tick has run on the body)
+  add[mgf_batch::ACOL1][i] = make_float4(c.d.x, c.d.y, c.d.z, kf);
+  return MGF_OK;
+}
+
 extern "C" mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mgf_component* comps, int64_t n, const float* mass, const float* restitution,
                                            const float* friction, const mgf_vec3* world_force, uint64_t* first_id) {
   if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
@@ -540,51 +602,130 @@ extern "C" mgf_status mgf_batch_add_bodies(mgf_batch* b, int64_t world, const mg
   const size_t N = (size_t)n;
   std::vector<float4> add[mgf_batch::kArr];
   for (int a = 0; a < mgf_batch::kArr; ++a) add[a].resize(N * mgf_batch::kWords[a]);
-  for (size_t i = 0; i < N; ++i) {
-    Comp c = comp_of(comps[i]);
-    if (c.kind == KIND_SPHERE) c.d = mk3(0, 0, 0);
-    // Component::deconstruct compound.rs:42-52
-    V3 px; Quat pq; float half_h = 0.0f;
-    if (c.kind == KIND_SPHERE) { px = c.p; pq = mkq(1.0f, mk3(0, 0, 0)); }
-    else {
-      const float h = mag(c.d);
-      pq = quat_from_arc(mk3(0.0f, 1.0f, 0.0f) * h, c.d);
-      px = c.p + c.d * 0.5f;
-      half_h = h * 0.5f;
+  for (size_t i = 0; i < N; ++i) MGF_TRY(batch_body_rows(b, comps[i], mass[i], restitution[i], friction[i], world_force[i], add, i));
+  MGF_TRY(batch_pull(b));
+  MGF_TRY(batch_insert(b, k, add, N));
+  batch_rigs_stale(b);
+  return MGF_OK;
+}
+
+// The batch gets part rows - empty slots for the bodies it holds, all of them ordinary - where its state is: in the mirror, or on the
+// device behind whatever the stream still runs.  From here on its tick is k_batch_parts.h's.
+static mgf_status batch_parts_enable(mgf_batch* b) {
+  if (b->parts) return MGF_OK;
+  hipStream_t s = b->ctx->stream;
+  const size_t words = (size_t)kMaxParts * b->total();
+  for (int a = mgf_batch::kArrPlain; a < mgf_batch::kArr; ++a) {
+    if (b->dev_valid) {
+      MGF_TRY(b->dm[a].ensure(std::max<size_t>(words, 1), s));
+      MGF_HIP_TRY(hipMemsetAsync(b->dm[a].p, 0, 16 * words, s));
+    } else {
+      b->hm[a].assign(words, make_float4(0, 0, 0, 0));
     }
-    Comp local = c; local.p = c.p + -px;  // collider - x.to_vec()
+  }
+  if (b->dev_valid) MGF_TRY(b->pool.ensure(3 * std::max<size_t>(b->h_coff.empty() ? 0 : b->h_coff[b->K], 1), s));
+  b->parts = true;
+  return MGF_OK;
+}
+// the calls that read the shapes of bodies do not see parts yet: refused on a batch that holds a body of several components
+static mgf_status batch_single_parts(const mgf_batch* b, const char* call) {
+  if (!b->parts) return MGF_OK;
+  return fail(MGF_ERR_INVALID, (std::string(call) + ": the batch holds bodies of several components, which this call does not see yet").c_str());
+}
+
+// Bodies of 1..4 components for one world of the batch, as mgf_world_add_compound_bodies (the oracle's RigidBodyVec::add_compound_body:
+// mass = sum, x = centre of mass, q = identity, tensor = sum of the components' tensors about the centre of mass, parts fixed in the
+// body frame).  A body of one component is the ordinary body mgf_batch_add_bodies adds, with the component's mass.
+extern "C" mgf_status mgf_batch_add_compound_bodies(mgf_batch* b, int64_t world, const mgf_component* comps, const float* comp_mass, const int64_t* offsets, int64_t n,
+                                                    const float* restitution, const float* friction, const mgf_vec3* world_force, uint64_t* first_id) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (!comps || !offsets || !first_id) return fail(MGF_ERR_INVALID, "NULL argument");
+  if (n < 0) return fail(MGF_ERR_INVALID, "n is negative");
+  if (n && (!comp_mass || !restitution || !friction || !world_force)) return fail(MGF_ERR_INVALID, "NULL argument");
+  if (world < 0) return fail(MGF_ERR_INVALID, "world index out of range");
+  if (n > MGF_BATCH_MAX_BODIES) return fail(MGF_ERR_INVALID, "a world of a batch holds at most MGF_BATCH_MAX_BODIES (1024) bodies");
+  if (offsets[0] != 0) return fail(MGF_ERR_INVALID, "offsets[0] must be 0");
+  bool several = false;
+  for (int64_t r = 0; r < n; ++r) {
+    const int64_t cnt = offsets[r + 1] - offsets[r];
+    if (cnt < 1 || cnt > kMaxParts)
+      return fail(MGF_ERR_INVALID, "a body of a batch needs 1..4 components (the batch takes four, the lone world 32): nothing was added");
+    several = several || cnt > 1;
+  }
+  for (int64_t c = 0; c < offsets[n]; ++c) {
+    if (comps[c].tag != MGF_SPHERE && comps[c].tag != MGF_CAPSULE) return fail(MGF_ERR_INVALID, "component tag must be sphere (0) or capsule (1)");
+    if (!(comps[c].r > 0.0f)) return fail(MGF_ERR_INVALID, "radius must be > 0 (geom.rs:300,328)");
+  }
+  MGF_TRY(ctx_bind(b->ctx));
+  if (world >= (int64_t)b->K) return fail(MGF_ERR_INVALID, "world index out of range");
+  const uint32_t k = (uint32_t)world;
+  if ((int64_t)b->h_n[k] + n > MGF_BATCH_MAX_BODIES) return fail(MGF_ERR_INVALID, "a world of a batch holds at most MGF_BATCH_MAX_BODIES (1024) bodies: nothing was added");
+  *first_id = b->h_n[k];
+  if (n == 0) return MGF_OK;
+  const size_t N = (size_t)n;
+  std::vector<float4> add[mgf_batch::kArr];
+  for (int a = 0; a < mgf_batch::kArr; ++a) add[a].resize(N * mgf_batch::kWords[a]);
+  const V3 fm = mk3(b->params.fat_margin, b->params.fat_margin, b->params.fat_margin);
+  for (size_t r = 0; r < N; ++r) {
+    const int64_t k0 = offsets[r], k1 = offsets[r + 1];
+    if (k1 - k0 == 1) {
+      MGF_TRY(batch_body_rows(b, comps[k0], comp_mass[k0], restitution[r], friction[r], world_force[r], add, r));
+      continue;
+    }
+    Comp part[kMaxParts];  // (mgf_world_add_compound_bodies, operation for operation)
+    float total = 0.0f;
+    V3 acc = mk3(0, 0, 0);
+    for (int64_t c = k0; c < k1; ++c) {
+      Comp p = comp_of(comps[c]);
+      if (p.kind == KIND_SPHERE) p.d = mk3(0, 0, 0);
+      part[c - k0] = p;
+      total += comp_mass[c];
+      acc = acc + comp_center(p) * comp_mass[c];
+    }
+    const V3 com = acc / total;
+    M3 t = m3_cols(mk3(0, 0, 0), mk3(0, 0, 0), mk3(0, 0, 0));
+    for (int64_t c = k0; c < k1; ++c) { Comp l = part[c - k0]; l.p = l.p + -com; t = t + tensor_of(l, comp_mass[c]); }
     M3 inv;
-    if (!invert(tensor_of(local, mass[i]), &inv)) return fail(MGF_ERR_SINGULAR, "inertia tensor is not invertible (physics.rs:212)");
-    const float inv_mass = 1.0f / mass[i];
-    const V3 force = mk3(world_force[i].x, world_force[i].y, world_force[i].z) * mass[i];
-    add[mgf_batch::AX][i] = make_float4(px.x, px.y, px.z, 0.0f);
-    add[mgf_batch::AQ][i] = make_float4(pq.s, pq.v.x, pq.v.y, pq.v.z);
-    float4* sr = &add[mgf_batch::ASREC][4 * i];
+    if (!invert(t, &inv)) return fail(MGF_ERR_SINGULAR, "inertia tensor is not invertible");
+    const float inv_mass = 1.0f / total;
+    const V3 force = mk3(world_force[r].x, world_force[r].y, world_force[r].z) * total;
+    add[mgf_batch::AX][r] = make_float4(com.x, com.y, com.z, 0.0f);
+    add[mgf_batch::AQ][r] = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+    float4* sr = &add[mgf_batch::ASREC][4 * r];
     sr[0] = make_float4(0, 0, 0, 0);
     sr[1] = make_float4(0, 0, inv_mass, inv.c[0].x);
     sr[2] = make_float4(inv.c[0].y, inv.c[0].z, inv.c[1].x, inv.c[1].y);
     sr[3] = make_float4(inv.c[1].z, inv.c[2].x, inv.c[2].y, inv.c[2].z);
-    add[mgf_batch::ASP0][i] = make_float4(force.x, force.y, force.z, restitution[i]);
-    add[mgf_batch::ASP1][i] = make_float4(0, 0, 0, friction[i]);
-    const uint32_t kind_bits = (uint32_t)c.kind;
-    float kf; memcpy(&kf, &kind_bits, 4);
-    add[mgf_batch::ACTOR][i] = make_float4(kf, c.r, half_h, 0.0f);
-    for (int col = 0; col < 3; ++col) add[mgf_batch::AIMB][3 * i + col] = make_float4(inv.c[col].x, inv.c[col].y, inv.c[col].z, 0.0f);
-    add[mgf_batch::ADELTA][i] = make_float4(0, 0, 0, friction[i]);
-    const Box tb = swept_bounds(c, mk3(0, 0, 0));
-    const V3 fr = tb.r + mk3(b->params.fat_margin, b->params.fat_margin, b->params.fat_margin);
-    add[mgf_batch::AFBC][i] = make_float4(tb.c.x, tb.c.y, tb.c.z, 0.0f);
-    add[mgf_batch::AFBR][i] = make_float4(fr.x, fr.y, fr.z, 0.0f);
-    add[mgf_batch::ACOL0][i] = make_float4(c.p.x, c.p.y, c.p.z, c.r);  // (what a query sees until a tick has run on the body)
-    add[mgf_batch::ACOL1][i] = make_float4(c.d.x, c.d.y, c.d.z, kf);
+    add[mgf_batch::ASP0][r] = make_float4(force.x, force.y, force.z, restitution[r]);
+    add[mgf_batch::ASP1][r] = make_float4(0, 0, 0, friction[r]);
+    const uint32_t kind_bits = 2u, cnt_bits = (uint32_t)(k1 - k0);  // constructor kind: a body of several parts, and how many (batch_np, k_batch_parts.h)
+    float kf, cf; memcpy(&kf, &kind_bits, 4); memcpy(&cf, &cnt_bits, 4);
+    add[mgf_batch::ACTOR][r] = make_float4(kf, cf, 0.0f, 0.0f);
+    for (int col = 0; col < 3; ++col) add[mgf_batch::AIMB][3 * r + col] = make_float4(inv.c[col].x, inv.c[col].y, inv.c[col].z, 0.0f);
+    add[mgf_batch::ADELTA][r] = make_float4(0, 0, 0, friction[r]);
+    const uint32_t sph = (uint32_t)KIND_SPHERE; float sf; memcpy(&sf, &sph, 4);
+    add[mgf_batch::ACOL0][r] = make_float4(com.x, com.y, com.z, 0.0f);  // the carrier: a radius-0 sphere at the centre of mass
+    add[mgf_batch::ACOL1][r] = make_float4(0, 0, 0, sf);
+    Box tb;
+    for (int64_t c = k0; c < k1; ++c) {
+      const Comp& p = part[c - k0];
+      const uint32_t kb = (uint32_t)p.kind; float kbf; memcpy(&kbf, &kb, 4);
+      const V3 lp = p.p + -com;
+      const size_t at = (size_t)kMaxParts * r + (size_t)(c - k0);
+      add[mgf_batch::ALP0][at] = make_float4(lp.x, lp.y, lp.z, p.r);
+      add[mgf_batch::ALP1][at] = make_float4(p.d.x, p.d.y, p.d.z, kbf);
+      add[mgf_batch::AWP0][at] = make_float4(p.p.x, p.p.y, p.p.z, p.r);
+      add[mgf_batch::AWP1][at] = make_float4(p.d.x, p.d.y, p.d.z, kbf);
+      const Box pb = swept_bounds(p, mk3(0, 0, 0));
+      tb = c == k0 ? pb : box_combine(tb, pb);
+    }
+    const V3 frr = tb.r + fm;
+    add[mgf_batch::AFBC][r] = make_float4(tb.c.x, tb.c.y, tb.c.z, 0.0f);
+    add[mgf_batch::AFBR][r] = make_float4(frr.x, frr.y, frr.z, 0.0f);
   }
   MGF_TRY(batch_pull(b));
-  const size_t at = b->h_off[k + 1];  // behind the world's last body
-  for (int a = 0; a < mgf_batch::kArr; ++a) b->hm[a].insert(b->hm[a].begin() + at * mgf_batch::kWords[a], add[a].begin(), add[a].end());
-  b->h_n[k] += (uint32_t)n;
-  batch_offsets(b);
-  std::fill(b->h_ccount.begin(), b->h_ccount.end(), 0u);
-  b->ccount_stale = false;
+  if (several) MGF_TRY(batch_parts_enable(b));
+  MGF_TRY(batch_insert(b, k, add, N));
   batch_rigs_stale(b);
   return MGF_OK;
 }
@@ -649,6 +790,39 @@ extern "C" mgf_status mgf_batch_write_state(mgf_batch* b, int64_t world, const m
   return MGF_OK;
 }
 
+// The launches of a tick ahead of k_batch_setup and k_batch_solve, a workgroup per world each: the four of a batch of ordinary bodies ...
+static mgf_status batch_collide(mgf_batch* b, const BatchArgs& A, uint32_t nmax) {
+  hipStream_t s = b->ctx->stream;
+  const uint32_t K = b->K;
+  k_batch_front<<<K, kBatchBlock, 68u * nmax, s>>>(A);
+  LAUNCH_CHECK();
+  k_batch_faces<<<K, kBatchBlock, 0, s>>>(A);
+  LAUNCH_CHECK();
+  k_batch_pairs<<<K, kBatchBlock, 0, s>>>(A);
+  LAUNCH_CHECK();
+  k_batch_pack<<<K, kBatchBlock, 0, s>>>(A);
+  LAUNCH_CHECK();
+  return MGF_OK;
+}
+// ... and the five of a batch that holds bodies of several components (k_batch_parts.h)
+static mgf_status batch_collide_parts(mgf_batch* b, const BatchArgs& A, uint32_t nmax) {
+  hipStream_t s = b->ctx->stream;
+  const uint32_t K = b->K;
+  BatchPartsArgs PA;
+  PA.A = A; PA.pool = b->pool.p;
+  k_batch_parts_front<<<K, kBatchBlock, 68u * nmax, s>>>(A);
+  LAUNCH_CHECK();
+  k_batch_parts_faces<<<K, kBatchBlock, 0, s>>>(A);
+  LAUNCH_CHECK();
+  k_batch_parts_obst<<<K, kBatchBlock, 0, s>>>(A);
+  LAUNCH_CHECK();
+  k_batch_parts_pairs<<<K, kBatchBlock, 0, s>>>(PA);
+  LAUNCH_CHECK();
+  k_batch_parts_pack<<<K, kBatchBlock, 0, s>>>(PA);
+  LAUNCH_CHECK();
+  return MGF_OK;
+}
+
 // n_ticks x World::step (world.rs:227-294) of every world: one launch per tick, no host wait between the ticks.
 extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats) {
   if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
@@ -666,11 +840,12 @@ extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int6
   const uint32_t lds = 80u * nmax;  // k_batch_solve: 64 bytes a body of solver records, four words of counts (k_batch_front: 64 + 4, k_batch_setup: 12)
   if (lds > b->lds_set) {
     MGF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch_front), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(68u * MGF_BATCH_MAX_BODIES)));
+    MGF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch_parts_front), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(68u * MGF_BATCH_MAX_BODIES)));
     MGF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(80u * MGF_BATCH_MAX_BODIES)));
     b->lds_set = 80u * MGF_BATCH_MAX_BODIES;
   }
   MGF_TRY(b->d_stats.ensure((size_t)NT * K * 8, s));
-  b->cols_stale = true;  // (the tick's six launches stay as they are: the colliders are gathered before the first reader)
+  b->cols_stale = true;  // (the tick's launches - six, seven with bodies of several components - stay as they are: the colliders are gathered before the first reader)
   MGF_HIP_TRY(hipMemsetAsync(b->d_done.p, 0, 4 * (size_t)K, s));
   MGF_HIP_TRY(hipMemsetAsync(b->d_need.p, 0, 8 * (size_t)K, s));
   MGF_HIP_TRY(hipMemsetAsync(b->d_stage.p, 0, 4 * (size_t)K, s));
@@ -691,14 +866,8 @@ extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int6
     A.dt = dt; A.fat_margin = b->params.fat_margin; A.baumgarte = b->params.baumgarte; A.slop = b->params.penetration_slop;
     for (uint32_t t = first; t < NT; ++t) {
       A.tick = t;
-      k_batch_front<<<K, kBatchBlock, 68u * nmax, s>>>(A);
-      LAUNCH_CHECK();
-      k_batch_faces<<<K, kBatchBlock, 0, s>>>(A);
-      LAUNCH_CHECK();
-      k_batch_pairs<<<K, kBatchBlock, 0, s>>>(A);
-      LAUNCH_CHECK();
-      k_batch_pack<<<K, kBatchBlock, 0, s>>>(A);
-      LAUNCH_CHECK();
+      if (b->parts) MGF_TRY(batch_collide_parts(b, A, nmax));
+      else MGF_TRY(batch_collide(b, A, nmax));
       k_batch_setup<<<K, kBatchBlock, 12u * nmax, s>>>(A);
       LAUNCH_CHECK();
       k_batch_solve<<<K, kBatchBlock, lds, s>>>(A);

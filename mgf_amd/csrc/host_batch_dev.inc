@@ -186,6 +186,7 @@ extern "C" mgf_status mgf_batch_copy_worlds_where(mgf_batch* dst, const int32_t*
   k_batch_dev_copy_where<<<(unsigned)n, kBatchBlock, 0, s>>>(A);
   LAUNCH_CHECK();
   ++dst->d_launches;
+  MGF_TRY(batch_copy_parts(dst, src, dst->w_pairs_d.p, n, mask_dev));
   dst->ccount_stale = true;
   return MGF_OK;
 }

@@ -169,6 +169,7 @@ static mgf_status batch_copy_check(mgf_batch* dst, const int32_t* dst_world, con
 static mgf_status batch_copy_open(mgf_batch* dst, const int32_t* dst_world, mgf_batch* src, const int32_t* src_world, size_t n) {
   MGF_TRY(batch_push(src));
   MGF_TRY(batch_push(dst));
+  if (src->parts) MGF_TRY(batch_parts_enable(dst));  // (a destination of ordinary bodies gets part rows before anything of the copy is enqueued)
   MGF_TRY(batch_ccount_fresh(src));  // (behind a masked copy into `src`, host_batch_dev.inc)
   bool grow = false;
   const std::vector<uint32_t> floor_was = dst->h_floor;
@@ -196,6 +197,21 @@ static BatchCopyArgs batch_copy_args(const mgf_batch* dst, const mgf_batch* src,
   return A;
 }
 
+// the part rows of the copied worlds, behind the copy's own launch: a clone of a world of bodies of several components has its parts,
+// and a world of ordinary bodies copied over one has none (a batch without part rows has neither: no launch)
+static mgf_status batch_copy_parts(mgf_batch* dst, const mgf_batch* src, const uint2* pairs, size_t n, const int32_t* mask) {
+  if (!dst->parts) return MGF_OK;
+  BatchPartsCopyArgs A;
+  memset(&A, 0, sizeof(A));
+  A.D = dst->bodies(0); A.S = src->bodies(0);
+  A.s_parts = src->parts ? 1u : 0u;
+  A.pairs = pairs; A.d_off = dst->d_off.p; A.s_off = src->d_off.p; A.mask = mask;
+  k_batch_parts_copy<<<(unsigned)n, kBatchBlock, 0, dst->ctx->stream>>>(A);
+  LAUNCH_CHECK();
+  ++dst->d_launches;
+  return MGF_OK;
+}
+
 extern "C" mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_world, const mgf_batch* src_in, const int32_t* src_world, int64_t n_in) {
   MGF_TRY(batch_copy_check(dst, dst_world, src_in, src_world, n_in));
   mgf_batch* src = const_cast<mgf_batch*>(src_in);  // (its mirror may have to go up, its colliders are read where they are: nothing of its state changes)
@@ -212,6 +228,7 @@ extern "C" mgf_status mgf_batch_copy_worlds(mgf_batch* dst, const int32_t* dst_w
   k_batch_drive_copy<<<(unsigned)n, kBatchBlock, 0, s>>>(A);
   LAUNCH_CHECK();
   ++dst->d_launches;
+  MGF_TRY(batch_copy_parts(dst, src, A.pairs, n, nullptr));
   MGF_HIP_TRY(hipStreamSynchronize(s));  // (`pairs` is read by the copy until here)
   for (size_t i = 0; i < n; ++i) dst->h_ccount[(size_t)dst_world[i]] = src->h_ccount[(size_t)src_world[i]];
   return MGF_OK;

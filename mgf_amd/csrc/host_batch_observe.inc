@@ -46,6 +46,7 @@ extern "C" mgf_status mgf_batch_overlap_aabb_many(mgf_batch* b, const int32_t* w
   MGF_TRY(batch_query_worlds(world, n_in, "too many boxes in one call"));
   static_assert(sizeof(mgf_aabb) == 24, "k_batch_observe_overlap reads mgf_aabb as six words");
   const size_t n = (size_t)n_in;
+  MGF_TRY(batch_single_parts(b, "mgf_batch_overlap_aabb_many"));
   MGF_TRY(batch_query_open(b, world, n));
   out_offsets[0] = 0;
   if (total) *total = 0;

@@ -155,6 +155,7 @@ static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* q
   constexpr bool kRays = std::is_same<Q, ParticleIn>::value;
   constexpr size_t kOut = kRays ? 7 : 13;
   const size_t n = (size_t)n_in;
+  MGF_TRY(batch_single_parts(b, "mgf_batch_raycast_many / mgf_batch_sweep_many"));
   MGF_TRY(batch_query_open(b, world, n));
   if (n == 0) return MGF_OK;
   hipStream_t s = b->ctx->stream;

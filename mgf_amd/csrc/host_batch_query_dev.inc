@@ -42,6 +42,7 @@ static mgf_status batch_query_dev_run(mgf_batch* b, const int32_t* world_dev, co
   if (n_in && (!q_dev || !out_dev)) return fail(MGF_ERR_INVALID, "NULL argument");
   MGF_TRY(query_mask_check(kinds_mask));
   const size_t n = (size_t)n_in;
+  MGF_TRY(batch_single_parts(b, "mgf_batch_raycast_many_dev / mgf_batch_sweep_many_dev"));
   MGF_TRY(ctx_bind(b->ctx));
   if (!world_dev && n % b->K) return fail(MGF_ERR_INVALID, "without world indices n is a multiple of the number of worlds");
   MGF_TRY(dev_span(b->ctx, world_dev, 4 * n, "world_dev"));

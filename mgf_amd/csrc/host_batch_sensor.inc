@@ -65,6 +65,7 @@ static mgf_status batch_sensor_args(const mgf_batch* b, int32_t kinds_mask, cons
 extern "C" mgf_status mgf_batch_cast_sensors(mgf_batch* b, int32_t kinds_mask, mgf_ray_hit* out, mgf_particle* parts_out, int64_t cap) {
   size_t n = 0;
   MGF_TRY(batch_sensor_args(b, kinds_mask, out, cap, &n));
+  MGF_TRY(batch_single_parts(b, "mgf_batch_cast_sensors"));
   MGF_TRY(ctx_bind(b->ctx));
   batch_call_begin(b);
   if (n == 0) return MGF_OK;
@@ -81,6 +82,7 @@ extern "C" mgf_status mgf_batch_cast_sensors(mgf_batch* b, int32_t kinds_mask, m
 extern "C" mgf_status mgf_batch_cast_sensors_dev(mgf_batch* b, int32_t kinds_mask, mgf_ray_hit* out_dev, mgf_particle* parts_out_dev, int64_t cap) {
   size_t n = 0;
   MGF_TRY(batch_sensor_args(b, kinds_mask, out_dev, cap, &n));
+  MGF_TRY(batch_single_parts(b, "mgf_batch_cast_sensors_dev"));
   MGF_TRY(ctx_bind(b->ctx));
   MGF_TRY(dev_span(b->ctx, out_dev, 28 * n, "out_dev"));
   MGF_TRY(dev_span(b->ctx, parts_out_dev, 28 * n, "parts_out_dev"));

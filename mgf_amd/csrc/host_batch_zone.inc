@@ -76,6 +76,7 @@ static mgf_status batch_zone_read_args(const mgf_batch* b, int32_t k, const void
 extern "C" mgf_status mgf_batch_read_zones(mgf_batch* b, int32_t k, int32_t* out, mgf_aabb* boxes_out, int64_t cap) {
   size_t n = 0;
   MGF_TRY(batch_zone_read_args(b, k, out, cap, &n));
+  MGF_TRY(batch_single_parts(b, "mgf_batch_read_zones"));
   MGF_TRY(ctx_bind(b->ctx));
   batch_call_begin(b);
   if (n == 0) return MGF_OK;
@@ -100,6 +101,7 @@ extern "C" mgf_status mgf_batch_read_zones(mgf_batch* b, int32_t k, int32_t* out
 extern "C" mgf_status mgf_batch_read_zones_dev(mgf_batch* b, int32_t k, int32_t* out_dev, mgf_aabb* boxes_out_dev, int64_t cap) {
   size_t n = 0;
   MGF_TRY(batch_zone_read_args(b, k, out_dev, cap, &n));
+  MGF_TRY(batch_single_parts(b, "mgf_batch_read_zones_dev"));
   MGF_TRY(ctx_bind(b->ctx));
   const size_t out_bytes = 4 * ((size_t)k + 1) * n;
   MGF_TRY(dev_span(b->ctx, out_dev, out_bytes, "out_dev"));
@@ -120,6 +122,7 @@ extern "C" mgf_status mgf_batch_overlap_first_dev(mgf_batch* b, const mgf_aabb* 
   MGF_TRY(zone_k_check(k));
   static_assert(sizeof(mgf_aabb) == 24, "k_batch_zone_first reads mgf_aabb as six words");
   const size_t n = (size_t)n_in;
+  MGF_TRY(batch_single_parts(b, "mgf_batch_overlap_first_dev"));
   MGF_TRY(ctx_bind(b->ctx));
   if (n % b->K) return fail(MGF_ERR_INVALID, "n is a multiple of the number of worlds");
   const size_t out_bytes = 4 * ((size_t)k + 1) * n;

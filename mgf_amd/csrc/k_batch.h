@@ -22,6 +22,8 @@
 //                   which is all the sequential sweep defines)
 // A world whose share of the candidate or constraint storage is too small for the tick puts its bodies back as the tick found them
 // (TickUndo) and leaves its tick counter where it was; the host grows the share and runs the tick again (counter "capacity_retries").
+// A batch that holds bodies of several components (mgf_batch_add_compound_bodies) runs k_batch_parts.h's front, faces, obstacle, pair and
+// pack launches in the first four's places; the kernels here are its tick's last two, and the whole tick of every other batch.
 #pragma once
 #include "k_api.h"
 

@@ -362,11 +362,17 @@ __device__ __forceinline__ LocalContact parts_local(const PairCentres& P, const 
   LocalContact nc; nc.la = c.a + -(P.ci + P.vA * c.t); nc.lb = c.b + -(P.cj + P.vB * c.t); nc.g = c;
   return nc;
 }
-__device__ __forceinline__ int parts_prune(const PairCentres& P, const NContact* mine, uint32_t* keep_out, float* min_t_out, V3* normal) {
+// Written once for every caller: SLOTS raw slots a pair, BITS bits of slot number per kept contact in a word of type Keep (SLOTS * BITS
+// bits) - 4 slots of 2 bits in 32 for the bodies of up to two components here (parts_prune), 16 slots of 4 bits in 64 for the batch's
+// bodies of up to four (k_batch_parts_pairs, k_batch_parts.h: slot = 4 a + b, an absent part pair an empty slot).
+template <uint32_t SLOTS, uint32_t BITS, class Keep>
+__device__ __forceinline__ int parts_prune_n(const PairCentres& P, const NContact* mine, Keep* keep_out, float* min_t_out, V3* normal) {
+  static_assert(SLOTS * BITS <= 8 * sizeof(Keep) && SLOTS <= (1u << BITS), "a kept contact is a slot number of BITS bits");
+  constexpr Keep kMask = (Keep)((1u << BITS) - 1u);
   float min_t = kInf;
   int cnt = 0;
-  uint32_t keep = 0u;  // (keep >> 2k) & 3: the slot of the k-th kept contact
-  for (uint32_t slot = 0; slot < 4u; ++slot) {
+  Keep keep = 0;  // (keep >> BITS k) & kMask: the slot of the k-th kept contact
+  for (uint32_t slot = 0; slot < SLOTS; ++slot) {
     const NContact raw = mine[slot];
     if (raw.lb.w == 0.0f) continue;
     const LocalContact nc = parts_local(P, raw);
@@ -374,23 +380,26 @@ __device__ __forceinline__ int parts_prune(const PairCentres& P, const NContact*
     if (nc.g.t > min_t + kCollisionEps) continue;
     bool merged = false;
     for (int k = 0; k < cnt && !merged; ++k) {
-      const LocalContact kc = parts_local(P, mine[(keep >> (2 * k)) & 3u]);
+      const LocalContact kc = parts_local(P, mine[(uint32_t)((keep >> (BITS * k)) & kMask)]);
       const V3 ra = nc.g.a - kc.g.a, rb = nc.g.b - kc.g.b;
       if (mag2(ra) <= kPersistentThresholdSq || mag2(rb) <= kPersistentThresholdSq) {
         const float prev = mag2(kc.la) + mag2(kc.lb), cur = mag2(nc.la) + mag2(nc.lb);
-        if (prev < cur) keep = (keep & ~(3u << (2 * k))) | (slot << (2 * k));
+        if (prev < cur) keep = (keep & ~(kMask << (BITS * k))) | ((Keep)slot << (BITS * k));
         merged = true;
       }
     }
-    if (!merged) { keep = (keep & ~(3u << (2 * cnt))) | (slot << (2 * cnt)); ++cnt; }
+    if (!merged) { keep = (keep & ~(kMask << (BITS * cnt))) | ((Keep)slot << (BITS * cnt)); ++cnt; }
   }
   if (cnt) {
     V3 sum = mk3(0.0f, 0.0f, 0.0f);
-    for (int k = 0; k < cnt; ++k) sum = sum + xyz(mine[(keep >> (2 * k)) & 3u].n);
+    for (int k = 0; k < cnt; ++k) sum = sum + xyz(mine[(uint32_t)((keep >> (BITS * k)) & kMask)].n);
     *normal = sum / (float)cnt;
   }
   *keep_out = keep; *min_t_out = min_t;
   return cnt;
+}
+__device__ __forceinline__ int parts_prune(const PairCentres& P, const NContact* mine, uint32_t* keep_out, float* min_t_out, V3* normal) {
+  return parts_prune_n<4u, 2u, uint32_t>(P, mine, keep_out, min_t_out, normal);
 }
 
 // PARTS: the world holds bodies of up to two components - the accepted partners whose tight boxes meet are pooled (k_narrow_pairs_parts'

@@ -80,6 +80,14 @@
 //                      a batch of small independent worlds (mgf_batch_*): the whole tick of one world by one workgroup per launch - integrate,
 //                      the boxes and the pair search in LDS, the tests, the constraint records, Solver::solve with the bodies' records and
 //                      progress counters in LDS
+//   k_batch_parts_front / _faces / _obst / _pairs / _pack / _copy (k_batch_parts.h)
+//                      for a batch that holds bodies of up to four components (mgf_batch_add_compound_bodies) five launches in the
+//                      places of that tick's first four - seven a tick: the part in the candidate word, the obstacle candidates in a
+//                      launch of their own (_obst), every part pair of a pair of bodies through the pruner and the manifold, up to 16
+//                      records a pair; _setup and _solve follow unchanged.  The pruner is the lone world's, written once:
+//                      parts_prune_n<SLOTS, BITS> (k_front_rows.h) serves k_pair_grid_n's four slots and _pairs' sixteen;
+//                      k_narrow_pairs_parts<MP> (k_contacts.h) keeps its own in-place copy over global memory.  _copy: the part rows
+//                      of a copied world
 //   k_batch_query_gather / _ray / _sweep_bodies / _sweep_faces (k_batch_query.h)
 //                      ray casts and sweeps against the worlds of a batch (mgf_batch_raycast_many / _sweep_many): a workgroup per (world,
 //                      up to 256 queries; BatchWork), the world's colliders in LDS, 256 / count lanes a query and the best of them by
@@ -135,6 +143,7 @@
 #include "k_api.h"
 #include "k_query.h"  // the world queries between ticks (k_query_*), beside the tick
 #include "k_batch.h"  // many small worlds, a workgroup each (k_batch_*), beside the one-world tick
+#include "k_batch_parts.h"  // the same tick for bodies of up to four components (k_batch_parts_*)
 #include "k_batch_query.h"  // the queries of k_query.h for the worlds of a batch (k_batch_query_*)
 #include "k_batch_observe.h"  // per-body contact summaries and box overlaps of a batch (k_batch_observe_*)
 #include "k_batch_drive.h"  // get / set, forces, impulses and world copies of a batch (k_batch_drive_*)
