@@ -997,7 +997,7 @@ MGF_API mgf_status mgf_batch_cast_cameras_dev(mgf_batch* b, int32_t kinds_mask, 
  * "query_launches" of a read: the collider gather behind a step (1, once), then MGF_BATCH_ZONE_LAUNCHES = 1, whatever the number of
  * worlds, zones and k.  No HIP events: "query_run_ns" is 0.
  * OUT OF SCOPE here: a world tensor for mgf_batch_overlap_first_dev; oriented boxes (the reference's Overlaps is AABB against AABB);
- * nearest-first ordering; zones on the lone mgf_world; a rig chosen per call by a device mask; hipGraph capture; terrain faces or
+ * (nearest first: the next section, "box zones, nearest first"); zones on the lone mgf_world; a rig chosen per call by a device mask; hipGraph capture; terrain faces or
  * obstacles in a zone. */
 #define MGF_BATCH_ZONE_LAUNCHES 1
 typedef struct mgf_batch_zone { int32_t world, body; mgf_vec3 p, r; int32_t flags, reserved; } mgf_batch_zone;  /* 40 bytes */
@@ -1028,6 +1028,54 @@ MGF_API mgf_status mgf_batch_read_zones_dev(mgf_batch* b, int32_t k, int32_t* ou
  * 4 (1 + k) n), out_dev's bytes overlapping those of an input array.  Not waited for; MGF_BATCH_ZONE_LAUNCHES = 1 launch. */
 MGF_API mgf_status mgf_batch_overlap_first_dev(mgf_batch* b, const mgf_aabb* boxes_dev, int64_t n, const int32_t* ignore_body_dev, int32_t k,
                                                int32_t* out_dev);
+/* ---- box zones, nearest first: the count and the k nearest bodies of every box, every word defined to the bit ----
+ * Once a box holds more than k bodies, the first k in ascending index are an arbitrary subset of them.  "The k bodies near me" wants the
+ * near ones, nearest first, and - for an observation - how far they are.  These are the zone rig's three reads (above) with that record;
+ * the rig, mgf_batch_set_zones and every call above are unchanged.
+ * A zone's box Q = (c, r) is formed exactly as above: c = x + rotate(q, p), and c = p for body = -1.  `list` is a zone's list as above:
+ * what mgf_batch_overlap_aabb_many reports for Q against the zone's world, with the zone's own body removed if MGF_SENSOR_IGNORE_SELF
+ * is set.  For body i of list let m_i be the centre of its tight box - the c of BoundedBy<AABB> (bounds.rs:170-188) of the collider a
+ * query sees, the box the overlap test itself uses: a sphere's c; a capsule's a + d * 0.5.  With e = m_i - c the distance is
+ *     d2_i = (e.x * e.x + e.y * e.y) + e.z * e.z
+ * in f32, every operation rounded on its own, no fused multiply-add.  A listed body's d2 is never NaN (a NaN difference on any axis
+ * fails Overlaps<AABB>: such a body is not in list); it lies in [+0, +inf], and f32 `<` on it is a total order.
+ * The nearest record of a zone, for a call's k, is 1 + k int32 words: word 0 is len(list), the full count - the word
+ * mgf_batch_read_zones writes; words 1 .. min(len, k) are the bodies of list in ascending (d2, body index); the rest are -1.  Where
+ * asked for there are also k f32 words per zone: d2 of the listed bodies in the same order, then +INFINITY (0x7F800000) in every unused
+ * word - a listed body whose d2 overflowed also reads +inf: the count says how many words are real.  Every word is defined to the bit:
+ * it depends on neither the lanes a zone gets, nor the other zones of its work item, nor the rig's order.
+ * 0 <= k <= MGF_BATCH_ZONE_NEAREST_MAX_K = 32: an observation of nearest neighbours is short, and the first-k record stays for anything
+ * longer.  A NaN or negative box answers as the zones do (it holds nothing: count 0).  A zone follows mgf_batch_write_state AT ONCE, the
+ * colliders move at the next tick, and nothing of the tick's state is touched, as above.  On a batch that holds bodies of several
+ * components the three calls return MGF_ERR_INVALID ("several components"), as every call that reads shapes.
+ * "query_launches" of a read: the collider gather behind a step (1, once), then MGF_BATCH_NEAREST_LAUNCHES = 1, whatever the number of
+ * worlds, zones and k.  No HIP events: "query_run_ns" is 0.  The cost is 1 + ceil(k / 4) passes over a world's bodies, shared by a zone's
+ * lanes.
+ * OUT OF SCOPE here: the distance to a body's surface instead of its tight box's centre; terrain faces or obstacles in a zone; k above
+ * 32; a world tensor for the fixed layout; zones on the lone mgf_world; hipGraph capture. */
+#define MGF_BATCH_ZONE_NEAREST_MAX_K 32
+#define MGF_BATCH_NEAREST_LAUNCHES 1
+/* mgf_batch_read_zones with the nearest record: zone i's at out[(1 + k) * i], in the rig's order; dist2_out non-NULL: its k distances
+ * at dist2_out[k * i]; boxes_out non-NULL: its box (c, r) as formed at boxes_out[i].  cap: records each array holds.  Refused as
+ * mgf_batch_read_zones refuses, in its order - MGF_ERR_INVALID: a NULL batch, k < 0 or k > MGF_BATCH_ZONE_NEAREST_MAX_K ("k is outside
+ * [0, MGF_BATCH_ZONE_NEAREST_MAX_K]", ahead of a negative cap), a negative cap, NULL out with a rig that is not empty;
+ * MGF_ERR_CAPACITY: cap below mgf_batch_zone_count.  An empty rig: MGF_OK, nothing enqueued.  Synchronous: one download, one host wait. */
+MGF_API mgf_status mgf_batch_read_zones_nearest(mgf_batch* b, int32_t k, int32_t* out, float* dist2_out, mgf_aabb* boxes_out, int64_t cap);
+/* The same with the arrays in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for; in
+ * the steady state no host wait and no copy between host and device.  Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer
+ * that fails the look-up of the device-pointer calls (4 (1 + k) count, 4 k count and 24 count bytes), and any two of the three arrays
+ * overlapping. */
+MGF_API mgf_status mgf_batch_read_zones_nearest_dev(mgf_batch* b, int32_t k, int32_t* out_dev, float* dist2_out_dev, mgf_aabb* boxes_out_dev, int64_t cap);
+/* mgf_batch_overlap_first_dev with the nearest record, for boxes the caller computed on the device.  The fixed layout only: n must be a
+ * multiple of n_worlds (else MGF_ERR_INVALID), box i is held against world i / (n / n_worlds); out_dev[(1 + k) * i ...] is the nearest
+ * record of box i and dist2_out_dev[k * i ...] (NULL: not stored) its distances, with ignore_body_dev[i] (NULL: none) removed from its
+ * list - only ever compared with a body index.  Refused with MGF_ERR_INVALID, nothing enqueued, in the order of
+ * mgf_batch_overlap_first_dev: a NULL batch, a negative n or n > INT32_MAX, NULL boxes_dev / out_dev with n > 0, k outside
+ * [0, MGF_BATCH_ZONE_NEAREST_MAX_K], n no multiple of n_worlds, a pointer that fails the look-up (boxes_dev 24 n bytes, ignore_body_dev
+ * 4 n, out_dev 4 (1 + k) n, dist2_out_dev 4 k n), out_dev's or dist2_out_dev's bytes overlapping each other's or those of an input
+ * array.  Not waited for; MGF_BATCH_NEAREST_LAUNCHES = 1 launch. */
+MGF_API mgf_status mgf_batch_overlap_nearest_dev(mgf_batch* b, const mgf_aabb* boxes_dev, int64_t n, const int32_t* ignore_body_dev, int32_t k,
+                                                 int32_t* out_dev, float* dist2_out_dev);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /

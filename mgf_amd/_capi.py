@@ -148,6 +148,8 @@ BATCH_SENSOR_LAUNCHES = 1  # MGF_BATCH_SENSOR_LAUNCHES
 BATCH_CAMERA_LAUNCHES = 1  # MGF_BATCH_CAMERA_LAUNCHES
 CAMERA_MAX_SIDE = 4096  # MGF_CAMERA_MAX_SIDE
 BATCH_ZONE_LAUNCHES = 1  # MGF_BATCH_ZONE_LAUNCHES
+BATCH_ZONE_NEAREST_MAX_K = 32  # MGF_BATCH_ZONE_NEAREST_MAX_K
+BATCH_NEAREST_LAUNCHES = 1  # MGF_BATCH_NEAREST_LAUNCHES
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -190,6 +192,7 @@ SYMBOLS = [
     "mgf_batch_set_sensors", "mgf_batch_sensor_count", "mgf_batch_cast_sensors", "mgf_batch_cast_sensors_dev",
     "mgf_batch_set_cameras", "mgf_batch_camera_count", "mgf_batch_camera_pixels", "mgf_batch_cast_cameras", "mgf_batch_cast_cameras_dev",
     "mgf_batch_set_zones", "mgf_batch_zone_count", "mgf_batch_read_zones", "mgf_batch_read_zones_dev", "mgf_batch_overlap_first_dev",
+    "mgf_batch_read_zones_nearest", "mgf_batch_read_zones_nearest_dev", "mgf_batch_overlap_nearest_dev",
 ]
 
 _lib = None
@@ -369,6 +372,9 @@ def load_library():
         "mgf_batch_read_zones": (i32, [vp, i32, vp, vp, i64]),
         "mgf_batch_read_zones_dev": (i32, [vp, i32, vp, vp, i64]),
         "mgf_batch_overlap_first_dev": (i32, [vp, vp, i64, vp, i32, vp]),
+        "mgf_batch_read_zones_nearest": (i32, [vp, i32, vp, vp, vp, i64]),
+        "mgf_batch_read_zones_nearest_dev": (i32, [vp, i32, vp, vp, vp, i64]),
+        "mgf_batch_overlap_nearest_dev": (i32, [vp, vp, i64, vp, i32, vp, vp]),
         "mgf_batch_set_cameras": (i32, [vp, vp, i64]),
         "mgf_batch_camera_count": (i64, [vp]),
         "mgf_batch_camera_pixels": (i64, [vp]),
@@ -1856,6 +1862,50 @@ class WorldBatch:
             raise ValueError("n is a multiple of the number of worlds")
         bp, ip, op = _dev_arg(boxes, "float32", 6, n, "boxes"), _dev_arg(ignore, "int32", 1, n, "ignore"), _dev_arg(out, "int32", 1 + k, n, "out")
         _check(load_library().mgf_batch_overlap_first_dev(self._h, bp, n, ip, k, op))
+
+    # ---- box zones, nearest first: the same rig, the k <= BATCH_ZONE_NEAREST_MAX_K nearest bodies of every box and their distances ---------
+    def read_zones_nearest(self, k, dist2=False, boxes=False):
+        """every zone of the rig, nearest first (mgf_batch_read_zones_nearest): (count[n], bodies[n, k]) int32 in the rig's order -
+        count as read_zones', bodies the first k of the zone's list in ascending (d2, body index), d2 the squared distance of a body's
+        tight box's centre from the zone's, then -1; dist2=True: then dist2[n, k] float32, +inf behind the listed ones; boxes=True:
+        then boxes[n, 6] - the boxes (c.xyz, r.xyz) as formed"""
+        n, k = max(self.zone_count(), 0), int(k)
+        out = np.zeros((n, 1 + max(k, 0)), np.int32)
+        d2 = np.zeros((n, max(k, 0)), np.float32) if dist2 else None
+        bx = np.zeros((n, 6), np.float32) if boxes else None
+        _check(load_library().mgf_batch_read_zones_nearest(self._h, k, out.ctypes.data, _ptr(d2), _ptr(bx), n))
+        return (out[:, 0], out[:, 1:]) + ((d2,) if dist2 else ()) + ((bx,) if boxes else ())
+
+    def read_zones_nearest_dev(self, out, dist2=None, boxes=None, k=None):
+        """read_zones_nearest into device memory (mgf_batch_read_zones_nearest_dev), enqueued on the context's stream and not waited
+        for.  out: CUDA int32 [n, 1 + k], n = zone_count() - column 0 the count, columns 1: the k nearest bodies, -1 behind them; k is
+        out.shape[1] - 1 (a raw address: give k).  dist2: CUDA float32 [n, k] or None - their squared distances, +inf behind them.
+        boxes: CUDA float32 [n, 6] or None - a row (c.xyz, r.xyz), the zone's box."""
+        if out is None:
+            raise ValueError("out is required")
+        k = _record_k(out, k)
+        n = max(self.zone_count(), 0)
+        op, dp, bp = _dev_arg(out, "int32", 1 + k, n, "out"), _dev_arg(dist2, "float32", k, n, "dist2"), _dev_arg(boxes, "float32", 6, n, "boxes")
+        _check(load_library().mgf_batch_read_zones_nearest_dev(self._h, k, op, dp, bp, n))
+
+    def overlap_nearest_dev(self, boxes, out, dist2=None, ignore=None, n=None, k=None):
+        """the records of read_zones_nearest for boxes the caller computed on the device (mgf_batch_overlap_nearest_dev), not waited
+        for.  boxes: CUDA float32 [n, 6], a row (c.xyz, r.xyz); the fixed layout: n a multiple of n_worlds, box i against world
+        i // (n // n_worlds).  out: CUDA int32 [n, 1 + k].  dist2: CUDA float32 [n, k] or None.  ignore: CUDA int32 [n] or None - a
+        body of the box's world left out of its list.  Raw addresses: give n and k."""
+        if boxes is None or out is None:
+            raise ValueError("boxes and out are both required")
+        if n is None:
+            if not hasattr(boxes, "data_ptr") or boxes.dim() != 2:
+                raise ValueError("n must be given with a raw address")
+            n = int(boxes.shape[0])
+        k = _record_k(out, k)
+        n = int(n)
+        if n % self.n_worlds:
+            raise ValueError("n is a multiple of the number of worlds")
+        bp, ip, op = _dev_arg(boxes, "float32", 6, n, "boxes"), _dev_arg(ignore, "int32", 1, n, "ignore"), _dev_arg(out, "int32", 1 + k, n, "out")
+        dp = _dev_arg(dist2, "float32", k, n, "dist2")
+        _check(load_library().mgf_batch_overlap_nearest_dev(self._h, bp, n, ip, k, op, dp))
 
     def counter(self, name):
         v = C.c_int64()

@@ -106,6 +106,7 @@ struct mgf_batch {
   DBuf<float> c_parts, c_depth;         // of a camera cast: 7 words a pixel, one word a pixel
   DBuf<int32_t> c_world;                // [pixels] a pixel's world, written by the tile pass for the obstacle pass
   DBuf<int32_t> z_out;                  // what the host-memory read of the zones downloads: 1 + k words a zone, then - where asked for - six a zone
+                                        // (host_batch_nearest.inc: records | k distances a zone | boxes)
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {

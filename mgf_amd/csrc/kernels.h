@@ -128,6 +128,12 @@
 //                      the caller's own boxes from device memory (mgf_batch_overlap_first_dev): per box the count and the first k bodies,
 //                      a record of fixed width - through bo_front (k_batch_observe.h), k_batch_observe_overlap's front, with the ignored
 //                      body on: count and fill in one pass, no total, no host wait
+//   k_batch_nearest<SRC> (k_batch_nearest.h)
+//                      the same zones and boxes, nearest first (mgf_batch_read_zones_nearest / _read_zones_nearest_dev /
+//                      _overlap_nearest_dev): per box the count and the k <= 32 nearest bodies by the squared distance of their tight
+//                      box's centre from the box's, ties by index, and those distances where asked for - the count through bo_front,
+//                      then k rounds of selection over the staged boxes: a lane's least 64-bit key (bits(d2) << 32) | index above the
+//                      last one chosen, min-reduced over the zone's lanes by __shfl_xor; one launch, no sort, no atomic
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -152,3 +158,4 @@
 #include "k_batch_sensor.h"  // ray sensors fixed in the frame of a body, cast from the resident poses (k_batch_sensor_ray)
 #include "k_batch_camera.h"  // depth cameras fixed in the frame of a body, a workgroup per image tile (k_batch_camera_*)
 #include "k_batch_zone.h"  // box zones: the count and the first k bodies of every box, a fixed-width record (k_batch_zone_first)
+#include "k_batch_nearest.h"  // box zones, nearest first: the count and the k nearest bodies of every box (k_batch_nearest)

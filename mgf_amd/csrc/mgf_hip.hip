@@ -172,3 +172,4 @@ extern "C" mgf_status mgf_exclusive_scan_u32(mgf_ctx* ctx, const uint32_t* in, i
 #include "host_batch_sensor.inc"
 #include "host_batch_camera.inc"
 #include "host_batch_zone.inc"
+#include "host_batch_nearest.inc"
