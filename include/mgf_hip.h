@@ -1076,6 +1076,72 @@ MGF_API mgf_status mgf_batch_read_zones_nearest_dev(mgf_batch* b, int32_t k, int
  * array.  Not waited for; MGF_BATCH_NEAREST_LAUNCHES = 1 launch. */
 MGF_API mgf_status mgf_batch_overlap_nearest_dev(mgf_batch* b, const mgf_aabb* boxes_dev, int64_t n, const int32_t* ignore_body_dev, int32_t k,
                                                  int32_t* out_dev, float* dist2_out_dev);
+/* ---- contact sensors: touched by whom - the constraint list of the last tick folded per (body, partner), every word defined to the bit ----
+ * mgf_batch_read_body_contacts sums over every partner of a body and separates the terrain only as a count.  "Is this foot on the ground,
+ * and with what impulse", "did the agent reach that object", "is anything but the floor pushing on the torso", "where on the body is the
+ * strongest contact" need the partner.  A contact sensor is the fourth rig of a batch beside ray sensors, cameras and zones: set once,
+ * checked and sorted on the host, read every tick in one launch, a report of fixed width.  The struct and its definition are this
+ * build's: the reference has no such report (its Solver keeps the list, solver.rs:53-79; nothing there folds it).  It reads no shapes,
+ * so - unlike rays, sweeps, zones, sensors and cameras - it works on a batch that holds bodies of several components.
+ * Sensor (world, body = x, other, flags).  L is the list mgf_batch_read_constraints(world) would return at that moment: the last tick's,
+ * in insertion order; empty before the first tick and, for every world, once bodies have been added behind a tick; unchanged by
+ * mgf_batch_write_state.
+ * Chain: the records of L with a == x in ascending list index, then the records with b == x in ascending list index - the order
+ * ContactConstraint::solve (solver.rs:203-252) meets them in, the order of mgf_body_contacts.
+ * Partner of a chain record: b where x is `a` (-1 for RigidBodyRef::Static), a where x is `b`.
+ * Match: other >= 0: the partner equals other; MGF_TOUCH_STATIC: the partner is -1 (terrain and obstacle contacts alike);
+ * MGF_TOUCH_ANY_BODY: the partner is >= 0; MGF_TOUCH_ANY: always.
+ * Fold over the matching records in chain order, impulse and normal_impulse starting at +0, ni = the record's normal_impulse and
+ * t = (normal.x * ni, normal.y * ni, normal.z * ni):  x is `a`: impulse = impulse - t;  x is `b`: impulse = impulse + t;  in both roles
+ * normal_impulse = normal_impulse + ni;  n_contacts counts the matching records.  Sequential f32 operations in that order, no fused
+ * multiply-add.  So an MGF_TOUCH_ANY sensor's n_contacts, impulse and normal_impulse equal that body's mgf_body_contacts bit for bit, and
+ * an MGF_TOUCH_STATIC sensor's n_contacts equals its n_terrain.
+ * Strongest contact: the first matching record starts as the strongest; a later one replaces it only if its ni > the current one's, an
+ * f32 compare - ties and NaN keep the earlier record.  Of that record: `record` is its list index within the world, `partner` its
+ * partner, strongest_impulse its ni; push is its normal with every sign bit flipped where x is `a` and as stored where x is `b` - the
+ * direction the impulse pushes x (solver.rs:243-247); arm is ra where x is `a` and rb where x is `b`.
+ * Body frame: with MGF_TOUCH_BODY_FRAME and at least one match, impulse, push and arm are each replaced, after the fold, by
+ * rotate((q.s, -q.x, -q.y, -q.z), v) with q the body's row as mgf_batch_read_state returns it at the moment of the read and rotate the
+ * sensors' (tmp = q.v x v + v * q.s; (q.v x tmp) * 2 + v), every operation rounded on its own.  After mgf_batch_write_state the rotation
+ * follows the new q AT ONCE; the list does not move.
+ * No match, whatever the flags: n_contacts = 0, partner = MGF_TOUCH_NONE, record = -1, every other word +0.  reserved0 and reserved1
+ * are always 0.  A report depends on its sensor and its world only: not on the other sensors, their order, or what else the batch holds.
+ * A read writes nothing of the tick's state (not even `rows`, which mgf_batch_read_body_contacts rebuilds): a step after a read is
+ * bit-identical to one without it.  mgf_batch_copy_worlds(_where) carries the list, so the destination's sensors answer as the
+ * source's would.
+ * "query_launches" of either read: MGF_BATCH_TOUCH_LAUNCHES = 1 whatever the worlds, sensors and list lengths; there is no collider
+ * gather, since nothing here reads a shape.  No HIP events: "query_run_ns" is 0.
+ * OUT OF SCOPE here: sums over the ticks of a multi-tick mgf_batch_step call (the report describes the last tick, as
+ * mgf_batch_read_body_contacts does); tangent impulses (mgf_constraint does not carry them); groups of bodies as a partner filter; the k
+ * strongest contacts rather than one; sensors on the lone mgf_world; a rig chosen per call by a device mask; hipGraph capture. */
+#define MGF_TOUCH_STATIC   (-1)  /* RigidBodyRef::Static: the world's terrain and obstacles alike (b = -1) */
+#define MGF_TOUCH_ANY_BODY (-2)  /* any body of the world */
+#define MGF_TOUCH_ANY      (-3)  /* every record that names the body */
+#define MGF_TOUCH_NONE     (-4)  /* mgf_touch_report.partner where nothing matched */
+#define MGF_TOUCH_BODY_FRAME 1   /* flags: the three vectors in the frame of the body */
+#define MGF_BATCH_TOUCH_LAUNCHES 1
+typedef struct mgf_batch_touch { int32_t world, body, other, flags; } mgf_batch_touch;   /* 16 bytes */
+typedef struct mgf_touch_report {
+  int32_t n_contacts, partner, record, reserved0;
+  mgf_vec3 impulse;  float normal_impulse;
+  mgf_vec3 push;     float strongest_impulse;
+  mgf_vec3 arm;      float reserved1;
+} mgf_touch_report;                                                                       /* 64 bytes */
+/* Replaces the rig; n = 0 clears it.  No device work: the rig goes up with the next read.  Refused with MGF_ERR_INVALID, the rig as it
+ * was, in this order: what mgf_batch_set_sensors refuses - a NULL batch, a negative n or n > INT32_MAX, a NULL array with n > 0, then
+ * per record a world out of range, a body outside [0, mgf_batch_len(b, world)) - then other < -3 or other >= mgf_batch_len(b, world),
+ * other == body, a flag bit beyond MGF_TOUCH_BODY_FRAME.  The rig names (world, body): mgf_batch_add_bodies and
+ * mgf_batch_add_compound_bodies afterwards leave every sensor on the bodies it named.  Independent of the other three rigs. */
+MGF_API mgf_status mgf_batch_set_touches(mgf_batch* b, const mgf_batch_touch* t, int64_t n);
+MGF_API int64_t    mgf_batch_touch_count(const mgf_batch* b);                 /* -1 for NULL */
+/* The report of sensor i at out[i], in the order of the array given to mgf_batch_set_touches; cap: reports `out` holds.
+ * MGF_ERR_INVALID: a NULL batch, a negative cap, NULL out with a rig that is not empty; MGF_ERR_CAPACITY: cap below
+ * mgf_batch_touch_count, nothing written.  An empty rig: MGF_OK, nothing enqueued.  Synchronous: one launch, one download, one host wait. */
+MGF_API mgf_status mgf_batch_read_touches(mgf_batch* b, mgf_touch_report* out, int64_t cap);
+/* The same with the reports in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for; in
+ * the steady state no host wait and no copy between host and device.  Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer
+ * that fails the look-up of the device-pointer calls (64 count bytes, aligned to 4 bytes). */
+MGF_API mgf_status mgf_batch_read_touches_dev(mgf_batch* b, mgf_touch_report* out_dev, int64_t cap);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /

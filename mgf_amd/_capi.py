@@ -150,6 +150,15 @@ CAMERA_MAX_SIDE = 4096  # MGF_CAMERA_MAX_SIDE
 BATCH_ZONE_LAUNCHES = 1  # MGF_BATCH_ZONE_LAUNCHES
 BATCH_ZONE_NEAREST_MAX_K = 32  # MGF_BATCH_ZONE_NEAREST_MAX_K
 BATCH_NEAREST_LAUNCHES = 1  # MGF_BATCH_NEAREST_LAUNCHES
+# mgf_batch_touch: a contact sensor on body `body` of world `world`; other: a body of that world or TOUCH_STATIC / _ANY_BODY / _ANY
+TOUCH_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("other", "<i4"), ("flags", "<i4")])
+# mgf_touch_report
+TOUCH_REPORT_DTYPE = np.dtype([("n_contacts", "<i4"), ("partner", "<i4"), ("record", "<i4"), ("reserved0", "<i4"), ("impulse", "<f4", 3),
+                               ("normal_impulse", "<f4"), ("push", "<f4", 3), ("strongest_impulse", "<f4"), ("arm", "<f4", 3), ("reserved1", "<f4")])
+assert TOUCH_DTYPE.itemsize == 16 and TOUCH_REPORT_DTYPE.itemsize == 64
+TOUCH_STATIC, TOUCH_ANY_BODY, TOUCH_ANY, TOUCH_NONE = -1, -2, -3, -4  # MGF_TOUCH_STATIC, _ANY_BODY, _ANY, _NONE
+TOUCH_BODY_FRAME = 1  # MGF_TOUCH_BODY_FRAME
+BATCH_TOUCH_LAUNCHES = 1  # MGF_BATCH_TOUCH_LAUNCHES
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -193,6 +202,7 @@ SYMBOLS = [
     "mgf_batch_set_cameras", "mgf_batch_camera_count", "mgf_batch_camera_pixels", "mgf_batch_cast_cameras", "mgf_batch_cast_cameras_dev",
     "mgf_batch_set_zones", "mgf_batch_zone_count", "mgf_batch_read_zones", "mgf_batch_read_zones_dev", "mgf_batch_overlap_first_dev",
     "mgf_batch_read_zones_nearest", "mgf_batch_read_zones_nearest_dev", "mgf_batch_overlap_nearest_dev",
+    "mgf_batch_set_touches", "mgf_batch_touch_count", "mgf_batch_read_touches", "mgf_batch_read_touches_dev",
 ]
 
 _lib = None
@@ -375,6 +385,10 @@ def load_library():
         "mgf_batch_read_zones_nearest": (i32, [vp, i32, vp, vp, vp, i64]),
         "mgf_batch_read_zones_nearest_dev": (i32, [vp, i32, vp, vp, vp, i64]),
         "mgf_batch_overlap_nearest_dev": (i32, [vp, vp, i64, vp, i32, vp, vp]),
+        "mgf_batch_set_touches": (i32, [vp, vp, i64]),
+        "mgf_batch_touch_count": (i64, [vp]),
+        "mgf_batch_read_touches": (i32, [vp, vp, i64]),
+        "mgf_batch_read_touches_dev": (i32, [vp, vp, i64]),
         "mgf_batch_set_cameras": (i32, [vp, vp, i64]),
         "mgf_batch_camera_count": (i64, [vp]),
         "mgf_batch_camera_pixels": (i64, [vp]),
@@ -1906,6 +1920,43 @@ class WorldBatch:
         bp, ip, op = _dev_arg(boxes, "float32", 6, n, "boxes"), _dev_arg(ignore, "int32", 1, n, "ignore"), _dev_arg(out, "int32", 1 + k, n, "out")
         dp = _dev_arg(dist2, "float32", k, n, "dist2")
         _check(load_library().mgf_batch_overlap_nearest_dev(self._h, bp, n, ip, k, op, dp))
+
+    # ---- contact sensors: a rig set once, the last tick's constraint list folded per (body, partner) on the device ------------------------
+    def set_touches(self, world, body=None, other=TOUCH_ANY, body_frame=False):
+        """the batch's contact-sensor rig replaced (mgf_batch_set_touches): sensor i reports the records of world[i]'s last tick that
+        name body[i] and whose partner passes other[i] - a body of that world, TOUCH_STATIC (terrain and obstacles), TOUCH_ANY_BODY or
+        TOUCH_ANY; body_frame[i]: the report's three vectors in the frame of the body.  Arrays, or scalars for all: the number of
+        sensors is that of the longest argument.  No sensors (empty arrays) clears the rig.  Also takes a TOUCH_DTYPE array as `world`
+        with every other argument left."""
+        if isinstance(world, np.ndarray) and world.dtype == TOUCH_DTYPE:
+            rig = np.ascontiguousarray(world.reshape(-1))
+        else:
+            if body is None:
+                raise ValueError("body is required")
+            rig = _rig_rows(TOUCH_DTYPE, world=world, body=body, other=other, flags=np.where(np.asarray(body_frame, bool), TOUCH_BODY_FRAME, 0))
+        _check(load_library().mgf_batch_set_touches(self._h, rig.ctypes.data if len(rig) else None, len(rig)))
+
+    def touch_count(self):
+        return load_library().mgf_batch_touch_count(self._h)
+
+    def read_touches(self):
+        """every sensor of the rig against the last tick's constraint list (mgf_batch_read_touches): a TOUCH_REPORT_DTYPE array in the
+        rig's order - n_contacts, impulse and normal_impulse of the matching records folded in the body's chain order, and partner,
+        record, push, strongest_impulse and arm of the strongest of them; nothing matched: n_contacts 0, partner TOUCH_NONE, record -1"""
+        n = max(self.touch_count(), 0)
+        out = np.zeros(n, TOUCH_REPORT_DTYPE)
+        _check(load_library().mgf_batch_read_touches(self._h, out.ctypes.data if n else None, n))
+        return out
+
+    def read_touches_dev(self, out):
+        """read_touches into device memory (mgf_batch_read_touches_dev), enqueued on the context's stream and not waited for.
+        out: a CUDA tensor of int32 or float32 [n, 16], n = touch_count() - a row is TOUCH_REPORT_DTYPE's sixteen words - or a raw
+        address."""
+        if out is None:
+            raise ValueError("out is required")
+        n = max(self.touch_count(), 0)
+        dtype = "float32" if str(getattr(out, "dtype", "")) == "torch.float32" else "int32"
+        _check(load_library().mgf_batch_read_touches_dev(self._h, _dev_arg(out, dtype, 16, n, "out"), n))
 
     def counter(self, name):
         v = C.c_int64()

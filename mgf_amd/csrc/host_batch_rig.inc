@@ -1,7 +1,7 @@
-// What the rigs of a batch - body-mounted ray sensors, depth cameras, box zones (host_batch_sensor.inc, host_batch_camera.inc,
-// host_batch_zone.inc) - share, written once around BatchRig<Rec> (host_batch.inc, beside the handle that holds the three).  Part of the
-// single translation unit mgf_hip.hip (included there, in order, behind host_batch_query_dev.inc and ahead of the three); not compiled on
-// its own.
+// What the rigs of a batch - body-mounted ray sensors, depth cameras, box zones, contact sensors (host_batch_sensor.inc,
+// host_batch_camera.inc, host_batch_zone.inc, host_batch_touch.inc) - share, written once around BatchRig<Rec> (host_batch.inc, beside
+// the handle that holds the four).  Part of the single translation unit mgf_hip.hip (included there, in order, behind
+// host_batch_query_dev.inc and ahead of the four); not compiled on its own.
 //
 // A rig is static: which body, where on it, and what the record says beyond that.  Everything that depends on the rig alone is done once,
 // when it is set: the checks (batch_rig_set_args, batch_rig_ref_check and the rig's own), and - sensors and zones - the sort by world and
@@ -18,8 +18,8 @@ static mgf_status batch_rig_set_args(const mgf_batch* b, const void* recs, int64
   return MGF_OK;
 }
 
-// what a record of a rig - a sensor's, a camera's, a zone's - names: a world of the batch, a body of that world (or_world: or -1, the
-// world itself - a zone's), no flag but the one defined
+// what a record of a rig - a sensor's, a camera's, a zone's, a contact sensor's - names: a world of the batch, a body of that world
+// (or_world: or -1, the world itself - a zone's), no flag but the one defined (a contact sensor's flag word is its own: it passes 0)
 static mgf_status batch_rig_ref_check(const mgf_batch* b, int32_t world, int32_t body, int32_t flags, const char* what, bool or_world = false) {
   if (world < 0 || (uint32_t)world >= b->K) return fail(MGF_ERR_INVALID, "world index out of range: the rig was not changed");
   if (!(or_world && body == -1) && (body < 0 || (uint32_t)body >= b->h_n[(size_t)world]))

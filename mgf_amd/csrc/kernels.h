@@ -134,6 +134,12 @@
 //                      box's centre from the box's, ties by index, and those distances where asked for - the count through bo_front,
 //                      then k rounds of selection over the staged boxes: a lane's least 64-bit key (bits(d2) << 32) | index above the
 //                      last one chosen, min-reduced over the zone's lanes by __shfl_xor; one launch, no sort, no atomic
+//   k_batch_touch (k_batch_touch.h)
+//                      contact sensors (mgf_batch_set_touches / _read_touches / _read_touches_dev): per (body, partner filter) the last
+//                      tick's constraint list folded in the body's chain order - count, net normal impulse, sum of the normal impulses -
+//                      and the strongest matching record's partner, index, direction and arm; a lane per sensor, the ranges of `a` by
+//                      binary search, the list's `b` column through LDS a tile at a time for the filters that need a body's `b`
+//                      occurrences; nothing built in global memory, one launch, no atomic
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -159,3 +165,4 @@
 #include "k_batch_camera.h"  // depth cameras fixed in the frame of a body, a workgroup per image tile (k_batch_camera_*)
 #include "k_batch_zone.h"  // box zones: the count and the first k bodies of every box, a fixed-width record (k_batch_zone_first)
 #include "k_batch_nearest.h"  // box zones, nearest first: the count and the k nearest bodies of every box (k_batch_nearest)
+#include "k_batch_touch.h"  // contact sensors: the constraint list folded per (body, partner), a fixed-width report (k_batch_touch)
