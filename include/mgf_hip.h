@@ -571,7 +571,7 @@ MGF_API mgf_status mgf_world_release_device_ptrs(mgf_world* w);
  * LIMITS: bodies of one to four components (spheres and capsules; mgf_batch_add_compound_bodies below - the lone world takes 32, a body
  * of 5..32 is refused here); on a batch that holds a body of more than one component the calls that read the shapes of bodies -
  * mgf_batch_raycast_many(_dev), _sweep_many(_dev), _overlap_aabb_many, _overlap_first_dev, _cast_sensors(_dev), _cast_cameras(_dev),
- * _read_zones(_dev) - return MGF_ERR_INVALID ("... several components ..."), enqueue nothing and change nothing: they do not see
+ * _read_zones(_dev), _cast_feelers(_dev) - return MGF_ERR_INVALID ("... several components ..."), enqueue nothing and change nothing: they do not see
  * parts yet (the set_* calls of the rigs stay as they are); at most MGF_BATCH_MAX_BODIES bodies per world, counted in bodies, not parts (a call that would exceed it
  * is refused with MGF_ERR_INVALID and adds nothing); the static geometry of a world is one terrain mesh, or none: an entry of the
  * batch's terrain table (meshes are copied in; any number of worlds may share an entry) at a position of the world's own, and beside it
@@ -1142,6 +1142,65 @@ MGF_API mgf_status mgf_batch_read_touches(mgf_batch* b, mgf_touch_report* out, i
  * the steady state no host wait and no copy between host and device.  Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer
  * that fails the look-up of the device-pointer calls (64 count bytes, aligned to 4 bytes). */
 MGF_API mgf_status mgf_batch_read_touches_dev(mgf_batch* b, mgf_touch_report* out_dev, int64_t cap);
+/* ---- body-mounted feelers: spheres and capsules with a displacement, fixed in the frame of a body, swept from the resident poses ----
+ * A foothold or clearance probe ("can this foot come down here", "does my own body fit one step ahead"), the slope of the ground under
+ * an agent, a bumper or whisker of finite thickness: the sweep is the one query whose answer carries a contact normal (mgf_ray_hit has
+ * none), and a feeler is its rig - the fifth beside ray sensors, cameras, zones and contact sensors: set once, checked and sorted on the
+ * host, cast every tick from the poses resident on the device.
+ * A feeler is a record (world, body, tag, flags, p, d, r, delta): body an index within world; p, d and - without
+ * MGF_FEELER_WORLD_DELTA - delta in the body's frame.  With x and q the body's rows as mgf_batch_read_state returns them - that is
+ * x WITHOUT delta, the pose the sensors use - the feeler's cast C is
+ *   shape: with MGF_FEELER_OWN_SHAPE, mgf_batch_read_colliders(world)[body].shape as it stands (tag, p, d, r of the record are not
+ *          read); otherwise tag and r are the record's, P = x + rotate(q, p) and D = rotate(q, d) whatever the tag (a sphere's d is
+ *          carried and not used, as by mgf_batch_sweep_many);
+ *   displacement: with MGF_FEELER_WORLD_DELTA, C.delta = delta ("straight down" whatever the tilt); otherwise C.delta = rotate(q, delta);
+ * rotate and the sum are the sensors' (Rotation::rotate_vector, a plain vector add, every operation a separate f32 one, no fused
+ * multiply-add): C is defined to the bit.  The feeler's answer is, bit for bit, the mgf_sweep_hit that mgf_batch_sweep_many reports for
+ * C against world `world` with the same kinds_mask and the ignore value `body` with MGF_FEELER_IGNORE_SELF, -1 without it.  Every rule
+ * of that call holds unchanged, and nothing of the tick's state is touched.  On request the casts themselves come back as
+ * mgf_moving_component, bit for bit the C above.
+ * Poses written with mgf_batch_write_state, mgf_batch_set_many and the like move a feeler AT ONCE.  The colliders, and with them an
+ * MGF_FEELER_OWN_SHAPE shape, move at the next tick.  (So behind a write an own-shape feeler casts the OLD collider along a delta turned
+ * by the NEW q.)
+ * A cast is MGF_BATCH_FEELER_LAUNCHES = 1 launch, one more where the mask asks for terrain and a world of the batch has a mesh, one more
+ * where it asks for obstacles and a world has one, and the collider gather once behind a step ("query_launches") - whatever the number
+ * of feelers and worlds; no plan, no index arrays.  No HIP events: "query_run_ns" is 0.
+ * OUT OF SCOPE here: the parts of bodies of several components (LIMITS, above: both cast calls return MGF_ERR_INVALID,
+ * "several components"; mgf_batch_set_feelers stays as it is); a kinds mask per feeler; more than one shape per record; feelers on the
+ * lone mgf_world. */
+#define MGF_FEELER_IGNORE_SELF 1   /* the body does not meet itself (the value of MGF_SENSOR_IGNORE_SELF) */
+#define MGF_FEELER_WORLD_DELTA 2   /* delta is in world coordinates: "straight down" whatever the tilt */
+#define MGF_FEELER_OWN_SHAPE   4   /* the cast is the body's own resident collider; tag, p, d, r are not read */
+#define MGF_BATCH_FEELER_LAUNCHES 1  /* what one cast adds to "query_launches" without faces and obstacles */
+typedef struct mgf_batch_feeler {
+  int32_t world, body, tag, flags;
+  mgf_vec3 p, d;
+  float r;
+  mgf_vec3 delta;
+  int32_t reserved[2];     /* 0 */
+} mgf_batch_feeler;        /* 64 bytes */
+/* Replaces the rig by a copy of f[0 .. n); n = 0 clears it.  No device work: the rig goes up with the next cast.  Refused with
+ * MGF_ERR_INVALID, the rig as it was ("the rig was not changed"), in this order: what mgf_batch_set_sensors refuses - a NULL batch, a
+ * negative n or n > INT32_MAX, a NULL array with n > 0, then per record a world out of range, a body outside
+ * [0, mgf_batch_len(b, world)) - then a flag bit beyond 7, a tag other than 0 or 1 without MGF_FEELER_OWN_SHAPE, MGF_FEELER_OWN_SHAPE
+ * without MGF_FEELER_IGNORE_SELF (the body would meet itself at t = 0), a non-zero reserved word.  Radii, lengths and non-finite values
+ * are not judged: mgf_batch_sweep_many does not judge them either, and the answer is defined as that call's.  The rig names
+ * (world, body): mgf_batch_add_bodies and mgf_batch_add_compound_bodies afterwards leave every feeler on the body it named.
+ * Independent of the other four rigs. */
+MGF_API mgf_status mgf_batch_set_feelers(mgf_batch* b, const mgf_batch_feeler* f, int64_t n);
+MGF_API int64_t    mgf_batch_feeler_count(const mgf_batch* b);                /* -1 for NULL */
+/* The hit of feeler i at out[i], in the order of the array given to mgf_batch_set_feelers; casts_out non-NULL: also its cast C at
+ * casts_out[i].  cap: records each array holds.  Refused in this order - MGF_ERR_INVALID: a NULL batch, a negative cap, a mask of 0 or
+ * with bits beyond MGF_QUERY_ALL; MGF_ERR_CAPACITY: cap below mgf_batch_feeler_count; MGF_ERR_INVALID: NULL out with a rig that is not
+ * empty, a batch that holds a body of several components.  An empty rig: MGF_OK, nothing enqueued.  Synchronous, as
+ * mgf_batch_sweep_many: one download, one host wait. */
+MGF_API mgf_status mgf_batch_cast_feelers(mgf_batch* b, int32_t kinds_mask, mgf_sweep_hit* out, mgf_moving_component* casts_out, int64_t cap);
+/* The same with both arrays in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for.  In
+ * the steady state no host wait and no copy between host and device.  Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer
+ * that fails the look-up of the device-pointer calls (52 * count bytes of out_dev, 44 * count of casts_out_dev), and out_dev's bytes
+ * overlapping casts_out_dev's. */
+MGF_API mgf_status mgf_batch_cast_feelers_dev(mgf_batch* b, int32_t kinds_mask, mgf_sweep_hit* out_dev, mgf_moving_component* casts_out_dev,
+                                              int64_t cap);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /

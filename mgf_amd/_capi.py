@@ -55,6 +55,11 @@ class BatchZone(C.Structure):
     _fields_ = [("world", C.c_int32), ("body", C.c_int32), ("p", Vec3), ("r", Vec3), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BatchFeeler(C.Structure):
+    _fields_ = [("world", C.c_int32), ("body", C.c_int32), ("tag", C.c_int32), ("flags", C.c_int32), ("p", Vec3), ("d", Vec3), ("r", C.c_float),
+                ("delta", Vec3), ("reserved", C.c_int32 * 2)]
+
+
 class Component(C.Structure):
     _fields_ = [("tag", C.c_int32), ("p", Vec3), ("d", Vec3), ("r", C.c_float)]
 
@@ -159,6 +164,12 @@ assert TOUCH_DTYPE.itemsize == 16 and TOUCH_REPORT_DTYPE.itemsize == 64
 TOUCH_STATIC, TOUCH_ANY_BODY, TOUCH_ANY, TOUCH_NONE = -1, -2, -3, -4  # MGF_TOUCH_STATIC, _ANY_BODY, _ANY, _NONE
 TOUCH_BODY_FRAME = 1  # MGF_TOUCH_BODY_FRAME
 BATCH_TOUCH_LAUNCHES = 1  # MGF_BATCH_TOUCH_LAUNCHES
+# mgf_batch_feeler: a sphere (tag 0) or capsule (tag 1) swept by delta, fixed in the frame of body `body` of world `world`
+FEELER_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("tag", "<i4"), ("flags", "<i4"), ("p", "<f4", 3), ("d", "<f4", 3), ("r", "<f4"),
+                         ("delta", "<f4", 3), ("reserved", "<i4", 2)])
+assert FEELER_DTYPE.itemsize == C.sizeof(BatchFeeler) == 64
+FEELER_IGNORE_SELF, FEELER_WORLD_DELTA, FEELER_OWN_SHAPE = 1, 2, 4  # MGF_FEELER_IGNORE_SELF, _WORLD_DELTA, _OWN_SHAPE
+BATCH_FEELER_LAUNCHES = 1  # MGF_BATCH_FEELER_LAUNCHES
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -203,6 +214,7 @@ SYMBOLS = [
     "mgf_batch_set_zones", "mgf_batch_zone_count", "mgf_batch_read_zones", "mgf_batch_read_zones_dev", "mgf_batch_overlap_first_dev",
     "mgf_batch_read_zones_nearest", "mgf_batch_read_zones_nearest_dev", "mgf_batch_overlap_nearest_dev",
     "mgf_batch_set_touches", "mgf_batch_touch_count", "mgf_batch_read_touches", "mgf_batch_read_touches_dev",
+    "mgf_batch_set_feelers", "mgf_batch_feeler_count", "mgf_batch_cast_feelers", "mgf_batch_cast_feelers_dev",
 ]
 
 _lib = None
@@ -389,6 +401,10 @@ def load_library():
         "mgf_batch_touch_count": (i64, [vp]),
         "mgf_batch_read_touches": (i32, [vp, vp, i64]),
         "mgf_batch_read_touches_dev": (i32, [vp, vp, i64]),
+        "mgf_batch_set_feelers": (i32, [vp, vp, i64]),
+        "mgf_batch_feeler_count": (i64, [vp]),
+        "mgf_batch_cast_feelers": (i32, [vp, i32, vp, vp, i64]),
+        "mgf_batch_cast_feelers_dev": (i32, [vp, i32, vp, vp, i64]),
         "mgf_batch_set_cameras": (i32, [vp, vp, i64]),
         "mgf_batch_camera_count": (i64, [vp]),
         "mgf_batch_camera_pixels": (i64, [vp]),
@@ -1353,7 +1369,7 @@ class WorldBatch:
     """Many small independent worlds resident on one GPU, stepped together (mgf_batch_*): per world `step` is
     mgf_demo/world.rs::World::step, one workgroup a world.  At most BATCH_MAX_BODIES bodies of one to four components per world
     (add_compound_bodies; on a batch that holds a body of more than one component the calls that read the shapes of bodies - ray
-    casts, sweeps, box overlaps, sensors, cameras, zones - raise ERR_INVALID: they do not see parts yet); a world's
+    casts, sweeps, box overlaps, sensors, cameras, zones, feelers - raise ERR_INVALID: they do not see parts yet); a world's
     terrain is an entry of the batch's terrain table (shared by any number of worlds) at a position of its own, or none; its static
     Compound obstacles are a list of entries of the batch's obstacle table, each at a pose of the world's own."""
 
@@ -1957,6 +1973,46 @@ class WorldBatch:
         n = max(self.touch_count(), 0)
         dtype = "float32" if str(getattr(out, "dtype", "")) == "torch.float32" else "int32"
         _check(load_library().mgf_batch_read_touches_dev(self._h, _dev_arg(out, dtype, 16, n, "out"), n))
+
+    # ---- body-mounted feelers: a rig set once, spheres and capsules swept from the resident poses -----------------------------------------
+    def set_feelers(self, world, body=None, tag=None, p=None, d=None, r=None, delta=None, ignore_self=True, world_delta=False, own_shape=False):
+        """the batch's feeler rig replaced (mgf_batch_set_feelers): feeler i is the sphere (tag 0: centre p[i], radius r[i]) or capsule
+        (tag 1: from p[i] along d[i], radius r[i]) in the frame of body[i] of world[i], swept by delta[i] - in the body's frame, or
+        (world_delta[i]) in world coordinates; own_shape[i]: the cast is the body's own resident collider, and tag, p, d, r are not
+        read (it needs ignore_self[i]); ignore_self[i]: its own body is not a target.  Arrays, or scalars / single rows for all: the
+        number of feelers is that of the longest argument; an argument left None stays zero.  No feelers (empty arrays) clears the
+        rig.  Also takes a FEELER_DTYPE array as `world` with every other argument None."""
+        if isinstance(world, np.ndarray) and world.dtype == FEELER_DTYPE:
+            rig = np.ascontiguousarray(world.reshape(-1))
+        else:
+            flags = (np.where(np.asarray(ignore_self, bool), FEELER_IGNORE_SELF, 0) | np.where(np.asarray(world_delta, bool), FEELER_WORLD_DELTA, 0)
+                     | np.where(np.asarray(own_shape, bool), FEELER_OWN_SHAPE, 0))
+            given = {k: v for k, v in dict(tag=tag, p=p, d=d, r=r, delta=delta).items() if v is not None}
+            rig = _rig_rows(FEELER_DTYPE, world=world, body=body, flags=flags, **given)
+        _check(load_library().mgf_batch_set_feelers(self._h, rig.ctypes.data if len(rig) else None, len(rig)))
+
+    def feeler_count(self):
+        return load_library().mgf_batch_feeler_count(self._h)
+
+    def cast_feelers(self, kinds=QUERY_ALL, casts=False):
+        """every feeler of the rig swept from its body's current pose (mgf_batch_cast_feelers): a SWEEP_HIT_DTYPE array in the rig's
+        order, as sweep returns it; casts=True: (hits, casts) - the MOVING_DTYPE array of the casts in world coordinates"""
+        n = max(self.feeler_count(), 0)
+        out = np.zeros(n, SWEEP_HIT_DTYPE)
+        cs = np.zeros(n, MOVING_DTYPE) if casts else None
+        _check(load_library().mgf_batch_cast_feelers(self._h, int(kinds), out.ctypes.data, _ptr(cs), n))
+        return (out, cs) if casts else out
+
+    def cast_feelers_dev(self, out, kinds=QUERY_ALL, casts=None):
+        """cast_feelers into device memory (mgf_batch_cast_feelers_dev), enqueued on the context's stream and not waited for.
+        out: CUDA int32 [n, 13], SWEEP_HIT_DTYPE's words as sweep_dev writes them, n = feeler_count(); casts: CUDA [n, 11], float32 or
+        int32, or None - MOVING_DTYPE's words (tag, p.xyz, d.xyz, r, delta.xyz) as sweep_dev reads them: word 0 holds the tag's BITS."""
+        if out is None:
+            raise ValueError("out is required")
+        n = max(self.feeler_count(), 0)
+        words = "int32" if str(getattr(casts, "dtype", "")) == "torch.int32" else "float32"
+        op, cp = _dev_arg(out, "int32", 13, n, "out"), _dev_arg(casts, words, 11, n, "casts")
+        _check(load_library().mgf_batch_cast_feelers_dev(self._h, int(kinds), op, cp, n))
 
     def counter(self, name):
         v = C.c_int64()

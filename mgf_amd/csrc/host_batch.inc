@@ -12,7 +12,7 @@
 // one store each - and per world a list of (entry, disp, rot); the kernels read a descriptor per list entry (BatchObstacles, k_batch.h).
 // Both tables and all lists live beside the mirror: adding bodies behind a tick, or none yet, leaves them as they are.
 
-// A rig of a batch - sensors, cameras, zones, contact sensors: the records in the caller's order, what is built from them when the rig is set, and the
+// A rig of a batch - sensors, cameras, zones, contact sensors, feelers: the records in the caller's order, what is built from them when the rig is set, and the
 // device copy of both (host_batch_rig.inc)
 template <class Rec>
 struct BatchRig {
@@ -96,11 +96,12 @@ struct mgf_batch {
   DBuf<int32_t> p_world;                // [n] the call's own copy of the worlds, -1: a skipped record
   DBuf<uint32_t> p_rank, p_order;       // [n] a query's rank within its world; sorted position -> the caller's index
   DBuf<uint4> p_items;                  // the work items
-  // the rigs (host_batch_rig.inc): body-mounted ray sensors, depth cameras, box zones and contact sensors (host_batch_sensor.inc, _camera.inc, _zone.inc, _touch.inc)
+  // the rigs (host_batch_rig.inc): body-mounted ray sensors, depth cameras, box zones, contact sensors and feelers (host_batch_sensor.inc, _camera.inc, _zone.inc, _touch.inc, _feeler.inc)
   BatchRig<mgf_batch_sensor> sensors;   // on the device: items | records | order | worlds
   BatchRig<mgf_batch_camera> cameras;   // on the device: tiles | records - (camera, the camera's first pixel, x0 | y0 << 16, -): a tile of kCamTileW x kCamTileH pixels
   BatchRig<mgf_batch_zone> zones;       // on the device: items | records | order
   BatchRig<mgf_batch_touch> touches;    // on the device: items | records | order - the contact sensors (host_batch_touch.inc)
+  BatchRig<mgf_batch_feeler> feelers;   // on the device: items | records | order | worlds - the feelers (host_batch_feeler.inc)
   // ... and what a call on one of them has nowhere else to put
   DBuf<float> s_parts;                  // the particles of a sensor cast: 7 words a sensor
   size_t c_pixels = 0;                  // the pixels of the camera rig, camera by camera
@@ -109,6 +110,7 @@ struct mgf_batch {
   DBuf<int32_t> z_out;                  // what the host-memory read of the zones downloads: 1 + k words a zone, then - where asked for - six a zone
                                         // (host_batch_nearest.inc: records | k distances a zone | boxes)
   DBuf<float4> touch_out;               // what the host-memory read of the contact sensors downloads: four words a sensor
+  DBuf<float> f_casts;                  // the casts of a feeler cast where the caller takes none: 11 words a feeler
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {
@@ -532,6 +534,7 @@ static void batch_rigs_stale(mgf_batch* b) {
   b->cameras.stale = true;
   b->zones.stale = true;
   b->touches.stale = true;
+  b->feelers.stale = true;
 }
 
 // the rows of `n` new bodies (empty part slots where the caller has filled none) behind world k's last body

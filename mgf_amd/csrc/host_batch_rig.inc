@@ -1,7 +1,7 @@
-// What the rigs of a batch - body-mounted ray sensors, depth cameras, box zones, contact sensors (host_batch_sensor.inc,
-// host_batch_camera.inc, host_batch_zone.inc, host_batch_touch.inc) - share, written once around BatchRig<Rec> (host_batch.inc, beside
-// the handle that holds the four).  Part of the single translation unit mgf_hip.hip (included there, in order, behind
-// host_batch_query_dev.inc and ahead of the four); not compiled on its own.
+// What the rigs of a batch - body-mounted ray sensors, depth cameras, box zones, contact sensors, feelers (host_batch_sensor.inc,
+// host_batch_camera.inc, host_batch_zone.inc, host_batch_touch.inc, host_batch_feeler.inc) - share, written once around BatchRig<Rec>
+// (host_batch.inc, beside the handle that holds the five).  Part of the single translation unit mgf_hip.hip (included there, in order,
+// behind host_batch_query_dev.inc and ahead of the five); not compiled on its own.
 //
 // A rig is static: which body, where on it, and what the record says beyond that.  Everything that depends on the rig alone is done once,
 // when it is set: the checks (batch_rig_set_args, batch_rig_ref_check and the rig's own), and - sensors and zones - the sort by world and
@@ -60,7 +60,8 @@ static mgf_status batch_rig_upload(mgf_batch* b, DBuf<float4>& dev, const RigSec
 }
 
 // The rig onto the device where the copy there is behind (n > 0): the first n_sec of items | records | order | worlds - the cameras'
-// two (tiles | records), the zones' three, the sensors' four (the obstacle pass reads a sensor's world by the caller's index).
+// two (tiles | records), the zones' three, the sensors' and the feelers' four (the passes with a lane per query read a record's world
+// by the caller's index).
 // or_world: a body of -1 is the world itself.
 template <class Rec>
 static mgf_status batch_rig_up(mgf_batch* b, BatchRig<Rec>& R, const char* what, size_t n_sec, bool or_world = false) {

@@ -140,6 +140,12 @@
 //                      and the strongest matching record's partner, index, direction and arm; a lane per sensor, the ranges of `a` by
 //                      binary search, the list's `b` column through LDS a tile at a time for the filters that need a body's `b`
 //                      occurrences; nothing built in global memory, one launch, no atomic
+//   k_batch_feeler_bodies (k_batch_feeler.h)
+//                      feelers fixed in the frame of a body (mgf_batch_set_feelers / _cast_feelers / _cast_feelers_dev): a sphere or
+//                      capsule with a displacement - or the body's own resident collider - formed from the bodies' x and q, P = x +
+//                      rotate(q, p), D = rotate(q, d), delta turned by q or kept in world coordinates, and swept against the world's
+//                      staged colliders with k_batch_query_sweep_bodies' walk and reduction (bf_sweep_front); the cast is always
+//                      stored, and k_batch_query_sweep_faces / _sweep_obstacles take it up again from there
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -166,3 +172,4 @@
 #include "k_batch_zone.h"  // box zones: the count and the first k bodies of every box, a fixed-width record (k_batch_zone_first)
 #include "k_batch_nearest.h"  // box zones, nearest first: the count and the k nearest bodies of every box (k_batch_nearest)
 #include "k_batch_touch.h"  // contact sensors: the constraint list folded per (body, partner), a fixed-width report (k_batch_touch)
+#include "k_batch_feeler.h"  // feelers: spheres and capsules fixed in the frame of a body, swept from the resident poses (k_batch_feeler_bodies)
