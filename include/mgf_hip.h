@@ -1201,6 +1201,66 @@ MGF_API mgf_status mgf_batch_cast_feelers(mgf_batch* b, int32_t kinds_mask, mgf_
  * overlapping casts_out_dev's. */
 MGF_API mgf_status mgf_batch_cast_feelers_dev(mgf_batch* b, int32_t kinds_mask, mgf_sweep_hit* out_dev, mgf_moving_component* casts_out_dev,
                                               int64_t cap);
+/* ---- body-mounted actuators: directions and arms fixed in the frame of a body, wrenches formed from the resident poses ----
+ * A rotor, a thruster, a wheel's drive, a reaction wheel, a foot pushing at its own point: the action-side mirror of the feeler, and
+ * the sixth rig - set once, checked and sorted on the host, applied every tick from the poses resident on the device in one launch.
+ * What a caller otherwise assembles per tick (mgf_batch_gather_state_dev for q, directions and arms turned in an expression of its own,
+ * a cross product, a sum per body, mgf_batch_apply_impulses_dev) is here one call whose answer is defined to the bit.
+ * An actuator is a record (world, body, flags, gain, p, lo, d, hi): body an index within world; the arm p in the body's frame; the
+ * direction d in the body's frame or, with MGF_ACTUATOR_WORLD_DIR, the world's; one control value u[i] a call.
+ * THE WRENCH of actuator i, with q the body's row as mgf_batch_read_state returns it at that moment - every line a separate f32
+ * operation, no fused multiply-add:
+ *   c = u[i];  if (c < lo) c = lo;  if (c > hi) c = hi;        (a NaN stays a NaN)
+ *   s = gain * c
+ *   e = WORLD_DIR ? d : rotate(q, d)                            rotate: the sensors' Rotation::rotate_vector
+ *   TORQUE:      L = (0,0,0);  A = e * s
+ *   otherwise:   L = e * s;  r = rotate(q, p);  A = cross(r, L)
+ *                cross(a,b) = (a.y*b.z - a.z*b.y,  a.z*b.x - a.x*b.z,  a.x*b.y - a.y*b.x)
+ *   s not finite: L = A = (0,0,0), and the actuator is counted in mgf_batch_counter "actuators_skipped"
+ *                 (cumulative; reading it waits for the stream, like "device_skipped")
+ * wrench_out is optional: when given it receives the six floats (L, A) of actuator i at row i, rows in the order of the array given
+ * to mgf_batch_set_actuators.
+ * WHAT A CALL DOES TO THE BATCH.  MGF_ACTUATE_IMPULSE: the batch ends bit for bit as after mgf_batch_apply_impulses(world, body, n,
+ * L, A) with the rig's (world, body) and those wrenches in rig order - per body, in the caller's order, v = v + L * inv_mass,
+ * omega = omega + I * A.  MGF_ACTUATE_FORCE: per body, in the caller's order, force = force + L, torque = torque + A - what
+ * mgf_batch_get_many's force and torque rows, the same sequential f32 adds on the host and mgf_batch_set_forces give.  The force and
+ * torque rows ACCUMULATE from call to call and hold for every later tick: a caller who wants "gravity plus this tick's thrust" writes
+ * the rest rows first with mgf_batch_set_forces_dev, then calls this.  Nothing else of the tick's state is written: what
+ * mgf_batch_set_forces and mgf_batch_apply_impulses leave alone stays alone, and a world no actuator names is untouched to the bit.
+ * Actuators read no shapes: a batch with bodies of several components is answered, as by the contact sensors.
+ * A pose written with mgf_batch_write_state, mgf_batch_set_many and the like turns the next wrench AT ONCE.
+ * A call is MGF_BATCH_ACTUATOR_LAUNCHES = 1 launch, counted in "drive_launches", whatever the number of actuators and worlds: a lane
+ * per body that has an actuator walks the body's actuators in the caller's order - no float atomic, nothing depends on lane scheduling.
+ * OUT OF SCOPE here: actuators on the lone mgf_world; re-evaluation of a wrench per tick inside a multi-tick mgf_batch_step (a FORCE
+ * wrench stays fixed in the world's frame until the next call); joints and motors between two bodies. */
+#define MGF_ACTUATOR_TORQUE     1   /* a pure couple about d: no force, p is not read */
+#define MGF_ACTUATOR_WORLD_DIR  2   /* d is in world coordinates; the arm p stays in the body's frame */
+#define MGF_ACTUATE_IMPULSE 0
+#define MGF_ACTUATE_FORCE   1
+#define MGF_BATCH_ACTUATOR_LAUNCHES 1  /* what one call adds to "drive_launches" */
+typedef struct mgf_batch_actuator {
+  int32_t world, body; uint32_t flags; float gain;
+  mgf_vec3 p; float lo;
+  mgf_vec3 d; float hi;
+} mgf_batch_actuator;   /* 48 bytes: three 16-byte words */
+/* Replaces the rig by a copy of a[0 .. n); n = 0 clears it.  No device work: the rig goes up with the next call.  Refused with
+ * MGF_ERR_INVALID, the rig as it was ("the rig was not changed"), in this order: what mgf_batch_set_sensors refuses - a NULL batch, a
+ * negative n or n > INT32_MAX, a NULL array with n > 0, then per record a world out of range, a body outside
+ * [0, mgf_batch_len(b, world)) - then a flag bit beyond 3, a non-finite p, d or gain, a NaN lo or hi or lo > hi (-inf and +inf mean
+ * "no clamp").  The rig names (world, body): mgf_batch_add_bodies and mgf_batch_add_compound_bodies afterwards leave every actuator on
+ * the body it named.  Independent of the other five rigs. */
+MGF_API mgf_status mgf_batch_set_actuators(mgf_batch* b, const mgf_batch_actuator* a, int64_t n);
+MGF_API int64_t    mgf_batch_actuator_count(const mgf_batch* b);            /* -1 for NULL */
+/* The wrenches of u[0 .. n) formed and applied (above).  Refused with MGF_ERR_INVALID in this order, nothing enqueued and nothing
+ * changed: a NULL batch, a negative n, a mode other than MGF_ACTUATE_IMPULSE or MGF_ACTUATE_FORCE, n != mgf_batch_actuator_count(b) (a
+ * control vector of the wrong length is a bug, not a prefix), NULL u with a rig that is not empty.  An empty rig: MGF_OK, nothing
+ * enqueued.  Synchronous: one upload of u, one download where wrench_out is given, one host wait. */
+MGF_API mgf_status mgf_batch_actuate(mgf_batch* b, const float* u, int64_t n, int32_t mode, float* wrench_out);
+/* The same with both arrays in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for.  In
+ * the steady state no host wait and no copy between host and device.  Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer
+ * that fails the look-up of the device-pointer calls (4 n bytes of u_dev, 24 n of wrench_out_dev), and wrench_out_dev's bytes
+ * overlapping u_dev's. */
+MGF_API mgf_status mgf_batch_actuate_dev(mgf_batch* b, const float* u_dev, int64_t n, int32_t mode, float* wrench_out_dev);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /

@@ -60,6 +60,11 @@ class BatchFeeler(C.Structure):
                 ("delta", Vec3), ("reserved", C.c_int32 * 2)]
 
 
+class BatchActuator(C.Structure):
+    _fields_ = [("world", C.c_int32), ("body", C.c_int32), ("flags", C.c_uint32), ("gain", C.c_float), ("p", Vec3), ("lo", C.c_float),
+                ("d", Vec3), ("hi", C.c_float)]
+
+
 class Component(C.Structure):
     _fields_ = [("tag", C.c_int32), ("p", Vec3), ("d", Vec3), ("r", C.c_float)]
 
@@ -170,6 +175,13 @@ FEELER_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("tag", "<i4"), ("fl
 assert FEELER_DTYPE.itemsize == C.sizeof(BatchFeeler) == 64
 FEELER_IGNORE_SELF, FEELER_WORLD_DELTA, FEELER_OWN_SHAPE = 1, 2, 4  # MGF_FEELER_IGNORE_SELF, _WORLD_DELTA, _OWN_SHAPE
 BATCH_FEELER_LAUNCHES = 1  # MGF_BATCH_FEELER_LAUNCHES
+# mgf_batch_actuator: a direction d and an arm p fixed in the frame of body `body` of world `world`, a gain and a clamp [lo, hi]
+ACTUATOR_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("flags", "<u4"), ("gain", "<f4"), ("p", "<f4", 3), ("lo", "<f4"),
+                           ("d", "<f4", 3), ("hi", "<f4")])
+assert ACTUATOR_DTYPE.itemsize == C.sizeof(BatchActuator) == 48
+ACTUATOR_TORQUE, ACTUATOR_WORLD_DIR = 1, 2  # MGF_ACTUATOR_TORQUE, _WORLD_DIR
+ACTUATE_IMPULSE, ACTUATE_FORCE = 0, 1  # MGF_ACTUATE_IMPULSE, _FORCE
+BATCH_ACTUATOR_LAUNCHES = 1  # MGF_BATCH_ACTUATOR_LAUNCHES
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -215,6 +227,7 @@ SYMBOLS = [
     "mgf_batch_read_zones_nearest", "mgf_batch_read_zones_nearest_dev", "mgf_batch_overlap_nearest_dev",
     "mgf_batch_set_touches", "mgf_batch_touch_count", "mgf_batch_read_touches", "mgf_batch_read_touches_dev",
     "mgf_batch_set_feelers", "mgf_batch_feeler_count", "mgf_batch_cast_feelers", "mgf_batch_cast_feelers_dev",
+    "mgf_batch_set_actuators", "mgf_batch_actuator_count", "mgf_batch_actuate", "mgf_batch_actuate_dev",
 ]
 
 _lib = None
@@ -405,6 +418,10 @@ def load_library():
         "mgf_batch_feeler_count": (i64, [vp]),
         "mgf_batch_cast_feelers": (i32, [vp, i32, vp, vp, i64]),
         "mgf_batch_cast_feelers_dev": (i32, [vp, i32, vp, vp, i64]),
+        "mgf_batch_set_actuators": (i32, [vp, vp, i64]),
+        "mgf_batch_actuator_count": (i64, [vp]),
+        "mgf_batch_actuate": (i32, [vp, vp, i64, i32, vp]),
+        "mgf_batch_actuate_dev": (i32, [vp, vp, i64, i32, vp]),
         "mgf_batch_set_cameras": (i32, [vp, vp, i64]),
         "mgf_batch_camera_count": (i64, [vp]),
         "mgf_batch_camera_pixels": (i64, [vp]),
@@ -2013,6 +2030,44 @@ class WorldBatch:
         words = "int32" if str(getattr(casts, "dtype", "")) == "torch.int32" else "float32"
         op, cp = _dev_arg(out, "int32", 13, n, "out"), _dev_arg(casts, words, 11, n, "casts")
         _check(load_library().mgf_batch_cast_feelers_dev(self._h, int(kinds), op, cp, n))
+
+    # ---- body-mounted actuators: a rig set once, wrenches formed from the resident poses and applied in one launch ------------------------
+    def set_actuators(self, world, body=None, p=None, d=None, gain=1.0, lo=float("-inf"), hi=float("inf"), torque=False, world_dir=False):
+        """the batch's actuator rig replaced (mgf_batch_set_actuators): actuator i acts on body[i] of world[i] along d[i] - in the
+        body's frame, or (world_dir[i]) in world coordinates - at the arm p[i] in the body's frame, with gain[i] times its control
+        clamped to [lo[i], hi[i]] (-inf / inf: no clamp); torque[i]: a pure couple about d[i], p is not read.  Arrays, or scalars /
+        single rows for all: the number of actuators is that of the longest argument; p and d left None stay zero.  No actuators
+        (empty arrays) clears the rig.  Also takes an ACTUATOR_DTYPE array as `world`, the other arguments not read."""
+        if isinstance(world, np.ndarray) and world.dtype == ACTUATOR_DTYPE:
+            rig = np.ascontiguousarray(world.reshape(-1))
+        else:
+            flags = np.where(np.asarray(torque, bool), ACTUATOR_TORQUE, 0) | np.where(np.asarray(world_dir, bool), ACTUATOR_WORLD_DIR, 0)
+            given = {k: v for k, v in dict(p=p, d=d).items() if v is not None}
+            rig = _rig_rows(ACTUATOR_DTYPE, world=world, body=body, flags=flags, gain=gain, lo=lo, hi=hi, **given)
+        _check(load_library().mgf_batch_set_actuators(self._h, rig.ctypes.data if len(rig) else None, len(rig)))
+
+    def actuator_count(self):
+        return load_library().mgf_batch_actuator_count(self._h)
+
+    def actuate(self, u, mode=ACTUATE_IMPULSE, wrenches=False):
+        """the wrench of every actuator formed from its body's current q and its control u[i], and applied (mgf_batch_actuate):
+        ACTUATE_IMPULSE as apply_impulses of those wrenches in the rig's order; ACTUATE_FORCE added to the force and torque rows, which
+        accumulate from call to call and hold for every later tick.  u: one float an actuator (a scalar: for all).  wrenches=True:
+        returns the float32 [n, 6] array of (L, A) in the rig's order."""
+        n = max(self.actuator_count(), 0)
+        uu = np.ascontiguousarray(np.broadcast_to(np.asarray(u, np.float32), (n,)))
+        out = np.zeros((n, 6), np.float32) if wrenches else None
+        _check(load_library().mgf_batch_actuate(self._h, uu.ctypes.data if n else None, n, int(mode), _ptr(out)))
+        return out
+
+    def actuate_dev(self, u, mode=ACTUATE_IMPULSE, wrenches_out=None):
+        """actuate with the controls in device memory (mgf_batch_actuate_dev), enqueued on the context's stream and not waited for.
+        u: CUDA float32 [n], n = actuator_count(); wrenches_out: CUDA float32 [n, 6] or None - (L, A) of every actuator."""
+        if u is None:
+            raise ValueError("u is required")
+        n = max(self.actuator_count(), 0)
+        up, wp = _dev_arg(u, "float32", 1, n, "u"), _dev_arg(wrenches_out, "float32", 6, n, "wrenches_out")
+        _check(load_library().mgf_batch_actuate_dev(self._h, up, n, int(mode), wp))
 
     def counter(self, name):
         v = C.c_int64()

@@ -102,6 +102,7 @@ struct mgf_batch {
   BatchRig<mgf_batch_zone> zones;       // on the device: items | records | order
   BatchRig<mgf_batch_touch> touches;    // on the device: items | records | order - the contact sensors (host_batch_touch.inc)
   BatchRig<mgf_batch_feeler> feelers;   // on the device: items | records | order | worlds - the feelers (host_batch_feeler.inc)
+  BatchRig<mgf_batch_actuator> actuators;  // on the device: runs | records | order - the actuators; `items` holds the runs of one body (host_batch_actuator.inc)
   // ... and what a call on one of them has nowhere else to put
   DBuf<float> s_parts;                  // the particles of a sensor cast: 7 words a sensor
   size_t c_pixels = 0;                  // the pixels of the camera rig, camera by camera
@@ -111,6 +112,7 @@ struct mgf_batch {
                                         // (host_batch_nearest.inc: records | k distances a zone | boxes)
   DBuf<float4> touch_out;               // what the host-memory read of the contact sensors downloads: four words a sensor
   DBuf<float> f_casts;                  // the casts of a feeler cast where the caller takes none: 11 words a feeler
+  DBuf<unsigned long long> a_skipped;   // actuators whose gain * clamp(u) was not finite, cumulative (counter "actuators_skipped")
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {
@@ -301,6 +303,12 @@ extern "C" mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, in
   if (!strcmp(name, "device_skipped")) {  // (on the device: the stream is waited for)
     unsigned long long v = 0;
     if (b->v_skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, b->v_skipped.p, 1)); }
+    *out = (int64_t)v;
+    return MGF_OK;
+  }
+  if (!strcmp(name, "actuators_skipped")) {  // (on the device: the stream is waited for)
+    unsigned long long v = 0;
+    if (b->a_skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, b->a_skipped.p, 1)); }
     *out = (int64_t)v;
     return MGF_OK;
   }
@@ -535,6 +543,7 @@ static void batch_rigs_stale(mgf_batch* b) {
   b->zones.stale = true;
   b->touches.stale = true;
   b->feelers.stale = true;
+  b->actuators.stale = true;
 }
 
 // the rows of `n` new bodies (empty part slots where the caller has filled none) behind world k's last body

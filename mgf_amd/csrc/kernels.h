@@ -146,6 +146,11 @@
 //                      rotate(q, p), D = rotate(q, d), delta turned by q or kept in world coordinates, and swept against the world's
 //                      staged colliders with k_batch_query_sweep_bodies' walk and reduction (bf_sweep_front); the cast is always
 //                      stored, and k_batch_query_sweep_faces / _sweep_obstacles take it up again from there
+//   k_batch_actuate<MODE, OUT> (k_batch_actuator.h)
+//                      actuators fixed in the frame of a body (mgf_batch_set_actuators / _actuate / _actuate_dev): a lane per run of one
+//                      body's actuators, sorted on the host when the rig is set; per actuator s = gain * clamp(u), the direction and
+//                      the arm turned by the body's q, the wrench (L, A) = (e s, cross(r, L)) or a pure couple, applied in the caller's
+//                      order with batch_drive_apply's arithmetic - an impulse, or added to the force and torque rows; no float atomic
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -173,3 +178,4 @@
 #include "k_batch_nearest.h"  // box zones, nearest first: the count and the k nearest bodies of every box (k_batch_nearest)
 #include "k_batch_touch.h"  // contact sensors: the constraint list folded per (body, partner), a fixed-width report (k_batch_touch)
 #include "k_batch_feeler.h"  // feelers: spheres and capsules fixed in the frame of a body, swept from the resident poses (k_batch_feeler_bodies)
+#include "k_batch_actuator.h"  // actuators: wrenches formed from the resident poses and applied, a lane per body (k_batch_actuate)
