@@ -1232,7 +1232,7 @@ MGF_API mgf_status mgf_batch_cast_feelers_dev(mgf_batch* b, int32_t kinds_mask, 
  * A call is MGF_BATCH_ACTUATOR_LAUNCHES = 1 launch, counted in "drive_launches", whatever the number of actuators and worlds: a lane
  * per body that has an actuator walks the body's actuators in the caller's order - no float atomic, nothing depends on lane scheduling.
  * OUT OF SCOPE here: actuators on the lone mgf_world; re-evaluation of a wrench per tick inside a multi-tick mgf_batch_step (a FORCE
- * wrench stays fixed in the world's frame until the next call); joints and motors between two bodies. */
+ * wrench stays fixed in the world's frame until the next call) (since: Rollouts, below - mgf_batch_rollout); joints and motors between two bodies. */
 #define MGF_ACTUATOR_TORQUE     1   /* a pure couple about d: no force, p is not read */
 #define MGF_ACTUATOR_WORLD_DIR  2   /* d is in world coordinates; the arm p stays in the body's frame */
 #define MGF_ACTUATE_IMPULSE 0
@@ -1261,12 +1261,54 @@ MGF_API mgf_status mgf_batch_actuate(mgf_batch* b, const float* u, int64_t n, in
  * that fails the look-up of the device-pointer calls (4 n bytes of u_dev, 24 n of wrench_out_dev), and wrench_out_dev's bytes
  * overlapping u_dev's. */
 MGF_API mgf_status mgf_batch_actuate_dev(mgf_batch* b, const float* u_dev, int64_t n, int32_t mode, float* wrench_out_dev);
+/* ---- rollouts: n_ticks ticks under n_ticks rows of controls, a row of state traced behind every tick, in ONE step call ----
+ * The inner loop of sampling MPC, of trajectory optimisation and of any open-loop evaluation: a horizon of T ticks under T control
+ * vectors, fanned out over the worlds of a batch (mgf_batch_copy_worlds copies one state to K worlds).  Call by call it costs T host
+ * waits; a rollout is the same loop with the step's one.
+ * THE DEFINITION is calls that exist, bit for bit.  With u[T][n_act], a mode, m flat body indices body[] (NULL: body i) and outputs
+ * x[T][m][3], q[T][m][4], v[T][m][3], omega[T][m][3], any of them NULL, a rollout of T = n_ticks leaves the batch and the outputs as
+ *   for t in 0 .. T-1:
+ *     mgf_batch_actuate_dev(b, u[t], n_act, mode, NULL)                                        (skipped when n_act == 0)
+ *     mgf_batch_step(b, dt, iters, 1, stats + t * n_worlds)
+ *     mgf_batch_gather_state_dev(b, body, m, x[t], q[t], v[t], omega[t], NULL, NULL)           (skipped when m == 0)
+ * leaves them: state, delta, the force and torque rows, the last tick's constraint lists, the stats rows, "actuators_skipped",
+ * "device_skipped" (an index of body[] outside the batch is skipped and counted once a tick, its rows are not written), and what every
+ * rig and reader reports afterwards - the last tick.  MGF_ACTUATE_FORCE accumulates from tick to tick exactly as the loop's calls
+ * would.  n_act == 0 and nothing traced: mgf_batch_step(b, dt, iters, n_ticks, stats).  Actuators and the gather read no shapes: a batch
+ * with bodies of several components is answered.
+ * ONE HOST WAIT per pass of the step's re-run loop - one when no world outgrows its share of the storage.  A world whose tick did not
+ * fit is undone, sits out the rest of the pass and is run again from that tick ("capacity_retries", as in the step); its control
+ * row is applied ONCE all the same - the undo keeps tick t's impulse and never held the force rows, so the re-run does not actuate
+ * again - and its trace rows are written in the pass in which it completes the tick.
+ * The call adds at most MGF_BATCH_ROLLOUT_LAUNCHES_PER_TICK launches to a tick's own ("launches_per_tick" keeps its meaning and value):
+ * one ahead of the tick where the rig is not empty, one behind it - whatever the worlds, the actuators and the traced bodies.
+ * mgf_batch_counter "rollout_launches": the launches of the last rollout call beyond its ticks' own.  "drive_launches" is not touched.
+ * REFUSED with MGF_ERR_INVALID, nothing enqueued and nothing changed, in this order - ahead of the handle's contents: a NULL batch; a
+ * negative n_ticks, iters, n_act or m, in that order; n_ticks > 2^20; a mode other than MGF_ACTUATE_IMPULSE or MGF_ACTUATE_FORCE;
+ * m > INT32_MAX; a byte count (4 * n_ticks * n_act; 16 * n_ticks * m cannot) that overflows int64_t - then the handle's own:
+ * n_act != mgf_batch_actuator_count(b); NULL u with n_act > 0 and n_ticks > 0; body == NULL with m > mgf_batch_len(b, -1).
+ * n_ticks == 0: MGF_OK, nothing enqueued beyond what mgf_batch_step(b, dt, iters, 0, stats) does.
+ * OUT OF SCOPE here: closed-loop policies inside the call (u is fixed when the call is made); a step with no host wait at all; the
+ * wrenches per tick; contact or touch sums per tick; a world mask; the lone mgf_world; hipGraph capture. */
+#define MGF_BATCH_ROLLOUT_LAUNCHES_PER_TICK 2  /* what the call adds to a tick's launches, at most */
+/* The host form: one upload (u and body), the device core, one download (the outputs given).  stats: NULL or n_ticks * n_worlds rows,
+ * row t * n_worlds + k world k's tick t.  A row of an index outside the batch comes back as zeros. */
+MGF_API mgf_status mgf_batch_rollout(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u, int64_t n_act, int32_t mode,
+                                     const int32_t* body, int64_t m, float* x, float* q, float* v, float* omega, mgf_step_stats* stats);
+/* The same with u, body and the outputs in device memory (the device-pointer calls, above); stats stays host memory.  No copy between
+ * host and device beyond the step's own.  Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the
+ * device-pointer calls for its full extent (4 * n_ticks * n_act bytes of u_dev, 4 m of body_dev, 12 * n_ticks * m of x_dev, v_dev and
+ * omega_dev, 16 * n_ticks * m of q_dev), an output's bytes overlapping another output's or an input's.  A row of an index outside the
+ * batch is left as the caller had it. */
+MGF_API mgf_status mgf_batch_rollout_dev(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u_dev, int64_t n_act, int32_t mode,
+                                         const int32_t* body_dev, int64_t m, float* x_dev, float* q_dev, float* v_dev, float* omega_dev, mgf_step_stats* stats);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /
  * _set_forces / _apply_impulses / _copy_worlds call or device-pointer call on this batch - for a copy, on its destination: it depends on
  * neither n_worlds nor n), "device_skipped" (records of the device-pointer calls whose index was out of range, cumulative; waits for the
- * stream), "pair_table_uploads" (uploads of mgf_batch_copy_worlds_where's pair table, cumulative)}. */
+ * stream), "pair_table_uploads" (uploads of mgf_batch_copy_worlds_where's pair table, cumulative), "actuators_skipped" (above),
+ * "rollout_launches" (launches of the last mgf_batch_rollout / _rollout_dev call beyond its ticks' own)}. */
 MGF_API mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out);
 /* Options (test knobs): "cons_per_body" [4] = the constraint records per body a world's share of the storage starts with (1 .. 4096); a
  * low value makes the first busy tick outgrow it, which the re-run path then handles. */

@@ -13,4 +13,5 @@ from ._capi import (MgfError, Context, Mesh, Bvh, World, WorldBatch, BATCH_MAX_B
                     RAY_HIT_DTYPE, SWEEP_HIT_DTYPE, BODY_CONTACTS_DTYPE, BODY_GET_DTYPE, HIT_NONE, HIT_BODY, HIT_TERRAIN, HIT_OBSTACLE, QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL,
                     TOUCH_DTYPE, TOUCH_REPORT_DTYPE, TOUCH_STATIC, TOUCH_ANY_BODY, TOUCH_ANY, TOUCH_NONE, TOUCH_BODY_FRAME, BATCH_TOUCH_LAUNCHES,
                     FEELER_DTYPE, FEELER_IGNORE_SELF, FEELER_WORLD_DELTA, FEELER_OWN_SHAPE, BATCH_FEELER_LAUNCHES,
-                    ACTUATOR_DTYPE, ACTUATOR_TORQUE, ACTUATOR_WORLD_DIR, ACTUATE_IMPULSE, ACTUATE_FORCE, BATCH_ACTUATOR_LAUNCHES)
+                    ACTUATOR_DTYPE, ACTUATOR_TORQUE, ACTUATOR_WORLD_DIR, ACTUATE_IMPULSE, ACTUATE_FORCE, BATCH_ACTUATOR_LAUNCHES,
+                    BATCH_ROLLOUT_LAUNCHES_PER_TICK)

@@ -182,6 +182,7 @@ assert ACTUATOR_DTYPE.itemsize == C.sizeof(BatchActuator) == 48
 ACTUATOR_TORQUE, ACTUATOR_WORLD_DIR = 1, 2  # MGF_ACTUATOR_TORQUE, _WORLD_DIR
 ACTUATE_IMPULSE, ACTUATE_FORCE = 0, 1  # MGF_ACTUATE_IMPULSE, _FORCE
 BATCH_ACTUATOR_LAUNCHES = 1  # MGF_BATCH_ACTUATOR_LAUNCHES
+BATCH_ROLLOUT_LAUNCHES_PER_TICK = 2  # MGF_BATCH_ROLLOUT_LAUNCHES_PER_TICK
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -228,6 +229,7 @@ SYMBOLS = [
     "mgf_batch_set_touches", "mgf_batch_touch_count", "mgf_batch_read_touches", "mgf_batch_read_touches_dev",
     "mgf_batch_set_feelers", "mgf_batch_feeler_count", "mgf_batch_cast_feelers", "mgf_batch_cast_feelers_dev",
     "mgf_batch_set_actuators", "mgf_batch_actuator_count", "mgf_batch_actuate", "mgf_batch_actuate_dev",
+    "mgf_batch_rollout", "mgf_batch_rollout_dev",
 ]
 
 _lib = None
@@ -422,6 +424,8 @@ def load_library():
         "mgf_batch_actuator_count": (i64, [vp]),
         "mgf_batch_actuate": (i32, [vp, vp, i64, i32, vp]),
         "mgf_batch_actuate_dev": (i32, [vp, vp, i64, i32, vp]),
+        "mgf_batch_rollout": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp]),
+        "mgf_batch_rollout_dev": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp]),
         "mgf_batch_set_cameras": (i32, [vp, vp, i64]),
         "mgf_batch_camera_count": (i64, [vp]),
         "mgf_batch_camera_pixels": (i64, [vp]),
@@ -2068,6 +2072,73 @@ class WorldBatch:
         n = max(self.actuator_count(), 0)
         up, wp = _dev_arg(u, "float32", 1, n, "u"), _dev_arg(wrenches_out, "float32", 6, n, "wrenches_out")
         _check(load_library().mgf_batch_actuate_dev(self._h, up, n, int(mode), wp))
+
+    # ---- rollouts: T ticks under T rows of controls, a row of state traced behind every tick, in one step call ---------------------------
+    def rollout(self, u, dt, iters, mode=ACTUATE_IMPULSE, body=None, trace=("x", "q", "v", "omega")):
+        """T ticks as the loop actuate(u[t]) | step(dt, iters) | gather of `body` leaves the batch, with the step's one host wait
+        (mgf_batch_rollout).  u: float32 [T, actuator_count()] (an int T where the rig is empty); body: flat indices (None: every
+        body); trace: which of x (= x + delta), q, v, omega to return.  Returns a dict of float32 [T, m, 3 | 4] arrays by name and
+        "stats", arr[t * n_worlds + k] = world k's tick t."""
+        n = max(self.actuator_count(), 0)
+        if isinstance(u, (int, np.integer)):
+            if n:
+                raise ValueError("u: a number of ticks stands for the controls of an empty rig only")
+            uu = np.zeros((int(u), 0), np.float32)
+        else:
+            uu = np.ascontiguousarray(u, np.float32)
+        if uu.ndim != 2 or uu.shape[1] != n:
+            raise ValueError(f"u: {uu.shape} is not [T, {n}]")
+        unknown = [k for k in trace if k not in ("x", "q", "v", "omega")]
+        if unknown:
+            raise ValueError(f"trace: {unknown[0]!r} is not one of x, q, v, omega")
+        T = uu.shape[0]
+        bb = None if body is None else np.ascontiguousarray(body, np.int32).reshape(-1)
+        m = len(self) if bb is None else len(bb)
+        out = {k: np.zeros((T, m, 4 if k == "q" else 3), np.float32) for k in ("x", "q", "v", "omega") if k in trace}
+        arr = (StepStats * (T * self.n_worlds))()
+        _check(load_library().mgf_batch_rollout(self._h, float(dt), int(iters), T, uu.ctypes.data if uu.size else None, n, int(mode),
+                                                bb.ctypes.data if bb is not None and m else None, m,
+                                                *[out[k].ctypes.data if k in out and out[k].size else None for k in ("x", "q", "v", "omega")], arr))
+        out["stats"] = arr
+        return out
+
+    def rollout_dev(self, u, dt, iters, mode=ACTUATE_IMPULSE, body=None, x=None, q=None, v=None, omega=None):
+        """rollout with the controls, the indices and the traces in device memory (mgf_batch_rollout_dev).  u: CUDA float32
+        [T, actuator_count()] (an int T where the rig is empty); body: CUDA int32 [m] or None - every body; x, v, omega: CUDA float32
+        [T, m, 3], q: [T, m, 4], None: not asked for.  Returns the statistics, arr[t * n_worlds + k] = world k's tick t; the traces
+        are complete when the call returns (it waits as step does)."""
+        if u is None:
+            raise ValueError("u is required")
+        n = max(self.actuator_count(), 0)
+        if isinstance(u, (int, np.integer)):
+            if n:
+                raise ValueError("u: a number of ticks stands for the controls of an empty rig only")
+            T, up = int(u), None
+        else:
+            if not hasattr(u, "data_ptr"):
+                raise ValueError(f"u: a torch tensor on the GPU, not {type(u).__name__}")
+            if u.dim() != 2 or u.shape[1] != n:
+                raise ValueError(f"u: {tuple(u.shape)} is not [T, {n}]")
+            T = int(u.shape[0])
+            up = _dev_arg(u, "float32", n, T, "u")
+        if body is None:
+            bp, m = None, len(self)
+        else:
+            if not hasattr(body, "data_ptr"):
+                raise ValueError(f"body: a torch tensor on the GPU, not {type(body).__name__}")
+            m = int(body.numel())
+            bp = _dev_arg(body, "int32", 1, m, "body")
+        p = []
+        for a, name, cols in ((x, "x", 3), (q, "q", 4), (v, "v", 3), (omega, "omega", 3)):
+            if a is not None:
+                if not hasattr(a, "data_ptr"):
+                    raise ValueError(f"{name}: a torch tensor on the GPU, not {type(a).__name__}")
+                if tuple(a.shape) != (T, m, cols):
+                    raise ValueError(f"{name}: {tuple(a.shape)} is not [{T}, {m}, {cols}]")
+            p.append(_dev_arg(a, "float32", m * cols, T, name))
+        arr = (StepStats * (T * self.n_worlds))()
+        _check(load_library().mgf_batch_rollout_dev(self._h, float(dt), int(iters), T, up, n, int(mode), bp, m, *p, arr))
+        return arr
 
     def counter(self, name):
         v = C.c_int64()

@@ -113,6 +113,9 @@ struct mgf_batch {
   DBuf<float4> touch_out;               // what the host-memory read of the contact sensors downloads: four words a sensor
   DBuf<float> f_casts;                  // the casts of a feeler cast where the caller takes none: 11 words a feeler
   DBuf<unsigned long long> a_skipped;   // actuators whose gain * clamp(u) was not finite, cumulative (counter "actuators_skipped")
+  // the rollouts (host_batch_rollout.inc)
+  DBuf<uint32_t> d_act;                 // per world, beside d_done: ticks of the call whose actuation the world has behind it (k_batch_rollout.h)
+  int64_t r_launches = 0;               // launches of the last rollout call beyond its ticks' own (counter "rollout_launches")
 
   size_t total() const { return h_off.empty() ? 0 : h_off.back(); }
   Bodies bodies(size_t first) const {
@@ -299,6 +302,7 @@ extern "C" mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, in
   if (!strcmp(name, "query_launches")) { *out = b->q_launches; return MGF_OK; }
   if (!strcmp(name, "query_run_ns")) { *out = (int64_t)((double)b->q_run_ms * 1e6); return MGF_OK; }
   if (!strcmp(name, "drive_launches")) { *out = b->d_launches; return MGF_OK; }
+  if (!strcmp(name, "rollout_launches")) { *out = b->r_launches; return MGF_OK; }
   if (!strcmp(name, "pair_table_uploads")) { *out = b->w_uploads; return MGF_OK; }
   if (!strcmp(name, "device_skipped")) {  // (on the device: the stream is waited for)
     unsigned long long v = 0;
@@ -839,13 +843,19 @@ static mgf_status batch_collide_parts(mgf_batch* b, const BatchArgs& A, uint32_t
   return MGF_OK;
 }
 
-// n_ticks x World::step (world.rs:227-294) of every world: one launch per tick, no host wait between the ticks.
-extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats) {
-  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
-  if (n_ticks < 0) return fail(MGF_ERR_INVALID, "n_ticks is negative");
-  if (iters < 0) return fail(MGF_ERR_INVALID, "iters is negative");
-  if (n_ticks > (1 << 20)) return fail(MGF_ERR_INVALID, "n_ticks must be at most 2^20");
-  MGF_TRY(ctx_bind(b->ctx));
+// What a rollout (host_batch_rollout.inc, k_batch_rollout.h) hangs into the step's launch train: row t of the controls applied ahead of
+// tick t's launches, row t of the traces written behind them - both under the train's own gate, so that they are skipped and run again
+// world by world as the tick's launches are.
+struct BatchRolloutHook {
+  BatchRolloutArgs A;    // everything but done, act, tick and count, which the train fills in
+  int32_t mode = 0;      // MGF_ACTUATE_IMPULSE / _FORCE
+  bool act = false;      // the rig is not empty: k_batch_rollout_act ahead of every tick
+  int64_t launches = 0;  // what the hook added to the train's launches
+};
+
+// The step's launch train, behind the refusals: n_ticks x World::step (world.rs:227-294) of every world, six (seven) launches a tick, one
+// host wait per pass - and with a hook a rollout's two launches a tick among them.  hook == nullptr: mgf_batch_step, launch for launch.
+static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats, BatchRolloutHook* hook) {
   MGF_TRY(batch_push(b));
   MGF_TRY(batch_env_sync(b));
   if (n_ticks == 0) return MGF_OK;
@@ -865,8 +875,15 @@ extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int6
   MGF_HIP_TRY(hipMemsetAsync(b->d_done.p, 0, 4 * (size_t)K, s));
   MGF_HIP_TRY(hipMemsetAsync(b->d_need.p, 0, 8 * (size_t)K, s));
   MGF_HIP_TRY(hipMemsetAsync(b->d_stage.p, 0, 4 * (size_t)K, s));
+  if (hook) {  // (the word beside `done`, zeroed where `done` is)
+    MGF_TRY(b->d_act.ensure(K, s));
+    MGF_HIP_TRY(hipMemsetAsync(b->d_act.p, 0, 4 * (size_t)K, s));
+    hook->A.done = b->d_done.p; hook->A.act = b->d_act.p;
+  }
+  const unsigned hook_act_blocks = hook ? (unsigned)((hook->A.n_runs + kBatchBlock - 1) / kBatchBlock) : 0u;
+  const unsigned hook_rec_blocks = hook ? (unsigned)((std::max(hook->A.m, K) + kBatchBlock - 1) / kBatchBlock) : 0u;
   std::vector<uint32_t> done(K), need(2 * (size_t)K);
-  for (uint32_t first = 0; first < NT;) {
+  for (uint32_t first = 0, pass = 0; first < NT; ++pass) {
     BatchArgs A;
     memset(&A, 0, sizeof(A));
     A.B = b->bodies(0);
@@ -882,12 +899,24 @@ extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int6
     A.dt = dt; A.fat_margin = b->params.fat_margin; A.baumgarte = b->params.baumgarte; A.slop = b->params.penetration_slop;
     for (uint32_t t = first; t < NT; ++t) {
       A.tick = t;
+      if (hook) { hook->A.tick = t; hook->A.count = pass == 0 ? 1u : 0u; }  // (an index outside the batch is counted once a tick)
+      if (hook && hook->act) {
+        if (hook->mode == MGF_ACTUATE_IMPULSE) k_batch_rollout_act<ACTUATE_IMPULSE><<<hook_act_blocks, kBatchBlock, 0, s>>>(hook->A);
+        else k_batch_rollout_act<ACTUATE_FORCE><<<hook_act_blocks, kBatchBlock, 0, s>>>(hook->A);
+        LAUNCH_CHECK();
+        ++hook->launches;
+      }
       if (b->parts) MGF_TRY(batch_collide_parts(b, A, nmax));
       else MGF_TRY(batch_collide(b, A, nmax));
       k_batch_setup<<<K, kBatchBlock, 12u * nmax, s>>>(A);
       LAUNCH_CHECK();
       k_batch_solve<<<K, kBatchBlock, lds, s>>>(A);
       LAUNCH_CHECK();
+      if (hook) {
+        k_batch_rollout_record<<<hook_rec_blocks, kBatchBlock, 0, s>>>(hook->A);
+        LAUNCH_CHECK();
+        ++hook->launches;
+      }
     }
     MGF_TRY(d2h(ctx, done.data(), b->d_done.p, K));
     uint32_t err = 0;
@@ -918,6 +947,16 @@ extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int6
     }
   }
   return MGF_OK;
+}
+
+// n_ticks x World::step (world.rs:227-294) of every world: one launch per tick, no host wait between the ticks.
+extern "C" mgf_status mgf_batch_step(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats) {
+  if (!b) return fail(MGF_ERR_INVALID, "batch is NULL");
+  if (n_ticks < 0) return fail(MGF_ERR_INVALID, "n_ticks is negative");
+  if (iters < 0) return fail(MGF_ERR_INVALID, "iters is negative");
+  if (n_ticks > (1 << 20)) return fail(MGF_ERR_INVALID, "n_ticks must be at most 2^20");
+  MGF_TRY(ctx_bind(b->ctx));
+  return batch_step_run(b, dt, iters, n_ticks, stats, nullptr);
 }
 
 // The Solver's constraint list of world `world`'s last tick, in insertion order (bodies named by their index in the world).

@@ -1,0 +1,140 @@
+// mgf_batch_rollout, mgf_batch_rollout_dev: n_ticks ticks of a batch with a row of controls applied ahead of every tick and a row of
+// state written behind it - the loop  mgf_batch_actuate_dev(u[t]) | mgf_batch_step(1) | mgf_batch_gather_state_dev(row t)  in one call
+// with the step's one host wait per pass (k_batch_rollout.h).  Part of the single translation unit mgf_hip.hip (included there, in
+// order, behind host_batch_actuator.inc); not compiled on its own.
+//
+// The launch train is the step's own (batch_step_run, host_batch.inc) with a hook: k_batch_rollout_act ahead of a tick's launches where
+// the rig is not empty, k_batch_rollout_record behind them - MGF_BATCH_ROLLOUT_LAUNCHES_PER_TICK = 2 at most, whatever the worlds, the
+// actuators and the traced bodies ("rollout_launches").  Both obey the train's gate world by world, and the word `act` beside `done`
+// keeps a world whose tick is run again from being actuated twice (k_batch_rollout.h).  The rig is the actuators' (BatchRig::items: no
+// plan and no upload format of its own), the trace rows are k_batch_dev_gather's.  "drive_launches" is not touched.
+// The order of both calls: the refusals that need no handle, the handle's own, (device form) EVERY device pointer looked up for its
+// n_ticks-fold extent and the outputs held against each other and against the inputs - and only then the first thing is enqueued.
+
+struct RolloutBytes { size_t u, body, out[4]; };  // what the call touches of u, body, x, q, v, omega
+
+// the refusals of both forms, in the header's order; nothing is enqueued here
+static mgf_status batch_rollout_args(const mgf_batch* b, int32_t iters, int64_t n_ticks, const float* u, int64_t n_act, int32_t mode, const int32_t* body,
+                                     int64_t m, RolloutBytes* bytes) {
+  MGF_TRY(batch_rig_handle(b));
+  if (n_ticks < 0) return fail(MGF_ERR_INVALID, "n_ticks is negative");
+  if (iters < 0) return fail(MGF_ERR_INVALID, "iters is negative");
+  if (n_act < 0) return fail(MGF_ERR_INVALID, "n_act is negative");
+  if (m < 0) return fail(MGF_ERR_INVALID, "m is negative");
+  if (n_ticks > (1 << 20)) return fail(MGF_ERR_INVALID, "n_ticks must be at most 2^20");
+  if (mode != MGF_ACTUATE_IMPULSE && mode != MGF_ACTUATE_FORCE) return fail(MGF_ERR_INVALID, "mode is neither MGF_ACTUATE_IMPULSE nor MGF_ACTUATE_FORCE");
+  if (m > (int64_t)INT32_MAX) return fail(MGF_ERR_INVALID, "too many traced bodies in one call");
+  // (n_ticks <= 2^20 and m < 2^31: 16 * n_ticks * m < 2^55)
+  if (n_ticks > 0 && n_act > INT64_MAX / 4 / n_ticks) return fail(MGF_ERR_INVALID, "4 * n_ticks * n_act overflows int64_t");
+  if ((uint64_t)n_act != (uint64_t)b->actuators.recs.size()) return fail(MGF_ERR_INVALID, "n_act is not mgf_batch_actuator_count: control rows of another length than the rig");
+  if (n_act > 0 && n_ticks > 0 && !u) return fail(MGF_ERR_INVALID, "NULL argument: u");
+  if (!body && m > mgf_batch_len(b, -1)) return fail(MGF_ERR_INVALID, "without body indices m is at most the number of bodies");
+  const size_t T = (size_t)n_ticks, M = (size_t)m;
+  bytes->u = 4 * T * (size_t)n_act; bytes->body = 4 * M;
+  bytes->out[0] = 12 * T * M; bytes->out[1] = 16 * T * M; bytes->out[2] = 12 * T * M; bytes->out[3] = 12 * T * M;
+  return MGF_OK;
+}
+
+// The device core, behind every check: the arrays are device memory (the caller's or the handle's).
+static mgf_status batch_rollout_run(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u_dev, int64_t n_act, int32_t mode, const int32_t* body_dev,
+                                    int64_t m, float* x, float* q, float* v, float* omega, mgf_step_stats* stats) {
+  b->r_launches = 0;
+  const bool trace = m > 0 && (x || q || v || omega);
+  if (n_ticks == 0 || (n_act == 0 && !trace)) return batch_step_run(b, dt, iters, n_ticks, stats, nullptr);
+  hipStream_t s = b->ctx->stream;
+  BatchRig<mgf_batch_actuator>& R = b->actuators;
+  MGF_TRY(batch_push(b));
+  BatchRolloutHook H;
+  memset(&H.A, 0, sizeof(H.A));
+  if (n_act > 0) {
+    MGF_TRY(batch_rig_up(b, R, "actuator", 3));
+    if (!b->a_skipped.p) {
+      MGF_TRY(b->a_skipped.ensure(1, s));
+      MGF_HIP_TRY(hipMemsetAsync(b->a_skipped.p, 0, sizeof(unsigned long long), s));
+    }
+    H.A.runs = reinterpret_cast<const uint4*>(R.dev.p);
+    H.A.rig = R.dev.p + R.off[1];
+    H.A.order = reinterpret_cast<const uint32_t*>(R.dev.p + R.off[2]);
+    H.A.u = u_dev;
+    H.A.a_skipped = b->a_skipped.p;
+    H.A.n_runs = (uint32_t)R.items.size();
+    H.A.n_act = (uint32_t)n_act;
+    H.act = true;
+  }
+  if (trace) {
+    if (!b->v_skipped.p) {
+      MGF_TRY(b->v_skipped.ensure(1, s));
+      MGF_HIP_TRY(hipMemsetAsync(b->v_skipped.p, 0, sizeof(unsigned long long), s));
+    }
+    H.A.body = body_dev; H.A.m = (uint32_t)m;
+    H.A.x = x; H.A.q = q; H.A.v = v; H.A.om = omega;
+    H.A.v_skipped = b->v_skipped.p;
+  }
+  H.A.B = b->bodies(0);
+  H.A.w_off = b->d_off.p;
+  H.A.total = (uint32_t)b->total();
+  H.A.n_worlds = b->K;
+  H.mode = mode;
+  const mgf_status st = batch_step_run(b, dt, iters, n_ticks, stats, &H);
+  b->r_launches = H.launches;
+  return st;
+}
+
+extern "C" mgf_status mgf_batch_rollout_dev(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u_dev, int64_t n_act, int32_t mode,
+                                            const int32_t* body_dev, int64_t m, float* x_dev, float* q_dev, float* v_dev, float* omega_dev, mgf_step_stats* stats) {
+  RolloutBytes n;
+  MGF_TRY(batch_rollout_args(b, iters, n_ticks, u_dev, n_act, mode, body_dev, m, &n));
+  MGF_TRY(ctx_bind(b->ctx));
+  MGF_TRY(dev_span(b->ctx, u_dev, n.u, "u_dev"));
+  MGF_TRY(dev_span(b->ctx, body_dev, n.body, "body_dev"));
+  MGF_TRY(dev_span(b->ctx, x_dev, n.out[0], "x_dev"));
+  MGF_TRY(dev_span(b->ctx, q_dev, n.out[1], "q_dev"));
+  MGF_TRY(dev_span(b->ctx, v_dev, n.out[2], "v_dev"));
+  MGF_TRY(dev_span(b->ctx, omega_dev, n.out[3], "omega_dev"));
+  const DevBytes arrays[6] = {{x_dev, n.out[0], "x_dev"}, {q_dev, n.out[1], "q_dev"}, {v_dev, n.out[2], "v_dev"}, {omega_dev, n.out[3], "omega_dev"},
+                              {u_dev, n.u, "u_dev"}, {body_dev, n.body, "body_dev"}};
+  MGF_TRY(dev_outputs_overlap(arrays, 6, 4));
+  return batch_rollout_run(b, dt, iters, n_ticks, u_dev, n_act, mode, body_dev, m, x_dev, q_dev, v_dev, omega_dev, stats);
+}
+
+// The host form: one upload (u | body), the device core, one download (x | q | v | omega).  A row of an index outside the batch, which
+// the device form leaves as the caller had it, comes back as zeros: the handle's buffer is cleared, not filled from the caller's rows.
+extern "C" mgf_status mgf_batch_rollout(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u, int64_t n_act, int32_t mode, const int32_t* body,
+                                        int64_t m, float* x, float* q, float* v, float* omega, mgf_step_stats* stats) {
+  RolloutBytes n;
+  MGF_TRY(batch_rollout_args(b, iters, n_ticks, u, n_act, mode, body, m, &n));
+  MGF_TRY(ctx_bind(b->ctx));
+  hipStream_t s = b->ctx->stream;
+  float* host_out[4] = {x, q, v, omega};
+  // the handle's buffer, every section from a 16-byte boundary: u | body | x | q | v | omega
+  size_t off[7] = {0, 0, 0, 0, 0, 0, 0};
+  off[1] = (n.u + 15) / 16;
+  off[2] = off[1] + (body ? (n.body + 15) / 16 : 0);
+  for (int k = 0; k < 4; ++k) off[3 + k] = off[2 + k] + (host_out[k] ? (n.out[k] + 15) / 16 : 0);
+  float* dev_out[4] = {nullptr, nullptr, nullptr, nullptr};
+  const float* u_dev = nullptr;
+  const int32_t* body_dev = nullptr;
+  std::vector<float4> stage;
+  if (off[6]) {
+    MGF_TRY(b->q_in.ensure(off[6], s));
+    if (n.u) u_dev = reinterpret_cast<const float*>(b->q_in.p);
+    if (body && n.body) body_dev = reinterpret_cast<const int32_t*>(b->q_in.p + off[1]);
+    for (int k = 0; k < 4; ++k)
+      if (host_out[k] && n.out[k]) dev_out[k] = reinterpret_cast<float*>(b->q_in.p + off[2 + k]);
+    if (off[2]) {
+      stage.resize(off[2]);
+      if (n.u) memcpy(stage.data(), u, n.u);
+      if (body_dev) memcpy(stage.data() + off[1], body, n.body);
+      MGF_TRY(h2d(b->ctx, b->q_in.p, stage.data(), off[2]));
+    }
+    if (off[6] > off[2]) MGF_HIP_TRY(hipMemsetAsync(b->q_in.p + off[2], 0, 16 * (off[6] - off[2]), s));
+  }
+  MGF_TRY(batch_rollout_run(b, dt, iters, n_ticks, u_dev, n_act, mode, body_dev, m, dev_out[0], dev_out[1], dev_out[2], dev_out[3], stats));
+  if (off[6] > off[2]) {
+    stage.resize(off[6] - off[2]);
+    MGF_TRY(d2h(b->ctx, stage.data(), b->q_in.p + off[2], stage.size()));
+    for (int k = 0; k < 4; ++k)
+      if (dev_out[k]) memcpy(host_out[k], stage.data() + (off[2 + k] - off[2]), n.out[k]);
+  }
+  return MGF_OK;
+}

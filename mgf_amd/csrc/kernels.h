@@ -151,6 +151,11 @@
 //                      body's actuators, sorted on the host when the rig is set; per actuator s = gain * clamp(u), the direction and
 //                      the arm turned by the body's q, the wrench (L, A) = (e s, cross(r, L)) or a pure couple, applied in the caller's
 //                      order with batch_drive_apply's arithmetic - an impulse, or added to the force and torque rows; no float atomic
+//   k_batch_rollout_act<MODE> / k_batch_rollout_record (k_batch_rollout.h)
+//                      a rollout's two launches a tick inside the step's launch train (mgf_batch_rollout / _rollout_dev): k_batch_actuate's
+//                      walk on row t of the controls ahead of tick t's launches, k_batch_dev_gather's rows into row t of the traces
+//                      behind them - both under the train's gate done[k] == tick, and a word `act` beside `done` that keeps a world
+//                      whose tick is undone and run again from being actuated twice; record advances it, a lane per world
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -179,3 +184,4 @@
 #include "k_batch_touch.h"  // contact sensors: the constraint list folded per (body, partner), a fixed-width report (k_batch_touch)
 #include "k_batch_feeler.h"  // feelers: spheres and capsules fixed in the frame of a body, swept from the resident poses (k_batch_feeler_bodies)
 #include "k_batch_actuator.h"  // actuators: wrenches formed from the resident poses and applied, a lane per body (k_batch_actuate)
+#include "k_batch_rollout.h"  // rollouts: a row of controls ahead of every tick of a step call, a row of state behind it (k_batch_rollout_act, _record)
