@@ -1232,7 +1232,8 @@ MGF_API mgf_status mgf_batch_cast_feelers_dev(mgf_batch* b, int32_t kinds_mask, 
  * A call is MGF_BATCH_ACTUATOR_LAUNCHES = 1 launch, counted in "drive_launches", whatever the number of actuators and worlds: a lane
  * per body that has an actuator walks the body's actuators in the caller's order - no float atomic, nothing depends on lane scheduling.
  * OUT OF SCOPE here: actuators on the lone mgf_world; re-evaluation of a wrench per tick inside a multi-tick mgf_batch_step (a FORCE
- * wrench stays fixed in the world's frame until the next call) (since: Rollouts, below - mgf_batch_rollout); joints and motors between two bodies. */
+ * wrench stays fixed in the world's frame until the next call) (since: Rollouts, below - mgf_batch_rollout); joints and motors between two bodies (spring-dampers since: Springs
+ * between bodies, below - mgf_batch_set_springs). */
 #define MGF_ACTUATOR_TORQUE     1   /* a pure couple about d: no force, p is not read */
 #define MGF_ACTUATOR_WORLD_DIR  2   /* d is in world coordinates; the arm p stays in the body's frame */
 #define MGF_ACTUATE_IMPULSE 0
@@ -1290,7 +1291,7 @@ MGF_API mgf_status mgf_batch_actuate_dev(mgf_batch* b, const float* u_dev, int64
  * n_ticks == 0: MGF_OK, nothing enqueued beyond what mgf_batch_step(b, dt, iters, 0, stats) does.
  * OUT OF SCOPE here: closed-loop policies inside the call (u is fixed when the call is made); a step with no host wait at all; the
  * wrenches per tick; contact or touch sums per tick; a world mask; the lone mgf_world; hipGraph capture. */
-#define MGF_BATCH_ROLLOUT_LAUNCHES_PER_TICK 2  /* what the call adds to a tick's launches, at most */
+#define MGF_BATCH_ROLLOUT_LAUNCHES_PER_TICK 2  /* what the call adds to a tick's launches, at most, with an empty spring rig */
 /* The host form: one upload (u and body), the device core, one download (the outputs given).  stats: NULL or n_ticks * n_worlds rows,
  * row t * n_worlds + k world k's tick t.  A row of an index outside the batch comes back as zeros. */
 MGF_API mgf_status mgf_batch_rollout(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u, int64_t n_act, int32_t mode,
@@ -1302,13 +1303,80 @@ MGF_API mgf_status mgf_batch_rollout(mgf_batch* b, float dt, int32_t iters, int6
  * batch is left as the caller had it. */
 MGF_API mgf_status mgf_batch_rollout_dev(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u_dev, int64_t n_act, int32_t mode,
                                          const int32_t* body_dev, int64_t m, float* x_dev, float* q_dev, float* v_dev, float* omega_dev, mgf_step_stats* stats);
+/* ---- springs between bodies: spring-dampers between two body-fixed points, impulses formed from the resident state ----
+ * A tendon, a tether, a suspension strut, a soft hinge made of two springs, a body tied to a point of the world: the seventh rig and
+ * the second on the action side - set once, checked and sorted on the host, applied from the state resident on the device.  What a
+ * caller otherwise assembles per tick (mgf_batch_gather_state_dev of both ends, two arms turned by two quaternions, point velocities,
+ * a length, a unit vector, a clamp, two cross products, a sum per body, mgf_batch_apply_impulses_dev) is here one call whose answer is
+ * defined to the bit - and, ahead of every tick, part of a rollout.  No solver constraint: the reference has no joint (solver.rs knows
+ * ContactConstraint only), and no tick kernel changes.
+ * A spring is a record (world, body, other, flags, pa, rest, pb, k, c, lo, hi, pad): body and other indices within world; the arm pa
+ * in body's frame; pb the arm in other's frame or, with other = -1, a point of the world; rest length, stiffness, damping and a clamp
+ * [lo, hi] of the scalar force.  A rope is lo = 0, a strut that only pushes is hi = 0; -inf / +inf mean "no clamp".
+ * THE WRENCH of spring i, with h the call's time step and x, q, v, omega of each end what mgf_batch_gather_state_dev returns at that
+ * moment (x is x + delta) - every line a separate f32 operation, no fused multiply-add:
+ *   ra = rotate(q_a, pa);  Pa = x_a + ra;  Va = v_a + cross(omega_a, ra)      rotate: the sensors' Rotation::rotate_vector, (q, vector)
+ *   other >= 0:  rb = rotate(q_b, pb);  Pb = x_b + rb;  Vb = v_b + cross(omega_b, rb)
+ *   other == -1: Pb = pb;  Vb = (0,0,0)
+ *   d = Pb - Pa;  len = sqrt(dot(d, d));  n = d / len            (component-wise division)
+ *                dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z;  cross(a,b) the actuators' (above), operands in the order written
+ *   rate = dot(Vb - Va, n)
+ *   f = k * (len - rest) + c * rate;  if (f < lo) f = lo;  if (f > hi) f = hi      (a NaN stays a NaN)
+ *   s = f * h
+ *   L = n * s;  A = cross(ra, L)                                  the impulse on `body`: pulled towards the far end for f > 0
+ *   other >= 0:  Lb = -L;  Ab = cross(rb, Lb)                     the impulse on `other`
+ *   len == 0, or len or s not finite:  all four vectors zero, and the spring is counted in mgf_batch_counter "springs_skipped"
+ *                                      (cumulative; reading it waits for the stream, like "actuators_skipped")
+ * wrench_out is optional: when given it receives the twelve floats (L, A, Lb, Ab) of spring i at row i - zeros for the far end of a
+ * world anchor - rows in the order of the array given to mgf_batch_set_springs.
+ * WHAT A CALL DOES TO THE BATCH.  Form the record list: for i in rig order (world_i, body_i, L, A), then, where other_i >= 0,
+ * (world_i, other_i, Lb, Ab).  The batch ends, bit for bit, as after mgf_batch_apply_impulses of that list: per body, in list order,
+ * v = v + L * inv_mass, omega = omega + I * A.  EVERY wrench is formed from the state before the call, whatever the order of the rig.
+ * Nothing but velocities is written, and a world that no spring names is untouched to the bit.  Springs read no shapes: a batch with
+ * bodies of several components is answered.
+ * A call is at most MGF_BATCH_SPRING_LAUNCHES = 2 launches, counted in "drive_launches", whatever the number of springs and worlds: a
+ * lane per spring forms the wrenches, then a lane per body that carries an end walks the body's ends in list order - no float atomic,
+ * nothing depends on lane scheduling.
+ * IN A ROLLOUT.  With a spring rig that is not empty, mgf_batch_rollout / _rollout_dev become, bit for bit, the loop
+ *   mgf_batch_apply_springs_dev(b, dt, NULL) | mgf_batch_actuate_dev(u[t]) | mgf_batch_step(1) | mgf_batch_gather_state_dev(row t)
+ * - the springs first, because a damper reads the velocities an impulse actuator writes.  Signatures, refusals and their order stay
+ * as they are; with an empty spring rig the call is launch for launch what it was.  The springs add at most
+ * MGF_BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK = 2 launches ahead of a tick, counted in "rollout_launches".  n_act == 0 with nothing
+ * traced is then NOT mgf_batch_step: it is the stepping call of a batch with springs.  A world whose tick is undone and run again
+ * gets tick t's springs ONCE, as it gets its control row once, and "springs_skipped" counts as the loop's calls would.
+ * mgf_batch_step itself stays World::step, launch for launch: it applies no spring.
+ * OUT OF SCOPE here: hard joints and limits in the solver; springs on the lone mgf_world; springs inside mgf_batch_step; the wrenches
+ * per tick of a rollout; angular (torsion) springs; rest lengths or gains driven per tick from a control row. */
+#define MGF_BATCH_SPRING_LAUNCHES 2  /* the most one call adds to "drive_launches" */
+#define MGF_BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK 2  /* what a spring rig that is not empty adds to a rollout's tick, at most */
+typedef struct mgf_batch_spring {
+  int32_t world, body, other; uint32_t flags;   /* other = -1: the far end is a point of the world; flags must be 0 */
+  mgf_vec3 pa; float rest;                      /* arm in body's frame; rest length >= 0 */
+  mgf_vec3 pb; float k;                         /* arm in other's frame, or the world point; stiffness */
+  float c, lo, hi, pad;                         /* damping; clamp of the scalar force; pad = 0 */
+} mgf_batch_spring;                             /* 64 bytes: four 16-byte words */
+/* Replaces the rig by a copy of s[0 .. n); n = 0 clears it.  No device work: the rig goes up with the next call.  Refused with
+ * MGF_ERR_INVALID, the rig as it was ("the rig was not changed"), in this order: what mgf_batch_set_sensors refuses - a NULL batch, a
+ * negative n or n > INT32_MAX, a NULL array with n > 0, then per record a world out of range, a body outside
+ * [0, mgf_batch_len(b, world)) - then other < -1 or other outside the world, other == body, flags != 0, a non-finite pa, pb, k, c or
+ * rest, rest < 0, a NaN lo or hi or lo > hi.  The rig names (world, body) and (world, other): mgf_batch_add_bodies and
+ * mgf_batch_add_compound_bodies afterwards leave every spring on the bodies it named.  Independent of the other six rigs. */
+MGF_API mgf_status mgf_batch_set_springs(mgf_batch* b, const mgf_batch_spring* s, int64_t n);
+MGF_API int64_t    mgf_batch_spring_count(const mgf_batch* b);              /* -1 for NULL */
+/* The wrenches formed and applied (above).  Refused with MGF_ERR_INVALID, nothing enqueued and nothing changed: a NULL batch, a
+ * non-finite h.  An empty rig: MGF_OK, nothing enqueued.  Synchronous: one download where wrench_out is given, one host wait. */
+MGF_API mgf_status mgf_batch_apply_springs(mgf_batch* b, float h, float* wrench_out);
+/* The same with wrench_out in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for.
+ * Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls (48 bytes a
+ * spring of wrench_out_dev). */
+MGF_API mgf_status mgf_batch_apply_springs_dev(mgf_batch* b, float h, float* wrench_out_dev);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /
  * _set_forces / _apply_impulses / _copy_worlds call or device-pointer call on this batch - for a copy, on its destination: it depends on
  * neither n_worlds nor n), "device_skipped" (records of the device-pointer calls whose index was out of range, cumulative; waits for the
  * stream), "pair_table_uploads" (uploads of mgf_batch_copy_worlds_where's pair table, cumulative), "actuators_skipped" (above),
- * "rollout_launches" (launches of the last mgf_batch_rollout / _rollout_dev call beyond its ticks' own)}. */
+ * "rollout_launches" (launches of the last mgf_batch_rollout / _rollout_dev call beyond its ticks' own), "springs_skipped" (above)}. */
 MGF_API mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out);
 /* Options (test knobs): "cons_per_body" [4] = the constraint records per body a world's share of the storage starts with (1 .. 4096); a
  * low value makes the first busy tick outgrow it, which the re-run path then handles. */

@@ -65,6 +65,11 @@ class BatchActuator(C.Structure):
                 ("d", Vec3), ("hi", C.c_float)]
 
 
+class BatchSpring(C.Structure):
+    _fields_ = [("world", C.c_int32), ("body", C.c_int32), ("other", C.c_int32), ("flags", C.c_uint32), ("pa", Vec3), ("rest", C.c_float),
+                ("pb", Vec3), ("k", C.c_float), ("c", C.c_float), ("lo", C.c_float), ("hi", C.c_float), ("pad", C.c_float)]
+
+
 class Component(C.Structure):
     _fields_ = [("tag", C.c_int32), ("p", Vec3), ("d", Vec3), ("r", C.c_float)]
 
@@ -183,6 +188,13 @@ ACTUATOR_TORQUE, ACTUATOR_WORLD_DIR = 1, 2  # MGF_ACTUATOR_TORQUE, _WORLD_DIR
 ACTUATE_IMPULSE, ACTUATE_FORCE = 0, 1  # MGF_ACTUATE_IMPULSE, _FORCE
 BATCH_ACTUATOR_LAUNCHES = 1  # MGF_BATCH_ACTUATOR_LAUNCHES
 BATCH_ROLLOUT_LAUNCHES_PER_TICK = 2  # MGF_BATCH_ROLLOUT_LAUNCHES_PER_TICK
+# mgf_batch_spring: a spring-damper between the arm pa of body `body` and the arm pb of body `other` of world `world` (other = -1: pb
+# is a point of the world), rest length, stiffness k, damping c and a clamp [lo, hi] of the scalar force
+SPRING_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("other", "<i4"), ("flags", "<u4"), ("pa", "<f4", 3), ("rest", "<f4"),
+                         ("pb", "<f4", 3), ("k", "<f4"), ("c", "<f4"), ("lo", "<f4"), ("hi", "<f4"), ("pad", "<f4")])
+assert SPRING_DTYPE.itemsize == C.sizeof(BatchSpring) == 64
+BATCH_SPRING_LAUNCHES = 2  # MGF_BATCH_SPRING_LAUNCHES
+BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK = 2  # MGF_BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -230,6 +242,7 @@ SYMBOLS = [
     "mgf_batch_set_feelers", "mgf_batch_feeler_count", "mgf_batch_cast_feelers", "mgf_batch_cast_feelers_dev",
     "mgf_batch_set_actuators", "mgf_batch_actuator_count", "mgf_batch_actuate", "mgf_batch_actuate_dev",
     "mgf_batch_rollout", "mgf_batch_rollout_dev",
+    "mgf_batch_set_springs", "mgf_batch_spring_count", "mgf_batch_apply_springs", "mgf_batch_apply_springs_dev",
 ]
 
 _lib = None
@@ -426,6 +439,10 @@ def load_library():
         "mgf_batch_actuate_dev": (i32, [vp, vp, i64, i32, vp]),
         "mgf_batch_rollout": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp]),
         "mgf_batch_rollout_dev": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp]),
+        "mgf_batch_set_springs": (i32, [vp, vp, i64]),
+        "mgf_batch_spring_count": (i64, [vp]),
+        "mgf_batch_apply_springs": (i32, [vp, f32, vp]),
+        "mgf_batch_apply_springs_dev": (i32, [vp, f32, vp]),
         "mgf_batch_set_cameras": (i32, [vp, vp, i64]),
         "mgf_batch_camera_count": (i64, [vp]),
         "mgf_batch_camera_pixels": (i64, [vp]),
@@ -2139,6 +2156,38 @@ class WorldBatch:
         arr = (StepStats * (T * self.n_worlds))()
         _check(load_library().mgf_batch_rollout_dev(self._h, float(dt), int(iters), T, up, n, int(mode), bp, m, *p, arr))
         return arr
+
+    # ---- springs between bodies: a rig set once, impulses formed from the resident state and applied in two launches -----------------------
+    def set_springs(self, world, body=None, other=-1, pa=None, pb=None, rest=0.0, k=0.0, c=0.0, lo=float("-inf"), hi=float("inf")):
+        """the batch's spring rig replaced (mgf_batch_set_springs): spring i ties the arm pa[i] of body[i] - in the body's frame - to the
+        arm pb[i] of other[i], both of world[i], or (other[i] = -1) to the point pb[i] of the world, with rest length rest[i], stiffness
+        k[i], damping c[i] and the scalar force clamped to [lo[i], hi[i]] (-inf / inf: no clamp; a rope is lo = 0).  Arrays, or scalars
+        / single rows for all: the number of springs is that of the longest argument; pa and pb left None stay zero.  No springs
+        (empty arrays) clears the rig.  Also takes a SPRING_DTYPE array as `world`, the other arguments not read."""
+        if isinstance(world, np.ndarray) and world.dtype == SPRING_DTYPE:
+            rig = np.ascontiguousarray(world.reshape(-1))
+        else:
+            given = {key: v for key, v in dict(pa=pa, pb=pb).items() if v is not None}
+            rig = _rig_rows(SPRING_DTYPE, world=world, body=body, other=other, rest=rest, k=k, c=c, lo=lo, hi=hi, **given)
+        _check(load_library().mgf_batch_set_springs(self._h, rig.ctypes.data if len(rig) else None, len(rig)))
+
+    def spring_count(self):
+        return load_library().mgf_batch_spring_count(self._h)
+
+    def apply_springs(self, h, wrenches=False):
+        """the impulse of every spring over the time step h formed from the current state of its ends, and applied as apply_impulses of
+        (body, L, A) and (other, Lb, Ab) in the rig's order (mgf_batch_apply_springs).  wrenches=True: returns the float32 [n, 12]
+        array of (L, A, Lb, Ab) in the rig's order."""
+        n = max(self.spring_count(), 0)
+        out = np.zeros((n, 12), np.float32) if wrenches else None
+        _check(load_library().mgf_batch_apply_springs(self._h, float(h), _ptr(out)))
+        return out
+
+    def apply_springs_dev(self, h, wrenches_out=None):
+        """apply_springs enqueued on the context's stream and not waited for (mgf_batch_apply_springs_dev).  wrenches_out: CUDA
+        float32 [n, 12], n = spring_count(), or None - (L, A, Lb, Ab) of every spring."""
+        n = max(self.spring_count(), 0)
+        _check(load_library().mgf_batch_apply_springs_dev(self._h, float(h), _dev_arg(wrenches_out, "float32", 12, n, "wrenches_out")))
 
     def counter(self, name):
         v = C.c_int64()

@@ -103,6 +103,7 @@ struct mgf_batch {
   BatchRig<mgf_batch_touch> touches;    // on the device: items | records | order - the contact sensors (host_batch_touch.inc)
   BatchRig<mgf_batch_feeler> feelers;   // on the device: items | records | order | worlds - the feelers (host_batch_feeler.inc)
   BatchRig<mgf_batch_actuator> actuators;  // on the device: runs | records | order - the actuators; `items` holds the runs of one body (host_batch_actuator.inc)
+  BatchRig<mgf_batch_spring> springs;   // on the device: runs | records | order - the springs; `items` holds the runs of one body's ENDS, `order` the ends (host_batch_spring.inc)
   // ... and what a call on one of them has nowhere else to put
   DBuf<float> s_parts;                  // the particles of a sensor cast: 7 words a sensor
   size_t c_pixels = 0;                  // the pixels of the camera rig, camera by camera
@@ -113,6 +114,8 @@ struct mgf_batch {
   DBuf<float4> touch_out;               // what the host-memory read of the contact sensors downloads: four words a sensor
   DBuf<float> f_casts;                  // the casts of a feeler cast where the caller takes none: 11 words a feeler
   DBuf<unsigned long long> a_skipped;   // actuators whose gain * clamp(u) was not finite, cumulative (counter "actuators_skipped")
+  DBuf<float> sp_wr;                    // the impulses of the springs, twelve floats a spring: written by one launch of a call, applied by the next
+  DBuf<unsigned long long> sp_skipped;  // springs whose wrench was zeroed (len == 0, len or f * h not finite), cumulative (counter "springs_skipped")
   // the rollouts (host_batch_rollout.inc)
   DBuf<uint32_t> d_act;                 // per world, beside d_done: ticks of the call whose actuation the world has behind it (k_batch_rollout.h)
   int64_t r_launches = 0;               // launches of the last rollout call beyond its ticks' own (counter "rollout_launches")
@@ -313,6 +316,12 @@ extern "C" mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, in
   if (!strcmp(name, "actuators_skipped")) {  // (on the device: the stream is waited for)
     unsigned long long v = 0;
     if (b->a_skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, b->a_skipped.p, 1)); }
+    *out = (int64_t)v;
+    return MGF_OK;
+  }
+  if (!strcmp(name, "springs_skipped")) {  // (on the device: the stream is waited for)
+    unsigned long long v = 0;
+    if (b->sp_skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, b->sp_skipped.p, 1)); }
     *out = (int64_t)v;
     return MGF_OK;
   }
@@ -548,6 +557,7 @@ static void batch_rigs_stale(mgf_batch* b) {
   b->touches.stale = true;
   b->feelers.stale = true;
   b->actuators.stale = true;
+  b->springs.stale = true;
 }
 
 // the rows of `n` new bodies (empty part slots where the caller has filled none) behind world k's last body
@@ -850,11 +860,14 @@ struct BatchRolloutHook {
   BatchRolloutArgs A;    // everything but done, act, tick and count, which the train fills in
   int32_t mode = 0;      // MGF_ACTUATE_IMPULSE / _FORCE
   bool act = false;      // the rig is not empty: k_batch_rollout_act ahead of every tick
+  BatchSpringArgs S;     // the springs' two launches (k_batch_spring.h), everything but done, act and tick
+  bool springs = false;  // the spring rig is not empty: they go ahead of the actuation, which a damper must not see
   int64_t launches = 0;  // what the hook added to the train's launches
 };
 
 // The step's launch train, behind the refusals: n_ticks x World::step (world.rs:227-294) of every world, six (seven) launches a tick, one
-// host wait per pass - and with a hook a rollout's two launches a tick among them.  hook == nullptr: mgf_batch_step, launch for launch.
+// host wait per pass - and with a hook a rollout's two launches a tick among them, and the springs' two where that rig is not empty.
+// hook == nullptr: mgf_batch_step, launch for launch.
 static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats, BatchRolloutHook* hook) {
   MGF_TRY(batch_push(b));
   MGF_TRY(batch_env_sync(b));
@@ -879,6 +892,7 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
     MGF_TRY(b->d_act.ensure(K, s));
     MGF_HIP_TRY(hipMemsetAsync(b->d_act.p, 0, 4 * (size_t)K, s));
     hook->A.done = b->d_done.p; hook->A.act = b->d_act.p;
+    hook->S.done = b->d_done.p; hook->S.act = b->d_act.p;
   }
   const unsigned hook_act_blocks = hook ? (unsigned)((hook->A.n_runs + kBatchBlock - 1) / kBatchBlock) : 0u;
   const unsigned hook_rec_blocks = hook ? (unsigned)((std::max(hook->A.m, K) + kBatchBlock - 1) / kBatchBlock) : 0u;
@@ -900,6 +914,14 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
     for (uint32_t t = first; t < NT; ++t) {
       A.tick = t;
       if (hook) { hook->A.tick = t; hook->A.count = pass == 0 ? 1u : 0u; }  // (an index outside the batch is counted once a tick)
+      if (hook && hook->springs) {  // (under the same gate as the actuation behind them: `act` moves behind the tick)
+        hook->S.tick = t;
+        k_batch_spring_wrench<<<(hook->S.n + kBatchBlock - 1) / kBatchBlock, kBatchBlock, 0, s>>>(hook->S);
+        LAUNCH_CHECK();
+        k_batch_spring_apply<true><<<(hook->S.n_runs + kBatchBlock - 1) / kBatchBlock, kBatchBlock, 0, s>>>(hook->S);
+        LAUNCH_CHECK();
+        hook->launches += MGF_BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK;
+      }
       if (hook && hook->act) {
         if (hook->mode == MGF_ACTUATE_IMPULSE) k_batch_rollout_act<ACTUATE_IMPULSE><<<hook_act_blocks, kBatchBlock, 0, s>>>(hook->A);
         else k_batch_rollout_act<ACTUATE_FORCE><<<hook_act_blocks, kBatchBlock, 0, s>>>(hook->A);

@@ -6,10 +6,15 @@
 // The launch train is the step's own (batch_step_run, host_batch.inc) with a hook: k_batch_rollout_act ahead of a tick's launches where
 // the rig is not empty, k_batch_rollout_record behind them - MGF_BATCH_ROLLOUT_LAUNCHES_PER_TICK = 2 at most, whatever the worlds, the
 // actuators and the traced bodies ("rollout_launches").  Both obey the train's gate world by world, and the word `act` beside `done`
-// keeps a world whose tick is run again from being actuated twice (k_batch_rollout.h).  The rig is the actuators' (BatchRig::items: no
-// plan and no upload format of its own), the trace rows are k_batch_dev_gather's.  "drive_launches" is not touched.
+// keeps a world whose tick is run again from being actuated twice (k_batch_rollout.h).  Where the spring rig is not empty its two
+// launches (k_batch_spring.h, MGF_BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK) go ahead of the actuation under the same two words.
+// The rig is the actuators' (BatchRig::items: no plan and no upload format of its own), the trace rows are k_batch_dev_gather's.
+// "drive_launches" is not touched.
 // The order of both calls: the refusals that need no handle, the handle's own, (device form) EVERY device pointer looked up for its
 // n_ticks-fold extent and the outputs held against each other and against the inputs - and only then the first thing is enqueued.
+
+// (host_batch_spring.inc, behind this file) the springs' arguments for the train: the rig up, the wrench buffer and the skip counter there
+static mgf_status batch_spring_ready(mgf_batch* b, float h, float* out_dev, BatchSpringArgs* A);
 
 struct RolloutBytes { size_t u, body, out[4]; };  // what the call touches of u, body, x, q, v, omega
 
@@ -40,7 +45,8 @@ static mgf_status batch_rollout_run(mgf_batch* b, float dt, int32_t iters, int64
                                     int64_t m, float* x, float* q, float* v, float* omega, mgf_step_stats* stats) {
   b->r_launches = 0;
   const bool trace = m > 0 && (x || q || v || omega);
-  if (n_ticks == 0 || (n_act == 0 && !trace)) return batch_step_run(b, dt, iters, n_ticks, stats, nullptr);
+  const bool springs = !b->springs.recs.empty();  // (then even a call without controls and traces is not mgf_batch_step: the springs act ahead of every tick)
+  if (n_ticks == 0 || (n_act == 0 && !trace && !springs)) return batch_step_run(b, dt, iters, n_ticks, stats, nullptr);
   hipStream_t s = b->ctx->stream;
   BatchRig<mgf_batch_actuator>& R = b->actuators;
   MGF_TRY(batch_push(b));
@@ -69,6 +75,10 @@ static mgf_status batch_rollout_run(mgf_batch* b, float dt, int32_t iters, int64
     H.A.body = body_dev; H.A.m = (uint32_t)m;
     H.A.x = x; H.A.q = q; H.A.v = v; H.A.om = omega;
     H.A.v_skipped = b->v_skipped.p;
+  }
+  if (springs) {
+    MGF_TRY(batch_spring_ready(b, dt, nullptr, &H.S));
+    H.springs = true;
   }
   H.A.B = b->bodies(0);
   H.A.w_off = b->d_off.p;

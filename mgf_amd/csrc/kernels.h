@@ -156,6 +156,13 @@
 //                      walk on row t of the controls ahead of tick t's launches, k_batch_dev_gather's rows into row t of the traces
 //                      behind them - both under the train's gate done[k] == tick, and a word `act` beside `done` that keeps a world
 //                      whose tick is undone and run again from being actuated twice; record advances it, a lane per world
+//   k_batch_spring_wrench / k_batch_spring_apply<GATED> (k_batch_spring.h)
+//                      spring-dampers between two body-fixed points, or one and a point of the world (mgf_batch_set_springs /
+//                      _apply_springs / _apply_springs_dev, and ahead of every tick of a rollout): a lane per spring forms the
+//                      impulses on both ends from the state before the call - lengths, point velocities, a clamp, two cross
+//                      products - into the handle's buffer; then a lane per run of one body's ends, sorted on the host when the rig
+//                      is set, applies them in list order with batch_drive_apply's arithmetic; no float atomic.  GATED: under the
+//                      rollout train's gate done[k] == tick && act[k] == tick, folded into the run length
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -185,3 +192,4 @@
 #include "k_batch_feeler.h"  // feelers: spheres and capsules fixed in the frame of a body, swept from the resident poses (k_batch_feeler_bodies)
 #include "k_batch_actuator.h"  // actuators: wrenches formed from the resident poses and applied, a lane per body (k_batch_actuate)
 #include "k_batch_rollout.h"  // rollouts: a row of controls ahead of every tick of a step call, a row of state behind it (k_batch_rollout_act, _record)
+#include "k_batch_spring.h"  // springs between bodies: impulses formed from the resident state, applied a lane per body (k_batch_spring_wrench, _apply)
