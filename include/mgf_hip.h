@@ -1112,7 +1112,8 @@ MGF_API mgf_status mgf_batch_overlap_nearest_dev(mgf_batch* b, const mgf_aabb* b
  * "query_launches" of either read: MGF_BATCH_TOUCH_LAUNCHES = 1 whatever the worlds, sensors and list lengths; there is no collider
  * gather, since nothing here reads a shape.  No HIP events: "query_run_ns" is 0.
  * OUT OF SCOPE here: sums over the ticks of a multi-tick mgf_batch_step call (the report describes the last tick, as
- * mgf_batch_read_body_contacts does); tangent impulses (mgf_constraint does not carry them); groups of bodies as a partner filter; the k
+ * mgf_batch_read_body_contacts does) (since: Rollout touch traces, below - mgf_batch_rollout_touches writes a report per tick, and a sum
+ * is a reduction of its rows); tangent impulses (mgf_constraint does not carry them); groups of bodies as a partner filter; the k
  * strongest contacts rather than one; sensors on the lone mgf_world; a rig chosen per call by a device mask; hipGraph capture. */
 #define MGF_TOUCH_STATIC   (-1)  /* RigidBodyRef::Static: the world's terrain and obstacles alike (b = -1) */
 #define MGF_TOUCH_ANY_BODY (-2)  /* any body of the world */
@@ -1290,7 +1291,8 @@ MGF_API mgf_status mgf_batch_actuate_dev(mgf_batch* b, const float* u_dev, int64
  * n_act != mgf_batch_actuator_count(b); NULL u with n_act > 0 and n_ticks > 0; body == NULL with m > mgf_batch_len(b, -1).
  * n_ticks == 0: MGF_OK, nothing enqueued beyond what mgf_batch_step(b, dt, iters, 0, stats) does.
  * OUT OF SCOPE here: closed-loop policies inside the call (u is fixed when the call is made); a step with no host wait at all; the
- * wrenches per tick; contact or touch sums per tick; a world mask; the lone mgf_world; hipGraph capture. */
+ * wrenches per tick; contact or touch sums per tick (the contact sensors' reports per tick since: Rollout touch traces, below -
+ * mgf_batch_rollout_touches); a world mask; the lone mgf_world; hipGraph capture. */
 #define MGF_BATCH_ROLLOUT_LAUNCHES_PER_TICK 2  /* what the call adds to a tick's launches, at most, with an empty spring rig */
 /* The host form: one upload (u and body), the device core, one download (the outputs given).  stats: NULL or n_ticks * n_worlds rows,
  * row t * n_worlds + k world k's tick t.  A row of an index outside the batch comes back as zeros. */
@@ -1370,13 +1372,63 @@ MGF_API mgf_status mgf_batch_apply_springs(mgf_batch* b, float h, float* wrench_
  * Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls (48 bytes a
  * spring of wrench_out_dev). */
 MGF_API mgf_status mgf_batch_apply_springs_dev(mgf_batch* b, float h, float* wrench_out_dev);
+/* ---- rollout touch traces: the contact sensors' reports behind every tick of a rollout ----
+ * A rollout records the STATE of chosen bodies behind every tick.  A sampling planner or a cost function also asks "did the foot
+ * touch, how hard, and what touched it" at every tick of the horizon; call by call that is T host waits again.  These two calls are
+ * mgf_batch_rollout / _rollout_dev with one more output: row t of the reports of the contact sensors' rig (mgf_batch_set_touches)
+ * behind tick t.
+ * THE DEFINITION is calls that exist, bit for bit.  With touch[T][n_touch] in the rig's order, the batch and every output are left as
+ *   for t in 0 .. T-1:
+ *     mgf_batch_apply_springs_dev(b, dt, NULL)                                                  (with a spring rig that is not empty)
+ *     mgf_batch_actuate_dev(b, u[t], n_act, mode, NULL)                                        (skipped when n_act == 0)
+ *     mgf_batch_step(b, dt, iters, 1, stats + t * n_worlds)
+ *     mgf_batch_gather_state_dev(b, body, m, x[t], q[t], v[t], omega[t], NULL, NULL)           (skipped when m == 0)
+ *     mgf_batch_read_touches_dev(b, touch + t * n_touch, n_touch)
+ * leaves them.  touch_format MGF_ROLLOUT_TOUCH_FULL: an entry is that mgf_touch_report, 64 bytes.  MGF_ROLLOUT_TOUCH_SHORT: an entry
+ * is 16 bytes - the words n_contacts, partner, normal_impulse, strongest_impulse of that report, in this order - for a caller who
+ * asks "touched, by whom, how hard" and wants a quarter of the traffic.  EVERY entry is written: every world completes every tick of
+ * a call that returns MGF_OK.  MGF_TOUCH_BODY_FRAME turns the vectors by the body's q behind tick t, as a read between the ticks
+ * does.  The reports read no shapes: a batch with bodies of several components is answered, as by both parents.
+ * touch == NULL, or n_touch == 0 with an empty rig: the call IS mgf_batch_rollout / _rollout_dev, launch for launch.
+ * ONE HOST WAIT per pass, as in a rollout.  A world whose tick t did not fit is undone and skipped by this launch as by every other of
+ * the pass; its row t is written in the pass in which it completes t, and never from a list that a later, undone tick wrote into.
+ * The trace adds MGF_BATCH_ROLLOUT_TOUCH_LAUNCHES_PER_TICK = 1 launch behind a tick in every pass that runs it, whatever the worlds,
+ * the sensors and the list lengths, counted in "rollout_launches"; "query_launches" and "drive_launches" are not touched.
+ * REFUSED with MGF_ERR_INVALID, nothing enqueued and nothing changed, in this order - ahead of the handle's contents: a NULL batch; a
+ * negative n_ticks, iters, n_act, m or n_touch, in that order; n_ticks > 2^20; a mode other than MGF_ACTUATE_IMPULSE or
+ * MGF_ACTUATE_FORCE; a touch_format other than MGF_ROLLOUT_TOUCH_FULL or MGF_ROLLOUT_TOUCH_SHORT; m > INT32_MAX; a byte count
+ * (4 * n_ticks * n_act, then 64 * n_ticks * n_touch) that overflows int64_t - then the handle's own:
+ * n_act != mgf_batch_actuator_count(b); n_touch != mgf_batch_touch_count(b) (report rows of the wrong length are a bug, not a prefix);
+ * NULL u with n_act > 0 and n_ticks > 0; NULL touch with n_touch > 0 and n_ticks > 0; body == NULL with m > mgf_batch_len(b, -1).
+ * n_ticks == 0: MGF_OK, nothing written, nothing enqueued beyond what mgf_batch_step(b, dt, iters, 0, stats) does.
+ * OUT OF SCOPE here: ray sensors, feelers, zones or cameras per tick (they need the collider gather in the train); sums over the
+ * horizon (a reduction of the rows); the lone mgf_world; hipGraph capture. */
+#define MGF_ROLLOUT_TOUCH_FULL  0   /* a row entry is mgf_touch_report, 64 bytes */
+#define MGF_ROLLOUT_TOUCH_SHORT 1   /* 16 bytes: n_contacts, partner, normal_impulse, strongest_impulse of that report */
+#define MGF_BATCH_ROLLOUT_TOUCH_LAUNCHES_PER_TICK 1  /* what the touch trace adds to a rollout's tick, in every pass that runs it */
+typedef struct mgf_touch_short {
+  int32_t n_contacts, partner;
+  float normal_impulse, strongest_impulse;
+} mgf_touch_short;                  /* 16 bytes: an entry of an MGF_ROLLOUT_TOUCH_SHORT row */
+/* The host form: one upload (u and body), the device core, one download (the outputs given, the touch rows among them). */
+MGF_API mgf_status mgf_batch_rollout_touches(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u, int64_t n_act, int32_t mode,
+                                             const int32_t* body, int64_t m, float* x, float* q, float* v, float* omega,
+                                             void* touch, int64_t n_touch, int32_t touch_format, mgf_step_stats* stats);
+/* The same with u, body and the outputs in device memory (the device-pointer calls, above); stats stays host memory.  Also refused with
+ * MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls for its full extent (mgf_batch_rollout_dev's,
+ * and 64 * n_ticks * n_touch bytes of touch_dev - 16 * n_ticks * n_touch for MGF_ROLLOUT_TOUCH_SHORT), an output's bytes overlapping
+ * another output's or an input's: touch_dev is held against x_dev, q_dev, v_dev, omega_dev, u_dev and body_dev. */
+MGF_API mgf_status mgf_batch_rollout_touches_dev(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u_dev, int64_t n_act, int32_t mode,
+                                                 const int32_t* body_dev, int64_t m, float* x_dev, float* q_dev, float* v_dev, float* omega_dev,
+                                                 void* touch_dev, int64_t n_touch, int32_t touch_format, mgf_step_stats* stats);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /
  * _set_forces / _apply_impulses / _copy_worlds call or device-pointer call on this batch - for a copy, on its destination: it depends on
  * neither n_worlds nor n), "device_skipped" (records of the device-pointer calls whose index was out of range, cumulative; waits for the
  * stream), "pair_table_uploads" (uploads of mgf_batch_copy_worlds_where's pair table, cumulative), "actuators_skipped" (above),
- * "rollout_launches" (launches of the last mgf_batch_rollout / _rollout_dev call beyond its ticks' own), "springs_skipped" (above)}. */
+ * "rollout_launches" (launches of the last mgf_batch_rollout / _rollout_dev / _rollout_touches / _rollout_touches_dev call beyond its
+ * ticks' own, the touch trace's one a tick a pass among them), "springs_skipped" (above)}. */
 MGF_API mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out);
 /* Options (test knobs): "cons_per_body" [4] = the constraint records per body a world's share of the storage starts with (1 .. 4096); a
  * low value makes the first busy tick outgrow it, which the re-run path then handles. */

@@ -195,6 +195,11 @@ SPRING_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("other", "<i4"), ("
 assert SPRING_DTYPE.itemsize == C.sizeof(BatchSpring) == 64
 BATCH_SPRING_LAUNCHES = 2  # MGF_BATCH_SPRING_LAUNCHES
 BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK = 2  # MGF_BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK
+# mgf_touch_short: an entry of a rollout's touch rows in the short format - four words of mgf_touch_report
+TOUCH_SHORT_DTYPE = np.dtype([("n_contacts", "<i4"), ("partner", "<i4"), ("normal_impulse", "<f4"), ("strongest_impulse", "<f4")])
+assert TOUCH_SHORT_DTYPE.itemsize == 16
+ROLLOUT_TOUCH_FULL, ROLLOUT_TOUCH_SHORT = 0, 1  # MGF_ROLLOUT_TOUCH_FULL, _SHORT
+BATCH_ROLLOUT_TOUCH_LAUNCHES_PER_TICK = 1  # MGF_BATCH_ROLLOUT_TOUCH_LAUNCHES_PER_TICK
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -241,7 +246,7 @@ SYMBOLS = [
     "mgf_batch_set_touches", "mgf_batch_touch_count", "mgf_batch_read_touches", "mgf_batch_read_touches_dev",
     "mgf_batch_set_feelers", "mgf_batch_feeler_count", "mgf_batch_cast_feelers", "mgf_batch_cast_feelers_dev",
     "mgf_batch_set_actuators", "mgf_batch_actuator_count", "mgf_batch_actuate", "mgf_batch_actuate_dev",
-    "mgf_batch_rollout", "mgf_batch_rollout_dev",
+    "mgf_batch_rollout", "mgf_batch_rollout_dev", "mgf_batch_rollout_touches", "mgf_batch_rollout_touches_dev",
     "mgf_batch_set_springs", "mgf_batch_spring_count", "mgf_batch_apply_springs", "mgf_batch_apply_springs_dev",
 ]
 
@@ -439,6 +444,8 @@ def load_library():
         "mgf_batch_actuate_dev": (i32, [vp, vp, i64, i32, vp]),
         "mgf_batch_rollout": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp]),
         "mgf_batch_rollout_dev": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp]),
+        "mgf_batch_rollout_touches": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i64, i32, vp]),
+        "mgf_batch_rollout_touches_dev": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i64, i32, vp]),
         "mgf_batch_set_springs": (i32, [vp, vp, i64]),
         "mgf_batch_spring_count": (i64, [vp]),
         "mgf_batch_apply_springs": (i32, [vp, f32, vp]),
@@ -2155,6 +2162,83 @@ class WorldBatch:
             p.append(_dev_arg(a, "float32", m * cols, T, name))
         arr = (StepStats * (T * self.n_worlds))()
         _check(load_library().mgf_batch_rollout_dev(self._h, float(dt), int(iters), T, up, n, int(mode), bp, m, *p, arr))
+        return arr
+
+    # ---- rollout touch traces: the contact sensors' reports behind every tick of a rollout -------------------------------------------------
+    def rollout_touches(self, u, dt, iters, mode=ACTUATE_IMPULSE, body=None, trace=("x", "q", "v", "omega"), short=False):
+        """rollout, and row t of the contact sensors' reports behind tick t as well (mgf_batch_rollout_touches): the loop
+        actuate(u[t]) | step(dt, iters) | gather of `body` | read_touches with the step's one host wait.  The arguments are rollout's;
+        the result has one more entry, "touches": a TOUCH_REPORT_DTYPE array [T, touch_count()] in the rig's order, or (short) a
+        TOUCH_SHORT_DTYPE one - n_contacts, partner, normal_impulse, strongest_impulse of those reports."""
+        n = max(self.actuator_count(), 0)
+        if isinstance(u, (int, np.integer)):
+            if n:
+                raise ValueError("u: a number of ticks stands for the controls of an empty rig only")
+            uu = np.zeros((int(u), 0), np.float32)
+        else:
+            uu = np.ascontiguousarray(u, np.float32)
+        if uu.ndim != 2 or uu.shape[1] != n:
+            raise ValueError(f"u: {uu.shape} is not [T, {n}]")
+        unknown = [k for k in trace if k not in ("x", "q", "v", "omega")]
+        if unknown:
+            raise ValueError(f"trace: {unknown[0]!r} is not one of x, q, v, omega")
+        T = uu.shape[0]
+        bb = None if body is None else np.ascontiguousarray(body, np.int32).reshape(-1)
+        m = len(self) if bb is None else len(bb)
+        out = {k: np.zeros((T, m, 4 if k == "q" else 3), np.float32) for k in ("x", "q", "v", "omega") if k in trace}
+        nt = max(self.touch_count(), 0)
+        touches = np.zeros((T, nt), TOUCH_SHORT_DTYPE if short else TOUCH_REPORT_DTYPE)
+        arr = (StepStats * (T * self.n_worlds))()
+        _check(load_library().mgf_batch_rollout_touches(self._h, float(dt), int(iters), T, uu.ctypes.data if uu.size else None, n, int(mode),
+                                                        bb.ctypes.data if bb is not None and m else None, m,
+                                                        *[out[k].ctypes.data if k in out and out[k].size else None for k in ("x", "q", "v", "omega")],
+                                                        touches.ctypes.data if touches.size else None, nt,
+                                                        ROLLOUT_TOUCH_SHORT if short else ROLLOUT_TOUCH_FULL, arr))
+        out["touches"] = touches
+        out["stats"] = arr
+        return out
+
+    def rollout_touches_dev(self, u, dt, iters, mode=ACTUATE_IMPULSE, body=None, x=None, q=None, v=None, omega=None, touches=None, short=False):
+        """rollout_dev, and row t of the contact sensors' reports behind tick t as well (mgf_batch_rollout_touches_dev).  touches: a
+        CUDA tensor of int32 or float32 [T, n, 16], n = touch_count() - an entry is TOUCH_REPORT_DTYPE's sixteen words - or (short)
+        [T, n, 4], TOUCH_SHORT_DTYPE's four; a raw address; None: rollout_dev.  The other arguments and the result are rollout_dev's."""
+        if u is None:
+            raise ValueError("u is required")
+        n = max(self.actuator_count(), 0)
+        if isinstance(u, (int, np.integer)):
+            if n:
+                raise ValueError("u: a number of ticks stands for the controls of an empty rig only")
+            T, up = int(u), None
+        else:
+            if not hasattr(u, "data_ptr"):
+                raise ValueError(f"u: a torch tensor on the GPU, not {type(u).__name__}")
+            if u.dim() != 2 or u.shape[1] != n:
+                raise ValueError(f"u: {tuple(u.shape)} is not [T, {n}]")
+            T = int(u.shape[0])
+            up = _dev_arg(u, "float32", n, T, "u")
+        if body is None:
+            bp, m = None, len(self)
+        else:
+            if not hasattr(body, "data_ptr"):
+                raise ValueError(f"body: a torch tensor on the GPU, not {type(body).__name__}")
+            m = int(body.numel())
+            bp = _dev_arg(body, "int32", 1, m, "body")
+        p = []
+        for a, name, cols in ((x, "x", 3), (q, "q", 4), (v, "v", 3), (omega, "omega", 3)):
+            if a is not None:
+                if not hasattr(a, "data_ptr"):
+                    raise ValueError(f"{name}: a torch tensor on the GPU, not {type(a).__name__}")
+                if tuple(a.shape) != (T, m, cols):
+                    raise ValueError(f"{name}: {tuple(a.shape)} is not [{T}, {m}, {cols}]")
+            p.append(_dev_arg(a, "float32", m * cols, T, name))
+        nt, words = max(self.touch_count(), 0), 4 if short else 16
+        if hasattr(touches, "data_ptr") and tuple(touches.shape) != (T, nt, words):
+            raise ValueError(f"touches: {tuple(touches.shape)} is not [{T}, {nt}, {words}]")
+        dtype = "float32" if str(getattr(touches, "dtype", "")) == "torch.float32" else "int32"
+        tp = _dev_arg(touches, dtype, nt * words, T, "touches")
+        arr = (StepStats * (T * self.n_worlds))()
+        _check(load_library().mgf_batch_rollout_touches_dev(self._h, float(dt), int(iters), T, up, n, int(mode), bp, m, *p, tp, nt,
+                                                            ROLLOUT_TOUCH_SHORT if short else ROLLOUT_TOUCH_FULL, arr))
         return arr
 
     # ---- springs between bodies: a rig set once, impulses formed from the resident state and applied in two launches -----------------------

@@ -862,11 +862,15 @@ struct BatchRolloutHook {
   bool act = false;      // the rig is not empty: k_batch_rollout_act ahead of every tick
   BatchSpringArgs S;     // the springs' two launches (k_batch_spring.h), everything but done, act and tick
   bool springs = false;  // the spring rig is not empty: they go ahead of the actuation, which a damper must not see
+  BatchTraceTouchArgs T;  // the touch trace (k_batch_trace.h): V.out - row 0 - and n_touch; the train fills the rest in, the lists' view per PASS
+  int32_t touch = -1;    // MGF_ROLLOUT_TOUCH_FULL / _SHORT: k_batch_trace_touch behind every tick's record; -1: no touch trace
   int64_t launches = 0;  // what the hook added to the train's launches
 };
+static uint32_t batch_touch_tile(const mgf_batch* b);  // (host_batch_touch.inc, behind this file) the words of dynamic LDS the contact sensors' fold stages
 
 // The step's launch train, behind the refusals: n_ticks x World::step (world.rs:227-294) of every world, six (seven) launches a tick, one
-// host wait per pass - and with a hook a rollout's two launches a tick among them, and the springs' two where that rig is not empty.
+// host wait per pass - and with a hook a rollout's two launches a tick among them, the springs' two where that rig is not empty and the
+// touch trace's one where it is asked for.
 // hook == nullptr: mgf_batch_step, launch for launch.
 static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats, BatchRolloutHook* hook) {
   MGF_TRY(batch_push(b));
@@ -911,6 +915,17 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
     A.done = b->d_done.p; A.need = b->d_need.p; A.c_count = b->d_ccount.p; A.err = b->d_err.p; A.stats = b->d_stats.p;
     A.n_worlds = K; A.iters = (uint32_t)iters;
     A.dt = dt; A.fat_margin = b->params.fat_margin; A.baumgarte = b->params.baumgarte; A.slop = b->params.penetration_slop;
+    if (hook && hook->touch >= 0) {  // (batch_allot moves the lists between passes: the view is rebuilt with BatchArgs, never kept from an earlier pass)
+      BatchRig<mgf_batch_touch>& R = b->touches;
+      BatchTouchArgs& V = hook->T.V;
+      V.items = reinterpret_cast<const uint4*>(R.dev.p);
+      V.order = reinterpret_cast<const uint32_t*>(R.dev.p + R.off[2]);
+      V.rig = reinterpret_cast<const TouchIn*>(R.dev.p + R.off[1]);
+      V.cons = b->cons.p; V.c_off = b->d_coff.p; V.c_count = b->d_ccount.p; V.w_off = b->d_off.p;
+      V.q = b->dm[mgf_batch::AQ].p;
+      V.tile = batch_touch_tile(b);
+      hook->T.done = b->d_done.p; hook->T.act = b->d_act.p;
+    }
     for (uint32_t t = first; t < NT; ++t) {
       A.tick = t;
       if (hook) { hook->A.tick = t; hook->A.count = pass == 0 ? 1u : 0u; }  // (an index outside the batch is counted once a tick)
@@ -938,6 +953,14 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
         k_batch_rollout_record<<<hook_rec_blocks, kBatchBlock, 0, s>>>(hook->A);
         LAUNCH_CHECK();
         ++hook->launches;
+      }
+      if (hook && hook->touch >= 0) {  // (behind the record: act[k] is final; a workgroup per work item of the contact sensors' plan)
+        hook->T.tick = t;
+        const unsigned items = (unsigned)b->touches.items.size(), lds_touch = 4u * hook->T.V.tile;
+        if (hook->touch == MGF_ROLLOUT_TOUCH_SHORT) k_batch_trace_touch<kTraceTouchShort><<<items, kBatchBlock, lds_touch, s>>>(hook->T);
+        else k_batch_trace_touch<kTraceTouchFull><<<items, kBatchBlock, lds_touch, s>>>(hook->T);
+        LAUNCH_CHECK();
+        hook->launches += MGF_BATCH_ROLLOUT_TOUCH_LAUNCHES_PER_TICK;
       }
     }
     MGF_TRY(d2h(ctx, done.data(), b->d_done.p, K));

@@ -163,6 +163,11 @@
 //                      products - into the handle's buffer; then a lane per run of one body's ends, sorted on the host when the rig
 //                      is set, applies them in list order with batch_drive_apply's arithmetic; no float atomic.  GATED: under the
 //                      rollout train's gate done[k] == tick && act[k] == tick, folded into the run length
+//   k_batch_trace_touch<FORMAT> (k_batch_trace.h)
+//                      the touch trace of a rollout (mgf_batch_rollout_touches / _touches_dev): k_batch_touch's fold of every world's
+//                      list behind tick t into row t of the reports, one launch a tick behind k_batch_rollout_record; the train's gate
+//                      done[k] == t + 1 && act[k] <= t + 1 is the workgroup's and is folded into the item's count and the list's
+//                      length; a full report of 64 bytes or a short one of 16
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -193,3 +198,4 @@
 #include "k_batch_actuator.h"  // actuators: wrenches formed from the resident poses and applied, a lane per body (k_batch_actuate)
 #include "k_batch_rollout.h"  // rollouts: a row of controls ahead of every tick of a step call, a row of state behind it (k_batch_rollout_act, _record)
 #include "k_batch_spring.h"  // springs between bodies: impulses formed from the resident state, applied a lane per body (k_batch_spring_wrench, _apply)
+#include "k_batch_trace.h"  // the touch trace of a rollout: the contact sensors' reports behind every tick (k_batch_trace_touch)
