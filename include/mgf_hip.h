@@ -580,7 +580,22 @@ MGF_API mgf_status mgf_world_release_device_ptrs(mgf_world* w);
  * no ghosts or tiles and no constraint_order = demo: a batch has no entry point for them.  A tick never fails for list sizes: a world whose
  * constraints outgrow its share of the storage gets its tick undone on the device and run again with more (Solver::solve and
  * World::step have no capacity failure, solver.rs:72-78); mgf_batch_counter "capacity_retries" counts those re-runs.
- * Calls are synchronous on the context's stream; the handle keeps a reference on the context; there is no CPU fallback. */
+ * Calls are synchronous on the context's stream; the handle keeps a reference on the context; there is no CPU fallback.
+ * PART QUERIES: mgf_batch_set_option(b, "part_queries", 1) (default 0: the refusals above stay) makes the calls that read shapes see
+ * the parts of bodies of several components, on a batch that holds such bodies (without them the option changes no launch).  IN
+ * SCOPE: mgf_batch_raycast_many(_dev), _sweep_many(_dev), _cast_sensors(_dev), _cast_feelers(_dev), _overlap_aabb_many,
+ * _overlap_first_dev, _overlap_nearest_dev, _read_zones(_dev), _read_zones_nearest(_dev).  Each answers for world k, bit for bit, what
+ * the lone mgf_world answers that has been through the same add calls and ticks: a ray tests every part of every body not ignored
+ * (Intersects<Sphere | Capsule>), ranked (t, kind, index, part) ascending, and `part` of the hit is the part's index (0 for an ordinary
+ * body); a sweep tests every part, ranked (t, kind, index, part, order emitted); a body's box is BoundedBy<AABB> of its parts combined
+ * in order (bounds.rs:113-130), which is what the box overlaps, the zones and overlap_first_dev test and whose centre the nearest
+ * forms measure from; an ignored body - ignore_body, MGF_SENSOR_IGNORE_SELF, MGF_FEELER_IGNORE_SELF - is skipped with every part of it.
+ * The rigs' definitions do not change: a sensor answers mgf_batch_raycast_many of the particle it forms, a feeler _sweep_many of its
+ * cast, a zone the box overlap of its box; MGF_FEELER_OWN_SHAPE on a body of several components casts the collider row as
+ * mgf_batch_read_colliders packs it - a radius-0 sphere at the centre of mass.  Between ticks the parts are those of the last tick, or
+ * as added before any tick (as the colliders): mgf_batch_write_state and mgf_batch_set_many move no part.  A call makes the number of
+ * launches it makes without the option.  OUT OF SCOPE: mgf_batch_cast_cameras(_dev) stay refused ("several components") with the
+ * option set too - the tile cull over parts is not built. */
 #define MGF_BATCH_MAX_BODIES 1024
 MGF_API mgf_status mgf_batch_new(mgf_ctx* ctx, const mgf_params* params, int64_t n_worlds, mgf_batch** out);  /* n_worlds x World::new world.rs:160 */
 MGF_API void mgf_batch_free(mgf_batch* b);
@@ -1431,7 +1446,8 @@ MGF_API mgf_status mgf_batch_rollout_touches_dev(mgf_batch* b, float dt, int32_t
  * ticks' own, the touch trace's one a tick a pass among them), "springs_skipped" (above)}. */
 MGF_API mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out);
 /* Options (test knobs): "cons_per_body" [4] = the constraint records per body a world's share of the storage starts with (1 .. 4096); a
- * low value makes the first busy tick outgrow it, which the re-run path then handles. */
+ * low value makes the first busy tick outgrow it, which the re-run path then handles.  "part_queries" [0] = 0 | 1 (any other value:
+ * MGF_ERR_INVALID): rays, sweeps and box queries see the parts of bodies of several components (PART QUERIES, above); no device work. */
 MGF_API mgf_status mgf_batch_set_option(mgf_batch* b, const char* key, int64_t value);
 
 #ifdef __cplusplus

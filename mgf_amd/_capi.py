@@ -2279,6 +2279,8 @@ class WorldBatch:
         return v.value
 
     def set_option(self, key, value):
+        """mgf_batch_set_option: "cons_per_body" (1 .. 4096), or "part_queries" (0 | 1) - with 1 raycast, sweep, the sensors, feelers,
+        box overlaps and zones of a batch that holds bodies of several components see their parts (a hit's `part`); the cameras do not"""
         _check(load_library().mgf_batch_set_option(self._h, key.encode(), int(value)))
 
 

@@ -33,6 +33,7 @@ struct mgf_batch {
   enum { AX, AQ, ASREC, ASP0, ASP1, ACTOR, AIMB, ADELTA, AFBC, AFBR, ACOL0, ACOL1, ALP0, ALP1, AWP0, AWP1, kArr, kArrPlain = ALP0 };
   static constexpr int kWords[kArr] = {1, 1, 4, 1, 1, 1, 3, 1, 1, 1, 1, 1, kMaxParts, kMaxParts, kMaxParts, kMaxParts};
   bool parts = false;                // the batch has part rows: its tick is k_batch_parts.h's, the calls that read shapes are refused
+  bool part_queries = false;         // option "part_queries": with part rows, rays, sweeps and box queries answer part by part (host_batch_part_query.inc)
   int n_arr() const { return parts ? (int)kArr : (int)kArrPlain; }
   DBuf<float4> pool;                 // ... and the kept contacts of its pairs of bodies, three words an entry, as many as constraint records
   std::vector<float4> hm[kArr];
@@ -294,6 +295,11 @@ extern "C" mgf_status mgf_batch_set_option(mgf_batch* b, const char* key, int64_
     std::fill(b->h_floor.begin(), b->h_floor.end(), 0u);
     std::fill(b->h_qfloor.begin(), b->h_qfloor.end(), 0u);
     if (b->dev_valid) { b->lists_valid = false; MGF_TRY(batch_allot(b, false)); }
+    return MGF_OK;
+  }
+  if (!strcmp(key, "part_queries")) {  // (no device work: the next query call launches the other kernels)
+    if (value != 0 && value != 1) return fail(MGF_ERR_INVALID, "part_queries must be 0 or 1");
+    b->part_queries = value == 1;
     return MGF_OK;
   }
   return fail(MGF_ERR_INVALID, "unknown batch option");
@@ -657,9 +663,10 @@ static mgf_status batch_parts_enable(mgf_batch* b) {
   b->parts = true;
   return MGF_OK;
 }
-// the calls that read the shapes of bodies do not see parts yet: refused on a batch that holds a body of several components
-static mgf_status batch_single_parts(const mgf_batch* b, const char* call) {
-  if (!b->parts) return MGF_OK;
+// the calls that read the shapes of bodies do not see parts unless asked to: refused on a batch that holds a body of several components,
+// except - for the calls that have a part-aware body pass (part_aware: all but the cameras') - under option "part_queries"
+static mgf_status batch_single_parts(const mgf_batch* b, const char* call, bool part_aware = true) {
+  if (!b->parts || (part_aware && b->part_queries)) return MGF_OK;
   return fail(MGF_ERR_INVALID, (std::string(call) + ": the batch holds bodies of several components, which this call does not see yet").c_str());
 }
 

@@ -110,7 +110,7 @@ static mgf_status batch_camera_args(const mgf_batch* b, int32_t kinds_mask, cons
 extern "C" mgf_status mgf_batch_cast_cameras(mgf_batch* b, int32_t kinds_mask, float* depth, mgf_ray_hit* hits, mgf_particle* parts_out, int64_t cap) {
   size_t n = 0;
   MGF_TRY(batch_camera_args(b, kinds_mask, depth, hits, cap, &n));
-  MGF_TRY(batch_single_parts(b, "mgf_batch_cast_cameras"));
+  MGF_TRY(batch_single_parts(b, "mgf_batch_cast_cameras", false));
   MGF_TRY(ctx_bind(b->ctx));
   batch_call_begin(b);
   if (n == 0) return MGF_OK;
@@ -130,7 +130,7 @@ extern "C" mgf_status mgf_batch_cast_cameras_dev(mgf_batch* b, int32_t kinds_mas
                                                  int64_t cap) {
   size_t n = 0;
   MGF_TRY(batch_camera_args(b, kinds_mask, depth_dev, hits_dev, cap, &n));
-  MGF_TRY(batch_single_parts(b, "mgf_batch_cast_cameras_dev"));
+  MGF_TRY(batch_single_parts(b, "mgf_batch_cast_cameras_dev", false));
   MGF_TRY(ctx_bind(b->ctx));
   MGF_TRY(dev_span(b->ctx, depth_dev, 4 * n, "depth_dev"));
   MGF_TRY(dev_span(b->ctx, hits_dev, 28 * n, "hits_dev"));

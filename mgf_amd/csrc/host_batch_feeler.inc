@@ -57,7 +57,8 @@ static mgf_status batch_feeler_run(mgf_batch* b, int32_t kinds_mask, int32_t* ou
   A.x = b->dm[mgf_batch::AX].p; A.q = b->dm[mgf_batch::AQ].p;
   A.rig = reinterpret_cast<const FeelerIn*>(R.dev.p + R.off[1]);
   A.casts = casts_dev;
-  k_batch_feeler_bodies<<<(unsigned)R.items.size(), kBatchBlock, batch_ray_lds(b), b->ctx->stream>>>(A);
+  if (batch_part_queries(b)) MGF_TRY(batch_pq_feeler(b, A, (unsigned)R.items.size()));  // (the body pass sees parts)
+  else k_batch_feeler_bodies<<<(unsigned)R.items.size(), kBatchBlock, batch_ray_lds(b), b->ctx->stream>>>(A);
   LAUNCH_CHECK();
   b->q_launches += MGF_BATCH_FEELER_LAUNCHES;
   return batch_sweep_tail(b, batch_has_faces(b, kinds_mask), batch_has_obstacles(b, kinds_mask), reinterpret_cast<const int32_t*>(R.dev.p + R.off[3]), 0u, casts_dev,

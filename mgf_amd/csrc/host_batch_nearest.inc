@@ -39,7 +39,8 @@ static mgf_status batch_nearest_run(mgf_batch* b, int32_t k, int32_t* out_dev, f
   A.boxes_out = boxes_dev;
   BatchItemSrc S;
   memset(&S, 0, sizeof(S));
-  k_batch_nearest<kItemTable><<<(unsigned)R.items.size(), kBatchBlock, batch_zone_lds(b), b->ctx->stream>>>(A, S);
+  if (batch_part_queries(b)) MGF_TRY(batch_pq_nearest<kItemTable>(b, A, S, (unsigned)R.items.size(), batch_zone_lds(b)));  // (a body's box: the union of its parts')
+  else k_batch_nearest<kItemTable><<<(unsigned)R.items.size(), kBatchBlock, batch_zone_lds(b), b->ctx->stream>>>(A, S);
   LAUNCH_CHECK();
   b->q_launches += MGF_BATCH_NEAREST_LAUNCHES;
   return MGF_OK;
@@ -131,7 +132,8 @@ extern "C" mgf_status mgf_batch_overlap_nearest_dev(mgf_batch* b, const mgf_aabb
   memset(&S, 0, sizeof(S));
   S.per = (uint32_t)(n / b->K);  // (n > 0 and a multiple of K: at least 1)
   const unsigned grid = (unsigned)((size_t)b->K * ((S.per + 255u) / 256u));
-  k_batch_nearest<kItemFixed><<<grid, kBatchBlock, batch_zone_lds(b), b->ctx->stream>>>(A, S);
+  if (batch_part_queries(b)) MGF_TRY(batch_pq_nearest<kItemFixed>(b, A, S, grid, batch_zone_lds(b)));
+  else k_batch_nearest<kItemFixed><<<grid, kBatchBlock, batch_zone_lds(b), b->ctx->stream>>>(A, S);
   LAUNCH_CHECK();
   b->q_launches += MGF_BATCH_NEAREST_LAUNCHES;
   return MGF_OK;

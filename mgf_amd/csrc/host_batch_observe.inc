@@ -62,7 +62,9 @@ extern "C" mgf_status mgf_batch_overlap_aabb_many(mgf_batch* b, const int32_t* w
   A.boxes = reinterpret_cast<const float*>(U.queries);
   A.cnt = b->q_cnt.p; A.off = b->q_off.p;
   MGF_TRY(b->q_tm.mark(0, s));
-  k_batch_observe_overlap<false><<<(unsigned)U.n_items, kBatchBlock, U.lds, s>>>(A);
+  const bool pq = batch_part_queries(b);  // a body's box: the union of its parts' (host_batch_part_query.inc)
+  if (pq) MGF_TRY(batch_pq_overlap<false>(b, A, (unsigned)U.n_items, U.lds));
+  else k_batch_observe_overlap<false><<<(unsigned)U.n_items, kBatchBlock, U.lds, s>>>(A);
   LAUNCH_CHECK();
   ++b->q_launches;
   MGF_TRY(b->q_tm.mark(1, s));
@@ -76,7 +78,8 @@ extern "C" mgf_status mgf_batch_overlap_aabb_many(mgf_batch* b, const int32_t* w
   A.out = b->q_vals.p;
   MGF_TRY(b->q_tm.mark(0, s));
   MGF_TRY(prim_exclusive_scan_u32(ctx, b->q_cnt.p, b->q_off.p, n + 1));  // (a library primitive: not counted among the launches)
-  k_batch_observe_overlap<true><<<(unsigned)U.n_items, kBatchBlock, U.lds, s>>>(A);
+  if (pq) MGF_TRY(batch_pq_overlap<true>(b, A, (unsigned)U.n_items, U.lds));
+  else k_batch_observe_overlap<true><<<(unsigned)U.n_items, kBatchBlock, U.lds, s>>>(A);
   LAUNCH_CHECK();
   ++b->q_launches;
   MGF_TRY(b->q_tm.mark(1, s));

@@ -173,13 +173,16 @@ static mgf_status batch_query_run(mgf_batch* b, const int32_t* world, const Q* q
   A.out = b->q_out.p;
   const Q* dq = reinterpret_cast<const Q*>(U.queries);
   MGF_TRY(b->q_tm.mark(0, s));
+  const bool pq = batch_part_queries(b);  // the body pass sees parts (host_batch_part_query.inc)
   if constexpr (kRays) {
-    k_batch_query_ray<<<(unsigned)U.n_items, kBatchBlock, lds, s>>>(A, dq);
+    if (pq) MGF_TRY(batch_pq_bodies<kItemTable>(b, A, dq, BatchItemSrc(), (unsigned)U.n_items));
+    else k_batch_query_ray<<<(unsigned)U.n_items, kBatchBlock, lds, s>>>(A, dq);
     LAUNCH_CHECK();
     ++b->q_launches;
     if (obstacles) MGF_TRY(batch_ray_obstacles(b, U.world, 0u, dq, n, A.out));
   } else {
-    k_batch_query_sweep_bodies<<<(unsigned)U.n_items, kBatchBlock, lds, s>>>(A, dq);
+    if (pq) MGF_TRY(batch_pq_bodies<kItemTable>(b, A, dq, BatchItemSrc(), (unsigned)U.n_items));
+    else k_batch_query_sweep_bodies<<<(unsigned)U.n_items, kBatchBlock, lds, s>>>(A, dq);
     LAUNCH_CHECK();
     ++b->q_launches;
     MGF_TRY(batch_sweep_tail(b, faces, obstacles, U.world, 0u, dq, n, A.out));

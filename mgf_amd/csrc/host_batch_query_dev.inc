@@ -72,6 +72,7 @@ static mgf_status batch_query_dev_run(mgf_batch* b, const int32_t* world_dev, co
   BatchItemSrc S;
   memset(&S, 0, sizeof(S));
   S.skipped = D.skipped;
+  const bool pq = batch_part_queries(b);  // the body pass sees parts (host_batch_part_query.inc)
   const int32_t* lane_world = nullptr;  // what the lane-per-query passes take a query's world from (null: i / per)
   if (world_dev) {
     const size_t item_cap = n / 256 + std::min<size_t>(n, K);
@@ -97,12 +98,14 @@ static mgf_status batch_query_dev_run(mgf_batch* b, const int32_t* world_dev, co
     A.items = P.items; A.order = P.order;
     S.n_items = P.istart + K;
     lane_world = P.wsan;
-    if constexpr (kRays) k_batch_query_ray_dev<kItemPlan><<<(unsigned)item_cap, kBatchBlock, lds, s>>>(A, q_dev, S);
+    if (pq) MGF_TRY(batch_pq_bodies<kItemPlan>(b, A, q_dev, S, (unsigned)item_cap));
+    else if constexpr (kRays) k_batch_query_ray_dev<kItemPlan><<<(unsigned)item_cap, kBatchBlock, lds, s>>>(A, q_dev, S);
     else k_batch_query_sweep_bodies_dev<kItemPlan><<<(unsigned)item_cap, kBatchBlock, lds, s>>>(A, q_dev, S);
   } else {
     S.per = (uint32_t)(n / K);  // (n > 0 and a multiple of K: at least 1)
     const unsigned grid = (unsigned)((size_t)K * ((S.per + 255u) / 256u));
-    if constexpr (kRays) k_batch_query_ray_dev<kItemFixed><<<grid, kBatchBlock, lds, s>>>(A, q_dev, S);
+    if (pq) MGF_TRY(batch_pq_bodies<kItemFixed>(b, A, q_dev, S, grid));
+    else if constexpr (kRays) k_batch_query_ray_dev<kItemFixed><<<grid, kBatchBlock, lds, s>>>(A, q_dev, S);
     else k_batch_query_sweep_bodies_dev<kItemFixed><<<grid, kBatchBlock, lds, s>>>(A, q_dev, S);
   }
   LAUNCH_CHECK();

@@ -46,7 +46,8 @@ static mgf_status batch_sensor_run(mgf_batch* b, int32_t kinds_mask, int32_t* ou
   A.x = b->dm[mgf_batch::AX].p; A.q = b->dm[mgf_batch::AQ].p;
   A.rig = reinterpret_cast<const SensorIn*>(R.dev.p + R.off[1]);
   A.parts = parts_dev;
-  k_batch_sensor_ray<<<(unsigned)R.items.size(), kBatchBlock, batch_ray_lds(b), s>>>(A);
+  if (batch_part_queries(b)) MGF_TRY(batch_pq_sensor(b, A, (unsigned)R.items.size()));  // (the body pass sees parts)
+  else k_batch_sensor_ray<<<(unsigned)R.items.size(), kBatchBlock, batch_ray_lds(b), s>>>(A);
   LAUNCH_CHECK();
   b->q_launches += MGF_BATCH_SENSOR_LAUNCHES;
   if (!obstacles) return MGF_OK;

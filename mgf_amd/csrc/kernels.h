@@ -168,6 +168,12 @@
 //                      list behind tick t into row t of the reports, one launch a tick behind k_batch_rollout_record; the train's gate
 //                      done[k] == t + 1 && act[k] <= t + 1 is the workgroup's and is folded into the item's count and the list's
 //                      length; a full report of 64 bytes or a short one of 16
+//   k_batch_pq_ray<SRC> / _sweep<SRC> / _sensor / _feeler / _overlap<FILL> / _zone<SRC> / _nearest<SRC> (k_batch_part_query.h)
+//                      the body passes of the rays, sweeps, sensors, feelers, box overlaps and zones of a batch that holds bodies of
+//                      several components, under option "part_queries": the fronts of the kernels above restated with every part of
+//                      every body through the single-shape test (`part` of a hit), a reject sphere per body of several parts staged
+//                      beside the colliders, the parts read from wp0 / wp1 for the bodies that survive it, `part` carried through
+//                      the reduction (PartBest); a body's box the union of its parts' bounds.  The passes behind them are unchanged
 //   k_query_* (k_query.h) ray casts, sweeps and box overlaps against the world's bodies, terrain and obstacles between ticks, over a grid
 //                      of the bodies' current tight boxes built per call (never the tick's lists).  k_query.h is also where every test
 //                      and record of a query is written once, for the world's kernels and the batch's: to_comp(float4, float4), the
@@ -198,4 +204,5 @@
 #include "k_batch_actuator.h"  // actuators: wrenches formed from the resident poses and applied, a lane per body (k_batch_actuate)
 #include "k_batch_rollout.h"  // rollouts: a row of controls ahead of every tick of a step call, a row of state behind it (k_batch_rollout_act, _record)
 #include "k_batch_spring.h"  // springs between bodies: impulses formed from the resident state, applied a lane per body (k_batch_spring_wrench, _apply)
+#include "k_batch_part_query.h"  // rays, sweeps and box queries that see the parts of bodies of several components (k_batch_pq_*)
 #include "k_batch_trace.h"  // the touch trace of a rollout: the contact sensors' reports behind every tick (k_batch_trace_touch)

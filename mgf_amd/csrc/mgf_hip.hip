@@ -163,6 +163,7 @@ extern "C" mgf_status mgf_exclusive_scan_u32(mgf_ctx* ctx, const uint32_t* in, i
 #include "host_tiles_native.inc"
 #include "host_query.inc"
 #include "host_batch.inc"
+#include "host_batch_part_query.inc"
 #include "host_batch_query.inc"
 #include "host_batch_observe.inc"
 #include "host_batch_drive.inc"
