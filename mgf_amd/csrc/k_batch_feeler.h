@@ -10,15 +10,14 @@
 // forms its particle.  Its answer is what k_batch_query_sweep_bodies (and the two passes behind it) write for C against that world, with
 // `body` ignored if MGF_FEELER_IGNORE_SELF is set.
 //   k_batch_feeler_bodies   a workgroup per work item of the rig's table - built on the host when the rig is set (BatchQueryPlan: a
-//                           world's feelers in the caller's order, up to 256 an item, 256 / next_pow2(count) lanes a feeler).  The
-//                           world's colliders staged as bq_stage does - whatever the mask: an OWN_SHAPE feeler reads its body's - then
-//                           every live lane loads its record and the body's x and q and forms C; the walk over the bodies is
-//                           bq_sweep_item's (q_sweep_far, then comp_mcomp, then SweepBest::offer), the reduction bq_reduce; the feeler's
-//                           first lane stores the hit (q_sweep_store) and, always, C - into the caller's array or the handle's
-// bq_sweep_item itself stays as it is: k_batch_query_sweep_bodies and its _dev forms keep their register figures (tests/util.py), so
-// the loop over the bodies stands here a second time, in bf_sweep_front - a front with a loader, as bq_ray_front is.
+//                           world's feelers in the caller's order, up to 256 an item, 256 / next_pow2(count) lanes a feeler) - through
+//                           bq_sweep_front (k_batch_query.h), the front of k_batch_query_sweep_bodies: the staging, the lanes a feeler
+//                           gets, the walk over the bodies (q_sweep_far, then comp_mcomp, then SweepBest::offer), the reduction and the
+//                           stored hit (q_sweep_store) are that function's, written once.  What is here is where the cast comes from -
+//                           every live lane loads its record and the body's x and q and forms C - and, behind the hit, C stored by
+//                           the feeler's first lane - always, into the caller's array or the handle's
 // The terrain faces and the obstacles are k_batch_query_sweep_faces' / _sweep_obstacles' (k_batch_query.h), unchanged, over the stored
-// casts and the rig's worlds.  Every exit and every barrier is bf_sweep_front's: the loader and the store below hold neither.
+// casts and the rig's worlds.  Every exit and every barrier is bq_sweep_front's: the loader and the store below hold neither.
 #pragma once
 #include "k_batch_query.h"
 
@@ -35,49 +34,16 @@ struct BatchFeelerArgs : BatchQueryArgs {
   MovingIn* casts;       // by the caller's index: 11 words a feeler (mgf_moving_component); never null
 };
 
-// A live feeler's cast in world coordinates and the body of its world it does not meet (-1: none): what a loader hands bf_sweep_front
-struct BatchCast { MovingIn m; int32_t ign; };
-
-// A workgroup's work item of casts formed by a loader - load(qi, g0, s_c0, s_c1) -> BatchCast, run by the live lanes behind the
-// staging - and what else a cast's first lane does behind the stored hit - done(qi, m).  Neither holds a barrier nor leaves the kernel.
-// The colliders are staged whatever the mask (the loader may read them); the bodies are walked where the mask asks for them.
-// The only exit is behind bq_reduce: a whole workgroup reaches both barriers.
-template <class Load, class Done>
-__device__ __forceinline__ void bf_sweep_front(const BatchQueryArgs& A, float4* s_dyn, Load&& load, Done&& done) {
-  BatchWork W(A, true);
-  const uint32_t n = W.n;
-  float4 *s_c0 = s_dyn, *s_c1 = s_dyn + n, *s_red = s_dyn + 2 * (size_t)n;
-  bq_stage(A, W.g0, n, s_c0, s_c1);
-  W.split(A, W.shift());
-  const uint32_t qi = W.qi;
-  SweepBest best;
-  BatchCast c;
-  if (W.live) {
-    c = load(qi, W.g0, s_c0, s_c1);
-    if (A.mask & MGF_QUERY_BODIES) {
-      const SweepCast K = bq_sweep_cast(c.m);
-      const int32_t ign = c.ign;
-      for (uint32_t i = W.sub; i < n; i += W.L) {
-        if ((int32_t)i == ign) continue;
-        const Comp t = to_comp(s_c0[i], s_c1[i]);
-        if (q_sweep_far(t, K)) continue;
-        Contact k;
-        if (comp_mcomp(t, K.s, K.v, &k)) best.offer(k, MGF_HIT_BODY, i, 0u, 0u);
-      }
-    }
-  }
-  bq_reduce(best, W, s_red);
-  if (W.sub != 0u || !W.live) return;
-  q_sweep_store(A.out + 13 * (size_t)qi, best);
-  done(qi, c.m);
-}
-
-// LDS (dynamic): 32 bytes a body, kBatchQueryRed words - as k_batch_query_sweep_bodies.
-__global__ __launch_bounds__(kBatchBlock) void k_batch_feeler_bodies(BatchFeelerArgs A) {
-  extern __shared__ float4 s_dyn[];
-  bf_sweep_front(
-      A, s_dyn,
-      [&](uint32_t qi, uint32_t g0, const float4* s_c0, const float4* s_c1) {
+// A work item of the rig's table through bq_sweep_front, over either policy of the bodies (k_batch_feeler_bodies, and its part-aware
+// form in k_batch_part_query.h): the loader that forms a feeler's cast, and the cast stored behind the hit.  MGF_FEELER_OWN_SHAPE: the
+// body's collider row as mgf_batch_read_colliders packs it, read from col0 / col1 themselves, not from the staged rows - a mask without
+// bodies stages none, and the part rows stage a reject sphere, which is no shape of the body (for a body of several parts the row is
+// a radius-0 sphere at the centre of mass).
+template <class Bodies>
+__device__ __forceinline__ void bf_casts(const BatchFeelerArgs& A, Bodies bodies, float4* s_dyn) {
+  bq_sweep_front<kItemTable>(
+      A, bodies, BatchItemSrc(), s_dyn,
+      [&](uint32_t qi, uint32_t g0) {
         const FeelerIn f = A.rig[qi];
         const size_t g = (size_t)g0 + (uint32_t)f.body;
         const float4 bx = A.x[g], bq = A.q[g];
@@ -85,7 +51,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_feeler_bodies(BatchFeeler
         BatchCast c;
         V3 P, D;
         if (f.flags & MGF_FEELER_OWN_SHAPE) {  // (k_pack_colliders' words)
-          const float4 a = s_c0[f.body], b = s_c1[f.body];
+          const float4 a = A.col0[g], b = A.col1[g];
           c.m.tag = (int)f2u(b.w); c.m.r = a.w;
           P = xyz(a); D = xyz(b);
         } else {
@@ -100,6 +66,12 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_feeler_bodies(BatchFeeler
         return c;
       },
       [&](uint32_t qi, const MovingIn& m) { A.casts[qi] = m; });
+}
+
+// LDS (dynamic): 32 bytes a body, kBatchQueryRed words - as k_batch_query_sweep_bodies.
+__global__ __launch_bounds__(kBatchBlock) void k_batch_feeler_bodies(BatchFeelerArgs A) {
+  extern __shared__ float4 s_dyn[];
+  bf_casts(A, PlainBodies(A), s_dyn);
 }
 
 }  // namespace mgf

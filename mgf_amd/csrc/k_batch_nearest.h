@@ -62,30 +62,17 @@ struct NearestPick {
   }
 };
 
-// LDS (dynamic): 32 bytes a body.
-template <int SRC>
-__global__ __launch_bounds__(kBatchBlock) void k_batch_nearest(BatchNearestArgs A, BatchItemSrc S) {
-  extern __shared__ float4 s_dyn[];
+// k_batch_nearest<SRC> and its part-aware form (k_batch_part_query.h), written once over the bodies' policy: the distances are measured
+// from the centre of the box the policy staged
+template <int SRC, class Bodies>
+__device__ __forceinline__ void bn_nearest(const BatchNearestArgs& A, const Bodies& bodies, const BatchItemSrc& S, float4* s_dyn) {
   BatchWork W(A, true, bq_item<SRC>(A, S));
   const uint32_t k = A.k;
   BatchBox z;
-  const auto fixed = [&](uint32_t qi, uint32_t) {
-    return BatchBox{{ld3(A.boxes + 6 * (size_t)qi), ld3(A.boxes + 6 * (size_t)qi + 3)}, A.ignore ? A.ignore[qi] : -1};
-  };
-  const auto mounted = [&](uint32_t qi, uint32_t g0) {
-    const ZoneIn s = A.rig[qi];
-    BatchBox b;
-    b.Q.c = ld3(s.p); b.Q.r = ld3(s.r);
-    if (s.body >= 0) {
-      const size_t g = (size_t)g0 + (uint32_t)s.body;
-      const float4 bx = A.x[g], bq = A.q[g];
-      b.Q.c = xyz(bx) + rotate(mkq(bq.x, mk3(bq.y, bq.z, bq.w)), ld3(s.p));
-    }
-    b.ign = (s.flags & MGF_SENSOR_IGNORE_SELF) ? s.body : -1;
-    return b;
-  };
+  const auto fixed = [&](uint32_t qi, uint32_t) { return bz_fixed(A, qi); };
+  const auto mounted = [&](uint32_t qi, uint32_t g0) { return bz_mounted(A, qi, g0); };
   const auto count_only = [](bool, uint32_t, uint32_t) {};
-  const uint32_t m = SRC == kItemFixed ? bo_front<true, true>(A, W, s_dyn, z, fixed, count_only) : bo_front<false, true>(A, W, s_dyn, z, mounted, count_only);
+  const uint32_t m = SRC == kItemFixed ? bo_front<true, true>(A, bodies, W, s_dyn, z, fixed, count_only) : bo_front<false, true>(A, bodies, W, s_dyn, z, mounted, count_only);
   const uint32_t n = W.n, L = W.L, sub = W.sub;
   const bool live = W.live, first = live && sub == 0u;
   const float4 *s_c = s_dyn, *s_r = s_dyn + n;  // (as the front staged them)
@@ -125,11 +112,15 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_nearest(BatchNearestArgs 
   }
   if (first) {
     o[0] = (int32_t)m;
-    if (A.boxes_out) {
-      float* bo = A.boxes_out + 6 * (size_t)W.qi;
-      bo[0] = Q.c.x; bo[1] = Q.c.y; bo[2] = Q.c.z; bo[3] = Q.r.x; bo[4] = Q.r.y; bo[5] = Q.r.z;
-    }
+    if (A.boxes_out) bz_box_out(A.boxes_out, W.qi, Q);
   }
+}
+
+// LDS (dynamic): 32 bytes a body.
+template <int SRC>
+__global__ __launch_bounds__(kBatchBlock) void k_batch_nearest(BatchNearestArgs A, BatchItemSrc S) {
+  extern __shared__ float4 s_dyn[];
+  bn_nearest<SRC>(A, PlainBodies(A), S, s_dyn);
 }
 
 }  // namespace mgf

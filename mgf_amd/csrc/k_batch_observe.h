@@ -108,14 +108,15 @@ struct BatchOverlapArgs : BatchWorkArgs {
 struct BatchBox { Box Q; int32_t ign; };
 
 // IGNORE = false: no box of the kernel names a body - `ign` is not looked at.  W comes back split, z as loaded (not live: zeros, -1).
+// bodies: where a body's box comes from - box(g), PlainBodies' or PartBodies' (k_batch_query.h).
 // Every lane of a wave makes every trip of the loop (n and L are the work item's); there is no exit; a NaN box hits nothing because
 // box_overlaps is false for it.
-template <bool IDENTITY, bool IGNORE, class Load, class Put>
-__device__ __forceinline__ uint32_t bo_front(const BatchWorkArgs& A, BatchWork& W, float4* s_dyn, BatchBox& z, Load&& load, Put&& put) {
+template <bool IDENTITY, bool IGNORE, class Bodies, class Load, class Put>
+__device__ __forceinline__ uint32_t bo_front(const BatchWorkArgs& A, const Bodies& bodies, BatchWork& W, float4* s_dyn, BatchBox& z, Load&& load, Put&& put) {
   const uint32_t tid = threadIdx.x, g0 = W.g0, n = W.n;
   float4 *s_c = s_dyn, *s_r = s_dyn + n;
   for (uint32_t i = tid; i < n; i += kBatchBlock) {
-    const Box tb = comp_bounds(to_comp(A.col0[(size_t)g0 + i], A.col1[(size_t)g0 + i]));
+    const Box tb = bodies.box((size_t)g0 + i);
     s_c[i] = mk4(tb.c, 0.0f); s_r[i] = mk4(tb.r, 0.0f);
   }
   __syncthreads();
@@ -143,15 +144,14 @@ __device__ __forceinline__ uint32_t bo_front(const BatchWorkArgs& A, BatchWork& 
   return m;
 }
 
-// LDS (dynamic): 32 bytes a body.
-template <bool FILL>
-__global__ __launch_bounds__(kBatchBlock) void k_batch_observe_overlap(BatchOverlapArgs A) {
-  extern __shared__ float4 s_dyn[];
+// k_batch_observe_overlap<FILL> and its part-aware form (k_batch_part_query.h), written once over the bodies' policy
+template <bool FILL, class Bodies>
+__device__ __forceinline__ void bo_overlap(const BatchOverlapArgs& A, const Bodies& bodies, float4* s_dyn) {
   BatchWork W(A, true);
   BatchBox z;
   uint32_t base = 0u;  // FILL: where the box's list begins
   const uint32_t m = bo_front<false, false>(
-      A, W, s_dyn, z,
+      A, bodies, W, s_dyn, z,
       [&](uint32_t qi, uint32_t) {
         if (FILL) base = A.off[qi];
         return BatchBox{{ld3(A.boxes + 6 * (size_t)qi), ld3(A.boxes + 6 * (size_t)qi + 3)}, -1};
@@ -160,6 +160,13 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_observe_overlap(BatchOver
         if (FILL && hit) A.out[base + rank] = i;
       });
   if (!FILL && W.live && W.sub == 0u) A.cnt[W.qi] = m;
+}
+
+// LDS (dynamic): 32 bytes a body.
+template <bool FILL>
+__global__ __launch_bounds__(kBatchBlock) void k_batch_observe_overlap(BatchOverlapArgs A) {
+  extern __shared__ float4 s_dyn[];
+  bo_overlap<FILL>(A, PlainBodies(A), s_dyn);
 }
 
 }  // namespace mgf

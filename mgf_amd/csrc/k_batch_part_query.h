@@ -7,13 +7,14 @@
 // parts are the world parts wp0 / wp1 (four slots a body: written when the body is added and by k_batch_parts_front every tick), the
 // part count the second word of the constructor row of a body whose first word is 2 (batch_np, k_batch_parts.h) - taken as
 // min(count, kMaxParts), so that a bad word in memory cannot lengthen a loop.
-// The work split is k_batch_query.h's and k_batch_observe.h's, restated here so that those kernels keep their compiler figures: a
-// workgroup per work item, 256 / next_pow2(count) lanes a query, bq_reduce across lanes and waves; the box fronts a query's lanes in
-// one wave and a hit's rank from the ballot.
-//   k_batch_pq_ray<SRC>      bq_ray_item over pq_ray_front      k_batch_pq_sensor    k_batch_sensor_ray over pq_ray_front
-//   k_batch_pq_sweep<SRC>    bq_sweep_item over pq_sweep_front  k_batch_pq_feeler    k_batch_feeler_bodies over pq_sweep_front
-//   k_batch_pq_overlap<FILL> k_batch_observe_overlap, k_batch_pq_zone<SRC> k_batch_zone_first, k_batch_pq_nearest<SRC> k_batch_nearest,
-//                            each over pq_bo_front: only the staging differs - the staged box is the union of the parts' bounds
+// The work split, the fronts and the kernels' bodies are the existing kernels' own, written once in their headers over a policy of the
+// bodies (k_batch_query.h, at PlainBodies): a workgroup per work item, 256 / next_pow2(count) lanes a query, bq_reduce across lanes and
+// waves; the box front a query's lanes in one wave and a hit's rank from the ballot.  Here is the policy that sees parts, PartBodies -
+// the staging, the body-level rejects, the two walks, a body's box - and a kernel per existing kernel that passes it:
+//   k_batch_pq_ray<SRC>      bq_ray_item (bq_ray_front)             k_batch_pq_sensor    bs_rays (k_batch_sensor.h)
+//   k_batch_pq_sweep<SRC>    bq_sweep_item (bq_sweep_front)         k_batch_pq_feeler    bf_casts (k_batch_feeler.h)
+//   k_batch_pq_overlap<FILL> bo_overlap (k_batch_observe.h), k_batch_pq_zone<SRC> bz_first (k_batch_zone.h), k_batch_pq_nearest<SRC>
+//                            bn_nearest (k_batch_nearest.h), each through bo_front: the staged box is the union of the parts' bounds
 // The passes behind a body pass - k_batch_query_sweep_faces, _ray_obstacles, _sweep_obstacles, q_ray_terrain in the ray front's tail -
 // are the existing ones, unchanged.
 //
@@ -47,8 +48,7 @@
 // PART THROUGH THE REDUCTION.  QueryBest's shfl / pack / unpack / merge leave `part` behind (the bodies of the existing kernels have
 // one).  PartBest carries it - in the packed candidate's free fourth word - and merges with it; SweepBest carries it already.
 //
-// BARRIERS.  As in the fronts restated: no lane leaves ahead of a __syncthreads (kItemPlan: a whole workgroup at or beyond the item
-// total leaves before the first); the only other exit is behind bq_reduce; every lane of a wave makes every trip of a ballot loop.
+// BARRIERS.  The fronts': the staging below ends with a front's first and holds no other, a walk holds none and leaves no kernel.
 // Between ticks the parts are those of the last tick, or as added before any tick - as col0 / col1; write_state and set_many move none.
 // No workgroup waits for another.
 #pragma once
@@ -149,347 +149,108 @@ __device__ __forceinline__ bool pq_sweep_far_body(float4 a, const SweepCast& K) 
   return dot(e, e) > lim * lim;
 }
 
-// the dynamic LDS of the ray and sweep fronts: rows | rows | kBatchQueryRed words | counts
-struct PqLds {
-  float4 *c0, *c1, *red;
-  uint32_t* np;
-  __device__ __forceinline__ PqLds(float4* s_dyn, uint32_t n) : c0(s_dyn), c1(s_dyn + n), red(s_dyn + 2 * (size_t)n) {
-    np = reinterpret_cast<uint32_t*>(red + kBatchQueryRed);
-  }
-};
-
-// bq_ray_front over parts (its remarks hold: load(qi, g0) -> BatchRay, done(qi, p, d, dt))
-template <int SRC, class Load, class Done>
-__device__ __forceinline__ void pq_ray_front(const BatchQueryArgs& A, const BatchPartRows& P, const BatchItemSrc& S, float4* s_dyn, Load&& load, Done&& done) {
-  if (SRC == kItemPlan && blockIdx.x >= *S.n_items) return;
-  BatchWork W(A, A.mask & MGF_QUERY_BODIES, bq_item<SRC>(A, S));
-  const uint32_t n = W.n;
-  const PqLds s(s_dyn, n);
-  pq_stage(A, P, W.g0, n, s.c0, s.c1, s.np);
-  W.template split<SRC == kItemFixed>(A, W.shift());
-  const uint32_t qi = W.qi;
-  V3 p = mk3(0.0f, 0.0f, 0.0f), d = p;
-  float dt = 0.0f;
-  int32_t ign = -1, mask = 0;
-  if (W.live) {
-    const BatchRay r = load(qi, W.g0);
-    p = r.p; d = r.d; dt = r.dt; ign = r.ign;
-    mask = A.mask;
-    if (d.x == 0.0f && d.y == 0.0f && d.z == 0.0f) mask = 0;  // (no direction: no hit, by definition - k_query_ray)
-  }
-  PartBest best;
-  if (mask & MGF_QUERY_BODIES) {
-    const float dd = dot(d, d);
-    for (uint32_t i = W.sub; i < n; i += W.L) {
-      if ((int32_t)i == ign) continue;  // (an ignored body: with every part of it)
-      const float4 a = s.c0[i], b = s.c1[i];
-      const uint32_t cw = s.np[i], np = cw & (kPqSeveral - 1u);
-      const bool several = cw & kPqSeveral;
-      if (several && pq_ray_far_body(a, p, d, dd, dt)) continue;
-      const size_t at = (size_t)kMaxParts * ((size_t)W.g0 + i);
-#pragma unroll 1
-      for (uint32_t k = 0; k < np; ++k) {
-        const float4 pa = several ? P.wp0[at + k] : a, pb = several ? P.wp1[at + k] : b;
-        if (bq_ray_far(pa, pb, p, d, dd, dt)) continue;
-        V3 ip; float t;
-        if (q_ray_comp(p, d, dt, pa, pb, &ip, &t)) best.offer(ip, t, MGF_HIT_BODY, i, k);
-      }
-    }
-  }
-  bq_reduce(best, W, s.red);
-  if (W.sub != 0u || !W.live) return;
-  if (mask & MGF_QUERY_TERRAIN) {
-    const BatchTerrain M = batch_terrain_of(A.T, W.it.x);  // (the work item's world: wave-uniform loads)
-    if (M.n_nodes) q_ray_terrain(M, p, d, dt, nullptr, best);
-  }
-  q_ray_store(A.out + 7 * (size_t)qi, best);
-  done(qi, p, d, dt);
-}
-
-// LDS (dynamic): 36 bytes a body, kBatchQueryRed words.
-template <int SRC>
-__global__ __launch_bounds__(kBatchBlock) void k_batch_pq_ray(BatchQueryArgs A, BatchPartRows P, const ParticleIn* parts, BatchItemSrc S) {
-  extern __shared__ float4 s_dyn[];
-  pq_ray_front<SRC>(
-      A, P, S, s_dyn,
-      [&](uint32_t qi, uint32_t) {
-        const ParticleIn q = parts[qi];
-        return BatchRay{ld3(q.p), ld3(q.d), q.dt, A.ignore ? A.ignore[qi] : -1};
-      },
-      [](uint32_t, V3, V3, float) {});
-}
-// k_batch_sensor_ray's loader and store (k_batch_sensor.h)
-__global__ __launch_bounds__(kBatchBlock) void k_batch_pq_sensor(BatchSensorArgs A, BatchPartRows P) {
-  extern __shared__ float4 s_dyn[];
-  pq_ray_front<kItemTable>(
-      A, P, BatchItemSrc(), s_dyn,
-      [&](uint32_t qi, uint32_t g0) {
-        const SensorIn s = A.rig[qi];
-        const size_t g = (size_t)g0 + (uint32_t)s.body;
-        const float4 bx = A.x[g], bq = A.q[g];
-        const Quat rot = mkq(bq.x, mk3(bq.y, bq.z, bq.w));
-        return BatchRay{xyz(bx) + rotate(rot, ld3(s.p)), rotate(rot, ld3(s.d)), s.dt, (s.flags & MGF_SENSOR_IGNORE_SELF) ? s.body : -1};
-      },
-      [&](uint32_t qi, V3 p, V3 d, float dt) {
-        if (A.parts) {
-          float* o = A.parts + 7 * (size_t)qi;
-          o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = d.x; o[4] = d.y; o[5] = d.z; o[6] = dt;
-        }
-      });
-}
-
-// bq_sweep_item and bf_sweep_front over parts, one front with a loader - load(qi, g0) -> BatchCast, run by the live lanes behind the
-// staging - and done(qi, m) behind the stored hit.  No loader reads the staged rows (the feelers' takes a body's own shape from col0 /
-// col1): a mask without bodies stages nothing.  kItemFixed: a cast whose tag is no component's is matched against nothing, keeps the
-// no-hit record and is counted by the first of its lanes (bq_sweep_item).
-template <int SRC, class Load, class Done>
-__device__ __forceinline__ void pq_sweep_front(const BatchQueryArgs& A, const BatchPartRows& P, const BatchItemSrc& S, float4* s_dyn, Load&& load, Done&& done) {
-  if (SRC == kItemPlan && blockIdx.x >= *S.n_items) return;
-  BatchWork W(A, A.mask & MGF_QUERY_BODIES, bq_item<SRC>(A, S));
-  const uint32_t n = W.n;
-  const PqLds s(s_dyn, n);
-  pq_stage(A, P, W.g0, n, s.c0, s.c1, s.np);
-  W.template split<SRC == kItemFixed>(A, W.shift());
-  const uint32_t qi = W.qi;
-  SweepBest best;
-  BatchCast c;
-  bool ok = W.live;
-  if (ok) {
-    c = load(qi, W.g0);
-    if (SRC == kItemFixed && (uint32_t)c.m.tag > (uint32_t)KIND_CAPSULE) {
-      ok = false;
-      if (W.sub == 0u) atomicAdd(S.skipped, 1ull);
-    }
-  }
-  if (ok && n) {  // (n: the mask asks for bodies, and the world has some)
-    const SweepCast K = bq_sweep_cast(c.m);
-    const int32_t ign = c.ign;
-    // (a lane's own pointers into the part rows, stepped with i: the rows' bases need no scalar registers through comp_mcomp)
-    const float4 *w0 = P.wp0 + (size_t)kMaxParts * ((size_t)W.g0 + W.sub), *w1 = P.wp1 + (size_t)kMaxParts * ((size_t)W.g0 + W.sub);
-    // ONE loop over (body i, part k) with one place for comp_mcomp - a loop of parts inside the loop of bodies costs the scalar
-    // registers that comp_mcomp has not to spare: a trip tests part k of body i, or skips the body whole (ignored; beyond the reject)
-    uint32_t k = 0u;
-    for (uint32_t i = W.sub; i < n;) {
-      const float4 a = s.c0[i], b = s.c1[i];
-      const uint32_t cw = s.np[i], np = cw & (kPqSeveral - 1u);
-      const bool several = cw & kPqSeveral;
-      bool next = (int32_t)i == ign || (several && k == 0u && pq_sweep_far_body(a, K));  // (an ignored body: with every part of it)
-      if (!next) {
-        const Comp t = several ? to_comp(w0[k], w1[k]) : to_comp(a, b);
-        Contact ct;
-        if (!q_sweep_far(t, K) && comp_mcomp(t, K.s, K.v, &ct)) best.offer(ct, MGF_HIT_BODY, i, k, 0u);
-        next = ++k >= np;
-      }
-      if (next) { k = 0u; i += W.L; w0 += (size_t)kMaxParts * W.L; w1 += (size_t)kMaxParts * W.L; }
-    }
-  }
-  bq_reduce(best, W, s.red);
-  if (W.sub != 0u || !W.live) return;
-  q_sweep_store(A.out + 13 * (size_t)qi, best);
-  done(qi, c.m);
-}
-
-// LDS (dynamic): 36 bytes a body, kBatchQueryRed words.
-template <int SRC>
-__global__ __launch_bounds__(kBatchBlock) void k_batch_pq_sweep(BatchQueryArgs A, BatchPartRows P, const MovingIn* casts, BatchItemSrc S) {
-  extern __shared__ float4 s_dyn[];
-  pq_sweep_front<SRC>(
-      A, P, S, s_dyn, [&](uint32_t qi, uint32_t) { return BatchCast{casts[qi], A.ignore ? A.ignore[qi] : -1}; }, [](uint32_t, const MovingIn&) {});
-}
-// k_batch_feeler_bodies' loader and store (k_batch_feeler.h).  MGF_FEELER_OWN_SHAPE: the body's collider row as mgf_batch_read_colliders
-// packs it, read from col0 / col1 - for a body of several parts a radius-0 sphere at the centre of mass (its staged rows hold the
-// reject sphere, which is no shape of the body).
-__global__ __launch_bounds__(kBatchBlock) void k_batch_pq_feeler(BatchFeelerArgs A, BatchPartRows P) {
-  extern __shared__ float4 s_dyn[];
-  pq_sweep_front<kItemTable>(
-      A, P, BatchItemSrc(), s_dyn,
-      [&](uint32_t qi, uint32_t g0) {
-        const FeelerIn f = A.rig[qi];
-        const size_t g = (size_t)g0 + (uint32_t)f.body;
-        const float4 bx = A.x[g], bq = A.q[g];
-        const Quat rot = mkq(bq.x, mk3(bq.y, bq.z, bq.w));
-        BatchCast c;
-        V3 Pw, D;
-        if (f.flags & MGF_FEELER_OWN_SHAPE) {  // (k_pack_colliders' words)
-          const float4 a = A.col0[g], b = A.col1[g];
-          c.m.tag = (int)f2u(b.w); c.m.r = a.w;
-          Pw = xyz(a); D = xyz(b);
-        } else {
-          c.m.tag = f.tag; c.m.r = f.r;
-          Pw = xyz(bx) + rotate(rot, ld3(f.p)); D = rotate(rot, ld3(f.d));
-        }
-        const V3 v = (f.flags & MGF_FEELER_WORLD_DELTA) ? ld3(f.delta) : rotate(rot, ld3(f.delta));
-        c.m.p[0] = Pw.x; c.m.p[1] = Pw.y; c.m.p[2] = Pw.z;
-        c.m.d[0] = D.x; c.m.d[1] = D.y; c.m.d[2] = D.z;
-        c.m.delta[0] = v.x; c.m.delta[1] = v.y; c.m.delta[2] = v.z;
-        c.ign = (f.flags & MGF_FEELER_IGNORE_SELF) ? f.body : -1;
-        return c;
-      },
-      [&](uint32_t qi, const MovingIn& m) { A.casts[qi] = m; });
-}
-
-// ---- boxes ----------------------------------------------------------------------------------------------------------------------------
-// q_body_box of body g: comp_bounds of its parts combined in order, or comp_bounds of the collider row
+// q_body_box of body g: comp_bounds of its parts combined in order, or the collider row's
 __device__ __forceinline__ Box pq_body_box(const BatchWorkArgs& A, const BatchPartRows& P, size_t g) {
-  if (!pq_several(P, g)) return comp_bounds(to_comp(A.col0[g], A.col1[g]));
+  if (!pq_several(P, g)) return PlainBodies(A).box(g);
   Box tb = comp_bounds(to_comp(P.wp0[kMaxParts * g], P.wp1[kMaxParts * g]));
   const uint32_t np = pq_count(P, g);  // (at least 1)
   for (uint32_t k = 1; k < np; ++k) tb = box_combine(tb, comp_bounds(to_comp(P.wp0[kMaxParts * g + k], P.wp1[kMaxParts * g + k])));
   return tb;
 }
 
-// KEEP IN STEP: pq_bo_front, k_batch_pq_overlap, k_batch_pq_zone and k_batch_pq_nearest are bo_front, k_batch_observe_overlap,
-// k_batch_zone_first and k_batch_nearest (k_batch_observe.h, k_batch_zone.h, k_batch_nearest.h) line for line behind the staging: a
-// change to one of those is made here as well.  They are restated, not shared, because the host tests of those kernels hold bo_front's
-// text and template list and the kernels' bodies as they stand, and their compiler figures.
-// bo_front (k_batch_observe.h; its remarks hold) with the bodies' boxes staged from their parts
-template <bool IDENTITY, bool IGNORE, class Load, class Put>
-__device__ __forceinline__ uint32_t pq_bo_front(const BatchWorkArgs& A, const BatchPartRows& P, BatchWork& W, float4* s_dyn, BatchBox& z, Load&& load, Put&& put) {
-  const uint32_t tid = threadIdx.x, g0 = W.g0, n = W.n;
-  float4 *s_c = s_dyn, *s_r = s_dyn + n;
-  for (uint32_t i = tid; i < n; i += kBatchBlock) {
-    const Box tb = pq_body_box(A, P, (size_t)g0 + i);
-    s_c[i] = mk4(tb.c, 0.0f); s_r[i] = mk4(tb.r, 0.0f);
+// The bodies' policy of the fronts (k_batch_query.h) that sees parts.  Dynamic LDS of a ray or sweep kernel: rows | rows |
+// kBatchQueryRed words | counts
+struct PartBodies {
+  using Best = PartBest;
+  const BatchWorkArgs& A;
+  const BatchPartRows& P;
+  const float4 *c0 = nullptr, *c1 = nullptr;  // the staged rows ...
+  const uint32_t* np = nullptr;               // ... and counts
+  __device__ __forceinline__ PartBodies(const BatchWorkArgs& a, const BatchPartRows& p) : A(a), P(p) {}
+  __device__ __forceinline__ void stage(uint32_t g0, uint32_t n, float4* s_dyn) {
+    uint32_t* s_np = reinterpret_cast<uint32_t*>(s_dyn + 2 * (size_t)n + kBatchQueryRed);
+    pq_stage(A, P, g0, n, s_dyn, s_dyn + n, s_np);
+    c0 = s_dyn; c1 = s_dyn + n; np = s_np;
   }
-  __syncthreads();
-  W.template split<IDENTITY>(A, min(W.shift(), 6u));  // (a box's lanes in one wave: the ballot)
-  const uint32_t L = W.L, sub = W.sub;
-  const bool live = W.live;
-  z.Q.c = mk3(0.0f, 0.0f, 0.0f); z.Q.r = z.Q.c; z.ign = -1;
-  if (live) z = load(W.qi, g0);
-  const Box Q = z.Q;
-  const int32_t ign = z.ign;
-  const uint32_t shift = (tid & 63u) - sub;                        // the first lane of the box's group within the wave
-  const uint64_t group = L == 64u ? ~0ull : ((1ull << L) - 1ull);  // the group's lanes, from that lane
-  uint32_t m = 0;
-  for (uint32_t i0 = 0; i0 < n; i0 += L) {  // (n and L are the work item's: every lane of the wave makes every trip)
-    const uint32_t i = i0 + sub;
-    bool hit = false;
-    if (live && i < n && (!IGNORE || (int32_t)i != ign)) {
-      Box b; b.c = xyz(s_c[i]); b.r = xyz(s_r[i]);
-      hit = box_overlaps(b, Q);
+  __device__ __forceinline__ PartBest ray_walk(const BatchWork& W, V3 p, V3 d, float dt, int32_t ign) const {
+    PartBest best;
+    const float dd = dot(d, d);
+    for (uint32_t i = W.sub; i < W.n; i += W.L) {
+      if ((int32_t)i == ign) continue;  // (an ignored body: with every part of it)
+      const float4 a = c0[i], b = c1[i];
+      const uint32_t cw = np[i], nk = cw & (kPqSeveral - 1u);
+      const bool several = cw & kPqSeveral;
+      if (several && pq_ray_far_body(a, p, d, dd, dt)) continue;
+      const size_t at = (size_t)kMaxParts * ((size_t)W.g0 + i);
+#pragma unroll 1
+      for (uint32_t k = 0; k < nk; ++k) {
+        const float4 pa = several ? P.wp0[at + k] : a, pb = several ? P.wp1[at + k] : b;
+        if (bq_ray_far(pa, pb, p, d, dd, dt)) continue;
+        V3 ip; float t;
+        if (q_ray_comp(p, d, dt, pa, pb, &ip, &t)) best.offer(ip, t, MGF_HIT_BODY, i, k);
+      }
     }
-    const uint64_t g = ((uint64_t)__ballot(hit) >> shift) & group;
-    put(hit, i, m + (uint32_t)__popcll(g & ((1ull << sub) - 1ull)));
-    m += (uint32_t)__popcll(g);
+    return best;
   }
-  return m;
-}
+  __device__ __forceinline__ SweepBest sweep_walk(const BatchWork& W, const SweepCast& K, int32_t ign) const {
+    SweepBest best;
+    // (a lane's own pointers into the part rows, stepped with i: the rows' bases need no scalar registers through comp_mcomp)
+    const float4 *w0 = P.wp0 + (size_t)kMaxParts * ((size_t)W.g0 + W.sub), *w1 = P.wp1 + (size_t)kMaxParts * ((size_t)W.g0 + W.sub);
+    // ONE loop over (body i, part k) with one place for comp_mcomp - a loop of parts inside the loop of bodies costs the scalar
+    // registers that comp_mcomp has not to spare: a trip tests part k of body i, or skips the body whole (ignored; beyond the reject)
+    uint32_t k = 0u;
+    for (uint32_t i = W.sub; i < W.n;) {
+      const float4 a = c0[i], b = c1[i];
+      const uint32_t cw = np[i], nk = cw & (kPqSeveral - 1u);
+      const bool several = cw & kPqSeveral;
+      bool next = (int32_t)i == ign || (several && k == 0u && pq_sweep_far_body(a, K));  // (an ignored body: with every part of it)
+      if (!next) {
+        const Comp t = several ? to_comp(w0[k], w1[k]) : to_comp(a, b);
+        Contact ct;
+        if (!q_sweep_far(t, K) && comp_mcomp(t, K.s, K.v, &ct)) best.offer(ct, MGF_HIT_BODY, i, k, 0u);
+        next = ++k >= nk;
+      }
+      if (next) { k = 0u; i += W.L; w0 += (size_t)kMaxParts * W.L; w1 += (size_t)kMaxParts * W.L; }
+    }
+    return best;
+  }
+  __device__ __forceinline__ Box box(size_t g) const { return pq_body_box(A, P, g); }
+};
 
-// LDS (dynamic): 32 bytes a body.
+// LDS (dynamic): 36 bytes a body, kBatchQueryRed words (rays, sweeps, the sensors' and the feelers' kernels); 32 bytes a body (the
+// boxes' kernels).
+template <int SRC>
+__global__ __launch_bounds__(kBatchBlock) void k_batch_pq_ray(BatchQueryArgs A, BatchPartRows P, const ParticleIn* parts, BatchItemSrc S) {
+  extern __shared__ float4 s_dyn[];
+  bq_ray_item<SRC>(A, PartBodies(A, P), parts, S, s_dyn);
+}
+__global__ __launch_bounds__(kBatchBlock) void k_batch_pq_sensor(BatchSensorArgs A, BatchPartRows P) {
+  extern __shared__ float4 s_dyn[];
+  bs_rays(A, PartBodies(A, P), s_dyn);
+}
+template <int SRC>
+__global__ __launch_bounds__(kBatchBlock) void k_batch_pq_sweep(BatchQueryArgs A, BatchPartRows P, const MovingIn* casts, BatchItemSrc S) {
+  extern __shared__ float4 s_dyn[];
+  bq_sweep_item<SRC>(A, PartBodies(A, P), casts, S, s_dyn);
+}
+__global__ __launch_bounds__(kBatchBlock) void k_batch_pq_feeler(BatchFeelerArgs A, BatchPartRows P) {
+  extern __shared__ float4 s_dyn[];
+  bf_casts(A, PartBodies(A, P), s_dyn);
+}
 template <bool FILL>
 __global__ __launch_bounds__(kBatchBlock) void k_batch_pq_overlap(BatchOverlapArgs A, BatchPartRows P) {
   extern __shared__ float4 s_dyn[];
-  BatchWork W(A, true);
-  BatchBox z;
-  uint32_t base = 0u;  // FILL: where the box's list begins
-  const uint32_t m = pq_bo_front<false, false>(
-      A, P, W, s_dyn, z,
-      [&](uint32_t qi, uint32_t) {
-        if (FILL) base = A.off[qi];
-        return BatchBox{{ld3(A.boxes + 6 * (size_t)qi), ld3(A.boxes + 6 * (size_t)qi + 3)}, -1};
-      },
-      [&](bool hit, uint32_t i, uint32_t rank) {
-        if (FILL && hit) A.out[base + rank] = i;
-      });
-  if (!FILL && W.live && W.sub == 0u) A.cnt[W.qi] = m;
+  bo_overlap<FILL>(A, PartBodies(A, P), s_dyn);
 }
-
-// the two loaders of a zone's box (k_batch_zone_first's): the caller's, and the one formed from the rig's record and the body's x and q
-__device__ __forceinline__ BatchBox pq_zone_fixed(const BatchZoneArgs& A, uint32_t qi) {
-  return BatchBox{{ld3(A.boxes + 6 * (size_t)qi), ld3(A.boxes + 6 * (size_t)qi + 3)}, A.ignore ? A.ignore[qi] : -1};
-}
-__device__ __forceinline__ BatchBox pq_zone_mounted(const BatchZoneArgs& A, uint32_t qi, uint32_t g0) {
-  const ZoneIn s = A.rig[qi];
-  BatchBox b;
-  b.Q.c = ld3(s.p); b.Q.r = ld3(s.r);
-  if (s.body >= 0) {
-    const size_t g = (size_t)g0 + (uint32_t)s.body;
-    const float4 bx = A.x[g], bq = A.q[g];
-    b.Q.c = xyz(bx) + rotate(mkq(bq.x, mk3(bq.y, bq.z, bq.w)), ld3(s.p));
-  }
-  b.ign = (s.flags & MGF_SENSOR_IGNORE_SELF) ? s.body : -1;
-  return b;
-}
-__device__ __forceinline__ void pq_zone_box_out(float* boxes_out, uint32_t qi, const Box& Q) {
-  float* bo = boxes_out + 6 * (size_t)qi;
-  bo[0] = Q.c.x; bo[1] = Q.c.y; bo[2] = Q.c.z; bo[3] = Q.r.x; bo[4] = Q.r.y; bo[5] = Q.r.z;
-}
-
-// LDS (dynamic): 32 bytes a body.  k_batch_zone_first over pq_bo_front.
 template <int SRC>
 __global__ __launch_bounds__(kBatchBlock) void k_batch_pq_zone(BatchZoneArgs A, BatchPartRows P, BatchItemSrc S) {
   extern __shared__ float4 s_dyn[];
-  BatchWork W(A, true, bq_item<SRC>(A, S));
-  const uint32_t k = A.k;
-  BatchBox z;
-  const auto fixed = [&](uint32_t qi, uint32_t) { return pq_zone_fixed(A, qi); };
-  const auto mounted = [&](uint32_t qi, uint32_t g0) { return pq_zone_mounted(A, qi, g0); };
-  const auto record = [&]() { return A.out + (size_t)(1u + k) * W.qi; };  // (of a live lane, W split)
-  const auto store = [&](bool hit, uint32_t i, uint32_t rank) {
-    if (hit && rank < k) record()[1u + rank] = (int32_t)i;
-  };
-  const uint32_t m = SRC == kItemFixed ? pq_bo_front<true, true>(A, P, W, s_dyn, z, fixed, store) : pq_bo_front<false, true>(A, P, W, s_dyn, z, mounted, store);
-  if (W.live) {
-    const uint32_t sub = W.sub;
-    int32_t* o = record();
-    if (sub == 0u) o[0] = (int32_t)m;
-    for (uint32_t s = min(m, k) + sub; s < k; s += W.L) o[1u + s] = -1;
-    if (sub == 0u && A.boxes_out) pq_zone_box_out(A.boxes_out, W.qi, z.Q);
-  }
+  bz_first<SRC>(A, PartBodies(A, P), S, s_dyn);
 }
-
-// LDS (dynamic): 32 bytes a body.  k_batch_nearest over pq_bo_front: the distances are measured from the centre of the staged box.
 template <int SRC>
 __global__ __launch_bounds__(kBatchBlock) void k_batch_pq_nearest(BatchNearestArgs A, BatchPartRows P, BatchItemSrc S) {
   extern __shared__ float4 s_dyn[];
-  BatchWork W(A, true, bq_item<SRC>(A, S));
-  const uint32_t k = A.k;
-  BatchBox z;
-  const auto fixed = [&](uint32_t qi, uint32_t) { return pq_zone_fixed(A, qi); };
-  const auto mounted = [&](uint32_t qi, uint32_t g0) { return pq_zone_mounted(A, qi, g0); };
-  const auto count_only = [](bool, uint32_t, uint32_t) {};
-  const uint32_t m = SRC == kItemFixed ? pq_bo_front<true, true>(A, P, W, s_dyn, z, fixed, count_only) : pq_bo_front<false, true>(A, P, W, s_dyn, z, mounted, count_only);
-  const uint32_t n = W.n, L = W.L, sub = W.sub;
-  const bool live = W.live, first = live && sub == 0u;
-  const float4 *s_c = s_dyn, *s_r = s_dyn + n;  // (as the front staged them)
-  const Box Q = z.Q;
-  const int32_t ign = z.ign;
-  int32_t* o = A.out + (size_t)(1u + k) * W.qi;  // (of a live lane)
-  float* od = A.dist2_out ? A.dist2_out + (size_t)k * W.qi : nullptr;
-  const auto put = [&](uint32_t slot, uint64_t key) {  // (of the zone's first lane) slot < k: the record's word 1 + slot, its distance
-    const bool none = key == kNearestNone;
-    o[1u + slot] = none ? -1 : (int32_t)(uint32_t)key;
-    if (od) od[slot] = none ? u2f(0x7F800000u) : u2f((uint32_t)(key >> 32));
-  };
-  uint64_t lo = 0ull;  // the least key a pass may choose: one above the last chosen
-  for (uint32_t r0 = 0; r0 < k; r0 += 4u) {
-    NearestPick best;
-    best.clear();
-#pragma unroll 2
-    for (uint32_t i0 = 0; i0 < n; i0 += L) {  // (n and L are the work item's: every lane of the wave makes every trip)
-      const uint32_t i = i0 + sub, at = min(i, n - 1u);
-      const V3 bc = xyz(s_c[at]), br = xyz(s_r[at]);
-      const V3 e = bc - Q.c;
-      const float ax = fabs_rs(e.x), ay = fabs_rs(e.y), az = fabs_rs(e.z);  // box_overlaps(body, Q): its three tests, no early exit
-      const bool hit = (ax <= (br.x + Q.r.x)) & (ay <= (br.y + Q.r.y)) & (az <= (br.z + Q.r.z));
-      const uint64_t key = ((uint64_t)f2u(dot(e, e)) << 32) | i;
-      const bool ok = live & (i < n) & ((int32_t)i != ign) & hit & (key >= lo);
-      best.put(ok ? key : kNearestNone);
-    }
-    for (uint32_t off = L >> 1; off > 0u; off >>= 1) best.merge(best.shfl((int)off));
-    if (first) {
-      put(r0, best.t0);
-      if (r0 + 1u < k) put(r0 + 1u, best.t1);
-      if (r0 + 2u < k) put(r0 + 2u, best.t2);
-      if (r0 + 3u < k) put(r0 + 3u, best.t3);
-    }
-    lo = best.t3 == kNearestNone ? kNearestNone : best.t3 + 1ull;
-  }
-  if (first) {
-    o[0] = (int32_t)m;
-    if (A.boxes_out) pq_zone_box_out(A.boxes_out, W.qi, Q);
-  }
+  bn_nearest<SRC>(A, PartBodies(A, P), S, s_dyn);
 }
 
 }  // namespace mgf

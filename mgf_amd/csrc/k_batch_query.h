@@ -26,8 +26,11 @@
 // item, nor the split into launches changes a bit of an answer.  No workgroup waits for another.
 // The two kernels with a workgroup per work item are bq_ray_item<SRC> / bq_sweep_item<SRC> behind a kernel's signature: SRC says where
 // the work item comes from - the host's table here (kItemTable), the device-built table or arithmetic on blockIdx.x for the
-// device-pointer calls (kItemPlan, kItemFixed: k_batch_query_dev.h).  bq_ray_item is bq_ray_front - the front of a ray cast, written
-// once - over the caller's particles; k_batch_sensor_ray (k_batch_sensor.h) is the same front over particles formed from a rig.  The three lane-per-query passes take the world of query i from
+// device-pointer calls (kItemPlan, kItemFixed: k_batch_query_dev.h).  They are bq_ray_front / bq_sweep_front - the front of a ray cast
+// and of a sweep, each written once - over the caller's particles and casts; k_batch_sensor_ray (k_batch_sensor.h) and
+// k_batch_feeler_bodies (k_batch_feeler.h) are the same fronts over particles and casts formed from a rig, and the kernels of
+// k_batch_part_query.h the same fronts again over bodies that show their parts: what the bodies of a world are to a front is a policy
+// (PlainBodies, PartBodies - below, at PlainBodies).  The three lane-per-query passes take the world of query i from
 // world[i], or (world == null: every world has `per` queries) as i / per, and leave at once for a negative world - a record the
 // device-pointer calls skip - and for a cast whose tag is no component's; the host-memory calls refuse both before anything runs.
 #pragma once
@@ -131,7 +134,7 @@ struct BatchWork {
   }
 };
 
-__device__ __forceinline__ void bq_stage(const BatchQueryArgs& A, uint32_t g0, uint32_t n, float4* s_c0, float4* s_c1) {
+__device__ __forceinline__ void bq_stage(const BatchWorkArgs& A, uint32_t g0, uint32_t n, float4* s_c0, float4* s_c1) {
   for (uint32_t i = threadIdx.x; i < n; i += kBatchBlock) { s_c0[i] = A.col0[(size_t)g0 + i]; s_c1[i] = A.col1[(size_t)g0 + i]; }
   __syncthreads();
 }
@@ -168,20 +171,86 @@ __device__ __forceinline__ bool bq_ray_far(float4 a, float4 b, V3 p, V3 d, float
 
 // A live query's particle in world coordinates and the body of its world it does not see (-1: none): what a loader hands bq_ray_front
 struct BatchRay { V3 p, d; float dt; int32_t ign; };
+// A live cast in world coordinates and the body of its world it does not meet (-1: none): what a loader hands bq_sweep_front.
+// BatchCast: a cast the loader formed.  BatchCastAt: a cast where the caller keeps it - the front reads of it what it needs, when it
+// needs it, as it would of the array itself.
+struct BatchCast {
+  MovingIn m;
+  int32_t ign;
+  __device__ __forceinline__ const MovingIn& cast() const { return m; }
+};
+struct BatchCastAt {
+  const MovingIn* at;
+  int32_t ign;
+  __device__ __forceinline__ const MovingIn& cast() const { return *at; }
+};
+
+// q_sweep_cast without a grid: the reject's pad keeps its millimetre and the rounding of the path
+__device__ __forceinline__ SweepCast bq_sweep_cast(const MovingIn& m) {
+  QueryGrid G;
+  G.margin = 0.0f;
+  return q_sweep_cast(m, G);
+}
+
+// THE BODIES OF A WORK ITEM'S WORLD are a policy of the two fronts below and of bo_front (k_batch_observe.h), each written once:
+//   stage(g0, n, s_dyn)               what a lane's walk reads of bodies [g0, g0 + n), into dynamic LDS: two rows of n float4 words, behind
+//                                     them the kBatchQueryRed words of bq_reduce, behind those whatever else the policy keeps.  Ends with
+//                                     the front's first barrier
+//   ray_walk(W, p, d, dt, ign)        the best of lane W.sub's bodies - W.sub, W.sub + W.L, ... - against a particle (a Best: the policy's)
+//   sweep_walk(W, K, ign)             the same against a cast (a SweepBest)
+//   box(g)                            the tight box of body g of the batch (what bo_front stages)
+// PlainBodies, here: a body is its collider row col0 / col1 and reports part 0; Best is QueryBest.  PartBodies (k_batch_part_query.h):
+// a body of several components is walked part by part behind a body-level reject and its box is the union of its parts'; Best is
+// PartBest, which carries `part` through the reduction.  A walk holds no barrier and leaves no kernel.  (A walk RETURNS its best: one
+// that fills the front's through a reference cost every ray kernel two vector and four scalar registers.)
+struct PlainBodies {
+  using Best = QueryBest;
+  const BatchWorkArgs& A;
+  const float4 *c0 = nullptr, *c1 = nullptr;  // the staged rows
+  __device__ __forceinline__ explicit PlainBodies(const BatchWorkArgs& a) : A(a) {}
+  __device__ __forceinline__ void stage(uint32_t g0, uint32_t n, float4* s_dyn) {
+    bq_stage(A, g0, n, s_dyn, s_dyn + n);
+    c0 = s_dyn; c1 = s_dyn + n;
+  }
+  __device__ __forceinline__ QueryBest ray_walk(const BatchWork& W, V3 p, V3 d, float dt, int32_t ign) const {
+    QueryBest best;
+    const float dd = dot(d, d);
+    for (uint32_t i = W.sub; i < W.n; i += W.L) {
+      if ((int32_t)i == ign) continue;
+      const float4 a = c0[i], b = c1[i];
+      if (bq_ray_far(a, b, p, d, dd, dt)) continue;
+      V3 ip; float t;
+      if (q_ray_comp(p, d, dt, a, b, &ip, &t)) best.offer(ip, t, MGF_HIT_BODY, i, 0u);
+    }
+    return best;
+  }
+  __device__ __forceinline__ SweepBest sweep_walk(const BatchWork& W, const SweepCast& K, int32_t ign) const {
+    SweepBest best;
+    for (uint32_t i = W.sub; i < W.n; i += W.L) {
+      if ((int32_t)i == ign) continue;
+      const Comp t = to_comp(c0[i], c1[i]);
+      if (q_sweep_far(t, K)) continue;
+      Contact c;
+      if (comp_mcomp(t, K.s, K.v, &c)) best.offer(c, MGF_HIT_BODY, i, 0u, 0u);
+    }
+    return best;
+  }
+  __device__ __forceinline__ Box box(size_t g) const { return comp_bounds(to_comp(A.col0[g], A.col1[g])); }
+};
 
 // A workgroup's work item of rays, written once for every kernel that casts rays with a workgroup per work item: k_batch_query_ray,
-// k_batch_query_ray_dev<SRC> (bq_ray_item) and k_batch_sensor_ray (k_batch_sensor.h).  What a kernel brings is where a particle comes
-// from - load(qi, g0) -> BatchRay, run by the live lanes behind the staging - and what else its first lane does behind the stored hit -
-// done(qi, p, d, dt).  Neither holds a barrier nor leaves the kernel.
+// k_batch_query_ray_dev<SRC> (bq_ray_item), k_batch_sensor_ray (k_batch_sensor.h) and their part-aware forms (k_batch_part_query.h).
+// What a kernel brings is the bodies' policy, where a particle comes from - load(qi, g0) -> BatchRay, run by the live lanes behind the
+// staging - and what else its first lane does behind the stored hit - done(qi, p, d, dt).  Neither hook holds a barrier nor leaves the
+// kernel; the policy's only barrier is the one its staging ends with.
 // kItemPlan: a workgroup at or beyond the device's item total has no work item - it leaves, the whole of it, before anything is staged
 // and ahead of the first __syncthreads.  The only other exit is behind bq_reduce.
-template <int SRC, class Load, class Done>
-__device__ __forceinline__ void bq_ray_front(const BatchQueryArgs& A, const BatchItemSrc& S, float4* s_dyn, Load&& load, Done&& done) {
+template <int SRC, class Bodies, class Load, class Done>
+__device__ __forceinline__ void bq_ray_front(const BatchQueryArgs& A, Bodies bodies, const BatchItemSrc& S, float4* s_dyn, Load&& load, Done&& done) {
   if (SRC == kItemPlan && blockIdx.x >= *S.n_items) return;
   BatchWork W(A, A.mask & MGF_QUERY_BODIES, bq_item<SRC>(A, S));
   const uint32_t n = W.n;
-  float4 *s_c0 = s_dyn, *s_c1 = s_dyn + n, *s_red = s_dyn + 2 * (size_t)n;
-  bq_stage(A, W.g0, n, s_c0, s_c1);
+  bodies.stage(W.g0, n, s_dyn);
   W.template split<SRC == kItemFixed>(A, W.shift());
   const uint32_t qi = W.qi;
   V3 p = mk3(0.0f, 0.0f, 0.0f), d = p;
@@ -193,18 +262,9 @@ __device__ __forceinline__ void bq_ray_front(const BatchQueryArgs& A, const Batc
     mask = A.mask;
     if (d.x == 0.0f && d.y == 0.0f && d.z == 0.0f) mask = 0;  // (no direction: no hit, by definition - k_query_ray)
   }
-  QueryBest best;
-  if (mask & MGF_QUERY_BODIES) {
-    const float dd = dot(d, d);
-    for (uint32_t i = W.sub; i < n; i += W.L) {
-      if ((int32_t)i == ign) continue;
-      const float4 a = s_c0[i], b = s_c1[i];
-      if (bq_ray_far(a, b, p, d, dd, dt)) continue;
-      V3 ip; float t;
-      if (q_ray_comp(p, d, dt, a, b, &ip, &t)) best.offer(ip, t, MGF_HIT_BODY, i, 0u);
-    }
-  }
-  bq_reduce(best, W, s_red);
+  typename Bodies::Best best;
+  if (mask & MGF_QUERY_BODIES) best = bodies.ray_walk(W, p, d, dt, ign);
+  bq_reduce(best, W, s_dyn + 2 * (size_t)n);
   if (W.sub != 0u || !W.live) return;
   if (mask & MGF_QUERY_TERRAIN) {
     const BatchTerrain M = batch_terrain_of(A.T, W.it.x);  // (the work item's world: wave-uniform loads)
@@ -214,10 +274,10 @@ __device__ __forceinline__ void bq_ray_front(const BatchQueryArgs& A, const Batc
   done(qi, p, d, dt);
 }
 // the front over the caller's particles: parts[qi] as it stands, A.ignore, nothing behind the hit
-template <int SRC>
-__device__ __forceinline__ void bq_ray_item(const BatchQueryArgs& A, const ParticleIn* parts, const BatchItemSrc& S, float4* s_dyn) {
+template <int SRC, class Bodies>
+__device__ __forceinline__ void bq_ray_item(const BatchQueryArgs& A, Bodies bodies, const ParticleIn* parts, const BatchItemSrc& S, float4* s_dyn) {
   bq_ray_front<SRC>(
-      A, S, s_dyn,
+      A, bodies, S, s_dyn,
       [&](uint32_t qi, uint32_t) {
         const ParticleIn q = parts[qi];
         return BatchRay{ld3(q.p), ld3(q.d), q.dt, A.ignore ? A.ignore[qi] : -1};
@@ -227,52 +287,44 @@ __device__ __forceinline__ void bq_ray_item(const BatchQueryArgs& A, const Parti
 // LDS (dynamic): 32 bytes a body, kBatchQueryRed words.
 __global__ __launch_bounds__(kBatchBlock) void k_batch_query_ray(BatchQueryArgs A, const ParticleIn* parts) {
   extern __shared__ float4 s_dyn[];
-  bq_ray_item<kItemTable>(A, parts, BatchItemSrc(), s_dyn);
+  bq_ray_item<kItemTable>(A, PlainBodies(A), parts, BatchItemSrc(), s_dyn);
 }
 
-// q_sweep_cast without a grid: the reject's pad keeps its millimetre and the rounding of the path
-__device__ __forceinline__ SweepCast bq_sweep_cast(const MovingIn& m) {
-  QueryGrid G;
-  G.margin = 0.0f;
-  return q_sweep_cast(m, G);
-}
-
-// A workgroup's work item of casts (bq_ray_front's remarks).  kItemFixed: no plan has looked at the casts - one whose tag is no
-// component's is matched against nothing, keeps the no-hit record and is counted by the first of its lanes.
-template <int SRC>
-__device__ __forceinline__ void bq_sweep_item(const BatchQueryArgs& A, const MovingIn* casts, const BatchItemSrc& S, float4* s_dyn) {
+// A workgroup's work item of casts, written once as the rays' is (bq_ray_front's remarks): load(qi, g0) -> BatchCast or BatchCastAt,
+// done(qi, m) behind the stored hit.  No loader reads the staged rows: a mask without bodies stages nothing.  kItemFixed: no plan has looked at the
+// casts - one whose tag is no component's is matched against nothing, keeps the no-hit record and is counted by the first of its lanes.
+template <int SRC, class Bodies, class Load, class Done>
+__device__ __forceinline__ void bq_sweep_front(const BatchQueryArgs& A, Bodies bodies, const BatchItemSrc& S, float4* s_dyn, Load&& load, Done&& done) {
   if (SRC == kItemPlan && blockIdx.x >= *S.n_items) return;
   BatchWork W(A, A.mask & MGF_QUERY_BODIES, bq_item<SRC>(A, S));
   const uint32_t n = W.n;
-  float4 *s_c0 = s_dyn, *s_c1 = s_dyn + n, *s_red = s_dyn + 2 * (size_t)n;
-  bq_stage(A, W.g0, n, s_c0, s_c1);
+  bodies.stage(W.g0, n, s_dyn);
   W.template split<SRC == kItemFixed>(A, W.shift());
   const uint32_t qi = W.qi;
   SweepBest best;
+  decltype(load(qi, W.g0)) c;
   bool ok = W.live;
-  if (SRC == kItemFixed && ok && (uint32_t)casts[qi].tag > (uint32_t)KIND_CAPSULE) {
+  if (ok) c = load(qi, W.g0);
+  if (SRC == kItemFixed && ok && (uint32_t)c.cast().tag > (uint32_t)KIND_CAPSULE) {
     ok = false;
     if (W.sub == 0u) atomicAdd(S.skipped, 1ull);
   }
-  if (ok && n) {
-    const SweepCast K = bq_sweep_cast(casts[qi]);
-    const int32_t ign = A.ignore ? A.ignore[qi] : -1;
-    for (uint32_t i = W.sub; i < n; i += W.L) {
-      if ((int32_t)i == ign) continue;
-      const Comp t = to_comp(s_c0[i], s_c1[i]);
-      if (q_sweep_far(t, K)) continue;
-      Contact c;
-      if (comp_mcomp(t, K.s, K.v, &c)) best.offer(c, MGF_HIT_BODY, i, 0u, 0u);
-    }
-  }
-  bq_reduce(best, W, s_red);
+  if (ok && n) best = bodies.sweep_walk(W, bq_sweep_cast(c.cast()), c.ign);  // (n: the mask asks for bodies, and the world has some)
+  bq_reduce(best, W, s_dyn + 2 * (size_t)n);
   if (W.sub != 0u || !W.live) return;
   q_sweep_store(A.out + 13 * (size_t)qi, best);
+  done(qi, c.cast());
+}
+// the front over the caller's casts: casts[qi] as it stands, A.ignore, nothing behind the hit
+template <int SRC, class Bodies>
+__device__ __forceinline__ void bq_sweep_item(const BatchQueryArgs& A, Bodies bodies, const MovingIn* casts, const BatchItemSrc& S, float4* s_dyn) {
+  bq_sweep_front<SRC>(
+      A, bodies, S, s_dyn, [&](uint32_t qi, uint32_t) { return BatchCastAt{casts + qi, A.ignore ? A.ignore[qi] : -1}; }, [](uint32_t, const MovingIn&) {});
 }
 // LDS (dynamic): 32 bytes a body, kBatchQueryRed words.
 __global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_bodies(BatchQueryArgs A, const MovingIn* casts) {
   extern __shared__ float4 s_dyn[];
-  bq_sweep_item<kItemTable>(A, casts, BatchItemSrc(), s_dyn);
+  bq_sweep_item<kItemTable>(A, PlainBodies(A), casts, BatchItemSrc(), s_dyn);
 }
 
 // the world of query i for a lane-per-query pass; negative: the record is skipped

@@ -82,12 +82,12 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_query_plan_fill(BatchPlan
 template <int SRC>
 __global__ __launch_bounds__(kBatchBlock) void k_batch_query_ray_dev(BatchQueryArgs A, const ParticleIn* parts, BatchItemSrc S) {
   extern __shared__ float4 s_dyn[];
-  bq_ray_item<SRC>(A, parts, S, s_dyn);
+  bq_ray_item<SRC>(A, PlainBodies(A), parts, S, s_dyn);
 }
 template <int SRC>
 __global__ __launch_bounds__(kBatchBlock) void k_batch_query_sweep_bodies_dev(BatchQueryArgs A, const MovingIn* casts, BatchItemSrc S) {
   extern __shared__ float4 s_dyn[];
-  bq_sweep_item<SRC>(A, casts, S, s_dyn);
+  bq_sweep_item<SRC>(A, PlainBodies(A), casts, S, s_dyn);
 }
 
 }  // namespace mgf

@@ -30,11 +30,12 @@ struct BatchSensorArgs : BatchQueryArgs {
   float* parts;         // by the caller's index: 7 words a sensor (mgf_particle); null: not stored
 };
 
-// LDS (dynamic): 32 bytes a body, kBatchQueryRed words - as k_batch_query_ray.
-__global__ __launch_bounds__(kBatchBlock) void k_batch_sensor_ray(BatchSensorArgs A) {
-  extern __shared__ float4 s_dyn[];
+// A work item of the rig's table through bq_ray_front, over either policy of the bodies: the loader that forms a sensor's particle,
+// and the particle stored behind the hit where there is somewhere to store it
+template <class Bodies>
+__device__ __forceinline__ void bs_rays(const BatchSensorArgs& A, Bodies bodies, float4* s_dyn) {
   bq_ray_front<kItemTable>(
-      A, BatchItemSrc(), s_dyn,
+      A, bodies, BatchItemSrc(), s_dyn,
       [&](uint32_t qi, uint32_t g0) {
         const SensorIn s = A.rig[qi];
         const size_t g = (size_t)g0 + (uint32_t)s.body;
@@ -48,6 +49,12 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_sensor_ray(BatchSensorArg
           o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = d.x; o[4] = d.y; o[5] = d.z; o[6] = dt;
         }
       });
+}
+
+// LDS (dynamic): 32 bytes a body, kBatchQueryRed words - as k_batch_query_ray.
+__global__ __launch_bounds__(kBatchBlock) void k_batch_sensor_ray(BatchSensorArgs A) {
+  extern __shared__ float4 s_dyn[];
+  bs_rays(A, PlainBodies(A), s_dyn);
 }
 
 }  // namespace mgf

@@ -38,44 +38,56 @@ struct BatchZoneArgs : BatchWorkArgs {
   float* boxes_out;       // by the caller's index: c.xyz, r.xyz as formed; null: not stored
 };
 
-// LDS (dynamic): 32 bytes a body.
-template <int SRC>
-__global__ __launch_bounds__(kBatchBlock) void k_batch_zone_first(BatchZoneArgs A, BatchItemSrc S) {
-  extern __shared__ float4 s_dyn[];
+// The two loaders of a zone's box - the caller's (kItemFixed), and the one formed from the rig's record and the body's x and q
+// (kItemTable) - and the box as stored where asked for: written once, for this kernel and for every kernel built on a zone's box in
+// the headers that include this one
+__device__ __forceinline__ BatchBox bz_fixed(const BatchZoneArgs& A, uint32_t qi) {
+  return BatchBox{{ld3(A.boxes + 6 * (size_t)qi), ld3(A.boxes + 6 * (size_t)qi + 3)}, A.ignore ? A.ignore[qi] : -1};
+}
+__device__ __forceinline__ BatchBox bz_mounted(const BatchZoneArgs& A, uint32_t qi, uint32_t g0) {
+  const ZoneIn s = A.rig[qi];
+  BatchBox b;
+  b.Q.c = ld3(s.p); b.Q.r = ld3(s.r);
+  if (s.body >= 0) {
+    const size_t g = (size_t)g0 + (uint32_t)s.body;
+    const float4 bx = A.x[g], bq = A.q[g];
+    b.Q.c = xyz(bx) + rotate(mkq(bq.x, mk3(bq.y, bq.z, bq.w)), ld3(s.p));
+  }
+  b.ign = (s.flags & MGF_SENSOR_IGNORE_SELF) ? s.body : -1;
+  return b;
+}
+__device__ __forceinline__ void bz_box_out(float* boxes_out, uint32_t qi, const Box& Q) {
+  float* bo = boxes_out + 6 * (size_t)qi;
+  bo[0] = Q.c.x; bo[1] = Q.c.y; bo[2] = Q.c.z; bo[3] = Q.r.x; bo[4] = Q.r.y; bo[5] = Q.r.z;
+}
+
+// k_batch_zone_first<SRC> and its part-aware form (k_batch_part_query.h), written once over the bodies' policy
+template <int SRC, class Bodies>
+__device__ __forceinline__ void bz_first(const BatchZoneArgs& A, const Bodies& bodies, const BatchItemSrc& S, float4* s_dyn) {
   BatchWork W(A, true, bq_item<SRC>(A, S));
   const uint32_t k = A.k;
   BatchBox z;
-  const auto fixed = [&](uint32_t qi, uint32_t) {
-    return BatchBox{{ld3(A.boxes + 6 * (size_t)qi), ld3(A.boxes + 6 * (size_t)qi + 3)}, A.ignore ? A.ignore[qi] : -1};
-  };
-  const auto mounted = [&](uint32_t qi, uint32_t g0) {
-    const ZoneIn s = A.rig[qi];
-    BatchBox b;
-    b.Q.c = ld3(s.p); b.Q.r = ld3(s.r);
-    if (s.body >= 0) {
-      const size_t g = (size_t)g0 + (uint32_t)s.body;
-      const float4 bx = A.x[g], bq = A.q[g];
-      b.Q.c = xyz(bx) + rotate(mkq(bq.x, mk3(bq.y, bq.z, bq.w)), ld3(s.p));
-    }
-    b.ign = (s.flags & MGF_SENSOR_IGNORE_SELF) ? s.body : -1;
-    return b;
-  };
+  const auto fixed = [&](uint32_t qi, uint32_t) { return bz_fixed(A, qi); };
+  const auto mounted = [&](uint32_t qi, uint32_t g0) { return bz_mounted(A, qi, g0); };
   const auto record = [&]() { return A.out + (size_t)(1u + k) * W.qi; };  // (of a live lane, W split)
   const auto store = [&](bool hit, uint32_t i, uint32_t rank) {
     if (hit && rank < k) record()[1u + rank] = (int32_t)i;
   };
-  const uint32_t m = SRC == kItemFixed ? bo_front<true, true>(A, W, s_dyn, z, fixed, store) : bo_front<false, true>(A, W, s_dyn, z, mounted, store);
+  const uint32_t m = SRC == kItemFixed ? bo_front<true, true>(A, bodies, W, s_dyn, z, fixed, store) : bo_front<false, true>(A, bodies, W, s_dyn, z, mounted, store);
   if (W.live) {
     const uint32_t sub = W.sub;
     int32_t* o = record();
     if (sub == 0u) o[0] = (int32_t)m;
     for (uint32_t s = min(m, k) + sub; s < k; s += W.L) o[1u + s] = -1;
-    if (sub == 0u && A.boxes_out) {
-      const Box Q = z.Q;
-      float* bo = A.boxes_out + 6 * (size_t)W.qi;
-      bo[0] = Q.c.x; bo[1] = Q.c.y; bo[2] = Q.c.z; bo[3] = Q.r.x; bo[4] = Q.r.y; bo[5] = Q.r.z;
-    }
+    if (sub == 0u && A.boxes_out) bz_box_out(A.boxes_out, W.qi, z.Q);
   }
+}
+
+// LDS (dynamic): 32 bytes a body.
+template <int SRC>
+__global__ __launch_bounds__(kBatchBlock) void k_batch_zone_first(BatchZoneArgs A, BatchItemSrc S) {
+  extern __shared__ float4 s_dyn[];
+  bz_first<SRC>(A, PlainBodies(A), S, s_dyn);
 }
 
 }  // namespace mgf

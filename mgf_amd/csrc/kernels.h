@@ -97,7 +97,8 @@
 //                      (mgf_batch_read_body_contacts: a workgroup per world, the per-body ranges rebuilt in LDS, a lane per body walks its
 //                      chain) and the bodies in a box (mgf_batch_overlap_aabb_many: the world's tight boxes in LDS, ballot-rank compaction).
 //                      bo_front is that walk written once - the staging, the one barrier, the lane split, the ballot loop and a hit's
-//                      rank - with a loader for the box and a hook for what a hit stores: the overlap kernels' and k_batch_zone_first's
+//                      rank - with the bodies' policy for a body's box, a loader for the box and a hook for what a hit stores: the
+//                      overlap kernels', k_batch_zone_first's and k_batch_nearest's
 //   k_batch_drive_get / _set<MODE> / _copy (k_batch_drive.h)
 //                      acting on a batch between ticks: ConstrainedSet::get / set, the force and torque rows and impulses for any mix
 //                      of (world, body) records (mgf_batch_get_many / _set_many / _set_forces / _apply_impulses: a lane per body the call
@@ -144,7 +145,7 @@
 //                      feelers fixed in the frame of a body (mgf_batch_set_feelers / _cast_feelers / _cast_feelers_dev): a sphere or
 //                      capsule with a displacement - or the body's own resident collider - formed from the bodies' x and q, P = x +
 //                      rotate(q, p), D = rotate(q, d), delta turned by q or kept in world coordinates, and swept against the world's
-//                      staged colliders with k_batch_query_sweep_bodies' walk and reduction (bf_sweep_front); the cast is always
+//                      staged colliders through bq_sweep_front (k_batch_query.h), k_batch_query_sweep_bodies' front; the cast is always
 //                      stored, and k_batch_query_sweep_faces / _sweep_obstacles take it up again from there
 //   k_batch_actuate<MODE, OUT> (k_batch_actuator.h)
 //                      actuators fixed in the frame of a body (mgf_batch_set_actuators / _actuate / _actuate_dev): a lane per run of one
@@ -170,7 +171,9 @@
 //                      length; a full report of 64 bytes or a short one of 16
 //   k_batch_pq_ray<SRC> / _sweep<SRC> / _sensor / _feeler / _overlap<FILL> / _zone<SRC> / _nearest<SRC> (k_batch_part_query.h)
 //                      the body passes of the rays, sweeps, sensors, feelers, box overlaps and zones of a batch that holds bodies of
-//                      several components, under option "part_queries": the fronts of the kernels above restated with every part of
+//                      several components, under option "part_queries": the fronts and bodies of the kernels above - each written
+//                      once, over a policy of what the bodies of a world are (PlainBodies, k_batch_query.h) - with the policy that
+//                      sees parts (PartBodies): every part of
 //                      every body through the single-shape test (`part` of a hit), a reject sphere per body of several parts staged
 //                      beside the colliders, the parts read from wp0 / wp1 for the bodies that survive it, `part` carried through
 //                      the reduction (PartBest); a body's box the union of its parts' bounds.  The passes behind them are unchanged

@@ -149,6 +149,49 @@ def test_hits_and_casts_equal_the_definition_byte_for_byte(ctx):
     _assert_casts(b, ALL, want, want_casts, "by arrays")
 
 
+def test_own_shapes_under_a_mask_without_bodies_against_the_lone_worlds(ctx):
+    """Two worlds of three bodies, one of them a capsule; every body carries a feeler of its own shape and an ordinary one.  The casts
+    and the hits under a mask of terrain only - nothing of the bodies is staged then, and an own shape is still the body's collider
+    row - and under bodies and terrain equal mgf_world_sweep_many of the lone worlds byte for byte, at tick 0, when the lone worlds'
+    state is the batch's by construction."""
+    import mgf_amd
+    from mgf_amd import scenes
+    f32 = np.float32
+    scs = [FC._capsuled(scenes.sphere_pile(3, 1, 1, seed=311 + k), k) for k in range(2)]
+    b = _make(ctx, scs)
+    lone = [mgf_amd.World.from_scene(ctx, sc) for sc in scs]
+    assert _lengths(b) == [3, 3] and [len(w) for w in lone] == [3, 3]
+    assert [int(np.sum(b.colliders(k)["tag"] == 1)) for k in range(2)] == [1, 1]
+    n = 12
+    world, body = np.repeat(np.int32([0, 1]), 6), np.tile(np.repeat(np.int32([0, 1, 2]), 2), 2)
+    own = np.arange(n) % 2 == 0                                          # feeler 2j: body j's own shape; 2j + 1: a thin sphere from above it
+    p = np.tile(f32([0.0, 0.9, 0.0]), (n, 1))
+    delta = np.where(own[:, None], f32([0.8, 0.4, 0.0]), f32([0.0, -3.0, 0.0])).astype(f32)
+    b.set_feelers(world, body, np.zeros(n, np.int32), p, np.zeros((n, 3), f32), np.full(n, 0.1, f32), delta, ignore_self=own, world_delta=True, own_shape=own)
+    ign = np.where(own, body, -1).astype(np.int32)
+    seen = {}
+    for kinds in (TERRAIN, BODIES | TERRAIN):
+        hits, casts = b.cast_feelers(kinds, casts=True)
+        for k in range(2):
+            sel = world == k
+            want = lone[k].sweep(casts[sel], ignore=ign[sel], kinds=kinds)
+            assert hits[sel].tobytes() == want.tobytes(), (kinds, k, _where(hits[sel], want))
+        got, cs = _cast_dev(b, kinds)
+        assert got.tobytes() == hits.tobytes() and cs.tobytes() == casts.tobytes(), kinds
+        seen[kinds] = (hits, casts)
+    assert seen[TERRAIN][1].tobytes() == seen[BODIES | TERRAIN][1].tobytes()       # the casts do not depend on the mask
+    casts = seen[TERRAIN][1]
+    col = b.colliders()[3 * world + body]
+    for key in ("tag", "p", "d", "r"):                                   # an own shape: the collider row as it stands, capsule and spheres
+        assert casts[key][own].tobytes() == col[key][own].tobytes(), key
+    assert sorted(casts["tag"][own].tolist()) == [0, 0, 0, 0, 1, 1] and np.all(casts["r"][own] >= f32(0.4))
+    # the conditions of the case, from the lone worlds' answers: the thin spheres above the sphere bodies (whose q is the identity)
+    # meet the floor, or - where bodies are asked for - a body
+    thin = ~own & (col["tag"] == 0)
+    assert int(np.sum(thin)) == 4 and set(seen[TERRAIN][0]["kind"].tolist()) <= {-1, 1} and np.all(seen[TERRAIN][0]["kind"][thin] == 1)
+    assert np.all(seen[BODIES | TERRAIN][0]["kind"][thin] == 0)
+
+
 # ---- 2 ------------------------------------------------------------------------------------------------------------------------------------
 def test_items_of_one_of_256_of_257_and_of_600_feelers(ctx):
     """one feeler on 256 lanes (the reduction across waves), a full item, an item of one behind a full one, three items"""

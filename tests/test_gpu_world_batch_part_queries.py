@@ -436,6 +436,37 @@ def test_feelers_answer_sweep_of_their_casts(six):
         b.set_feelers(np.zeros(0, _capi.FEELER_DTYPE))
 
 
+def test_feelers_of_own_shape_with_and_without_bodies_in_the_mask(six):
+    """One world, a dumbbell and two plain spheres of it; each carries a feeler of its own shape and an ordinary one.  Under a mask of
+    terrain only - no body is staged then - and under bodies and terrain, the hits are the lone world's sweep of the casts byte for
+    byte, and an own shape is the collider row whatever the mask."""
+    c = six[30]
+    b, lone, k = c["b"], c["lone"][PC.DUMBBELLS], PC.DUMBBELLS
+    bodies = np.array(sorted(QC.compound_parts(c["scs"][k]))[:1] + [0, 1], np.int32)
+    n = 6
+    body = np.repeat(bodies, 2)
+    own = np.arange(n) % 2 == 0
+    p = np.tile(f32([0.0, 1.6, 0.0]), (n, 1))
+    delta = np.where(own[:, None], f32([0.6, -0.8, 0.3]), f32([0.0, -4.0, 0.0])).astype(f32)
+    b.set_feelers(np.full(n, k, np.int32), body, np.zeros(n, np.int32), p, np.zeros((n, 3), f32), np.full(n, 0.1, f32), delta, ignore_self=own, world_delta=True,
+                  own_shape=own)
+    try:
+        ign = np.where(own, body, -1).astype(np.int32)
+        seen = {}
+        for kinds in (2, 1 | 2):                                          # terrain; bodies and terrain
+            hits, casts = b.cast_feelers(kinds, casts=True)
+            assert same_bytes(hits, lone.sweep(casts, ignore=ign, kinds=kinds)), kinds
+            seen[kinds] = (hits, casts)
+        assert seen[2][1].tobytes() == seen[3][1].tobytes()               # the casts do not depend on the mask
+        rows = b.colliders(k)[body[own]]
+        for key in ("tag", "p", "d", "r"):
+            assert seen[2][1][key][own].tobytes() == rows[key].tobytes(), key
+        assert seen[2][1]["r"][0] == 0.0 and np.all(seen[2][1]["r"][own][1:] > 0)      # the dumbbell's row: a radius-0 sphere; the plain bodies' own
+        assert set(seen[2][0]["kind"].tolist()) <= {-1, 1}
+    finally:
+        b.set_feelers(np.zeros(0, _capi.FEELER_DTYPE))
+
+
 # ---- 9: boxes ---------------------------------------------------------------------------------------------------------------------------
 def _end_boxes(sc):
     """boxes that meet only the outer half of a dumbbell's end sphere - not its centre of mass, not its collider row"""

@@ -210,14 +210,24 @@ def test_both_pointers_are_looked_up_before_the_first_enqueue_and_the_rig_file_r
         text = host[host.index(add):]
         assert "batch_rigs_stale(b);" in text[:text.index("\n}\n")], add
     # the kernel: every exit and every barrier is the front's; the loader and the store hold neither; its name is off the query prefix
-    k = read("mgf_amd", "csrc", "k_batch_feeler.h")
-    front = k[k.index("void bf_sweep_front("):]
+    # (the front is the one k_batch_query_sweep_bodies has - bq_sweep_front, k_batch_query.h - whose other exit is the device plan's,
+    # a whole workgroup ahead of the staging, and whose only atomic is the fixed layout's count of skipped casts; the walk over the
+    # bodies is the bodies' policy's)
+    k, q = read("mgf_amd", "csrc", "k_batch_feeler.h"), read("mgf_amd", "csrc", "k_batch_query.h")
+    front = q[q.index("void bq_sweep_front("):]
     front = front[:front.index("\n}\n")]
-    assert front.count("return;") == 1 and "atomic" not in front and "__syncthreads" not in front    # (the barriers are bq_stage's and bq_reduce's)
-    assert (front.index("bq_stage(") < front.index("load(") < front.index("q_sweep_far(") < front.index("comp_mcomp(") < front.index("best.offer(")
+    assert front.count("return;") == 2 and front.index("return;") < front.index("bodies.stage(") and "__syncthreads" not in front    # (the barriers are bq_stage's and bq_reduce's)
+    assert "if (SRC == kItemPlan && blockIdx.x >= *S.n_items) return;" in front and re.findall(r"atomic\w*\([^;]*", front) == ["atomicAdd(S.skipped, 1ull)"]
+    assert (front.index("bodies.stage(") < front.index("load(qi, W.g0);") < front.index("bodies.sweep_walk(")
             < front.index("bq_reduce(") < front.index("if (W.sub != 0u || !W.live) return;") < front.index("q_sweep_store(") < front.index("done("))
-    body = k[k.index("void k_batch_feeler_bodies("):]
-    assert "bf_sweep_front(" in body and not re.search(r"return;|__syncthreads|atomic|bq_stage|bq_reduce", body)
+    plain = q[q.index("struct PlainBodies {"):q.index("void bq_ray_front(")]
+    assert "bq_stage(A, g0, n, s_dyn, s_dyn + n);" in plain
+    walk = plain[plain.index("SweepBest sweep_walk("):plain.index("Box box(")]
+    assert walk.index("q_sweep_far(") < walk.index("comp_mcomp(") < walk.index("best.offer(") and not re.search(r"return;|__syncthreads|atomic", walk)
+    body = k[k.index("void bf_casts("):]
+    assert "bq_sweep_front<kItemTable>(" in body and not re.search(r"return;|__syncthreads|atomic|bq_stage|bq_reduce", body)
+    assert body.count("bf_casts(A, PlainBodies(A), s_dyn);") == 1 and body.index("bq_sweep_front<kItemTable>(") < body.index("void k_batch_feeler_bodies(")
+    assert "const float4 a = A.col0[g], b = A.col1[g];" in body              # a body's own shape: the collider rows themselves, whatever was staged
     assert len(re.findall(r"__global__ __launch_bounds__\(kBatchBlock\)", k)) == len(re.findall(r"__global__", k)) == 1
     assert not re.search(r"void k_batch_query_\w+\(", k)
 

@@ -163,17 +163,24 @@ def test_both_device_forms_look_every_pointer_up_before_the_first_enqueue():
     assert host.index("return MGF_OK;\n  }\n  std::vector<int32_t> h(") > host.index("hipStreamSynchronize(")      # each path: one of each
     # the kernel: no exit, no atomic, no barrier of its own; every loop's bounds are the work item's or the call's
     k = read("mgf_amd", "csrc", "k_batch_nearest.h")
-    body = k[k.index("struct NearestPick {"):]          # the selection's registers and the kernel
+    # (the kernel's body is bn_nearest, written once for this kernel and its part-aware form; the kernel is the one call of it with the
+    # plain bodies; the two box loaders and the box store are k_batch_zone.h's)
+    body = k[k.index("struct NearestPick {"):]          # the selection's registers, the shared body and the kernel
     assert not re.search(r"return;|break;|continue;|__syncthreads|atomic|__shared__ (?!float4 s_dyn)", body.replace("extern __shared__ float4 s_dyn[];", ""))
-    assert not re.search(r"return (?!b;|o;|BatchBox\{)", body)
-    assert (body.index("__shfl_xor(") < body.index("void k_batch_nearest(") < body.index("bo_front<true, true>(") < body.index("for (uint32_t r0 = 0; r0 < k; r0 += 4u)")
+    assert not re.search(r"return (?!b;|o;|BatchBox\{|bz_fixed\(A, qi\);|bz_mounted\(A, qi, g0\);)", body)
+    zone = read("mgf_amd", "csrc", "k_batch_zone.h")
+    loaders = zone[zone.index("BatchBox bz_fixed("):zone.index("void bz_first(")]
+    assert not re.search(r"return;|break;|continue;|__syncthreads|atomic|__shared__", loaders) and not re.search(r"return (?!b;|BatchBox\{)", loaders)
+    assert body.count("bn_nearest<SRC>(A, PlainBodies(A), S, s_dyn);") == 1 and body.index("void bn_nearest(") < body.index("void k_batch_nearest(")
+    assert (body.index("__shfl_xor(") < body.index("void bn_nearest(") < body.index("bo_front<true, true>(") < body.index("for (uint32_t r0 = 0; r0 < k; r0 += 4u)")
             < body.index("for (uint32_t i0 = 0; i0 < n; i0 += L)") < body.index("min(i, n - 1u)") < body.index("live & (i < n) & ((int32_t)i != ign) & hit & (key >= lo)")
             < body.index("best.put(ok ? key : kNearestNone)") < body.index("for (uint32_t off = L >> 1; off > 0u; off >>= 1) best.merge(best.shfl((int)off));")
             < body.index("put(r0, best.t0);") < body.index("if (r0 + 3u < k) put(r0 + 3u, best.t3);") < body.index("o[0] = (int32_t)m"))
-    kernel = body[body.index("void k_batch_nearest("):]
-    assert not re.search(r"\bif \((?!first|s\.body >= 0|r0 \+ \du < k|od|A\.boxes_out)", kernel)      # a trip of the selection has no branch of its own
+    kernel = body[body.index("void bn_nearest("):]
+    assert not re.search(r"\bif \((?!first|r0 \+ \du < k|od|A\.boxes_out)", kernel)                    # a trip of the selection has no branch of its own
+    assert not re.search(r"\bif \((?!s\.body >= 0)", loaders)
     assert "dot(e, e)" in body and not re.search(r"\bfmaf?\(|__fm", body)
-    assert "[" not in re.sub(r"//[^\n]*", "", body[:body.index("// LDS (dynamic)")])                  # the four registers by name, never by index
+    assert "[" not in re.sub(r"//[^\n]*", "", body[:body.index("// k_batch_nearest<SRC> and its part-aware form")])                  # the four registers by name, never by index
     assert len(re.findall(r"__global__ __launch_bounds__\(kBatchBlock\)", k)) == len(re.findall(r"__global__", k)) == 1
 
 

@@ -66,14 +66,35 @@ def test_the_kernels_source():
     # `part` travels: the candidate of the ray front carries it through shfl, pack, unpack and merge
     best = k[k.index("struct PartBest : QueryBest"):k.index("// col0 / col1 of an ordinary body")]
     assert "o.part = (uint32_t)__shfl_xor((int)part, off)" in best and "u2f(part)" in best and "o.part = f2u(r0.w)" in best and "o.index, o.part)" in best
-    ray = k[k.index("void pq_ray_front("):k.index("void k_batch_pq_ray(")]
-    assert "PartBest best;" in ray and "best.offer(ip, t, MGF_HIT_BODY, i, k)" in ray
-    # the fronts' barrier discipline: one exit ahead of the staging (a whole workgroup), one behind the reduction
-    for a, b in (("void pq_ray_front(", "void k_batch_pq_ray("), ("void pq_sweep_front(", "void k_batch_pq_sweep(")):
-        body = k[k.index(a):k.index(b)]
-        assert body.count("return;") == 2 and body.index("return;") < body.index("pq_stage(") < body.index("bq_reduce(") < body.rindex("return;")
-    box = k[k.index("uint32_t pq_bo_front("):k.index("void k_batch_pq_overlap(")]
-    assert "return;" not in box and box.count("__syncthreads()") == 1 and "__ballot(hit)" in box
+    # the part walks are the policy's (PartBodies), and the ray front's candidate is the policy's type
+    policy = k[k.index("struct PartBodies {"):k.index("void k_batch_pq_ray(")]
+    ray = policy[policy.index("PartBest ray_walk("):policy.index("SweepBest sweep_walk(")]
+    assert "using Best = PartBest;" in policy and "PartBest best;" in ray and "best.offer(ip, t, MGF_HIT_BODY, i, k)" in ray
+    sweep = policy[policy.index("SweepBest sweep_walk("):policy.index("Box box(")]
+    assert sweep.count("comp_mcomp(") == 1 and "best.offer(ct, MGF_HIT_BODY, i, k, 0u)" in sweep and "scalar" in sweep and "ONE loop over (body i, part k)" in sweep
+    assert "pq_stage(A, P, g0, n, " in policy and not re.search(r"return;|__syncthreads|atomic", policy)
+    # the fronts' barrier discipline: one exit ahead of the staging (a whole workgroup), one behind the reduction - on the fronts the
+    # existing kernels share with these (k_batch_query.h): one text serves both
+    q = read("mgf_amd", "csrc", "k_batch_query.h")
+    for a in ("void bq_ray_front(", "void bq_sweep_front("):
+        body = q[q.index(a):]
+        body = body[:body.index("\n}\n")]
+        assert body.count("return;") == 2 and body.index("return;") < body.index("bodies.stage(") < body.index("bq_reduce(") < body.rindex("return;")
+        assert "__syncthreads" not in body                                 # (the barriers are the staging's and bq_reduce's)
+    assert "typename Bodies::Best best;" in q[q.index("void bq_ray_front("):q.index("void bq_ray_item(")]
+    stage = k[k.index("void pq_stage("):k.index("// the body-level rejects")]
+    assert stage.count("__syncthreads()") == 1 and stage.rstrip().endswith("__syncthreads();\n}") and "return" not in stage
+    # the box front is k_batch_observe.h's own: nothing of it stands here, only a body's box
+    for text in ("bo_front", "__ballot(", "min(W.shift(), 6u)", "box_overlaps("):
+        assert text not in k[k.index("#pragma once"):], text
+    o = read("mgf_amd", "csrc", "k_batch_observe.h")
+    box = o[o.index("uint32_t bo_front("):o.index("void bo_overlap(")]
+    assert "return;" not in box and box.count("__syncthreads()") == 1 and "__ballot(hit)" in box and "bodies.box((size_t)g0 + i)" in box
+    assert "Box box(size_t g) const { return pq_body_box(A, P, g); }" in policy
+    # every kernel is one call of the body it shares with the existing kernel
+    for call in ("bq_ray_item<SRC>(A, PartBodies(A, P), ", "bs_rays(A, PartBodies(A, P), ", "bq_sweep_item<SRC>(A, PartBodies(A, P), ", "bf_casts(A, PartBodies(A, P), ",
+                 "bo_overlap<FILL>(A, PartBodies(A, P), ", "bz_first<SRC>(A, PartBodies(A, P), ", "bn_nearest<SRC>(A, PartBodies(A, P), "):
+        assert k.count(call) == 1, call
     # the existing kernels' sources are not the place of a new kernel
     for f in ("k_batch_query.h", "k_batch_query_dev.h", "k_batch_sensor.h", "k_batch_feeler.h", "k_batch_zone.h", "k_batch_nearest.h", "k_batch_observe.h"):
         assert "pq_" not in read("mgf_amd", "csrc", f), f

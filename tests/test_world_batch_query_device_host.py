@@ -136,11 +136,13 @@ def test_every_device_pointer_is_looked_up_before_the_first_enqueue():
         body = body[:body.index("\n}\n")]
         assert body.index("if (w < 0) return;") < min(body.index("tdesc[") if "tdesc[" in body else 1 << 30, body.index("batch_terrain_of(") if "batch_terrain_of(" in body else 1 << 30), kernel
         assert "world[i]" not in body, kernel
-    for item in ("bq_ray_front", "bq_sweep_item"):   # (bq_ray_item<SRC> is bq_ray_front<SRC> over the caller's particles)
+    for item in ("bq_ray_front", "bq_sweep_front"):   # (bq_ray_item<SRC> / bq_sweep_item<SRC> are these over the caller's particles / casts)
         body = q[q.index("void " + item + "("):]
-        assert body.index("blockIdx.x >= *S.n_items) return;") < body.index("bq_stage(") < body.index("\n}\n"), item
+        assert body.index("blockIdx.x >= *S.n_items) return;") < body.index("bodies.stage(") < body.index("\n}\n"), item
     wrapper = q[q.index("void bq_ray_item("):q.index("void k_batch_query_ray(")]
     assert "bq_ray_front<SRC>(" in wrapper and not re.search(r"return;|__syncthreads|atomic", wrapper)
+    wrapper = q[q.index("void bq_sweep_item("):q.index("void k_batch_query_sweep_bodies(")]
+    assert "bq_sweep_front<SRC>(" in wrapper and not re.search(r"return;|__syncthreads|atomic", wrapper)
 
 
 # ---- 4 ------------------------------------------------------------------------------------------------------------------------------------

@@ -104,16 +104,82 @@ def test_the_shared_steps_are_written_once_and_refuse_without_changing_anything(
 
 def test_the_overlap_front_is_written_once():
     o, z = read("mgf_amd", "csrc", "k_batch_observe.h"), read("mgf_amd", "csrc", "k_batch_zone.h")
-    assert o.count("uint32_t bo_front(") == 1 and "bo_front(" not in z.replace("bo_front<", "")
+    near, part, q = read("mgf_amd", "csrc", "k_batch_nearest.h"), read("mgf_amd", "csrc", "k_batch_part_query.h"), read("mgf_amd", "csrc", "k_batch_query.h")
+    assert o.count("uint32_t bo_front(") == 1
+    for other in (z, near, part):
+        assert "bo_front(" not in other.replace("bo_front<", "")
     assert '#include "k_batch_observe.h"' in z
     half = o[o.index("struct BatchOverlapArgs"):]                        # (the overlap half of the file: behind k_batch_observe_contacts)
-    for text in ("comp_bounds(to_comp(", "__ballot(", "__syncthreads()", "min(W.shift(), 6u)"):
-        assert half.count(text) == 1 and text not in z[z.index("#pragma once"):], text
+    for text in ("__ballot(", "__syncthreads()", "min(W.shift(), 6u)"):
+        assert half.count(text) == 1, text
+        for other in (z, near) if text == "__syncthreads()" else (z, near, part):
+            assert text not in other[other.index("#pragma once"):], text
+    # (the part rows' one barrier is the end of their ray and sweep staging; no box kernel runs it)
+    code = part[part.index("#pragma once"):]
+    assert code.count("__syncthreads()") == 1 and code.index("void pq_stage(") < code.index("__syncthreads()") < code.index("// the body-level rejects")
+    # across the batch's headers: the box front's split once; its ballot the only one of a box query (the cameras' tile compaction
+    # and the parts' tick have their own, which are no box front)
+    assert sum(read("mgf_amd", "csrc", f).count("min(W.shift(), 6u)") for f in _batch_headers()) == 1
+    assert {f for f in _batch_headers() if "__ballot(" in read("mgf_amd", "csrc", f)} == {"k_batch_observe.h", "k_batch_camera.h", "k_batch_parts.h"}
+    # a body's box comes from the bodies' policy; the plain one is the collider row's tight bounds, written once
+    assert half.count("bodies.box((size_t)g0 + i)") == 1 and "comp_bounds(" not in half
+    plain = q[q.index("struct PlainBodies {"):q.index("void bq_ray_front(")]
+    assert plain.count("comp_bounds(to_comp(A.col0[g], A.col1[g]))") == 1
+    assert sum(read("mgf_amd", "csrc", f).count("comp_bounds(to_comp(A.col0[") for f in _batch_headers()) == 1
+    for other in (z, near):
+        assert "comp_bounds(to_comp(" not in other[other.index("#pragma once"):]
     # the overlap kernels have no ignored body, the zones have; the fixed layout has no order array
     assert o.count("bo_front<false, false>(") == 1 and "(!IGNORE || (int32_t)i != ign)" in o
-    assert "SRC == kItemFixed ? bo_front<true, true>(A, W, s_dyn, z, fixed, store) : bo_front<false, true>(A, W, s_dyn, z, mounted, store)" in z
+    assert ("SRC == kItemFixed ? bo_front<true, true>(A, bodies, W, s_dyn, z, fixed, store) : bo_front<false, true>(A, bodies, W, s_dyn, z, mounted, store)"
+            in z)
     kernels = read("mgf_amd", "csrc", "kernels.h")
     assert "bo_front" in kernels[kernels.index("k_batch_observe_contacts / _overlap<FILL>"):kernels.index("k_batch_zone_first<SRC>")]
+
+
+def _batch_headers():
+    return sorted(f for f in os.listdir(os.path.join(ROOT, "mgf_amd", "csrc")) if f.startswith("k_batch_") and f.endswith(".h"))
+
+
+def test_every_query_front_is_written_once():
+    """The guard that the fronts of the batch's query kernels stay written once: the defining line of each occurs once across
+    mgf_amd/csrc/k_batch_*.h, and no header asks that a change be made twice."""
+    text = {f: read("mgf_amd", "csrc", f) for f in _batch_headers()}
+    assert len(text) >= 17, sorted(text)
+    once = {
+        "the ray front": "__device__ __forceinline__ void bq_ray_front(",
+        "the sweep front": "__device__ __forceinline__ void bq_sweep_front(",
+        "the box front": "__device__ __forceinline__ uint32_t bo_front(",
+        "the overlap kernels' body": "__device__ __forceinline__ void bo_overlap(",
+        "the zone-first kernels' body": "__device__ __forceinline__ void bz_first(",
+        "the nearest kernels' body": "__device__ __forceinline__ void bn_nearest(",
+        "the zones' fixed loader": "__device__ __forceinline__ BatchBox bz_fixed(",
+        "the zones' mounted loader": "__device__ __forceinline__ BatchBox bz_mounted(",
+        "the zones' box store": "__device__ __forceinline__ void bz_box_out(",
+        "the sensors' loader and store": "__device__ __forceinline__ void bs_rays(",
+        "the feelers' loader and store": "__device__ __forceinline__ void bf_casts(",
+    }
+    where = {"bq_ray_front(": "k_batch_query.h", "bq_sweep_front(": "k_batch_query.h", "bo_front(": "k_batch_observe.h", "bo_overlap(": "k_batch_observe.h",
+             "bz_first(": "k_batch_zone.h", "bn_nearest(": "k_batch_nearest.h", "bz_fixed(": "k_batch_zone.h", "bz_mounted(": "k_batch_zone.h",
+             "bz_box_out(": "k_batch_zone.h", "bs_rays(": "k_batch_sensor.h", "bf_casts(": "k_batch_feeler.h"}
+    for what, line in once.items():
+        assert sum(t.count(line) for t in text.values()) == 1, what
+        fn = line.split()[-1]
+        assert line in text[where[fn]], what
+        assert len(re.findall(r"^[^/\n]*\b(?:void|uint32_t|BatchBox) " + re.escape(fn), "".join(text.values()), re.M)) == 1, what     # however it is spelt
+    # the loaders' and stores' own lines: once each
+    for line in ("const SensorIn s = A.rig[qi];", "const FeelerIn f = A.rig[qi];", "const ZoneIn s = A.rig[qi];", "A.casts[qi] = m;",
+                 "float* o = A.parts + 7 * (size_t)qi;", "float* bo = boxes_out + 6 * (size_t)qi;", "for (uint32_t r0 = 0; r0 < k; r0 += 4u)",
+                 "if (hit && rank < k) record()[1u + rank] = (int32_t)i;", "if (FILL && hit) A.out[base + rank] = i;",
+                 "q_ray_store(A.out + 7 * (size_t)qi, best);", "q_sweep_store(A.out + 13 * (size_t)qi, best);"):
+        assert sum(t.count(line) for t in text.values()) == 1, line
+    for f, t in text.items():
+        assert "KEEP IN STEP" not in t, f
+    for f in ("k_batch_query.h", "k_batch_query_dev.h", "k_batch_sensor.h", "k_batch_feeler.h", "k_batch_observe.h", "k_batch_zone.h", "k_batch_nearest.h",
+              "k_batch_part_query.h"):
+        assert "restated" not in text[f] and "a second time" not in text[f], f
+    # both policies of the bodies are named where the fronts stand
+    q = text["k_batch_query.h"]
+    assert "struct PlainBodies {" in q and "PartBodies (k_batch_part_query.h)" in q and "struct PartBodies {" in text["k_batch_part_query.h"]
 
 
 def test_the_query_kernels_keep_their_figures_and_the_library_holds_no_lane_mask():

@@ -203,11 +203,18 @@ def test_both_pointers_are_looked_up_before_the_first_enqueue():
     front = q[q.index("void bq_ray_front("):]
     front = front[:front.index("\n}\n")]
     assert front.count("return;") == 2 and "atomic" not in front
-    assert (front.index("blockIdx.x >= *S.n_items) return;") < front.index("bq_stage(") < front.index("load(") < front.index("bq_reduce(")
-            < front.index("if (W.sub != 0u || !W.live) return;") < front.index("q_ray_store(") < front.index("done("))
+    assert (front.index("blockIdx.x >= *S.n_items) return;") < front.index("bodies.stage(") < front.index("load(qi, W.g0);") < front.index("bodies.ray_walk(")
+            < front.index("bq_reduce(") < front.index("if (W.sub != 0u || !W.live) return;") < front.index("q_ray_store(") < front.index("done("))
+    assert "__syncthreads" not in front                                   # (the barriers are the staging's - bq_stage's - and bq_reduce's)
+    plain = q[q.index("struct PlainBodies {"):q.index("void bq_ray_front(")]
+    assert "bq_stage(A, g0, n, s_dyn, s_dyn + n);" in plain
+    walk = plain[plain.index("QueryBest ray_walk("):plain.index("SweepBest sweep_walk(")]
+    assert walk.index("bq_ray_far(") < walk.index("q_ray_comp(") < walk.index("best.offer(") and not re.search(r"return;|__syncthreads|atomic", walk)
+    # (the loader and the store are bs_rays, written once for this kernel and its part-aware form; the kernel is the one call of it)
     k = read("mgf_amd", "csrc", "k_batch_sensor.h")
-    body = k[k.index("void k_batch_sensor_ray("):]
+    body = k[k.index("void bs_rays("):]
     assert "bq_ray_front<kItemTable>(" in body and not re.search(r"return;|__syncthreads|atomic|bq_stage|bq_reduce", body)
+    assert body.count("bs_rays(A, PlainBodies(A), s_dyn);") == 1 and body.index("bq_ray_front<kItemTable>(") < body.index("void k_batch_sensor_ray(")
 
 
 # ---- 5 ------------------------------------------------------------------------------------------------------------------------------------

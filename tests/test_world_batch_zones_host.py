@@ -235,22 +235,30 @@ def test_both_device_forms_look_every_pointer_up_before_the_first_enqueue():
     assert host.count("hipMemcpyAsync(") == 2 and host.count("hipStreamSynchronize(") == 2 and host.index("if (!boxes_out) {") < host.index("hipMemcpyAsync(")
     # the kernel: no exit at all, no atomic, one barrier ahead of the split; every lane makes every trip
     # (read in the front the kernel shares with k_batch_observe_overlap - bo_front, k_batch_observe.h - followed by the kernel itself,
-    # which brings the loaders, the store behind a hit and the epilogue)
+    # which brings the loaders, the store behind a hit and the epilogue: the loaders and the kernel's body - bz_first - are written once
+    # for this kernel and its part-aware form, and the kernel is the one call of that body with the plain bodies)
     k, o = read("mgf_amd", "csrc", "k_batch_zone.h"), read("mgf_amd", "csrc", "k_batch_observe.h")
-    shared = o[o.index("uint32_t bo_front("):o.index("// LDS (dynamic): 32 bytes a body.")]
-    body = k[k.index("void k_batch_zone_first("):]
+    shared = o[o.index("uint32_t bo_front("):o.index("// k_batch_observe_overlap<FILL> and its part-aware form")]
+    body = k[k.index("BatchBox bz_fixed("):]
+    assert body.count("bz_first<SRC>(A, PlainBodies(A), S, s_dyn);") == 1 and body.index("void bz_first(") < body.index("void k_batch_zone_first(")
     front = shared + body
     # (the only returns: the front's count at its end and the values of the kernel's hooks - a loader's box, the record's address)
-    assert "return;" not in front and not re.search(r"return (?!m;|b;|BatchBox\{|A\.out \+)", front) and shared.rstrip().endswith("return m;\n}")
+    assert "return;" not in front and not re.search(r"return (?!m;|b;|BatchBox\{|A\.out \+|bz_fixed\(A, qi\);|bz_mounted\(A, qi, g0\);)", front)
+    assert shared.rstrip().endswith("return m;\n}")
     assert "atomic" not in front and front.count("__syncthreads()") == 1
     assert (front.index("__syncthreads()") < front.index("W.template split<IDENTITY>(A, min(W.shift(), 6u))") < front.index("load(W.qi, g0)")
             < front.index("for (uint32_t i0 = 0; i0 < n; i0 += L)") < front.index("(int32_t)i != ign") < front.index("__ballot(hit)")
             < front.index("put(hit, i, m + (uint32_t)__popcll(g & ((1ull << sub) - 1ull)));") < len(shared)
             < front.index("if (hit && rank < k) record()[1u + rank] = (int32_t)i") < front.index("o[0] = (int32_t)m") < front.index("o[1u + s] = -1"))
     # the fixed layout splits with the identity for an order, and both layouts drop the ignored body
-    assert "SRC == kItemFixed ? bo_front<true, true>(A, W, s_dyn, z, fixed, store) : bo_front<false, true>(A, W, s_dyn, z, mounted, store)" in body
-    assert "template <bool IDENTITY, bool IGNORE, class Load, class Put>" in o and "(!IGNORE || (int32_t)i != ign)" in shared
-    assert "comp_bounds(to_comp(A.col0[(size_t)g0 + i], A.col1[(size_t)g0 + i]))" in shared and "isnan" not in k and "isnan" not in o
+    assert ("SRC == kItemFixed ? bo_front<true, true>(A, bodies, W, s_dyn, z, fixed, store) : bo_front<false, true>(A, bodies, W, s_dyn, z, mounted, store)"
+            in body)
+    assert "template <bool IDENTITY, bool IGNORE, class Bodies, class Load, class Put>" in o and "(!IGNORE || (int32_t)i != ign)" in shared
+    # the staged box is the bodies' policy's: the plain one is the tight bounds of the collider row
+    q = read("mgf_amd", "csrc", "k_batch_query.h")
+    plain = q[q.index("struct PlainBodies {"):q.index("void bq_ray_front(")]
+    assert "bodies.box((size_t)g0 + i)" in shared and plain.count("comp_bounds(to_comp(A.col0[g], A.col1[g]))") == 1 and "isnan" not in plain
+    assert "isnan" not in k and "isnan" not in o
     assert not re.search(r"return;|__syncthreads|atomic|__shared__ (?!float4 s_dyn)", body.replace("extern __shared__ float4 s_dyn[];", ""))
 
 
