@@ -1416,7 +1416,9 @@ MGF_API mgf_status mgf_batch_apply_springs_dev(mgf_batch* b, float h, float* wre
  * n_act != mgf_batch_actuator_count(b); n_touch != mgf_batch_touch_count(b) (report rows of the wrong length are a bug, not a prefix);
  * NULL u with n_act > 0 and n_ticks > 0; NULL touch with n_touch > 0 and n_ticks > 0; body == NULL with m > mgf_batch_len(b, -1).
  * n_ticks == 0: MGF_OK, nothing written, nothing enqueued beyond what mgf_batch_step(b, dt, iters, 0, stats) does.
- * OUT OF SCOPE here: ray sensors, feelers, zones or cameras per tick (they need the collider gather in the train); sums over the
+ * OUT OF SCOPE here: ray sensors, feelers, zones or cameras per tick (they need the collider gather in the train) (since: Rollout sensor traces,
+ * below - mgf_batch_rollout_observe writes the ray sensors' answers per tick, staged from the tick's own packed bodies, without the
+ * gather; feelers, zones and cameras still not); sums over the
  * horizon (a reduction of the rows); the lone mgf_world; hipGraph capture. */
 #define MGF_ROLLOUT_TOUCH_FULL  0   /* a row entry is mgf_touch_report, 64 bytes */
 #define MGF_ROLLOUT_TOUCH_SHORT 1   /* 16 bytes: n_contacts, partner, normal_impulse, strongest_impulse of that report */
@@ -1436,6 +1438,71 @@ MGF_API mgf_status mgf_batch_rollout_touches(mgf_batch* b, float dt, int32_t ite
 MGF_API mgf_status mgf_batch_rollout_touches_dev(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u_dev, int64_t n_act, int32_t mode,
                                                  const int32_t* body_dev, int64_t m, float* x_dev, float* q_dev, float* v_dev, float* omega_dev,
                                                  void* touch_dev, int64_t n_touch, int32_t touch_format, mgf_step_stats* stats);
+/* ---- rollout sensor traces: the ray sensors' answers behind every tick of a rollout ----
+ * A rollout records the state of chosen bodies behind every tick, and (rollout touch traces) what touched them.  What the agents SEE -
+ * the ray-sensor rig of mgf_batch_set_sensors, the cheapest and most used observation of a batch - was still a loop of T casts with T
+ * host waits.  These two calls are a rollout that can also write, behind tick t, row t of the contact sensors' reports and row t of the
+ * ray sensors' answers.  The traces come in ONE struct, so that the next trace is a field and not another entry point.
+ * THE DEFINITION is calls that exist, bit for bit.  With sensor[T][n_sensor] in the rig's order, the batch and every output are left as
+ *   for t in 0 .. T-1:
+ *     mgf_batch_apply_springs_dev(b, dt, NULL)                                                  (with a spring rig that is not empty)
+ *     mgf_batch_actuate_dev(b, u[t], n_act, mode, NULL)                                        (skipped when n_act == 0)
+ *     mgf_batch_step(b, dt, iters, 1, stats + t * n_worlds)
+ *     mgf_batch_gather_state_dev(b, body, m, x[t], q[t], v[t], omega[t], NULL, NULL)           (skipped when m == 0)
+ *     mgf_batch_read_touches_dev(b, touch + t * n_touch, n_touch)                              (with a touch trace)
+ *     mgf_batch_cast_sensors_dev(b, sensor_mask, hits_row_t, NULL, n_sensor)                   (with a sensor trace)
+ * leaves them.  sensor_format MGF_ROLLOUT_SENSOR_HIT: entry i of row t is hits_row_t[i], the 28-byte mgf_ray_hit.
+ * MGF_ROLLOUT_SENSOR_DEPTH: an entry is one f32 - that hit's t, or the sensor's dt where nothing is hit (the depth cameras' rule: inf
+ * for a sensor set with dt = inf; a sensor without a direction hits nothing).  EVERY entry of every row is written by a call that
+ * returns MGF_OK.  The touch rows are mgf_batch_rollout_touches'.
+ * A TRACE IS ASKED FOR by rows that are not NULL and a count that is not 0; then the count must be the rig's.  NULL rows, or a count
+ * of 0, name no trace, whatever the rig holds (so a batch with a touch rig can trace its ray sensors alone); the formats and the reserved
+ * words are checked all the same, the mask with a sensor trace alone (a zeroed struct with the touch fields set is in order).
+ * traces == NULL: the call IS mgf_batch_rollout / _rollout_dev, launch for launch.  No sensor trace: it IS mgf_batch_rollout_touches /
+ * _touches_dev with the struct's touch fields, launch for launch and byte for byte.  No touch trace: no launch of the touch trace.
+ * ONE HOST WAIT per pass, as in a rollout.  NO COLLIDER GATHER rides in the train: behind a tick the tick's packed copy of the bodies is
+ * what the gather would copy, and the cast stages from it.  A world whose tick t did not fit is undone and its row t is written in the
+ * pass in which it completes t - never from a cast of an undone tick: the rows are written under the gate of the state rows.  (The
+ * cast itself is not gated: a pass that runs a tick again casts for every world, and only the rows of the worlds that completed the
+ * tick in this pass are written.)  The handle's scratch holds the cast (28 + 28 bytes a sensor); a cast call behind the rollout answers
+ * as if the loop had run.
+ * The trace adds MGF_BATCH_ROLLOUT_SENSOR_LAUNCHES_PER_TICK = 2 launches behind a tick in every pass that runs it - the cast, and the
+ * rows with the obstacles of the sensors' worlds - whatever the worlds and the sensors, counted in "rollout_launches"; "query_launches"
+ * and "drive_launches" are not touched.
+ * REFUSED with MGF_ERR_INVALID, nothing enqueued and nothing changed, in this order - ahead of the handle's contents: a NULL batch; a
+ * negative n_ticks, iters, n_act, m, n_touch or n_sensor, in that order; n_ticks > 2^20; a mode other than MGF_ACTUATE_IMPULSE or
+ * MGF_ACTUATE_FORCE; a touch_format other than MGF_ROLLOUT_TOUCH_FULL or MGF_ROLLOUT_TOUCH_SHORT; a sensor_format other than
+ * MGF_ROLLOUT_SENSOR_HIT or MGF_ROLLOUT_SENSOR_DEPTH; with a sensor trace a sensor_mask that a cast refuses (no bit, or one outside MGF_QUERY_ALL); a reserved word
+ * that is not 0; m > INT32_MAX; a byte count (4 * n_ticks * n_act, then 64 * n_ticks * n_touch, then 28 * n_ticks * n_sensor - the
+ * full records' bounds, whatever the formats) that overflows int64_t - then the handle's own: n_act != mgf_batch_actuator_count(b);
+ * with a touch trace n_touch != mgf_batch_touch_count(b); with a sensor trace n_sensor != mgf_batch_sensor_count(b) (rows of the wrong
+ * length are a bug, not a prefix); NULL u with n_act > 0 and n_ticks > 0; body == NULL with m > mgf_batch_len(b, -1); with a sensor
+ * trace, a batch that holds bodies of several components - option "part_queries" or not: the cast in the train sees one collider a body.
+ * n_ticks == 0: MGF_OK, nothing written, nothing enqueued beyond what mgf_batch_step(b, dt, iters, 0, stats) does.
+ * OUT OF SCOPE here: feelers, zones and cameras per tick; batches with bodies of several components (the part-aware staging reads the
+ * gathered colliders); the particles per tick; a kinds mask per sensor; the lone mgf_world; hipGraph capture. */
+#define MGF_ROLLOUT_SENSOR_HIT   0   /* a row entry is mgf_ray_hit, 28 bytes */
+#define MGF_ROLLOUT_SENSOR_DEPTH 1   /* one f32: the hit's t, or the sensor's dt where nothing is hit */
+#define MGF_BATCH_ROLLOUT_SENSOR_LAUNCHES_PER_TICK 2   /* what the sensor trace adds to a rollout's tick, in every pass that runs it */
+typedef void* mgf_trace_rows;            /* the rows of a trace: host memory for the host form, device memory for the device form */
+typedef struct mgf_rollout_traces {      /* 64 bytes */
+  mgf_trace_rows touch;  int64_t n_touch;    /* as mgf_batch_rollout_touches'; NULL or 0: no touch trace */
+  mgf_trace_rows sensor; int64_t n_sensor;   /* [n_ticks][n_sensor] entries; NULL or 0: no sensor trace */
+  int32_t touch_format, sensor_format, sensor_mask;   /* MGF_ROLLOUT_TOUCH_*, MGF_ROLLOUT_SENSOR_*, MGF_QUERY_* */
+  int32_t reserved[5];                   /* must be 0 */
+} mgf_rollout_traces;
+/* The host form: one upload (u and body), the device core, one download (the outputs given, both traces' rows among them). */
+MGF_API mgf_status mgf_batch_rollout_observe(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u, int64_t n_act, int32_t mode,
+                                             const int32_t* body, int64_t m, float* x, float* q, float* v, float* omega,
+                                             const mgf_rollout_traces* traces, mgf_step_stats* stats);
+/* The same with u, body, the outputs and both trace pointers in device memory (the device-pointer calls, above); the struct itself and
+ * stats stay host memory.  Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer
+ * calls for its full extent (mgf_batch_rollout_touches_dev's, and 28 * n_ticks * n_sensor bytes of traces->sensor - 4 * n_ticks *
+ * n_sensor for MGF_ROLLOUT_SENSOR_DEPTH), an output's bytes overlapping another output's or an input's: the six outputs are held
+ * against each other and against u_dev and body_dev. */
+MGF_API mgf_status mgf_batch_rollout_observe_dev(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u_dev, int64_t n_act, int32_t mode,
+                                                 const int32_t* body_dev, int64_t m, float* x_dev, float* q_dev, float* v_dev, float* omega_dev,
+                                                 const mgf_rollout_traces* traces, mgf_step_stats* stats);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /
@@ -1443,7 +1510,7 @@ MGF_API mgf_status mgf_batch_rollout_touches_dev(mgf_batch* b, float dt, int32_t
  * neither n_worlds nor n), "device_skipped" (records of the device-pointer calls whose index was out of range, cumulative; waits for the
  * stream), "pair_table_uploads" (uploads of mgf_batch_copy_worlds_where's pair table, cumulative), "actuators_skipped" (above),
  * "rollout_launches" (launches of the last mgf_batch_rollout / _rollout_dev / _rollout_touches / _rollout_touches_dev call beyond its
- * ticks' own, the touch trace's one a tick a pass among them), "springs_skipped" (above)}. */
+ * ticks' own, the touch trace's one a tick a pass among them - and of the last mgf_batch_rollout_observe / _observe_dev call, the sensor trace's two a tick a pass among them), "springs_skipped" (above)}. */
 MGF_API mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out);
 /* Options (test knobs): "cons_per_body" [4] = the constraint records per body a world's share of the storage starts with (1 .. 4096); a
  * low value makes the first busy tick outgrow it, which the re-run path then handles.  "part_queries" [0] = 0 | 1 (any other value:

@@ -200,6 +200,17 @@ TOUCH_SHORT_DTYPE = np.dtype([("n_contacts", "<i4"), ("partner", "<i4"), ("norma
 assert TOUCH_SHORT_DTYPE.itemsize == 16
 ROLLOUT_TOUCH_FULL, ROLLOUT_TOUCH_SHORT = 0, 1  # MGF_ROLLOUT_TOUCH_FULL, _SHORT
 BATCH_ROLLOUT_TOUCH_LAUNCHES_PER_TICK = 1  # MGF_BATCH_ROLLOUT_TOUCH_LAUNCHES_PER_TICK
+ROLLOUT_SENSOR_HIT, ROLLOUT_SENSOR_DEPTH = 0, 1  # MGF_ROLLOUT_SENSOR_HIT, _DEPTH
+BATCH_ROLLOUT_SENSOR_LAUNCHES_PER_TICK = 2  # MGF_BATCH_ROLLOUT_SENSOR_LAUNCHES_PER_TICK
+
+
+class ROLLOUT_TRACES(C.Structure):
+    """mgf_rollout_traces: the traces of mgf_batch_rollout_observe / _observe_dev, 64 bytes"""
+    _fields_ = [("touch", C.c_void_p), ("n_touch", C.c_int64), ("sensor", C.c_void_p), ("n_sensor", C.c_int64),
+                ("touch_format", C.c_int32), ("sensor_format", C.c_int32), ("sensor_mask", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+assert C.sizeof(ROLLOUT_TRACES) == 64
 QUERY_BODIES, QUERY_TERRAIN, QUERY_OBSTACLES, QUERY_ALL = 1, 2, 4, 7
 
 # every symbol include/mgf_hip.h declares (tests check the library exports all of them)
@@ -247,6 +258,7 @@ SYMBOLS = [
     "mgf_batch_set_feelers", "mgf_batch_feeler_count", "mgf_batch_cast_feelers", "mgf_batch_cast_feelers_dev",
     "mgf_batch_set_actuators", "mgf_batch_actuator_count", "mgf_batch_actuate", "mgf_batch_actuate_dev",
     "mgf_batch_rollout", "mgf_batch_rollout_dev", "mgf_batch_rollout_touches", "mgf_batch_rollout_touches_dev",
+    "mgf_batch_rollout_observe", "mgf_batch_rollout_observe_dev",
     "mgf_batch_set_springs", "mgf_batch_spring_count", "mgf_batch_apply_springs", "mgf_batch_apply_springs_dev",
 ]
 
@@ -446,6 +458,8 @@ def load_library():
         "mgf_batch_rollout_dev": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp]),
         "mgf_batch_rollout_touches": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i64, i32, vp]),
         "mgf_batch_rollout_touches_dev": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i64, i32, vp]),
+        "mgf_batch_rollout_observe": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, C.POINTER(ROLLOUT_TRACES), vp]),
+        "mgf_batch_rollout_observe_dev": (i32, [vp, f32, i32, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, C.POINTER(ROLLOUT_TRACES), vp]),
         "mgf_batch_set_springs": (i32, [vp, vp, i64]),
         "mgf_batch_spring_count": (i64, [vp]),
         "mgf_batch_apply_springs": (i32, [vp, f32, vp]),
@@ -2239,6 +2253,108 @@ class WorldBatch:
         arr = (StepStats * (T * self.n_worlds))()
         _check(load_library().mgf_batch_rollout_touches_dev(self._h, float(dt), int(iters), T, up, n, int(mode), bp, m, *p, tp, nt,
                                                             ROLLOUT_TOUCH_SHORT if short else ROLLOUT_TOUCH_FULL, arr))
+        return arr
+
+    # ---- rollout sensor traces: the ray sensors' answers behind every tick of a rollout ---------------------------------------------------
+    def rollout_observe(self, u, dt, iters, mode=ACTUATE_IMPULSE, body=None, trace=("x", "q", "v", "omega"), touches=False, short=False, sensors=None,
+                        kinds=QUERY_ALL):
+        """rollout, and behind tick t row t of the contact sensors' reports (touches=True; short: rollout_touches') and / or row t of the
+        ray sensors' answers (mgf_batch_rollout_observe): the loop actuate(u[t]) | step(dt, iters) | gather of `body` | read_touches |
+        cast_sensors(kinds) with the step's one host wait.  sensors: "hit" - the result's "sensors" is a RAY_HIT_DTYPE array
+        [T, sensor_count()] in the rig's order - or "depth" - a float32 [T, sensor_count()] array, a hit's t or the sensor's dt where
+        nothing is hit - or None.  The other arguments and result entries are rollout_touches'."""
+        if sensors not in (None, "hit", "depth"):
+            raise ValueError(f"sensors: {sensors!r} is not one of 'hit', 'depth', None")
+        n = max(self.actuator_count(), 0)
+        if isinstance(u, (int, np.integer)):
+            if n:
+                raise ValueError("u: a number of ticks stands for the controls of an empty rig only")
+            uu = np.zeros((int(u), 0), np.float32)
+        else:
+            uu = np.ascontiguousarray(u, np.float32)
+        if uu.ndim != 2 or uu.shape[1] != n:
+            raise ValueError(f"u: {uu.shape} is not [T, {n}]")
+        unknown = [k for k in trace if k not in ("x", "q", "v", "omega")]
+        if unknown:
+            raise ValueError(f"trace: {unknown[0]!r} is not one of x, q, v, omega")
+        T = uu.shape[0]
+        bb = None if body is None else np.ascontiguousarray(body, np.int32).reshape(-1)
+        m = len(self) if bb is None else len(bb)
+        out = {k: np.zeros((T, m, 4 if k == "q" else 3), np.float32) for k in ("x", "q", "v", "omega") if k in trace}
+        tr = ROLLOUT_TRACES()
+        tr.touch_format = ROLLOUT_TOUCH_SHORT if short else ROLLOUT_TOUCH_FULL
+        tr.sensor_format = ROLLOUT_SENSOR_DEPTH if sensors == "depth" else ROLLOUT_SENSOR_HIT
+        tr.sensor_mask = int(kinds)
+        if touches:
+            nt = max(self.touch_count(), 0)
+            out["touches"] = np.zeros((T, nt), TOUCH_SHORT_DTYPE if short else TOUCH_REPORT_DTYPE)
+            tr.touch, tr.n_touch = (out["touches"].ctypes.data if out["touches"].size else None), nt
+        if sensors is not None:
+            ns = max(self.sensor_count(), 0)
+            out["sensors"] = np.zeros((T, ns), np.float32 if sensors == "depth" else RAY_HIT_DTYPE)
+            tr.sensor, tr.n_sensor = (out["sensors"].ctypes.data if out["sensors"].size else None), ns
+        arr = (StepStats * (T * self.n_worlds))()
+        _check(load_library().mgf_batch_rollout_observe(self._h, float(dt), int(iters), T, uu.ctypes.data if uu.size else None, n, int(mode),
+                                                        bb.ctypes.data if bb is not None and m else None, m,
+                                                        *[out[k].ctypes.data if k in out and out[k].size else None for k in ("x", "q", "v", "omega")],
+                                                        C.byref(tr), arr))
+        out["stats"] = arr
+        return out
+
+    def rollout_observe_dev(self, u, dt, iters, mode=ACTUATE_IMPULSE, body=None, x=None, q=None, v=None, omega=None, touches=None, short=False, sensors=None,
+                            depth=False, kinds=QUERY_ALL):
+        """rollout_touches_dev, and row t of the ray sensors' answers behind tick t as well (mgf_batch_rollout_observe_dev).  sensors: a
+        CUDA tensor of int32 or float32 [T, n, 7], n = sensor_count() - an entry is RAY_HIT_DTYPE's seven words - or (depth) float32
+        [T, n]; a raw address; None: rollout_touches_dev.  touches: rollout_touches_dev's, or None - no touch trace.  The other
+        arguments and the result are rollout_dev's."""
+        if u is None:
+            raise ValueError("u is required")
+        n = max(self.actuator_count(), 0)
+        if isinstance(u, (int, np.integer)):
+            if n:
+                raise ValueError("u: a number of ticks stands for the controls of an empty rig only")
+            T, up = int(u), None
+        else:
+            if not hasattr(u, "data_ptr"):
+                raise ValueError(f"u: a torch tensor on the GPU, not {type(u).__name__}")
+            if u.dim() != 2 or u.shape[1] != n:
+                raise ValueError(f"u: {tuple(u.shape)} is not [T, {n}]")
+            T = int(u.shape[0])
+            up = _dev_arg(u, "float32", n, T, "u")
+        if body is None:
+            bp, m = None, len(self)
+        else:
+            if not hasattr(body, "data_ptr"):
+                raise ValueError(f"body: a torch tensor on the GPU, not {type(body).__name__}")
+            m = int(body.numel())
+            bp = _dev_arg(body, "int32", 1, m, "body")
+        p = []
+        for a, name, cols in ((x, "x", 3), (q, "q", 4), (v, "v", 3), (omega, "omega", 3)):
+            if a is not None:
+                if not hasattr(a, "data_ptr"):
+                    raise ValueError(f"{name}: a torch tensor on the GPU, not {type(a).__name__}")
+                if tuple(a.shape) != (T, m, cols):
+                    raise ValueError(f"{name}: {tuple(a.shape)} is not [{T}, {m}, {cols}]")
+            p.append(_dev_arg(a, "float32", m * cols, T, name))
+        tr = ROLLOUT_TRACES()
+        tr.touch_format = ROLLOUT_TOUCH_SHORT if short else ROLLOUT_TOUCH_FULL
+        tr.sensor_format = ROLLOUT_SENSOR_DEPTH if depth else ROLLOUT_SENSOR_HIT
+        tr.sensor_mask = int(kinds)
+        if touches is not None:
+            nt, words = max(self.touch_count(), 0), 4 if short else 16
+            if hasattr(touches, "data_ptr") and tuple(touches.shape) != (T, nt, words):
+                raise ValueError(f"touches: {tuple(touches.shape)} is not [{T}, {nt}, {words}]")
+            dtype = "float32" if str(getattr(touches, "dtype", "")) == "torch.float32" else "int32"
+            tr.touch, tr.n_touch = _dev_arg(touches, dtype, nt * words, T, "touches"), nt
+        if sensors is not None:
+            ns = max(self.sensor_count(), 0)
+            shape = (T, ns) if depth else (T, ns, 7)
+            if hasattr(sensors, "data_ptr") and tuple(sensors.shape) != shape:
+                raise ValueError(f"sensors: {tuple(sensors.shape)} is not {list(shape)}")
+            dtype = "float32" if depth or str(getattr(sensors, "dtype", "")) == "torch.float32" else "int32"
+            tr.sensor, tr.n_sensor = _dev_arg(sensors, dtype, ns * (1 if depth else 7), T, "sensors"), ns
+        arr = (StepStats * (T * self.n_worlds))()
+        _check(load_library().mgf_batch_rollout_observe_dev(self._h, float(dt), int(iters), T, up, n, int(mode), bp, m, *p, C.byref(tr), arr))
         return arr
 
     # ---- springs between bodies: a rig set once, impulses formed from the resident state and applied in two launches -----------------------

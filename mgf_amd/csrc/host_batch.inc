@@ -871,13 +871,20 @@ struct BatchRolloutHook {
   bool springs = false;  // the spring rig is not empty: they go ahead of the actuation, which a damper must not see
   BatchTraceTouchArgs T;  // the touch trace (k_batch_trace.h): V.out - row 0 - and n_touch; the train fills the rest in, the lists' view per PASS
   int32_t touch = -1;    // MGF_ROLLOUT_TOUCH_FULL / _SHORT: k_batch_trace_touch behind every tick's record; -1: no touch trace
+  BatchSensorArgs R;     // the sensor trace's cast (k_batch_scan.h): mask, out and parts - the handle's scratch; the train fills the rest in per PASS
+  BatchScanRowsArgs W;   // ... and its rows: out - row 0 - and n_sensor; the train fills the rest in per PASS
+  int32_t scan = -1;     // MGF_ROLLOUT_SENSOR_HIT / _DEPTH: k_batch_scan_rays and k_batch_scan_rows behind every tick's touch trace; -1: no sensor trace
   int64_t launches = 0;  // what the hook added to the train's launches
 };
 static uint32_t batch_touch_tile(const mgf_batch* b);  // (host_batch_touch.inc, behind this file) the words of dynamic LDS the contact sensors' fold stages
+// (host_batch_query.inc, behind this file) the dynamic LDS of a ray cast with a workgroup per work item; what a cast reads of the handle; has it obstacles to meet
+static uint32_t batch_ray_lds(const mgf_batch* b);
+static void batch_work_args(const mgf_batch* b, BatchWorkArgs* A);
+static bool batch_has_obstacles(const mgf_batch* b, int32_t kinds_mask);
 
 // The step's launch train, behind the refusals: n_ticks x World::step (world.rs:227-294) of every world, six (seven) launches a tick, one
 // host wait per pass - and with a hook a rollout's two launches a tick among them, the springs' two where that rig is not empty and the
-// touch trace's one where it is asked for.
+// touch trace's one and the sensor trace's two where they are asked for.
 // hook == nullptr: mgf_batch_step, launch for launch.
 static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats, BatchRolloutHook* hook) {
   MGF_TRY(batch_push(b));
@@ -933,6 +940,22 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
       V.tile = batch_touch_tile(b);
       hook->T.done = b->d_done.p; hook->T.act = b->d_act.p;
     }
+    if (hook && hook->scan >= 0) {  // (the same rule for the sensor trace: what it reads of the handle is looked up again for every pass)
+      BatchRig<mgf_batch_sensor>& R = b->sensors;
+      BatchSensorArgs& V = hook->R;
+      batch_work_args(b, &V);
+      V.items = reinterpret_cast<const uint4*>(R.dev.p);
+      V.order = reinterpret_cast<const uint32_t*>(R.dev.p + R.off[2]);
+      V.rig = reinterpret_cast<const SensorIn*>(R.dev.p + R.off[1]);
+      V.T = A.T;
+      V.x = b->dm[mgf_batch::AX].p; V.q = b->dm[mgf_batch::AQ].p;
+      BatchScanRowsArgs& W = hook->W;
+      W.hits = V.out; W.parts = reinterpret_cast<const ParticleIn*>(V.parts);
+      W.worlds = reinterpret_cast<const int32_t*>(R.dev.p + R.off[3]);
+      W.O = batch_obstacles(b); W.tdesc = b->t_desc.p;
+      W.obstacles = batch_has_obstacles(b, V.mask) ? 1u : 0u;
+      W.done = b->d_done.p; W.act = b->d_act.p;
+    }
     for (uint32_t t = first; t < NT; ++t) {
       A.tick = t;
       if (hook) { hook->A.tick = t; hook->A.count = pass == 0 ? 1u : 0u; }  // (an index outside the batch is counted once a tick)
@@ -968,6 +991,16 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
         else k_batch_trace_touch<kTraceTouchFull><<<items, kBatchBlock, lds_touch, s>>>(hook->T);
         LAUNCH_CHECK();
         hook->launches += MGF_BATCH_ROLLOUT_TOUCH_LAUNCHES_PER_TICK;
+      }
+      if (hook && hook->scan >= 0) {  // (behind the record: act[k] is final; the cast for every world from bpk, then the rows of the worlds that completed tick t)
+        hook->W.tick = t;
+        const unsigned rows = (unsigned)((hook->W.n_sensor + kBatchBlock - 1) / kBatchBlock);
+        k_batch_scan_rays<<<(unsigned)b->sensors.items.size(), kBatchBlock, batch_ray_lds(b), s>>>(hook->R, b->bpk.p);
+        LAUNCH_CHECK();
+        if (hook->scan == MGF_ROLLOUT_SENSOR_DEPTH) k_batch_scan_rows<kScanDepth><<<rows, kBatchBlock, 0, s>>>(hook->W);
+        else k_batch_scan_rows<kScanHit><<<rows, kBatchBlock, 0, s>>>(hook->W);
+        LAUNCH_CHECK();
+        hook->launches += MGF_BATCH_ROLLOUT_SENSOR_LAUNCHES_PER_TICK;
       }
     }
     MGF_TRY(d2h(ctx, done.data(), b->d_done.p, K));

@@ -16,55 +16,79 @@
 // (host_batch_spring.inc, behind this file) the springs' arguments for the train: the rig up, the wrench buffer and the skip counter there
 static mgf_status batch_spring_ready(mgf_batch* b, float h, float* out_dev, BatchSpringArgs* A);
 
-struct RolloutBytes { size_t u, body, out[4], touch; };  // what the call touches of u, body, x, q, v, omega, touch
-// the touch trace of mgf_batch_rollout_touches / _touches_dev (host_batch_trace.inc): rows of n reports, device memory when it reaches the core
-struct RolloutTouch { void* out; int64_t n; int32_t format; };
+struct RolloutBytes { size_t u, body, out[4], touch, sensor; };  // what the call touches of u, body, x, q, v, omega, touch, sensor
+// the touch trace of mgf_batch_rollout_touches / _touches_dev (host_batch_trace.inc): rows of n reports, device memory when it reaches the core.
+// lax (mgf_batch_rollout_observe, host_batch_scan.inc): NULL rows or n == 0 name no trace - off() - where mgf_batch_rollout_touches holds them against the rig
+struct RolloutTouch {
+  void* out; int64_t n; int32_t format; bool lax = false;
+  bool off() const { return lax && (!out || n == 0); }
+};
+// the sensor trace of mgf_batch_rollout_observe / _observe_dev (host_batch_scan.inc): rows of n answers of the ray sensors; NULL rows or n == 0: no trace
+struct RolloutScan {
+  void* out; int64_t n; int32_t format, mask; bool reserved;  // reserved: a reserved word of the caller's struct is not 0
+  bool off() const { return !out || n == 0; }
+};
 
 // the refusals of both forms, in the header's order; nothing is enqueued here.  tt: the call traces the contact sensors
-// (mgf_batch_rollout_touches), whose refusals are slotted in where that header states them; null: mgf_batch_rollout's own, unchanged
+// (mgf_batch_rollout_touches), whose refusals are slotted in where that header states them; null: mgf_batch_rollout's own, unchanged.
+// ts: the call may trace the ray sensors (mgf_batch_rollout_observe), whose refusals stand behind the touch trace's at every stage
 static mgf_status batch_rollout_args(const mgf_batch* b, int32_t iters, int64_t n_ticks, const float* u, int64_t n_act, int32_t mode, const int32_t* body,
-                                     int64_t m, RolloutBytes* bytes, const RolloutTouch* tt = nullptr) {
+                                     int64_t m, RolloutBytes* bytes, const RolloutTouch* tt = nullptr, const RolloutScan* ts = nullptr) {
   MGF_TRY(batch_rig_handle(b));
   if (n_ticks < 0) return fail(MGF_ERR_INVALID, "n_ticks is negative");
   if (iters < 0) return fail(MGF_ERR_INVALID, "iters is negative");
   if (n_act < 0) return fail(MGF_ERR_INVALID, "n_act is negative");
   if (m < 0) return fail(MGF_ERR_INVALID, "m is negative");
   if (tt && tt->n < 0) return fail(MGF_ERR_INVALID, "n_touch is negative");
+  if (ts && ts->n < 0) return fail(MGF_ERR_INVALID, "n_sensor is negative");
   if (n_ticks > (1 << 20)) return fail(MGF_ERR_INVALID, "n_ticks must be at most 2^20");
   if (mode != MGF_ACTUATE_IMPULSE && mode != MGF_ACTUATE_FORCE) return fail(MGF_ERR_INVALID, "mode is neither MGF_ACTUATE_IMPULSE nor MGF_ACTUATE_FORCE");
   if (tt && tt->format != MGF_ROLLOUT_TOUCH_FULL && tt->format != MGF_ROLLOUT_TOUCH_SHORT)
     return fail(MGF_ERR_INVALID, "touch_format is neither MGF_ROLLOUT_TOUCH_FULL nor MGF_ROLLOUT_TOUCH_SHORT");
+  if (ts && ts->format != MGF_ROLLOUT_SENSOR_HIT && ts->format != MGF_ROLLOUT_SENSOR_DEPTH)
+    return fail(MGF_ERR_INVALID, "sensor_format is neither MGF_ROLLOUT_SENSOR_HIT nor MGF_ROLLOUT_SENSOR_DEPTH");
+  if (ts && !ts->off()) MGF_TRY(query_mask_check(ts->mask));  // (a struct that names no sensor trace may leave the mask 0)
+  if (ts && ts->reserved) return fail(MGF_ERR_INVALID, "a reserved word of mgf_rollout_traces is not 0");
   if (m > (int64_t)INT32_MAX) return fail(MGF_ERR_INVALID, "too many traced bodies in one call");
   // (n_ticks <= 2^20 and m < 2^31: 16 * n_ticks * m < 2^55)
   if (n_ticks > 0 && n_act > INT64_MAX / 4 / n_ticks) return fail(MGF_ERR_INVALID, "4 * n_ticks * n_act overflows int64_t");
   if (tt && n_ticks > 0 && tt->n > INT64_MAX / 64 / n_ticks) return fail(MGF_ERR_INVALID, "64 * n_ticks * n_touch overflows int64_t");
+  if (ts && n_ticks > 0 && ts->n > INT64_MAX / 28 / n_ticks) return fail(MGF_ERR_INVALID, "28 * n_ticks * n_sensor overflows int64_t");
   if ((uint64_t)n_act != (uint64_t)b->actuators.recs.size()) return fail(MGF_ERR_INVALID, "n_act is not mgf_batch_actuator_count: control rows of another length than the rig");
-  if (tt && (uint64_t)tt->n != (uint64_t)b->touches.recs.size()) return fail(MGF_ERR_INVALID, "n_touch is not mgf_batch_touch_count: report rows of another length than the rig");
+  if (tt && !tt->off() && (uint64_t)tt->n != (uint64_t)b->touches.recs.size()) return fail(MGF_ERR_INVALID, "n_touch is not mgf_batch_touch_count: report rows of another length than the rig");
+  if (ts && !ts->off() && (uint64_t)ts->n != (uint64_t)b->sensors.recs.size()) return fail(MGF_ERR_INVALID, "n_sensor is not mgf_batch_sensor_count: answer rows of another length than the rig");
   if (n_act > 0 && n_ticks > 0 && !u) return fail(MGF_ERR_INVALID, "NULL argument: u");
-  if (tt && tt->n > 0 && n_ticks > 0 && !tt->out) return fail(MGF_ERR_INVALID, "NULL argument: touch");
+  if (tt && !tt->off() && tt->n > 0 && n_ticks > 0 && !tt->out) return fail(MGF_ERR_INVALID, "NULL argument: touch");
   if (!body && m > mgf_batch_len(b, -1)) return fail(MGF_ERR_INVALID, "without body indices m is at most the number of bodies");
   const size_t T = (size_t)n_ticks, M = (size_t)m;
   bytes->u = 4 * T * (size_t)n_act; bytes->body = 4 * M;
   bytes->out[0] = 12 * T * M; bytes->out[1] = 16 * T * M; bytes->out[2] = 12 * T * M; bytes->out[3] = 12 * T * M;
   bytes->touch = tt ? (tt->format == MGF_ROLLOUT_TOUCH_SHORT ? 16u : 64u) * T * (size_t)tt->n : 0;
+  if (tt && tt->off()) bytes->touch = 0;
+  bytes->sensor = ts && !ts->off() ? (ts->format == MGF_ROLLOUT_SENSOR_DEPTH ? 4u : 28u) * T * (size_t)ts->n : 0;
   return MGF_OK;
 }
 
 // The device core, behind every check: the arrays are device memory (the caller's or the handle's).  tt: rows of the contact sensors'
 // reports behind every tick as well (k_batch_trace.h); null, no sensors or no rows: mgf_batch_rollout's train, launch for launch.
+// ts: rows of the ray sensors' answers behind every tick as well (k_batch_scan.h); null, no sensors or no rows: the train without them.
 static mgf_status batch_rollout_run(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u_dev, int64_t n_act, int32_t mode, const int32_t* body_dev,
-                                    int64_t m, float* x, float* q, float* v, float* omega, mgf_step_stats* stats, const RolloutTouch* tt = nullptr) {
+                                    int64_t m, float* x, float* q, float* v, float* omega, mgf_step_stats* stats, const RolloutTouch* tt = nullptr,
+                                    const RolloutScan* ts = nullptr) {
   b->r_launches = 0;
   const bool trace = m > 0 && (x || q || v || omega);
   const bool springs = !b->springs.recs.empty();  // (then even a call without controls and traces is not mgf_batch_step: the springs act ahead of every tick)
   const bool touches = tt && tt->n > 0 && tt->out;
-  if (n_ticks == 0 || (n_act == 0 && !trace && !springs && !touches)) return batch_step_run(b, dt, iters, n_ticks, stats, nullptr);
+  const bool scan = ts && ts->n > 0 && ts->out;
+  if (n_ticks == 0 || (n_act == 0 && !trace && !springs && !touches && !scan)) return batch_step_run(b, dt, iters, n_ticks, stats, nullptr);
   hipStream_t s = b->ctx->stream;
   BatchRig<mgf_batch_actuator>& R = b->actuators;
   MGF_TRY(batch_push(b));
   BatchRolloutHook H;
   memset(&H.A, 0, sizeof(H.A));
   memset(&H.T, 0, sizeof(H.T));
+  memset(&H.R, 0, sizeof(H.R));
+  memset(&H.W, 0, sizeof(H.W));
   if (n_act > 0) {
     MGF_TRY(batch_rig_up(b, R, "actuator", 3));
     if (!b->a_skipped.p) {
@@ -99,6 +123,16 @@ static mgf_status batch_rollout_run(mgf_batch* b, float dt, int32_t iters, int64
     H.T.V.out = reinterpret_cast<TouchWord*>(tt->out);
     H.T.n_touch = (uint32_t)tt->n;
     H.touch = tt->format;
+  }
+  if (scan) {  // (the sensors' rig up ahead of the train; the cast writes the handle's scratch, the rows go to the caller's; the rest is the train's to fill, pass by pass)
+    MGF_TRY(batch_rig_up(b, b->sensors, "sensor", 4));
+    MGF_TRY(b->q_out.ensure(7 * (size_t)ts->n, s));
+    MGF_TRY(b->s_parts.ensure(7 * (size_t)ts->n, s));
+    static_assert(sizeof(mgf_ray_hit) == 28 && sizeof(ParticleIn) == 28, "k_batch_scan_rows takes a hit and a particle up as seven words each");
+    H.R.mask = ts->mask;
+    H.R.out = b->q_out.p; H.R.parts = b->s_parts.p;
+    H.W.out = ts->out; H.W.n_sensor = (uint32_t)ts->n;
+    H.scan = ts->format;
   }
   H.A.B = b->bodies(0);
   H.A.w_off = b->d_off.p;

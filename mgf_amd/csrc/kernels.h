@@ -169,6 +169,12 @@
 //                      list behind tick t into row t of the reports, one launch a tick behind k_batch_rollout_record; the train's gate
 //                      done[k] == t + 1 && act[k] <= t + 1 is the workgroup's and is folded into the item's count and the list's
 //                      length; a full report of 64 bytes or a short one of 16
+//   k_batch_scan_rays / k_batch_scan_rows<FORMAT> (k_batch_scan.h)
+//                      the sensor trace of a rollout (mgf_batch_rollout_observe / _observe_dev): two launches a tick behind the touch
+//                      trace's.  The ray sensors' cast - bs_rays over TickBodies, the policy that stages a world's bodies from bpk,
+//                      the tick's packed copy, so no collider gather rides in the train - into the handle's scratch, ungated; then a
+//                      lane per sensor under the train's gate done[k] == t + 1 && act[k] <= t + 1 takes the record up, puts the
+//                      stored particle through its world's obstacles and writes row t: the 28-byte hit, or the depth alone
 //   k_batch_pq_ray<SRC> / _sweep<SRC> / _sensor / _feeler / _overlap<FILL> / _zone<SRC> / _nearest<SRC> (k_batch_part_query.h)
 //                      the body passes of the rays, sweeps, sensors, feelers, box overlaps and zones of a batch that holds bodies of
 //                      several components, under option "part_queries": the fronts and bodies of the kernels above - each written
@@ -209,3 +215,4 @@
 #include "k_batch_spring.h"  // springs between bodies: impulses formed from the resident state, applied a lane per body (k_batch_spring_wrench, _apply)
 #include "k_batch_part_query.h"  // rays, sweeps and box queries that see the parts of bodies of several components (k_batch_pq_*)
 #include "k_batch_trace.h"  // the touch trace of a rollout: the contact sensors' reports behind every tick (k_batch_trace_touch)
+#include "k_batch_scan.h"  // the sensor trace of a rollout: the ray sensors' answers behind every tick (k_batch_scan_rays, _rows)
