@@ -1249,7 +1249,7 @@ MGF_API mgf_status mgf_batch_cast_feelers_dev(mgf_batch* b, int32_t kinds_mask, 
  * per body that has an actuator walks the body's actuators in the caller's order - no float atomic, nothing depends on lane scheduling.
  * OUT OF SCOPE here: actuators on the lone mgf_world; re-evaluation of a wrench per tick inside a multi-tick mgf_batch_step (a FORCE
  * wrench stays fixed in the world's frame until the next call) (since: Rollouts, below - mgf_batch_rollout); joints and motors between two bodies (spring-dampers since: Springs
- * between bodies, below - mgf_batch_set_springs). */
+ * between bodies, below - mgf_batch_set_springs; ball joints since: Ball joints between bodies, below - mgf_batch_set_joints). */
 #define MGF_ACTUATOR_TORQUE     1   /* a pure couple about d: no force, p is not read */
 #define MGF_ACTUATOR_WORLD_DIR  2   /* d is in world coordinates; the arm p stays in the body's frame */
 #define MGF_ACTUATE_IMPULSE 0
@@ -1362,7 +1362,8 @@ MGF_API mgf_status mgf_batch_rollout_dev(mgf_batch* b, float dt, int32_t iters, 
  * traced is then NOT mgf_batch_step: it is the stepping call of a batch with springs.  A world whose tick is undone and run again
  * gets tick t's springs ONCE, as it gets its control row once, and "springs_skipped" counts as the loop's calls would.
  * mgf_batch_step itself stays World::step, launch for launch: it applies no spring.
- * OUT OF SCOPE here: hard joints and limits in the solver; springs on the lone mgf_world; springs inside mgf_batch_step; the wrenches
+ * OUT OF SCOPE here: hard joints and limits in the solver (ball joints in a pass of their own since: Ball joints between bodies, below -
+ * mgf_batch_set_joints); springs on the lone mgf_world; springs inside mgf_batch_step; the wrenches
  * per tick of a rollout; angular (torsion) springs; rest lengths or gains driven per tick from a control row. */
 #define MGF_BATCH_SPRING_LAUNCHES 2  /* the most one call adds to "drive_launches" */
 #define MGF_BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK 2  /* what a spring rig that is not empty adds to a rollout's tick, at most */
@@ -1387,6 +1388,88 @@ MGF_API mgf_status mgf_batch_apply_springs(mgf_batch* b, float h, float* wrench_
  * Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls (48 bytes a
  * spring of wrench_out_dev). */
 MGF_API mgf_status mgf_batch_apply_springs_dev(mgf_batch* b, float h, float* wrench_out_dev);
+/* ---- ball joints between bodies: point-to-point constraints, solved by sequential impulses from the resident state ----
+ * A limb on a torso, a rope or a chain (a row of joints), a hinge (two joints on the hinge axis), a body pinned to the world (a joint
+ * with a world anchor): the eighth rig and the spring's hard counterpart.  A spring is an explicit force - to hold two points together
+ * it needs a stiffness the tick's time step cannot carry, and it lets them drift apart under load; a joint makes the VELOCITIES of its
+ * two anchor points agree and removes a share of their gap per call.  The reference has no joint (solver.rs knows ContactConstraint
+ * only), so this is the build's own definition, as the springs are; no tick kernel changes and mgf_batch_step applies no joint: the
+ * joints are a pass of their own over the resident velocities, meant to run behind every external impulse and just ahead of the tick
+ * that integrates them - which is where a rollout puts it (below).
+ * A joint is a record (world, body, other, flags, pa, beta, pb, pad): body and other indices within world; pa the anchor in body's
+ * frame; pb the anchor in other's frame or, with other = -1, a point of the world; beta in [0, 1] the share of the position error
+ * removed per call (Baumgarte); flags and pad must be 0.
+ * ONE CALL, mgf_batch_solve_joints(b, h, iters, impulse_out), reads of each end x (= x + delta) and q as
+ * mgf_batch_gather_state_dev returns them, v and omega, and im and the 3x3 I - the inverse mass and the inverse inertia that
+ * mgf_batch_apply_impulses uses.  Every line below is a separate rounded f32 operation, no fused multiply-add; rotate is the
+ * sensors' Rotation::rotate_vector, (q, vector); dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z; cross(a,b) the actuators' (above), operands
+ * in the order written; M * v row by row, (m.c[0].r * v.x + m.c[1].r * v.y) + m.c[2].r * v.z; invert is cgmath's SquareMatrix::invert:
+ * det = c0.x * (c1.y * c2.z - c2.y * c1.z) - c1.x * (c0.y * c2.z - c2.y * c0.z) + c2.x * (c0.y * c1.z - c1.y * c0.z), the rows of the
+ * inverse cross(c1, c2) / det, cross(c2, c0) / det, cross(c0, c1) / det.
+ * SETUP, per joint i, from the state BEFORE the call:
+ *   ra = rotate(q_a, pa);  Pa = x_a + ra
+ *   other >= 0:  rb = rotate(q_b, pb);  Pb = x_b + rb;  im_b, I_b the body's
+ *   other == -1: rb = 0;  Pb = pb;  im_b = 0;  I_b = 0
+ *   C = Pb - Pa;  s = beta / h;  bias = C * s
+ *   column k of K, e_k the unit vector:
+ *       (e_k * im_a + cross(I_a * cross(ra, e_k), ra)) + (e_k * im_b + cross(I_b * cross(rb, e_k), rb))
+ *   Kinv = invert(K)
+ * A joint is SKIPPED if invert fails (det == 0) or any word of ra, rb, bias or Kinv is not finite: it is counted in
+ * mgf_batch_counter "joints_skipped" (cumulative; reading it waits for the stream, like "springs_skipped"), touches no velocity and
+ * reports a zero impulse - and it still takes its place in the order.
+ * SWEEPS, iters times, over the joints of a world in the order of the array given to mgf_batch_set_joints; worlds are independent:
+ *   Va = v_a + cross(omega_a, ra);  Vb = v_b + cross(omega_b, rb)      (other == -1: Vb = 0)
+ *   P = Kinv * ((Vb - Va) + bias)
+ *   v_a = v_a + P * im_a;  omega_a = omega_a + I_a * cross(ra, P)
+ *   Pn = -P;  v_b = v_b + Pn * im_b;  omega_b = omega_b + I_b * cross(rb, Pn)   (other >= 0 only)
+ *   acc_i = acc_i + P
+ * Nothing but v and omega is written; a body that no joint names is untouched to the bit, and so is a world that no joint names.
+ * impulse_out is optional: when given, row i receives acc_i, three floats - the joint's reaction over the call - rows in the order
+ * of the array given to mgf_batch_set_joints.  There is no warm start: no state is kept between calls.  Joints read no shapes: a batch
+ * with bodies of several components is answered.
+ * A call is MGF_BATCH_JOINT_LAUNCHES = 1 launch, counted in "drive_launches", whatever the number of joints and worlds: a workgroup
+ * per world that has joints, a lane per joint - hence at most MGF_BATCH_MAX_WORLD_JOINTS = 256 joints a world - which solves its
+ * joint as soon as both its bodies have been through the joints listed ahead of it; no float atomic, and the result does not depend
+ * on lane scheduling.
+ * IN A ROLLOUT.  With a joint rig that is not empty, mgf_batch_rollout and its _dev, _touches and _observe forms become, bit for bit,
+ * the loop
+ *   [mgf_batch_apply_springs_dev(dt)] | mgf_batch_actuate_dev(u[t]) | mgf_batch_solve_joints_dev(b, dt, iters, NULL) | mgf_batch_step(dt, iters, 1) |
+ *   mgf_batch_gather_state_dev(row t) | [traces]
+ * - the joints behind every external impulse, with the call's own iters: there is no new argument and no new option.  Signatures,
+ * refusals and their order stay as they are; with an empty joint rig every call is launch for launch what it was.  The joints add
+ * MGF_BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK = 1 launch to a tick, counted in "rollout_launches".  n_act == 0 with nothing traced is
+ * then NOT mgf_batch_step: it is the stepping call of a batch with joints.  A world whose tick is undone and run again gets tick t's
+ * joints ONCE, as it gets its springs once, and "joints_skipped" counts as the loop's calls would.
+ * mgf_batch_step itself stays World::step, launch for launch: it applies no joint.
+ * OUT OF SCOPE here: joints inside the tick's solver, coupled with the contacts in one sweep; angular rows, limits and motors (a
+ * hinge is two joints); warm starting; more than MGF_BATCH_MAX_WORLD_JOINTS joints a world; joints on the lone mgf_world;
+ * joints inside mgf_batch_step; the impulses per tick of a rollout; beta or anchors driven per tick from a control row. */
+#define MGF_BATCH_JOINT_LAUNCHES 1  /* what one solve call adds to "drive_launches" */
+#define MGF_BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK 1  /* what a joint rig that is not empty adds to a rollout's tick */
+#define MGF_BATCH_MAX_WORLD_JOINTS 256  /* joints one world holds at most */
+typedef struct mgf_batch_joint {
+  int32_t world, body, other; uint32_t flags;   /* other = -1: the far end is a point of the world; flags must be 0 */
+  mgf_vec3 pa; float beta;                      /* anchor in body's frame; the share of the position error removed per call, in [0, 1] */
+  mgf_vec3 pb; float pad;                       /* anchor in other's frame, or the world point; pad = 0 */
+} mgf_batch_joint;                              /* 48 bytes: three 16-byte words */
+/* Replaces the rig by a copy of j[0 .. n); n = 0 clears it.  No device work: the rig goes up with the next call.  Refused with
+ * MGF_ERR_INVALID, the rig as it was ("the rig was not changed"), in this order: what mgf_batch_set_sensors refuses - a NULL batch, a
+ * negative n or n > INT32_MAX, a NULL array with n > 0, then per record a world out of range, a body outside
+ * [0, mgf_batch_len(b, world)) - then other < -1 or other outside the world, other == body, flags != 0 or pad != 0, a non-finite pa
+ * or pb, a beta that is not finite or outside [0, 1], a world's joint beyond its MGF_BATCH_MAX_WORLD_JOINTS-th.  The rig names
+ * (world, body) and (world, other): mgf_batch_add_bodies and mgf_batch_add_compound_bodies afterwards leave every joint on the bodies
+ * it named.  Independent of the other seven rigs. */
+MGF_API mgf_status mgf_batch_set_joints(mgf_batch* b, const mgf_batch_joint* j, int64_t n);
+MGF_API int64_t    mgf_batch_joint_count(const mgf_batch* b);               /* -1 for NULL */
+/* The joints solved (above).  Refused with MGF_ERR_INVALID, nothing enqueued and nothing changed, in this order: a NULL batch, a
+ * non-finite h, iters < 0.  iters == 0 or an empty rig: MGF_OK, nothing enqueued, impulse_out not written.  Synchronous: one download
+ * where impulse_out is given, one host wait.  MGF_ERR_HIP "internal error" behind the wait: a lane gave up waiting for its turn - a
+ * bug, never a wait for another workgroup; the world's velocities are then as the call found them. */
+MGF_API mgf_status mgf_batch_solve_joints(mgf_batch* b, float h, int32_t iters, float* impulse_out);
+/* The same with impulse_out in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for.
+ * Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls (12 bytes a
+ * joint of impulse_out_dev). */
+MGF_API mgf_status mgf_batch_solve_joints_dev(mgf_batch* b, float h, int32_t iters, float* impulse_out_dev);
 /* ---- rollout touch traces: the contact sensors' reports behind every tick of a rollout ----
  * A rollout records the STATE of chosen bodies behind every tick.  A sampling planner or a cost function also asks "did the foot
  * touch, how hard, and what touched it" at every tick of the horizon; call by call that is T host waits again.  These two calls are
@@ -1510,7 +1593,7 @@ MGF_API mgf_status mgf_batch_rollout_observe_dev(mgf_batch* b, float dt, int32_t
  * neither n_worlds nor n), "device_skipped" (records of the device-pointer calls whose index was out of range, cumulative; waits for the
  * stream), "pair_table_uploads" (uploads of mgf_batch_copy_worlds_where's pair table, cumulative), "actuators_skipped" (above),
  * "rollout_launches" (launches of the last mgf_batch_rollout / _rollout_dev / _rollout_touches / _rollout_touches_dev call beyond its
- * ticks' own, the touch trace's one a tick a pass among them - and of the last mgf_batch_rollout_observe / _observe_dev call, the sensor trace's two a tick a pass among them), "springs_skipped" (above)}. */
+ * ticks' own, the touch trace's one a tick a pass among them - and of the last mgf_batch_rollout_observe / _observe_dev call, the sensor trace's two a tick a pass among them), "springs_skipped" (above), "joints_skipped" (above)}. */
 MGF_API mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out);
 /* Options (test knobs): "cons_per_body" [4] = the constraint records per body a world's share of the storage starts with (1 .. 4096); a
  * low value makes the first busy tick outgrow it, which the re-run path then handles.  "part_queries" [0] = 0 | 1 (any other value:

@@ -70,6 +70,11 @@ class BatchSpring(C.Structure):
                 ("pb", Vec3), ("k", C.c_float), ("c", C.c_float), ("lo", C.c_float), ("hi", C.c_float), ("pad", C.c_float)]
 
 
+class BatchJoint(C.Structure):
+    _fields_ = [("world", C.c_int32), ("body", C.c_int32), ("other", C.c_int32), ("flags", C.c_uint32), ("pa", Vec3), ("beta", C.c_float),
+                ("pb", Vec3), ("pad", C.c_float)]
+
+
 class Component(C.Structure):
     _fields_ = [("tag", C.c_int32), ("p", Vec3), ("d", Vec3), ("r", C.c_float)]
 
@@ -195,6 +200,14 @@ SPRING_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("other", "<i4"), ("
 assert SPRING_DTYPE.itemsize == C.sizeof(BatchSpring) == 64
 BATCH_SPRING_LAUNCHES = 2  # MGF_BATCH_SPRING_LAUNCHES
 BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK = 2  # MGF_BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK
+# mgf_batch_joint: a ball joint between the anchor pa of body `body` and the anchor pb of body `other` of world `world` (other = -1: pb
+# is a point of the world), beta the share of the position error removed per call
+JOINT_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("other", "<i4"), ("flags", "<u4"), ("pa", "<f4", 3), ("beta", "<f4"),
+                        ("pb", "<f4", 3), ("pad", "<f4")])
+assert JOINT_DTYPE.itemsize == C.sizeof(BatchJoint) == 48
+BATCH_JOINT_LAUNCHES = 1  # MGF_BATCH_JOINT_LAUNCHES
+BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK = 1  # MGF_BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK
+BATCH_MAX_WORLD_JOINTS = 256  # MGF_BATCH_MAX_WORLD_JOINTS
 # mgf_touch_short: an entry of a rollout's touch rows in the short format - four words of mgf_touch_report
 TOUCH_SHORT_DTYPE = np.dtype([("n_contacts", "<i4"), ("partner", "<i4"), ("normal_impulse", "<f4"), ("strongest_impulse", "<f4")])
 assert TOUCH_SHORT_DTYPE.itemsize == 16
@@ -260,6 +273,7 @@ SYMBOLS = [
     "mgf_batch_rollout", "mgf_batch_rollout_dev", "mgf_batch_rollout_touches", "mgf_batch_rollout_touches_dev",
     "mgf_batch_rollout_observe", "mgf_batch_rollout_observe_dev",
     "mgf_batch_set_springs", "mgf_batch_spring_count", "mgf_batch_apply_springs", "mgf_batch_apply_springs_dev",
+    "mgf_batch_set_joints", "mgf_batch_joint_count", "mgf_batch_solve_joints", "mgf_batch_solve_joints_dev",
 ]
 
 _lib = None
@@ -464,6 +478,10 @@ def load_library():
         "mgf_batch_spring_count": (i64, [vp]),
         "mgf_batch_apply_springs": (i32, [vp, f32, vp]),
         "mgf_batch_apply_springs_dev": (i32, [vp, f32, vp]),
+        "mgf_batch_set_joints": (i32, [vp, vp, i64]),
+        "mgf_batch_joint_count": (i64, [vp]),
+        "mgf_batch_solve_joints": (i32, [vp, f32, i32, vp]),
+        "mgf_batch_solve_joints_dev": (i32, [vp, f32, i32, vp]),
         "mgf_batch_set_cameras": (i32, [vp, vp, i64]),
         "mgf_batch_camera_count": (i64, [vp]),
         "mgf_batch_camera_pixels": (i64, [vp]),
@@ -2388,6 +2406,38 @@ class WorldBatch:
         float32 [n, 12], n = spring_count(), or None - (L, A, Lb, Ab) of every spring."""
         n = max(self.spring_count(), 0)
         _check(load_library().mgf_batch_apply_springs_dev(self._h, float(h), _dev_arg(wrenches_out, "float32", 12, n, "wrenches_out")))
+
+    # ---- ball joints between bodies: a rig set once, sequential impulses over the resident velocities in one launch ------------------------
+    def set_joints(self, world, body=None, other=-1, pa=None, pb=None, beta=0.0):
+        """the batch's joint rig replaced (mgf_batch_set_joints): joint i ties the anchor pa[i] of body[i] - in the body's frame - to the
+        anchor pb[i] of other[i], both of world[i], or (other[i] = -1) to the point pb[i] of the world; beta[i] in [0, 1] is the share
+        of the gap removed per call.  Arrays, or scalars / single rows for all: the number of joints is that of the longest argument;
+        pa and pb left None stay zero.  At most BATCH_MAX_WORLD_JOINTS joints a world.  No joints (empty arrays) clears the rig.  Also
+        takes a JOINT_DTYPE array as `world`, the other arguments not read."""
+        if isinstance(world, np.ndarray) and world.dtype == JOINT_DTYPE:
+            rig = np.ascontiguousarray(world.reshape(-1))
+        else:
+            given = {key: v for key, v in dict(pa=pa, pb=pb).items() if v is not None}
+            rig = _rig_rows(JOINT_DTYPE, world=world, body=body, other=other, beta=beta, **given)
+        _check(load_library().mgf_batch_set_joints(self._h, rig.ctypes.data if len(rig) else None, len(rig)))
+
+    def joint_count(self):
+        return load_library().mgf_batch_joint_count(self._h)
+
+    def solve_joints(self, h, iters, impulses=False):
+        """`iters` sweeps of sequential impulses over every world's joints in the rig's order, from the current state of their ends:
+        the velocities of every joint's two anchor points made to agree, beta / h of their gap added (mgf_batch_solve_joints).
+        impulses=True: returns the float32 [n, 3] array of every joint's reaction over the call, in the rig's order."""
+        n = max(self.joint_count(), 0)
+        out = np.zeros((n, 3), np.float32) if impulses else None
+        _check(load_library().mgf_batch_solve_joints(self._h, float(h), int(iters), _ptr(out)))
+        return out
+
+    def solve_joints_dev(self, h, iters, impulses_dev=None):
+        """solve_joints enqueued on the context's stream and not waited for (mgf_batch_solve_joints_dev).  impulses_dev: CUDA
+        float32 [n, 3], n = joint_count(), or None - every joint's reaction over the call."""
+        n = max(self.joint_count(), 0)
+        _check(load_library().mgf_batch_solve_joints_dev(self._h, float(h), int(iters), _dev_arg(impulses_dev, "float32", 3, n, "impulses_dev")))
 
     def counter(self, name):
         v = C.c_int64()

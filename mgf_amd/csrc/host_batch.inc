@@ -105,6 +105,7 @@ struct mgf_batch {
   BatchRig<mgf_batch_feeler> feelers;   // on the device: items | records | order | worlds - the feelers (host_batch_feeler.inc)
   BatchRig<mgf_batch_actuator> actuators;  // on the device: runs | records | order - the actuators; `items` holds the runs of one body (host_batch_actuator.inc)
   BatchRig<mgf_batch_spring> springs;   // on the device: runs | records | order - the springs; `items` holds the runs of one body's ENDS, `order` the ends (host_batch_spring.inc)
+  BatchRig<mgf_batch_joint> joints;     // on the device: items | records | plan, slots - the ball joints; `items` holds a world's joints each, `order` the plan and the slots (host_batch_joint.inc)
   // ... and what a call on one of them has nowhere else to put
   DBuf<float> s_parts;                  // the particles of a sensor cast: 7 words a sensor
   size_t c_pixels = 0;                  // the pixels of the camera rig, camera by camera
@@ -117,6 +118,8 @@ struct mgf_batch {
   DBuf<unsigned long long> a_skipped;   // actuators whose gain * clamp(u) was not finite, cumulative (counter "actuators_skipped")
   DBuf<float> sp_wr;                    // the impulses of the springs, twelve floats a spring: written by one launch of a call, applied by the next
   DBuf<unsigned long long> sp_skipped;  // springs whose wrench was zeroed (len == 0, len or f * h not finite), cumulative (counter "springs_skipped")
+  DBuf<float> j_acc;                    // the impulses of the joints over a call, three floats a joint
+  DBuf<unsigned long long> j_skipped;   // joints that were skipped (a singular K, a word of the setup not finite), cumulative (counter "joints_skipped")
   // the rollouts (host_batch_rollout.inc)
   DBuf<uint32_t> d_act;                 // per world, beside d_done: ticks of the call whose actuation the world has behind it (k_batch_rollout.h)
   int64_t r_launches = 0;               // launches of the last rollout call beyond its ticks' own (counter "rollout_launches")
@@ -328,6 +331,12 @@ extern "C" mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, in
   if (!strcmp(name, "springs_skipped")) {  // (on the device: the stream is waited for)
     unsigned long long v = 0;
     if (b->sp_skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, b->sp_skipped.p, 1)); }
+    *out = (int64_t)v;
+    return MGF_OK;
+  }
+  if (!strcmp(name, "joints_skipped")) {  // (on the device: the stream is waited for)
+    unsigned long long v = 0;
+    if (b->j_skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, b->j_skipped.p, 1)); }
     *out = (int64_t)v;
     return MGF_OK;
   }
@@ -564,6 +573,7 @@ static void batch_rigs_stale(mgf_batch* b) {
   b->feelers.stale = true;
   b->actuators.stale = true;
   b->springs.stale = true;
+  b->joints.stale = true;
 }
 
 // the rows of `n` new bodies (empty part slots where the caller has filled none) behind world k's last body
@@ -869,6 +879,9 @@ struct BatchRolloutHook {
   bool act = false;      // the rig is not empty: k_batch_rollout_act ahead of every tick
   BatchSpringArgs S;     // the springs' two launches (k_batch_spring.h), everything but done, act and tick
   bool springs = false;  // the spring rig is not empty: they go ahead of the actuation, which a damper must not see
+  BatchJointArgs J;      // the joints' launch (k_batch_joint.h): out, h and iters; the train fills the rest in, the handle's view per PASS
+  uint32_t joint_lds = 0;  // ... and its dynamic LDS
+  bool joints = false;   // the joint rig is not empty: solved behind the actuation and ahead of the tick, which integrates what they leave
   BatchTraceTouchArgs T;  // the touch trace (k_batch_trace.h): V.out - row 0 - and n_touch; the train fills the rest in, the lists' view per PASS
   int32_t touch = -1;    // MGF_ROLLOUT_TOUCH_FULL / _SHORT: k_batch_trace_touch behind every tick's record; -1: no touch trace
   BatchSensorArgs R;     // the sensor trace's cast (k_batch_scan.h): mask, out and parts - the handle's scratch; the train fills the rest in per PASS
@@ -876,6 +889,7 @@ struct BatchRolloutHook {
   int32_t scan = -1;     // MGF_ROLLOUT_SENSOR_HIT / _DEPTH: k_batch_scan_rays and k_batch_scan_rows behind every tick's touch trace; -1: no sensor trace
   int64_t launches = 0;  // what the hook added to the train's launches
 };
+static void batch_joint_view(const mgf_batch* b, BatchJointArgs* A);  // (host_batch_joint.inc, behind this file) what the joints' kernel reads of the handle
 static uint32_t batch_touch_tile(const mgf_batch* b);  // (host_batch_touch.inc, behind this file) the words of dynamic LDS the contact sensors' fold stages
 // (host_batch_query.inc, behind this file) the dynamic LDS of a ray cast with a workgroup per work item; what a cast reads of the handle; has it obstacles to meet
 static uint32_t batch_ray_lds(const mgf_batch* b);
@@ -884,7 +898,7 @@ static bool batch_has_obstacles(const mgf_batch* b, int32_t kinds_mask);
 
 // The step's launch train, behind the refusals: n_ticks x World::step (world.rs:227-294) of every world, six (seven) launches a tick, one
 // host wait per pass - and with a hook a rollout's two launches a tick among them, the springs' two where that rig is not empty and the
-// touch trace's one and the sensor trace's two where they are asked for.
+// touch trace's one and the sensor trace's two where they are asked for, and the joints' one where that rig is not empty.
 // hook == nullptr: mgf_batch_step, launch for launch.
 static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats, BatchRolloutHook* hook) {
   MGF_TRY(batch_push(b));
@@ -929,6 +943,10 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
     A.done = b->d_done.p; A.need = b->d_need.p; A.c_count = b->d_ccount.p; A.err = b->d_err.p; A.stats = b->d_stats.p;
     A.n_worlds = K; A.iters = (uint32_t)iters;
     A.dt = dt; A.fat_margin = b->params.fat_margin; A.baumgarte = b->params.baumgarte; A.slop = b->params.penetration_slop;
+    if (hook && hook->joints) {  // (looked up again for every pass, as the views below are)
+      batch_joint_view(b, &hook->J);
+      hook->J.done = b->d_done.p; hook->J.act = b->d_act.p;
+    }
     if (hook && hook->touch >= 0) {  // (batch_allot moves the lists between passes: the view is rebuilt with BatchArgs, never kept from an earlier pass)
       BatchRig<mgf_batch_touch>& R = b->touches;
       BatchTouchArgs& V = hook->T.V;
@@ -973,6 +991,12 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
         LAUNCH_CHECK();
         ++hook->launches;
       }
+      if (hook && hook->joints) {  // (behind every external impulse and just ahead of the integration; the springs' gate: `act` moves behind the tick)
+        hook->J.tick = t;
+        k_batch_joint_solve<true><<<(unsigned)b->joints.items.size(), kBatchBlock, hook->joint_lds, s>>>(hook->J);
+        LAUNCH_CHECK();
+        hook->launches += MGF_BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK;
+      }
       if (b->parts) MGF_TRY(batch_collide_parts(b, A, nmax));
       else MGF_TRY(batch_collide(b, A, nmax));
       k_batch_setup<<<K, kBatchBlock, 12u * nmax, s>>>(A);
@@ -1004,9 +1028,10 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
       }
     }
     MGF_TRY(d2h(ctx, done.data(), b->d_done.p, K));
-    uint32_t err = 0;
-    MGF_TRY(d2h(ctx, &err, b->d_err.p, 1));
-    if (err) return fail(MGF_ERR_HIP, "internal error: a lane of the batch solver gave up waiting for its turn");
+    uint32_t err[2] = {0u, 0u};  // [0] k_batch_solve's, [1] k_batch_joint_solve's
+    MGF_TRY(d2h(ctx, err, b->d_err.p, 2));
+    if (err[0]) return fail(MGF_ERR_HIP, "internal error: a lane of the batch solver gave up waiting for its turn");
+    if (err[1]) return fail(MGF_ERR_HIP, "internal error: a lane of the joint solver gave up waiting for its turn");
     first = *std::min_element(done.begin(), done.end());
     if (first >= NT) break;
     // Solver::solve and World::step have no capacity failure (solver.rs:72-78): the worlds whose tick did not fit get what it asked for, and half again

@@ -164,6 +164,13 @@
 //                      products - into the handle's buffer; then a lane per run of one body's ends, sorted on the host when the rig
 //                      is set, applies them in list order with batch_drive_apply's arithmetic; no float atomic.  GATED: under the
 //                      rollout train's gate done[k] == tick && act[k] == tick, folded into the run length
+//   k_batch_joint_solve<GATED> (k_batch_joint.h)
+//                      ball joints between two body-fixed points, or one and a point of the world (mgf_batch_set_joints /
+//                      _solve_joints / _solve_joints_dev, and between the actuation and the tick of a rollout): sequential impulses
+//                      over the resident velocities - a workgroup per world, a lane per joint; the lane keeps its joint's arms, bias
+//                      and inverse K in registers, the world's jointed bodies sit in LDS slots, and the sweeps run in list order by
+//                      k_batch_solve's dataflow over ranks and degrees the host planned; bounded spin, no float atomic.  GATED:
+//                      under the rollout train's gate done[k] == tick && act[k] == tick, the workgroup's early return
 //   k_batch_trace_touch<FORMAT> (k_batch_trace.h)
 //                      the touch trace of a rollout (mgf_batch_rollout_touches / _touches_dev): k_batch_touch's fold of every world's
 //                      list behind tick t into row t of the reports, one launch a tick behind k_batch_rollout_record; the train's gate
@@ -213,6 +220,7 @@
 #include "k_batch_actuator.h"  // actuators: wrenches formed from the resident poses and applied, a lane per body (k_batch_actuate)
 #include "k_batch_rollout.h"  // rollouts: a row of controls ahead of every tick of a step call, a row of state behind it (k_batch_rollout_act, _record)
 #include "k_batch_spring.h"  // springs between bodies: impulses formed from the resident state, applied a lane per body (k_batch_spring_wrench, _apply)
+#include "k_batch_joint.h"  // ball joints between bodies: sequential impulses over the resident velocities, a workgroup per world (k_batch_joint_solve)
 #include "k_batch_part_query.h"  // rays, sweeps and box queries that see the parts of bodies of several components (k_batch_pq_*)
 #include "k_batch_trace.h"  // the touch trace of a rollout: the contact sensors' reports behind every tick (k_batch_trace_touch)
 #include "k_batch_scan.h"  // the sensor trace of a rollout: the ray sensors' answers behind every tick (k_batch_scan_rays, _rows)
