@@ -1249,7 +1249,8 @@ MGF_API mgf_status mgf_batch_cast_feelers_dev(mgf_batch* b, int32_t kinds_mask, 
  * per body that has an actuator walks the body's actuators in the caller's order - no float atomic, nothing depends on lane scheduling.
  * OUT OF SCOPE here: actuators on the lone mgf_world; re-evaluation of a wrench per tick inside a multi-tick mgf_batch_step (a FORCE
  * wrench stays fixed in the world's frame until the next call) (since: Rollouts, below - mgf_batch_rollout); joints and motors between two bodies (spring-dampers since: Springs
- * between bodies, below - mgf_batch_set_springs; ball joints since: Ball joints between bodies, below - mgf_batch_set_joints). */
+ * between bodies, below - mgf_batch_set_springs; ball joints since: Ball joints between bodies, below - mgf_batch_set_joints; hinges
+ * with limits and motors since: Hinge joints between bodies, below - mgf_batch_set_hinges). */
 #define MGF_ACTUATOR_TORQUE     1   /* a pure couple about d: no force, p is not read */
 #define MGF_ACTUATOR_WORLD_DIR  2   /* d is in world coordinates; the arm p stays in the body's frame */
 #define MGF_ACTUATE_IMPULSE 0
@@ -1363,7 +1364,7 @@ MGF_API mgf_status mgf_batch_rollout_dev(mgf_batch* b, float dt, int32_t iters, 
  * gets tick t's springs ONCE, as it gets its control row once, and "springs_skipped" counts as the loop's calls would.
  * mgf_batch_step itself stays World::step, launch for launch: it applies no spring.
  * OUT OF SCOPE here: hard joints and limits in the solver (ball joints in a pass of their own since: Ball joints between bodies, below -
- * mgf_batch_set_joints); springs on the lone mgf_world; springs inside mgf_batch_step; the wrenches
+ * mgf_batch_set_joints; hinges with limits since: Hinge joints between bodies, below - mgf_batch_set_hinges); springs on the lone mgf_world; springs inside mgf_batch_step; the wrenches
  * per tick of a rollout; angular (torsion) springs; rest lengths or gains driven per tick from a control row. */
 #define MGF_BATCH_SPRING_LAUNCHES 2  /* the most one call adds to "drive_launches" */
 #define MGF_BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK 2  /* what a spring rig that is not empty adds to a rollout's tick, at most */
@@ -1443,7 +1444,9 @@ MGF_API mgf_status mgf_batch_apply_springs_dev(mgf_batch* b, float h, float* wre
  * mgf_batch_step itself stays World::step, launch for launch: it applies no joint.
  * OUT OF SCOPE here: joints inside the tick's solver, coupled with the contacts in one sweep; angular rows, limits and motors (a
  * hinge is two joints); warm starting; more than MGF_BATCH_MAX_WORLD_JOINTS joints a world; joints on the lone mgf_world;
- * joints inside mgf_batch_step; the impulses per tick of a rollout; beta or anchors driven per tick from a control row. */
+ * joints inside mgf_batch_step; the impulses per tick of a rollout; beta or anchors driven per tick from a control row.
+ * (Angular rows, limits and motors since: Hinge joints between bodies, below - mgf_batch_set_hinges, whose motors are driven per tick
+ * from a table.) */
 #define MGF_BATCH_JOINT_LAUNCHES 1  /* what one solve call adds to "drive_launches" */
 #define MGF_BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK 1  /* what a joint rig that is not empty adds to a rollout's tick */
 #define MGF_BATCH_MAX_WORLD_JOINTS 256  /* joints one world holds at most */
@@ -1470,6 +1473,125 @@ MGF_API mgf_status mgf_batch_solve_joints(mgf_batch* b, float h, int32_t iters, 
  * Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls (12 bytes a
  * joint of impulse_out_dev). */
 MGF_API mgf_status mgf_batch_solve_joints_dev(mgf_batch* b, float h, int32_t iters, float* impulse_out_dev);
+/* ---- hinge joints between bodies: a point, two angular rows, a limit and a motor, solved from the resident state ----
+ * A knee, an elbow, a gripper's finger, a wheel on an axle, a door: a revolute joint with a range and a drive - the ninth rig.  A ball
+ * joint (above) leaves all three rotations free, and two of them on an axis give the axis and nothing more: no limit, so a knee folds
+ * through itself, and no motor, so a policy can only throw external wrenches that do not react on the other body.  A hinge is
+ *   - a point constraint, solved as the ball joint's;
+ *   - two angular rows that keep the hinge axis of `body` and that of `other` parallel;
+ *   - with MGF_HINGE_LIMIT a limit lo <= theta <= hi of the hinge angle;
+ *   - with MGF_HINGE_MOTOR a velocity motor: the relative speed about the axis driven to a target, the torque capped at tmax; the
+ *     target comes from a table of the handle's, a row a call (a rollout: a row a tick), so that a policy can drive it.
+ * The reference has no joint, so this is the build's own definition, as the ball joints are; no tick kernel changes and
+ * mgf_batch_step applies no hinge: the hinges are a pass of their own over the resident velocities.
+ * A hinge is a record (world, body, other, flags, pa, beta, pb, tmax, ax, cm, ua, sm, bx, ch, ub, sh): body and other indices within
+ * world (other = -1: the far end is the world); pa, ax, ua the anchor, the unit hinge axis and a unit zero-angle reference
+ * perpendicular to it in body's frame; pb, bx, ub the same in other's frame, or the world's; beta in [0, 1] the share of the
+ * position error removed per call, used by the point, angular and limit rows; tmax >= 0 the motor's largest torque (+inf allowed);
+ * (cm, sm) = (cos, sin) of mid = (lo + hi) / 2 and (ch, sh) = (cos, sin) of half = (hi - lo) / 2 in [0, pi], so sh >= 0.  With
+ * A, T1, T2 the axis, the reference and their cross product of `body` in the world and U1 the reference of `other` there (below), the
+ * hinge angle is theta = atan2(dot(U1, T2), dot(U1, T1)) - the angle of other's reference about body's axis - and its rate is
+ * dot(omega_b - omega_a, A).  NO arctangent is ever evaluated: the limit is held through the four cosines and sines of the record, so
+ * the definition uses + - * / and comparisons alone.
+ * ONE CALL, mgf_batch_solve_hinges(b, h, iters, row, impulse_out), reads what mgf_batch_solve_joints reads of each end.  Every line
+ * below is a separate rounded f32 operation, no fused multiply-add; rotate, cross, dot, M * v and invert are the ball joints' (above);
+ * a sum or product of three terms is taken left to right; -x / y is (-x) / y.
+ * SETUP, per hinge i, from the state BEFORE the call:
+ *   ra, rb, Pa, Pb, C, s = beta / h, bias, K, Kinv: the ball joint's lines, with this record's pa, pb and beta
+ *   A = rotate(q_a, ax);  T1 = rotate(q_a, ua);  T2 = cross(A, T1)
+ *   other >= 0:  B = rotate(q_b, bx);  U1 = rotate(q_b, ub)
+ *   other == -1: B = bx;  U1 = ub;  omega_b = 0;  I_b = 0
+ *   n1 = cross(B, T1);  n2 = cross(B, T2);  g1 = dot(B, T1) * s;  g2 = dot(B, T2) * s
+ *   J(n) = I_a * n + I_b * n
+ *   k11 = dot(n1, J(n1));  k12 = dot(n1, J(n2));  k21 = dot(n2, J(n1));  k22 = dot(n2, J(n2));  d2 = k11 * k22 - k12 * k21
+ *   m11 = k22 / d2;  m12 = -k12 / d2;  m21 = -k21 / d2;  m22 = k11 / d2
+ *   Km = dot(A, J(A))
+ *   c = dot(U1, T1);  sn = dot(U1, T2);  cphi = c * cm + sn * sm;  sphi = sn * cm - c * sm
+ *   LIMIT and cphi <= ch:  err = fabs(sphi) * ch - cphi * sh;  sphi >= 0: side = +1, lb = -(err * s);  else side = -1, lb = err * s
+ *   otherwise side = 0, lb = 0    (the limit row is off for this call: a limit acts from the call after the angle passed it)
+ *   MOTOR:  mmax = tmax * h;  w = entry i of the target table's row for this call (below)
+ * A hinge is SKIPPED on any of: what skips a ball joint (det == 0, a word of ra, rb, bias or Kinv not finite); d2 == 0; Km == 0 with
+ * either flag set; a word of n1, n2, g1, g2, m11, m12, m21, m22, Km or lb not finite; with MOTOR a NaN mmax or a w that is not finite.
+ * It is counted in mgf_batch_counter "hinges_skipped" (cumulative; reading it waits for the stream), touches no velocity and reports
+ * zeros - and it still takes its place in the order.
+ * SWEEPS, iters times, over the hinges of a world in the order of the array given to mgf_batch_set_hinges; worlds are independent.
+ * The rows of one hinge in this order, wd = omega_b - omega_a formed again from the current velocities ahead of each of the first
+ * three (other == -1: omega_b is the zero vector and is not written), am, al, a1, a2, acc starting from 0 with the call:
+ *   MOTOR:    lam = (w - dot(wd, A)) / Km;  t = am + lam;  if (t < -mmax) t = -mmax;  if (t > mmax) t = mmax;  lam = t - am;  am = t
+ *             imp = A * lam;  omega_a = omega_a - I_a * imp;  omega_b = omega_b + I_b * imp
+ *   side!=0:  lam = (lb - dot(wd, A)) / Km;  t = al + lam;  side < 0: if (t < 0) t = 0;  side > 0: if (t > 0) t = 0;  lam = t - al;  al = t
+ *             imp = A * lam;  the same two updates
+ *   angular:  r1 = dot(wd, n1) + g1;  r2 = dot(wd, n2) + g2;  l1 = -(m11 * r1 + m12 * r2);  l2 = -(m21 * r1 + m22 * r2)
+ *             imp = n1 * l1 + n2 * l2;  the same two updates;  a1 = a1 + l1;  a2 = a2 + l2
+ *   point:    Va = v_a + cross(omega_a, ra);  Vb = v_b + cross(omega_b, rb)  (other == -1: Vb = 0);  P = Kinv * ((Vb - Va) + bias)
+ *             v_a = v_a + P * im_a;  omega_a = omega_a + I_a * cross(ra, P)
+ *             Pn = -P;  v_b = v_b + Pn * im_b;  omega_b = omega_b + I_b * cross(rb, Pn)   (other >= 0 only);  acc = acc + P
+ * Nothing but v and omega is written; a body that no hinge names is untouched to the bit, and so is a world that no hinge names.
+ * impulse_out is optional: when given, row i receives eight floats, (acc.x, acc.y, acc.z, a1, a2, al, am, 0) - the point's reaction,
+ * the two angular impulses, the limit's and the motor's over the call.  There is no warm start: no state is kept between calls.
+ * Hinges read no shapes: a batch with bodies of several components is answered.
+ * THE TARGET TABLE.  The handle owns W[rows][mgf_batch_hinge_count] floats in device memory: mgf_batch_set_hinge_targets copies it
+ * from host memory, mgf_batch_set_hinge_targets_dev from device memory; a solve call names the row it reads.  Only hinges with MOTOR
+ * read their column.  A motor with target 0 is a brake; one with tmax = +inf and target 0 locks the angle's rate.
+ * mgf_batch_set_hinges makes the table one row of zeros.
+ * A call is MGF_BATCH_HINGE_LAUNCHES = 1 launch, counted in "drive_launches", whatever the number of hinges and worlds: a workgroup
+ * per world that has hinges, a lane per hinge - hence at most MGF_BATCH_MAX_WORLD_HINGES = 256 hinges a world - which solves all four
+ * rows of its hinge as soon as both its bodies have been through the hinges listed ahead of it; no float atomic, and the result does
+ * not depend on lane scheduling.
+ * IN A ROLLOUT.  With a hinge rig that is not empty, mgf_batch_rollout and its _dev, _touches and _observe forms become, bit for bit,
+ * the loop
+ *   [mgf_batch_apply_springs_dev(dt)] | mgf_batch_actuate_dev(u[t]) | [mgf_batch_solve_joints_dev(b, dt, iters, NULL)] |
+ *   mgf_batch_solve_hinges_dev(b, dt, iters, min(t, rows - 1), NULL) | mgf_batch_step(dt, iters, 1) | mgf_batch_gather_state_dev(row t) | [traces]
+ * - a table of one row holds its targets for the whole call, a table of T rows is a control tape, a row a tick.  Signatures, refusals
+ * and their order stay as they are; with an empty hinge rig every call is launch for launch what it was.  The hinges add
+ * MGF_BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK = 1 launch to a tick, counted in "rollout_launches".  n_act == 0 with nothing traced is
+ * then NOT mgf_batch_step.  A world whose tick is undone and run again gets tick t's hinges ONCE, and "hinges_skipped" counts as the
+ * loop's calls would.  mgf_batch_step itself stays World::step, launch for launch: it applies no hinge.
+ * OUT OF SCOPE here: hinges and ball joints in one interleaved sweep, or inside the tick's solver with the contacts; position (servo)
+ * motors, joint friction beyond a zero-target motor, prismatic and fixed joints; warm starting; limits that act speculatively before
+ * the angle passes them; more than MGF_BATCH_MAX_WORLD_HINGES hinges a world; hinges on the lone mgf_world;
+ * hinges inside mgf_batch_step; the impulses per tick of a rollout; joint angle and rate as a traced observation. */
+#define MGF_HINGE_LIMIT 1  /* the hinge angle is held to [lo, hi] through cm, sm, ch, sh */
+#define MGF_HINGE_MOTOR 2  /* the relative speed about the axis is driven to the table's target, the torque capped at tmax */
+#define MGF_BATCH_HINGE_LAUNCHES 1  /* what one solve call adds to "drive_launches" */
+#define MGF_BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK 1  /* what a hinge rig that is not empty adds to a rollout's tick */
+#define MGF_BATCH_MAX_WORLD_HINGES 256  /* hinges one world holds at most */
+typedef struct mgf_batch_hinge {
+  int32_t world, body, other; uint32_t flags;   /* other = -1: the far end is the world; flags: MGF_HINGE_LIMIT | MGF_HINGE_MOTOR */
+  mgf_vec3 pa; float beta;                      /* anchor in body's frame; Baumgarte share in [0, 1], used by the point, angular and limit rows */
+  mgf_vec3 pb; float tmax;                      /* anchor in other's frame, or the world point; the motor's largest torque, >= 0, +inf allowed */
+  mgf_vec3 ax; float cm;                        /* hinge axis in body's frame (unit); cos(mid), mid = (lo + hi) / 2 */
+  mgf_vec3 ua; float sm;                        /* zero-angle reference in body's frame, unit, perpendicular to ax; sin(mid) */
+  mgf_vec3 bx; float ch;                        /* hinge axis in other's frame, or the world's; cos(half), half = (hi - lo) / 2 in [0, pi] */
+  mgf_vec3 ub; float sh;                        /* reference in other's frame, or the world's, unit, perpendicular to bx; sin(half) >= 0 */
+} mgf_batch_hinge;                              /* 112 bytes: seven 16-byte words */
+/* Replaces the rig by a copy of j[0 .. n); n = 0 clears it; the target table becomes one row of zeros.  No device work: the rig goes
+ * up with the next call.  Refused with MGF_ERR_INVALID, the rig as it was ("the rig was not changed"), in this order: what
+ * mgf_batch_set_joints refuses up to other == body, in its order; a flag bit beyond MGF_HINGE_LIMIT | MGF_HINGE_MOTOR; a word of the
+ * record that is not finite (tmax may be +inf); beta outside [0, 1]; tmax < 0; then, in double on the host, |ax|^2, |ua|^2, |bx|^2,
+ * |ub|^2, cm^2 + sm^2 or ch^2 + sh^2 more than 1e-3 away from 1; |dot(ax, ua)| or |dot(bx, ub)| above 1e-3; sh < 0; last a world's
+ * hinge beyond its MGF_BATCH_MAX_WORLD_HINGES-th.  The rig names (world, body) and (world, other): mgf_batch_add_bodies and
+ * mgf_batch_add_compound_bodies afterwards leave every hinge on the bodies it named.  Independent of the other eight rigs. */
+MGF_API mgf_status mgf_batch_set_hinges(mgf_batch* b, const mgf_batch_hinge* j, int64_t n);
+MGF_API int64_t    mgf_batch_hinge_count(const mgf_batch* b);               /* -1 for NULL */
+/* The target table replaced by a copy of w[rows][mgf_batch_hinge_count] (host memory; one upload, waited for).  Refused with
+ * MGF_ERR_INVALID, the table as it was, in this order: a NULL batch; rows < 1 or rows > 2^20; a NULL w with a rig that is not empty; a
+ * byte count that overflows.  With an empty rig the number of rows is all that is kept. */
+MGF_API mgf_status mgf_batch_set_hinge_targets(mgf_batch* b, const float* w, int64_t rows);
+/* The same from device memory (the device-pointer calls, above): a device-to-device copy enqueued on the context's stream and NOT
+ * waited for - w_dev may be written again once the stream has passed the copy.  Also refused, nothing enqueued: a pointer that fails
+ * the look-up of the device-pointer calls (4 * rows * mgf_batch_hinge_count bytes of w_dev). */
+MGF_API mgf_status mgf_batch_set_hinge_targets_dev(mgf_batch* b, const float* w_dev, int64_t rows);
+/* The hinges solved (above), the motors' targets from row `row` of the table.  Refused with MGF_ERR_INVALID, nothing enqueued and
+ * nothing changed, in this order: a NULL batch, a non-finite h, iters < 0, row outside [0, rows).  iters == 0 or an empty rig: MGF_OK,
+ * nothing enqueued, impulse_out not written.  Synchronous: one download where impulse_out is given (32 bytes a hinge), one host wait.
+ * MGF_ERR_HIP "internal error" behind the wait: a lane gave up waiting for its turn - a bug, never a wait for another workgroup; the
+ * world's velocities are then as the call found them. */
+MGF_API mgf_status mgf_batch_solve_hinges(mgf_batch* b, float h, int32_t iters, int64_t row, float* impulse_out);
+/* The same with impulse_out in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for.
+ * Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls (32 bytes a
+ * hinge of impulse_out_dev). */
+MGF_API mgf_status mgf_batch_solve_hinges_dev(mgf_batch* b, float h, int32_t iters, int64_t row, float* impulse_out_dev);
 /* ---- rollout touch traces: the contact sensors' reports behind every tick of a rollout ----
  * A rollout records the STATE of chosen bodies behind every tick.  A sampling planner or a cost function also asks "did the foot
  * touch, how hard, and what touched it" at every tick of the horizon; call by call that is T host waits again.  These two calls are
@@ -1593,7 +1715,7 @@ MGF_API mgf_status mgf_batch_rollout_observe_dev(mgf_batch* b, float dt, int32_t
  * neither n_worlds nor n), "device_skipped" (records of the device-pointer calls whose index was out of range, cumulative; waits for the
  * stream), "pair_table_uploads" (uploads of mgf_batch_copy_worlds_where's pair table, cumulative), "actuators_skipped" (above),
  * "rollout_launches" (launches of the last mgf_batch_rollout / _rollout_dev / _rollout_touches / _rollout_touches_dev call beyond its
- * ticks' own, the touch trace's one a tick a pass among them - and of the last mgf_batch_rollout_observe / _observe_dev call, the sensor trace's two a tick a pass among them), "springs_skipped" (above), "joints_skipped" (above)}. */
+ * ticks' own, the touch trace's one a tick a pass among them - and of the last mgf_batch_rollout_observe / _observe_dev call, the sensor trace's two a tick a pass among them), "springs_skipped" (above), "joints_skipped" (above), "hinges_skipped" (above)}. */
 MGF_API mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out);
 /* Options (test knobs): "cons_per_body" [4] = the constraint records per body a world's share of the storage starts with (1 .. 4096); a
  * low value makes the first busy tick outgrow it, which the re-run path then handles.  "part_queries" [0] = 0 | 1 (any other value:

@@ -75,6 +75,12 @@ class BatchJoint(C.Structure):
                 ("pb", Vec3), ("pad", C.c_float)]
 
 
+class BatchHinge(C.Structure):
+    _fields_ = [("world", C.c_int32), ("body", C.c_int32), ("other", C.c_int32), ("flags", C.c_uint32), ("pa", Vec3), ("beta", C.c_float),
+                ("pb", Vec3), ("tmax", C.c_float), ("ax", Vec3), ("cm", C.c_float), ("ua", Vec3), ("sm", C.c_float),
+                ("bx", Vec3), ("ch", C.c_float), ("ub", Vec3), ("sh", C.c_float)]
+
+
 class Component(C.Structure):
     _fields_ = [("tag", C.c_int32), ("p", Vec3), ("d", Vec3), ("r", C.c_float)]
 
@@ -208,6 +214,18 @@ assert JOINT_DTYPE.itemsize == C.sizeof(BatchJoint) == 48
 BATCH_JOINT_LAUNCHES = 1  # MGF_BATCH_JOINT_LAUNCHES
 BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK = 1  # MGF_BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK
 BATCH_MAX_WORLD_JOINTS = 256  # MGF_BATCH_MAX_WORLD_JOINTS
+# mgf_batch_hinge: a hinge between body `body` and body `other` of world `world` (other = -1: the world) - anchors pa, pb, unit axes ax, bx
+# and unit zero-angle references ua, ub in each end's frame, beta the share of the position error removed per call, tmax the motor's
+# largest torque, (cm, sm) and (ch, sh) the cosine and sine of the limit's middle and half range
+HINGE_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("other", "<i4"), ("flags", "<u4"), ("pa", "<f4", 3), ("beta", "<f4"),
+                        ("pb", "<f4", 3), ("tmax", "<f4"), ("ax", "<f4", 3), ("cm", "<f4"), ("ua", "<f4", 3), ("sm", "<f4"),
+                        ("bx", "<f4", 3), ("ch", "<f4"), ("ub", "<f4", 3), ("sh", "<f4")])
+assert HINGE_DTYPE.itemsize == C.sizeof(BatchHinge) == 112
+HINGE_LIMIT = 1  # MGF_HINGE_LIMIT
+HINGE_MOTOR = 2  # MGF_HINGE_MOTOR
+BATCH_HINGE_LAUNCHES = 1  # MGF_BATCH_HINGE_LAUNCHES
+BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK = 1  # MGF_BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK
+BATCH_MAX_WORLD_HINGES = 256  # MGF_BATCH_MAX_WORLD_HINGES
 # mgf_touch_short: an entry of a rollout's touch rows in the short format - four words of mgf_touch_report
 TOUCH_SHORT_DTYPE = np.dtype([("n_contacts", "<i4"), ("partner", "<i4"), ("normal_impulse", "<f4"), ("strongest_impulse", "<f4")])
 assert TOUCH_SHORT_DTYPE.itemsize == 16
@@ -274,6 +292,8 @@ SYMBOLS = [
     "mgf_batch_rollout_observe", "mgf_batch_rollout_observe_dev",
     "mgf_batch_set_springs", "mgf_batch_spring_count", "mgf_batch_apply_springs", "mgf_batch_apply_springs_dev",
     "mgf_batch_set_joints", "mgf_batch_joint_count", "mgf_batch_solve_joints", "mgf_batch_solve_joints_dev",
+    "mgf_batch_set_hinges", "mgf_batch_hinge_count", "mgf_batch_set_hinge_targets", "mgf_batch_set_hinge_targets_dev",
+    "mgf_batch_solve_hinges", "mgf_batch_solve_hinges_dev",
 ]
 
 _lib = None
@@ -482,6 +502,12 @@ def load_library():
         "mgf_batch_joint_count": (i64, [vp]),
         "mgf_batch_solve_joints": (i32, [vp, f32, i32, vp]),
         "mgf_batch_solve_joints_dev": (i32, [vp, f32, i32, vp]),
+        "mgf_batch_set_hinges": (i32, [vp, vp, i64]),
+        "mgf_batch_hinge_count": (i64, [vp]),
+        "mgf_batch_set_hinge_targets": (i32, [vp, vp, i64]),
+        "mgf_batch_set_hinge_targets_dev": (i32, [vp, vp, i64]),
+        "mgf_batch_solve_hinges": (i32, [vp, f32, i32, i64, vp]),
+        "mgf_batch_solve_hinges_dev": (i32, [vp, f32, i32, i64, vp]),
         "mgf_batch_set_cameras": (i32, [vp, vp, i64]),
         "mgf_batch_camera_count": (i64, [vp]),
         "mgf_batch_camera_pixels": (i64, [vp]),
@@ -1077,6 +1103,42 @@ def _rig_rows(dtype, **fields):
     for k, v in vals.items():
         rig[k] = np.broadcast_to(v.reshape((-1,) + dtype[k].shape), (n,) + dtype[k].shape)
     return rig
+
+
+def hinge_frames(a, b, anchor_world, axis_world):
+    """pa, pb, ax, ua, bx, ub of hinges placed in the present pose: zero gap, parallel axes, theta = 0.  a: the state rows of every
+    hinge's `body` - a mapping with "x" [n, 3] and "q" [n, 4] (scalar first), and "delta" where x + delta is the pose, as state()
+    returns them; b: the same of `other`, or None where every far end is the world (a row of b whose q is all zero is the world too).
+    anchor_world [n, 3] and axis_world [n, 3] (any length but zero) in the world's frame.  Works in float64 and rounds once.  Returns
+    a dict of float32 [n, 3] arrays, ready for WorldBatch.set_hinges(**frames)."""
+    d = np.float64
+
+    def pose(s):
+        x = np.asarray(s["x"], np.float32).reshape(-1, 3)
+        names = (s.dtype.names or ()) if isinstance(s, np.ndarray) else s
+        if "delta" in names:
+            x = x + np.asarray(s["delta"], np.float32).reshape(-1, 3)      # (the state's own f32 sum, as gather_state returns it)
+        return x.astype(d), np.asarray(s["q"], d).reshape(-1, 4)
+
+    def local(x, q, p, point):
+        world = ~np.any(q != 0, axis=1)
+        s, v = q[:, 0:1], -q[:, 1:4]
+        r = p - x if point else p
+        out = np.cross(v, np.cross(v, r) + r * s) * 2.0 + r
+        return np.where(world[:, None], p, out)
+    anchor = np.asarray(anchor_world, d).reshape(-1, 3)
+    axis = np.asarray(axis_world, d).reshape(-1, 3)
+    axis = axis / np.linalg.norm(axis, axis=1, keepdims=True)
+    least = np.eye(3)[np.argmin(np.abs(axis), axis=1)]                      # the coordinate axis the hinge axis leans on least
+    ref = np.cross(axis, least)
+    ref = ref / np.linalg.norm(ref, axis=1, keepdims=True)
+    xa, qa = pose(a)
+    n = len(xa)
+    anchor, axis, ref = (np.broadcast_to(t, (n, 3)) for t in (anchor, axis, ref))
+    xb, qb = pose(b) if b is not None else (np.zeros((n, 3)), np.zeros((n, 4)))
+    out = {"pa": local(xa, qa, anchor, True), "ax": local(xa, qa, axis, False), "ua": local(xa, qa, ref, False),
+           "pb": local(xb, qb, anchor, True), "bx": local(xb, qb, axis, False), "ub": local(xb, qb, ref, False)}
+    return {k: v.astype(np.float32) for k, v in out.items()}
 
 
 def _record_k(out, k):
@@ -2438,6 +2500,68 @@ class WorldBatch:
         float32 [n, 3], n = joint_count(), or None - every joint's reaction over the call."""
         n = max(self.joint_count(), 0)
         _check(load_library().mgf_batch_solve_joints_dev(self._h, float(h), int(iters), _dev_arg(impulses_dev, "float32", 3, n, "impulses_dev")))
+
+    # ---- hinge joints between bodies: a point, two angular rows, a limit and a motor; the motors' targets a table of the handle's ------------
+    def set_hinges(self, world, body=None, other=-1, pa=None, pb=None, ax=None, ua=None, bx=None, ub=None, beta=0.0, lo=0.0, hi=0.0, tmax=0.0,
+                   limit=False, motor=False):
+        """the batch's hinge rig replaced (mgf_batch_set_hinges): hinge i ties body[i] to other[i] of world[i] (other[i] = -1: to the
+        world) at the anchors pa[i], pb[i] about the unit axes ax[i], bx[i], with the unit zero-angle references ua[i], ub[i] - each in
+        its end's frame, as hinge_frames() returns them; beta[i] in [0, 1] is the share of the position error removed per call;
+        limit[i]: the hinge angle is held to [lo[i], hi[i]] radians; motor[i]: the relative speed about the axis is driven to the
+        target table's entry (set_hinge_targets), the torque capped at tmax[i] (np.inf: no cap).  cos and sin of (lo + hi) / 2 and of
+        (hi - lo) / 2 are formed in float64 and rounded once.  Arrays, or scalars / single rows for all: the number of hinges is that
+        of the longest argument.  At most BATCH_MAX_WORLD_HINGES hinges a world.  No hinges (empty arrays) clears the rig.  The target
+        table becomes one row of zeros.  Also takes a HINGE_DTYPE array as `world`, the other arguments not read."""
+        if isinstance(world, np.ndarray) and world.dtype == HINGE_DTYPE:
+            rig = np.ascontiguousarray(world.reshape(-1))
+        else:
+            given = {key: v for key, v in dict(pa=pa, pb=pb, ax=ax, ua=ua, bx=bx, ub=ub).items() if v is not None}
+            lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+            mid, half = (lo + hi) / 2, (hi - lo) / 2
+            flags = np.asarray(limit, bool) * np.uint32(HINGE_LIMIT) + np.asarray(motor, bool) * np.uint32(HINGE_MOTOR)
+            rig = _rig_rows(HINGE_DTYPE, world=world, body=body, other=other, beta=beta, tmax=tmax, flags=flags, cm=np.cos(mid), sm=np.sin(mid),
+                            ch=np.cos(half), sh=np.sin(half), **given)
+        _check(load_library().mgf_batch_set_hinges(self._h, rig.ctypes.data if len(rig) else None, len(rig)))
+
+    def hinge_count(self):
+        return load_library().mgf_batch_hinge_count(self._h)
+
+    def set_hinge_targets(self, w):
+        """the motors' target table replaced (mgf_batch_set_hinge_targets): w float32 [rows, hinge_count()] rad/s, or one row
+        [hinge_count()].  solve_hinges names the row it reads; tick t of a rollout reads row min(t, rows - 1)."""
+        n = max(self.hinge_count(), 0)
+        w = np.ascontiguousarray(w, np.float32)
+        if w.ndim == 1:
+            w = w.reshape(1, -1)
+        if w.ndim != 2 or w.shape[1] != n:
+            raise ValueError(f"w: {w.shape} is not rows of {n} hinges")
+        _check(load_library().mgf_batch_set_hinge_targets(self._h, w.ctypes.data if w.size else None, w.shape[0]))
+
+    def set_hinge_targets_dev(self, w_dev, rows=None):
+        """set_hinge_targets from device memory, enqueued on the context's stream and not waited for (mgf_batch_set_hinge_targets_dev).
+        w_dev: CUDA float32 [rows, hinge_count()], or an integer address with `rows` given."""
+        n = max(self.hinge_count(), 0)
+        if rows is None:
+            if not hasattr(w_dev, "data_ptr") or w_dev.dim() != 2:
+                raise ValueError("w_dev: a tensor of rows of hinge_count() floats, or rows given with a raw address")
+            rows = int(w_dev.shape[0])
+        _check(load_library().mgf_batch_set_hinge_targets_dev(self._h, _dev_arg(w_dev, "float32", n, int(rows), "w_dev"), int(rows)))
+
+    def solve_hinges(self, h, iters, row=0, impulses=False):
+        """`iters` sweeps of sequential impulses over every world's hinges in the rig's order, from the current state of their ends:
+        per hinge the motor, the limit, the two angular rows and the point (mgf_batch_solve_hinges); the motors' targets are row `row`
+        of the table.  impulses=True: returns the float32 [n, 8] array (acc.x, acc.y, acc.z, a1, a2, al, am, 0) of every hinge - the
+        point's reaction, the angular impulses, the limit's and the motor's over the call - in the rig's order."""
+        n = max(self.hinge_count(), 0)
+        out = np.zeros((n, 8), np.float32) if impulses else None
+        _check(load_library().mgf_batch_solve_hinges(self._h, float(h), int(iters), int(row), _ptr(out)))
+        return out
+
+    def solve_hinges_dev(self, h, iters, row=0, impulses_dev=None):
+        """solve_hinges enqueued on the context's stream and not waited for (mgf_batch_solve_hinges_dev).  impulses_dev: CUDA
+        float32 [n, 8], n = hinge_count(), or None."""
+        n = max(self.hinge_count(), 0)
+        _check(load_library().mgf_batch_solve_hinges_dev(self._h, float(h), int(iters), int(row), _dev_arg(impulses_dev, "float32", 8, n, "impulses_dev")))
 
     def counter(self, name):
         v = C.c_int64()

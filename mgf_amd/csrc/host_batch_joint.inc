@@ -21,7 +21,9 @@
 // The records become the rig: reached only behind every check of every record - this is the first change of the rig.  R.items holds the
 // worlds' items: (world, first sorted position, count | slots << 16, first slot); R.order four words a sorted position - (the caller's
 // index, slot_a | slot_b << 16, rank_a | rank_b << 16, 0) - and behind them two words a slot: (body, deg).  No device is needed.
-static void batch_joint_plan(BatchRig<mgf_batch_joint>& R, const mgf_batch_joint* recs, size_t n) {
+// Rec: mgf_batch_joint, or mgf_batch_hinge (host_batch_hinge.inc) - the plan reads a record's world, body and other alone.
+template <class Rec>
+static void batch_joint_plan(BatchRig<Rec>& R, const Rec* recs, size_t n) {
   std::vector<uint32_t> sorted(n);
   for (size_t i = 0; i < n; ++i) sorted[i] = (uint32_t)i;
   std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t l, uint32_t r) { return recs[l].world < recs[r].world; });
@@ -40,7 +42,7 @@ static void batch_joint_plan(BatchRig<mgf_batch_joint>& R, const mgf_batch_joint
     return std::make_pair(s, rank);
   };
   for (size_t p = 0; p < n; ++p) {
-    const mgf_batch_joint& r = recs[sorted[p]];
+    const Rec& r = recs[sorted[p]];
     if (p == 0 || r.world != recs[sorted[p - 1]].world) {
       std::fill(slot_of.begin(), slot_of.end(), kJointNoSlot);
       first_slot = slots.size() / 2;

@@ -8,7 +8,8 @@
 // actuators and the traced bodies ("rollout_launches").  Both obey the train's gate world by world, and the word `act` beside `done`
 // keeps a world whose tick is run again from being actuated twice (k_batch_rollout.h).  Where the spring rig is not empty its two
 // launches (k_batch_spring.h, MGF_BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK) go ahead of the actuation under the same two words, and
-// where the joint rig is not empty its one launch (k_batch_joint.h, MGF_BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK) behind the actuation.
+// where the joint rig is not empty its one launch (k_batch_joint.h, MGF_BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK) behind the actuation,
+// and where the hinge rig is not empty its one launch (k_batch_hinge.h, MGF_BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK) behind the joints'.
 // The rig is the actuators' (BatchRig::items: no plan and no upload format of its own), the trace rows are k_batch_dev_gather's.
 // "drive_launches" is not touched.
 // The order of both calls: the refusals that need no handle, the handle's own, (device form) EVERY device pointer looked up for its
@@ -18,6 +19,8 @@
 static mgf_status batch_spring_ready(mgf_batch* b, float h, float* out_dev, BatchSpringArgs* A);
 // (host_batch_joint.inc, behind this file) the joints' arguments for the train: the rig up, the impulse buffer and the skip counter there
 static mgf_status batch_joint_ready(mgf_batch* b, float h, int32_t iters, float* out_dev, BatchJointArgs* A, uint32_t* lds);
+// (host_batch_hinge.inc, behind this file) the hinges' arguments for the train: the rig and the target table up, the impulse buffer and the skip counter there
+static mgf_status batch_hinge_ready(mgf_batch* b, float h, int32_t iters, float* out_dev, BatchHingeArgs* A, uint32_t* lds);
 
 struct RolloutBytes { size_t u, body, out[4], touch, sensor; };  // what the call touches of u, body, x, q, v, omega, touch, sensor
 // the touch trace of mgf_batch_rollout_touches / _touches_dev (host_batch_trace.inc): rows of n reports, device memory when it reaches the core.
@@ -84,7 +87,8 @@ static mgf_status batch_rollout_run(mgf_batch* b, float dt, int32_t iters, int64
   const bool touches = tt && tt->n > 0 && tt->out;
   const bool scan = ts && ts->n > 0 && ts->out;
   const bool joints = !b->joints.recs.empty();  // (the same holds for the joints: they are solved ahead of every tick)
-  if (n_ticks == 0 || (n_act == 0 && !trace && !springs && !joints && !touches && !scan)) return batch_step_run(b, dt, iters, n_ticks, stats, nullptr);
+  const bool hinges = !b->hinges.recs.empty();  // (and for the hinges, solved behind them)
+  if (n_ticks == 0 || (n_act == 0 && !trace && !springs && !joints && !hinges && !touches && !scan)) return batch_step_run(b, dt, iters, n_ticks, stats, nullptr);
   hipStream_t s = b->ctx->stream;
   BatchRig<mgf_batch_actuator>& R = b->actuators;
   MGF_TRY(batch_push(b));
@@ -124,6 +128,10 @@ static mgf_status batch_rollout_run(mgf_batch* b, float dt, int32_t iters, int64
   if (joints && iters > 0) {  // (iters == 0: mgf_batch_solve_joints_dev enqueues nothing)
     MGF_TRY(batch_joint_ready(b, dt, iters, nullptr, &H.J, &H.joint_lds));
     H.joints = true;
+  }
+  if (hinges && iters > 0) {  // (iters == 0: mgf_batch_solve_hinges_dev enqueues nothing)
+    MGF_TRY(batch_hinge_ready(b, dt, iters, nullptr, &H.G, &H.hinge_lds));
+    H.hinges = true;
   }
   if (touches) {  // (the sensors' rig up ahead of the train; the lists' view is the train's to fill, pass by pass)
     MGF_TRY(batch_rig_up(b, b->touches, "contact sensor", 3));

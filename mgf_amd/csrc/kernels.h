@@ -171,6 +171,12 @@
 //                      and inverse K in registers, the world's jointed bodies sit in LDS slots, and the sweeps run in list order by
 //                      k_batch_solve's dataflow over ranks and degrees the host planned; bounded spin, no float atomic.  GATED:
 //                      under the rollout train's gate done[k] == tick && act[k] == tick, the workgroup's early return
+//   k_batch_hinge_solve<GATED> (k_batch_hinge.h)
+//                      hinge joints (mgf_batch_set_hinges / _set_hinge_targets / _solve_hinges / _solve_hinges_dev, and behind the
+//                      ball joints of a rollout's tick): k_batch_joint_solve's launch with four rows a hinge - a velocity motor with
+//                      a torque cap, a limit of the hinge angle, two angular rows that keep the axes parallel, the point - solved in
+//                      one turn of the lane with both bodies' velocities in registers; the same plan, slots, dataflow, bounded spin
+//                      and gate; the motors' targets from a row of the handle's table
 //   k_batch_trace_touch<FORMAT> (k_batch_trace.h)
 //                      the touch trace of a rollout (mgf_batch_rollout_touches / _touches_dev): k_batch_touch's fold of every world's
 //                      list behind tick t into row t of the reports, one launch a tick behind k_batch_rollout_record; the train's gate
@@ -221,6 +227,7 @@
 #include "k_batch_rollout.h"  // rollouts: a row of controls ahead of every tick of a step call, a row of state behind it (k_batch_rollout_act, _record)
 #include "k_batch_spring.h"  // springs between bodies: impulses formed from the resident state, applied a lane per body (k_batch_spring_wrench, _apply)
 #include "k_batch_joint.h"  // ball joints between bodies: sequential impulses over the resident velocities, a workgroup per world (k_batch_joint_solve)
+#include "k_batch_hinge.h"  // hinge joints between bodies: the joints' launch with motor, limit, angular and point rows (k_batch_hinge_solve)
 #include "k_batch_part_query.h"  // rays, sweeps and box queries that see the parts of bodies of several components (k_batch_pq_*)
 #include "k_batch_trace.h"  // the touch trace of a rollout: the contact sensors' reports behind every tick (k_batch_trace_touch)
 #include "k_batch_scan.h"  // the sensor trace of a rollout: the ray sensors' answers behind every tick (k_batch_scan_rays, _rows)

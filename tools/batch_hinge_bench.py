@@ -1,0 +1,150 @@
+"""Times the hinge rig of a batch, by the method of tools/batch_joint_bench.py - K worlds of sphere_pile(8, 8, 8) after --ticks ticks,
+64 hinges a world as 16 chains of five consecutive bodies, placed by hinge_frames at the midpoint of each pair as the bodies lie when the
+rig is set (no gap, parallel axes, theta = 0), every other hinge limited to [-0.5, 0.7], the others motorised without a cap with seeded
+targets, beta = 0.2, iters = 4, the library's work on one stream, the paths rotating their order round by round, warm-up excluded, the
+median and the quartiles of --reps:
+  (a) one solve_hinges_dev(dt, 4, row 0): one launch;
+  (b) beside it, one solve_joints_dev(dt, 4) of a ball-joint rig on the same ends and anchors, on a batch of its own: one launch;
+  (c) one step(1) of that batch: the tick the hinges ride ahead of;
+  (d) rollout_dev of T = 32 ticks that traces x of 16 bodies a world, on the batch with the hinge rig and a table of T rows;
+  (e) the same rollout on a batch without a rig.
+Before the timed rounds, once and unclocked: the impulses, v and omega of (a) against the numpy restatement of the header's definition
+(tests/batch_hinge_cases.py) for the first 4 worlds, equal bytes; and the largest anchor gap |C| and axis misalignment |cross(A, B)|
+over the rig after 32 ticks of (d) and of (e), from state().  Run by hand; prints one JSON line per K."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mgf_amd  # noqa: E402
+from mgf_amd import scenes  # noqa: E402
+from tests import batch_hinge_cases as HC  # noqa: E402
+
+f32 = np.float32
+T = 32
+
+
+def full_state(b, worlds=None):
+    """what the restatement reads: state() and get()'s inverse mass and inertia, every body (or the first `worlds` worlds')"""
+    n = len(b) if worlds is None else sum(b.world_len(k) for k in range(worlds))
+    lens = [b.world_len(k) for k in range(b.n_worlds)]
+    w = np.concatenate([np.full(m, k, np.int32) for k, m in enumerate(lens)])[:n]
+    bd = np.concatenate([np.arange(m, dtype=np.int32) for m in lens])[:n]
+    st = {k: v[:n] for k, v in b.state().items()}
+    got = b.get(w, bd)
+    st["inv_mass"], st["inv_moment"] = got["inv_mass"], got["inv_moment"]
+    return st
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ks", type=int, nargs="+", default=[256])
+    ap.add_argument("--ticks", type=int, default=30)
+    ap.add_argument("--iters", type=int, default=4)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=31)
+    a = ap.parse_args()
+    ctx = mgf_amd.Context(0)
+    stream = torch.cuda.Stream()
+    ctx.set_stream(stream.cuda_stream)
+    sc = scenes.sphere_pile(8, 8, 8)
+    dt, iters, nb = float(sc["dt"]), sc["iters"], len(sc["comps"])
+    try:
+        commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], capture_output=True, text=True, cwd=os.path.dirname(os.path.abspath(__file__))).stdout.strip()
+    except OSError:
+        commit = ""
+    with torch.cuda.stream(stream):
+        for K in a.ks:
+            bh, bj, b0 = (mgf_amd.WorldBatch.from_scenes(ctx, [sc] * K) for _ in range(3))
+            for b in (bh, bj, b0):
+                b.step(dt, iters, a.ticks)
+            lens = [nb] * K
+            rig = HC.place(HC.chains_rig(K, nb), bh.state(), lens, seed=11)
+            per = len(rig) // K
+            W = np.random.default_rng(12).uniform(-1.5, 1.5, (T, len(rig))).astype(f32)
+            bh.set_hinges(rig)
+            bh.set_hinge_targets(W)
+            joints = np.zeros(len(rig), mgf_amd.JOINT_DTYPE)
+            for k in ("world", "body", "other", "pa", "pb", "beta"):
+                joints[k] = rig[k]
+            bj.set_joints(joints)
+            body = torch.from_numpy(np.concatenate([k * nb + np.arange(16) * 5 for k in range(K)]).astype(np.int32)).cuda()
+            xs = torch.empty((T, len(body), 3), dtype=torch.float32, device="cuda")
+            imp = torch.empty((len(rig), 8), dtype=torch.float32, device="cuda")
+
+            def sync():
+                stream.synchronize()
+
+            def solve_hinges():
+                bh.solve_hinges_dev(dt, a.iters, 0)
+
+            def solve_joints():
+                bj.solve_joints_dev(dt, a.iters)
+
+            def step_1():
+                bj.step(dt, iters, 1)
+
+            def rollout_hinges():
+                bh.rollout_dev(T, dt, iters, body=body, x=xs)
+
+            def rollout_plain():
+                b0.rollout_dev(T, dt, iters, body=body, x=xs)
+
+            sync()
+            # once, unclocked: (a)'s impulses and velocities against the definition restated on the host, the first 4 worlds
+            head = 4 * per
+            st4 = full_state(bh, 4)
+            imp.fill_(float("nan"))
+            bh.solve_hinges_dev(dt, a.iters, 0, impulses_dev=imp)
+            sync()
+            want = HC.solve(rig[:head], dt, a.iters, W[0, :head], st4, lens[:4])
+            after = full_state(bh, 4)
+            equal = dict(impulses=imp.cpu().numpy()[:head].tobytes() == want[2].tobytes(), v=after["v"].tobytes() == want[0].tobytes(),
+                         omega=after["omega"].tobytes() == want[1].tobytes())
+            gap0, tilt0 = float(HC.gaps(rig[:head], st4, lens[:4]).max()), float(HC.misalignment(rig[:head], st4, lens[:4]).max())
+            # ... and the gaps and misalignments behind 32 ticks with and without the hinges (b0 carries no rig: what its bodies would show)
+            rollout_hinges()
+            rollout_plain()
+            sync()
+            launches_roll = bh.counter("rollout_launches")
+            sh, s0 = bh.state(), b0.state()
+            gap_with, gap_without = HC.gaps(rig, sh, lens), HC.gaps(rig, s0, lens)
+            tilt_with, tilt_without = HC.misalignment(rig, sh, lens), HC.misalignment(rig, s0, lens)
+            th = HC.thetas(rig, sh, lens)[(rig["flags"] & HC.LIMIT) != 0]
+            fns = (solve_hinges, solve_joints, step_1, rollout_hinges, rollout_plain)
+            t = {fn.__name__: [] for fn in fns}
+            for rep in range(a.warmup + a.reps):
+                for j in range(len(fns)):
+                    fn = fns[(rep + j) % len(fns)]
+                    sync()
+                    t0 = time.perf_counter()
+                    fn()
+                    sync()
+                    if rep >= a.warmup:
+                        t[fn.__name__].append(time.perf_counter() - t0)
+            launches = {}
+            for fn, b in ((solve_hinges, bh), (solve_joints, bj)):   # (unclocked)
+                fn()
+                launches[fn.__name__] = b.counter("drive_launches")
+            sync()
+            med = {key: round(1e3 * float(np.median(val)), 4) for key, val in t.items()}
+            quart = {key: [round(1e3 * float(v_), 4) for v_ in np.percentile(val, [25, 75])] for key, val in t.items()}
+            print(json.dumps(dict(K=K, bodies_per_world=nb, hinges_per_world=per, iters=a.iters, T=T, ticks=a.ticks, reps=a.reps, gpu=torch.cuda.get_device_name(0),
+                                  commit=commit, median_ms=med, quartiles_ms=quart, drive_launches=launches, rollout_launches_with_hinges=launches_roll,
+                                  equal=equal, gap_when_set=gap0, misalignment_when_set=tilt0, max_gap_after_T_with_hinges=float(gap_with.max()),
+                                  max_gap_after_T_without=float(gap_without.max()), max_misalignment_after_T_with_hinges=float(tilt_with.max()),
+                                  max_misalignment_after_T_without=float(tilt_without.max()), limited_theta_after_T=[float(th.min()), float(th.max())],
+                                  hinges_skipped=bh.counter("hinges_skipped"), capacity_retries=[bh.counter("capacity_retries"), b0.counter("capacity_retries")])), flush=True)
+            del bh, bj, b0
+    stream.synchronize()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
