@@ -1550,7 +1550,9 @@ MGF_API mgf_status mgf_batch_solve_joints_dev(mgf_batch* b, float h, int32_t ite
  * OUT OF SCOPE here: hinges and ball joints in one interleaved sweep, or inside the tick's solver with the contacts; position (servo)
  * motors, joint friction beyond a zero-target motor, prismatic and fixed joints; warm starting; limits that act speculatively before
  * the angle passes them; more than MGF_BATCH_MAX_WORLD_HINGES hinges a world; hinges on the lone mgf_world;
- * hinges inside mgf_batch_step; the impulses per tick of a rollout; joint angle and rate as a traced observation. */
+ * hinges inside mgf_batch_step; the impulses per tick of a rollout; joint angle and rate as a traced observation.
+ * (The impulses per tick, and angle and rate as a call and as a traced observation since: Hinge encoders, below -
+ * mgf_batch_read_hinges, mgf_batch_set_hinge_trace.) */
 #define MGF_HINGE_LIMIT 1  /* the hinge angle is held to [lo, hi] through cm, sm, ch, sh */
 #define MGF_HINGE_MOTOR 2  /* the relative speed about the axis is driven to the table's target, the torque capped at tmax */
 #define MGF_BATCH_HINGE_LAUNCHES 1  /* what one solve call adds to "drive_launches" */
@@ -1592,6 +1594,76 @@ MGF_API mgf_status mgf_batch_solve_hinges(mgf_batch* b, float h, int32_t iters, 
  * Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls (32 bytes a
  * hinge of impulse_out_dev). */
 MGF_API mgf_status mgf_batch_solve_hinges_dev(mgf_batch* b, float h, int32_t iters, int64_t row, float* impulse_out_dev);
+/* ---- hinge encoders: angle, rate, limit side, gap and tilt of every hinge, read from the resident state and traced per tick ----
+ * A policy that drives a knee has to feel it: the hinge angle and its rate are the first two numbers a controller reads of a joint, a
+ * planner's cost wants them - and the torque the motor spent - at every tick of the horizon, and whoever tunes beta and iters wants to
+ * know how far the anchors gap and the axes tilt under load.  A READING is eight floats, 32 bytes,
+ *   (c, sn, rate, side, gap.x, gap.y, gap.z, tilt2)
+ * formed from the state AS IT STANDS by the SETUP lines of the hinge section above, verbatim, with the same helpers (rotate, cross,
+ * dot); every line below is a separate rounded f32 operation, no fused multiply-add:
+ *   ra, rb, Pa, Pb, C, A, T1, T2, B, U1: SETUP's lines (other == -1: B = bx, U1 = ub, Pb = pb, omega_b = 0)
+ *   c = dot(U1, T1);  sn = dot(U1, T2)         the hinge angle is theta = atan2(sn, c); NO arctangent is evaluated on the device
+ *   rate = dot(omega_b - omega_a, A)
+ *   cphi = c * cm + sn * sm;  sphi = sn * cm - c * sm
+ *   LIMIT and cphi <= ch:  sphi >= 0: side = +1.0f;  else side = -1.0f;  otherwise side = 0.0f
+ *                                              - whether the NEXT solve's limit row would be on, and on which side
+ *   gap = C                                    the anchors' gap in the world
+ *   e1 = dot(B, T1);  e2 = dot(B, T2);  tilt2 = e1 * e1 + e2 * e2      the squared sine of the angle between the two axes
+ * There is no division: no hinge is skipped and there is no counter.  Non-finite state gives non-finite words.  A reading reads no
+ * shapes - a batch with bodies of several components is answered - and writes nothing but its output: the state is untouched to the bit.
+ * ONE CALL, mgf_batch_read_hinges(b, out), is MGF_BATCH_HINGE_READ_LAUNCHES = 1 launch, counted in "drive_launches" as the solve's is: a
+ * lane per hinge by the caller's index over all worlds.  What set_many, mgf_batch_add_bodies or mgf_batch_set_hinges left on the host
+ * goes up first, by the path the solve uses.
+ * THE READINGS TABLE.  mgf_rollout_traces has no word left for it, so the trace mirrors the target table: targets are a table in, a
+ * row a tick; readings are a table out, a row a tick.  mgf_batch_set_hinge_trace(b, rows, format) makes the handle allocate and zero
+ * R[rows][mgf_batch_hinge_count] entries in device memory; rows == 0 frees it and turns the trace off, which is the default, and
+ * mgf_batch_set_hinges sets it back to 0 rows as it resets the target table.  An entry is
+ *   MGF_HINGE_TRACE_READING  32 bytes: the reading;
+ *   MGF_HINGE_TRACE_FULL     64 bytes: the reading, then the eight floats (acc.x, acc.y, acc.z, a1, a2, al, am, 0) of tick t's hinge
+ *                            solve - am / dt is the torque the motor applied in tick t, al / dt the limit's.
+ * IN A ROLLOUT.  With a hinge rig that is not empty and rows > 0, mgf_batch_rollout and its _dev, _touches, _touches_dev, _observe and
+ * _observe_dev forms - no new entry point, no changed signature - are the defining loop of the hinge section with one more line at the
+ * end of tick t < rows:
+ *   ... | mgf_batch_step(dt, iters, 1) | mgf_batch_gather_state_dev(row t) | [traces] | mgf_batch_read_hinges_dev(b, row t)
+ * and every row is bit for bit what that loop gives; for FULL the impulse words are those of tick t's
+ * mgf_batch_solve_hinges_dev(..., impulse_out) in that loop, and zeros with iters == 0, where no solve is enqueued.  Ticks t >= rows
+ * write nothing and launch nothing - there is NO clamp: an output is never overwritten silently - and rows the call does not reach stay
+ * as they were.  The trace adds MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK = 1 launch to a tick that has a row, behind the state
+ * trace's, counted in "rollout_launches"; with rows == 0 or an empty rig every rollout is launch for launch what it was.  A world
+ * whose tick is undone and run again gets its row t in the pass in which it completes t, with the impulses of the pass that solved t.
+ * OUT OF SCOPE here: position (servo) motors; readings for ball joints; readings inside mgf_rollout_traces; a clamp or ring-buffer
+ * mode of the table; the lone mgf_world; hipGraph capture. */
+#define MGF_BATCH_HINGE_READ_LAUNCHES 1  /* what one read call adds to "drive_launches" */
+#define MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK 1  /* what the readings table adds to a rollout's tick t < rows */
+#define MGF_HINGE_TRACE_READING 0  /* an entry of the table is the 32-byte reading */
+#define MGF_HINGE_TRACE_FULL 1     /* 64 bytes: the reading and the eight impulse words of the tick's hinge solve */
+typedef struct mgf_hinge_reading {
+  float c, sn;     /* cosine and sine of the hinge angle: theta = atan2(sn, c) */
+  float rate;      /* dot(omega_b - omega_a, A), rad/s */
+  float side;      /* +1 or -1: LIMIT is set and the angle is past hi or lo - the next solve's limit row is on; 0: it is off */
+  mgf_vec3 gap;    /* Pb - Pa, the anchors' gap in the world */
+  float tilt2;     /* the squared sine of the angle between the two hinge axes */
+} mgf_hinge_reading;  /* 32 bytes: two 16-byte words */
+/* The readings of every hinge into out[0 .. mgf_batch_hinge_count) (host memory): one download, one host wait.  Refused with
+ * MGF_ERR_INVALID, nothing enqueued, in this order: a NULL batch; a NULL out with a rig that is not empty.  An empty rig: MGF_OK,
+ * nothing enqueued. */
+MGF_API mgf_status mgf_batch_read_hinges(mgf_batch* b, mgf_hinge_reading* out);
+/* The same with out in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for.  Also
+ * refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls (32 bytes a hinge of
+ * out_dev), or that is not aligned to 16 bytes - the readings are stored as 16-byte words. */
+MGF_API mgf_status mgf_batch_read_hinges_dev(mgf_batch* b, mgf_hinge_reading* out_dev);
+/* The readings table made rows x mgf_batch_hinge_count entries of zeros in `format`; rows == 0: freed, no trace.  Refused with
+ * MGF_ERR_INVALID, the table as it was, in this order: a NULL batch; rows < 0 or rows > 2^20; a format that is neither
+ * MGF_HINGE_TRACE_READING nor MGF_HINGE_TRACE_FULL; a byte count that overflows.  With an empty rig rows and format are all that is kept. */
+MGF_API mgf_status mgf_batch_set_hinge_trace(mgf_batch* b, int64_t rows, int32_t format);
+MGF_API int64_t    mgf_batch_hinge_trace_rows(const mgf_batch* b);          /* -1 for NULL */
+/* Rows [row0, row0 + n_rows) of the table into out (host memory, n_rows x mgf_batch_hinge_count entries of 32 or 64 bytes): one
+ * download, waited for.  Refused with MGF_ERR_INVALID, in this order: a NULL batch; row0 < 0; n_rows < 0; row0 + n_rows beyond the
+ * table's rows; a NULL out with bytes to copy. */
+MGF_API mgf_status mgf_batch_get_hinge_trace(mgf_batch* b, void* out, int64_t row0, int64_t n_rows);
+/* The same as a device-to-device copy, enqueued on the context's stream and NOT waited for.  Also refused, nothing enqueued: a pointer
+ * that fails the look-up of the device-pointer calls. */
+MGF_API mgf_status mgf_batch_get_hinge_trace_dev(mgf_batch* b, void* out_dev, int64_t row0, int64_t n_rows);
 /* ---- rollout touch traces: the contact sensors' reports behind every tick of a rollout ----
  * A rollout records the STATE of chosen bodies behind every tick.  A sampling planner or a cost function also asks "did the foot
  * touch, how hard, and what touched it" at every tick of the horizon; call by call that is T host waits again.  These two calls are

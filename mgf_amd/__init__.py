@@ -17,6 +17,7 @@ from ._capi import (MgfError, Context, Mesh, Bvh, World, WorldBatch, BATCH_MAX_B
                     BATCH_ROLLOUT_LAUNCHES_PER_TICK, SPRING_DTYPE, BATCH_SPRING_LAUNCHES, BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK,
                     JOINT_DTYPE, BATCH_JOINT_LAUNCHES, BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK, BATCH_MAX_WORLD_JOINTS,
                     HINGE_DTYPE, HINGE_LIMIT, HINGE_MOTOR, BATCH_HINGE_LAUNCHES, BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK, BATCH_MAX_WORLD_HINGES,
-                    hinge_frames,
+                    hinge_frames, HINGE_READING_DTYPE, HINGE_TRACE_FULL_DTYPE, HINGE_TRACE_READING, HINGE_TRACE_FULL, BATCH_HINGE_READ_LAUNCHES,
+                    BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK, hinge_angles,
                     TOUCH_SHORT_DTYPE, ROLLOUT_TOUCH_FULL, ROLLOUT_TOUCH_SHORT, BATCH_ROLLOUT_TOUCH_LAUNCHES_PER_TICK,
                     ROLLOUT_TRACES, ROLLOUT_SENSOR_HIT, ROLLOUT_SENSOR_DEPTH, BATCH_ROLLOUT_SENSOR_LAUNCHES_PER_TICK)

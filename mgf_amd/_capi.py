@@ -226,6 +226,16 @@ HINGE_MOTOR = 2  # MGF_HINGE_MOTOR
 BATCH_HINGE_LAUNCHES = 1  # MGF_BATCH_HINGE_LAUNCHES
 BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK = 1  # MGF_BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK
 BATCH_MAX_WORLD_HINGES = 256  # MGF_BATCH_MAX_WORLD_HINGES
+# mgf_hinge_reading: a hinge's encoder - cosine and sine of its angle, its rate, the side of its limit (+1, -1, 0: off), the anchors' gap
+# in the world and the squared sine of the angle between the two axes; HINGE_TRACE_FULL_DTYPE: an entry of the readings table in the full
+# format - the reading and the eight impulse words of the tick's hinge solve (am / dt: the motor's torque)
+HINGE_READING_DTYPE = np.dtype([("c", "<f4"), ("sn", "<f4"), ("rate", "<f4"), ("side", "<f4"), ("gap", "<f4", 3), ("tilt2", "<f4")])
+HINGE_TRACE_FULL_DTYPE = np.dtype([("c", "<f4"), ("sn", "<f4"), ("rate", "<f4"), ("side", "<f4"), ("gap", "<f4", 3), ("tilt2", "<f4"),
+                                   ("acc", "<f4", 3), ("a1", "<f4"), ("a2", "<f4"), ("al", "<f4"), ("am", "<f4"), ("pad", "<f4")])
+assert HINGE_READING_DTYPE.itemsize == 32 and HINGE_TRACE_FULL_DTYPE.itemsize == 64
+HINGE_TRACE_READING, HINGE_TRACE_FULL = 0, 1  # MGF_HINGE_TRACE_READING, _FULL
+BATCH_HINGE_READ_LAUNCHES = 1  # MGF_BATCH_HINGE_READ_LAUNCHES
+BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK = 1  # MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK
 # mgf_touch_short: an entry of a rollout's touch rows in the short format - four words of mgf_touch_report
 TOUCH_SHORT_DTYPE = np.dtype([("n_contacts", "<i4"), ("partner", "<i4"), ("normal_impulse", "<f4"), ("strongest_impulse", "<f4")])
 assert TOUCH_SHORT_DTYPE.itemsize == 16
@@ -294,6 +304,8 @@ SYMBOLS = [
     "mgf_batch_set_joints", "mgf_batch_joint_count", "mgf_batch_solve_joints", "mgf_batch_solve_joints_dev",
     "mgf_batch_set_hinges", "mgf_batch_hinge_count", "mgf_batch_set_hinge_targets", "mgf_batch_set_hinge_targets_dev",
     "mgf_batch_solve_hinges", "mgf_batch_solve_hinges_dev",
+    "mgf_batch_read_hinges", "mgf_batch_read_hinges_dev", "mgf_batch_set_hinge_trace", "mgf_batch_hinge_trace_rows",
+    "mgf_batch_get_hinge_trace", "mgf_batch_get_hinge_trace_dev",
 ]
 
 _lib = None
@@ -508,6 +520,12 @@ def load_library():
         "mgf_batch_set_hinge_targets_dev": (i32, [vp, vp, i64]),
         "mgf_batch_solve_hinges": (i32, [vp, f32, i32, i64, vp]),
         "mgf_batch_solve_hinges_dev": (i32, [vp, f32, i32, i64, vp]),
+        "mgf_batch_read_hinges": (i32, [vp, vp]),
+        "mgf_batch_read_hinges_dev": (i32, [vp, vp]),
+        "mgf_batch_set_hinge_trace": (i32, [vp, i64, i32]),
+        "mgf_batch_hinge_trace_rows": (i64, [vp]),
+        "mgf_batch_get_hinge_trace": (i32, [vp, vp, i64, i64]),
+        "mgf_batch_get_hinge_trace_dev": (i32, [vp, vp, i64, i64]),
         "mgf_batch_set_cameras": (i32, [vp, vp, i64]),
         "mgf_batch_camera_count": (i64, [vp]),
         "mgf_batch_camera_pixels": (i64, [vp]),
@@ -1103,6 +1121,13 @@ def _rig_rows(dtype, **fields):
     for k, v in vals.items():
         rig[k] = np.broadcast_to(v.reshape((-1,) + dtype[k].shape), (n,) + dtype[k].shape)
     return rig
+
+
+def hinge_angles(readings):
+    """(theta, rate) of hinge readings - a HINGE_READING_DTYPE or HINGE_TRACE_FULL_DTYPE array of any shape, as WorldBatch.read_hinges
+    and hinge_trace return them: theta = arctan2(sn, c) in float64, radians in (-pi, pi]; rate in rad/s, float64"""
+    r = np.asarray(readings)
+    return np.arctan2(r["sn"].astype(np.float64), r["c"].astype(np.float64)), r["rate"].astype(np.float64)
 
 
 def hinge_frames(a, b, anchor_world, axis_world):
@@ -2562,6 +2587,56 @@ class WorldBatch:
         float32 [n, 8], n = hinge_count(), or None."""
         n = max(self.hinge_count(), 0)
         _check(load_library().mgf_batch_solve_hinges_dev(self._h, float(h), int(iters), int(row), _dev_arg(impulses_dev, "float32", 8, n, "impulses_dev")))
+
+    # ---- hinge encoders: angle, rate, limit side, gap and tilt of every hinge; a readings table every rollout fills, a row a tick ------------
+    def read_hinges(self):
+        """the reading of every hinge from the state as it stands (mgf_batch_read_hinges): a HINGE_READING_DTYPE array [hinge_count()]
+        in the rig's order - c, sn (the angle is arctan2(sn, c): hinge_angles), rate, side (+1 / -1: the next solve's limit row is on,
+        past hi / lo; 0: off), gap (the anchors' gap in the world) and tilt2 (the squared sine of the angle between the axes).  One
+        launch, one download; the state is not touched."""
+        out = np.zeros(max(self.hinge_count(), 0), HINGE_READING_DTYPE)
+        _check(load_library().mgf_batch_read_hinges(self._h, out.ctypes.data if len(out) else None))
+        return out
+
+    def read_hinges_dev(self, out_dev):
+        """read_hinges enqueued on the context's stream and not waited for (mgf_batch_read_hinges_dev).  out_dev: CUDA float32
+        [hinge_count(), 8], or an integer address aligned to 16 bytes."""
+        n = max(self.hinge_count(), 0)
+        _check(load_library().mgf_batch_read_hinges_dev(self._h, _dev_arg(out_dev, "float32", 8, n, "out_dev")))
+
+    def set_hinge_trace(self, rows, full=False):
+        """the readings table made `rows` rows of hinge_count() entries of zeros (mgf_batch_set_hinge_trace): tick t < rows of every
+        rollout form writes row t behind the tick, later ticks write nothing.  full=True: an entry also carries the eight impulse words
+        of the tick's hinge solve (HINGE_TRACE_FULL_DTYPE; am / dt is the motor's torque).  rows = 0 frees the table: no trace, which
+        is the default and what set_hinges leaves."""
+        _check(load_library().mgf_batch_set_hinge_trace(self._h, int(rows), HINGE_TRACE_FULL if full else HINGE_TRACE_READING))
+        self._hinge_trace_full = bool(full)
+
+    def hinge_trace_rows(self):
+        return load_library().mgf_batch_hinge_trace_rows(self._h)
+
+    def _hinge_trace_span(self, row0, rows):
+        total = max(self.hinge_trace_rows(), 0)
+        rows = total - int(row0) if rows is None else int(rows)
+        if row0 < 0 or rows < 0 or row0 + rows > total:
+            raise ValueError(f"rows [{row0}, {row0 + rows}) are not rows of a table of {total}")
+        return int(row0), rows
+
+    def hinge_trace(self, row0=0, rows=None):
+        """rows [row0, row0 + rows) of the readings table (mgf_batch_get_hinge_trace; rows=None: to the table's end): an array
+        [rows, hinge_count()] of HINGE_READING_DTYPE, or of HINGE_TRACE_FULL_DTYPE where the table was set with full=True.  One
+        download, waited for."""
+        row0, rows = self._hinge_trace_span(row0, rows)
+        out = np.zeros((rows, max(self.hinge_count(), 0)), HINGE_TRACE_FULL_DTYPE if getattr(self, "_hinge_trace_full", False) else HINGE_READING_DTYPE)
+        _check(load_library().mgf_batch_get_hinge_trace(self._h, out.ctypes.data if out.size else None, row0, rows))
+        return out
+
+    def hinge_trace_dev(self, out_dev, row0=0, rows=None):
+        """hinge_trace as a device-to-device copy, enqueued on the context's stream and not waited for (mgf_batch_get_hinge_trace_dev).
+        out_dev: CUDA float32 [rows * hinge_count(), 8] - 16 with full=True - or an integer address."""
+        row0, rows = self._hinge_trace_span(row0, rows)
+        cols = 16 if getattr(self, "_hinge_trace_full", False) else 8
+        _check(load_library().mgf_batch_get_hinge_trace_dev(self._h, _dev_arg(out_dev, "float32", cols, rows * max(self.hinge_count(), 0), "out_dev"), row0, rows))
 
     def counter(self, name):
         v = C.c_int64()

@@ -126,6 +126,10 @@ struct mgf_batch {
   DBuf<float> hg_w;                     // the motors' target table, hg_rows rows of a float a hinge (mgf_batch_set_hinge_targets)
   int64_t hg_rows = 1;                  // ... its rows
   bool hg_zero = true;                  // ... and: the rig was set behind the last table - it is one row of zeros, made where the rig goes up
+  DBuf<float4> ht_tab;                  // the hinges' readings table, ht_rows rows of an entry a hinge: two words, four with the impulses (mgf_batch_set_hinge_trace)
+  int64_t ht_rows = 0;                  // ... its rows; 0: no trace (host_batch_hinge_read.inc)
+  int32_t ht_format = 0;                // ... and MGF_HINGE_TRACE_READING / _FULL
+  DBuf<float4> ht_out;                  // what the host-memory read of the hinges downloads: two words a hinge
   // the rollouts (host_batch_rollout.inc)
   DBuf<uint32_t> d_act;                 // per world, beside d_done: ticks of the call whose actuation the world has behind it (k_batch_rollout.h)
   int64_t r_launches = 0;               // launches of the last rollout call beyond its ticks' own (counter "rollout_launches")
@@ -903,10 +907,13 @@ struct BatchRolloutHook {
   BatchSensorArgs R;     // the sensor trace's cast (k_batch_scan.h): mask, out and parts - the handle's scratch; the train fills the rest in per PASS
   BatchScanRowsArgs W;   // ... and its rows: out - row 0 - and n_sensor; the train fills the rest in per PASS
   int32_t scan = -1;     // MGF_ROLLOUT_SENSOR_HIT / _DEPTH: k_batch_scan_rays and k_batch_scan_rows behind every tick's touch trace; -1: no sensor trace
+  BatchHingeReadArgs E;  // the hinge trace's launch (k_batch_hinge_read.h): n; the train fills the rest in, the handle's view per PASS, the table's row per TICK
+  int32_t hinge_read = -1;  // kHingeReadReading / _Full / _FullZero: k_batch_read_hinges behind every tick t < the table's rows; -1: no hinge trace
   int64_t launches = 0;  // what the hook added to the train's launches
 };
 static void batch_joint_view(const mgf_batch* b, BatchJointArgs* A);  // (host_batch_joint.inc, behind this file) what the joints' kernel reads of the handle
 static void batch_hinge_view(const mgf_batch* b, BatchHingeArgs* A);  // (host_batch_hinge.inc, behind this file) what the hinges' kernel reads of the handle
+static void batch_hinge_read_view(const mgf_batch* b, BatchHingeReadArgs* A);  // (host_batch_hinge_read.inc, behind this file) what the hinge trace's kernel reads of the handle
 static uint32_t batch_touch_tile(const mgf_batch* b);  // (host_batch_touch.inc, behind this file) the words of dynamic LDS the contact sensors' fold stages
 // (host_batch_query.inc, behind this file) the dynamic LDS of a ray cast with a workgroup per work item; what a cast reads of the handle; has it obstacles to meet
 static uint32_t batch_ray_lds(const mgf_batch* b);
@@ -916,7 +923,7 @@ static bool batch_has_obstacles(const mgf_batch* b, int32_t kinds_mask);
 // The step's launch train, behind the refusals: n_ticks x World::step (world.rs:227-294) of every world, six (seven) launches a tick, one
 // host wait per pass - and with a hook a rollout's two launches a tick among them, the springs' two where that rig is not empty and the
 // touch trace's one and the sensor trace's two where they are asked for, and the joints' one where that rig is not empty, and the
-// hinges' one where theirs is not.
+// hinges' one where theirs is not, and the hinge trace's one behind every tick that has a row in the readings table.
 // hook == nullptr: mgf_batch_step, launch for launch.
 static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats, BatchRolloutHook* hook) {
   MGF_TRY(batch_push(b));
@@ -968,6 +975,10 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
     if (hook && hook->hinges) {
       batch_hinge_view(b, &hook->G);
       hook->G.done = b->d_done.p; hook->G.act = b->d_act.p;
+    }
+    if (hook && hook->hinge_read >= 0) {  // (the same rule for the hinge trace: the rig, the impulse buffer and the TABLE are looked up again for every pass)
+      batch_hinge_read_view(b, &hook->E);
+      hook->E.done = b->d_done.p; hook->E.act = b->d_act.p;
     }
     if (hook && hook->touch >= 0) {  // (batch_allot moves the lists between passes: the view is rebuilt with BatchArgs, never kept from an earlier pass)
       BatchRig<mgf_batch_touch>& R = b->touches;
@@ -1054,6 +1065,17 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
         else k_batch_scan_rows<kScanHit><<<rows, kBatchBlock, 0, s>>>(hook->W);
         LAUNCH_CHECK();
         hook->launches += MGF_BATCH_ROLLOUT_SENSOR_LAUNCHES_PER_TICK;
+      }
+      if (hook && hook->hinge_read >= 0 && (int64_t)t < b->ht_rows) {  // (behind the record: act[k] is final; row t, and no launch for a tick the table has no row for)
+        BatchHingeReadArgs& E = hook->E;
+        const unsigned blocks = (E.n + kBatchBlock - 1) / kBatchBlock;
+        E.tick = t;
+        E.out = b->ht_tab.p + (size_t)t * E.n * (hook->hinge_read == kHingeReadReading ? 2u : 4u);
+        if (hook->hinge_read == kHingeReadFull) k_batch_read_hinges<true, kHingeReadFull><<<blocks, kBatchBlock, 0, s>>>(E);
+        else if (hook->hinge_read == kHingeReadFullZero) k_batch_read_hinges<true, kHingeReadFullZero><<<blocks, kBatchBlock, 0, s>>>(E);
+        else k_batch_read_hinges<true, kHingeReadReading><<<blocks, kBatchBlock, 0, s>>>(E);
+        LAUNCH_CHECK();
+        hook->launches += MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK;
       }
     }
     MGF_TRY(d2h(ctx, done.data(), b->d_done.p, K));

@@ -52,6 +52,7 @@ extern "C" mgf_status mgf_batch_set_hinges(mgf_batch* b, const mgf_batch_hinge* 
   batch_joint_plan(b->hinges, j, n);
   b->hg_rows = 1;  // (the table: one row of zeros, made where the rig goes up)
   b->hg_zero = true;
+  b->ht_rows = 0;  // (the readings table is rows of the OLD rig's hinges: the trace is off until mgf_batch_set_hinge_trace names it again)
   return MGF_OK;
 }
 

@@ -177,6 +177,13 @@
 //                      a torque cap, a limit of the hinge angle, two angular rows that keep the axes parallel, the point - solved in
 //                      one turn of the lane with both bodies' velocities in registers; the same plan, slots, dataflow, bounded spin
 //                      and gate; the motors' targets from a row of the handle's table
+//   k_batch_read_hinges<GATED, FORMAT> (k_batch_hinge_read.h; the frame lines in k_batch_hinge_frame.h)
+//                      hinge encoders (mgf_batch_read_hinges / _read_hinges_dev, and behind the record of every tick of a rollout that
+//                      has a row in the readings table - mgf_batch_set_hinge_trace): a lane per hinge by the caller's index forms the
+//                      hinge's SETUP frames from the state as it stands and writes (c, sn, rate, side, gap, tilt2) - 32 bytes, or 64
+//                      with the eight impulse words of the tick's solve behind them - with float4 stores; no plan, no LDS, no
+//                      division, no atomic, nothing written but the output.  GATED: the traces' gate done[k] == t + 1 &&
+//                      act[k] <= t + 1, the lane's own, ahead of every load of state
 //   k_batch_trace_touch<FORMAT> (k_batch_trace.h)
 //                      the touch trace of a rollout (mgf_batch_rollout_touches / _touches_dev): k_batch_touch's fold of every world's
 //                      list behind tick t into row t of the reports, one launch a tick behind k_batch_rollout_record; the train's gate
@@ -228,6 +235,7 @@
 #include "k_batch_spring.h"  // springs between bodies: impulses formed from the resident state, applied a lane per body (k_batch_spring_wrench, _apply)
 #include "k_batch_joint.h"  // ball joints between bodies: sequential impulses over the resident velocities, a workgroup per world (k_batch_joint_solve)
 #include "k_batch_hinge.h"  // hinge joints between bodies: the joints' launch with motor, limit, angular and point rows (k_batch_hinge_solve)
+#include "k_batch_hinge_read.h"  // hinge encoders: angle, rate, limit side, gap and tilt from the resident state, a lane per hinge (k_batch_read_hinges)
 #include "k_batch_part_query.h"  // rays, sweeps and box queries that see the parts of bodies of several components (k_batch_pq_*)
 #include "k_batch_trace.h"  // the touch trace of a rollout: the contact sensors' reports behind every tick (k_batch_trace_touch)
 #include "k_batch_scan.h"  // the sensor trace of a rollout: the ray sensors' answers behind every tick (k_batch_scan_rays, _rows)
