@@ -247,6 +247,10 @@ static mgf_status tick_scan(mgf_world* w, int job, const uint32_t* a, uint32_t* 
   LAUNCH_CHECK();
   return MGF_OK;
 }
+// scan_ws: per k_scan job 2 * scan_tiles status words (64 bits each) + its ticket (2 words); behind the three jobs the numbering's own
+// (option scan_fused, bit 1): room for a status word per 256 bodies and one more - nblk(n) + 1; a run is kNumSubs x 256 bodies - and its ticket
+static size_t scan_ws_num_at(const mgf_world* w) { return 3 * (2 * (size_t)w->scan_tiles + 2); }
+static size_t scan_ws_words(const mgf_world* w) { return scan_ws_num_at(w) + 2 * ((size_t)nblk(w->n) + 1) + 2; }
 // The collide phase's buffers, the cell grid's level and the clearing launch.  `early` (the fused tick, from world_begin): the
 // clearing launch is k_tick_clear - it also does k_reset_step's work and runs AHEAD of k_integrate; the collide phase that follows
 // on the same bodies finds `plan.zero_launched` and does not clear again (a re-run of the phase inside the tick does).
@@ -276,7 +280,7 @@ static mgf_status collide_prepare(mgf_world* w, bool solver_follows, bool early,
   w->list_generic = false;
   w->flow5_ok = true; w->flow5_prepped = false; w->flow6_prepped = false; w->f6_fail_known = false; w->canon_ready = false;
   w->scan_tiles = (uint32_t)(((size_t)std::max(cells, n) + 1 + kScanTile - 1) / kScanTile) + 1;
-  MGF_TRY(w->scan_ws.ensure(3 * (2 * (size_t)w->scan_tiles + 2), s));
+  MGF_TRY(w->scan_ws.ensure(scan_ws_words(w), s));
   MGF_TRY(w->cs_sums.ensure(3 * kCsSumStride, s)); MGF_TRY(w->tcn.ensure(n + 1, s)); MGF_TRY(w->front_cnt.ensure(2 * kTnRegions * kTnCntStride, s));
   MGF_TRY(w->lnodes.ensure(qlevel_offset(levels), s)); MGF_TRY(w->leaves.ensure(n, s));
   MGF_TRY(w->cell_lo.ensure((size_t)cells + 1, s)); MGF_TRY(w->cell_cnt.ensure((size_t)cells + 1, s));
@@ -303,7 +307,7 @@ static mgf_status collide_prepare(mgf_world* w, bool solver_follows, bool early,
     z.p[6] = w->word(kWTerrainWide); z.words[6] = 1;  // terrain-grid-too-wide flag
     z.p[7] = w->pair_stat.p; z.words[7] = kPairStatWords;
     z.p[16] = w->word(kWBrickSlow); z.words[16] = 1;  // queries k_pair_brick answered from global memory
-    z.p[17] = w->scan_ws.p; z.words[17] = 3 * (2 * w->scan_tiles + 2);  // the three scans' status words and tickets
+    z.p[17] = w->scan_ws.p; z.words[17] = (uint32_t)scan_ws_words(w);  // the three scans' status words and tickets, and the numbering's (k_contacts_rows_index_scan)
     z.p[18] = w->cs_sums.p; z.words[18] = ((early || !rows_done) ? 3 : 2) * kCsSumStride;  // k_terrain_contacts' two counters (and the length of the near list, unless this tick's k_integrate's tail has built it already)
     z.p[20] = w->front_cnt.p; z.words[20] = 2 * kTnRegions * kTnCntStride;                          // k_terrain_near's slot counters and partial counts
     z.p[21] = w->word(kWBigPartsOverflow); z.words[21] = 1;  // k_narrow_pairs_big: a pair of bodies of many parts with more contacts than its lists hold
@@ -607,17 +611,20 @@ static mgf_status stage_pair_search(mgf_world* w, const CollidePlan& P) {
 // the list-free front ends (contacts_fused, front_rows): from the rows to the constraint records - numbering, ContactConstraint::new - in one launch
 static mgf_status contacts_from_rows(mgf_world* w, const CollidePlan& P, float dt) {
   MGF_TRY(w->base.ensure(P.n + 1, P.s)); MGF_TRY(w->tpos.ensure(P.n + 1, P.s));
-  {
-    ScanEpilogue E;
-    memset(&E, 0, sizeof(E));
-    E.kind = 3; E.cap_a = P.cap_t; E.cap_b = P.cap_c; E.row_overflow = w->word(kWRowOverflow); E.grid_wide = P.use_grid ? w->word(kWGridWide) : nullptr;
-    E.terrain_wide = (P.front_rows && P.terrain_grid) ? w->word(kWTerrainWide) : nullptr;
-    E.wide_n = P.wide_now ? &w->sb.p->pad : nullptr;
-    E.guard = w->word(kWSkipGuard); E.sc = P.sc; E.sum_t = w->cs_sums.p; E.sum_ct = w->cs_sums.p + kCsSumStride;
-    if (P.side_terrain) { E.sum_t = w->front_cnt.p + (size_t)kTnRegions * kTnCntStride; E.sum_t_parts = kTnRegions; E.sum_t_stride = kTnCntStride; }
-    MGF_TRY(tick_scan(w, 2, w->p_cnt.p, w->base.p, nullptr, nullptr, (size_t)P.n + 1, &E, w->tcn.p));
-  }
+  // (option scan_fused, bit 1) a world of spheres with the split launch: the numbering inside k_contacts_rows_index_scan - no scan launch.  The other
+  // front ends keep the scan: k_contacts_rows_index<false>'s slot blocks and k_contacts_rows_parts' terrain blocks read base of arbitrary bodies.
+  const bool num_fused = (w->opt.scan_fused & 1) && w->opt.contacts_split && !P.front_rows && !P.side_terrain;
+  ScanEpilogue E;
+  memset(&E, 0, sizeof(E));
+  E.kind = 3; E.cap_a = P.cap_t; E.cap_b = P.cap_c; E.row_overflow = w->word(kWRowOverflow); E.grid_wide = P.use_grid ? w->word(kWGridWide) : nullptr;
+  E.terrain_wide = (P.front_rows && P.terrain_grid) ? w->word(kWTerrainWide) : nullptr;
+  E.wide_n = P.wide_now ? &w->sb.p->pad : nullptr;
+  E.guard = w->word(kWSkipGuard); E.sc = P.sc; E.sum_t = w->cs_sums.p; E.sum_ct = w->cs_sums.p + kCsSumStride;
+  if (P.side_terrain) { E.sum_t = w->front_cnt.p + (size_t)kTnRegions * kTnCntStride; E.sum_t_parts = kTnRegions; E.sum_t_stride = kTnCntStride; }
+  if (!num_fused) MGF_TRY(tick_scan(w, 2, w->p_cnt.p, w->base.p, nullptr, nullptr, (size_t)P.n + 1, &E, w->tcn.p));
   ContactsSpheres A;
+  memset(&A, 0, sizeof(A));
+  A.epi = E;
   A.sc = P.sc; A.n = P.n; A.cap_row_t = w->row_cap_t; A.cap_c = P.cap_c; A.cap_t = P.cap_t; A.t_out = w->t_out.p;
   A.rows_p = w->rows.p; A.t_cnt = w->t_cnt.p; A.p_cnt = w->p_cnt.p; A.base = w->base.p; A.tcn = w->tcn.p; A.tpos = w->tpos.p;
   A.dt = dt; A.baumgarte = w->params.baumgarte; A.slop = w->params.penetration_slop;
@@ -637,6 +644,13 @@ static mgf_status contacts_from_rows(mgf_world* w, const CollidePlan& P, float d
   }
   else if (w->opt.contacts_split) {  // the numbering now, the partner contacts' records beside the solver's table kernels or behind them (stage_links)
     if (P.front_rows) k_contacts_rows_index<false><<<A.t_blocks + nblk(P.n), kBlock, 0, P.s>>>(P.B, P.M, A);
+    else if (num_fused) {
+      uint32_t* ws = w->scan_ws.p + scan_ws_num_at(w);
+      A.base_out = w->base.p; A.num_runs = (P.n + kNumSubs * kBlock - 1) / (kNumSubs * kBlock);  // (a workgroup: kNumSubs groups of 256 bodies, one ticket)
+      A.num_status = reinterpret_cast<unsigned long long*>(ws); A.num_ticket = ws + 2 * ((size_t)nblk(P.n) + 1);
+      k_contacts_rows_index_scan<<<A.num_runs, kNumSubs * kBlock, 0, P.s>>>(P.B, P.M, A);
+      w->ts->num_fused = true;
+    }
     else k_contacts_rows_index<true><<<nblk(P.n), kBlock, 0, P.s>>>(P.B, P.M, A);
     w->rec_B = P.B; w->rec_A = A; w->rec_sph = !P.front_rows; w->records_pending = true;
   }
@@ -790,7 +804,7 @@ static mgf_status collide_enqueue(mgf_world* w, float dt, bool solver_follows = 
   w->ts->two_pass = P.two_pass;
   w->ts->tree = !P.two_pass && !P.use_grid && !P.demo;
   w->ts->big_parts = P.big;
-  w->records_pending = false; w->ts->split_fused = false; w->ts->split_alone = false;
+  w->records_pending = false; w->ts->split_fused = false; w->ts->split_alone = false; w->ts->num_fused = false;
   MGF_TRY(stage_cells(w, P));
   MGF_TRY(stage_side_terrain(w, P));
   MGF_TRY(stage_scatter(w, P));
@@ -949,7 +963,7 @@ static mgf_status collide_process(mgf_world* w, bool* retry) {
   }
   if (*retry) { w->n_cap_retries++; return MGF_OK; }
   w->n_path_ticks[0] += w->ts->brick; w->n_path_ticks[1] += w->ts->front_rows; w->n_path_ticks[2] += w->ts->contacts_fused; w->n_path_ticks[3] += w->ts->cells_early;
-  w->n_split_ticks[0] += w->ts->split_fused; w->n_split_ticks[1] += w->ts->split_alone;
+  w->n_split_ticks[0] += w->ts->split_fused; w->n_split_ticks[1] += w->ts->split_alone; w->n_scan_fused_ticks[0] += w->ts->num_fused;
   w->n_path_ticks[4] += w->ts->two_pass; w->n_path_ticks[5] += w->ts->tree; w->n_path_ticks[6] += w->ts->big_parts;
   if (w->opt.wide_list) {  // the wide bodies' limit for the ticks to come (WideSpec, k_bodies.h)
     if (w->wide_tick_on) {  // (the read-back's rmax is the largest half extent of the bodies that were NOT wide)

@@ -26,6 +26,9 @@ struct WorldOptions {
   // experiments (EXPERIMENTS.md r07): 2: as its first blocks; 3: a launch of their own on the side stream, joined behind the links; 4: a launch of their
   // own on the main stream, always (what every path without tables in the collide phase does); 0: k_contacts_rows
   int64_t contacts_split = 1;
+  // (r08) the tick's prefix sums inside their consumers' launches.  Bit 1: the constraint numbering of a world of spheres inside k_contacts_rows_index's
+  // launch (k_contacts_rows_index_scan: no k_scan<1> launch over p_cnt + tcn; needs contacts_split); 0: tick_scan(job 2), then k_contacts_rows_index<true>
+  int64_t scan_fused = 1;
   int64_t front_rows = 1;              // (r06) worlds of single-component bodies that are not all spheres: the list-free front end (k_front_rows.h; 0: candidate lists, one narrowphase launch per shape-pair type)
   int64_t front_rows_check = 0;        // tests: the faces k_terrain_near's cheap reject (comp_tri_far) drops go through the reference's tests as well; a contact among them is an internal error
   int64_t side_stream = 1;             // (r06) the terrain kernels of the list-free front end on the context's second stream, beside the pair search (0: one stream)
@@ -156,6 +159,7 @@ struct mgf_world {
   Bodies rec_B;
   ContactsSpheres rec_A;
   uint64_t n_split_ticks[2] = {0, 0};  // [0] fused into the links launch (or beside it on the side stream), [1] a launch of their own
+  uint64_t n_scan_fused_ticks[1] = {0};  // option scan_fused: [0] ticks whose constraints were numbered inside k_contacts_rows_index_scan's launch
   DBuf<float4> wide_list;
   // mgf_world_raycast_many / mgf_world_overlap_aabb_many (host_query.inc): the query's own grid and lists - nothing of the tick's is read or written
   DBuf<float4> q_bc, q_br;
@@ -307,6 +311,7 @@ struct mgf_world {
     bool two_pass = false;            // ... counted and filled its candidate lists in two passes (k_candidates)
     bool tree = false;                // ... searched its pairs in the tree (k_pair_rows), not in the cell grid
     bool split_fused = false, split_alone = false;  // ... wrote its partner records beside k_flow6_links / in a launch of their own (option contacts_split)
+    bool num_fused = false;           // ... numbered its constraints inside k_contacts_rows_index_scan's launch (option scan_fused, bit 1)
     bool big_parts = false;           // ... ran k_narrow_pairs_big / k_narrow_terrain_big (a body of more than kMaxParts components)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // the side stream's start and end inside the tick (no timing: created on first use)
     uint32_t* pin = nullptr;
@@ -431,6 +436,7 @@ static const OptionEntry kOptionTable[] = {
     {"pair_brick", &WorldOptions::pair_brick, 1, 0, nullptr, false, false},
     {"fused_contacts", &WorldOptions::fused_contacts, 1, 0, nullptr, false, false},
     {"contacts_split", &WorldOptions::contacts_split, 0, 4, "contacts_split: 0..4", false, false},
+    {"scan_fused", &WorldOptions::scan_fused, 0, 1, "scan_fused: 0..1", false, false},
     {"front_rows", &WorldOptions::front_rows, 1, 0, nullptr, false, false},
     {"front_rows_check", &WorldOptions::front_rows_check, 1, 0, nullptr, false, false},
     {"side_stream", &WorldOptions::side_stream, 1, 0, nullptr, false, false},
@@ -630,6 +636,9 @@ extern "C" mgf_status mgf_world_counter(const mgf_world* w, const char* name, in
   if (!strcmp(name, "big_parts_ticks")) { *out = (int64_t)w->n_path_ticks[6]; return MGF_OK; }
   if (!strcmp(name, "contacts_split_fused")) { *out = (int64_t)w->n_split_ticks[0]; return MGF_OK; }
   if (!strcmp(name, "contacts_split_standalone")) { *out = (int64_t)w->n_split_ticks[1]; return MGF_OK; }
+  if (!strcmp(name, "scan_fused_numbering_ticks")) { *out = (int64_t)w->n_scan_fused_ticks[0]; return MGF_OK; }
+  if (!strcmp(name, "scan_fused_look")) { *out = (int64_t)kNumLook * 64; return MGF_OK; }  // (runs per sweep of the numbering's look-back ...
+  if (!strcmp(name, "scan_fused_run")) { *out = (int64_t)kNumSubs * kBlock; return MGF_OK; }  // ... and bodies per run)
   if (!strcmp(name, "contacts_records_pending")) { *out = w->records_pending ? 1 : 0; return MGF_OK; }
   if (!strcmp(name, "max_parts")) { *out = (int64_t)w->max_parts; return MGF_OK; }
   if (!strcmp(name, "wide_ticks")) { *out = (int64_t)w->n_wide_ticks; return MGF_OK; }

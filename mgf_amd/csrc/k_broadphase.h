@@ -219,27 +219,38 @@ __device__ __forceinline__ void caps_candidates(const ScanEpilogue& E, uint32_t 
 }
 // kind 3: the scanned counts were the bodies' constraint counts themselves (contacts only in the partner rows, terrain contacts counted by
 // k_terrain_contacts): the tick's counts in one go
-__device__ __forceinline__ void caps_contacts(const ScanEpilogue& E, uint32_t c) {
-  StepCounts r;
+// ... what of it does not depend on the constraint count: the flags and the terrain sums, final once the pair search and the terrain kernels have
+// run.  (k_contacts_rows_index_scan, which numbers the constraints itself, has every block read them: no StepCounts exists when it starts.)
+struct CapsPre { uint32_t fail, mt, need_mt, ct; };
+__device__ __forceinline__ CapsPre caps_contacts_pre(const ScanEpilogue& E) {
+  CapsPre p;
   uint32_t mt = *E.sum_t;
   for (uint32_t k = 1; k < E.sum_t_parts; ++k) mt += E.sum_t[(size_t)k * E.sum_t_stride];
-  const uint32_t ct = *E.sum_ct;
-  r.need_Mt = mt; r.need_Mp = c - ct; r.need_C = c; r.need_Ct = ct;
-  r.fail = 0;
-  if (E.row_overflow && (*E.row_overflow & 4u)) { r.fail |= kFailCandCap; r.need_Mt = max(mt, 2u * E.cap_a); }  // (k_terrain_near: a region of the slots ran full)
-  if (E.row_overflow && (*E.row_overflow & 1u)) r.fail |= kFailRowOverflow;
-  if (E.row_overflow && (*E.row_overflow & 2u)) r.fail |= kFailTerrainRow;
-  if (E.grid_wide && *E.grid_wide) r.fail |= kFailGridWide;
-  if (E.terrain_wide && *E.terrain_wide) r.fail |= kFailTerrainWide;
-  if (E.wide_n && *E.wide_n > kWideCap) r.fail |= kFailWide;
-  if (*E.guard) r.fail |= kFailSkipped;
-  if (!r.fail && mt > E.cap_a) r.fail |= kFailCandCap;
-  if (!r.fail && c > E.cap_b) r.fail |= kFailConsCap;
+  p.mt = mt; p.need_mt = mt; p.ct = *E.sum_ct;
+  p.fail = 0;
+  if (E.row_overflow && (*E.row_overflow & 4u)) { p.fail |= kFailCandCap; p.need_mt = max(mt, 2u * E.cap_a); }  // (k_terrain_near: a region of the slots ran full)
+  if (E.row_overflow && (*E.row_overflow & 1u)) p.fail |= kFailRowOverflow;
+  if (E.row_overflow && (*E.row_overflow & 2u)) p.fail |= kFailTerrainRow;
+  if (E.grid_wide && *E.grid_wide) p.fail |= kFailGridWide;
+  if (E.terrain_wide && *E.terrain_wide) p.fail |= kFailTerrainWide;
+  if (E.wide_n && *E.wide_n > kWideCap) p.fail |= kFailWide;
+  if (*E.guard) p.fail |= kFailSkipped;
+  if (!p.fail && mt > E.cap_a) p.fail |= kFailCandCap;
+  return p;
+}
+// ... and the rest, once the constraints are counted
+__device__ __forceinline__ void caps_contacts_post(StepCounts* sc, uint32_t cap_c, const CapsPre& p, uint32_t c) {
+  StepCounts r;
+  const uint32_t mt = p.mt, ct = p.ct;
+  r.need_Mt = p.need_mt; r.need_Mp = c - ct; r.need_C = c; r.need_Ct = ct;
+  r.fail = p.fail;
+  if (!r.fail && c > cap_c) r.fail |= kFailConsCap;
   r.Mt = r.fail ? 0u : mt; r.Mp = r.fail ? 0u : r.need_Mp; r.C = r.fail ? 0u : c; r.Ct = r.fail ? 0u : ct;
   for (int k = 0; k < 6; ++k) r.bins[k] = 0;
   r.ct_sum = ct;
-  *E.sc = r;
+  *sc = r;
 }
+__device__ __forceinline__ void caps_contacts(const ScanEpilogue& E, uint32_t c) { caps_contacts_post(E.sc, E.cap_b, caps_contacts_pre(E), c); }
 __device__ __forceinline__ void caps_constraints(const ScanEpilogue& E, uint32_t c) {
   StepCounts* sc = E.sc;
   if (sc->fail) return;

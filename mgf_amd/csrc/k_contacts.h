@@ -1074,6 +1074,10 @@ struct ContactsSpheres {
   // by their bodies' threads one after the other (a block of bodies on the floor held the launch up: 256 threads with six slots each, the rest idle)
   uint32_t t_blocks, region_cap, regions, cnt_stride;
   const uint32_t *slot_body, *slot_cnt;
+  // (option scan_fused, bit 1: k_contacts_rows_index_scan numbers the constraints itself) the prefix it writes, a status word per run of kNumSubs x 256 bodies
+  // and the ticket (zeroed by the tick's clearing launch), the runs, and what the closing block checks the tick's sizes against
+  uint32_t* base_out; unsigned long long* num_status; uint32_t* num_ticket; uint32_t num_runs;
+  ScanEpilogue epi;
 };
 // a body's partner row -> the block's list in LDS, canonical order (entries of the window [w0, w0 + kCsEntCap))
 __device__ __forceinline__ void cs_list_row(const uint32_t* rp, uint32_t np, const uint32_t* ext, uint32_t first, uint32_t w0, uint32_t owner, uint32_t* s_j, uint16_t* s_b) {
@@ -1249,14 +1253,47 @@ __global__ __launch_bounds__(kBlock) void k_contacts_rows(Bodies B, TerrainDev M
 // blocks of k_flow6_links' launch, or as a launch of its own where no tables are built.
 // The index half: k_contacts_rows without the partner contacts' records.  The terrain contacts' records stay here (few; their slot cannot be
 // recovered from ab).  (A contact the pair test would refuse is numbered all the same: the record half raises the flag, the tick is an error.)
-template <bool SPH>
-__global__ __launch_bounds__(kBlock) void k_contacts_rows_index(Bodies B, TerrainDev M, ContactsSpheres A) {
-  __shared__ uint32_t s_j[kCsEntCap];           // the pass's partner contacts in canonical order: partner ...
-  __shared__ uint16_t s_b[kCsEntCap];           // ... and owner (the block's body)
-  __shared__ uint32_t s_cbase[kBlock];          // body -> id of its first partner constraint minus its first entry's position
-  __shared__ uint32_t s_wave[kBlock / 64];
-  if (A.sc->fail) return;  // (the scan's closing thread found a flag up or a capacity exceeded: the host re-runs the phase)
-  if (blockIdx.x < A.t_blocks) {  // ---- ContactConstraint::new for the terrain contacts (world.rs:243-251), a lane per slot
+//
+// NUM (option scan_fused, bit 1; a world of spheres, t_blocks == 0): the constraint numbering - k_scan<1> over p_cnt + tcn and its epilogue - inside
+// this launch.  A block takes a TICKET for its run of kNumSubs x 256 bodies, scans their counts, publishes the run's total in a status word and goes on to
+// list its rows (the count loads, the row loads, the ext gathers and the twelve-entry sort need no id); its first wave then sums the totals of
+// the runs before it (kNumLook x 64 status words per sweep, nearest first, up to the nearest run whose inclusive prefix is known) and publishes
+// its own inclusive prefix; the barrier ahead of the entry loop hands the block's first id to every thread.  base[i] is written as k_scan wrote
+// it, the block with the last ticket writes base[n] and the tick's StepCounts (caps_contacts).  The status words and the ticket are zeroed by
+// the tick's clearing launch.
+// Forward progress: a block waits only for status words of LOWER tickets, in one place (the sweep).  A block with a lower ticket has taken it,
+// so it is running, and it stores its total BEFORE its own sweep, behind nothing but its own loads and a barrier of its own waves: by
+// induction over the ticket every awaited word arrives, however few blocks are resident and in whatever order they start.  The sweep spins on
+// the whole wave's vote (__all), never lane by lane.
+// Failing ticks: the flags caps_contacts reads are final before the launch, so every block evaluates them (caps_contacts_pre) and, where one is
+// up, takes part in the numbering (need_C is reported) and writes nothing else.  The constraint capacity is known per block: a block whose ids
+// end beyond cap_c writes no ab / rev / degb / record; the blocks before it have written theirs, all inside the capacity - the tick fails with
+// kFailConsCap, every later kernel of it leaves at the fail word, and the re-run's clearing launch zeroes degb and the rev flag again
+// (collide_prepare's ZeroList, entries 2 and 3; collide_process reads only the StepCounts and the flag words of such a tick).
+#ifndef MGF_NUM_LOOK
+#define MGF_NUM_LOOK 4
+#endif
+#ifndef MGF_NUM_SUBS
+#define MGF_NUM_SUBS 4
+#endif
+// A ticket per 256 bodies was measured first: 1 024 returning atomics on one word are handed out at ~88 per us (MI355X_MICROARCH.md, `dequeue`), the
+// last block started 11.6 us late and the launch took 36.6 us against k_contacts_rows_index<true>'s 24.5 (profiles/r08_*, EXPERIMENTS.md).  So a
+// workgroup of the numbering launch is kNumSubs groups of 256 threads - each lists its own 256 bodies' rows in its own part of LDS, as a workgroup
+// of k_contacts_rows_index does - with ONE ticket and one status word: config 2's launch takes 256 tickets.
+constexpr int kNumSubs = MGF_NUM_SUBS;  // groups of 256 bodies per workgroup (run) of k_contacts_rows_index_scan
+constexpr int kNumLook = MGF_NUM_LOOK;  // status words per lane and sweep: 256 runs, config 2's every predecessor in one
+template <bool SPH, bool NUM>
+__device__ __forceinline__ void contacts_index_body(const Bodies& B, const TerrainDev& M, const ContactsSpheres& A) {
+  constexpr int SUBS = NUM ? kNumSubs : 1, WAVES = SUBS * kBlock / 64;
+  __shared__ uint32_t s_j[SUBS][kCsEntCap];     // the pass's partner contacts in canonical order: partner ...
+  __shared__ uint16_t s_b[SUBS][kCsEntCap];     // ... and owner (the group's body)
+  __shared__ uint32_t s_cbase[SUBS * kBlock];   // body -> id of its first partner constraint minus its first entry's position (NUM: less the block's first id)
+  __shared__ uint32_t s_wave[WAVES];
+  __shared__ uint32_t s_wave_c[WAVES];          // NUM: the waves' constraint counts, ...
+  __shared__ uint32_t s_num[2];                 // ... the block's ticket, the constraints of the runs before ...
+  __shared__ CapsPre s_pre;                     // ... and what is known of the tick's counts and fail bits before the launch
+  if (!NUM && A.sc->fail) return;  // (the scan's closing thread found a flag up or a capacity exceeded: the host re-runs the phase)
+  if (!NUM && blockIdx.x < A.t_blocks) {  // ---- ContactConstraint::new for the terrain contacts (world.rs:243-251), a lane per slot
     const uint32_t p = blockIdx.x * (uint32_t)kBlock + threadIdx.x, region = p / A.region_cap;
     if (region >= A.regions || p - region * A.region_cap >= min(A.slot_cnt[region * A.cnt_stride], A.region_cap)) return;
     const NContact in0 = A.t_out[2 * (size_t)p];
@@ -1278,28 +1315,83 @@ __global__ __launch_bounds__(kBlock) void k_contacts_rows_index(Bodies B, Terrai
     return;
   }
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const uint32_t i0 = (blockIdx.x - A.t_blocks) * (uint32_t)kBlock, i = i0 + (uint32_t)t;
+  uint32_t run_no = blockIdx.x - A.t_blocks, tick_fail = 0;
+  if (NUM) {  // the run of bodies by ticket, the flags that are final before the launch
+    if (t == 0) { s_num[0] = atomicAdd(A.num_ticket, 1u); s_pre = caps_contacts_pre(A.epi); }
+    __syncthreads();
+    run_no = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_num[0]); tick_fail = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pre.fail);
+  }
+  // (NUM: `sub` = the thread's group of 256 and `tt` its place in it; else the one group is the workgroup)
+  const int sub = t / kBlock, tt = t % kBlock, wv0 = sub * (kBlock / 64);
+  const uint32_t i0 = run_no * (uint32_t)(SUBS * kBlock) + (uint32_t)(sub * kBlock), i = i0 + (uint32_t)tt;
   uint32_t np = 0, run = 0, base_i = 0;
-  if (i < A.n) { np = A.p_cnt[i]; run = A.tcn[i]; base_i = A.base[i]; }
-  // ---- where the body's partner contacts start in the block's list
-  uint32_t inc_p = np;
+  if (i < A.n) { np = A.p_cnt[i]; run = A.tcn[i]; if (!NUM) base_i = A.base[i]; }
+  // ---- where the body's partner contacts start in the group's list (NUM: and its constraints in the block's ids)
+  uint32_t inc_p = np, inc_c = np + run;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(inc_p, o); if (lane >= o) inc_p += v; }
-  if (lane == 63) s_wave[wv] = inc_p;
+  if (NUM) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(inc_c, o); if (lane >= o) inc_c += v; }
+  }
+  if (lane == 63) { s_wave[wv] = inc_p; if (NUM) s_wave_c[wv] = inc_c; }
   __syncthreads();
-  uint32_t before_p = 0, totalp = 0;
-  for (int k = 0; k < kBlock / 64; ++k) { const uint32_t v = s_wave[k]; if (k < wv) before_p += v; totalp += v; }
-  const uint32_t excl_p = before_p + inc_p - np;
+  uint32_t before_p = 0, totalp = 0, before_c = 0, total_c = 0, totalp_max = 0;
+  for (int k = 0; k < kBlock / 64; ++k) { const uint32_t v = s_wave[wv0 + k]; if (wv0 + k < wv) before_p += v; totalp += v; }
+  totalp_max = totalp;
+  if (NUM) {
+    for (int k = 0; k < WAVES; ++k) { const uint32_t v = s_wave_c[k]; if (k < wv) before_c += v; total_c += v; }
+    for (int g = 0; g < SUBS; ++g) { uint32_t u = 0; for (int k = 0; k < kBlock / 64; ++k) u += s_wave[g * (kBlock / 64) + k]; totalp_max = max(totalp_max, u); }  // (the same in every thread: the window loop's barriers)
+  }
+  const uint32_t excl_p = before_p + inc_p - np, excl_c = before_c + inc_c - (np + run);
+  // NUM: the run's total, at once (run 0: its inclusive prefix).  The value rides in the flagged word itself: relaxed, no payload beside it.
+  if (NUM && t == 0) __hip_atomic_store(&A.num_status[run_no], (run_no == 0u ? kScanInc : kScanAgg) | (unsigned long long)total_c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const uint32_t* rp = A.rows_p + (size_t)i * kRowCap;
-  if (np) cs_list_row(rp, np, A.ext, excl_p, 0u, (uint32_t)t, s_j, s_b);
-  s_cbase[t] = base_i + run - excl_p;
+  if (np && !tick_fail) cs_list_row(rp, np, A.ext, excl_p, 0u, (uint32_t)tt, s_j[sub], s_b[sub]);
+  s_cbase[t] = (NUM ? excl_c : base_i) + run - excl_p;
+  if (NUM && wv == 0) {  // ---- the constraints of the runs before this one (the whole wave, every trip: the waits are the wave's vote)
+    uint32_t prev = 0;
+    if (run_no != 0u) {
+      int back = (int)run_no - 1;  // nearest predecessor not yet summed
+      for (;;) {
+        unsigned long long st[kNumLook];
+        for (;;) {  // (see the forward-progress argument above: words of lower tickets only, each stored ahead of its block's own sweep)
+          bool ok = true;
+#pragma unroll
+          for (int k = 0; k < kNumLook; ++k) {
+            const int idx = back - k * 64 - lane;
+            st[k] = kScanInc;  // (lanes before run 0 read as "inclusive, 0")
+            if (idx >= 0) st[k] = __hip_atomic_load(&A.num_status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ok = ok && (st[k] & kScanFlag) != 0ull;
+          }
+          if (__all(ok)) break;
+          __builtin_amdgcn_s_sleep(1);
+        }
+        int first = kNumLook * 64;  // distance of the nearest run whose inclusive prefix is known: the lane's own, then the wave's
+#pragma unroll
+        for (int k = kNumLook - 1; k >= 0; --k) if ((st[k] & kScanFlag) == kScanInc) first = k * 64 + lane;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) first = min(first, __shfl_xor(first, o));
+        first = __builtin_amdgcn_readfirstlane(first);  // (the same in every lane: the loop's exit is the wave's)
+        uint32_t u = 0;
+#pragma unroll
+        for (int k = 0; k < kNumLook; ++k) if (k * 64 + lane <= first) u += (uint32_t)(st[k] & 0xFFFFFFFFull);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) u += __shfl_xor(u, o);
+        prev += u;
+        if (first < kNumLook * 64) break;
+        back -= kNumLook * 64;
+      }
+      if (lane == 0) __hip_atomic_store(&A.num_status[run_no], kScanInc | (unsigned long long)(prev + total_c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (lane == 0) s_num[1] = prev;
+  }
   // ---- ContactConstraint::new for the terrain contacts (world.rs:243-251): the body's own thread (setup_terrain_one's work)
-  if (run && A.t_blocks == 0u) {
+  auto terrain_records = [&](uint32_t c) {
     const uint32_t nt = A.t_cnt[i], tp = A.tpos[i];
     const V3 mx = mk3(M.x[0], M.x[1], M.x[2]);
     const BodyDyn Ad = load_dyn(B.srec, i), S = static_dyn();
     const BodyPack Pa = load_pack(B, i, false);
-    uint32_t c = base_i;
     for (uint32_t a = 0; a < nt; ++a) {
       const NContact in0 = A.t_out[2 * (size_t)(tp + a)];
       const uint32_t nc = f2u(in0.lb.w);
@@ -1311,19 +1403,34 @@ __global__ __launch_bounds__(kBlock) void k_contacts_rows_index(Bodies B, Terrai
         A.ab[c] = make_uint2(i, kNone);
       }
     }
+  };
+  uint32_t first_c = 0;
+  if (!NUM) {
+    if (run && A.t_blocks == 0u) terrain_records(base_i);
+    __syncthreads();  // (the list's first pass, s_cbase)
+  } else {
+    __syncthreads();  // (... and the block's first id)
+    first_c = s_num[1];
+    base_i = first_c + excl_c;
+    if (i < A.n) A.base_out[i] = base_i;
+    if (run_no + 1u == A.num_runs && t == 0) {  // the last ticket: the closing prefix and the tick's counts (what k_scan's closing thread did)
+      A.base_out[A.n] = first_c + total_c;
+      caps_contacts_post(A.epi.sc, A.cap_c, s_pre, first_c + total_c);
+    }
+    if (tick_fail || first_c + total_c > A.cap_c || first_c + total_c < first_c) return;  // (the whole block)
+    if (run) terrain_records(base_i);  // (they need the id: behind the barrier)
   }
-  // ---- the partner contacts' ids, and their rows: the block's list, kCsEntCap entries per pass, an entry per thread
-  __syncthreads();  // (the list's first pass, s_cbase)
-  for (uint32_t w0 = 0; w0 < totalp; w0 += kCsEntCap) {
-    if (w0) {  // (rare: a block with more contacts than a pass holds lists the next window)
+  // ---- the partner contacts' ids, and their rows: the group's list, kCsEntCap entries per pass, an entry per thread
+  for (uint32_t w0 = 0; w0 < totalp_max; w0 += kCsEntCap) {  // (NUM: as many passes as the block's longest list takes - the barriers are the block's)
+    if (w0) {  // (rare: a group with more contacts than a pass holds lists the next window)
       __syncthreads();
-      if (np) cs_list_row_again(rp, np, A.ext, excl_p, w0, (uint32_t)t, s_j, s_b);
+      if (np && w0 < totalp) cs_list_row_again(rp, np, A.ext, excl_p, w0, (uint32_t)tt, s_j[sub], s_b[sub]);
       __syncthreads();
     }
-    const uint32_t m = min(totalp - w0, kCsEntCap);
-    for (uint32_t e = (uint32_t)t; e < m; e += (uint32_t)kBlock) {
-      const uint32_t b = s_b[e], j = s_j[e], ia = i0 + b;
-      const uint32_t c = s_cbase[b] + w0 + e;
+    const uint32_t m = w0 < totalp ? min(totalp - w0, kCsEntCap) : 0u;
+    for (uint32_t e = (uint32_t)tt; e < m; e += (uint32_t)kBlock) {
+      const uint32_t b = s_b[sub][e], j = s_j[sub][e], ia = i0 + b;
+      const uint32_t c = first_c + s_cbase[sub * kBlock + b] + w0 + e;
       A.ab[c] = make_uint2(ia, j);
       // body j's row of the constraints it takes part in as `b` (k_chain_rows); as `a` a body owns a contiguous id range
       const uint32_t pos = atomicAdd(&A.degb[j], 1u);
@@ -1332,6 +1439,9 @@ __global__ __launch_bounds__(kBlock) void k_contacts_rows_index(Bodies B, Terrai
     }
   }
 }
+template <bool SPH>
+__global__ __launch_bounds__(kBlock) void k_contacts_rows_index(Bodies B, TerrainDev M, ContactsSpheres A) { contacts_index_body<SPH, false>(B, M, A); }
+__global__ __launch_bounds__(kNumSubs * kBlock) void k_contacts_rows_index_scan(Bodies B, TerrainDev M, ContactsSpheres A) { contacts_index_body<true, true>(B, M, A); }
 // The record half: a thread per constraint id (the grid is sized from the list's capacity: its length is on the device).  ids are dense, so a
 // wave's 64 records are consecutive and leave as whole lines through the same LDS transpose.  Terrain constraints (b = kNone) have their records.
 template <bool SPH>

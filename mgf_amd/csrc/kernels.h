@@ -45,6 +45,11 @@
 //   k_contacts_rows_index<SPH> / k_contacts_rows_records<SPH> / k_flow6_links_records<SPH> (r07, option contacts_split)
 //                      k_contacts_rows in two: ids, (a, b), degb / rev rows and the terrain contacts' records first; the partner contacts'
 //                      records - what the solver's table kernels never read - as the last blocks of the links launch, or a launch of their own
+//   k_contacts_rows_index_scan (r08, option scan_fused)
+//                      k_contacts_rows_index<true> with the constraint numbering inside: no k_scan<1> over p_cnt + tcn ahead of it.  A
+//                      workgroup of four groups of 256 bodies takes a ticket, publishes its run's total in a status word, lists its rows,
+//                      and its first wave sums the totals of the runs before it (256 status words per sweep); the last ticket writes
+//                      base[n] and the tick's counts (caps_contacts_pre / _post).  The other front ends keep the scan launch.
 //   k_pair_wide (r06)  the few bodies whose fat box is far larger than the rest's (WideSpec, k_bodies.h: kept out of the scene
 //                      bounds and rmax by k_integrate, never partners of the grid's pair search) find their partners-to-be
 //                      from their own side: a workgroup per listed body
