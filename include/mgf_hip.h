@@ -1556,7 +1556,8 @@ MGF_API mgf_status mgf_batch_solve_joints_dev(mgf_batch* b, float h, int32_t ite
  * the angle passes them; more than MGF_BATCH_MAX_WORLD_HINGES hinges a world; hinges on the lone mgf_world;
  * hinges inside mgf_batch_step; the impulses per tick of a rollout; joint angle and rate as a traced observation.
  * (The impulses per tick, and angle and rate as a call and as a traced observation since: Hinge encoders, below -
- * mgf_batch_read_hinges, mgf_batch_set_hinge_trace.) */
+ * mgf_batch_read_hinges, mgf_batch_set_hinge_trace.  Prismatic and fixed joints since: Sliders between bodies, below -
+ * mgf_batch_set_sliders.) */
 #define MGF_HINGE_LIMIT 1  /* the hinge angle is held to [lo, hi] through cm, sm, ch, sh */
 #define MGF_HINGE_MOTOR 2  /* the relative speed about the axis is driven to the table's target, the torque capped at tmax */
 #define MGF_BATCH_HINGE_LAUNCHES 1  /* what one solve call adds to "drive_launches" */
@@ -1784,6 +1785,131 @@ MGF_API mgf_status mgf_batch_rollout_observe(mgf_batch* b, float dt, int32_t ite
 MGF_API mgf_status mgf_batch_rollout_observe_dev(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, const float* u_dev, int64_t n_act, int32_t mode,
                                                  const int32_t* body_dev, int64_t m, float* x_dev, float* q_dev, float* v_dev, float* omega_dev,
                                                  const mgf_rollout_traces* traces, mgf_step_stats* stats);
+/* ---- slider joints between bodies: three angular rows, two off-axis rows, a limit, a motor and a lock, solved from the resident state ----
+ * A gripper with parallel jaws, a lift, a telescopic leg, a suspension strut that stays on its axis, a piston - and, locked, a weld of
+ * two bodies into one: a prismatic joint with a range and a drive, the tenth rig.  A spring cannot stand in for it (it needs a
+ * stiffness the tick cannot carry and leaves five degrees of freedom open), and a hinge's free degree of freedom is the wrong one.
+ * A slider ties `body` to `other` of one world, or to the world itself with other = -1:
+ *   - three angular rows hold the frame of `other` onto the frame of `body`;
+ *   - two linear rows hold other's anchor on the axis through body's anchor;
+ *   - along that axis the anchor is free, or one of
+ *       MGF_SLIDER_LIMIT  the travel d is held to [lo, hi];
+ *       MGF_SLIDER_MOTOR  the relative speed along the axis is driven to a target from a table of the handle's, a row a call (a
+ *                         rollout: a row a tick), the force capped at fmax;
+ *       MGF_SLIDER_LOCK   the axis row is bilateral and holds d = lo: a fixed (weld) joint.  LOCK excludes the other two flags.
+ * The reference has no joint, so this is the build's own definition, as the hinges are; no tick kernel changes and mgf_batch_step
+ * applies no slider: the sliders are a pass of their own over the resident velocities.
+ * A slider is a record (world, body, other, flags, pa, beta, pb, fmax, ax, lo, ua, hi, bx, pad0, ub, pad1): body and other indices
+ * within world (other = -1: the far end is the world); pa, ax, ua the anchor, the unit slide axis and a unit reference perpendicular
+ * to it in body's frame; pb, bx, ub the same in other's frame, or the world's; beta in [0, 1] the share of the position error removed
+ * per call, used by the angular, off-axis, limit and lock rows; fmax >= 0 the motor's largest force (+inf allowed); lo <= hi the
+ * travel range in length units; pad0 = pad1 = 0.  The travel is d = dot(Pb - Pa, A): other's anchor seen from body's along body's axis.
+ * ONE CALL, mgf_batch_solve_sliders(b, h, iters, row, impulse_out), reads what mgf_batch_solve_joints reads of each end.  Every line
+ * below is a separate rounded f32 operation, no fused multiply-add; rotate, cross, dot, M * v and invert are the ball joints' (above);
+ * a sum of three terms is taken left to right; -x / y is (-x) / y; a vector times a scalar is (v.x * s, v.y * s, v.z * s).
+ * SETUP, per slider i, from the state BEFORE the call:
+ *   ra, rb, Pa, Pb, C = Pb - Pa, s = beta / h: the ball joint's lines, with this record's pa, pb and beta
+ *   (other == -1: rb = 0, Pb = pb, im_b = 0, I_b = 0, v_b = omega_b = 0 and never written)
+ *   A = rotate(q_a, ax);  T1 = rotate(q_a, ua);  T2 = cross(A, T1)
+ *   other >= 0:  B = rotate(q_b, bx);  U1 = rotate(q_b, ub)
+ *   other == -1: B = bx;  U1 = ub
+ *   U2 = cross(B, U1);  ca = ra + C;  d = dot(C, A);  ims = im_a + im_b
+ *   axis:     sA = cross(ca, A);  sB = cross(rb, A);  Km = (ims + dot(sA, I_a * sA)) + dot(sB, I_b * sB)
+ *   off-axis: pA1 = cross(ca, T1);  pB1 = cross(rb, T1);  g1 = dot(C, T1) * s;  pA2 = cross(ca, T2);  pB2 = cross(rb, T2);  g2 = dot(C, T2) * s
+ *             k11 = (ims + dot(pA1, I_a * pA1)) + dot(pB1, I_b * pB1);  k22 = (ims + dot(pA2, I_a * pA2)) + dot(pB2, I_b * pB2)
+ *             k12 = dot(pA1, I_a * pA2) + dot(pB1, I_b * pB2);  k21 = dot(pA2, I_a * pA1) + dot(pB2, I_b * pB1)
+ *             d2 = k11 * k22 - k12 * k21;  m11 = k22 / d2;  m12 = -k12 / d2;  m21 = -k21 / d2;  m22 = k11 / d2
+ *   angular:  e = ((cross(A, B) + cross(T1, U1)) + cross(T2, U2)) * 0.5;  gw = e * s;  Kw = I_a + I_b (word by word);  Kwinv = invert(Kw)
+ *   LOCK:                side = 2,  lb = (lo - d) * s
+ *   LIMIT and d < lo:    side = -1, lb = (lo - d) * s
+ *   LIMIT and d > hi:    side = +1, lb = -((d - hi) * s)
+ *   otherwise:           side = 0, lb = 0    (the limit row is off for this call: a limit acts from the call after the travel passed it)
+ *   MOTOR:  mmax = fmax * h;  w = entry i of the target table's row for this call (below)
+ * A slider is SKIPPED on any of: d2 == 0; Km == 0 with any flag set; invert(Kw) failing (det == 0); a word of ra, rb, sA, sB, pA1, pA2,
+ * pB1, pB2, g1, g2, gw, m11, m12, m21, m22, Km, Kwinv or lb not finite; with MOTOR a NaN mmax or a w that is not finite.  It is counted
+ * in mgf_batch_counter "sliders_skipped" (cumulative; reading it waits for the stream), touches no velocity and reports zeros - and it
+ * still takes its place in the order.
+ * With  rate(n, a, b) = (dot(v_b - v_a, n) + dot(omega_b, b)) - dot(omega_a, a)  the update apply(n, a, b, lam) is
+ *   v_a = v_a - n * (lam * im_a);  omega_a = omega_a - I_a * (a * lam)
+ *   v_b = v_b + n * (lam * im_b);  omega_b = omega_b + I_b * (b * lam)      (other >= 0 only)
+ * SWEEPS, iters times, over the sliders of a world in the order of the array given to mgf_batch_set_sliders; worlds are independent.
+ * The rows of one slider in this order, each reading the current velocities (other == -1: v_b and omega_b are the zero vector and are
+ * not written), am, al, aw, p1, p2 starting from 0 with the call:
+ *   MOTOR:     lam = (w - rate(A, sA, sB)) / Km;  t = am + lam;  if (t < -mmax) t = -mmax;  if (t > mmax) t = mmax;  lam = t - am;  am = t
+ *              apply(A, sA, sB, lam)
+ *   side != 0: lam = (lb - rate(A, sA, sB)) / Km;  t = al + lam;  side == -1: if (t < 0) t = 0;  side == +1: if (t > 0) t = 0;  lam = t - al;  al = t
+ *              apply(A, sA, sB, lam)
+ *   angular:   L = -(Kwinv * ((omega_b - omega_a) + gw));  omega_a = omega_a - I_a * L;  omega_b = omega_b + I_b * L;  aw = aw + L
+ *   off-axis:  r1 = rate(T1, pA1, pB1) + g1;  r2 = rate(T2, pA2, pB2) + g2;  l1 = -(m11 * r1 + m12 * r2);  l2 = -(m21 * r1 + m22 * r2)
+ *              n = T1 * l1 + T2 * l2;  v_a = v_a - n * im_a;  omega_a = omega_a - I_a * (pA1 * l1 + pA2 * l2)
+ *              v_b = v_b + n * im_b;  omega_b = omega_b + I_b * (pB1 * l1 + pB2 * l2);  p1 = p1 + l1;  p2 = p2 + l2
+ * Nothing but v and omega is written; a body that no slider names is untouched to the bit, and so is a world that no slider names.
+ * impulse_out is optional: when given, row i receives eight floats, (p1, p2, al, am, aw.x, aw.y, aw.z, 0) - the two off-axis
+ * impulses, the limit's or the lock's, the motor's and the angular impulse over the call.  There is no warm start: no state is kept
+ * between calls.  Sliders read no shapes: a batch with bodies of several components is answered.
+ * THE TARGET TABLE.  The handle owns W[rows][mgf_batch_slider_count] floats in device memory: mgf_batch_set_slider_targets copies it
+ * from host memory, mgf_batch_set_slider_targets_dev from device memory; a solve call names the row it reads.  Only sliders with MOTOR
+ * read their column.  A motor with target 0 is a brake.  mgf_batch_set_sliders makes the table one row of zeros.
+ * A call is MGF_BATCH_SLIDER_LAUNCHES = 1 launch, counted in "drive_launches", whatever the number of sliders and worlds: a workgroup
+ * per world that has sliders, a lane per slider - hence at most MGF_BATCH_MAX_WORLD_SLIDERS = 256 sliders a world - which solves all
+ * the rows of its slider as soon as both its bodies have been through the sliders listed ahead of it; no float atomic, and the result
+ * does not depend on lane scheduling.
+ * IN A ROLLOUT.  With a slider rig that is not empty, mgf_batch_rollout and its _dev, _touches and _observe forms become, bit for bit,
+ * the loop
+ *   [mgf_batch_apply_springs_dev(dt)] | mgf_batch_actuate_dev(u[t]) | [mgf_batch_solve_joints_dev(b, dt, iters, NULL)] |
+ *   [mgf_batch_solve_hinges_dev(b, dt, iters, min(t, rows - 1), NULL)] | mgf_batch_solve_sliders_dev(b, dt, iters, min(t, rows - 1), NULL) |
+ *   mgf_batch_step(dt, iters, 1) | mgf_batch_gather_state_dev(row t) | [traces]
+ * - each table with its own rows.  Signatures, refusals and their order stay as they are; with an empty slider rig every call is
+ * launch for launch what it was.  The sliders add MGF_BATCH_ROLLOUT_SLIDER_LAUNCHES_PER_TICK = 1 launch to a tick, counted in
+ * "rollout_launches".  n_act == 0 with nothing traced is then NOT mgf_batch_step.  A world whose tick is undone and run again gets
+ * tick t's sliders ONCE, and "sliders_skipped" counts as the loop's calls would.  mgf_batch_step itself stays World::step, launch for
+ * launch: it applies no slider.
+ * OUT OF SCOPE here: slider encoders - d, rate and side as a call and as a traced row (until then a caller forms d from
+ * mgf_batch_gather_state); position (servo) motors; warm starting; sliders interleaved with hinges or with the contacts in one sweep;
+ * more than MGF_BATCH_MAX_WORLD_SLIDERS sliders a world; sliders on the lone mgf_world; sliders inside mgf_batch_step. */
+#define MGF_SLIDER_LIMIT 1  /* the travel along the axis is held to [lo, hi] */
+#define MGF_SLIDER_MOTOR 2  /* the relative speed along the axis is driven to the table's target, the force capped at fmax */
+#define MGF_SLIDER_LOCK 4   /* the axis row is bilateral and holds d = lo: a weld; excludes the other two */
+#define MGF_BATCH_SLIDER_LAUNCHES 1  /* what one solve call adds to "drive_launches" */
+#define MGF_BATCH_ROLLOUT_SLIDER_LAUNCHES_PER_TICK 1  /* what a slider rig that is not empty adds to a rollout's tick */
+#define MGF_BATCH_MAX_WORLD_SLIDERS 256  /* sliders one world holds at most */
+typedef struct mgf_batch_slider {
+  int32_t world, body, other; uint32_t flags;   /* other = -1: the far end is the world; flags: MGF_SLIDER_LIMIT | MGF_SLIDER_MOTOR, or MGF_SLIDER_LOCK */
+  mgf_vec3 pa; float beta;                      /* anchor in body's frame; Baumgarte share in [0, 1], used by the angular, off-axis, limit and lock rows */
+  mgf_vec3 pb; float fmax;                      /* anchor in other's frame, or the world point; the motor's largest force, >= 0, +inf allowed */
+  mgf_vec3 ax; float lo;                        /* slide axis in body's frame (unit); the lower end of the travel - with LOCK the travel held */
+  mgf_vec3 ua; float hi;                        /* reference in body's frame, unit, perpendicular to ax; the upper end of the travel, >= lo */
+  mgf_vec3 bx; float pad0;                      /* slide axis in other's frame, or the world's (unit); pad0 = 0 */
+  mgf_vec3 ub; float pad1;                      /* reference in other's frame, or the world's, unit, perpendicular to bx; pad1 = 0 */
+} mgf_batch_slider;                             /* 112 bytes: seven 16-byte words */
+/* Replaces the rig by a copy of j[0 .. n); n = 0 clears it; the target table becomes one row of zeros.  No device work: the rig goes
+ * up with the next call.  Refused with MGF_ERR_INVALID, the rig as it was ("the rig was not changed"), in this order: what
+ * mgf_batch_set_joints refuses up to other == body, in its order; a flag bit beyond 7; MGF_SLIDER_LOCK together with MGF_SLIDER_LIMIT
+ * or MGF_SLIDER_MOTOR; a word of the record that is not finite (fmax may be +inf); pad0 or pad1 not 0; beta outside [0, 1]; fmax < 0;
+ * lo > hi; then, in double on the host, |ax|^2, |ua|^2, |bx|^2 or |ub|^2 more than 1e-3 away from 1; |dot(ax, ua)| or |dot(bx, ub)|
+ * above 1e-3; last a world's slider beyond its MGF_BATCH_MAX_WORLD_SLIDERS-th.  The rig names (world, body) and (world, other):
+ * mgf_batch_add_bodies and mgf_batch_add_compound_bodies afterwards leave every slider on the bodies it named.  Independent of the
+ * other nine rigs. */
+MGF_API mgf_status mgf_batch_set_sliders(mgf_batch* b, const mgf_batch_slider* j, int64_t n);
+MGF_API int64_t    mgf_batch_slider_count(const mgf_batch* b);              /* -1 for NULL */
+/* The target table replaced by a copy of w[rows][mgf_batch_slider_count] (host memory; one upload, waited for).  Refused with
+ * MGF_ERR_INVALID, the table as it was, in this order: a NULL batch; rows < 1 or rows > 2^20; a NULL w with a rig that is not empty; a
+ * byte count that overflows.  With an empty rig the number of rows is all that is kept. */
+MGF_API mgf_status mgf_batch_set_slider_targets(mgf_batch* b, const float* w, int64_t rows);
+/* The same from device memory (the device-pointer calls, above): a device-to-device copy enqueued on the context's stream and NOT
+ * waited for - w_dev may be written again once the stream has passed the copy.  Also refused, nothing enqueued: a pointer that fails
+ * the look-up of the device-pointer calls (4 * rows * mgf_batch_slider_count bytes of w_dev). */
+MGF_API mgf_status mgf_batch_set_slider_targets_dev(mgf_batch* b, const float* w_dev, int64_t rows);
+/* The sliders solved (above), the motors' targets from row `row` of the table.  Refused with MGF_ERR_INVALID, nothing enqueued and
+ * nothing changed, in this order: a NULL batch, a non-finite h, iters < 0, row outside [0, rows).  iters == 0 or an empty rig: MGF_OK,
+ * nothing enqueued, impulse_out not written.  Synchronous: one download where impulse_out is given (32 bytes a slider), one host wait.
+ * MGF_ERR_HIP "internal error" behind the wait: a lane gave up waiting for its turn - a bug, never a wait for another workgroup; the
+ * world's velocities are then as the call found them. */
+MGF_API mgf_status mgf_batch_solve_sliders(mgf_batch* b, float h, int32_t iters, int64_t row, float* impulse_out);
+/* The same with impulse_out in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for.
+ * Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls (32 bytes a
+ * slider of impulse_out_dev). */
+MGF_API mgf_status mgf_batch_solve_sliders_dev(mgf_batch* b, float h, int32_t iters, int64_t row, float* impulse_out_dev);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /
@@ -1791,7 +1917,7 @@ MGF_API mgf_status mgf_batch_rollout_observe_dev(mgf_batch* b, float dt, int32_t
  * neither n_worlds nor n), "device_skipped" (records of the device-pointer calls whose index was out of range, cumulative; waits for the
  * stream), "pair_table_uploads" (uploads of mgf_batch_copy_worlds_where's pair table, cumulative), "actuators_skipped" (above),
  * "rollout_launches" (launches of the last mgf_batch_rollout / _rollout_dev / _rollout_touches / _rollout_touches_dev call beyond its
- * ticks' own, the touch trace's one a tick a pass among them - and of the last mgf_batch_rollout_observe / _observe_dev call, the sensor trace's two a tick a pass among them), "springs_skipped" (above), "joints_skipped" (above), "hinges_skipped" (above)}. */
+ * ticks' own, the touch trace's one a tick a pass among them - and of the last mgf_batch_rollout_observe / _observe_dev call, the sensor trace's two a tick a pass among them), "springs_skipped" (above), "joints_skipped" (above), "hinges_skipped" (above), "sliders_skipped" (above)}. */
 MGF_API mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out);
 /* Options (test knobs): "cons_per_body" [4] = the constraint records per body a world's share of the storage starts with (1 .. 4096); a
  * low value makes the first busy tick outgrow it, which the re-run path then handles.  "part_queries" [0] = 0 | 1 (any other value:

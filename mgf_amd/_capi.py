@@ -81,6 +81,12 @@ class BatchHinge(C.Structure):
                 ("bx", Vec3), ("ch", C.c_float), ("ub", Vec3), ("sh", C.c_float)]
 
 
+class BatchSlider(C.Structure):
+    _fields_ = [("world", C.c_int32), ("body", C.c_int32), ("other", C.c_int32), ("flags", C.c_uint32), ("pa", Vec3), ("beta", C.c_float),
+                ("pb", Vec3), ("fmax", C.c_float), ("ax", Vec3), ("lo", C.c_float), ("ua", Vec3), ("hi", C.c_float),
+                ("bx", Vec3), ("pad0", C.c_float), ("ub", Vec3), ("pad1", C.c_float)]
+
+
 class Component(C.Structure):
     _fields_ = [("tag", C.c_int32), ("p", Vec3), ("d", Vec3), ("r", C.c_float)]
 
@@ -226,6 +232,19 @@ HINGE_MOTOR = 2  # MGF_HINGE_MOTOR
 BATCH_HINGE_LAUNCHES = 1  # MGF_BATCH_HINGE_LAUNCHES
 BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK = 1  # MGF_BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK
 BATCH_MAX_WORLD_HINGES = 256  # MGF_BATCH_MAX_WORLD_HINGES
+# mgf_batch_slider: a slider between body `body` and body `other` of world `world` (other = -1: the world) - anchors pa, pb, unit slide axes
+# ax, bx and unit references ua, ub in each end's frame, beta the share of the position error removed per call, fmax the motor's largest
+# force, [lo, hi] the travel range (with SLIDER_LOCK the travel held is lo)
+SLIDER_DTYPE = np.dtype([("world", "<i4"), ("body", "<i4"), ("other", "<i4"), ("flags", "<u4"), ("pa", "<f4", 3), ("beta", "<f4"),
+                         ("pb", "<f4", 3), ("fmax", "<f4"), ("ax", "<f4", 3), ("lo", "<f4"), ("ua", "<f4", 3), ("hi", "<f4"),
+                         ("bx", "<f4", 3), ("pad0", "<f4"), ("ub", "<f4", 3), ("pad1", "<f4")])
+assert SLIDER_DTYPE.itemsize == C.sizeof(BatchSlider) == 112
+SLIDER_LIMIT = 1  # MGF_SLIDER_LIMIT
+SLIDER_MOTOR = 2  # MGF_SLIDER_MOTOR
+SLIDER_LOCK = 4  # MGF_SLIDER_LOCK
+BATCH_SLIDER_LAUNCHES = 1  # MGF_BATCH_SLIDER_LAUNCHES
+BATCH_ROLLOUT_SLIDER_LAUNCHES_PER_TICK = 1  # MGF_BATCH_ROLLOUT_SLIDER_LAUNCHES_PER_TICK
+BATCH_MAX_WORLD_SLIDERS = 256  # MGF_BATCH_MAX_WORLD_SLIDERS
 # mgf_hinge_reading: a hinge's encoder - cosine and sine of its angle, its rate, the side of its limit (+1, -1, 0: off), the anchors' gap
 # in the world and the squared sine of the angle between the two axes; HINGE_TRACE_FULL_DTYPE: an entry of the readings table in the full
 # format - the reading and the eight impulse words of the tick's hinge solve (am / dt: the motor's torque)
@@ -306,6 +325,8 @@ SYMBOLS = [
     "mgf_batch_solve_hinges", "mgf_batch_solve_hinges_dev",
     "mgf_batch_read_hinges", "mgf_batch_read_hinges_dev", "mgf_batch_set_hinge_trace", "mgf_batch_hinge_trace_rows",
     "mgf_batch_get_hinge_trace", "mgf_batch_get_hinge_trace_dev",
+    "mgf_batch_set_sliders", "mgf_batch_slider_count", "mgf_batch_set_slider_targets", "mgf_batch_set_slider_targets_dev",
+    "mgf_batch_solve_sliders", "mgf_batch_solve_sliders_dev",
 ]
 
 _lib = None
@@ -526,6 +547,12 @@ def load_library():
         "mgf_batch_hinge_trace_rows": (i64, [vp]),
         "mgf_batch_get_hinge_trace": (i32, [vp, vp, i64, i64]),
         "mgf_batch_get_hinge_trace_dev": (i32, [vp, vp, i64, i64]),
+        "mgf_batch_set_sliders": (i32, [vp, vp, i64]),
+        "mgf_batch_slider_count": (i64, [vp]),
+        "mgf_batch_set_slider_targets": (i32, [vp, vp, i64]),
+        "mgf_batch_set_slider_targets_dev": (i32, [vp, vp, i64]),
+        "mgf_batch_solve_sliders": (i32, [vp, f32, i32, i64, vp]),
+        "mgf_batch_solve_sliders_dev": (i32, [vp, f32, i32, i64, vp]),
         "mgf_batch_set_cameras": (i32, [vp, vp, i64]),
         "mgf_batch_camera_count": (i64, [vp]),
         "mgf_batch_camera_pixels": (i64, [vp]),
@@ -1164,6 +1191,14 @@ def hinge_frames(a, b, anchor_world, axis_world):
     out = {"pa": local(xa, qa, anchor, True), "ax": local(xa, qa, axis, False), "ua": local(xa, qa, ref, False),
            "pb": local(xb, qb, anchor, True), "bx": local(xb, qb, axis, False), "ub": local(xb, qb, ref, False)}
     return {k: v.astype(np.float32) for k, v in out.items()}
+
+
+def slider_frames(a, b, anchor_world, axis_world):
+    """pa, pb, ax, ua, bx, ub of sliders placed in the present pose: zero gap, aligned frames, travel d = 0.  The arguments are
+    hinge_frames': a and b the state rows of every slider's `body` and `other` (b None, or a row whose q is all zero: the world),
+    anchor_world [n, 3] and axis_world [n, 3] - the slide axis, any length but zero - in the world's frame.  Works in float64 and
+    rounds once.  Returns a dict of float32 [n, 3] arrays, ready for WorldBatch.set_sliders(**frames)."""
+    return hinge_frames(a, b, anchor_world, axis_world)
 
 
 def _record_k(out, k):
@@ -2637,6 +2672,67 @@ class WorldBatch:
         row0, rows = self._hinge_trace_span(row0, rows)
         cols = 16 if getattr(self, "_hinge_trace_full", False) else 8
         _check(load_library().mgf_batch_get_hinge_trace_dev(self._h, _dev_arg(out_dev, "float32", cols, rows * max(self.hinge_count(), 0), "out_dev"), row0, rows))
+
+    # ---- slider joints between bodies: three angular rows, two off-axis rows, a limit, a motor or a lock along the axis ---------------------
+    def set_sliders(self, world, body=None, other=-1, pa=None, pb=None, ax=None, ua=None, bx=None, ub=None, beta=0.0, lo=0.0, hi=0.0, fmax=0.0,
+                    limit=False, motor=False, lock=False):
+        """the batch's slider rig replaced (mgf_batch_set_sliders): slider i ties body[i] to other[i] of world[i] (other[i] = -1: to the
+        world) at the anchors pa[i], pb[i] along the unit axes ax[i], bx[i], with the unit references ua[i], ub[i] - each in its end's
+        frame, as slider_frames() returns them; beta[i] in [0, 1] is the share of the position error removed per call; limit[i]: the
+        travel along the axis is held to [lo[i], hi[i]]; motor[i]: the relative speed along the axis is driven to the target table's
+        entry (set_slider_targets), the force capped at fmax[i] (np.inf: no cap); lock[i]: the travel is held at lo[i] - a weld -
+        and neither limit[i] nor motor[i] may be set.  Arrays, or scalars / single rows for all: the number of sliders is that of the
+        longest argument.  At most BATCH_MAX_WORLD_SLIDERS sliders a world.  No sliders (empty arrays) clears the rig.  The target
+        table becomes one row of zeros.  Also takes a SLIDER_DTYPE array as `world`, the other arguments not read."""
+        if isinstance(world, np.ndarray) and world.dtype == SLIDER_DTYPE:
+            rig = np.ascontiguousarray(world.reshape(-1))
+        else:
+            given = {key: v for key, v in dict(pa=pa, pb=pb, ax=ax, ua=ua, bx=bx, ub=ub).items() if v is not None}
+            flags = (np.asarray(limit, bool) * np.uint32(SLIDER_LIMIT) + np.asarray(motor, bool) * np.uint32(SLIDER_MOTOR) +
+                     np.asarray(lock, bool) * np.uint32(SLIDER_LOCK))
+            rig = _rig_rows(SLIDER_DTYPE, world=world, body=body, other=other, beta=beta, fmax=fmax, flags=flags, lo=lo, hi=hi, **given)
+        _check(load_library().mgf_batch_set_sliders(self._h, rig.ctypes.data if len(rig) else None, len(rig)))
+
+    def slider_count(self):
+        return load_library().mgf_batch_slider_count(self._h)
+
+    def set_slider_targets(self, w):
+        """the motors' target table replaced (mgf_batch_set_slider_targets): w float32 [rows, slider_count()] length units a second, or
+        one row [slider_count()].  solve_sliders names the row it reads; tick t of a rollout reads row min(t, rows - 1)."""
+        n = max(self.slider_count(), 0)
+        w = np.ascontiguousarray(w, np.float32)
+        if w.ndim == 1:
+            w = w.reshape(1, -1)
+        if w.ndim != 2 or w.shape[1] != n:
+            raise ValueError(f"w: {w.shape} is not rows of {n} sliders")
+        _check(load_library().mgf_batch_set_slider_targets(self._h, w.ctypes.data if w.size else None, w.shape[0]))
+
+    def set_slider_targets_dev(self, w_dev, rows=None):
+        """set_slider_targets from device memory, enqueued on the context's stream and not waited for
+        (mgf_batch_set_slider_targets_dev).  w_dev: CUDA float32 [rows, slider_count()], or an integer address with `rows` given."""
+        n = max(self.slider_count(), 0)
+        if rows is None:
+            if not hasattr(w_dev, "data_ptr") or w_dev.dim() != 2:
+                raise ValueError("w_dev: a tensor of rows of slider_count() floats, or rows given with a raw address")
+            rows = int(w_dev.shape[0])
+        _check(load_library().mgf_batch_set_slider_targets_dev(self._h, _dev_arg(w_dev, "float32", n, int(rows), "w_dev"), int(rows)))
+
+    def solve_sliders(self, h, iters, row=0, impulses=False):
+        """`iters` sweeps of sequential impulses over every world's sliders in the rig's order, from the current state of their ends:
+        per slider the motor, the limit or the lock, the three angular rows and the two off-axis rows (mgf_batch_solve_sliders); the
+        motors' targets are row `row` of the table.  impulses=True: returns the float32 [n, 8] array (p1, p2, al, am, aw.x, aw.y,
+        aw.z, 0) of every slider - the off-axis impulses, the limit's or lock's, the motor's and the angular impulse over the call -
+        in the rig's order."""
+        n = max(self.slider_count(), 0)
+        out = np.zeros((n, 8), np.float32) if impulses else None
+        _check(load_library().mgf_batch_solve_sliders(self._h, float(h), int(iters), int(row), _ptr(out)))
+        return out
+
+    def solve_sliders_dev(self, h, iters, row=0, impulses_dev=None):
+        """solve_sliders enqueued on the context's stream and not waited for (mgf_batch_solve_sliders_dev).  impulses_dev: CUDA
+        float32 [n, 8], n = slider_count(), or None."""
+        n = max(self.slider_count(), 0)
+        _check(load_library().mgf_batch_solve_sliders_dev(self._h, float(h), int(iters), int(row), _dev_arg(impulses_dev, "float32", 8, n, "impulses_dev")))
 
     def counter(self, name):
         v = C.c_int64()

@@ -107,6 +107,7 @@ struct mgf_batch {
   BatchRig<mgf_batch_spring> springs;   // on the device: runs | records | order - the springs; `items` holds the runs of one body's ENDS, `order` the ends (host_batch_spring.inc)
   BatchRig<mgf_batch_joint> joints;     // on the device: items | records | plan, slots - the ball joints; `items` holds a world's joints each, `order` the plan and the slots (host_batch_joint.inc)
   BatchRig<mgf_batch_hinge> hinges;     // on the device: items | records | plan, slots - the hinges, laid out as the ball joints are (host_batch_hinge.inc)
+  BatchRig<mgf_batch_slider> sliders;   // on the device: items | records | plan, slots - the sliders, laid out as the ball joints are (host_batch_slider.inc)
   // ... and what a call on one of them has nowhere else to put
   DBuf<float> s_parts;                  // the particles of a sensor cast: 7 words a sensor
   size_t c_pixels = 0;                  // the pixels of the camera rig, camera by camera
@@ -130,6 +131,11 @@ struct mgf_batch {
   int64_t ht_rows = 0;                  // ... its rows; 0: no trace (host_batch_hinge_read.inc)
   int32_t ht_format = 0;                // ... and MGF_HINGE_TRACE_READING / _FULL
   DBuf<float4> ht_out;                  // what the host-memory read of the hinges downloads: two words a hinge
+  DBuf<float> sg_acc;                   // the impulses of the sliders over a call, eight floats a slider
+  DBuf<unsigned long long> sg_skipped;  // sliders that were skipped, cumulative (counter "sliders_skipped")
+  DBuf<float> sg_w;                     // the motors' target table, sg_rows rows of a float a slider (mgf_batch_set_slider_targets)
+  int64_t sg_rows = 1;                  // ... its rows
+  bool sg_zero = true;                  // ... and: the rig was set behind the last table - it is one row of zeros, made where the rig goes up
   // the rollouts (host_batch_rollout.inc)
   DBuf<uint32_t> d_act;                 // per world, beside d_done: ticks of the call whose actuation the world has behind it (k_batch_rollout.h)
   int64_t r_launches = 0;               // launches of the last rollout call beyond its ticks' own (counter "rollout_launches")
@@ -353,6 +359,12 @@ extern "C" mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, in
   if (!strcmp(name, "hinges_skipped")) {  // (on the device: the stream is waited for)
     unsigned long long v = 0;
     if (b->hg_skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, b->hg_skipped.p, 1)); }
+    *out = (int64_t)v;
+    return MGF_OK;
+  }
+  if (!strcmp(name, "sliders_skipped")) {  // (on the device: the stream is waited for)
+    unsigned long long v = 0;
+    if (b->sg_skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, b->sg_skipped.p, 1)); }
     *out = (int64_t)v;
     return MGF_OK;
   }
@@ -591,6 +603,7 @@ static void batch_rigs_stale(mgf_batch* b) {
   b->springs.stale = true;
   b->joints.stale = true;
   b->hinges.stale = true;
+  b->sliders.stale = true;
 }
 
 // the rows of `n` new bodies (empty part slots where the caller has filled none) behind world k's last body
@@ -902,6 +915,9 @@ struct BatchRolloutHook {
   BatchHingeArgs G;      // the hinges' launch (k_batch_hinge.h): out, h and iters; the train fills the rest in, the handle's view per PASS, the table's row per TICK
   uint32_t hinge_lds = 0;  // ... and its dynamic LDS
   bool hinges = false;   // the hinge rig is not empty: solved behind the ball joints and ahead of the tick
+  BatchSliderArgs Z;     // the sliders' launch (k_batch_slider.h): out, h and iters; the train fills the rest in, the handle's view per PASS, the table's row per TICK
+  uint32_t slider_lds = 0;  // ... and its dynamic LDS
+  bool sliders = false;  // the slider rig is not empty: solved behind the hinges and ahead of the tick
   BatchTraceTouchArgs T;  // the touch trace (k_batch_trace.h): V.out - row 0 - and n_touch; the train fills the rest in, the lists' view per PASS
   int32_t touch = -1;    // MGF_ROLLOUT_TOUCH_FULL / _SHORT: k_batch_trace_touch behind every tick's record; -1: no touch trace
   BatchSensorArgs R;     // the sensor trace's cast (k_batch_scan.h): mask, out and parts - the handle's scratch; the train fills the rest in per PASS
@@ -914,6 +930,7 @@ struct BatchRolloutHook {
 static void batch_joint_view(const mgf_batch* b, BatchJointArgs* A);  // (host_batch_joint.inc, behind this file) what the joints' kernel reads of the handle
 static void batch_hinge_view(const mgf_batch* b, BatchHingeArgs* A);  // (host_batch_hinge.inc, behind this file) what the hinges' kernel reads of the handle
 static void batch_hinge_read_view(const mgf_batch* b, BatchHingeReadArgs* A);  // (host_batch_hinge_read.inc, behind this file) what the hinge trace's kernel reads of the handle
+static void batch_slider_view(const mgf_batch* b, BatchSliderArgs* A);  // (host_batch_slider.inc, behind this file) what the sliders' kernel reads of the handle
 static uint32_t batch_touch_tile(const mgf_batch* b);  // (host_batch_touch.inc, behind this file) the words of dynamic LDS the contact sensors' fold stages
 // (host_batch_query.inc, behind this file) the dynamic LDS of a ray cast with a workgroup per work item; what a cast reads of the handle; has it obstacles to meet
 static uint32_t batch_ray_lds(const mgf_batch* b);
@@ -923,7 +940,8 @@ static bool batch_has_obstacles(const mgf_batch* b, int32_t kinds_mask);
 // The step's launch train, behind the refusals: n_ticks x World::step (world.rs:227-294) of every world, six (seven) launches a tick, one
 // host wait per pass - and with a hook a rollout's two launches a tick among them, the springs' two where that rig is not empty and the
 // touch trace's one and the sensor trace's two where they are asked for, and the joints' one where that rig is not empty, and the
-// hinges' one where theirs is not, and the hinge trace's one behind every tick that has a row in the readings table.
+// hinges' one where theirs is not, and the hinge trace's one behind every tick that has a row in the readings table, and the sliders'
+// one behind the hinges' where that rig is not empty.
 // hook == nullptr: mgf_batch_step, launch for launch.
 static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats, BatchRolloutHook* hook) {
   MGF_TRY(batch_push(b));
@@ -975,6 +993,10 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
     if (hook && hook->hinges) {
       batch_hinge_view(b, &hook->G);
       hook->G.done = b->d_done.p; hook->G.act = b->d_act.p;
+    }
+    if (hook && hook->sliders) {
+      batch_slider_view(b, &hook->Z);
+      hook->Z.done = b->d_done.p; hook->Z.act = b->d_act.p;
     }
     if (hook && hook->hinge_read >= 0) {  // (the same rule for the hinge trace: the rig, the impulse buffer and the TABLE are looked up again for every pass)
       batch_hinge_read_view(b, &hook->E);
@@ -1037,6 +1059,13 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
         LAUNCH_CHECK();
         hook->launches += MGF_BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK;
       }
+      if (hook && hook->sliders) {  // (behind the hinges, under their gate; tick t reads the target table's row min(t, rows - 1))
+        hook->Z.tick = t;
+        hook->Z.w = b->sg_w.p + (size_t)std::min<int64_t>((int64_t)t, b->sg_rows - 1) * b->sliders.recs.size();
+        k_batch_slider_solve<true><<<(unsigned)b->sliders.items.size(), kBatchBlock, hook->slider_lds, s>>>(hook->Z);
+        LAUNCH_CHECK();
+        hook->launches += MGF_BATCH_ROLLOUT_SLIDER_LAUNCHES_PER_TICK;
+      }
       if (b->parts) MGF_TRY(batch_collide_parts(b, A, nmax));
       else MGF_TRY(batch_collide(b, A, nmax));
       k_batch_setup<<<K, kBatchBlock, 12u * nmax, s>>>(A);
@@ -1079,7 +1108,7 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
       }
     }
     MGF_TRY(d2h(ctx, done.data(), b->d_done.p, K));
-    uint32_t err[2] = {0u, 0u};  // [0] k_batch_solve's, [1] k_batch_joint_solve's and k_batch_hinge_solve's
+    uint32_t err[2] = {0u, 0u};  // [0] k_batch_solve's, [1] k_batch_joint_solve's and k_batch_hinge_solve's (and k_batch_slider_solve's)
     MGF_TRY(d2h(ctx, err, b->d_err.p, 2));
     if (err[0]) return fail(MGF_ERR_HIP, "internal error: a lane of the batch solver gave up waiting for its turn");
     if (err[1]) return fail(MGF_ERR_HIP, "internal error: a lane of the joint solver gave up waiting for its turn");

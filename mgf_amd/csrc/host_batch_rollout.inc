@@ -10,6 +10,7 @@
 // launches (k_batch_spring.h, MGF_BATCH_ROLLOUT_SPRING_LAUNCHES_PER_TICK) go ahead of the actuation under the same two words, and
 // where the joint rig is not empty its one launch (k_batch_joint.h, MGF_BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK) behind the actuation,
 // and where the hinge rig is not empty its one launch (k_batch_hinge.h, MGF_BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK) behind the joints'.
+// Where the slider rig is not empty its one launch (k_batch_slider.h, MGF_BATCH_ROLLOUT_SLIDER_LAUNCHES_PER_TICK) goes behind the hinges'.
 // Where the hinge rig is not empty and the readings table has rows (mgf_batch_set_hinge_trace), the hinge trace's one launch
 // (k_batch_hinge_read.h, MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK) goes behind the record of every tick t < rows.
 // The rig is the actuators' (BatchRig::items: no plan and no upload format of its own), the trace rows are k_batch_dev_gather's.
@@ -25,6 +26,8 @@ static mgf_status batch_joint_ready(mgf_batch* b, float h, int32_t iters, float*
 static mgf_status batch_hinge_ready(mgf_batch* b, float h, int32_t iters, float* out_dev, BatchHingeArgs* A, uint32_t* lds);
 // (host_batch_hinge_read.inc, behind this file) the hinge trace's arguments for the train: the rig up, the impulse buffer there
 static mgf_status batch_hinge_read_ready(mgf_batch* b, BatchHingeReadArgs* A);
+// (host_batch_slider.inc, behind this file) the sliders' arguments for the train: the rig and the target table up, the impulse buffer and the skip counter there
+static mgf_status batch_slider_ready(mgf_batch* b, float h, int32_t iters, float* out_dev, BatchSliderArgs* A, uint32_t* lds);
 
 struct RolloutBytes { size_t u, body, out[4], touch, sensor; };  // what the call touches of u, body, x, q, v, omega, touch, sensor
 // the touch trace of mgf_batch_rollout_touches / _touches_dev (host_batch_trace.inc): rows of n reports, device memory when it reaches the core.
@@ -92,7 +95,8 @@ static mgf_status batch_rollout_run(mgf_batch* b, float dt, int32_t iters, int64
   const bool scan = ts && ts->n > 0 && ts->out;
   const bool joints = !b->joints.recs.empty();  // (the same holds for the joints: they are solved ahead of every tick)
   const bool hinges = !b->hinges.recs.empty();  // (and for the hinges, solved behind them)
-  if (n_ticks == 0 || (n_act == 0 && !trace && !springs && !joints && !hinges && !touches && !scan)) return batch_step_run(b, dt, iters, n_ticks, stats, nullptr);
+  const bool sliders = !b->sliders.recs.empty();  // (and for the sliders, solved behind the hinges)
+  if (n_ticks == 0 || (n_act == 0 && !trace && !springs && !joints && !hinges && !sliders && !touches && !scan)) return batch_step_run(b, dt, iters, n_ticks, stats, nullptr);
   hipStream_t s = b->ctx->stream;
   BatchRig<mgf_batch_actuator>& R = b->actuators;
   MGF_TRY(batch_push(b));
@@ -136,6 +140,10 @@ static mgf_status batch_rollout_run(mgf_batch* b, float dt, int32_t iters, int64
   if (hinges && iters > 0) {  // (iters == 0: mgf_batch_solve_hinges_dev enqueues nothing)
     MGF_TRY(batch_hinge_ready(b, dt, iters, nullptr, &H.G, &H.hinge_lds));
     H.hinges = true;
+  }
+  if (sliders && iters > 0) {  // (iters == 0: mgf_batch_solve_sliders_dev enqueues nothing)
+    MGF_TRY(batch_slider_ready(b, dt, iters, nullptr, &H.Z, &H.slider_lds));
+    H.sliders = true;
   }
   if (hinges && b->ht_rows > 0) {  // (the readings table has rows: k_batch_read_hinges behind every tick t < rows; with iters == 0 no solve wrote an impulse)
     MGF_TRY(batch_hinge_read_ready(b, &H.E));

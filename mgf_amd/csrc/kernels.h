@@ -189,6 +189,13 @@
 //                      with the eight impulse words of the tick's solve behind them - with float4 stores; no plan, no LDS, no
 //                      division, no atomic, nothing written but the output.  GATED: the traces' gate done[k] == t + 1 &&
 //                      act[k] <= t + 1, the lane's own, ahead of every load of state
+//   k_batch_slider_solve<GATED> (k_batch_slider.h)
+//                      slider joints (mgf_batch_set_sliders / _set_slider_targets / _solve_sliders / _solve_sliders_dev, and behind the
+//                      hinges of a rollout's tick): k_batch_hinge_solve's launch with the rows of a slider - a velocity motor with a
+//                      force cap along the axis, a limit of the travel or a lock, three angular rows that hold the two frames
+//                      together, two linear rows that hold the anchor on the axis - solved in one turn of the lane with both
+//                      bodies' velocities in registers; the same plan, slots, dataflow, bounded spin and gate; the motors' targets
+//                      from a row of the handle's table
 //   k_batch_trace_touch<FORMAT> (k_batch_trace.h)
 //                      the touch trace of a rollout (mgf_batch_rollout_touches / _touches_dev): k_batch_touch's fold of every world's
 //                      list behind tick t into row t of the reports, one launch a tick behind k_batch_rollout_record; the train's gate
@@ -241,6 +248,7 @@
 #include "k_batch_joint.h"  // ball joints between bodies: sequential impulses over the resident velocities, a workgroup per world (k_batch_joint_solve)
 #include "k_batch_hinge.h"  // hinge joints between bodies: the joints' launch with motor, limit, angular and point rows (k_batch_hinge_solve)
 #include "k_batch_hinge_read.h"  // hinge encoders: angle, rate, limit side, gap and tilt from the resident state, a lane per hinge (k_batch_read_hinges)
+#include "k_batch_slider.h"  // slider joints between bodies: the hinges' launch with motor, axis, angular and off-axis rows (k_batch_slider_solve)
 #include "k_batch_part_query.h"  // rays, sweeps and box queries that see the parts of bodies of several components (k_batch_pq_*)
 #include "k_batch_trace.h"  // the touch trace of a rollout: the contact sensors' reports behind every tick (k_batch_trace_touch)
 #include "k_batch_scan.h"  // the sensor trace of a rollout: the ray sensors' answers behind every tick (k_batch_scan_rays, _rows)
