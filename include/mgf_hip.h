@@ -509,6 +509,10 @@ MGF_API int64_t mgf_tiles_counter(const mgf_tiles* t, const char* key);
  * launch, 3 = a launch on the context's second stream, 4 = always a launch of their own: experiments; 0 = one launch, k_contacts_rows);
  * "scan_fused" [1] (a world of spheres with contacts_split on: the constraint numbering - the prefix sum of the bodies' constraint counts and the
  * tick's list sizes - inside the numbering launch itself; 0 = a prefix-sum launch of its own ahead of it.  The results are the same bit for bit);
+ * "tables_fused" [1] (with scan_fused, the block-local solver and a store kept in cell order - resort_every - whose solver blocks hold at most
+ * 1 024 bodies: the numbering launch takes a ticket per solver block and also writes that block's part of the solver's tables - the bodies'
+ * look-up words, the foreign bodies, every own constraint's row; 0 = a launch of its own behind it, which every other world keeps.  The results
+ * are the same bit for bit);
  * "front_rows" [1] (r06: a world of single-component bodies that are not all spheres - capsules, mixed - or of bodies of up to two components:
  * the pair search runs the pair test on the partners it accepts, the bodies near the mesh get their faces and the body-triangle test in
  * launches of their own, the constraint records are written from the rows; 0 = candidate lists and one narrowphase launch per shape-pair
@@ -552,7 +556,8 @@ MGF_API mgf_status mgf_world_set_option(mgf_world* w, const char* key, int64_t v
  * narrowphase ran the kernels for bodies of more than four components), "contacts_split_fused" / "contacts_split_standalone" (ticks whose partner
  * records were written beside the links launch / by a launch of their own; both 0: option contacts_split = 0 or another front end),
  * "scan_fused_numbering_ticks" (ticks whose constraints were numbered inside the numbering launch: option scan_fused; a tick that was run again
- * counts in none of these), "scan_fused_run" / "scan_fused_look" (bodies per ticketed run of that launch, runs read per sweep of its look-back),
+ * counts in none of these), "tables_fused_ticks" (ticks whose solver tables were built inside that launch: option tables_fused; ticks run again
+ * count in neither), "scan_fused_run" / "scan_fused_look" (bodies per ticketed run of that launch, runs read per sweep of its look-back),
  * "contacts_records_pending" (tests: 1 only inside a collide phase being enqueued), "max_parts" (the most components any body has)}. */
 MGF_API mgf_status mgf_world_counter(const mgf_world* w, const char* name, int64_t* out);
 /* Raw device pointers of resident state for zero-copy exchange (multi-GPU halo): name in

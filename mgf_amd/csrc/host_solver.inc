@@ -314,8 +314,11 @@ static mgf_status flow6_build_tables(mgf_world* w, uint32_t cap_c, bool* built) 
     MGF_TRY(records_launch_alone(w, w->ctx->aux));
     MGF_TRY(side_done(w));
   }
-  k_flow6_blocks<<<F.nblocks, kF6PrepThreads, 0, s>>>(F, w->links());
-  LAUNCH_CHECK();
+  if (!w->f6_tables_early) {  // (option tables_fused: the numbering launch of this collide phase built them, a ticket per block)
+    k_flow6_blocks<<<F.nblocks, kF6PrepThreads, 0, s>>>(F, w->links());
+    LAUNCH_CHECK();
+  }
+  w->f6_tables_early = false;
   // (the channel layout - k_flow6_chan's work - is done by the links launch's last block: kWLinksTicket is its ticket, 0 between launches)
   const uint32_t iters = w->f6_prep_iters ? w->f6_prep_iters : 10u;
   MGF_TRY(w->vsnap.ensure(2 * (size_t)std::max(w->n, 1u), s));

@@ -228,6 +228,7 @@ static mgf_status flow6_plan(mgf_world* w, uint32_t cap_c, uint32_t iters, bool*
 static mgf_status flow6_build_tables(mgf_world* w, uint32_t cap_c, bool* built);
 static mgf_status chain_rows_launch(mgf_world* w, const uint32_t* only_if);
 static void flow6_zero_entries(mgf_world* w, uint32_t cap_c, ZeroList& z, int first);
+static Flow6 flow6_args(mgf_world* w);
 // One of the tick's three prefix sums (job 0: cells, 1: candidate rows, 2: constraints per body) by the hand-written single-pass
 // k_scan; its status words were cleared by this collide phase's k_zero_many.
 static mgf_status tick_scan(mgf_world* w, int job, const uint32_t* a, uint32_t* oa, const uint32_t* b, uint32_t* ob, size_t n_plus_1,
@@ -648,7 +649,25 @@ static mgf_status contacts_from_rows(mgf_world* w, const CollidePlan& P, float d
       uint32_t* ws = w->scan_ws.p + scan_ws_num_at(w);
       A.base_out = w->base.p; A.num_runs = (P.n + kNumSubs * kBlock - 1) / (kNumSubs * kBlock);  // (a workgroup: kNumSubs groups of 256 bodies, one ticket)
       A.num_status = reinterpret_cast<unsigned long long*>(ws); A.num_ticket = ws + 2 * ((size_t)nblk(P.n) + 1);
-      k_contacts_rows_index_scan<<<A.num_runs, kNumSubs * kBlock, 0, P.s>>>(P.B, P.M, A);
+      // (option tables_fused) ... and the solver's block tables, a ticket per solver block, where stage_links would launch k_flow6_blocks on a
+      // re-sorted store: mode 6's plan was made and its words cleared by this phase's clearing launch (flow6_zeroed: the solver follows), no
+      // re-run with the global solver, blocks of at most a workgroup's bodies and no more of them than the numbering has status words.  The plan is
+      // made again here from the host's values of earlier ticks - what flow6_build_tables will find behind this launch, inside the same enqueue.
+      bool tab = false;
+      Flow6 F;
+      if (w->opt.tables_fused && w->opt.solver_mode == 6 && !w->tick_mode1 && w->flow6_zeroed && w->flow5_ok && !w->flow6_prepped) {
+        MGF_TRY(flow6_plan(w, P.cap_c, w->f6_prep_iters ? w->f6_prep_iters : 10u, &tab));
+        if (tab) {
+          F = flow6_args(w);
+          tab = F.ident && F.n == P.n && F.nb <= (uint32_t)(kNumSubs * kBlock) && F.nblocks <= nblk(P.n) + 1u;
+        }
+      }
+      if (tab) {
+        A.num_runs = F.nblocks;
+        k_contacts_rows_index_tables<<<A.num_runs, kNumSubs * kBlock, 0, P.s>>>(P.B, P.M, A, F);
+        w->f6_tables_early = true; w->ts->tab_fused = true;
+      }
+      else k_contacts_rows_index_scan<<<A.num_runs, kNumSubs * kBlock, 0, P.s>>>(P.B, P.M, A);
       w->ts->num_fused = true;
     }
     else k_contacts_rows_index<true><<<nblk(P.n), kBlock, 0, P.s>>>(P.B, P.M, A);
@@ -805,6 +824,7 @@ static mgf_status collide_enqueue(mgf_world* w, float dt, bool solver_follows = 
   w->ts->tree = !P.two_pass && !P.use_grid && !P.demo;
   w->ts->big_parts = P.big;
   w->records_pending = false; w->ts->split_fused = false; w->ts->split_alone = false; w->ts->num_fused = false;
+  w->f6_tables_early = false; w->ts->tab_fused = false;
   MGF_TRY(stage_cells(w, P));
   MGF_TRY(stage_side_terrain(w, P));
   MGF_TRY(stage_scatter(w, P));
@@ -963,7 +983,7 @@ static mgf_status collide_process(mgf_world* w, bool* retry) {
   }
   if (*retry) { w->n_cap_retries++; return MGF_OK; }
   w->n_path_ticks[0] += w->ts->brick; w->n_path_ticks[1] += w->ts->front_rows; w->n_path_ticks[2] += w->ts->contacts_fused; w->n_path_ticks[3] += w->ts->cells_early;
-  w->n_split_ticks[0] += w->ts->split_fused; w->n_split_ticks[1] += w->ts->split_alone; w->n_scan_fused_ticks[0] += w->ts->num_fused;
+  w->n_split_ticks[0] += w->ts->split_fused; w->n_split_ticks[1] += w->ts->split_alone; w->n_scan_fused_ticks[0] += w->ts->num_fused; w->n_tables_fused_ticks += w->ts->tab_fused;
   w->n_path_ticks[4] += w->ts->two_pass; w->n_path_ticks[5] += w->ts->tree; w->n_path_ticks[6] += w->ts->big_parts;
   if (w->opt.wide_list) {  // the wide bodies' limit for the ticks to come (WideSpec, k_bodies.h)
     if (w->wide_tick_on) {  // (the read-back's rmax is the largest half extent of the bodies that were NOT wide)

@@ -29,6 +29,11 @@ struct WorldOptions {
   // (r08) the tick's prefix sums inside their consumers' launches.  Bit 1: the constraint numbering of a world of spheres inside k_contacts_rows_index's
   // launch (k_contacts_rows_index_scan: no k_scan<1> launch over p_cnt + tcn; needs contacts_split); 0: tick_scan(job 2), then k_contacts_rows_index<true>
   int64_t scan_fused = 1;
+  // (r09) the solver's block tables inside the numbering launch (k_contacts_rows_index_tables: what k_flow6_blocks builds - binfo, bref, the foreign bodies,
+  // the rows' own part - from what the numbering holds in LDS; a ticket per solver block).  Runs when the numbering launch runs (scan_fused, spheres,
+  // contacts_split), solver mode 6 builds its tables inside the collide phase, the store is re-sorted (blocks are runs of slots) and a block is no
+  // longer than the launch's workgroup; everything else - and 0 - keeps the k_flow6_blocks launch
+  int64_t tables_fused = 1;
   int64_t front_rows = 1;              // (r06) worlds of single-component bodies that are not all spheres: the list-free front end (k_front_rows.h; 0: candidate lists, one narrowphase launch per shape-pair type)
   int64_t front_rows_check = 0;        // tests: the faces k_terrain_near's cheap reject (comp_tri_far) drops go through the reference's tests as well; a contact among them is an internal error
   int64_t side_stream = 1;             // (r06) the terrain kernels of the list-free front end on the context's second stream, beside the pair search (0: one stream)
@@ -159,6 +164,8 @@ struct mgf_world {
   Bodies rec_B;
   ContactsSpheres rec_A;
   uint64_t n_split_ticks[2] = {0, 0};  // [0] fused into the links launch (or beside it on the side stream), [1] a launch of their own
+  bool f6_tables_early = false;  // this collide phase's numbering launch built k_flow6_blocks' tables (option tables_fused): flow6_build_tables skips that launch
+  uint64_t n_tables_fused_ticks = 0;  // option tables_fused: ticks whose block tables were built inside the numbering launch
   uint64_t n_scan_fused_ticks[1] = {0};  // option scan_fused: [0] ticks whose constraints were numbered inside k_contacts_rows_index_scan's launch
   DBuf<float4> wide_list;
   // mgf_world_raycast_many / mgf_world_overlap_aabb_many (host_query.inc): the query's own grid and lists - nothing of the tick's is read or written
@@ -311,6 +318,7 @@ struct mgf_world {
     bool two_pass = false;            // ... counted and filled its candidate lists in two passes (k_candidates)
     bool tree = false;                // ... searched its pairs in the tree (k_pair_rows), not in the cell grid
     bool split_fused = false, split_alone = false;  // ... wrote its partner records beside k_flow6_links / in a launch of their own (option contacts_split)
+    bool tab_fused = false;           // ... and built the solver's block tables there too (option tables_fused)
     bool num_fused = false;           // ... numbered its constraints inside k_contacts_rows_index_scan's launch (option scan_fused, bit 1)
     bool big_parts = false;           // ... ran k_narrow_pairs_big / k_narrow_terrain_big (a body of more than kMaxParts components)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // the side stream's start and end inside the tick (no timing: created on first use)
@@ -437,6 +445,7 @@ static const OptionEntry kOptionTable[] = {
     {"fused_contacts", &WorldOptions::fused_contacts, 1, 0, nullptr, false, false},
     {"contacts_split", &WorldOptions::contacts_split, 0, 4, "contacts_split: 0..4", false, false},
     {"scan_fused", &WorldOptions::scan_fused, 0, 1, "scan_fused: 0..1", false, false},
+    {"tables_fused", &WorldOptions::tables_fused, 0, 1, "tables_fused: 0..1", false, false},
     {"front_rows", &WorldOptions::front_rows, 1, 0, nullptr, false, false},
     {"front_rows_check", &WorldOptions::front_rows_check, 1, 0, nullptr, false, false},
     {"side_stream", &WorldOptions::side_stream, 1, 0, nullptr, false, false},
@@ -637,6 +646,7 @@ extern "C" mgf_status mgf_world_counter(const mgf_world* w, const char* name, in
   if (!strcmp(name, "contacts_split_fused")) { *out = (int64_t)w->n_split_ticks[0]; return MGF_OK; }
   if (!strcmp(name, "contacts_split_standalone")) { *out = (int64_t)w->n_split_ticks[1]; return MGF_OK; }
   if (!strcmp(name, "scan_fused_numbering_ticks")) { *out = (int64_t)w->n_scan_fused_ticks[0]; return MGF_OK; }
+  if (!strcmp(name, "tables_fused_ticks")) { *out = (int64_t)w->n_tables_fused_ticks; return MGF_OK; }
   if (!strcmp(name, "scan_fused_look")) { *out = (int64_t)kNumLook * 64; return MGF_OK; }  // (runs per sweep of the numbering's look-back ...
   if (!strcmp(name, "scan_fused_run")) { *out = (int64_t)kNumSubs * kBlock; return MGF_OK; }  // ... and bodies per run)
   if (!strcmp(name, "contacts_records_pending")) { *out = w->records_pending ? 1 : 0; return MGF_OK; }

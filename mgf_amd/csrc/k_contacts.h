@@ -1282,8 +1282,30 @@ __global__ __launch_bounds__(kBlock) void k_contacts_rows(Bodies B, TerrainDev M
 // of k_contacts_rows_index does - with ONE ticket and one status word: config 2's launch takes 256 tickets.
 constexpr int kNumSubs = MGF_NUM_SUBS;  // groups of 256 bodies per workgroup (run) of k_contacts_rows_index_scan
 constexpr int kNumLook = MGF_NUM_LOOK;  // status words per lane and sweep: 256 runs, config 2's every predecessor in one
-template <bool SPH, bool NUM>
-__device__ __forceinline__ void contacts_index_body(const Bodies& B, const TerrainDev& M, const ContactsSpheres& A) {
+// TAB (r09, option tables_fused; with NUM, on a re-sorted store whose solver blocks - runs of `nb` consecutive body slots - are no longer than a
+// workgroup's bodies): the launch takes a ticket per SOLVER BLOCK (a run is `nb` bodies; threads beyond it idle) and writes what k_flow6_blocks
+// (k_solver_flow6.h) would build for that block in a launch of its own - binfo, bref, fbody / fcnt / nslots, both halves of every own F6Row, max_slots,
+// max_foreign, fail bits 1, 2 and 16 - from what it holds anyway: body a (the owner's place in the run), partner b (the list), the counts, the
+// exclusive prefix of the constraint counts inside the run (= the constraint's slot in the block's table) and, behind the look-back, the id.
+//   * What waits for the id: the row's `c`, bref[c] and binfo.z.  The foreign bodies go into the LDS hash set and are numbered AHEAD of the barrier
+//     that hands out the block's first id (one barrier of the block's own waves in between; the first wave goes straight on to its look-back, the
+//     other fifteen number the set) - the forward-progress argument above holds as it stands: the run's total is stored before either, and nothing
+//     new waits on another block.
+//   * More than one window: every body inserts the foreign partners of its WHOLE row (rp[0 .. np), read again from the row: L1 hits behind
+//     cs_list_row's loads) before the first window's rows are written, so the set is complete before any bref is formed, however many windows
+//     the entry loop takes; the rows are written window by window as the ids are.
+//   * A block that returns early (tick_fail, ids beyond cap_c) writes no table - at most its own fbody entries, which nobody reads without its
+//     fcnt: k_flow6_links leaves at sc->fail, the solver at F.fail / C == 0, and the tick is run again on the candidate lists.
+//   * Foreign bodies are numbered in the order the waves meet them in the hash set - any numbering is correct (k_flow6_blocks' own is arbitrary).
+struct NumTables {  // Flow6's fields that the table phase writes (k_contacts_rows_index_tables, k_solver_flow6.h, fills it in)
+  uint4* binfo; uint32_t* bref; uint32_t *fcnt, *fbody, *nslots; uint4* table; uint32_t *fail, *max_slots, *max_foreign;
+  uint32_t nb, rows, fcap, slot_cap;
+};
+// (k_solver_flow6.h's constants, which this header precedes: checked against them there)
+constexpr uint32_t kNtHash = 4096, kNtBodyBits = 11, kNtNoBody = (1u << kNtBodyBits) - 1u, kNtMaxSlots = (1u << 13) - 1u, kNtCntStride = 32;
+template <bool SPH, bool NUM, bool TAB = false>
+__device__ __forceinline__ void contacts_index_body(const Bodies& B, const TerrainDev& M, const ContactsSpheres& A, const NumTables& T = NumTables{}) {
+  static_assert(!TAB || NUM, "the table phase rides the numbering launch");
   constexpr int SUBS = NUM ? kNumSubs : 1, WAVES = SUBS * kBlock / 64;
   __shared__ uint32_t s_j[SUBS][kCsEntCap];     // the pass's partner contacts in canonical order: partner ...
   __shared__ uint16_t s_b[SUBS][kCsEntCap];     // ... and owner (the group's body)
@@ -1292,6 +1314,9 @@ __device__ __forceinline__ void contacts_index_body(const Bodies& B, const Terra
   __shared__ uint32_t s_wave_c[WAVES];          // NUM: the waves' constraint counts, ...
   __shared__ uint32_t s_num[2];                 // ... the block's ticket, the constraints of the runs before ...
   __shared__ CapsPre s_pre;                     // ... and what is known of the tick's counts and fail bits before the launch
+  __shared__ uint32_t s_key[TAB ? kNtHash : 1], s_val[TAB ? kNtHash : 1];  // TAB: the block's foreign bodies (id + 1; 0 = empty) and their numbers
+  __shared__ uint32_t s_first[TAB ? SUBS * kBlock + 1 : 1];                // ... body -> slot of its first own constraint (the next body's: one past its last)
+  __shared__ uint32_t s_fcnt;                                              // ... foreign bodies numbered so far
   if (!NUM && A.sc->fail) return;  // (the scan's closing thread found a flag up or a capacity exceeded: the host re-runs the phase)
   if (!NUM && blockIdx.x < A.t_blocks) {  // ---- ContactConstraint::new for the terrain contacts (world.rs:243-251), a lane per slot
     const uint32_t p = blockIdx.x * (uint32_t)kBlock + threadIdx.x, region = p / A.region_cap;
@@ -1317,15 +1342,18 @@ __device__ __forceinline__ void contacts_index_body(const Bodies& B, const Terra
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   uint32_t run_no = blockIdx.x - A.t_blocks, tick_fail = 0;
   if (NUM) {  // the run of bodies by ticket, the flags that are final before the launch
-    if (t == 0) { s_num[0] = atomicAdd(A.num_ticket, 1u); s_pre = caps_contacts_pre(A.epi); }
+    if (t == 0) { s_num[0] = atomicAdd(A.num_ticket, 1u); s_pre = caps_contacts_pre(A.epi); if (TAB) s_fcnt = 0u; }
+    if (TAB) for (uint32_t e = (uint32_t)t; e < kNtHash; e += (uint32_t)(SUBS * kBlock)) s_key[e] = 0u;
     __syncthreads();
     run_no = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_num[0]); tick_fail = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pre.fail);
   }
-  // (NUM: `sub` = the thread's group of 256 and `tt` its place in it; else the one group is the workgroup)
+  // (NUM: `sub` = the thread's group of 256 and `tt` its place in it; else the one group is the workgroup.  TAB: the run is the solver block's `nb` bodies)
   const int sub = t / kBlock, tt = t % kBlock, wv0 = sub * (kBlock / 64);
-  const uint32_t i0 = run_no * (uint32_t)(SUBS * kBlock) + (uint32_t)(sub * kBlock), i = i0 + (uint32_t)tt;
+  const uint32_t run_len = TAB ? T.nb : (uint32_t)(SUBS * kBlock), run_lo = run_no * run_len;
+  const uint32_t i0 = run_lo + (uint32_t)(sub * kBlock), i = i0 + (uint32_t)tt;
+  const bool live = (!TAB || (uint32_t)t < run_len) && i < A.n;
   uint32_t np = 0, run = 0, base_i = 0;
-  if (i < A.n) { np = A.p_cnt[i]; run = A.tcn[i]; if (!NUM) base_i = A.base[i]; }
+  if (live) { np = A.p_cnt[i]; run = A.tcn[i]; if (!NUM) base_i = A.base[i]; }
   // ---- where the body's partner contacts start in the group's list (NUM: and its constraints in the block's ids)
   uint32_t inc_p = np, inc_c = np + run;
 #pragma unroll
@@ -1349,6 +1377,32 @@ __device__ __forceinline__ void contacts_index_body(const Bodies& B, const Terra
   const uint32_t* rp = A.rows_p + (size_t)i * kRowCap;
   if (np && !tick_fail) cs_list_row(rp, np, A.ext, excl_p, 0u, (uint32_t)tt, s_j[sub], s_b[sub]);
   s_cbase[t] = (NUM ? excl_c : base_i) + run - excl_p;
+  if (TAB) {  // ---- the block's foreign bodies: the partners outside the run, from every window of the row, into the hash set; then numbered
+    s_first[t] = excl_c;
+    if (t == 0) s_first[SUBS * kBlock] = total_c;
+    if (!tick_fail) {
+      for (uint32_t a = 0; a < np; ++a) {
+        const uint32_t j = rp[a];
+        if (j - run_lo < run_len) continue;  // (own: brank is the identity, so "foreign" is j / nb != run_no)
+        uint32_t h = (j * 2654435761u) >> 20;
+        for (uint32_t probe = 0; probe < kNtHash; ++probe, h = (h + 1u) & (kNtHash - 1u)) {
+          const uint32_t cur = atomicCAS(&s_key[h], 0u, j + 1u);
+          if (cur == 0u || cur == j + 1u) break;
+        }
+      }
+    }
+    __syncthreads();  // (the set is complete; the block's own waves only)
+    if (wv != 0) {    // (the first wave goes on to the look-back)
+      for (uint32_t e = (uint32_t)t - 64u; e < kNtHash; e += (uint32_t)(SUBS * kBlock) - 64u) {
+        const uint32_t key = s_key[e];
+        if (key) {
+          const uint32_t k = atomicAdd(&s_fcnt, 1u);
+          s_val[e] = k;
+          if (k < T.fcap) T.fbody[(size_t)run_no * T.fcap + k] = key - 1u;
+        }
+      }
+    }
+  }
   if (NUM && wv == 0) {  // ---- the constraints of the runs before this one (the whole wave, every trip: the waits are the wave's vote)
     uint32_t prev = 0;
     if (run_no != 0u) {
@@ -1412,12 +1466,31 @@ __device__ __forceinline__ void contacts_index_body(const Bodies& B, const Terra
     __syncthreads();  // (... and the block's first id)
     first_c = s_num[1];
     base_i = first_c + excl_c;
-    if (i < A.n) A.base_out[i] = base_i;
+    if (live) A.base_out[i] = base_i;
     if (run_no + 1u == A.num_runs && t == 0) {  // the last ticket: the closing prefix and the tick's counts (what k_scan's closing thread did)
       A.base_out[A.n] = first_c + total_c;
       caps_contacts_post(A.epi.sc, A.cap_c, s_pre, first_c + total_c);
     }
     if (tick_fail || first_c + total_c > A.cap_c || first_c + total_c < first_c) return;  // (the whole block)
+    if (TAB) {  // the block's counts (one thread, as k_flow6_blocks), every body's look-up word, the terrain constraints' rows
+      if (t == 0) {
+        const uint32_t fc = s_fcnt;
+        T.nslots[(size_t)run_no * kNtCntStride] = total_c;
+        atomicMax(T.max_slots, total_c);
+        if (total_c > T.slot_cap || total_c > kNtMaxSlots) atomicOr(T.fail, 2u);
+        T.fcnt[(size_t)run_no * kNtCntStride] = fc;
+        atomicMax(T.max_foreign, fc);
+        if (fc > T.fcap || fc >= kNtHash / 2u) atomicOr(T.fail, 1u);
+      }
+      if (live) T.binfo[i] = make_uint4(i, excl_c, base_i, np + run);
+      for (uint32_t k = 0; k < run; ++k) {  // (b = kNone: no bref, pred_b = 0)
+        const uint32_t slot = excl_c + k;
+        if (slot >= T.slot_cap || slot >= kNtMaxSlots) break;  // (fail bit 2 is up)
+        uint4* dst = T.table + 2 * ((size_t)run_no * T.rows + slot);
+        dst[0] = make_uint4(base_i + k, (uint32_t)t | (kNtNoBody << kNtBodyBits), k + 1u < np + run ? slot + 1u : 0u, 0u);
+        dst[1] = make_uint4(k > 0u ? 1u : 0u, 0u, 0u, 0u);
+      }
+    }
     if (run) terrain_records(base_i);  // (they need the id: behind the barrier)
   }
   // ---- the partner contacts' ids, and their rows: the group's list, kCsEntCap entries per pass, an entry per thread
@@ -1432,6 +1505,26 @@ __device__ __forceinline__ void contacts_index_body(const Bodies& B, const Terra
       const uint32_t b = s_b[sub][e], j = s_j[sub][e], ia = i0 + b;
       const uint32_t c = first_c + s_cbase[sub * kBlock + b] + w0 + e;
       A.ab[c] = make_uint2(ia, j);
+      if (TAB) {  // the constraint's row of its block's table: its slot = its id less the block's first
+        const uint32_t ob = (uint32_t)(sub * kBlock) + b, slot = c - first_c, lo = s_first[ob], hi = s_first[ob + 1u];
+        uint32_t bref = j - run_lo;  // own: b's place in the run
+        if (bref >= run_len) {       // foreign: behind the own bodies, by its number in the set
+          bref = kNtNoBody;          // (not found - a set that overflowed, fail bit 1 is up: bit 16 below)
+          uint32_t h = (j * 2654435761u) >> 20;
+          for (uint32_t probe = 0; probe < kNtHash; ++probe, h = (h + 1u) & (kNtHash - 1u)) {
+            const uint32_t cur = s_key[h];
+            if (cur == j + 1u) { bref = run_len + s_val[h]; break; }
+            if (cur == 0u) break;
+          }
+        }
+        T.bref[c] = bref;
+        if (bref >= kNtNoBody) atomicOr(T.fail, 16u);
+        if (slot < T.slot_cap && slot < kNtMaxSlots) {
+          uint4* dst = T.table + 2 * ((size_t)run_no * T.rows + slot);
+          dst[0] = make_uint4(c, ob | (min(bref, kNtNoBody) << kNtBodyBits), slot + 1u < hi ? slot + 1u : 0u, 0u);
+          dst[1] = make_uint4(slot > lo ? 1u : 0u, 1u, 0u, 0u);  // (pred_b: k_flow6_links clears it where the chain starts)
+        }
+      }
       // body j's row of the constraints it takes part in as `b` (k_chain_rows); as `a` a body owns a contiguous id range
       const uint32_t pos = atomicAdd(&A.degb[j], 1u);
       if (pos < A.rev_cap) A.rev[(size_t)j * A.rev_cap + pos] = RevEnt{c, ia, order_id(A.ext, ia), 0u};

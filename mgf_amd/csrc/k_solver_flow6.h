@@ -222,6 +222,17 @@ __global__ __launch_bounds__(kF6PrepThreads) void k_flow6_blocks(Flow6 F, ConsLi
     }
   }
 }
+// (r09, option tables_fused) ... or, on a re-sorted store (F.ident) whose blocks are no longer than the numbering launch's workgroup, inside
+// k_contacts_rows_index_scan's launch: the numbering takes a ticket per solver block and writes the block's part of the tables from what it holds in
+// LDS and registers (contacts_index_body<true, true, true>, k_contacts.h: the TAB notes in its header) - k_flow6_blocks is not launched.
+static_assert(kNtHash == kF6Hash && kNtBodyBits == kF6BodyBits && kNtNoBody == kF6NoBody && kNtMaxSlots == kF6MaxSlots && kNtCntStride == kF6CntStride,
+              "the numbering launch's table phase writes k_flow6_blocks' tables");
+__global__ __launch_bounds__(kNumSubs * kBlock) void k_contacts_rows_index_tables(Bodies B, TerrainDev M, ContactsSpheres A, Flow6 F) {
+  NumTables T;
+  T.binfo = F.binfo; T.bref = F.bref; T.fcnt = F.fcnt; T.fbody = F.fbody; T.nslots = F.nslots; T.table = reinterpret_cast<uint4*>(F.table);
+  T.fail = F.fail; T.max_slots = F.max_slots; T.max_foreign = F.max_foreign; T.nb = F.nb; T.rows = F.rows; T.fcap = F.fcap; T.slot_cap = F.slot_cap;
+  contacts_index_body<true, true, true>(B, M, A, T);
+}
 // hash slot of `key1` (= key + 1, never 0) in a table of kF6Chan words; inserts it if absent
 __device__ __forceinline__ uint32_t f6_chan_slot(uint32_t* keys, uint32_t key1, uint32_t* fail) {
   const uint32_t h = (key1 * 2654435761u) >> 26;

@@ -50,6 +50,11 @@
 //                      workgroup of four groups of 256 bodies takes a ticket, publishes its run's total in a status word, lists its rows,
 //                      and its first wave sums the totals of the runs before it (256 status words per sweep); the last ticket writes
 //                      base[n] and the tick's counts (caps_contacts_pre / _post).  The other front ends keep the scan launch.
+//   k_contacts_rows_index_tables (r09, option tables_fused)
+//                      the same launch with a ticket per SOLVER BLOCK of a re-sorted store (a run of nb <= 1 024 body slots) and k_flow6_blocks'
+//                      work for that block inside: the foreign partners into an LDS hash set and numbered ahead of the barrier that hands
+//                      out the block's first id; binfo, bref, fbody / fcnt / nslots and both halves of every own F6Row from the owner, the
+//                      partner, the counts and the exclusive prefix the numbering holds in LDS.  No k_flow6_blocks launch in such a tick
 //   k_pair_wide (r06)  the few bodies whose fat box is far larger than the rest's (WideSpec, k_bodies.h: kept out of the scene
 //                      bounds and rmax by k_integrate, never partners of the grid's pair search) find their partners-to-be
 //                      from their own side: a workgroup per listed body
