@@ -24,6 +24,16 @@ struct BatchRig {
   size_t off[4] = {0, 0, 0, 0}; // ... section k at off[k]: items, records, order, worlds
 };
 
+// A rig of joints - ball joints, hinges, sliders (host_batch_joint.inc): the rig, and what a solve of it leaves in the handle
+template <class Rec>
+struct BatchJointRig : BatchRig<Rec> {
+  DBuf<float> acc;                      // the impulses over a call, the kind's Rows::kFloats floats a joint
+  DBuf<unsigned long long> skipped;     // joints that were skipped (a singular K, a word of the setup not finite), cumulative (counter "<kind>s_skipped")
+  DBuf<float> w;                        // the motors' target table, `rows` rows of a float a joint (mgf_batch_set_hinge_targets, _slider_targets); the ball joints have none
+  int64_t rows = 1;                     // ... its rows
+  bool zero = true;                     // ... and: the rig was set behind the last table - it is one row of zeros, made where the rig goes up
+};
+
 struct mgf_batch {
   mgf_ctx* ctx = nullptr;
   mgf_params params;
@@ -105,9 +115,9 @@ struct mgf_batch {
   BatchRig<mgf_batch_feeler> feelers;   // on the device: items | records | order | worlds - the feelers (host_batch_feeler.inc)
   BatchRig<mgf_batch_actuator> actuators;  // on the device: runs | records | order - the actuators; `items` holds the runs of one body (host_batch_actuator.inc)
   BatchRig<mgf_batch_spring> springs;   // on the device: runs | records | order - the springs; `items` holds the runs of one body's ENDS, `order` the ends (host_batch_spring.inc)
-  BatchRig<mgf_batch_joint> joints;     // on the device: items | records | plan, slots - the ball joints; `items` holds a world's joints each, `order` the plan and the slots (host_batch_joint.inc)
-  BatchRig<mgf_batch_hinge> hinges;     // on the device: items | records | plan, slots - the hinges, laid out as the ball joints are (host_batch_hinge.inc)
-  BatchRig<mgf_batch_slider> sliders;   // on the device: items | records | plan, slots - the sliders, laid out as the ball joints are (host_batch_slider.inc)
+  BatchJointRig<mgf_batch_joint> joints;   // on the device: items | records | plan, slots - the ball joints; `items` holds a world's joints each, `order` the plan and the slots (host_batch_joint.inc)
+  BatchJointRig<mgf_batch_hinge> hinges;   // on the device: items | records | plan, slots - the hinges, laid out as the ball joints are (host_batch_hinge.inc)
+  BatchJointRig<mgf_batch_slider> sliders;  // on the device: items | records | plan, slots - the sliders, laid out as the ball joints are (host_batch_slider.inc)
   // ... and what a call on one of them has nowhere else to put
   DBuf<float> s_parts;                  // the particles of a sensor cast: 7 words a sensor
   size_t c_pixels = 0;                  // the pixels of the camera rig, camera by camera
@@ -120,22 +130,10 @@ struct mgf_batch {
   DBuf<unsigned long long> a_skipped;   // actuators whose gain * clamp(u) was not finite, cumulative (counter "actuators_skipped")
   DBuf<float> sp_wr;                    // the impulses of the springs, twelve floats a spring: written by one launch of a call, applied by the next
   DBuf<unsigned long long> sp_skipped;  // springs whose wrench was zeroed (len == 0, len or f * h not finite), cumulative (counter "springs_skipped")
-  DBuf<float> j_acc;                    // the impulses of the joints over a call, three floats a joint
-  DBuf<unsigned long long> j_skipped;   // joints that were skipped (a singular K, a word of the setup not finite), cumulative (counter "joints_skipped")
-  DBuf<float> hg_acc;                   // the impulses of the hinges over a call, eight floats a hinge
-  DBuf<unsigned long long> hg_skipped;  // hinges that were skipped, cumulative (counter "hinges_skipped")
-  DBuf<float> hg_w;                     // the motors' target table, hg_rows rows of a float a hinge (mgf_batch_set_hinge_targets)
-  int64_t hg_rows = 1;                  // ... its rows
-  bool hg_zero = true;                  // ... and: the rig was set behind the last table - it is one row of zeros, made where the rig goes up
   DBuf<float4> ht_tab;                  // the hinges' readings table, ht_rows rows of an entry a hinge: two words, four with the impulses (mgf_batch_set_hinge_trace)
   int64_t ht_rows = 0;                  // ... its rows; 0: no trace (host_batch_hinge_read.inc)
   int32_t ht_format = 0;                // ... and MGF_HINGE_TRACE_READING / _FULL
   DBuf<float4> ht_out;                  // what the host-memory read of the hinges downloads: two words a hinge
-  DBuf<float> sg_acc;                   // the impulses of the sliders over a call, eight floats a slider
-  DBuf<unsigned long long> sg_skipped;  // sliders that were skipped, cumulative (counter "sliders_skipped")
-  DBuf<float> sg_w;                     // the motors' target table, sg_rows rows of a float a slider (mgf_batch_set_slider_targets)
-  int64_t sg_rows = 1;                  // ... its rows
-  bool sg_zero = true;                  // ... and: the rig was set behind the last table - it is one row of zeros, made where the rig goes up
   // the rollouts (host_batch_rollout.inc)
   DBuf<uint32_t> d_act;                 // per world, beside d_done: ticks of the call whose actuation the world has behind it (k_batch_rollout.h)
   int64_t r_launches = 0;               // launches of the last rollout call beyond its ticks' own (counter "rollout_launches")
@@ -323,6 +321,14 @@ extern "C" mgf_status mgf_batch_set_option(mgf_batch* b, const char* key, int64_
   }
   return fail(MGF_ERR_INVALID, "unknown batch option");
 }
+// a joint rig's skip counter (on the device: the stream is waited for)
+template <class Rec>
+static mgf_status batch_joint_skipped(const mgf_batch* b, const BatchJointRig<Rec>& R, int64_t* out) {
+  unsigned long long v = 0;
+  if (R.skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, R.skipped.p, 1)); }
+  *out = (int64_t)v;
+  return MGF_OK;
+}
 extern "C" mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, int64_t* out) {
   if (!b || !name || !out) return fail(MGF_ERR_INVALID, "NULL argument");
   if (!strcmp(name, "launches_per_tick")) { *out = b->parts ? 7 : 6; return MGF_OK; }
@@ -350,24 +356,9 @@ extern "C" mgf_status mgf_batch_counter(const mgf_batch* b, const char* name, in
     *out = (int64_t)v;
     return MGF_OK;
   }
-  if (!strcmp(name, "joints_skipped")) {  // (on the device: the stream is waited for)
-    unsigned long long v = 0;
-    if (b->j_skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, b->j_skipped.p, 1)); }
-    *out = (int64_t)v;
-    return MGF_OK;
-  }
-  if (!strcmp(name, "hinges_skipped")) {  // (on the device: the stream is waited for)
-    unsigned long long v = 0;
-    if (b->hg_skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, b->hg_skipped.p, 1)); }
-    *out = (int64_t)v;
-    return MGF_OK;
-  }
-  if (!strcmp(name, "sliders_skipped")) {  // (on the device: the stream is waited for)
-    unsigned long long v = 0;
-    if (b->sg_skipped.p) { MGF_TRY(ctx_bind(b->ctx)); MGF_TRY(d2h(b->ctx, &v, b->sg_skipped.p, 1)); }
-    *out = (int64_t)v;
-    return MGF_OK;
-  }
+  if (!strcmp(name, "joints_skipped")) return batch_joint_skipped(b, b->joints, out);
+  if (!strcmp(name, "hinges_skipped")) return batch_joint_skipped(b, b->hinges, out);
+  if (!strcmp(name, "sliders_skipped")) return batch_joint_skipped(b, b->sliders, out);
   return fail(MGF_ERR_INVALID, "unknown batch counter");
 }
 
@@ -903,21 +894,19 @@ static mgf_status batch_collide_parts(mgf_batch* b, const BatchArgs& A, uint32_t
 // What a rollout (host_batch_rollout.inc, k_batch_rollout.h) hangs into the step's launch train: row t of the controls applied ahead of
 // tick t's launches, row t of the traces written behind them - both under the train's own gate, so that they are skipped and run again
 // world by world as the tick's launches are.
+// ... and of one kind of joints (host_batch_joint.inc): its launch, solved behind the actuation and ahead of the tick, which integrates what it leaves
+struct BatchJointHook {
+  BatchJointArgs A;  // out, h and iters; the train fills the rest in, the handle's view per PASS, the target table's row per TICK
+  uint32_t lds = 0;  // ... and its dynamic LDS
+  bool on = false;   // the rig is not empty
+};
 struct BatchRolloutHook {
   BatchRolloutArgs A;    // everything but done, act, tick and count, which the train fills in
   int32_t mode = 0;      // MGF_ACTUATE_IMPULSE / _FORCE
   bool act = false;      // the rig is not empty: k_batch_rollout_act ahead of every tick
   BatchSpringArgs S;     // the springs' two launches (k_batch_spring.h), everything but done, act and tick
   bool springs = false;  // the spring rig is not empty: they go ahead of the actuation, which a damper must not see
-  BatchJointArgs J;      // the joints' launch (k_batch_joint.h): out, h and iters; the train fills the rest in, the handle's view per PASS
-  uint32_t joint_lds = 0;  // ... and its dynamic LDS
-  bool joints = false;   // the joint rig is not empty: solved behind the actuation and ahead of the tick, which integrates what they leave
-  BatchHingeArgs G;      // the hinges' launch (k_batch_hinge.h): out, h and iters; the train fills the rest in, the handle's view per PASS, the table's row per TICK
-  uint32_t hinge_lds = 0;  // ... and its dynamic LDS
-  bool hinges = false;   // the hinge rig is not empty: solved behind the ball joints and ahead of the tick
-  BatchSliderArgs Z;     // the sliders' launch (k_batch_slider.h): out, h and iters; the train fills the rest in, the handle's view per PASS, the table's row per TICK
-  uint32_t slider_lds = 0;  // ... and its dynamic LDS
-  bool sliders = false;  // the slider rig is not empty: solved behind the hinges and ahead of the tick
+  BatchJointHook joints, hinges, sliders;  // k_batch_joint.h, k_batch_hinge.h, k_batch_slider.h: solved in this order
   BatchTraceTouchArgs T;  // the touch trace (k_batch_trace.h): V.out - row 0 - and n_touch; the train fills the rest in, the lists' view per PASS
   int32_t touch = -1;    // MGF_ROLLOUT_TOUCH_FULL / _SHORT: k_batch_trace_touch behind every tick's record; -1: no touch trace
   BatchSensorArgs R;     // the sensor trace's cast (k_batch_scan.h): mask, out and parts - the handle's scratch; the train fills the rest in per PASS
@@ -927,10 +916,15 @@ struct BatchRolloutHook {
   int32_t hinge_read = -1;  // kHingeReadReading / _Full / _FullZero: k_batch_read_hinges behind every tick t < the table's rows; -1: no hinge trace
   int64_t launches = 0;  // what the hook added to the train's launches
 };
-static void batch_joint_view(const mgf_batch* b, BatchJointArgs* A);  // (host_batch_joint.inc, behind this file) what the joints' kernel reads of the handle
-static void batch_hinge_view(const mgf_batch* b, BatchHingeArgs* A);  // (host_batch_hinge.inc, behind this file) what the hinges' kernel reads of the handle
+// (host_batch_joint.inc, _hinge.inc, _slider.inc, behind this file) the kinds of joints, and a kind's part of the train: per pass what its kernel reads of the handle, per tick its launch
+struct JointKind;
+struct HingeKind;
+struct SliderKind;
+template <class T>
+static void batch_joint_pass(const mgf_batch* b, BatchJointHook& H);
+template <class T>
+static mgf_status batch_joint_tick(mgf_batch* b, BatchJointHook& H, uint32_t t, int64_t* launches);
 static void batch_hinge_read_view(const mgf_batch* b, BatchHingeReadArgs* A);  // (host_batch_hinge_read.inc, behind this file) what the hinge trace's kernel reads of the handle
-static void batch_slider_view(const mgf_batch* b, BatchSliderArgs* A);  // (host_batch_slider.inc, behind this file) what the sliders' kernel reads of the handle
 static uint32_t batch_touch_tile(const mgf_batch* b);  // (host_batch_touch.inc, behind this file) the words of dynamic LDS the contact sensors' fold stages
 // (host_batch_query.inc, behind this file) the dynamic LDS of a ray cast with a workgroup per work item; what a cast reads of the handle; has it obstacles to meet
 static uint32_t batch_ray_lds(const mgf_batch* b);
@@ -986,17 +980,10 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
     A.done = b->d_done.p; A.need = b->d_need.p; A.c_count = b->d_ccount.p; A.err = b->d_err.p; A.stats = b->d_stats.p;
     A.n_worlds = K; A.iters = (uint32_t)iters;
     A.dt = dt; A.fat_margin = b->params.fat_margin; A.baumgarte = b->params.baumgarte; A.slop = b->params.penetration_slop;
-    if (hook && hook->joints) {  // (looked up again for every pass, as the views below are)
-      batch_joint_view(b, &hook->J);
-      hook->J.done = b->d_done.p; hook->J.act = b->d_act.p;
-    }
-    if (hook && hook->hinges) {
-      batch_hinge_view(b, &hook->G);
-      hook->G.done = b->d_done.p; hook->G.act = b->d_act.p;
-    }
-    if (hook && hook->sliders) {
-      batch_slider_view(b, &hook->Z);
-      hook->Z.done = b->d_done.p; hook->Z.act = b->d_act.p;
+    if (hook) {  // (looked up again for every pass, as the views below are)
+      batch_joint_pass<JointKind>(b, hook->joints);
+      batch_joint_pass<HingeKind>(b, hook->hinges);
+      batch_joint_pass<SliderKind>(b, hook->sliders);
     }
     if (hook && hook->hinge_read >= 0) {  // (the same rule for the hinge trace: the rig, the impulse buffer and the TABLE are looked up again for every pass)
       batch_hinge_read_view(b, &hook->E);
@@ -1046,25 +1033,10 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
         LAUNCH_CHECK();
         ++hook->launches;
       }
-      if (hook && hook->joints) {  // (behind every external impulse and just ahead of the integration; the springs' gate: `act` moves behind the tick)
-        hook->J.tick = t;
-        k_batch_joint_solve<true><<<(unsigned)b->joints.items.size(), kBatchBlock, hook->joint_lds, s>>>(hook->J);
-        LAUNCH_CHECK();
-        hook->launches += MGF_BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK;
-      }
-      if (hook && hook->hinges) {  // (behind the ball joints, under their gate; tick t reads the target table's row min(t, rows - 1))
-        hook->G.tick = t;
-        hook->G.w = b->hg_w.p + (size_t)std::min<int64_t>((int64_t)t, b->hg_rows - 1) * b->hinges.recs.size();
-        k_batch_hinge_solve<true><<<(unsigned)b->hinges.items.size(), kBatchBlock, hook->hinge_lds, s>>>(hook->G);
-        LAUNCH_CHECK();
-        hook->launches += MGF_BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK;
-      }
-      if (hook && hook->sliders) {  // (behind the hinges, under their gate; tick t reads the target table's row min(t, rows - 1))
-        hook->Z.tick = t;
-        hook->Z.w = b->sg_w.p + (size_t)std::min<int64_t>((int64_t)t, b->sg_rows - 1) * b->sliders.recs.size();
-        k_batch_slider_solve<true><<<(unsigned)b->sliders.items.size(), kBatchBlock, hook->slider_lds, s>>>(hook->Z);
-        LAUNCH_CHECK();
-        hook->launches += MGF_BATCH_ROLLOUT_SLIDER_LAUNCHES_PER_TICK;
+      if (hook) {  // (behind every external impulse and just ahead of the integration: the ball joints, behind them the hinges, behind them the sliders, under one gate)
+        MGF_TRY(batch_joint_tick<JointKind>(b, hook->joints, t, &hook->launches));
+        MGF_TRY(batch_joint_tick<HingeKind>(b, hook->hinges, t, &hook->launches));
+        MGF_TRY(batch_joint_tick<SliderKind>(b, hook->sliders, t, &hook->launches));
       }
       if (b->parts) MGF_TRY(batch_collide_parts(b, A, nmax));
       else MGF_TRY(batch_collide(b, A, nmax));

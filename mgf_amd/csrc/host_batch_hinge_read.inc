@@ -19,21 +19,18 @@ static void batch_hinge_read_view(const mgf_batch* b, BatchHingeReadArgs* A) {
   A->B = b->bodies(0);
   A->w_off = b->d_off.p;
   A->rig = R.dev.p + R.off[1];
-  A->acc = reinterpret_cast<const float4*>(b->hg_acc.p);
+  A->acc = reinterpret_cast<const float4*>(b->hinges.acc.p);
   A->n = (uint32_t)R.recs.size();
 }
 
 // What the launch reads, behind batch_push (n > 0): the rig up - by batch_hinge_ready's steps - and the impulse buffer there.
 // Shared with the rollouts, whose train fills done, act, tick and the table's row in.
 static mgf_status batch_hinge_read_ready(mgf_batch* b, BatchHingeReadArgs* A) {
-  BatchRig<mgf_batch_hinge>& R = b->hinges;
+  BatchJointRig<mgf_batch_hinge>& R = b->hinges;
   const size_t n = R.recs.size();
-  if (R.stale)  // (bodies may have been added: the far ends against the lengths that go up, as batch_rig_up holds `body`)
-    for (size_t i = 0; i < n; ++i)
-      if (R.recs[i].other >= 0 && (uint32_t)R.recs[i].other >= b->h_n[(size_t)R.recs[i].world])
-        return fail(MGF_ERR_INVALID, "internal error: a hinge's other is outside its world");
+  MGF_TRY(batch_joint_far_ends<HingeKind>(b));  // (bodies may have been added)
   MGF_TRY(batch_rig_up(b, R, "hinge", 3));
-  MGF_TRY(b->hg_acc.ensure(8 * n, b->ctx->stream));
+  MGF_TRY(R.acc.ensure(8 * n, b->ctx->stream));
   static_assert(sizeof(mgf_hinge_reading) == 32 && sizeof(float4) == 16, "k_batch_read_hinges writes a reading as two words of 16 bytes");
   memset(A, 0, sizeof(*A));
   batch_hinge_read_view(b, A);

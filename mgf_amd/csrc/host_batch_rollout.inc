@@ -20,14 +20,11 @@
 
 // (host_batch_spring.inc, behind this file) the springs' arguments for the train: the rig up, the wrench buffer and the skip counter there
 static mgf_status batch_spring_ready(mgf_batch* b, float h, float* out_dev, BatchSpringArgs* A);
-// (host_batch_joint.inc, behind this file) the joints' arguments for the train: the rig up, the impulse buffer and the skip counter there
-static mgf_status batch_joint_ready(mgf_batch* b, float h, int32_t iters, float* out_dev, BatchJointArgs* A, uint32_t* lds);
-// (host_batch_hinge.inc, behind this file) the hinges' arguments for the train: the rig and the target table up, the impulse buffer and the skip counter there
-static mgf_status batch_hinge_ready(mgf_batch* b, float h, int32_t iters, float* out_dev, BatchHingeArgs* A, uint32_t* lds);
+// (host_batch_joint.inc, behind this file) a kind of joints' arguments for the train: the rig and the target table up, the impulse buffer and the skip counter there
+template <class T>
+static mgf_status batch_joint_hook(mgf_batch* b, float h, int32_t iters, BatchJointHook* H);
 // (host_batch_hinge_read.inc, behind this file) the hinge trace's arguments for the train: the rig up, the impulse buffer there
 static mgf_status batch_hinge_read_ready(mgf_batch* b, BatchHingeReadArgs* A);
-// (host_batch_slider.inc, behind this file) the sliders' arguments for the train: the rig and the target table up, the impulse buffer and the skip counter there
-static mgf_status batch_slider_ready(mgf_batch* b, float h, int32_t iters, float* out_dev, BatchSliderArgs* A, uint32_t* lds);
 
 struct RolloutBytes { size_t u, body, out[4], touch, sensor; };  // what the call touches of u, body, x, q, v, omega, touch, sensor
 // the touch trace of mgf_batch_rollout_touches / _touches_dev (host_batch_trace.inc): rows of n reports, device memory when it reaches the core.
@@ -133,18 +130,9 @@ static mgf_status batch_rollout_run(mgf_batch* b, float dt, int32_t iters, int64
     MGF_TRY(batch_spring_ready(b, dt, nullptr, &H.S));
     H.springs = true;
   }
-  if (joints && iters > 0) {  // (iters == 0: mgf_batch_solve_joints_dev enqueues nothing)
-    MGF_TRY(batch_joint_ready(b, dt, iters, nullptr, &H.J, &H.joint_lds));
-    H.joints = true;
-  }
-  if (hinges && iters > 0) {  // (iters == 0: mgf_batch_solve_hinges_dev enqueues nothing)
-    MGF_TRY(batch_hinge_ready(b, dt, iters, nullptr, &H.G, &H.hinge_lds));
-    H.hinges = true;
-  }
-  if (sliders && iters > 0) {  // (iters == 0: mgf_batch_solve_sliders_dev enqueues nothing)
-    MGF_TRY(batch_slider_ready(b, dt, iters, nullptr, &H.Z, &H.slider_lds));
-    H.sliders = true;
-  }
+  MGF_TRY(batch_joint_hook<JointKind>(b, dt, iters, &H.joints));  // (where the rig is not empty and iters > 0: with iters == 0 the solve calls enqueue nothing)
+  MGF_TRY(batch_joint_hook<HingeKind>(b, dt, iters, &H.hinges));
+  MGF_TRY(batch_joint_hook<SliderKind>(b, dt, iters, &H.sliders));
   if (hinges && b->ht_rows > 0) {  // (the readings table has rows: k_batch_read_hinges behind every tick t < rows; with iters == 0 no solve wrote an impulse)
     MGF_TRY(batch_hinge_read_ready(b, &H.E));
     H.hinge_read = b->ht_format == MGF_HINGE_TRACE_FULL ? (iters > 0 ? kHingeReadFull : kHingeReadFullZero) : kHingeReadReading;

@@ -1,49 +1,40 @@
-// The frame lines of a hinge's SETUP (include/mgf_hip.h, "hinge joints between bodies"), written once for the kernels that form a hinge's
-// frames without solving it (k_batch_hinge_read.h).  (Part of the kernel set described in kernels.h.)
+// The frame lines of a hinge's SETUP (include/mgf_hip.h, "hinge joints between bodies"), written once for every kernel that forms a
+// hinge's frames: the hinges' solver (k_batch_hinge.h), the sliders', whose frames are the same lines (k_batch_slider.h), and the
+// hinges' encoders, which form them without solving (k_batch_hinge_read.h).  (Part of the kernel set described in kernels.h.)
 //
 // Every helper is the header's line, the same helpers (rotate, cross, dot) in the same order, each a separately rounded f32 operation
-// (-ffp-contract=off): what they give is bit for bit what k_batch_hinge_solve's setup forms of the same state.  k_batch_hinge.h keeps
-// its own copy of these lines, as it was written.
-//   hinge_end     one end as the state stands: q, x + delta (physics.rs:282, as k_batch_dev_gather) and omega (srec words 0 and 1)
-//   hinge_frame   ra, rb, Pa, Pb, C, A, T1, T2, B, U1 of the record's words; other == -1: B = bx, U1 = ub, Pb = pb
+// (-ffp-contract=off): the encoders read bit for bit what the solver's setup forms of the same state.  The ends are loaded by
+// joint_ends (k_batch_joint_loop.h), the ball joints' too.
+//   hinge_frame   ra, rb, C, A, T1, T2, B, U1 of the record's words; other == -1: rb = 0, Pb = pb, B = bx, U1 = ub
 //   hinge_side    cphi, sphi and the limit's side: +1 or -1 by SETUP's rule with LIMIT and cphi <= ch, otherwise 0
 #pragma once
-#include "k_batch_hinge.h"
+#include "k_batch_joint.h"
 
 namespace mgf {
 
-struct HingeEnd {
-  Quat q;
-  V3 x, om;
-};
+constexpr uint32_t kHingeLimit = 1u, kHingeMotor = 2u;  // MGF_HINGE_LIMIT, MGF_HINGE_MOTOR
+
 struct HingeFrame {
-  V3 C, A, T1, T2, B, U1;
+  V3 ra, rb, C, A, T1, T2, B, U1;
 };
 
-__device__ __forceinline__ HingeEnd hinge_end(const Bodies& B, size_t g) {
-  const float4 q = B.q[g], s0 = B.srec[4 * g], s1 = B.srec[4 * g + 1];
-  HingeEnd e;
-  e.q = mkq(q.x, mk3(q.y, q.z, q.w));
-  e.x = xyz(B.x[g]) + xyz(B.delta[g]);
-  e.om = mk3(s0.w, s1.x, s1.y);
-  return e;
-}
-
-// w1 .. w6: the record's words (pa, beta), (pb, tmax), (ax, cm), (ua, sm), (bx, ch), (ub, sh); b is read where has_b alone
-__device__ __forceinline__ HingeFrame hinge_frame(const HingeEnd& a, const HingeEnd& b, bool has_b, float4 w1, float4 w2, float4 w3, float4 w4, float4 w5,
+// a, b: the ends (joint_ends); w1 .. w6: the record's words (pa, beta), (pb, tmax), (ax, cm), (ua, sm), (bx, ch), (ub, sh); b is read
+// where has_b alone
+__device__ __forceinline__ HingeFrame hinge_frame(const JointEnd& a, const JointEnd& b, bool has_b, float4 w1, float4 w2, float4 w3, float4 w4, float4 w5,
                                                   float4 w6) {
   HingeFrame F;
-  const V3 ra = rotate(a.q, xyz(w1));
-  const V3 Pa = a.x + ra;
+  F.ra = rotate(a.q, xyz(w1));
+  const V3 Pa = a.x + F.ra;
   F.A = rotate(a.q, xyz(w3));
   F.T1 = rotate(a.q, xyz(w4));
   F.T2 = cross(F.A, F.T1);
+  F.rb = mk3(0.0f, 0.0f, 0.0f);
   V3 Pb = xyz(w2);
   F.B = xyz(w5);
   F.U1 = xyz(w6);
   if (has_b) {
-    const V3 rb = rotate(b.q, xyz(w2));
-    Pb = b.x + rb;
+    F.rb = rotate(b.q, xyz(w2));
+    Pb = b.x + F.rb;
     F.B = rotate(b.q, xyz(w5));
     F.U1 = rotate(b.q, xyz(w6));
   }

@@ -53,12 +53,8 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_read_hinges(BatchHingeRea
   const float4 w1 = rec[1], w2 = rec[2], w3 = rec[3], w4 = rec[4], w5 = rec[5], w6 = rec[6];
   const size_t g0 = A.w_off[k];
   const bool has_b = f2u(w0.z) != 0xFFFFFFFFu;  // other == -1: the far end is the world
-  const HingeEnd a = hinge_end(A.B, g0 + f2u(w0.y));
-  HingeEnd b;
-  b.q = mkq(1.0f, mk3(0.0f, 0.0f, 0.0f));
-  b.x = mk3(0.0f, 0.0f, 0.0f);
-  b.om = b.x;
-  if (has_b) b = hinge_end(A.B, g0 + f2u(w0.z));
+  JointEnd a, b;
+  joint_ends(A.B, g0, w0, has_b, &a, &b);
   const HingeFrame F = hinge_frame(a, b, has_b, w1, w2, w3, w4, w5, w6);
   const float c = dot(F.U1, F.T1), sn = dot(F.U1, F.T2);
   const float rate = dot(b.om - a.om, F.A);

@@ -174,6 +174,9 @@
 //                      products - into the handle's buffer; then a lane per run of one body's ends, sorted on the host when the rig
 //                      is set, applies them in list order with batch_drive_apply's arithmetic; no float atomic.  GATED: under the
 //                      rollout train's gate done[k] == tick && act[k] == tick, folded into the run length
+//   batch_joint_loop<Rows, GATED> (k_batch_joint_loop.h) - no kernel: the skeleton of the three joint solvers below, each of which is
+//                      one call of it - the gate, the slots' load, the plan's words, the dataflow loop with its bounded spin, the
+//                      store-back and the impulse row - over a Rows type that holds the kind's registers, setup, rows and store
 //   k_batch_joint_solve<GATED> (k_batch_joint.h)
 //                      ball joints between two body-fixed points, or one and a point of the world (mgf_batch_set_joints /
 //                      _solve_joints / _solve_joints_dev, and between the actuation and the tick of a rollout): sequential impulses
@@ -250,6 +253,7 @@
 #include "k_batch_actuator.h"  // actuators: wrenches formed from the resident poses and applied, a lane per body (k_batch_actuate)
 #include "k_batch_rollout.h"  // rollouts: a row of controls ahead of every tick of a step call, a row of state behind it (k_batch_rollout_act, _record)
 #include "k_batch_spring.h"  // springs between bodies: impulses formed from the resident state, applied a lane per body (k_batch_spring_wrench, _apply)
+#include "k_batch_joint_loop.h"  // the joint solvers' skeleton: one launch shape and one dataflow loop over a Rows type (batch_joint_loop)
 #include "k_batch_joint.h"  // ball joints between bodies: sequential impulses over the resident velocities, a workgroup per world (k_batch_joint_solve)
 #include "k_batch_hinge.h"  // hinge joints between bodies: the joints' launch with motor, limit, angular and point rows (k_batch_hinge_solve)
 #include "k_batch_hinge_read.h"  // hinge encoders: angle, rate, limit side, gap and tilt from the resident state, a lane per hinge (k_batch_read_hinges)

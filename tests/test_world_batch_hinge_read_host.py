@@ -151,7 +151,8 @@ def test_what_needs_no_device_is_refused_in_the_headers_order():
     assert run.count("<<<") == 1 and run.index("batch_push(") < run.index("batch_hinge_read_ready(") < run.index("k_batch_read_hinges<false, kHingeReadReading><<<")
     assert "b->d_launches += MGF_BATCH_HINGE_READ_LAUNCHES;" in run and "batch_single_parts(" not in src      # a reading reads no shapes
     ready = src[src.index("static mgf_status batch_hinge_read_ready("):src.index("static mgf_status batch_hinge_read_run(")]
-    assert ready.index("(uint32_t)R.recs[i].other >= b->h_n[(size_t)R.recs[i].world]") < ready.index('batch_rig_up(b, R, "hinge", 3)')
+    assert ready.index("batch_joint_far_ends<HingeKind>(b)") < ready.index('batch_rig_up(b, R, "hinge", 3)')   # (the joint rigs' check of the far ends: `other` against the lengths that go up)
+    assert "(uint32_t)R.recs[i].other >= b->h_n[(size_t)R.recs[i].world]" in read("mgf_amd", "csrc", "host_batch_joint.inc")
     # the table: the refusals in the header's order, ahead of the context and of everything that changes the table
     st = src[src.index('extern "C" mgf_status mgf_batch_set_hinge_trace('):src.index('extern "C" int64_t mgf_batch_hinge_trace_rows(')]
     order = [st.index(s) for s in ("batch_rig_handle(b)", "rows < 0 || rows > (1 << 20)", "format != MGF_HINGE_TRACE_READING && format != MGF_HINGE_TRACE_FULL",
@@ -269,7 +270,7 @@ def test_the_kernel_is_a_lane_per_hinge_with_its_own_gate_ahead_of_every_load_of
     body = body[:body.index("\n}\n")]
     gate = "if (GATED && !(A.done[k] == A.tick + 1u && A.act[k] <= A.tick + 1u)) return;"
     assert gate in body and "template <bool GATED, int FORMAT>" in k
-    for load in ("hinge_end(", "rec[1]", "A.w_off[", "A.acc["):
+    for load in ("joint_ends(", "rec[1]", "A.w_off[", "A.acc["):
         assert body.index(gate) < body.index(load), load
     assert body.index("if (i >= A.n) return;") < body.index("rec[0]") < body.index(gate)
     assert not re.search(r"atomic|__shared__|__syncthreads|s_dyn|A\.plan|A\.slots|A\.items| / ", body)       # no plan, no LDS, no atomic, no division
@@ -280,13 +281,16 @@ def test_the_kernel_is_a_lane_per_hinge_with_its_own_gate_ahead_of_every_load_of
     assert stores == ["o[0] = ", "o[1] = ", "o[2] = ", "o[3] = ", "o[2] = ", "o[3] = "] and "float4* o = A.out" in body
     assert body.count("FORMAT == kHingeReadFull)") == 1 and body.count("FORMAT == kHingeReadFullZero)") == 1
     assert len(re.findall(r"__global__ __launch_bounds__\(kBatchBlock\)", k)) == len(re.findall(r"__global__", k)) == 1
-    # the frame lines are lifted, not pasted: written once in a header of their own, which the solver's header does not include
+    # the frame lines are lifted, not pasted: written once in a header of their own, which the hinges' solver uses too (and through it
+    # the sliders'); an end is loaded by the joint solvers' joint_end
     frame = read("mgf_amd", "csrc", "k_batch_hinge_frame.h")
     assert '#include "k_batch_hinge_frame.h"' in k and "rotate(" not in body and "cross(" not in body
-    for fn in ("HingeEnd hinge_end(", "HingeFrame hinge_frame(", "float hinge_side("):
+    for fn in ("HingeFrame hinge_frame(", "float hinge_side("):
         assert "__device__ __forceinline__ " + fn in frame, fn
+    assert "__device__ __forceinline__ JointEnd joint_end(" in read("mgf_amd", "csrc", "k_batch_joint_loop.h") and "srec[" not in frame and "srec[" not in body
     assert "F.T2 = cross(F.A, F.T1);" in frame and "F.C = Pb - Pa;" in frame and "cphi <= ch" in frame and "__global__" not in frame
-    assert "k_batch_hinge_frame.h" not in read("mgf_amd", "csrc", "k_batch_hinge.h")
+    solver = re.sub(r"//[^\n]*", "", read("mgf_amd", "csrc", "k_batch_hinge.h"))
+    assert '#include "k_batch_hinge_frame.h"' in solver and "hinge_frame(a, b, has_b, w1, w2, w3, w4, w5, w6)" in solver and "rotate(" not in solver   # no second copy
 
 
 def test_the_new_kernel_uses_no_scratch_and_spills_nothing_and_the_solvers_are_as_they_were():
@@ -301,11 +305,11 @@ def test_the_new_kernel_uses_no_scratch_and_spills_nothing_and_the_solvers_are_a
         assert int(v[0]) < 105, (name, v)                                                  # far fewer than the solve's
         assert "`%s` %s / %s / 0 / 0 / 0" % (name, v[0], v[1]) in design, (name, v)
     # the solvers' kernels are what tests/test_world_batch_hinges_host.py expects of them: untouched
-    old = kernel_resources("k_batch_hinge_solve")
-    assert old == {"k_batch_hinge_solve<false>": ("105", "67", "0", "16", "0", "0"), "k_batch_hinge_solve<true>": ("105", "67", "0", "16", "0", "0")}, old
+    old = kernel_resources("k_batch_hinge_solve")                                         # (105 / 67 and 80 / 60 until the three solvers became one skeleton)
+    assert old == {"k_batch_hinge_solve<false>": ("103", "55", "0", "16", "0", "0"), "k_batch_hinge_solve<true>": ("103", "55", "0", "16", "0", "0")}, old
     assert set(kernel_resources("k_batch_hinge")) == set(old)                             # (that test selects them by this substring)
     old = kernel_resources("k_batch_joint")
-    assert old == {"k_batch_joint_solve<false>": ("80", "60", "0", "16", "0", "0"), "k_batch_joint_solve<true>": ("80", "60", "0", "16", "0", "0")}, old
+    assert old == {"k_batch_joint_solve<false>": ("78", "51", "0", "16", "0", "0"), "k_batch_joint_solve<true>": ("78", "51", "0", "16", "0", "0")}, old
 
 
 # ---- 5 ------------------------------------------------------------------------------------------------------------------------------------
@@ -314,7 +318,7 @@ def test_the_rollout_launches_the_read_once_behind_the_record_under_t_below_rows
     roll = read("mgf_amd", "csrc", "host_batch_rollout.inc")
     core = roll[roll.index("static mgf_status batch_rollout_run("):roll.index('extern "C" mgf_status mgf_batch_rollout_dev(')]
     arm = "if (hinges && b->ht_rows > 0) {"
-    assert (core.index("batch_push(") < core.index("batch_hinge_ready(") < core.index(arm) < core.index("batch_hinge_read_ready(b, &H.E)")
+    assert (core.index("batch_push(") < core.index("batch_joint_hook<HingeKind>(") < core.index(arm) < core.index("batch_hinge_read_ready(b, &H.E)")
             < core.index("batch_step_run(b, dt, iters, n_ticks, stats, &H)"))
     assert "b->ht_format == MGF_HINGE_TRACE_FULL ? (iters > 0 ? kHingeReadFull : kHingeReadFullZero) : kHingeReadReading" in core   # iters == 0: no solve, zeros
     assert core.count("batch_hinge_read_ready(") == 1 and "hinge_read" not in roll[roll.index('extern "C" mgf_status mgf_batch_rollout_dev('):]   # no entry point changes
@@ -331,7 +335,7 @@ def test_the_rollout_launches_the_read_once_behind_the_record_under_t_below_rows
     assert "hook->E.done = b->d_done.p; hook->E.act = b->d_act.p;" in train
     view = read("mgf_amd", "csrc", READ_FILE)
     view = view[view.index("static void batch_hinge_read_view("):view.index("// What the launch reads")]
-    for word in ("A->B = b->bodies(0);", "A->w_off = b->d_off.p;", "A->rig = R.dev.p + R.off[1];", "A->acc = reinterpret_cast<const float4*>(b->hg_acc.p);"):
+    for word in ("A->B = b->bodies(0);", "A->w_off = b->d_off.p;", "A->rig = R.dev.p + R.off[1];", "A->acc = reinterpret_cast<const float4*>(b->hinges.acc.p);"):
         assert word in view, word
     step = host[host.index('extern "C" mgf_status mgf_batch_step('):host.index('extern "C" mgf_status mgf_batch_read_constraints(')]
     assert "batch_step_run(b, dt, iters, n_ticks, stats, nullptr)" in step and "hinge" not in step   # mgf_batch_step traces nothing

@@ -200,7 +200,7 @@ def test_the_seeded_rig_holds_every_case_and_its_dataflow_gives_the_sequential_o
     assert other[1].tobytes() != want[1].tobytes()
     # the host's plan is the ball joints': one template, both record types
     src = read("mgf_amd", "csrc", "host_batch_joint.inc")
-    assert "template <class Rec>\nstatic void batch_joint_plan(BatchRig<Rec>& R, const Rec* recs, size_t n) {" in src
+    assert "template <class Rec>\nstatic void batch_joint_plan(BatchJointRig<Rec>& R, const Rec* recs, size_t n) {" in src
     assert "batch_joint_plan(b->hinges, j, n);" in read("mgf_amd", "csrc", RIG_FILE)
 
 
@@ -316,50 +316,42 @@ def test_what_needs_no_device_is_refused_in_the_headers_order_with_the_rig_uncha
     src = read("mgf_amd", "csrc", RIG_FILE)
     body = src[src.index('extern "C" mgf_status mgf_batch_set_hinges('):src.index('extern "C" int64_t mgf_batch_hinge_count(')]
     plan_call = "batch_joint_plan(b->hinges, j, n);"
-    marks = ["batch_rig_set_args(b, j, n_in)", 'batch_rig_ref_check(b, r.world, r.body, 0, "hinge")', "r.other < -1 || (r.other >= 0 && (uint32_t)r.other >= b->h_n[(size_t)r.world])",
-             "r.other == r.body", "r.flags & ~(uint32_t)(MGF_HINGE_LIMIT | MGF_HINGE_MOTOR)", "a word of a hinge is not finite (tmax may be +inf): the rig was not changed",
+    # (the two checks of `other`, with their two refusals, are the joint rigs' shared step; the plan step makes the table one row of zeros:
+    # tests/test_world_batch_joint_family_host.py)
+    marks = ["batch_rig_set_args(b, j, n_in)", 'batch_rig_ref_check(b, r.world, r.body, 0, "hinge")', "batch_joint_other_check<HingeKind>(b, r)",
+             "r.flags & ~(uint32_t)(MGF_HINGE_LIMIT | MGF_HINGE_MOTOR)", "a word of a hinge is not finite (tmax may be +inf): the rig was not changed",
              "a hinge's beta is not in [0, 1]: the rig was not changed", "a hinge's tmax is negative: the rig was not changed", "is not of unit length: the rig was not changed",
              "is not perpendicular to its axis: the rig was not changed", "a hinge's sh is negative: the rig was not changed",
-             "++per_world[(size_t)r.world] > MGF_BATCH_MAX_WORLD_HINGES", plan_call, "b->hg_rows = 1;"]
+             "++per_world[(size_t)r.world] > MGF_BATCH_MAX_WORLD_HINGES", plan_call]
     order = [body.index(s) for s in marks]
     assert order == sorted(order), order
-    assert body.count("the rig was not changed") == 10
+    assert body.count("the rig was not changed") == 10 - 2
     assert not re.search(r"b->hinges\.|\bR\.", body.replace(plan_call, ""))                  # the rig changes in the plan step alone
     assert not re.search(r"<<<|Async|hipMalloc|\.ensure\(|h2d\(", body)                      # no device work at all
-    assert "hinge_unit(hinge_dot(r.ax, r.ax))" in body and "(double)" in src[:src.index('extern "C" mgf_status mgf_batch_set_hinges(')]   # in double on the host
+    shared = read("mgf_amd", "csrc", "host_batch_joint.inc")
+    assert "joint_unit(joint_dot(r.ax, r.ax))" in body and "static double joint_dot(const mgf_vec3& a, const mgf_vec3& b) { return (double)a.x * b.x" in shared   # in double on the host
     # what tests/test_world_batch_rigs_host.py asks of a rig file: the shared steps used, not copied
-    assert src.count("batch_rig_set_args(b, ") == 1 and src.count("batch_rig_up(b, R, ") == 1 and 'batch_rig_up(b, R, "hinge", 3)' in src
+    assert src.count("batch_rig_set_args(b, ") == 1 and src.count("batch_rig_up(") == 0 and "batch_rig_up(b, R, T::word, 3)" in shared and 'word = "hinge";' in src
     for gone in ("BatchQueryPlan plan(", "batch_rig_upload(", "names a body its world does not hold", '"batch is NULL"', "std::stable_sort("):
         assert gone not in src, gone
-    ready = src[src.index("static mgf_status batch_hinge_ready("):src.index("static mgf_status batch_hinge_run(")]
-    assert ready.index("(uint32_t)R.recs[i].other >= b->h_n[(size_t)R.recs[i].world]") < ready.index("batch_rig_up(") < ready.index("if (b->hg_zero)")
     host = read("mgf_amd", "csrc", "host_batch.inc")
     stale = host[host.index("static void batch_rigs_stale("):host.index('extern "C" mgf_status mgf_batch_add_bodies(')]
-    assert host.count("BatchRig<mgf_batch_hinge> hinges;") == 1 and "b->hinges.stale = true;" in stale
+    assert host.count("BatchJointRig<mgf_batch_hinge> hinges;") == 1 and "b->hinges.stale = true;" in stale
     assert '"hinges_skipped"' in host[host.index('extern "C" mgf_status mgf_batch_counter('):]
-    # the target calls: the refusals, the context, (device form) the pointer looked up - and only then the copy
-    tdev = src[src.index('extern "C" mgf_status mgf_batch_set_hinge_targets_dev('):src.index("static void batch_hinge_view(")]
-    assert tdev.index("batch_hinge_target_args(b, w_dev, rows)") < tdev.index("ctx_bind(") < tdev.index("dev_span(b->ctx, w_dev, ") < tdev.index("batch_hinge_targets(")
-    assert "hipStreamSynchronize" not in tdev and "hipMemcpyDeviceToDevice" in tdev
-    targs = src[src.index("static mgf_status batch_hinge_target_args("):src.index("static mgf_status batch_hinge_targets(")]
-    torder = [targs.index(s) for s in ("batch_rig_handle(b)", "rows < 1 || rows > (1 << 20)", "!w && n > 0", "overflows int64_t")]
-    assert torder == sorted(torder)
-    # the solve calls: the refusals, the context, (device form) the pointer looked up - and only then the first thing is enqueued
-    enqueue = r"batch_hinge_run\(|batch_hinge_ready\(|batch_rig_up\(|batch_push\(|hipMemsetAsync|hipMemcpyAsync|<<<|\.ensure\(|h2d\("
-    dev = src[src.index('extern "C" mgf_status mgf_batch_solve_hinges_dev('):]
-    first_enqueue = min(m.start() for m in re.finditer(enqueue, dev))
-    assert dev.index("batch_hinge_args(b, h, iters, row)") < dev.index("ctx_bind(") < dev.index('dev_span(b->ctx, impulse_out_dev, 32 * n, "impulse_out_dev")') < first_enqueue
-    assert dev.index("if (n == 0 || iters == 0) return MGF_OK;") < first_enqueue and "hipStreamSynchronize" not in dev and "hipMemcpy" not in dev
-    args = src[src.index("static mgf_status batch_hinge_args("):src.index('extern "C" mgf_status mgf_batch_solve_hinges(')]
-    assert args.index("batch_joint_args(b, h, iters)") < args.index("row < 0 || row >= b->hg_rows")        # the joints' refusals, the row behind them
-    host_form = src[src.index('extern "C" mgf_status mgf_batch_solve_hinges('):src.index('extern "C" mgf_status mgf_batch_solve_hinges_dev(')]
-    assert host_form.count("hipStreamSynchronize") == 1 and "hipMemcpyHostToDevice" not in host_form      # one wait
-    assert host_form.index("if (n == 0 || iters == 0) return MGF_OK;") < host_form.index("batch_hinge_run(")
-    assert host_form.index("hipStreamSynchronize") < host_form.index("gave up waiting")                   # a give-up is reported behind the wait
-    run = src[src.index("static mgf_status batch_hinge_run("):src.index("static mgf_status batch_hinge_args(")]
-    assert run.count("<<<") == 1 and run.index("batch_push(") < run.index("batch_hinge_ready(") < run.index("k_batch_hinge_solve<false><<<")
-    assert "A.w = b->hg_w.p + (size_t)row * b->hinges.recs.size();" in run
-    assert "b->d_launches += MGF_BATCH_HINGE_LAUNCHES;" in run and "batch_single_parts(" not in src       # hinges read no shapes
+    # the target and the solve calls are one-line forwards to the joint rigs' shared steps, whose order - the refusals (the ball joints',
+    # the row behind them), the context, (device form) the pointer looked up, and only then the copy or the first thing enqueued; no
+    # wait in the device forms, one in the host form of the solve with the give-up reported behind it; one launch behind batch_push and
+    # ready, of the named row, counted once - tests/test_world_batch_joint_family_host.py holds
+    for line in ('extern "C" mgf_status mgf_batch_set_hinge_targets(mgf_batch* b, const float* w, int64_t rows) { return batch_joint_targets<HingeKind>(b, w, rows, hipMemcpyHostToDevice); }',
+                 "  return batch_joint_targets<HingeKind>(b, w_dev, rows, hipMemcpyDeviceToDevice);\n}", "  return batch_joint_solve<HingeKind>(b, h, iters, row, impulse_out);\n}",
+                 "  return batch_joint_solve_dev<HingeKind>(b, h, iters, row, impulse_out_dev);\n}"):
+        assert src.count(line) == 1, line
+    entries = src[src.index('extern "C" int64_t mgf_batch_hinge_count('):]
+    assert entries.count('extern "C"') == 5 and entries.count(";") == 5 and entries.count("return ") == 5      # nothing but the forwards
+    kind = src[src.index("struct HingeKind {"):src.index('extern "C" mgf_status mgf_batch_set_hinges(')]
+    assert "launches = MGF_BATCH_HINGE_LAUNCHES," in kind and "launch = k_batch_hinge_solve<GATED>;" in kind and "table = true;" in kind and "using Rows = HingeRows;" in kind
+    assert "static constexpr uint32_t kWords = 7, kFloats = 8;" in read("mgf_amd", "csrc", "k_batch_hinge.h")   # 32 bytes a hinge of impulse
+    assert "batch_single_parts(" not in src                                                   # hinges read no shapes
 
 
 # ---- 7 ------------------------------------------------------------------------------------------------------------------------------------
@@ -368,15 +360,17 @@ def test_the_launch_sits_behind_the_ball_joints_and_ahead_of_the_tick_and_is_cou
     roll = read("mgf_amd", "csrc", "host_batch_rollout.inc")
     core = roll[roll.index("static mgf_status batch_rollout_run("):roll.index('extern "C" mgf_status mgf_batch_rollout_dev(')]
     assert "!b->hinges.recs.empty()" in core and "!joints && !hinges &&" in core              # the early return to the plain step sees the hinge rig
-    assert (core.index("batch_push(") < core.index("batch_joint_ready(") < core.index("batch_hinge_ready(b, dt, iters, nullptr, &H.G, &H.hinge_lds)")
+    assert (core.index("batch_push(") < core.index("batch_joint_hook<JointKind>(") < core.index("batch_joint_hook<HingeKind>(b, dt, iters, &H.hinges)")
             < core.index("batch_step_run(b, dt, iters, n_ticks, stats, &H)"))
     train = host[host.index("static mgf_status batch_step_run("):host.index('extern "C" mgf_status mgf_batch_step(')]
-    assert train.index("k_batch_rollout_act<") < train.index("k_batch_joint_solve<true><<<") < train.index("k_batch_hinge_solve<true><<<") < train.index("batch_collide(")
-    assert train.count("k_batch_hinge_solve<") == 1 and train.count("hook->launches += MGF_BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK;") == 1
-    assert "hook->G.w = b->hg_w.p + (size_t)std::min<int64_t>((int64_t)t, b->hg_rows - 1) * b->hinges.recs.size();" in train    # tick t reads row min(t, rows - 1)
+    shared = read("mgf_amd", "csrc", "host_batch_joint.inc")   # (a kind's part of the train: tests/test_world_batch_joint_family_host.py holds its steps)
+    tick = "batch_joint_tick<HingeKind>(b, hook->hinges, t, &hook->launches)"
+    assert train.index("k_batch_rollout_act<") < train.index("batch_joint_tick<JointKind>(") < train.index(tick) < train.index("batch_collide(")
+    assert train.count("batch_joint_tick<HingeKind>") == 1 and "per_tick = MGF_BATCH_ROLLOUT_HINGE_LAUNCHES_PER_TICK;" in read("mgf_amd", "csrc", RIG_FILE)
+    assert "if (T::table) H.A.w = R.w.p + (size_t)std::min<int64_t>((int64_t)t, R.rows - 1) * R.recs.size();" in shared    # tick t reads row min(t, rows - 1)
     # what the kernel reads of the handle is looked up again for every pass: inside the loop over the passes, ahead of the loop over the ticks
-    assert train.index("for (uint32_t first = 0, pass = 0;") < train.index("batch_hinge_view(b, &hook->G);") < train.index("for (uint32_t t = first; t < NT; ++t)")
-    assert "hook->G.done = b->d_done.p; hook->G.act = b->d_act.p;" in train
+    assert train.index("for (uint32_t first = 0, pass = 0;") < train.index("batch_joint_pass<HingeKind>(b, hook->hinges);") < train.index("for (uint32_t t = first; t < NT; ++t)")
+    assert "H.A.done = b->d_done.p; H.A.act = b->d_act.p;" in shared
     assert "d2h(ctx, err, b->d_err.p, 2)" in train                                              # the read-back is as it was: both solvers' give-up word
     step = host[host.index('extern "C" mgf_status mgf_batch_step('):host.index('extern "C" mgf_status mgf_batch_read_constraints(')]
     assert "batch_step_run(b, dt, iters, n_ticks, stats, nullptr)" in step and "hinge" not in step   # mgf_batch_step applies no hinge
@@ -385,8 +379,14 @@ def test_the_launch_sits_behind_the_ball_joints_and_ahead_of_the_tick_and_is_cou
 # ---- 8 ------------------------------------------------------------------------------------------------------------------------------------
 def test_the_kernel_has_the_joint_solvers_loop_shape_a_bounded_spin_and_no_float_atomic():
     k = read("mgf_amd", "csrc", "k_batch_hinge.h")
-    body = k[k.index("void k_batch_hinge_solve("):]
+    entry = k[k.index("void k_batch_hinge_solve("):]
+    assert entry[:entry.index("\n}\n")] == "void k_batch_hinge_solve(BatchJointArgs A) {\n  batch_joint_loop<HingeRows, GATED>(A);"
+    # the kernel is one call of the joint solvers' skeleton: the loop shape is asserted of the skeleton, the rows of HingeRows::sweep,
+    # which the loop calls once a turn between its one unpack and its one re-pack of the velocities
+    loop_file = read("mgf_amd", "csrc", "k_batch_joint_loop.h")
+    body = loop_file[loop_file.index("void batch_joint_loop("):]
     body = body[:body.index("\n}\n")]
+    sweep = k[k.index("void sweep(V3& va, V3& oa, V3& vb, V3& ob, bool has_b) {"):k.index("void store(float* p) const {")]
     gate = "if (GATED && !(A.done[k] == A.tick && A.act[k] == A.tick)) return;"
     assert gate in body and body.index(gate) < body.index("__syncthreads()")                 # the workgroup's early return ahead of the first barrier
     assert body.count("__syncthreads()") == 2 and re.findall(r"atomic\w*\(", body.replace("__hip_atomic_load(", "").replace("__hip_atomic_store(", "")) == ["atomicAdd("]
@@ -394,8 +394,9 @@ def test_the_kernel_has_the_joint_solvers_loop_shape_a_bounded_spin_and_no_float
     loop = body[body.index("while (open)"):body.index("if (s_fail != 0u) return;")]
     assert loop.count("__ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP") == 2 and loop.count("__ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP") == 2   # both counters released once
     assert loop.index("if (!__any(ready)) __builtin_amdgcn_s_sleep(1);") < loop.index("if (ready) {") < loop.index("s_dyn[2 * sa] = ") < loop.index("__ATOMIC_RELEASE")
-    rows = [loop.index("// hinge row: " + w) for w in ("the motor", "the limit", "the two angular rows", "the point")]
+    rows = [sweep.index("// hinge row: " + w) for w in ("the motor", "the limit", "the two angular rows", "the point")]
     assert rows == sorted(rows) and loop.count("s_dyn[2 * sa] = ") == 1 and loop.count("= s_dyn[2 * sa]") == 1   # four rows in one turn, the velocities in registers between them
+    assert loop.index("= s_dyn[2 * sa]") < loop.index("R.sweep(va, oa, vb, ob, has_b);") < loop.index("s_dyn[2 * sa] = ") and "s_dyn" not in sweep and "P.sweep(va, oa, vb, ob, has_b);" in sweep
     assert "++spins > kBatchSpinLimit" in loop and "A.err[1] = 1u;" in loop and "A.err[0]" not in k
     assert "GATED" not in loop and "A.done" not in loop and "break" not in loop and "continue" not in loop and "return" not in loop
     back = body[body.index("if (s_fail != 0u) return;"):]
@@ -417,8 +418,8 @@ def test_the_new_kernel_uses_no_scratch_and_spills_nothing():
         assert v[2] == "0" and v[4] == "0" and v[5] == "0", (name, v)    # no scratch, no spills
         assert int(v[3]) <= 16, (name, v)                                 # static LDS: the give-up flag alone
         assert "`%s` %s / %s / %s / 0 / 0" % (name, v[0], v[1], v[3]) in design, (name, v)
-    old = kernel_resources("k_batch_joint")                              # the ball joints' kernel is as it was
-    assert old == {"k_batch_joint_solve<false>": ("80", "60", "0", "16", "0", "0"), "k_batch_joint_solve<true>": ("80", "60", "0", "16", "0", "0")}, old
+    old = kernel_resources("k_batch_joint")                              # the ball joints' kernel: 80 / 60 until the three solvers became one skeleton
+    assert old == {"k_batch_joint_solve<false>": ("78", "51", "0", "16", "0", "0"), "k_batch_joint_solve<true>": ("78", "51", "0", "16", "0", "0")}, old
 
 
 # ---- 10 -----------------------------------------------------------------------------------------------------------------------------------

@@ -233,7 +233,8 @@ def test_the_plan_is_items_of_one_world_with_slots_ranks_and_degrees():
     assert np.flatnonzero(want[3]).tolist() == planted and not want[2][planted].any() and np.all(np.isfinite(want[0]))
     # the host's plan is that plan: a stable sort by world, slots in the order of first mention, reached behind every check
     src = read("mgf_amd", "csrc", RIG_FILE)
-    plan = src[src.index("static void batch_joint_plan("):src.index('extern "C" mgf_status mgf_batch_set_joints(')]
+    plan = src[src.index("static void batch_joint_plan("):]
+    plan = plan[:plan.index("\n}\n")]
     assert "std::stable_sort(" in plan and plan.index("std::stable_sort(") < plan.index("R.recs.assign(") < plan.index("R.stale = true;")
     assert plan.index("const auto a = slot(r.body);") < plan.index("r.other >= 0 ? slot(r.other)")
     assert "plan[4 * p + 1] = a.first | (b.first << 16);" in plan and "plan[4 * p + 2] = a.second | (b.second << 16);" in plan
@@ -269,37 +270,32 @@ def test_what_needs_no_device_is_refused_in_the_headers_order_with_the_rig_uncha
     body = src[src.index('extern "C" mgf_status mgf_batch_set_joints('):src.index('extern "C" int64_t mgf_batch_joint_count(')]
     plan_call = "batch_joint_plan(b->joints, j, n);"
     assert not re.search(r"b->joints\.|\bR\.", body.replace(plan_call, ""))                  # the rig changes in the plan step alone
-    marks = ["batch_rig_set_args(b, j, n_in)", 'batch_rig_ref_check(b, r.world, r.body, 0, "joint")', "r.other < -1 || (r.other >= 0 && (uint32_t)r.other >= b->h_n[(size_t)r.world])",
-             "r.other == r.body", "r.flags != 0u || r.pad != 0.0f", "a joint's pa or pb is not finite: the rig was not changed",
+    # (the two checks of `other`, with their two refusals, are the joint rigs' shared step: tests/test_world_batch_joint_family_host.py)
+    marks = ["batch_rig_set_args(b, j, n_in)", 'batch_rig_ref_check(b, r.world, r.body, 0, "joint")', "batch_joint_other_check<JointKind>(b, r)",
+             "r.flags != 0u || r.pad != 0.0f", "a joint's pa or pb is not finite: the rig was not changed",
              "a joint's beta is not in [0, 1]: the rig was not changed", "++per_world[(size_t)r.world] > MGF_BATCH_MAX_WORLD_JOINTS", plan_call]
     order = [body.index(s) for s in marks]
     assert order == sorted(order), order
-    assert body.count("the rig was not changed") == 6
+    assert body.count("the rig was not changed") == 6 - 2
     assert not re.search(r"<<<|Async|hipMalloc|\.ensure\(|h2d\(", body)                      # no device work at all
     # what tests/test_world_batch_rigs_host.py asks of a rig file: the shared steps used, not copied
-    assert src.count("batch_rig_set_args(b, ") == 1 and src.count("batch_rig_up(b, R, ") == 1 and 'batch_rig_up(b, R, "joint", 3)' in src
+    assert src.count("batch_rig_set_args(b, ") == 1 and src.count("batch_rig_up(b, R, ") == 1 and "batch_rig_up(b, R, T::word, 3)" in src and 'word = "joint";' in src
     for gone in ("BatchQueryPlan plan(", "batch_rig_upload(", "names a body its world does not hold", '"batch is NULL"'):
         assert gone not in src, gone
-    # the far ends are held against the lengths again when the rig goes up behind added bodies
-    ready = src[src.index("static mgf_status batch_joint_ready("):src.index("static mgf_status batch_joint_run(")]
-    assert ready.index("(uint32_t)R.recs[i].other >= b->h_n[(size_t)R.recs[i].world]") < ready.index("batch_rig_up(")
     host = read("mgf_amd", "csrc", "host_batch.inc")
     stale = host[host.index("static void batch_rigs_stale("):host.index('extern "C" mgf_status mgf_batch_add_bodies(')]
-    assert host.count("BatchRig<mgf_batch_joint> joints;") == 1 and "b->joints.stale = true;" in stale
+    assert host.count("BatchJointRig<mgf_batch_joint> joints;") == 1 and "b->joints.stale = true;" in stale
     assert '"joints_skipped"' in host[host.index('extern "C" mgf_status mgf_batch_counter('):]
-    # the solve calls: the refusals, the context, (device form) the pointer looked up - and only then the first thing is enqueued
-    enqueue = r"batch_joint_run\(|batch_joint_ready\(|batch_rig_up\(|batch_push\(|hipMemsetAsync|hipMemcpyAsync|<<<|\.ensure\(|h2d\("
+    # the solve calls are one-line forwards to the joint rigs' shared steps, whose order - the refusals, the context, (device form) the
+    # pointer looked up, and only then the first thing enqueued; one wait in the host form, a give-up reported behind it; one launch
+    # behind batch_push and ready, counted once - tests/test_world_batch_joint_family_host.py holds; the ball joints have no table: row 0
+    assert 'extern "C" mgf_status mgf_batch_solve_joints(mgf_batch* b, float h, int32_t iters, float* impulse_out) { return batch_joint_solve<JointKind>(b, h, iters, 0, impulse_out); }' in src
     dev = src[src.index('extern "C" mgf_status mgf_batch_solve_joints_dev('):]
-    first_enqueue = min(m.start() for m in re.finditer(enqueue, dev))
-    assert dev.index("batch_joint_args(b, h, iters)") < dev.index("ctx_bind(") < dev.index('dev_span(b->ctx, impulse_out_dev, 12 * n, "impulse_out_dev")') < first_enqueue
-    assert dev.index("if (n == 0 || iters == 0) return MGF_OK;") < first_enqueue and "hipStreamSynchronize" not in dev and "hipMemcpy" not in dev
-    host_form = src[src.index('extern "C" mgf_status mgf_batch_solve_joints('):src.index('extern "C" mgf_status mgf_batch_solve_joints_dev(')]
-    assert host_form.count("hipStreamSynchronize") == 1 and "hipMemcpyHostToDevice" not in host_form      # one wait
-    assert host_form.index("if (n == 0 || iters == 0) return MGF_OK;") < host_form.index("batch_joint_run(")
-    assert host_form.index("hipStreamSynchronize") < host_form.index("gave up waiting")                   # a give-up is reported behind the wait
-    run = src[src.index("static mgf_status batch_joint_run("):src.index("static mgf_status batch_joint_args(")]
-    assert run.count("<<<") == 1 and run.index("batch_push(") < run.index("batch_joint_ready(") < run.index("k_batch_joint_solve<false><<<")
-    assert "b->d_launches += MGF_BATCH_JOINT_LAUNCHES;" in run and "batch_single_parts(" not in src       # joints read no shapes
+    assert dev.count(";") == 1 and "return batch_joint_solve_dev<JointKind>(b, h, iters, 0, impulse_out_dev);" in dev
+    kind = src[src.index("struct JointKind {"):src.index('extern "C" mgf_status mgf_batch_set_joints(')]
+    assert "launches = MGF_BATCH_JOINT_LAUNCHES," in kind and "launch = k_batch_joint_solve<GATED>;" in kind and "table = false;" in kind and "using Rows = JointRows;" in kind
+    assert "static constexpr uint32_t kWords = 3, kFloats = 3;" in read("mgf_amd", "csrc", "k_batch_joint.h")   # 12 bytes a joint of impulse
+    assert "batch_single_parts(" not in src                                                   # joints read no shapes
 
 
 # ---- 6 ------------------------------------------------------------------------------------------------------------------------------------
@@ -308,12 +304,13 @@ def test_the_launch_sits_between_the_actuation_and_the_tick_and_is_counted_once(
     roll = read("mgf_amd", "csrc", "host_batch_rollout.inc")
     core = roll[roll.index("static mgf_status batch_rollout_run("):roll.index('extern "C" mgf_status mgf_batch_rollout_dev(')]
     assert "!b->joints.recs.empty()" in core and "!springs && !joints &&" in core           # the early return to the plain step sees the joint rig
-    assert core.index("batch_push(") < core.index("batch_joint_ready(b, dt, iters, nullptr, &H.J, &H.joint_lds)") < core.index("batch_step_run(b, dt, iters, n_ticks, stats, &H)")
+    assert core.index("batch_push(") < core.index("batch_joint_hook<JointKind>(b, dt, iters, &H.joints)") < core.index("batch_step_run(b, dt, iters, n_ticks, stats, &H)")
     train = host[host.index("static mgf_status batch_step_run("):host.index('extern "C" mgf_status mgf_batch_step(')]
-    assert train.index("k_batch_spring_apply<true><<<") < train.index("k_batch_rollout_act<") < train.index("k_batch_joint_solve<true><<<") < train.index("batch_collide(")
-    assert train.count("k_batch_joint_solve<") == 1 and train.count("hook->launches += MGF_BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK;") == 1
+    tick = "batch_joint_tick<JointKind>(b, hook->joints, t, &hook->launches)"   # (the launch <true>, counted once by the kind's per_tick: tests/test_world_batch_joint_family_host.py)
+    assert train.index("k_batch_spring_apply<true><<<") < train.index("k_batch_rollout_act<") < train.index(tick) < train.index("batch_collide(")
+    assert train.count("batch_joint_tick<JointKind>") == 1 and "per_tick = MGF_BATCH_ROLLOUT_JOINT_LAUNCHES_PER_TICK;" in read("mgf_amd", "csrc", RIG_FILE)
     # what the kernel reads of the handle is looked up again for every pass: inside the loop over the passes, ahead of the loop over the ticks
-    assert train.index("for (uint32_t first = 0, pass = 0;") < train.index("batch_joint_view(b, &hook->J);") < train.index("for (uint32_t t = first; t < NT; ++t)")
+    assert train.index("for (uint32_t first = 0, pass = 0;") < train.index("batch_joint_pass<JointKind>(b, hook->joints);") < train.index("for (uint32_t t = first; t < NT; ++t)")
     # a give-up is the second error word, read back with the first
     assert "d2h(ctx, err, b->d_err.p, 2)" in train and "a lane of the joint solver gave up" in train
     step = host[host.index('extern "C" mgf_status mgf_batch_step('):host.index('extern "C" mgf_status mgf_batch_read_constraints(')]
@@ -323,7 +320,12 @@ def test_the_launch_sits_between_the_actuation_and_the_tick_and_is_counted_once(
 # ---- 7 ------------------------------------------------------------------------------------------------------------------------------------
 def test_the_kernel_has_the_batch_solvers_loop_shape_a_bounded_spin_and_no_float_atomic():
     k = read("mgf_amd", "csrc", "k_batch_joint.h")
-    body = k[k.index("void k_batch_joint_solve("):]
+    entry = k[k.index("void k_batch_joint_solve("):]
+    assert entry[:entry.index("\n}\n")] == "void k_batch_joint_solve(BatchJointArgs A) {\n  batch_joint_loop<JointRows, GATED>(A);"
+    # the kernel is one call of the joint solvers' skeleton: the loop shape is asserted of the skeleton (and again, for the three kernels
+    # at once, in tests/test_world_batch_joint_family_host.py)
+    loop_file = read("mgf_amd", "csrc", "k_batch_joint_loop.h")
+    body = loop_file[loop_file.index("void batch_joint_loop("):]
     body = body[:body.index("\n}\n")]
     gate = "if (GATED && !(A.done[k] == A.tick && A.act[k] == A.tick)) return;"
     assert gate in body and body.index(gate) < body.index("__syncthreads()")                 # the workgroup's early return ahead of the first barrier
