@@ -1870,7 +1870,7 @@ MGF_API mgf_status mgf_batch_rollout_observe_dev(mgf_batch* b, float dt, int32_t
  * tick t's sliders ONCE, and "sliders_skipped" counts as the loop's calls would.  mgf_batch_step itself stays World::step, launch for
  * launch: it applies no slider.
  * OUT OF SCOPE here: slider encoders - d, rate and side as a call and as a traced row (until then a caller forms d from
- * mgf_batch_gather_state); position (servo) motors; warm starting; sliders interleaved with hinges or with the contacts in one sweep;
+ * mgf_batch_gather_state) (since: Slider encoders, below - mgf_batch_read_sliders, mgf_batch_set_slider_trace); position (servo) motors; warm starting; sliders interleaved with hinges or with the contacts in one sweep;
  * more than MGF_BATCH_MAX_WORLD_SLIDERS sliders a world; sliders on the lone mgf_world; sliders inside mgf_batch_step. */
 #define MGF_SLIDER_LIMIT 1  /* the travel along the axis is held to [lo, hi] */
 #define MGF_SLIDER_MOTOR 2  /* the relative speed along the axis is driven to the table's target, the force capped at fmax */
@@ -1915,6 +1915,83 @@ MGF_API mgf_status mgf_batch_solve_sliders(mgf_batch* b, float h, int32_t iters,
  * Also refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls (32 bytes a
  * slider of impulse_out_dev). */
 MGF_API mgf_status mgf_batch_solve_sliders_dev(mgf_batch* b, float h, int32_t iters, int64_t row, float* impulse_out_dev);
+/* ---- slider encoders: travel, rate, limit side, off-axis gap and frame error of every slider, read from the resident state and traced per tick ----
+ * Whoever drives a lift, a gripper jaw or a telescopic leg has to feel it: the travel d and its rate are the first two numbers a
+ * controller reads of a prismatic joint, a planner's cost wants them - and the force the motor spent - at every tick of the horizon, and
+ * whoever tunes beta and iters wants to know how far the far anchor leaves the axis and the two frames part under load.  A READING is
+ * eight floats, 32 bytes,
+ *   (d, rate, side, off1, off2, e.x, e.y, e.z)
+ * formed from the state AS IT STANDS by the SETUP lines of the slider section above, verbatim, with the same helpers (rotate, cross,
+ * dot); every line below is a separate rounded f32 operation, no fused multiply-add:
+ *   ra, rb, Pa, Pb, C, A, T1, T2, B, U1: SETUP's lines (other == -1: B = bx, U1 = ub, Pb = pb, rb = 0, v_b = 0, omega_b = 0)
+ *   U2 = cross(B, U1)
+ *   ca = ra + C
+ *   sA = cross(ca, A)
+ *   sB = cross(rb, A)
+ *   d = dot(C, A)                              the travel along the axis
+ *   rate = (dot(v_b - v_a, A) + dot(omega_b, sB)) - dot(omega_a, sA)
+ *                                              - rate(A, sA, sB) of the slider section: what the motor and axis rows of the NEXT solve see
+ *   LOCK: side = 2.0f;  LIMIT and d < lo: side = -1.0f;  LIMIT and d > hi: side = +1.0f;  otherwise side = 0.0f
+ *                                              - SETUP's flag rule: whether the NEXT solve's axis row would be on, and on which side
+ *   off1 = dot(C, T1)
+ *   off2 = dot(C, T2)                          the far anchor's distance from the axis: g1, g2 without the factor s
+ *   e = ((cross(A, B) + cross(T1, U1)) + cross(T2, U2)) * 0.5      the frames' error: gw without the factor s
+ * There is no division, no h and no beta: no slider is skipped and there is no counter.  Non-finite state gives non-finite words.  A
+ * reading reads no shapes - a batch with bodies of several components is answered - and writes nothing but its output: the state is
+ * untouched to the bit.
+ * ONE CALL, mgf_batch_read_sliders(b, out), is MGF_BATCH_SLIDER_READ_LAUNCHES = 1 launch, counted in "drive_launches" as the solve's is:
+ * a lane per slider by the caller's index over all worlds.  What set_many, mgf_batch_add_bodies or mgf_batch_set_sliders left on the
+ * host goes up first, by the path the solve uses.
+ * THE READINGS TABLE is the hinge encoders', kept apart from theirs: mgf_batch_set_slider_trace(b, rows, format) makes the handle
+ * allocate and zero R[rows][mgf_batch_slider_count] entries in device memory; rows == 0 frees it and turns the trace off, which is the
+ * default, and mgf_batch_set_sliders sets it back to 0 rows as it resets the target table.  An entry is
+ *   MGF_SLIDER_TRACE_READING  32 bytes: the reading;
+ *   MGF_SLIDER_TRACE_FULL     64 bytes: the reading, then the eight floats (p1, p2, al, am, aw.x, aw.y, aw.z, 0) of tick t's slider
+ *                             solve - am / dt is the force the motor applied in tick t, al / dt the limit's or the lock's.
+ * IN A ROLLOUT.  With a slider rig that is not empty and rows > 0, mgf_batch_rollout and its _dev, _touches, _touches_dev, _observe and
+ * _observe_dev forms - no new entry point, no changed signature - are the defining loop of the slider section with one more line at the
+ * end of tick t < rows:
+ *   ... | mgf_batch_step(dt, iters, 1) | mgf_batch_gather_state_dev(row t) | [traces] | [mgf_batch_read_hinges_dev(b, row t)] | mgf_batch_read_sliders_dev(b, row t)
+ * and every row is bit for bit what that loop gives; for FULL the impulse words are those of tick t's
+ * mgf_batch_solve_sliders_dev(..., impulse_out) in that loop, and zeros with iters == 0, where no solve is enqueued.  Ticks t >= rows
+ * write nothing and launch nothing - there is NO clamp: an output is never overwritten silently - and rows the call does not reach stay
+ * as they were.  The trace adds MGF_BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK = 1 launch to a tick that has a row, behind the hinge
+ * trace's, counted in "rollout_launches"; with rows == 0 or an empty rig every rollout is launch for launch what it was.  A world
+ * whose tick is undone and run again gets its row t in the pass in which it completes t, with the impulses of the pass that solved t.
+ * mgf_batch_step traces nothing.
+ * OUT OF SCOPE here: position (servo) motors; readings for ball joints; readings inside mgf_rollout_traces; a clamp or ring-buffer
+ * mode of the table; the lone mgf_world; hipGraph capture. */
+#define MGF_BATCH_SLIDER_READ_LAUNCHES 1  /* what one read call adds to "drive_launches" */
+#define MGF_BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK 1  /* what the sliders' readings table adds to a rollout's tick t < rows */
+#define MGF_SLIDER_TRACE_READING 0  /* an entry of the table is the 32-byte reading */
+#define MGF_SLIDER_TRACE_FULL 1     /* 64 bytes: the reading and the eight impulse words of the tick's slider solve */
+typedef struct mgf_slider_reading {
+  float d;         /* dot(C, A): the travel along the axis */
+  float rate;      /* the rate of d as the next solve's motor and axis rows see it */
+  float side;      /* 2: LOCK; -1 or +1: LIMIT is set and d is below lo or above hi - the next solve's axis row is on; 0: it is off */
+  float off1, off2;  /* dot(C, T1), dot(C, T2): the far anchor's distance from the axis */
+  mgf_vec3 e;      /* the frames' error, half the sum of the three cross products of the frames' vectors */
+} mgf_slider_reading;  /* 32 bytes: two 16-byte words */
+/* The readings of every slider into out[0 .. mgf_batch_slider_count) (host memory): one download, one host wait.  Refused with
+ * MGF_ERR_INVALID, nothing enqueued, in this order: a NULL batch; a NULL out with a rig that is not empty.  An empty rig: MGF_OK,
+ * nothing enqueued. */
+MGF_API mgf_status mgf_batch_read_sliders(mgf_batch* b, mgf_slider_reading* out);
+/* The same with out in device memory (the device-pointer calls, above): enqueued on the context's stream and NOT waited for.  Also
+ * refused with MGF_ERR_INVALID, nothing enqueued: a pointer that fails the look-up of the device-pointer calls (32 bytes a slider of
+ * out_dev), or that is not aligned to 16 bytes - the readings are stored as 16-byte words. */
+MGF_API mgf_status mgf_batch_read_sliders_dev(mgf_batch* b, mgf_slider_reading* out_dev);
+/* The readings table made rows x mgf_batch_slider_count entries of zeros in `format`; rows == 0: freed, no trace.  Refused with
+ * MGF_ERR_INVALID, the table as it was, in this order: a NULL batch; rows < 0 or rows > 2^20; a format that is neither
+ * MGF_SLIDER_TRACE_READING nor MGF_SLIDER_TRACE_FULL; a byte count that overflows.  With an empty rig rows and format are all that is kept. */
+MGF_API mgf_status mgf_batch_set_slider_trace(mgf_batch* b, int64_t rows, int32_t format);
+MGF_API int64_t    mgf_batch_slider_trace_rows(const mgf_batch* b);         /* -1 for NULL */
+/* Rows [row0, row0 + n_rows) of the table into out (host memory, n_rows x mgf_batch_slider_count entries of 32 or 64 bytes): one
+ * download, waited for.  Refused with MGF_ERR_INVALID, in this order: a NULL batch; row0 < 0; n_rows < 0; row0 + n_rows beyond the
+ * table's rows; a NULL out with bytes to copy. */
+MGF_API mgf_status mgf_batch_get_slider_trace(mgf_batch* b, void* out, int64_t row0, int64_t n_rows);
+/* The same as a device-to-device copy, enqueued on the context's stream and NOT waited for.  Also refused, nothing enqueued: a pointer
+ * that fails the look-up of the device-pointer calls. */
+MGF_API mgf_status mgf_batch_get_slider_trace_dev(mgf_batch* b, void* out_dev, int64_t row0, int64_t n_rows);
 /* name in {"launches_per_tick" (kernel launches one tick of the whole batch costs: 6, with or without obstacles; it does not grow with n_worlds), "capacity_retries",
  * "query_launches" (kernel launches of the last query call: it depends on neither n_worlds nor n), "query_run_ns" (HIP-event time of
  * the last query call's kernels, as mgf_world_counter's), "drive_launches" (kernel launches of the last mgf_batch_get_many / _set_many /

@@ -21,5 +21,7 @@ from ._capi import (MgfError, Context, Mesh, Bvh, World, WorldBatch, BATCH_MAX_B
                     BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK, hinge_angles,
                     BatchSlider, SLIDER_DTYPE, SLIDER_LIMIT, SLIDER_MOTOR, SLIDER_LOCK, BATCH_SLIDER_LAUNCHES, BATCH_ROLLOUT_SLIDER_LAUNCHES_PER_TICK,
                     BATCH_MAX_WORLD_SLIDERS, slider_frames,
+                    SLIDER_READING_DTYPE, SLIDER_TRACE_FULL_DTYPE, SLIDER_TRACE_READING, SLIDER_TRACE_FULL, BATCH_SLIDER_READ_LAUNCHES,
+                    BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK,
                     TOUCH_SHORT_DTYPE, ROLLOUT_TOUCH_FULL, ROLLOUT_TOUCH_SHORT, BATCH_ROLLOUT_TOUCH_LAUNCHES_PER_TICK,
                     ROLLOUT_TRACES, ROLLOUT_SENSOR_HIT, ROLLOUT_SENSOR_DEPTH, BATCH_ROLLOUT_SENSOR_LAUNCHES_PER_TICK)

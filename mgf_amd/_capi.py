@@ -255,6 +255,17 @@ assert HINGE_READING_DTYPE.itemsize == 32 and HINGE_TRACE_FULL_DTYPE.itemsize ==
 HINGE_TRACE_READING, HINGE_TRACE_FULL = 0, 1  # MGF_HINGE_TRACE_READING, _FULL
 BATCH_HINGE_READ_LAUNCHES = 1  # MGF_BATCH_HINGE_READ_LAUNCHES
 BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK = 1  # MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK
+# mgf_slider_reading: a slider's encoder - its travel along the axis, its rate as the next solve's axis rows see it, the side of its
+# limit (+1, -1; 2: locked; 0: off), the far anchor's distance from the axis along the two references and the frames' error;
+# SLIDER_TRACE_FULL_DTYPE: an entry of the readings table in the full format - the reading and the eight impulse words of the tick's
+# slider solve (am / dt: the motor's force)
+SLIDER_READING_DTYPE = np.dtype([("d", "<f4"), ("rate", "<f4"), ("side", "<f4"), ("off", "<f4", 2), ("e", "<f4", 3)])
+SLIDER_TRACE_FULL_DTYPE = np.dtype([("d", "<f4"), ("rate", "<f4"), ("side", "<f4"), ("off", "<f4", 2), ("e", "<f4", 3),
+                                    ("p1", "<f4"), ("p2", "<f4"), ("al", "<f4"), ("am", "<f4"), ("aw", "<f4", 3), ("pad", "<f4")])
+assert SLIDER_READING_DTYPE.itemsize == 32 and SLIDER_TRACE_FULL_DTYPE.itemsize == 64
+SLIDER_TRACE_READING, SLIDER_TRACE_FULL = 0, 1  # MGF_SLIDER_TRACE_READING, _FULL
+BATCH_SLIDER_READ_LAUNCHES = 1  # MGF_BATCH_SLIDER_READ_LAUNCHES
+BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK = 1  # MGF_BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK
 # mgf_touch_short: an entry of a rollout's touch rows in the short format - four words of mgf_touch_report
 TOUCH_SHORT_DTYPE = np.dtype([("n_contacts", "<i4"), ("partner", "<i4"), ("normal_impulse", "<f4"), ("strongest_impulse", "<f4")])
 assert TOUCH_SHORT_DTYPE.itemsize == 16
@@ -325,6 +336,8 @@ SYMBOLS = [
     "mgf_batch_solve_hinges", "mgf_batch_solve_hinges_dev",
     "mgf_batch_read_hinges", "mgf_batch_read_hinges_dev", "mgf_batch_set_hinge_trace", "mgf_batch_hinge_trace_rows",
     "mgf_batch_get_hinge_trace", "mgf_batch_get_hinge_trace_dev",
+    "mgf_batch_read_sliders", "mgf_batch_read_sliders_dev", "mgf_batch_set_slider_trace", "mgf_batch_slider_trace_rows",
+    "mgf_batch_get_slider_trace", "mgf_batch_get_slider_trace_dev",
     "mgf_batch_set_sliders", "mgf_batch_slider_count", "mgf_batch_set_slider_targets", "mgf_batch_set_slider_targets_dev",
     "mgf_batch_solve_sliders", "mgf_batch_solve_sliders_dev",
 ]
@@ -547,6 +560,12 @@ def load_library():
         "mgf_batch_hinge_trace_rows": (i64, [vp]),
         "mgf_batch_get_hinge_trace": (i32, [vp, vp, i64, i64]),
         "mgf_batch_get_hinge_trace_dev": (i32, [vp, vp, i64, i64]),
+        "mgf_batch_read_sliders": (i32, [vp, vp]),
+        "mgf_batch_read_sliders_dev": (i32, [vp, vp]),
+        "mgf_batch_set_slider_trace": (i32, [vp, i64, i32]),
+        "mgf_batch_slider_trace_rows": (i64, [vp]),
+        "mgf_batch_get_slider_trace": (i32, [vp, vp, i64, i64]),
+        "mgf_batch_get_slider_trace_dev": (i32, [vp, vp, i64, i64]),
         "mgf_batch_set_sliders": (i32, [vp, vp, i64]),
         "mgf_batch_slider_count": (i64, [vp]),
         "mgf_batch_set_slider_targets": (i32, [vp, vp, i64]),
@@ -2733,6 +2752,56 @@ class WorldBatch:
         float32 [n, 8], n = slider_count(), or None."""
         n = max(self.slider_count(), 0)
         _check(load_library().mgf_batch_solve_sliders_dev(self._h, float(h), int(iters), int(row), _dev_arg(impulses_dev, "float32", 8, n, "impulses_dev")))
+
+    # ---- slider encoders: travel, rate, limit side, off-axis gap and frame error of every slider; a readings table every rollout fills -------
+    def read_sliders(self):
+        """the reading of every slider from the state as it stands (mgf_batch_read_sliders): a SLIDER_READING_DTYPE array
+        [slider_count()] in the rig's order - d (the travel along the axis), rate (as the next solve's motor and axis rows see it), side
+        (+1 / -1: the next solve's limit row is on, above hi / below lo; 2: locked; 0: off), off (the far anchor's distance from the
+        axis along the two references) and e (the frames' error).  One launch, one download; the state is not touched."""
+        out = np.zeros(max(self.slider_count(), 0), SLIDER_READING_DTYPE)
+        _check(load_library().mgf_batch_read_sliders(self._h, out.ctypes.data if len(out) else None))
+        return out
+
+    def read_sliders_dev(self, out_dev):
+        """read_sliders enqueued on the context's stream and not waited for (mgf_batch_read_sliders_dev).  out_dev: CUDA float32
+        [slider_count(), 8], or an integer address aligned to 16 bytes."""
+        n = max(self.slider_count(), 0)
+        _check(load_library().mgf_batch_read_sliders_dev(self._h, _dev_arg(out_dev, "float32", 8, n, "out_dev")))
+
+    def set_slider_trace(self, rows, full=False):
+        """the sliders' readings table made `rows` rows of slider_count() entries of zeros (mgf_batch_set_slider_trace): tick t < rows of
+        every rollout form writes row t behind the tick, later ticks write nothing.  full=True: an entry also carries the eight impulse
+        words of the tick's slider solve (SLIDER_TRACE_FULL_DTYPE; am / dt is the motor's force).  rows = 0 frees the table: no trace,
+        which is the default and what set_sliders leaves."""
+        _check(load_library().mgf_batch_set_slider_trace(self._h, int(rows), SLIDER_TRACE_FULL if full else SLIDER_TRACE_READING))
+        self._slider_trace_full = bool(full)
+
+    def slider_trace_rows(self):
+        return load_library().mgf_batch_slider_trace_rows(self._h)
+
+    def _slider_trace_span(self, row0, rows):
+        total = max(self.slider_trace_rows(), 0)
+        rows = total - int(row0) if rows is None else int(rows)
+        if row0 < 0 or rows < 0 or row0 + rows > total:
+            raise ValueError(f"rows [{row0}, {row0 + rows}) are not rows of a table of {total}")
+        return int(row0), rows
+
+    def slider_trace(self, row0=0, rows=None):
+        """rows [row0, row0 + rows) of the sliders' readings table (mgf_batch_get_slider_trace; rows=None: to the table's end): an array
+        [rows, slider_count()] of SLIDER_READING_DTYPE, or of SLIDER_TRACE_FULL_DTYPE where the table was set with full=True.  One
+        download, waited for."""
+        row0, rows = self._slider_trace_span(row0, rows)
+        out = np.zeros((rows, max(self.slider_count(), 0)), SLIDER_TRACE_FULL_DTYPE if getattr(self, "_slider_trace_full", False) else SLIDER_READING_DTYPE)
+        _check(load_library().mgf_batch_get_slider_trace(self._h, out.ctypes.data if out.size else None, row0, rows))
+        return out
+
+    def slider_trace_dev(self, out_dev, row0=0, rows=None):
+        """slider_trace as a device-to-device copy, enqueued on the context's stream and not waited for (mgf_batch_get_slider_trace_dev).
+        out_dev: CUDA float32 [rows * slider_count(), 8] - 16 with full=True - or an integer address."""
+        row0, rows = self._slider_trace_span(row0, rows)
+        cols = 16 if getattr(self, "_slider_trace_full", False) else 8
+        _check(load_library().mgf_batch_get_slider_trace_dev(self._h, _dev_arg(out_dev, "float32", cols, rows * max(self.slider_count(), 0), "out_dev"), row0, rows))
 
     def counter(self, name):
         v = C.c_int64()

@@ -134,6 +134,10 @@ struct mgf_batch {
   int64_t ht_rows = 0;                  // ... its rows; 0: no trace (host_batch_hinge_read.inc)
   int32_t ht_format = 0;                // ... and MGF_HINGE_TRACE_READING / _FULL
   DBuf<float4> ht_out;                  // what the host-memory read of the hinges downloads: two words a hinge
+  DBuf<float4> st_tab;                  // the sliders' readings table, st_rows rows of an entry a slider: two words, four with the impulses (mgf_batch_set_slider_trace)
+  int64_t st_rows = 0;                  // ... its rows; 0: no trace (host_batch_slider_read.inc)
+  int32_t st_format = 0;                // ... and MGF_SLIDER_TRACE_READING / _FULL
+  DBuf<float4> st_out;                  // what the host-memory read of the sliders downloads: two words a slider
   // the rollouts (host_batch_rollout.inc)
   DBuf<uint32_t> d_act;                 // per world, beside d_done: ticks of the call whose actuation the world has behind it (k_batch_rollout.h)
   int64_t r_launches = 0;               // launches of the last rollout call beyond its ticks' own (counter "rollout_launches")
@@ -914,6 +918,8 @@ struct BatchRolloutHook {
   int32_t scan = -1;     // MGF_ROLLOUT_SENSOR_HIT / _DEPTH: k_batch_scan_rays and k_batch_scan_rows behind every tick's touch trace; -1: no sensor trace
   BatchHingeReadArgs E;  // the hinge trace's launch (k_batch_hinge_read.h): n; the train fills the rest in, the handle's view per PASS, the table's row per TICK
   int32_t hinge_read = -1;  // kHingeReadReading / _Full / _FullZero: k_batch_read_hinges behind every tick t < the table's rows; -1: no hinge trace
+  BatchSliderReadArgs L;  // the slider trace's launch (k_batch_slider_read.h): n; the train fills the rest in, the handle's view per PASS, the table's row per TICK
+  int32_t slider_read = -1;  // kSliderReadReading / _Full / _FullZero: k_batch_read_sliders behind every tick t < the table's rows; -1: no slider trace
   int64_t launches = 0;  // what the hook added to the train's launches
 };
 // (host_batch_joint.inc, _hinge.inc, _slider.inc, behind this file) the kinds of joints, and a kind's part of the train: per pass what its kernel reads of the handle, per tick its launch
@@ -925,6 +931,7 @@ static void batch_joint_pass(const mgf_batch* b, BatchJointHook& H);
 template <class T>
 static mgf_status batch_joint_tick(mgf_batch* b, BatchJointHook& H, uint32_t t, int64_t* launches);
 static void batch_hinge_read_view(const mgf_batch* b, BatchHingeReadArgs* A);  // (host_batch_hinge_read.inc, behind this file) what the hinge trace's kernel reads of the handle
+static void batch_slider_read_view(const mgf_batch* b, BatchSliderReadArgs* A);  // (host_batch_slider_read.inc, behind this file) what the slider trace's kernel reads of the handle
 static uint32_t batch_touch_tile(const mgf_batch* b);  // (host_batch_touch.inc, behind this file) the words of dynamic LDS the contact sensors' fold stages
 // (host_batch_query.inc, behind this file) the dynamic LDS of a ray cast with a workgroup per work item; what a cast reads of the handle; has it obstacles to meet
 static uint32_t batch_ray_lds(const mgf_batch* b);
@@ -935,7 +942,8 @@ static bool batch_has_obstacles(const mgf_batch* b, int32_t kinds_mask);
 // host wait per pass - and with a hook a rollout's two launches a tick among them, the springs' two where that rig is not empty and the
 // touch trace's one and the sensor trace's two where they are asked for, and the joints' one where that rig is not empty, and the
 // hinges' one where theirs is not, and the hinge trace's one behind every tick that has a row in the readings table, and the sliders'
-// one behind the hinges' where that rig is not empty.
+// one behind the hinges' where that rig is not empty, and the slider trace's one behind the hinge trace's for every tick that has a row in
+// the sliders' readings table.
 // hook == nullptr: mgf_batch_step, launch for launch.
 static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t n_ticks, mgf_step_stats* stats, BatchRolloutHook* hook) {
   MGF_TRY(batch_push(b));
@@ -988,6 +996,10 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
     if (hook && hook->hinge_read >= 0) {  // (the same rule for the hinge trace: the rig, the impulse buffer and the TABLE are looked up again for every pass)
       batch_hinge_read_view(b, &hook->E);
       hook->E.done = b->d_done.p; hook->E.act = b->d_act.p;
+    }
+    if (hook && hook->slider_read >= 0) {  // (and for the slider trace: the rig, the impulse buffer and the TABLE are looked up again for every pass)
+      batch_slider_read_view(b, &hook->L);
+      hook->L.done = b->d_done.p; hook->L.act = b->d_act.p;
     }
     if (hook && hook->touch >= 0) {  // (batch_allot moves the lists between passes: the view is rebuilt with BatchArgs, never kept from an earlier pass)
       BatchRig<mgf_batch_touch>& R = b->touches;
@@ -1077,6 +1089,17 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
         else k_batch_read_hinges<true, kHingeReadReading><<<blocks, kBatchBlock, 0, s>>>(E);
         LAUNCH_CHECK();
         hook->launches += MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK;
+      }
+      if (hook && hook->slider_read >= 0 && (int64_t)t < b->st_rows) {  // (behind the record: act[k] is final; row t, and no launch for a tick the table has no row for)
+        BatchSliderReadArgs& L = hook->L;
+        const unsigned blocks = (L.n + kBatchBlock - 1) / kBatchBlock;
+        L.tick = t;
+        L.out = b->st_tab.p + (size_t)t * L.n * (hook->slider_read == kSliderReadReading ? 2u : 4u);
+        if (hook->slider_read == kSliderReadFull) k_batch_read_sliders<true, kSliderReadFull><<<blocks, kBatchBlock, 0, s>>>(L);
+        else if (hook->slider_read == kSliderReadFullZero) k_batch_read_sliders<true, kSliderReadFullZero><<<blocks, kBatchBlock, 0, s>>>(L);
+        else k_batch_read_sliders<true, kSliderReadReading><<<blocks, kBatchBlock, 0, s>>>(L);
+        LAUNCH_CHECK();
+        hook->launches += MGF_BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK;
       }
     }
     MGF_TRY(d2h(ctx, done.data(), b->d_done.p, K));

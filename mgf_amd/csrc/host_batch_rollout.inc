@@ -13,6 +13,8 @@
 // Where the slider rig is not empty its one launch (k_batch_slider.h, MGF_BATCH_ROLLOUT_SLIDER_LAUNCHES_PER_TICK) goes behind the hinges'.
 // Where the hinge rig is not empty and the readings table has rows (mgf_batch_set_hinge_trace), the hinge trace's one launch
 // (k_batch_hinge_read.h, MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK) goes behind the record of every tick t < rows.
+// Where the slider rig is not empty and its readings table has rows (mgf_batch_set_slider_trace), the slider trace's one launch
+// (k_batch_slider_read.h, MGF_BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK) goes behind the hinge trace's of every tick t < rows.
 // The rig is the actuators' (BatchRig::items: no plan and no upload format of its own), the trace rows are k_batch_dev_gather's.
 // "drive_launches" is not touched.
 // The order of both calls: the refusals that need no handle, the handle's own, (device form) EVERY device pointer looked up for its
@@ -25,6 +27,8 @@ template <class T>
 static mgf_status batch_joint_hook(mgf_batch* b, float h, int32_t iters, BatchJointHook* H);
 // (host_batch_hinge_read.inc, behind this file) the hinge trace's arguments for the train: the rig up, the impulse buffer there
 static mgf_status batch_hinge_read_ready(mgf_batch* b, BatchHingeReadArgs* A);
+// (host_batch_slider_read.inc, behind this file) the slider trace's arguments for the train: the rig up, the impulse buffer there
+static mgf_status batch_slider_read_ready(mgf_batch* b, BatchSliderReadArgs* A);
 
 struct RolloutBytes { size_t u, body, out[4], touch, sensor; };  // what the call touches of u, body, x, q, v, omega, touch, sensor
 // the touch trace of mgf_batch_rollout_touches / _touches_dev (host_batch_trace.inc): rows of n reports, device memory when it reaches the core.
@@ -136,6 +140,10 @@ static mgf_status batch_rollout_run(mgf_batch* b, float dt, int32_t iters, int64
   if (hinges && b->ht_rows > 0) {  // (the readings table has rows: k_batch_read_hinges behind every tick t < rows; with iters == 0 no solve wrote an impulse)
     MGF_TRY(batch_hinge_read_ready(b, &H.E));
     H.hinge_read = b->ht_format == MGF_HINGE_TRACE_FULL ? (iters > 0 ? kHingeReadFull : kHingeReadFullZero) : kHingeReadReading;
+  }
+  if (sliders && b->st_rows > 0) {  // (the sliders' readings table has rows: k_batch_read_sliders behind every tick t < rows; with iters == 0 no solve wrote an impulse)
+    MGF_TRY(batch_slider_read_ready(b, &H.L));
+    H.slider_read = b->st_format == MGF_SLIDER_TRACE_FULL ? (iters > 0 ? kSliderReadFull : kSliderReadFullZero) : kSliderReadReading;
   }
   if (touches) {  // (the sensors' rig up ahead of the train; the lists' view is the train's to fill, pass by pass)
     MGF_TRY(batch_rig_up(b, b->touches, "contact sensor", 3));

@@ -50,6 +50,7 @@ extern "C" mgf_status mgf_batch_set_sliders(mgf_batch* b, const mgf_batch_slider
       return fail(MGF_ERR_INVALID, "a world holds at most MGF_BATCH_MAX_WORLD_SLIDERS (256) sliders: the rig was not changed");
   }
   batch_joint_plan(b->sliders, j, n);
+  b->st_rows = 0;  // (the readings table is rows of the OLD rig's sliders: the trace is off until mgf_batch_set_slider_trace names it again)
   return MGF_OK;
 }
 

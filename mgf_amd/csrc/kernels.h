@@ -204,6 +204,12 @@
 //                      together, two linear rows that hold the anchor on the axis - solved in one turn of the lane with both
 //                      bodies' velocities in registers; the same plan, slots, dataflow, bounded spin and gate; the motors' targets
 //                      from a row of the handle's table
+//   k_batch_read_sliders<GATED, FORMAT> (k_batch_slider_read.h; the frame lines in k_batch_hinge_frame.h)
+//                      slider encoders (mgf_batch_read_sliders / _read_sliders_dev, and behind the record of every tick of a rollout that
+//                      has a row in the readings table - mgf_batch_set_slider_trace): a lane per slider by the caller's index forms the
+//                      slider's SETUP frames from the state as it stands and writes (d, rate, side, off1, off2, e) - 32 bytes, or 64
+//                      with the eight impulse words of the tick's solve behind them - with float4 stores; k_batch_read_hinges' shape
+//                      and gate, the lane's own, ahead of every load of state
 //   k_batch_trace_touch<FORMAT> (k_batch_trace.h)
 //                      the touch trace of a rollout (mgf_batch_rollout_touches / _touches_dev): k_batch_touch's fold of every world's
 //                      list behind tick t into row t of the reports, one launch a tick behind k_batch_rollout_record; the train's gate
@@ -258,6 +264,7 @@
 #include "k_batch_hinge.h"  // hinge joints between bodies: the joints' launch with motor, limit, angular and point rows (k_batch_hinge_solve)
 #include "k_batch_hinge_read.h"  // hinge encoders: angle, rate, limit side, gap and tilt from the resident state, a lane per hinge (k_batch_read_hinges)
 #include "k_batch_slider.h"  // slider joints between bodies: the hinges' launch with motor, axis, angular and off-axis rows (k_batch_slider_solve)
+#include "k_batch_slider_read.h"  // slider encoders: travel, rate, limit side, off-axis gap and frame error from the resident state, a lane per slider (k_batch_read_sliders)
 #include "k_batch_part_query.h"  // rays, sweeps and box queries that see the parts of bodies of several components (k_batch_pq_*)
 #include "k_batch_trace.h"  // the touch trace of a rollout: the contact sensors' reports behind every tick (k_batch_trace_touch)
 #include "k_batch_scan.h"  // the sensor trace of a rollout: the ray sensors' answers behind every tick (k_batch_scan_rays, _rows)
