@@ -266,6 +266,9 @@ assert SLIDER_READING_DTYPE.itemsize == 32 and SLIDER_TRACE_FULL_DTYPE.itemsize 
 SLIDER_TRACE_READING, SLIDER_TRACE_FULL = 0, 1  # MGF_SLIDER_TRACE_READING, _FULL
 BATCH_SLIDER_READ_LAUNCHES = 1  # MGF_BATCH_SLIDER_READ_LAUNCHES
 BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK = 1  # MGF_BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK
+# what WorldBatch's encoder helpers take of a kind: its word in the methods and the symbols, the reading's and the full entry's dtype, the two formats
+_HINGE_ENC = ("hinge", HINGE_READING_DTYPE, HINGE_TRACE_FULL_DTYPE, HINGE_TRACE_READING, HINGE_TRACE_FULL)
+_SLIDER_ENC = ("slider", SLIDER_READING_DTYPE, SLIDER_TRACE_FULL_DTYPE, SLIDER_TRACE_READING, SLIDER_TRACE_FULL)
 # mgf_touch_short: an entry of a rollout's touch rows in the short format - four words of mgf_touch_report
 TOUCH_SHORT_DTYPE = np.dtype([("n_contacts", "<i4"), ("partner", "<i4"), ("normal_impulse", "<f4"), ("strongest_impulse", "<f4")])
 assert TOUCH_SHORT_DTYPE.itemsize == 16
@@ -2642,55 +2645,67 @@ class WorldBatch:
         n = max(self.hinge_count(), 0)
         _check(load_library().mgf_batch_solve_hinges_dev(self._h, float(h), int(iters), int(row), _dev_arg(impulses_dev, "float32", 8, n, "impulses_dev")))
 
+    # ---- the encoders of the hinges and the sliders, each call written once over a kind, _HINGE_ENC or _SLIDER_ENC; dev: the device form ------
+    def _enc_call(self, kind, name, *args):
+        _check(getattr(load_library(), "mgf_batch_" + name.format(kind[0]))(self._h, *args))
+
+    def _enc_read(self, kind, out_dev=None, dev=False):
+        n = max(getattr(self, kind[0] + "_count")(), 0)
+        if dev:
+            return self._enc_call(kind, "read_{}s_dev", _dev_arg(out_dev, "float32", 8, n, "out_dev"))
+        out = np.zeros(n, kind[1])
+        self._enc_call(kind, "read_{}s", out.ctypes.data if len(out) else None)
+        return out
+
+    def _enc_set_trace(self, kind, rows, full):
+        self._enc_call(kind, "set_{}_trace", int(rows), kind[4] if full else kind[3])
+        setattr(self, "_%s_trace_full" % kind[0], bool(full))
+
+    def _enc_trace(self, kind, row0, rows, out_dev=None, dev=False):
+        total = max(getattr(self, kind[0] + "_trace_rows")(), 0)
+        rows = total - int(row0) if rows is None else int(rows)
+        if row0 < 0 or rows < 0 or row0 + rows > total:
+            raise ValueError(f"rows [{row0}, {row0 + rows}) are not rows of a table of {total}")
+        n, full = max(getattr(self, kind[0] + "_count")(), 0), getattr(self, "_%s_trace_full" % kind[0], False)
+        if dev:
+            return self._enc_call(kind, "get_{}_trace_dev", _dev_arg(out_dev, "float32", 16 if full else 8, rows * n, "out_dev"), int(row0), rows)
+        out = np.zeros((rows, n), kind[2] if full else kind[1])
+        self._enc_call(kind, "get_{}_trace", out.ctypes.data if out.size else None, int(row0), rows)
+        return out
+
     # ---- hinge encoders: angle, rate, limit side, gap and tilt of every hinge; a readings table every rollout fills, a row a tick ------------
     def read_hinges(self):
         """the reading of every hinge from the state as it stands (mgf_batch_read_hinges): a HINGE_READING_DTYPE array [hinge_count()]
         in the rig's order - c, sn (the angle is arctan2(sn, c): hinge_angles), rate, side (+1 / -1: the next solve's limit row is on,
         past hi / lo; 0: off), gap (the anchors' gap in the world) and tilt2 (the squared sine of the angle between the axes).  One
         launch, one download; the state is not touched."""
-        out = np.zeros(max(self.hinge_count(), 0), HINGE_READING_DTYPE)
-        _check(load_library().mgf_batch_read_hinges(self._h, out.ctypes.data if len(out) else None))
-        return out
+        return self._enc_read(_HINGE_ENC)
 
     def read_hinges_dev(self, out_dev):
         """read_hinges enqueued on the context's stream and not waited for (mgf_batch_read_hinges_dev).  out_dev: CUDA float32
         [hinge_count(), 8], or an integer address aligned to 16 bytes."""
-        n = max(self.hinge_count(), 0)
-        _check(load_library().mgf_batch_read_hinges_dev(self._h, _dev_arg(out_dev, "float32", 8, n, "out_dev")))
+        self._enc_read(_HINGE_ENC, out_dev, dev=True)
 
     def set_hinge_trace(self, rows, full=False):
         """the readings table made `rows` rows of hinge_count() entries of zeros (mgf_batch_set_hinge_trace): tick t < rows of every
         rollout form writes row t behind the tick, later ticks write nothing.  full=True: an entry also carries the eight impulse words
         of the tick's hinge solve (HINGE_TRACE_FULL_DTYPE; am / dt is the motor's torque).  rows = 0 frees the table: no trace, which
         is the default and what set_hinges leaves."""
-        _check(load_library().mgf_batch_set_hinge_trace(self._h, int(rows), HINGE_TRACE_FULL if full else HINGE_TRACE_READING))
-        self._hinge_trace_full = bool(full)
+        self._enc_set_trace(_HINGE_ENC, rows, full)
 
     def hinge_trace_rows(self):
         return load_library().mgf_batch_hinge_trace_rows(self._h)
-
-    def _hinge_trace_span(self, row0, rows):
-        total = max(self.hinge_trace_rows(), 0)
-        rows = total - int(row0) if rows is None else int(rows)
-        if row0 < 0 or rows < 0 or row0 + rows > total:
-            raise ValueError(f"rows [{row0}, {row0 + rows}) are not rows of a table of {total}")
-        return int(row0), rows
 
     def hinge_trace(self, row0=0, rows=None):
         """rows [row0, row0 + rows) of the readings table (mgf_batch_get_hinge_trace; rows=None: to the table's end): an array
         [rows, hinge_count()] of HINGE_READING_DTYPE, or of HINGE_TRACE_FULL_DTYPE where the table was set with full=True.  One
         download, waited for."""
-        row0, rows = self._hinge_trace_span(row0, rows)
-        out = np.zeros((rows, max(self.hinge_count(), 0)), HINGE_TRACE_FULL_DTYPE if getattr(self, "_hinge_trace_full", False) else HINGE_READING_DTYPE)
-        _check(load_library().mgf_batch_get_hinge_trace(self._h, out.ctypes.data if out.size else None, row0, rows))
-        return out
+        return self._enc_trace(_HINGE_ENC, row0, rows)
 
     def hinge_trace_dev(self, out_dev, row0=0, rows=None):
         """hinge_trace as a device-to-device copy, enqueued on the context's stream and not waited for (mgf_batch_get_hinge_trace_dev).
         out_dev: CUDA float32 [rows * hinge_count(), 8] - 16 with full=True - or an integer address."""
-        row0, rows = self._hinge_trace_span(row0, rows)
-        cols = 16 if getattr(self, "_hinge_trace_full", False) else 8
-        _check(load_library().mgf_batch_get_hinge_trace_dev(self._h, _dev_arg(out_dev, "float32", cols, rows * max(self.hinge_count(), 0), "out_dev"), row0, rows))
+        self._enc_trace(_HINGE_ENC, row0, rows, out_dev, dev=True)
 
     # ---- slider joints between bodies: three angular rows, two off-axis rows, a limit, a motor or a lock along the axis ---------------------
     def set_sliders(self, world, body=None, other=-1, pa=None, pb=None, ax=None, ua=None, bx=None, ub=None, beta=0.0, lo=0.0, hi=0.0, fmax=0.0,
@@ -2759,49 +2774,33 @@ class WorldBatch:
         [slider_count()] in the rig's order - d (the travel along the axis), rate (as the next solve's motor and axis rows see it), side
         (+1 / -1: the next solve's limit row is on, above hi / below lo; 2: locked; 0: off), off (the far anchor's distance from the
         axis along the two references) and e (the frames' error).  One launch, one download; the state is not touched."""
-        out = np.zeros(max(self.slider_count(), 0), SLIDER_READING_DTYPE)
-        _check(load_library().mgf_batch_read_sliders(self._h, out.ctypes.data if len(out) else None))
-        return out
+        return self._enc_read(_SLIDER_ENC)
 
     def read_sliders_dev(self, out_dev):
         """read_sliders enqueued on the context's stream and not waited for (mgf_batch_read_sliders_dev).  out_dev: CUDA float32
         [slider_count(), 8], or an integer address aligned to 16 bytes."""
-        n = max(self.slider_count(), 0)
-        _check(load_library().mgf_batch_read_sliders_dev(self._h, _dev_arg(out_dev, "float32", 8, n, "out_dev")))
+        self._enc_read(_SLIDER_ENC, out_dev, dev=True)
 
     def set_slider_trace(self, rows, full=False):
         """the sliders' readings table made `rows` rows of slider_count() entries of zeros (mgf_batch_set_slider_trace): tick t < rows of
         every rollout form writes row t behind the tick, later ticks write nothing.  full=True: an entry also carries the eight impulse
         words of the tick's slider solve (SLIDER_TRACE_FULL_DTYPE; am / dt is the motor's force).  rows = 0 frees the table: no trace,
         which is the default and what set_sliders leaves."""
-        _check(load_library().mgf_batch_set_slider_trace(self._h, int(rows), SLIDER_TRACE_FULL if full else SLIDER_TRACE_READING))
-        self._slider_trace_full = bool(full)
+        self._enc_set_trace(_SLIDER_ENC, rows, full)
 
     def slider_trace_rows(self):
         return load_library().mgf_batch_slider_trace_rows(self._h)
-
-    def _slider_trace_span(self, row0, rows):
-        total = max(self.slider_trace_rows(), 0)
-        rows = total - int(row0) if rows is None else int(rows)
-        if row0 < 0 or rows < 0 or row0 + rows > total:
-            raise ValueError(f"rows [{row0}, {row0 + rows}) are not rows of a table of {total}")
-        return int(row0), rows
 
     def slider_trace(self, row0=0, rows=None):
         """rows [row0, row0 + rows) of the sliders' readings table (mgf_batch_get_slider_trace; rows=None: to the table's end): an array
         [rows, slider_count()] of SLIDER_READING_DTYPE, or of SLIDER_TRACE_FULL_DTYPE where the table was set with full=True.  One
         download, waited for."""
-        row0, rows = self._slider_trace_span(row0, rows)
-        out = np.zeros((rows, max(self.slider_count(), 0)), SLIDER_TRACE_FULL_DTYPE if getattr(self, "_slider_trace_full", False) else SLIDER_READING_DTYPE)
-        _check(load_library().mgf_batch_get_slider_trace(self._h, out.ctypes.data if out.size else None, row0, rows))
-        return out
+        return self._enc_trace(_SLIDER_ENC, row0, rows)
 
     def slider_trace_dev(self, out_dev, row0=0, rows=None):
         """slider_trace as a device-to-device copy, enqueued on the context's stream and not waited for (mgf_batch_get_slider_trace_dev).
         out_dev: CUDA float32 [rows * slider_count(), 8] - 16 with full=True - or an integer address."""
-        row0, rows = self._slider_trace_span(row0, rows)
-        cols = 16 if getattr(self, "_slider_trace_full", False) else 8
-        _check(load_library().mgf_batch_get_slider_trace_dev(self._h, _dev_arg(out_dev, "float32", cols, rows * max(self.slider_count(), 0), "out_dev"), row0, rows))
+        self._enc_trace(_SLIDER_ENC, row0, rows, out_dev, dev=True)
 
     def counter(self, name):
         v = C.c_int64()

@@ -24,6 +24,14 @@ struct BatchRig {
   size_t off[4] = {0, 0, 0, 0}; // ... section k at off[k]: items, records, order, worlds
 };
 
+// What the encoders of a joint rig keep in the handle (host_batch_joint_read.inc): a member for the hinges' and one for the sliders'
+struct BatchJointTrace {
+  DBuf<float4> tab;                     // the readings table, `rows` rows of an entry a joint: two words, four with the impulses (mgf_batch_set_hinge_trace, _set_slider_trace)
+  int64_t rows = 0;                     // ... its rows; 0: no trace
+  int32_t format = 0;                   // ... and MGF_HINGE_TRACE_READING / _FULL, MGF_SLIDER_TRACE_READING / _FULL
+  DBuf<float4> out;                     // what the host-memory read of the rig downloads: two words a joint
+};
+
 // A rig of joints - ball joints, hinges, sliders (host_batch_joint.inc): the rig, and what a solve of it leaves in the handle
 template <class Rec>
 struct BatchJointRig : BatchRig<Rec> {
@@ -130,14 +138,7 @@ struct mgf_batch {
   DBuf<unsigned long long> a_skipped;   // actuators whose gain * clamp(u) was not finite, cumulative (counter "actuators_skipped")
   DBuf<float> sp_wr;                    // the impulses of the springs, twelve floats a spring: written by one launch of a call, applied by the next
   DBuf<unsigned long long> sp_skipped;  // springs whose wrench was zeroed (len == 0, len or f * h not finite), cumulative (counter "springs_skipped")
-  DBuf<float4> ht_tab;                  // the hinges' readings table, ht_rows rows of an entry a hinge: two words, four with the impulses (mgf_batch_set_hinge_trace)
-  int64_t ht_rows = 0;                  // ... its rows; 0: no trace (host_batch_hinge_read.inc)
-  int32_t ht_format = 0;                // ... and MGF_HINGE_TRACE_READING / _FULL
-  DBuf<float4> ht_out;                  // what the host-memory read of the hinges downloads: two words a hinge
-  DBuf<float4> st_tab;                  // the sliders' readings table, st_rows rows of an entry a slider: two words, four with the impulses (mgf_batch_set_slider_trace)
-  int64_t st_rows = 0;                  // ... its rows; 0: no trace (host_batch_slider_read.inc)
-  int32_t st_format = 0;                // ... and MGF_SLIDER_TRACE_READING / _FULL
-  DBuf<float4> st_out;                  // what the host-memory read of the sliders downloads: two words a slider
+  BatchJointTrace hinge_trace, slider_trace;  // the hinges' and the sliders' readings tables and staging buffers (host_batch_joint_read.inc)
   // the rollouts (host_batch_rollout.inc)
   DBuf<uint32_t> d_act;                 // per world, beside d_done: ticks of the call whose actuation the world has behind it (k_batch_rollout.h)
   int64_t r_launches = 0;               // launches of the last rollout call beyond its ticks' own (counter "rollout_launches")
@@ -904,6 +905,11 @@ struct BatchJointHook {
   uint32_t lds = 0;  // ... and its dynamic LDS
   bool on = false;   // the rig is not empty
 };
+// ... and of one kind of encoders (host_batch_joint_read.inc): its launch behind the record of every tick that has a row in the kind's readings table
+struct BatchJointReadHook {
+  BatchJointReadArgs A;  // n; the train fills the rest in, the handle's view per PASS, the table's row per TICK
+  int32_t format = -1;   // kJointReadReading / _Full / _FullZero (k_batch_joint_read.h); -1: no trace of the kind
+};
 struct BatchRolloutHook {
   BatchRolloutArgs A;    // everything but done, act, tick and count, which the train fills in
   int32_t mode = 0;      // MGF_ACTUATE_IMPULSE / _FORCE
@@ -916,10 +922,7 @@ struct BatchRolloutHook {
   BatchSensorArgs R;     // the sensor trace's cast (k_batch_scan.h): mask, out and parts - the handle's scratch; the train fills the rest in per PASS
   BatchScanRowsArgs W;   // ... and its rows: out - row 0 - and n_sensor; the train fills the rest in per PASS
   int32_t scan = -1;     // MGF_ROLLOUT_SENSOR_HIT / _DEPTH: k_batch_scan_rays and k_batch_scan_rows behind every tick's touch trace; -1: no sensor trace
-  BatchHingeReadArgs E;  // the hinge trace's launch (k_batch_hinge_read.h): n; the train fills the rest in, the handle's view per PASS, the table's row per TICK
-  int32_t hinge_read = -1;  // kHingeReadReading / _Full / _FullZero: k_batch_read_hinges behind every tick t < the table's rows; -1: no hinge trace
-  BatchSliderReadArgs L;  // the slider trace's launch (k_batch_slider_read.h): n; the train fills the rest in, the handle's view per PASS, the table's row per TICK
-  int32_t slider_read = -1;  // kSliderReadReading / _Full / _FullZero: k_batch_read_sliders behind every tick t < the table's rows; -1: no slider trace
+  BatchJointReadHook hinge_read, slider_read;  // k_batch_read_hinges, k_batch_read_sliders behind every tick t < the kind's table's rows, in this order
   int64_t launches = 0;  // what the hook added to the train's launches
 };
 // (host_batch_joint.inc, _hinge.inc, _slider.inc, behind this file) the kinds of joints, and a kind's part of the train: per pass what its kernel reads of the handle, per tick its launch
@@ -930,8 +933,11 @@ template <class T>
 static void batch_joint_pass(const mgf_batch* b, BatchJointHook& H);
 template <class T>
 static mgf_status batch_joint_tick(mgf_batch* b, BatchJointHook& H, uint32_t t, int64_t* launches);
-static void batch_hinge_read_view(const mgf_batch* b, BatchHingeReadArgs* A);  // (host_batch_hinge_read.inc, behind this file) what the hinge trace's kernel reads of the handle
-static void batch_slider_read_view(const mgf_batch* b, BatchSliderReadArgs* A);  // (host_batch_slider_read.inc, behind this file) what the slider trace's kernel reads of the handle
+// (host_batch_joint_read.inc, behind this file) a kind of encoders' part of the train: per pass what its kernel reads of the handle, per tick its launch into the table's row
+template <class T>
+static void batch_joint_read_pass(const mgf_batch* b, BatchJointReadHook& H);
+template <class T>
+static mgf_status batch_joint_read_tick(mgf_batch* b, BatchJointReadHook& H, uint32_t t, int64_t* launches);
 static uint32_t batch_touch_tile(const mgf_batch* b);  // (host_batch_touch.inc, behind this file) the words of dynamic LDS the contact sensors' fold stages
 // (host_batch_query.inc, behind this file) the dynamic LDS of a ray cast with a workgroup per work item; what a cast reads of the handle; has it obstacles to meet
 static uint32_t batch_ray_lds(const mgf_batch* b);
@@ -992,14 +998,8 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
       batch_joint_pass<JointKind>(b, hook->joints);
       batch_joint_pass<HingeKind>(b, hook->hinges);
       batch_joint_pass<SliderKind>(b, hook->sliders);
-    }
-    if (hook && hook->hinge_read >= 0) {  // (the same rule for the hinge trace: the rig, the impulse buffer and the TABLE are looked up again for every pass)
-      batch_hinge_read_view(b, &hook->E);
-      hook->E.done = b->d_done.p; hook->E.act = b->d_act.p;
-    }
-    if (hook && hook->slider_read >= 0) {  // (and for the slider trace: the rig, the impulse buffer and the TABLE are looked up again for every pass)
-      batch_slider_read_view(b, &hook->L);
-      hook->L.done = b->d_done.p; hook->L.act = b->d_act.p;
+      batch_joint_read_pass<HingeKind>(b, hook->hinge_read);  // (the same rule for the encoders' traces: the rig, the impulse buffer and the TABLE)
+      batch_joint_read_pass<SliderKind>(b, hook->slider_read);
     }
     if (hook && hook->touch >= 0) {  // (batch_allot moves the lists between passes: the view is rebuilt with BatchArgs, never kept from an earlier pass)
       BatchRig<mgf_batch_touch>& R = b->touches;
@@ -1079,27 +1079,9 @@ static mgf_status batch_step_run(mgf_batch* b, float dt, int32_t iters, int64_t 
         LAUNCH_CHECK();
         hook->launches += MGF_BATCH_ROLLOUT_SENSOR_LAUNCHES_PER_TICK;
       }
-      if (hook && hook->hinge_read >= 0 && (int64_t)t < b->ht_rows) {  // (behind the record: act[k] is final; row t, and no launch for a tick the table has no row for)
-        BatchHingeReadArgs& E = hook->E;
-        const unsigned blocks = (E.n + kBatchBlock - 1) / kBatchBlock;
-        E.tick = t;
-        E.out = b->ht_tab.p + (size_t)t * E.n * (hook->hinge_read == kHingeReadReading ? 2u : 4u);
-        if (hook->hinge_read == kHingeReadFull) k_batch_read_hinges<true, kHingeReadFull><<<blocks, kBatchBlock, 0, s>>>(E);
-        else if (hook->hinge_read == kHingeReadFullZero) k_batch_read_hinges<true, kHingeReadFullZero><<<blocks, kBatchBlock, 0, s>>>(E);
-        else k_batch_read_hinges<true, kHingeReadReading><<<blocks, kBatchBlock, 0, s>>>(E);
-        LAUNCH_CHECK();
-        hook->launches += MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK;
-      }
-      if (hook && hook->slider_read >= 0 && (int64_t)t < b->st_rows) {  // (behind the record: act[k] is final; row t, and no launch for a tick the table has no row for)
-        BatchSliderReadArgs& L = hook->L;
-        const unsigned blocks = (L.n + kBatchBlock - 1) / kBatchBlock;
-        L.tick = t;
-        L.out = b->st_tab.p + (size_t)t * L.n * (hook->slider_read == kSliderReadReading ? 2u : 4u);
-        if (hook->slider_read == kSliderReadFull) k_batch_read_sliders<true, kSliderReadFull><<<blocks, kBatchBlock, 0, s>>>(L);
-        else if (hook->slider_read == kSliderReadFullZero) k_batch_read_sliders<true, kSliderReadFullZero><<<blocks, kBatchBlock, 0, s>>>(L);
-        else k_batch_read_sliders<true, kSliderReadReading><<<blocks, kBatchBlock, 0, s>>>(L);
-        LAUNCH_CHECK();
-        hook->launches += MGF_BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK;
+      if (hook) {  // (behind the record: act[k] is final; the hinges' readings, then the sliders', row t - and no launch for a tick a table has no row for)
+        MGF_TRY(batch_joint_read_tick<HingeKind>(b, hook->hinge_read, t, &hook->launches));
+        MGF_TRY(batch_joint_read_tick<SliderKind>(b, hook->slider_read, t, &hook->launches));
       }
     }
     MGF_TRY(d2h(ctx, done.data(), b->d_done.p, K));

@@ -17,6 +17,14 @@ struct HingeKind {
   static constexpr BatchJointRig<Rec> mgf_batch::*rig = &mgf_batch::hinges;
   template <bool GATED>
   static constexpr auto launch = k_batch_hinge_solve<GATED>;
+  // the kind's encoders (host_batch_joint_read.inc)
+  using Reading = mgf_hinge_reading;
+  static constexpr BatchJointTrace mgf_batch::*trace = &mgf_batch::hinge_trace;
+  static constexpr const char* caps = "HINGE";
+  static constexpr int64_t read_launches = MGF_BATCH_HINGE_READ_LAUNCHES, read_per_tick = MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK;
+  static constexpr int32_t trace_reading = MGF_HINGE_TRACE_READING, trace_full = MGF_HINGE_TRACE_FULL;
+  template <bool GATED, int FORMAT>
+  static constexpr auto read = k_batch_read_hinges<GATED, FORMAT>;
 };
 
 extern "C" mgf_status mgf_batch_set_hinges(mgf_batch* b, const mgf_batch_hinge* j, int64_t n_in) {
@@ -47,7 +55,7 @@ extern "C" mgf_status mgf_batch_set_hinges(mgf_batch* b, const mgf_batch_hinge* 
       return fail(MGF_ERR_INVALID, "a world holds at most MGF_BATCH_MAX_WORLD_HINGES (256) hinges: the rig was not changed");
   }
   batch_joint_plan(b->hinges, j, n);
-  b->ht_rows = 0;  // (the readings table is rows of the OLD rig's hinges: the trace is off until mgf_batch_set_hinge_trace names it again)
+  b->hinge_trace.rows = 0;  // (the readings table is rows of the OLD rig's hinges: the trace is off until mgf_batch_set_hinge_trace names it again)
   return MGF_OK;
 }
 

@@ -14,7 +14,8 @@
 // Where the hinge rig is not empty and the readings table has rows (mgf_batch_set_hinge_trace), the hinge trace's one launch
 // (k_batch_hinge_read.h, MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK) goes behind the record of every tick t < rows.
 // Where the slider rig is not empty and its readings table has rows (mgf_batch_set_slider_trace), the slider trace's one launch
-// (k_batch_slider_read.h, MGF_BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK) goes behind the hinge trace's of every tick t < rows.
+// (k_batch_slider_read.h, MGF_BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK) goes behind the hinge trace's of every tick t < rows
+// (both through host_batch_joint_read.inc).
 // The rig is the actuators' (BatchRig::items: no plan and no upload format of its own), the trace rows are k_batch_dev_gather's.
 // "drive_launches" is not touched.
 // The order of both calls: the refusals that need no handle, the handle's own, (device form) EVERY device pointer looked up for its
@@ -25,10 +26,9 @@ static mgf_status batch_spring_ready(mgf_batch* b, float h, float* out_dev, Batc
 // (host_batch_joint.inc, behind this file) a kind of joints' arguments for the train: the rig and the target table up, the impulse buffer and the skip counter there
 template <class T>
 static mgf_status batch_joint_hook(mgf_batch* b, float h, int32_t iters, BatchJointHook* H);
-// (host_batch_hinge_read.inc, behind this file) the hinge trace's arguments for the train: the rig up, the impulse buffer there
-static mgf_status batch_hinge_read_ready(mgf_batch* b, BatchHingeReadArgs* A);
-// (host_batch_slider_read.inc, behind this file) the slider trace's arguments for the train: the rig up, the impulse buffer there
-static mgf_status batch_slider_read_ready(mgf_batch* b, BatchSliderReadArgs* A);
+// (host_batch_joint_read.inc, behind this file) a kind of encoders' arguments for the train, where its readings table has rows: the rig up, the impulse buffer there
+template <class T>
+static mgf_status batch_joint_read_hook(mgf_batch* b, int32_t iters, BatchJointReadHook* H);
 
 struct RolloutBytes { size_t u, body, out[4], touch, sensor; };  // what the call touches of u, body, x, q, v, omega, touch, sensor
 // the touch trace of mgf_batch_rollout_touches / _touches_dev (host_batch_trace.inc): rows of n reports, device memory when it reaches the core.
@@ -137,14 +137,8 @@ static mgf_status batch_rollout_run(mgf_batch* b, float dt, int32_t iters, int64
   MGF_TRY(batch_joint_hook<JointKind>(b, dt, iters, &H.joints));  // (where the rig is not empty and iters > 0: with iters == 0 the solve calls enqueue nothing)
   MGF_TRY(batch_joint_hook<HingeKind>(b, dt, iters, &H.hinges));
   MGF_TRY(batch_joint_hook<SliderKind>(b, dt, iters, &H.sliders));
-  if (hinges && b->ht_rows > 0) {  // (the readings table has rows: k_batch_read_hinges behind every tick t < rows; with iters == 0 no solve wrote an impulse)
-    MGF_TRY(batch_hinge_read_ready(b, &H.E));
-    H.hinge_read = b->ht_format == MGF_HINGE_TRACE_FULL ? (iters > 0 ? kHingeReadFull : kHingeReadFullZero) : kHingeReadReading;
-  }
-  if (sliders && b->st_rows > 0) {  // (the sliders' readings table has rows: k_batch_read_sliders behind every tick t < rows; with iters == 0 no solve wrote an impulse)
-    MGF_TRY(batch_slider_read_ready(b, &H.L));
-    H.slider_read = b->st_format == MGF_SLIDER_TRACE_FULL ? (iters > 0 ? kSliderReadFull : kSliderReadFullZero) : kSliderReadReading;
-  }
+  MGF_TRY(batch_joint_read_hook<HingeKind>(b, iters, &H.hinge_read));  // (where the rig is not empty and its readings table has rows: the kind's read kernel behind every tick t < rows)
+  MGF_TRY(batch_joint_read_hook<SliderKind>(b, iters, &H.slider_read));
   if (touches) {  // (the sensors' rig up ahead of the train; the lists' view is the train's to fill, pass by pass)
     MGF_TRY(batch_rig_up(b, b->touches, "contact sensor", 3));
     static_assert(sizeof(mgf_touch_report) == 64 && sizeof(TouchWord) == 16, "k_batch_trace_touch writes a report as four words of 16 bytes, a short one as one");

@@ -3,7 +3,7 @@
 // rows that hold other's frame onto body's, two linear rows that hold other's anchor on the axis through body's, and along the axis an
 // optional limit of the travel, an optional velocity motor with a force cap, or a lock (a weld) - solved by sequential impulses over
 // the velocities resident on the device (k_batch_slider.h).  Part of the single translation unit mgf_hip.hip (included there, in
-// order, behind host_batch_hinge_read.inc); not compiled on its own.
+// order, behind host_batch_hinge.inc); not compiled on its own.
 //
 // The tenth rig.  Every step but the checks of a record is the joint rigs' (host_batch_joint.inc), under SliderKind: the plan, the
 // target table, the upload, the launch - MGF_BATCH_SLIDER_LAUNCHES = 1 - and a rollout's launch behind the hinges' and ahead of the
@@ -18,6 +18,14 @@ struct SliderKind {
   static constexpr BatchJointRig<Rec> mgf_batch::*rig = &mgf_batch::sliders;
   template <bool GATED>
   static constexpr auto launch = k_batch_slider_solve<GATED>;
+  // the kind's encoders (host_batch_joint_read.inc)
+  using Reading = mgf_slider_reading;
+  static constexpr BatchJointTrace mgf_batch::*trace = &mgf_batch::slider_trace;
+  static constexpr const char* caps = "SLIDER";
+  static constexpr int64_t read_launches = MGF_BATCH_SLIDER_READ_LAUNCHES, read_per_tick = MGF_BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK;
+  static constexpr int32_t trace_reading = MGF_SLIDER_TRACE_READING, trace_full = MGF_SLIDER_TRACE_FULL;
+  template <bool GATED, int FORMAT>
+  static constexpr auto read = k_batch_read_sliders<GATED, FORMAT>;
 };
 
 extern "C" mgf_status mgf_batch_set_sliders(mgf_batch* b, const mgf_batch_slider* j, int64_t n_in) {
@@ -50,7 +58,7 @@ extern "C" mgf_status mgf_batch_set_sliders(mgf_batch* b, const mgf_batch_slider
       return fail(MGF_ERR_INVALID, "a world holds at most MGF_BATCH_MAX_WORLD_SLIDERS (256) sliders: the rig was not changed");
   }
   batch_joint_plan(b->sliders, j, n);
-  b->st_rows = 0;  // (the readings table is rows of the OLD rig's sliders: the trace is off until mgf_batch_set_slider_trace names it again)
+  b->slider_trace.rows = 0;  // (the readings table is rows of the OLD rig's sliders: the trace is off until mgf_batch_set_slider_trace names it again)
   return MGF_OK;
 }
 

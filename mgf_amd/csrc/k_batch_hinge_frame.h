@@ -1,6 +1,6 @@
 // The frame lines of a hinge's SETUP (include/mgf_hip.h, "hinge joints between bodies"), written once for every kernel that forms a
 // hinge's frames: the hinges' solver (k_batch_hinge.h), the sliders', whose frames are the same lines (k_batch_slider.h), and the
-// hinges' encoders, which form them without solving (k_batch_hinge_read.h).  (Part of the kernel set described in kernels.h.)
+// encoders' skeleton, which forms them without solving (k_batch_joint_read.h).  (Part of the kernel set described in kernels.h.)
 //
 // Every helper is the header's line, the same helpers (rotate, cross, dot) in the same order, each a separately rounded f32 operation
 // (-ffp-contract=off): the encoders read bit for bit what the solver's setup forms of the same state.  The ends are loaded by

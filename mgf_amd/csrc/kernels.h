@@ -190,13 +190,6 @@
 //                      a torque cap, a limit of the hinge angle, two angular rows that keep the axes parallel, the point - solved in
 //                      one turn of the lane with both bodies' velocities in registers; the same plan, slots, dataflow, bounded spin
 //                      and gate; the motors' targets from a row of the handle's table
-//   k_batch_read_hinges<GATED, FORMAT> (k_batch_hinge_read.h; the frame lines in k_batch_hinge_frame.h)
-//                      hinge encoders (mgf_batch_read_hinges / _read_hinges_dev, and behind the record of every tick of a rollout that
-//                      has a row in the readings table - mgf_batch_set_hinge_trace): a lane per hinge by the caller's index forms the
-//                      hinge's SETUP frames from the state as it stands and writes (c, sn, rate, side, gap, tilt2) - 32 bytes, or 64
-//                      with the eight impulse words of the tick's solve behind them - with float4 stores; no plan, no LDS, no
-//                      division, no atomic, nothing written but the output.  GATED: the traces' gate done[k] == t + 1 &&
-//                      act[k] <= t + 1, the lane's own, ahead of every load of state
 //   k_batch_slider_solve<GATED> (k_batch_slider.h)
 //                      slider joints (mgf_batch_set_sliders / _set_slider_targets / _solve_sliders / _solve_sliders_dev, and behind the
 //                      hinges of a rollout's tick): k_batch_hinge_solve's launch with the rows of a slider - a velocity motor with a
@@ -204,12 +197,19 @@
 //                      together, two linear rows that hold the anchor on the axis - solved in one turn of the lane with both
 //                      bodies' velocities in registers; the same plan, slots, dataflow, bounded spin and gate; the motors' targets
 //                      from a row of the handle's table
-//   k_batch_read_sliders<GATED, FORMAT> (k_batch_slider_read.h; the frame lines in k_batch_hinge_frame.h)
-//                      slider encoders (mgf_batch_read_sliders / _read_sliders_dev, and behind the record of every tick of a rollout that
-//                      has a row in the readings table - mgf_batch_set_slider_trace): a lane per slider by the caller's index forms the
-//                      slider's SETUP frames from the state as it stands and writes (d, rate, side, off1, off2, e) - 32 bytes, or 64
-//                      with the eight impulse words of the tick's solve behind them - with float4 stores; k_batch_read_hinges' shape
-//                      and gate, the lane's own, ahead of every load of state
+//   batch_joint_read<Reading, GATED, FORMAT> (k_batch_joint_read.h; the frame lines in k_batch_hinge_frame.h) - no kernel: the skeleton
+//                      of the two encoders below, each of which is one call of it - a lane per joint by the caller's index loads the
+//                      record and both ends, forms the SETUP frames from the state as it stands, takes the entry's two words from
+//                      the kind's Reading and writes them - 32 bytes, or 64 with the eight impulse words of the tick's solve behind
+//                      them - with float4 stores; no plan, no LDS, no division, no atomic, nothing written but the output.  GATED:
+//                      the traces' gate done[k] == t + 1 && act[k] <= t + 1, the lane's own, ahead of every load of state
+//   k_batch_read_hinges<GATED, FORMAT> (k_batch_hinge_read.h)
+//                      hinge encoders (mgf_batch_read_hinges / _read_hinges_dev, and behind the record of every tick of a rollout that
+//                      has a row in the readings table - mgf_batch_set_hinge_trace): (c, sn, rate, side, gap, tilt2) a hinge
+//   k_batch_read_sliders<GATED, FORMAT> (k_batch_slider_read.h)
+//                      slider encoders (mgf_batch_read_sliders / _read_sliders_dev, and behind the hinge trace's launch of every tick
+//                      that has a row in the sliders' table - mgf_batch_set_slider_trace): (d, rate, side, off1, off2, e) a slider,
+//                      with two loads of its own for the ends' linear velocities
 //   k_batch_trace_touch<FORMAT> (k_batch_trace.h)
 //                      the touch trace of a rollout (mgf_batch_rollout_touches / _touches_dev): k_batch_touch's fold of every world's
 //                      list behind tick t into row t of the reports, one launch a tick behind k_batch_rollout_record; the train's gate
@@ -262,8 +262,9 @@
 #include "k_batch_joint_loop.h"  // the joint solvers' skeleton: one launch shape and one dataflow loop over a Rows type (batch_joint_loop)
 #include "k_batch_joint.h"  // ball joints between bodies: sequential impulses over the resident velocities, a workgroup per world (k_batch_joint_solve)
 #include "k_batch_hinge.h"  // hinge joints between bodies: the joints' launch with motor, limit, angular and point rows (k_batch_hinge_solve)
-#include "k_batch_hinge_read.h"  // hinge encoders: angle, rate, limit side, gap and tilt from the resident state, a lane per hinge (k_batch_read_hinges)
 #include "k_batch_slider.h"  // slider joints between bodies: the hinges' launch with motor, axis, angular and off-axis rows (k_batch_slider_solve)
+#include "k_batch_joint_read.h"  // the encoders' skeleton: one lane's walk, gate, loads and stores over a Reading type (batch_joint_read)
+#include "k_batch_hinge_read.h"  // hinge encoders: angle, rate, limit side, gap and tilt from the resident state, a lane per hinge (k_batch_read_hinges)
 #include "k_batch_slider_read.h"  // slider encoders: travel, rate, limit side, off-axis gap and frame error from the resident state, a lane per slider (k_batch_read_sliders)
 #include "k_batch_part_query.h"  // rays, sweeps and box queries that see the parts of bodies of several components (k_batch_pq_*)
 #include "k_batch_trace.h"  // the touch trace of a rollout: the contact sensors' reports behind every tick (k_batch_trace_touch)

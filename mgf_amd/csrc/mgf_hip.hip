@@ -181,8 +181,7 @@ extern "C" mgf_status mgf_exclusive_scan_u32(mgf_ctx* ctx, const uint32_t* in, i
 #include "host_batch_spring.inc"
 #include "host_batch_joint.inc"
 #include "host_batch_hinge.inc"
-#include "host_batch_hinge_read.inc"
 #include "host_batch_slider.inc"
-#include "host_batch_slider_read.inc"
+#include "host_batch_joint_read.inc"
 #include "host_batch_trace.inc"
 #include "host_batch_scan.inc"

@@ -3,8 +3,9 @@ mgf_batch_get_hinge_trace, mgf_batch_get_hinge_trace_dev) without a GPU: the hea
 the calls, the record of 32 bytes and the constants; what needs no device is refused in the header's order; the f32 restatement of the
 reading (tests/batch_hinge_read_cases.py) holds against the float64 one within bounds derived from the count of rounded operations, its
 angle against tests/batch_hinge_cases.py's thetas, its side against that file's setup; the arm's angle stays clear of its limits; the
-kernel has a lane's own gate ahead of every load of state, no scratch and no spills, and the solvers' kernels are as they were; and the
-rollout's sources launch the read once, behind the record, under t < rows."""
+kernel's reading holds the hinge's own lines, the kernel uses no scratch and spills nothing, and the solvers' kernels are as they were.
+What the hinge encoders share with the sliders' - the kernel's skeleton, the host steps, the train's site - is asserted once, in
+tests/test_world_batch_encoder_family_host.py."""
 import ctypes as C
 import os
 import re
@@ -21,7 +22,7 @@ from tests.util import ROOT, kernel_resources, read
 f32 = np.float32
 CALLS = ("mgf_batch_read_hinges", "mgf_batch_read_hinges_dev", "mgf_batch_set_hinge_trace", "mgf_batch_hinge_trace_rows", "mgf_batch_get_hinge_trace",
          "mgf_batch_get_hinge_trace_dev")
-READ_FILE = "host_batch_hinge_read.inc"
+READ_FILE = "host_batch_joint_read.inc"
 NAMES = ["c", "sn", "rate", "side", "gap", "tilt2"]
 
 
@@ -131,46 +132,11 @@ def test_what_needs_no_device_is_refused_in_the_headers_order():
         assert fn(None, None, -1, -1) == INV and "batch is NULL" in err()                     # the handle first
         assert fn(fake, out, -1, -1) == INV and "row0 is negative" in err()                   # row0 ahead of n_rows
         assert fn(fake, out, 0, -1) == INV and "n_rows is negative" in err()
-    src = read("mgf_amd", "csrc", READ_FILE)
-    enqueue = r"batch_hinge_read_run\(|batch_hinge_read_ready\(|batch_rig_up\(|batch_push\(|hipMemsetAsync|hipMemcpyAsync|<<<|\.ensure\(|h2d\(|hipFree\("
-    # the read calls: the refusals, the context, (device form) the pointer looked up - and only then the first thing is enqueued
-    args = src[src.index("static mgf_status batch_hinge_read_args("):src.index("// a device pointer the kernel stores")]
-    assert args.index("batch_rig_handle(b)") < args.index("!out && !b->hinges.recs.empty()") and not re.search(enqueue, args)
-    host_form = src[src.index('extern "C" mgf_status mgf_batch_read_hinges('):src.index('extern "C" mgf_status mgf_batch_read_hinges_dev(')]
-    first = min(m.start() for m in re.finditer(enqueue, host_form))
-    assert host_form.index("batch_hinge_read_args(b, out)") < host_form.index("ctx_bind(") < host_form.index("if (n == 0) return MGF_OK;") < first
-    assert host_form.count("hipStreamSynchronize") == 1 and host_form.count("hipMemcpyAsync") == 1 and "hipMemcpyHostToDevice" not in host_form   # one download, one wait
-    dev = src[src.index('extern "C" mgf_status mgf_batch_read_hinges_dev('):src.index("static size_t hinge_trace_entry(")]
-    first = min(m.start() for m in re.finditer(enqueue, dev))
-    assert dev.index("batch_hinge_read_args(b, out_dev)") < dev.index("ctx_bind(") < dev.index('batch_hinge_dev_span(b, out_dev, 32 * n, "out_dev")') < first
-    assert dev.index("if (n == 0) return MGF_OK;") < first and "hipStreamSynchronize" not in dev and "hipMemcpy" not in dev
-    span = src[src.index("static mgf_status batch_hinge_dev_span("):src.index('extern "C" mgf_status mgf_batch_read_hinges(')]
-    assert span.index("dev_span(b->ctx, p, bytes, what)") < span.index("& 15u")
-    # pending host-side state goes up first, by the path the solve uses; one launch, counted where the solve counts its own
-    run = src[src.index("static mgf_status batch_hinge_read_run("):src.index("static mgf_status batch_hinge_read_args(")]
-    assert run.count("<<<") == 1 and run.index("batch_push(") < run.index("batch_hinge_read_ready(") < run.index("k_batch_read_hinges<false, kHingeReadReading><<<")
-    assert "b->d_launches += MGF_BATCH_HINGE_READ_LAUNCHES;" in run and "batch_single_parts(" not in src      # a reading reads no shapes
-    ready = src[src.index("static mgf_status batch_hinge_read_ready("):src.index("static mgf_status batch_hinge_read_run(")]
-    assert ready.index("batch_joint_far_ends<HingeKind>(b)") < ready.index('batch_rig_up(b, R, "hinge", 3)')   # (the joint rigs' check of the far ends: `other` against the lengths that go up)
-    assert "(uint32_t)R.recs[i].other >= b->h_n[(size_t)R.recs[i].world]" in read("mgf_amd", "csrc", "host_batch_joint.inc")
-    # the table: the refusals in the header's order, ahead of the context and of everything that changes the table
-    st = src[src.index('extern "C" mgf_status mgf_batch_set_hinge_trace('):src.index('extern "C" int64_t mgf_batch_hinge_trace_rows(')]
-    order = [st.index(s) for s in ("batch_rig_handle(b)", "rows < 0 || rows > (1 << 20)", "format != MGF_HINGE_TRACE_READING && format != MGF_HINGE_TRACE_FULL",
-                                   "overflows int64_t", "ctx_bind(", "b->ht_tab.ensure(", "hipMemsetAsync(b->ht_tab.p, 0, 16 * words, s)", "b->ht_rows = rows;")]
-    assert order == sorted(order) and min(m.start() for m in re.finditer(enqueue, st)) > st.index("ctx_bind(")
-    assert "hipFree(b->ht_tab.p)" in st and st.index("hipStreamSynchronize(s)") < st.index("hipFree(b->ht_tab.p)")   # rows == 0 frees it, behind the stream
-    ta = src[src.index("static mgf_status batch_hinge_trace_args("):src.index('extern "C" mgf_status mgf_batch_get_hinge_trace(')]
-    order = [ta.index(s) for s in ("batch_rig_handle(b)", "row0 < 0", "n_rows < 0", "n_rows > b->ht_rows - row0", "*bytes && !out")]
-    assert order == sorted(order) and not re.search(enqueue, ta)
-    get = src[src.index('extern "C" mgf_status mgf_batch_get_hinge_trace('):src.index('extern "C" mgf_status mgf_batch_get_hinge_trace_dev(')]
-    assert get.count("hipStreamSynchronize") == 1 and "hipMemcpyDeviceToHost" in get
-    gdev = src[src.index('extern "C" mgf_status mgf_batch_get_hinge_trace_dev('):]
-    assert gdev.index("batch_hinge_trace_args(") < gdev.index("ctx_bind(") < gdev.index('dev_span(b->ctx, out_dev, bytes, "out_dev")') < gdev.index("hipMemcpyAsync(")
-    assert "hipStreamSynchronize" not in gdev and "hipMemcpyDeviceToDevice" in gdev
+    # (the order of refusals, context, pointer look-up and first enqueue inside every call: tests/test_world_batch_encoder_family_host.py)
     # mgf_batch_set_hinges turns the trace off, with no device work
     rig = read("mgf_amd", "csrc", "host_batch_hinge.inc")
     body = rig[rig.index('extern "C" mgf_status mgf_batch_set_hinges('):rig.index('extern "C" int64_t mgf_batch_hinge_count(')]
-    assert body.index("batch_joint_plan(b->hinges, j, n);") < body.index("b->ht_rows = 0;") and not re.search(r"<<<|Async|hipMalloc|hipFree|\.ensure\(", body)
+    assert body.index("batch_joint_plan(b->hinges, j, n);") < body.index("b->hinge_trace.rows = 0;") and not re.search(r"<<<|Async|hipMalloc|hipFree|\.ensure\(", body)
 
 
 # ---- 3 ------------------------------------------------------------------------------------------------------------------------------------
@@ -264,31 +230,24 @@ def test_the_arms_angle_stays_clear_of_its_limits_but_for_two_ticks_at_most():
 
 
 # ---- 4 ------------------------------------------------------------------------------------------------------------------------------------
-def test_the_kernel_is_a_lane_per_hinge_with_its_own_gate_ahead_of_every_load_of_state():
+def test_the_hinges_reading_holds_the_hinges_own_lines_and_loads_nothing_of_its_own():
+    """The lane's walk, its gate ahead of every load and the stores are the skeleton's (k_batch_joint_read.h), asserted in
+    tests/test_world_batch_encoder_family_host.py; here: what HingeReading forms of the ends and the frames."""
     k = read("mgf_amd", "csrc", "k_batch_hinge_read.h")
-    body = k[k.index("void k_batch_read_hinges("):]
-    body = body[:body.index("\n}\n")]
-    gate = "if (GATED && !(A.done[k] == A.tick + 1u && A.act[k] <= A.tick + 1u)) return;"
-    assert gate in body and "template <bool GATED, int FORMAT>" in k
-    for load in ("joint_ends(", "rec[1]", "A.w_off[", "A.acc["):
-        assert body.index(gate) < body.index(load), load
-    assert body.index("if (i >= A.n) return;") < body.index("rec[0]") < body.index(gate)
+    body = k[k.index("struct HingeReading {"):k.index("template <bool GATED, int FORMAT>")]
+    for line in ("const float c = dot(F.U1, F.T1), sn = dot(F.U1, F.T2);", "const float rate = dot(b.om - a.om, F.A);",
+                 "const float side = hinge_side(f2u(w0.w), c, sn, w3.w, w4.w, w5.w);", "const float e1 = dot(F.B, F.T1), e2 = dot(F.B, F.T2);",
+                 "const float tilt2 = e1 * e1 + e2 * e2;", "return {make_float4(c, sn, rate, side), make_float4(F.C.x, F.C.y, F.C.z, tilt2)};"):
+        assert line in body, line
+    assert "template <bool GATED, int FORMAT>" in k and "void k_batch_read_hinges(" in k
     assert not re.search(r"atomic|__shared__|__syncthreads|s_dyn|A\.plan|A\.slots|A\.items| / ", body)       # no plan, no LDS, no atomic, no division
     assert not re.search(r"A\.B\.\w+\[[^\]]*\] =[^=]|srec\[[^\]]*\] =[^=]", k)
-    code = k[k.index("#pragma once"):] + read("mgf_amd", "csrc", "k_batch_hinge_frame.h").split("#pragma once")[1]
+    code = k[k.index("#pragma once"):] + read("mgf_amd", "csrc", "k_batch_joint_read.h").split("#pragma once")[1] + read("mgf_amd", "csrc", "k_batch_hinge_frame.h").split("#pragma once")[1]
     assert "atan" not in code and "sinf" not in code and "cosf" not in code               # no arctangent is evaluated on the device
-    stores = re.findall(r"\bo\[\d\] = ", body)
-    assert stores == ["o[0] = ", "o[1] = ", "o[2] = ", "o[3] = ", "o[2] = ", "o[3] = "] and "float4* o = A.out" in body
-    assert body.count("FORMAT == kHingeReadFull)") == 1 and body.count("FORMAT == kHingeReadFullZero)") == 1
-    assert len(re.findall(r"__global__ __launch_bounds__\(kBatchBlock\)", k)) == len(re.findall(r"__global__", k)) == 1
     # the frame lines are lifted, not pasted: written once in a header of their own, which the hinges' solver uses too (and through it
     # the sliders'); an end is loaded by the joint solvers' joint_end
-    frame = read("mgf_amd", "csrc", "k_batch_hinge_frame.h")
-    assert '#include "k_batch_hinge_frame.h"' in k and "rotate(" not in body and "cross(" not in body
-    for fn in ("HingeFrame hinge_frame(", "float hinge_side("):
-        assert "__device__ __forceinline__ " + fn in frame, fn
-    assert "__device__ __forceinline__ JointEnd joint_end(" in read("mgf_amd", "csrc", "k_batch_joint_loop.h") and "srec[" not in frame and "srec[" not in body
-    assert "F.T2 = cross(F.A, F.T1);" in frame and "F.C = Pb - Pa;" in frame and "cphi <= ch" in frame and "__global__" not in frame
+    assert '#include "k_batch_joint_read.h"' in k and '#include "k_batch_hinge_frame.h"' in read("mgf_amd", "csrc", "k_batch_joint_read.h")
+    assert "rotate(" not in body and "cross(" not in body and "srec[" not in body
     solver = re.sub(r"//[^\n]*", "", read("mgf_amd", "csrc", "k_batch_hinge.h"))
     assert '#include "k_batch_hinge_frame.h"' in solver and "hinge_frame(a, b, has_b, w1, w2, w3, w4, w5, w6)" in solver and "rotate(" not in solver   # no second copy
 
@@ -313,35 +272,6 @@ def test_the_new_kernel_uses_no_scratch_and_spills_nothing_and_the_solvers_are_a
 
 
 # ---- 5 ------------------------------------------------------------------------------------------------------------------------------------
-def test_the_rollout_launches_the_read_once_behind_the_record_under_t_below_rows():
-    host = read("mgf_amd", "csrc", "host_batch.inc")
-    roll = read("mgf_amd", "csrc", "host_batch_rollout.inc")
-    core = roll[roll.index("static mgf_status batch_rollout_run("):roll.index('extern "C" mgf_status mgf_batch_rollout_dev(')]
-    arm = "if (hinges && b->ht_rows > 0) {"
-    assert (core.index("batch_push(") < core.index("batch_joint_hook<HingeKind>(") < core.index(arm) < core.index("batch_hinge_read_ready(b, &H.E)")
-            < core.index("batch_step_run(b, dt, iters, n_ticks, stats, &H)"))
-    assert "b->ht_format == MGF_HINGE_TRACE_FULL ? (iters > 0 ? kHingeReadFull : kHingeReadFullZero) : kHingeReadReading" in core   # iters == 0: no solve, zeros
-    assert core.count("batch_hinge_read_ready(") == 1 and "hinge_read" not in roll[roll.index('extern "C" mgf_status mgf_batch_rollout_dev('):]   # no entry point changes
-    train = host[host.index("static mgf_status batch_step_run("):host.index('extern "C" mgf_status mgf_batch_step(')]
-    site = "if (hook && hook->hinge_read >= 0 && (int64_t)t < b->ht_rows) {"
-    assert train.count(site) == 1 and train.count("hook->launches += MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK;") == 1
-    assert train.index("k_batch_solve<<<") < train.index("k_batch_rollout_record<<<") < train.index(site) < train.index("d2h(ctx, done.data(), b->d_done.p, K)")
-    block = train[train.index(site):train.index("hook->launches += MGF_BATCH_ROLLOUT_HINGE_READ_LAUNCHES_PER_TICK;")]
-    assert sorted(re.findall(r"k_batch_read_hinges<true, (\w+)><<<", block)) == ["kHingeReadFull", "kHingeReadFullZero", "kHingeReadReading"]
-    assert train.count("k_batch_read_hinges<") == 3 and "else if" in block and "std::min" not in block          # one of the three is launched; no clamp of the row
-    assert "E.out = b->ht_tab.p + (size_t)t * E.n * (hook->hinge_read == kHingeReadReading ? 2u : 4u);" in block   # row t, from the handle's pointer as it is now
-    # what the kernel reads of the handle is looked up again for every pass: inside the loop over the passes, ahead of the loop over the ticks
-    assert train.index("for (uint32_t first = 0, pass = 0;") < train.index("batch_hinge_read_view(b, &hook->E);") < train.index("for (uint32_t t = first; t < NT; ++t)")
-    assert "hook->E.done = b->d_done.p; hook->E.act = b->d_act.p;" in train
-    view = read("mgf_amd", "csrc", READ_FILE)
-    view = view[view.index("static void batch_hinge_read_view("):view.index("// What the launch reads")]
-    for word in ("A->B = b->bodies(0);", "A->w_off = b->d_off.p;", "A->rig = R.dev.p + R.off[1];", "A->acc = reinterpret_cast<const float4*>(b->hinges.acc.p);"):
-        assert word in view, word
-    step = host[host.index('extern "C" mgf_status mgf_batch_step('):host.index('extern "C" mgf_status mgf_batch_read_constraints(')]
-    assert "batch_step_run(b, dt, iters, n_ticks, stats, nullptr)" in step and "hinge" not in step   # mgf_batch_step traces nothing
-
-
-# ---- 6 ------------------------------------------------------------------------------------------------------------------------------------
 def test_the_binding_shapes_its_arrays_and_turns_a_wrong_tensor_down_before_it_calls_c():
     import torch
 

@@ -3,9 +3,9 @@ mgf_batch_slider_trace_rows, mgf_batch_get_slider_trace, mgf_batch_get_slider_tr
 binding and the documents carry the calls, the record of 32 bytes and the constants; what needs no device is refused in the header's
 order; the f32 restatement of the reading (tests/batch_slider_read_cases.py) holds against the float64 one within bounds derived from
 the rounded operations, and its words are tests/batch_slider_cases.py's setup words and its solve's first motor-row rate by bytes; the
-lift's travel stays clear of its limits; the kernel has a lane's own gate ahead of every load of state, no scratch and no spills, and the
-solvers' and the hinge encoders' kernels are as they were; and the rollout's sources launch the read once, behind the hinge trace's,
-under t < rows."""
+lift's travel stays clear of its limits; the kernel's reading holds the slider's own lines, the kernel uses no scratch and spills nothing,
+and the solvers' and the hinge encoders' kernels are as they were.  What the slider encoders share with the hinges' - the kernel's
+skeleton, the host steps, the train's site - is asserted once, in tests/test_world_batch_encoder_family_host.py."""
 import ctypes as C
 import os
 import re
@@ -22,7 +22,7 @@ from tests.util import ROOT, kernel_resources, read
 f32 = np.float32
 CALLS = ("mgf_batch_read_sliders", "mgf_batch_read_sliders_dev", "mgf_batch_set_slider_trace", "mgf_batch_slider_trace_rows", "mgf_batch_get_slider_trace",
          "mgf_batch_get_slider_trace_dev")
-READ_FILE = "host_batch_slider_read.inc"
+READ_FILE = "host_batch_joint_read.inc"
 NAMES = ["d", "rate", "side", "off", "e"]
 
 
@@ -137,50 +137,11 @@ def test_what_needs_no_device_is_refused_in_the_headers_order():
         assert fn(None, None, -1, -1) == INV and "batch is NULL" in err()                     # the handle first
         assert fn(fake, out, -1, -1) == INV and "row0 is negative" in err()                   # row0 ahead of n_rows
         assert fn(fake, out, 0, -1) == INV and "n_rows is negative" in err()
-    src = read("mgf_amd", "csrc", READ_FILE)
-    enqueue = r"batch_slider_read_run\(|batch_slider_read_ready\(|batch_rig_up\(|batch_push\(|hipMemsetAsync|hipMemcpyAsync|<<<|\.ensure\(|h2d\(|hipFree\("
-    # the read calls: the refusals, the context, (device form) the pointer looked up - and only then the first thing is enqueued
-    args = src[src.index("static mgf_status batch_slider_read_args("):src.index('extern "C" mgf_status mgf_batch_read_sliders(')]
-    assert args.index("batch_rig_handle(b)") < args.index("!out && !b->sliders.recs.empty()") and not re.search(enqueue, args)
-    host_form = src[src.index('extern "C" mgf_status mgf_batch_read_sliders('):src.index('extern "C" mgf_status mgf_batch_read_sliders_dev(')]
-    first = min(m.start() for m in re.finditer(enqueue, host_form))
-    assert host_form.index("batch_slider_read_args(b, out)") < host_form.index("ctx_bind(") < host_form.index("if (n == 0) return MGF_OK;") < first
-    assert host_form.count("hipStreamSynchronize") == 1 and host_form.count("hipMemcpyAsync") == 1 and "hipMemcpyHostToDevice" not in host_form   # one download, one wait
-    dev = src[src.index('extern "C" mgf_status mgf_batch_read_sliders_dev('):src.index("static size_t slider_trace_entry(")]
-    first = min(m.start() for m in re.finditer(enqueue, dev))
-    assert dev.index("batch_slider_read_args(b, out_dev)") < dev.index("ctx_bind(") < dev.index('batch_hinge_dev_span(b, out_dev, 32 * n, "out_dev")') < first
-    assert dev.index("if (n == 0) return MGF_OK;") < first and "hipStreamSynchronize" not in dev and "hipMemcpy" not in dev
-    hinge = read("mgf_amd", "csrc", "host_batch_hinge_read.inc")                               # the alignment check is the hinge encoders', used by name
-    span = hinge[hinge.index("static mgf_status batch_hinge_dev_span("):hinge.index('extern "C" mgf_status mgf_batch_read_hinges(')]
-    assert span.index("dev_span(b->ctx, p, bytes, what)") < span.index("& 15u")
-    # pending host-side state goes up first, by the path the solve uses; one launch, counted where the solve counts its own
-    run = src[src.index("static mgf_status batch_slider_read_run("):src.index("static mgf_status batch_slider_read_args(")]
-    assert run.count("<<<") == 1 and run.index("batch_push(") < run.index("batch_slider_read_ready(") < run.index("k_batch_read_sliders<false, kSliderReadReading><<<")
-    assert "b->d_launches += MGF_BATCH_SLIDER_READ_LAUNCHES;" in run and "batch_single_parts(" not in src and src.count("<<<") == 1   # a reading reads no shapes
-    ready = src[src.index("static mgf_status batch_slider_read_ready("):src.index("static mgf_status batch_slider_read_run(")]
-    order = [ready.index(s) for s in ("batch_joint_far_ends<SliderKind>(b)", 'batch_rig_up(b, R, "slider", 3)', "R.acc.ensure(8 * n, b->ctx->stream)", "batch_slider_read_view(b, A)")]
-    assert order == sorted(order)
-    # the table: the refusals in the header's order, ahead of the context and of everything that changes the table
-    st = src[src.index('extern "C" mgf_status mgf_batch_set_slider_trace('):src.index('extern "C" int64_t mgf_batch_slider_trace_rows(')]
-    order = [st.index(s) for s in ("batch_rig_handle(b)", "rows < 0 || rows > (1 << 20)", "format != MGF_SLIDER_TRACE_READING && format != MGF_SLIDER_TRACE_FULL",
-                                   "overflows int64_t", "ctx_bind(", "b->st_tab.ensure(", "hipMemsetAsync(b->st_tab.p, 0, 16 * words, s)", "b->st_rows = rows;")]
-    assert order == sorted(order) and min(m.start() for m in re.finditer(enqueue, st)) > st.index("ctx_bind(")
-    assert "hipFree(b->st_tab.p)" in st and st.index("hipStreamSynchronize(s)") < st.index("hipFree(b->st_tab.p)")   # rows == 0 frees it, behind the stream
-    ta = src[src.index("static mgf_status batch_slider_trace_args("):src.index('extern "C" mgf_status mgf_batch_get_slider_trace(')]
-    order = [ta.index(s) for s in ("batch_rig_handle(b)", "row0 < 0", "n_rows < 0", "n_rows > b->st_rows - row0", "*bytes && !out")]
-    assert order == sorted(order) and not re.search(enqueue, ta)
-    get = src[src.index('extern "C" mgf_status mgf_batch_get_slider_trace('):src.index('extern "C" mgf_status mgf_batch_get_slider_trace_dev(')]
-    assert get.count("hipStreamSynchronize") == 1 and "hipMemcpyDeviceToHost" in get
-    gdev = src[src.index('extern "C" mgf_status mgf_batch_get_slider_trace_dev('):]
-    assert gdev.index("batch_slider_trace_args(") < gdev.index("ctx_bind(") < gdev.index('dev_span(b->ctx, out_dev, bytes, "out_dev")') < gdev.index("hipMemcpyAsync(")
-    assert "hipStreamSynchronize" not in gdev and "hipMemcpyDeviceToDevice" in gdev
-    # mgf_batch_set_sliders turns the trace off, with no device work; the handle's state
+    # (the order of refusals, context, pointer look-up and first enqueue inside every call: tests/test_world_batch_encoder_family_host.py)
+    # mgf_batch_set_sliders turns the trace off, with no device work
     rig = read("mgf_amd", "csrc", "host_batch_slider.inc")
     body = rig[rig.index('extern "C" mgf_status mgf_batch_set_sliders('):rig.index('extern "C" int64_t mgf_batch_slider_count(')]
-    assert body.index("batch_joint_plan(b->sliders, j, n);") < body.index("b->st_rows = 0;") and not re.search(r"<<<|Async|hipMalloc|hipFree|\.ensure\(", body)
-    host = read("mgf_amd", "csrc", "host_batch.inc")
-    for member in ("DBuf<float4> st_tab;", "int64_t st_rows = 0;", "int32_t st_format = 0;"):
-        assert host.count(member) == 1, member
+    assert body.index("batch_joint_plan(b->sliders, j, n);") < body.index("b->slider_trace.rows = 0;") and not re.search(r"<<<|Async|hipMalloc|hipFree|\.ensure\(", body)
 
 
 # ---- 3 ------------------------------------------------------------------------------------------------------------------------------------
@@ -322,30 +283,22 @@ def test_the_lifts_travel_stays_clear_of_its_limits():
 
 
 # ---- 4 ------------------------------------------------------------------------------------------------------------------------------------
-def test_the_kernel_is_a_lane_per_slider_with_its_own_gate_ahead_of_every_load_of_state():
+def test_the_sliders_reading_holds_the_sliders_own_lines_and_its_two_loads_of_v():
+    """The lane's walk, its gate ahead of every load and the stores are the skeleton's (k_batch_joint_read.h), asserted in
+    tests/test_world_batch_encoder_family_host.py; here: what SliderReading forms of the ends and the frames, one f32 operation a line."""
     k = read("mgf_amd", "csrc", "k_batch_slider_read.h")
-    body = k[k.index("void k_batch_read_sliders("):]
-    body = body[:body.index("\n}\n")]
-    gate = "if (GATED && !(A.done[k] == A.tick + 1u && A.act[k] <= A.tick + 1u)) return;"
-    assert gate in body and "template <bool GATED, int FORMAT>" in k
-    for load in ("joint_ends(", "slider_read_v(", "rec[1]", "A.w_off[", "A.acc["):
-        assert body.index(gate) < body.index(load), load
-    assert body.index("if (i >= A.n) return;") < body.index("rec[0]") < body.index(gate)
+    body = k[k.index("struct SliderReading {"):k.index("template <bool GATED, int FORMAT>")]
+    assert "template <bool GATED, int FORMAT>" in k and "void k_batch_read_sliders(" in k
     assert not re.search(r"atomic|__shared__|__syncthreads|s_dyn|A\.plan|A\.slots|A\.items| / |A\.h\b", body)    # no plan, no LDS, no atomic, no barrier, no division, no h
     assert not re.search(r"A\.B\.\w+\[[^\]]*\] =[^=]|srec\[[^\]]*\] =[^=]", k)                                   # nothing written but the output
-    assert "hinge_frame(a, b, has_b, w1, w2, w3, w4, w5, w6)" in body and "joint_ends(A.B, g0, w0, has_b, &a, &b);" in body and "rotate(" not in body
-    assert "slider_rate(va, a.om, vb, b.om, F.A, sA, sB)" in body and "srec[" not in body
+    assert "rotate(" not in body and "slider_rate(own.va, a.om, own.vb, b.om, F.A, sA, sB)" in body and "srec[" not in body
     assert "__device__ __forceinline__ V3 slider_read_v(const Bodies& B, size_t g) { return xyz(B.srec[4 * g]); }" in k        # v: srec word 0's xyz
-    for line in ("const V3 U2 = cross(F.B, F.U1);", "const V3 ca = F.ra + F.C;", "const V3 sA = cross(ca, F.A);", "const V3 sB = cross(F.rb, F.A);", "const float d = dot(F.C, F.A);",
+    for line in ("const uint32_t flags = f2u(w0.w);", "o.va = slider_read_v(B, g0 + f2u(w0.y));", "o.vb = mk3(0.0f, 0.0f, 0.0f);", "if (has_b) o.vb = slider_read_v(B, g0 + f2u(w0.z));",
+                 "const V3 U2 = cross(F.B, F.U1);", "const V3 ca = F.ra + F.C;", "const V3 sA = cross(ca, F.A);", "const V3 sB = cross(F.rb, F.A);", "const float d = dot(F.C, F.A);",
                  "const float off1 = dot(F.C, F.T1), off2 = dot(F.C, F.T2);", "const V3 e = ((cross(F.A, F.B) + cross(F.T1, F.U1)) + cross(F.T2, U2)) * 0.5f;",
                  "if ((flags & kSliderLock) != 0u) side = 2.0f;", "else if ((flags & kSliderLimit) != 0u && d < w3.w) side = -1.0f;",
-                 "else if ((flags & kSliderLimit) != 0u && d > w4.w) side = 1.0f;"):
+                 "else if ((flags & kSliderLimit) != 0u && d > w4.w) side = 1.0f;", "return {make_float4(d, rate, side, off1), make_float4(off2, e.x, e.y, e.z)};"):
         assert line in body, line
-    stores = re.findall(r"\bo\[\d\] = ", body)
-    assert stores == ["o[0] = ", "o[1] = ", "o[2] = ", "o[3] = ", "o[2] = ", "o[3] = "] and "float4* o = A.out" in body
-    assert "o[0] = make_float4(d, rate, side, off1);" in body and "o[1] = make_float4(off2, e.x, e.y, e.z);" in body
-    assert body.count("FORMAT == kSliderReadFull)") == 1 and body.count("FORMAT == kSliderReadFullZero)") == 1
-    assert len(re.findall(r"__global__ __launch_bounds__\(kBatchBlock\)", k)) == len(re.findall(r"__global__", k)) == 1
     code = k[k.index("#pragma once"):]
     assert not re.search(r"k_batch_slider\w*<|k_batch_joint\w*<|void k_batch_slider|void k_batch_joint", code)      # (the solvers' kernels are selected by those substrings)
     assert '#include "k_batch_slider.h"' in k and "struct JointEnd {\n  Quat q;\n  V3 x, om;\n  float im;\n  M3 I;\n};" in read("mgf_amd", "csrc", "k_batch_joint_loop.h")
@@ -377,39 +330,6 @@ def test_the_new_kernel_uses_no_scratch_and_spills_nothing_and_the_other_kernels
 
 
 # ---- 5 ------------------------------------------------------------------------------------------------------------------------------------
-def test_the_rollout_launches_the_read_once_behind_the_hinge_trace_under_t_below_rows():
-    host = read("mgf_amd", "csrc", "host_batch.inc")
-    roll = read("mgf_amd", "csrc", "host_batch_rollout.inc")
-    core = roll[roll.index("static mgf_status batch_rollout_run("):roll.index('extern "C" mgf_status mgf_batch_rollout_dev(')]
-    arm = "if (sliders && b->st_rows > 0) {"
-    assert (core.index("batch_push(") < core.index("batch_joint_hook<SliderKind>(") < core.index(arm) < core.index("batch_slider_read_ready(b, &H.L)")
-            < core.index("batch_step_run(b, dt, iters, n_ticks, stats, &H)"))
-    assert "b->st_format == MGF_SLIDER_TRACE_FULL ? (iters > 0 ? kSliderReadFull : kSliderReadFullZero) : kSliderReadReading" in core   # iters == 0: no solve, zeros
-    assert core.count("batch_slider_read_ready(") == 1 and "slider_read" not in roll[roll.index('extern "C" mgf_status mgf_batch_rollout_dev('):]   # no entry point changes
-    hook = host[host.index("struct BatchRolloutHook {"):host.index("struct JointKind;")]
-    assert hook.index("BatchHingeReadArgs E;") < hook.index("int32_t hinge_read = -1;") < hook.index("BatchSliderReadArgs L;") < hook.index("int32_t slider_read = -1;")
-    train = host[host.index("static mgf_status batch_step_run("):host.index('extern "C" mgf_status mgf_batch_step(')]
-    site = "if (hook && hook->slider_read >= 0 && (int64_t)t < b->st_rows) {"
-    hinge_site = "if (hook && hook->hinge_read >= 0 && (int64_t)t < b->ht_rows) {"
-    assert train.count(site) == 1 and train.count("hook->launches += MGF_BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK;") == 1
-    assert (train.index("k_batch_solve<<<") < train.index("k_batch_rollout_record<<<") < train.index(hinge_site) < train.index(site)
-            < train.index("d2h(ctx, done.data(), b->d_done.p, K)"))
-    block = train[train.index(site):train.index("hook->launches += MGF_BATCH_ROLLOUT_SLIDER_READ_LAUNCHES_PER_TICK;")]
-    assert sorted(re.findall(r"k_batch_read_sliders<true, (\w+)><<<", block)) == ["kSliderReadFull", "kSliderReadFullZero", "kSliderReadReading"]
-    assert train.count("k_batch_read_sliders<") == 3 and "else if" in block and "std::min" not in block         # one of the three is launched; no clamp of the row
-    assert "L.out = b->st_tab.p + (size_t)t * L.n * (hook->slider_read == kSliderReadReading ? 2u : 4u);" in block   # row t, from the handle's pointer as it is now
-    # what the kernel reads of the handle is looked up again for every pass: inside the loop over the passes, ahead of the loop over the ticks
-    assert train.index("for (uint32_t first = 0, pass = 0;") < train.index("batch_slider_read_view(b, &hook->L);") < train.index("for (uint32_t t = first; t < NT; ++t)")
-    assert "hook->L.done = b->d_done.p; hook->L.act = b->d_act.p;" in train
-    view = read("mgf_amd", "csrc", READ_FILE)
-    view = view[view.index("static void batch_slider_read_view("):view.index("// What the launch reads")]
-    for word in ("A->B = b->bodies(0);", "A->w_off = b->d_off.p;", "A->rig = R.dev.p + R.off[1];", "A->acc = reinterpret_cast<const float4*>(b->sliders.acc.p);"):
-        assert word in view, word
-    step = host[host.index('extern "C" mgf_status mgf_batch_step('):host.index('extern "C" mgf_status mgf_batch_read_constraints(')]
-    assert "batch_step_run(b, dt, iters, n_ticks, stats, nullptr)" in step and "slider" not in step   # mgf_batch_step traces nothing
-
-
-# ---- 6 ------------------------------------------------------------------------------------------------------------------------------------
 def test_the_binding_shapes_its_arrays_and_turns_a_wrong_tensor_down_before_it_calls_c():
     import torch
 

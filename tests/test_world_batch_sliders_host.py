@@ -108,10 +108,10 @@ def test_header_library_binding_and_documents_carry_the_calls_the_record_and_the
                 "pub unsafe fn solve_sliders_dev("):
         assert sig in flat, sig
     kernels = read("mgf_amd", "csrc", "kernels.h")
-    assert kernels.index('#include "k_batch_hinge_read.h"') < kernels.index('#include "k_batch_slider.h"')
+    assert kernels.index('#include "k_batch_hinge.h"') < kernels.index('#include "k_batch_slider.h"') < kernels.index('#include "k_batch_joint_read.h"')
     assert "k_batch_slider_solve<GATED> (k_batch_slider.h)" in kernels
     hip = read("mgf_amd", "csrc", "mgf_hip.hip")
-    assert hip.index('#include "host_batch_hinge.inc"') < hip.index('#include "host_batch_hinge_read.inc"') < hip.index('#include "%s"' % RIG_FILE)
+    assert hip.index('#include "host_batch_hinge.inc"') < hip.index('#include "%s"' % RIG_FILE) < hip.index('#include "host_batch_joint_read.inc"')
     design = read("DESIGN.md")
     assert design.index("### Hinge encoders") < design.index("### Sliders between bodies") < design.index("### Rollout touch traces")
     sub = design[design.index("### Sliders between bodies"):design.index("### Rollout touch traces")]
