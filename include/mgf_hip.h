@@ -289,7 +289,20 @@ MGF_API mgf_status mgf_world_read_colliders(mgf_world* w, mgf_moving_component* 
  * parts in order), terrain faces (ascending index), obstacles (in the order added).  inter is bit-identical to that single test.
  * kind: MGF_HIT_NONE (-1, the other fields zero), MGF_HIT_BODY (index = the caller's body index), MGF_HIT_TERRAIN (index = face),
  * MGF_HIT_OBSTACLE (index = obstacle); part = the component within a body of several components or within an obstacle (else 0).
- * A particle with d = 0 hits nothing (the single tests divide by |d|^2 there: every sphere would answer at t = 0). */
+ * A particle with d = 0 hits nothing (the single tests divide by |d|^2 there: every sphere would answer at t = 0).
+ * More generally a particle is cast only if the largest |component| of d lies in [MGF_RAY_DMIN, MGF_RAY_DMAX]; outside that band - and
+ * for a d with a NaN - it hits nothing.  Outside it the single tests stop being local: |d|^2 underflows or the discriminants overflow,
+ * and a sphere or a capsule nowhere near the line answers at t = 0, inf or NaN (EXPERIMENTS.md, "the direction band of a ray").
+ * A hit whose t is not finite is not a candidate (the sweeps' rule, below): whatever target offers it, it is passed over.
+ * The single tests are not local for an origin far away either, and their answers stand as the definition's: ray_sphere decides by the sign
+ * of b^2 - a c, which cancels, so a sphere of radius r whose centre is m from the origin answers when the line passes its centre within
+ * sqrt(r^2 + 1e-6 m^2) - from 1e5 away a body 50 off the line can be the hit.  The walk is laid over the grid's box grown by that tube,
+ * cells beside the grid included, and looks that far around the line at each; where the tube is more than two cells a particle whose path
+ * meets the grown box is put to every body.  The bound is the spheres' and the capsules' end caps'; the cylinder test of
+ * a capsule divides the same noise by sin^2 of the angle between particle and axis, so a particle that runs nearly along a far capsule's
+ * axis may be answered from further off than the walk looks: a stated limit (the batch's bounding-sphere reject allows 1e-2 m). */
+#define MGF_RAY_DMIN 1e-20f
+#define MGF_RAY_DMAX 1e12f
 #define MGF_HIT_NONE (-1)
 #define MGF_HIT_BODY 0
 #define MGF_HIT_TERRAIN 1
@@ -698,7 +711,8 @@ MGF_API mgf_status mgf_batch_read_constraints(mgf_batch* b, int64_t world, mgf_c
  * obstacles at their poses (the obstacle table, above), and has been through the same calls.
  *   Ray cast: the closest hit of Intersects<shape> (collision.rs:169-373; compound.rs:150 for a component), the smallest t, ties to the
  *   target first in the order bodies (ascending index), terrain faces (ascending index), obstacles (Intersects<Compound>,
- *   compound.rs:309-332; ascending place in the world's list); a particle with d = 0 hits nothing.
+ *   compound.rs:309-332; ascending place in the world's list); a particle with d = 0 or with max|d_k| outside [MGF_RAY_DMIN,
+ *   MGF_RAY_DMAX] hits nothing, and a hit whose t is not finite is not a candidate (mgf_world_raycast_many: one predicate serves both).
  *   Sweep: the earliest contact of Contacts<Moving<Sphere | Capsule>> of a body's sphere or capsule (collision.rs:1089-1356; :1143
  *   through commute_contacts!) and of Contacts<Moving<_>> for Poly of each face (collision.rs:610-1000, up to two contacts for a
  *   capsule) and of Compound::contacts of the cast for each obstacle (compound.rs:334-352), the least (t, kind, index, part, order

@@ -13,9 +13,10 @@ static mgf_status query_grid(mgf_world* w, QueryGrid* G) {
   hipStream_t s = ctx->stream;
   const uint32_t n = w->n_owned;
   MGF_TRY(w->q_misc.ensure(16, s));
-  // [0..2] lo, [3..5] hi (ordered ints), [6] large-body count, [7] traversal error
-  int32_t init[8] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, (int32_t)0x80000000, (int32_t)0x80000000, (int32_t)0x80000000, 0, 0};
-  MGF_TRY(h2d(ctx, w->q_misc.p, reinterpret_cast<const uint32_t*>(init), 8));
+  // [0..2] lo, [3..5] hi (ordered ints), [6] large-body count, [7] traversal error, [8] the smallest radius in the grid (ordered int)
+  int32_t init[9] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, (int32_t)0x80000000, (int32_t)0x80000000, (int32_t)0x80000000, 0, 0, 0x7FFFFFFF};
+  MGF_TRY(h2d(ctx, w->q_misc.p, reinterpret_cast<const uint32_t*>(init), 9));
+  G->rmin = 0.0f;
   G->dims[0] = G->dims[1] = G->dims[2] = 0;
   G->n_large = w->q_misc.p + 6;
   G->start = G->items = nullptr;
@@ -31,8 +32,8 @@ static mgf_status query_grid(mgf_world* w, QueryGrid* G) {
   k_query_boxes<<<nblk(n), kBlock, 0, s>>>(w->bodies(), n, h, margin, w->q_bc.p, w->q_br.p, reinterpret_cast<int*>(w->q_misc.p), w->q_large.p,
                                            w->q_misc.p + 6);
   LAUNCH_CHECK();
-  int32_t got[8];
-  MGF_TRY(d2h(ctx, reinterpret_cast<uint32_t*>(got), w->q_misc.p, 8));
+  int32_t got[9];
+  MGF_TRY(d2h(ctx, reinterpret_cast<uint32_t*>(got), w->q_misc.p, 9));
   w->q_last_large = (uint32_t)got[6];
   const uint32_t n_grid = n - (uint32_t)got[6];
   if (n_grid == 0) { G->h = h; G->inv_h = 1.0f / h; G->margin = margin; return MGF_OK; }
@@ -53,6 +54,8 @@ static mgf_status query_grid(mgf_world* w, QueryGrid* G) {
   }
   for (int k = 0; k < 3; ++k) { G->lo[k] = lo[k] - margin; G->dims[k] = dims[k] + 1; }
   G->h = h; G->inv_h = 1.0f / h; G->margin = margin;
+  G->rmin = ord_f(got[8]);
+  if (!(G->rmin >= 0.0f) || !std::isfinite(G->rmin)) G->rmin = 0.0f;
   const uint32_t cells = (uint32_t)G->dims[0] * (uint32_t)G->dims[1] * (uint32_t)G->dims[2];
   w->q_last_cells = cells;
   MGF_TRY(w->q_cnt.ensure((size_t)cells + 1, s)); MGF_TRY(w->q_start.ensure((size_t)cells + 1, s));
@@ -124,11 +127,11 @@ static mgf_status world_query_run(mgf_world* w, DBuf<Q>& d_q, const Q* queries, 
     MGF_TRY(w->q_misc.ensure(16, s));
     MGF_HIP_TRY(hipMemsetAsync(w->q_misc.p, 0, 64, s));
     G.dims[0] = G.dims[1] = G.dims[2] = 0; G.n_large = w->q_misc.p + 6; G.large = nullptr; G.start = G.items = nullptr;
-    G.h = G.inv_h = 1.0f; G.margin = 0.0f; G.lo[0] = G.lo[1] = G.lo[2] = 0.0f;
+    G.h = G.inv_h = 1.0f; G.margin = 0.0f; G.rmin = 0.0f; G.lo[0] = G.lo[1] = G.lo[2] = 0.0f;
   }
   MGF_TRY(w->q_tm.mark(1, s));
   QueryTargets T;
-  T.B = w->bodies(); T.ext = w->ext_ptr(); T.qb_c = w->q_bc.p; T.qb_r = w->q_br.p;
+  T.B = w->bodies(); T.ext = w->ext_ptr(); T.qb_c = w->q_bc.p; T.qb_r = w->q_br.p; T.n = w->n_owned;
   T.err = w->q_misc.p + 7;
   T.M.n_nodes = 0;
   if ((kinds_mask & MGF_QUERY_TERRAIN) && w->terrain) { MGF_TRY(w->terrain->sync()); T.M = w->terrain->dev(T.err); }

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_camera_tile(BatchCameraAr
   if (live) {
     d = rotate(rot, rotate(rc, cam_dir(c, ix, iy)));
     mask = A.mask;
-    if (d.x == 0.0f && d.y == 0.0f && d.z == 0.0f) mask = 0;  // (no direction: no hit, by definition - k_query_ray)
+    if (!q_ray_castable(d)) mask = 0;  // (no direction, or one outside the band: no hit, by definition - k_query.h)
   }
   const float dd = dot(d, d);
   // the tile's cone, from the corners of its live rectangle (uniform)

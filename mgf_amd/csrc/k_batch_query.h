@@ -260,7 +260,7 @@ __device__ __forceinline__ void bq_ray_front(const BatchQueryArgs& A, Bodies bod
     const BatchRay r = load(qi, W.g0);
     p = r.p; d = r.d; dt = r.dt; ign = r.ign;
     mask = A.mask;
-    if (d.x == 0.0f && d.y == 0.0f && d.z == 0.0f) mask = 0;  // (no direction: no hit, by definition - k_query_ray)
+    if (!q_ray_castable(d)) mask = 0;  // (no direction, or one outside the band: no hit, by definition - k_query.h)
   }
   typename Bodies::Best best;
   if (mask & MGF_QUERY_BODIES) best = bodies.ray_walk(W, p, d, dt, ign);
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_query_ray_obstacles(Batch
   const uint32_t obst = tdesc[2 * (size_t)w + 1].w, ob0 = batch_obst_first(obst), ob1 = ob0 + batch_obst_count(obst);
   if (ob0 == ob1) return;
   const ParticleIn q = parts[i];
-  if (q.d[0] == 0.0f && q.d[1] == 0.0f && q.d[2] == 0.0f) return;  // (no direction: no hit, by definition - k_query_ray)
+  if (!q_ray_castable(ld3(q.d))) return;  // (no direction, or one outside the band: no hit, by definition - k_query.h)
   int32_t* o = out + 7 * (size_t)i;
   QueryBest best = q_ray_load(o);  // k_batch_query_ray's answer
 #pragma unroll 1

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kBatchBlock) void k_batch_scan_rows(BatchScanRowsAr
     QueryBest best = q_ray_load(A.hits + 7 * (size_t)i);
     if (A.obstacles) {
       const uint32_t obst = A.tdesc[2 * (size_t)k + 1].w, ob0 = batch_obst_first(obst), ob1 = ob0 + batch_obst_count(obst);
-      if (!(q.d[0] == 0.0f && q.d[1] == 0.0f && q.d[2] == 0.0f)) {  // (no direction: no hit, by definition - k_query_ray)
+      if (q_ray_castable(ld3(q.d))) {  // (no direction, or one outside the band: no hit, by definition - k_query.h)
 #pragma unroll 1
         for (uint32_t e = ob0; e < ob1; ++e) q_ray_obstacle(batch_obstacle_of(A.O, e), e - ob0, q, nullptr, best);
       }

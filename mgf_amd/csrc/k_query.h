@@ -33,6 +33,7 @@ struct QueryGrid {
   float h, inv_h;
   int dims[3];
   float margin;            // world-space pad of every box the grid files or looks up (covers the rounding of the walk)
+  float rmin;              // the smallest radius of a component of a body in the grid (q_ray_tube)
   const uint32_t* start;   // cells + 1 offsets into items (exclusive scan of the counts)
   const uint32_t* items;   // slots
   const uint32_t* large;   // slots of the bodies wider than a cell, tested by every query
@@ -73,12 +74,26 @@ __device__ __forceinline__ Box q_body_box(const Bodies& B, uint32_t i) {
   return tb;
 }
 
-// bounds[0..2] = ordered-int min of the padded low corners, [3..5] max of the high corners (bodies that go to the grid): reduced
-// across the wave first, one atomic per wave and word
+// the smallest radius among slot i's components
+__device__ __forceinline__ float q_body_rmin(const Bodies& B, uint32_t i) {
+  const uint32_t pc = B.pcount ? B.pcount[i] : 0u;
+  if (!pc) return B.col0[i].w;
+  float r = kInf;
+  for (uint32_t k = 0; k < pc; ++k) {
+    float4 a, b;
+    world_part(B, i, k, pc, a, b);
+    r = fminf(r, a.w);
+  }
+  return r;
+}
+
+// bounds[0..2] = ordered-int min of the padded low corners, [3..5] max of the high corners, [8] the min of q_body_rmin (bodies that go to
+// the grid): reduced across the wave first, one atomic per wave and word
 __global__ __launch_bounds__(kBlock) void k_query_boxes(Bodies B, uint32_t n, float h, float margin, float4* qb_c, float4* qb_r, int* bounds,
                                                         uint32_t* large, uint32_t* n_large) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   int lo[3] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, hi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+  int rm = 0x7FFFFFFF;
   if (i < n) {
     const Box b = q_body_box(B, i);
     const bool wide = !(2.0f * (b.r.x + margin) <= h && 2.0f * (b.r.y + margin) <= h && 2.0f * (b.r.z + margin) <= h);  // (NaN: wide)
@@ -89,8 +104,11 @@ __global__ __launch_bounds__(kBlock) void k_query_boxes(Bodies B, uint32_t n, fl
     } else {
 #pragma unroll
       for (int k = 0; k < 3; ++k) { lo[k] = f_ord(at(b.c, k) - at(b.r, k) - margin); hi[k] = f_ord(at(b.c, k) + at(b.r, k) + margin); }
+      rm = f_ord(fmaxf(q_body_rmin(B, i), 0.0f));  // (NaN: 0)
     }
   }
+  for (int off = 32; off > 0; off >>= 1) rm = min(rm, __shfl_xor(rm, off));
+  if ((threadIdx.x & 63) == 0) atomicMin(bounds + 8, rm);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     int a = lo[k], c = hi[k];
@@ -134,6 +152,7 @@ struct QueryBest {
   float t = 0.0f;
   // (t, kind, index, part) ascending: the rule of the definition, whatever order the targets are visited in
   __device__ __forceinline__ void offer(V3 ip, float it, int k, uint32_t idx, uint32_t pt) {
+    if (!(fabsf(it) < kInf)) return;  // a hit whose t is not finite is not a candidate (a NaN taken first could never be replaced)
     const bool better = !have || it < t || (it == t && (k < kind || (k == kind && (idx < index || (idx == index && pt < part)))));
     if (better) { have = true; kind = k; index = idx; part = pt; p = ip; t = it; }
   }
@@ -203,6 +222,13 @@ __device__ __forceinline__ bool q_slab(V3 p, V3 d, V3 c, V3 r, float pad, float 
   return t0 <= t1;
 }
 __device__ __forceinline__ float q_maxabs(V3 v) { return fmaxf(fabsf(v.x), fmaxf(fabsf(v.y), fabsf(v.z))); }
+// Is a particle of direction d cast at all?  The rule of include/mgf_hip.h, written once for every front that casts rays (k_query_ray,
+// bq_ray_front and with it the sensors and the part queries, the cameras, the obstacle passes of the batch and of a rollout's trace): the
+// largest |component| of d within [MGF_RAY_DMIN, MGF_RAY_DMAX].  Outside the band - d = 0 and a d with a NaN included - the particle hits
+// nothing: the single tests divide by |d|^2 and square |m||d|, and where those underflow or overflow a target nowhere near the line answers.
+__device__ __forceinline__ bool q_ray_castable(V3 d) {
+  return q_maxabs(d) >= MGF_RAY_DMIN && fabsf(d.x) <= MGF_RAY_DMAX && fabsf(d.y) <= MGF_RAY_DMAX && fabsf(d.z) <= MGF_RAY_DMAX;
+}
 
 // The DDA's next step from cell c along p + d t (Amanatides-Woo): the axis whose cell face the path crosses first and the parameter tn
 // there, computed afresh from the face - nothing accumulates.  -1: no axis steps.
@@ -227,6 +253,7 @@ struct QueryTargets {
   TerrainDev M;          // n_nodes 0: no terrain
   const CompoundDev* obs;
   uint32_t n_obs;
+  uint32_t n;            // owned bodies (slots 0 .. n - 1; qb_r[s].w != 0: s is on the large list)
   uint32_t* err;         // [0]: a traversal stack overflowed
 };
 
@@ -340,10 +367,19 @@ __device__ __forceinline__ void q_ray_terrain(const Mesh& M, V3 p, V3 d, float d
       });
 }
 
-// the grid cell (x, y, z) - with `fat`, its 3x3x3 neighbourhood - for one particle
-__device__ __forceinline__ void q_ray_cells(const QueryGrid& G, const QueryTargets& T, const int c[3], bool fat, V3 p, V3 d, float dt, int32_t ign,
+// How far from a sphere's or a capsule's surface the line of a particle may pass and the single test still answer, for a component of
+// radius >= rmin whose points are at most m from the particle's origin.  ray_sphere (and ray_capsule's end caps) decide by the sign of
+// b^2 - a c, b = m . d, a = |d|^2, c = |m|^2 - r^2, which is a (r^2 - e^2) for a line passing the centre at e.  In f32 each of b^2 and
+// a c carries at most 8 roundings of 2^-24 relative to a |m|^2, so the sign is wrong only where |e^2 - r^2| <= 1e-6 |m|^2: e stays below
+// sqrt(r^2 + 1e-6 m^2), largest beyond the surface for the smallest r.  (Measured over the query corpus: 2.6e-7 |m|^2 at the most.)
+__device__ __forceinline__ float q_ray_tube(float rmin, float m) {
+  const float k = 1e-6f * m * m;
+  return k / (__builtin_sqrtf(rmin * rmin + k) + rmin + 1e-30f);
+}
+
+// the grid cell (x, y, z) and its neighbourhood of r cells every way, for one particle
+__device__ __forceinline__ void q_ray_cells(const QueryGrid& G, const QueryTargets& T, const int c[3], int r, V3 p, V3 d, float dt, int32_t ign,
                                             QueryBest& best) {
-  const int r = fat ? 1 : 0;
   for (int z = max(c[2] - r, 0); z <= min(c[2] + r, G.dims[2] - 1); ++z)
     for (int y = max(c[1] - r, 0); y <= min(c[1] + r, G.dims[1] - 1); ++y)
       for (int x = max(c[0] - r, 0); x <= min(c[0] + r, G.dims[0] - 1); ++x) {
@@ -361,7 +397,7 @@ __global__ __launch_bounds__(kBlock) void k_query_ray(QueryGrid G, QueryTargets 
   const float dt = q.dt;
   const int32_t ign = ignore ? ignore[i] : -1;
   QueryBest best;
-  if (d.x == 0.0f && d.y == 0.0f && d.z == 0.0f) mask = 0;  // (no direction: the reference's tests divide by |d|^2 = 0 - no hit, by definition)
+  if (!q_ray_castable(d)) mask = 0;  // (no direction, or one outside the band: no hit, by definition)
   if (mask & MGF_QUERY_BODIES) {
     const uint32_t nl = *G.n_large;
     for (uint32_t k = 0; k < nl; ++k) q_ray_body(T, G.large[k], p, d, dt, ign, best);
@@ -370,29 +406,59 @@ __global__ __launch_bounds__(kBlock) void k_query_ray(QueryGrid G, QueryTargets 
     for (uint32_t o = 0; o < T.n_obs; ++o) q_ray_obstacle(T.obs[o], o, q, T.err, best);
   if ((mask & MGF_QUERY_TERRAIN) && T.M.n_nodes) q_ray_terrain(T.M, p, d, dt, T.err, best);
   if ((mask & MGF_QUERY_BODIES) && G.dims[0] > 0) {
-    // clip to the grid's box, then walk its cells in the order the particle enters them
-    float t0 = 0.0f, t1 = dt;
+    // The single tests are not local for an origin far away (q_ray_tube): a body the line passes by up to the tube answers.  So the walk
+    // is laid over the grid's box GROWN by the tube - the tube at the distance of the box's farthest corner, which bounds every body's -
+    // and the margin, and at each cell, inside the grid or beside it, looks as many cells around as the tube at the distance the
+    // particle has covered when it leaves the cell (the reach of the cells looked at added: two cells around are 3 sqrt(3) h).  Where
+    // the tube is more than two cells, or nothing bounds the distance, a particle whose path meets the grown box is put to every body
+    // of the grid.  A particle whose tube stays inside a quarter of the margin walks the grid's own cells, one at a time.  (This takes in
+    // what a rule on the particle's own rounding, 4e-7 of |p| and of the stretch against a quarter of the margin, used to add: wherever
+    // that fired the tube is at least a cell.)
     float ghi[3];
+    V3 fc;
 #pragma unroll
     for (int k = 0; k < 3; ++k) ghi[k] = G.lo[k] + (float)G.dims[k] * G.h;
-    if (q_clip(p, d, G.lo, ghi, nullptr, t0, t1)) {
+    fc.x = fmaxf(fabsf(p.x - G.lo[0]), fabsf(p.x - ghi[0])); fc.y = fmaxf(fabsf(p.y - G.lo[1]), fabsf(p.y - ghi[1])); fc.z = fmaxf(fabsf(p.z - G.lo[2]), fabsf(p.z - ghi[2]));
+    const float dlen = mag(d);
+    const float far_tube = q_ray_tube(G.rmin, mag(fc));
+    const bool wide = !(far_tube <= 0.25f * G.margin);  // (NaN: wide)
+    const bool all = wide && !(far_tube <= 2.0f * G.h);  // more than two cells (NaN, inf: all)
+    const float pad = !wide ? 0.0f : (far_tube < kInf ? far_tube + G.margin : kInf);
+    const int out_cells = wide ? 3 : 0;  // cells beside the grid the walk may stand in: a walked pad is below three
+    const auto every_body = [&]() {
+      for (uint32_t b = 0; b < T.n; ++b)
+        if (T.qb_r[b].w == 0.0f) q_ray_body(T, b, p, d, dt, ign, best);
+    };
+    float t0 = 0.0f, t1 = dt;
+    float plo[3], phi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { plo[k] = G.lo[k] - pad; phi[k] = ghi[k] + pad; }
+    const bool meets = !(pad < kInf) || q_clip(p, d, plo, phi, nullptr, t0, t1);
+    if (meets && all) {
+      every_body();
+    } else if (meets) {
       const V3 e = p + d * t0;
       int c[3], step[3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) { c[k] = q_cell(at(e, k), k, G); step[k] = at(d, k) > 0.0f ? 1 : (at(d, k) < 0.0f ? -1 : 0); }
+      for (int k = 0; k < 3; ++k) {
+        const float f = floorf((at(e, k) - G.lo[k]) * G.inv_h);
+        c[k] = (int)fminf(fmaxf(f, (float)-out_cells), (float)(G.dims[k] - 1 + out_cells));  // (NaN: the low end)
+        step[k] = at(d, k) > 0.0f ? 1 : (at(d, k) < 0.0f ? -1 : 0);
+      }
       const float dmax = q_maxabs(d);
       const float tpad = dmax > 0.0f ? G.h / dmax : kInf;  // one cell along the fastest axis: covers the rounding of the crossings
-      // a particle whose own rounding (its origin far from the grid, a long stretch) may exceed the pad looks at the neighbours too
-      const bool fat = 4e-7f * (q_maxabs(p) + dmax * t1) > 0.25f * G.margin;
-      const int max_steps = G.dims[0] + G.dims[1] + G.dims[2] + 3;
+      const int max_steps = G.dims[0] + G.dims[1] + G.dims[2] + 6 * out_cells + 3;
       for (int s = 0; s < max_steps; ++s) {
-        q_ray_cells(G, T, c, fat, p, d, dt, ign, best);
         float tn;
         const int ax = q_next_crossing(G, c, step, p, d, tn);
+        const float tube = q_ray_tube(G.rmin, dlen * fminf(tn, t1) + 6.0f * G.h);
+        const int r = !(tube <= 0.25f * G.margin) ? (int)fminf(ceilf(tube * G.inv_h), 3.0f) : 0;  // (NaN: every body)
+        if (!(r <= 2)) { every_body(); break; }
+        q_ray_cells(G, T, c, r, p, d, dt, ign, best);  // (the cells around c that the grid has: none for a c far beside it)
         if (ax < 0 || !(tn <= t1 + tpad)) break;
         if (best.have && tn > best.t + tpad) break;
         c[ax] += step[ax];
-        if (c[ax] < 0 || c[ax] >= G.dims[ax]) break;
+        if (c[ax] < -out_cells || c[ax] >= G.dims[ax] + out_cells) break;
       }
     }
   }

@@ -111,6 +111,8 @@ def lib():
         L.mgfo_intersection.restype = C.c_int
         L.mgfo_intersection_aabb.argtypes = [P(Vec3), P(Vec3), C.c_float, P(Aabb), P(Vec3), P(C.c_float)]
         L.mgfo_intersection_aabb.restype = C.c_int
+        L.mgfo_intersection_batch.argtypes = [C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3
+        L.mgfo_intersection_batch.restype = None
         L.mgfo_bvh_raytrace.argtypes = [C.c_void_p, P(Vec3), P(Vec3), C.c_float, P(C.c_uint64), P(Vec3), P(C.c_float), C.c_int64]
         L.mgfo_bvh_raytrace.restype = C.c_int64
         L.mgfo_compound_new.argtypes = [P(Component), C.c_int64]
@@ -295,6 +297,26 @@ def contacts_batch(a, vel_a, b, vel_b, has_vel, slots=2):
     lib().mgfo_contacts_batch(n, a.ctypes.data, va.ctypes.data, b.ctypes.data, vb.ctypes.data, hv.ctypes.data, out.ctypes.data, slots,
                               counts.ctypes.data)
     return out, counts
+
+
+def intersection_batch(p, d, dt, shapes, every=False):
+    """intersection() for n particles held in arrays: p, d (n, 3), dt (n,) or a scalar, shapes SHAPE_DTYPE.  every=False: particle i
+    against shapes[i] -> (hit (n,) int32, point (n, 3), t (n,)); every=True: each particle against every shape -> the same with a
+    second axis of len(shapes).  point and t are zero where hit is 0."""
+    p, d = (np.ascontiguousarray(v, np.float32).reshape(-1, 3) for v in (p, d))
+    n = len(p)
+    dt = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float32), (n,)))
+    shapes = np.ascontiguousarray(shapes, SHAPE_DTYPE).reshape(-1)
+    m = len(shapes) if every else 0
+    assert every or len(shapes) == n
+    dims = (n, m) if every else (n,)
+    ip, t, hit = np.zeros(dims + (3,), np.float32), np.zeros(dims, np.float32), np.zeros(dims, np.int32)
+    if n and (m or not every):
+        lib().mgfo_intersection_batch(n, p.ctypes.data, d.ctypes.data, dt.ctypes.data, shapes.ctypes.data, m, ip.ctypes.data, t.ctypes.data,
+                                      hit.ctypes.data)
+    if np.any(hit < 0):
+        raise ValueError("unsupported shape")
+    return hit, ip, t
 
 
 def local_contacts_pair_batch(a, delta_a, b, delta_b, slots=1):

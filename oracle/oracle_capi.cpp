@@ -164,6 +164,21 @@ int mgfo_intersection(const o_vec3* p, const o_vec3* d, float dt, const o_shape*
   *ip = O(i.p); *t = i.t;
   return 1;
 }
+// Batched form of mgfo_intersection for corpora of many thousand particles (tests/query_corpus.py): particle i against shape i, or - with
+// n_shapes > 0 - every particle against each of the n_shapes shapes (row i of the outputs holds particle i's n_shapes answers).
+// hit[k]: mgfo_intersection's return value; ip, t are written only where it is 1.
+void mgfo_intersection_batch(int64_t n, const o_vec3* p, const o_vec3* d, const float* dt, const o_shape* sh, int64_t n_shapes, o_vec3* ip, float* t,
+                             int32_t* hit) {
+  if (n_shapes <= 0) {
+    for (int64_t i = 0; i < n; ++i) hit[i] = mgfo_intersection(p + i, d + i, dt[i], sh + i, ip + i, t + i);
+    return;
+  }
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t j = 0; j < n_shapes; ++j) {
+      const int64_t k = i * n_shapes + j;
+      hit[k] = mgfo_intersection(p + i, d + i, dt[i], sh + j, ip + k, t + k);
+    }
+}
 int mgfo_intersection_aabb(const o_vec3* p, const o_vec3* d, float dt, const o_aabb* a, o_vec3* ip, float* t) {
   Intersection i;
   if (!ray_aabb(Ray{V(*p), V(*d)}, AABB{V(a->c), V(a->r)}, &i, dt)) return 0;

@@ -14,6 +14,26 @@ INF = float("inf")
 f32 = np.float32
 
 
+def _direction_band():
+    """(MGF_RAY_DMIN, MGF_RAY_DMAX) as include/mgf_hip.h states them"""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mgf_hip.h")) as f:
+        text = f.read()
+    return tuple(np.float32(re.search(r"#define\s+%s\s+([0-9.eE+-]+)f" % k, text).group(1)) for k in ("MGF_RAY_DMIN", "MGF_RAY_DMAX"))
+
+
+RAY_DMIN, RAY_DMAX = _direction_band()
+
+
+def ray_castable(d, band=None):
+    """the rule of include/mgf_hip.h: a particle is cast only if the largest |component| of its direction lies in [DMIN, DMAX].
+    band: another (DMIN, DMAX) - (0, inf) is the rule as it stood before the band: only d = 0 (or a NaN) hits nothing"""
+    lo, hi = (RAY_DMIN, RAY_DMAX) if band is None else band
+    m = np.abs(np.asarray(d, np.float32)).max()
+    return bool(m > 0 and lo <= m <= hi)
+
+
 @pytest.fixture(scope="module")
 def ctx():
     c = mgf_amd.Context(0)
@@ -57,16 +77,23 @@ class Targets:
         q = p + t[:, None] * d
         return np.linalg.norm(c - q, axis=1) <= r + 1e-6 * (1.0 + np.abs(p).max())
 
-    def raycast(self, p, d, dt, ignore=-1, kinds=7):
+    def raycast(self, p, d, dt, ignore=-1, kinds=7, filtered=True, band=None):
+        """the definition's answer (t, kind, index, part, point) or None.  filtered: only the targets whose bounding sphere the particle
+        comes near are tried (_near) - right wherever the single tests are local; filtered=False puts every target of the world through
+        the oracle's test (raycast_all), which is the definition itself"""
+        if not filtered:
+            return self.raycast_all(np.asarray(p, np.float32)[None], np.asarray(d, np.float32)[None], dt, ignore, kinds, band)[0]
         best = None  # (t, kind, index, part, point)
-        if not np.any(np.asarray(d) != 0):
-            return None  # a particle without a direction hits nothing (include/mgf_hip.h)
+        if not ray_castable(d, band):
+            return None  # a particle whose direction is outside the band hits nothing, d = 0 included (include/mgf_hip.h)
 
         def offer(res, kind, index, part):
             nonlocal best
             if res is None:
                 return
             (ip, t) = res
+            if not np.isfinite(t):
+                return  # a hit whose t is not finite is not a candidate (include/mgf_hip.h)
             key = (t, kind, index, part)
             if best is None or key < best[:4]:
                 best = (t, kind, index, part, ip)
@@ -85,6 +112,58 @@ class Targets:
             for o, c in enumerate(self.obstacles):
                 offer(c.intersection(p, d, dt), 2, o, None)
         return best
+
+    def _all_shapes(self):
+        """every component and every face as the oracle's shapes, components first"""
+        if getattr(self, "_shapes", None) is None:
+            sh = np.zeros(len(self.comps) + len(self.faces), O.SHAPE_DTYPE)
+            nc = len(self.comps)
+            cap = self.comps["tag"] == 1
+            sh["kind"][:nc] = np.where(cap, O.CAPSULE, O.SPHERE)
+            sh["v"][:nc, :3] = self.comps["p"]
+            sh["v"][:nc, 3:6][cap] = self.comps["d"][cap]
+            sh["v"][:nc, 6][cap] = self.comps["r"][cap]
+            sh["v"][:nc, 3][~cap] = self.comps["r"][~cap]
+            sh["kind"][nc:] = O.TRIANGLE
+            sh["v"][nc:, :9] = self.faces.reshape(-1, 9)
+            self._shapes = sh
+        return self._shapes
+
+    def raycast_all(self, p, d, dt, ignore=-1, kinds=7, band=None):
+        """the unfiltered definition for n particles at once: every component, face and obstacle through the oracle's single test, then the
+        least (t, kind, index, part).  Returns a list of (t, kind, index, part, point) or None"""
+        p, d = np.ascontiguousarray(p, np.float32).reshape(-1, 3), np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        n, nc = len(p), len(self.comps)
+        dts = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float32), (n,)))
+        ign = np.broadcast_to(np.asarray(ignore, np.int64), (n,))
+        hit, ip, t = O.intersection_batch(p, d, dts, self._all_shapes(), every=True)
+        ok = (hit == 1) & np.isfinite(t)
+        if not kinds & 1:
+            ok[:, :nc] = False
+        if not kinds & 2:
+            ok[:, nc:] = False
+        if nc:
+            ok[:, :nc] &= self.owner[None, :] != ign[:, None]
+        # the columns stand in the definition's order (kind, index, part): the first least t of a row is its answer
+        tt = np.where(ok, t, np.inf)
+        col = np.argmin(tt, axis=1) if tt.shape[1] else np.zeros(n, np.int64)
+        out = []
+        for i in range(n):
+            if not ray_castable(d[i], band):
+                out.append(None)
+                continue
+            best = None
+            if tt.shape[1] and ok[i, col[i]]:
+                c = int(col[i])
+                kind, index, part = (0, int(self.owner[c]), int(self.part[c])) if c < nc else (1, c - nc, 0)
+                best = (float(t[i, c]), kind, index, part, tuple(float(x) for x in ip[i, c]))
+            if kinds & 4:
+                for o, c in enumerate(self.obstacles):
+                    res = c.intersection(p[i], d[i], float(dts[i]))
+                    if res is not None and np.isfinite(res[1]) and (best is None or (res[1], 2, o) < best[:3]):
+                        best = (res[1], 2, o, None, res[0])
+            out.append(best)
+        return out
 
     def boxes(self):
         """BoundedBy<AABB> per body (bounds.rs:170-190), parts combined in order (box_combine, :113-130), in f32"""

@@ -71,7 +71,9 @@ class Sweeper:
         t = np.where(t > 1.0 + 1e-6, np.inf, t)
         return np.where(np.isfinite(R) | inside, np.maximum(t - 1e-6, 0.0), 0.0)
 
-    def answer(self, cast, ignore=-1, kinds=7):
+    def answer(self, cast, ignore=-1, kinds=7, filtered=True):
+        """filtered=False: every body's component and every face is put through the oracle's test, whatever its bounding sphere says -
+        the definition itself; the filter is right wherever the single tests are local"""
         T = self.T
         tag, p, d, r, v = int(cast["tag"]), cast["p"].astype(np.float64), cast["d"].astype(np.float64), float(cast["r"]), cast["delta"].astype(np.float64)
         sh = _shape(tag, cast["p"], cast["d"], r)
@@ -95,13 +97,13 @@ class Sweeper:
 
         cands = []  # (t_lo, kind, index)
         if kinds & 1 and len(T.comps):
-            if np.isfinite(rc) and np.all(np.isfinite(cc)):
+            if filtered and np.isfinite(rc) and np.all(np.isfinite(cc)):
                 mid = cc + 0.5 * v
                 idx = np.array(self.tree.query_ball_point(mid, 0.5 * np.linalg.norm(v) + rc + self.brmax), np.int64)
             else:
                 idx = np.arange(len(T.comps))
             if len(idx):
-                tl = self._t_lo(T.bc[idx], T.br[idx] + rc, cc, v)
+                tl = self._t_lo(T.bc[idx], T.br[idx] + rc, cc, v) if filtered else np.zeros(len(idx))
                 cands += [(t, 0, int(e)) for t, e in zip(tl, idx) if np.isfinite(t) and T.owner[e] != ignore]
         if kinds & 2 and len(T.faces):
             reach = 0.0 if tag == 0 else max(1.0, float(np.linalg.norm(d)))  # a capsule's face test reaches further (include/mgf_hip.h)
@@ -109,6 +111,8 @@ class Sweeper:
             d32 = cast["delta"].astype(f32)
             if tag == 1 and (d32[0] * d32[0] + d32[1] * d32[1]) + d32[2] * d32[2] == 0:
                 tl = np.zeros(len(T.faces))  # a capsule that does not move may meet any face at t = 0 (include/mgf_hip.h)
+            if not filtered:
+                tl = np.zeros(len(T.faces))
             cands += [(t, 1, int(f)) for f, t in enumerate(tl) if np.isfinite(t)]
         if kinds & 4:
             for o, comp in enumerate(T.obstacles):
@@ -121,7 +125,7 @@ class Sweeper:
                 offer(res, 2, o, part_of)
         cands.sort()
         for t_lo, kind, i in cands:
-            if best is not None and t_lo > best[0] + 1e-6:
+            if filtered and best is not None and t_lo > best[0] + 1e-6:
                 break
             if kind == 0:
                 offer(O.contacts(self._body_shape(i), None, sh, vec), 0, int(T.owner[i]), lambda c, i=i: int(T.part[i]))
@@ -129,6 +133,66 @@ class Sweeper:
                 tri = T.faces[i]
                 offer(O.contacts(O.shape(O.TRIANGLE, tri[0], tri[1], tri[2]), None, sh, vec), 1, i, lambda c: 0)
         return best
+
+
+def answer_all(T, casts, ignore=-1, kinds=3, obstacles=()):
+    """The unfiltered definition for n casts at once: every component and every face of T through the oracle's continuous test
+    (contacts_batch: the target at rest, the cast moving) and, with kinds & 4, every obstacle of `obstacles` [(comps, disp, rot)] through
+    Compound.contacts (the component a contact came from found as Sweeper finds it), then the least (t, kind, index, part, order) among
+    the contacts whose t is finite.  A list of what Sweeper.answer returns."""
+    if kinds & 4 and len(obstacles):
+        S = Sweeper(T, obstacles)
+        rest = answer_all(T, casts, ignore, kinds & 3) if kinds & 3 else [None] * len(casts)
+        out = []
+        for i, best in enumerate(rest):
+            sh = _shape(casts["tag"][i], casts["p"][i], casts["d"][i], casts["r"][i])
+            for o, comp in enumerate(T.obstacles):
+                for j, c in enumerate(comp.contacts(sh, casts["delta"][i])):
+                    if not np.isfinite(c["t"]):
+                        continue
+                    ks = [k for k, one in enumerate(S.singles[o]) if any(_same(c, x) for x in one.contacts(sh, casts["delta"][i]))]
+                    assert ks, ("an obstacle's contact matches none of its components", o, c)
+                    key = (float(c["t"]) + 0.0, 2, o, ks[0], j)
+                    if best is None or key < (best[0] + 0.0,) + tuple(best[1:5]):
+                        best = key + (c,)
+            out.append(best)
+        return out
+    kinds &= 3
+    if not kinds:
+        return [None] * len(casts)
+    sh = T._all_shapes()
+    n, m, nc = len(casts), len(sh), len(T.comps)
+    B = np.zeros(n, O.SHAPE_DTYPE)
+    cap = casts["tag"] == 1
+    B["kind"] = np.where(cap, O.CAPSULE, O.SPHERE)
+    B["v"][:, :3] = casts["p"]
+    B["v"][:, 3:6][cap] = casts["d"][cap]
+    B["v"][:, 6][cap] = casts["r"][cap]
+    B["v"][:, 3][~cap] = casts["r"][~cap]
+    if m == 0:
+        return [None] * n
+    con, cnt = O.contacts_batch(np.tile(sh, n), np.zeros((n * m, 3), f32), np.repeat(B, m), np.repeat(casts["delta"], m, axis=0), np.full(n * m, 2, np.uint8), slots=2)
+    con, cnt = con.reshape(n, m, 2), cnt.reshape(n, m)
+    ok = (np.arange(2)[None, None, :] < cnt[:, :, None]) & np.isfinite(con["t"])
+    ign = np.broadcast_to(np.asarray(ignore, np.int64), (n,))
+    if nc:
+        ok[:, :nc] &= (T.owner[None, :] != ign[:, None])[:, :, None]
+    if not kinds & 1:
+        ok[:, :nc] = False
+    if not kinds & 2:
+        ok[:, nc:] = False
+    tt = np.where(ok, con["t"], np.inf).reshape(n, 2 * m)   # columns in the definition's order: (kind, index, part), order emitted within
+    col = np.argmin(tt, axis=1)
+    out = []
+    for i in range(n):
+        c, j = divmod(int(col[i]), 2)
+        if not ok[i, c, j]:
+            out.append(None)
+            continue
+        kind, index, part = (0, int(T.owner[c]), int(T.part[c])) if c < nc else (1, c - nc, 0)
+        k = con[i, c, j]
+        out.append((float(k["t"]), kind, index, part, j, dict(a=tuple(k["a"]), b=tuple(k["b"]), n=tuple(k["n"]), t=k["t"])))
+    return out
 
 
 def _same(a, b):

@@ -305,7 +305,7 @@ def test_the_kernels_are_the_two_the_header_names_and_the_ray_front_is_not_resta
     assert "__syncthreads" not in rows and "s_dyn" not in rows and "return;" not in rows
     assert "const bool on = in && (!MGF_SCAN_GATE || (A.done[k] == t + 1u && A.act[k] <= t + 1u));" in rows and "#define MGF_SCAN_GATE 1" in code
     assert rows.index("if (on) {") < rows.index("q_ray_load(") < rows.index("q_ray_obstacle(") < rows.index("const size_t at = (size_t)t * A.n_sensor + i;")
-    assert "if (!(q.d[0] == 0.0f && q.d[1] == 0.0f && q.d[2] == 0.0f))" in rows
+    assert "if (q_ray_castable(ld3(q.d)))" in rows      # the one predicate of k_query.h: no direction, or one outside the band, hits nothing
     stores = re.findall(r"(static_cast<float\*>\(A\.out\)\[at\] = |q_ray_store\(static_cast<int32_t\*>\(A\.out\) \+ 7 \* at, best\))", rows)
     assert len(stores) == 2 and rows.count("A.out") == 2                                               # the only global stores
     assert not re.findall(r"\bA\.\w+(?:\[[^\]]*\])? = ", rows)                                         # nothing of the arguments is written

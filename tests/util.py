@@ -33,10 +33,10 @@ Z = ("0", "0", "0", "0")
 RESOURCES = {  # DESIGN.md, "Device-pointer queries", compiler output: VGPR, SGPR | scratch, static LDS, spills
     "k_batch_query_gather": ("10", "14") + Z, "k_batch_query_plan_count<7u>": ("9", "20") + Z, "k_batch_query_plan_count<13u>": ("14", "26") + Z,
     "k_batch_query_plan_cut": ("4", "14") + Z, "k_batch_query_plan_fill": ("10", "20") + Z,
-    "k_batch_query_ray": ("45", "65") + Z, "k_batch_query_ray_dev<1>": ("45", "65") + Z, "k_batch_query_ray_dev<2>": ("45", "65") + Z,
+    "k_batch_query_ray": ("45", "66") + Z, "k_batch_query_ray_dev<1>": ("45", "66") + Z, "k_batch_query_ray_dev<2>": ("45", "66") + Z,
     "k_batch_query_sweep_bodies": ("108", "90") + Z, "k_batch_query_sweep_bodies_dev<1>": ("108", "90") + Z,
     "k_batch_query_sweep_bodies_dev<2>": ("108", "90") + Z, "k_batch_query_sweep_faces": ("133", "69", "0", "9216", "0", "0"),
-    "k_batch_query_ray_obstacles": ("68", "63") + Z, "k_batch_query_sweep_obstacles": ("115", "87") + Z,
+    "k_batch_query_ray_obstacles": ("68", "64") + Z, "k_batch_query_sweep_obstacles": ("115", "87") + Z,
 }
 
 
